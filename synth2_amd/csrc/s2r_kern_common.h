@@ -976,8 +976,8 @@ __device__ __forceinline__ void combine_groups(const S2rRenderParams &p, const S
 // The mix of the workgroups' partial rows in the fixed order of DESIGN.md 4.3:
 //   runs of 16 consecutive workgroups sequentially -> the run sums of a mix group sequentially
 //   -> the mix groups sequentially -> root (+0.0) + total.
-// One workgroup (256 threads) handles one block of 16 frames: thread (slot, f) adds whole runs (16 independent loads in
-// flight each), the run sums meet in LDS (s_run: [total runs][16 frames]), 16 threads finish.  Runs never straddle a mix
+// One workgroup (256 threads; in fused_tail a render workgroup of 64 to 256) handles one block of 16 frames: thread
+// (slot, f) adds whole runs (16 independent loads in flight each; slot steps by the workgroup's blockDim.x / 16 slots), the run sums meet in LDS (s_run: [total runs][16 frames]), 16 threads finish.  Runs never straddle a mix
 // group.  `ov`: the rows come from workgroups of other compute units that may still be running (sc1 loads, ov_load).
 // `sys`: the output goes to memory the host or another device reads behind a flag (system-scope stores).
 // ---------------------------------------------------------------------------------------
@@ -988,8 +988,9 @@ __device__ __forceinline__ void mix_block(const S2rMixParams &m, uint32_t block,
     const uint32_t f = block * 16u + f_local;
     const uint32_t runs_per_group = (m.blocks_per_group + kMixRun - 1) / kMixRun;
     const uint32_t total_runs = runs_per_group * m.n_groups;
+    const uint32_t n_slots = blockDim.x >> 4;                    // (fused_tail: a render workgroup of 64, 128 or 256 threads)
     if (f < m.frames) {
-        for (uint32_t run = slot; run < total_runs; run += 16u) {
+        for (uint32_t run = slot; run < total_runs; run += n_slots) {
             const uint32_t g = run / runs_per_group, rg = run % runs_per_group;
             const uint32_t gb0 = g * m.blocks_per_group;
             uint32_t gb1 = gb0 + m.blocks_per_group; if (gb1 > m.n_blocks) gb1 = m.n_blocks;
