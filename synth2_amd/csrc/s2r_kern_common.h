@@ -1318,8 +1318,8 @@ __device__ __forceinline__ void pool_loop(const S2rRenderArgs &a, const S2rPool 
 // common case runs this straight-line code: 4 quads, closed-form part on 4-vectors, then the
 // recurrence, all in one basic block.
 //   Preconditions (checked by the caller for the whole wave): no envelope threshold inside the
-//   chunk; period > 0 and 0 <= phase < 1 (then fmodf(period*phase, period) is `off` itself unless
-//   off == period, where it is +0); no oscillator FM.
+//   chunk; a normal period (>= 2^-126) and 0 <= phase < 1 (then fmodf(period*phase, period) is `off` itself: only on a
+//   denormal period's grid can RN(period*phase) reach the period, where fmodf gives +0); no oscillator FM.
 //   SRC: 0 = every voice flat (constant coefficient), 1 = coefficient tables (`tab`: this lane's entry for the chunk's
 //        first frame, S2rTabRef), 2 = compute in-lane.
 // ---------------------------------------------------------------------------------------

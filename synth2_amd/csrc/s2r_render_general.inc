@@ -556,10 +556,13 @@ __device__ __forceinline__ void general_fill(const S2rRenderArgs &a, const FillC
                         }
                         if (most > 1u) { if (clear_for(most)) run = most; else if (most > 4u && clear_for(4u)) run = 4u; }
                         // the tables serve offsets below 2^24; a lane whose phase or period is out of the ordinary (a pitch
-                        // of 0, inf or NaN) sends the wave through the frame loop
+                        // of 0, inf or NaN; a denormal period, on whose grid RN(period * phase) can reach the period itself — under
+                        // FM the per-frame periods are not below 2^-125 while sr >= pitch * 2^-115) sends the wave through the
+                        // frame loop
                         const float period0 = lp.sr / r.pitch;
                         const bool lane_bad = live && !(o_chunk + run * kChunk <= (1u << 24) && o_chunk <= (1u << 24)
-                                                        && period0 > 0.0f && period0 < __builtin_inff() && r.phase >= 0.0f && r.phase < 1.0f);
+                                                        && period0 >= 0x1p-126f && period0 < __builtin_inff() && r.phase >= 0.0f && r.phase < 1.0f
+                                                        && (lp.amt_osc == 0.0f || lp.sr >= r.pitch * 0x1p-115f));
                         if (__ballot(lane_bad) != 0ull) run = 0u;
                     }
                     if (run) {
@@ -648,7 +651,9 @@ __device__ __forceinline__ void general_fill(const S2rRenderArgs &a, const FillC
                         if (n > 1u && clear_for(n)) run = n;
                     }
                     if (tab_chunk && __ballot(o_chunk + run * kChunk > (1u << 24)) != 0ull) run = 1u;
-                    if (__ballot(!(((tab_chunk && fmv) || (k.period > 0.0f && k.period < __builtin_inff())) && r.phase >= 0.0f && r.phase < 1.0f)) != 0ull) run = 0u;
+                    // (a NORMAL period — on a denormal one's grid RN(period * phase) can reach the period itself, which chunk_fast does not
+                    // fold back to +0; the tables' per-frame periods are not below 2^-125 while sr >= pitch * 2^-115, the power of two being at most 2^10; underflow only)
+                    if (__ballot(!(((tab_chunk && fmv) ? (!live || lp.sr >= r.pitch * 0x1p-115f) : (k.period >= 0x1p-126f && k.period < __builtin_inff())) && r.phase >= 0.0f && r.phase < 1.0f)) != 0ull) run = 0u;
                     if (run) {
                         run = (uint32_t)__builtin_amdgcn_readfirstlane((int)run);
                         FlatCache fcx; fcx.xc = xc; fcx.k = k;

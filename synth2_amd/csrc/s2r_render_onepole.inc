@@ -212,8 +212,10 @@ __device__ __forceinline__ void render_fill(const S2rRenderArgs &a, const FillCt
     // (phase' = fmodf(phase + 1/period, 1) stays in [0,1) for a positive period)
     // Under oscillator FM the period constants are per-frame values — except while every lane's mod envelope
     // is flat, when they are the ones cached at stage entry (fc.k): that case is checked per run.
+    // (a NORMAL period: RN(period * phase) stays below a normal period, but on a denormal one's grid of 2^-149 it can round up
+    // to the period itself, where fmodf(off, period) is +0 and not `off` — such a wave takes the general path)
     const bool fast_ok = __ballot(!(r.phase >= 0.0f && r.phase < 1.0f)) == 0ull &&
-        (FM || __ballot(!(k_const.period > 0.0f && k_const.period < __builtin_inff())) == 0ull);
+        (FM || __ballot(!(k_const.period >= 0x1p-126f && k_const.period < __builtin_inff())) == 0ull);
     const size_t pv_base = (size_t)vi * ctl.frames;
     float *bp = ctl.partials + (size_t)blockIdx.x * p.frames_stride;
     uint32_t buf = 0;
@@ -246,7 +248,7 @@ __device__ __forceinline__ void render_fill(const S2rRenderArgs &a, const FillCt
     bool w_flat = false, w_aflat = false, w_aligned = false, w_small = false;
     auto reclassify_stages = [&]() {                             // what a stage change can move
         w_flat = !p.no_flat_shortcut && __ballot(live && em.s0 != 0.0f) == 0ull &&
-                 (!FM || __ballot(!(fc.k.period > 0.0f && fc.k.period < __builtin_inff())) == 0ull);
+                 (!FM || __ballot(!(fc.k.period >= 0x1p-126f && fc.k.period < __builtin_inff())) == 0ull);
         w_aflat = __ballot(live && ea.s0 != 0.0f) == 0ull;
     };
     auto reclassify = [&]() {
@@ -341,7 +343,7 @@ __device__ __forceinline__ void render_fill(const S2rRenderArgs &a, const FillCt
         }
         wave_events = __ballot(ev_idx >= 0) != 0ull;
         w_flat = !p.no_flat_shortcut && __ballot(live && em.s0 != 0.0f) == 0ull &&
-                 (!FM || __ballot(!(fc.k.period > 0.0f && fc.k.period < __builtin_inff())) == 0ull);
+                 (!FM || __ballot(!(fc.k.period >= 0x1p-126f && fc.k.period < __builtin_inff())) == 0ull);
         w_aflat = __ballot(live && ea.s0 != 0.0f) == 0ull;
     };
 
@@ -405,7 +407,10 @@ __device__ __forceinline__ void render_fill(const S2rRenderArgs &a, const FillCt
                 // its first boundary itself: no second look at them here)
                 if (TEV) apply_events_at(sc0 + c16);
                 // (entered when the wave's next event is at most two chunks ahead)
+                // (under FM its chunks take per-frame periods from the tables' FM plane, flat envelope or not: the pitch bound of
+                // the run logic below; a voice restarted inside the loop gets a MIDI pitch, which meets it at any sample rate)
                 const bool dense = TEV && wave_events && fast_ok && have_tab && w_small && w_aligned && p.noise_level == 0.0f &&
+                                   (!FM || __ballot(live && !(p.sr >= r.pitch * 0x1p-115f)) == 0ull) &&
                                    (dense_stay || wave_min_u32((ev_frame - (sc0 + c16)) >> 4) <= 2u);
                 dbg_t_top += S2R_DBG_NOW() - dbg_tt0;
                 if (dense) {
@@ -585,6 +590,10 @@ __device__ __forceinline__ void render_fill(const S2rRenderArgs &a, const FillCt
                         flat = w_flat;
                         tab_ok = !flat && have_tab && offs_small;
                         if (FM && !flat && !tab_ok) run = 0;
+                        // (the tables' per-frame periods are sr / (2^(mod * amount) * pitch) with the power at most 2^10: not
+                        // below 2^-125 while sr >= pitch * 2^-115.  This covers underflow only; a product 2^x * pitch that
+                        // overflows makes the period +0 and the reference's sample NaN, which nothing here reproduces)
+                        if (FM && !flat && __ballot(live && !(p.sr >= r.pitch * 0x1p-115f)) != 0ull) run = 0;
                     }
                     if (run) {
                         ++dbg_runs; dbg_runchunks += run;

@@ -118,6 +118,25 @@ def assert_bits_equal(a, b, what=""):
             what, bad[0].size, a.size, idx, a[idx], b[idx]))
 
 
+def assert_bits_equal_finite(got, want, what=""):
+    """The strict form: `want` (the oracle) is finite everywhere — an input for which it is not is a badly chosen input, to be
+    replaced, not compared — and `got` has its bit patterns, with no NaN allowance: +0 and -0 differ, denormals count."""
+    got = np.ascontiguousarray(got, dtype=np.float32)
+    want = np.ascontiguousarray(want, dtype=np.float32)
+    assert got.shape == want.shape, (what, got.shape, want.shape)
+    nonfinite = np.nonzero(~np.isfinite(want))
+    if nonfinite[0].size:
+        idx = tuple(int(x[0]) for x in nonfinite)
+        raise AssertionError("%s: the oracle is not finite at %d of %d values (first at %s: %r): choose another input" % (
+            what, nonfinite[0].size, want.size, idx, want[idx]))
+    bad = np.nonzero(got.view(np.uint32) != want.view(np.uint32))
+    if bad[0].size:
+        idx = tuple(int(x[0]) for x in bad)
+        raise AssertionError("%s: %d of %d values differ bitwise; first at %s: got %s (0x%08x), the oracle has %s (0x%08x)" % (
+            what, bad[0].size, got.size, idx, float(got[idx]).hex(), int(got.view(np.uint32)[idx]),
+            float(want[idx]).hex(), int(want.view(np.uint32)[idx])))
+
+
 def ulp_diff(a, b):
     """max distance in units of float32 ULP (monotone integer mapping)"""
     def key(x):
