@@ -82,10 +82,21 @@ class Synth {
     // a batch of events, each at frame 0 or at its 16-frame boundary inside the next buffer (main.rs:138-143)
     void note_events(const s2r_note_event *events, size_t n) { check(s2r_note_events(h_, events, n)); }
 
+    // true stereo (build-defined; s2r.h: s2r_fill_panned): a pan and a key spread per bank program, given to a voice at its
+    // note_on; `buffer` takes 2 * len floats, interleaved L, R
+    void set_program_pan(uint32_t program, float pan, float key_spread = 0.0f) { check(s2r_set_program_pan(h_, program, pan, key_spread)); }
+    void get_program_pan(uint32_t program, float *pan, float *key_spread) const { check(s2r_get_program_pan(h_, program, pan, key_spread)); }
+    void voice_pans(float *pans) { check(s2r_get_voice_pans(h_, pans)); }                     // shard_voices entries, local order
+    void set_voice_pans(const float *pans) { check(s2r_set_voice_pans(h_, pans)); }
+    void sample_panned(float *buffer, size_t len, SampleRateKhz sample_rate) { check(s2r_fill_panned(h_, buffer, len, sample_rate.v)); }
+    // host only: the pan a note_on gives its voice, and a pan's constant-power gains
+    static float voice_pan(float pan, float key_spread, Note note) { return s2r_voice_pan(pan, key_spread, note.v); }
+    static void pan_gains(float p, float *gl, float *gr) { s2r_pan_gains(p, gl, gr); }
+
     s2r_synth *handle() { return h_; }
 
   private:
-    void check(int rc) {
+    void check(int rc) const {
         if (rc != S2R_OK) throw Error(rc, s2r_last_error(h_));
     }
     s2r_synth *h_ = nullptr;

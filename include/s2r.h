@@ -31,7 +31,8 @@ extern "C" {
 
 /* Changes when a struct layout or an existing signature changes.  Entry points added since 4.0 without touching either:
  * s2r_set_low_latency, s2r_low_latency_active, s2r_build_id, s2r_set_resident, s2r_resident_active, s2r_quiesce,
- * s2r_exchange_create, s2r_exchange_attach, s2r_voice_pool_set_threads, s2r_voice_pool_resolve. */
+ * s2r_exchange_create, s2r_exchange_attach, s2r_voice_pool_set_threads, s2r_voice_pool_resolve, s2r_set_program_pan,
+ * s2r_get_program_pan, s2r_get_voice_pans, s2r_set_voice_pans, s2r_fill_panned, s2r_voice_pan, s2r_pan_gains. */
 #define S2R_ABI_VERSION 4
 
 typedef enum {
@@ -221,6 +222,33 @@ uint32_t s2r_fills_in_flight(const s2r_synth *s);
  * done on device: interleaved L,R with L == R. */
 int s2r_fill_stereo(s2r_synth *s, float *interleaved_lr_out, size_t frames, uint32_t sample_rate_hz);
 
+/* BUILD-DEFINED true stereo (the reference has the copy above and nothing else; DESIGN.md 4.12 gives the op sequence).
+ * Every program of the bank has a `pan` and a `key_spread`, both in [-1, 1], both 0 by default, held beside the bank (not in
+ * s2r_patch).  A note_on gives its voice the pan p = s2r_voice_pan(pan, key_spread, note) of the program current at that
+ * note_on — exactly as it gives it its patch — and the voice keeps p until it is restarted; a voice never started has p = 0;
+ * changing a program's pan affects later note_ons only.  s2r_set_patch_bank keeps the pans of the programs that survive and
+ * gives new ones 0 / 0.
+ *   s2r_set_program_pan: S2R_ERR_INVALID if program >= bank size, S2R_ERR_PATCH_RANGE for a value outside [-1, 1] or NaN.
+ *   s2r_get_voice_pans / s2r_set_voice_pans: every shard voice's p, shard_voices entries in local order — the companion of
+ *   s2r_export_state / s2r_import_state for checkpoint / resume; the setter is range-checked like the program's (nothing is
+ *   changed when one entry is refused).  Single-device handles (a device-list handle: S2R_ERR_INVALID).
+ *   s2r_fill_panned: s2r_fill with every voice placed in the stereo field.  Synchronous; overwrites 2 * frames floats,
+ *   interleaved L, R: channel c of frame i is the mix tree of DESIGN.md 4.3 over x_c[v][i] = row[v][i] * g_c[v] (one rounded
+ *   multiply, denormals kept), row = what s2r_render_voices returns and (gL, gR) = s2r_pan_gains(p of voice v).  Like
+ *   s2r_fill a handle that renders a shard returns that shard's root-added mix.  Voice state advances exactly as under
+ *   s2r_fill; events with a frame inside the fill take effect there (the fill is rendered segment after segment).  The
+ *   voices' rows pass through a device buffer allocated ONCE, by the first panned fill, and never per call after that:
+ *   shard_voices * min(round_up(max_frames, 16), max(16, round_down(256 MiB / (4 * shard_voices), 16))) floats — at most
+ *   256 MiB, which is 65 536 voices x 1024 frames unsliced (16 frames per voice beyond four million voices); a longer fill is
+ *   rendered in slices of that many frames.  It stops
+ *   resident kernels like every other entry point that touches the device.  Single-device handles without an exchange
+ *   attached (S2R_ERR_INVALID otherwise; the handle stays usable). */
+int s2r_set_program_pan(s2r_synth *s, uint32_t program, float pan, float key_spread);
+int s2r_get_program_pan(const s2r_synth *s, uint32_t program, float *pan, float *key_spread);
+int s2r_get_voice_pans(s2r_synth *s, float *pans);
+int s2r_set_voice_pans(s2r_synth *s, const float *pans);
+int s2r_fill_panned(s2r_synth *s, float *interleaved_lr_out, size_t frames, uint32_t sample_rate_hz);
+
 /* BUILD-DEFINED 4x oversampling (the reference has none; BASELINE config [4]): renders 4 * frames at
  * 4 * sample_rate_hz through the same path and decimates the mix by a 63-tap windowed sinc whose history
  * carries over from call to call (DESIGN.md 4.9 gives taps and arithmetic).  4 * frames must not exceed
@@ -370,6 +398,12 @@ size_t s2r_stream_frame_json(const float *samples, size_t n, char *out, size_t c
 
 /* The .synth2 parser on its own; err_buf (may be NULL) receives a message on failure. */
 int s2r_parse_patch_text(const char *text, size_t len, s2r_patch *out, char *err_buf, size_t err_cap);
+
+/* The pan a note_on gives its voice, and the constant-power gains of a pan.  binary32, every operation
+ * rounded on its own:  k = (float)((int)note - 64) * 0.015625f;  p = pan + key_spread * k, clamped to [-1, 1];
+ * gL = sqrtf((1 - p) * 0.5f), gR = sqrtf((1 + p) * 0.5f): the centre gives sqrt(0.5) on both sides, p = -1 gives (1, 0). */
+float s2r_voice_pan(float pan, float key_spread, uint8_t note);
+void s2r_pan_gains(float p, float *gl, float *gr);
 
 /* The voice-allocation / release policy of Synth (synth.rs:61-120) for a pool of any size,
  * O(1) per event, without rendering.  Offsets advance by s2r_voice_pool_advance. */

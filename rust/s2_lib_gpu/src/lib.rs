@@ -137,6 +137,14 @@ pub mod ffi {
         pub fn s2r_fills_in_flight(s: *const S2rSynth) -> u32;
         pub fn s2r_fill_stereo(s: *mut S2rSynth, interleaved_lr_out: *mut f32, frames: usize, sample_rate_hz: u32) -> c_int;
         pub fn s2r_fill_oversampled(s: *mut S2rSynth, mono_out: *mut f32, frames: usize, sample_rate_hz: u32) -> c_int;
+        pub fn s2r_set_program_pan(s: *mut S2rSynth, program: u32, pan: f32, key_spread: f32) -> c_int;
+        pub fn s2r_get_program_pan(s: *const S2rSynth, program: u32, pan: *mut f32, key_spread: *mut f32) -> c_int;
+        pub fn s2r_get_voice_pans(s: *mut S2rSynth, pans: *mut f32) -> c_int;
+        pub fn s2r_set_voice_pans(s: *mut S2rSynth, pans: *const f32) -> c_int;
+        pub fn s2r_fill_panned(s: *mut S2rSynth, interleaved_lr_out: *mut f32, frames: usize, sample_rate_hz: u32) -> c_int;
+        pub fn s2r_voice_pan(pan: f32, key_spread: f32, note: u8) -> f32;
+        pub fn s2r_pan_gains(p: f32, gl: *mut f32, gr: *mut f32);
+        pub fn s2r_shard_voices(s: *const S2rSynth) -> u32;
         pub fn s2r_fill_device(s: *mut S2rSynth, dev_out: *mut f32, frames: usize, sample_rate_hz: u32,
                                hip_stream: *mut c_void) -> c_int;
         pub fn s2r_device_count(s: *const S2rSynth) -> u32;
@@ -152,6 +160,17 @@ pub mod ffi {
         pub fn s2r_last_error(s: *const S2rSynth) -> *const c_char;
         pub fn s2r_status_string(status: c_int) -> *const c_char;
     }
+}
+
+/// Host-only: the pan a note_on gives its voice, and a pan's constant-power gains (gL, gR) — DESIGN.md 4.12.
+pub fn voice_pan(pan: f32, key_spread: f32, note: u8) -> f32 {
+    unsafe { ffi::s2r_voice_pan(pan, key_spread, note) }
+}
+
+pub fn pan_gains(p: f32) -> (f32, f32) {
+    let (mut gl, mut gr) = (0.0f32, 0.0f32);
+    unsafe { ffi::s2r_pan_gains(p, &mut gl, &mut gr) };
+    (gl, gr)
 }
 
 pub mod synth {
@@ -315,6 +334,38 @@ pub mod synth {
         pub fn sample_oversampled(&mut self, buffer: &mut [f32], sample_rate: SampleRateKhz) {
             self.check(unsafe {
                 ffi::s2r_fill_oversampled(self.handle, buffer.as_mut_ptr(), buffer.len(), sample_rate.0)
+            });
+        }
+
+        /// Build-defined true stereo (`s2r_fill_panned`, include/s2r.h): pan and key spread, both in [-1, 1], of a bank
+        /// program — what a note_on under that program gives its voice.
+        pub fn set_program_pan(&mut self, program: u32, pan: f32, key_spread: f32) {
+            self.check(unsafe { ffi::s2r_set_program_pan(self.handle, program, pan, key_spread) });
+        }
+
+        pub fn get_program_pan(&self, program: u32) -> (f32, f32) {
+            let (mut pan, mut spread) = (0.0f32, 0.0f32);
+            self.check(unsafe { ffi::s2r_get_program_pan(self.handle, program, &mut pan, &mut spread) });
+            (pan, spread)
+        }
+
+        /// Every voice's pan, pool order on a handle that renders its whole pool: the checkpoint companion of the state.
+        pub fn voice_pans(&mut self) -> Vec<f32> {
+            let mut pans = vec![0.0f32; unsafe { ffi::s2r_shard_voices(self.handle) } as usize];
+            self.check(unsafe { ffi::s2r_get_voice_pans(self.handle, pans.as_mut_ptr()) });
+            pans
+        }
+
+        pub fn set_voice_pans(&mut self, pans: &[f32]) {
+            assert!(pans.len() == unsafe { ffi::s2r_shard_voices(self.handle) } as usize);
+            self.check(unsafe { ffi::s2r_set_voice_pans(self.handle, pans.as_ptr()) });
+        }
+
+        /// The panned two-channel mixdown: `interleaved` holds L, R pairs; its length is twice the frame count.
+        pub fn sample_panned(&mut self, interleaved: &mut [f32], sample_rate: SampleRateKhz) {
+            assert!(interleaved.len() % 2 == 0);
+            self.check(unsafe {
+                ffi::s2r_fill_panned(self.handle, interleaved.as_mut_ptr(), interleaved.len() / 2, sample_rate.0)
             });
         }
 

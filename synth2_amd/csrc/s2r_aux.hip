@@ -122,6 +122,90 @@ __global__ void s2r_decimate4_history_kernel(float *x, uint32_t n_out) {
     if (i < kDecimTaps - 1) x[i] = v;
 }
 
+// ---------------------------------------------------------------------------------------
+// The panned mixdown (s2r_fill_panned).  x_c[v][i] = row[v][i] * g_c[v] for the two channels c, each through
+// the tree of DESIGN.md 4.3 — every addition of oracle/s2_oracle.c:rows_blocks_sum, in its order:
+//   s2r_pan_mix_kernel: workgroup (tile, b) takes the block_voices voices of workgroup b of the render grid and a tile of
+//   32 * W frames.  A thread adds ONE run of 16 voices for W consecutive frames, sequentially in index order from the first
+//   voice's value — sixteen independent loads in flight (16 bytes each where the rows allow it: W = 4), every element read once
+//   and multiplied by both of its voice's gains — the run sums meet in LDS and are added in run order; voices past the pool add
+//   +0.0 (a row of +0.0 times a gain of 0).  The L and R partial rows go to memory.
+//   s2r_pan_combine_kernel: one thread per output float adds the workgroups' rows: runs of 16 sequentially, the run sums within
+//   a mix group, the groups onto a root of +0.0.
+// No atomics, no order that depends on timing.  -ffp-contract=off: a product and the sum that takes it stay two roundings.
+// ---------------------------------------------------------------------------------------
+constexpr uint32_t kPanLanes = 32;                               // threads along frames; 256 / 32 = 8 runs of voices side by side
+
+template <int W>
+__global__ void __launch_bounds__(256) s2r_pan_mix_kernel(const S2rPanMix m) {
+    extern __shared__ float s_grp[];                             // [block_voices / 16][2][32 * W]
+    constexpr uint32_t TF = kPanLanes * (uint32_t)W;
+    const uint32_t lane = threadIdx.x & (kPanLanes - 1u), slot = threadIdx.x / kPanLanes, n_slots = blockDim.x / kPanLanes;
+    const uint32_t b = blockIdx.y, fl = lane * (uint32_t)W, f0 = blockIdx.x * TF + fl;
+    const uint32_t n_grp = m.block_voices / 16u;
+    for (uint32_t g = slot; g < n_grp; g += n_slots) {
+        const uint32_t v0 = b * m.block_voices + 16u * g;
+        float x[16][W], gl[16], gr[16];
+#pragma unroll
+        for (uint32_t k = 0; k < 16u; ++k) {
+            const uint32_t v = v0 + k;
+            gl[k] = m.gain_l[v]; gr[k] = m.gain_r[v];            // (padded with 0 up to the grid's last voice)
+            const float *src = m.rows + (size_t)v * m.stride + f0;
+            if (W == 4) {
+                const f4 q = (v < m.n_voices && f0 < m.frames) ? *reinterpret_cast<const f4 *>(src) : (f4){0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+                for (int j = 0; j < W; ++j) x[k][j] = q[j];
+            } else {
+#pragma unroll
+                for (int j = 0; j < W; ++j) x[k][j] = (v < m.n_voices && f0 + (uint32_t)j < m.frames) ? src[j] : 0.0f;
+            }
+        }
+        float al[W], ar[W];
+#pragma unroll
+        for (int j = 0; j < W; ++j) { al[j] = x[0][j] * gl[0]; ar[j] = x[0][j] * gr[0]; }
+#pragma unroll
+        for (uint32_t k = 1; k < 16u; ++k) {
+#pragma unroll
+            for (int j = 0; j < W; ++j) { al[j] = al[j] + x[k][j] * gl[k]; ar[j] = ar[j] + x[k][j] * gr[k]; }
+        }
+#pragma unroll
+        for (int j = 0; j < W; ++j) { s_grp[(2u * g) * TF + fl + (uint32_t)j] = al[j]; s_grp[(2u * g + 1u) * TF + fl + (uint32_t)j] = ar[j]; }
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < 2u * TF; i += blockDim.x) {
+        const uint32_t c = i / TF, t = i - c * TF, f = blockIdx.x * TF + t;
+        if (f >= m.frames) continue;
+        float acc = s_grp[c * TF + t];
+        for (uint32_t g = 1; g < n_grp; ++g) acc = acc + s_grp[(2u * g + c) * TF + t];
+        m.partials[((size_t)b * 2u + c) * m.pstride + f] = acc;
+    }
+}
+
+__global__ void __launch_bounds__(256) s2r_pan_combine_kernel(const S2rPanMix m) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;    // out[i]: frame i / 2, channel i & 1
+    const uint32_t f = i >> 1, c = i & 1u;
+    if (f >= m.frames) return;
+    float total = 0.0f;                                          // accum = splat(0.0), synth.rs:176
+    for (uint32_t g = 0; g < m.n_groups; ++g) {
+        const uint32_t gb0 = g * m.blocks_per_group;
+        uint32_t gb1 = gb0 + m.blocks_per_group; if (gb1 > m.n_blocks) gb1 = m.n_blocks;
+        if (gb0 >= gb1) continue;
+        float grp = 0.0f;
+        for (uint32_t r0 = gb0; r0 < gb1; r0 += kMixRun) {
+            const uint32_t r1 = r0 + kMixRun < gb1 ? r0 + kMixRun : gb1;
+            float v[kMixRun];
+#pragma unroll
+            for (uint32_t j = 0; j < kMixRun; ++j) v[j] = (r0 + j < r1) ? m.partials[((size_t)(r0 + j) * 2u + c) * m.pstride + f] : 0.0f;
+            float acc = v[0];
+#pragma unroll
+            for (uint32_t j = 1; j < kMixRun; ++j) if (r0 + j < r1) acc = acc + v[j];
+            grp = (r0 == gb0) ? acc : grp + acc;
+        }
+        total = total + grp;
+    }
+    m.out[i] = total;
+}
+
 // publishes the first timed event of every touched voice
 // ... and moves the records from mapped host memory into HBM in one coalesced sweep: the coefficient pass and
 // the render kernel follow per-voice chains through them, and a PCIe round trip per hop is what they cannot afford
@@ -313,5 +397,23 @@ hipError_t s2r_launch_sum_rows(const float *rows, uint32_t n_rows, uint32_t fram
     if (frames == 0) return hipSuccess;
     hipLaunchKernelGGL(s2r_sum_rows_kernel, dim3((frames + 255) / 256), dim3(256), 0, stream, rows, n_rows, frames, stride, stereo, out,
                        done ? *done : S2rDone{nullptr, 0u, nullptr});
+    return hipGetLastError();
+}
+
+hipError_t s2r_launch_pan_mix(const S2rPanMix &m, hipStream_t stream) {
+    if (m.frames == 0 || m.n_voices == 0) return hipSuccess;
+    if (m.block_voices < 64 || m.block_voices > 1024 || (m.block_voices & 63u) || m.n_blocks * m.block_voices < m.n_voices || m.n_blocks > 65535u ||
+        m.stride < m.frames || m.pstride < m.frames || m.n_groups == 0 || m.blocks_per_group * m.n_groups < m.n_blocks)
+        return hipErrorInvalidValue;
+    // 16-byte loads where every row starts on a 16-byte boundary and holds whole quads of frames; else a frame per thread
+    const bool wide = (m.stride & 3u) == 0 && (m.frames & 3u) == 0 && (reinterpret_cast<uintptr_t>(m.rows) & 15u) == 0;
+    const uint32_t tf = kPanLanes * (wide ? 4u : 1u);
+    const size_t lds = (size_t)(m.block_voices / 16u) * 2u * tf * sizeof(float);      // at most 64 KiB (1024 voices, wide)
+    const dim3 grid((m.frames + tf - 1u) / tf, m.n_blocks);
+    if (wide) hipLaunchKernelGGL(s2r_pan_mix_kernel<4>, grid, dim3(256), lds, stream, m);
+    else hipLaunchKernelGGL(s2r_pan_mix_kernel<1>, grid, dim3(256), lds, stream, m);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(s2r_pan_combine_kernel, dim3((2u * m.frames + 255u) / 256u), dim3(256), 0, stream, m);
     return hipGetLastError();
 }

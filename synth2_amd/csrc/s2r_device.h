@@ -340,6 +340,19 @@ struct S2rMixParams {
     uint32_t granule_tag;
 };
 
+// The panned two-channel mixdown (s2r_fill_panned): the voices' rows of a MODE 1 render, each multiplied by
+// its voice's two gains, through the mix tree of DESIGN.md 4.3 once per channel.
+struct S2rPanMix {
+    const float *rows;            // [n_voices][stride]: what the render kernel left in S2rRenderParams.per_voice
+    const float *gain_l, *gain_r; // [n_blocks * block_voices] each, entries past n_voices hold 0
+    uint32_t n_voices, block_voices, n_blocks;
+    uint32_t frames, stride;      // stride >= frames
+    float *partials;              // [n_blocks][2][pstride]: the workgroups' L and R partial rows
+    uint32_t pstride;             // >= frames
+    uint32_t blocks_per_group, n_groups;
+    float *out;                   // interleaved L, R: 2 * frames floats
+};
+
 hipError_t s2r_launch_tables(const S2rTabBuild &b, hipStream_t stream);
 hipError_t s2r_launch_noise_table(float *table_65536, hipStream_t stream);
 // one-pole single-patch handles of one workgroup only (a.p.direct_out set, a.p.frames = the longest fill): false otherwise
@@ -359,3 +372,6 @@ hipError_t s2r_launch_decimate4(float *x_with_history, const float *taps, uint32
 // out[i] = ((+0.0 + rows[0][i]) + rows[1][i]) + ...; rows are `stride` floats apart; stereo: interleaved L, R with L == R
 hipError_t s2r_launch_sum_rows(const float *rows, uint32_t n_rows, uint32_t frames, uint32_t stride, int stereo, float *out, hipStream_t stream,
                                const S2rDone *done);
+// s2r_pan_mix_kernel (a workgroup's voices, both channels from one load of every row element) and the kernel that adds the
+// workgroups' partial rows in the documented order, rooted at +0.0
+hipError_t s2r_launch_pan_mix(const S2rPanMix &m, hipStream_t stream);

@@ -4,6 +4,7 @@
 // Reference boundary being replaced: s2_lib::try3::synth::Synth
 // (/root/reference/components/s2_lib/src/try3/synth.rs:9-203).
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -264,6 +265,23 @@ struct s2r_synth {
     uint32_t *res_cmd = nullptr;                         // the command as the CPU writes it: res_host, or 32 words of fine-grained
     uint32_t *res_cmd_dev = nullptr;                     // DEVICE memory (large BAR) that the kernel polls without crossing the link
     bool res_cmd_vram = false;
+    // True stereo (s2r_fill_panned).  Host bookkeeping: a pan and a key spread per program, beside the bank; the
+    // pan every shard voice got at its note_on (local order).  Nothing of it is touched until a pan is set for the first time
+    // (pan_used): until then every voice's pan is 0 and the note_on paths pay one branch.
+    std::vector<float> prog_pan, prog_spread;    // one entry per bank patch
+    bool pan_used = false;
+    std::vector<float> pans;                     // [shard_voices] once pan_used
+    struct PanEvent { uint32_t local, frame; float pan; };
+    std::vector<PanEvent> pan_timed;             // note_ons at a frame INSIDE the next fill, in event order: their pans take effect there
+    bool gains_dirty = true;                     // pans changed since the gains were last sent to the device
+    float *gains_host = nullptr, *gains_dev = nullptr;   // [2][padded_voices]: gL then gR (pinned / device); entries past the shard hold 0
+    hipEvent_t gains_sent = nullptr;             // behind the last copy out of gains_host
+    float *pan_rows = nullptr;                   // [shard_voices][pan_slice]: the voices' rows of one slice (allocated by the first panned fill)
+    uint32_t pan_slice = 0;                      // frames per slice, a multiple of 16
+    float *pan_partials = nullptr;               // [n_blocks][2][pan_slice]
+    std::vector<hipEvent_t> pan_ev;              // s2r_set_timing: a pair of events around every slice's mixdown of the last panned fill
+    size_t pan_ev_used = 0;
+    float pan_mix_ms = -1.0f;                    // ... and their sum (tools/pan_time.py reads it through s2r_debug_pan_mix_ms)
     float pitch_table[256];
     hipEvent_t t0 = nullptr, t1 = nullptr;
     bool timing = false, timed = false, no_flat_shortcut = false;
@@ -1558,6 +1576,78 @@ int resident_fill(s2r_synth *s, float *out, size_t frames, uint32_t sample_rate,
     return S2R_OK;
 }
 
+// ---- true stereo ----
+inline bool pan_in_range(float x) { return x >= -1.0f && x <= 1.0f; }          // (false for NaN)
+
+// the first pan ever set on this handle: from here on the note_on paths record every voice's pan
+void pan_begin(s2r_synth *s) {
+    if (s->pan_used) return;
+    s->pans.assign(s->shard_voices, 0.0f);
+    s->pan_used = true; s->gains_dirty = true;
+}
+
+// Pans of note_ons that had a frame inside a fill which has been rendered since (by any fill: fill_time is back at 0) are the
+// voices' pans now.  Called before anything reads or writes `pans`.
+void pan_settle(s2r_synth *s) {
+    if (s->pan_timed.empty() || s->fill_time != 0) return;
+    for (const s2r_synth::PanEvent &e : s->pan_timed) s->pans[e.local] = e.pan;
+    s->pan_timed.clear();
+    s->gains_dirty = true;
+}
+
+// a note_on took shard voice `local` (the caller has settled): the pan of the program in force, now or at its frame
+inline void pan_note_on(s2r_synth *s, uint32_t local, uint8_t note, uint32_t frame) {
+    const float p = s2r_voice_pan(s->prog_pan[s->program], s->prog_spread[s->program], note);
+    if (frame == 0) { s->pans[local] = p; s->gains_dirty = true; }
+    else s->pan_timed.push_back(s2r_synth::PanEvent{local, frame, p});
+}
+
+// the gains of the voices' pans, from pinned memory to the device on the handle's stream (when a pan changed)
+int pan_send_gains(s2r_synth *s) {
+    if (!s->gains_dirty) return S2R_OK;
+    const size_t pv = s->padded_voices;
+    if (!s->gains_host) {
+        S2R_HIP(s, hipHostMalloc((void **)&s->gains_host, 2 * pv * sizeof(float), hipHostMallocDefault));
+        std::memset(s->gains_host, 0, 2 * pv * sizeof(float));
+        S2R_HIP(s, hipMalloc((void **)&s->gains_dev, 2 * pv * sizeof(float)));
+        S2R_HIP(s, hipEventCreateWithFlags(&s->gains_sent, hipEventDisableTiming));
+    } else S2R_HIP(s, hipEventSynchronize(s->gains_sent));       // (the last copy may still be reading the pinned buffer)
+    for (uint32_t i = 0; i < s->shard_voices; i++) s2r_pan_gains(s->pan_used ? s->pans[i] : 0.0f, s->gains_host + i, s->gains_host + pv + i);
+    S2R_HIP(s, hipMemcpyAsync(s->gains_dev, s->gains_host, 2 * pv * sizeof(float), hipMemcpyHostToDevice, s->stream));
+    S2R_HIP(s, hipEventRecord(s->gains_sent, s->stream));
+    s->gains_dirty = false;
+    return S2R_OK;
+}
+
+// Frames [at, at + n) of a panned fill, the events of frame `at` already folded into `pending`: slice after slice the MODE 1
+// launch into the rows buffer and the panned mixdown into the mapped output.  `last_event`: the frame the pool's clock has
+// already been moved to by the fill's events (fill_time at entry) — the slices from there on move it further.
+int pan_segment(s2r_synth *s, uint32_t at, uint32_t n, uint32_t last_event, uint32_t sample_rate) {
+    int rc = pan_send_gains(s);
+    if (rc != S2R_OK) return rc;
+    for (uint32_t done = 0; done < n;) {
+        const uint32_t len = n - done < s->pan_slice ? n - done : s->pan_slice;
+        s->fill_time = at + done >= last_event ? 0u : len;       // enqueue_fill moves the clock by len - fill_time
+        rc = enqueue_fill(s, len, sample_rate, s->stream, nullptr, false, false, s->pan_rows);
+        if (rc != S2R_OK) return rc;
+        S2rPanMix m{};
+        m.rows = s->pan_rows; m.gain_l = s->gains_dev; m.gain_r = s->gains_dev + s->padded_voices;
+        m.n_voices = s->shard_voices; m.block_voices = s->block_voices; m.n_blocks = s->n_blocks;
+        m.frames = len; m.stride = len;                          // (the render kernel's rows are `frames` apart)
+        m.partials = s->pan_partials; m.pstride = s->pan_slice;
+        m.n_groups = s->mix_groups; m.blocks_per_group = (s->n_blocks + m.n_groups - 1) / m.n_groups;
+        m.out = s->out_host_dev + 2u * (size_t)(at + done);
+        if (s->timing) {
+            while (s->pan_ev.size() < s->pan_ev_used + 2) { hipEvent_t e; S2R_HIP(s, hipEventCreate(&e)); s->pan_ev.push_back(e); }
+            S2R_HIP(s, hipEventRecord(s->pan_ev[s->pan_ev_used], s->stream));
+        }
+        S2R_HIP(s, s2r_launch_pan_mix(m, s->stream));
+        if (s->timing) { S2R_HIP(s, hipEventRecord(s->pan_ev[s->pan_ev_used + 1], s->stream)); s->pan_ev_used += 2; }
+        done += len;
+    }
+    return S2R_OK;
+}
+
 int fill_host(s2r_synth *s, float *out, size_t frames, uint32_t sample_rate, bool stereo) {
     int rc = check_fill(s, frames, sample_rate);
     if (rc != S2R_OK) return rc;
@@ -1654,6 +1744,12 @@ void release_all(s2r_synth *s) {
     if (s->res_host) (void)hipHostFree(s->res_host);
     if (s->res_gran) (void)hipHostFree(s->res_gran);
     if (s->per_voice_dev) (void)hipFree(s->per_voice_dev);
+    if (s->gains_host) (void)hipHostFree(s->gains_host);
+    if (s->gains_dev) (void)hipFree(s->gains_dev);
+    if (s->gains_sent) (void)hipEventDestroy(s->gains_sent);
+    if (s->pan_rows) (void)hipFree(s->pan_rows);
+    if (s->pan_partials) (void)hipFree(s->pan_partials);
+    for (hipEvent_t e : s->pan_ev) (void)hipEventDestroy(e);
     if (s->voice_ev_head) (void)hipFree(s->voice_ev_head);
     if (s->tev_copy) (void)hipFree(s->tev_copy);
     if (s->partials2[1]) (void)hipFree(s->partials2[1]);
@@ -1757,6 +1853,7 @@ static int create_single(const s2r_config *cfg, std::shared_ptr<S2rVoicePool> po
     if (cfg->reserved0 != 0) { delete s; return S2R_ERR_INVALID; }
     s->parent = parent;
     s->bank.resize(1);
+    s->prog_pan.assign(1, 0.0f); s->prog_spread.assign(1, 0.0f);
     s2r_default_patch(&s->bank[0]);
     if (pool) s->pool = pool;
     else { s->pool.reset(new S2rVoicePool(cfg->total_voices)); s->seed_override.assign(cfg->total_voices, 0u); configure_policy_threads(s->pool.get(), cfg->total_voices); }
@@ -2008,6 +2105,7 @@ int s2r_set_patch_bank(s2r_synth *s, const s2r_patch *patches, uint32_t n) {
     }
     S2R_QUIESCE(s);
     s->bank.assign(patches, patches + n);
+    s->prog_pan.resize(n, 0.0f); s->prog_spread.resize(n, 0.0f);   // the surviving programs keep their pans
     if (s->program >= n) s->program = 0;
     s->bank_dirty = true; s->tab_dirty = true;
     for (s2r_synth *kid : s->kids) { kid->bank = s->bank; kid->bank_dirty = true; kid->tab_dirty = true; }
@@ -2057,6 +2155,11 @@ int s2r_note_on_ex(s2r_synth *s, uint8_t note, float velocity, uint32_t *voice_i
     const uint32_t i = s->pool->note_on(note, velocity);
     if (voice_index_out) *voice_index_out = i;
     if (s->voice_log) s->voice_log(s->voice_log_user, i, note);
+    if (s->pan_used && s->kids.empty()) {
+        pan_settle(s);
+        const int64_t mine = to_local(s, i);
+        if (mine >= 0) pan_note_on(s, (uint32_t)mine, note, 0u);
+    }
     if (!append_frame0_record(s, i, S2R_EV_RESTART, s->pitch_table[note], s->seed_override[i], s->program))
         push_event(s, i, S2R_EV_RESTART, s->pitch_table[note], s->seed_override[i], s->program);
     return S2R_OK;
@@ -2103,6 +2206,7 @@ int s2r_note_events(s2r_synth *s, const s2r_note_event *events, size_t n) {
     // and note_off over the events computes — on several threads for a multi-GPU-sized batch): the voice every event takes or
     // releases.  An event inside the next fill first moves the pool's clock to its frame (the policy sees the offsets every
     // voice has AT that frame, like the reference between two 16-frame calls); frame-0 events take effect before the fill.
+    if (s->pan_used) pan_settle(s);                              // (while fill_time still says whether the last fill's events are behind us)
     static thread_local std::vector<int64_t> chosen;
     if (chosen.size() < n) chosen.resize(n);
     static_assert(sizeof(S2rPolicyEvent) == 4 && S2R_NOTE_ON == S2R_POLICY_NOTE_ON && S2R_NOTE_OFF == S2R_POLICY_NOTE_OFF, "s2r_note_event's first four bytes");
@@ -2143,6 +2247,7 @@ int s2r_note_events(s2r_synth *s, const s2r_note_event *events, size_t n) {
         }
         const uint32_t frame = e.frame;
         const bool on = e.kind == S2R_NOTE_ON;
+        if (on && one && one->pan_used) pan_note_on(one, local, e.note, frame);
         if (frame == 0 && may_fold && sh->tpending.empty()) {
             if (on) push_event(s, (uint32_t)vi, S2R_EV_RESTART, pitch_of[e.note], seed_of[(size_t)vi], s->program);
             else push_event(s, (uint32_t)vi, S2R_EV_RELEASE, 0.0f, 0u);
@@ -2223,6 +2328,133 @@ int s2r_fill_end(s2r_synth *s, float *mono_out, size_t capacity) {
 
 int s2r_fill_stereo(s2r_synth *s, float *interleaved_lr_out, size_t frames, uint32_t sample_rate_hz) {
     return fill_host(s, interleaved_lr_out, frames, sample_rate_hz, true);
+}
+
+// ---- true stereo ----
+float s2r_voice_pan(float pan, float key_spread, uint8_t note) {
+    const float k = (float)((int)note - 64) * 0.015625f;        // exact
+    const float spread = key_spread * k;                         // (-ffp-contract=off: rounded before the sum)
+    const float p = pan + spread;
+    return p < -1.0f ? -1.0f : (p > 1.0f ? 1.0f : p);
+}
+
+void s2r_pan_gains(float p, float *gl, float *gr) {
+    const float l = (1.0f - p) * 0.5f, r = (1.0f + p) * 0.5f;
+    if (gl) *gl = std::sqrt(l);                                  // IEEE 754 sqrt: correctly rounded
+    if (gr) *gr = std::sqrt(r);
+}
+
+int s2r_set_program_pan(s2r_synth *s, uint32_t program, float pan, float key_spread) {
+    // (the values first: they are wrong whatever the handle holds — and a front-end can ask without a device)
+    if (!pan_in_range(pan) || !pan_in_range(key_spread))
+        return set_err(s, S2R_ERR_PATCH_RANGE, "program %u: pan %g, key_spread %g: both lie in [-1, 1]", program, (double)pan, (double)key_spread);
+    if (!s) return S2R_ERR_INVALID;
+    if (program >= s->bank.size()) return set_err(s, S2R_ERR_INVALID, "program %u: the bank holds %zu patches", program, s->bank.size());
+    if (pan != 0.0f || key_spread != 0.0f) { pan_begin(s); pan_settle(s); }
+    s->prog_pan[program] = pan; s->prog_spread[program] = key_spread;
+    return S2R_OK;
+}
+
+int s2r_get_program_pan(const s2r_synth *s, uint32_t program, float *pan, float *key_spread) {
+    if (!s) return S2R_ERR_INVALID;
+    if (program >= s->bank.size()) return S2R_ERR_INVALID;
+    if (pan) *pan = s->prog_pan[program];
+    if (key_spread) *key_spread = s->prog_spread[program];
+    return S2R_OK;
+}
+
+int s2r_get_voice_pans(s2r_synth *s, float *pans) {
+    if (!s || !pans) return S2R_ERR_INVALID;
+    if (!s->kids.empty()) return set_err(s, S2R_ERR_INVALID, "voice pans are kept by single-device handles, not by a device list");
+    if (!s->pan_used) { std::fill(pans, pans + s->shard_voices, 0.0f); return S2R_OK; }
+    // (pans of note_ons inside a fill not rendered yet are not the voices' yet)
+    pan_settle(s);
+    std::memcpy(pans, s->pans.data(), (size_t)s->shard_voices * sizeof(float));
+    return S2R_OK;
+}
+
+int s2r_set_voice_pans(s2r_synth *s, const float *pans) {
+    if (!s || !pans) return S2R_ERR_INVALID;
+    if (!s->kids.empty()) return set_err(s, S2R_ERR_INVALID, "voice pans are kept by single-device handles, not by a device list");
+    for (uint32_t i = 0; i < s->shard_voices; i++)
+        if (!pan_in_range(pans[i])) return set_err(s, S2R_ERR_PATCH_RANGE, "voice %u: pan %g does not lie in [-1, 1]", i, (double)pans[i]);
+    pan_begin(s);
+    pan_settle(s);
+    std::memcpy(s->pans.data(), pans, (size_t)s->shard_voices * sizeof(float));
+    s->gains_dirty = true;
+    return S2R_OK;
+}
+
+int s2r_fill_panned(s2r_synth *s, float *interleaved_lr_out, size_t frames, uint32_t sample_rate_hz) {
+    if (!s) return S2R_ERR_INVALID;
+    if (!s->kids.empty() || s->parent) return set_err(s, S2R_ERR_INVALID, "s2r_fill_panned takes a single-device handle, not a device list");
+    if (s->xg_on) return set_err(s, S2R_ERR_INVALID, "s2r_fill_panned takes a handle without an exchange attached");
+    int rc = check_fill(s, frames, sample_rate_hz);
+    if (rc != S2R_OK) return rc;
+    if (frames == 0) return S2R_OK;
+    if (!interleaved_lr_out) return set_err(s, S2R_ERR_INVALID, "null output buffer");
+    if (s->ring_count) return set_err(s, S2R_ERR_INVALID, "s2r_fill_panned with fills of s2r_fill_begin in flight: s2r_fill_end first");
+    S2R_QUIESCE(s);
+    S2R_HIP(s, hipSetDevice(s->device));
+    if (!s->pan_rows) {
+        // The rows buffer, sized ONCE (s2r.h): whole fills where they fit into 256 MiB, else slices of a multiple of 16 frames —
+        // a fill split at a multiple of 16 renders the same bits (s2r.h, s2r_note_events).  (Shorter slices, whose rows would
+        // stay closer to the compute units, were measured and are slower: profiles/r05/pan_mix.txt)
+        uint32_t slice = (uint32_t)std::min<size_t>((((size_t)256 << 20) / sizeof(float) / s->shard_voices) & ~(size_t)15, 1u << 30);
+        if (const char *e = std::getenv("S2R_PAN_SLICE")) slice = (uint32_t)std::atol(e) & ~15u;      // (measurement: tools/pan_time.py)
+        const uint32_t whole = (s->cfg.max_frames + 15u) & ~15u;
+        if (slice < 16u) slice = 16u;
+        if (slice > whole) slice = whole;
+        S2R_HIP(s, hipMalloc((void **)&s->pan_partials, (size_t)s->n_blocks * 2u * slice * sizeof(float)));
+        S2R_HIP(s, hipMalloc((void **)&s->pan_rows, (size_t)s->shard_voices * slice * sizeof(float)));
+        s->pan_slice = slice;
+    }
+    fold_frame0_records(s);
+    if (s->pan_used) pan_settle(s);
+    s->pan_ev_used = 0;
+    const uint32_t last_event = s->fill_time;
+    if (s->tpending.empty()) {
+        rc = pan_segment(s, 0u, (uint32_t)frames, last_event, sample_rate_hz);
+        if (rc != S2R_OK) return rc;
+    } else {
+        // Events inside the fill: the per-voice rows and the event chains exclude each other in the render kernels, and an
+        // event at frame f acts "exactly as if the caller had split the fill there" (s2r.h) — so the fill IS split there: the
+        // records of one frame are folded like untimed ones (fold_frame0_records), their note_ons' pans become the voices', and
+        // the segment up to the next event frame is rendered.  (Records arrive in non-decreasing frame order.)
+        std::vector<S2rTimedEvent> recs;
+        recs.swap(s->tpending);
+        for (const S2rTimedEvent &te : recs) s->tlast[te.voice] = -1;
+        std::vector<s2r_synth::PanEvent> pev;
+        pev.swap(s->pan_timed);
+        size_t k = 0, kp = 0;
+        uint32_t at = 0;
+        while (at < frames) {
+            for (; k < recs.size() && recs[k].frame <= at; k++) {
+                const S2rTimedEvent &te = recs[k];
+                int32_t slot = s->pending_slot[te.voice];
+                if (slot < 0) {
+                    slot = (int32_t)s->pending.size();
+                    s->pending_slot[te.voice] = slot;
+                    s->pending.push_back(S2rVoiceEvent{te.voice, 0u, 0.0f, 0u});
+                }
+                S2rVoiceEvent &e = s->pending[(size_t)slot];
+                if (te.flags & S2R_EV_RESTART) { e.flags = S2R_EV_RESTART | (te.program << S2R_EV_PROGRAM_SHIFT); e.pitch = te.pitch; e.seed = te.seed; }
+                if (te.flags & S2R_EV_RELEASE) e.flags |= S2R_EV_RELEASE;
+            }
+            for (; kp < pev.size() && pev[kp].frame <= at; kp++) { s->pans[pev[kp].local] = pev[kp].pan; s->gains_dirty = true; }
+            const uint32_t next = k < recs.size() && recs[k].frame < frames ? recs[k].frame : (uint32_t)frames;
+            rc = pan_segment(s, at, next - at, last_event, sample_rate_hz);
+            if (rc != S2R_OK) { s->fill_time = 0; return rc; }
+            at = next;
+        }
+    }
+    S2R_HIP(s, hipStreamSynchronize(s->stream));
+    std::memcpy(interleaved_lr_out, s->out_host, 2 * frames * sizeof(float));
+    if (s->timing) {
+        s->pan_mix_ms = 0.0f;
+        for (size_t k = 0; k < s->pan_ev_used; k += 2) { float ms = 0.0f; S2R_HIP(s, hipEventElapsedTime(&ms, s->pan_ev[k], s->pan_ev[k + 1])); s->pan_mix_ms += ms; }
+    }
+    return S2R_OK;
 }
 
 int s2r_fill_oversampled(s2r_synth *s, float *mono_out, size_t frames, uint32_t sample_rate_hz) {
@@ -2647,6 +2879,11 @@ const char *s2r_last_error(const s2r_synth *s) { return s ? s->err.c_str() : "nu
 
 // Diagnostic builds only (-DS2R_STAMPS; tools/stamps.py): copies the last fill's per-wave phase stamps ([waves][16]
 // s_memtime ticks) to `out`; returns the number of waves, 0 in a product build.  Not declared in s2r.h.
+// measurement (tools/pan_time.py): device time of the panned mixdown's kernels in the last s2r_fill_panned, summed over its
+// slices, in milliseconds (s2r_set_timing on; < 0 otherwise); and the frames per slice of the rows buffer (0: not allocated yet)
+extern "C" float s2r_debug_pan_mix_ms(const s2r_synth *s) { return s && s->timing ? s->pan_mix_ms : -1.0f; }
+extern "C" uint32_t s2r_debug_pan_slice(const s2r_synth *s) { return s ? s->pan_slice : 0u; }
+
 extern "C" uint32_t s2r_debug_read_stamps(s2r_synth *s, unsigned long long *out, uint32_t max_waves) {
 #if defined(S2R_STAMPS)
     if (!s) return 0;

@@ -164,6 +164,13 @@ def load_library():
         "s2r_fills_in_flight": (C.c_uint32, [H]),
         "s2r_fill_stereo": (C.c_int, [H, _f32p, C.c_size_t, C.c_uint32]),
         "s2r_fill_oversampled": (C.c_int, [H, _f32p, C.c_size_t, C.c_uint32]),
+        "s2r_set_program_pan": (C.c_int, [H, C.c_uint32, C.c_float, C.c_float]),
+        "s2r_get_program_pan": (C.c_int, [H, C.c_uint32, _f32p, _f32p]),
+        "s2r_get_voice_pans": (C.c_int, [H, _f32p]),
+        "s2r_set_voice_pans": (C.c_int, [H, _f32p]),
+        "s2r_fill_panned": (C.c_int, [H, _f32p, C.c_size_t, C.c_uint32]),
+        "s2r_voice_pan": (C.c_float, [C.c_float, C.c_float, C.c_uint8]),
+        "s2r_pan_gains": (None, [C.c_float, _f32p, _f32p]),
         "s2r_fill_device": (C.c_int, [H, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
         "s2r_fill_device_root": (C.c_int, [H, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
         "s2r_sum_partials_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_size_t, C.c_void_p, C.c_void_p]),
@@ -227,6 +234,18 @@ def parse_patch(text):
     if rc != S2R_OK:
         raise S2rError(rc, err.value.decode())
     return p
+
+
+def voice_pan(pan, key_spread, note):
+    """the pan a note_on gives its voice under a program's pan and key spread (s2r_voice_pan; host only)"""
+    return float(load_library().s2r_voice_pan(float(pan), float(key_spread), int(note)))
+
+
+def pan_gains(p):
+    """(gL, gR) of pan p: the constant-power law sqrt((1 -/+ p) / 2) in binary32 (s2r_pan_gains; host only)"""
+    gl, gr = C.c_float(), C.c_float()
+    load_library().s2r_pan_gains(float(p), C.byref(gl), C.byref(gr))
+    return gl.value, gr.value
 
 
 def stream_frame_json(samples):
@@ -413,6 +432,33 @@ class Synth:
     def sample_stereo(self, frames, sample_rate=SampleRateKhz(48000)):
         out = np.empty(2 * frames, dtype=np.float32)
         self._check(self.L.s2r_fill_stereo(self.h, out.ctypes.data_as(_f32p), frames, int(sample_rate)))
+        return out.reshape(frames, 2)
+
+    # --- true stereo (build-defined; s2r.h: s2r_fill_panned) ---
+    def set_program_pan(self, program, pan, key_spread=0.0):
+        """pan and key spread (both in [-1, 1]) of a bank program: what a note_on under that program gives its voice"""
+        self._check(self.L.s2r_set_program_pan(self.h, int(program), float(pan), float(key_spread)))
+
+    def get_program_pan(self, program):
+        pan, spread = C.c_float(), C.c_float()
+        self._check(self.L.s2r_get_program_pan(self.h, int(program), C.byref(pan), C.byref(spread)))
+        return pan.value, spread.value
+
+    def voice_pans(self):
+        """every shard voice's pan, local order (the checkpoint companion of export_state)"""
+        out = np.empty(self.shard_voices, dtype=np.float32)
+        self._check(self.L.s2r_get_voice_pans(self.h, out.ctypes.data_as(_f32p)))
+        return out
+
+    def set_voice_pans(self, pans):
+        arr = np.ascontiguousarray(pans, dtype=np.float32)
+        assert arr.size == self.shard_voices
+        self._check(self.L.s2r_set_voice_pans(self.h, arr.ctypes.data_as(_f32p)))
+
+    def sample_panned(self, frames, sample_rate=SampleRateKhz(48000)):
+        """the panned two-channel mixdown: (frames, 2) float32, columns L and R"""
+        out = np.empty(2 * frames, dtype=np.float32)
+        self._check(self.L.s2r_fill_panned(self.h, out.ctypes.data_as(_f32p), frames, int(sample_rate)))
         return out.reshape(frames, 2)
 
     def render_voices(self, frames, sample_rate=SampleRateKhz(48000)):
