@@ -93,6 +93,18 @@ class Synth {
     static float voice_pan(float pan, float key_spread, Note note) { return s2r_voice_pan(pan, key_spread, note.v); }
     static void pan_gains(float p, float *gl, float *gr) { s2r_pan_gains(p, gl, gr); }
 
+    // the voice mixer (build-defined; s2r.h: s2r_fill_buses): level, velocity sensitivity and output bus per bank program, given
+    // to a voice at its note_on; `buffer` takes 2 * len * n_buses floats, bus-major, L, R interleaved inside a bus
+    void set_program_mix(uint32_t program, float level, float velocity_sens = 0.0f, uint32_t bus = 0) { check(s2r_set_program_mix(h_, program, level, velocity_sens, bus)); }
+    void get_program_mix(uint32_t program, float *level, float *velocity_sens, uint32_t *bus) const { check(s2r_get_program_mix(h_, program, level, velocity_sens, bus)); }
+    void voice_mix(float *gains, uint8_t *buses) { check(s2r_get_voice_mix(h_, gains, buses)); }    // shard_voices entries each, local order
+    void set_voice_mix(const float *gains, const uint8_t *buses) { check(s2r_set_voice_mix(h_, gains, buses)); }
+    void sample_buses(float *buffer, size_t capacity, uint32_t n_buses, size_t len, SampleRateKhz sample_rate) {
+        check(s2r_fill_buses(h_, buffer, capacity, n_buses, len, sample_rate.v));
+    }
+    // host only: the gain a note_on of `velocity` gives its voice
+    static float voice_gain(float level, float velocity_sens, float velocity) { return s2r_voice_gain(level, velocity_sens, velocity); }
+
     s2r_synth *handle() { return h_; }
 
   private:

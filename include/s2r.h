@@ -32,7 +32,8 @@ extern "C" {
 /* Changes when a struct layout or an existing signature changes.  Entry points added since 4.0 without touching either:
  * s2r_set_low_latency, s2r_low_latency_active, s2r_build_id, s2r_set_resident, s2r_resident_active, s2r_quiesce,
  * s2r_exchange_create, s2r_exchange_attach, s2r_voice_pool_set_threads, s2r_voice_pool_resolve, s2r_set_program_pan,
- * s2r_get_program_pan, s2r_get_voice_pans, s2r_set_voice_pans, s2r_fill_panned, s2r_voice_pan, s2r_pan_gains. */
+ * s2r_get_program_pan, s2r_get_voice_pans, s2r_set_voice_pans, s2r_fill_panned, s2r_voice_pan, s2r_pan_gains,
+ * s2r_set_program_mix, s2r_get_program_mix, s2r_get_voice_mix, s2r_set_voice_mix, s2r_voice_gain, s2r_fill_buses. */
 #define S2R_ABI_VERSION 4
 
 typedef enum {
@@ -249,6 +250,41 @@ int s2r_get_voice_pans(s2r_synth *s, float *pans);
 int s2r_set_voice_pans(s2r_synth *s, const float *pans);
 int s2r_fill_panned(s2r_synth *s, float *interleaved_lr_out, size_t frames, uint32_t sample_rate_hz);
 
+/* BUILD-DEFINED voice mixer (the reference has neither; DESIGN.md 4.13 gives the op sequence): a level, a velocity sensitivity
+ * and an output bus per bank program, and a fill that writes up to S2R_MAX_BUSES stereo buses from one render pass.
+ * Every program of the bank has a `level` in [0, 1] (default 1), a `velocity_sens` in [0, 1] (default 0) and a `bus` in
+ * [0, S2R_MAX_BUSES) (default 0), held beside the bank like pan / key_spread (not in s2r_patch).  A note_on gives its voice the
+ * gain w = s2r_voice_gain(level, velocity_sens, velocity) and the bus of the program current at that note_on (a
+ * S2R_PROGRAM_CHANGE inside a batch included; an event inside a fill takes effect at its frame, as its pan does); the voice keeps
+ * both until it is restarted; a voice never started has w = 1 and bus 0; changing a program's mix affects later note_ons only.
+ * With the defaults w == 1.0f exactly.  s2r_set_patch_bank keeps the values of the programs that survive and gives new ones the
+ * defaults.
+ * ONLY s2r_fill_buses applies them: s2r_fill, s2r_fill_stereo, s2r_fill_panned, s2r_fill_oversampled, s2r_fill_begin / _end,
+ * s2r_fill_device and s2r_render_voices ignore level, velocity and bus and return exactly what they returned before (the
+ * reference stores a velocity and never uses it).
+ *   s2r_set_program_mix: S2R_ERR_PATCH_RANGE for a level or sensitivity outside [0, 1] or NaN or a bus >= S2R_MAX_BUSES (checked
+ *   before the handle is looked at; nothing is changed), S2R_ERR_INVALID if program >= bank size.
+ *   s2r_get_voice_mix / s2r_set_voice_mix: every shard voice's w and bus, shard_voices entries each in local order: the
+ *   companions of s2r_export_state and s2r_get_voice_pans for checkpoint / resume.  The setter refuses a gain outside [0, 1] or
+ *   NaN and a bus >= S2R_MAX_BUSES with S2R_ERR_PATCH_RANGE and changes nothing then.  Single-device handles.
+ *   s2r_fill_buses: s2r_fill_panned onto n_buses (1 .. S2R_MAX_BUSES) stereo buses.  Synchronous; overwrites
+ *   2 * frames * n_buses floats, bus-major, L, R interleaved inside a bus: out[(b * frames + i) * 2 + c] is the mix tree of
+ *   DESIGN.md 4.3 over x[v][i] = row[v][i] * gb_c[v] (one rounded multiply, denormals kept) with
+ *   gb_c[v] = (min(bus of v, n_buses - 1) == b) ? s2r_pan_gains(pan of v)_c * w[v] : +0.0f (the product rounded once, on the
+ *   host).  A voice booked on a bus >= n_buses sounds on the LAST bus; an off-bus voice is a term with gain +0.0, not a skipped
+ *   one (what s2r_fill_panned does at hard left or right).  `capacity` is the number of floats `out` can take: a smaller one
+ *   than 2 * frames * n_buses returns S2R_ERR_INVALID and consumes nothing, like n_buses == 0 or > S2R_MAX_BUSES.  State,
+ *   events inside the fill, the rows buffer (shared with s2r_fill_panned: allocated by whichever of the two comes first) and
+ *   the restrictions are s2r_fill_panned's: single-device handles without an exchange attached, no s2r_fill_begin in flight;
+ *   resident kernels are stopped.  The first bus fill also allocates, once, the workgroups' partial rows
+ *   (n_blocks * S2R_MAX_BUSES * 2 * slice floats) and a pinned output of 2 * S2R_MAX_BUSES * max_frames floats. */
+#define S2R_MAX_BUSES 8u
+int s2r_set_program_mix(s2r_synth *s, uint32_t program, float level, float velocity_sens, uint32_t bus);
+int s2r_get_program_mix(const s2r_synth *s, uint32_t program, float *level, float *velocity_sens, uint32_t *bus);
+int s2r_get_voice_mix(s2r_synth *s, float *gains, uint8_t *buses);
+int s2r_set_voice_mix(s2r_synth *s, const float *gains, const uint8_t *buses);
+int s2r_fill_buses(s2r_synth *s, float *out, size_t capacity, uint32_t n_buses, size_t frames, uint32_t sample_rate_hz);
+
 /* BUILD-DEFINED 4x oversampling (the reference has none; BASELINE config [4]): renders 4 * frames at
  * 4 * sample_rate_hz through the same path and decimates the mix by a 63-tap windowed sinc whose history
  * carries over from call to call (DESIGN.md 4.9 gives taps and arithmetic).  4 * frames must not exceed
@@ -404,6 +440,11 @@ int s2r_parse_patch_text(const char *text, size_t len, s2r_patch *out, char *err
  * gL = sqrtf((1 - p) * 0.5f), gR = sqrtf((1 + p) * 0.5f): the centre gives sqrt(0.5) on both sides, p = -1 gives (1, 0). */
 float s2r_voice_pan(float pan, float key_spread, uint8_t note);
 void s2r_pan_gains(float p, float *gl, float *gr);
+
+/* The gain a note_on gives its voice.  binary32, every operation rounded on its own, no fma:
+ *   u = velocity < 1.0f ? velocity : 1.0f  (NaN -> 1);  u = u > 0.0f ? u : 0.0f;  a = 1.0f - velocity_sens * (1.0f - u);
+ *   w = level * a.   w == 1.0f exactly for level 1, sensitivity 0, any velocity. */
+float s2r_voice_gain(float level, float velocity_sens, float velocity);
 
 /* The voice-allocation / release policy of Synth (synth.rs:61-120) for a pool of any size,
  * O(1) per event, without rendering.  Offsets advance by s2r_voice_pool_advance. */

@@ -144,6 +144,12 @@ pub mod ffi {
         pub fn s2r_fill_panned(s: *mut S2rSynth, interleaved_lr_out: *mut f32, frames: usize, sample_rate_hz: u32) -> c_int;
         pub fn s2r_voice_pan(pan: f32, key_spread: f32, note: u8) -> f32;
         pub fn s2r_pan_gains(p: f32, gl: *mut f32, gr: *mut f32);
+        pub fn s2r_set_program_mix(s: *mut S2rSynth, program: u32, level: f32, velocity_sens: f32, bus: u32) -> c_int;
+        pub fn s2r_get_program_mix(s: *const S2rSynth, program: u32, level: *mut f32, velocity_sens: *mut f32, bus: *mut u32) -> c_int;
+        pub fn s2r_get_voice_mix(s: *mut S2rSynth, gains: *mut f32, buses: *mut u8) -> c_int;
+        pub fn s2r_set_voice_mix(s: *mut S2rSynth, gains: *const f32, buses: *const u8) -> c_int;
+        pub fn s2r_voice_gain(level: f32, velocity_sens: f32, velocity: f32) -> f32;
+        pub fn s2r_fill_buses(s: *mut S2rSynth, out: *mut f32, capacity: usize, n_buses: u32, frames: usize, sample_rate_hz: u32) -> c_int;
         pub fn s2r_shard_voices(s: *const S2rSynth) -> u32;
         pub fn s2r_fill_device(s: *mut S2rSynth, dev_out: *mut f32, frames: usize, sample_rate_hz: u32,
                                hip_stream: *mut c_void) -> c_int;
@@ -171,6 +177,14 @@ pub fn pan_gains(p: f32) -> (f32, f32) {
     let (mut gl, mut gr) = (0.0f32, 0.0f32);
     unsafe { ffi::s2r_pan_gains(p, &mut gl, &mut gr) };
     (gl, gr)
+}
+
+/// `S2R_MAX_BUSES`: the most stereo buses one `sample_buses` call writes.
+pub const MAX_BUSES: u32 = 8;
+
+/// Host-only: the gain a note_on of `velocity` gives its voice under a program's level and velocity sensitivity — DESIGN.md 4.13.
+pub fn voice_gain(level: f32, velocity_sens: f32, velocity: f32) -> f32 {
+    unsafe { ffi::s2r_voice_gain(level, velocity_sens, velocity) }
 }
 
 pub mod synth {
@@ -367,6 +381,40 @@ pub mod synth {
             self.check(unsafe {
                 ffi::s2r_fill_panned(self.handle, interleaved.as_mut_ptr(), interleaved.len() / 2, sample_rate.0)
             });
+        }
+
+        /// Build-defined voice mixer (`s2r_fill_buses`, include/s2r.h): level and velocity sensitivity (both in [0, 1]) and
+        /// output bus (below `MAX_BUSES`) of a bank program — what a note_on under that program gives its voice.
+        pub fn set_program_mix(&mut self, program: u32, level: f32, velocity_sens: f32, bus: u32) {
+            self.check(unsafe { ffi::s2r_set_program_mix(self.handle, program, level, velocity_sens, bus) });
+        }
+
+        pub fn get_program_mix(&self, program: u32) -> (f32, f32, u32) {
+            let (mut level, mut sens, mut bus) = (0.0f32, 0.0f32, 0u32);
+            self.check(unsafe { ffi::s2r_get_program_mix(self.handle, program, &mut level, &mut sens, &mut bus) });
+            (level, sens, bus)
+        }
+
+        /// Every voice's gain and bus, pool order on a handle that renders its whole pool: checkpoint companions of the state.
+        pub fn voice_mix(&mut self) -> (Vec<f32>, Vec<u8>) {
+            let n = unsafe { ffi::s2r_shard_voices(self.handle) } as usize;
+            let (mut gains, mut buses) = (vec![0.0f32; n], vec![0u8; n]);
+            self.check(unsafe { ffi::s2r_get_voice_mix(self.handle, gains.as_mut_ptr(), buses.as_mut_ptr()) });
+            (gains, buses)
+        }
+
+        pub fn set_voice_mix(&mut self, gains: &[f32], buses: &[u8]) {
+            let n = unsafe { ffi::s2r_shard_voices(self.handle) } as usize;
+            assert!(gains.len() == n && buses.len() == n);
+            self.check(unsafe { ffi::s2r_set_voice_mix(self.handle, gains.as_ptr(), buses.as_ptr()) });
+        }
+
+        /// The panned mixdown onto `n_buses` stereo buses from one render pass: `out` is bus-major, L, R pairs inside a bus;
+        /// its length is `2 * frames * n_buses`.
+        pub fn sample_buses(&mut self, out: &mut [f32], n_buses: u32, sample_rate: SampleRateKhz) {
+            assert!(n_buses >= 1 && out.len() % (2 * n_buses as usize) == 0);
+            let frames = out.len() / (2 * n_buses as usize);
+            self.check(unsafe { ffi::s2r_fill_buses(self.handle, out.as_mut_ptr(), out.len(), n_buses, frames, sample_rate.0) });
         }
 
         /// For the reference's own call pattern — `sample()` per 16 frames from the audio callback (main.rs:138-147): keeps a

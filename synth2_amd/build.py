@@ -49,6 +49,10 @@ PER_FILE_FLAGS = {}
 for _f in ("s2r_render_general_square.hip", "s2r_render_general_saw.hip", "s2r_render_general_triangle.hip", "s2r_render_general_sine.hip",
            "s2r_render_general_bank.hip"):
     PER_FILE_FLAGS[_f] = ["-ftrivial-auto-var-init=zero"]
+# s2r_aux.hip is compiled with the back end's resource-usage remarks: the bus mixdown keeps up to sixteen sums per frame in
+# registers by compiling the bus count in, and _check_no_scratch() fails the build if an instantiation went to scratch.
+PER_FILE_FLAGS["s2r_aux.hip"] = ["-Rpass-analysis=kernel-resource-usage"]
+NO_SCRATCH_KERNELS = ("s2r_bus_mix_kernel", "s2r_bus_combine_kernel")
 if os.environ.get("S2R_EXPERIMENT_BANK_FLAGS"):                 # (development: extra flags for the patch-bank translation unit)
     PER_FILE_FLAGS["s2r_render_general_bank.hip"] = PER_FILE_FLAGS["s2r_render_general_bank.hip"] + os.environ["S2R_EXPERIMENT_BANK_FLAGS"].split()
 
@@ -140,10 +144,47 @@ def _compile_one(args):
     cmd = [cc] + flags + extra + ["-x", "hip", "-c", "-I", os.path.join(ROOT, "include"), "-I", CSRC, "-o", obj, src]
     if verbose:
         print(" ".join(cmd), file=sys.stderr)
-    subprocess.check_call(cmd)
+    if "-Rpass-analysis=kernel-resource-usage" in extra:
+        r = subprocess.run(cmd, stderr=subprocess.PIPE, universal_newlines=True)
+        if r.returncode:
+            sys.stderr.write(r.stderr)
+            raise subprocess.CalledProcessError(r.returncode, cmd)
+        usage = kernel_resources(r.stderr)
+        with open(os.path.splitext(obj)[0] + ".resources.txt", "w") as f:
+            for name, u in usage:
+                f.write("%s: %s\n" % (name, ", ".join("%s %s" % kv for kv in u.items())))
+        _check_no_scratch(usage)
+    else:
+        subprocess.check_call(cmd)
     with open(obj + ".id", "w") as f:
         f.write(stamp)
     return obj
+
+
+def kernel_resources(remarks):
+    """[(mangled kernel name, {figure: value})] from the text of -Rpass-analysis=kernel-resource-usage"""
+    out = []
+    for line in remarks.splitlines():
+        m = re.search(r"remark:\s+(.*?)\s+\[-Rpass-analysis=kernel-resource-usage\]", line)
+        if not m:
+            continue
+        key, _, val = m.group(1).partition(": ")
+        if key == "Function Name":
+            out.append((val, {}))
+        elif out:
+            out[-1][1][key] = val
+    return out
+
+
+def _check_no_scratch(usage):
+    seen = 0
+    for name, u in usage:
+        if any(k in name for k in NO_SCRATCH_KERNELS):
+            seen += 1
+            if u.get("ScratchSize [bytes/lane]") != "0" or u.get("VGPRs Spill") != "0":
+                raise RuntimeError("libs2r: %s uses scratch (%r): its sums must stay in registers" % (name, u))
+    if seen < 9:
+        raise RuntimeError("libs2r: resource usage of %d bus-mix kernels reported, 9 expected (2 load widths x 4 bus counts, and the combine)" % seen)
 
 
 def check_m0_contract(lib=None, texts=None):

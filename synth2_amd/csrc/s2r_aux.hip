@@ -206,6 +206,107 @@ __global__ void __launch_bounds__(256) s2r_pan_combine_kernel(const S2rPanMix m)
     m.out[i] = total;
 }
 
+// ---------------------------------------------------------------------------------------
+// The bus mixdown (s2r_fill_buses): up to 8 stereo buses from ONE read of the rows.  Per bus q and channel c
+// x[v][i] = row[v][i] * gb_c[v], gb_c[v] = (min(bus[v], n_buses - 1) == q) ? g_c[v] : +0.0 (g_c: the pan gain times the voice's
+// gain, multiplied on the host), through the same tree as the panned mixdown above — an off-bus voice is a term of row * +0.0,
+// not a skipped one.
+//   s2r_bus_mix_kernel<W, NB>: the geometry of s2r_pan_mix_kernel — workgroup (tile, b), a thread adds ONE run of 16 voices for W
+//   consecutive frames — with `lanes` threads along the frames: the launcher halves the tile until [block_voices / 16][2 * NB][tile]
+//   floats fit 32 KiB of LDS, so that several workgroups share a compute unit.  The run's 16 x W row elements are loaded once and
+//   stay in registers; bus after bus (NB is compiled in: no indexed accumulator, nothing in scratch) the sixteen gains are
+//   selected once per voice and the run is multiplied and added into W L and W R sums, which go to LDS.  The surplus buses of an
+//   instantiation (n_buses < NB) are neither computed nor stored.
+//   s2r_bus_combine_kernel: s2r_pan_combine_kernel with a bus index.
+// ---------------------------------------------------------------------------------------
+constexpr uint32_t kBusLdsBytes = 32u << 10;
+
+template <int W, int NB>
+__global__ void __launch_bounds__(256) s2r_bus_mix_kernel(const S2rBusMix m) {
+    extern __shared__ float s_bus[];                             // [block_voices / 16][2 * NB][lanes * W]
+    const uint32_t lanes = m.lanes, TF = lanes * (uint32_t)W;
+    const uint32_t lane = threadIdx.x & (lanes - 1u), slot = threadIdx.x / lanes, n_slots = blockDim.x / lanes;
+    const uint32_t b = blockIdx.y, fl = lane * (uint32_t)W, f0 = blockIdx.x * TF + fl;
+    const uint32_t n_grp = m.block_voices / 16u, last = m.n_buses - 1u;
+    for (uint32_t g = slot; g < n_grp; g += n_slots) {
+        const uint32_t v0 = b * m.block_voices + 16u * g;
+        float x[16][W], gl[16], gr[16];
+        uint32_t vb[16];
+#pragma unroll
+        for (uint32_t k = 0; k < 16u; ++k) {
+            const uint32_t v = v0 + k;
+            gl[k] = m.gain_l[v]; gr[k] = m.gain_r[v];            // (padded with 0 up to the grid's last voice)
+            const uint32_t q = m.bus[v];
+            vb[k] = q < last ? q : last;                         // a voice booked past the call's buses sounds on the last one
+            const float *src = m.rows + (size_t)v * m.stride + f0;
+            if (W == 4) {
+                const f4 r = (v < m.n_voices && f0 < m.frames) ? *reinterpret_cast<const f4 *>(src) : (f4){0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+                for (int j = 0; j < W; ++j) x[k][j] = r[j];
+            } else {
+#pragma unroll
+                for (int j = 0; j < W; ++j) x[k][j] = (v < m.n_voices && f0 + (uint32_t)j < m.frames) ? src[j] : 0.0f;
+            }
+        }
+#pragma unroll
+        for (uint32_t q = 0; q < (uint32_t)NB; ++q) {
+            if (q > last) break;
+            float al[W], ar[W];
+#pragma unroll
+            for (uint32_t k = 0; k < 16u; ++k) {
+                const float sl = vb[k] == q ? gl[k] : 0.0f, sr = vb[k] == q ? gr[k] : 0.0f;
+#pragma unroll
+                for (int j = 0; j < W; ++j) {
+                    const float pl = x[k][j] * sl, pr = x[k][j] * sr;
+                    al[j] = k ? al[j] + pl : pl; ar[j] = k ? ar[j] + pr : pr;
+                }
+            }
+            float *dl = s_bus + ((size_t)g * (2u * NB) + 2u * q) * TF + fl, *dr = dl + TF;
+            if (W == 4) {
+                *reinterpret_cast<f4 *>(dl) = (f4){al[0], al[1 % W], al[2 % W], al[3 % W]};
+                *reinterpret_cast<f4 *>(dr) = (f4){ar[0], ar[1 % W], ar[2 % W], ar[3 % W]};
+            } else {
+#pragma unroll
+                for (int j = 0; j < W; ++j) { dl[j] = al[j]; dr[j] = ar[j]; }
+            }
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < 2u * m.n_buses * TF; i += blockDim.x) {
+        const uint32_t c = i / TF, t = i - c * TF, f = blockIdx.x * TF + t;       // c: 2 * bus + channel
+        if (f >= m.frames) continue;
+        float acc = s_bus[c * TF + t];
+        for (uint32_t g = 1; g < n_grp; ++g) acc = acc + s_bus[((size_t)g * (2u * NB) + c) * TF + t];
+        m.partials[((size_t)b * (2u * S2R_MAX_BUSES) + c) * m.pstride + f] = acc;
+    }
+}
+
+__global__ void __launch_bounds__(256) s2r_bus_combine_kernel(const S2rBusMix m) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;    // bus i / (2 * frames); inside it frame r / 2, channel r & 1
+    const uint32_t per = 2u * m.frames, q = i / per, r = i - q * per, f = r >> 1, c = 2u * q + (r & 1u);
+    if (q >= m.n_buses) return;
+    float total = 0.0f;                                          // accum = splat(0.0), synth.rs:176
+    for (uint32_t g = 0; g < m.n_groups; ++g) {
+        const uint32_t gb0 = g * m.blocks_per_group;
+        uint32_t gb1 = gb0 + m.blocks_per_group; if (gb1 > m.n_blocks) gb1 = m.n_blocks;
+        if (gb0 >= gb1) continue;
+        float grp = 0.0f;
+        for (uint32_t r0 = gb0; r0 < gb1; r0 += kMixRun) {
+            const uint32_t r1 = r0 + kMixRun < gb1 ? r0 + kMixRun : gb1;
+            float v[kMixRun];
+#pragma unroll
+            for (uint32_t j = 0; j < kMixRun; ++j)
+                v[j] = (r0 + j < r1) ? m.partials[((size_t)(r0 + j) * (2u * S2R_MAX_BUSES) + c) * m.pstride + f] : 0.0f;
+            float acc = v[0];
+#pragma unroll
+            for (uint32_t j = 1; j < kMixRun; ++j) if (r0 + j < r1) acc = acc + v[j];
+            grp = (r0 == gb0) ? acc : grp + acc;
+        }
+        total = total + grp;
+    }
+    m.out[(size_t)q * m.ostride + r] = total;
+}
+
 // publishes the first timed event of every touched voice
 // ... and moves the records from mapped host memory into HBM in one coalesced sweep: the coefficient pass and
 // the render kernel follow per-voice chains through them, and a PCIe round trip per hop is what they cannot afford
@@ -415,5 +516,43 @@ hipError_t s2r_launch_pan_mix(const S2rPanMix &m, hipStream_t stream) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(s2r_pan_combine_kernel, dim3((2u * m.frames + 255u) / 256u), dim3(256), 0, stream, m);
+    return hipGetLastError();
+}
+
+template <int W>
+static void bus_mix_launch(const S2rBusMix &m, uint32_t nb, dim3 grid, dim3 block, size_t lds, hipStream_t stream) {
+    switch (nb) {
+    case 1: hipLaunchKernelGGL((s2r_bus_mix_kernel<W, 1>), grid, block, lds, stream, m); break;
+    case 2: hipLaunchKernelGGL((s2r_bus_mix_kernel<W, 2>), grid, block, lds, stream, m); break;
+    case 4: hipLaunchKernelGGL((s2r_bus_mix_kernel<W, 4>), grid, block, lds, stream, m); break;
+    default: hipLaunchKernelGGL((s2r_bus_mix_kernel<W, 8>), grid, block, lds, stream, m); break;
+    }
+}
+
+hipError_t s2r_launch_bus_mix(const S2rBusMix &in, hipStream_t stream) {
+    S2rBusMix m = in;
+    if (m.frames == 0 || m.n_voices == 0) return hipSuccess;
+    if (m.block_voices < 64 || m.block_voices > 1024 || (m.block_voices & 63u) || m.n_blocks * m.block_voices < m.n_voices || m.n_blocks > 65535u ||
+        m.stride < m.frames || m.pstride < m.frames || m.n_groups == 0 || m.blocks_per_group * m.n_groups < m.n_blocks ||
+        m.n_buses == 0 || m.n_buses > S2R_MAX_BUSES || m.ostride < 2u * (size_t)m.frames)
+        return hipErrorInvalidValue;
+    // 16-byte loads where every row starts on a 16-byte boundary and holds whole quads of frames; else a frame per thread
+    const bool wide = (m.stride & 3u) == 0 && (m.frames & 3u) == 0 && (reinterpret_cast<uintptr_t>(m.rows) & 15u) == 0;
+    const uint32_t w = wide ? 4u : 1u, nb = m.n_buses <= 1u ? 1u : m.n_buses <= 2u ? 2u : m.n_buses <= 4u ? 4u : 8u;
+    const uint32_t n_grp = m.block_voices / 16u;
+    // the frame tile: 32 threads along the frames, halved until the run sums of every bus fit kBusLdsBytes (256 voices: 8 buses
+    // 8 lanes, 4 buses 16, fewer 32 — 32 KiB at the most, 16 KiB for 1024 voices and 8 buses on one lane)
+    m.lanes = kPanLanes;
+    while (m.lanes > 1u && (size_t)n_grp * 2u * nb * m.lanes * w * sizeof(float) > kBusLdsBytes) m.lanes >>= 1;
+    const uint32_t tf = m.lanes * w;
+    const size_t lds = (size_t)n_grp * 2u * nb * tf * sizeof(float);
+    uint32_t threads = (n_grp * m.lanes + 63u) & ~63u;            // a thread per run and lane, whole waves, 256 at the most
+    if (threads > 256u) threads = 256u;
+    const dim3 grid((m.frames + tf - 1u) / tf, m.n_blocks);
+    if (wide) bus_mix_launch<4>(m, nb, grid, dim3(threads), lds, stream);
+    else bus_mix_launch<1>(m, nb, grid, dim3(threads), lds, stream);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(s2r_bus_combine_kernel, dim3((2u * m.frames * m.n_buses + 255u) / 256u), dim3(256), 0, stream, m);
     return hipGetLastError();
 }

@@ -353,6 +353,23 @@ struct S2rPanMix {
     float *out;                   // interleaved L, R: 2 * frames floats
 };
 
+// The bus mixdown (s2r_fill_buses): the same rows, each voice on one of n_buses stereo buses, its two gains
+// already scaled by the voice's gain; every bus and channel through the mix tree of DESIGN.md 4.3, all from one read of the rows.
+struct S2rBusMix {
+    const float *rows;            // [n_voices][stride]
+    const float *gain_l, *gain_r; // [n_blocks * block_voices] each: pan gain times voice gain, entries past n_voices hold 0
+    const uint8_t *bus;           // [n_blocks * block_voices]: the bus a voice is booked on (folded onto n_buses - 1 by the kernel)
+    uint32_t n_voices, block_voices, n_blocks;
+    uint32_t frames, stride;      // stride >= frames
+    float *partials;              // [n_blocks][S2R_MAX_BUSES][2][pstride]: the workgroups' partial rows per bus and channel
+    uint32_t pstride;             // >= frames
+    uint32_t blocks_per_group, n_groups;
+    float *out;                   // [n_buses][ostride]: bus-major, L, R interleaved inside a bus
+    size_t ostride;               // floats from one bus to the next, >= 2 * frames
+    uint32_t n_buses;             // 1 .. S2R_MAX_BUSES
+    uint32_t lanes;               // threads along the frames of a tile (set by s2r_launch_bus_mix)
+};
+
 hipError_t s2r_launch_tables(const S2rTabBuild &b, hipStream_t stream);
 hipError_t s2r_launch_noise_table(float *table_65536, hipStream_t stream);
 // one-pole single-patch handles of one workgroup only (a.p.direct_out set, a.p.frames = the longest fill): false otherwise
@@ -375,3 +392,5 @@ hipError_t s2r_launch_sum_rows(const float *rows, uint32_t n_rows, uint32_t fram
 // s2r_pan_mix_kernel (a workgroup's voices, both channels from one load of every row element) and the kernel that adds the
 // workgroups' partial rows in the documented order, rooted at +0.0
 hipError_t s2r_launch_pan_mix(const S2rPanMix &m, hipStream_t stream);
+// s2r_bus_mix_kernel (the instantiation for the call's bus count and the rows' alignment) and s2r_bus_combine_kernel
+hipError_t s2r_launch_bus_mix(const S2rBusMix &m, hipStream_t stream);

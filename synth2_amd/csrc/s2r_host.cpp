@@ -128,6 +128,7 @@ struct EventSlot {
 // mapped host memory the host polls, or reads behind a flag the device sets: coherent (fine-grained) whatever the
 // runtime's default or HIP_HOST_COHERENT say, and visible to every device of a device list
 constexpr unsigned kHostPolled = hipHostMallocMapped | hipHostMallocCoherent | hipHostMallocPortable;
+constexpr unsigned kGainsPan = 1u, kGainsBus = 2u, kGainsAll = 3u;   // s2r_synth::gains_dirty: the panned fill's device arrays, the bus fill's
 
 }  // namespace
 
@@ -273,7 +274,7 @@ struct s2r_synth {
     std::vector<float> pans;                     // [shard_voices] once pan_used
     struct PanEvent { uint32_t local, frame; float pan; };
     std::vector<PanEvent> pan_timed;             // note_ons at a frame INSIDE the next fill, in event order: their pans take effect there
-    bool gains_dirty = true;                     // pans changed since the gains were last sent to the device
+    unsigned gains_dirty = kGainsAll;            // pans or voice mixes changed since the gains were last sent to the device: kGainsPan | kGainsBus
     float *gains_host = nullptr, *gains_dev = nullptr;   // [2][padded_voices]: gL then gR (pinned / device); entries past the shard hold 0
     hipEvent_t gains_sent = nullptr;             // behind the last copy out of gains_host
     float *pan_rows = nullptr;                   // [shard_voices][pan_slice]: the voices' rows of one slice (allocated by the first panned fill)
@@ -282,6 +283,21 @@ struct s2r_synth {
     std::vector<hipEvent_t> pan_ev;              // s2r_set_timing: a pair of events around every slice's mixdown of the last panned fill
     size_t pan_ev_used = 0;
     float pan_mix_ms = -1.0f;                    // ... and their sum (tools/pan_time.py reads it through s2r_debug_pan_mix_ms)
+    // The voice mixer (s2r_fill_buses), kept exactly like the pans: level, velocity sensitivity and bus per
+    // program beside the bank; the gain and the bus every shard voice got at its note_on (local order).  Nothing of it is touched
+    // until a program mix or a voice mix is set for the first time (mix_used): until then every voice has gain 1 on bus 0.
+    std::vector<float> prog_level, prog_sens;    // one entry per bank patch
+    std::vector<uint8_t> prog_bus;
+    bool mix_used = false;
+    std::vector<float> vgain;                    // [shard_voices] once mix_used
+    std::vector<uint8_t> vbus;
+    struct MixEvent { uint32_t local, frame; float gain; uint8_t bus; };
+    std::vector<MixEvent> mix_timed;             // like pan_timed
+    char *bus_gains_host = nullptr, *bus_gains_dev = nullptr;    // [2][padded_voices] floats: gL * w, gR * w; then [padded_voices] bus bytes
+    hipEvent_t bus_gains_sent = nullptr;
+    float *bus_partials = nullptr;               // [n_blocks][S2R_MAX_BUSES][2][pan_slice], allocated by the first bus fill
+    float *bus_out = nullptr, *bus_out_dev = nullptr;            // pinned and device-mapped: S2R_MAX_BUSES * 2 * max_frames floats
+    float bus_mix_ms = -1.0f;                    // pan_mix_ms of the last s2r_fill_buses (tools/bus_time.py)
     float pitch_table[256];
     hipEvent_t t0 = nullptr, t1 = nullptr;
     bool timing = false, timed = false, no_flat_shortcut = false;
@@ -1583,7 +1599,7 @@ inline bool pan_in_range(float x) { return x >= -1.0f && x <= 1.0f; }          /
 void pan_begin(s2r_synth *s) {
     if (s->pan_used) return;
     s->pans.assign(s->shard_voices, 0.0f);
-    s->pan_used = true; s->gains_dirty = true;
+    s->pan_used = true; s->gains_dirty = kGainsAll;
 }
 
 // Pans of note_ons that had a frame inside a fill which has been rendered since (by any fill: fill_time is back at 0) are the
@@ -1592,19 +1608,19 @@ void pan_settle(s2r_synth *s) {
     if (s->pan_timed.empty() || s->fill_time != 0) return;
     for (const s2r_synth::PanEvent &e : s->pan_timed) s->pans[e.local] = e.pan;
     s->pan_timed.clear();
-    s->gains_dirty = true;
+    s->gains_dirty = kGainsAll;
 }
 
 // a note_on took shard voice `local` (the caller has settled): the pan of the program in force, now or at its frame
 inline void pan_note_on(s2r_synth *s, uint32_t local, uint8_t note, uint32_t frame) {
     const float p = s2r_voice_pan(s->prog_pan[s->program], s->prog_spread[s->program], note);
-    if (frame == 0) { s->pans[local] = p; s->gains_dirty = true; }
+    if (frame == 0) { s->pans[local] = p; s->gains_dirty = kGainsAll; }
     else s->pan_timed.push_back(s2r_synth::PanEvent{local, frame, p});
 }
 
 // the gains of the voices' pans, from pinned memory to the device on the handle's stream (when a pan changed)
 int pan_send_gains(s2r_synth *s) {
-    if (!s->gains_dirty) return S2R_OK;
+    if (!(s->gains_dirty & kGainsPan)) return S2R_OK;
     const size_t pv = s->padded_voices;
     if (!s->gains_host) {
         S2R_HIP(s, hipHostMalloc((void **)&s->gains_host, 2 * pv * sizeof(float), hipHostMallocDefault));
@@ -1615,15 +1631,66 @@ int pan_send_gains(s2r_synth *s) {
     for (uint32_t i = 0; i < s->shard_voices; i++) s2r_pan_gains(s->pan_used ? s->pans[i] : 0.0f, s->gains_host + i, s->gains_host + pv + i);
     S2R_HIP(s, hipMemcpyAsync(s->gains_dev, s->gains_host, 2 * pv * sizeof(float), hipMemcpyHostToDevice, s->stream));
     S2R_HIP(s, hipEventRecord(s->gains_sent, s->stream));
-    s->gains_dirty = false;
+    s->gains_dirty &= ~kGainsPan;
     return S2R_OK;
 }
 
-// Frames [at, at + n) of a panned fill, the events of frame `at` already folded into `pending`: slice after slice the MODE 1
-// launch into the rows buffer and the panned mixdown into the mapped output.  `last_event`: the frame the pool's clock has
-// already been moved to by the fill's events (fill_time at entry) — the slices from there on move it further.
-int pan_segment(s2r_synth *s, uint32_t at, uint32_t n, uint32_t last_event, uint32_t sample_rate) {
-    int rc = pan_send_gains(s);
+// ---- the voice mixer: the pans' bookkeeping once more, for the gain and the bus of every voice ----
+inline bool unit_in_range(float x) { return x >= 0.0f && x <= 1.0f; }           // (false for NaN)
+
+void mix_begin(s2r_synth *s) {
+    if (s->mix_used) return;
+    s->vgain.assign(s->shard_voices, 1.0f);
+    s->vbus.assign(s->shard_voices, 0u);
+    s->mix_used = true; s->gains_dirty = kGainsAll;
+}
+
+void mix_settle(s2r_synth *s) {
+    if (s->mix_timed.empty() || s->fill_time != 0) return;
+    for (const s2r_synth::MixEvent &e : s->mix_timed) { s->vgain[e.local] = e.gain; s->vbus[e.local] = e.bus; }
+    s->mix_timed.clear();
+    s->gains_dirty = kGainsAll;
+}
+
+inline void mix_note_on(s2r_synth *s, uint32_t local, float velocity, uint32_t frame) {
+    const float w = s2r_voice_gain(s->prog_level[s->program], s->prog_sens[s->program], velocity);
+    const uint8_t bus = s->prog_bus[s->program];
+    if (frame == 0) { s->vgain[local] = w; s->vbus[local] = bus; s->gains_dirty = kGainsAll; }
+    else s->mix_timed.push_back(s2r_synth::MixEvent{local, frame, w, bus});
+}
+
+// what the bus mixdown reads per voice — both pan gains times the voice's gain (one rounded multiply each) and the bus byte — from
+// pinned memory to the device on the handle's stream (when a pan or a mix changed)
+int bus_send_gains(s2r_synth *s) {
+    if (!(s->gains_dirty & kGainsBus)) return S2R_OK;
+    const size_t pv = s->padded_voices, bytes = pv * (2 * sizeof(float) + 1);
+    if (!s->bus_gains_host) {
+        S2R_HIP(s, hipHostMalloc((void **)&s->bus_gains_host, bytes, hipHostMallocDefault));
+        std::memset(s->bus_gains_host, 0, bytes);
+        S2R_HIP(s, hipMalloc((void **)&s->bus_gains_dev, bytes));
+        S2R_HIP(s, hipEventCreateWithFlags(&s->bus_gains_sent, hipEventDisableTiming));
+    } else S2R_HIP(s, hipEventSynchronize(s->bus_gains_sent));
+    float *g = reinterpret_cast<float *>(s->bus_gains_host);
+    uint8_t *b = reinterpret_cast<uint8_t *>(s->bus_gains_host + 2 * pv * sizeof(float));
+    for (uint32_t i = 0; i < s->shard_voices; i++) {
+        float gl, gr;
+        s2r_pan_gains(s->pan_used ? s->pans[i] : 0.0f, &gl, &gr);
+        const float w = s->mix_used ? s->vgain[i] : 1.0f;
+        g[i] = gl * w; g[pv + i] = gr * w;
+        b[i] = s->mix_used ? s->vbus[i] : (uint8_t)0;
+    }
+    S2R_HIP(s, hipMemcpyAsync(s->bus_gains_dev, s->bus_gains_host, bytes, hipMemcpyHostToDevice, s->stream));
+    S2R_HIP(s, hipEventRecord(s->bus_gains_sent, s->stream));
+    s->gains_dirty &= ~kGainsBus;
+    return S2R_OK;
+}
+
+// Frames [at, at + n) of a panned fill (n_buses == 0) or of a bus fill of `total` frames, the events of frame `at` already folded
+// into `pending`: slice after slice the MODE 1 launch into the rows buffer and the mixdown into the mapped output.  `last_event`:
+// the frame the pool's clock has already been moved to by the fill's events (fill_time at entry) — the slices from there on move
+// it further.
+int pan_segment(s2r_synth *s, uint32_t at, uint32_t n, uint32_t last_event, uint32_t sample_rate, uint32_t n_buses, uint32_t total) {
+    int rc = n_buses ? bus_send_gains(s) : pan_send_gains(s);
     if (rc != S2R_OK) return rc;
     for (uint32_t done = 0; done < n;) {
         const uint32_t len = n - done < s->pan_slice ? n - done : s->pan_slice;
@@ -1641,7 +1708,19 @@ int pan_segment(s2r_synth *s, uint32_t at, uint32_t n, uint32_t last_event, uint
             while (s->pan_ev.size() < s->pan_ev_used + 2) { hipEvent_t e; S2R_HIP(s, hipEventCreate(&e)); s->pan_ev.push_back(e); }
             S2R_HIP(s, hipEventRecord(s->pan_ev[s->pan_ev_used], s->stream));
         }
-        S2R_HIP(s, s2r_launch_pan_mix(m, s->stream));
+        if (n_buses) {
+            S2rBusMix bm{};
+            const float *g = reinterpret_cast<const float *>(s->bus_gains_dev);
+            bm.rows = m.rows; bm.gain_l = g; bm.gain_r = g + s->padded_voices;
+            bm.bus = reinterpret_cast<const uint8_t *>(g + 2 * (size_t)s->padded_voices);
+            bm.n_voices = m.n_voices; bm.block_voices = m.block_voices; bm.n_blocks = m.n_blocks;
+            bm.frames = len; bm.stride = len;
+            bm.partials = s->bus_partials; bm.pstride = s->pan_slice;
+            bm.n_groups = m.n_groups; bm.blocks_per_group = m.blocks_per_group;
+            bm.out = s->bus_out_dev + 2u * (size_t)(at + done); bm.ostride = 2u * (size_t)total;
+            bm.n_buses = n_buses;
+            S2R_HIP(s, s2r_launch_bus_mix(bm, s->stream));
+        } else S2R_HIP(s, s2r_launch_pan_mix(m, s->stream));
         if (s->timing) { S2R_HIP(s, hipEventRecord(s->pan_ev[s->pan_ev_used + 1], s->stream)); s->pan_ev_used += 2; }
         done += len;
     }
@@ -1749,6 +1828,11 @@ void release_all(s2r_synth *s) {
     if (s->gains_sent) (void)hipEventDestroy(s->gains_sent);
     if (s->pan_rows) (void)hipFree(s->pan_rows);
     if (s->pan_partials) (void)hipFree(s->pan_partials);
+    if (s->bus_gains_host) (void)hipHostFree(s->bus_gains_host);
+    if (s->bus_gains_dev) (void)hipFree(s->bus_gains_dev);
+    if (s->bus_gains_sent) (void)hipEventDestroy(s->bus_gains_sent);
+    if (s->bus_partials) (void)hipFree(s->bus_partials);
+    if (s->bus_out) (void)hipHostFree(s->bus_out);
     for (hipEvent_t e : s->pan_ev) (void)hipEventDestroy(e);
     if (s->voice_ev_head) (void)hipFree(s->voice_ev_head);
     if (s->tev_copy) (void)hipFree(s->tev_copy);
@@ -1854,6 +1938,7 @@ static int create_single(const s2r_config *cfg, std::shared_ptr<S2rVoicePool> po
     s->parent = parent;
     s->bank.resize(1);
     s->prog_pan.assign(1, 0.0f); s->prog_spread.assign(1, 0.0f);
+    s->prog_level.assign(1, 1.0f); s->prog_sens.assign(1, 0.0f); s->prog_bus.assign(1, 0u);
     s2r_default_patch(&s->bank[0]);
     if (pool) s->pool = pool;
     else { s->pool.reset(new S2rVoicePool(cfg->total_voices)); s->seed_override.assign(cfg->total_voices, 0u); configure_policy_threads(s->pool.get(), cfg->total_voices); }
@@ -2106,6 +2191,7 @@ int s2r_set_patch_bank(s2r_synth *s, const s2r_patch *patches, uint32_t n) {
     S2R_QUIESCE(s);
     s->bank.assign(patches, patches + n);
     s->prog_pan.resize(n, 0.0f); s->prog_spread.resize(n, 0.0f);   // the surviving programs keep their pans
+    s->prog_level.resize(n, 1.0f); s->prog_sens.resize(n, 0.0f); s->prog_bus.resize(n, 0u);      // ... and their mix
     if (s->program >= n) s->program = 0;
     s->bank_dirty = true; s->tab_dirty = true;
     for (s2r_synth *kid : s->kids) { kid->bank = s->bank; kid->bank_dirty = true; kid->tab_dirty = true; }
@@ -2155,10 +2241,10 @@ int s2r_note_on_ex(s2r_synth *s, uint8_t note, float velocity, uint32_t *voice_i
     const uint32_t i = s->pool->note_on(note, velocity);
     if (voice_index_out) *voice_index_out = i;
     if (s->voice_log) s->voice_log(s->voice_log_user, i, note);
-    if (s->pan_used && s->kids.empty()) {
-        pan_settle(s);
+    if ((s->pan_used | s->mix_used) && s->kids.empty()) {
         const int64_t mine = to_local(s, i);
-        if (mine >= 0) pan_note_on(s, (uint32_t)mine, note, 0u);
+        if (s->pan_used) { pan_settle(s); if (mine >= 0) pan_note_on(s, (uint32_t)mine, note, 0u); }
+        if (s->mix_used) { mix_settle(s); if (mine >= 0) mix_note_on(s, (uint32_t)mine, velocity, 0u); }
     }
     if (!append_frame0_record(s, i, S2R_EV_RESTART, s->pitch_table[note], s->seed_override[i], s->program))
         push_event(s, i, S2R_EV_RESTART, s->pitch_table[note], s->seed_override[i], s->program);
@@ -2206,7 +2292,7 @@ int s2r_note_events(s2r_synth *s, const s2r_note_event *events, size_t n) {
     // and note_off over the events computes — on several threads for a multi-GPU-sized batch): the voice every event takes or
     // releases.  An event inside the next fill first moves the pool's clock to its frame (the policy sees the offsets every
     // voice has AT that frame, like the reference between two 16-frame calls); frame-0 events take effect before the fill.
-    if (s->pan_used) pan_settle(s);                              // (while fill_time still says whether the last fill's events are behind us)
+    if (s->pan_used | s->mix_used) { pan_settle(s); mix_settle(s); }      // (while fill_time still says whether the last fill's events are behind us)
     static thread_local std::vector<int64_t> chosen;
     if (chosen.size() < n) chosen.resize(n);
     static_assert(sizeof(S2rPolicyEvent) == 4 && S2R_NOTE_ON == S2R_POLICY_NOTE_ON && S2R_NOTE_OFF == S2R_POLICY_NOTE_OFF, "s2r_note_event's first four bytes");
@@ -2247,7 +2333,10 @@ int s2r_note_events(s2r_synth *s, const s2r_note_event *events, size_t n) {
         }
         const uint32_t frame = e.frame;
         const bool on = e.kind == S2R_NOTE_ON;
-        if (on && one && one->pan_used) pan_note_on(one, local, e.note, frame);
+        if (on && one && (one->pan_used | one->mix_used)) {
+            if (one->pan_used) pan_note_on(one, local, e.note, frame);
+            if (one->mix_used) mix_note_on(one, local, e.velocity, frame);
+        }
         if (frame == 0 && may_fold && sh->tpending.empty()) {
             if (on) push_event(s, (uint32_t)vi, S2R_EV_RESTART, pitch_of[e.note], seed_of[(size_t)vi], s->program);
             else push_event(s, (uint32_t)vi, S2R_EV_RELEASE, 0.0f, 0u);
@@ -2381,19 +2470,22 @@ int s2r_set_voice_pans(s2r_synth *s, const float *pans) {
     pan_begin(s);
     pan_settle(s);
     std::memcpy(s->pans.data(), pans, (size_t)s->shard_voices * sizeof(float));
-    s->gains_dirty = true;
+    s->gains_dirty = kGainsAll;
     return S2R_OK;
 }
 
-int s2r_fill_panned(s2r_synth *s, float *interleaved_lr_out, size_t frames, uint32_t sample_rate_hz) {
+// s2r_fill_panned (n_buses == 0: two channels into `out`) and s2r_fill_buses (n_buses stereo buses, bus-major, `capacity` floats)
+static int fill_rows_mixed(s2r_synth *s, float *out, size_t capacity, uint32_t n_buses, size_t frames, uint32_t sample_rate_hz, const char *who) {
     if (!s) return S2R_ERR_INVALID;
-    if (!s->kids.empty() || s->parent) return set_err(s, S2R_ERR_INVALID, "s2r_fill_panned takes a single-device handle, not a device list");
-    if (s->xg_on) return set_err(s, S2R_ERR_INVALID, "s2r_fill_panned takes a handle without an exchange attached");
+    if (!s->kids.empty() || s->parent) return set_err(s, S2R_ERR_INVALID, "%s takes a single-device handle, not a device list", who);
+    if (s->xg_on) return set_err(s, S2R_ERR_INVALID, "%s takes a handle without an exchange attached", who);
     int rc = check_fill(s, frames, sample_rate_hz);
     if (rc != S2R_OK) return rc;
     if (frames == 0) return S2R_OK;
-    if (!interleaved_lr_out) return set_err(s, S2R_ERR_INVALID, "null output buffer");
-    if (s->ring_count) return set_err(s, S2R_ERR_INVALID, "s2r_fill_panned with fills of s2r_fill_begin in flight: s2r_fill_end first");
+    if (!out) return set_err(s, S2R_ERR_INVALID, "null output buffer");
+    if (n_buses && capacity < 2 * frames * n_buses)
+        return set_err(s, S2R_ERR_INVALID, "%s: %u buses of %zu frames take %zu floats, the buffer holds %zu", who, n_buses, frames, 2 * frames * n_buses, capacity);
+    if (s->ring_count) return set_err(s, S2R_ERR_INVALID, "%s with fills of s2r_fill_begin in flight: s2r_fill_end first", who);
     S2R_QUIESCE(s);
     S2R_HIP(s, hipSetDevice(s->device));
     if (!s->pan_rows) {
@@ -2405,16 +2497,22 @@ int s2r_fill_panned(s2r_synth *s, float *interleaved_lr_out, size_t frames, uint
         const uint32_t whole = (s->cfg.max_frames + 15u) & ~15u;
         if (slice < 16u) slice = 16u;
         if (slice > whole) slice = whole;
-        S2R_HIP(s, hipMalloc((void **)&s->pan_partials, (size_t)s->n_blocks * 2u * slice * sizeof(float)));
         S2R_HIP(s, hipMalloc((void **)&s->pan_rows, (size_t)s->shard_voices * slice * sizeof(float)));
         s->pan_slice = slice;
     }
+    // the workgroups' partial rows of the mixdown asked for (and the bus fill's pinned output), once each
+    if (!n_buses && !s->pan_partials) S2R_HIP(s, hipMalloc((void **)&s->pan_partials, (size_t)s->n_blocks * 2u * s->pan_slice * sizeof(float)));
+    if (n_buses && !s->bus_partials) S2R_HIP(s, hipMalloc((void **)&s->bus_partials, (size_t)s->n_blocks * 2u * S2R_MAX_BUSES * s->pan_slice * sizeof(float)));
+    if (n_buses && !s->bus_out) {
+        S2R_HIP(s, hipHostMalloc((void **)&s->bus_out, (size_t)2 * S2R_MAX_BUSES * s->cfg.max_frames * sizeof(float), kHostPolled));
+        S2R_HIP(s, hipHostGetDevicePointer((void **)&s->bus_out_dev, s->bus_out, 0));
+    }
     fold_frame0_records(s);
-    if (s->pan_used) pan_settle(s);
+    pan_settle(s); mix_settle(s);
     s->pan_ev_used = 0;
     const uint32_t last_event = s->fill_time;
     if (s->tpending.empty()) {
-        rc = pan_segment(s, 0u, (uint32_t)frames, last_event, sample_rate_hz);
+        rc = pan_segment(s, 0u, (uint32_t)frames, last_event, sample_rate_hz, n_buses, (uint32_t)frames);
         if (rc != S2R_OK) return rc;
     } else {
         // Events inside the fill: the per-voice rows and the event chains exclude each other in the render kernels, and an
@@ -2426,7 +2524,9 @@ int s2r_fill_panned(s2r_synth *s, float *interleaved_lr_out, size_t frames, uint
         for (const S2rTimedEvent &te : recs) s->tlast[te.voice] = -1;
         std::vector<s2r_synth::PanEvent> pev;
         pev.swap(s->pan_timed);
-        size_t k = 0, kp = 0;
+        std::vector<s2r_synth::MixEvent> mev;
+        mev.swap(s->mix_timed);
+        size_t k = 0, kp = 0, km = 0;
         uint32_t at = 0;
         while (at < frames) {
             for (; k < recs.size() && recs[k].frame <= at; k++) {
@@ -2441,20 +2541,88 @@ int s2r_fill_panned(s2r_synth *s, float *interleaved_lr_out, size_t frames, uint
                 if (te.flags & S2R_EV_RESTART) { e.flags = S2R_EV_RESTART | (te.program << S2R_EV_PROGRAM_SHIFT); e.pitch = te.pitch; e.seed = te.seed; }
                 if (te.flags & S2R_EV_RELEASE) e.flags |= S2R_EV_RELEASE;
             }
-            for (; kp < pev.size() && pev[kp].frame <= at; kp++) { s->pans[pev[kp].local] = pev[kp].pan; s->gains_dirty = true; }
+            for (; kp < pev.size() && pev[kp].frame <= at; kp++) { s->pans[pev[kp].local] = pev[kp].pan; s->gains_dirty = kGainsAll; }
             const uint32_t next = k < recs.size() && recs[k].frame < frames ? recs[k].frame : (uint32_t)frames;
-            rc = pan_segment(s, at, next - at, last_event, sample_rate_hz);
+            for (; km < mev.size() && mev[km].frame <= at; km++) { s->vgain[mev[km].local] = mev[km].gain; s->vbus[mev[km].local] = mev[km].bus; s->gains_dirty = kGainsAll; }
+            rc = pan_segment(s, at, next - at, last_event, sample_rate_hz, n_buses, (uint32_t)frames);
             if (rc != S2R_OK) { s->fill_time = 0; return rc; }
             at = next;
         }
     }
     S2R_HIP(s, hipStreamSynchronize(s->stream));
-    std::memcpy(interleaved_lr_out, s->out_host, 2 * frames * sizeof(float));
+    if (n_buses) std::memcpy(out, s->bus_out, 2 * frames * n_buses * sizeof(float));
+    else std::memcpy(out, s->out_host, 2 * frames * sizeof(float));
     if (s->timing) {
-        s->pan_mix_ms = 0.0f;
-        for (size_t k = 0; k < s->pan_ev_used; k += 2) { float ms = 0.0f; S2R_HIP(s, hipEventElapsedTime(&ms, s->pan_ev[k], s->pan_ev[k + 1])); s->pan_mix_ms += ms; }
+        float sum = 0.0f;
+        for (size_t k = 0; k < s->pan_ev_used; k += 2) { float ms = 0.0f; S2R_HIP(s, hipEventElapsedTime(&ms, s->pan_ev[k], s->pan_ev[k + 1])); sum += ms; }
+        (n_buses ? s->bus_mix_ms : s->pan_mix_ms) = sum;
     }
     return S2R_OK;
+}
+
+int s2r_fill_panned(s2r_synth *s, float *interleaved_lr_out, size_t frames, uint32_t sample_rate_hz) {
+    return fill_rows_mixed(s, interleaved_lr_out, 0, 0u, frames, sample_rate_hz, "s2r_fill_panned");
+}
+
+// ---- the voice mixer ----
+float s2r_voice_gain(float level, float velocity_sens, float velocity) {
+    float u = velocity < 1.0f ? velocity : 1.0f;                 // NaN -> 1
+    u = u > 0.0f ? u : 0.0f;
+    const float d = 1.0f - u;
+    const float t = velocity_sens * d;                           // (-ffp-contract=off: rounded before the difference)
+    const float a = 1.0f - t;
+    return level * a;
+}
+
+int s2r_set_program_mix(s2r_synth *s, uint32_t program, float level, float velocity_sens, uint32_t bus) {
+    // (the values first, like s2r_set_program_pan)
+    if (!unit_in_range(level) || !unit_in_range(velocity_sens) || bus >= S2R_MAX_BUSES)
+        return set_err(s, S2R_ERR_PATCH_RANGE, "program %u: level %g, velocity_sens %g, bus %u: both values lie in [0, 1], the bus below %u", program,
+                       (double)level, (double)velocity_sens, bus, S2R_MAX_BUSES);
+    if (!s) return S2R_ERR_INVALID;
+    if (program >= s->bank.size()) return set_err(s, S2R_ERR_INVALID, "program %u: the bank holds %zu patches", program, s->bank.size());
+    if (level != 1.0f || velocity_sens != 0.0f || bus != 0u) { mix_begin(s); mix_settle(s); }
+    s->prog_level[program] = level; s->prog_sens[program] = velocity_sens; s->prog_bus[program] = (uint8_t)bus;
+    return S2R_OK;
+}
+
+int s2r_get_program_mix(const s2r_synth *s, uint32_t program, float *level, float *velocity_sens, uint32_t *bus) {
+    if (!s) return S2R_ERR_INVALID;
+    if (program >= s->bank.size()) return S2R_ERR_INVALID;
+    if (level) *level = s->prog_level[program];
+    if (velocity_sens) *velocity_sens = s->prog_sens[program];
+    if (bus) *bus = s->prog_bus[program];
+    return S2R_OK;
+}
+
+int s2r_get_voice_mix(s2r_synth *s, float *gains, uint8_t *buses) {
+    if (!s || !gains || !buses) return S2R_ERR_INVALID;
+    if (!s->kids.empty()) return set_err(s, S2R_ERR_INVALID, "voice mixes are kept by single-device handles, not by a device list");
+    if (!s->mix_used) { std::fill(gains, gains + s->shard_voices, 1.0f); std::memset(buses, 0, s->shard_voices); return S2R_OK; }
+    mix_settle(s);
+    std::memcpy(gains, s->vgain.data(), (size_t)s->shard_voices * sizeof(float));
+    std::memcpy(buses, s->vbus.data(), (size_t)s->shard_voices);
+    return S2R_OK;
+}
+
+int s2r_set_voice_mix(s2r_synth *s, const float *gains, const uint8_t *buses) {
+    if (!s || !gains || !buses) return S2R_ERR_INVALID;
+    if (!s->kids.empty()) return set_err(s, S2R_ERR_INVALID, "voice mixes are kept by single-device handles, not by a device list");
+    for (uint32_t i = 0; i < s->shard_voices; i++)
+        if (!unit_in_range(gains[i]) || buses[i] >= S2R_MAX_BUSES)
+            return set_err(s, S2R_ERR_PATCH_RANGE, "voice %u: gain %g, bus %u: the gain lies in [0, 1], the bus below %u", i, (double)gains[i], (unsigned)buses[i], S2R_MAX_BUSES);
+    mix_begin(s);
+    mix_settle(s);
+    std::memcpy(s->vgain.data(), gains, (size_t)s->shard_voices * sizeof(float));
+    std::memcpy(s->vbus.data(), buses, (size_t)s->shard_voices);
+    s->gains_dirty = kGainsAll;
+    return S2R_OK;
+}
+
+int s2r_fill_buses(s2r_synth *s, float *out, size_t capacity, uint32_t n_buses, size_t frames, uint32_t sample_rate_hz) {
+    if (!s) return S2R_ERR_INVALID;
+    if (n_buses == 0 || n_buses > S2R_MAX_BUSES) return set_err(s, S2R_ERR_INVALID, "s2r_fill_buses: %u buses (1 .. %u)", n_buses, S2R_MAX_BUSES);
+    return fill_rows_mixed(s, out, capacity, n_buses, frames, sample_rate_hz, "s2r_fill_buses");
 }
 
 int s2r_fill_oversampled(s2r_synth *s, float *mono_out, size_t frames, uint32_t sample_rate_hz) {
@@ -2883,6 +3051,8 @@ const char *s2r_last_error(const s2r_synth *s) { return s ? s->err.c_str() : "nu
 // slices, in milliseconds (s2r_set_timing on; < 0 otherwise); and the frames per slice of the rows buffer (0: not allocated yet)
 extern "C" float s2r_debug_pan_mix_ms(const s2r_synth *s) { return s && s->timing ? s->pan_mix_ms : -1.0f; }
 extern "C" uint32_t s2r_debug_pan_slice(const s2r_synth *s) { return s ? s->pan_slice : 0u; }
+// ... and of the bus mixdown's kernels in the last s2r_fill_buses (tools/bus_time.py)
+extern "C" float s2r_debug_bus_mix_ms(const s2r_synth *s) { return s && s->timing ? s->bus_mix_ms : -1.0f; }
 
 extern "C" uint32_t s2r_debug_read_stamps(s2r_synth *s, unsigned long long *out, uint32_t max_waves) {
 #if defined(S2R_STAMPS)

@@ -33,6 +33,7 @@ S2R_ERR_PATCH_RANGE = -5
 S2R_ERR_TOO_MANY_FRAMES = -6
 S2R_ERR_OFFSET_OVERFLOW = -7
 S2R_ERR_OUT_OF_MEMORY = -8
+MAX_BUSES = 8                               # S2R_MAX_BUSES
 
 
 class S2rError(RuntimeError):
@@ -171,6 +172,12 @@ def load_library():
         "s2r_fill_panned": (C.c_int, [H, _f32p, C.c_size_t, C.c_uint32]),
         "s2r_voice_pan": (C.c_float, [C.c_float, C.c_float, C.c_uint8]),
         "s2r_pan_gains": (None, [C.c_float, _f32p, _f32p]),
+        "s2r_set_program_mix": (C.c_int, [H, C.c_uint32, C.c_float, C.c_float, C.c_uint32]),
+        "s2r_get_program_mix": (C.c_int, [H, C.c_uint32, _f32p, _f32p, C.POINTER(C.c_uint32)]),
+        "s2r_get_voice_mix": (C.c_int, [H, _f32p, C.POINTER(C.c_uint8)]),
+        "s2r_set_voice_mix": (C.c_int, [H, _f32p, C.POINTER(C.c_uint8)]),
+        "s2r_voice_gain": (C.c_float, [C.c_float, C.c_float, C.c_float]),
+        "s2r_fill_buses": (C.c_int, [H, _f32p, C.c_size_t, C.c_uint32, C.c_size_t, C.c_uint32]),
         "s2r_fill_device": (C.c_int, [H, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
         "s2r_fill_device_root": (C.c_int, [H, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
         "s2r_sum_partials_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_size_t, C.c_void_p, C.c_void_p]),
@@ -246,6 +253,11 @@ def pan_gains(p):
     gl, gr = C.c_float(), C.c_float()
     load_library().s2r_pan_gains(float(p), C.byref(gl), C.byref(gr))
     return gl.value, gr.value
+
+
+def voice_gain(level, velocity_sens, velocity):
+    """the gain a note_on of `velocity` gives its voice under a program's level and velocity sensitivity (s2r_voice_gain; host only)"""
+    return float(load_library().s2r_voice_gain(float(level), float(velocity_sens), float(velocity)))
 
 
 def stream_frame_json(samples):
@@ -460,6 +472,36 @@ class Synth:
         out = np.empty(2 * frames, dtype=np.float32)
         self._check(self.L.s2r_fill_panned(self.h, out.ctypes.data_as(_f32p), frames, int(sample_rate)))
         return out.reshape(frames, 2)
+
+    # --- the voice mixer (build-defined; s2r.h: s2r_fill_buses) ---
+    def set_program_mix(self, program, level=1.0, velocity_sens=0.0, bus=0):
+        """level and velocity sensitivity (both in [0, 1]) and output bus (below MAX_BUSES) of a bank program: what a note_on under
+        that program gives its voice.  Only sample_buses applies them."""
+        self._check(self.L.s2r_set_program_mix(self.h, int(program), float(level), float(velocity_sens), int(bus)))
+
+    def get_program_mix(self, program):
+        level, sens, bus = C.c_float(), C.c_float(), C.c_uint32()
+        self._check(self.L.s2r_get_program_mix(self.h, int(program), C.byref(level), C.byref(sens), C.byref(bus)))
+        return level.value, sens.value, bus.value
+
+    def voice_mix(self):
+        """(gains float32, buses uint8) of every shard voice, local order (checkpoint companions of export_state and voice_pans)"""
+        gains = np.empty(self.shard_voices, dtype=np.float32)
+        buses = np.empty(self.shard_voices, dtype=np.uint8)
+        self._check(self.L.s2r_get_voice_mix(self.h, gains.ctypes.data_as(_f32p), buses.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return gains, buses
+
+    def set_voice_mix(self, gains, buses):
+        g = np.ascontiguousarray(gains, dtype=np.float32)
+        b = np.ascontiguousarray(buses, dtype=np.uint8)
+        assert g.size == self.shard_voices and b.size == self.shard_voices
+        self._check(self.L.s2r_set_voice_mix(self.h, g.ctypes.data_as(_f32p), b.ctypes.data_as(C.POINTER(C.c_uint8))))
+
+    def sample_buses(self, frames, sample_rate=SampleRateKhz(48000), n_buses=1):
+        """the panned mixdown onto n_buses stereo buses from one render pass: (n_buses, frames, 2) float32"""
+        out = np.empty(2 * frames * max(int(n_buses), 0), dtype=np.float32)
+        self._check(self.L.s2r_fill_buses(self.h, out.ctypes.data_as(_f32p), out.size, int(n_buses), frames, int(sample_rate)))
+        return out.reshape(n_buses, frames, 2)
 
     def render_voices(self, frames, sample_rate=SampleRateKhz(48000)):
         """Mix disabled: (shard_voices, frames) float32."""
