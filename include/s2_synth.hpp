@@ -105,6 +105,16 @@ class Synth {
     // host only: the gain a note_on of `velocity` gives its voice
     static float voice_gain(float level, float velocity_sens, float velocity) { return s2r_voice_gain(level, velocity_sens, velocity); }
 
+    // live program faders (build-defined; s2r.h: s2r_set_program_fader): a fader and a pan shift per bank program that act on
+    // every voice sounding on it and reach their target as a ramp across the next sample_buses call
+    void set_program_fader(uint32_t program, float fader, float pan_shift = 0.0f) { check(s2r_set_program_fader(h_, program, fader, pan_shift)); }
+    void get_program_fader(uint32_t program, float *fader, float *pan_shift, float *applied_fader = nullptr, float *applied_pan_shift = nullptr) const {
+        check(s2r_get_program_fader(h_, program, fader, pan_shift, applied_fader, applied_pan_shift));
+    }
+    void snap_program_faders() { check(s2r_snap_program_faders(h_)); }
+    // host only: the two gains of a voice with pan `pan` and gain `w` under a fader pair
+    static void fader_gains(float pan, float w, float fader, float pan_shift, float *gl, float *gr) { s2r_fader_gains(pan, w, fader, pan_shift, gl, gr); }
+
     s2r_synth *handle() { return h_; }
 
   private:

@@ -33,7 +33,8 @@ extern "C" {
  * s2r_set_low_latency, s2r_low_latency_active, s2r_build_id, s2r_set_resident, s2r_resident_active, s2r_quiesce,
  * s2r_exchange_create, s2r_exchange_attach, s2r_voice_pool_set_threads, s2r_voice_pool_resolve, s2r_set_program_pan,
  * s2r_get_program_pan, s2r_get_voice_pans, s2r_set_voice_pans, s2r_fill_panned, s2r_voice_pan, s2r_pan_gains,
- * s2r_set_program_mix, s2r_get_program_mix, s2r_get_voice_mix, s2r_set_voice_mix, s2r_voice_gain, s2r_fill_buses. */
+ * s2r_set_program_mix, s2r_get_program_mix, s2r_get_voice_mix, s2r_set_voice_mix, s2r_voice_gain, s2r_fill_buses,
+ * s2r_set_program_fader, s2r_get_program_fader, s2r_snap_program_faders, s2r_fader_gains. */
 #define S2R_ABI_VERSION 4
 
 typedef enum {
@@ -256,7 +257,7 @@ int s2r_fill_panned(s2r_synth *s, float *interleaved_lr_out, size_t frames, uint
  * [0, S2R_MAX_BUSES) (default 0), held beside the bank like pan / key_spread (not in s2r_patch).  A note_on gives its voice the
  * gain w = s2r_voice_gain(level, velocity_sens, velocity) and the bus of the program current at that note_on (a
  * S2R_PROGRAM_CHANGE inside a batch included; an event inside a fill takes effect at its frame, as its pan does); the voice keeps
- * both until it is restarted; a voice never started has w = 1 and bus 0; changing a program's mix affects later note_ons only.
+ * both until it is restarted; a voice never started has w = 1 and bus 0; changing a program's mix affects later note_ons only (the program FADERS below reach sounding voices).
  * With the defaults w == 1.0f exactly.  s2r_set_patch_bank keeps the values of the programs that survive and gives new ones the
  * defaults.
  * ONLY s2r_fill_buses applies them: s2r_fill, s2r_fill_stereo, s2r_fill_panned, s2r_fill_oversampled, s2r_fill_begin / _end,
@@ -284,6 +285,33 @@ int s2r_get_program_mix(const s2r_synth *s, uint32_t program, float *level, floa
 int s2r_get_voice_mix(s2r_synth *s, float *gains, uint8_t *buses);
 int s2r_set_voice_mix(s2r_synth *s, const float *gains, const uint8_t *buses);
 int s2r_fill_buses(s2r_synth *s, float *out, size_t capacity, uint32_t n_buses, size_t frames, uint32_t sample_rate_hz);
+
+/* BUILD-DEFINED live program faders (the reference has none; DESIGN.md 4.14 gives the op sequence): the mixer's channel volume
+ * and pan control (MIDI CC7 / CC11 / CC10).  Every program of the bank has a `fader` in [0, 1] (default 1) and a `pan_shift` in
+ * [-2, 2] (default 0; 2 takes a hard-left voice hard right), held beside the bank like level / pan, in two copies: the TARGET
+ * the caller last set and the APPLIED pair where the last bus fill left it (both (1, 0) on a fresh handle).  They act on every
+ * voice SOUNDING on the program — a voice follows the program it was started with (s2r_voice_state.program), not the current
+ * one; a voice whose program lies past a later, smaller bank follows program 0, as it renders with patch 0 — and they move as a
+ * ramp across ONE s2r_fill_buses call of N frames: with (G0_L, G0_R) = s2r_fader_gains(pan of v, w of v, applied pair) and
+ * (G1_L, G1_R) the same under the target pair, d_c = (G1_c - G0_c) / (float)N (IEEE division) and at frame i of the CALL the
+ * voice's gain is g_c[v][i] = G0_c + (float)i * d_c (the product rounded, then the sum; no fma), which takes the place of
+ * s2r_fill_buses' constant gain: gb_c[v][i] = (min(bus of v, n_buses - 1) == b) ? g_c[v][i] : +0.0f.  A voice whose program did
+ * not move has d == +0 and its terms are the static fill's, bit for bit; with every pair at (1, 0) the bus fill is exactly what
+ * it was without faders.  When the call returns S2R_OK applied becomes target for every program; a call that fails leaves
+ * applied alone.  A note_on inside the fill gives its voice its new program's G0, G1 and d from its frame on; i keeps counting
+ * from the start of the call.  ONLY s2r_fill_buses applies or commits faders: every other fill ignores them, s2r_fill_panned
+ * included.  s2r_set_patch_bank keeps the pairs of the programs that survive and gives new ones (1, 0).
+ *   s2r_set_program_fader sets the target: S2R_ERR_PATCH_RANGE for a value outside its range or NaN (checked before the handle
+ *   is looked at; nothing is changed), S2R_ERR_INVALID if program >= bank size.  The first call that leaves (1, 0) reads the
+ *   voices' programs back from the device once (resident kernels are stopped).
+ *   s2r_get_program_fader: target and applied pair; any pointer may be NULL.
+ *   s2r_snap_program_faders: applied = target for every program, now — a hard cut, and the way to restore a checkpoint: set
+ *   the applied values, snap, then set the targets.
+ *   Single-device handles (a device-list handle: S2R_ERR_INVALID from all three, like s2r_set_voice_mix; it takes no bus fill
+ *   either).  A handle with an exchange attached takes them, and refuses the bus fill as before. */
+int s2r_set_program_fader(s2r_synth *s, uint32_t program, float fader, float pan_shift);
+int s2r_get_program_fader(const s2r_synth *s, uint32_t program, float *fader, float *pan_shift, float *applied_fader, float *applied_pan_shift);
+int s2r_snap_program_faders(s2r_synth *s);
 
 /* BUILD-DEFINED 4x oversampling (the reference has none; BASELINE config [4]): renders 4 * frames at
  * 4 * sample_rate_hz through the same path and decimates the mix by a 63-tap windowed sinc whose history
@@ -445,6 +473,12 @@ void s2r_pan_gains(float p, float *gl, float *gr);
  *   u = velocity < 1.0f ? velocity : 1.0f  (NaN -> 1);  u = u > 0.0f ? u : 0.0f;  a = 1.0f - velocity_sens * (1.0f - u);
  *   w = level * a.   w == 1.0f exactly for level 1, sensitivity 0, any velocity. */
 float s2r_voice_gain(float level, float velocity_sens, float velocity);
+
+/* The two gains of a voice with pan `pan` and gain `w` under a program fader pair.  binary32, every operation
+ * rounded on its own, no fma:  q = pan + pan_shift, clamped to [-1, 1] (q < -1 ? -1 : q > 1 ? 1 : q);
+ * (aL, aR) = s2r_pan_gains(q);  gL = (aL * w) * fader, gR = (aR * w) * fader.  With fader 1 and shift 0: aL * w, aR * w exactly.
+ * Either pointer may be NULL. */
+void s2r_fader_gains(float pan, float w, float fader, float pan_shift, float *gl, float *gr);
 
 /* The voice-allocation / release policy of Synth (synth.rs:61-120) for a pool of any size,
  * O(1) per event, without rendering.  Offsets advance by s2r_voice_pool_advance. */

@@ -150,6 +150,11 @@ pub mod ffi {
         pub fn s2r_set_voice_mix(s: *mut S2rSynth, gains: *const f32, buses: *const u8) -> c_int;
         pub fn s2r_voice_gain(level: f32, velocity_sens: f32, velocity: f32) -> f32;
         pub fn s2r_fill_buses(s: *mut S2rSynth, out: *mut f32, capacity: usize, n_buses: u32, frames: usize, sample_rate_hz: u32) -> c_int;
+        pub fn s2r_set_program_fader(s: *mut S2rSynth, program: u32, fader: f32, pan_shift: f32) -> c_int;
+        pub fn s2r_get_program_fader(s: *const S2rSynth, program: u32, fader: *mut f32, pan_shift: *mut f32, applied_fader: *mut f32,
+                                     applied_pan_shift: *mut f32) -> c_int;
+        pub fn s2r_snap_program_faders(s: *mut S2rSynth) -> c_int;
+        pub fn s2r_fader_gains(pan: f32, w: f32, fader: f32, pan_shift: f32, gl: *mut f32, gr: *mut f32);
         pub fn s2r_shard_voices(s: *const S2rSynth) -> u32;
         pub fn s2r_fill_device(s: *mut S2rSynth, dev_out: *mut f32, frames: usize, sample_rate_hz: u32,
                                hip_stream: *mut c_void) -> c_int;
@@ -185,6 +190,13 @@ pub const MAX_BUSES: u32 = 8;
 /// Host-only: the gain a note_on of `velocity` gives its voice under a program's level and velocity sensitivity — DESIGN.md 4.13.
 pub fn voice_gain(level: f32, velocity_sens: f32, velocity: f32) -> f32 {
     unsafe { ffi::s2r_voice_gain(level, velocity_sens, velocity) }
+}
+
+/// Host-only: the gains (gL, gR) of a voice with pan `pan` and gain `w` under a program fader pair — DESIGN.md 4.14.
+pub fn fader_gains(pan: f32, w: f32, fader: f32, pan_shift: f32) -> (f32, f32) {
+    let (mut gl, mut gr) = (0.0f32, 0.0f32);
+    unsafe { ffi::s2r_fader_gains(pan, w, fader, pan_shift, &mut gl, &mut gr) };
+    (gl, gr)
 }
 
 pub mod synth {
@@ -415,6 +427,25 @@ pub mod synth {
             assert!(n_buses >= 1 && out.len() % (2 * n_buses as usize) == 0);
             let frames = out.len() / (2 * n_buses as usize);
             self.check(unsafe { ffi::s2r_fill_buses(self.handle, out.as_mut_ptr(), out.len(), n_buses, frames, sample_rate.0) });
+        }
+
+        /// Build-defined live program faders (`s2r_set_program_fader`, include/s2r.h): the target of a program's fader (in
+        /// [0, 1]) and pan shift (in [-2, 2]); every voice sounding on the program reaches it as a ramp across the next
+        /// `sample_buses` call.
+        pub fn set_program_fader(&mut self, program: u32, fader: f32, pan_shift: f32) {
+            self.check(unsafe { ffi::s2r_set_program_fader(self.handle, program, fader, pan_shift) });
+        }
+
+        /// (fader, pan_shift, applied_fader, applied_pan_shift): the target, and where the last bus fill left the pair.
+        pub fn get_program_fader(&self, program: u32) -> (f32, f32, f32, f32) {
+            let (mut f, mut sh, mut af, mut ash) = (0.0f32, 0.0f32, 0.0f32, 0.0f32);
+            self.check(unsafe { ffi::s2r_get_program_fader(self.handle, program, &mut f, &mut sh, &mut af, &mut ash) });
+            (f, sh, af, ash)
+        }
+
+        /// applied = target for every program, now: a hard cut, and the middle step of restoring a checkpoint.
+        pub fn snap_program_faders(&mut self) {
+            self.check(unsafe { ffi::s2r_snap_program_faders(self.handle) });
         }
 
         /// For the reference's own call pattern — `sample()` per 16 frames from the audio callback (main.rs:138-147): keeps a

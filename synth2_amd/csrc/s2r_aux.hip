@@ -221,9 +221,24 @@ __global__ void __launch_bounds__(256) s2r_pan_combine_kernel(const S2rPanMix m)
 // ---------------------------------------------------------------------------------------
 constexpr uint32_t kBusLdsBytes = 32u << 10;
 
-template <int W, int NB>
-__global__ void __launch_bounds__(256) s2r_bus_mix_kernel(const S2rBusMix m) {
+//   RAMP (program faders moving): the gain of a voice is G0 + (float)i * d at frame i of the CALL — the arguments
+//   carry the call-relative frame of the rows' first frame.  Per bus the run selects (G0, d) once per voice and channel, exactly as
+//   the static form selects its gain (an off-bus voice: +0.0 + i * +0.0 = +0.0), and every element takes a multiply and an add for
+//   its gain in front of the static form's multiply and add: nothing but the sixteen voices' two steps and W frame numbers is
+//   added to the registers the run keeps live.  RAMP = false compiles to the static kernel, instruction for instruction.
+template <bool RAMP> struct BusMixArgs { typedef S2rBusMix type; };
+template <> struct BusMixArgs<true> { typedef S2rBusRampMix type; };
+__device__ __forceinline__ const S2rBusMix &bus_mix_of(const S2rBusMix &a) { return a; }
+__device__ __forceinline__ const S2rBusMix &bus_mix_of(const S2rBusRampMix &a) { return a.m; }
+__device__ __forceinline__ const float *bus_step_of(const S2rBusMix &, int) { return nullptr; }
+__device__ __forceinline__ const float *bus_step_of(const S2rBusRampMix &a, int c) { return c ? a.d_r : a.d_l; }
+__device__ __forceinline__ uint32_t bus_base_of(const S2rBusMix &) { return 0u; }
+__device__ __forceinline__ uint32_t bus_base_of(const S2rBusRampMix &a) { return a.frame_base; }
+
+template <int W, int NB, bool RAMP>
+__global__ void __launch_bounds__(256) s2r_bus_mix_kernel(const typename BusMixArgs<RAMP>::type a) {
     extern __shared__ float s_bus[];                             // [block_voices / 16][2 * NB][lanes * W]
+    const S2rBusMix &m = bus_mix_of(a);
     const uint32_t lanes = m.lanes, TF = lanes * (uint32_t)W;
     const uint32_t lane = threadIdx.x & (lanes - 1u), slot = threadIdx.x / lanes, n_slots = blockDim.x / lanes;
     const uint32_t b = blockIdx.y, fl = lane * (uint32_t)W, f0 = blockIdx.x * TF + fl;
@@ -231,11 +246,17 @@ __global__ void __launch_bounds__(256) s2r_bus_mix_kernel(const S2rBusMix m) {
     for (uint32_t g = slot; g < n_grp; g += n_slots) {
         const uint32_t v0 = b * m.block_voices + 16u * g;
         float x[16][W], gl[16], gr[16];
+        float dl[RAMP ? 16 : 1], dr[RAMP ? 16 : 1], fi[RAMP ? W : 1];
         uint32_t vb[16];
+        if (RAMP) {
+#pragma unroll
+            for (int j = 0; j < W; ++j) fi[RAMP ? j : 0] = (float)(bus_base_of(a) + f0 + (uint32_t)j);      // i of the call, not of the slice
+        }
 #pragma unroll
         for (uint32_t k = 0; k < 16u; ++k) {
             const uint32_t v = v0 + k;
             gl[k] = m.gain_l[v]; gr[k] = m.gain_r[v];            // (padded with 0 up to the grid's last voice)
+            if (RAMP) { dl[RAMP ? k : 0u] = bus_step_of(a, 0)[v]; dr[RAMP ? k : 0u] = bus_step_of(a, 1)[v]; }
             const uint32_t q = m.bus[v];
             vb[k] = q < last ? q : last;                         // a voice booked past the call's buses sounds on the last one
             const float *src = m.rows + (size_t)v * m.stride + f0;
@@ -255,19 +276,25 @@ __global__ void __launch_bounds__(256) s2r_bus_mix_kernel(const S2rBusMix m) {
 #pragma unroll
             for (uint32_t k = 0; k < 16u; ++k) {
                 const float sl = vb[k] == q ? gl[k] : 0.0f, sr = vb[k] == q ? gr[k] : 0.0f;
+                const float tl = RAMP && vb[k] == q ? dl[RAMP ? k : 0u] : 0.0f, tr = RAMP && vb[k] == q ? dr[RAMP ? k : 0u] : 0.0f;
 #pragma unroll
                 for (int j = 0; j < W; ++j) {
-                    const float pl = x[k][j] * sl, pr = x[k][j] * sr;
+                    float el = sl, er = sr;
+                    if (RAMP) {                                  // (-ffp-contract=off: the step's product is rounded before the sum)
+                        const float ul = fi[RAMP ? j : 0] * tl, ur = fi[RAMP ? j : 0] * tr;
+                        el = sl + ul; er = sr + ur;
+                    }
+                    const float pl = x[k][j] * el, pr = x[k][j] * er;
                     al[j] = k ? al[j] + pl : pl; ar[j] = k ? ar[j] + pr : pr;
                 }
             }
-            float *dl = s_bus + ((size_t)g * (2u * NB) + 2u * q) * TF + fl, *dr = dl + TF;
+            float *dst_l = s_bus + ((size_t)g * (2u * NB) + 2u * q) * TF + fl, *dst_r = dst_l + TF;
             if (W == 4) {
-                *reinterpret_cast<f4 *>(dl) = (f4){al[0], al[1 % W], al[2 % W], al[3 % W]};
-                *reinterpret_cast<f4 *>(dr) = (f4){ar[0], ar[1 % W], ar[2 % W], ar[3 % W]};
+                *reinterpret_cast<f4 *>(dst_l) = (f4){al[0], al[1 % W], al[2 % W], al[3 % W]};
+                *reinterpret_cast<f4 *>(dst_r) = (f4){ar[0], ar[1 % W], ar[2 % W], ar[3 % W]};
             } else {
 #pragma unroll
-                for (int j = 0; j < W; ++j) { dl[j] = al[j]; dr[j] = ar[j]; }
+                for (int j = 0; j < W; ++j) { dst_l[j] = al[j]; dst_r[j] = ar[j]; }
             }
         }
     }
@@ -519,18 +546,23 @@ hipError_t s2r_launch_pan_mix(const S2rPanMix &m, hipStream_t stream) {
     return hipGetLastError();
 }
 
-template <int W>
-static void bus_mix_launch(const S2rBusMix &m, uint32_t nb, dim3 grid, dim3 block, size_t lds, hipStream_t stream) {
+template <int W, bool RAMP>
+static void bus_mix_launch(const typename BusMixArgs<RAMP>::type &a, uint32_t nb, dim3 grid, dim3 block, size_t lds, hipStream_t stream) {
     switch (nb) {
-    case 1: hipLaunchKernelGGL((s2r_bus_mix_kernel<W, 1>), grid, block, lds, stream, m); break;
-    case 2: hipLaunchKernelGGL((s2r_bus_mix_kernel<W, 2>), grid, block, lds, stream, m); break;
-    case 4: hipLaunchKernelGGL((s2r_bus_mix_kernel<W, 4>), grid, block, lds, stream, m); break;
-    default: hipLaunchKernelGGL((s2r_bus_mix_kernel<W, 8>), grid, block, lds, stream, m); break;
+    case 1: hipLaunchKernelGGL((s2r_bus_mix_kernel<W, 1, RAMP>), grid, block, lds, stream, a); break;
+    case 2: hipLaunchKernelGGL((s2r_bus_mix_kernel<W, 2, RAMP>), grid, block, lds, stream, a); break;
+    case 4: hipLaunchKernelGGL((s2r_bus_mix_kernel<W, 4, RAMP>), grid, block, lds, stream, a); break;
+    default: hipLaunchKernelGGL((s2r_bus_mix_kernel<W, 8, RAMP>), grid, block, lds, stream, a); break;
     }
 }
 
-hipError_t s2r_launch_bus_mix(const S2rBusMix &in, hipStream_t stream) {
-    S2rBusMix m = in;
+static S2rBusMix &bus_mix_of_host(S2rBusMix &a) { return a; }
+static S2rBusMix &bus_mix_of_host(S2rBusRampMix &a) { return a.m; }
+
+template <bool RAMP>
+static hipError_t bus_mix_launch_any(const typename BusMixArgs<RAMP>::type &in, hipStream_t stream) {
+    typename BusMixArgs<RAMP>::type a = in;
+    S2rBusMix &m = bus_mix_of_host(a);
     if (m.frames == 0 || m.n_voices == 0) return hipSuccess;
     if (m.block_voices < 64 || m.block_voices > 1024 || (m.block_voices & 63u) || m.n_blocks * m.block_voices < m.n_voices || m.n_blocks > 65535u ||
         m.stride < m.frames || m.pstride < m.frames || m.n_groups == 0 || m.blocks_per_group * m.n_groups < m.n_blocks ||
@@ -549,10 +581,17 @@ hipError_t s2r_launch_bus_mix(const S2rBusMix &in, hipStream_t stream) {
     uint32_t threads = (n_grp * m.lanes + 63u) & ~63u;            // a thread per run and lane, whole waves, 256 at the most
     if (threads > 256u) threads = 256u;
     const dim3 grid((m.frames + tf - 1u) / tf, m.n_blocks);
-    if (wide) bus_mix_launch<4>(m, nb, grid, dim3(threads), lds, stream);
-    else bus_mix_launch<1>(m, nb, grid, dim3(threads), lds, stream);
+    if (wide) bus_mix_launch<4, RAMP>(a, nb, grid, dim3(threads), lds, stream);
+    else bus_mix_launch<1, RAMP>(a, nb, grid, dim3(threads), lds, stream);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(s2r_bus_combine_kernel, dim3((2u * m.frames * m.n_buses + 255u) / 256u), dim3(256), 0, stream, m);
     return hipGetLastError();
+}
+
+hipError_t s2r_launch_bus_mix(const S2rBusMix &m, hipStream_t stream) { return bus_mix_launch_any<false>(m, stream); }
+
+hipError_t s2r_launch_bus_mix_ramped(const S2rBusRampMix &r, hipStream_t stream) {
+    if (!r.d_l || !r.d_r) return hipErrorInvalidValue;
+    return bus_mix_launch_any<true>(r, stream);
 }

@@ -370,6 +370,14 @@ struct S2rBusMix {
     uint32_t lanes;               // threads along the frames of a tile (set by s2r_launch_bus_mix)
 };
 
+// The bus mixdown under moving program faders: the gain of voice v at frame i of the CALL is
+// g_c[v][i] = G0_c[v] + (float)i * d_c[v] (the product rounded, then the sum); m.gain_l / m.gain_r hold G0.
+struct S2rBusRampMix {
+    S2rBusMix m;
+    const float *d_l, *d_r;       // [n_blocks * block_voices] each: the gain's step per frame, entries past n_voices hold 0
+    uint32_t frame_base;          // the call-relative frame of m.rows' first frame (a segment's or a slice's start)
+};
+
 hipError_t s2r_launch_tables(const S2rTabBuild &b, hipStream_t stream);
 hipError_t s2r_launch_noise_table(float *table_65536, hipStream_t stream);
 // one-pole single-patch handles of one workgroup only (a.p.direct_out set, a.p.frames = the longest fill): false otherwise
@@ -394,3 +402,5 @@ hipError_t s2r_launch_sum_rows(const float *rows, uint32_t n_rows, uint32_t fram
 hipError_t s2r_launch_pan_mix(const S2rPanMix &m, hipStream_t stream);
 // s2r_bus_mix_kernel (the instantiation for the call's bus count and the rows' alignment) and s2r_bus_combine_kernel
 hipError_t s2r_launch_bus_mix(const S2rBusMix &m, hipStream_t stream);
+// ... and its ramped instantiation (per-frame gains), same geometry, same combine
+hipError_t s2r_launch_bus_mix_ramped(const S2rBusRampMix &r, hipStream_t stream);

@@ -293,11 +293,22 @@ struct s2r_synth {
     std::vector<uint8_t> vbus;
     struct MixEvent { uint32_t local, frame; float gain; uint8_t bus; };
     std::vector<MixEvent> mix_timed;             // like pan_timed
-    char *bus_gains_host = nullptr, *bus_gains_dev = nullptr;    // [2][padded_voices] floats: gL * w, gR * w; then [padded_voices] bus bytes
+    char *bus_gains_host = nullptr, *bus_gains_dev = nullptr;    // [2][padded_voices] floats: gL * w, gR * w; then [padded_voices] bus bytes;
+                                                                 // then (a ramped fill) [2][padded_voices] floats: the gains' steps per frame
     hipEvent_t bus_gains_sent = nullptr;
     float *bus_partials = nullptr;               // [n_blocks][S2R_MAX_BUSES][2][pan_slice], allocated by the first bus fill
     float *bus_out = nullptr, *bus_out_dev = nullptr;            // pinned and device-mapped: S2R_MAX_BUSES * 2 * max_frames floats
     float bus_mix_ms = -1.0f;                    // pan_mix_ms of the last s2r_fill_buses (tools/bus_time.py)
+    // Program faders: per program the pair (fader, pan_shift) the caller last set — the target — and the pair the
+    // last bus fill left — the applied one; a bus fill ramps every voice's gains from the one to the other.  A voice follows the
+    // program it was STARTED with: vprog mirrors the device's per-voice program (local order) from the first fader that leaves
+    // the default on (fader_used: read back once, then kept by the note_on paths like the pans); nothing of it is touched before.
+    std::vector<float> prog_fader, prog_shift, prog_fader_app, prog_shift_app;    // one entry per bank patch
+    bool fader_used = false;
+    std::vector<uint8_t> vprog;                  // [shard_voices] once fader_used
+    struct ProgEvent { uint32_t local, frame; uint8_t program; };
+    std::vector<ProgEvent> prog_timed;           // like pan_timed
+    bool bus_dev_ramped = false;                 // what bus_gains_dev holds was sent for a ramped fill: (G0, step), not the static gains
     float pitch_table[256];
     hipEvent_t t0 = nullptr, t1 = nullptr;
     bool timing = false, timed = false, no_flat_shortcut = false;
@@ -1659,11 +1670,57 @@ inline void mix_note_on(s2r_synth *s, uint32_t local, float velocity, uint32_t f
     else s->mix_timed.push_back(s2r_synth::MixEvent{local, frame, w, bus});
 }
 
-// what the bus mixdown reads per voice — both pan gains times the voice's gain (one rounded multiply each) and the bus byte — from
-// pinned memory to the device on the handle's stream (when a pan or a mix changed)
-int bus_send_gains(s2r_synth *s) {
-    if (!(s->gains_dirty & kGainsBus)) return S2R_OK;
-    const size_t pv = s->padded_voices, bytes = pv * (2 * sizeof(float) + 1);
+// ---- program faders ----
+inline bool fader_in_range(float fader, float shift) { return fader >= 0.0f && fader <= 1.0f && shift >= -2.0f && shift <= 2.0f; }   // (false for NaN)
+
+// The first fader that leaves (1, 0): from here on the host mirrors every shard voice's program.  What the voices hold NOW is on
+// the device (the render kernels keep it); on top of it come the events the host still holds for the next fill, in their order.
+int fader_begin(s2r_synth *s) {
+    if (s->fader_used) return S2R_OK;
+    S2R_QUIESCE(s);
+    S2R_HIP(s, hipSetDevice(s->device));
+    std::vector<uint32_t> h(s->padded_voices);
+    S2R_HIP(s, hipMemcpyAsync(h.data(), s->v.program, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+    S2R_HIP(s, hipStreamSynchronize(s->stream));
+    s->vprog.resize(s->shard_voices);
+    for (uint32_t i = 0; i < s->shard_voices; i++) s->vprog[i] = (uint8_t)h[i];
+    for (const S2rVoiceEvent &e : s->pending) if (e.flags & S2R_EV_RESTART) s->vprog[e.voice] = (uint8_t)(e.flags >> S2R_EV_PROGRAM_SHIFT);
+    s->prog_timed.clear();
+    for (const S2rTimedEvent &te : s->tpending) {
+        if (!(te.flags & S2R_EV_RESTART)) continue;
+        if (te.frame == 0) s->vprog[te.voice] = (uint8_t)te.program;
+        else s->prog_timed.push_back(s2r_synth::ProgEvent{te.voice, te.frame, (uint8_t)te.program});
+    }
+    s->fader_used = true; s->gains_dirty = kGainsAll;
+    return S2R_OK;
+}
+
+void prog_settle(s2r_synth *s) {
+    if (s->prog_timed.empty() || s->fill_time != 0) return;
+    for (const s2r_synth::ProgEvent &e : s->prog_timed) s->vprog[e.local] = e.program;
+    s->prog_timed.clear();
+    s->gains_dirty = kGainsAll;
+}
+
+inline void prog_note_on(s2r_synth *s, uint32_t local, uint32_t frame) {
+    if (frame == 0) { s->vprog[local] = (uint8_t)s->program; s->gains_dirty = kGainsAll; }
+    else s->prog_timed.push_back(s2r_synth::ProgEvent{local, frame, (uint8_t)s->program});
+}
+
+inline bool faders_moving(const s2r_synth *s) {
+    if (!s->fader_used) return false;
+    for (size_t k = 0; k < s->prog_fader.size(); k++)
+        if (s->prog_fader[k] != s->prog_fader_app[k] || s->prog_shift[k] != s->prog_shift_app[k]) return true;
+    return false;
+}
+
+// what the bus mixdown reads per voice — both pan gains times the voice's gain (one rounded multiply each), times its program's
+// applied fader once faders are in use, and the bus byte — from pinned memory to the device on the handle's stream (when a pan, a
+// mix or a fader changed).  `ramp`: a bus fill of `total` frames with a fader on its way: the gains under the applied pairs and,
+// behind the bus bytes, their steps per frame towards the gains under the targets — one staging buffer, one copy.
+int bus_send_gains(s2r_synth *s, bool ramp, uint32_t total) {
+    if (!(s->gains_dirty & kGainsBus) && s->bus_dev_ramped == ramp) return S2R_OK;
+    const size_t pv = s->padded_voices, static_bytes = pv * (2 * sizeof(float) + 1), bytes = pv * (4 * sizeof(float) + 1);
     if (!s->bus_gains_host) {
         S2R_HIP(s, hipHostMalloc((void **)&s->bus_gains_host, bytes, hipHostMallocDefault));
         std::memset(s->bus_gains_host, 0, bytes);
@@ -1672,16 +1729,34 @@ int bus_send_gains(s2r_synth *s) {
     } else S2R_HIP(s, hipEventSynchronize(s->bus_gains_sent));
     float *g = reinterpret_cast<float *>(s->bus_gains_host);
     uint8_t *b = reinterpret_cast<uint8_t *>(s->bus_gains_host + 2 * pv * sizeof(float));
+    float *d = reinterpret_cast<float *>(s->bus_gains_host + static_bytes);
+    const size_t n_prog = s->prog_fader.size();
+    const float fn = (float)total;
     for (uint32_t i = 0; i < s->shard_voices; i++) {
-        float gl, gr;
-        s2r_pan_gains(s->pan_used ? s->pans[i] : 0.0f, &gl, &gr);
-        const float w = s->mix_used ? s->vgain[i] : 1.0f;
-        g[i] = gl * w; g[pv + i] = gr * w;
+        const float pan = s->pan_used ? s->pans[i] : 0.0f, w = s->mix_used ? s->vgain[i] : 1.0f;
         b[i] = s->mix_used ? s->vbus[i] : (uint8_t)0;
+        if (!s->fader_used) {
+            float gl, gr;
+            s2r_pan_gains(pan, &gl, &gr);
+            g[i] = gl * w; g[pv + i] = gr * w;
+            continue;
+        }
+        const size_t k = s->vprog[i] < n_prog ? s->vprog[i] : 0u;                 // (past a later, smaller bank: program 0, as its patch is)
+        float g0l, g0r;
+        s2r_fader_gains(pan, w, s->prog_fader_app[k], s->prog_shift_app[k], &g0l, &g0r);
+        g[i] = g0l; g[pv + i] = g0r;
+        if (!ramp) continue;
+        if (s->prog_fader[k] != s->prog_fader_app[k] || s->prog_shift[k] != s->prog_shift_app[k]) {
+            float g1l, g1r;
+            s2r_fader_gains(pan, w, s->prog_fader[k], s->prog_shift[k], &g1l, &g1r);
+            const float dl = g1l - g0l, dr = g1r - g0r;
+            d[i] = dl / fn; d[pv + i] = dr / fn;
+        } else { d[i] = 0.0f; d[pv + i] = 0.0f; }
     }
-    S2R_HIP(s, hipMemcpyAsync(s->bus_gains_dev, s->bus_gains_host, bytes, hipMemcpyHostToDevice, s->stream));
+    S2R_HIP(s, hipMemcpyAsync(s->bus_gains_dev, s->bus_gains_host, ramp ? bytes : static_bytes, hipMemcpyHostToDevice, s->stream));
     S2R_HIP(s, hipEventRecord(s->bus_gains_sent, s->stream));
     s->gains_dirty &= ~kGainsBus;
+    s->bus_dev_ramped = ramp;
     return S2R_OK;
 }
 
@@ -1689,8 +1764,9 @@ int bus_send_gains(s2r_synth *s) {
 // into `pending`: slice after slice the MODE 1 launch into the rows buffer and the mixdown into the mapped output.  `last_event`:
 // the frame the pool's clock has already been moved to by the fill's events (fill_time at entry) — the slices from there on move
 // it further.
-int pan_segment(s2r_synth *s, uint32_t at, uint32_t n, uint32_t last_event, uint32_t sample_rate, uint32_t n_buses, uint32_t total) {
-    int rc = n_buses ? bus_send_gains(s) : pan_send_gains(s);
+// `ramp`: a bus fill under moving faders — the ramped mixdown, which is told where in the CALL each slice begins.
+int pan_segment(s2r_synth *s, uint32_t at, uint32_t n, uint32_t last_event, uint32_t sample_rate, uint32_t n_buses, uint32_t total, bool ramp) {
+    int rc = n_buses ? bus_send_gains(s, ramp, total) : pan_send_gains(s);
     if (rc != S2R_OK) return rc;
     for (uint32_t done = 0; done < n;) {
         const uint32_t len = n - done < s->pan_slice ? n - done : s->pan_slice;
@@ -1719,7 +1795,14 @@ int pan_segment(s2r_synth *s, uint32_t at, uint32_t n, uint32_t last_event, uint
             bm.n_groups = m.n_groups; bm.blocks_per_group = m.blocks_per_group;
             bm.out = s->bus_out_dev + 2u * (size_t)(at + done); bm.ostride = 2u * (size_t)total;
             bm.n_buses = n_buses;
-            S2R_HIP(s, s2r_launch_bus_mix(bm, s->stream));
+            if (ramp) {
+                S2rBusRampMix rm{};
+                rm.m = bm;
+                rm.d_l = reinterpret_cast<const float *>(s->bus_gains_dev + s->padded_voices * (2 * sizeof(float) + 1));
+                rm.d_r = rm.d_l + s->padded_voices;
+                rm.frame_base = at + done;
+                S2R_HIP(s, s2r_launch_bus_mix_ramped(rm, s->stream));
+            } else S2R_HIP(s, s2r_launch_bus_mix(bm, s->stream));
         } else S2R_HIP(s, s2r_launch_pan_mix(m, s->stream));
         if (s->timing) { S2R_HIP(s, hipEventRecord(s->pan_ev[s->pan_ev_used + 1], s->stream)); s->pan_ev_used += 2; }
         done += len;
@@ -1939,6 +2022,7 @@ static int create_single(const s2r_config *cfg, std::shared_ptr<S2rVoicePool> po
     s->bank.resize(1);
     s->prog_pan.assign(1, 0.0f); s->prog_spread.assign(1, 0.0f);
     s->prog_level.assign(1, 1.0f); s->prog_sens.assign(1, 0.0f); s->prog_bus.assign(1, 0u);
+    s->prog_fader.assign(1, 1.0f); s->prog_shift.assign(1, 0.0f); s->prog_fader_app.assign(1, 1.0f); s->prog_shift_app.assign(1, 0.0f);
     s2r_default_patch(&s->bank[0]);
     if (pool) s->pool = pool;
     else { s->pool.reset(new S2rVoicePool(cfg->total_voices)); s->seed_override.assign(cfg->total_voices, 0u); configure_policy_threads(s->pool.get(), cfg->total_voices); }
@@ -2192,6 +2276,8 @@ int s2r_set_patch_bank(s2r_synth *s, const s2r_patch *patches, uint32_t n) {
     s->bank.assign(patches, patches + n);
     s->prog_pan.resize(n, 0.0f); s->prog_spread.resize(n, 0.0f);   // the surviving programs keep their pans
     s->prog_level.resize(n, 1.0f); s->prog_sens.resize(n, 0.0f); s->prog_bus.resize(n, 0u);      // ... and their mix
+    s->prog_fader.resize(n, 1.0f); s->prog_shift.resize(n, 0.0f); s->prog_fader_app.resize(n, 1.0f); s->prog_shift_app.resize(n, 0.0f);   // ... and faders
+    if (s->fader_used) s->gains_dirty = kGainsAll;               // (a voice whose program fell off the bank follows program 0 now)
     if (s->program >= n) s->program = 0;
     s->bank_dirty = true; s->tab_dirty = true;
     for (s2r_synth *kid : s->kids) { kid->bank = s->bank; kid->bank_dirty = true; kid->tab_dirty = true; }
@@ -2241,10 +2327,11 @@ int s2r_note_on_ex(s2r_synth *s, uint8_t note, float velocity, uint32_t *voice_i
     const uint32_t i = s->pool->note_on(note, velocity);
     if (voice_index_out) *voice_index_out = i;
     if (s->voice_log) s->voice_log(s->voice_log_user, i, note);
-    if ((s->pan_used | s->mix_used) && s->kids.empty()) {
+    if ((s->pan_used | s->mix_used | s->fader_used) && s->kids.empty()) {
         const int64_t mine = to_local(s, i);
         if (s->pan_used) { pan_settle(s); if (mine >= 0) pan_note_on(s, (uint32_t)mine, note, 0u); }
         if (s->mix_used) { mix_settle(s); if (mine >= 0) mix_note_on(s, (uint32_t)mine, velocity, 0u); }
+        if (s->fader_used) { prog_settle(s); if (mine >= 0) prog_note_on(s, (uint32_t)mine, 0u); }
     }
     if (!append_frame0_record(s, i, S2R_EV_RESTART, s->pitch_table[note], s->seed_override[i], s->program))
         push_event(s, i, S2R_EV_RESTART, s->pitch_table[note], s->seed_override[i], s->program);
@@ -2292,7 +2379,7 @@ int s2r_note_events(s2r_synth *s, const s2r_note_event *events, size_t n) {
     // and note_off over the events computes — on several threads for a multi-GPU-sized batch): the voice every event takes or
     // releases.  An event inside the next fill first moves the pool's clock to its frame (the policy sees the offsets every
     // voice has AT that frame, like the reference between two 16-frame calls); frame-0 events take effect before the fill.
-    if (s->pan_used | s->mix_used) { pan_settle(s); mix_settle(s); }      // (while fill_time still says whether the last fill's events are behind us)
+    if (s->pan_used | s->mix_used | s->fader_used) { pan_settle(s); mix_settle(s); prog_settle(s); }      // (while fill_time still says whether the last fill's events are behind us)
     static thread_local std::vector<int64_t> chosen;
     if (chosen.size() < n) chosen.resize(n);
     static_assert(sizeof(S2rPolicyEvent) == 4 && S2R_NOTE_ON == S2R_POLICY_NOTE_ON && S2R_NOTE_OFF == S2R_POLICY_NOTE_OFF, "s2r_note_event's first four bytes");
@@ -2333,9 +2420,10 @@ int s2r_note_events(s2r_synth *s, const s2r_note_event *events, size_t n) {
         }
         const uint32_t frame = e.frame;
         const bool on = e.kind == S2R_NOTE_ON;
-        if (on && one && (one->pan_used | one->mix_used)) {
+        if (on && one && (one->pan_used | one->mix_used | one->fader_used)) {
             if (one->pan_used) pan_note_on(one, local, e.note, frame);
             if (one->mix_used) mix_note_on(one, local, e.velocity, frame);
+            if (one->fader_used) prog_note_on(one, local, frame);
         }
         if (frame == 0 && may_fold && sh->tpending.empty()) {
             if (on) push_event(s, (uint32_t)vi, S2R_EV_RESTART, pitch_of[e.note], seed_of[(size_t)vi], s->program);
@@ -2508,11 +2596,15 @@ static int fill_rows_mixed(s2r_synth *s, float *out, size_t capacity, uint32_t n
         S2R_HIP(s, hipHostGetDevicePointer((void **)&s->bus_out_dev, s->bus_out, 0));
     }
     fold_frame0_records(s);
-    pan_settle(s); mix_settle(s);
+    pan_settle(s); mix_settle(s); prog_settle(s);
     s->pan_ev_used = 0;
     const uint32_t last_event = s->fill_time;
+    // a bus fill with a program fader away from where the last one left it ramps; whatever the device holds from
+    // an earlier ramp is stale, and what this one sends is no static gain either (bus_dev_ramped)
+    const bool ramp = n_buses && faders_moving(s);
+    if (ramp) s->gains_dirty |= kGainsBus;
     if (s->tpending.empty()) {
-        rc = pan_segment(s, 0u, (uint32_t)frames, last_event, sample_rate_hz, n_buses, (uint32_t)frames);
+        rc = pan_segment(s, 0u, (uint32_t)frames, last_event, sample_rate_hz, n_buses, (uint32_t)frames, ramp);
         if (rc != S2R_OK) return rc;
     } else {
         // Events inside the fill: the per-voice rows and the event chains exclude each other in the render kernels, and an
@@ -2526,7 +2618,9 @@ static int fill_rows_mixed(s2r_synth *s, float *out, size_t capacity, uint32_t n
         pev.swap(s->pan_timed);
         std::vector<s2r_synth::MixEvent> mev;
         mev.swap(s->mix_timed);
-        size_t k = 0, kp = 0, km = 0;
+        std::vector<s2r_synth::ProgEvent> gev;
+        gev.swap(s->prog_timed);
+        size_t k = 0, kp = 0, km = 0, kg = 0;
         uint32_t at = 0;
         while (at < frames) {
             for (; k < recs.size() && recs[k].frame <= at; k++) {
@@ -2544,12 +2638,14 @@ static int fill_rows_mixed(s2r_synth *s, float *out, size_t capacity, uint32_t n
             for (; kp < pev.size() && pev[kp].frame <= at; kp++) { s->pans[pev[kp].local] = pev[kp].pan; s->gains_dirty = kGainsAll; }
             const uint32_t next = k < recs.size() && recs[k].frame < frames ? recs[k].frame : (uint32_t)frames;
             for (; km < mev.size() && mev[km].frame <= at; km++) { s->vgain[mev[km].local] = mev[km].gain; s->vbus[mev[km].local] = mev[km].bus; s->gains_dirty = kGainsAll; }
-            rc = pan_segment(s, at, next - at, last_event, sample_rate_hz, n_buses, (uint32_t)frames);
+            for (; kg < gev.size() && gev[kg].frame <= at; kg++) { s->vprog[gev[kg].local] = gev[kg].program; s->gains_dirty = kGainsAll; }
+            rc = pan_segment(s, at, next - at, last_event, sample_rate_hz, n_buses, (uint32_t)frames, ramp);
             if (rc != S2R_OK) { s->fill_time = 0; return rc; }
             at = next;
         }
     }
     S2R_HIP(s, hipStreamSynchronize(s->stream));
+    if (n_buses && s->fader_used) { s->prog_fader_app = s->prog_fader; s->prog_shift_app = s->prog_shift; }      // the faders have arrived
     if (n_buses) std::memcpy(out, s->bus_out, 2 * frames * n_buses * sizeof(float));
     else std::memcpy(out, s->out_host, 2 * frames * sizeof(float));
     if (s->timing) {
@@ -2616,6 +2712,51 @@ int s2r_set_voice_mix(s2r_synth *s, const float *gains, const uint8_t *buses) {
     std::memcpy(s->vgain.data(), gains, (size_t)s->shard_voices * sizeof(float));
     std::memcpy(s->vbus.data(), buses, (size_t)s->shard_voices);
     s->gains_dirty = kGainsAll;
+    return S2R_OK;
+}
+
+// ---- program faders ----
+void s2r_fader_gains(float pan, float w, float fader, float pan_shift, float *gl, float *gr) {
+    const float q0 = pan + pan_shift;
+    const float q = q0 < -1.0f ? -1.0f : (q0 > 1.0f ? 1.0f : q0);
+    float al, ar;
+    s2r_pan_gains(q, &al, &ar);
+    const float tl = al * w, tr = ar * w;                        // (-ffp-contract=off; with fader 1 and shift 0: the mixer's a * w, bit for bit)
+    if (gl) *gl = tl * fader;
+    if (gr) *gr = tr * fader;
+}
+
+int s2r_set_program_fader(s2r_synth *s, uint32_t program, float fader, float pan_shift) {
+    // (the values first, like s2r_set_program_pan)
+    if (!fader_in_range(fader, pan_shift))
+        return set_err(s, S2R_ERR_PATCH_RANGE, "program %u: fader %g, pan_shift %g: the fader lies in [0, 1], the shift in [-2, 2]", program, (double)fader, (double)pan_shift);
+    if (!s) return S2R_ERR_INVALID;
+    if (!s->kids.empty() || s->parent) return set_err(s, S2R_ERR_INVALID, "program faders are kept by single-device handles, not by a device list");
+    if (program >= s->bank.size()) return set_err(s, S2R_ERR_INVALID, "program %u: the bank holds %zu patches", program, s->bank.size());
+    if (fader != 1.0f || pan_shift != 0.0f) {
+        S2R_REFUSE_BROKEN(s);
+        const int rc = fader_begin(s);
+        if (rc != S2R_OK) return rc;
+    }
+    s->prog_fader[program] = fader; s->prog_shift[program] = pan_shift;
+    return S2R_OK;
+}
+
+int s2r_get_program_fader(const s2r_synth *s, uint32_t program, float *fader, float *pan_shift, float *applied_fader, float *applied_pan_shift) {
+    if (!s) return S2R_ERR_INVALID;
+    if (!s->kids.empty() || s->parent || program >= s->bank.size()) return S2R_ERR_INVALID;
+    if (fader) *fader = s->prog_fader[program];
+    if (pan_shift) *pan_shift = s->prog_shift[program];
+    if (applied_fader) *applied_fader = s->prog_fader_app[program];
+    if (applied_pan_shift) *applied_pan_shift = s->prog_shift_app[program];
+    return S2R_OK;
+}
+
+int s2r_snap_program_faders(s2r_synth *s) {
+    if (!s) return S2R_ERR_INVALID;
+    if (!s->kids.empty() || s->parent) return set_err(s, S2R_ERR_INVALID, "program faders are kept by single-device handles, not by a device list");
+    s->prog_fader_app = s->prog_fader; s->prog_shift_app = s->prog_shift;
+    s->gains_dirty |= kGainsBus;
     return S2R_OK;
 }
 
@@ -2806,11 +2947,13 @@ int s2r_import_state(s2r_synth *s, const s2r_voice_state *voices) {
         h[7 * pv + i] = s2r_f2u(in.filt_x1); h[8 * pv + i] = s2r_f2u(in.filt_x2);
         h[9 * pv + i] = s2r_f2u(in.filt_y1); h[10 * pv + i] = s2r_f2u(in.filt_y2);
         h[11 * pv + i] = in.program;
+        if (s->fader_used) s->vprog[i] = in.program;
         h[12 * pv + i] = s2r_f2u(in.osc_z);
         s->pool->set_voice(to_pool(s, i), in.note, in.started != 0, in.released != 0,
                            in.current_frame_offset, in.release_frame_offset, in.velocity);
     }
     s->pool->rebuild();
+    if (s->fader_used) { s->prog_timed.clear(); s->gains_dirty = kGainsAll; }
     S2R_HIP(s, hipMemcpyAsync(s->voice_mem, h.data(), pv * kVoiceWords * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
     S2R_HIP(s, hipStreamSynchronize(s->stream));
     return S2R_OK;

@@ -178,6 +178,10 @@ def load_library():
         "s2r_set_voice_mix": (C.c_int, [H, _f32p, C.POINTER(C.c_uint8)]),
         "s2r_voice_gain": (C.c_float, [C.c_float, C.c_float, C.c_float]),
         "s2r_fill_buses": (C.c_int, [H, _f32p, C.c_size_t, C.c_uint32, C.c_size_t, C.c_uint32]),
+        "s2r_set_program_fader": (C.c_int, [H, C.c_uint32, C.c_float, C.c_float]),
+        "s2r_get_program_fader": (C.c_int, [H, C.c_uint32, _f32p, _f32p, _f32p, _f32p]),
+        "s2r_snap_program_faders": (C.c_int, [H]),
+        "s2r_fader_gains": (None, [C.c_float, C.c_float, C.c_float, C.c_float, _f32p, _f32p]),
         "s2r_fill_device": (C.c_int, [H, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
         "s2r_fill_device_root": (C.c_int, [H, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
         "s2r_sum_partials_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_size_t, C.c_void_p, C.c_void_p]),
@@ -258,6 +262,14 @@ def pan_gains(p):
 def voice_gain(level, velocity_sens, velocity):
     """the gain a note_on of `velocity` gives its voice under a program's level and velocity sensitivity (s2r_voice_gain; host only)"""
     return float(load_library().s2r_voice_gain(float(level), float(velocity_sens), float(velocity)))
+
+
+def fader_gains(pan, w, fader, pan_shift):
+    """(gL, gR) of a voice with pan `pan` and gain `w` under a program fader pair: the pan shifted and clamped, its
+    constant-power gains times w, times the fader (s2r_fader_gains; host only)"""
+    gl, gr = C.c_float(), C.c_float()
+    load_library().s2r_fader_gains(float(pan), float(w), float(fader), float(pan_shift), C.byref(gl), C.byref(gr))
+    return gl.value, gr.value
 
 
 def stream_frame_json(samples):
@@ -502,6 +514,22 @@ class Synth:
         out = np.empty(2 * frames * max(int(n_buses), 0), dtype=np.float32)
         self._check(self.L.s2r_fill_buses(self.h, out.ctypes.data_as(_f32p), out.size, int(n_buses), frames, int(sample_rate)))
         return out.reshape(n_buses, frames, 2)
+
+    # --- live program faders (build-defined; s2r.h: s2r_set_program_fader) ---
+    def set_program_fader(self, program, fader=1.0, pan_shift=0.0):
+        """the target of a bank program's fader (in [0, 1]) and pan shift (in [-2, 2]): every voice sounding on the program
+        reaches it as a ramp across the next sample_buses call.  Only sample_buses applies them."""
+        self._check(self.L.s2r_set_program_fader(self.h, int(program), float(fader), float(pan_shift)))
+
+    def get_program_fader(self, program):
+        """(fader, pan_shift, applied_fader, applied_pan_shift): the target, and where the last bus fill left the pair"""
+        f, sh, af, ash = C.c_float(), C.c_float(), C.c_float(), C.c_float()
+        self._check(self.L.s2r_get_program_fader(self.h, int(program), C.byref(f), C.byref(sh), C.byref(af), C.byref(ash)))
+        return f.value, sh.value, af.value, ash.value
+
+    def snap_program_faders(self):
+        """applied = target for every program, now (a hard cut; restoring a checkpoint: set the applied values, snap, set the targets)"""
+        self._check(self.L.s2r_snap_program_faders(self.h))
 
     def render_voices(self, frames, sample_rate=SampleRateKhz(48000)):
         """Mix disabled: (shard_voices, frames) float32."""
