@@ -115,6 +115,14 @@ class Synth {
     // host only: the two gains of a voice with pan `pan` and gain `w` under a fader pair
     static void fader_gains(float pan, float w, float fader, float pan_shift, float *gl, float *gr) { s2r_fader_gains(pan, w, fader, pan_shift, gl, gr); }
 
+    // aux sends (build-defined; s2r.h: s2r_set_program_send): a send in [0, 1] and the bus it feeds per bank program, given to a
+    // voice at its note_on — a second feed of gain * send, post-pan and post-fader, in sample_buses only
+    void set_program_send(uint32_t program, float send, uint32_t send_bus = 0) { check(s2r_set_program_send(h_, program, send, send_bus)); }
+    void get_program_send(uint32_t program, float *send, uint32_t *send_bus) const { check(s2r_get_program_send(h_, program, send, send_bus)); }
+    void voice_sends(float *sends, uint8_t *send_buses) { check(s2r_get_voice_sends(h_, sends, send_buses)); }    // shard_voices entries each, local order
+    void set_voice_sends(const float *sends, const uint8_t *send_buses) { check(s2r_set_voice_sends(h_, sends, send_buses)); }
+    static float send_gain(float g, float send) { return s2r_send_gain(g, send); }
+
     s2r_synth *handle() { return h_; }
 
   private:

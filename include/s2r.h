@@ -34,7 +34,8 @@ extern "C" {
  * s2r_exchange_create, s2r_exchange_attach, s2r_voice_pool_set_threads, s2r_voice_pool_resolve, s2r_set_program_pan,
  * s2r_get_program_pan, s2r_get_voice_pans, s2r_set_voice_pans, s2r_fill_panned, s2r_voice_pan, s2r_pan_gains,
  * s2r_set_program_mix, s2r_get_program_mix, s2r_get_voice_mix, s2r_set_voice_mix, s2r_voice_gain, s2r_fill_buses,
- * s2r_set_program_fader, s2r_get_program_fader, s2r_snap_program_faders, s2r_fader_gains. */
+ * s2r_set_program_fader, s2r_get_program_fader, s2r_snap_program_faders, s2r_fader_gains, s2r_set_program_send,
+ * s2r_get_program_send, s2r_get_voice_sends, s2r_set_voice_sends, s2r_send_gain. */
 #define S2R_ABI_VERSION 4
 
 typedef enum {
@@ -313,6 +314,33 @@ int s2r_set_program_fader(s2r_synth *s, uint32_t program, float fader, float pan
 int s2r_get_program_fader(const s2r_synth *s, uint32_t program, float *fader, float *pan_shift, float *applied_fader, float *applied_pan_shift);
 int s2r_snap_program_faders(s2r_synth *s);
 
+/* BUILD-DEFINED aux sends (the reference has none; DESIGN.md 4.15 gives the op sequence): a second, scaled feed from each
+ * program to another bus of s2r_fill_buses — "some of the strings, some of the lead" on a bus that the caller's reverb or delay
+ * consumes.  Every program of the bank has a `send` in [0, 1] (default 0) and a `send_bus` in [0, S2R_MAX_BUSES) (default 0),
+ * held beside the bank like level / bus.  A note_on gives its voice the send s and the send bus sb of the program current at
+ * that note_on (a S2R_PROGRAM_CHANGE inside a batch included; an event inside a fill takes effect at its frame, as its gain and
+ * bus do); the voice keeps both until it is restarted; a voice never started has s = 0, sb = 0.  s2r_set_patch_bank keeps the
+ * values of the programs that survive and gives new ones (0, 0).
+ * In s2r_fill_buses, with g_c[v] the voice's gain as above (a_c * w, or (a_c * w) * fader): h_c[v] = g_c[v] * s[v] (one rounded
+ * multiply: the send is post-pan and post-fader), and the gain of voice v on bus b is
+ *   gb_c[v] = ((min(bus of v, n_buses - 1) == b) ? g_c[v] : +0.0f) + ((min(sb of v, n_buses - 1) == b) ? h_c[v] : +0.0f)
+ * (one rounded add): the send bus folds onto the last bus of the call as the main bus does, and a voice whose send lands on its
+ * own main bus has the gain g + h there.  With s = 0 gb is the main term bit for bit: a fill whose voices all have send 0 is the
+ * fill without sends.  Under moving faders base and step are formed the same way from (G0, G0 * s) and (d, d * s):
+ * g[i] = (sel(G0) + sel(G0 * s)) + (float)i * (sel(d) + sel(d * s)); the next fill starts from the static G1 * s, which the last
+ * ramp frame approaches up to rounding.  ONLY s2r_fill_buses applies sends; every other fill ignores them.
+ *   s2r_set_program_send: S2R_ERR_PATCH_RANGE for a send outside [0, 1] or NaN or a bus >= S2R_MAX_BUSES (checked before the
+ *   handle is looked at; nothing is changed), S2R_ERR_INVALID if program >= bank size.
+ *   s2r_get_program_send: either pointer may be NULL.
+ *   s2r_get_voice_sends / s2r_set_voice_sends: every shard voice's s and sb, shard_voices entries each in local order: the
+ *   checkpoint companions of s2r_get_voice_mix / s2r_set_voice_mix.  The setter refuses a send outside [0, 1] or NaN and a bus
+ *   >= S2R_MAX_BUSES with S2R_ERR_PATCH_RANGE and changes nothing then.
+ *   Single-device handles (a device-list handle: S2R_ERR_INVALID from all four; it takes no bus fill either). */
+int s2r_set_program_send(s2r_synth *s, uint32_t program, float send, uint32_t send_bus);
+int s2r_get_program_send(const s2r_synth *s, uint32_t program, float *send, uint32_t *send_bus);
+int s2r_get_voice_sends(s2r_synth *s, float *sends, uint8_t *send_buses);
+int s2r_set_voice_sends(s2r_synth *s, const float *sends, const uint8_t *send_buses);
+
 /* BUILD-DEFINED 4x oversampling (the reference has none; BASELINE config [4]): renders 4 * frames at
  * 4 * sample_rate_hz through the same path and decimates the mix by a 63-tap windowed sinc whose history
  * carries over from call to call (DESIGN.md 4.9 gives taps and arithmetic).  4 * frames must not exceed
@@ -479,6 +507,9 @@ float s2r_voice_gain(float level, float velocity_sens, float velocity);
  * (aL, aR) = s2r_pan_gains(q);  gL = (aL * w) * fader, gR = (aR * w) * fader.  With fader 1 and shift 0: aL * w, aR * w exactly.
  * Either pointer may be NULL. */
 void s2r_fader_gains(float pan, float w, float fader, float pan_shift, float *gl, float *gr);
+
+/* The gain of a voice's aux send: g * send, one rounded binary32 multiply. */
+float s2r_send_gain(float g, float send);
 
 /* The voice-allocation / release policy of Synth (synth.rs:61-120) for a pool of any size,
  * O(1) per event, without rendering.  Offsets advance by s2r_voice_pool_advance. */

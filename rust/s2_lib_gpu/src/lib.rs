@@ -155,6 +155,11 @@ pub mod ffi {
                                      applied_pan_shift: *mut f32) -> c_int;
         pub fn s2r_snap_program_faders(s: *mut S2rSynth) -> c_int;
         pub fn s2r_fader_gains(pan: f32, w: f32, fader: f32, pan_shift: f32, gl: *mut f32, gr: *mut f32);
+        pub fn s2r_set_program_send(s: *mut S2rSynth, program: u32, send: f32, send_bus: u32) -> c_int;
+        pub fn s2r_get_program_send(s: *const S2rSynth, program: u32, send: *mut f32, send_bus: *mut u32) -> c_int;
+        pub fn s2r_get_voice_sends(s: *mut S2rSynth, sends: *mut f32, send_buses: *mut u8) -> c_int;
+        pub fn s2r_set_voice_sends(s: *mut S2rSynth, sends: *const f32, send_buses: *const u8) -> c_int;
+        pub fn s2r_send_gain(g: f32, send: f32) -> f32;
         pub fn s2r_shard_voices(s: *const S2rSynth) -> u32;
         pub fn s2r_fill_device(s: *mut S2rSynth, dev_out: *mut f32, frames: usize, sample_rate_hz: u32,
                                hip_stream: *mut c_void) -> c_int;
@@ -197,6 +202,11 @@ pub fn fader_gains(pan: f32, w: f32, fader: f32, pan_shift: f32) -> (f32, f32) {
     let (mut gl, mut gr) = (0.0f32, 0.0f32);
     unsafe { ffi::s2r_fader_gains(pan, w, fader, pan_shift, &mut gl, &mut gr) };
     (gl, gr)
+}
+
+/// Host-only: the gain of a voice's aux send, `g * send` in one rounded multiply — DESIGN.md 4.15.
+pub fn send_gain(g: f32, send: f32) -> f32 {
+    unsafe { ffi::s2r_send_gain(g, send) }
 }
 
 pub mod synth {
@@ -446,6 +456,33 @@ pub mod synth {
         /// applied = target for every program, now: a hard cut, and the middle step of restoring a checkpoint.
         pub fn snap_program_faders(&mut self) {
             self.check(unsafe { ffi::s2r_snap_program_faders(self.handle) });
+        }
+
+        /// Build-defined aux sends (`s2r_set_program_send`, include/s2r.h): the send (in [0, 1]) of a bank program and the bus it
+        /// feeds (below `MAX_BUSES`) — what a note_on under that program gives its voice: a second feed of gain * send, post-pan and
+        /// post-fader, in `sample_buses` only.
+        pub fn set_program_send(&mut self, program: u32, send: f32, send_bus: u32) {
+            self.check(unsafe { ffi::s2r_set_program_send(self.handle, program, send, send_bus) });
+        }
+
+        pub fn get_program_send(&self, program: u32) -> (f32, u32) {
+            let (mut send, mut bus) = (0.0f32, 0u32);
+            self.check(unsafe { ffi::s2r_get_program_send(self.handle, program, &mut send, &mut bus) });
+            (send, bus)
+        }
+
+        /// Every voice's send and send bus: checkpoint companions of `voice_mix`.
+        pub fn voice_sends(&mut self) -> (Vec<f32>, Vec<u8>) {
+            let n = unsafe { ffi::s2r_shard_voices(self.handle) } as usize;
+            let (mut sends, mut buses) = (vec![0.0f32; n], vec![0u8; n]);
+            self.check(unsafe { ffi::s2r_get_voice_sends(self.handle, sends.as_mut_ptr(), buses.as_mut_ptr()) });
+            (sends, buses)
+        }
+
+        pub fn set_voice_sends(&mut self, sends: &[f32], send_buses: &[u8]) {
+            let n = unsafe { ffi::s2r_shard_voices(self.handle) } as usize;
+            assert!(sends.len() == n && send_buses.len() == n);
+            self.check(unsafe { ffi::s2r_set_voice_sends(self.handle, sends.as_ptr(), send_buses.as_ptr()) });
         }
 
         /// For the reference's own call pattern — `sample()` per 16 frames from the audio callback (main.rs:138-147): keeps a

@@ -226,17 +226,38 @@ constexpr uint32_t kBusLdsBytes = 32u << 10;
 //   the static form selects its gain (an off-bus voice: +0.0 + i * +0.0 = +0.0), and every element takes a multiply and an add for
 //   its gain in front of the static form's multiply and add: nothing but the sixteen voices' two steps and W frame numbers is
 //   added to the registers the run keeps live.  RAMP = false compiles to the static kernel, instruction for instruction.
-template <bool RAMP> struct BusMixArgs { typedef S2rBusMix type; };
-template <> struct BusMixArgs<true> { typedef S2rBusRampMix type; };
+//   SEND (aux sends): a voice feeds a second bus with its gain times its send, h = g * s (one rounded multiply,
+//   here: the arguments carry the voices' s and send bus, so the run keeps 32 more values live, not the 48 or 80 of gains multiplied
+//   on the host).  Per bus the run selects the main gain and the send's gain with a compare each and adds them once per voice and
+//   channel — M + A, and under RAMP likewise for the step — before the W frames are touched; with s = 0 the sum is M bit for bit
+//   (gains are finite and not negative).  SEND = false takes the arguments above and compiles to the same instructions as before.
+template <bool RAMP, bool SEND> struct BusMixArgs { typedef S2rBusMix type; };
+template <> struct BusMixArgs<true, false> { typedef S2rBusRampMix type; };
+template <> struct BusMixArgs<false, true> { typedef S2rBusSendMix type; };
+template <> struct BusMixArgs<true, true> { typedef S2rBusSendRampMix type; };
 __device__ __forceinline__ const S2rBusMix &bus_mix_of(const S2rBusMix &a) { return a; }
 __device__ __forceinline__ const S2rBusMix &bus_mix_of(const S2rBusRampMix &a) { return a.m; }
+__device__ __forceinline__ const S2rBusMix &bus_mix_of(const S2rBusSendMix &a) { return a.m; }
+__device__ __forceinline__ const S2rBusMix &bus_mix_of(const S2rBusSendRampMix &a) { return a.r.m; }
 __device__ __forceinline__ const float *bus_step_of(const S2rBusMix &, int) { return nullptr; }
 __device__ __forceinline__ const float *bus_step_of(const S2rBusRampMix &a, int c) { return c ? a.d_r : a.d_l; }
+__device__ __forceinline__ const float *bus_step_of(const S2rBusSendMix &, int) { return nullptr; }
+__device__ __forceinline__ const float *bus_step_of(const S2rBusSendRampMix &a, int c) { return c ? a.r.d_r : a.r.d_l; }
 __device__ __forceinline__ uint32_t bus_base_of(const S2rBusMix &) { return 0u; }
 __device__ __forceinline__ uint32_t bus_base_of(const S2rBusRampMix &a) { return a.frame_base; }
+__device__ __forceinline__ uint32_t bus_base_of(const S2rBusSendMix &) { return 0u; }
+__device__ __forceinline__ uint32_t bus_base_of(const S2rBusSendRampMix &a) { return a.r.frame_base; }
+__device__ __forceinline__ const float *bus_send_of(const S2rBusMix &) { return nullptr; }
+__device__ __forceinline__ const float *bus_send_of(const S2rBusRampMix &) { return nullptr; }
+__device__ __forceinline__ const float *bus_send_of(const S2rBusSendMix &a) { return a.send; }
+__device__ __forceinline__ const float *bus_send_of(const S2rBusSendRampMix &a) { return a.send; }
+__device__ __forceinline__ const uint8_t *bus_sbus_of(const S2rBusMix &) { return nullptr; }
+__device__ __forceinline__ const uint8_t *bus_sbus_of(const S2rBusRampMix &) { return nullptr; }
+__device__ __forceinline__ const uint8_t *bus_sbus_of(const S2rBusSendMix &a) { return a.send_bus; }
+__device__ __forceinline__ const uint8_t *bus_sbus_of(const S2rBusSendRampMix &a) { return a.send_bus; }
 
-template <int W, int NB, bool RAMP>
-__global__ void __launch_bounds__(256) s2r_bus_mix_kernel(const typename BusMixArgs<RAMP>::type a) {
+template <int W, int NB, bool RAMP, bool SEND>
+__global__ void __launch_bounds__(256) s2r_bus_mix_kernel(const typename BusMixArgs<RAMP, SEND>::type a) {
     extern __shared__ float s_bus[];                             // [block_voices / 16][2 * NB][lanes * W]
     const S2rBusMix &m = bus_mix_of(a);
     const uint32_t lanes = m.lanes, TF = lanes * (uint32_t)W;
@@ -247,7 +268,8 @@ __global__ void __launch_bounds__(256) s2r_bus_mix_kernel(const typename BusMixA
         const uint32_t v0 = b * m.block_voices + 16u * g;
         float x[16][W], gl[16], gr[16];
         float dl[RAMP ? 16 : 1], dr[RAMP ? 16 : 1], fi[RAMP ? W : 1];
-        uint32_t vb[16];
+        float sd[SEND ? 16 : 1];
+        uint32_t vb[16], sq[SEND ? 16 : 1];
         if (RAMP) {
 #pragma unroll
             for (int j = 0; j < W; ++j) fi[RAMP ? j : 0] = (float)(bus_base_of(a) + f0 + (uint32_t)j);      // i of the call, not of the slice
@@ -259,6 +281,11 @@ __global__ void __launch_bounds__(256) s2r_bus_mix_kernel(const typename BusMixA
             if (RAMP) { dl[RAMP ? k : 0u] = bus_step_of(a, 0)[v]; dr[RAMP ? k : 0u] = bus_step_of(a, 1)[v]; }
             const uint32_t q = m.bus[v];
             vb[k] = q < last ? q : last;                         // a voice booked past the call's buses sounds on the last one
+            if (SEND) {
+                sd[SEND ? k : 0u] = bus_send_of(a)[v];
+                const uint32_t t = bus_sbus_of(a)[v];
+                sq[SEND ? k : 0u] = t < last ? t : last;         // ... and so does its send
+            }
             const float *src = m.rows + (size_t)v * m.stride + f0;
             if (W == 4) {
                 const f4 r = (v < m.n_voices && f0 < m.frames) ? *reinterpret_cast<const f4 *>(src) : (f4){0.0f, 0.0f, 0.0f, 0.0f};
@@ -275,8 +302,18 @@ __global__ void __launch_bounds__(256) s2r_bus_mix_kernel(const typename BusMixA
             float al[W], ar[W];
 #pragma unroll
             for (uint32_t k = 0; k < 16u; ++k) {
-                const float sl = vb[k] == q ? gl[k] : 0.0f, sr = vb[k] == q ? gr[k] : 0.0f;
-                const float tl = RAMP && vb[k] == q ? dl[RAMP ? k : 0u] : 0.0f, tr = RAMP && vb[k] == q ? dr[RAMP ? k : 0u] : 0.0f;
+                float sl = vb[k] == q ? gl[k] : 0.0f, sr = vb[k] == q ? gr[k] : 0.0f;
+                float tl = RAMP && vb[k] == q ? dl[RAMP ? k : 0u] : 0.0f, tr = RAMP && vb[k] == q ? dr[RAMP ? k : 0u] : 0.0f;
+                if (SEND) {                                      // gb = M + A: the main gain or +0.0, plus g * s or +0.0 (one rounded add)
+                    const bool on = sq[SEND ? k : 0u] == q;
+                    const float s = sd[SEND ? k : 0u];
+                    const float hl = gl[k] * s, hr = gr[k] * s;
+                    sl = sl + (on ? hl : 0.0f); sr = sr + (on ? hr : 0.0f);
+                    if (RAMP) {
+                        const float el = dl[RAMP ? k : 0u] * s, er = dr[RAMP ? k : 0u] * s;
+                        tl = tl + (on ? el : 0.0f); tr = tr + (on ? er : 0.0f);
+                    }
+                }
 #pragma unroll
                 for (int j = 0; j < W; ++j) {
                     float el = sl, er = sr;
@@ -546,22 +583,24 @@ hipError_t s2r_launch_pan_mix(const S2rPanMix &m, hipStream_t stream) {
     return hipGetLastError();
 }
 
-template <int W, bool RAMP>
-static void bus_mix_launch(const typename BusMixArgs<RAMP>::type &a, uint32_t nb, dim3 grid, dim3 block, size_t lds, hipStream_t stream) {
+template <int W, bool RAMP, bool SEND>
+static void bus_mix_launch(const typename BusMixArgs<RAMP, SEND>::type &a, uint32_t nb, dim3 grid, dim3 block, size_t lds, hipStream_t stream) {
     switch (nb) {
-    case 1: hipLaunchKernelGGL((s2r_bus_mix_kernel<W, 1, RAMP>), grid, block, lds, stream, a); break;
-    case 2: hipLaunchKernelGGL((s2r_bus_mix_kernel<W, 2, RAMP>), grid, block, lds, stream, a); break;
-    case 4: hipLaunchKernelGGL((s2r_bus_mix_kernel<W, 4, RAMP>), grid, block, lds, stream, a); break;
-    default: hipLaunchKernelGGL((s2r_bus_mix_kernel<W, 8, RAMP>), grid, block, lds, stream, a); break;
+    case 1: hipLaunchKernelGGL((s2r_bus_mix_kernel<W, 1, RAMP, SEND>), grid, block, lds, stream, a); break;
+    case 2: hipLaunchKernelGGL((s2r_bus_mix_kernel<W, 2, RAMP, SEND>), grid, block, lds, stream, a); break;
+    case 4: hipLaunchKernelGGL((s2r_bus_mix_kernel<W, 4, RAMP, SEND>), grid, block, lds, stream, a); break;
+    default: hipLaunchKernelGGL((s2r_bus_mix_kernel<W, 8, RAMP, SEND>), grid, block, lds, stream, a); break;
     }
 }
 
 static S2rBusMix &bus_mix_of_host(S2rBusMix &a) { return a; }
 static S2rBusMix &bus_mix_of_host(S2rBusRampMix &a) { return a.m; }
+static S2rBusMix &bus_mix_of_host(S2rBusSendMix &a) { return a.m; }
+static S2rBusMix &bus_mix_of_host(S2rBusSendRampMix &a) { return a.r.m; }
 
-template <bool RAMP>
-static hipError_t bus_mix_launch_any(const typename BusMixArgs<RAMP>::type &in, hipStream_t stream) {
-    typename BusMixArgs<RAMP>::type a = in;
+template <bool RAMP, bool SEND>
+static hipError_t bus_mix_launch_any(const typename BusMixArgs<RAMP, SEND>::type &in, hipStream_t stream) {
+    typename BusMixArgs<RAMP, SEND>::type a = in;
     S2rBusMix &m = bus_mix_of_host(a);
     if (m.frames == 0 || m.n_voices == 0) return hipSuccess;
     if (m.block_voices < 64 || m.block_voices > 1024 || (m.block_voices & 63u) || m.n_blocks * m.block_voices < m.n_voices || m.n_blocks > 65535u ||
@@ -581,17 +620,27 @@ static hipError_t bus_mix_launch_any(const typename BusMixArgs<RAMP>::type &in, 
     uint32_t threads = (n_grp * m.lanes + 63u) & ~63u;            // a thread per run and lane, whole waves, 256 at the most
     if (threads > 256u) threads = 256u;
     const dim3 grid((m.frames + tf - 1u) / tf, m.n_blocks);
-    if (wide) bus_mix_launch<4, RAMP>(a, nb, grid, dim3(threads), lds, stream);
-    else bus_mix_launch<1, RAMP>(a, nb, grid, dim3(threads), lds, stream);
+    if (wide) bus_mix_launch<4, RAMP, SEND>(a, nb, grid, dim3(threads), lds, stream);
+    else bus_mix_launch<1, RAMP, SEND>(a, nb, grid, dim3(threads), lds, stream);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(s2r_bus_combine_kernel, dim3((2u * m.frames * m.n_buses + 255u) / 256u), dim3(256), 0, stream, m);
     return hipGetLastError();
 }
 
-hipError_t s2r_launch_bus_mix(const S2rBusMix &m, hipStream_t stream) { return bus_mix_launch_any<false>(m, stream); }
+hipError_t s2r_launch_bus_mix(const S2rBusMix &m, hipStream_t stream) { return bus_mix_launch_any<false, false>(m, stream); }
 
 hipError_t s2r_launch_bus_mix_ramped(const S2rBusRampMix &r, hipStream_t stream) {
     if (!r.d_l || !r.d_r) return hipErrorInvalidValue;
-    return bus_mix_launch_any<true>(r, stream);
+    return bus_mix_launch_any<true, false>(r, stream);
+}
+
+hipError_t s2r_launch_bus_mix_send(const S2rBusSendMix &a, hipStream_t stream) {
+    if (!a.send || !a.send_bus) return hipErrorInvalidValue;
+    return bus_mix_launch_any<false, true>(a, stream);
+}
+
+hipError_t s2r_launch_bus_mix_send_ramped(const S2rBusSendRampMix &a, hipStream_t stream) {
+    if (!a.send || !a.send_bus || !a.r.d_l || !a.r.d_r) return hipErrorInvalidValue;
+    return bus_mix_launch_any<true, true>(a, stream);
 }

@@ -378,6 +378,20 @@ struct S2rBusRampMix {
     uint32_t frame_base;          // the call-relative frame of m.rows' first frame (a segment's or a slice's start)
 };
 
+// The bus mixdown with aux sends: voice v also feeds bus min(send_bus[v], n_buses - 1) with h_c = g_c * send[v]
+// (under a ramp: H0 = G0 * send, e = d * send), one rounded multiply each, in the kernel; on a bus that is both its main and its
+// send bus its gain is g + h.  The static and the ramped arguments as they are, and the voices' two arrays.
+struct S2rBusSendMix {
+    S2rBusMix m;
+    const float *send;            // [n_blocks * block_voices]: the voice's send in [0, 1], entries past n_voices hold 0
+    const uint8_t *send_bus;      // [n_blocks * block_voices]: the bus it feeds (folded onto n_buses - 1 by the kernel)
+};
+struct S2rBusSendRampMix {
+    S2rBusRampMix r;
+    const float *send;
+    const uint8_t *send_bus;
+};
+
 hipError_t s2r_launch_tables(const S2rTabBuild &b, hipStream_t stream);
 hipError_t s2r_launch_noise_table(float *table_65536, hipStream_t stream);
 // one-pole single-patch handles of one workgroup only (a.p.direct_out set, a.p.frames = the longest fill): false otherwise
@@ -404,3 +418,6 @@ hipError_t s2r_launch_pan_mix(const S2rPanMix &m, hipStream_t stream);
 hipError_t s2r_launch_bus_mix(const S2rBusMix &m, hipStream_t stream);
 // ... and its ramped instantiation (per-frame gains), same geometry, same combine
 hipError_t s2r_launch_bus_mix_ramped(const S2rBusRampMix &r, hipStream_t stream);
+// ... and the two with aux sends
+hipError_t s2r_launch_bus_mix_send(const S2rBusSendMix &a, hipStream_t stream);
+hipError_t s2r_launch_bus_mix_send_ramped(const S2rBusSendRampMix &a, hipStream_t stream);

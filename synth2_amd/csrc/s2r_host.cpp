@@ -309,6 +309,16 @@ struct s2r_synth {
     struct ProgEvent { uint32_t local, frame; uint8_t program; };
     std::vector<ProgEvent> prog_timed;           // like pan_timed
     bool bus_dev_ramped = false;                 // what bus_gains_dev holds was sent for a ramped fill: (G0, step), not the static gains
+    // Aux sends: a send in [0, 1] and a send bus per program beside the bank; what every shard voice got at its
+    // note_on (local order), kept exactly like vgain / vbus.  Nothing of it is touched until a send is set for the first time
+    // (send_used): until then every voice has send 0 and the bus fill launches the kernels and arguments it always did.
+    std::vector<float> prog_send;                // one entry per bank patch
+    std::vector<uint8_t> prog_sbus;
+    bool send_used = false;
+    std::vector<float> vsend;                    // [shard_voices] once send_used
+    std::vector<uint8_t> vsbus;
+    struct SendEvent { uint32_t local, frame; float send; uint8_t bus; };
+    std::vector<SendEvent> send_timed;           // like pan_timed
     float pitch_table[256];
     hipEvent_t t0 = nullptr, t1 = nullptr;
     bool timing = false, timed = false, no_flat_shortcut = false;
@@ -1647,6 +1657,8 @@ int pan_send_gains(s2r_synth *s) {
 }
 
 // ---- the voice mixer: the pans' bookkeeping once more, for the gain and the bus of every voice ----
+// bytes per padded voice of the bus fill's staging buffer: gL, gR, the bus byte, (with sends: the send, the send bus byte,) dL, dR
+constexpr size_t kBusGainBytes = 4 * sizeof(float) + 1 + sizeof(float) + 1;
 inline bool unit_in_range(float x) { return x >= 0.0f && x <= 1.0f; }           // (false for NaN)
 
 void mix_begin(s2r_synth *s) {
@@ -1668,6 +1680,33 @@ inline void mix_note_on(s2r_synth *s, uint32_t local, float velocity, uint32_t f
     const uint8_t bus = s->prog_bus[s->program];
     if (frame == 0) { s->vgain[local] = w; s->vbus[local] = bus; s->gains_dirty = kGainsAll; }
     else s->mix_timed.push_back(s2r_synth::MixEvent{local, frame, w, bus});
+}
+
+// ---- aux sends: the mixer's bookkeeping once more, for the send and the send bus of every voice ----
+int send_begin(s2r_synth *s) {
+    if (s->send_used) return S2R_OK;
+    s->vsend.assign(s->shard_voices, 0.0f);
+    s->vsbus.assign(s->shard_voices, 0u);
+    if (s->bus_gains_host) {                                     // the staging buffer is laid out anew (bus_send_gains): nothing stale in it
+        S2R_HIP(s, hipEventSynchronize(s->bus_gains_sent));
+        std::memset(s->bus_gains_host, 0, s->padded_voices * kBusGainBytes);
+    }
+    s->send_used = true; s->gains_dirty = kGainsAll;
+    return S2R_OK;
+}
+
+void send_settle(s2r_synth *s) {
+    if (s->send_timed.empty() || s->fill_time != 0) return;
+    for (const s2r_synth::SendEvent &e : s->send_timed) { s->vsend[e.local] = e.send; s->vsbus[e.local] = e.bus; }
+    s->send_timed.clear();
+    s->gains_dirty = kGainsAll;
+}
+
+inline void send_note_on(s2r_synth *s, uint32_t local, uint32_t frame) {
+    const float sd = s->prog_send[s->program];
+    const uint8_t bus = s->prog_sbus[s->program];
+    if (frame == 0) { s->vsend[local] = sd; s->vsbus[local] = bus; s->gains_dirty = kGainsAll; }
+    else s->send_timed.push_back(s2r_synth::SendEvent{local, frame, sd, bus});
 }
 
 // ---- program faders ----
@@ -1717,14 +1756,17 @@ inline bool faders_moving(const s2r_synth *s) {
 // what the bus mixdown reads per voice — both pan gains times the voice's gain (one rounded multiply each), times its program's
 // applied fader once faders are in use, and the bus byte — from pinned memory to the device on the handle's stream (when a pan, a
 // mix or a fader changed).  `ramp`: a bus fill of `total` frames with a fader on its way: the gains under the applied pairs and,
-// behind the bus bytes, their steps per frame towards the gains under the targets — one staging buffer, one copy.
+// behind the bus bytes, their steps per frame towards the gains under the targets — one staging buffer, one copy.  Once sends are
+// in use the voices' sends and send bus bytes lie between the bus bytes and the steps (bus_static_bytes), in the same copy.
+inline size_t bus_static_bytes(const s2r_synth *s) { return s->padded_voices * (2 * sizeof(float) + 1 + (s->send_used ? sizeof(float) + 1 : 0)); }
+
 int bus_send_gains(s2r_synth *s, bool ramp, uint32_t total) {
     if (!(s->gains_dirty & kGainsBus) && s->bus_dev_ramped == ramp) return S2R_OK;
-    const size_t pv = s->padded_voices, static_bytes = pv * (2 * sizeof(float) + 1), bytes = pv * (4 * sizeof(float) + 1);
+    const size_t pv = s->padded_voices, static_bytes = bus_static_bytes(s), bytes = static_bytes + pv * 2 * sizeof(float);
     if (!s->bus_gains_host) {
-        S2R_HIP(s, hipHostMalloc((void **)&s->bus_gains_host, bytes, hipHostMallocDefault));
-        std::memset(s->bus_gains_host, 0, bytes);
-        S2R_HIP(s, hipMalloc((void **)&s->bus_gains_dev, bytes));
+        S2R_HIP(s, hipHostMalloc((void **)&s->bus_gains_host, pv * kBusGainBytes, hipHostMallocDefault));
+        std::memset(s->bus_gains_host, 0, pv * kBusGainBytes);
+        S2R_HIP(s, hipMalloc((void **)&s->bus_gains_dev, pv * kBusGainBytes));
         S2R_HIP(s, hipEventCreateWithFlags(&s->bus_gains_sent, hipEventDisableTiming));
     } else S2R_HIP(s, hipEventSynchronize(s->bus_gains_sent));
     float *g = reinterpret_cast<float *>(s->bus_gains_host);
@@ -1732,6 +1774,10 @@ int bus_send_gains(s2r_synth *s, bool ramp, uint32_t total) {
     float *d = reinterpret_cast<float *>(s->bus_gains_host + static_bytes);
     const size_t n_prog = s->prog_fader.size();
     const float fn = (float)total;
+    if (s->send_used) {
+        std::memcpy(s->bus_gains_host + pv * (2 * sizeof(float) + 1), s->vsend.data(), (size_t)s->shard_voices * sizeof(float));
+        std::memcpy(s->bus_gains_host + pv * (3 * sizeof(float) + 1), s->vsbus.data(), (size_t)s->shard_voices);
+    }
     for (uint32_t i = 0; i < s->shard_voices; i++) {
         const float pan = s->pan_used ? s->pans[i] : 0.0f, w = s->mix_used ? s->vgain[i] : 1.0f;
         b[i] = s->mix_used ? s->vbus[i] : (uint8_t)0;
@@ -1798,10 +1844,22 @@ int pan_segment(s2r_synth *s, uint32_t at, uint32_t n, uint32_t last_event, uint
             if (ramp) {
                 S2rBusRampMix rm{};
                 rm.m = bm;
-                rm.d_l = reinterpret_cast<const float *>(s->bus_gains_dev + s->padded_voices * (2 * sizeof(float) + 1));
+                rm.d_l = reinterpret_cast<const float *>(s->bus_gains_dev + bus_static_bytes(s));
                 rm.d_r = rm.d_l + s->padded_voices;
                 rm.frame_base = at + done;
-                S2R_HIP(s, s2r_launch_bus_mix_ramped(rm, s->stream));
+                if (s->send_used) {
+                    S2rBusSendRampMix sm{};
+                    sm.r = rm;
+                    sm.send = reinterpret_cast<const float *>(s->bus_gains_dev + s->padded_voices * (2 * sizeof(float) + 1));
+                    sm.send_bus = reinterpret_cast<const uint8_t *>(sm.send + s->padded_voices);
+                    S2R_HIP(s, s2r_launch_bus_mix_send_ramped(sm, s->stream));
+                } else S2R_HIP(s, s2r_launch_bus_mix_ramped(rm, s->stream));
+            } else if (s->send_used) {
+                S2rBusSendMix sm{};
+                sm.m = bm;
+                sm.send = reinterpret_cast<const float *>(s->bus_gains_dev + s->padded_voices * (2 * sizeof(float) + 1));
+                sm.send_bus = reinterpret_cast<const uint8_t *>(sm.send + s->padded_voices);
+                S2R_HIP(s, s2r_launch_bus_mix_send(sm, s->stream));
             } else S2R_HIP(s, s2r_launch_bus_mix(bm, s->stream));
         } else S2R_HIP(s, s2r_launch_pan_mix(m, s->stream));
         if (s->timing) { S2R_HIP(s, hipEventRecord(s->pan_ev[s->pan_ev_used + 1], s->stream)); s->pan_ev_used += 2; }
@@ -2022,6 +2080,7 @@ static int create_single(const s2r_config *cfg, std::shared_ptr<S2rVoicePool> po
     s->bank.resize(1);
     s->prog_pan.assign(1, 0.0f); s->prog_spread.assign(1, 0.0f);
     s->prog_level.assign(1, 1.0f); s->prog_sens.assign(1, 0.0f); s->prog_bus.assign(1, 0u);
+    s->prog_send.assign(1, 0.0f); s->prog_sbus.assign(1, 0u);
     s->prog_fader.assign(1, 1.0f); s->prog_shift.assign(1, 0.0f); s->prog_fader_app.assign(1, 1.0f); s->prog_shift_app.assign(1, 0.0f);
     s2r_default_patch(&s->bank[0]);
     if (pool) s->pool = pool;
@@ -2277,6 +2336,7 @@ int s2r_set_patch_bank(s2r_synth *s, const s2r_patch *patches, uint32_t n) {
     s->prog_pan.resize(n, 0.0f); s->prog_spread.resize(n, 0.0f);   // the surviving programs keep their pans
     s->prog_level.resize(n, 1.0f); s->prog_sens.resize(n, 0.0f); s->prog_bus.resize(n, 0u);      // ... and their mix
     s->prog_fader.resize(n, 1.0f); s->prog_shift.resize(n, 0.0f); s->prog_fader_app.resize(n, 1.0f); s->prog_shift_app.resize(n, 0.0f);   // ... and faders
+    s->prog_send.resize(n, 0.0f); s->prog_sbus.resize(n, 0u);    // ... and sends
     if (s->fader_used) s->gains_dirty = kGainsAll;               // (a voice whose program fell off the bank follows program 0 now)
     if (s->program >= n) s->program = 0;
     s->bank_dirty = true; s->tab_dirty = true;
@@ -2327,11 +2387,12 @@ int s2r_note_on_ex(s2r_synth *s, uint8_t note, float velocity, uint32_t *voice_i
     const uint32_t i = s->pool->note_on(note, velocity);
     if (voice_index_out) *voice_index_out = i;
     if (s->voice_log) s->voice_log(s->voice_log_user, i, note);
-    if ((s->pan_used | s->mix_used | s->fader_used) && s->kids.empty()) {
+    if ((s->pan_used | s->mix_used | s->fader_used | s->send_used) && s->kids.empty()) {
         const int64_t mine = to_local(s, i);
         if (s->pan_used) { pan_settle(s); if (mine >= 0) pan_note_on(s, (uint32_t)mine, note, 0u); }
         if (s->mix_used) { mix_settle(s); if (mine >= 0) mix_note_on(s, (uint32_t)mine, velocity, 0u); }
         if (s->fader_used) { prog_settle(s); if (mine >= 0) prog_note_on(s, (uint32_t)mine, 0u); }
+        if (s->send_used) { send_settle(s); if (mine >= 0) send_note_on(s, (uint32_t)mine, 0u); }
     }
     if (!append_frame0_record(s, i, S2R_EV_RESTART, s->pitch_table[note], s->seed_override[i], s->program))
         push_event(s, i, S2R_EV_RESTART, s->pitch_table[note], s->seed_override[i], s->program);
@@ -2379,7 +2440,7 @@ int s2r_note_events(s2r_synth *s, const s2r_note_event *events, size_t n) {
     // and note_off over the events computes — on several threads for a multi-GPU-sized batch): the voice every event takes or
     // releases.  An event inside the next fill first moves the pool's clock to its frame (the policy sees the offsets every
     // voice has AT that frame, like the reference between two 16-frame calls); frame-0 events take effect before the fill.
-    if (s->pan_used | s->mix_used | s->fader_used) { pan_settle(s); mix_settle(s); prog_settle(s); }      // (while fill_time still says whether the last fill's events are behind us)
+    if (s->pan_used | s->mix_used | s->fader_used | s->send_used) { pan_settle(s); mix_settle(s); prog_settle(s); send_settle(s); }      // (while fill_time still says whether the last fill's events are behind us)
     static thread_local std::vector<int64_t> chosen;
     if (chosen.size() < n) chosen.resize(n);
     static_assert(sizeof(S2rPolicyEvent) == 4 && S2R_NOTE_ON == S2R_POLICY_NOTE_ON && S2R_NOTE_OFF == S2R_POLICY_NOTE_OFF, "s2r_note_event's first four bytes");
@@ -2420,10 +2481,11 @@ int s2r_note_events(s2r_synth *s, const s2r_note_event *events, size_t n) {
         }
         const uint32_t frame = e.frame;
         const bool on = e.kind == S2R_NOTE_ON;
-        if (on && one && (one->pan_used | one->mix_used | one->fader_used)) {
+        if (on && one && (one->pan_used | one->mix_used | one->fader_used | one->send_used)) {
             if (one->pan_used) pan_note_on(one, local, e.note, frame);
             if (one->mix_used) mix_note_on(one, local, e.velocity, frame);
             if (one->fader_used) prog_note_on(one, local, frame);
+            if (one->send_used) send_note_on(one, local, frame);
         }
         if (frame == 0 && may_fold && sh->tpending.empty()) {
             if (on) push_event(s, (uint32_t)vi, S2R_EV_RESTART, pitch_of[e.note], seed_of[(size_t)vi], s->program);
@@ -2596,7 +2658,7 @@ static int fill_rows_mixed(s2r_synth *s, float *out, size_t capacity, uint32_t n
         S2R_HIP(s, hipHostGetDevicePointer((void **)&s->bus_out_dev, s->bus_out, 0));
     }
     fold_frame0_records(s);
-    pan_settle(s); mix_settle(s); prog_settle(s);
+    pan_settle(s); mix_settle(s); prog_settle(s); send_settle(s);
     s->pan_ev_used = 0;
     const uint32_t last_event = s->fill_time;
     // a bus fill with a program fader away from where the last one left it ramps; whatever the device holds from
@@ -2620,7 +2682,9 @@ static int fill_rows_mixed(s2r_synth *s, float *out, size_t capacity, uint32_t n
         mev.swap(s->mix_timed);
         std::vector<s2r_synth::ProgEvent> gev;
         gev.swap(s->prog_timed);
-        size_t k = 0, kp = 0, km = 0, kg = 0;
+        std::vector<s2r_synth::SendEvent> sev;
+        sev.swap(s->send_timed);
+        size_t k = 0, kp = 0, km = 0, kg = 0, ks = 0;
         uint32_t at = 0;
         while (at < frames) {
             for (; k < recs.size() && recs[k].frame <= at; k++) {
@@ -2639,6 +2703,7 @@ static int fill_rows_mixed(s2r_synth *s, float *out, size_t capacity, uint32_t n
             const uint32_t next = k < recs.size() && recs[k].frame < frames ? recs[k].frame : (uint32_t)frames;
             for (; km < mev.size() && mev[km].frame <= at; km++) { s->vgain[mev[km].local] = mev[km].gain; s->vbus[mev[km].local] = mev[km].bus; s->gains_dirty = kGainsAll; }
             for (; kg < gev.size() && gev[kg].frame <= at; kg++) { s->vprog[gev[kg].local] = gev[kg].program; s->gains_dirty = kGainsAll; }
+            for (; ks < sev.size() && sev[ks].frame <= at; ks++) { s->vsend[sev[ks].local] = sev[ks].send; s->vsbus[sev[ks].local] = sev[ks].bus; s->gains_dirty = kGainsAll; }
             rc = pan_segment(s, at, next - at, last_event, sample_rate_hz, n_buses, (uint32_t)frames, ramp);
             if (rc != S2R_OK) { s->fill_time = 0; return rc; }
             at = next;
@@ -2711,6 +2776,58 @@ int s2r_set_voice_mix(s2r_synth *s, const float *gains, const uint8_t *buses) {
     mix_settle(s);
     std::memcpy(s->vgain.data(), gains, (size_t)s->shard_voices * sizeof(float));
     std::memcpy(s->vbus.data(), buses, (size_t)s->shard_voices);
+    s->gains_dirty = kGainsAll;
+    return S2R_OK;
+}
+
+// ---- aux sends ----
+float s2r_send_gain(float g, float send) { return g * send; }
+
+int s2r_set_program_send(s2r_synth *s, uint32_t program, float send, uint32_t send_bus) {
+    // (the values first, like s2r_set_program_mix)
+    if (!unit_in_range(send) || send_bus >= S2R_MAX_BUSES)
+        return set_err(s, S2R_ERR_PATCH_RANGE, "program %u: send %g, send bus %u: the send lies in [0, 1], the bus below %u", program, (double)send, send_bus, S2R_MAX_BUSES);
+    if (!s) return S2R_ERR_INVALID;
+    if (!s->kids.empty() || s->parent) return set_err(s, S2R_ERR_INVALID, "program sends are kept by single-device handles, not by a device list");
+    if (program >= s->bank.size()) return set_err(s, S2R_ERR_INVALID, "program %u: the bank holds %zu patches", program, s->bank.size());
+    if (send != 0.0f || send_bus != 0u) {
+        const int rc = send_begin(s);
+        if (rc != S2R_OK) return rc;
+        send_settle(s);
+    }
+    s->prog_send[program] = send; s->prog_sbus[program] = (uint8_t)send_bus;
+    return S2R_OK;
+}
+
+int s2r_get_program_send(const s2r_synth *s, uint32_t program, float *send, uint32_t *send_bus) {
+    if (!s) return S2R_ERR_INVALID;
+    if (!s->kids.empty() || s->parent || program >= s->bank.size()) return S2R_ERR_INVALID;
+    if (send) *send = s->prog_send[program];
+    if (send_bus) *send_bus = s->prog_sbus[program];
+    return S2R_OK;
+}
+
+int s2r_get_voice_sends(s2r_synth *s, float *sends, uint8_t *send_buses) {
+    if (!s || !sends || !send_buses) return S2R_ERR_INVALID;
+    if (!s->kids.empty() || s->parent) return set_err(s, S2R_ERR_INVALID, "voice sends are kept by single-device handles, not by a device list");
+    if (!s->send_used) { std::fill(sends, sends + s->shard_voices, 0.0f); std::memset(send_buses, 0, s->shard_voices); return S2R_OK; }
+    send_settle(s);
+    std::memcpy(sends, s->vsend.data(), (size_t)s->shard_voices * sizeof(float));
+    std::memcpy(send_buses, s->vsbus.data(), (size_t)s->shard_voices);
+    return S2R_OK;
+}
+
+int s2r_set_voice_sends(s2r_synth *s, const float *sends, const uint8_t *send_buses) {
+    if (!s || !sends || !send_buses) return S2R_ERR_INVALID;
+    if (!s->kids.empty() || s->parent) return set_err(s, S2R_ERR_INVALID, "voice sends are kept by single-device handles, not by a device list");
+    for (uint32_t i = 0; i < s->shard_voices; i++)
+        if (!unit_in_range(sends[i]) || send_buses[i] >= S2R_MAX_BUSES)
+            return set_err(s, S2R_ERR_PATCH_RANGE, "voice %u: send %g, send bus %u: the send lies in [0, 1], the bus below %u", i, (double)sends[i], (unsigned)send_buses[i], S2R_MAX_BUSES);
+    const int rc = send_begin(s);
+    if (rc != S2R_OK) return rc;
+    send_settle(s);
+    std::memcpy(s->vsend.data(), sends, (size_t)s->shard_voices * sizeof(float));
+    std::memcpy(s->vsbus.data(), send_buses, (size_t)s->shard_voices);
     s->gains_dirty = kGainsAll;
     return S2R_OK;
 }

@@ -182,6 +182,11 @@ def load_library():
         "s2r_get_program_fader": (C.c_int, [H, C.c_uint32, _f32p, _f32p, _f32p, _f32p]),
         "s2r_snap_program_faders": (C.c_int, [H]),
         "s2r_fader_gains": (None, [C.c_float, C.c_float, C.c_float, C.c_float, _f32p, _f32p]),
+        "s2r_set_program_send": (C.c_int, [H, C.c_uint32, C.c_float, C.c_uint32]),
+        "s2r_get_program_send": (C.c_int, [H, C.c_uint32, _f32p, C.POINTER(C.c_uint32)]),
+        "s2r_get_voice_sends": (C.c_int, [H, _f32p, C.POINTER(C.c_uint8)]),
+        "s2r_set_voice_sends": (C.c_int, [H, _f32p, C.POINTER(C.c_uint8)]),
+        "s2r_send_gain": (C.c_float, [C.c_float, C.c_float]),
         "s2r_fill_device": (C.c_int, [H, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
         "s2r_fill_device_root": (C.c_int, [H, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
         "s2r_sum_partials_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_size_t, C.c_void_p, C.c_void_p]),
@@ -219,6 +224,8 @@ def load_library():
         "s2r_voice_pool_query": (C.c_int, [H, C.c_uint32, C.POINTER(VoiceState)]),
     }
     for name, (res, args) in sig.items():
+        if _build.AB_LIB and not hasattr(L, name):               # (a library kept from an older build of these sources: A/B timing)
+            continue
         f = getattr(L, name)
         f.restype = res
         f.argtypes = args
@@ -270,6 +277,11 @@ def fader_gains(pan, w, fader, pan_shift):
     gl, gr = C.c_float(), C.c_float()
     load_library().s2r_fader_gains(float(pan), float(w), float(fader), float(pan_shift), C.byref(gl), C.byref(gr))
     return gl.value, gr.value
+
+
+def send_gain(g, send):
+    """the gain of a voice's aux send: g * send, one rounded binary32 multiply (s2r_send_gain; host only)"""
+    return float(load_library().s2r_send_gain(float(g), float(send)))
 
 
 def stream_frame_json(samples):
@@ -530,6 +542,34 @@ class Synth:
     def snap_program_faders(self):
         """applied = target for every program, now (a hard cut; restoring a checkpoint: set the applied values, snap, set the targets)"""
         self._check(self.L.s2r_snap_program_faders(self.h))
+
+    # --- aux sends (build-defined; s2r.h: s2r_set_program_send) ---
+    def set_program_send(self, program, send=0.0, send_bus=0):
+        """the aux send (in [0, 1]) and the bus it feeds (below MAX_BUSES) of a bank program: what a note_on under that program
+        gives its voice — a second feed of gain * send, post-pan and post-fader, onto send_bus.  Only sample_buses applies them."""
+        self._check(self.L.s2r_set_program_send(self.h, int(program), float(send), int(send_bus)))
+
+    def get_program_send(self, program):
+        send, bus = C.c_float(), C.c_uint32()
+        self._check(self.L.s2r_get_program_send(self.h, int(program), C.byref(send), C.byref(bus)))
+        return send.value, bus.value
+
+    def voice_sends(self):
+        """(sends float32, send buses uint8) of every shard voice, local order (checkpoint companions of voice_mix)"""
+        sends = np.empty(self.shard_voices, dtype=np.float32)
+        buses = np.empty(self.shard_voices, dtype=np.uint8)
+        self._check(self.L.s2r_get_voice_sends(self.h, sends.ctypes.data_as(_f32p), buses.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return sends, buses
+
+    def set_voice_sends(self, sends, send_buses):
+        g = np.ascontiguousarray(sends, dtype=np.float32)
+        b = np.ascontiguousarray(send_buses, dtype=np.uint8)
+        assert g.size == self.shard_voices and b.size == self.shard_voices
+        self._check(self.L.s2r_set_voice_sends(self.h, g.ctypes.data_as(_f32p), b.ctypes.data_as(C.POINTER(C.c_uint8))))
+
+    @staticmethod
+    def send_gain(g, send):
+        return send_gain(g, send)
 
     def render_voices(self, frames, sample_rate=SampleRateKhz(48000)):
         """Mix disabled: (shard_voices, frames) float32."""
