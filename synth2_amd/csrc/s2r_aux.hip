@@ -130,11 +130,51 @@ __global__ void s2r_decimate4_history_kernel(float *x, uint32_t n_out) {
 //   voice's value — sixteen independent loads in flight (16 bytes each where the rows allow it: W = 4), every element read once
 //   and multiplied by both of its voice's gains — the run sums meet in LDS and are added in run order; voices past the pool add
 //   +0.0 (a row of +0.0 times a gain of 0).  The L and R partial rows go to memory.
-//   s2r_pan_combine_kernel: one thread per output float adds the workgroups' rows: runs of 16 sequentially, the run sums within
-//   a mix group, the groups onto a root of +0.0.
+//   s2r_pan_combine_kernel: one thread per output float adds the workgroups' rows (combine_partials).
 // No atomics, no order that depends on timing.  -ffp-contract=off: a product and the sum that takes it stay two roundings.
 // ---------------------------------------------------------------------------------------
 constexpr uint32_t kPanLanes = 32;                               // threads along frames; 256 / 32 = 8 runs of voices side by side
+
+// What the panned and the bus mixdown share.  One voice's part of a run's rows, x[16][W]: W consecutive frames from f0 — 16 bytes
+// where the rows allow it (W == 4: the launcher has checked alignment and whole quads), else a frame per thread; +0.0 past the
+// pool (!in_pool) and past the fill.  `src`: the voice's row at frame f0.
+template <int W>
+__device__ __forceinline__ void load_row(float (&x)[W], const float *src, bool in_pool, uint32_t f0, uint32_t frames) {
+    if (W == 4) {
+        const f4 q = (in_pool && f0 < frames) ? *reinterpret_cast<const f4 *>(src) : (f4){0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int j = 0; j < W; ++j) x[j] = q[j];
+    } else {
+#pragma unroll
+        for (int j = 0; j < W; ++j) x[j] = (in_pool && f0 + (uint32_t)j < frames) ? src[j] : 0.0f;
+    }
+}
+
+// One output float of a combine kernel: frame f of row c of every workgroup's partial rows, [n_blocks][rows_per_block][pstride],
+// added as DESIGN.md 4.3 says — runs of kMixRun workgroups sequentially, the run sums within a mix group, the groups onto a
+// root of +0.0.
+__device__ __forceinline__ float combine_partials(const float *partials, uint32_t rows_per_block, uint32_t c, uint32_t pstride, uint32_t f,
+                                                  uint32_t n_blocks, uint32_t blocks_per_group, uint32_t n_groups) {
+    float total = 0.0f;                                          // accum = splat(0.0), synth.rs:176
+    for (uint32_t g = 0; g < n_groups; ++g) {
+        const uint32_t gb0 = g * blocks_per_group;
+        uint32_t gb1 = gb0 + blocks_per_group; if (gb1 > n_blocks) gb1 = n_blocks;
+        if (gb0 >= gb1) continue;
+        float grp = 0.0f;
+        for (uint32_t r0 = gb0; r0 < gb1; r0 += kMixRun) {
+            const uint32_t r1 = r0 + kMixRun < gb1 ? r0 + kMixRun : gb1;
+            float v[kMixRun];
+#pragma unroll
+            for (uint32_t j = 0; j < kMixRun; ++j) v[j] = (r0 + j < r1) ? partials[((size_t)(r0 + j) * rows_per_block + c) * pstride + f] : 0.0f;
+            float acc = v[0];
+#pragma unroll
+            for (uint32_t j = 1; j < kMixRun; ++j) if (r0 + j < r1) acc = acc + v[j];
+            grp = (r0 == gb0) ? acc : grp + acc;
+        }
+        total = total + grp;
+    }
+    return total;
+}
 
 template <int W>
 __global__ void __launch_bounds__(256) s2r_pan_mix_kernel(const S2rPanMix m) {
@@ -150,15 +190,7 @@ __global__ void __launch_bounds__(256) s2r_pan_mix_kernel(const S2rPanMix m) {
         for (uint32_t k = 0; k < 16u; ++k) {
             const uint32_t v = v0 + k;
             gl[k] = m.gain_l[v]; gr[k] = m.gain_r[v];            // (padded with 0 up to the grid's last voice)
-            const float *src = m.rows + (size_t)v * m.stride + f0;
-            if (W == 4) {
-                const f4 q = (v < m.n_voices && f0 < m.frames) ? *reinterpret_cast<const f4 *>(src) : (f4){0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-                for (int j = 0; j < W; ++j) x[k][j] = q[j];
-            } else {
-#pragma unroll
-                for (int j = 0; j < W; ++j) x[k][j] = (v < m.n_voices && f0 + (uint32_t)j < m.frames) ? src[j] : 0.0f;
-            }
+            load_row<W>(x[k], m.rows + (size_t)v * m.stride + f0, v < m.n_voices, f0, m.frames);
         }
         float al[W], ar[W];
 #pragma unroll
@@ -185,25 +217,7 @@ __global__ void __launch_bounds__(256) s2r_pan_combine_kernel(const S2rPanMix m)
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;    // out[i]: frame i / 2, channel i & 1
     const uint32_t f = i >> 1, c = i & 1u;
     if (f >= m.frames) return;
-    float total = 0.0f;                                          // accum = splat(0.0), synth.rs:176
-    for (uint32_t g = 0; g < m.n_groups; ++g) {
-        const uint32_t gb0 = g * m.blocks_per_group;
-        uint32_t gb1 = gb0 + m.blocks_per_group; if (gb1 > m.n_blocks) gb1 = m.n_blocks;
-        if (gb0 >= gb1) continue;
-        float grp = 0.0f;
-        for (uint32_t r0 = gb0; r0 < gb1; r0 += kMixRun) {
-            const uint32_t r1 = r0 + kMixRun < gb1 ? r0 + kMixRun : gb1;
-            float v[kMixRun];
-#pragma unroll
-            for (uint32_t j = 0; j < kMixRun; ++j) v[j] = (r0 + j < r1) ? m.partials[((size_t)(r0 + j) * 2u + c) * m.pstride + f] : 0.0f;
-            float acc = v[0];
-#pragma unroll
-            for (uint32_t j = 1; j < kMixRun; ++j) if (r0 + j < r1) acc = acc + v[j];
-            grp = (r0 == gb0) ? acc : grp + acc;
-        }
-        total = total + grp;
-    }
-    m.out[i] = total;
+    m.out[i] = combine_partials(m.partials, 2u, c, m.pstride, f, m.n_blocks, m.blocks_per_group, m.n_groups);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -211,7 +225,7 @@ __global__ void __launch_bounds__(256) s2r_pan_combine_kernel(const S2rPanMix m)
 // x[v][i] = row[v][i] * gb_c[v], gb_c[v] = (min(bus[v], n_buses - 1) == q) ? g_c[v] : +0.0 (g_c: the pan gain times the voice's
 // gain, multiplied on the host), through the same tree as the panned mixdown above — an off-bus voice is a term of row * +0.0,
 // not a skipped one.
-//   s2r_bus_mix_kernel<W, NB>: the geometry of s2r_pan_mix_kernel — workgroup (tile, b), a thread adds ONE run of 16 voices for W
+//   s2r_bus_mix_kernel<W, NB, RAMP, SEND>: the geometry of s2r_pan_mix_kernel — workgroup (tile, b), a thread adds ONE run of 16 voices for W
 //   consecutive frames — with `lanes` threads along the frames: the launcher halves the tile until [block_voices / 16][2 * NB][tile]
 //   floats fit 32 KiB of LDS, so that several workgroups share a compute unit.  The run's 16 x W row elements are loaded once and
 //   stay in registers; bus after bus (NB is compiled in: no indexed accumulator, nothing in scratch) the sixteen gains are
@@ -221,45 +235,21 @@ __global__ void __launch_bounds__(256) s2r_pan_combine_kernel(const S2rPanMix m)
 // ---------------------------------------------------------------------------------------
 constexpr uint32_t kBusLdsBytes = 32u << 10;
 
-//   RAMP (program faders moving): the gain of a voice is G0 + (float)i * d at frame i of the CALL — the arguments
-//   carry the call-relative frame of the rows' first frame.  Per bus the run selects (G0, d) once per voice and channel, exactly as
-//   the static form selects its gain (an off-bus voice: +0.0 + i * +0.0 = +0.0), and every element takes a multiply and an add for
-//   its gain in front of the static form's multiply and add: nothing but the sixteen voices' two steps and W frame numbers is
-//   added to the registers the run keeps live.  RAMP = false compiles to the static kernel, instruction for instruction.
-//   SEND (aux sends): a voice feeds a second bus with its gain times its send, h = g * s (one rounded multiply,
-//   here: the arguments carry the voices' s and send bus, so the run keeps 32 more values live, not the 48 or 80 of gains multiplied
-//   on the host).  Per bus the run selects the main gain and the send's gain with a compare each and adds them once per voice and
+// One argument block (S2rBusMix) for every form; the launcher compiles in which of its optional pointers are given.
+//   RAMP (d_l, d_r given: program faders moving): the gain of a voice is G0 + (float)i * d at frame i of the CALL —
+//   frame_base is the call-relative frame of the rows' first frame.  Per bus the run selects (G0, d) once per voice and channel,
+//   exactly as the static form selects its gain (an off-bus voice: +0.0 + i * +0.0 = +0.0), and every element takes a multiply and
+//   an add for its gain in front of the static form's multiply and add: nothing but the sixteen voices' two steps and W frame
+//   numbers is added to the registers the run keeps live.
+//   SEND (send, send_bus given: aux sends): a voice feeds a second bus with its gain times its send, h = g * s (one
+//   rounded multiply, here: the run keeps the voices' s and send bus live, 32 more values, not the 48 or 80 of gains multiplied on
+//   the host).  Per bus the run selects the main gain and the send's gain with a compare each and adds them once per voice and
 //   channel — M + A, and under RAMP likewise for the step — before the W frames are touched; with s = 0 the sum is M bit for bit
-//   (gains are finite and not negative).  SEND = false takes the arguments above and compiles to the same instructions as before.
-template <bool RAMP, bool SEND> struct BusMixArgs { typedef S2rBusMix type; };
-template <> struct BusMixArgs<true, false> { typedef S2rBusRampMix type; };
-template <> struct BusMixArgs<false, true> { typedef S2rBusSendMix type; };
-template <> struct BusMixArgs<true, true> { typedef S2rBusSendRampMix type; };
-__device__ __forceinline__ const S2rBusMix &bus_mix_of(const S2rBusMix &a) { return a; }
-__device__ __forceinline__ const S2rBusMix &bus_mix_of(const S2rBusRampMix &a) { return a.m; }
-__device__ __forceinline__ const S2rBusMix &bus_mix_of(const S2rBusSendMix &a) { return a.m; }
-__device__ __forceinline__ const S2rBusMix &bus_mix_of(const S2rBusSendRampMix &a) { return a.r.m; }
-__device__ __forceinline__ const float *bus_step_of(const S2rBusMix &, int) { return nullptr; }
-__device__ __forceinline__ const float *bus_step_of(const S2rBusRampMix &a, int c) { return c ? a.d_r : a.d_l; }
-__device__ __forceinline__ const float *bus_step_of(const S2rBusSendMix &, int) { return nullptr; }
-__device__ __forceinline__ const float *bus_step_of(const S2rBusSendRampMix &a, int c) { return c ? a.r.d_r : a.r.d_l; }
-__device__ __forceinline__ uint32_t bus_base_of(const S2rBusMix &) { return 0u; }
-__device__ __forceinline__ uint32_t bus_base_of(const S2rBusRampMix &a) { return a.frame_base; }
-__device__ __forceinline__ uint32_t bus_base_of(const S2rBusSendMix &) { return 0u; }
-__device__ __forceinline__ uint32_t bus_base_of(const S2rBusSendRampMix &a) { return a.r.frame_base; }
-__device__ __forceinline__ const float *bus_send_of(const S2rBusMix &) { return nullptr; }
-__device__ __forceinline__ const float *bus_send_of(const S2rBusRampMix &) { return nullptr; }
-__device__ __forceinline__ const float *bus_send_of(const S2rBusSendMix &a) { return a.send; }
-__device__ __forceinline__ const float *bus_send_of(const S2rBusSendRampMix &a) { return a.send; }
-__device__ __forceinline__ const uint8_t *bus_sbus_of(const S2rBusMix &) { return nullptr; }
-__device__ __forceinline__ const uint8_t *bus_sbus_of(const S2rBusRampMix &) { return nullptr; }
-__device__ __forceinline__ const uint8_t *bus_sbus_of(const S2rBusSendMix &a) { return a.send_bus; }
-__device__ __forceinline__ const uint8_t *bus_sbus_of(const S2rBusSendRampMix &a) { return a.send_bus; }
-
+//   (gains are finite and not negative).
+//   A form that is compiled out reads none of its pointers and keeps none of its values.
 template <int W, int NB, bool RAMP, bool SEND>
-__global__ void __launch_bounds__(256) s2r_bus_mix_kernel(const typename BusMixArgs<RAMP, SEND>::type a) {
+__global__ void __launch_bounds__(256) s2r_bus_mix_kernel(const S2rBusMix m) {
     extern __shared__ float s_bus[];                             // [block_voices / 16][2 * NB][lanes * W]
-    const S2rBusMix &m = bus_mix_of(a);
     const uint32_t lanes = m.lanes, TF = lanes * (uint32_t)W;
     const uint32_t lane = threadIdx.x & (lanes - 1u), slot = threadIdx.x / lanes, n_slots = blockDim.x / lanes;
     const uint32_t b = blockIdx.y, fl = lane * (uint32_t)W, f0 = blockIdx.x * TF + fl;
@@ -272,29 +262,21 @@ __global__ void __launch_bounds__(256) s2r_bus_mix_kernel(const typename BusMixA
         uint32_t vb[16], sq[SEND ? 16 : 1];
         if (RAMP) {
 #pragma unroll
-            for (int j = 0; j < W; ++j) fi[RAMP ? j : 0] = (float)(bus_base_of(a) + f0 + (uint32_t)j);      // i of the call, not of the slice
+            for (int j = 0; j < W; ++j) fi[RAMP ? j : 0] = (float)(m.frame_base + f0 + (uint32_t)j);      // i of the call, not of the slice
         }
 #pragma unroll
         for (uint32_t k = 0; k < 16u; ++k) {
             const uint32_t v = v0 + k;
             gl[k] = m.gain_l[v]; gr[k] = m.gain_r[v];            // (padded with 0 up to the grid's last voice)
-            if (RAMP) { dl[RAMP ? k : 0u] = bus_step_of(a, 0)[v]; dr[RAMP ? k : 0u] = bus_step_of(a, 1)[v]; }
+            if (RAMP) { dl[RAMP ? k : 0u] = m.d_l[v]; dr[RAMP ? k : 0u] = m.d_r[v]; }
             const uint32_t q = m.bus[v];
             vb[k] = q < last ? q : last;                         // a voice booked past the call's buses sounds on the last one
             if (SEND) {
-                sd[SEND ? k : 0u] = bus_send_of(a)[v];
-                const uint32_t t = bus_sbus_of(a)[v];
+                sd[SEND ? k : 0u] = m.send[v];
+                const uint32_t t = m.send_bus[v];
                 sq[SEND ? k : 0u] = t < last ? t : last;         // ... and so does its send
             }
-            const float *src = m.rows + (size_t)v * m.stride + f0;
-            if (W == 4) {
-                const f4 r = (v < m.n_voices && f0 < m.frames) ? *reinterpret_cast<const f4 *>(src) : (f4){0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-                for (int j = 0; j < W; ++j) x[k][j] = r[j];
-            } else {
-#pragma unroll
-                for (int j = 0; j < W; ++j) x[k][j] = (v < m.n_voices && f0 + (uint32_t)j < m.frames) ? src[j] : 0.0f;
-            }
+            load_row<W>(x[k], m.rows + (size_t)v * m.stride + f0, v < m.n_voices, f0, m.frames);
         }
 #pragma unroll
         for (uint32_t q = 0; q < (uint32_t)NB; ++q) {
@@ -349,26 +331,7 @@ __global__ void __launch_bounds__(256) s2r_bus_combine_kernel(const S2rBusMix m)
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;    // bus i / (2 * frames); inside it frame r / 2, channel r & 1
     const uint32_t per = 2u * m.frames, q = i / per, r = i - q * per, f = r >> 1, c = 2u * q + (r & 1u);
     if (q >= m.n_buses) return;
-    float total = 0.0f;                                          // accum = splat(0.0), synth.rs:176
-    for (uint32_t g = 0; g < m.n_groups; ++g) {
-        const uint32_t gb0 = g * m.blocks_per_group;
-        uint32_t gb1 = gb0 + m.blocks_per_group; if (gb1 > m.n_blocks) gb1 = m.n_blocks;
-        if (gb0 >= gb1) continue;
-        float grp = 0.0f;
-        for (uint32_t r0 = gb0; r0 < gb1; r0 += kMixRun) {
-            const uint32_t r1 = r0 + kMixRun < gb1 ? r0 + kMixRun : gb1;
-            float v[kMixRun];
-#pragma unroll
-            for (uint32_t j = 0; j < kMixRun; ++j)
-                v[j] = (r0 + j < r1) ? m.partials[((size_t)(r0 + j) * (2u * S2R_MAX_BUSES) + c) * m.pstride + f] : 0.0f;
-            float acc = v[0];
-#pragma unroll
-            for (uint32_t j = 1; j < kMixRun; ++j) if (r0 + j < r1) acc = acc + v[j];
-            grp = (r0 == gb0) ? acc : grp + acc;
-        }
-        total = total + grp;
-    }
-    m.out[(size_t)q * m.ostride + r] = total;
+    m.out[(size_t)q * m.ostride + r] = combine_partials(m.partials, 2u * S2R_MAX_BUSES, c, m.pstride, f, m.n_blocks, m.blocks_per_group, m.n_groups);
 }
 
 // publishes the first timed event of every touched voice
@@ -584,24 +547,27 @@ hipError_t s2r_launch_pan_mix(const S2rPanMix &m, hipStream_t stream) {
 }
 
 template <int W, bool RAMP, bool SEND>
-static void bus_mix_launch(const typename BusMixArgs<RAMP, SEND>::type &a, uint32_t nb, dim3 grid, dim3 block, size_t lds, hipStream_t stream) {
+static void bus_mix_launch(const S2rBusMix &m, uint32_t nb, dim3 grid, dim3 block, size_t lds, hipStream_t stream) {
     switch (nb) {
-    case 1: hipLaunchKernelGGL((s2r_bus_mix_kernel<W, 1, RAMP, SEND>), grid, block, lds, stream, a); break;
-    case 2: hipLaunchKernelGGL((s2r_bus_mix_kernel<W, 2, RAMP, SEND>), grid, block, lds, stream, a); break;
-    case 4: hipLaunchKernelGGL((s2r_bus_mix_kernel<W, 4, RAMP, SEND>), grid, block, lds, stream, a); break;
-    default: hipLaunchKernelGGL((s2r_bus_mix_kernel<W, 8, RAMP, SEND>), grid, block, lds, stream, a); break;
+    case 1: hipLaunchKernelGGL((s2r_bus_mix_kernel<W, 1, RAMP, SEND>), grid, block, lds, stream, m); break;
+    case 2: hipLaunchKernelGGL((s2r_bus_mix_kernel<W, 2, RAMP, SEND>), grid, block, lds, stream, m); break;
+    case 4: hipLaunchKernelGGL((s2r_bus_mix_kernel<W, 4, RAMP, SEND>), grid, block, lds, stream, m); break;
+    default: hipLaunchKernelGGL((s2r_bus_mix_kernel<W, 8, RAMP, SEND>), grid, block, lds, stream, m); break;
     }
 }
 
-static S2rBusMix &bus_mix_of_host(S2rBusMix &a) { return a; }
-static S2rBusMix &bus_mix_of_host(S2rBusRampMix &a) { return a.m; }
-static S2rBusMix &bus_mix_of_host(S2rBusSendMix &a) { return a.m; }
-static S2rBusMix &bus_mix_of_host(S2rBusSendRampMix &a) { return a.r.m; }
+template <int W>
+static void bus_mix_launch(const S2rBusMix &m, uint32_t nb, dim3 grid, dim3 block, size_t lds, hipStream_t stream) {
+    const bool ramp = m.d_l != nullptr, send = m.send != nullptr;
+    if (ramp && send) bus_mix_launch<W, true, true>(m, nb, grid, block, lds, stream);
+    else if (ramp) bus_mix_launch<W, true, false>(m, nb, grid, block, lds, stream);
+    else if (send) bus_mix_launch<W, false, true>(m, nb, grid, block, lds, stream);
+    else bus_mix_launch<W, false, false>(m, nb, grid, block, lds, stream);
+}
 
-template <bool RAMP, bool SEND>
-static hipError_t bus_mix_launch_any(const typename BusMixArgs<RAMP, SEND>::type &in, hipStream_t stream) {
-    typename BusMixArgs<RAMP, SEND>::type a = in;
-    S2rBusMix &m = bus_mix_of_host(a);
+hipError_t s2r_launch_bus_mix(const S2rBusMix &in, hipStream_t stream) {
+    S2rBusMix m = in;
+    if (!m.d_l != !m.d_r || !m.send != !m.send_bus) return hipErrorInvalidValue;     // half a pair
     if (m.frames == 0 || m.n_voices == 0) return hipSuccess;
     if (m.block_voices < 64 || m.block_voices > 1024 || (m.block_voices & 63u) || m.n_blocks * m.block_voices < m.n_voices || m.n_blocks > 65535u ||
         m.stride < m.frames || m.pstride < m.frames || m.n_groups == 0 || m.blocks_per_group * m.n_groups < m.n_blocks ||
@@ -620,27 +586,10 @@ static hipError_t bus_mix_launch_any(const typename BusMixArgs<RAMP, SEND>::type
     uint32_t threads = (n_grp * m.lanes + 63u) & ~63u;            // a thread per run and lane, whole waves, 256 at the most
     if (threads > 256u) threads = 256u;
     const dim3 grid((m.frames + tf - 1u) / tf, m.n_blocks);
-    if (wide) bus_mix_launch<4, RAMP, SEND>(a, nb, grid, dim3(threads), lds, stream);
-    else bus_mix_launch<1, RAMP, SEND>(a, nb, grid, dim3(threads), lds, stream);
+    if (wide) bus_mix_launch<4>(m, nb, grid, dim3(threads), lds, stream);
+    else bus_mix_launch<1>(m, nb, grid, dim3(threads), lds, stream);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(s2r_bus_combine_kernel, dim3((2u * m.frames * m.n_buses + 255u) / 256u), dim3(256), 0, stream, m);
     return hipGetLastError();
-}
-
-hipError_t s2r_launch_bus_mix(const S2rBusMix &m, hipStream_t stream) { return bus_mix_launch_any<false, false>(m, stream); }
-
-hipError_t s2r_launch_bus_mix_ramped(const S2rBusRampMix &r, hipStream_t stream) {
-    if (!r.d_l || !r.d_r) return hipErrorInvalidValue;
-    return bus_mix_launch_any<true, false>(r, stream);
-}
-
-hipError_t s2r_launch_bus_mix_send(const S2rBusSendMix &a, hipStream_t stream) {
-    if (!a.send || !a.send_bus) return hipErrorInvalidValue;
-    return bus_mix_launch_any<false, true>(a, stream);
-}
-
-hipError_t s2r_launch_bus_mix_send_ramped(const S2rBusSendRampMix &a, hipStream_t stream) {
-    if (!a.send || !a.send_bus || !a.r.d_l || !a.r.d_r) return hipErrorInvalidValue;
-    return bus_mix_launch_any<true, true>(a, stream);
 }

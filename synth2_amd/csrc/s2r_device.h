@@ -353,8 +353,14 @@ struct S2rPanMix {
     float *out;                   // interleaved L, R: 2 * frames floats
 };
 
-// The bus mixdown (s2r_fill_buses; DESIGN.md 4.13): the same rows, each voice on one of n_buses stereo buses, its two gains
+// The bus mixdown (s2r_fill_buses; DESIGN.md 4.13-4.15): the same rows, each voice on one of n_buses stereo buses, its two gains
 // already scaled by the voice's gain; every bus and channel through the mix tree of DESIGN.md 4.3, all from one read of the rows.
+// ONE argument block for every form of it; the optional pointers at its end say which form a fill is:
+//   d_l != nullptr: program faders on their way (4.14) — the gain of voice v at frame i of the CALL is g_c[v][i] = G0_c[v] +
+//   (float)i * d_c[v] (the product rounded, then the sum); gain_l / gain_r hold G0.
+//   send != nullptr: aux sends (4.15) — voice v also feeds bus min(send_bus[v], n_buses - 1) with h_c = g_c * send[v] (under a
+//   ramp: H0 = G0 * send, e = d * send), one rounded multiply each, in the kernel; on a bus that is both its main and its send
+//   bus its gain is g + h.
 struct S2rBusMix {
     const float *rows;            // [n_voices][stride]
     const float *gain_l, *gain_r; // [n_blocks * block_voices] each: pan gain times voice gain, entries past n_voices hold 0
@@ -368,28 +374,10 @@ struct S2rBusMix {
     size_t ostride;               // floats from one bus to the next, >= 2 * frames
     uint32_t n_buses;             // 1 .. S2R_MAX_BUSES
     uint32_t lanes;               // threads along the frames of a tile (set by s2r_launch_bus_mix)
-};
-
-// The bus mixdown under moving program faders: the gain of voice v at frame i of the CALL is
-// g_c[v][i] = G0_c[v] + (float)i * d_c[v] (the product rounded, then the sum); m.gain_l / m.gain_r hold G0.
-struct S2rBusRampMix {
-    S2rBusMix m;
-    const float *d_l, *d_r;       // [n_blocks * block_voices] each: the gain's step per frame, entries past n_voices hold 0
-    uint32_t frame_base;          // the call-relative frame of m.rows' first frame (a segment's or a slice's start)
-};
-
-// The bus mixdown with aux sends: voice v also feeds bus min(send_bus[v], n_buses - 1) with h_c = g_c * send[v]
-// (under a ramp: H0 = G0 * send, e = d * send), one rounded multiply each, in the kernel; on a bus that is both its main and its
-// send bus its gain is g + h.  The static and the ramped arguments as they are, and the voices' two arrays.
-struct S2rBusSendMix {
-    S2rBusMix m;
-    const float *send;            // [n_blocks * block_voices]: the voice's send in [0, 1], entries past n_voices hold 0
+    const float *d_l, *d_r;       // [n_blocks * block_voices] each: the gain's step per frame, entries past n_voices hold 0; nullptr: a static fill
+    uint32_t frame_base;          // the call-relative frame of rows' first frame (a segment's or a slice's start)
+    const float *send;            // [n_blocks * block_voices]: the voice's send in [0, 1], entries past n_voices hold 0; nullptr: no sends
     const uint8_t *send_bus;      // [n_blocks * block_voices]: the bus it feeds (folded onto n_buses - 1 by the kernel)
-};
-struct S2rBusSendRampMix {
-    S2rBusRampMix r;
-    const float *send;
-    const uint8_t *send_bus;
 };
 
 hipError_t s2r_launch_tables(const S2rTabBuild &b, hipStream_t stream);
@@ -414,10 +402,6 @@ hipError_t s2r_launch_sum_rows(const float *rows, uint32_t n_rows, uint32_t fram
 // s2r_pan_mix_kernel (a workgroup's voices, both channels from one load of every row element) and the kernel that adds the
 // workgroups' partial rows in the documented order, rooted at +0.0
 hipError_t s2r_launch_pan_mix(const S2rPanMix &m, hipStream_t stream);
-// s2r_bus_mix_kernel (the instantiation for the call's bus count and the rows' alignment) and s2r_bus_combine_kernel
+// s2r_bus_mix_kernel (the instantiation for the call's bus count, the rows' alignment, RAMP = d_l != nullptr and SEND = send !=
+// nullptr) and s2r_bus_combine_kernel; d_l without d_r or send without send_bus: hipErrorInvalidValue
 hipError_t s2r_launch_bus_mix(const S2rBusMix &m, hipStream_t stream);
-// ... and its ramped instantiation (per-frame gains), same geometry, same combine
-hipError_t s2r_launch_bus_mix_ramped(const S2rBusRampMix &r, hipStream_t stream);
-// ... and the two with aux sends
-hipError_t s2r_launch_bus_mix_send(const S2rBusSendMix &a, hipStream_t stream);
-hipError_t s2r_launch_bus_mix_send_ramped(const S2rBusSendRampMix &a, hipStream_t stream);

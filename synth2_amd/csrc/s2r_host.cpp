@@ -129,6 +129,7 @@ struct EventSlot {
 // runtime's default or HIP_HOST_COHERENT say, and visible to every device of a device list
 constexpr unsigned kHostPolled = hipHostMallocMapped | hipHostMallocCoherent | hipHostMallocPortable;
 constexpr unsigned kGainsPan = 1u, kGainsBus = 2u, kGainsAll = 3u;   // s2r_synth::gains_dirty: the panned fill's device arrays, the bus fill's
+constexpr uint32_t kMixPan = 1u, kMixLevel = 2u, kMixFader = 4u, kMixSend = 8u;   // s2r_synth::Mixer::used
 
 }  // namespace
 
@@ -266,59 +267,54 @@ struct s2r_synth {
     uint32_t *res_cmd = nullptr;                         // the command as the CPU writes it: res_host, or 32 words of fine-grained
     uint32_t *res_cmd_dev = nullptr;                     // DEVICE memory (large BAR) that the kernel polls without crossing the link
     bool res_cmd_vram = false;
-    // True stereo (s2r_fill_panned).  Host bookkeeping: a pan and a key spread per program, beside the bank; the
-    // pan every shard voice got at its note_on (local order).  Nothing of it is touched until a pan is set for the first time
-    // (pan_used): until then every voice's pan is 0 and the note_on paths pay one branch.
-    std::vector<float> prog_pan, prog_spread;    // one entry per bank patch
-    bool pan_used = false;
-    std::vector<float> pans;                     // [shard_voices] once pan_used
-    struct PanEvent { uint32_t local, frame; float pan; };
-    std::vector<PanEvent> pan_timed;             // note_ons at a frame INSIDE the next fill, in event order: their pans take effect there
-    unsigned gains_dirty = kGainsAll;            // pans or voice mixes changed since the gains were last sent to the device: kGainsPan | kGainsBus
-    float *gains_host = nullptr, *gains_dev = nullptr;   // [2][padded_voices]: gL then gR (pinned / device); entries past the shard hold 0
+    // The voice mixer (s2r_fill_panned, s2r_fill_buses): what a program gives the voices started under it,
+    // beside the bank — the defaults are a handle that never heard of the mixer.
+    struct ProgramMix {
+        float pan = 0.0f, spread = 0.0f;                         // s2r_set_program_pan
+        float level = 1.0f, sens = 0.0f; uint8_t bus = 0;        // s2r_set_program_mix
+        float send = 0.0f; uint8_t send_bus = 0;                 // s2r_set_program_send
+        // s2r_set_program_fader: the pair the caller last set — the target — and the pair the last bus fill left — the applied
+        // one; a bus fill ramps every voice's gains from the one to the other
+        float fader = 1.0f, shift = 0.0f, fader_app = 1.0f, shift_app = 0.0f;
+        bool moving() const { return fader != fader_app || shift != shift_app; }
+    };
+    // ... and what every shard voice got at its note_on (local order).  One bit of `used` per attribute — pan, level (gain and
+    // bus), fader (the program the voice was started with: a voice follows that program's fader) and send (send and send bus) —
+    // set by the first call that leaves the attribute's default (mixer_begin); an attribute's arrays exist from then on, and
+    // until then every voice has its default (pan 0, gain 1 on bus 0, send 0 to bus 0), nothing of it is staged or launched, and
+    // with used == 0 the note_on paths pay one test.
+    struct Mixer {
+        uint32_t used = 0;                                       // kMixPan | kMixLevel | kMixFader | kMixSend
+        std::vector<ProgramMix> prog;                            // one entry per bank patch
+        std::vector<float> pan, gain, send;                      // [shard_voices] each, once its bit is set
+        std::vector<uint8_t> bus, send_bus, program;
+        // a note_on at a frame INSIDE the next fill: what it gives its voice takes effect there (`mask`: the attributes in use
+        // when it came; the other fields hold nothing)
+        struct Record { uint32_t local, frame, mask; float pan, gain, send; uint8_t bus, send_bus, program; };
+        std::vector<Record> timed;                               // in non-decreasing frame order, event order within a frame
+        // the only place that writes the voices' arrays from a record
+        void apply(const Record &r) {
+            if (r.mask & kMixPan) pan[r.local] = r.pan;
+            if (r.mask & kMixLevel) { gain[r.local] = r.gain; bus[r.local] = r.bus; }
+            if (r.mask & kMixFader) program[r.local] = r.program;
+            if (r.mask & kMixSend) { send[r.local] = r.send; send_bus[r.local] = r.send_bus; }
+        }
+    } mixer;
+    unsigned gains_dirty = kGainsAll;            // the voices' arrays changed since the gains were last sent to the device: kGainsPan | kGainsBus
+    float *gains_host = nullptr, *gains_dev = nullptr;   // the panned fill's [2][padded_voices]: gL then gR (pinned / device); entries past the shard hold 0
     hipEvent_t gains_sent = nullptr;             // behind the last copy out of gains_host
-    float *pan_rows = nullptr;                   // [shard_voices][pan_slice]: the voices' rows of one slice (allocated by the first panned fill)
+    float *pan_rows = nullptr;                   // [shard_voices][pan_slice]: the voices' rows of one slice (allocated by the first panned or bus fill)
     uint32_t pan_slice = 0;                      // frames per slice, a multiple of 16
     float *pan_partials = nullptr;               // [n_blocks][2][pan_slice]
-    std::vector<hipEvent_t> pan_ev;              // s2r_set_timing: a pair of events around every slice's mixdown of the last panned fill
+    std::vector<hipEvent_t> pan_ev;              // s2r_set_timing: a pair of events around every slice's mixdown of the last panned or bus fill
     size_t pan_ev_used = 0;
     float pan_mix_ms = -1.0f;                    // ... and their sum (tools/pan_time.py reads it through s2r_debug_pan_mix_ms)
-    // The voice mixer (s2r_fill_buses), kept exactly like the pans: level, velocity sensitivity and bus per
-    // program beside the bank; the gain and the bus every shard voice got at its note_on (local order).  Nothing of it is touched
-    // until a program mix or a voice mix is set for the first time (mix_used): until then every voice has gain 1 on bus 0.
-    std::vector<float> prog_level, prog_sens;    // one entry per bank patch
-    std::vector<uint8_t> prog_bus;
-    bool mix_used = false;
-    std::vector<float> vgain;                    // [shard_voices] once mix_used
-    std::vector<uint8_t> vbus;
-    struct MixEvent { uint32_t local, frame; float gain; uint8_t bus; };
-    std::vector<MixEvent> mix_timed;             // like pan_timed
-    char *bus_gains_host = nullptr, *bus_gains_dev = nullptr;    // [2][padded_voices] floats: gL * w, gR * w; then [padded_voices] bus bytes;
-                                                                 // then (a ramped fill) [2][padded_voices] floats: the gains' steps per frame
+    char *bus_gains_host = nullptr, *bus_gains_dev = nullptr;    // the bus fill's staging buffer (BusLayout)
     hipEvent_t bus_gains_sent = nullptr;
     float *bus_partials = nullptr;               // [n_blocks][S2R_MAX_BUSES][2][pan_slice], allocated by the first bus fill
     float *bus_out = nullptr, *bus_out_dev = nullptr;            // pinned and device-mapped: S2R_MAX_BUSES * 2 * max_frames floats
     float bus_mix_ms = -1.0f;                    // pan_mix_ms of the last s2r_fill_buses (tools/bus_time.py)
-    // Program faders: per program the pair (fader, pan_shift) the caller last set — the target — and the pair the
-    // last bus fill left — the applied one; a bus fill ramps every voice's gains from the one to the other.  A voice follows the
-    // program it was STARTED with: vprog mirrors the device's per-voice program (local order) from the first fader that leaves
-    // the default on (fader_used: read back once, then kept by the note_on paths like the pans); nothing of it is touched before.
-    std::vector<float> prog_fader, prog_shift, prog_fader_app, prog_shift_app;    // one entry per bank patch
-    bool fader_used = false;
-    std::vector<uint8_t> vprog;                  // [shard_voices] once fader_used
-    struct ProgEvent { uint32_t local, frame; uint8_t program; };
-    std::vector<ProgEvent> prog_timed;           // like pan_timed
     bool bus_dev_ramped = false;                 // what bus_gains_dev holds was sent for a ramped fill: (G0, step), not the static gains
-    // Aux sends: a send in [0, 1] and a send bus per program beside the bank; what every shard voice got at its
-    // note_on (local order), kept exactly like vgain / vbus.  Nothing of it is touched until a send is set for the first time
-    // (send_used): until then every voice has send 0 and the bus fill launches the kernels and arguments it always did.
-    std::vector<float> prog_send;                // one entry per bank patch
-    std::vector<uint8_t> prog_sbus;
-    bool send_used = false;
-    std::vector<float> vsend;                    // [shard_voices] once send_used
-    std::vector<uint8_t> vsbus;
-    struct SendEvent { uint32_t local, frame; float send; uint8_t bus; };
-    std::vector<SendEvent> send_timed;           // like pan_timed
     float pitch_table[256];
     hipEvent_t t0 = nullptr, t1 = nullptr;
     bool timing = false, timed = false, no_flat_shortcut = false;
@@ -1613,193 +1609,157 @@ int resident_fill(s2r_synth *s, float *out, size_t frames, uint32_t sample_rate,
     return S2R_OK;
 }
 
-// ---- true stereo ----
+// ---- the voice mixer's bookkeeping ----
 inline bool pan_in_range(float x) { return x >= -1.0f && x <= 1.0f; }          // (false for NaN)
+inline bool unit_in_range(float x) { return x >= 0.0f && x <= 1.0f; }           // (false for NaN)
+inline bool fader_in_range(float fader, float shift) { return fader >= 0.0f && fader <= 1.0f && shift >= -2.0f && shift <= 2.0f; }   // (false for NaN)
 
-// the first pan ever set on this handle: from here on the note_on paths record every voice's pan
-void pan_begin(s2r_synth *s) {
-    if (s->pan_used) return;
-    s->pans.assign(s->shard_voices, 0.0f);
-    s->pan_used = true; s->gains_dirty = kGainsAll;
+// The bus fill's staging buffer, once: byte offsets of the [padded_voices] arrays in bus_gains_host / bus_gains_dev.  gL, gR
+// (floats: pan gain times voice gain, times the applied fader), the bus bytes, — once sends are in use — the sends (floats) and
+// the send bus bytes, and behind them, sent with a ramped fill only, the gains' steps per frame dL, dR (floats).
+constexpr size_t kBusGainBytes = 4 * sizeof(float) + 1 + sizeof(float) + 1;     // per padded voice, everything in use
+struct BusLayout { size_t gl, gr, bus, send, send_bus, dl, dr, end; };
+inline BusLayout bus_layout(const s2r_synth *s) {
+    const size_t pv = s->padded_voices, f = pv * sizeof(float);
+    BusLayout o{};
+    o.gr = f; o.bus = 2 * f; o.send = o.bus + pv; o.send_bus = o.send + f;
+    o.dl = (s->mixer.used & kMixSend) ? o.send_bus + pv : o.send;
+    o.dr = o.dl + f; o.end = o.dr + f;
+    return o;
 }
 
-// Pans of note_ons that had a frame inside a fill which has been rendered since (by any fill: fill_time is back at 0) are the
-// voices' pans now.  Called before anything reads or writes `pans`.
-void pan_settle(s2r_synth *s) {
-    if (s->pan_timed.empty() || s->fill_time != 0) return;
-    for (const s2r_synth::PanEvent &e : s->pan_timed) s->pans[e.local] = e.pan;
-    s->pan_timed.clear();
+// Records of note_ons that had a frame inside a fill which has been rendered since (by any fill: fill_time is back at 0) are the
+// voices' values now.  Called before anything reads or writes the voices' arrays.
+void mixer_settle(s2r_synth *s) {
+    s2r_synth::Mixer &m = s->mixer;
+    if (m.timed.empty() || s->fill_time != 0) return;
+    for (const s2r_synth::Mixer::Record &r : m.timed) m.apply(r);
+    m.timed.clear();
     s->gains_dirty = kGainsAll;
 }
 
-// a note_on took shard voice `local` (the caller has settled): the pan of the program in force, now or at its frame
-inline void pan_note_on(s2r_synth *s, uint32_t local, uint8_t note, uint32_t frame) {
-    const float p = s2r_voice_pan(s->prog_pan[s->program], s->prog_spread[s->program], note);
-    if (frame == 0) { s->pans[local] = p; s->gains_dirty = kGainsAll; }
-    else s->pan_timed.push_back(s2r_synth::PanEvent{local, frame, p});
+// The first call that takes attribute `bit` off its default: its arrays, and from here on the note_on paths record it.
+int mixer_begin(s2r_synth *s, uint32_t bit) {
+    s2r_synth::Mixer &m = s->mixer;
+    if (m.used & bit) return S2R_OK;
+    if (bit == kMixFader) {
+        // The host mirrors every shard voice's program from now on.  What the voices hold NOW is on the device (the render
+        // kernels keep it); on top of it come the events the host still holds for the next fill, in their order — the timed
+        // ones as records of their own beside what the queue already holds for those note_ons (a stable sort by frame: the
+        // fields are disjoint, and the order within a frame is the events').
+        S2R_QUIESCE(s);
+        S2R_HIP(s, hipSetDevice(s->device));
+        std::vector<uint32_t> h(s->padded_voices);
+        S2R_HIP(s, hipMemcpyAsync(h.data(), s->v.program, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+        S2R_HIP(s, hipStreamSynchronize(s->stream));
+        m.program.resize(s->shard_voices);
+        for (uint32_t i = 0; i < s->shard_voices; i++) m.program[i] = (uint8_t)h[i];
+        for (const S2rVoiceEvent &e : s->pending) if (e.flags & S2R_EV_RESTART) m.program[e.voice] = (uint8_t)(e.flags >> S2R_EV_PROGRAM_SHIFT);
+        for (const S2rTimedEvent &te : s->tpending) {
+            if (!(te.flags & S2R_EV_RESTART)) continue;
+            if (te.frame == 0) m.program[te.voice] = (uint8_t)te.program;
+            else m.timed.push_back(s2r_synth::Mixer::Record{te.voice, te.frame, kMixFader, 0.0f, 0.0f, 0.0f, 0u, 0u, (uint8_t)te.program});
+        }
+        std::stable_sort(m.timed.begin(), m.timed.end(), [](const s2r_synth::Mixer::Record &a, const s2r_synth::Mixer::Record &b) { return a.frame < b.frame; });
+    }
+    if (bit == kMixSend && s->bus_gains_host) {                  // the staging buffer is laid out anew (bus_layout): nothing stale in it
+        S2R_HIP(s, hipEventSynchronize(s->bus_gains_sent));
+        std::memset(s->bus_gains_host, 0, s->padded_voices * kBusGainBytes);
+    }
+    if (bit == kMixPan) m.pan.assign(s->shard_voices, 0.0f);
+    if (bit == kMixLevel) { m.gain.assign(s->shard_voices, 1.0f); m.bus.assign(s->shard_voices, 0u); }
+    if (bit == kMixSend) { m.send.assign(s->shard_voices, 0.0f); m.send_bus.assign(s->shard_voices, 0u); }
+    m.used |= bit; s->gains_dirty = kGainsAll;
+    return S2R_OK;
+}
+
+// a note_on took shard voice `local` (the caller has settled): what the program in force gives it, now or at its frame
+inline void mixer_note_on(s2r_synth *s, uint32_t local, uint8_t note, float velocity, uint32_t frame) {
+    s2r_synth::Mixer &m = s->mixer;
+    const s2r_synth::ProgramMix &p = m.prog[s->program];
+    s2r_synth::Mixer::Record r{local, frame, m.used, 0.0f, 0.0f, p.send, p.bus, p.send_bus, (uint8_t)s->program};
+    if (m.used & kMixPan) r.pan = s2r_voice_pan(p.pan, p.spread, note);
+    if (m.used & kMixLevel) r.gain = s2r_voice_gain(p.level, p.sens, velocity);      // (the other fields are copies: apply looks at r.mask)
+    if (frame == 0) { m.apply(r); s->gains_dirty = kGainsAll; }
+    else m.timed.push_back(r);
+}
+
+inline void snap_faders(s2r_synth *s) {
+    for (s2r_synth::ProgramMix &p : s->mixer.prog) { p.fader_app = p.fader; p.shift_app = p.shift; }
+}
+
+inline bool faders_moving(const s2r_synth *s) {
+    if (!(s->mixer.used & kMixFader)) return false;
+    for (const s2r_synth::ProgramMix &p : s->mixer.prog) if (p.moving()) return true;
+    return false;
 }
 
 // the gains of the voices' pans, from pinned memory to the device on the handle's stream (when a pan changed)
 int pan_send_gains(s2r_synth *s) {
     if (!(s->gains_dirty & kGainsPan)) return S2R_OK;
     const size_t pv = s->padded_voices;
+    const s2r_synth::Mixer &m = s->mixer;
     if (!s->gains_host) {
         S2R_HIP(s, hipHostMalloc((void **)&s->gains_host, 2 * pv * sizeof(float), hipHostMallocDefault));
         std::memset(s->gains_host, 0, 2 * pv * sizeof(float));
         S2R_HIP(s, hipMalloc((void **)&s->gains_dev, 2 * pv * sizeof(float)));
         S2R_HIP(s, hipEventCreateWithFlags(&s->gains_sent, hipEventDisableTiming));
     } else S2R_HIP(s, hipEventSynchronize(s->gains_sent));       // (the last copy may still be reading the pinned buffer)
-    for (uint32_t i = 0; i < s->shard_voices; i++) s2r_pan_gains(s->pan_used ? s->pans[i] : 0.0f, s->gains_host + i, s->gains_host + pv + i);
+    for (uint32_t i = 0; i < s->shard_voices; i++) s2r_pan_gains((m.used & kMixPan) ? m.pan[i] : 0.0f, s->gains_host + i, s->gains_host + pv + i);
     S2R_HIP(s, hipMemcpyAsync(s->gains_dev, s->gains_host, 2 * pv * sizeof(float), hipMemcpyHostToDevice, s->stream));
     S2R_HIP(s, hipEventRecord(s->gains_sent, s->stream));
     s->gains_dirty &= ~kGainsPan;
     return S2R_OK;
 }
 
-// ---- the voice mixer: the pans' bookkeeping once more, for the gain and the bus of every voice ----
-// bytes per padded voice of the bus fill's staging buffer: gL, gR, the bus byte, (with sends: the send, the send bus byte,) dL, dR
-constexpr size_t kBusGainBytes = 4 * sizeof(float) + 1 + sizeof(float) + 1;
-inline bool unit_in_range(float x) { return x >= 0.0f && x <= 1.0f; }           // (false for NaN)
-
-void mix_begin(s2r_synth *s) {
-    if (s->mix_used) return;
-    s->vgain.assign(s->shard_voices, 1.0f);
-    s->vbus.assign(s->shard_voices, 0u);
-    s->mix_used = true; s->gains_dirty = kGainsAll;
-}
-
-void mix_settle(s2r_synth *s) {
-    if (s->mix_timed.empty() || s->fill_time != 0) return;
-    for (const s2r_synth::MixEvent &e : s->mix_timed) { s->vgain[e.local] = e.gain; s->vbus[e.local] = e.bus; }
-    s->mix_timed.clear();
-    s->gains_dirty = kGainsAll;
-}
-
-inline void mix_note_on(s2r_synth *s, uint32_t local, float velocity, uint32_t frame) {
-    const float w = s2r_voice_gain(s->prog_level[s->program], s->prog_sens[s->program], velocity);
-    const uint8_t bus = s->prog_bus[s->program];
-    if (frame == 0) { s->vgain[local] = w; s->vbus[local] = bus; s->gains_dirty = kGainsAll; }
-    else s->mix_timed.push_back(s2r_synth::MixEvent{local, frame, w, bus});
-}
-
-// ---- aux sends: the mixer's bookkeeping once more, for the send and the send bus of every voice ----
-int send_begin(s2r_synth *s) {
-    if (s->send_used) return S2R_OK;
-    s->vsend.assign(s->shard_voices, 0.0f);
-    s->vsbus.assign(s->shard_voices, 0u);
-    if (s->bus_gains_host) {                                     // the staging buffer is laid out anew (bus_send_gains): nothing stale in it
-        S2R_HIP(s, hipEventSynchronize(s->bus_gains_sent));
-        std::memset(s->bus_gains_host, 0, s->padded_voices * kBusGainBytes);
-    }
-    s->send_used = true; s->gains_dirty = kGainsAll;
-    return S2R_OK;
-}
-
-void send_settle(s2r_synth *s) {
-    if (s->send_timed.empty() || s->fill_time != 0) return;
-    for (const s2r_synth::SendEvent &e : s->send_timed) { s->vsend[e.local] = e.send; s->vsbus[e.local] = e.bus; }
-    s->send_timed.clear();
-    s->gains_dirty = kGainsAll;
-}
-
-inline void send_note_on(s2r_synth *s, uint32_t local, uint32_t frame) {
-    const float sd = s->prog_send[s->program];
-    const uint8_t bus = s->prog_sbus[s->program];
-    if (frame == 0) { s->vsend[local] = sd; s->vsbus[local] = bus; s->gains_dirty = kGainsAll; }
-    else s->send_timed.push_back(s2r_synth::SendEvent{local, frame, sd, bus});
-}
-
-// ---- program faders ----
-inline bool fader_in_range(float fader, float shift) { return fader >= 0.0f && fader <= 1.0f && shift >= -2.0f && shift <= 2.0f; }   // (false for NaN)
-
-// The first fader that leaves (1, 0): from here on the host mirrors every shard voice's program.  What the voices hold NOW is on
-// the device (the render kernels keep it); on top of it come the events the host still holds for the next fill, in their order.
-int fader_begin(s2r_synth *s) {
-    if (s->fader_used) return S2R_OK;
-    S2R_QUIESCE(s);
-    S2R_HIP(s, hipSetDevice(s->device));
-    std::vector<uint32_t> h(s->padded_voices);
-    S2R_HIP(s, hipMemcpyAsync(h.data(), s->v.program, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
-    S2R_HIP(s, hipStreamSynchronize(s->stream));
-    s->vprog.resize(s->shard_voices);
-    for (uint32_t i = 0; i < s->shard_voices; i++) s->vprog[i] = (uint8_t)h[i];
-    for (const S2rVoiceEvent &e : s->pending) if (e.flags & S2R_EV_RESTART) s->vprog[e.voice] = (uint8_t)(e.flags >> S2R_EV_PROGRAM_SHIFT);
-    s->prog_timed.clear();
-    for (const S2rTimedEvent &te : s->tpending) {
-        if (!(te.flags & S2R_EV_RESTART)) continue;
-        if (te.frame == 0) s->vprog[te.voice] = (uint8_t)te.program;
-        else s->prog_timed.push_back(s2r_synth::ProgEvent{te.voice, te.frame, (uint8_t)te.program});
-    }
-    s->fader_used = true; s->gains_dirty = kGainsAll;
-    return S2R_OK;
-}
-
-void prog_settle(s2r_synth *s) {
-    if (s->prog_timed.empty() || s->fill_time != 0) return;
-    for (const s2r_synth::ProgEvent &e : s->prog_timed) s->vprog[e.local] = e.program;
-    s->prog_timed.clear();
-    s->gains_dirty = kGainsAll;
-}
-
-inline void prog_note_on(s2r_synth *s, uint32_t local, uint32_t frame) {
-    if (frame == 0) { s->vprog[local] = (uint8_t)s->program; s->gains_dirty = kGainsAll; }
-    else s->prog_timed.push_back(s2r_synth::ProgEvent{local, frame, (uint8_t)s->program});
-}
-
-inline bool faders_moving(const s2r_synth *s) {
-    if (!s->fader_used) return false;
-    for (size_t k = 0; k < s->prog_fader.size(); k++)
-        if (s->prog_fader[k] != s->prog_fader_app[k] || s->prog_shift[k] != s->prog_shift_app[k]) return true;
-    return false;
-}
-
-// what the bus mixdown reads per voice — both pan gains times the voice's gain (one rounded multiply each), times its program's
-// applied fader once faders are in use, and the bus byte — from pinned memory to the device on the handle's stream (when a pan, a
-// mix or a fader changed).  `ramp`: a bus fill of `total` frames with a fader on its way: the gains under the applied pairs and,
-// behind the bus bytes, their steps per frame towards the gains under the targets — one staging buffer, one copy.  Once sends are
-// in use the voices' sends and send bus bytes lie between the bus bytes and the steps (bus_static_bytes), in the same copy.
-inline size_t bus_static_bytes(const s2r_synth *s) { return s->padded_voices * (2 * sizeof(float) + 1 + (s->send_used ? sizeof(float) + 1 : 0)); }
-
+// What the bus mixdown reads per voice (BusLayout) — both pan gains times the voice's gain (one rounded multiply each), times its
+// program's applied fader once faders are in use, the bus byte, the send and its bus byte once sends are in use — from pinned memory
+// to the device on the handle's stream (when a pan, a mix, a send or a fader changed).  `ramp`: a bus fill of `total` frames with a
+// fader on its way: the gains under the applied pairs and their steps per frame towards the gains under the targets — one staging
+// buffer, one copy.
 int bus_send_gains(s2r_synth *s, bool ramp, uint32_t total) {
     if (!(s->gains_dirty & kGainsBus) && s->bus_dev_ramped == ramp) return S2R_OK;
-    const size_t pv = s->padded_voices, static_bytes = bus_static_bytes(s), bytes = static_bytes + pv * 2 * sizeof(float);
+    const size_t pv = s->padded_voices;
+    const BusLayout o = bus_layout(s);
+    const s2r_synth::Mixer &m = s->mixer;
     if (!s->bus_gains_host) {
         S2R_HIP(s, hipHostMalloc((void **)&s->bus_gains_host, pv * kBusGainBytes, hipHostMallocDefault));
         std::memset(s->bus_gains_host, 0, pv * kBusGainBytes);
         S2R_HIP(s, hipMalloc((void **)&s->bus_gains_dev, pv * kBusGainBytes));
         S2R_HIP(s, hipEventCreateWithFlags(&s->bus_gains_sent, hipEventDisableTiming));
     } else S2R_HIP(s, hipEventSynchronize(s->bus_gains_sent));
-    float *g = reinterpret_cast<float *>(s->bus_gains_host);
-    uint8_t *b = reinterpret_cast<uint8_t *>(s->bus_gains_host + 2 * pv * sizeof(float));
-    float *d = reinterpret_cast<float *>(s->bus_gains_host + static_bytes);
-    const size_t n_prog = s->prog_fader.size();
+    char *host = s->bus_gains_host;
+    float *gl = reinterpret_cast<float *>(host + o.gl), *gr = reinterpret_cast<float *>(host + o.gr);
+    float *dl = reinterpret_cast<float *>(host + o.dl), *dr = reinterpret_cast<float *>(host + o.dr);
+    uint8_t *b = reinterpret_cast<uint8_t *>(host + o.bus);
+    const size_t n_prog = m.prog.size();
     const float fn = (float)total;
-    if (s->send_used) {
-        std::memcpy(s->bus_gains_host + pv * (2 * sizeof(float) + 1), s->vsend.data(), (size_t)s->shard_voices * sizeof(float));
-        std::memcpy(s->bus_gains_host + pv * (3 * sizeof(float) + 1), s->vsbus.data(), (size_t)s->shard_voices);
+    if (m.used & kMixSend) {
+        std::memcpy(host + o.send, m.send.data(), (size_t)s->shard_voices * sizeof(float));
+        std::memcpy(host + o.send_bus, m.send_bus.data(), (size_t)s->shard_voices);
     }
     for (uint32_t i = 0; i < s->shard_voices; i++) {
-        const float pan = s->pan_used ? s->pans[i] : 0.0f, w = s->mix_used ? s->vgain[i] : 1.0f;
-        b[i] = s->mix_used ? s->vbus[i] : (uint8_t)0;
-        if (!s->fader_used) {
-            float gl, gr;
-            s2r_pan_gains(pan, &gl, &gr);
-            g[i] = gl * w; g[pv + i] = gr * w;
+        const float pan = (m.used & kMixPan) ? m.pan[i] : 0.0f, w = (m.used & kMixLevel) ? m.gain[i] : 1.0f;
+        b[i] = (m.used & kMixLevel) ? m.bus[i] : (uint8_t)0;
+        if (!(m.used & kMixFader)) {
+            float l, r;
+            s2r_pan_gains(pan, &l, &r);
+            gl[i] = l * w; gr[i] = r * w;
             continue;
         }
-        const size_t k = s->vprog[i] < n_prog ? s->vprog[i] : 0u;                 // (past a later, smaller bank: program 0, as its patch is)
+        const s2r_synth::ProgramMix &p = m.prog[m.program[i] < n_prog ? m.program[i] : 0u];      // (past a later, smaller bank: program 0, as its patch is)
         float g0l, g0r;
-        s2r_fader_gains(pan, w, s->prog_fader_app[k], s->prog_shift_app[k], &g0l, &g0r);
-        g[i] = g0l; g[pv + i] = g0r;
+        s2r_fader_gains(pan, w, p.fader_app, p.shift_app, &g0l, &g0r);
+        gl[i] = g0l; gr[i] = g0r;
         if (!ramp) continue;
-        if (s->prog_fader[k] != s->prog_fader_app[k] || s->prog_shift[k] != s->prog_shift_app[k]) {
+        if (p.moving()) {
             float g1l, g1r;
-            s2r_fader_gains(pan, w, s->prog_fader[k], s->prog_shift[k], &g1l, &g1r);
-            const float dl = g1l - g0l, dr = g1r - g0r;
-            d[i] = dl / fn; d[pv + i] = dr / fn;
-        } else { d[i] = 0.0f; d[pv + i] = 0.0f; }
+            s2r_fader_gains(pan, w, p.fader, p.shift, &g1l, &g1r);
+            const float sl = g1l - g0l, sr = g1r - g0r;
+            dl[i] = sl / fn; dr[i] = sr / fn;
+        } else { dl[i] = 0.0f; dr[i] = 0.0f; }
     }
-    S2R_HIP(s, hipMemcpyAsync(s->bus_gains_dev, s->bus_gains_host, ramp ? bytes : static_bytes, hipMemcpyHostToDevice, s->stream));
+    S2R_HIP(s, hipMemcpyAsync(s->bus_gains_dev, host, ramp ? o.end : o.dl, hipMemcpyHostToDevice, s->stream));
     S2R_HIP(s, hipEventRecord(s->bus_gains_sent, s->stream));
     s->gains_dirty &= ~kGainsBus;
     s->bus_dev_ramped = ramp;
@@ -1819,49 +1779,42 @@ int pan_segment(s2r_synth *s, uint32_t at, uint32_t n, uint32_t last_event, uint
         s->fill_time = at + done >= last_event ? 0u : len;       // enqueue_fill moves the clock by len - fill_time
         rc = enqueue_fill(s, len, sample_rate, s->stream, nullptr, false, false, s->pan_rows);
         if (rc != S2R_OK) return rc;
-        S2rPanMix m{};
-        m.rows = s->pan_rows; m.gain_l = s->gains_dev; m.gain_r = s->gains_dev + s->padded_voices;
-        m.n_voices = s->shard_voices; m.block_voices = s->block_voices; m.n_blocks = s->n_blocks;
-        m.frames = len; m.stride = len;                          // (the render kernel's rows are `frames` apart)
-        m.partials = s->pan_partials; m.pstride = s->pan_slice;
-        m.n_groups = s->mix_groups; m.blocks_per_group = (s->n_blocks + m.n_groups - 1) / m.n_groups;
-        m.out = s->out_host_dev + 2u * (size_t)(at + done);
+        const uint32_t n_groups = s->mix_groups, blocks_per_group = (s->n_blocks + n_groups - 1) / n_groups;
         if (s->timing) {
             while (s->pan_ev.size() < s->pan_ev_used + 2) { hipEvent_t e; S2R_HIP(s, hipEventCreate(&e)); s->pan_ev.push_back(e); }
             S2R_HIP(s, hipEventRecord(s->pan_ev[s->pan_ev_used], s->stream));
         }
         if (n_buses) {
-            S2rBusMix bm{};
-            const float *g = reinterpret_cast<const float *>(s->bus_gains_dev);
-            bm.rows = m.rows; bm.gain_l = g; bm.gain_r = g + s->padded_voices;
-            bm.bus = reinterpret_cast<const uint8_t *>(g + 2 * (size_t)s->padded_voices);
-            bm.n_voices = m.n_voices; bm.block_voices = m.block_voices; bm.n_blocks = m.n_blocks;
-            bm.frames = len; bm.stride = len;
-            bm.partials = s->bus_partials; bm.pstride = s->pan_slice;
-            bm.n_groups = m.n_groups; bm.blocks_per_group = m.blocks_per_group;
-            bm.out = s->bus_out_dev + 2u * (size_t)(at + done); bm.ostride = 2u * (size_t)total;
-            bm.n_buses = n_buses;
+            S2rBusMix m{};
+            const BusLayout o = bus_layout(s);
+            const char *dev = s->bus_gains_dev;
+            m.rows = s->pan_rows;
+            m.gain_l = reinterpret_cast<const float *>(dev + o.gl); m.gain_r = reinterpret_cast<const float *>(dev + o.gr);
+            m.bus = reinterpret_cast<const uint8_t *>(dev + o.bus);
+            m.n_voices = s->shard_voices; m.block_voices = s->block_voices; m.n_blocks = s->n_blocks;
+            m.frames = len; m.stride = len;                      // (the render kernel's rows are `frames` apart)
+            m.partials = s->bus_partials; m.pstride = s->pan_slice;
+            m.n_groups = n_groups; m.blocks_per_group = blocks_per_group;
+            m.out = s->bus_out_dev + 2u * (size_t)(at + done); m.ostride = 2u * (size_t)total;
+            m.n_buses = n_buses;
             if (ramp) {
-                S2rBusRampMix rm{};
-                rm.m = bm;
-                rm.d_l = reinterpret_cast<const float *>(s->bus_gains_dev + bus_static_bytes(s));
-                rm.d_r = rm.d_l + s->padded_voices;
-                rm.frame_base = at + done;
-                if (s->send_used) {
-                    S2rBusSendRampMix sm{};
-                    sm.r = rm;
-                    sm.send = reinterpret_cast<const float *>(s->bus_gains_dev + s->padded_voices * (2 * sizeof(float) + 1));
-                    sm.send_bus = reinterpret_cast<const uint8_t *>(sm.send + s->padded_voices);
-                    S2R_HIP(s, s2r_launch_bus_mix_send_ramped(sm, s->stream));
-                } else S2R_HIP(s, s2r_launch_bus_mix_ramped(rm, s->stream));
-            } else if (s->send_used) {
-                S2rBusSendMix sm{};
-                sm.m = bm;
-                sm.send = reinterpret_cast<const float *>(s->bus_gains_dev + s->padded_voices * (2 * sizeof(float) + 1));
-                sm.send_bus = reinterpret_cast<const uint8_t *>(sm.send + s->padded_voices);
-                S2R_HIP(s, s2r_launch_bus_mix_send(sm, s->stream));
-            } else S2R_HIP(s, s2r_launch_bus_mix(bm, s->stream));
-        } else S2R_HIP(s, s2r_launch_pan_mix(m, s->stream));
+                m.d_l = reinterpret_cast<const float *>(dev + o.dl); m.d_r = reinterpret_cast<const float *>(dev + o.dr);
+                m.frame_base = at + done;
+            }
+            if (s->mixer.used & kMixSend) {
+                m.send = reinterpret_cast<const float *>(dev + o.send); m.send_bus = reinterpret_cast<const uint8_t *>(dev + o.send_bus);
+            }
+            S2R_HIP(s, s2r_launch_bus_mix(m, s->stream));
+        } else {
+            S2rPanMix m{};
+            m.rows = s->pan_rows; m.gain_l = s->gains_dev; m.gain_r = s->gains_dev + s->padded_voices;
+            m.n_voices = s->shard_voices; m.block_voices = s->block_voices; m.n_blocks = s->n_blocks;
+            m.frames = len; m.stride = len;                      // (the render kernel's rows are `frames` apart)
+            m.partials = s->pan_partials; m.pstride = s->pan_slice;
+            m.n_groups = n_groups; m.blocks_per_group = blocks_per_group;
+            m.out = s->out_host_dev + 2u * (size_t)(at + done);
+            S2R_HIP(s, s2r_launch_pan_mix(m, s->stream));
+        }
         if (s->timing) { S2R_HIP(s, hipEventRecord(s->pan_ev[s->pan_ev_used + 1], s->stream)); s->pan_ev_used += 2; }
         done += len;
     }
@@ -2078,10 +2031,7 @@ static int create_single(const s2r_config *cfg, std::shared_ptr<S2rVoicePool> po
     if (cfg->reserved0 != 0) { delete s; return S2R_ERR_INVALID; }
     s->parent = parent;
     s->bank.resize(1);
-    s->prog_pan.assign(1, 0.0f); s->prog_spread.assign(1, 0.0f);
-    s->prog_level.assign(1, 1.0f); s->prog_sens.assign(1, 0.0f); s->prog_bus.assign(1, 0u);
-    s->prog_send.assign(1, 0.0f); s->prog_sbus.assign(1, 0u);
-    s->prog_fader.assign(1, 1.0f); s->prog_shift.assign(1, 0.0f); s->prog_fader_app.assign(1, 1.0f); s->prog_shift_app.assign(1, 0.0f);
+    s->mixer.prog.resize(1);
     s2r_default_patch(&s->bank[0]);
     if (pool) s->pool = pool;
     else { s->pool.reset(new S2rVoicePool(cfg->total_voices)); s->seed_override.assign(cfg->total_voices, 0u); configure_policy_threads(s->pool.get(), cfg->total_voices); }
@@ -2333,11 +2283,8 @@ int s2r_set_patch_bank(s2r_synth *s, const s2r_patch *patches, uint32_t n) {
     }
     S2R_QUIESCE(s);
     s->bank.assign(patches, patches + n);
-    s->prog_pan.resize(n, 0.0f); s->prog_spread.resize(n, 0.0f);   // the surviving programs keep their pans
-    s->prog_level.resize(n, 1.0f); s->prog_sens.resize(n, 0.0f); s->prog_bus.resize(n, 0u);      // ... and their mix
-    s->prog_fader.resize(n, 1.0f); s->prog_shift.resize(n, 0.0f); s->prog_fader_app.resize(n, 1.0f); s->prog_shift_app.resize(n, 0.0f);   // ... and faders
-    s->prog_send.resize(n, 0.0f); s->prog_sbus.resize(n, 0u);    // ... and sends
-    if (s->fader_used) s->gains_dirty = kGainsAll;               // (a voice whose program fell off the bank follows program 0 now)
+    s->mixer.prog.resize(n);                                     // the surviving programs keep their pans, mix, sends and faders
+    if (s->mixer.used & kMixFader) s->gains_dirty = kGainsAll;   // (a voice whose program fell off the bank follows program 0 now)
     if (s->program >= n) s->program = 0;
     s->bank_dirty = true; s->tab_dirty = true;
     for (s2r_synth *kid : s->kids) { kid->bank = s->bank; kid->bank_dirty = true; kid->tab_dirty = true; }
@@ -2387,12 +2334,10 @@ int s2r_note_on_ex(s2r_synth *s, uint8_t note, float velocity, uint32_t *voice_i
     const uint32_t i = s->pool->note_on(note, velocity);
     if (voice_index_out) *voice_index_out = i;
     if (s->voice_log) s->voice_log(s->voice_log_user, i, note);
-    if ((s->pan_used | s->mix_used | s->fader_used | s->send_used) && s->kids.empty()) {
+    if (s->mixer.used && s->kids.empty()) {
         const int64_t mine = to_local(s, i);
-        if (s->pan_used) { pan_settle(s); if (mine >= 0) pan_note_on(s, (uint32_t)mine, note, 0u); }
-        if (s->mix_used) { mix_settle(s); if (mine >= 0) mix_note_on(s, (uint32_t)mine, velocity, 0u); }
-        if (s->fader_used) { prog_settle(s); if (mine >= 0) prog_note_on(s, (uint32_t)mine, 0u); }
-        if (s->send_used) { send_settle(s); if (mine >= 0) send_note_on(s, (uint32_t)mine, 0u); }
+        mixer_settle(s);
+        if (mine >= 0) mixer_note_on(s, (uint32_t)mine, note, velocity, 0u);
     }
     if (!append_frame0_record(s, i, S2R_EV_RESTART, s->pitch_table[note], s->seed_override[i], s->program))
         push_event(s, i, S2R_EV_RESTART, s->pitch_table[note], s->seed_override[i], s->program);
@@ -2440,7 +2385,7 @@ int s2r_note_events(s2r_synth *s, const s2r_note_event *events, size_t n) {
     // and note_off over the events computes — on several threads for a multi-GPU-sized batch): the voice every event takes or
     // releases.  An event inside the next fill first moves the pool's clock to its frame (the policy sees the offsets every
     // voice has AT that frame, like the reference between two 16-frame calls); frame-0 events take effect before the fill.
-    if (s->pan_used | s->mix_used | s->fader_used | s->send_used) { pan_settle(s); mix_settle(s); prog_settle(s); send_settle(s); }      // (while fill_time still says whether the last fill's events are behind us)
+    if (s->mixer.used) mixer_settle(s);                          // (while fill_time still says whether the last fill's events are behind us)
     static thread_local std::vector<int64_t> chosen;
     if (chosen.size() < n) chosen.resize(n);
     static_assert(sizeof(S2rPolicyEvent) == 4 && S2R_NOTE_ON == S2R_POLICY_NOTE_ON && S2R_NOTE_OFF == S2R_POLICY_NOTE_OFF, "s2r_note_event's first four bytes");
@@ -2481,12 +2426,7 @@ int s2r_note_events(s2r_synth *s, const s2r_note_event *events, size_t n) {
         }
         const uint32_t frame = e.frame;
         const bool on = e.kind == S2R_NOTE_ON;
-        if (on && one && (one->pan_used | one->mix_used | one->fader_used | one->send_used)) {
-            if (one->pan_used) pan_note_on(one, local, e.note, frame);
-            if (one->mix_used) mix_note_on(one, local, e.velocity, frame);
-            if (one->fader_used) prog_note_on(one, local, frame);
-            if (one->send_used) send_note_on(one, local, frame);
-        }
+        if (on && one && one->mixer.used) mixer_note_on(one, local, e.note, e.velocity, frame);
         if (frame == 0 && may_fold && sh->tpending.empty()) {
             if (on) push_event(s, (uint32_t)vi, S2R_EV_RESTART, pitch_of[e.note], seed_of[(size_t)vi], s->program);
             else push_event(s, (uint32_t)vi, S2R_EV_RELEASE, 0.0f, 0u);
@@ -2589,26 +2529,26 @@ int s2r_set_program_pan(s2r_synth *s, uint32_t program, float pan, float key_spr
         return set_err(s, S2R_ERR_PATCH_RANGE, "program %u: pan %g, key_spread %g: both lie in [-1, 1]", program, (double)pan, (double)key_spread);
     if (!s) return S2R_ERR_INVALID;
     if (program >= s->bank.size()) return set_err(s, S2R_ERR_INVALID, "program %u: the bank holds %zu patches", program, s->bank.size());
-    if (pan != 0.0f || key_spread != 0.0f) { pan_begin(s); pan_settle(s); }
-    s->prog_pan[program] = pan; s->prog_spread[program] = key_spread;
+    if (pan != 0.0f || key_spread != 0.0f) { (void)mixer_begin(s, kMixPan); mixer_settle(s); }
+    s->mixer.prog[program].pan = pan; s->mixer.prog[program].spread = key_spread;
     return S2R_OK;
 }
 
 int s2r_get_program_pan(const s2r_synth *s, uint32_t program, float *pan, float *key_spread) {
     if (!s) return S2R_ERR_INVALID;
     if (program >= s->bank.size()) return S2R_ERR_INVALID;
-    if (pan) *pan = s->prog_pan[program];
-    if (key_spread) *key_spread = s->prog_spread[program];
+    if (pan) *pan = s->mixer.prog[program].pan;
+    if (key_spread) *key_spread = s->mixer.prog[program].spread;
     return S2R_OK;
 }
 
 int s2r_get_voice_pans(s2r_synth *s, float *pans) {
     if (!s || !pans) return S2R_ERR_INVALID;
     if (!s->kids.empty()) return set_err(s, S2R_ERR_INVALID, "voice pans are kept by single-device handles, not by a device list");
-    if (!s->pan_used) { std::fill(pans, pans + s->shard_voices, 0.0f); return S2R_OK; }
+    if (!(s->mixer.used & kMixPan)) { std::fill(pans, pans + s->shard_voices, 0.0f); return S2R_OK; }
     // (pans of note_ons inside a fill not rendered yet are not the voices' yet)
-    pan_settle(s);
-    std::memcpy(pans, s->pans.data(), (size_t)s->shard_voices * sizeof(float));
+    mixer_settle(s);
+    std::memcpy(pans, s->mixer.pan.data(), (size_t)s->shard_voices * sizeof(float));
     return S2R_OK;
 }
 
@@ -2617,9 +2557,9 @@ int s2r_set_voice_pans(s2r_synth *s, const float *pans) {
     if (!s->kids.empty()) return set_err(s, S2R_ERR_INVALID, "voice pans are kept by single-device handles, not by a device list");
     for (uint32_t i = 0; i < s->shard_voices; i++)
         if (!pan_in_range(pans[i])) return set_err(s, S2R_ERR_PATCH_RANGE, "voice %u: pan %g does not lie in [-1, 1]", i, (double)pans[i]);
-    pan_begin(s);
-    pan_settle(s);
-    std::memcpy(s->pans.data(), pans, (size_t)s->shard_voices * sizeof(float));
+    (void)mixer_begin(s, kMixPan);
+    mixer_settle(s);
+    std::memcpy(s->mixer.pan.data(), pans, (size_t)s->shard_voices * sizeof(float));
     s->gains_dirty = kGainsAll;
     return S2R_OK;
 }
@@ -2658,7 +2598,7 @@ static int fill_rows_mixed(s2r_synth *s, float *out, size_t capacity, uint32_t n
         S2R_HIP(s, hipHostGetDevicePointer((void **)&s->bus_out_dev, s->bus_out, 0));
     }
     fold_frame0_records(s);
-    pan_settle(s); mix_settle(s); prog_settle(s); send_settle(s);
+    mixer_settle(s);
     s->pan_ev_used = 0;
     const uint32_t last_event = s->fill_time;
     // a bus fill with a program fader away from where the last one left it ramps; whatever the device holds from
@@ -2671,20 +2611,14 @@ static int fill_rows_mixed(s2r_synth *s, float *out, size_t capacity, uint32_t n
     } else {
         // Events inside the fill: the per-voice rows and the event chains exclude each other in the render kernels, and an
         // event at frame f acts "exactly as if the caller had split the fill there" (s2r.h) — so the fill IS split there: the
-        // records of one frame are folded like untimed ones (fold_frame0_records), their note_ons' pans become the voices', and
+        // records of one frame are folded like untimed ones (fold_frame0_records), what their note_ons give becomes the voices', and
         // the segment up to the next event frame is rendered.  (Records arrive in non-decreasing frame order.)
         std::vector<S2rTimedEvent> recs;
         recs.swap(s->tpending);
         for (const S2rTimedEvent &te : recs) s->tlast[te.voice] = -1;
-        std::vector<s2r_synth::PanEvent> pev;
-        pev.swap(s->pan_timed);
-        std::vector<s2r_synth::MixEvent> mev;
-        mev.swap(s->mix_timed);
-        std::vector<s2r_synth::ProgEvent> gev;
-        gev.swap(s->prog_timed);
-        std::vector<s2r_synth::SendEvent> sev;
-        sev.swap(s->send_timed);
-        size_t k = 0, kp = 0, km = 0, kg = 0, ks = 0;
+        std::vector<s2r_synth::Mixer::Record> mrecs;
+        mrecs.swap(s->mixer.timed);
+        size_t k = 0, km = 0;
         uint32_t at = 0;
         while (at < frames) {
             for (; k < recs.size() && recs[k].frame <= at; k++) {
@@ -2699,18 +2633,15 @@ static int fill_rows_mixed(s2r_synth *s, float *out, size_t capacity, uint32_t n
                 if (te.flags & S2R_EV_RESTART) { e.flags = S2R_EV_RESTART | (te.program << S2R_EV_PROGRAM_SHIFT); e.pitch = te.pitch; e.seed = te.seed; }
                 if (te.flags & S2R_EV_RELEASE) e.flags |= S2R_EV_RELEASE;
             }
-            for (; kp < pev.size() && pev[kp].frame <= at; kp++) { s->pans[pev[kp].local] = pev[kp].pan; s->gains_dirty = kGainsAll; }
+            for (; km < mrecs.size() && mrecs[km].frame <= at; km++) { s->mixer.apply(mrecs[km]); s->gains_dirty = kGainsAll; }
             const uint32_t next = k < recs.size() && recs[k].frame < frames ? recs[k].frame : (uint32_t)frames;
-            for (; km < mev.size() && mev[km].frame <= at; km++) { s->vgain[mev[km].local] = mev[km].gain; s->vbus[mev[km].local] = mev[km].bus; s->gains_dirty = kGainsAll; }
-            for (; kg < gev.size() && gev[kg].frame <= at; kg++) { s->vprog[gev[kg].local] = gev[kg].program; s->gains_dirty = kGainsAll; }
-            for (; ks < sev.size() && sev[ks].frame <= at; ks++) { s->vsend[sev[ks].local] = sev[ks].send; s->vsbus[sev[ks].local] = sev[ks].bus; s->gains_dirty = kGainsAll; }
             rc = pan_segment(s, at, next - at, last_event, sample_rate_hz, n_buses, (uint32_t)frames, ramp);
             if (rc != S2R_OK) { s->fill_time = 0; return rc; }
             at = next;
         }
     }
     S2R_HIP(s, hipStreamSynchronize(s->stream));
-    if (n_buses && s->fader_used) { s->prog_fader_app = s->prog_fader; s->prog_shift_app = s->prog_shift; }      // the faders have arrived
+    if (n_buses && (s->mixer.used & kMixFader)) snap_faders(s);  // the faders have arrived
     if (n_buses) std::memcpy(out, s->bus_out, 2 * frames * n_buses * sizeof(float));
     else std::memcpy(out, s->out_host, 2 * frames * sizeof(float));
     if (s->timing) {
@@ -2742,27 +2673,29 @@ int s2r_set_program_mix(s2r_synth *s, uint32_t program, float level, float veloc
                        (double)level, (double)velocity_sens, bus, S2R_MAX_BUSES);
     if (!s) return S2R_ERR_INVALID;
     if (program >= s->bank.size()) return set_err(s, S2R_ERR_INVALID, "program %u: the bank holds %zu patches", program, s->bank.size());
-    if (level != 1.0f || velocity_sens != 0.0f || bus != 0u) { mix_begin(s); mix_settle(s); }
-    s->prog_level[program] = level; s->prog_sens[program] = velocity_sens; s->prog_bus[program] = (uint8_t)bus;
+    if (level != 1.0f || velocity_sens != 0.0f || bus != 0u) { (void)mixer_begin(s, kMixLevel); mixer_settle(s); }
+    s2r_synth::ProgramMix &p = s->mixer.prog[program];
+    p.level = level; p.sens = velocity_sens; p.bus = (uint8_t)bus;
     return S2R_OK;
 }
 
 int s2r_get_program_mix(const s2r_synth *s, uint32_t program, float *level, float *velocity_sens, uint32_t *bus) {
     if (!s) return S2R_ERR_INVALID;
     if (program >= s->bank.size()) return S2R_ERR_INVALID;
-    if (level) *level = s->prog_level[program];
-    if (velocity_sens) *velocity_sens = s->prog_sens[program];
-    if (bus) *bus = s->prog_bus[program];
+    const s2r_synth::ProgramMix &p = s->mixer.prog[program];
+    if (level) *level = p.level;
+    if (velocity_sens) *velocity_sens = p.sens;
+    if (bus) *bus = p.bus;
     return S2R_OK;
 }
 
 int s2r_get_voice_mix(s2r_synth *s, float *gains, uint8_t *buses) {
     if (!s || !gains || !buses) return S2R_ERR_INVALID;
     if (!s->kids.empty()) return set_err(s, S2R_ERR_INVALID, "voice mixes are kept by single-device handles, not by a device list");
-    if (!s->mix_used) { std::fill(gains, gains + s->shard_voices, 1.0f); std::memset(buses, 0, s->shard_voices); return S2R_OK; }
-    mix_settle(s);
-    std::memcpy(gains, s->vgain.data(), (size_t)s->shard_voices * sizeof(float));
-    std::memcpy(buses, s->vbus.data(), (size_t)s->shard_voices);
+    if (!(s->mixer.used & kMixLevel)) { std::fill(gains, gains + s->shard_voices, 1.0f); std::memset(buses, 0, s->shard_voices); return S2R_OK; }
+    mixer_settle(s);
+    std::memcpy(gains, s->mixer.gain.data(), (size_t)s->shard_voices * sizeof(float));
+    std::memcpy(buses, s->mixer.bus.data(), (size_t)s->shard_voices);
     return S2R_OK;
 }
 
@@ -2772,10 +2705,10 @@ int s2r_set_voice_mix(s2r_synth *s, const float *gains, const uint8_t *buses) {
     for (uint32_t i = 0; i < s->shard_voices; i++)
         if (!unit_in_range(gains[i]) || buses[i] >= S2R_MAX_BUSES)
             return set_err(s, S2R_ERR_PATCH_RANGE, "voice %u: gain %g, bus %u: the gain lies in [0, 1], the bus below %u", i, (double)gains[i], (unsigned)buses[i], S2R_MAX_BUSES);
-    mix_begin(s);
-    mix_settle(s);
-    std::memcpy(s->vgain.data(), gains, (size_t)s->shard_voices * sizeof(float));
-    std::memcpy(s->vbus.data(), buses, (size_t)s->shard_voices);
+    (void)mixer_begin(s, kMixLevel);
+    mixer_settle(s);
+    std::memcpy(s->mixer.gain.data(), gains, (size_t)s->shard_voices * sizeof(float));
+    std::memcpy(s->mixer.bus.data(), buses, (size_t)s->shard_voices);
     s->gains_dirty = kGainsAll;
     return S2R_OK;
 }
@@ -2791,29 +2724,29 @@ int s2r_set_program_send(s2r_synth *s, uint32_t program, float send, uint32_t se
     if (!s->kids.empty() || s->parent) return set_err(s, S2R_ERR_INVALID, "program sends are kept by single-device handles, not by a device list");
     if (program >= s->bank.size()) return set_err(s, S2R_ERR_INVALID, "program %u: the bank holds %zu patches", program, s->bank.size());
     if (send != 0.0f || send_bus != 0u) {
-        const int rc = send_begin(s);
+        const int rc = mixer_begin(s, kMixSend);
         if (rc != S2R_OK) return rc;
-        send_settle(s);
+        mixer_settle(s);
     }
-    s->prog_send[program] = send; s->prog_sbus[program] = (uint8_t)send_bus;
+    s->mixer.prog[program].send = send; s->mixer.prog[program].send_bus = (uint8_t)send_bus;
     return S2R_OK;
 }
 
 int s2r_get_program_send(const s2r_synth *s, uint32_t program, float *send, uint32_t *send_bus) {
     if (!s) return S2R_ERR_INVALID;
     if (!s->kids.empty() || s->parent || program >= s->bank.size()) return S2R_ERR_INVALID;
-    if (send) *send = s->prog_send[program];
-    if (send_bus) *send_bus = s->prog_sbus[program];
+    if (send) *send = s->mixer.prog[program].send;
+    if (send_bus) *send_bus = s->mixer.prog[program].send_bus;
     return S2R_OK;
 }
 
 int s2r_get_voice_sends(s2r_synth *s, float *sends, uint8_t *send_buses) {
     if (!s || !sends || !send_buses) return S2R_ERR_INVALID;
     if (!s->kids.empty() || s->parent) return set_err(s, S2R_ERR_INVALID, "voice sends are kept by single-device handles, not by a device list");
-    if (!s->send_used) { std::fill(sends, sends + s->shard_voices, 0.0f); std::memset(send_buses, 0, s->shard_voices); return S2R_OK; }
-    send_settle(s);
-    std::memcpy(sends, s->vsend.data(), (size_t)s->shard_voices * sizeof(float));
-    std::memcpy(send_buses, s->vsbus.data(), (size_t)s->shard_voices);
+    if (!(s->mixer.used & kMixSend)) { std::fill(sends, sends + s->shard_voices, 0.0f); std::memset(send_buses, 0, s->shard_voices); return S2R_OK; }
+    mixer_settle(s);
+    std::memcpy(sends, s->mixer.send.data(), (size_t)s->shard_voices * sizeof(float));
+    std::memcpy(send_buses, s->mixer.send_bus.data(), (size_t)s->shard_voices);
     return S2R_OK;
 }
 
@@ -2823,11 +2756,11 @@ int s2r_set_voice_sends(s2r_synth *s, const float *sends, const uint8_t *send_bu
     for (uint32_t i = 0; i < s->shard_voices; i++)
         if (!unit_in_range(sends[i]) || send_buses[i] >= S2R_MAX_BUSES)
             return set_err(s, S2R_ERR_PATCH_RANGE, "voice %u: send %g, send bus %u: the send lies in [0, 1], the bus below %u", i, (double)sends[i], (unsigned)send_buses[i], S2R_MAX_BUSES);
-    const int rc = send_begin(s);
+    const int rc = mixer_begin(s, kMixSend);
     if (rc != S2R_OK) return rc;
-    send_settle(s);
-    std::memcpy(s->vsend.data(), sends, (size_t)s->shard_voices * sizeof(float));
-    std::memcpy(s->vsbus.data(), send_buses, (size_t)s->shard_voices);
+    mixer_settle(s);
+    std::memcpy(s->mixer.send.data(), sends, (size_t)s->shard_voices * sizeof(float));
+    std::memcpy(s->mixer.send_bus.data(), send_buses, (size_t)s->shard_voices);
     s->gains_dirty = kGainsAll;
     return S2R_OK;
 }
@@ -2852,27 +2785,28 @@ int s2r_set_program_fader(s2r_synth *s, uint32_t program, float fader, float pan
     if (program >= s->bank.size()) return set_err(s, S2R_ERR_INVALID, "program %u: the bank holds %zu patches", program, s->bank.size());
     if (fader != 1.0f || pan_shift != 0.0f) {
         S2R_REFUSE_BROKEN(s);
-        const int rc = fader_begin(s);
+        const int rc = mixer_begin(s, kMixFader);
         if (rc != S2R_OK) return rc;
     }
-    s->prog_fader[program] = fader; s->prog_shift[program] = pan_shift;
+    s->mixer.prog[program].fader = fader; s->mixer.prog[program].shift = pan_shift;
     return S2R_OK;
 }
 
 int s2r_get_program_fader(const s2r_synth *s, uint32_t program, float *fader, float *pan_shift, float *applied_fader, float *applied_pan_shift) {
     if (!s) return S2R_ERR_INVALID;
     if (!s->kids.empty() || s->parent || program >= s->bank.size()) return S2R_ERR_INVALID;
-    if (fader) *fader = s->prog_fader[program];
-    if (pan_shift) *pan_shift = s->prog_shift[program];
-    if (applied_fader) *applied_fader = s->prog_fader_app[program];
-    if (applied_pan_shift) *applied_pan_shift = s->prog_shift_app[program];
+    const s2r_synth::ProgramMix &p = s->mixer.prog[program];
+    if (fader) *fader = p.fader;
+    if (pan_shift) *pan_shift = p.shift;
+    if (applied_fader) *applied_fader = p.fader_app;
+    if (applied_pan_shift) *applied_pan_shift = p.shift_app;
     return S2R_OK;
 }
 
 int s2r_snap_program_faders(s2r_synth *s) {
     if (!s) return S2R_ERR_INVALID;
     if (!s->kids.empty() || s->parent) return set_err(s, S2R_ERR_INVALID, "program faders are kept by single-device handles, not by a device list");
-    s->prog_fader_app = s->prog_fader; s->prog_shift_app = s->prog_shift;
+    snap_faders(s);
     s->gains_dirty |= kGainsBus;
     return S2R_OK;
 }
@@ -3064,13 +2998,18 @@ int s2r_import_state(s2r_synth *s, const s2r_voice_state *voices) {
         h[7 * pv + i] = s2r_f2u(in.filt_x1); h[8 * pv + i] = s2r_f2u(in.filt_x2);
         h[9 * pv + i] = s2r_f2u(in.filt_y1); h[10 * pv + i] = s2r_f2u(in.filt_y2);
         h[11 * pv + i] = in.program;
-        if (s->fader_used) s->vprog[i] = in.program;
+        if (s->mixer.used & kMixFader) s->mixer.program[i] = in.program;
         h[12 * pv + i] = s2r_f2u(in.osc_z);
         s->pool->set_voice(to_pool(s, i), in.note, in.started != 0, in.released != 0,
                            in.current_frame_offset, in.release_frame_offset, in.velocity);
     }
     s->pool->rebuild();
-    if (s->fader_used) { s->prog_timed.clear(); s->gains_dirty = kGainsAll; }
+    if (s->mixer.used & kMixFader) {                             // (programs still queued belong to the state that was replaced)
+        std::vector<s2r_synth::Mixer::Record> &q = s->mixer.timed;
+        for (s2r_synth::Mixer::Record &r : q) r.mask &= ~kMixFader;
+        q.erase(std::remove_if(q.begin(), q.end(), [](const s2r_synth::Mixer::Record &r) { return r.mask == 0; }), q.end());
+        s->gains_dirty = kGainsAll;
+    }
     S2R_HIP(s, hipMemcpyAsync(s->voice_mem, h.data(), pv * kVoiceWords * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
     S2R_HIP(s, hipStreamSynchronize(s->stream));
     return S2R_OK;

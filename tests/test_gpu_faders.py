@@ -217,6 +217,50 @@ def test_the_frame_index_counts_from_the_start_of_the_call_across_event_segments
     tw.check_bus_fill(64, [8], "the static fill after it")
 
 
+@pytest.mark.parametrize("frames", [256, 250])
+def test_the_first_fader_call_finds_timed_note_ons_waiting(frames):
+    """pans and a mix in use, one batch with note_ons at frames 0, 16 and 128 (program 1 from 16, program 0 again from 128) and
+    a note_off at 128 — and only then the handle's FIRST fader call: the programs of the note_ons that wait join the pans and
+    gains already queued for them.  The voices started at 0 and 128 ramp, those started at 16 stand still.  250 frames: the last
+    segment holds 122, a frame per thread; the others take the 16-byte loads.  Segment by segment from the oracle."""
+    tw = FaderTwin(272, max_frames=256, block=64, bank=_bank2())
+    gpu = tw.gpus[0]
+    tw.set_program_pan(0, -0.5, 1.0)
+    tw.set_program_pan(1, 0.7, -1.0 / 3.0)
+    tw.set_program_mix(0, 0.7, 0.5, 0)
+    tw.set_program_mix(1, 1.0, 1.0 / 3.0, 1)
+    ev = [(ON, 36 + v % 61, 0, VELS[v % 4]) for v in range(40)]
+    ev += [(PROGRAM, 1, 16, 0.0)] + [(ON, 50 + k, 16, VELS[(k + 1) % 4]) for k in range(12)]
+    ev += [(PROGRAM, 0, 128, 0.0)] + [(ON, 70 + k, 128, VELS[(k + 2) % 4]) for k in range(9)] + [(OFF, 40, 128, 0.0)]
+    gpu.note_events(np.array(ev, dtype=s2.NOTE_EVENT_DTYPE))
+    tw.set_program_fader(0, 0.25, 0.5)
+    assert tw.moving()
+    got = gpu.sample_buses(frames, SR, 2)
+    want = np.zeros((2, frames, 2), dtype=F)
+    still = np.zeros((2, frames, 2), dtype=F)
+    started = {0: [], 16: [], 128: []}
+    bounds = [0, 16, 128, frames]
+    for a, b in zip(bounds[:-1], bounds[1:]):
+        for k, n, f, vel in ev:
+            if f == a and k == ON:
+                started[a].append(tw._cpu_on(n, vel))
+            elif f == a:
+                tw.cpu_event(k, n, vel)
+        pv = tw.rows(b - a)
+        want[:, a:b] = tw.want_faded(pv, 2, i0=a, n_call=frames)
+        still[:, a:b] = tw.want_faded(pv, 2, i0=a, n_call=frames, ramp=False)
+    assert len(set(sum(started.values(), []))) == 40 + 12 + 9     # nobody took another's voice
+    g0l, g0r, dl, dr = tw.ramp(0, frames)
+    moves = (dl != 0.0) | (dr != 0.0)
+    assert moves[started[0]].all() and moves[started[128]].all() and not moves[started[16]].any()
+    assert not np.array_equal(ubits(want[0]), ubits(still[0])) and ubits(want[1]).any()
+    assert_bits_equal_finite(got, want, "first fader call over waiting note_ons, %d frames" % frames)
+    tw.commit()
+    tw.check_faders("after the first fader call")
+    tw.check_mix("after the first fader call")
+    tw.check_bus_fill(64, [2], "the static fill after it")
+
+
 def test_the_frame_index_counts_from_the_start_of_the_call_across_slices(monkeypatch):
     """the same ramp on a handle whose rows buffer holds 48 frames: 21 slices, one mixdown launch each"""
     monkeypatch.setenv("S2R_PAN_SLICE", "48")

@@ -324,6 +324,80 @@ def test_events_inside_a_bus_fill_with_sends(frames):
     tw.check_bus_fill(32, [4], "after a mono fill with timed events")
 
 
+@pytest.mark.parametrize("frames", [256, 250])
+@pytest.mark.parametrize("n_buses", [3, 8])
+def test_pans_levels_sends_and_a_moving_fader_over_event_segments_and_slices(n_buses, frames, monkeypatch):
+    """every attribute of the mixer in one fill: pans with key spread, levels and buses on both programs, sends from both to
+    different buses, program 0's fader on its way, note_ons, note_offs and program changes at frames 0, 16 and 128, and a rows
+    buffer of 48 frames, so that the segments are sliced as well.  The expectation is the oracle's rows times M + A under the
+    ramp, segment by segment.  Then a checkpoint with a fader move pending into a fresh handle: the next fill is equal on both."""
+    monkeypatch.setenv("S2R_PAN_SLICE", "48")
+    V = 272
+    tw = SendTwin(V, max_frames=256, block=64, bank=_bank2())
+    a = tw.gpus[0]
+    tw.set_program_pan(0, -0.5, 1.0)
+    tw.set_program_pan(1, 0.7, -1.0 / 3.0)
+    tw.set_program_mix(0, 0.7, 0.5, 1)
+    tw.set_program_mix(1, 1.0, 1.0 / 3.0, 3)                     # (a 3-bus call folds it onto bus 2, where its send lands too)
+    tw.set_program_send(0, 0.5, 0)
+    tw.set_program_send(1, 1.0 / 3.0, 2)
+    for v in range(V // 2):
+        if v % 34 == 0:
+            tw.program_change((v // 34) % 2)
+        tw.note_on(36 + v % 61, VELS[(v + v // 4) % 4])
+    tw.set_program_fader(1, 0.5, 0.25)
+    tw.snap()
+    tw.set_program_fader(0, 0.25, 1.0)
+    ev = [(OFF, 40, 0, 0.0), (PROGRAM, 0, 0, 0.0), (ON, 90, 0, 0.25), (PROGRAM, 1, 0, 0.0), (ON, 91, 0, 0.6)]
+    ev += [(ON, 50, 16, 0.6), (OFF, 36, 16, 0.0), (PROGRAM, 0, 16, 0.0), (ON, 50, 16, 0.25), (ON, 77, 16, 1.0)]
+    ev += [(OFF, 50, 128, 0.0), (PROGRAM, 1, 128, 0.0)] + [(ON, 60 + k, 128, VELS[(k + 1) % 4]) for k in range(8)] + [(OFF, 61, 128, 0.0)]
+    a.note_events(np.array(ev, dtype=s2.NOTE_EVENT_DTYPE))
+    got = a.sample_buses(frames, SR, n_buses)
+    a.L.s2r_debug_pan_slice.restype = C.c_uint32
+    a.L.s2r_debug_pan_slice.argtypes = [C.c_void_p]
+    assert a.L.s2r_debug_pan_slice(a.h) == 48
+    want = np.zeros((n_buses, frames, 2), dtype=F)
+    still = np.zeros((n_buses, frames, 2), dtype=F)
+    bounds = [0, 16, 128, frames]
+    for lo, hi in zip(bounds[:-1], bounds[1:]):
+        for k, n, f, vel in ev:
+            if f == lo:
+                tw.cpu_event(k, n, vel)
+        pv = tw.rows(hi - lo)
+        want[:, lo:hi] = tw.want_sends(pv, n_buses, i0=lo, n_call=frames)
+        still[:, lo:hi] = tw.want_sends(pv, n_buses, i0=lo, n_call=frames, ramp=False)
+    assert ubits(want[0]).any() and ubits(want[2]).any() and not np.array_equal(ubits(want), ubits(still))
+    assert_bits_equal_finite(got, want, "everything at once, %d buses, %d frames" % (n_buses, frames))
+    tw.commit()
+    tw.check_faders("everything at once")
+    tw.check_sends("everything at once")
+    # the checkpoint: state, voice pans, voice mix, voice sends and the faders' four values, a move pending
+    tw.set_program_fader(0, 0.75, -1.5)
+    tw.set_program_fader(1, 0.0, 0.25)
+    state, pans, (gains, buses), (sends, sbuses) = a.export_state(), a.voice_pans(), a.voice_mix(), a.voice_sends()
+    faders = [a.get_program_fader(p) for p in range(2)]
+    assert all(f[:2] != f[2:] for f in faders)
+    b = s2.Synth(V, max_frames=256, block_voices=64)
+    b.set_patch_bank(_bank2())
+    b.import_state(state)
+    b.set_voice_pans(pans)
+    b.set_voice_mix(gains, buses)
+    b.set_voice_sends(sends, sbuses)
+    for p, f in enumerate(faders):
+        b.set_program_fader(p, f[2], f[3])
+    b.snap_program_faders()
+    for p, f in enumerate(faders):
+        b.set_program_fader(p, f[0], f[1])
+    assert [b.get_program_fader(p) for p in range(2)] == faders
+    tw.note_off(41)
+    b.note_off(41)
+    pv = tw.rows(frames)
+    want = tw.want_sends(pv, n_buses)
+    x, y = a.sample_buses(frames, SR, n_buses), b.sample_buses(frames, SR, n_buses)
+    assert_bits_equal_finite(x, want, "the checkpointed handle")
+    assert_bits_equal_finite(y, x, "the resumed handle")
+
+
 def test_checkpoint_carries_the_voice_sends():
     V = 272
     tw = SendTwin(V, max_frames=256, block=64, bank=_bank2())
