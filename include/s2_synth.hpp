@@ -123,6 +123,20 @@ class Synth {
     void set_voice_sends(const float *sends, const uint8_t *send_buses) { check(s2r_set_voice_sends(h_, sends, send_buses)); }
     static float send_gain(float g, float send) { return s2r_send_gain(g, send); }
 
+    // per-bus convolution reverb (build-defined; s2r.h: s2r_set_bus_reverb): n_taps taps per channel (ir_r nullptr: ir_l for both), a
+    // dry and a wet in [0, 1] and a history of n_taps - 1 stereo frames that carries from call to call — in sample_buses only
+    void set_bus_reverb(uint32_t bus, const float *ir_l, const float *ir_r, uint32_t n_taps, float dry = 0.0f, float wet = 1.0f) {
+        check(s2r_set_bus_reverb(h_, bus, ir_l, ir_r, n_taps, dry, wet));
+    }
+    void clear_bus_reverb(uint32_t bus) { check(s2r_set_bus_reverb(h_, bus, nullptr, nullptr, 0, 0.0f, 0.0f)); }
+    void set_bus_reverb_mix(uint32_t bus, float dry, float wet) { check(s2r_set_bus_reverb_mix(h_, bus, dry, wet)); }
+    void get_bus_reverb(uint32_t bus, uint32_t *n_taps, float *dry, float *wet) const { check(s2r_get_bus_reverb(h_, bus, n_taps, dry, wet)); }
+    void bus_reverb_history(uint32_t bus, float *lr, size_t capacity) { check(s2r_get_bus_reverb_history(h_, bus, lr, capacity)); }     // 2 * (n_taps - 1) floats, oldest first, L R
+    void set_bus_reverb_history(uint32_t bus, const float *lr, size_t count) { check(s2r_set_bus_reverb_history(h_, bus, lr, count)); }
+    static int reverb_reference(const float *ir, uint32_t n_taps, const float *x_with_history, uint32_t frames, float dry, float wet, float *out) {
+        return s2r_reverb_reference(ir, n_taps, x_with_history, frames, dry, wet, out);
+    }
+
     s2r_synth *handle() { return h_; }
 
   private:

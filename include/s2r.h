@@ -35,7 +35,8 @@ extern "C" {
  * s2r_get_program_pan, s2r_get_voice_pans, s2r_set_voice_pans, s2r_fill_panned, s2r_voice_pan, s2r_pan_gains,
  * s2r_set_program_mix, s2r_get_program_mix, s2r_get_voice_mix, s2r_set_voice_mix, s2r_voice_gain, s2r_fill_buses,
  * s2r_set_program_fader, s2r_get_program_fader, s2r_snap_program_faders, s2r_fader_gains, s2r_set_program_send,
- * s2r_get_program_send, s2r_get_voice_sends, s2r_set_voice_sends, s2r_send_gain. */
+ * s2r_get_program_send, s2r_get_voice_sends, s2r_set_voice_sends, s2r_send_gain, s2r_set_bus_reverb, s2r_set_bus_reverb_mix,
+ * s2r_get_bus_reverb, s2r_get_bus_reverb_history, s2r_set_bus_reverb_history, s2r_reverb_reference. */
 #define S2R_ABI_VERSION 4
 
 typedef enum {
@@ -340,6 +341,46 @@ int s2r_set_program_send(s2r_synth *s, uint32_t program, float send, uint32_t se
 int s2r_get_program_send(const s2r_synth *s, uint32_t program, float *send, uint32_t *send_bus);
 int s2r_get_voice_sends(s2r_synth *s, float *sends, uint8_t *send_buses);
 int s2r_set_voice_sends(s2r_synth *s, const float *sends, const uint8_t *send_buses);
+
+/* BUILD-DEFINED per-bus convolution reverb (the reference has no effects; DESIGN.md 4.16 gives the op sequence): the effect at the end
+ * of the send -> effect -> return chain, computed on the device the bus signal is already on.  A bus b in [0, S2R_MAX_BUSES) may carry
+ * a reverb: K taps (1 .. S2R_MAX_IR_TAPS) per channel, ir_l[k] and ir_r[k] (left feeds left, right feeds right; ir_r NULL: ir_l for
+ * both), a `dry` and a `wet` in [0, 1], and a history of K - 1 stereo frames that carries from call to call, +0.0 right after the reverb
+ * is set.  With x_c[i] what s2r_fill_buses writes for bus b, channel c, frame i of a call of N frames WITHOUT a reverb (the dry signal, bit
+ * for bit), h_c[j] (j = 1 .. K - 1) the dry sample j frames before frame 0 of the call, and xs(i - k) = i >= k ? x_c[i - k] : h_c[k - i]:
+ *   P_s = ((+0.0 + ir[256 s] * xs(i - 256 s)) + ir[256 s + 1] * xs(i - 256 s - 1)) + ...   for the taps of segment s = 0 .. ceil(K / 256) - 1
+ *   in index order (S2R_IR_SEGMENT = 256 taps; the last segment ends at tap K - 1), every product rounded, then every sum;
+ *   r = ((+0.0 + P_0) + P_1) + ...;   y = (dry * x_c[i]) + (wet * r)   (two rounded products, one rounded sum; binary32, no fma,
+ *   denormals kept) — and y is what the call writes to out[(b * N + i) * 2 + c].  Non-finite bus samples are outside the contract.
+ * After a call that returns S2R_OK the history is the last K - 1 frames of (old history, then x_c[0 .. N)): calls of any lengths
+ * concatenate.  The reverb runs once per call over all N frames, after every event segment and rows slice of the call has been mixed.  A
+ * reverb on a bus >= the call's n_buses is idle in that call (no output, history untouched); voices folded onto the last bus of a call
+ * are part of that bus's dry signal.  ONLY s2r_fill_buses applies reverbs; every other fill ignores them.  A reverb is a property of
+ * the bus: s2r_set_patch_bank, program changes and s2r_import_state leave it alone.  A s2r_fill_buses call refused before any launch
+ * (capacity, bus count, frames) leaves every history untouched.  A handle on which no reverb was ever set launches what it launched
+ * before.  Taps, history, the segments' partial sums and a staging buffer for the dry buses live in device memory allocated when a
+ * reverb is set (S2R_ERR_OUT_OF_MEMORY when that fails), never inside a fill, and released with the handle.
+ *   s2r_set_bus_reverb: replaces any earlier reverb of the bus and zeroes its history; n_taps == 0 removes it (the bus then returns the
+ *   dry signal bit for bit, -0.0 included).  S2R_ERR_PATCH_RANGE for a dry or wet outside [0, 1] or NaN, n_taps > S2R_MAX_IR_TAPS,
+ *   bus >= S2R_MAX_BUSES or a tap that is not finite (checked before the handle is looked at; nothing is changed); S2R_ERR_INVALID for
+ *   a NULL ir_l with n_taps > 0.
+ *   s2r_set_bus_reverb_mix: dry and wet alone; taps and history stay.  s2r_get_bus_reverb: n_taps is 0 for a bus without one; any
+ *   pointer may be NULL.
+ *   s2r_get_bus_reverb_history / s2r_set_bus_reverb_history: the 2 * (K - 1) floats of the history, oldest frame first, L then R inside
+ *   a frame: the checkpoint companions of s2r_get_voice_sends / s2r_set_voice_sends.  S2R_ERR_INVALID for a capacity below, or a
+ *   count other than, 2 * (K - 1), and — like s2r_set_bus_reverb_mix — on a bus without a reverb.
+ *   Single-device handles (a device-list handle: S2R_ERR_INVALID from all five).
+ *   s2r_reverb_reference: the rule above for ONE channel on the host (no device, no handle): x_with_history holds K - 1 samples of
+ *   history, oldest first, then `frames` dry samples; out receives `frames` samples.  Range checks as above; S2R_ERR_INVALID for a NULL
+ *   pointer or n_taps == 0. */
+#define S2R_MAX_IR_TAPS 65536u
+#define S2R_IR_SEGMENT 256u
+int s2r_set_bus_reverb(s2r_synth *s, uint32_t bus, const float *ir_l, const float *ir_r, uint32_t n_taps, float dry, float wet);
+int s2r_set_bus_reverb_mix(s2r_synth *s, uint32_t bus, float dry, float wet);
+int s2r_get_bus_reverb(const s2r_synth *s, uint32_t bus, uint32_t *n_taps, float *dry, float *wet);
+int s2r_get_bus_reverb_history(s2r_synth *s, uint32_t bus, float *lr, size_t capacity);
+int s2r_set_bus_reverb_history(s2r_synth *s, uint32_t bus, const float *lr, size_t count);
+int s2r_reverb_reference(const float *ir, uint32_t n_taps, const float *x_with_history, uint32_t frames, float dry, float wet, float *out);
 
 /* BUILD-DEFINED 4x oversampling (the reference has none; BASELINE config [4]): renders 4 * frames at
  * 4 * sample_rate_hz through the same path and decimates the mix by a 63-tap windowed sinc whose history

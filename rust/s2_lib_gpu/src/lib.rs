@@ -160,6 +160,13 @@ pub mod ffi {
         pub fn s2r_get_voice_sends(s: *mut S2rSynth, sends: *mut f32, send_buses: *mut u8) -> c_int;
         pub fn s2r_set_voice_sends(s: *mut S2rSynth, sends: *const f32, send_buses: *const u8) -> c_int;
         pub fn s2r_send_gain(g: f32, send: f32) -> f32;
+        pub fn s2r_set_bus_reverb(s: *mut S2rSynth, bus: u32, ir_l: *const f32, ir_r: *const f32, n_taps: u32, dry: f32, wet: f32) -> c_int;
+        pub fn s2r_set_bus_reverb_mix(s: *mut S2rSynth, bus: u32, dry: f32, wet: f32) -> c_int;
+        pub fn s2r_get_bus_reverb(s: *const S2rSynth, bus: u32, n_taps: *mut u32, dry: *mut f32, wet: *mut f32) -> c_int;
+        pub fn s2r_get_bus_reverb_history(s: *mut S2rSynth, bus: u32, lr: *mut f32, capacity: usize) -> c_int;
+        pub fn s2r_set_bus_reverb_history(s: *mut S2rSynth, bus: u32, lr: *const f32, count: usize) -> c_int;
+        pub fn s2r_reverb_reference(ir: *const f32, n_taps: u32, x_with_history: *const f32, frames: u32, dry: f32, wet: f32,
+                                    out: *mut f32) -> c_int;
         pub fn s2r_shard_voices(s: *const S2rSynth) -> u32;
         pub fn s2r_fill_device(s: *mut S2rSynth, dev_out: *mut f32, frames: usize, sample_rate_hz: u32,
                                hip_stream: *mut c_void) -> c_int;
@@ -191,6 +198,10 @@ pub fn pan_gains(p: f32) -> (f32, f32) {
 
 /// `S2R_MAX_BUSES`: the most stereo buses one `sample_buses` call writes.
 pub const MAX_BUSES: u32 = 8;
+/// `S2R_MAX_IR_TAPS`: the longest response of a bus reverb, per channel.
+pub const MAX_IR_TAPS: u32 = 65536;
+/// `S2R_IR_SEGMENT`: the taps of one segment of the reverb's sum (part of its rule).
+pub const IR_SEGMENT: u32 = 256;
 
 /// Host-only: the gain a note_on of `velocity` gives its voice under a program's level and velocity sensitivity — DESIGN.md 4.13.
 pub fn voice_gain(level: f32, velocity_sens: f32, velocity: f32) -> f32 {
@@ -202,6 +213,18 @@ pub fn fader_gains(pan: f32, w: f32, fader: f32, pan_shift: f32) -> (f32, f32) {
     let (mut gl, mut gr) = (0.0f32, 0.0f32);
     unsafe { ffi::s2r_fader_gains(pan, w, fader, pan_shift, &mut gl, &mut gr) };
     (gl, gr)
+}
+
+/// Host-only: the bus reverb's rule for one channel (`s2r_reverb_reference`).  `x_with_history`: `ir.len() - 1`
+/// samples of history, oldest first, then the dry samples; returns one output sample per dry sample, or the status.
+pub fn reverb_reference(ir: &[f32], x_with_history: &[f32], dry: f32, wet: f32) -> Result<Vec<f32>, i32> {
+    assert!(!ir.is_empty() && x_with_history.len() + 1 >= ir.len());
+    let frames = x_with_history.len() + 1 - ir.len();
+    let mut out = vec![0.0f32; frames];
+    let rc = unsafe {
+        ffi::s2r_reverb_reference(ir.as_ptr(), ir.len() as u32, x_with_history.as_ptr(), frames as u32, dry, wet, out.as_mut_ptr())
+    };
+    if rc == 0 { Ok(out) } else { Err(rc) }
 }
 
 /// Host-only: the gain of a voice's aux send, `g * send` in one rounded multiply — DESIGN.md 4.15.
@@ -469,6 +492,43 @@ pub mod synth {
             let (mut send, mut bus) = (0.0f32, 0u32);
             self.check(unsafe { ffi::s2r_get_program_send(self.handle, program, &mut send, &mut bus) });
             (send, bus)
+        }
+
+        /// Build-defined per-bus convolution reverb (`s2r_set_bus_reverb`, include/s2r.h): `ir_l.len()` taps per channel (`ir_r`
+        /// `None`: `ir_l` for both), a dry and a wet in [0, 1]; replaces any earlier reverb of the bus and zeroes its history.  In
+        /// `sample_buses` only.
+        pub fn set_bus_reverb(&mut self, bus: u32, ir_l: &[f32], ir_r: Option<&[f32]>, dry: f32, wet: f32) {
+            assert!(!ir_l.is_empty() && ir_r.map_or(true, |r| r.len() == ir_l.len()));
+            let r = ir_r.map_or(std::ptr::null(), |r| r.as_ptr());
+            self.check(unsafe { ffi::s2r_set_bus_reverb(self.handle, bus, ir_l.as_ptr(), r, ir_l.len() as u32, dry, wet) });
+        }
+
+        pub fn clear_bus_reverb(&mut self, bus: u32) {
+            self.check(unsafe { ffi::s2r_set_bus_reverb(self.handle, bus, std::ptr::null(), std::ptr::null(), 0, 0.0, 0.0) });
+        }
+
+        /// Dry and wet alone; taps and history stay.
+        pub fn set_bus_reverb_mix(&mut self, bus: u32, dry: f32, wet: f32) {
+            self.check(unsafe { ffi::s2r_set_bus_reverb_mix(self.handle, bus, dry, wet) });
+        }
+
+        /// (n_taps, dry, wet); n_taps is 0 for a bus without a reverb.
+        pub fn get_bus_reverb(&self, bus: u32) -> (u32, f32, f32) {
+            let (mut k, mut dry, mut wet) = (0u32, 0.0f32, 0.0f32);
+            self.check(unsafe { ffi::s2r_get_bus_reverb(self.handle, bus, &mut k, &mut dry, &mut wet) });
+            (k, dry, wet)
+        }
+
+        /// The `2 * (n_taps - 1)` floats of the reverb's history, oldest frame first, L then R: checkpoint companion of `voice_sends`.
+        pub fn bus_reverb_history(&mut self, bus: u32) -> Vec<f32> {
+            let k = self.get_bus_reverb(bus).0 as usize;
+            let mut lr = vec![0.0f32; 2 * k.max(1) - 2];
+            self.check(unsafe { ffi::s2r_get_bus_reverb_history(self.handle, bus, lr.as_mut_ptr(), lr.len()) });
+            lr
+        }
+
+        pub fn set_bus_reverb_history(&mut self, bus: u32, lr: &[f32]) {
+            self.check(unsafe { ffi::s2r_set_bus_reverb_history(self.handle, bus, lr.as_ptr(), lr.len()) });
         }
 
         /// Every voice's send and send bus: checkpoint companions of `voice_mix`.

@@ -405,3 +405,24 @@ hipError_t s2r_launch_pan_mix(const S2rPanMix &m, hipStream_t stream);
 // s2r_bus_mix_kernel (the instantiation for the call's bus count, the rows' alignment, RAMP = d_l != nullptr and SEND = send !=
 // nullptr) and s2r_bus_combine_kernel; d_l without d_r or send without send_bus: hipErrorInvalidValue
 hipError_t s2r_launch_bus_mix(const S2rBusMix &m, hipStream_t stream);
+
+// The per-bus convolution reverb of s2r_fill_buses.  A bus's line holds, per channel, its K - 1 frames of history
+// and behind them the call's dry frames; `next` receives the history the next call starts from (the host swaps the two).
+struct S2rFxBus {
+    const float *taps;            // [2][tstride] planar: ir_L, then ir_R, each padded with +0.0 up to whole segments
+    float *line, *next;           // [2][lstride] planar each
+    float *partials;              // [2][n_seg][S2rFx.pstride]: P_s of every segment
+    uint32_t n_taps, n_seg;       // K (0: no reverb on this bus) and ceil(K / S2R_IR_SEGMENT)
+    uint32_t tstride, lstride;    // tstride >= n_seg * S2R_IR_SEGMENT; lstride >= K - 1 + frames
+    float dry, wet;
+};
+struct S2rFx {
+    S2rFxBus bus[S2R_MAX_BUSES];
+    const float *stage;           // [n_buses][2 * frames]: what the bus combine wrote, bus-major, L, R interleaved inside a bus
+    float *out;                   // the same layout: the caller-visible output
+    uint32_t n_buses, frames;
+    uint32_t pstride;             // >= frames, a multiple of 8
+};
+// stage -> lines (or, for a bus without a reverb, -> out unchanged), the segments' partial sums, and the kernel that adds them, mixes
+// dry and wet into `out` and advances the history
+hipError_t s2r_launch_bus_fx(const S2rFx &fx, hipStream_t stream);

@@ -315,6 +315,20 @@ struct s2r_synth {
     float *bus_out = nullptr, *bus_out_dev = nullptr;            // pinned and device-mapped: S2R_MAX_BUSES * 2 * max_frames floats
     float bus_mix_ms = -1.0f;                    // pan_mix_ms of the last s2r_fill_buses (tools/bus_time.py)
     bool bus_dev_ramped = false;                 // what bus_gains_dev holds was sent for a ramped fill: (G0, step), not the static gains
+    // The buses' convolution reverbs (s2r_set_bus_reverb).  Everything is allocated when a reverb is set, never in a fill.
+    struct BusFx {
+        uint32_t n_taps = 0;                     // K; 0: the bus has no reverb
+        float dry = 0.0f, wet = 0.0f;
+        float *taps = nullptr;                   // [2][tstride]: ir_L, ir_R, padded with +0.0 up to whole segments
+        float *line[2] = {nullptr, nullptr};     // [2][lstride] each: K - 1 frames of history per channel in front of a call's dry frames; line[cur] holds the history
+        float *partials = nullptr;               // [2][n_seg][fx_pstride]
+        uint32_t tstride = 0, lstride = 0;
+        int cur = 0;
+    } fx[S2R_MAX_BUSES];
+    float *fx_stage = nullptr;                   // [S2R_MAX_BUSES][2 * max_frames]: where the bus combine writes in a call that runs a reverb
+    float *bus_mix_out = nullptr;                // where the bus combine of the call under way writes: bus_out_dev, or fx_stage
+    hipEvent_t fx_ev[2] = {nullptr, nullptr};    // s2r_set_timing: around the reverb's kernels of the last bus fill
+    float bus_fx_ms = -1.0f;                     // ... and the time between them (0 when the fill ran none; tools/reverb_time.py)
     float pitch_table[256];
     hipEvent_t t0 = nullptr, t1 = nullptr;
     bool timing = false, timed = false, no_flat_shortcut = false;
@@ -1795,7 +1809,7 @@ int pan_segment(s2r_synth *s, uint32_t at, uint32_t n, uint32_t last_event, uint
             m.frames = len; m.stride = len;                      // (the render kernel's rows are `frames` apart)
             m.partials = s->bus_partials; m.pstride = s->pan_slice;
             m.n_groups = n_groups; m.blocks_per_group = blocks_per_group;
-            m.out = s->bus_out_dev + 2u * (size_t)(at + done); m.ostride = 2u * (size_t)total;
+            m.out = s->bus_mix_out + 2u * (size_t)(at + done); m.ostride = 2u * (size_t)total;
             m.n_buses = n_buses;
             if (ramp) {
                 m.d_l = reinterpret_cast<const float *>(dev + o.dl); m.d_r = reinterpret_cast<const float *>(dev + o.dr);
@@ -1873,6 +1887,43 @@ int fill_host(s2r_synth *s, float *out, size_t frames, uint32_t sample_rate, boo
     return S2R_OK;
 }
 
+void fx_release(s2r_synth::BusFx &f) {
+    if (f.taps) (void)hipFree(f.taps);
+    if (f.line[0]) (void)hipFree(f.line[0]);
+    if (f.line[1]) (void)hipFree(f.line[1]);
+    if (f.partials) (void)hipFree(f.partials);
+    f = s2r_synth::BusFx{};
+}
+
+inline uint32_t fx_pstride(const s2r_synth *s) { return (s->cfg.max_frames + 7u) & ~7u; }
+
+// the reverbs of the buses of a call of n_buses (one on a bus past them is idle in that call)
+inline bool fx_active(const s2r_synth *s, uint32_t n_buses) {
+    for (uint32_t b = 0; b < n_buses; b++) if (s->fx[b].n_taps) return true;
+    return false;
+}
+
+// After the last segment's mixdown of a bus fill that wrote into the staging buffer: the reverbs' kernels on the handle's stream.
+int fx_launch(s2r_synth *s, uint32_t n_buses, uint32_t frames) {
+    S2rFx fx{};
+    for (uint32_t b = 0; b < n_buses; b++) {
+        const s2r_synth::BusFx &f = s->fx[b];
+        if (!f.n_taps) continue;
+        S2rFxBus &d = fx.bus[b];
+        d.taps = f.taps; d.line = f.line[f.cur]; d.next = f.line[f.cur ^ 1]; d.partials = f.partials;
+        d.n_taps = f.n_taps; d.n_seg = (f.n_taps + S2R_IR_SEGMENT - 1u) / S2R_IR_SEGMENT;
+        d.tstride = f.tstride; d.lstride = f.lstride; d.dry = f.dry; d.wet = f.wet;
+    }
+    fx.stage = s->fx_stage; fx.out = s->bus_out_dev; fx.n_buses = n_buses; fx.frames = frames; fx.pstride = fx_pstride(s);
+    if (s->timing) {
+        for (hipEvent_t &e : s->fx_ev) if (!e) S2R_HIP(s, hipEventCreate(&e));
+        S2R_HIP(s, hipEventRecord(s->fx_ev[0], s->stream));
+    }
+    S2R_HIP(s, s2r_launch_bus_fx(fx, s->stream));
+    if (s->timing) S2R_HIP(s, hipEventRecord(s->fx_ev[1], s->stream));
+    return S2R_OK;
+}
+
 void release_all(s2r_synth *s) {
     if (!s) return;
     (void)quiesce(s);
@@ -1927,6 +1978,9 @@ void release_all(s2r_synth *s) {
     if (s->bus_gains_sent) (void)hipEventDestroy(s->bus_gains_sent);
     if (s->bus_partials) (void)hipFree(s->bus_partials);
     if (s->bus_out) (void)hipHostFree(s->bus_out);
+    for (s2r_synth::BusFx &f : s->fx) fx_release(f);
+    if (s->fx_stage) (void)hipFree(s->fx_stage);
+    for (hipEvent_t e : s->fx_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : s->pan_ev) (void)hipEventDestroy(e);
     if (s->voice_ev_head) (void)hipFree(s->voice_ev_head);
     if (s->tev_copy) (void)hipFree(s->tev_copy);
@@ -2597,6 +2651,10 @@ static int fill_rows_mixed(s2r_synth *s, float *out, size_t capacity, uint32_t n
         S2R_HIP(s, hipHostMalloc((void **)&s->bus_out, (size_t)2 * S2R_MAX_BUSES * s->cfg.max_frames * sizeof(float), kHostPolled));
         S2R_HIP(s, hipHostGetDevicePointer((void **)&s->bus_out_dev, s->bus_out, 0));
     }
+    // a call with a reverb on one of its buses mixes into the staging buffer, and the reverbs' kernels write the caller-visible
+    // output; without one the combine writes there itself, as it always did
+    const bool fx_on = n_buses && fx_active(s, n_buses);
+    s->bus_mix_out = fx_on ? s->fx_stage : s->bus_out_dev;
     fold_frame0_records(s);
     mixer_settle(s);
     s->pan_ev_used = 0;
@@ -2640,7 +2698,12 @@ static int fill_rows_mixed(s2r_synth *s, float *out, size_t capacity, uint32_t n
             at = next;
         }
     }
+    if (fx_on) {                                                 // once per call, over all of its frames
+        rc = fx_launch(s, n_buses, (uint32_t)frames);
+        if (rc != S2R_OK) return rc;
+    }
     S2R_HIP(s, hipStreamSynchronize(s->stream));
+    if (fx_on) for (uint32_t b = 0; b < n_buses; b++) if (s->fx[b].n_taps) s->fx[b].cur ^= 1;     // the histories have moved on
     if (n_buses && (s->mixer.used & kMixFader)) snap_faders(s);  // the faders have arrived
     if (n_buses) std::memcpy(out, s->bus_out, 2 * frames * n_buses * sizeof(float));
     else std::memcpy(out, s->out_host, 2 * frames * sizeof(float));
@@ -2648,6 +2711,10 @@ static int fill_rows_mixed(s2r_synth *s, float *out, size_t capacity, uint32_t n
         float sum = 0.0f;
         for (size_t k = 0; k < s->pan_ev_used; k += 2) { float ms = 0.0f; S2R_HIP(s, hipEventElapsedTime(&ms, s->pan_ev[k], s->pan_ev[k + 1])); sum += ms; }
         (n_buses ? s->bus_mix_ms : s->pan_mix_ms) = sum;
+        if (n_buses) {
+            s->bus_fx_ms = 0.0f;
+            if (fx_on) S2R_HIP(s, hipEventElapsedTime(&s->bus_fx_ms, s->fx_ev[0], s->fx_ev[1]));
+        }
     }
     return S2R_OK;
 }
@@ -2763,6 +2830,137 @@ int s2r_set_voice_sends(s2r_synth *s, const float *sends, const uint8_t *send_bu
     std::memcpy(s->mixer.send_bus.data(), send_buses, (size_t)s->shard_voices);
     s->gains_dirty = kGainsAll;
     return S2R_OK;
+}
+
+// ---- per-bus convolution reverb ----
+// The rule on the host, one channel: segments of S2R_IR_SEGMENT taps in index order from +0.0, the segments in order from +0.0,
+// y = dry * x + wet * r; every product and every sum rounded on its own.
+int s2r_reverb_reference(const float *ir, uint32_t n_taps, const float *x_with_history, uint32_t frames, float dry, float wet, float *out) {
+    if (!unit_in_range(dry) || !unit_in_range(wet) || n_taps > S2R_MAX_IR_TAPS) return S2R_ERR_PATCH_RANGE;
+    if (!ir || n_taps == 0 || !x_with_history || (!out && frames)) return S2R_ERR_INVALID;
+    for (uint32_t k = 0; k < n_taps; k++) if (!std::isfinite(ir[k])) return S2R_ERR_PATCH_RANGE;
+    for (uint32_t i = 0; i < frames; i++) {
+        const float *x = x_with_history + (n_taps - 1u) + i;     // x[-k]: the dry sample k frames before frame i
+        float r = 0.0f;
+        for (uint32_t k0 = 0; k0 < n_taps; k0 += S2R_IR_SEGMENT) {
+            const uint32_t k1 = k0 + S2R_IR_SEGMENT < n_taps ? k0 + S2R_IR_SEGMENT : n_taps;
+            float p = 0.0f;
+            for (uint32_t k = k0; k < k1; k++) {
+                const float t = ir[k] * x[-(ptrdiff_t)k];
+                p = p + t;
+            }
+            r = r + p;
+        }
+        const float d = dry * x[0], w = wet * r;
+        out[i] = d + w;
+    }
+    return S2R_OK;
+}
+
+static int fx_handle(const s2r_synth *s, const char *who) {
+    if (!s) return S2R_ERR_INVALID;
+    if (!s->kids.empty() || s->parent) return set_err(const_cast<s2r_synth *>(s), S2R_ERR_INVALID, "%s: bus reverbs are kept by single-device handles, not by a device list", who);
+    return S2R_OK;
+}
+
+int s2r_set_bus_reverb(s2r_synth *s, uint32_t bus, const float *ir_l, const float *ir_r, uint32_t n_taps, float dry, float wet) {
+    // (the values first, like s2r_set_program_send)
+    if (!unit_in_range(dry) || !unit_in_range(wet) || n_taps > S2R_MAX_IR_TAPS || bus >= S2R_MAX_BUSES)
+        return set_err(s, S2R_ERR_PATCH_RANGE, "bus %u: %u taps, dry %g, wet %g: dry and wet lie in [0, 1], at most %u taps, the bus below %u", bus, n_taps,
+                       (double)dry, (double)wet, S2R_MAX_IR_TAPS, S2R_MAX_BUSES);
+    if (!ir_r) ir_r = ir_l;
+    if (ir_l)
+        for (uint32_t k = 0; k < n_taps; k++)
+            if (!std::isfinite(ir_l[k]) || !std::isfinite(ir_r[k])) return set_err(s, S2R_ERR_PATCH_RANGE, "bus %u: tap %u is not finite", bus, k);
+    int rc = fx_handle(s, "s2r_set_bus_reverb");
+    if (rc != S2R_OK) return rc;
+    if (n_taps && !ir_l) return set_err(s, S2R_ERR_INVALID, "s2r_set_bus_reverb: %u taps and no response", n_taps);
+    if (s->ring_count) return set_err(s, S2R_ERR_INVALID, "s2r_set_bus_reverb with fills of s2r_fill_begin in flight: s2r_fill_end first");
+    S2R_QUIESCE(s);
+    S2R_HIP(s, hipSetDevice(s->device));
+    S2R_HIP(s, hipStreamSynchronize(s->stream));
+    if (n_taps == 0) { fx_release(s->fx[bus]); return S2R_OK; }
+    s2r_synth::BusFx f;
+    const uint32_t n_seg = (n_taps + S2R_IR_SEGMENT - 1u) / S2R_IR_SEGMENT;
+    f.n_taps = n_taps; f.dry = dry; f.wet = wet;
+    f.tstride = n_seg * S2R_IR_SEGMENT;
+    f.lstride = (n_taps - 1u + s->cfg.max_frames + 3u) & ~3u;
+    std::vector<float> padded(2u * (size_t)f.tstride, 0.0f);
+    std::memcpy(padded.data(), ir_l, (size_t)n_taps * sizeof(float));
+    std::memcpy(padded.data() + f.tstride, ir_r, (size_t)n_taps * sizeof(float));
+    const size_t line_bytes = 2u * (size_t)f.lstride * sizeof(float);
+    hipError_t e = hipSuccess;
+    if (!s->fx_stage) e = hipMalloc((void **)&s->fx_stage, (size_t)2 * S2R_MAX_BUSES * s->cfg.max_frames * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void **)&f.taps, padded.size() * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void **)&f.line[0], line_bytes);
+    if (e == hipSuccess) e = hipMalloc((void **)&f.line[1], line_bytes);
+    if (e == hipSuccess) e = hipMalloc((void **)&f.partials, (size_t)2 * n_seg * fx_pstride(s) * sizeof(float));
+    // (on the handle's stream, and waited for there: nothing here waits for another handle's kernels)
+    if (e == hipSuccess) e = hipMemcpyAsync(f.taps, padded.data(), padded.size() * sizeof(float), hipMemcpyHostToDevice, s->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(f.line[0], 0, line_bytes, s->stream);    // the history: +0.0 everywhere
+    if (e == hipSuccess) e = hipMemsetAsync(f.line[1], 0, line_bytes, s->stream);
+    { const hipError_t e2 = hipStreamSynchronize(s->stream); if (e == hipSuccess) e = e2; }
+    if (e != hipSuccess) {
+        fx_release(f);
+        return set_err(s, e == hipErrorOutOfMemory ? S2R_ERR_OUT_OF_MEMORY : S2R_ERR_HIP, "s2r_set_bus_reverb: %s", hipGetErrorString(e));
+    }
+    fx_release(s->fx[bus]);                                      // replaces any earlier reverb of the bus
+    s->fx[bus] = f;
+    return S2R_OK;
+}
+
+int s2r_set_bus_reverb_mix(s2r_synth *s, uint32_t bus, float dry, float wet) {
+    if (!unit_in_range(dry) || !unit_in_range(wet) || bus >= S2R_MAX_BUSES)
+        return set_err(s, S2R_ERR_PATCH_RANGE, "bus %u: dry %g, wet %g: both lie in [0, 1], the bus below %u", bus, (double)dry, (double)wet, S2R_MAX_BUSES);
+    const int rc = fx_handle(s, "s2r_set_bus_reverb_mix");
+    if (rc != S2R_OK) return rc;
+    if (!s->fx[bus].n_taps) return set_err(s, S2R_ERR_INVALID, "bus %u carries no reverb", bus);
+    s->fx[bus].dry = dry; s->fx[bus].wet = wet;
+    return S2R_OK;
+}
+
+int s2r_get_bus_reverb(const s2r_synth *s, uint32_t bus, uint32_t *n_taps, float *dry, float *wet) {
+    if (bus >= S2R_MAX_BUSES) return S2R_ERR_PATCH_RANGE;
+    if (!s || !s->kids.empty() || s->parent) return S2R_ERR_INVALID;
+    if (n_taps) *n_taps = s->fx[bus].n_taps;
+    if (dry) *dry = s->fx[bus].dry;
+    if (wet) *wet = s->fx[bus].wet;
+    return S2R_OK;
+}
+
+// the history crosses the boundary as frames, oldest first, L then R; the device keeps it planar
+static int fx_history(s2r_synth *s, uint32_t bus, float *get, const float *set, size_t count, const char *who) {
+    if (bus >= S2R_MAX_BUSES) return set_err(s, S2R_ERR_PATCH_RANGE, "%s: bus %u, below %u", who, bus, S2R_MAX_BUSES);
+    const int rc = fx_handle(s, who);
+    if (rc != S2R_OK) return rc;
+    s2r_synth::BusFx &f = s->fx[bus];
+    if (!f.n_taps) return set_err(s, S2R_ERR_INVALID, "%s: bus %u carries no reverb", who, bus);
+    const size_t h = f.n_taps - 1u;
+    if (set ? count != 2 * h : count < 2 * h) return set_err(s, S2R_ERR_INVALID, "%s: the history of bus %u is %zu floats, not %zu", who, bus, 2 * h, count);
+    if (h == 0) return S2R_OK;
+    if (!get && !set) return set_err(s, S2R_ERR_INVALID, "%s: null buffer", who);
+    S2R_QUIESCE(s);
+    S2R_HIP(s, hipSetDevice(s->device));
+    S2R_HIP(s, hipStreamSynchronize(s->stream));
+    std::vector<float> planar(2 * h);
+    float *line = f.line[f.cur];
+    if (get) {
+        for (int c = 0; c < 2; c++) S2R_HIP(s, hipMemcpyAsync(planar.data() + c * h, line + (size_t)c * f.lstride, h * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+        S2R_HIP(s, hipStreamSynchronize(s->stream));
+        for (size_t i = 0; i < h; i++) { get[2 * i] = planar[i]; get[2 * i + 1] = planar[h + i]; }
+    } else {
+        for (size_t i = 0; i < h; i++) { planar[i] = set[2 * i]; planar[h + i] = set[2 * i + 1]; }
+        for (int c = 0; c < 2; c++) S2R_HIP(s, hipMemcpyAsync(line + (size_t)c * f.lstride, planar.data() + c * h, h * sizeof(float), hipMemcpyHostToDevice, s->stream));
+        S2R_HIP(s, hipStreamSynchronize(s->stream));
+    }
+    return S2R_OK;
+}
+
+int s2r_get_bus_reverb_history(s2r_synth *s, uint32_t bus, float *lr, size_t capacity) { return fx_history(s, bus, lr, nullptr, capacity, "s2r_get_bus_reverb_history"); }
+
+int s2r_set_bus_reverb_history(s2r_synth *s, uint32_t bus, const float *lr, size_t count) {
+    static const float none = 0.0f;                              // (a null lr: refused by fx_history unless K = 1, which has no history)
+    return fx_history(s, bus, nullptr, lr ? lr : &none, lr ? count : (count ? (size_t)-1 : 0), "s2r_set_bus_reverb_history");
 }
 
 // ---- program faders ----
@@ -3252,6 +3450,8 @@ extern "C" float s2r_debug_pan_mix_ms(const s2r_synth *s) { return s && s->timin
 extern "C" uint32_t s2r_debug_pan_slice(const s2r_synth *s) { return s ? s->pan_slice : 0u; }
 // ... and of the bus mixdown's kernels in the last s2r_fill_buses (tools/bus_time.py)
 extern "C" float s2r_debug_bus_mix_ms(const s2r_synth *s) { return s && s->timing ? s->bus_mix_ms : -1.0f; }
+// ... and of the buses' reverb kernels in that fill: 0 when it ran none (tools/reverb_time.py)
+extern "C" float s2r_debug_bus_fx_ms(const s2r_synth *s) { return s && s->timing ? s->bus_fx_ms : -1.0f; }
 
 extern "C" uint32_t s2r_debug_read_stamps(s2r_synth *s, unsigned long long *out, uint32_t max_waves) {
 #if defined(S2R_STAMPS)

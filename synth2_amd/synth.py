@@ -34,6 +34,8 @@ S2R_ERR_TOO_MANY_FRAMES = -6
 S2R_ERR_OFFSET_OVERFLOW = -7
 S2R_ERR_OUT_OF_MEMORY = -8
 MAX_BUSES = 8                               # S2R_MAX_BUSES
+MAX_IR_TAPS = 65536                         # S2R_MAX_IR_TAPS
+IR_SEGMENT = 256                            # S2R_IR_SEGMENT
 
 
 class S2rError(RuntimeError):
@@ -187,6 +189,12 @@ def load_library():
         "s2r_get_voice_sends": (C.c_int, [H, _f32p, C.POINTER(C.c_uint8)]),
         "s2r_set_voice_sends": (C.c_int, [H, _f32p, C.POINTER(C.c_uint8)]),
         "s2r_send_gain": (C.c_float, [C.c_float, C.c_float]),
+        "s2r_set_bus_reverb": (C.c_int, [H, C.c_uint32, _f32p, _f32p, C.c_uint32, C.c_float, C.c_float]),
+        "s2r_set_bus_reverb_mix": (C.c_int, [H, C.c_uint32, C.c_float, C.c_float]),
+        "s2r_get_bus_reverb": (C.c_int, [H, C.c_uint32, C.POINTER(C.c_uint32), _f32p, _f32p]),
+        "s2r_get_bus_reverb_history": (C.c_int, [H, C.c_uint32, _f32p, C.c_size_t]),
+        "s2r_set_bus_reverb_history": (C.c_int, [H, C.c_uint32, _f32p, C.c_size_t]),
+        "s2r_reverb_reference": (C.c_int, [_f32p, C.c_uint32, _f32p, C.c_uint32, C.c_float, C.c_float, _f32p]),
         "s2r_fill_device": (C.c_int, [H, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
         "s2r_fill_device_root": (C.c_int, [H, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
         "s2r_sum_partials_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_size_t, C.c_void_p, C.c_void_p]),
@@ -282,6 +290,22 @@ def fader_gains(pan, w, fader, pan_shift):
 def send_gain(g, send):
     """the gain of a voice's aux send: g * send, one rounded binary32 multiply (s2r_send_gain; host only)"""
     return float(load_library().s2r_send_gain(float(g), float(send)))
+
+
+def reverb_reference(ir, x_with_history, frames, dry, wet):
+    """the bus reverb's rule for one channel on the host (s2r_reverb_reference): ir [K] float32, x_with_history K - 1 samples of
+    history (oldest first) followed by `frames` dry samples; returns the `frames` output samples"""
+    h = np.ascontiguousarray(ir, dtype=np.float32)
+    x = np.ascontiguousarray(x_with_history, dtype=np.float32)
+    frames = int(frames)
+    if h.ndim != 1 or h.size < 1 or x.ndim != 1 or frames < 0 or x.size != h.size - 1 + frames:
+        raise ValueError("reverb_reference: ir is [K] with K >= 1 and x_with_history holds K - 1 + frames samples")
+    out = np.empty(frames, dtype=np.float32)
+    rc = load_library().s2r_reverb_reference(h.ctypes.data_as(_f32p), h.size, x.ctypes.data_as(_f32p), frames, float(dry), float(wet),
+                                             out.ctypes.data_as(_f32p))
+    if rc != S2R_OK:
+        raise S2rError(rc, load_library().s2r_status_string(rc).decode())
+    return out
 
 
 def stream_frame_json(samples):
@@ -570,6 +594,54 @@ class Synth:
     @staticmethod
     def send_gain(g, send):
         return send_gain(g, send)
+
+    # --- per-bus convolution reverb (build-defined; s2r.h: s2r_set_bus_reverb) ---
+    def set_bus_reverb(self, bus, ir, dry=0.0, wet=1.0):
+        """a convolution reverb on a bus of sample_buses: ir is [K] (the same response for both channels) or [K, 2] (left, right),
+        float32, 1 <= K <= MAX_IR_TAPS; dry and wet in [0, 1].  Replaces any earlier reverb of the bus and zeroes its history.  Only
+        sample_buses applies it."""
+        h = np.asarray(ir, dtype=np.float32)
+        if h.ndim == 1:
+            left = right = np.ascontiguousarray(h)
+        elif h.ndim == 2 and h.shape[1] == 2:
+            left, right = np.ascontiguousarray(h[:, 0]), np.ascontiguousarray(h[:, 1])
+        else:
+            raise ValueError("set_bus_reverb: ir is [K] or [K, 2]")
+        if left.size < 1:
+            raise ValueError("set_bus_reverb: at least one tap (clear_bus_reverb removes a reverb)")
+        self._check(self.L.s2r_set_bus_reverb(self.h, int(bus), left.ctypes.data_as(_f32p), right.ctypes.data_as(_f32p), left.size, float(dry), float(wet)))
+
+    def clear_bus_reverb(self, bus):
+        """removes the bus's reverb: the bus returns the dry signal again, bit for bit"""
+        self._check(self.L.s2r_set_bus_reverb(self.h, int(bus), None, None, 0, 0.0, 0.0))
+
+    def set_bus_reverb_mix(self, bus, dry, wet):
+        """dry and wet of the bus's reverb alone; taps and history stay"""
+        self._check(self.L.s2r_set_bus_reverb_mix(self.h, int(bus), float(dry), float(wet)))
+
+    def get_bus_reverb(self, bus):
+        """(n_taps, dry, wet); n_taps is 0 for a bus without a reverb"""
+        k, d, w = C.c_uint32(), C.c_float(), C.c_float()
+        self._check(self.L.s2r_get_bus_reverb(self.h, int(bus), C.byref(k), C.byref(d), C.byref(w)))
+        return k.value, d.value, w.value
+
+    def bus_reverb_history(self, bus):
+        """the K - 1 stereo frames the bus's reverb carries into the next sample_buses call, oldest first: (K - 1, 2) float32
+        (the checkpoint companion of voice_sends)"""
+        k = self.get_bus_reverb(bus)[0]
+        out = np.empty((max(k, 1) - 1, 2), dtype=np.float32)
+        self._check(self.L.s2r_get_bus_reverb_history(self.h, int(bus), out.ctypes.data_as(_f32p), out.size))
+        return out
+
+    def set_bus_reverb_history(self, bus, history):
+        h = np.ascontiguousarray(history, dtype=np.float32)
+        if h.ndim != 2 or h.shape[1] != 2:
+            raise ValueError("set_bus_reverb_history: history is [K - 1, 2]")
+        self._check(self.L.s2r_set_bus_reverb_history(self.h, int(bus), h.ctypes.data_as(_f32p), h.size))
+
+    @staticmethod
+    def reverb_reference(ir, x_with_history, frames, dry, wet):
+        return reverb_reference(ir, x_with_history, frames, dry, wet)
 
     def render_voices(self, frames, sample_rate=SampleRateKhz(48000)):
         """Mix disabled: (shard_voices, frames) float32."""
