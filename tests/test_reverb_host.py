@@ -42,6 +42,46 @@ def np_reverb(ir, x_with_history, frames, dry, wet, segment=SEG):
     return y
 
 
+def f64_reverb_and_bound(ir, line, frames, dry, wet):
+    """One channel with no float32 arithmetic and no segments in it: y64 = dry * x + wet * np.convolve(line, ir)[K - 1 : K - 1 +
+    frames] in float64 over line = K - 1 samples of history, then `frames` dry samples, and the bound that any float32 evaluation of
+    the rule keeps against it.  The rule adds at most min(K, 256) rounded products in a segment, then ceil(K / 256) segment sums,
+    then takes two products and one sum for the mix: no term of y passes through more than n = min(K, 256) + ceil(K / 256) + 2
+    roundings, each of relative size u = 2^-24 while nothing underflows, so (Higham, Accuracy and Stability of Numerical
+    Algorithms, section 3.1) |y - y64| <= gamma_n * (dry * |x| + wet * (|ir| conv |line|)) with gamma_n = n u / (1 - n u); an
+    operation whose result is denormal errs by at most 2^-150 instead, and K products, K sums and the three operations of the mix
+    add at most (K + 3) * 2^-149 for that, generously.  Returns (y64, bound), float64 [frames]."""
+    ir64 = np.ascontiguousarray(ir, dtype=F).astype(np.float64)
+    line64 = np.ascontiguousarray(line, dtype=F).astype(np.float64)
+    K = ir64.size
+    assert line64.size == K - 1 + frames
+    d, w = float(F(dry)), float(F(wet))
+    x = line64[K - 1:]
+    y64 = d * x + w * np.convolve(line64, ir64)[K - 1:K - 1 + frames]
+    n = min(K, SEG) + (K + SEG - 1) // SEG + 2
+    u = 2.0 ** -24
+    gamma = n * u / (1.0 - n * u)
+    bound = gamma * (d * np.abs(x) + w * np.convolve(np.abs(line64), np.abs(ir64))[K - 1:K - 1 + frames]) + (K + 3) * 2.0 ** -149
+    return y64, bound
+
+
+def crafted_denormal(K, seed):
+    """a response scaled by 2^-70 and a history of K - 1 uniform samples scaled by 2^-68, one channel: every product is a denormal
+    (or zero) and so is every sum of them"""
+    ir, x = _case(K, 0, seed)
+    return (ir * F(2.0 ** -70)).astype(F), (x * F(2.0 ** -68)).astype(F)
+
+
+MIXED = np.array([1e30, -1e30, 2.0 ** -126, -2.0 ** -140, -0.0, 0.0, 3.0, 2.0 ** -149], dtype=F)
+
+
+def crafted_mixed(K, seed, shift=0):
+    """a response scaled by 1e-8 and a history of K - 1 samples that repeats MIXED from its element `shift` on, one channel: huge
+    terms that cancel, the smallest normal, denormals, both zeros and an ordinary sample under one segment's taps"""
+    ir, _ = _case(K, 0, seed)
+    return (ir * F(1e-8)).astype(F), np.resize(np.roll(MIXED, -shift), K - 1).astype(F)
+
+
 def _case(K, frames, seed):
     rng = np.random.default_rng(seed)
     ir = (rng.standard_normal(K) * np.exp(-np.arange(K) / max(K / 3.0, 1.0))).astype(F)
@@ -89,6 +129,51 @@ def test_the_longest_response():
     K, frames = s2.MAX_IR_TAPS, 64
     ir, x = _case(K, frames, 13)
     assert np.array_equal(bits(s2.reverb_reference(ir, x, frames, 0.25, 1.0)), bits(np_reverb(ir, x, frames, 0.25, 1.0)))
+
+
+@pytest.mark.parametrize("K", [1, 5, 600, 1300, 2049])
+def test_model_and_reference_are_a_float64_convolution(K):
+    """np_reverb and s2r_reverb_reference are two restatements of one reading of the rule; a plain float64 convolution is none.
+    Both stay inside the summation bound of f64_reverb_and_bound over 2500 frames, which is derived and not measured: a worst
+    case, of which the model uses about a third at K = 1 and under 1 % at K = 2049, so this catches a misreading of the rule — a
+    wrong tap order against the samples, a history off by one, dry and wet swapped — and not a single dropped term."""
+    frames = 2500
+    ir, x = _case(K, frames, 31 * K)
+    for dry, wet in [(0.0, 1.0), (1.0, 0.5), (0.25, 1.0)]:
+        y64, bound = f64_reverb_and_bound(ir, x, frames, dry, wet)
+        assert (bound > 0.0).all() and np.abs(y64).max() > 0.01
+        for name, got in (("np_reverb", np_reverb(ir, x, frames, dry, wet)), ("s2r_reverb_reference", s2.reverb_reference(ir, x, frames, dry, wet))):
+            ratio = np.abs(got.astype(np.float64) - y64) / bound
+            print("K %d dry %g wet %g %s: largest error over the bound %.4f" % (K, dry, wet, name, ratio.max()))
+            assert ratio.max() <= 1.0, (K, dry, wet, name, int(ratio.argmax()), float(ratio.max()))
+    # the bound has teeth where it is meant to: the response against the samples in the wrong order is far outside it
+    if K > 1:
+        y64, bound = f64_reverb_and_bound(ir, x, frames, 0.0, 1.0)
+        assert (np.abs(np_reverb(ir[::-1], x, frames, 0.0, 1.0).astype(np.float64) - y64) > bound).mean() > 0.9
+
+
+def test_reference_on_the_crafted_lines():
+    """the two lines that tests/test_gpu_reverb_tiles.py puts in front of the device through s2r_set_bus_reverb_history, at its K
+    and call length, over an idle bus (+0.0 behind the history) and a sounding one: the reference is the model on bits, so the device
+    test rests on a model that was checked at these inputs.  The conditions the device test states on the model are held here too."""
+    K, frames = 1300, 1500
+    rng = np.random.default_rng(5)
+    for tail in (np.zeros(frames, dtype=F), rng.uniform(-3.0, 3.0, frames).astype(F)):
+        ir, hist = crafted_denormal(K, 41)
+        line = np.concatenate([hist, tail])
+        for dry, wet in [(0.0, 1.0), (0.0, 0.5), (0.25, 1.0)]:
+            want = np_reverb(ir, line, frames, dry, wet)
+            assert np.array_equal(bits(s2.reverb_reference(ir, line, frames, dry, wet)), bits(want)), ("denormal", dry, wet)
+            if not tail.any():                                   # every frame that still sees the history is a denormal, none is flushed
+                mag = np.abs(want[:K - 1].astype(np.float64))
+                assert ((mag > 0.0) & (mag < 2.0 ** -126)).mean() >= 0.9, (dry, wet)
+                assert not bits(want[K - 1:]).any()
+        for shift in (0, 3):
+            ir, hist = crafted_mixed(K, 43, shift)
+            line = np.concatenate([hist, tail])
+            want = np_reverb(ir, line, frames, 0.25, 1.0)
+            assert np.isfinite(want).all() and 1e20 < np.abs(want).max() < 1e25
+            assert np.array_equal(bits(s2.reverb_reference(ir, line, frames, 0.25, 1.0)), bits(want)), ("mixed", shift)
 
 
 def _new_or_skip(**kw):
