@@ -137,6 +137,24 @@ class Synth {
         return s2r_reverb_reference(ir, n_taps, x_with_history, frames, dry, wet, out);
     }
 
+    // the master section (build-defined; s2r.h: s2r_fill_master): a return level per bus and a master fader, each in [0, 1] and each
+    // reaching its target as a ramp across the next sample_master call, and the meters of that call — in sample_master only
+    void set_bus_return(uint32_t bus, float level) { check(s2r_set_bus_return(h_, bus, level)); }
+    void get_bus_return(uint32_t bus, float *level, float *applied = nullptr) const { check(s2r_get_bus_return(h_, bus, level, applied)); }
+    void set_master_fader(float level) { check(s2r_set_master_fader(h_, level)); }
+    void get_master_fader(float *level, float *applied = nullptr) const { check(s2r_get_master_fader(h_, level, applied)); }
+    void snap_master() { check(s2r_snap_master(h_)); }
+    // master_lr: 2 * len floats; stems: nullptr (master only) or what sample_buses writes, stems_capacity floats
+    void sample_master(float *master_lr, float *stems, size_t stems_capacity, uint32_t n_buses, size_t len, SampleRateKhz sample_rate) {
+        check(s2r_fill_master(h_, master_lr, stems, stems_capacity, n_buses, len, sample_rate.v));
+    }
+    // (n_buses + 1) * 2 entries per array: bus-major, L then R, the master last; capacity: entries per array
+    void meters(uint32_t *n_buses, float *peak, float *energy, size_t capacity) const { check(s2r_get_meters(h_, n_buses, peak, energy, capacity)); }
+    static int master_reference(const float *stems, uint32_t n_buses, uint32_t frames, const float *r0, const float *r1, float m0, float m1,
+                                float *master_lr, float *peak, float *energy) {
+        return s2r_master_reference(stems, n_buses, frames, r0, r1, m0, m1, master_lr, peak, energy);
+    }
+
     s2r_synth *handle() { return h_; }
 
   private:

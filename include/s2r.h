@@ -36,7 +36,9 @@ extern "C" {
  * s2r_set_program_mix, s2r_get_program_mix, s2r_get_voice_mix, s2r_set_voice_mix, s2r_voice_gain, s2r_fill_buses,
  * s2r_set_program_fader, s2r_get_program_fader, s2r_snap_program_faders, s2r_fader_gains, s2r_set_program_send,
  * s2r_get_program_send, s2r_get_voice_sends, s2r_set_voice_sends, s2r_send_gain, s2r_set_bus_reverb, s2r_set_bus_reverb_mix,
- * s2r_get_bus_reverb, s2r_get_bus_reverb_history, s2r_set_bus_reverb_history, s2r_reverb_reference. */
+ * s2r_get_bus_reverb, s2r_get_bus_reverb_history, s2r_set_bus_reverb_history, s2r_reverb_reference, s2r_set_bus_return,
+ * s2r_get_bus_return, s2r_set_master_fader, s2r_get_master_fader, s2r_snap_master, s2r_fill_master, s2r_get_meters,
+ * s2r_master_reference. */
 #define S2R_ABI_VERSION 4
 
 typedef enum {
@@ -381,6 +383,48 @@ int s2r_get_bus_reverb(const s2r_synth *s, uint32_t bus, uint32_t *n_taps, float
 int s2r_get_bus_reverb_history(s2r_synth *s, uint32_t bus, float *lr, size_t capacity);
 int s2r_set_bus_reverb_history(s2r_synth *s, uint32_t bus, const float *lr, size_t count);
 int s2r_reverb_reference(const float *ir, uint32_t n_taps, const float *x_with_history, uint32_t frames, float dry, float wet, float *out);
+
+/* BUILD-DEFINED master section (the reference's Synth::sample returns one stream; DESIGN.md 4.17 gives the op sequence): the last stage
+ * of the chain send -> effect -> return -> master, on the device the bus signals are already on.  Every bus b in [0, S2R_MAX_BUSES) has
+ * a `return` level in [0, 1] (default 1) and the handle a master fader in [0, 1] (default 1); each is a target / applied pair like the
+ * program faders.  In a s2r_fill_master call of N frames over n_buses buses, with y_b,c[i] what s2r_fill_buses would write for bus b,
+ * channel c, frame i (reverbs included), (R0_b, R1_b) the bus's applied and target return and (M0, M1) the master's pair:
+ *   r_b[i] = R0_b + (float)i * ((R1_b - R0_b) / (float)N), m[i] likewise from M0 and M1 (i counts from the start of the call);
+ *   t_c[i] = ((+0.0 + r_0[i] * y_0,c[i]) + r_1[i] * y_1,c[i]) + ... in bus order over b < n_buses;  out[2 i + c] = m[i] * t_c[i];
+ * binary32, every operation rounded on its own, no fma, denormals kept.  A pair that did not move has a step of +0: its gain is R0
+ * exactly.  A return of 0 mutes its bus.  METERS of the call: the buses on y_b,c (post-effect, pre-return: what the stems hold), the
+ * master on out.  peak = max_i |v[i]|.  energy: q[i] = v[i] * v[i], rounded; the frames in blocks of S2R_METER_BLOCK, frames past N
+ * counting +0.0; every block reduced by the adjacent-pair tree s[j] = s[2 j] + s[2 j + 1], eight levels; the block sums added in block
+ * order from +0.0.  Non-finite bus samples are outside the contract.  When the call returns S2R_OK applied becomes target for every bus
+ * and the master, and the call commits the program faders and moves the reverb histories exactly as s2r_fill_buses does; a refused or
+ * failed call leaves returns, master fader, meters, faders and histories untouched.  ONLY s2r_fill_master applies returns, the master
+ * fader and the meters: s2r_fill_buses and every other fill ignore them.  They belong to the buses and the handle: s2r_set_patch_bank,
+ * program changes and s2r_import_state leave them alone.  Single-device handles; a handle with an exchange attached takes the setters
+ * and refuses the fill, as it does s2r_fill_buses.  A handle on which s2r_fill_master was never called launches what it launched before.
+ *   s2r_set_bus_return / s2r_set_master_fader set the target: S2R_ERR_PATCH_RANGE for a level outside [0, 1] or NaN or a bus >=
+ *   S2R_MAX_BUSES (checked before the handle is looked at; nothing is changed).  The getters: target and applied; any pointer may be
+ *   NULL.  s2r_snap_master: applied = target for every bus and the master, now — a hard cut, and the way to restore a checkpoint: set
+ *   the applied values, snap, set the targets.
+ *   s2r_fill_master: synchronous; writes 2 * frames floats to master_lr and — when `stems` is not NULL — what s2r_fill_buses writes to
+ *   `stems`, same layout, same capacity check.  stems NULL: master only, and the stems never cross to the host.  Restrictions, events
+ *   inside the call, rows slices and frames == 0 are s2r_fill_buses'.  The first call allocates a device buffer of 2 * S2R_MAX_BUSES *
+ *   max_frames floats and a pinned row of meter partials per S2R_METER_BLOCK frames of max_frames.
+ *   s2r_get_meters: the meters of the last successful s2r_fill_master: (n_buses + 1) * 2 entries per array — bus-major, L then R, the
+ *   master last; S2R_ERR_INVALID before the first successful master fill or when `capacity` (entries per array) is too small; either
+ *   array pointer and n_buses may be NULL.
+ *   s2r_master_reference: the rule above on the host (no device, no handle): stems [n_buses][frames][2], r0 / r1 [n_buses]; writes
+ *   master_lr [frames][2] and the meters in s2r_get_meters' layout; any output pointer may be NULL.  S2R_ERR_PATCH_RANGE for a level
+ *   out of range, S2R_ERR_INVALID for n_buses outside 1 .. S2R_MAX_BUSES or a NULL input. */
+#define S2R_METER_BLOCK 256u
+int s2r_set_bus_return(s2r_synth *s, uint32_t bus, float level);
+int s2r_get_bus_return(const s2r_synth *s, uint32_t bus, float *level, float *applied);
+int s2r_set_master_fader(s2r_synth *s, float level);
+int s2r_get_master_fader(const s2r_synth *s, float *level, float *applied);
+int s2r_snap_master(s2r_synth *s);
+int s2r_fill_master(s2r_synth *s, float *master_lr, float *stems, size_t stems_capacity, uint32_t n_buses, size_t frames, uint32_t sample_rate_hz);
+int s2r_get_meters(const s2r_synth *s, uint32_t *n_buses, float *peak, float *energy, size_t capacity);
+int s2r_master_reference(const float *stems, uint32_t n_buses, uint32_t frames, const float *r0, const float *r1, float m0, float m1,
+                         float *master_lr, float *peak, float *energy);
 
 /* BUILD-DEFINED 4x oversampling (the reference has none; BASELINE config [4]): renders 4 * frames at
  * 4 * sample_rate_hz through the same path and decimates the mix by a 63-tap windowed sinc whose history

@@ -167,6 +167,16 @@ pub mod ffi {
         pub fn s2r_set_bus_reverb_history(s: *mut S2rSynth, bus: u32, lr: *const f32, count: usize) -> c_int;
         pub fn s2r_reverb_reference(ir: *const f32, n_taps: u32, x_with_history: *const f32, frames: u32, dry: f32, wet: f32,
                                     out: *mut f32) -> c_int;
+        pub fn s2r_set_bus_return(s: *mut S2rSynth, bus: u32, level: f32) -> c_int;
+        pub fn s2r_get_bus_return(s: *const S2rSynth, bus: u32, level: *mut f32, applied: *mut f32) -> c_int;
+        pub fn s2r_set_master_fader(s: *mut S2rSynth, level: f32) -> c_int;
+        pub fn s2r_get_master_fader(s: *const S2rSynth, level: *mut f32, applied: *mut f32) -> c_int;
+        pub fn s2r_snap_master(s: *mut S2rSynth) -> c_int;
+        pub fn s2r_fill_master(s: *mut S2rSynth, master_lr: *mut f32, stems: *mut f32, stems_capacity: usize, n_buses: u32, frames: usize,
+                               sample_rate_hz: u32) -> c_int;
+        pub fn s2r_get_meters(s: *const S2rSynth, n_buses: *mut u32, peak: *mut f32, energy: *mut f32, capacity: usize) -> c_int;
+        pub fn s2r_master_reference(stems: *const f32, n_buses: u32, frames: u32, r0: *const f32, r1: *const f32, m0: f32, m1: f32,
+                                    master_lr: *mut f32, peak: *mut f32, energy: *mut f32) -> c_int;
         pub fn s2r_shard_voices(s: *const S2rSynth) -> u32;
         pub fn s2r_fill_device(s: *mut S2rSynth, dev_out: *mut f32, frames: usize, sample_rate_hz: u32,
                                hip_stream: *mut c_void) -> c_int;
@@ -202,6 +212,8 @@ pub const MAX_BUSES: u32 = 8;
 pub const MAX_IR_TAPS: u32 = 65536;
 /// `S2R_IR_SEGMENT`: the taps of one segment of the reverb's sum (part of its rule).
 pub const IR_SEGMENT: u32 = 256;
+/// `S2R_METER_BLOCK`: the frames of one block of the meters' energy tree (part of the master section's rule).
+pub const METER_BLOCK: u32 = 256;
 
 /// Host-only: the gain a note_on of `velocity` gives its voice under a program's level and velocity sensitivity — DESIGN.md 4.13.
 pub fn voice_gain(level: f32, velocity_sens: f32, velocity: f32) -> f32 {
@@ -225,6 +237,21 @@ pub fn reverb_reference(ir: &[f32], x_with_history: &[f32], dry: f32, wet: f32) 
         ffi::s2r_reverb_reference(ir.as_ptr(), ir.len() as u32, x_with_history.as_ptr(), frames as u32, dry, wet, out.as_mut_ptr())
     };
     if rc == 0 { Ok(out) } else { Err(rc) }
+}
+
+/// Host-only: the master section's rule (`s2r_master_reference`).  `stems`: `r0.len()` buses of `frames` L, R
+/// pairs, bus-major; `r0` / `r1`: the returns' applied and target levels; returns (master, peak, energy) — the meters hold
+/// `(n_buses + 1) * 2` entries, bus-major, L then R, the master last — or the status.
+pub fn master_reference(stems: &[f32], r0: &[f32], r1: &[f32], m0: f32, m1: f32) -> Result<(Vec<f32>, Vec<f32>, Vec<f32>), i32> {
+    let nb = r0.len();
+    assert!(nb >= 1 && r1.len() == nb && stems.len() % (2 * nb) == 0);
+    let frames = stems.len() / (2 * nb);
+    let (mut out, mut peak, mut energy) = (vec![0.0f32; 2 * frames], vec![0.0f32; 2 * (nb + 1)], vec![0.0f32; 2 * (nb + 1)]);
+    let rc = unsafe {
+        ffi::s2r_master_reference(stems.as_ptr(), nb as u32, frames as u32, r0.as_ptr(), r1.as_ptr(), m0, m1, out.as_mut_ptr(),
+                                  peak.as_mut_ptr(), energy.as_mut_ptr())
+    };
+    if rc == 0 { Ok((out, peak, energy)) } else { Err(rc) }
 }
 
 /// Host-only: the gain of a voice's aux send, `g * send` in one rounded multiply — DESIGN.md 4.15.
@@ -529,6 +556,57 @@ pub mod synth {
 
         pub fn set_bus_reverb_history(&mut self, bus: u32, lr: &[f32]) {
             self.check(unsafe { ffi::s2r_set_bus_reverb_history(self.handle, bus, lr.as_ptr(), lr.len()) });
+        }
+
+        /// Build-defined master section (`s2r_fill_master`, include/s2r.h): the target of a bus's return level (in [0, 1]), reached
+        /// as a ramp across the next `sample_master` call.  In `sample_master` only.
+        pub fn set_bus_return(&mut self, bus: u32, level: f32) {
+            self.check(unsafe { ffi::s2r_set_bus_return(self.handle, bus, level) });
+        }
+
+        /// (level, applied): the target, and where the last master fill left the return.
+        pub fn get_bus_return(&self, bus: u32) -> (f32, f32) {
+            let (mut level, mut applied) = (0.0f32, 0.0f32);
+            self.check(unsafe { ffi::s2r_get_bus_return(self.handle, bus, &mut level, &mut applied) });
+            (level, applied)
+        }
+
+        pub fn set_master_fader(&mut self, level: f32) {
+            self.check(unsafe { ffi::s2r_set_master_fader(self.handle, level) });
+        }
+
+        pub fn get_master_fader(&self) -> (f32, f32) {
+            let (mut level, mut applied) = (0.0f32, 0.0f32);
+            self.check(unsafe { ffi::s2r_get_master_fader(self.handle, &mut level, &mut applied) });
+            (level, applied)
+        }
+
+        /// applied = target for every return and the master fader, now: a hard cut, and the middle step of restoring a checkpoint.
+        pub fn snap_master(&mut self) {
+            self.check(unsafe { ffi::s2r_snap_master(self.handle) });
+        }
+
+        /// `sample_buses` with the master section behind it: `master` takes `2 * frames` floats; `stems`, when given, what
+        /// `sample_buses` writes (`2 * frames * n_buses` floats) — `None`: the stems never cross to the host.
+        pub fn sample_master(&mut self, master: &mut [f32], stems: Option<&mut [f32]>, n_buses: u32, sample_rate: SampleRateKhz) {
+            assert!(n_buses >= 1 && master.len() % 2 == 0);
+            let frames = master.len() / 2;
+            let (p, cap) = match stems {
+                Some(st) => { assert!(st.len() >= 2 * frames * n_buses as usize); (st.as_mut_ptr(), st.len()) }
+                None => (std::ptr::null_mut(), 0),
+            };
+            self.check(unsafe { ffi::s2r_fill_master(self.handle, master.as_mut_ptr(), p, cap, n_buses, frames, sample_rate.0) });
+        }
+
+        /// (peak, energy) of the last successful `sample_master` call: `(n_buses + 1) * 2` entries each, bus-major, L then R, the
+        /// master last.
+        pub fn meters(&self) -> (Vec<f32>, Vec<f32>) {
+            let cap = 2 * (super::MAX_BUSES as usize + 1);
+            let (mut n, mut peak, mut energy) = (0u32, vec![0.0f32; cap], vec![0.0f32; cap]);
+            self.check(unsafe { ffi::s2r_get_meters(self.handle, &mut n, peak.as_mut_ptr(), energy.as_mut_ptr(), cap) });
+            peak.truncate(2 * (n as usize + 1));
+            energy.truncate(2 * (n as usize + 1));
+            (peak, energy)
         }
 
         /// Every voice's send and send bus: checkpoint companions of `voice_mix`.

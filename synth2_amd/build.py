@@ -19,7 +19,7 @@ LIB = os.path.join(HERE, "libs2r.so")
 SOURCES = ["s2r_render_onepole_square.hip", "s2r_render_onepole_saw.hip", "s2r_render_onepole_triangle.hip",
            "s2r_render_onepole_sine.hip", "s2r_render_general_square.hip", "s2r_render_general_saw.hip",
            "s2r_render_general_triangle.hip", "s2r_render_general_sine.hip", "s2r_render_general_bank.hip",
-           "s2r_aux.hip", "s2r_fx.hip", "s2r_host.cpp", "s2r_patch.cpp", "s2r_stream.cpp"]
+           "s2r_aux.hip", "s2r_fx.hip", "s2r_master.hip", "s2r_host.cpp", "s2r_patch.cpp", "s2r_stream.cpp"]
 HEADERS = ["s2r_device.h", "s2r_math.h", "s2r_patch.h", "s2r_voices.h", "s2r_kern_common.h", "s2r_render_onepole.inc",
            "s2r_render_general.inc"]
 
@@ -57,6 +57,10 @@ NO_SCRATCH_KERNELS = ("s2r_bus_mix_kernel", "s2r_bus_combine_kernel")
 # _check_fx_no_scratch() fails the build if it or its two companions spilled.
 PER_FILE_FLAGS["s2r_fx.hip"] = ["-Rpass-analysis=kernel-resource-usage"]
 FX_KERNELS = ("s2r_fx_stage_kernel", "s2r_fx_convolve_kernel", "s2r_fx_finish_kernel")
+# s2r_master.hip likewise: the master kernel holds up to sixteen stem samples and eighteen meter values per thread, and
+# _check_master_no_scratch() fails the build if one of its four bus counts spilled.
+PER_FILE_FLAGS["s2r_master.hip"] = ["-Rpass-analysis=kernel-resource-usage"]
+MASTER_KERNEL = "s2r_master_kernel"
 if os.environ.get("S2R_EXPERIMENT_BANK_FLAGS"):                 # (development: extra flags for the patch-bank translation unit)
     PER_FILE_FLAGS["s2r_render_general_bank.hip"] = PER_FILE_FLAGS["s2r_render_general_bank.hip"] + os.environ["S2R_EXPERIMENT_BANK_FLAGS"].split()
 
@@ -157,7 +161,7 @@ def _compile_one(args):
         with open(os.path.splitext(obj)[0] + ".resources.txt", "w") as f:
             for name, u in usage:
                 f.write("%s: %s\n" % (name, ", ".join("%s %s" % kv for kv in u.items())))
-        (_check_fx_no_scratch if os.path.basename(src) == "s2r_fx.hip" else _check_no_scratch)(usage)
+        {"s2r_fx.hip": _check_fx_no_scratch, "s2r_master.hip": _check_master_no_scratch}.get(os.path.basename(src), _check_no_scratch)(usage)
     else:
         subprocess.check_call(cmd)
     with open(obj + ".id", "w") as f:
@@ -202,6 +206,17 @@ def _check_fx_no_scratch(usage):
                     raise RuntimeError("libs2r: %s uses scratch or spills (%r): its windows and sums must stay in registers" % (name, u))
     if len(seen) != len(FX_KERNELS):
         raise RuntimeError("libs2r: resource usage of the reverb kernels %s reported, %s expected" % (sorted(seen), list(FX_KERNELS)))
+
+
+def _check_master_no_scratch(usage):
+    seen = 0
+    for name, u in usage:
+        if MASTER_KERNEL in name:
+            seen += 1
+            if u.get("ScratchSize [bytes/lane]") != "0" or u.get("VGPRs Spill") != "0" or u.get("SGPRs Spill") != "0":
+                raise RuntimeError("libs2r: %s uses scratch or spills (%r): its stems and meter values must stay in registers" % (name, u))
+    if seen != 4:
+        raise RuntimeError("libs2r: resource usage of %d master kernels reported, 4 expected (the bus counts 1, 2, 4 and 8)" % seen)
 
 
 def check_m0_contract(lib=None, texts=None):

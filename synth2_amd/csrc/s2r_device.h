@@ -426,3 +426,20 @@ struct S2rFx {
 // stage -> lines (or, for a bus without a reverb, -> out unchanged), the segments' partial sums, and the kernel that adds them, mixes
 // dry and wet into `out` and advances the history
 hipError_t s2r_launch_bus_fx(const S2rFx &fx, hipStream_t stream);
+
+// The master section of s2r_fill_master: the stems of a call, post-effect, each times its return's ramp, added in
+// bus order from +0.0, times the master fader's ramp; and the call's meters.  gain at frame i of the CALL: r0 + (float)i * dr (the
+// product rounded, then the sum); a pair that did not move has dr = +0.0.
+#define S2R_MASTER_CH ((S2R_MAX_BUSES + 1u) * 2u)   // meter channels of a row at most: bus-major, L then R, the master behind the call's buses
+#define S2R_MASTER_ROW (2u * S2R_MASTER_CH)         // a row of block partials: the peaks, then the energies
+struct S2rMaster {
+    const float *stage;           // [n_buses][2 * frames] in device memory: what the last stem writer of the call left, L, R interleaved
+    float *out;                   // interleaved L, R: 2 * frames floats (mapped host memory)
+    float *stems;                 // nullptr, or where the caller-visible stems go (mapped host memory), the layout of `stage`
+    float *partials;              // [ceil(frames / S2R_METER_BLOCK)][S2R_MASTER_ROW] (mapped host memory): one row per meter block
+    uint32_t n_buses, frames;     // 1 .. S2R_MAX_BUSES
+    float r0[S2R_MAX_BUSES], dr[S2R_MAX_BUSES];     // the returns' applied positions and their steps per frame
+    float m0, dm;                 // the master fader's
+};
+// s2r_master_kernel<NB> for the call's bus count (1, 2, 4 or 8 compiled in; a count between them runs the next form with guarded buses)
+hipError_t s2r_launch_master(const S2rMaster &m, hipStream_t stream);

@@ -329,6 +329,22 @@ struct s2r_synth {
     float *bus_mix_out = nullptr;                // where the bus combine of the call under way writes: bus_out_dev, or fx_stage
     hipEvent_t fx_ev[2] = {nullptr, nullptr};    // s2r_set_timing: around the reverb's kernels of the last bus fill
     float bus_fx_ms = -1.0f;                     // ... and the time between them (0 when the fill ran none; tools/reverb_time.py)
+    // The master section (s2r_fill_master).  Nothing is allocated before the first master fill, and a handle that
+    // never makes one passes the pointers and makes the launches it always did.
+    struct Master {
+        // s2r_set_bus_return / s2r_set_master_fader: what the caller last set — the target — and what the last master fill left — the applied
+        float ret[S2R_MAX_BUSES], ret_app[S2R_MAX_BUSES];
+        float fader = 1.0f, fader_app = 1.0f;
+        float *stage = nullptr;                  // [S2R_MAX_BUSES][2 * max_frames] in device memory: where the last stem writer of a master fill writes
+        float *partials = nullptr, *partials_dev = nullptr;      // pinned and device-mapped: [ceil(max_frames / S2R_METER_BLOCK)][S2R_MASTER_ROW]
+        bool metered = false;                    // a master fill has succeeded: the meters below are its
+        uint32_t meter_buses = 0;
+        float peak[S2R_MASTER_CH], energy[S2R_MASTER_CH];
+        hipEvent_t ev[2] = {nullptr, nullptr};   // s2r_set_timing: around the master kernel of the last master fill
+        float ms = -1.0f;                        // ... and the time between them (tools/master_time.py)
+        Master() { for (uint32_t b = 0; b < S2R_MAX_BUSES; b++) ret[b] = ret_app[b] = 1.0f; }
+    } master;
+    float *stem_out = nullptr;                   // where the last stem writer of the call under way writes: bus_out_dev, or master.stage
     float pitch_table[256];
     hipEvent_t t0 = nullptr, t1 = nullptr;
     bool timing = false, timed = false, no_flat_shortcut = false;
@@ -1914,7 +1930,7 @@ int fx_launch(s2r_synth *s, uint32_t n_buses, uint32_t frames) {
         d.n_taps = f.n_taps; d.n_seg = (f.n_taps + S2R_IR_SEGMENT - 1u) / S2R_IR_SEGMENT;
         d.tstride = f.tstride; d.lstride = f.lstride; d.dry = f.dry; d.wet = f.wet;
     }
-    fx.stage = s->fx_stage; fx.out = s->bus_out_dev; fx.n_buses = n_buses; fx.frames = frames; fx.pstride = fx_pstride(s);
+    fx.stage = s->fx_stage; fx.out = s->stem_out; fx.n_buses = n_buses; fx.frames = frames; fx.pstride = fx_pstride(s);
     if (s->timing) {
         for (hipEvent_t &e : s->fx_ev) if (!e) S2R_HIP(s, hipEventCreate(&e));
         S2R_HIP(s, hipEventRecord(s->fx_ev[0], s->stream));
@@ -1922,6 +1938,47 @@ int fx_launch(s2r_synth *s, uint32_t n_buses, uint32_t frames) {
     S2R_HIP(s, s2r_launch_bus_fx(fx, s->stream));
     if (s->timing) S2R_HIP(s, hipEventRecord(s->fx_ev[1], s->stream));
     return S2R_OK;
+}
+
+// The last stage of a master fill, behind the reverbs' kernels and in front of the call's synchronise: returns, master fader and
+// the meters' block partials.  `stems`: the caller wants them too.
+int master_launch(s2r_synth *s, uint32_t n_buses, uint32_t frames, bool stems) {
+    const s2r_synth::Master &ms = s->master;
+    S2rMaster m{};
+    m.stage = ms.stage; m.out = s->out_host_dev; m.stems = stems ? s->bus_out_dev : nullptr; m.partials = ms.partials_dev;
+    m.n_buses = n_buses; m.frames = frames;
+    const float fn = (float)frames;
+    for (uint32_t b = 0; b < n_buses; b++) {
+        const float d = ms.ret[b] - ms.ret_app[b];               // (+0.0 for a pair that did not move, and so is its step)
+        m.r0[b] = ms.ret_app[b]; m.dr[b] = d / fn;
+    }
+    const float d = ms.fader - ms.fader_app;
+    m.m0 = ms.fader_app; m.dm = d / fn;
+    if (s->timing) {
+        for (hipEvent_t &e : s->master.ev) if (!e) S2R_HIP(s, hipEventCreate(&e));
+        S2R_HIP(s, hipEventRecord(s->master.ev[0], s->stream));
+    }
+    S2R_HIP(s, s2r_launch_master(m, s->stream));
+    if (s->timing) S2R_HIP(s, hipEventRecord(s->master.ev[1], s->stream));
+    return S2R_OK;
+}
+
+// after the synchronise of a master fill that succeeded: the block partials in block order, and applied = target
+void master_commit(s2r_synth *s, uint32_t n_buses, uint32_t frames) {
+    s2r_synth::Master &ms = s->master;
+    const uint32_t n_ch = (n_buses + 1u) * 2u, n_blocks = (frames + S2R_METER_BLOCK - 1u) / S2R_METER_BLOCK;
+    for (uint32_t ch = 0; ch < n_ch; ch++) {
+        float peak = 0.0f, energy = 0.0f;
+        for (uint32_t k = 0; k < n_blocks; k++) {
+            const float *row = ms.partials + (size_t)k * S2R_MASTER_ROW;
+            peak = row[ch] > peak ? row[ch] : peak;
+            energy = energy + row[S2R_MASTER_CH + ch];
+        }
+        ms.peak[ch] = peak; ms.energy[ch] = energy;
+    }
+    ms.metered = true; ms.meter_buses = n_buses;
+    for (uint32_t b = 0; b < S2R_MAX_BUSES; b++) ms.ret_app[b] = ms.ret[b];
+    ms.fader_app = ms.fader;
 }
 
 void release_all(s2r_synth *s) {
@@ -1980,6 +2037,9 @@ void release_all(s2r_synth *s) {
     if (s->bus_out) (void)hipHostFree(s->bus_out);
     for (s2r_synth::BusFx &f : s->fx) fx_release(f);
     if (s->fx_stage) (void)hipFree(s->fx_stage);
+    if (s->master.stage) (void)hipFree(s->master.stage);
+    if (s->master.partials) (void)hipHostFree(s->master.partials);
+    for (hipEvent_t e : s->master.ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : s->fx_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : s->pan_ev) (void)hipEventDestroy(e);
     if (s->voice_ev_head) (void)hipFree(s->voice_ev_head);
@@ -2618,16 +2678,18 @@ int s2r_set_voice_pans(s2r_synth *s, const float *pans) {
     return S2R_OK;
 }
 
-// s2r_fill_panned (n_buses == 0: two channels into `out`) and s2r_fill_buses (n_buses stereo buses, bus-major, `capacity` floats)
-static int fill_rows_mixed(s2r_synth *s, float *out, size_t capacity, uint32_t n_buses, size_t frames, uint32_t sample_rate_hz, const char *who) {
+// s2r_fill_panned (n_buses == 0: two channels into `out`), s2r_fill_buses (n_buses stereo buses, bus-major, `capacity` floats) and
+// s2r_fill_master (`master`: the master section behind the buses, its two channels into `master_lr`; `out` — the stems — may be null)
+static int fill_rows_mixed(s2r_synth *s, float *out, size_t capacity, uint32_t n_buses, size_t frames, uint32_t sample_rate_hz, const char *who,
+                           bool master = false, float *master_lr = nullptr) {
     if (!s) return S2R_ERR_INVALID;
     if (!s->kids.empty() || s->parent) return set_err(s, S2R_ERR_INVALID, "%s takes a single-device handle, not a device list", who);
     if (s->xg_on) return set_err(s, S2R_ERR_INVALID, "%s takes a handle without an exchange attached", who);
     int rc = check_fill(s, frames, sample_rate_hz);
     if (rc != S2R_OK) return rc;
     if (frames == 0) return S2R_OK;
-    if (!out) return set_err(s, S2R_ERR_INVALID, "null output buffer");
-    if (n_buses && capacity < 2 * frames * n_buses)
+    if (master ? !master_lr : !out) return set_err(s, S2R_ERR_INVALID, "null output buffer");
+    if (n_buses && out && capacity < 2 * frames * n_buses)
         return set_err(s, S2R_ERR_INVALID, "%s: %u buses of %zu frames take %zu floats, the buffer holds %zu", who, n_buses, frames, 2 * frames * n_buses, capacity);
     if (s->ring_count) return set_err(s, S2R_ERR_INVALID, "%s with fills of s2r_fill_begin in flight: s2r_fill_end first", who);
     S2R_QUIESCE(s);
@@ -2647,14 +2709,24 @@ static int fill_rows_mixed(s2r_synth *s, float *out, size_t capacity, uint32_t n
     // the workgroups' partial rows of the mixdown asked for (and the bus fill's pinned output), once each
     if (!n_buses && !s->pan_partials) S2R_HIP(s, hipMalloc((void **)&s->pan_partials, (size_t)s->n_blocks * 2u * s->pan_slice * sizeof(float)));
     if (n_buses && !s->bus_partials) S2R_HIP(s, hipMalloc((void **)&s->bus_partials, (size_t)s->n_blocks * 2u * S2R_MAX_BUSES * s->pan_slice * sizeof(float)));
-    if (n_buses && !s->bus_out) {
+    if (n_buses && out && !s->bus_out) {
         S2R_HIP(s, hipHostMalloc((void **)&s->bus_out, (size_t)2 * S2R_MAX_BUSES * s->cfg.max_frames * sizeof(float), kHostPolled));
         S2R_HIP(s, hipHostGetDevicePointer((void **)&s->bus_out_dev, s->bus_out, 0));
     }
+    // (and the master fill's device copy of the stems and its pinned rows of block partials, once each: DESIGN.md 4.17)
+    if (master && !s->master.stage) S2R_HIP(s, hipMalloc((void **)&s->master.stage, (size_t)2 * S2R_MAX_BUSES * s->cfg.max_frames * sizeof(float)));
+    if (master && !s->master.partials_dev) {
+        const size_t rows = (s->cfg.max_frames + S2R_METER_BLOCK - 1u) / S2R_METER_BLOCK;
+        if (!s->master.partials) S2R_HIP(s, hipHostMalloc((void **)&s->master.partials, rows * S2R_MASTER_ROW * sizeof(float), kHostPolled));
+        S2R_HIP(s, hipHostGetDevicePointer((void **)&s->master.partials_dev, s->master.partials, 0));
+    }
     // a call with a reverb on one of its buses mixes into the staging buffer, and the reverbs' kernels write the caller-visible
     // output; without one the combine writes there itself, as it always did
+    // ... and in a master fill whichever of the two writes the stems last writes them into device memory, where the master kernel
+    // reads them: it must not read the pinned output back
     const bool fx_on = n_buses && fx_active(s, n_buses);
-    s->bus_mix_out = fx_on ? s->fx_stage : s->bus_out_dev;
+    s->stem_out = master ? s->master.stage : s->bus_out_dev;
+    s->bus_mix_out = fx_on ? s->fx_stage : s->stem_out;
     fold_frame0_records(s);
     mixer_settle(s);
     s->pan_ev_used = 0;
@@ -2702,11 +2774,17 @@ static int fill_rows_mixed(s2r_synth *s, float *out, size_t capacity, uint32_t n
         rc = fx_launch(s, n_buses, (uint32_t)frames);
         if (rc != S2R_OK) return rc;
     }
+    if (master) {
+        rc = master_launch(s, n_buses, (uint32_t)frames, out != nullptr);
+        if (rc != S2R_OK) return rc;
+    }
     S2R_HIP(s, hipStreamSynchronize(s->stream));
     if (fx_on) for (uint32_t b = 0; b < n_buses; b++) if (s->fx[b].n_taps) s->fx[b].cur ^= 1;     // the histories have moved on
     if (n_buses && (s->mixer.used & kMixFader)) snap_faders(s);  // the faders have arrived
-    if (n_buses) std::memcpy(out, s->bus_out, 2 * frames * n_buses * sizeof(float));
-    else std::memcpy(out, s->out_host, 2 * frames * sizeof(float));
+    if (master) master_commit(s, n_buses, (uint32_t)frames);     // ... and so have the returns and the master fader
+    if (n_buses && out) std::memcpy(out, s->bus_out, 2 * frames * n_buses * sizeof(float));
+    if (master) std::memcpy(master_lr, s->out_host, 2 * frames * sizeof(float));
+    else if (!n_buses) std::memcpy(out, s->out_host, 2 * frames * sizeof(float));
     if (s->timing) {
         float sum = 0.0f;
         for (size_t k = 0; k < s->pan_ev_used; k += 2) { float ms = 0.0f; S2R_HIP(s, hipEventElapsedTime(&ms, s->pan_ev[k], s->pan_ev[k + 1])); sum += ms; }
@@ -2715,6 +2793,7 @@ static int fill_rows_mixed(s2r_synth *s, float *out, size_t capacity, uint32_t n
             s->bus_fx_ms = 0.0f;
             if (fx_on) S2R_HIP(s, hipEventElapsedTime(&s->bus_fx_ms, s->fx_ev[0], s->fx_ev[1]));
         }
+        if (master) S2R_HIP(s, hipEventElapsedTime(&s->master.ms, s->master.ev[0], s->master.ev[1]));
     }
     return S2R_OK;
 }
@@ -3013,6 +3092,128 @@ int s2r_fill_buses(s2r_synth *s, float *out, size_t capacity, uint32_t n_buses, 
     if (!s) return S2R_ERR_INVALID;
     if (n_buses == 0 || n_buses > S2R_MAX_BUSES) return set_err(s, S2R_ERR_INVALID, "s2r_fill_buses: %u buses (1 .. %u)", n_buses, S2R_MAX_BUSES);
     return fill_rows_mixed(s, out, capacity, n_buses, frames, sample_rate_hz, "s2r_fill_buses");
+}
+
+// ---- the master section ----
+// The rule on the host: the ramps, the sum in bus order from +0.0, the master gain; peaks, and energies by the adjacent-pair tree over
+// blocks of S2R_METER_BLOCK frames, the blocks in order from +0.0.  Every product and every sum rounded on its own.
+static float master_energy(const float *v, uint32_t frames) {     // v: one channel of an interleaved pair (stride 2)
+    float total = 0.0f;
+    for (uint32_t k0 = 0; k0 < frames; k0 += S2R_METER_BLOCK) {
+        float sq[S2R_METER_BLOCK];
+        for (uint32_t j = 0; j < S2R_METER_BLOCK; j++) {
+            const float x = k0 + j < frames ? v[2 * (size_t)(k0 + j)] : 0.0f;
+            sq[j] = x * x;
+        }
+        for (uint32_t n = S2R_METER_BLOCK / 2u; n >= 1u; n /= 2u)
+            for (uint32_t j = 0; j < n; j++) sq[j] = sq[2 * j] + sq[2 * j + 1];
+        total = total + sq[0];
+    }
+    return total;
+}
+
+static float master_peak(const float *v, uint32_t frames) {
+    float peak = 0.0f;
+    for (uint32_t i = 0; i < frames; i++) { const float a = std::fabs(v[2 * (size_t)i]); peak = a > peak ? a : peak; }
+    return peak;
+}
+
+int s2r_master_reference(const float *stems, uint32_t n_buses, uint32_t frames, const float *r0, const float *r1, float m0, float m1,
+                         float *master_lr, float *peak, float *energy) {
+    if (!unit_in_range(m0) || !unit_in_range(m1)) return S2R_ERR_PATCH_RANGE;
+    if (n_buses == 0 || n_buses > S2R_MAX_BUSES || !r0 || !r1 || (!stems && frames)) return S2R_ERR_INVALID;
+    for (uint32_t b = 0; b < n_buses; b++) if (!unit_in_range(r0[b]) || !unit_in_range(r1[b])) return S2R_ERR_PATCH_RANGE;
+    const float fn = (float)frames;
+    float dr[S2R_MAX_BUSES];
+    for (uint32_t b = 0; b < n_buses; b++) { const float d = r1[b] - r0[b]; dr[b] = d / fn; }
+    const float dm0 = m1 - m0, dm = dm0 / fn;
+    std::vector<float> own;
+    if (!master_lr) { own.resize(2 * (size_t)frames); master_lr = own.data(); }
+    for (uint32_t i = 0; i < frames; i++) {
+        const float fi = (float)i;
+        for (uint32_t c = 0; c < 2; c++) {
+            float t = 0.0f;
+            for (uint32_t b = 0; b < n_buses; b++) {
+                const float step = fi * dr[b];
+                const float r = r0[b] + step;
+                const float p = r * stems[((size_t)b * frames + i) * 2 + c];
+                t = t + p;
+            }
+            const float step = fi * dm;
+            const float g = m0 + step;
+            master_lr[2 * (size_t)i + c] = g * t;
+        }
+    }
+    for (uint32_t b = 0; b <= n_buses; b++)
+        for (uint32_t c = 0; c < 2; c++) {
+            const float *v = (b < n_buses ? stems + (size_t)b * frames * 2 : master_lr) + c;
+            if (peak) peak[2 * b + c] = master_peak(v, frames);
+            if (energy) energy[2 * b + c] = master_energy(v, frames);
+        }
+    return S2R_OK;
+}
+
+static int master_handle(const s2r_synth *s, const char *who) {
+    if (!s) return S2R_ERR_INVALID;
+    if (!s->kids.empty() || s->parent) return set_err(const_cast<s2r_synth *>(s), S2R_ERR_INVALID, "%s: the master section is kept by single-device handles, not by a device list", who);
+    return S2R_OK;
+}
+
+int s2r_set_bus_return(s2r_synth *s, uint32_t bus, float level) {
+    // (the values first, like s2r_set_bus_reverb_mix)
+    if (!unit_in_range(level) || bus >= S2R_MAX_BUSES)
+        return set_err(s, S2R_ERR_PATCH_RANGE, "bus %u: return %g: the level lies in [0, 1], the bus below %u", bus, (double)level, S2R_MAX_BUSES);
+    const int rc = master_handle(s, "s2r_set_bus_return");
+    if (rc != S2R_OK) return rc;
+    s->master.ret[bus] = level;
+    return S2R_OK;
+}
+
+int s2r_get_bus_return(const s2r_synth *s, uint32_t bus, float *level, float *applied) {
+    if (bus >= S2R_MAX_BUSES) return S2R_ERR_PATCH_RANGE;
+    if (!s || !s->kids.empty() || s->parent) return S2R_ERR_INVALID;
+    if (level) *level = s->master.ret[bus];
+    if (applied) *applied = s->master.ret_app[bus];
+    return S2R_OK;
+}
+
+int s2r_set_master_fader(s2r_synth *s, float level) {
+    if (!unit_in_range(level)) return set_err(s, S2R_ERR_PATCH_RANGE, "master fader %g: the level lies in [0, 1]", (double)level);
+    const int rc = master_handle(s, "s2r_set_master_fader");
+    if (rc != S2R_OK) return rc;
+    s->master.fader = level;
+    return S2R_OK;
+}
+
+int s2r_get_master_fader(const s2r_synth *s, float *level, float *applied) {
+    if (!s || !s->kids.empty() || s->parent) return S2R_ERR_INVALID;
+    if (level) *level = s->master.fader;
+    if (applied) *applied = s->master.fader_app;
+    return S2R_OK;
+}
+
+int s2r_snap_master(s2r_synth *s) {
+    const int rc = master_handle(s, "s2r_snap_master");
+    if (rc != S2R_OK) return rc;
+    for (uint32_t b = 0; b < S2R_MAX_BUSES; b++) s->master.ret_app[b] = s->master.ret[b];
+    s->master.fader_app = s->master.fader;
+    return S2R_OK;
+}
+
+int s2r_fill_master(s2r_synth *s, float *master_lr, float *stems, size_t stems_capacity, uint32_t n_buses, size_t frames, uint32_t sample_rate_hz) {
+    if (!s) return S2R_ERR_INVALID;
+    if (n_buses == 0 || n_buses > S2R_MAX_BUSES) return set_err(s, S2R_ERR_INVALID, "s2r_fill_master: %u buses (1 .. %u)", n_buses, S2R_MAX_BUSES);
+    return fill_rows_mixed(s, stems, stems_capacity, n_buses, frames, sample_rate_hz, "s2r_fill_master", true, master_lr);
+}
+
+int s2r_get_meters(const s2r_synth *s, uint32_t *n_buses, float *peak, float *energy, size_t capacity) {
+    if (!s || !s->kids.empty() || s->parent || !s->master.metered) return S2R_ERR_INVALID;
+    const size_t n = ((size_t)s->master.meter_buses + 1u) * 2u;
+    if (capacity < n) return S2R_ERR_INVALID;
+    if (n_buses) *n_buses = s->master.meter_buses;
+    if (peak) std::memcpy(peak, s->master.peak, n * sizeof(float));
+    if (energy) std::memcpy(energy, s->master.energy, n * sizeof(float));
+    return S2R_OK;
 }
 
 int s2r_fill_oversampled(s2r_synth *s, float *mono_out, size_t frames, uint32_t sample_rate_hz) {
@@ -3452,6 +3653,8 @@ extern "C" uint32_t s2r_debug_pan_slice(const s2r_synth *s) { return s ? s->pan_
 extern "C" float s2r_debug_bus_mix_ms(const s2r_synth *s) { return s && s->timing ? s->bus_mix_ms : -1.0f; }
 // ... and of the buses' reverb kernels in that fill: 0 when it ran none (tools/reverb_time.py)
 extern "C" float s2r_debug_bus_fx_ms(const s2r_synth *s) { return s && s->timing ? s->bus_fx_ms : -1.0f; }
+// ... and of the master kernel in the last s2r_fill_master (tools/master_time.py)
+extern "C" float s2r_debug_master_ms(const s2r_synth *s) { return s && s->timing ? s->master.ms : -1.0f; }
 
 extern "C" uint32_t s2r_debug_read_stamps(s2r_synth *s, unsigned long long *out, uint32_t max_waves) {
 #if defined(S2R_STAMPS)

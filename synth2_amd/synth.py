@@ -36,6 +36,7 @@ S2R_ERR_OUT_OF_MEMORY = -8
 MAX_BUSES = 8                               # S2R_MAX_BUSES
 MAX_IR_TAPS = 65536                         # S2R_MAX_IR_TAPS
 IR_SEGMENT = 256                            # S2R_IR_SEGMENT
+METER_BLOCK = 256                           # S2R_METER_BLOCK
 
 
 class S2rError(RuntimeError):
@@ -195,6 +196,14 @@ def load_library():
         "s2r_get_bus_reverb_history": (C.c_int, [H, C.c_uint32, _f32p, C.c_size_t]),
         "s2r_set_bus_reverb_history": (C.c_int, [H, C.c_uint32, _f32p, C.c_size_t]),
         "s2r_reverb_reference": (C.c_int, [_f32p, C.c_uint32, _f32p, C.c_uint32, C.c_float, C.c_float, _f32p]),
+        "s2r_set_bus_return": (C.c_int, [H, C.c_uint32, C.c_float]),
+        "s2r_get_bus_return": (C.c_int, [H, C.c_uint32, _f32p, _f32p]),
+        "s2r_set_master_fader": (C.c_int, [H, C.c_float]),
+        "s2r_get_master_fader": (C.c_int, [H, _f32p, _f32p]),
+        "s2r_snap_master": (C.c_int, [H]),
+        "s2r_fill_master": (C.c_int, [H, _f32p, _f32p, C.c_size_t, C.c_uint32, C.c_size_t, C.c_uint32]),
+        "s2r_get_meters": (C.c_int, [H, C.POINTER(C.c_uint32), _f32p, _f32p, C.c_size_t]),
+        "s2r_master_reference": (C.c_int, [_f32p, C.c_uint32, C.c_uint32, _f32p, _f32p, C.c_float, C.c_float, _f32p, _f32p, _f32p]),
         "s2r_fill_device": (C.c_int, [H, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
         "s2r_fill_device_root": (C.c_int, [H, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
         "s2r_sum_partials_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_size_t, C.c_void_p, C.c_void_p]),
@@ -306,6 +315,26 @@ def reverb_reference(ir, x_with_history, frames, dry, wet):
     if rc != S2R_OK:
         raise S2rError(rc, load_library().s2r_status_string(rc).decode())
     return out
+
+
+def master_reference(stems, r0, r1, m0, m1):
+    """the master section's rule on the host (s2r_master_reference): stems [n_buses, frames, 2] float32, r0 / r1 [n_buses] the returns'
+    applied and target levels, m0 / m1 the master fader's; returns (master [frames, 2], peak [n_buses + 1, 2], energy [n_buses + 1, 2])"""
+    y = np.ascontiguousarray(stems, dtype=np.float32)
+    a = np.ascontiguousarray(r0, dtype=np.float32)
+    b = np.ascontiguousarray(r1, dtype=np.float32)
+    if y.ndim != 3 or y.shape[2] != 2 or a.shape != (y.shape[0],) or b.shape != (y.shape[0],):
+        raise ValueError("master_reference: stems is [n_buses, frames, 2], r0 and r1 are [n_buses]")
+    n_buses, frames = y.shape[0], y.shape[1]
+    out = np.empty((frames, 2), dtype=np.float32)
+    peak = np.empty((n_buses + 1, 2), dtype=np.float32)
+    energy = np.empty((n_buses + 1, 2), dtype=np.float32)
+    rc = load_library().s2r_master_reference(y.ctypes.data_as(_f32p), n_buses, frames, a.ctypes.data_as(_f32p), b.ctypes.data_as(_f32p),
+                                             float(m0), float(m1), out.ctypes.data_as(_f32p), peak.ctypes.data_as(_f32p),
+                                             energy.ctypes.data_as(_f32p))
+    if rc != S2R_OK:
+        raise S2rError(rc, load_library().s2r_status_string(rc).decode())
+    return out, peak, energy
 
 
 def stream_frame_json(samples):
@@ -642,6 +671,55 @@ class Synth:
     @staticmethod
     def reverb_reference(ir, x_with_history, frames, dry, wet):
         return reverb_reference(ir, x_with_history, frames, dry, wet)
+
+    # --- the master section (build-defined; s2r.h: s2r_fill_master) ---
+    def set_bus_return(self, bus, level=1.0):
+        """the target of a bus's return level (in [0, 1]): reached as a ramp across the next sample_master call.  Only sample_master
+        applies returns, the master fader and the meters."""
+        self._check(self.L.s2r_set_bus_return(self.h, int(bus), float(level)))
+
+    def get_bus_return(self, bus):
+        """(level, applied): the target, and where the last master fill left the return"""
+        t, a = C.c_float(), C.c_float()
+        self._check(self.L.s2r_get_bus_return(self.h, int(bus), C.byref(t), C.byref(a)))
+        return t.value, a.value
+
+    def set_master_fader(self, level=1.0):
+        self._check(self.L.s2r_set_master_fader(self.h, float(level)))
+
+    def get_master_fader(self):
+        """(level, applied)"""
+        t, a = C.c_float(), C.c_float()
+        self._check(self.L.s2r_get_master_fader(self.h, C.byref(t), C.byref(a)))
+        return t.value, a.value
+
+    def snap_master(self):
+        """applied = target for every return and the master fader, now (a hard cut; restoring a checkpoint: set the applied values,
+        snap, set the targets)"""
+        self._check(self.L.s2r_snap_master(self.h))
+
+    def sample_master(self, frames, sample_rate=SampleRateKhz(48000), n_buses=1, stems=True):
+        """sample_buses with the master section behind it: (master [frames, 2], stems [n_buses, frames, 2]), or (master, None) with
+        stems=False — the stems then never cross to the host"""
+        out = np.empty(2 * frames, dtype=np.float32)
+        st = np.empty(2 * frames * max(int(n_buses), 0), dtype=np.float32) if stems else None
+        self._check(self.L.s2r_fill_master(self.h, out.ctypes.data_as(_f32p), st.ctypes.data_as(_f32p) if stems else None,
+                                           st.size if stems else 0, int(n_buses), frames, int(sample_rate)))
+        return out.reshape(frames, 2), (st.reshape(n_buses, frames, 2) if stems else None)
+
+    def meters(self):
+        """(peak, energy) of the last successful sample_master call, each [n_buses + 1, 2] float32: the buses (post-effect,
+        pre-return), then the master"""
+        n = C.c_uint32()
+        peak = np.empty(2 * (MAX_BUSES + 1), dtype=np.float32)
+        energy = np.empty(2 * (MAX_BUSES + 1), dtype=np.float32)
+        self._check(self.L.s2r_get_meters(self.h, C.byref(n), peak.ctypes.data_as(_f32p), energy.ctypes.data_as(_f32p), peak.size))
+        k = 2 * (n.value + 1)
+        return peak[:k].reshape(-1, 2).copy(), energy[:k].reshape(-1, 2).copy()
+
+    @staticmethod
+    def master_reference(stems, r0, r1, m0, m1):
+        return master_reference(stems, r0, r1, m0, m1)
 
     def render_voices(self, frames, sample_rate=SampleRateKhz(48000)):
         """Mix disabled: (shard_voices, frames) float32."""
