@@ -155,6 +155,21 @@ class Synth {
         return s2r_master_reference(stems, n_buses, frames, r0, r1, m0, m1, master_lr, peak, energy);
     }
 
+    // the master limiter (build-defined; s2r.h: s2r_set_master_limiter): a look-ahead limiter behind the master fader, in sample_master
+    // only — no sample of master_lr exceeds `ceiling`, and master_lr is delayed by `lookahead` frames (the stems are not)
+    void set_master_limiter(float ceiling, uint32_t lookahead, uint32_t hold = 0) { check(s2r_set_master_limiter(h_, ceiling, lookahead, hold)); }
+    void clear_master_limiter() { check(s2r_clear_master_limiter(h_)); }
+    // a lookahead of 0 means off
+    void get_master_limiter(float *ceiling, uint32_t *lookahead, uint32_t *hold) const { check(s2r_get_master_limiter(h_, ceiling, lookahead, hold)); }
+    // xh: 2 * lookahead floats; gh: 2 * lookahead + hold floats (checkpoints)
+    void limiter_state(float *xh, size_t n_x, float *gh, size_t n_g) { check(s2r_get_limiter_state(h_, xh, n_x, gh, n_g)); }
+    void set_limiter_state(const float *xh, size_t n_x, const float *gh, size_t n_g) { check(s2r_set_limiter_state(h_, xh, n_x, gh, n_g)); }
+    void limiter_meters(float *min_gain, float *out_peak) const { check(s2r_get_limiter_meters(h_, min_gain, out_peak)); }
+    static int limiter_reference(const float *x, uint32_t frames, float ceiling, uint32_t lookahead, uint32_t hold, float *xh, float *gh,
+                                 float *y, float *gain) {
+        return s2r_limiter_reference(x, frames, ceiling, lookahead, hold, xh, gh, y, gain);
+    }
+
     s2r_synth *handle() { return h_; }
 
   private:

@@ -38,7 +38,8 @@ extern "C" {
  * s2r_get_program_send, s2r_get_voice_sends, s2r_set_voice_sends, s2r_send_gain, s2r_set_bus_reverb, s2r_set_bus_reverb_mix,
  * s2r_get_bus_reverb, s2r_get_bus_reverb_history, s2r_set_bus_reverb_history, s2r_reverb_reference, s2r_set_bus_return,
  * s2r_get_bus_return, s2r_set_master_fader, s2r_get_master_fader, s2r_snap_master, s2r_fill_master, s2r_get_meters,
- * s2r_master_reference. */
+ * s2r_master_reference, s2r_set_master_limiter, s2r_clear_master_limiter, s2r_get_master_limiter, s2r_get_limiter_state,
+ * s2r_set_limiter_state, s2r_get_limiter_meters, s2r_limiter_reference. */
 #define S2R_ABI_VERSION 4
 
 typedef enum {
@@ -425,6 +426,54 @@ int s2r_fill_master(s2r_synth *s, float *master_lr, float *stems, size_t stems_c
 int s2r_get_meters(const s2r_synth *s, uint32_t *n_buses, float *peak, float *energy, size_t capacity);
 int s2r_master_reference(const float *stems, uint32_t n_buses, uint32_t frames, const float *r0, const float *r1, float m0, float m1,
                          float *master_lr, float *peak, float *energy);
+
+/* BUILD-DEFINED master limiter (the reference has none; DESIGN.md 4.18 gives the op sequence): a look-ahead peak limiter behind the
+ * master fader, in s2r_fill_master only, on the device the master is already on.  Off by default, and a handle on which it was never
+ * set launches exactly what it launched before.  Parameters: `ceiling` C, finite, in [2^-S2R_LIMITER_CEILING_LOG2,
+ * 2^S2R_LIMITER_CEILING_LOG2]; `lookahead` L in frames, 1 .. S2R_LIMITER_MAX_LOOKAHEAD; `hold` H in frames, 0 .. S2R_LIMITER_MAX_HOLD;
+ * W = L + 1, G = 2 L + H.  STATE carried from call to call: xh, the last L stereo frames of the limiter's input, oldest first,
+ * initially +0.0; gh, the last G values of g, oldest first, initially 1.0.  A call of N frames, x[n] what s2r_fill_master writes to
+ * master_lr without a limiter (x[n], g[n] for n < 0 from xh, gh):
+ *   1. p[n] = max(|x_L[n]|, |x_R[n]|);  g[n] = p[n] > C ? C / p[n] : 1.0f           (one gain for both channels)
+ *   2. m[n] = min over k = 0 .. L + H of g[n - k], n in [-L, N)                      (any order: a minimum has one value)
+ *   3. acc[n] = (((+0.0 + m[n]) + m[n - 1]) + ...) + m[n - L], W terms, newest first; s[n] = acc[n] / (float)W
+ *   4. s'[n] = min(s[n], g[n - L])
+ *   5. y_c[n] = min(max(x_c[n - L] * s'[n], -C), C)
+ * binary32, every operation rounded on its own, no fma, denormals kept, the division correctly rounded.  The output is the input
+ * delayed by L frames — in every bit under a signal that never exceeds C — and no output sample exceeds C in magnitude; the gain
+ * reaches its minimum at the frame the peak comes out, stays for H frames more and recovers along a line of W frames.  After the call
+ * xh and gh are the last L and G entries of history followed by call (also when N is shorter than either).  Non-finite input is
+ * outside the contract.  THE STEMS ARE NOT DELAYED: with a limiter set the stems of a master fill lead its master by L frames.  The
+ * master section's meters keep their rule: the master entry of s2r_get_meters is over x, before the limiter.  The limiter's own meters
+ * of a call: min_gain = min_n s'[n], out_peak = max_n,c |y_c[n]|.  s2r_fill_buses and every other fill ignore the limiter;
+ * s2r_set_patch_bank, program changes and s2r_import_state leave it alone.  A refused or failed call leaves state and meters as they
+ * were.  Single-device handles (a device list refuses every entry); a handle with an exchange attached takes the setters and refuses
+ * the fill.  The first master fill that finds a limiter set allocates a device buffer of 2 * max_frames floats, the two copies of the
+ * state and a pinned pair of meter partials per 256 frames of max_frames.
+ *   s2r_set_master_limiter: S2R_ERR_PATCH_RANGE for a NaN or a ceiling outside its range, lookahead 0 or too long, hold too long
+ *   (checked before the handle is looked at; nothing is changed).  Resets xh and gh to their initial values when lookahead or hold
+ *   differ from the present ones or the limiter was off; a call that changes the ceiling alone keeps the state (gh holds gains, not
+ *   levels).  s2r_clear_master_limiter: off; the master fill returns what it returned before, with no delay.
+ *   s2r_get_master_limiter: any pointer may be NULL; a lookahead of 0 means off (ceiling and hold are then 0).
+ *   s2r_get_limiter_state / s2r_set_limiter_state (checkpoints): xh as 2 * L floats (frames, L then R), gh as G floats.  The setter
+ *   takes exactly n_x == 2 * L and n_g == G, the getter capacities of at least that many; S2R_ERR_INVALID otherwise, with the limiter
+ *   off or for a NULL buffer.
+ *   s2r_get_limiter_meters: of the last successful s2r_fill_master that ran the limiter; S2R_ERR_INVALID before any such fill; either
+ *   pointer may be NULL.
+ *   s2r_limiter_reference: the rule above on the host (no device, no handle): x [frames][2], xh [lookahead][2] and gh [G] updated in
+ *   place, y [frames][2] and gain [frames] (s') written; y and gain may be NULL, y may be x.  S2R_ERR_PATCH_RANGE as the setter's,
+ *   S2R_ERR_INVALID for a NULL x (with frames > 0), xh or gh. */
+#define S2R_LIMITER_MAX_LOOKAHEAD 1024u
+#define S2R_LIMITER_MAX_HOLD 4096u
+#define S2R_LIMITER_CEILING_LOG2 20
+int s2r_set_master_limiter(s2r_synth *s, float ceiling, uint32_t lookahead, uint32_t hold);
+int s2r_clear_master_limiter(s2r_synth *s);
+int s2r_get_master_limiter(const s2r_synth *s, float *ceiling, uint32_t *lookahead, uint32_t *hold);
+int s2r_get_limiter_state(s2r_synth *s, float *xh, size_t n_x, float *gh, size_t n_g);
+int s2r_set_limiter_state(s2r_synth *s, const float *xh, size_t n_x, const float *gh, size_t n_g);
+int s2r_get_limiter_meters(const s2r_synth *s, float *min_gain, float *out_peak);
+int s2r_limiter_reference(const float *x, uint32_t frames, float ceiling, uint32_t lookahead, uint32_t hold, float *xh, float *gh,
+                          float *y, float *gain);
 
 /* BUILD-DEFINED 4x oversampling (the reference has none; BASELINE config [4]): renders 4 * frames at
  * 4 * sample_rate_hz through the same path and decimates the mix by a 63-tap windowed sinc whose history

@@ -177,6 +177,14 @@ pub mod ffi {
         pub fn s2r_get_meters(s: *const S2rSynth, n_buses: *mut u32, peak: *mut f32, energy: *mut f32, capacity: usize) -> c_int;
         pub fn s2r_master_reference(stems: *const f32, n_buses: u32, frames: u32, r0: *const f32, r1: *const f32, m0: f32, m1: f32,
                                     master_lr: *mut f32, peak: *mut f32, energy: *mut f32) -> c_int;
+        pub fn s2r_set_master_limiter(s: *mut S2rSynth, ceiling: f32, lookahead: u32, hold: u32) -> c_int;
+        pub fn s2r_clear_master_limiter(s: *mut S2rSynth) -> c_int;
+        pub fn s2r_get_master_limiter(s: *const S2rSynth, ceiling: *mut f32, lookahead: *mut u32, hold: *mut u32) -> c_int;
+        pub fn s2r_get_limiter_state(s: *mut S2rSynth, xh: *mut f32, n_x: usize, gh: *mut f32, n_g: usize) -> c_int;
+        pub fn s2r_set_limiter_state(s: *mut S2rSynth, xh: *const f32, n_x: usize, gh: *const f32, n_g: usize) -> c_int;
+        pub fn s2r_get_limiter_meters(s: *const S2rSynth, min_gain: *mut f32, out_peak: *mut f32) -> c_int;
+        pub fn s2r_limiter_reference(x: *const f32, frames: u32, ceiling: f32, lookahead: u32, hold: u32, xh: *mut f32, gh: *mut f32,
+                                     y: *mut f32, gain: *mut f32) -> c_int;
         pub fn s2r_shard_voices(s: *const S2rSynth) -> u32;
         pub fn s2r_fill_device(s: *mut S2rSynth, dev_out: *mut f32, frames: usize, sample_rate_hz: u32,
                                hip_stream: *mut c_void) -> c_int;
@@ -214,6 +222,11 @@ pub const MAX_IR_TAPS: u32 = 65536;
 pub const IR_SEGMENT: u32 = 256;
 /// `S2R_METER_BLOCK`: the frames of one block of the meters' energy tree (part of the master section's rule).
 pub const METER_BLOCK: u32 = 256;
+/// `S2R_LIMITER_MAX_LOOKAHEAD`, `S2R_LIMITER_MAX_HOLD`: the master limiter's longest lookahead and hold in frames, and
+/// `S2R_LIMITER_CEILING_LOG2`: its ceiling lies in [2^-20, 2^20].
+pub const LIMITER_MAX_LOOKAHEAD: u32 = 1024;
+pub const LIMITER_MAX_HOLD: u32 = 4096;
+pub const LIMITER_CEILING_LOG2: i32 = 20;
 
 /// Host-only: the gain a note_on of `velocity` gives its voice under a program's level and velocity sensitivity — DESIGN.md 4.13.
 pub fn voice_gain(level: f32, velocity_sens: f32, velocity: f32) -> f32 {
@@ -252,6 +265,19 @@ pub fn master_reference(stems: &[f32], r0: &[f32], r1: &[f32], m0: f32, m1: f32)
                                   peak.as_mut_ptr(), energy.as_mut_ptr())
     };
     if rc == 0 { Ok((out, peak, energy)) } else { Err(rc) }
+}
+
+/// Host-only: the master limiter's rule (`s2r_limiter_reference`).  `x`: L, R pairs; `xh` (`2 * lookahead`
+/// floats) and `gh` (`2 * lookahead + hold` floats) are the state, updated in place; returns (y, gain) or the status.
+pub fn limiter_reference(x: &[f32], ceiling: f32, lookahead: u32, hold: u32, xh: &mut [f32], gh: &mut [f32]) -> Result<(Vec<f32>, Vec<f32>), i32> {
+    assert!(x.len() % 2 == 0 && xh.len() == 2 * lookahead as usize && gh.len() == 2 * lookahead as usize + hold as usize);
+    let frames = x.len() / 2;
+    let (mut y, mut gain) = (vec![0.0f32; 2 * frames], vec![0.0f32; frames]);
+    let rc = unsafe {
+        ffi::s2r_limiter_reference(x.as_ptr(), frames as u32, ceiling, lookahead, hold, xh.as_mut_ptr(), gh.as_mut_ptr(), y.as_mut_ptr(),
+                                   gain.as_mut_ptr())
+    };
+    if rc == 0 { Ok((y, gain)) } else { Err(rc) }
 }
 
 /// Host-only: the gain of a voice's aux send, `g * send` in one rounded multiply — DESIGN.md 4.15.
@@ -607,6 +633,42 @@ pub mod synth {
             peak.truncate(2 * (n as usize + 1));
             energy.truncate(2 * (n as usize + 1));
             (peak, energy)
+        }
+
+        /// Build-defined master limiter (`s2r_set_master_limiter`, include/s2r.h): a look-ahead limiter behind the master fader, in
+        /// `sample_master` only.  The master is delayed by `lookahead` frames; the stems are not.
+        pub fn set_master_limiter(&mut self, ceiling: f32, lookahead: u32, hold: u32) {
+            self.check(unsafe { ffi::s2r_set_master_limiter(self.handle, ceiling, lookahead, hold) });
+        }
+
+        pub fn clear_master_limiter(&mut self) {
+            self.check(unsafe { ffi::s2r_clear_master_limiter(self.handle) });
+        }
+
+        /// (ceiling, lookahead, hold); a lookahead of 0 means off.
+        pub fn get_master_limiter(&self) -> (f32, u32, u32) {
+            let (mut c, mut l, mut h) = (0.0f32, 0u32, 0u32);
+            self.check(unsafe { ffi::s2r_get_master_limiter(self.handle, &mut c, &mut l, &mut h) });
+            (c, l, h)
+        }
+
+        /// (xh, gh): the limiter's carried input (`2 * lookahead` floats) and gains (`2 * lookahead + hold`), oldest first.
+        pub fn limiter_state(&mut self) -> (Vec<f32>, Vec<f32>) {
+            let (_, l, h) = self.get_master_limiter();
+            let (mut xh, mut gh) = (vec![0.0f32; 2 * l as usize], vec![0.0f32; 2 * l as usize + h as usize]);
+            self.check(unsafe { ffi::s2r_get_limiter_state(self.handle, xh.as_mut_ptr(), xh.len(), gh.as_mut_ptr(), gh.len()) });
+            (xh, gh)
+        }
+
+        pub fn set_limiter_state(&mut self, xh: &[f32], gh: &[f32]) {
+            self.check(unsafe { ffi::s2r_set_limiter_state(self.handle, xh.as_ptr(), xh.len(), gh.as_ptr(), gh.len()) });
+        }
+
+        /// (min_gain, out_peak) of the last successful `sample_master` call that ran the limiter.
+        pub fn limiter_meters(&self) -> (f32, f32) {
+            let (mut g, mut p) = (0.0f32, 0.0f32);
+            self.check(unsafe { ffi::s2r_get_limiter_meters(self.handle, &mut g, &mut p) });
+            (g, p)
         }
 
         /// Every voice's send and send bus: checkpoint companions of `voice_mix`.

@@ -19,7 +19,7 @@ LIB = os.path.join(HERE, "libs2r.so")
 SOURCES = ["s2r_render_onepole_square.hip", "s2r_render_onepole_saw.hip", "s2r_render_onepole_triangle.hip",
            "s2r_render_onepole_sine.hip", "s2r_render_general_square.hip", "s2r_render_general_saw.hip",
            "s2r_render_general_triangle.hip", "s2r_render_general_sine.hip", "s2r_render_general_bank.hip",
-           "s2r_aux.hip", "s2r_fx.hip", "s2r_master.hip", "s2r_host.cpp", "s2r_patch.cpp", "s2r_stream.cpp"]
+           "s2r_aux.hip", "s2r_fx.hip", "s2r_master.hip", "s2r_limiter.hip", "s2r_host.cpp", "s2r_patch.cpp", "s2r_stream.cpp"]
 HEADERS = ["s2r_device.h", "s2r_math.h", "s2r_patch.h", "s2r_voices.h", "s2r_kern_common.h", "s2r_render_onepole.inc",
            "s2r_render_general.inc"]
 
@@ -61,6 +61,10 @@ FX_KERNELS = ("s2r_fx_stage_kernel", "s2r_fx_convolve_kernel", "s2r_fx_finish_ke
 # _check_master_no_scratch() fails the build if one of its four bus counts spilled.
 PER_FILE_FLAGS["s2r_master.hip"] = ["-Rpass-analysis=kernel-resource-usage"]
 MASTER_KERNEL = "s2r_master_kernel"
+# s2r_limiter.hip likewise: the limiter kernel's windows live in LDS and its running values in a handful of registers, and
+# _check_limiter_no_scratch() fails the build if it went to scratch or spilled.
+PER_FILE_FLAGS["s2r_limiter.hip"] = ["-Rpass-analysis=kernel-resource-usage"]
+LIMITER_KERNEL = "s2r_limiter_kernel"
 if os.environ.get("S2R_EXPERIMENT_BANK_FLAGS"):                 # (development: extra flags for the patch-bank translation unit)
     PER_FILE_FLAGS["s2r_render_general_bank.hip"] = PER_FILE_FLAGS["s2r_render_general_bank.hip"] + os.environ["S2R_EXPERIMENT_BANK_FLAGS"].split()
 
@@ -161,7 +165,8 @@ def _compile_one(args):
         with open(os.path.splitext(obj)[0] + ".resources.txt", "w") as f:
             for name, u in usage:
                 f.write("%s: %s\n" % (name, ", ".join("%s %s" % kv for kv in u.items())))
-        {"s2r_fx.hip": _check_fx_no_scratch, "s2r_master.hip": _check_master_no_scratch}.get(os.path.basename(src), _check_no_scratch)(usage)
+        {"s2r_fx.hip": _check_fx_no_scratch, "s2r_master.hip": _check_master_no_scratch,
+         "s2r_limiter.hip": _check_limiter_no_scratch}.get(os.path.basename(src), _check_no_scratch)(usage)
     else:
         subprocess.check_call(cmd)
     with open(obj + ".id", "w") as f:
@@ -217,6 +222,17 @@ def _check_master_no_scratch(usage):
                 raise RuntimeError("libs2r: %s uses scratch or spills (%r): its stems and meter values must stay in registers" % (name, u))
     if seen != 4:
         raise RuntimeError("libs2r: resource usage of %d master kernels reported, 4 expected (the bus counts 1, 2, 4 and 8)" % seen)
+
+
+def _check_limiter_no_scratch(usage):
+    seen = 0
+    for name, u in usage:
+        if LIMITER_KERNEL in name:
+            seen += 1
+            if u.get("ScratchSize [bytes/lane]") != "0" or u.get("VGPRs Spill") != "0" or u.get("SGPRs Spill") != "0":
+                raise RuntimeError("libs2r: %s uses scratch or spills (%r): its windows live in LDS, the rest in registers" % (name, u))
+    if seen != 1:
+        raise RuntimeError("libs2r: resource usage of %d limiter kernels reported, 1 expected" % seen)
 
 
 def check_m0_contract(lib=None, texts=None):

@@ -443,3 +443,18 @@ struct S2rMaster {
 };
 // s2r_master_kernel<NB> for the call's bus count (1, 2, 4 or 8 compiled in; a count between them runs the next form with guarded buses)
 hipError_t s2r_launch_master(const S2rMaster &m, hipStream_t stream);
+
+// The master limiter of s2r_fill_master: one launch behind the master kernel.  It reads the master from device memory
+// and the current copy of the state, writes the limited master to the pinned output, the call's meter partials and the OTHER copy
+// of the state; the host flips the copies after a synchronise that succeeded.
+#define S2R_LIMITER_BLOCK 256u                      // frames of one workgroup, one per thread
+struct S2rLimiter {
+    const float *x;               // [frames][2] in device memory: what the master kernel of the call wrote
+    float *out;                   // interleaved L, R: 2 * frames floats (mapped host memory)
+    const float *xh, *gh;         // the state the call starts from: [lookahead][2] and [2 * lookahead + hold]
+    float *xh_next, *gh_next;     // ... and the state it leaves (never the buffers above)
+    float *partials;              // [ceil(frames / S2R_LIMITER_BLOCK)][2] (mapped host memory): min s', max |y| of each workgroup
+    uint32_t frames, lookahead, hold;
+    float ceiling;
+};
+hipError_t s2r_launch_limiter(const S2rLimiter &a, hipStream_t stream);

@@ -344,6 +344,25 @@ struct s2r_synth {
         float ms = -1.0f;                        // ... and the time between them (tools/master_time.py)
         Master() { for (uint32_t b = 0; b < S2R_MAX_BUSES; b++) ret[b] = ret_app[b] = 1.0f; }
     } master;
+    // The master limiter (s2r_set_master_limiter).  Nothing is allocated before the first master fill that finds it
+    // set, and a handle on which it never was passes the pointers and makes the launches it always did.
+    struct Limiter {
+        float ceiling = 0.0f;
+        uint32_t lookahead = 0, hold = 0;        // lookahead 0: off
+        // The state — xh [lookahead][2], then gh [2 * lookahead + hold] — lives in `host` while host_valid (set, reset or restored
+        // since the last fill, or no fill yet) and in state[cur] on the device otherwise.  A fill uploads a valid host copy into
+        // state[cur], the kernel writes state[cur ^ 1], and the commit flips cur and drops the host copy.
+        std::vector<float> host;
+        bool host_valid = false;
+        float *state[2] = {nullptr, nullptr};    // device memory, each 2 * S2R_LIMITER_MAX_LOOKAHEAD + (2 * S2R_LIMITER_MAX_LOOKAHEAD + S2R_LIMITER_MAX_HOLD) floats
+        int cur = 0;
+        float *in = nullptr;                     // [2 * max_frames] in device memory: where the master kernel writes when the limiter is on
+        float *partials = nullptr, *partials_dev = nullptr;      // pinned and device-mapped: [ceil(max_frames / S2R_LIMITER_BLOCK)][2]
+        bool metered = false;                    // a master fill has run the limiter: the meters below are its
+        float min_gain = 1.0f, out_peak = 0.0f;
+        hipEvent_t ev[2] = {nullptr, nullptr};   // s2r_set_timing: around the limiter kernel of the last master fill
+        float ms = -1.0f;                        // ... and the time between them (0 when the fill ran none; tools/limiter_time.py)
+    } limiter;
     float *stem_out = nullptr;                   // where the last stem writer of the call under way writes: bus_out_dev, or master.stage
     float pitch_table[256];
     hipEvent_t t0 = nullptr, t1 = nullptr;
@@ -1942,10 +1961,10 @@ int fx_launch(s2r_synth *s, uint32_t n_buses, uint32_t frames) {
 
 // The last stage of a master fill, behind the reverbs' kernels and in front of the call's synchronise: returns, master fader and
 // the meters' block partials.  `stems`: the caller wants them too.
-int master_launch(s2r_synth *s, uint32_t n_buses, uint32_t frames, bool stems) {
+int master_launch(s2r_synth *s, uint32_t n_buses, uint32_t frames, bool stems, bool limited) {
     const s2r_synth::Master &ms = s->master;
     S2rMaster m{};
-    m.stage = ms.stage; m.out = s->out_host_dev; m.stems = stems ? s->bus_out_dev : nullptr; m.partials = ms.partials_dev;
+    m.stage = ms.stage; m.out = limited ? s->limiter.in : s->out_host_dev; m.stems = stems ? s->bus_out_dev : nullptr; m.partials = ms.partials_dev;
     m.n_buses = n_buses; m.frames = frames;
     const float fn = (float)frames;
     for (uint32_t b = 0; b < n_buses; b++) {
@@ -1979,6 +1998,55 @@ void master_commit(s2r_synth *s, uint32_t n_buses, uint32_t frames) {
     ms.metered = true; ms.meter_buses = n_buses;
     for (uint32_t b = 0; b < S2R_MAX_BUSES; b++) ms.ret_app[b] = ms.ret[b];
     ms.fader_app = ms.fader;
+}
+
+// ---- the master limiter ----
+constexpr size_t kLimXh = 2u * S2R_LIMITER_MAX_LOOKAHEAD, kLimState = kLimXh + 2u * S2R_LIMITER_MAX_LOOKAHEAD + S2R_LIMITER_MAX_HOLD;
+
+inline size_t limiter_gains(uint32_t lookahead, uint32_t hold) { return 2u * (size_t)lookahead + hold; }
+
+// the initial state: xh +0.0, gh 1.0
+void limiter_reset(s2r_synth::Limiter &lm) {
+    lm.host.assign(2u * (size_t)lm.lookahead, 0.0f);
+    lm.host.resize(lm.host.size() + limiter_gains(lm.lookahead, lm.hold), 1.0f);
+    lm.host_valid = true;
+}
+
+// The limiter of a master fill, behind the master kernel and in front of the call's synchronise: the master from limiter.in, the
+// limited master into the pinned output, the next state into the copy that is not the current one.
+int limiter_launch(s2r_synth *s, uint32_t frames) {
+    s2r_synth::Limiter &lm = s->limiter;
+    const size_t nx = 2u * (size_t)lm.lookahead, ng = limiter_gains(lm.lookahead, lm.hold);
+    float *cur = lm.state[lm.cur], *next = lm.state[lm.cur ^ 1];
+    if (lm.host_valid) {                                         // (stays valid until the commit: a failed call leaves the state where it was)
+        S2R_HIP(s, hipMemcpyAsync(cur, lm.host.data(), nx * sizeof(float), hipMemcpyHostToDevice, s->stream));
+        S2R_HIP(s, hipMemcpyAsync(cur + kLimXh, lm.host.data() + nx, ng * sizeof(float), hipMemcpyHostToDevice, s->stream));
+    }
+    S2rLimiter a{};
+    a.x = lm.in; a.out = s->out_host_dev; a.xh = cur; a.gh = cur + kLimXh; a.xh_next = next; a.gh_next = next + kLimXh;
+    a.partials = lm.partials_dev; a.frames = frames; a.lookahead = lm.lookahead; a.hold = lm.hold; a.ceiling = lm.ceiling;
+    if (s->timing) {
+        for (hipEvent_t &e : lm.ev) if (!e) S2R_HIP(s, hipEventCreate(&e));
+        S2R_HIP(s, hipEventRecord(lm.ev[0], s->stream));
+    }
+    S2R_HIP(s, s2r_launch_limiter(a, s->stream));
+    if (s->timing) S2R_HIP(s, hipEventRecord(lm.ev[1], s->stream));
+    return S2R_OK;
+}
+
+// after the synchronise of a master fill that succeeded: the state has moved on, and the workgroups' rows give the call's meters
+void limiter_commit(s2r_synth *s, uint32_t frames) {
+    s2r_synth::Limiter &lm = s->limiter;
+    lm.cur ^= 1;
+    lm.host_valid = false;
+    const uint32_t n_blocks = (frames + S2R_LIMITER_BLOCK - 1u) / S2R_LIMITER_BLOCK;
+    float mn = lm.partials[0], pk = lm.partials[1];
+    for (uint32_t k = 1; k < n_blocks; k++) {
+        const float *row = lm.partials + (size_t)k * 2u;
+        mn = row[0] < mn ? row[0] : mn;
+        pk = row[1] > pk ? row[1] : pk;
+    }
+    lm.min_gain = mn; lm.out_peak = pk; lm.metered = true;
 }
 
 void release_all(s2r_synth *s) {
@@ -2040,6 +2108,10 @@ void release_all(s2r_synth *s) {
     if (s->master.stage) (void)hipFree(s->master.stage);
     if (s->master.partials) (void)hipHostFree(s->master.partials);
     for (hipEvent_t e : s->master.ev) if (e) (void)hipEventDestroy(e);
+    for (float *p : s->limiter.state) if (p) (void)hipFree(p);
+    if (s->limiter.in) (void)hipFree(s->limiter.in);
+    if (s->limiter.partials) (void)hipHostFree(s->limiter.partials);
+    for (hipEvent_t e : s->limiter.ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : s->fx_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : s->pan_ev) (void)hipEventDestroy(e);
     if (s->voice_ev_head) (void)hipFree(s->voice_ev_head);
@@ -2720,6 +2792,19 @@ static int fill_rows_mixed(s2r_synth *s, float *out, size_t capacity, uint32_t n
         if (!s->master.partials) S2R_HIP(s, hipHostMalloc((void **)&s->master.partials, rows * S2R_MASTER_ROW * sizeof(float), kHostPolled));
         S2R_HIP(s, hipHostGetDevicePointer((void **)&s->master.partials_dev, s->master.partials, 0));
     }
+    // (and the limiter's input, the two copies of its state and its pinned rows of meter partials, once each, by the first master
+    // fill that finds a limiter set: DESIGN.md 4.18)
+    const bool limited = master && s->limiter.lookahead != 0;
+    if (limited) {
+        s2r_synth::Limiter &lm = s->limiter;
+        if (!lm.in) S2R_HIP(s, hipMalloc((void **)&lm.in, (size_t)2 * s->cfg.max_frames * sizeof(float)));
+        for (float *&p : lm.state) if (!p) S2R_HIP(s, hipMalloc((void **)&p, kLimState * sizeof(float)));
+        if (!lm.partials_dev) {
+            const size_t rows = (s->cfg.max_frames + S2R_LIMITER_BLOCK - 1u) / S2R_LIMITER_BLOCK;
+            if (!lm.partials) S2R_HIP(s, hipHostMalloc((void **)&lm.partials, rows * 2u * sizeof(float), kHostPolled));
+            S2R_HIP(s, hipHostGetDevicePointer((void **)&lm.partials_dev, lm.partials, 0));
+        }
+    }
     // a call with a reverb on one of its buses mixes into the staging buffer, and the reverbs' kernels write the caller-visible
     // output; without one the combine writes there itself, as it always did
     // ... and in a master fill whichever of the two writes the stems last writes them into device memory, where the master kernel
@@ -2775,13 +2860,18 @@ static int fill_rows_mixed(s2r_synth *s, float *out, size_t capacity, uint32_t n
         if (rc != S2R_OK) return rc;
     }
     if (master) {
-        rc = master_launch(s, n_buses, (uint32_t)frames, out != nullptr);
+        rc = master_launch(s, n_buses, (uint32_t)frames, out != nullptr, limited);
+        if (rc != S2R_OK) return rc;
+    }
+    if (limited) {                                               // behind the master kernel: it writes the pinned output in its place
+        rc = limiter_launch(s, (uint32_t)frames);
         if (rc != S2R_OK) return rc;
     }
     S2R_HIP(s, hipStreamSynchronize(s->stream));
     if (fx_on) for (uint32_t b = 0; b < n_buses; b++) if (s->fx[b].n_taps) s->fx[b].cur ^= 1;     // the histories have moved on
     if (n_buses && (s->mixer.used & kMixFader)) snap_faders(s);  // the faders have arrived
     if (master) master_commit(s, n_buses, (uint32_t)frames);     // ... and so have the returns and the master fader
+    if (limited) limiter_commit(s, (uint32_t)frames);            // ... and the limiter's state
     if (n_buses && out) std::memcpy(out, s->bus_out, 2 * frames * n_buses * sizeof(float));
     if (master) std::memcpy(master_lr, s->out_host, 2 * frames * sizeof(float));
     else if (!n_buses) std::memcpy(out, s->out_host, 2 * frames * sizeof(float));
@@ -2794,6 +2884,10 @@ static int fill_rows_mixed(s2r_synth *s, float *out, size_t capacity, uint32_t n
             if (fx_on) S2R_HIP(s, hipEventElapsedTime(&s->bus_fx_ms, s->fx_ev[0], s->fx_ev[1]));
         }
         if (master) S2R_HIP(s, hipEventElapsedTime(&s->master.ms, s->master.ev[0], s->master.ev[1]));
+        if (master) {
+            s->limiter.ms = 0.0f;
+            if (limited) S2R_HIP(s, hipEventElapsedTime(&s->limiter.ms, s->limiter.ev[0], s->limiter.ev[1]));
+        }
     }
     return S2R_OK;
 }
@@ -3213,6 +3307,141 @@ int s2r_get_meters(const s2r_synth *s, uint32_t *n_buses, float *peak, float *en
     if (n_buses) *n_buses = s->master.meter_buses;
     if (peak) std::memcpy(peak, s->master.peak, n * sizeof(float));
     if (energy) std::memcpy(energy, s->master.energy, n * sizeof(float));
+    return S2R_OK;
+}
+
+// ---- the master limiter ----
+static bool limiter_in_range(float ceiling, uint32_t lookahead, uint32_t hold) {
+    const float lo = std::ldexp(1.0f, -S2R_LIMITER_CEILING_LOG2), hi = std::ldexp(1.0f, S2R_LIMITER_CEILING_LOG2);
+    return ceiling >= lo && ceiling <= hi && lookahead >= 1u && lookahead <= S2R_LIMITER_MAX_LOOKAHEAD && hold <= S2R_LIMITER_MAX_HOLD;   // (a NaN fails both comparisons)
+}
+
+// The rule on the host, in plain loops: the gains, the minimum of every window, the sum newest first, the division, the two minima
+// and the clamp.  It shares S2R_LIMITER_MAX_LOOKAHEAD, S2R_LIMITER_MAX_HOLD and S2R_LIMITER_CEILING_LOG2 with the kernel, nothing else.
+int s2r_limiter_reference(const float *x, uint32_t frames, float ceiling, uint32_t lookahead, uint32_t hold, float *xh, float *gh,
+                          float *y, float *gain) {
+    if (!limiter_in_range(ceiling, lookahead, hold)) return S2R_ERR_PATCH_RANGE;
+    if ((!x && frames) || !xh || !gh) return S2R_ERR_INVALID;
+    const size_t L = lookahead, H = hold, G = 2 * L + H, N = frames;
+    const float c = ceiling, w = (float)(lookahead + 1u);
+    std::vector<float> ge(G + N), xe(2 * (L + N)), m(L + N);
+    std::memcpy(ge.data(), gh, G * sizeof(float));
+    std::memcpy(xe.data(), xh, 2 * L * sizeof(float));
+    if (N) std::memcpy(xe.data() + 2 * L, x, 2 * N * sizeof(float));
+    for (size_t n = 0; n < N; n++) {
+        const float al = std::fabs(x[2 * n]), ar = std::fabs(x[2 * n + 1]);
+        const float p = al > ar ? al : ar;
+        ge[G + n] = p > c ? c / p : 1.0f;
+    }
+    for (size_t j = 0; j < L + N; j++) {                         // m[j] is m[n = j - L]: the minimum of g[n - L - H .. n], ge[j .. j + L + H]
+        float v = ge[j];
+        for (size_t k = 1; k <= L + H; k++) v = ge[j + k] < v ? ge[j + k] : v;
+        m[j] = v;
+    }
+    for (size_t n = 0; n < N; n++) {
+        float acc = 0.0f;
+        for (size_t k = 0; k <= L; k++) acc = acc + m[n + L - k];
+        const float s = acc / w, gd = ge[G - L + n];
+        const float sp = s < gd ? s : gd;
+        if (gain) gain[n] = sp;
+        if (y)
+            for (size_t ch = 0; ch < 2; ch++) {
+                float v = xe[2 * n + ch] * sp;
+                v = v < -c ? -c : v;
+                y[2 * n + ch] = v > c ? c : v;
+            }
+    }
+    std::memcpy(gh, ge.data() + N, G * sizeof(float));
+    std::memcpy(xh, xe.data() + 2 * N, 2 * L * sizeof(float));
+    return S2R_OK;
+}
+
+static int limiter_handle(const s2r_synth *s, const char *who) {
+    if (!s) return S2R_ERR_INVALID;
+    if (!s->kids.empty() || s->parent) return set_err(const_cast<s2r_synth *>(s), S2R_ERR_INVALID, "%s: the master limiter is kept by single-device handles, not by a device list", who);
+    return S2R_OK;
+}
+
+int s2r_set_master_limiter(s2r_synth *s, float ceiling, uint32_t lookahead, uint32_t hold) {
+    // (the values first, like s2r_set_bus_return)
+    if (!limiter_in_range(ceiling, lookahead, hold))
+        return set_err(s, S2R_ERR_PATCH_RANGE, "master limiter: ceiling %g, lookahead %u, hold %u: the ceiling lies in [2^-%d, 2^%d], the lookahead in 1 .. %u, the hold in 0 .. %u",
+                       (double)ceiling, lookahead, hold, S2R_LIMITER_CEILING_LOG2, S2R_LIMITER_CEILING_LOG2, S2R_LIMITER_MAX_LOOKAHEAD, S2R_LIMITER_MAX_HOLD);
+    const int rc = limiter_handle(s, "s2r_set_master_limiter");
+    if (rc != S2R_OK) return rc;
+    s2r_synth::Limiter &lm = s->limiter;
+    const bool reset = lm.lookahead != lookahead || lm.hold != hold;     // (off is a lookahead of 0: it differs)
+    lm.ceiling = ceiling; lm.lookahead = lookahead; lm.hold = hold;
+    if (reset) limiter_reset(lm);
+    return S2R_OK;
+}
+
+int s2r_clear_master_limiter(s2r_synth *s) {
+    const int rc = limiter_handle(s, "s2r_clear_master_limiter");
+    if (rc != S2R_OK) return rc;
+    s2r_synth::Limiter &lm = s->limiter;
+    lm.ceiling = 0.0f; lm.lookahead = 0; lm.hold = 0;
+    lm.host.clear(); lm.host_valid = false;
+    return S2R_OK;
+}
+
+int s2r_get_master_limiter(const s2r_synth *s, float *ceiling, uint32_t *lookahead, uint32_t *hold) {
+    if (!s || !s->kids.empty() || s->parent) return S2R_ERR_INVALID;
+    if (ceiling) *ceiling = s->limiter.ceiling;
+    if (lookahead) *lookahead = s->limiter.lookahead;
+    if (hold) *hold = s->limiter.hold;
+    return S2R_OK;
+}
+
+static int limiter_state(s2r_synth *s, float *get_x, float *get_g, const float *set_x, const float *set_g, size_t n_x, size_t n_g, const char *who) {
+    const int rc = limiter_handle(s, who);
+    if (rc != S2R_OK) return rc;
+    s2r_synth::Limiter &lm = s->limiter;
+    if (!lm.lookahead) return set_err(s, S2R_ERR_INVALID, "%s: no master limiter is set", who);
+    const size_t nx = 2u * (size_t)lm.lookahead, ng = limiter_gains(lm.lookahead, lm.hold);
+    const bool set = set_x || set_g;
+    if (set ? (n_x != nx || n_g != ng) : (n_x < nx || n_g < ng))
+        return set_err(s, S2R_ERR_INVALID, "%s: the state is %zu and %zu floats, not %zu and %zu", who, nx, ng, n_x, n_g);
+    if (set ? (!set_x || !set_g) : (!get_x || !get_g)) return set_err(s, S2R_ERR_INVALID, "%s: null buffer", who);
+    if (set) {
+        for (size_t i = 0; i < ng; i++)
+            if (!(set_g[i] >= 0.0f && set_g[i] <= 1.0f)) return set_err(s, S2R_ERR_PATCH_RANGE, "%s: gain %zu is %g, outside [0, 1]", who, i, (double)set_g[i]);
+        lm.host.assign(set_x, set_x + nx);
+        lm.host.insert(lm.host.end(), set_g, set_g + ng);
+        lm.host_valid = true;
+        return S2R_OK;
+    }
+    if (!lm.host_valid) {                                        // the device holds it: fetch it once, and keep it until the next fill
+        if (s->ring_count) return set_err(s, S2R_ERR_INVALID, "%s with fills of s2r_fill_begin in flight: s2r_fill_end first", who);
+        S2R_QUIESCE(s);
+        S2R_HIP(s, hipSetDevice(s->device));
+        std::vector<float> st(nx + ng);
+        const float *cur = lm.state[lm.cur];
+        S2R_HIP(s, hipMemcpyAsync(st.data(), cur, nx * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+        S2R_HIP(s, hipMemcpyAsync(st.data() + nx, cur + kLimXh, ng * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+        S2R_HIP(s, hipStreamSynchronize(s->stream));
+        lm.host.swap(st);
+        lm.host_valid = true;
+    }
+    std::memcpy(get_x, lm.host.data(), nx * sizeof(float));
+    std::memcpy(get_g, lm.host.data() + nx, ng * sizeof(float));
+    return S2R_OK;
+}
+
+int s2r_get_limiter_state(s2r_synth *s, float *xh, size_t n_x, float *gh, size_t n_g) {
+    return limiter_state(s, xh, gh, nullptr, nullptr, n_x, n_g, "s2r_get_limiter_state");
+}
+
+int s2r_set_limiter_state(s2r_synth *s, const float *xh, size_t n_x, const float *gh, size_t n_g) {
+    if (!s) return S2R_ERR_INVALID;
+    if (!xh || !gh) return set_err(s, S2R_ERR_INVALID, "s2r_set_limiter_state: null buffer");
+    return limiter_state(s, nullptr, nullptr, xh, gh, n_x, n_g, "s2r_set_limiter_state");
+}
+
+int s2r_get_limiter_meters(const s2r_synth *s, float *min_gain, float *out_peak) {
+    if (!s || !s->kids.empty() || s->parent || !s->limiter.metered) return S2R_ERR_INVALID;
+    if (min_gain) *min_gain = s->limiter.min_gain;
+    if (out_peak) *out_peak = s->limiter.out_peak;
     return S2R_OK;
 }
 
@@ -3655,6 +3884,8 @@ extern "C" float s2r_debug_bus_mix_ms(const s2r_synth *s) { return s && s->timin
 extern "C" float s2r_debug_bus_fx_ms(const s2r_synth *s) { return s && s->timing ? s->bus_fx_ms : -1.0f; }
 // ... and of the master kernel in the last s2r_fill_master (tools/master_time.py)
 extern "C" float s2r_debug_master_ms(const s2r_synth *s) { return s && s->timing ? s->master.ms : -1.0f; }
+// ... and of the limiter kernel in that fill: 0 when it ran none (tools/limiter_time.py)
+extern "C" float s2r_debug_limiter_ms(const s2r_synth *s) { return s && s->timing ? s->limiter.ms : -1.0f; }
 
 extern "C" uint32_t s2r_debug_read_stamps(s2r_synth *s, unsigned long long *out, uint32_t max_waves) {
 #if defined(S2R_STAMPS)

@@ -37,6 +37,9 @@ MAX_BUSES = 8                               # S2R_MAX_BUSES
 MAX_IR_TAPS = 65536                         # S2R_MAX_IR_TAPS
 IR_SEGMENT = 256                            # S2R_IR_SEGMENT
 METER_BLOCK = 256                           # S2R_METER_BLOCK
+LIMITER_MAX_LOOKAHEAD = 1024                # S2R_LIMITER_MAX_LOOKAHEAD
+LIMITER_MAX_HOLD = 4096                     # S2R_LIMITER_MAX_HOLD
+LIMITER_CEILING_LOG2 = 20                   # S2R_LIMITER_CEILING_LOG2
 
 
 class S2rError(RuntimeError):
@@ -204,6 +207,13 @@ def load_library():
         "s2r_fill_master": (C.c_int, [H, _f32p, _f32p, C.c_size_t, C.c_uint32, C.c_size_t, C.c_uint32]),
         "s2r_get_meters": (C.c_int, [H, C.POINTER(C.c_uint32), _f32p, _f32p, C.c_size_t]),
         "s2r_master_reference": (C.c_int, [_f32p, C.c_uint32, C.c_uint32, _f32p, _f32p, C.c_float, C.c_float, _f32p, _f32p, _f32p]),
+        "s2r_set_master_limiter": (C.c_int, [H, C.c_float, C.c_uint32, C.c_uint32]),
+        "s2r_clear_master_limiter": (C.c_int, [H]),
+        "s2r_get_master_limiter": (C.c_int, [H, _f32p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+        "s2r_get_limiter_state": (C.c_int, [H, _f32p, C.c_size_t, _f32p, C.c_size_t]),
+        "s2r_set_limiter_state": (C.c_int, [H, _f32p, C.c_size_t, _f32p, C.c_size_t]),
+        "s2r_get_limiter_meters": (C.c_int, [H, _f32p, _f32p]),
+        "s2r_limiter_reference": (C.c_int, [_f32p, C.c_uint32, C.c_float, C.c_uint32, C.c_uint32, _f32p, _f32p, _f32p, _f32p]),
         "s2r_fill_device": (C.c_int, [H, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
         "s2r_fill_device_root": (C.c_int, [H, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
         "s2r_sum_partials_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_size_t, C.c_void_p, C.c_void_p]),
@@ -335,6 +345,28 @@ def master_reference(stems, r0, r1, m0, m1):
     if rc != S2R_OK:
         raise S2rError(rc, load_library().s2r_status_string(rc).decode())
     return out, peak, energy
+
+
+def limiter_reference(x, ceiling, lookahead, hold, xh=None, gh=None):
+    """the master limiter's rule on the host (s2r_limiter_reference): x [frames, 2] float32; xh [lookahead, 2] and gh
+    [2 * lookahead + hold] the state the call starts from (None: the initial state).  Returns (y [frames, 2], gain [frames], xh, gh)
+    with the state the call leaves; the arguments are not modified."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    L, Hd = int(lookahead), int(hold)
+    if x.ndim != 2 or x.shape[1] != 2:
+        raise ValueError("limiter_reference: x is [frames, 2]")
+    xh = np.zeros((max(L, 0), 2), dtype=np.float32) if xh is None else np.array(xh, dtype=np.float32, order="C")
+    gh = np.ones(max(2 * L + Hd, 0), dtype=np.float32) if gh is None else np.array(gh, dtype=np.float32, order="C")
+    if 0 < L <= LIMITER_MAX_LOOKAHEAD and 0 <= Hd <= LIMITER_MAX_HOLD and (xh.shape != (L, 2) or gh.shape != (2 * L + Hd,)):
+        raise ValueError("limiter_reference: xh is [lookahead, 2], gh is [2 * lookahead + hold]")
+    frames = x.shape[0]
+    y = np.empty((frames, 2), dtype=np.float32)
+    gain = np.empty(frames, dtype=np.float32)
+    rc = load_library().s2r_limiter_reference(x.ctypes.data_as(_f32p), frames, float(ceiling), max(L, 0), max(Hd, 0), xh.ctypes.data_as(_f32p),
+                                              gh.ctypes.data_as(_f32p), y.ctypes.data_as(_f32p), gain.ctypes.data_as(_f32p))
+    if rc != S2R_OK:
+        raise S2rError(rc, load_library().s2r_status_string(rc).decode())
+    return y, gain, xh, gh
 
 
 def stream_frame_json(samples):
@@ -720,6 +752,44 @@ class Synth:
     @staticmethod
     def master_reference(stems, r0, r1, m0, m1):
         return master_reference(stems, r0, r1, m0, m1)
+
+    # --- the master limiter (build-defined; s2r.h: s2r_set_master_limiter) ---
+    def set_master_limiter(self, ceiling, lookahead, hold=0):
+        """a look-ahead limiter behind the master fader, in sample_master only: no sample of the master exceeds `ceiling`, and the
+        master is delayed by `lookahead` frames (the stems are not).  A new lookahead or hold resets the state; a new ceiling alone
+        keeps it."""
+        self._check(self.L.s2r_set_master_limiter(self.h, float(ceiling), int(lookahead), int(hold)))
+
+    def clear_master_limiter(self):
+        self._check(self.L.s2r_clear_master_limiter(self.h))
+
+    def get_master_limiter(self):
+        """(ceiling, lookahead, hold); a lookahead of 0 means off"""
+        c, l, h = C.c_float(), C.c_uint32(), C.c_uint32()
+        self._check(self.L.s2r_get_master_limiter(self.h, C.byref(c), C.byref(l), C.byref(h)))
+        return c.value, l.value, h.value
+
+    def limiter_state(self):
+        """(xh [lookahead, 2], gh [2 * lookahead + hold]): the limiter's carried input frames and gains, oldest first (checkpoints)"""
+        _, l, h = self.get_master_limiter()
+        xh, gh = np.empty((l, 2), dtype=np.float32), np.empty(2 * l + h, dtype=np.float32)
+        self._check(self.L.s2r_get_limiter_state(self.h, xh.ctypes.data_as(_f32p), xh.size, gh.ctypes.data_as(_f32p), gh.size))
+        return xh, gh
+
+    def set_limiter_state(self, xh, gh):
+        xh = np.ascontiguousarray(xh, dtype=np.float32)
+        gh = np.ascontiguousarray(gh, dtype=np.float32)
+        self._check(self.L.s2r_set_limiter_state(self.h, xh.ctypes.data_as(_f32p), xh.size, gh.ctypes.data_as(_f32p), gh.size))
+
+    def limiter_meters(self):
+        """(min_gain, out_peak) of the last successful sample_master call that ran the limiter"""
+        g, p = C.c_float(), C.c_float()
+        self._check(self.L.s2r_get_limiter_meters(self.h, C.byref(g), C.byref(p)))
+        return g.value, p.value
+
+    @staticmethod
+    def limiter_reference(x, ceiling, lookahead, hold, xh=None, gh=None):
+        return limiter_reference(x, ceiling, lookahead, hold, xh, gh)
 
     def render_voices(self, frames, sample_rate=SampleRateKhz(48000)):
         """Mix disabled: (shard_voices, frames) float32."""
