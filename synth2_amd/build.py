@@ -19,9 +19,10 @@ LIB = os.path.join(HERE, "libs2r.so")
 SOURCES = ["s2r_render_onepole_square.hip", "s2r_render_onepole_saw.hip", "s2r_render_onepole_triangle.hip",
            "s2r_render_onepole_sine.hip", "s2r_render_general_square.hip", "s2r_render_general_saw.hip",
            "s2r_render_general_triangle.hip", "s2r_render_general_sine.hip", "s2r_render_general_bank.hip",
-           "s2r_aux.hip", "s2r_fx.hip", "s2r_master.hip", "s2r_limiter.hip", "s2r_host.cpp", "s2r_patch.cpp", "s2r_stream.cpp"]
+           "s2r_aux.hip", "s2r_fx.hip", "s2r_master.hip", "s2r_limiter.hip", "s2r_host.cpp", "s2r_post.cpp", "s2r_rules.cpp", "s2r_patch.cpp",
+           "s2r_stream.cpp"]
 HEADERS = ["s2r_device.h", "s2r_math.h", "s2r_patch.h", "s2r_voices.h", "s2r_kern_common.h", "s2r_render_onepole.inc",
-           "s2r_render_general.inc"]
+           "s2r_render_general.inc", "s2r_post.h", "s2r_rules.h"]
 
 # -amdgpu-sched-strategy=max-ilp: the render kernels run one wavefront per SIMD (64 k voices =
 # 1024 waves), so nothing hides a dependent instruction's latency except independent work of the
@@ -49,22 +50,28 @@ PER_FILE_FLAGS = {}
 for _f in ("s2r_render_general_square.hip", "s2r_render_general_saw.hip", "s2r_render_general_triangle.hip", "s2r_render_general_sine.hip",
            "s2r_render_general_bank.hip"):
     PER_FILE_FLAGS[_f] = ["-ftrivial-auto-var-init=zero"]
-# s2r_aux.hip is compiled with the back end's resource-usage remarks: the bus mixdown keeps up to sixteen sums per frame in
-# registers by compiling the bus count in, and _check_no_scratch() fails the build if an instantiation went to scratch.
-PER_FILE_FLAGS["s2r_aux.hip"] = ["-Rpass-analysis=kernel-resource-usage"]
-NO_SCRATCH_KERNELS = ("s2r_bus_mix_kernel", "s2r_bus_combine_kernel")
-# s2r_fx.hip likewise: the convolution reverb's convolve kernel slides two windows of samples through registers, fully unrolled, and
-# _check_fx_no_scratch() fails the build if it or its two companions spilled.
-PER_FILE_FLAGS["s2r_fx.hip"] = ["-Rpass-analysis=kernel-resource-usage"]
-FX_KERNELS = ("s2r_fx_stage_kernel", "s2r_fx_convolve_kernel", "s2r_fx_finish_kernel")
-# s2r_master.hip likewise: the master kernel holds up to sixteen stem samples and eighteen meter values per thread, and
-# _check_master_no_scratch() fails the build if one of its four bus counts spilled.
-PER_FILE_FLAGS["s2r_master.hip"] = ["-Rpass-analysis=kernel-resource-usage"]
-MASTER_KERNEL = "s2r_master_kernel"
-# s2r_limiter.hip likewise: the limiter kernel's windows live in LDS and its running values in a handful of registers, and
-# _check_limiter_no_scratch() fails the build if it went to scratch or spilled.
-PER_FILE_FLAGS["s2r_limiter.hip"] = ["-Rpass-analysis=kernel-resource-usage"]
-LIMITER_KERNEL = "s2r_limiter_kernel"
+# Four translation units are compiled with the back end's resource-usage remarks, and _check_resources() fails the build when a
+# kernel named here went to scratch or spilled, or when fewer kernels report than the file instantiates.  Per source file: the
+# substrings that name its checked kernels; how many reports are expected — ("at least", n), ("exactly", n), or ("each", None):
+# one or more of every name — and why so many; the figures that must be "0"; and what the kernels keep where it belongs.  (The
+# bus mixdown's widest forms spill a few SGPRs, which costs nothing that was measured: s2r_aux.hip has no SGPR condition.)
+_SCRATCH, _VSPILL, _SSPILL = "ScratchSize [bytes/lane]", "VGPRs Spill", "SGPRs Spill"
+RESOURCE_CHECKS = {
+    # up to sixteen sums per frame in registers, the bus count compiled in
+    "s2r_aux.hip": (("s2r_bus_mix_kernel", "s2r_bus_combine_kernel"),
+                    ("at least", 33), "2 load widths x 4 bus counts, static and ramped, without and with aux sends, and the combine",
+                    (_SCRATCH, _VSPILL), "its sums must stay in registers"),
+    # the convolve kernel slides two windows of samples through registers, fully unrolled
+    "s2r_fx.hip": (("s2r_fx_stage_kernel", "s2r_fx_convolve_kernel", "s2r_fx_finish_kernel"), ("each", None), "the reverb's three kernels",
+                   (_SCRATCH, _VSPILL, _SSPILL), "its windows and sums must stay in registers"),
+    # up to sixteen stem samples and eighteen meter values per thread
+    "s2r_master.hip": (("s2r_master_kernel",), ("exactly", 4), "the bus counts 1, 2, 4 and 8",
+                       (_SCRATCH, _VSPILL, _SSPILL), "its stems and meter values must stay in registers"),
+    "s2r_limiter.hip": (("s2r_limiter_kernel",), ("exactly", 1), "one kernel",
+                        (_SCRATCH, _VSPILL, _SSPILL), "its windows live in LDS, the rest in registers"),
+}
+for _f in RESOURCE_CHECKS:
+    PER_FILE_FLAGS[_f] = ["-Rpass-analysis=kernel-resource-usage"]
 if os.environ.get("S2R_EXPERIMENT_BANK_FLAGS"):                 # (development: extra flags for the patch-bank translation unit)
     PER_FILE_FLAGS["s2r_render_general_bank.hip"] = PER_FILE_FLAGS["s2r_render_general_bank.hip"] + os.environ["S2R_EXPERIMENT_BANK_FLAGS"].split()
 
@@ -165,8 +172,7 @@ def _compile_one(args):
         with open(os.path.splitext(obj)[0] + ".resources.txt", "w") as f:
             for name, u in usage:
                 f.write("%s: %s\n" % (name, ", ".join("%s %s" % kv for kv in u.items())))
-        {"s2r_fx.hip": _check_fx_no_scratch, "s2r_master.hip": _check_master_no_scratch,
-         "s2r_limiter.hip": _check_limiter_no_scratch}.get(os.path.basename(src), _check_no_scratch)(usage)
+        _check_resources(os.path.basename(src), usage)
     else:
         subprocess.check_call(cmd)
     with open(obj + ".id", "w") as f:
@@ -189,50 +195,25 @@ def kernel_resources(remarks):
     return out
 
 
-def _check_no_scratch(usage):
-    seen = 0
+def _check_resources(source, usage):
+    if source not in RESOURCE_CHECKS:
+        raise RuntimeError("libs2r: %s is compiled with the resource-usage remarks and has no entry in RESOURCE_CHECKS" % source)
+    names, (rule, count), why_count, zero, why = RESOURCE_CHECKS[source]
+    seen = []
     for name, u in usage:
-        if any(k in name for k in NO_SCRATCH_KERNELS):
-            seen += 1
-            if u.get("ScratchSize [bytes/lane]") != "0" or u.get("VGPRs Spill") != "0":
-                raise RuntimeError("libs2r: %s uses scratch (%r): its sums must stay in registers" % (name, u))
-    if seen < 33:
-        raise RuntimeError("libs2r: resource usage of %d bus-mix kernels reported, 33 expected (2 load widths x 4 bus counts, static and ramped, "
-                           "without and with aux sends, and the combine)" % seen)
-
-
-def _check_fx_no_scratch(usage):
-    seen = set()
-    for name, u in usage:
-        for k in FX_KERNELS:
+        for k in names:
             if k in name:
-                seen.add(k)
-                if u.get("ScratchSize [bytes/lane]") != "0" or u.get("VGPRs Spill") != "0" or u.get("SGPRs Spill") != "0":
-                    raise RuntimeError("libs2r: %s uses scratch or spills (%r): its windows and sums must stay in registers" % (name, u))
-    if len(seen) != len(FX_KERNELS):
-        raise RuntimeError("libs2r: resource usage of the reverb kernels %s reported, %s expected" % (sorted(seen), list(FX_KERNELS)))
-
-
-def _check_master_no_scratch(usage):
-    seen = 0
-    for name, u in usage:
-        if MASTER_KERNEL in name:
-            seen += 1
-            if u.get("ScratchSize [bytes/lane]") != "0" or u.get("VGPRs Spill") != "0" or u.get("SGPRs Spill") != "0":
-                raise RuntimeError("libs2r: %s uses scratch or spills (%r): its stems and meter values must stay in registers" % (name, u))
-    if seen != 4:
-        raise RuntimeError("libs2r: resource usage of %d master kernels reported, 4 expected (the bus counts 1, 2, 4 and 8)" % seen)
-
-
-def _check_limiter_no_scratch(usage):
-    seen = 0
-    for name, u in usage:
-        if LIMITER_KERNEL in name:
-            seen += 1
-            if u.get("ScratchSize [bytes/lane]") != "0" or u.get("VGPRs Spill") != "0" or u.get("SGPRs Spill") != "0":
-                raise RuntimeError("libs2r: %s uses scratch or spills (%r): its windows live in LDS, the rest in registers" % (name, u))
-    if seen != 1:
-        raise RuntimeError("libs2r: resource usage of %d limiter kernels reported, 1 expected" % seen)
+                seen.append(k)
+                bad = [figure for figure in zero if u.get(figure) != "0"]
+                if bad:
+                    raise RuntimeError("libs2r: %s has a non-zero %s (%r): %s" % (name, ", ".join(bad), u, why))
+    if rule == "each":
+        ok, n = set(seen) == set(names), len(set(seen))
+    else:
+        ok, n = (len(seen) >= count if rule == "at least" else len(seen) == count), len(seen)
+    if not ok:
+        raise RuntimeError("libs2r: %s: resource usage of %d kernels (%s) reported, %s expected (%s)"
+                           % (source, n, ", ".join(sorted(set(seen))), "every one of %s" % list(names) if rule == "each" else "%s %d" % (rule, count), why_count))
 
 
 def check_m0_contract(lib=None, texts=None):

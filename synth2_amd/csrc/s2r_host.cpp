@@ -21,6 +21,8 @@
 #include "s2r_device.h"
 #include "s2r_math.h"
 #include "s2r_patch.h"
+#include "s2r_post.h"
+#include "s2r_rules.h"
 #include "s2r_voices.h"
 
 namespace {
@@ -315,55 +317,8 @@ struct s2r_synth {
     float *bus_out = nullptr, *bus_out_dev = nullptr;            // pinned and device-mapped: S2R_MAX_BUSES * 2 * max_frames floats
     float bus_mix_ms = -1.0f;                    // pan_mix_ms of the last s2r_fill_buses (tools/bus_time.py)
     bool bus_dev_ramped = false;                 // what bus_gains_dev holds was sent for a ramped fill: (G0, step), not the static gains
-    // The buses' convolution reverbs (s2r_set_bus_reverb).  Everything is allocated when a reverb is set, never in a fill.
-    struct BusFx {
-        uint32_t n_taps = 0;                     // K; 0: the bus has no reverb
-        float dry = 0.0f, wet = 0.0f;
-        float *taps = nullptr;                   // [2][tstride]: ir_L, ir_R, padded with +0.0 up to whole segments
-        float *line[2] = {nullptr, nullptr};     // [2][lstride] each: K - 1 frames of history per channel in front of a call's dry frames; line[cur] holds the history
-        float *partials = nullptr;               // [2][n_seg][fx_pstride]
-        uint32_t tstride = 0, lstride = 0;
-        int cur = 0;
-    } fx[S2R_MAX_BUSES];
-    float *fx_stage = nullptr;                   // [S2R_MAX_BUSES][2 * max_frames]: where the bus combine writes in a call that runs a reverb
-    float *bus_mix_out = nullptr;                // where the bus combine of the call under way writes: bus_out_dev, or fx_stage
-    hipEvent_t fx_ev[2] = {nullptr, nullptr};    // s2r_set_timing: around the reverb's kernels of the last bus fill
-    float bus_fx_ms = -1.0f;                     // ... and the time between them (0 when the fill ran none; tools/reverb_time.py)
-    // The master section (s2r_fill_master).  Nothing is allocated before the first master fill, and a handle that
-    // never makes one passes the pointers and makes the launches it always did.
-    struct Master {
-        // s2r_set_bus_return / s2r_set_master_fader: what the caller last set — the target — and what the last master fill left — the applied
-        float ret[S2R_MAX_BUSES], ret_app[S2R_MAX_BUSES];
-        float fader = 1.0f, fader_app = 1.0f;
-        float *stage = nullptr;                  // [S2R_MAX_BUSES][2 * max_frames] in device memory: where the last stem writer of a master fill writes
-        float *partials = nullptr, *partials_dev = nullptr;      // pinned and device-mapped: [ceil(max_frames / S2R_METER_BLOCK)][S2R_MASTER_ROW]
-        bool metered = false;                    // a master fill has succeeded: the meters below are its
-        uint32_t meter_buses = 0;
-        float peak[S2R_MASTER_CH], energy[S2R_MASTER_CH];
-        hipEvent_t ev[2] = {nullptr, nullptr};   // s2r_set_timing: around the master kernel of the last master fill
-        float ms = -1.0f;                        // ... and the time between them (tools/master_time.py)
-        Master() { for (uint32_t b = 0; b < S2R_MAX_BUSES; b++) ret[b] = ret_app[b] = 1.0f; }
-    } master;
-    // The master limiter (s2r_set_master_limiter).  Nothing is allocated before the first master fill that finds it
-    // set, and a handle on which it never was passes the pointers and makes the launches it always did.
-    struct Limiter {
-        float ceiling = 0.0f;
-        uint32_t lookahead = 0, hold = 0;        // lookahead 0: off
-        // The state — xh [lookahead][2], then gh [2 * lookahead + hold] — lives in `host` while host_valid (set, reset or restored
-        // since the last fill, or no fill yet) and in state[cur] on the device otherwise.  A fill uploads a valid host copy into
-        // state[cur], the kernel writes state[cur ^ 1], and the commit flips cur and drops the host copy.
-        std::vector<float> host;
-        bool host_valid = false;
-        float *state[2] = {nullptr, nullptr};    // device memory, each 2 * S2R_LIMITER_MAX_LOOKAHEAD + (2 * S2R_LIMITER_MAX_LOOKAHEAD + S2R_LIMITER_MAX_HOLD) floats
-        int cur = 0;
-        float *in = nullptr;                     // [2 * max_frames] in device memory: where the master kernel writes when the limiter is on
-        float *partials = nullptr, *partials_dev = nullptr;      // pinned and device-mapped: [ceil(max_frames / S2R_LIMITER_BLOCK)][2]
-        bool metered = false;                    // a master fill has run the limiter: the meters below are its
-        float min_gain = 1.0f, out_peak = 0.0f;
-        hipEvent_t ev[2] = {nullptr, nullptr};   // s2r_set_timing: around the limiter kernel of the last master fill
-        float ms = -1.0f;                        // ... and the time between them (0 when the fill ran none; tools/limiter_time.py)
-    } limiter;
-    float *stem_out = nullptr;                   // where the last stem writer of the call under way writes: bus_out_dev, or master.stage
+    // What runs behind the bus mixdown (s2r_post.h): the buses' reverbs, the master section and the master limiter
+    S2rPostChain post;
     float pitch_table[256];
     hipEvent_t t0 = nullptr, t1 = nullptr;
     bool timing = false, timed = false, no_flat_shortcut = false;
@@ -391,7 +346,8 @@ int set_err(s2r_synth *s, int code, const char *fmt, ...) {
 }
 
 // every entry point that touches the device, or anything a running resident kernel's arguments were built from, first
-#define S2R_QUIESCE(s) do { const int rc_q_ = quiesce(s); if (rc_q_ != S2R_OK) return rc_q_; } while (0)
+#define S2R_TRY(call) do { const int rc_t_ = (call); if (rc_t_ != S2R_OK) return rc_t_; } while (0)     // any step that returns a status
+#define S2R_QUIESCE(s) S2R_TRY(quiesce(s))
 int resident_stop(s2r_synth *s);
 int pool_stop(s2r_synth *s);
 int quiesce(s2r_synth *s) { int rc = resident_stop(s); return rc != S2R_OK ? rc : pool_stop(s); }
@@ -432,10 +388,8 @@ inline s2r_synth *shard_of(s2r_synth *s, uint32_t pool_index, uint32_t *local) {
     return s;
 }
 
-void push_event(s2r_synth *top, uint32_t pool_index, uint32_t flags, float pitch, uint32_t seed, uint32_t program = 0) {
-    uint32_t local = 0;
-    s2r_synth *s = shard_of(top, pool_index, &local);
-    if (!s) return;
+// one more event into the folded record of shard voice `local` (one record per touched voice between two fills)
+void fold_event(s2r_synth *s, uint32_t local, uint32_t flags, float pitch, uint32_t seed, uint32_t program) {
     int32_t slot = s->pending_slot[local];
     if (slot < 0) {
         slot = (int32_t)s->pending.size();
@@ -443,10 +397,13 @@ void push_event(s2r_synth *top, uint32_t pool_index, uint32_t flags, float pitch
         s->pending.push_back(S2rVoiceEvent{local, 0u, 0.0f, 0u});
     }
     S2rVoiceEvent &e = s->pending[(size_t)slot];
-    if (flags & S2R_EV_RESTART) {                 // wipes an earlier release
-        e.flags = S2R_EV_RESTART | (program << S2R_EV_PROGRAM_SHIFT); e.pitch = pitch; e.seed = seed;
-    }
+    if (flags & S2R_EV_RESTART) { e.flags = S2R_EV_RESTART | (program << S2R_EV_PROGRAM_SHIFT); e.pitch = pitch; e.seed = seed; }     // wipes an earlier release
     if (flags & S2R_EV_RELEASE) e.flags |= S2R_EV_RELEASE;
+}
+
+void push_event(s2r_synth *top, uint32_t pool_index, uint32_t flags, float pitch, uint32_t seed, uint32_t program = 0) {
+    uint32_t local = 0;
+    if (s2r_synth *s = shard_of(top, pool_index, &local)) fold_event(s, local, flags, pitch, seed, program);
 }
 
 // An untimed event of a voice whose shard already holds frame-0 RECORDS for the next fill (a big batch's, s2r_note_events) joins
@@ -472,17 +429,7 @@ void fold_frame0_records(s2r_synth *top) {
     for (s2r_synth *kid : top->kids) fold_frame0_records(kid);
     s2r_synth *root = top->parent ? top->parent : top;
     if (top->tpending.empty() || root->fill_time != 0) return;
-    for (const S2rTimedEvent &te : top->tpending) {
-        int32_t slot = top->pending_slot[te.voice];
-        if (slot < 0) {
-            slot = (int32_t)top->pending.size();
-            top->pending_slot[te.voice] = slot;
-            top->pending.push_back(S2rVoiceEvent{te.voice, 0u, 0.0f, 0u});
-        }
-        S2rVoiceEvent &e = top->pending[(size_t)slot];
-        if (te.flags & S2R_EV_RESTART) { e.flags = S2R_EV_RESTART | (te.program << S2R_EV_PROGRAM_SHIFT); e.pitch = te.pitch; e.seed = te.seed; }
-        if (te.flags & S2R_EV_RELEASE) e.flags |= S2R_EV_RELEASE;
-    }
+    for (const S2rTimedEvent &te : top->tpending) fold_event(top, te.voice, te.flags, te.pitch, te.seed, te.program);
     for (const S2rTimedEvent &te : top->tpending) top->tlast[te.voice] = -1;
     top->tpending.clear();
 }
@@ -518,8 +465,7 @@ int slot_release(s2r_synth *s, EventSlot &sl) {
     else if (sl.state == 2 && (int32_t)(*sl.word - sl.seq) < 0) {
         // (four slots rotate and at most two fills are in flight, so this is the rare path: the fill's last kernel — its
         // mix, possibly still deferred — has not reported yet)
-        int rc = launch_deferred_mix(s, s->stream);
-        if (rc != S2R_OK) return rc;
+        S2R_TRY(launch_deferred_mix(s, s->stream));
         if (!s->pool_running) S2R_HIP(s, hipStreamSynchronize(s->stream));
         if (s->ov_busy) S2R_HIP(s, hipStreamSynchronize(s->stream_b));
         // (a fill of the pool-resident kernel: only its completion word tells)
@@ -1242,8 +1188,7 @@ int enqueue_fill(s2r_synth *s, size_t frames, uint32_t sample_rate, hipStream_t 
     if (s->dmix.active && stream != s->stream) {
         // a fill on a caller's stream behind one in flight on ours: that one's mix reads the partial rows this fill
         // is about to overwrite
-        int rc = launch_deferred_mix(s, s->stream);
-        if (rc != S2R_OK) return rc;
+        S2R_TRY(launch_deferred_mix(s, s->stream));
         S2R_HIP(s, hipStreamSynchronize(s->stream));
     }
     // Two streams (S2rOverlapWords): the fills of s2r_fill_begin on our own stream, rendered into partial rows that a mix
@@ -1273,13 +1218,11 @@ int enqueue_fill(s2r_synth *s, size_t frames, uint32_t sample_rate, hipStream_t 
     EventSlot *timed_slot = nullptr;
     const S2rTimedEvent *tev_dev = nullptr;
     if (!arg_events) {
-        int rc = flush_events(s, stream, &timed_slot, &tev_dev, done, ov_parity);
-        if (rc != S2R_OK) return rc;
+        S2R_TRY(flush_events(s, stream, &timed_slot, &tev_dev, done, ov_parity));
     }
     {   // (no chain heads in this fill to take the previous fill's mix along: it goes alone, before the render kernel
         // overwrites the partial rows)
-        int rc = launch_deferred_mix(s, stream);
-        if (rc != S2R_OK) return rc;
+        S2R_TRY(launch_deferred_mix(s, stream));
     }
     bool bank_kernel = false;
     { int rc = ensure_bank(s, sample_rate, stream, &bank_kernel); if (rc != S2R_OK) return rc; }
@@ -1287,8 +1230,7 @@ int enqueue_fill(s2r_synth *s, size_t frames, uint32_t sample_rate, hipStream_t 
     S2rRenderParams &p = a.p;
     p = make_params(s, frames, sample_rate);
     {
-        int rc = ensure_tables(s, p, sample_rate, stream);
-        if (rc != S2R_OK) return rc;
+        S2R_TRY(ensure_tables(s, p, sample_rate, stream));
     }
     if (tables_wanted(s)) p.tab = s->tab;
     else if (bank_kernel) { p.tab = S2rTabRef{}; p.tab.base = s->bank_tab_dev; }      // the per-lane-patch kernel adds each entry's tab_off
@@ -1394,8 +1336,7 @@ int enqueue_multi(s2r_synth *s, size_t frames, uint32_t sample_rate, float *dev_
                 S2R_HIP(kid, hipMalloc((void **)&kid->per_voice_dev, need * sizeof(float)));
                 kid->per_voice_cap = need;
             }
-            int rc = enqueue_fill(kid, frames, sample_rate, kid->stream, nullptr, false, false, kid->per_voice_dev);
-            if (rc != S2R_OK) return rc;
+            S2R_TRY(enqueue_fill(kid, frames, sample_rate, kid->stream, nullptr, false, false, kid->per_voice_dev));
             return S2R_OK;
         }
         float *row = s->rows_dev[slot] + (size_t)k * s->cfg.max_frames;
@@ -1414,8 +1355,7 @@ int enqueue_multi(s2r_synth *s, size_t frames, uint32_t sample_rate, float *dev_
         float *dst = s->kid_stage[k] ? s->kid_stage[k] : row;
         // (the shard's own completion word: its event slots are then tracked without an event record per fill)
         const S2rDone kd{kid->done_dev + slot, ++kid->done_seq, kid->done_counter + slot};
-        int rc = enqueue_fill(kid, frames, sample_rate, kid->stream, dst, false, false, nullptr, -1, &kd);
-        if (rc != S2R_OK) return rc;
+        S2R_TRY(enqueue_fill(kid, frames, sample_rate, kid->stream, dst, false, false, nullptr, -1, &kd));
         if (s->kid_stage[k]) S2R_HIP(kid, hipMemcpyPeerAsync(row, s->device, dst, kid->device, frames * sizeof(float), kid->stream));
         S2R_HIP(kid, hipEventRecord(s->kid_done[slot][k], kid->stream));
         return S2R_OK;
@@ -1596,8 +1536,7 @@ int resident_launch(s2r_synth *s, uint32_t sample_rate, bool stereo) {
 
 int resident_fill(s2r_synth *s, float *out, size_t frames, uint32_t sample_rate, bool stereo) {
     if (s->res_running && (s->res_rate != sample_rate || s->res_stereo != stereo || resident_exited(s))) {
-        int rc = resident_stop(s);
-        if (rc != S2R_OK) return rc;
+        S2R_TRY(resident_stop(s));
     }
     if (!s->res_running) { int rc = resident_launch(s, sample_rate, stereo); if (rc != S2R_OK) return rc; }
     volatile uint32_t *c = s->res_cmd;
@@ -1659,9 +1598,6 @@ int resident_fill(s2r_synth *s, float *out, size_t frames, uint32_t sample_rate,
 }
 
 // ---- the voice mixer's bookkeeping ----
-inline bool pan_in_range(float x) { return x >= -1.0f && x <= 1.0f; }          // (false for NaN)
-inline bool unit_in_range(float x) { return x >= 0.0f && x <= 1.0f; }           // (false for NaN)
-inline bool fader_in_range(float fader, float shift) { return fader >= 0.0f && fader <= 1.0f && shift >= -2.0f && shift <= 2.0f; }   // (false for NaN)
 
 // The bus fill's staging buffer, once: byte offsets of the [padded_voices] arrays in bus_gains_host / bus_gains_dev.  gL, gR
 // (floats: pan gain times voice gain, times the applied fader), the bus bytes, — once sends are in use — the sends (floats) and
@@ -1727,8 +1663,8 @@ inline void mixer_note_on(s2r_synth *s, uint32_t local, uint8_t note, float velo
     s2r_synth::Mixer &m = s->mixer;
     const s2r_synth::ProgramMix &p = m.prog[s->program];
     s2r_synth::Mixer::Record r{local, frame, m.used, 0.0f, 0.0f, p.send, p.bus, p.send_bus, (uint8_t)s->program};
-    if (m.used & kMixPan) r.pan = s2r_voice_pan(p.pan, p.spread, note);
-    if (m.used & kMixLevel) r.gain = s2r_voice_gain(p.level, p.sens, velocity);      // (the other fields are copies: apply looks at r.mask)
+    if (m.used & kMixPan) r.pan = rule_voice_pan(p.pan, p.spread, note);
+    if (m.used & kMixLevel) r.gain = rule_voice_gain(p.level, p.sens, velocity);      // (the other fields are copies: apply looks at r.mask)
     if (frame == 0) { m.apply(r); s->gains_dirty = kGainsAll; }
     else m.timed.push_back(r);
 }
@@ -1754,7 +1690,7 @@ int pan_send_gains(s2r_synth *s) {
         S2R_HIP(s, hipMalloc((void **)&s->gains_dev, 2 * pv * sizeof(float)));
         S2R_HIP(s, hipEventCreateWithFlags(&s->gains_sent, hipEventDisableTiming));
     } else S2R_HIP(s, hipEventSynchronize(s->gains_sent));       // (the last copy may still be reading the pinned buffer)
-    for (uint32_t i = 0; i < s->shard_voices; i++) s2r_pan_gains((m.used & kMixPan) ? m.pan[i] : 0.0f, s->gains_host + i, s->gains_host + pv + i);
+    for (uint32_t i = 0; i < s->shard_voices; i++) rule_pan_gains((m.used & kMixPan) ? m.pan[i] : 0.0f, s->gains_host + i, s->gains_host + pv + i);
     S2R_HIP(s, hipMemcpyAsync(s->gains_dev, s->gains_host, 2 * pv * sizeof(float), hipMemcpyHostToDevice, s->stream));
     S2R_HIP(s, hipEventRecord(s->gains_sent, s->stream));
     s->gains_dirty &= ~kGainsPan;
@@ -1792,18 +1728,18 @@ int bus_send_gains(s2r_synth *s, bool ramp, uint32_t total) {
         b[i] = (m.used & kMixLevel) ? m.bus[i] : (uint8_t)0;
         if (!(m.used & kMixFader)) {
             float l, r;
-            s2r_pan_gains(pan, &l, &r);
+            rule_pan_gains(pan, &l, &r);
             gl[i] = l * w; gr[i] = r * w;
             continue;
         }
         const s2r_synth::ProgramMix &p = m.prog[m.program[i] < n_prog ? m.program[i] : 0u];      // (past a later, smaller bank: program 0, as its patch is)
         float g0l, g0r;
-        s2r_fader_gains(pan, w, p.fader_app, p.shift_app, &g0l, &g0r);
+        rule_fader_gains(pan, w, p.fader_app, p.shift_app, &g0l, &g0r);
         gl[i] = g0l; gr[i] = g0r;
         if (!ramp) continue;
         if (p.moving()) {
             float g1l, g1r;
-            s2r_fader_gains(pan, w, p.fader, p.shift, &g1l, &g1r);
+            rule_fader_gains(pan, w, p.fader, p.shift, &g1l, &g1r);
             const float sl = g1l - g0l, sr = g1r - g0r;
             dl[i] = sl / fn; dr[i] = sr / fn;
         } else { dl[i] = 0.0f; dr[i] = 0.0f; }
@@ -1819,15 +1755,14 @@ int bus_send_gains(s2r_synth *s, bool ramp, uint32_t total) {
 // into `pending`: slice after slice the MODE 1 launch into the rows buffer and the mixdown into the mapped output.  `last_event`:
 // the frame the pool's clock has already been moved to by the fill's events (fill_time at entry) — the slices from there on move
 // it further.
-// `ramp`: a bus fill under moving faders — the ramped mixdown, which is told where in the CALL each slice begins.
-int pan_segment(s2r_synth *s, uint32_t at, uint32_t n, uint32_t last_event, uint32_t sample_rate, uint32_t n_buses, uint32_t total, bool ramp) {
-    int rc = n_buses ? bus_send_gains(s, ramp, total) : pan_send_gains(s);
-    if (rc != S2R_OK) return rc;
+// `ramp`: a bus fill under moving faders — the ramped mixdown, told where in the CALL each slice begins.  `bus_dst`: the route's combine_out.
+int pan_segment(s2r_synth *s, uint32_t at, uint32_t n, uint32_t last_event, uint32_t sample_rate, uint32_t n_buses, uint32_t total, bool ramp,
+                float *bus_dst) {
+    S2R_TRY(n_buses ? bus_send_gains(s, ramp, total) : pan_send_gains(s));
     for (uint32_t done = 0; done < n;) {
         const uint32_t len = n - done < s->pan_slice ? n - done : s->pan_slice;
         s->fill_time = at + done >= last_event ? 0u : len;       // enqueue_fill moves the clock by len - fill_time
-        rc = enqueue_fill(s, len, sample_rate, s->stream, nullptr, false, false, s->pan_rows);
-        if (rc != S2R_OK) return rc;
+        S2R_TRY(enqueue_fill(s, len, sample_rate, s->stream, nullptr, false, false, s->pan_rows));
         const uint32_t n_groups = s->mix_groups, blocks_per_group = (s->n_blocks + n_groups - 1) / n_groups;
         if (s->timing) {
             while (s->pan_ev.size() < s->pan_ev_used + 2) { hipEvent_t e; S2R_HIP(s, hipEventCreate(&e)); s->pan_ev.push_back(e); }
@@ -1844,7 +1779,7 @@ int pan_segment(s2r_synth *s, uint32_t at, uint32_t n, uint32_t last_event, uint
             m.frames = len; m.stride = len;                      // (the render kernel's rows are `frames` apart)
             m.partials = s->bus_partials; m.pstride = s->pan_slice;
             m.n_groups = n_groups; m.blocks_per_group = blocks_per_group;
-            m.out = s->bus_mix_out + 2u * (size_t)(at + done); m.ostride = 2u * (size_t)total;
+            m.out = bus_dst + 2u * (size_t)(at + done); m.ostride = 2u * (size_t)total;
             m.n_buses = n_buses;
             if (ramp) {
                 m.d_l = reinterpret_cast<const float *>(dev + o.dl); m.d_r = reinterpret_cast<const float *>(dev + o.dr);
@@ -1871,8 +1806,7 @@ int pan_segment(s2r_synth *s, uint32_t at, uint32_t n, uint32_t last_event, uint
 }
 
 int fill_host(s2r_synth *s, float *out, size_t frames, uint32_t sample_rate, bool stereo) {
-    int rc = check_fill(s, frames, sample_rate);
-    if (rc != S2R_OK) return rc;
+    S2R_TRY(check_fill(s, frames, sample_rate));
     if (frames == 0) return S2R_OK;
     if (!out) return set_err(s, S2R_ERR_INVALID, "null output buffer");
     if (!s->kids.empty() && s->ring_count)
@@ -1880,13 +1814,11 @@ int fill_host(s2r_synth *s, float *out, size_t frames, uint32_t sample_rate, boo
     // (the resident kernel's fills make no HIP call while it runs)
     if (resident_eligible(s, frames)) return resident_fill(s, out, frames, sample_rate, stereo);
     S2R_HIP(s, hipSetDevice(s->device));
-    rc = resident_stop(s);
-    if (rc != S2R_OK) return rc;
+    S2R_TRY(resident_stop(s));
     // the last kernel of the fill writes the few KiB of output straight into mapped host memory: no copy
     // command between the launch and the wait
     const S2rDone done{s->done_dev + 2, ++s->done_seq, s->done_counter + 2};
-    rc = enqueue_root(s, frames, sample_rate, s->out_host_dev, stereo, -1, &done);
-    if (rc != S2R_OK) return rc;
+    S2R_TRY(enqueue_root(s, frames, sample_rate, s->out_host_dev, stereo, -1, &done));
     const size_t n = frames * (stereo ? 2 : 1);
     if (s->pool_gran_pending) {
         // the frames of a short fill of the pool-resident kernel, each with the fill's tag above the sample
@@ -1914,140 +1846,16 @@ int fill_host(s2r_synth *s, float *out, size_t frames, uint32_t sample_rate, boo
         }
         return S2R_OK;
     }
-    rc = wait_done(s, 2, done.value);
-    if (rc != S2R_OK) return rc;
+    S2R_TRY(wait_done(s, 2, done.value));
     { int rc2 = overlap_check(s); if (rc2 != S2R_OK) return rc2; }
     if (s->xg_on && s->xg_rank != 0) std::memset(out, 0, n * sizeof(float));        // (the mix is the root's)
     else std::memcpy(out, s->out_host, n * sizeof(float));
     return S2R_OK;
 }
 
-void fx_release(s2r_synth::BusFx &f) {
-    if (f.taps) (void)hipFree(f.taps);
-    if (f.line[0]) (void)hipFree(f.line[0]);
-    if (f.line[1]) (void)hipFree(f.line[1]);
-    if (f.partials) (void)hipFree(f.partials);
-    f = s2r_synth::BusFx{};
-}
-
-inline uint32_t fx_pstride(const s2r_synth *s) { return (s->cfg.max_frames + 7u) & ~7u; }
-
-// the reverbs of the buses of a call of n_buses (one on a bus past them is idle in that call)
-inline bool fx_active(const s2r_synth *s, uint32_t n_buses) {
-    for (uint32_t b = 0; b < n_buses; b++) if (s->fx[b].n_taps) return true;
-    return false;
-}
-
-// After the last segment's mixdown of a bus fill that wrote into the staging buffer: the reverbs' kernels on the handle's stream.
-int fx_launch(s2r_synth *s, uint32_t n_buses, uint32_t frames) {
-    S2rFx fx{};
-    for (uint32_t b = 0; b < n_buses; b++) {
-        const s2r_synth::BusFx &f = s->fx[b];
-        if (!f.n_taps) continue;
-        S2rFxBus &d = fx.bus[b];
-        d.taps = f.taps; d.line = f.line[f.cur]; d.next = f.line[f.cur ^ 1]; d.partials = f.partials;
-        d.n_taps = f.n_taps; d.n_seg = (f.n_taps + S2R_IR_SEGMENT - 1u) / S2R_IR_SEGMENT;
-        d.tstride = f.tstride; d.lstride = f.lstride; d.dry = f.dry; d.wet = f.wet;
-    }
-    fx.stage = s->fx_stage; fx.out = s->stem_out; fx.n_buses = n_buses; fx.frames = frames; fx.pstride = fx_pstride(s);
-    if (s->timing) {
-        for (hipEvent_t &e : s->fx_ev) if (!e) S2R_HIP(s, hipEventCreate(&e));
-        S2R_HIP(s, hipEventRecord(s->fx_ev[0], s->stream));
-    }
-    S2R_HIP(s, s2r_launch_bus_fx(fx, s->stream));
-    if (s->timing) S2R_HIP(s, hipEventRecord(s->fx_ev[1], s->stream));
-    return S2R_OK;
-}
-
-// The last stage of a master fill, behind the reverbs' kernels and in front of the call's synchronise: returns, master fader and
-// the meters' block partials.  `stems`: the caller wants them too.
-int master_launch(s2r_synth *s, uint32_t n_buses, uint32_t frames, bool stems, bool limited) {
-    const s2r_synth::Master &ms = s->master;
-    S2rMaster m{};
-    m.stage = ms.stage; m.out = limited ? s->limiter.in : s->out_host_dev; m.stems = stems ? s->bus_out_dev : nullptr; m.partials = ms.partials_dev;
-    m.n_buses = n_buses; m.frames = frames;
-    const float fn = (float)frames;
-    for (uint32_t b = 0; b < n_buses; b++) {
-        const float d = ms.ret[b] - ms.ret_app[b];               // (+0.0 for a pair that did not move, and so is its step)
-        m.r0[b] = ms.ret_app[b]; m.dr[b] = d / fn;
-    }
-    const float d = ms.fader - ms.fader_app;
-    m.m0 = ms.fader_app; m.dm = d / fn;
-    if (s->timing) {
-        for (hipEvent_t &e : s->master.ev) if (!e) S2R_HIP(s, hipEventCreate(&e));
-        S2R_HIP(s, hipEventRecord(s->master.ev[0], s->stream));
-    }
-    S2R_HIP(s, s2r_launch_master(m, s->stream));
-    if (s->timing) S2R_HIP(s, hipEventRecord(s->master.ev[1], s->stream));
-    return S2R_OK;
-}
-
-// after the synchronise of a master fill that succeeded: the block partials in block order, and applied = target
-void master_commit(s2r_synth *s, uint32_t n_buses, uint32_t frames) {
-    s2r_synth::Master &ms = s->master;
-    const uint32_t n_ch = (n_buses + 1u) * 2u, n_blocks = (frames + S2R_METER_BLOCK - 1u) / S2R_METER_BLOCK;
-    for (uint32_t ch = 0; ch < n_ch; ch++) {
-        float peak = 0.0f, energy = 0.0f;
-        for (uint32_t k = 0; k < n_blocks; k++) {
-            const float *row = ms.partials + (size_t)k * S2R_MASTER_ROW;
-            peak = row[ch] > peak ? row[ch] : peak;
-            energy = energy + row[S2R_MASTER_CH + ch];
-        }
-        ms.peak[ch] = peak; ms.energy[ch] = energy;
-    }
-    ms.metered = true; ms.meter_buses = n_buses;
-    for (uint32_t b = 0; b < S2R_MAX_BUSES; b++) ms.ret_app[b] = ms.ret[b];
-    ms.fader_app = ms.fader;
-}
-
-// ---- the master limiter ----
-constexpr size_t kLimXh = 2u * S2R_LIMITER_MAX_LOOKAHEAD, kLimState = kLimXh + 2u * S2R_LIMITER_MAX_LOOKAHEAD + S2R_LIMITER_MAX_HOLD;
-
-inline size_t limiter_gains(uint32_t lookahead, uint32_t hold) { return 2u * (size_t)lookahead + hold; }
-
-// the initial state: xh +0.0, gh 1.0
-void limiter_reset(s2r_synth::Limiter &lm) {
-    lm.host.assign(2u * (size_t)lm.lookahead, 0.0f);
-    lm.host.resize(lm.host.size() + limiter_gains(lm.lookahead, lm.hold), 1.0f);
-    lm.host_valid = true;
-}
-
-// The limiter of a master fill, behind the master kernel and in front of the call's synchronise: the master from limiter.in, the
-// limited master into the pinned output, the next state into the copy that is not the current one.
-int limiter_launch(s2r_synth *s, uint32_t frames) {
-    s2r_synth::Limiter &lm = s->limiter;
-    const size_t nx = 2u * (size_t)lm.lookahead, ng = limiter_gains(lm.lookahead, lm.hold);
-    float *cur = lm.state[lm.cur], *next = lm.state[lm.cur ^ 1];
-    if (lm.host_valid) {                                         // (stays valid until the commit: a failed call leaves the state where it was)
-        S2R_HIP(s, hipMemcpyAsync(cur, lm.host.data(), nx * sizeof(float), hipMemcpyHostToDevice, s->stream));
-        S2R_HIP(s, hipMemcpyAsync(cur + kLimXh, lm.host.data() + nx, ng * sizeof(float), hipMemcpyHostToDevice, s->stream));
-    }
-    S2rLimiter a{};
-    a.x = lm.in; a.out = s->out_host_dev; a.xh = cur; a.gh = cur + kLimXh; a.xh_next = next; a.gh_next = next + kLimXh;
-    a.partials = lm.partials_dev; a.frames = frames; a.lookahead = lm.lookahead; a.hold = lm.hold; a.ceiling = lm.ceiling;
-    if (s->timing) {
-        for (hipEvent_t &e : lm.ev) if (!e) S2R_HIP(s, hipEventCreate(&e));
-        S2R_HIP(s, hipEventRecord(lm.ev[0], s->stream));
-    }
-    S2R_HIP(s, s2r_launch_limiter(a, s->stream));
-    if (s->timing) S2R_HIP(s, hipEventRecord(lm.ev[1], s->stream));
-    return S2R_OK;
-}
-
-// after the synchronise of a master fill that succeeded: the state has moved on, and the workgroups' rows give the call's meters
-void limiter_commit(s2r_synth *s, uint32_t frames) {
-    s2r_synth::Limiter &lm = s->limiter;
-    lm.cur ^= 1;
-    lm.host_valid = false;
-    const uint32_t n_blocks = (frames + S2R_LIMITER_BLOCK - 1u) / S2R_LIMITER_BLOCK;
-    float mn = lm.partials[0], pk = lm.partials[1];
-    for (uint32_t k = 1; k < n_blocks; k++) {
-        const float *row = lm.partials + (size_t)k * 2u;
-        mn = row[0] < mn ? row[0] : mn;
-        pk = row[1] > pk ? row[1] : pk;
-    }
-    lm.min_gain = mn; lm.out_peak = pk; lm.metered = true;
-}
+// what the post-mix chain is told of the handle
+template <class T> inline void put(T *to, T v) { if (to) *to = v; }             // an optional output of a getter
+inline S2rPostCtx post_ctx(const s2r_synth *s) { return S2rPostCtx{s->stream, s->cfg.max_frames, s->timing, s->bus_out_dev, s->out_host_dev}; }
 
 void release_all(s2r_synth *s) {
     if (!s) return;
@@ -2103,16 +1911,7 @@ void release_all(s2r_synth *s) {
     if (s->bus_gains_sent) (void)hipEventDestroy(s->bus_gains_sent);
     if (s->bus_partials) (void)hipFree(s->bus_partials);
     if (s->bus_out) (void)hipHostFree(s->bus_out);
-    for (s2r_synth::BusFx &f : s->fx) fx_release(f);
-    if (s->fx_stage) (void)hipFree(s->fx_stage);
-    if (s->master.stage) (void)hipFree(s->master.stage);
-    if (s->master.partials) (void)hipHostFree(s->master.partials);
-    for (hipEvent_t e : s->master.ev) if (e) (void)hipEventDestroy(e);
-    for (float *p : s->limiter.state) if (p) (void)hipFree(p);
-    if (s->limiter.in) (void)hipFree(s->limiter.in);
-    if (s->limiter.partials) (void)hipHostFree(s->limiter.partials);
-    for (hipEvent_t e : s->limiter.ev) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : s->fx_ev) if (e) (void)hipEventDestroy(e);
+    s->post.release();
     for (hipEvent_t e : s->pan_ev) (void)hipEventDestroy(e);
     if (s->voice_ev_head) (void)hipFree(s->voice_ev_head);
     if (s->tev_copy) (void)hipFree(s->tev_copy);
@@ -2638,8 +2437,7 @@ int s2r_fill(s2r_synth *s, float *mono_out, size_t frames, uint32_t sample_rate_
 }
 
 int s2r_fill_begin(s2r_synth *s, size_t frames, uint32_t sample_rate_hz) {
-    int rc = check_fill(s, frames, sample_rate_hz);
-    if (rc != S2R_OK) return rc;
+    S2R_TRY(check_fill(s, frames, sample_rate_hz));
     if (s->ring_count >= 2) return set_err(s, S2R_ERR_INVALID, "two fills are already in flight: s2r_fill_end first");
     { const int rc_r = resident_stop(s); if (rc_r != S2R_OK) return rc_r; }      // (the pool-resident kernel stays: enqueue_root decides)
     S2R_HIP(s, hipSetDevice(s->device));
@@ -2647,8 +2445,7 @@ int s2r_fill_begin(s2r_synth *s, size_t frames, uint32_t sample_rate_hz) {
     if (frames) {
         // the last kernel of the fill writes the mix straight into this slot's mapped host buffer
         const S2rDone done{s->done_dev + slot, ++s->done_seq, s->done_counter + slot};
-        rc = enqueue_root(s, frames, sample_rate_hz, s->ring_dev[slot], false, (int)slot, &done);
-        if (rc != S2R_OK) return rc;
+        S2R_TRY(enqueue_root(s, frames, sample_rate_hz, s->ring_dev[slot], false, (int)slot, &done));
         s->ring_seq[slot] = done.value;
     } else s->ring_seq[slot] = 0;
     // (a fill is tracked by its completion word; an empty one by the event)
@@ -2670,8 +2467,7 @@ int s2r_fill_end(s2r_synth *s, float *mono_out, size_t capacity) {
         return set_err(s, S2R_ERR_INVALID, "the oldest fill in flight has %zu frames, the buffer takes %zu", s->ring_frames[slot], capacity);
     if (s->dmix.active && s->dmix.ring_slot == (int)slot) {      // nobody began another fill in the meantime
         S2R_HIP(s, hipSetDevice(s->device));
-        int rc = launch_deferred_mix(s, s->stream);
-        if (rc != S2R_OK) return rc;
+        S2R_TRY(launch_deferred_mix(s, s->stream));
     }
     // A fill that failed on the device is reported ONCE, with its buffer zeroed, and leaves the ring like any other: the next
     // s2r_fill_end is the next fill's (which, the handle being broken by then, reports that).
@@ -2696,19 +2492,6 @@ int s2r_fill_stereo(s2r_synth *s, float *interleaved_lr_out, size_t frames, uint
 }
 
 // ---- true stereo ----
-float s2r_voice_pan(float pan, float key_spread, uint8_t note) {
-    const float k = (float)((int)note - 64) * 0.015625f;        // exact
-    const float spread = key_spread * k;                         // (-ffp-contract=off: rounded before the sum)
-    const float p = pan + spread;
-    return p < -1.0f ? -1.0f : (p > 1.0f ? 1.0f : p);
-}
-
-void s2r_pan_gains(float p, float *gl, float *gr) {
-    const float l = (1.0f - p) * 0.5f, r = (1.0f + p) * 0.5f;
-    if (gl) *gl = std::sqrt(l);                                  // IEEE 754 sqrt: correctly rounded
-    if (gr) *gr = std::sqrt(r);
-}
-
 int s2r_set_program_pan(s2r_synth *s, uint32_t program, float pan, float key_spread) {
     // (the values first: they are wrong whatever the handle holds — and a front-end can ask without a device)
     if (!pan_in_range(pan) || !pan_in_range(key_spread))
@@ -2757,8 +2540,7 @@ static int fill_rows_mixed(s2r_synth *s, float *out, size_t capacity, uint32_t n
     if (!s) return S2R_ERR_INVALID;
     if (!s->kids.empty() || s->parent) return set_err(s, S2R_ERR_INVALID, "%s takes a single-device handle, not a device list", who);
     if (s->xg_on) return set_err(s, S2R_ERR_INVALID, "%s takes a handle without an exchange attached", who);
-    int rc = check_fill(s, frames, sample_rate_hz);
-    if (rc != S2R_OK) return rc;
+    S2R_TRY(check_fill(s, frames, sample_rate_hz));
     if (frames == 0) return S2R_OK;
     if (master ? !master_lr : !out) return set_err(s, S2R_ERR_INVALID, "null output buffer");
     if (n_buses && out && capacity < 2 * frames * n_buses)
@@ -2785,33 +2567,9 @@ static int fill_rows_mixed(s2r_synth *s, float *out, size_t capacity, uint32_t n
         S2R_HIP(s, hipHostMalloc((void **)&s->bus_out, (size_t)2 * S2R_MAX_BUSES * s->cfg.max_frames * sizeof(float), kHostPolled));
         S2R_HIP(s, hipHostGetDevicePointer((void **)&s->bus_out_dev, s->bus_out, 0));
     }
-    // (and the master fill's device copy of the stems and its pinned rows of block partials, once each: DESIGN.md 4.17)
-    if (master && !s->master.stage) S2R_HIP(s, hipMalloc((void **)&s->master.stage, (size_t)2 * S2R_MAX_BUSES * s->cfg.max_frames * sizeof(float)));
-    if (master && !s->master.partials_dev) {
-        const size_t rows = (s->cfg.max_frames + S2R_METER_BLOCK - 1u) / S2R_METER_BLOCK;
-        if (!s->master.partials) S2R_HIP(s, hipHostMalloc((void **)&s->master.partials, rows * S2R_MASTER_ROW * sizeof(float), kHostPolled));
-        S2R_HIP(s, hipHostGetDevicePointer((void **)&s->master.partials_dev, s->master.partials, 0));
-    }
-    // (and the limiter's input, the two copies of its state and its pinned rows of meter partials, once each, by the first master
-    // fill that finds a limiter set: DESIGN.md 4.18)
-    const bool limited = master && s->limiter.lookahead != 0;
-    if (limited) {
-        s2r_synth::Limiter &lm = s->limiter;
-        if (!lm.in) S2R_HIP(s, hipMalloc((void **)&lm.in, (size_t)2 * s->cfg.max_frames * sizeof(float)));
-        for (float *&p : lm.state) if (!p) S2R_HIP(s, hipMalloc((void **)&p, kLimState * sizeof(float)));
-        if (!lm.partials_dev) {
-            const size_t rows = (s->cfg.max_frames + S2R_LIMITER_BLOCK - 1u) / S2R_LIMITER_BLOCK;
-            if (!lm.partials) S2R_HIP(s, hipHostMalloc((void **)&lm.partials, rows * 2u * sizeof(float), kHostPolled));
-            S2R_HIP(s, hipHostGetDevicePointer((void **)&lm.partials_dev, lm.partials, 0));
-        }
-    }
-    // a call with a reverb on one of its buses mixes into the staging buffer, and the reverbs' kernels write the caller-visible
-    // output; without one the combine writes there itself, as it always did
-    // ... and in a master fill whichever of the two writes the stems last writes them into device memory, where the master kernel
-    // reads them: it must not read the pinned output back
-    const bool fx_on = n_buses && fx_active(s, n_buses);
-    s->stem_out = master ? s->master.stage : s->bus_out_dev;
-    s->bus_mix_out = fx_on ? s->fx_stage : s->stem_out;
+    // what runs behind the mixdown in this call, its once-only allocations and who writes where (s2r_post.h)
+    const S2rPostCtx pc = post_ctx(s); S2rPostCall call;
+    S2R_HIP(s, s->post.prepare(pc, n_buses, (uint32_t)frames, master, out != nullptr, call));
     fold_frame0_records(s);
     mixer_settle(s);
     s->pan_ev_used = 0;
@@ -2820,10 +2578,8 @@ static int fill_rows_mixed(s2r_synth *s, float *out, size_t capacity, uint32_t n
     // an earlier ramp is stale, and what this one sends is no static gain either (bus_dev_ramped)
     const bool ramp = n_buses && faders_moving(s);
     if (ramp) s->gains_dirty |= kGainsBus;
-    if (s->tpending.empty()) {
-        rc = pan_segment(s, 0u, (uint32_t)frames, last_event, sample_rate_hz, n_buses, (uint32_t)frames, ramp);
-        if (rc != S2R_OK) return rc;
-    } else {
+    if (s->tpending.empty()) S2R_TRY(pan_segment(s, 0u, (uint32_t)frames, last_event, sample_rate_hz, n_buses, (uint32_t)frames, ramp, call.route.combine_out));
+    else {
         // Events inside the fill: the per-voice rows and the event chains exclude each other in the render kernels, and an
         // event at frame f acts "exactly as if the caller had split the fill there" (s2r.h) — so the fill IS split there: the
         // records of one frame are folded like untimed ones (fold_frame0_records), what their note_ons give becomes the voices', and
@@ -2836,42 +2592,18 @@ static int fill_rows_mixed(s2r_synth *s, float *out, size_t capacity, uint32_t n
         size_t k = 0, km = 0;
         uint32_t at = 0;
         while (at < frames) {
-            for (; k < recs.size() && recs[k].frame <= at; k++) {
-                const S2rTimedEvent &te = recs[k];
-                int32_t slot = s->pending_slot[te.voice];
-                if (slot < 0) {
-                    slot = (int32_t)s->pending.size();
-                    s->pending_slot[te.voice] = slot;
-                    s->pending.push_back(S2rVoiceEvent{te.voice, 0u, 0.0f, 0u});
-                }
-                S2rVoiceEvent &e = s->pending[(size_t)slot];
-                if (te.flags & S2R_EV_RESTART) { e.flags = S2R_EV_RESTART | (te.program << S2R_EV_PROGRAM_SHIFT); e.pitch = te.pitch; e.seed = te.seed; }
-                if (te.flags & S2R_EV_RELEASE) e.flags |= S2R_EV_RELEASE;
-            }
+            for (; k < recs.size() && recs[k].frame <= at; k++) fold_event(s, recs[k].voice, recs[k].flags, recs[k].pitch, recs[k].seed, recs[k].program);
             for (; km < mrecs.size() && mrecs[km].frame <= at; km++) { s->mixer.apply(mrecs[km]); s->gains_dirty = kGainsAll; }
             const uint32_t next = k < recs.size() && recs[k].frame < frames ? recs[k].frame : (uint32_t)frames;
-            rc = pan_segment(s, at, next - at, last_event, sample_rate_hz, n_buses, (uint32_t)frames, ramp);
+            const int rc = pan_segment(s, at, next - at, last_event, sample_rate_hz, n_buses, (uint32_t)frames, ramp, call.route.combine_out);
             if (rc != S2R_OK) { s->fill_time = 0; return rc; }
             at = next;
         }
     }
-    if (fx_on) {                                                 // once per call, over all of its frames
-        rc = fx_launch(s, n_buses, (uint32_t)frames);
-        if (rc != S2R_OK) return rc;
-    }
-    if (master) {
-        rc = master_launch(s, n_buses, (uint32_t)frames, out != nullptr, limited);
-        if (rc != S2R_OK) return rc;
-    }
-    if (limited) {                                               // behind the master kernel: it writes the pinned output in its place
-        rc = limiter_launch(s, (uint32_t)frames);
-        if (rc != S2R_OK) return rc;
-    }
+    S2R_HIP(s, s->post.launch(pc, call));
     S2R_HIP(s, hipStreamSynchronize(s->stream));
-    if (fx_on) for (uint32_t b = 0; b < n_buses; b++) if (s->fx[b].n_taps) s->fx[b].cur ^= 1;     // the histories have moved on
     if (n_buses && (s->mixer.used & kMixFader)) snap_faders(s);  // the faders have arrived
-    if (master) master_commit(s, n_buses, (uint32_t)frames);     // ... and so have the returns and the master fader
-    if (limited) limiter_commit(s, (uint32_t)frames);            // ... and the limiter's state
+    s->post.commit(call);                                        // ... and so has everything behind the mixdown
     if (n_buses && out) std::memcpy(out, s->bus_out, 2 * frames * n_buses * sizeof(float));
     if (master) std::memcpy(master_lr, s->out_host, 2 * frames * sizeof(float));
     else if (!n_buses) std::memcpy(out, s->out_host, 2 * frames * sizeof(float));
@@ -2879,15 +2611,7 @@ static int fill_rows_mixed(s2r_synth *s, float *out, size_t capacity, uint32_t n
         float sum = 0.0f;
         for (size_t k = 0; k < s->pan_ev_used; k += 2) { float ms = 0.0f; S2R_HIP(s, hipEventElapsedTime(&ms, s->pan_ev[k], s->pan_ev[k + 1])); sum += ms; }
         (n_buses ? s->bus_mix_ms : s->pan_mix_ms) = sum;
-        if (n_buses) {
-            s->bus_fx_ms = 0.0f;
-            if (fx_on) S2R_HIP(s, hipEventElapsedTime(&s->bus_fx_ms, s->fx_ev[0], s->fx_ev[1]));
-        }
-        if (master) S2R_HIP(s, hipEventElapsedTime(&s->master.ms, s->master.ev[0], s->master.ev[1]));
-        if (master) {
-            s->limiter.ms = 0.0f;
-            if (limited) S2R_HIP(s, hipEventElapsedTime(&s->limiter.ms, s->limiter.ev[0], s->limiter.ev[1]));
-        }
+        S2R_HIP(s, s->post.read_timers(call));
     }
     return S2R_OK;
 }
@@ -2897,15 +2621,6 @@ int s2r_fill_panned(s2r_synth *s, float *interleaved_lr_out, size_t frames, uint
 }
 
 // ---- the voice mixer ----
-float s2r_voice_gain(float level, float velocity_sens, float velocity) {
-    float u = velocity < 1.0f ? velocity : 1.0f;                 // NaN -> 1
-    u = u > 0.0f ? u : 0.0f;
-    const float d = 1.0f - u;
-    const float t = velocity_sens * d;                           // (-ffp-contract=off: rounded before the difference)
-    const float a = 1.0f - t;
-    return level * a;
-}
-
 int s2r_set_program_mix(s2r_synth *s, uint32_t program, float level, float velocity_sens, uint32_t bus) {
     // (the values first, like s2r_set_program_pan)
     if (!unit_in_range(level) || !unit_in_range(velocity_sens) || bus >= S2R_MAX_BUSES)
@@ -2954,8 +2669,6 @@ int s2r_set_voice_mix(s2r_synth *s, const float *gains, const uint8_t *buses) {
 }
 
 // ---- aux sends ----
-float s2r_send_gain(float g, float send) { return g * send; }
-
 int s2r_set_program_send(s2r_synth *s, uint32_t program, float send, uint32_t send_bus) {
     // (the values first, like s2r_set_program_mix)
     if (!unit_in_range(send) || send_bus >= S2R_MAX_BUSES)
@@ -2964,8 +2677,7 @@ int s2r_set_program_send(s2r_synth *s, uint32_t program, float send, uint32_t se
     if (!s->kids.empty() || s->parent) return set_err(s, S2R_ERR_INVALID, "program sends are kept by single-device handles, not by a device list");
     if (program >= s->bank.size()) return set_err(s, S2R_ERR_INVALID, "program %u: the bank holds %zu patches", program, s->bank.size());
     if (send != 0.0f || send_bus != 0u) {
-        const int rc = mixer_begin(s, kMixSend);
-        if (rc != S2R_OK) return rc;
+        S2R_TRY(mixer_begin(s, kMixSend));
         mixer_settle(s);
     }
     s->mixer.prog[program].send = send; s->mixer.prog[program].send_bus = (uint8_t)send_bus;
@@ -2996,8 +2708,7 @@ int s2r_set_voice_sends(s2r_synth *s, const float *sends, const uint8_t *send_bu
     for (uint32_t i = 0; i < s->shard_voices; i++)
         if (!unit_in_range(sends[i]) || send_buses[i] >= S2R_MAX_BUSES)
             return set_err(s, S2R_ERR_PATCH_RANGE, "voice %u: send %g, send bus %u: the send lies in [0, 1], the bus below %u", i, (double)sends[i], (unsigned)send_buses[i], S2R_MAX_BUSES);
-    const int rc = mixer_begin(s, kMixSend);
-    if (rc != S2R_OK) return rc;
+    S2R_TRY(mixer_begin(s, kMixSend));
     mixer_settle(s);
     std::memcpy(s->mixer.send.data(), sends, (size_t)s->shard_voices * sizeof(float));
     std::memcpy(s->mixer.send_bus.data(), send_buses, (size_t)s->shard_voices);
@@ -3005,39 +2716,16 @@ int s2r_set_voice_sends(s2r_synth *s, const float *sends, const uint8_t *send_bu
     return S2R_OK;
 }
 
-// ---- per-bus convolution reverb ----
-// The rule on the host, one channel: segments of S2R_IR_SEGMENT taps in index order from +0.0, the segments in order from +0.0,
-// y = dry * x + wet * r; every product and every sum rounded on its own.
-int s2r_reverb_reference(const float *ir, uint32_t n_taps, const float *x_with_history, uint32_t frames, float dry, float wet, float *out) {
-    if (!unit_in_range(dry) || !unit_in_range(wet) || n_taps > S2R_MAX_IR_TAPS) return S2R_ERR_PATCH_RANGE;
-    if (!ir || n_taps == 0 || !x_with_history || (!out && frames)) return S2R_ERR_INVALID;
-    for (uint32_t k = 0; k < n_taps; k++) if (!std::isfinite(ir[k])) return S2R_ERR_PATCH_RANGE;
-    for (uint32_t i = 0; i < frames; i++) {
-        const float *x = x_with_history + (n_taps - 1u) + i;     // x[-k]: the dry sample k frames before frame i
-        float r = 0.0f;
-        for (uint32_t k0 = 0; k0 < n_taps; k0 += S2R_IR_SEGMENT) {
-            const uint32_t k1 = k0 + S2R_IR_SEGMENT < n_taps ? k0 + S2R_IR_SEGMENT : n_taps;
-            float p = 0.0f;
-            for (uint32_t k = k0; k < k1; k++) {
-                const float t = ir[k] * x[-(ptrdiff_t)k];
-                p = p + t;
-            }
-            r = r + p;
-        }
-        const float d = dry * x[0], w = wet * r;
-        out[i] = d + w;
-    }
-    return S2R_OK;
-}
-
-static int fx_handle(const s2r_synth *s, const char *who) {
+// ---- the post-mix chain: reverbs, master section, master limiter (s2r_post.h) ----
+// Every entry below looks at its values first (they are wrong whatever the handle holds), then at the handle, quiesces where it touches
+// the device, and calls into s->post for whatever is more than one value.  `what`: "bus reverbs are", "the master section is", ...
+static int post_handle(const s2r_synth *s, const char *who, const char *what) {
     if (!s) return S2R_ERR_INVALID;
-    if (!s->kids.empty() || s->parent) return set_err(const_cast<s2r_synth *>(s), S2R_ERR_INVALID, "%s: bus reverbs are kept by single-device handles, not by a device list", who);
+    if (!s->kids.empty() || s->parent) return set_err(const_cast<s2r_synth *>(s), S2R_ERR_INVALID, "%s: %s kept by single-device handles, not by a device list", who, what);
     return S2R_OK;
 }
 
 int s2r_set_bus_reverb(s2r_synth *s, uint32_t bus, const float *ir_l, const float *ir_r, uint32_t n_taps, float dry, float wet) {
-    // (the values first, like s2r_set_program_send)
     if (!unit_in_range(dry) || !unit_in_range(wet) || n_taps > S2R_MAX_IR_TAPS || bus >= S2R_MAX_BUSES)
         return set_err(s, S2R_ERR_PATCH_RANGE, "bus %u: %u taps, dry %g, wet %g: dry and wet lie in [0, 1], at most %u taps, the bus below %u", bus, n_taps,
                        (double)dry, (double)wet, S2R_MAX_IR_TAPS, S2R_MAX_BUSES);
@@ -3045,87 +2733,46 @@ int s2r_set_bus_reverb(s2r_synth *s, uint32_t bus, const float *ir_l, const floa
     if (ir_l)
         for (uint32_t k = 0; k < n_taps; k++)
             if (!std::isfinite(ir_l[k]) || !std::isfinite(ir_r[k])) return set_err(s, S2R_ERR_PATCH_RANGE, "bus %u: tap %u is not finite", bus, k);
-    int rc = fx_handle(s, "s2r_set_bus_reverb");
-    if (rc != S2R_OK) return rc;
+    S2R_TRY(post_handle(s, "s2r_set_bus_reverb", "bus reverbs are"));
     if (n_taps && !ir_l) return set_err(s, S2R_ERR_INVALID, "s2r_set_bus_reverb: %u taps and no response", n_taps);
     if (s->ring_count) return set_err(s, S2R_ERR_INVALID, "s2r_set_bus_reverb with fills of s2r_fill_begin in flight: s2r_fill_end first");
     S2R_QUIESCE(s);
     S2R_HIP(s, hipSetDevice(s->device));
     S2R_HIP(s, hipStreamSynchronize(s->stream));
-    if (n_taps == 0) { fx_release(s->fx[bus]); return S2R_OK; }
-    s2r_synth::BusFx f;
-    const uint32_t n_seg = (n_taps + S2R_IR_SEGMENT - 1u) / S2R_IR_SEGMENT;
-    f.n_taps = n_taps; f.dry = dry; f.wet = wet;
-    f.tstride = n_seg * S2R_IR_SEGMENT;
-    f.lstride = (n_taps - 1u + s->cfg.max_frames + 3u) & ~3u;
-    std::vector<float> padded(2u * (size_t)f.tstride, 0.0f);
-    std::memcpy(padded.data(), ir_l, (size_t)n_taps * sizeof(float));
-    std::memcpy(padded.data() + f.tstride, ir_r, (size_t)n_taps * sizeof(float));
-    const size_t line_bytes = 2u * (size_t)f.lstride * sizeof(float);
-    hipError_t e = hipSuccess;
-    if (!s->fx_stage) e = hipMalloc((void **)&s->fx_stage, (size_t)2 * S2R_MAX_BUSES * s->cfg.max_frames * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void **)&f.taps, padded.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void **)&f.line[0], line_bytes);
-    if (e == hipSuccess) e = hipMalloc((void **)&f.line[1], line_bytes);
-    if (e == hipSuccess) e = hipMalloc((void **)&f.partials, (size_t)2 * n_seg * fx_pstride(s) * sizeof(float));
-    // (on the handle's stream, and waited for there: nothing here waits for another handle's kernels)
-    if (e == hipSuccess) e = hipMemcpyAsync(f.taps, padded.data(), padded.size() * sizeof(float), hipMemcpyHostToDevice, s->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(f.line[0], 0, line_bytes, s->stream);    // the history: +0.0 everywhere
-    if (e == hipSuccess) e = hipMemsetAsync(f.line[1], 0, line_bytes, s->stream);
-    { const hipError_t e2 = hipStreamSynchronize(s->stream); if (e == hipSuccess) e = e2; }
-    if (e != hipSuccess) {
-        fx_release(f);
-        return set_err(s, e == hipErrorOutOfMemory ? S2R_ERR_OUT_OF_MEMORY : S2R_ERR_HIP, "s2r_set_bus_reverb: %s", hipGetErrorString(e));
-    }
-    fx_release(s->fx[bus]);                                      // replaces any earlier reverb of the bus
-    s->fx[bus] = f;
+    const hipError_t e = s->post.set_reverb(post_ctx(s), bus, ir_l, ir_r, n_taps, dry, wet);
+    if (e != hipSuccess) return set_err(s, e == hipErrorOutOfMemory ? S2R_ERR_OUT_OF_MEMORY : S2R_ERR_HIP, "s2r_set_bus_reverb: %s", hipGetErrorString(e));
     return S2R_OK;
 }
 
 int s2r_set_bus_reverb_mix(s2r_synth *s, uint32_t bus, float dry, float wet) {
     if (!unit_in_range(dry) || !unit_in_range(wet) || bus >= S2R_MAX_BUSES)
         return set_err(s, S2R_ERR_PATCH_RANGE, "bus %u: dry %g, wet %g: both lie in [0, 1], the bus below %u", bus, (double)dry, (double)wet, S2R_MAX_BUSES);
-    const int rc = fx_handle(s, "s2r_set_bus_reverb_mix");
-    if (rc != S2R_OK) return rc;
-    if (!s->fx[bus].n_taps) return set_err(s, S2R_ERR_INVALID, "bus %u carries no reverb", bus);
-    s->fx[bus].dry = dry; s->fx[bus].wet = wet;
+    S2R_TRY(post_handle(s, "s2r_set_bus_reverb_mix", "bus reverbs are"));
+    if (!s->post.fx[bus].n_taps) return set_err(s, S2R_ERR_INVALID, "bus %u carries no reverb", bus);
+    s->post.fx[bus].dry = dry; s->post.fx[bus].wet = wet;
     return S2R_OK;
 }
 
 int s2r_get_bus_reverb(const s2r_synth *s, uint32_t bus, uint32_t *n_taps, float *dry, float *wet) {
     if (bus >= S2R_MAX_BUSES) return S2R_ERR_PATCH_RANGE;
     if (!s || !s->kids.empty() || s->parent) return S2R_ERR_INVALID;
-    if (n_taps) *n_taps = s->fx[bus].n_taps;
-    if (dry) *dry = s->fx[bus].dry;
-    if (wet) *wet = s->fx[bus].wet;
+    put(n_taps, s->post.fx[bus].n_taps); put(dry, s->post.fx[bus].dry); put(wet, s->post.fx[bus].wet);
     return S2R_OK;
 }
 
-// the history crosses the boundary as frames, oldest first, L then R; the device keeps it planar
+// the history crosses the boundary as frames, oldest first, L then R
 static int fx_history(s2r_synth *s, uint32_t bus, float *get, const float *set, size_t count, const char *who) {
     if (bus >= S2R_MAX_BUSES) return set_err(s, S2R_ERR_PATCH_RANGE, "%s: bus %u, below %u", who, bus, S2R_MAX_BUSES);
-    const int rc = fx_handle(s, who);
-    if (rc != S2R_OK) return rc;
-    s2r_synth::BusFx &f = s->fx[bus];
-    if (!f.n_taps) return set_err(s, S2R_ERR_INVALID, "%s: bus %u carries no reverb", who, bus);
-    const size_t h = f.n_taps - 1u;
+    S2R_TRY(post_handle(s, who, "bus reverbs are"));
+    if (!s->post.fx[bus].n_taps) return set_err(s, S2R_ERR_INVALID, "%s: bus %u carries no reverb", who, bus);
+    const size_t h = s->post.fx[bus].n_taps - 1u;
     if (set ? count != 2 * h : count < 2 * h) return set_err(s, S2R_ERR_INVALID, "%s: the history of bus %u is %zu floats, not %zu", who, bus, 2 * h, count);
     if (h == 0) return S2R_OK;
     if (!get && !set) return set_err(s, S2R_ERR_INVALID, "%s: null buffer", who);
     S2R_QUIESCE(s);
     S2R_HIP(s, hipSetDevice(s->device));
     S2R_HIP(s, hipStreamSynchronize(s->stream));
-    std::vector<float> planar(2 * h);
-    float *line = f.line[f.cur];
-    if (get) {
-        for (int c = 0; c < 2; c++) S2R_HIP(s, hipMemcpyAsync(planar.data() + c * h, line + (size_t)c * f.lstride, h * sizeof(float), hipMemcpyDeviceToHost, s->stream));
-        S2R_HIP(s, hipStreamSynchronize(s->stream));
-        for (size_t i = 0; i < h; i++) { get[2 * i] = planar[i]; get[2 * i + 1] = planar[h + i]; }
-    } else {
-        for (size_t i = 0; i < h; i++) { planar[i] = set[2 * i]; planar[h + i] = set[2 * i + 1]; }
-        for (int c = 0; c < 2; c++) S2R_HIP(s, hipMemcpyAsync(line + (size_t)c * f.lstride, planar.data() + c * h, h * sizeof(float), hipMemcpyHostToDevice, s->stream));
-        S2R_HIP(s, hipStreamSynchronize(s->stream));
-    }
+    S2R_HIP(s, s->post.reverb_history(post_ctx(s), bus, get, set));
     return S2R_OK;
 }
 
@@ -3137,16 +2784,6 @@ int s2r_set_bus_reverb_history(s2r_synth *s, uint32_t bus, const float *lr, size
 }
 
 // ---- program faders ----
-void s2r_fader_gains(float pan, float w, float fader, float pan_shift, float *gl, float *gr) {
-    const float q0 = pan + pan_shift;
-    const float q = q0 < -1.0f ? -1.0f : (q0 > 1.0f ? 1.0f : q0);
-    float al, ar;
-    s2r_pan_gains(q, &al, &ar);
-    const float tl = al * w, tr = ar * w;                        // (-ffp-contract=off; with fader 1 and shift 0: the mixer's a * w, bit for bit)
-    if (gl) *gl = tl * fader;
-    if (gr) *gr = tr * fader;
-}
-
 int s2r_set_program_fader(s2r_synth *s, uint32_t program, float fader, float pan_shift) {
     // (the values first, like s2r_set_program_pan)
     if (!fader_in_range(fader, pan_shift))
@@ -3156,8 +2793,7 @@ int s2r_set_program_fader(s2r_synth *s, uint32_t program, float fader, float pan
     if (program >= s->bank.size()) return set_err(s, S2R_ERR_INVALID, "program %u: the bank holds %zu patches", program, s->bank.size());
     if (fader != 1.0f || pan_shift != 0.0f) {
         S2R_REFUSE_BROKEN(s);
-        const int rc = mixer_begin(s, kMixFader);
-        if (rc != S2R_OK) return rc;
+        S2R_TRY(mixer_begin(s, kMixFader));
     }
     s->mixer.prog[program].fader = fader; s->mixer.prog[program].shift = pan_shift;
     return S2R_OK;
@@ -3189,108 +2825,37 @@ int s2r_fill_buses(s2r_synth *s, float *out, size_t capacity, uint32_t n_buses, 
 }
 
 // ---- the master section ----
-// The rule on the host: the ramps, the sum in bus order from +0.0, the master gain; peaks, and energies by the adjacent-pair tree over
-// blocks of S2R_METER_BLOCK frames, the blocks in order from +0.0.  Every product and every sum rounded on its own.
-static float master_energy(const float *v, uint32_t frames) {     // v: one channel of an interleaved pair (stride 2)
-    float total = 0.0f;
-    for (uint32_t k0 = 0; k0 < frames; k0 += S2R_METER_BLOCK) {
-        float sq[S2R_METER_BLOCK];
-        for (uint32_t j = 0; j < S2R_METER_BLOCK; j++) {
-            const float x = k0 + j < frames ? v[2 * (size_t)(k0 + j)] : 0.0f;
-            sq[j] = x * x;
-        }
-        for (uint32_t n = S2R_METER_BLOCK / 2u; n >= 1u; n /= 2u)
-            for (uint32_t j = 0; j < n; j++) sq[j] = sq[2 * j] + sq[2 * j + 1];
-        total = total + sq[0];
-    }
-    return total;
-}
-
-static float master_peak(const float *v, uint32_t frames) {
-    float peak = 0.0f;
-    for (uint32_t i = 0; i < frames; i++) { const float a = std::fabs(v[2 * (size_t)i]); peak = a > peak ? a : peak; }
-    return peak;
-}
-
-int s2r_master_reference(const float *stems, uint32_t n_buses, uint32_t frames, const float *r0, const float *r1, float m0, float m1,
-                         float *master_lr, float *peak, float *energy) {
-    if (!unit_in_range(m0) || !unit_in_range(m1)) return S2R_ERR_PATCH_RANGE;
-    if (n_buses == 0 || n_buses > S2R_MAX_BUSES || !r0 || !r1 || (!stems && frames)) return S2R_ERR_INVALID;
-    for (uint32_t b = 0; b < n_buses; b++) if (!unit_in_range(r0[b]) || !unit_in_range(r1[b])) return S2R_ERR_PATCH_RANGE;
-    const float fn = (float)frames;
-    float dr[S2R_MAX_BUSES];
-    for (uint32_t b = 0; b < n_buses; b++) { const float d = r1[b] - r0[b]; dr[b] = d / fn; }
-    const float dm0 = m1 - m0, dm = dm0 / fn;
-    std::vector<float> own;
-    if (!master_lr) { own.resize(2 * (size_t)frames); master_lr = own.data(); }
-    for (uint32_t i = 0; i < frames; i++) {
-        const float fi = (float)i;
-        for (uint32_t c = 0; c < 2; c++) {
-            float t = 0.0f;
-            for (uint32_t b = 0; b < n_buses; b++) {
-                const float step = fi * dr[b];
-                const float r = r0[b] + step;
-                const float p = r * stems[((size_t)b * frames + i) * 2 + c];
-                t = t + p;
-            }
-            const float step = fi * dm;
-            const float g = m0 + step;
-            master_lr[2 * (size_t)i + c] = g * t;
-        }
-    }
-    for (uint32_t b = 0; b <= n_buses; b++)
-        for (uint32_t c = 0; c < 2; c++) {
-            const float *v = (b < n_buses ? stems + (size_t)b * frames * 2 : master_lr) + c;
-            if (peak) peak[2 * b + c] = master_peak(v, frames);
-            if (energy) energy[2 * b + c] = master_energy(v, frames);
-        }
-    return S2R_OK;
-}
-
-static int master_handle(const s2r_synth *s, const char *who) {
-    if (!s) return S2R_ERR_INVALID;
-    if (!s->kids.empty() || s->parent) return set_err(const_cast<s2r_synth *>(s), S2R_ERR_INVALID, "%s: the master section is kept by single-device handles, not by a device list", who);
-    return S2R_OK;
-}
-
 int s2r_set_bus_return(s2r_synth *s, uint32_t bus, float level) {
-    // (the values first, like s2r_set_bus_reverb_mix)
     if (!unit_in_range(level) || bus >= S2R_MAX_BUSES)
         return set_err(s, S2R_ERR_PATCH_RANGE, "bus %u: return %g: the level lies in [0, 1], the bus below %u", bus, (double)level, S2R_MAX_BUSES);
-    const int rc = master_handle(s, "s2r_set_bus_return");
-    if (rc != S2R_OK) return rc;
-    s->master.ret[bus] = level;
+    S2R_TRY(post_handle(s, "s2r_set_bus_return", "the master section is"));
+    s->post.master.ret[bus] = level;
     return S2R_OK;
 }
 
 int s2r_get_bus_return(const s2r_synth *s, uint32_t bus, float *level, float *applied) {
     if (bus >= S2R_MAX_BUSES) return S2R_ERR_PATCH_RANGE;
     if (!s || !s->kids.empty() || s->parent) return S2R_ERR_INVALID;
-    if (level) *level = s->master.ret[bus];
-    if (applied) *applied = s->master.ret_app[bus];
+    put(level, s->post.master.ret[bus]); put(applied, s->post.master.ret_app[bus]);
     return S2R_OK;
 }
 
 int s2r_set_master_fader(s2r_synth *s, float level) {
     if (!unit_in_range(level)) return set_err(s, S2R_ERR_PATCH_RANGE, "master fader %g: the level lies in [0, 1]", (double)level);
-    const int rc = master_handle(s, "s2r_set_master_fader");
-    if (rc != S2R_OK) return rc;
-    s->master.fader = level;
+    S2R_TRY(post_handle(s, "s2r_set_master_fader", "the master section is"));
+    s->post.master.fader = level;
     return S2R_OK;
 }
 
 int s2r_get_master_fader(const s2r_synth *s, float *level, float *applied) {
     if (!s || !s->kids.empty() || s->parent) return S2R_ERR_INVALID;
-    if (level) *level = s->master.fader;
-    if (applied) *applied = s->master.fader_app;
+    put(level, s->post.master.fader); put(applied, s->post.master.fader_app);
     return S2R_OK;
 }
 
 int s2r_snap_master(s2r_synth *s) {
-    const int rc = master_handle(s, "s2r_snap_master");
-    if (rc != S2R_OK) return rc;
-    for (uint32_t b = 0; b < S2R_MAX_BUSES; b++) s->master.ret_app[b] = s->master.ret[b];
-    s->master.fader_app = s->master.fader;
+    S2R_TRY(post_handle(s, "s2r_snap_master", "the master section is"));
+    s->post.snap_master();
     return S2R_OK;
 }
 
@@ -3301,136 +2866,65 @@ int s2r_fill_master(s2r_synth *s, float *master_lr, float *stems, size_t stems_c
 }
 
 int s2r_get_meters(const s2r_synth *s, uint32_t *n_buses, float *peak, float *energy, size_t capacity) {
-    if (!s || !s->kids.empty() || s->parent || !s->master.metered) return S2R_ERR_INVALID;
-    const size_t n = ((size_t)s->master.meter_buses + 1u) * 2u;
+    if (!s || !s->kids.empty() || s->parent || !s->post.master.metered) return S2R_ERR_INVALID;
+    const S2rPostChain::Master &ms = s->post.master;
+    const size_t n = ((size_t)ms.meter_buses + 1u) * 2u;
     if (capacity < n) return S2R_ERR_INVALID;
-    if (n_buses) *n_buses = s->master.meter_buses;
-    if (peak) std::memcpy(peak, s->master.peak, n * sizeof(float));
-    if (energy) std::memcpy(energy, s->master.energy, n * sizeof(float));
+    if (n_buses) *n_buses = ms.meter_buses;
+    if (peak) std::memcpy(peak, ms.peak, n * sizeof(float));
+    if (energy) std::memcpy(energy, ms.energy, n * sizeof(float));
     return S2R_OK;
 }
 
 // ---- the master limiter ----
-static bool limiter_in_range(float ceiling, uint32_t lookahead, uint32_t hold) {
-    const float lo = std::ldexp(1.0f, -S2R_LIMITER_CEILING_LOG2), hi = std::ldexp(1.0f, S2R_LIMITER_CEILING_LOG2);
-    return ceiling >= lo && ceiling <= hi && lookahead >= 1u && lookahead <= S2R_LIMITER_MAX_LOOKAHEAD && hold <= S2R_LIMITER_MAX_HOLD;   // (a NaN fails both comparisons)
-}
-
-// The rule on the host, in plain loops: the gains, the minimum of every window, the sum newest first, the division, the two minima
-// and the clamp.  It shares S2R_LIMITER_MAX_LOOKAHEAD, S2R_LIMITER_MAX_HOLD and S2R_LIMITER_CEILING_LOG2 with the kernel, nothing else.
-int s2r_limiter_reference(const float *x, uint32_t frames, float ceiling, uint32_t lookahead, uint32_t hold, float *xh, float *gh,
-                          float *y, float *gain) {
-    if (!limiter_in_range(ceiling, lookahead, hold)) return S2R_ERR_PATCH_RANGE;
-    if ((!x && frames) || !xh || !gh) return S2R_ERR_INVALID;
-    const size_t L = lookahead, H = hold, G = 2 * L + H, N = frames;
-    const float c = ceiling, w = (float)(lookahead + 1u);
-    std::vector<float> ge(G + N), xe(2 * (L + N)), m(L + N);
-    std::memcpy(ge.data(), gh, G * sizeof(float));
-    std::memcpy(xe.data(), xh, 2 * L * sizeof(float));
-    if (N) std::memcpy(xe.data() + 2 * L, x, 2 * N * sizeof(float));
-    for (size_t n = 0; n < N; n++) {
-        const float al = std::fabs(x[2 * n]), ar = std::fabs(x[2 * n + 1]);
-        const float p = al > ar ? al : ar;
-        ge[G + n] = p > c ? c / p : 1.0f;
-    }
-    for (size_t j = 0; j < L + N; j++) {                         // m[j] is m[n = j - L]: the minimum of g[n - L - H .. n], ge[j .. j + L + H]
-        float v = ge[j];
-        for (size_t k = 1; k <= L + H; k++) v = ge[j + k] < v ? ge[j + k] : v;
-        m[j] = v;
-    }
-    for (size_t n = 0; n < N; n++) {
-        float acc = 0.0f;
-        for (size_t k = 0; k <= L; k++) acc = acc + m[n + L - k];
-        const float s = acc / w, gd = ge[G - L + n];
-        const float sp = s < gd ? s : gd;
-        if (gain) gain[n] = sp;
-        if (y)
-            for (size_t ch = 0; ch < 2; ch++) {
-                float v = xe[2 * n + ch] * sp;
-                v = v < -c ? -c : v;
-                y[2 * n + ch] = v > c ? c : v;
-            }
-    }
-    std::memcpy(gh, ge.data() + N, G * sizeof(float));
-    std::memcpy(xh, xe.data() + 2 * N, 2 * L * sizeof(float));
-    return S2R_OK;
-}
-
-static int limiter_handle(const s2r_synth *s, const char *who) {
-    if (!s) return S2R_ERR_INVALID;
-    if (!s->kids.empty() || s->parent) return set_err(const_cast<s2r_synth *>(s), S2R_ERR_INVALID, "%s: the master limiter is kept by single-device handles, not by a device list", who);
-    return S2R_OK;
-}
-
 int s2r_set_master_limiter(s2r_synth *s, float ceiling, uint32_t lookahead, uint32_t hold) {
-    // (the values first, like s2r_set_bus_return)
     if (!limiter_in_range(ceiling, lookahead, hold))
         return set_err(s, S2R_ERR_PATCH_RANGE, "master limiter: ceiling %g, lookahead %u, hold %u: the ceiling lies in [2^-%d, 2^%d], the lookahead in 1 .. %u, the hold in 0 .. %u",
                        (double)ceiling, lookahead, hold, S2R_LIMITER_CEILING_LOG2, S2R_LIMITER_CEILING_LOG2, S2R_LIMITER_MAX_LOOKAHEAD, S2R_LIMITER_MAX_HOLD);
-    const int rc = limiter_handle(s, "s2r_set_master_limiter");
-    if (rc != S2R_OK) return rc;
-    s2r_synth::Limiter &lm = s->limiter;
-    const bool reset = lm.lookahead != lookahead || lm.hold != hold;     // (off is a lookahead of 0: it differs)
-    lm.ceiling = ceiling; lm.lookahead = lookahead; lm.hold = hold;
-    if (reset) limiter_reset(lm);
+    S2R_TRY(post_handle(s, "s2r_set_master_limiter", "the master limiter is"));
+    s->post.set_limiter(ceiling, lookahead, hold);
     return S2R_OK;
 }
 
 int s2r_clear_master_limiter(s2r_synth *s) {
-    const int rc = limiter_handle(s, "s2r_clear_master_limiter");
-    if (rc != S2R_OK) return rc;
-    s2r_synth::Limiter &lm = s->limiter;
-    lm.ceiling = 0.0f; lm.lookahead = 0; lm.hold = 0;
-    lm.host.clear(); lm.host_valid = false;
+    S2R_TRY(post_handle(s, "s2r_clear_master_limiter", "the master limiter is"));
+    s->post.set_limiter(0.0f, 0, 0);
     return S2R_OK;
 }
 
 int s2r_get_master_limiter(const s2r_synth *s, float *ceiling, uint32_t *lookahead, uint32_t *hold) {
     if (!s || !s->kids.empty() || s->parent) return S2R_ERR_INVALID;
-    if (ceiling) *ceiling = s->limiter.ceiling;
-    if (lookahead) *lookahead = s->limiter.lookahead;
-    if (hold) *hold = s->limiter.hold;
+    put(ceiling, s->post.limiter.ceiling); put(lookahead, s->post.limiter.lookahead); put(hold, s->post.limiter.hold);
     return S2R_OK;
 }
 
 static int limiter_state(s2r_synth *s, float *get_x, float *get_g, const float *set_x, const float *set_g, size_t n_x, size_t n_g, const char *who) {
-    const int rc = limiter_handle(s, who);
-    if (rc != S2R_OK) return rc;
-    s2r_synth::Limiter &lm = s->limiter;
+    S2R_TRY(post_handle(s, who, "the master limiter is"));
+    S2rPostChain::Limiter &lm = s->post.limiter;
     if (!lm.lookahead) return set_err(s, S2R_ERR_INVALID, "%s: no master limiter is set", who);
-    const size_t nx = 2u * (size_t)lm.lookahead, ng = limiter_gains(lm.lookahead, lm.hold);
+    const size_t nx = lm.n_x(), ng = lm.n_g();
     const bool set = set_x || set_g;
     if (set ? (n_x != nx || n_g != ng) : (n_x < nx || n_g < ng))
         return set_err(s, S2R_ERR_INVALID, "%s: the state is %zu and %zu floats, not %zu and %zu", who, nx, ng, n_x, n_g);
     if (set ? (!set_x || !set_g) : (!get_x || !get_g)) return set_err(s, S2R_ERR_INVALID, "%s: null buffer", who);
     if (set) {
         for (size_t i = 0; i < ng; i++)
-            if (!(set_g[i] >= 0.0f && set_g[i] <= 1.0f)) return set_err(s, S2R_ERR_PATCH_RANGE, "%s: gain %zu is %g, outside [0, 1]", who, i, (double)set_g[i]);
-        lm.host.assign(set_x, set_x + nx);
-        lm.host.insert(lm.host.end(), set_g, set_g + ng);
-        lm.host_valid = true;
+            if (!unit_in_range(set_g[i])) return set_err(s, S2R_ERR_PATCH_RANGE, "%s: gain %zu is %g, outside [0, 1]", who, i, (double)set_g[i]);
+        s->post.set_limiter_state(set_x, set_g);
         return S2R_OK;
     }
     if (!lm.host_valid) {                                        // the device holds it: fetch it once, and keep it until the next fill
         if (s->ring_count) return set_err(s, S2R_ERR_INVALID, "%s with fills of s2r_fill_begin in flight: s2r_fill_end first", who);
         S2R_QUIESCE(s);
         S2R_HIP(s, hipSetDevice(s->device));
-        std::vector<float> st(nx + ng);
-        const float *cur = lm.state[lm.cur];
-        S2R_HIP(s, hipMemcpyAsync(st.data(), cur, nx * sizeof(float), hipMemcpyDeviceToHost, s->stream));
-        S2R_HIP(s, hipMemcpyAsync(st.data() + nx, cur + kLimXh, ng * sizeof(float), hipMemcpyDeviceToHost, s->stream));
-        S2R_HIP(s, hipStreamSynchronize(s->stream));
-        lm.host.swap(st);
-        lm.host_valid = true;
+        S2R_HIP(s, s->post.fetch_limiter_state(post_ctx(s)));
     }
     std::memcpy(get_x, lm.host.data(), nx * sizeof(float));
     std::memcpy(get_g, lm.host.data() + nx, ng * sizeof(float));
     return S2R_OK;
 }
 
-int s2r_get_limiter_state(s2r_synth *s, float *xh, size_t n_x, float *gh, size_t n_g) {
-    return limiter_state(s, xh, gh, nullptr, nullptr, n_x, n_g, "s2r_get_limiter_state");
-}
+int s2r_get_limiter_state(s2r_synth *s, float *xh, size_t n_x, float *gh, size_t n_g) { return limiter_state(s, xh, gh, nullptr, nullptr, n_x, n_g, "s2r_get_limiter_state"); }
 
 int s2r_set_limiter_state(s2r_synth *s, const float *xh, size_t n_x, const float *gh, size_t n_g) {
     if (!s) return S2R_ERR_INVALID;
@@ -3439,9 +2933,8 @@ int s2r_set_limiter_state(s2r_synth *s, const float *xh, size_t n_x, const float
 }
 
 int s2r_get_limiter_meters(const s2r_synth *s, float *min_gain, float *out_peak) {
-    if (!s || !s->kids.empty() || s->parent || !s->limiter.metered) return S2R_ERR_INVALID;
-    if (min_gain) *min_gain = s->limiter.min_gain;
-    if (out_peak) *out_peak = s->limiter.out_peak;
+    if (!s || !s->kids.empty() || s->parent || !s->post.limiter.metered) return S2R_ERR_INVALID;
+    put(min_gain, s->post.limiter.min_gain); put(out_peak, s->post.limiter.out_peak);
     return S2R_OK;
 }
 
@@ -3451,8 +2944,7 @@ int s2r_fill_oversampled(s2r_synth *s, float *mono_out, size_t frames, uint32_t 
     S2R_QUIESCE(s);
     if (!s->kids.empty() && s->ring_count) return set_err(s, S2R_ERR_INVALID, "a device-list handle takes no synchronous fill while fills are in flight: s2r_fill_end first");
     const size_t os_frames = frames * S2R_OVERSAMPLE;
-    int rc = check_fill(s, os_frames, sample_rate_hz * S2R_OVERSAMPLE);
-    if (rc != S2R_OK) return rc;
+    S2R_TRY(check_fill(s, os_frames, sample_rate_hz * S2R_OVERSAMPLE));
     if (frames == 0) return S2R_OK;
     if (!mono_out) return set_err(s, S2R_ERR_INVALID, "null output buffer");
     S2R_HIP(s, hipSetDevice(s->device));
@@ -3474,8 +2966,7 @@ int s2r_fill_oversampled(s2r_synth *s, float *mono_out, size_t frames, uint32_t 
         S2R_HIP(s, hipMalloc((void **)&s->os_buf, ((size_t)(kTaps - 1) + s->cfg.max_frames) * sizeof(float)));
         S2R_HIP(s, hipMemsetAsync(s->os_buf, 0, ((size_t)(kTaps - 1) + s->cfg.max_frames) * sizeof(float), s->stream));
     }
-    rc = enqueue_root(s, os_frames, sample_rate_hz * S2R_OVERSAMPLE, s->os_buf + (kTaps - 1), false);
-    if (rc != S2R_OK) return rc;
+    S2R_TRY(enqueue_root(s, os_frames, sample_rate_hz * S2R_OVERSAMPLE, s->os_buf + (kTaps - 1), false));
     S2R_HIP(s, s2r_launch_decimate4(s->os_buf, s->os_taps, (uint32_t)frames, s->out_host_dev, s->stream));
     S2R_HIP(s, hipStreamSynchronize(s->stream));
     std::memcpy(mono_out, s->out_host, frames * sizeof(float));
@@ -3483,8 +2974,7 @@ int s2r_fill_oversampled(s2r_synth *s, float *mono_out, size_t frames, uint32_t 
 }
 
 int s2r_fill_device(s2r_synth *s, float *dev_partial_out, size_t frames, uint32_t sample_rate_hz, void *hip_stream) {
-    int rc = check_fill(s, frames, sample_rate_hz);
-    if (rc != S2R_OK) return rc;
+    S2R_TRY(check_fill(s, frames, sample_rate_hz));
     if (frames == 0) return S2R_OK;
     if (!dev_partial_out) return set_err(s, S2R_ERR_INVALID, "null device output buffer");
     if (!s->kids.empty()) return set_err(s, S2R_ERR_INVALID, "s2r_fill_device is the per-shard building block: a device-list handle combines its shards itself (s2r_fill)");
@@ -3494,8 +2984,7 @@ int s2r_fill_device(s2r_synth *s, float *dev_partial_out, size_t frames, uint32_
 }
 
 int s2r_fill_device_root(s2r_synth *s, float *dev_out, size_t frames, uint32_t sample_rate_hz, void *hip_stream) {
-    int rc = check_fill(s, frames, sample_rate_hz);
-    if (rc != S2R_OK) return rc;
+    S2R_TRY(check_fill(s, frames, sample_rate_hz));
     if (frames == 0) return S2R_OK;
     if (!dev_out) return set_err(s, S2R_ERR_INVALID, "null device output buffer");
     if (!s->kids.empty()) return set_err(s, S2R_ERR_INVALID, "s2r_fill_device_root takes a single-device handle");
@@ -3510,8 +2999,7 @@ int s2r_sum_partials_device(const float *dev_rows, uint32_t n_rows, size_t frame
 }
 
 int s2r_render_voices(s2r_synth *s, float *per_voice_out, size_t frames, uint32_t sample_rate_hz) {
-    int rc = check_fill(s, frames, sample_rate_hz);
-    if (rc != S2R_OK) return rc;
+    S2R_TRY(check_fill(s, frames, sample_rate_hz));
     if (frames == 0) return S2R_OK;
     if (!per_voice_out) return set_err(s, S2R_ERR_INVALID, "null output buffer");
     fold_frame0_records(s);
@@ -3520,8 +3008,7 @@ int s2r_render_voices(s2r_synth *s, float *per_voice_out, size_t frames, uint32_
     if (!s->kids.empty()) {                       // every shard's rows, put back into pool order
         if (s->ring_count) return set_err(s, S2R_ERR_INVALID, "a device-list handle takes no synchronous fill while fills are in flight: s2r_fill_end first");
         for (s2r_synth *kid : s->kids) if (!kid->tpending.empty()) return set_err(s, S2R_ERR_INVALID, "s2r_render_voices does not take timed events; use s2r_fill");
-        rc = enqueue_multi(s, frames, sample_rate_hz, nullptr, false, per_voice_out);
-        if (rc != S2R_OK) return rc;
+        S2R_TRY(enqueue_multi(s, frames, sample_rate_hz, nullptr, false, per_voice_out));
         std::vector<float> tmp;
         for (s2r_synth *kid : s->kids) {
             S2R_HIP(s, hipSetDevice(kid->device));
@@ -3540,8 +3027,7 @@ int s2r_render_voices(s2r_synth *s, float *per_voice_out, size_t frames, uint32_
         S2R_HIP(s, hipMalloc((void **)&s->per_voice_dev, need * sizeof(float)));
         s->per_voice_cap = need;
     }
-    rc = enqueue_fill(s, frames, sample_rate_hz, s->stream, nullptr, false, false, s->per_voice_dev);
-    if (rc != S2R_OK) return rc;
+    S2R_TRY(enqueue_fill(s, frames, sample_rate_hz, s->stream, nullptr, false, false, s->per_voice_dev));
     S2R_HIP(s, hipMemcpyAsync(per_voice_out, s->per_voice_dev, need * sizeof(float), hipMemcpyDeviceToHost, s->stream));
     S2R_HIP(s, hipStreamSynchronize(s->stream));
     return S2R_OK;
@@ -3564,8 +3050,7 @@ int s2r_export_state(s2r_synth *s, s2r_voice_state *voices) {
     S2R_HIP(s, hipSetDevice(s->device));
     if (!s->tpending.empty()) return set_err(s, S2R_ERR_INVALID, "export_state with timed events pending: fill first");
     EventSlot *ts = nullptr; const S2rTimedEvent *td = nullptr;
-    int rc = flush_events(s, s->stream, &ts, &td);
-    if (rc != S2R_OK) return rc;
+    S2R_TRY(flush_events(s, s->stream, &ts, &td));
     const size_t pv = s->padded_voices;
     std::vector<uint32_t> h(pv * kVoiceWords);
     S2R_HIP(s, hipMemcpyAsync(h.data(), s->voice_mem, pv * kVoiceWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
@@ -3669,16 +3154,13 @@ int s2r_process_layers(s2r_synth *s, s2r_layer_call *layers, uint32_t n_layers, 
         v.pitch_hz = c.pitch_hz; v.phase_accum = c.phase_accum; v.lpf_last = c.lpf_last; v.noise_seed = c.noise_seed; v.velocity = 1.0f;
         v.filt_x1 = c.filt_x1; v.filt_x2 = c.filt_x2; v.filt_y1 = c.filt_y1; v.filt_y2 = c.filt_y2; v.osc_z = c.osc_z;
     }
-    int rc = s2r_import_state(s, st.data());
-    if (rc != S2R_OK) return rc;
+    S2R_TRY(s2r_import_state(s, st.data()));
     if (frames && n_layers) {
         std::vector<float> rows((size_t)total * frames);
-        rc = s2r_render_voices(s, rows.data(), frames, sample_rate_hz);
-        if (rc != S2R_OK) return rc;
+        S2R_TRY(s2r_render_voices(s, rows.data(), frames, sample_rate_hz));
         std::memcpy(bufs, rows.data(), (size_t)n_layers * frames * sizeof(float));
     }
-    rc = s2r_export_state(s, st.data());
-    if (rc != S2R_OK) return rc;
+    S2R_TRY(s2r_export_state(s, st.data()));
     for (uint32_t i = 0; i < n_layers; i++) {
         s2r_layer_call &c = layers[i];
         const s2r_voice_state &v = st[i];
@@ -3881,11 +3363,11 @@ extern "C" uint32_t s2r_debug_pan_slice(const s2r_synth *s) { return s ? s->pan_
 // ... and of the bus mixdown's kernels in the last s2r_fill_buses (tools/bus_time.py)
 extern "C" float s2r_debug_bus_mix_ms(const s2r_synth *s) { return s && s->timing ? s->bus_mix_ms : -1.0f; }
 // ... and of the buses' reverb kernels in that fill: 0 when it ran none (tools/reverb_time.py)
-extern "C" float s2r_debug_bus_fx_ms(const s2r_synth *s) { return s && s->timing ? s->bus_fx_ms : -1.0f; }
+extern "C" float s2r_debug_bus_fx_ms(const s2r_synth *s) { return s && s->timing ? s->post.fx_timer.ms : -1.0f; }
 // ... and of the master kernel in the last s2r_fill_master (tools/master_time.py)
-extern "C" float s2r_debug_master_ms(const s2r_synth *s) { return s && s->timing ? s->master.ms : -1.0f; }
+extern "C" float s2r_debug_master_ms(const s2r_synth *s) { return s && s->timing ? s->post.master.timer.ms : -1.0f; }
 // ... and of the limiter kernel in that fill: 0 when it ran none (tools/limiter_time.py)
-extern "C" float s2r_debug_limiter_ms(const s2r_synth *s) { return s && s->timing ? s->limiter.ms : -1.0f; }
+extern "C" float s2r_debug_limiter_ms(const s2r_synth *s) { return s && s->timing ? s->post.limiter.timer.ms : -1.0f; }
 
 extern "C" uint32_t s2r_debug_read_stamps(s2r_synth *s, unsigned long long *out, uint32_t max_waves) {
 #if defined(S2R_STAMPS)

@@ -1,0 +1,137 @@
+// s2r_rules.cpp — the rules of libs2r that need neither a handle nor HIP: the voice mixer's gains, and the reverb, the master section
+// and the master limiter in plain host loops (s2r.h states each rule).  Plain C++17, -ffp-contract=off: every operation rounded on its own.
+#include <cstddef>
+#include <cstring>
+#include <vector>
+
+#include "s2r_rules.h"
+
+extern "C" {
+
+// ---- the voice mixer's gains: the rules are s2r_rules.h's, exported under their names ----
+float s2r_voice_pan(float pan, float key_spread, uint8_t note) { return rule_voice_pan(pan, key_spread, note); }
+void s2r_pan_gains(float p, float *gl, float *gr) { rule_pan_gains(p, gl, gr); }
+float s2r_voice_gain(float level, float velocity_sens, float velocity) { return rule_voice_gain(level, velocity_sens, velocity); }
+void s2r_fader_gains(float pan, float w, float fader, float pan_shift, float *gl, float *gr) { rule_fader_gains(pan, w, fader, pan_shift, gl, gr); }
+float s2r_send_gain(float g, float send) { return g * send; }
+
+// ---- per-bus convolution reverb, one channel ----
+int s2r_reverb_reference(const float *ir, uint32_t n_taps, const float *x_with_history, uint32_t frames, float dry, float wet, float *out) {
+    if (!unit_in_range(dry) || !unit_in_range(wet) || n_taps > S2R_MAX_IR_TAPS) return S2R_ERR_PATCH_RANGE;
+    if (!ir || n_taps == 0 || !x_with_history || (!out && frames)) return S2R_ERR_INVALID;
+    for (uint32_t k = 0; k < n_taps; k++) if (!std::isfinite(ir[k])) return S2R_ERR_PATCH_RANGE;
+    for (uint32_t i = 0; i < frames; i++) {
+        const float *x = x_with_history + (n_taps - 1u) + i;     // x[-k]: the dry sample k frames before frame i
+        float r = 0.0f;
+        for (uint32_t k0 = 0; k0 < n_taps; k0 += S2R_IR_SEGMENT) {
+            const uint32_t k1 = k0 + S2R_IR_SEGMENT < n_taps ? k0 + S2R_IR_SEGMENT : n_taps;
+            float p = 0.0f;
+            for (uint32_t k = k0; k < k1; k++) {
+                const float t = ir[k] * x[-(ptrdiff_t)k];
+                p = p + t;
+            }
+            r = r + p;
+        }
+        const float d = dry * x[0], w = wet * r;
+        out[i] = d + w;
+    }
+    return S2R_OK;
+}
+
+// ---- the master section: energies by the adjacent-pair tree over blocks of S2R_METER_BLOCK frames ----
+static float master_energy(const float *v, uint32_t frames) {     // v: one channel of an interleaved pair (stride 2)
+    float total = 0.0f;
+    for (uint32_t k0 = 0; k0 < frames; k0 += S2R_METER_BLOCK) {
+        float sq[S2R_METER_BLOCK];
+        for (uint32_t j = 0; j < S2R_METER_BLOCK; j++) {
+            const float x = k0 + j < frames ? v[2 * (size_t)(k0 + j)] : 0.0f;
+            sq[j] = x * x;
+        }
+        for (uint32_t n = S2R_METER_BLOCK / 2u; n >= 1u; n /= 2u)
+            for (uint32_t j = 0; j < n; j++) sq[j] = sq[2 * j] + sq[2 * j + 1];
+        total = total + sq[0];
+    }
+    return total;
+}
+
+static float master_peak(const float *v, uint32_t frames) {
+    float peak = 0.0f;
+    for (uint32_t i = 0; i < frames; i++) { const float a = std::fabs(v[2 * (size_t)i]); peak = a > peak ? a : peak; }
+    return peak;
+}
+
+int s2r_master_reference(const float *stems, uint32_t n_buses, uint32_t frames, const float *r0, const float *r1, float m0, float m1,
+                         float *master_lr, float *peak, float *energy) {
+    if (!unit_in_range(m0) || !unit_in_range(m1)) return S2R_ERR_PATCH_RANGE;
+    if (n_buses == 0 || n_buses > S2R_MAX_BUSES || !r0 || !r1 || (!stems && frames)) return S2R_ERR_INVALID;
+    for (uint32_t b = 0; b < n_buses; b++) if (!unit_in_range(r0[b]) || !unit_in_range(r1[b])) return S2R_ERR_PATCH_RANGE;
+    const float fn = (float)frames;
+    float dr[S2R_MAX_BUSES];
+    for (uint32_t b = 0; b < n_buses; b++) { const float d = r1[b] - r0[b]; dr[b] = d / fn; }
+    const float dm0 = m1 - m0, dm = dm0 / fn;
+    std::vector<float> own;
+    if (!master_lr) { own.resize(2 * (size_t)frames); master_lr = own.data(); }
+    for (uint32_t i = 0; i < frames; i++) {
+        const float fi = (float)i;
+        for (uint32_t c = 0; c < 2; c++) {
+            float t = 0.0f;
+            for (uint32_t b = 0; b < n_buses; b++) {
+                const float step = fi * dr[b];
+                const float r = r0[b] + step;
+                const float p = r * stems[((size_t)b * frames + i) * 2 + c];
+                t = t + p;
+            }
+            const float step = fi * dm;
+            const float g = m0 + step;
+            master_lr[2 * (size_t)i + c] = g * t;
+        }
+    }
+    for (uint32_t b = 0; b <= n_buses; b++)
+        for (uint32_t c = 0; c < 2; c++) {
+            const float *v = (b < n_buses ? stems + (size_t)b * frames * 2 : master_lr) + c;
+            if (peak) peak[2 * b + c] = master_peak(v, frames);
+            if (energy) energy[2 * b + c] = master_energy(v, frames);
+        }
+    return S2R_OK;
+}
+
+// ---- the master limiter: it shares its three constants with the kernel, nothing else ----
+int s2r_limiter_reference(const float *x, uint32_t frames, float ceiling, uint32_t lookahead, uint32_t hold, float *xh, float *gh,
+                          float *y, float *gain) {
+    if (!limiter_in_range(ceiling, lookahead, hold)) return S2R_ERR_PATCH_RANGE;
+    if ((!x && frames) || !xh || !gh) return S2R_ERR_INVALID;
+    const size_t L = lookahead, H = hold, G = 2 * L + H, N = frames;
+    const float c = ceiling, w = (float)(lookahead + 1u);
+    std::vector<float> ge(G + N), xe(2 * (L + N)), m(L + N);
+    std::memcpy(ge.data(), gh, G * sizeof(float));
+    std::memcpy(xe.data(), xh, 2 * L * sizeof(float));
+    if (N) std::memcpy(xe.data() + 2 * L, x, 2 * N * sizeof(float));
+    for (size_t n = 0; n < N; n++) {
+        const float al = std::fabs(x[2 * n]), ar = std::fabs(x[2 * n + 1]);
+        const float p = al > ar ? al : ar;
+        ge[G + n] = p > c ? c / p : 1.0f;
+    }
+    for (size_t j = 0; j < L + N; j++) {                         // m[j] is m[n = j - L]: the minimum of g[n - L - H .. n], ge[j .. j + L + H]
+        float v = ge[j];
+        for (size_t k = 1; k <= L + H; k++) v = ge[j + k] < v ? ge[j + k] : v;
+        m[j] = v;
+    }
+    for (size_t n = 0; n < N; n++) {
+        float acc = 0.0f;
+        for (size_t k = 0; k <= L; k++) acc = acc + m[n + L - k];
+        const float s = acc / w, gd = ge[G - L + n];
+        const float sp = s < gd ? s : gd;
+        if (gain) gain[n] = sp;
+        if (y)
+            for (size_t ch = 0; ch < 2; ch++) {
+                float v = xe[2 * n + ch] * sp;
+                v = v < -c ? -c : v;
+                y[2 * n + ch] = v > c ? c : v;
+            }
+    }
+    std::memcpy(gh, ge.data() + N, G * sizeof(float));
+    std::memcpy(xh, xe.data() + 2 * N, 2 * L * sizeof(float));
+    return S2R_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,26 @@
+"""ASan + UBSan over the handle-free rule functions (csrc/s2r_rules.cpp: the reverb, master and limiter references and the mixer's
+gain rules), which need neither a handle nor HIP: the file is compiled by plain g++ beside a small program of its own
+(tests/native/san_rules.cpp) and run as a child process, with no preload of any kind."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
+def test_rule_functions_under_asan_ubsan(tmp_path):
+    """the three references at their edges — frames 0 and 1; K = 1, S2R_IR_SEGMENT and S2R_IR_SEGMENT + 1; 1 and S2R_MAX_BUSES buses;
+    lookahead 1 and the maximum, hold 0 and the maximum; null optional outputs — on buffers of exactly the stated sizes, and the
+    answers that need no model: a one-tap response of 1.0 with dry 0 and wet 1 returns its input, a limiter input under the ceiling
+    comes out L frames late and otherwise unchanged, returns and fader at 1 make the master the in-order sum"""
+    exe = str(tmp_path / "san_rules")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "synth2_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "native", "san_rules.cpp"),
+                           os.path.join(ROOT, "synth2_amd", "csrc", "s2r_rules.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-3000:]
+    assert "rules ok" in out.stdout
