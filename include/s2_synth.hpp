@@ -136,6 +136,23 @@ class Synth {
     static int reverb_reference(const float *ir, uint32_t n_taps, const float *x_with_history, uint32_t frames, float dry, float wet, float *out) {
         return s2r_reverb_reference(ir, n_taps, x_with_history, frames, dry, wet, out);
     }
+    // per-bus feedback delay in front of the bus's reverb (build-defined; s2r.h: s2r_set_bus_delay): delay_frames in 1 ..
+    // S2R_MAX_DELAY_FRAMES, feedback and cross in [-1, 1] with |feedback| + |cross| <= 1, dry and wet in [0, 1]; in sample_buses and
+    // sample_master only
+    void set_bus_delay(uint32_t bus, uint32_t delay_frames, float feedback = 0.0f, float cross = 0.0f, float dry = 1.0f, float wet = 1.0f) {
+        check(s2r_set_bus_delay(h_, bus, delay_frames, feedback, cross, dry, wet));
+    }
+    void clear_bus_delay(uint32_t bus) { check(s2r_set_bus_delay(h_, bus, 0, 0.0f, 0.0f, 0.0f, 0.0f)); }
+    void set_bus_delay_mix(uint32_t bus, float feedback, float cross, float dry, float wet) { check(s2r_set_bus_delay_mix(h_, bus, feedback, cross, dry, wet)); }
+    void get_bus_delay(uint32_t bus, uint32_t *delay_frames, float *feedback, float *cross, float *dry, float *wet) const {
+        check(s2r_get_bus_delay(h_, bus, delay_frames, feedback, cross, dry, wet));
+    }
+    void bus_delay_history(uint32_t bus, float *lr, size_t capacity) { check(s2r_get_bus_delay_history(h_, bus, lr, capacity)); }     // 2 * delay_frames floats, oldest first, L R
+    void set_bus_delay_history(uint32_t bus, const float *lr, size_t count) { check(s2r_set_bus_delay_history(h_, bus, lr, count)); }
+    static int delay_reference(uint32_t delay_frames, float feedback, float cross, float dry, float wet, const float *x_lr, uint32_t frames, float *history_lr,
+                               float *out_lr) {
+        return s2r_delay_reference(delay_frames, feedback, cross, dry, wet, x_lr, frames, history_lr, out_lr);
+    }
 
     // the master section (build-defined; s2r.h: s2r_fill_master): a return level per bus and a master fader, each in [0, 1] and each
     // reaching its target as a ramp across the next sample_master call, and the meters of that call — in sample_master only

@@ -39,7 +39,8 @@ extern "C" {
  * s2r_get_bus_reverb, s2r_get_bus_reverb_history, s2r_set_bus_reverb_history, s2r_reverb_reference, s2r_set_bus_return,
  * s2r_get_bus_return, s2r_set_master_fader, s2r_get_master_fader, s2r_snap_master, s2r_fill_master, s2r_get_meters,
  * s2r_master_reference, s2r_set_master_limiter, s2r_clear_master_limiter, s2r_get_master_limiter, s2r_get_limiter_state,
- * s2r_set_limiter_state, s2r_get_limiter_meters, s2r_limiter_reference. */
+ * s2r_set_limiter_state, s2r_get_limiter_meters, s2r_limiter_reference, s2r_set_bus_delay, s2r_set_bus_delay_mix,
+ * s2r_get_bus_delay, s2r_get_bus_delay_history, s2r_set_bus_delay_history, s2r_delay_reference. */
 #define S2R_ABI_VERSION 4
 
 typedef enum {
@@ -350,7 +351,7 @@ int s2r_set_voice_sends(s2r_synth *s, const float *sends, const uint8_t *send_bu
  * a reverb: K taps (1 .. S2R_MAX_IR_TAPS) per channel, ir_l[k] and ir_r[k] (left feeds left, right feeds right; ir_r NULL: ir_l for
  * both), a `dry` and a `wet` in [0, 1], and a history of K - 1 stereo frames that carries from call to call, +0.0 right after the reverb
  * is set.  With x_c[i] what s2r_fill_buses writes for bus b, channel c, frame i of a call of N frames WITHOUT a reverb (the dry signal, bit
- * for bit), h_c[j] (j = 1 .. K - 1) the dry sample j frames before frame 0 of the call, and xs(i - k) = i >= k ? x_c[i - k] : h_c[k - i]:
+ * for bit: the bus combine's, or, on a bus that carries a delay — below —, the delay's output y), h_c[j] (j = 1 .. K - 1) the dry sample j frames before frame 0 of the call, and xs(i - k) = i >= k ? x_c[i - k] : h_c[k - i]:
  *   P_s = ((+0.0 + ir[256 s] * xs(i - 256 s)) + ir[256 s + 1] * xs(i - 256 s - 1)) + ...   for the taps of segment s = 0 .. ceil(K / 256) - 1
  *   in index order (S2R_IR_SEGMENT = 256 taps; the last segment ends at tap K - 1), every product rounded, then every sum;
  *   r = ((+0.0 + P_0) + P_1) + ...;   y = (dry * x_c[i]) + (wet * r)   (two rounded products, one rounded sum; binary32, no fma,
@@ -384,6 +385,51 @@ int s2r_get_bus_reverb(const s2r_synth *s, uint32_t bus, uint32_t *n_taps, float
 int s2r_get_bus_reverb_history(s2r_synth *s, uint32_t bus, float *lr, size_t capacity);
 int s2r_set_bus_reverb_history(s2r_synth *s, uint32_t bus, const float *lr, size_t count);
 int s2r_reverb_reference(const float *ir, uint32_t n_taps, const float *x_with_history, uint32_t frames, float dry, float wet, float *out);
+
+/* BUILD-DEFINED per-bus feedback delay with cross-feed ("ping-pong"; the reference has no effects): the other
+ * time-based effect of a send bus, computed on the device between the bus combine and the reverbs: combine -> delay -> reverb ->
+ * master -> limiter.  A bus b in [0, S2R_MAX_BUSES) may carry a delay: D frames (1 .. S2R_MAX_DELAY_FRAMES), the same for both
+ * channels; a `feedback` and a `cross` in [-1, 1] with |feedback| + |cross| <= 1 (evaluated in double from the two floats); a `dry`
+ * and a `wet` in [0, 1]; and a history of D stereo frames of the line signal W that carries from call to call, +0.0 right after the
+ * delay is set.  With x_c[n] what the bus combine writes for bus b, channel c, frame n of a call of N frames, and W_c[n] for n < 0
+ * the history:
+ *   t = W_c[n - D]          u = W_(1-c)[n - D]
+ *   p = feedback * t        q = cross * u
+ *   s = x_c[n] + p          W_c[n] = s + q
+ *   y_c[n] = (dry * x_c[n]) + (wet * t)
+ * binary32 throughout, every product and every sum rounded on its own (no fma), denormals kept, no add skipped for a zero
+ * coefficient: s + q with s = -0.0 and q = +0.0 is +0.0, and the rule says so.  y is the bus's signal from there on: a reverb on the
+ * same bus takes y as its dry signal, the stems and the master section see what the reverb, or without one the delay, wrote.
+ * Non-finite bus samples are outside the contract.  After a call that returns S2R_OK the history is the last D frames of (old
+ * history, then W[0 .. N)): calls of any lengths concatenate.  The delay runs once per call over all N frames, after every event
+ * segment and rows slice of the call has been mixed.  A delay on a bus >= the call's n_buses is idle in that call (no output, history
+ * untouched).  A bus without a delay passes through bit for bit, -0.0 included.  A refused or failed call leaves every history
+ * untouched.  ONLY s2r_fill_buses and s2r_fill_master apply delays; every other fill ignores them.  A delay is a property of the
+ * bus: s2r_set_patch_bank, program changes and s2r_import_state leave it alone.  A handle on which no delay was ever set launches
+ * what it launched before and allocates nothing for one.  The two copies of the history and a staging buffer for the combined buses
+ * live in device memory allocated when a delay is set (S2R_ERR_OUT_OF_MEMORY when that fails, and the earlier delay is kept), never
+ * inside a fill, and released with the handle.
+ *   s2r_set_bus_delay: replaces any earlier delay of the bus and zeroes its history; delay_frames == 0 removes it (the bus then
+ *   returns the combine's signal bit for bit).  S2R_ERR_PATCH_RANGE for a NaN, a value outside its range, |feedback| + |cross| > 1,
+ *   delay_frames > S2R_MAX_DELAY_FRAMES or bus >= S2R_MAX_BUSES (checked before the handle is looked at; nothing is changed).
+ *   s2r_set_bus_delay_mix: the four levels alone; D and the history stay.  S2R_ERR_INVALID on a bus without a delay.
+ *   s2r_get_bus_delay: delay_frames is 0 for a bus without one; any pointer may be NULL.
+ *   s2r_get_bus_delay_history / s2r_set_bus_delay_history: the 2 * D floats of the history, oldest frame first, L then R inside a
+ *   frame: the checkpoint companions of the reverb's pair.  S2R_ERR_INVALID for a capacity below, or a count other than, 2 * D, and
+ *   on a bus without a delay.
+ *   Single-device handles (a NULL or a device-list handle: S2R_ERR_INVALID from all five).
+ *   s2r_delay_reference: the rule above for BOTH channels on the host (no device, no handle; the cross-feed couples the channels):
+ *   x_lr is [frames][2]; history_lr is [delay_frames][2], oldest frame first, and is updated in place to the history after the call;
+ *   out_lr, [frames][2], may be NULL.  Range checks as above (and delay_frames >= 1); S2R_ERR_INVALID for a NULL history_lr or a
+ *   NULL x_lr with frames > 0. */
+#define S2R_MAX_DELAY_FRAMES 262144u
+int s2r_set_bus_delay(s2r_synth *s, uint32_t bus, uint32_t delay_frames, float feedback, float cross, float dry, float wet);
+int s2r_set_bus_delay_mix(s2r_synth *s, uint32_t bus, float feedback, float cross, float dry, float wet);
+int s2r_get_bus_delay(const s2r_synth *s, uint32_t bus, uint32_t *delay_frames, float *feedback, float *cross, float *dry, float *wet);
+int s2r_get_bus_delay_history(s2r_synth *s, uint32_t bus, float *lr, size_t capacity);
+int s2r_set_bus_delay_history(s2r_synth *s, uint32_t bus, const float *lr, size_t count);
+int s2r_delay_reference(uint32_t delay_frames, float feedback, float cross, float dry, float wet, const float *x_lr, uint32_t frames,
+                        float *history_lr, float *out_lr);
 
 /* BUILD-DEFINED master section (the reference's Synth::sample returns one stream; DESIGN.md 4.17 gives the op sequence): the last stage
  * of the chain send -> effect -> return -> master, on the device the bus signals are already on.  Every bus b in [0, S2R_MAX_BUSES) has

@@ -167,6 +167,14 @@ pub mod ffi {
         pub fn s2r_set_bus_reverb_history(s: *mut S2rSynth, bus: u32, lr: *const f32, count: usize) -> c_int;
         pub fn s2r_reverb_reference(ir: *const f32, n_taps: u32, x_with_history: *const f32, frames: u32, dry: f32, wet: f32,
                                     out: *mut f32) -> c_int;
+        pub fn s2r_set_bus_delay(s: *mut S2rSynth, bus: u32, delay_frames: u32, feedback: f32, cross: f32, dry: f32, wet: f32) -> c_int;
+        pub fn s2r_set_bus_delay_mix(s: *mut S2rSynth, bus: u32, feedback: f32, cross: f32, dry: f32, wet: f32) -> c_int;
+        pub fn s2r_get_bus_delay(s: *const S2rSynth, bus: u32, delay_frames: *mut u32, feedback: *mut f32, cross: *mut f32, dry: *mut f32,
+                                 wet: *mut f32) -> c_int;
+        pub fn s2r_get_bus_delay_history(s: *mut S2rSynth, bus: u32, lr: *mut f32, capacity: usize) -> c_int;
+        pub fn s2r_set_bus_delay_history(s: *mut S2rSynth, bus: u32, lr: *const f32, count: usize) -> c_int;
+        pub fn s2r_delay_reference(delay_frames: u32, feedback: f32, cross: f32, dry: f32, wet: f32, x_lr: *const f32, frames: u32,
+                                   history_lr: *mut f32, out_lr: *mut f32) -> c_int;
         pub fn s2r_set_bus_return(s: *mut S2rSynth, bus: u32, level: f32) -> c_int;
         pub fn s2r_get_bus_return(s: *const S2rSynth, bus: u32, level: *mut f32, applied: *mut f32) -> c_int;
         pub fn s2r_set_master_fader(s: *mut S2rSynth, level: f32) -> c_int;
@@ -220,6 +228,8 @@ pub const MAX_BUSES: u32 = 8;
 pub const MAX_IR_TAPS: u32 = 65536;
 /// `S2R_IR_SEGMENT`: the taps of one segment of the reverb's sum (part of its rule).
 pub const IR_SEGMENT: u32 = 256;
+/// `S2R_MAX_DELAY_FRAMES`: the longest time of a bus delay, in frames.
+pub const MAX_DELAY_FRAMES: u32 = 262144;
 /// `S2R_METER_BLOCK`: the frames of one block of the meters' energy tree (part of the master section's rule).
 pub const METER_BLOCK: u32 = 256;
 /// `S2R_LIMITER_MAX_LOOKAHEAD`, `S2R_LIMITER_MAX_HOLD`: the master limiter's longest lookahead and hold in frames, and
@@ -248,6 +258,19 @@ pub fn reverb_reference(ir: &[f32], x_with_history: &[f32], dry: f32, wet: f32) 
     let mut out = vec![0.0f32; frames];
     let rc = unsafe {
         ffi::s2r_reverb_reference(ir.as_ptr(), ir.len() as u32, x_with_history.as_ptr(), frames as u32, dry, wet, out.as_mut_ptr())
+    };
+    if rc == 0 { Ok(out) } else { Err(rc) }
+}
+
+/// Host-only: the bus delay's rule for both channels (`s2r_delay_reference`).  `x_lr`: L, R pairs; `history_lr`: the
+/// line's `2 * delay_frames` floats in front of them, oldest frame first, updated in place to the history after the call; returns one
+/// output pair per input pair, or the status.
+pub fn delay_reference(delay_frames: u32, feedback: f32, cross: f32, dry: f32, wet: f32, x_lr: &[f32], history_lr: &mut [f32]) -> Result<Vec<f32>, i32> {
+    assert!(x_lr.len() % 2 == 0 && history_lr.len() == 2 * delay_frames as usize);
+    let mut out = vec![0.0f32; x_lr.len()];
+    let rc = unsafe {
+        ffi::s2r_delay_reference(delay_frames, feedback, cross, dry, wet, x_lr.as_ptr(), (x_lr.len() / 2) as u32, history_lr.as_mut_ptr(),
+                                 out.as_mut_ptr())
     };
     if rc == 0 { Ok(out) } else { Err(rc) }
 }
@@ -582,6 +605,43 @@ pub mod synth {
 
         pub fn set_bus_reverb_history(&mut self, bus: u32, lr: &[f32]) {
             self.check(unsafe { ffi::s2r_set_bus_reverb_history(self.handle, bus, lr.as_ptr(), lr.len()) });
+        }
+
+        /// Build-defined per-bus feedback delay (`s2r_set_bus_delay`, include/s2r.h) in front of the bus's reverb: `delay_frames` in
+        /// 1 ..= MAX_DELAY_FRAMES, feedback and cross in [-1, 1] with |feedback| + |cross| <= 1, dry and wet in [0, 1]; replaces any
+        /// earlier delay of the bus and zeroes its history.  In `sample_buses` and `sample_master` only.
+        pub fn set_bus_delay(&mut self, bus: u32, delay_frames: u32, feedback: f32, cross: f32, dry: f32, wet: f32) {
+            assert!(delay_frames >= 1, "clear_bus_delay removes a delay");
+            self.check(unsafe { ffi::s2r_set_bus_delay(self.handle, bus, delay_frames, feedback, cross, dry, wet) });
+        }
+
+        pub fn clear_bus_delay(&mut self, bus: u32) {
+            self.check(unsafe { ffi::s2r_set_bus_delay(self.handle, bus, 0, 0.0, 0.0, 0.0, 0.0) });
+        }
+
+        /// The four levels alone; the delay's time and history stay.
+        pub fn set_bus_delay_mix(&mut self, bus: u32, feedback: f32, cross: f32, dry: f32, wet: f32) {
+            self.check(unsafe { ffi::s2r_set_bus_delay_mix(self.handle, bus, feedback, cross, dry, wet) });
+        }
+
+        /// (delay_frames, feedback, cross, dry, wet); delay_frames is 0 for a bus without a delay.
+        pub fn get_bus_delay(&self, bus: u32) -> (u32, f32, f32, f32, f32) {
+            let (mut d, mut fb, mut cross, mut dry, mut wet) = (0u32, 0.0f32, 0.0f32, 0.0f32, 0.0f32);
+            self.check(unsafe { ffi::s2r_get_bus_delay(self.handle, bus, &mut d, &mut fb, &mut cross, &mut dry, &mut wet) });
+            (d, fb, cross, dry, wet)
+        }
+
+        /// The `2 * delay_frames` floats of the delay's history, oldest frame first, L then R: checkpoint companion of
+        /// `bus_reverb_history`.
+        pub fn bus_delay_history(&mut self, bus: u32) -> Vec<f32> {
+            let d = self.get_bus_delay(bus).0 as usize;
+            let mut lr = vec![0.0f32; 2 * d];
+            self.check(unsafe { ffi::s2r_get_bus_delay_history(self.handle, bus, lr.as_mut_ptr(), lr.len()) });
+            lr
+        }
+
+        pub fn set_bus_delay_history(&mut self, bus: u32, lr: &[f32]) {
+            self.check(unsafe { ffi::s2r_set_bus_delay_history(self.handle, bus, lr.as_ptr(), lr.len()) });
         }
 
         /// Build-defined master section (`s2r_fill_master`, include/s2r.h): the target of a bus's return level (in [0, 1]), reached

@@ -427,6 +427,24 @@ struct S2rFx {
 // dry and wet into `out` and advances the history
 hipError_t s2r_launch_bus_fx(const S2rFx &fx, hipStream_t stream);
 
+// The per-bus feedback delay in front of the reverbs.  A bus's line holds its D frames of history of the line signal
+// W, oldest first, L, R interleaved; `next` receives the history the next call starts from (the host swaps the two).
+struct S2rDelayBus {
+    const float *line;            // [D][2]
+    float *next;                  // [D][2], not `line`
+    uint32_t delay;               // D (0: no delay on this bus: it is copied from `in` to `out`)
+    float feedback, cross, dry, wet;
+};
+struct S2rDelay {
+    S2rDelayBus bus[S2R_MAX_BUSES];
+    const float *in;              // [n_buses][2 * frames]: what the bus combine wrote, bus-major, L, R interleaved inside a bus
+    float *out;                   // the same layout, not `in`: what the next stage, or the caller, reads
+    uint32_t n_buses, frames;
+};
+// one kernel: the delays' outputs and next histories, the other buses unchanged; hipErrorInvalidValue for a null pointer, in == out,
+// a D past S2R_MAX_DELAY_FRAMES, line == next, n_buses past S2R_MAX_BUSES or no delay at all among the call's buses
+hipError_t s2r_launch_bus_delay(const S2rDelay &a, hipStream_t stream);
+
 // The master section of s2r_fill_master: the stems of a call, post-effect, each times its return's ramp, added in
 // bus order from +0.0, times the master fader's ramp; and the call's meters.  gain at frame i of the CALL: r0 + (float)i * dr (the
 // product rounded, then the sum); a pair that did not move has dr = +0.0.

@@ -317,7 +317,7 @@ struct s2r_synth {
     float *bus_out = nullptr, *bus_out_dev = nullptr;            // pinned and device-mapped: S2R_MAX_BUSES * 2 * max_frames floats
     float bus_mix_ms = -1.0f;                    // pan_mix_ms of the last s2r_fill_buses (tools/bus_time.py)
     bool bus_dev_ramped = false;                 // what bus_gains_dev holds was sent for a ramped fill: (G0, step), not the static gains
-    // What runs behind the bus mixdown (s2r_post.h): the buses' reverbs, the master section and the master limiter
+    // What runs behind the bus mixdown (s2r_post.h): the buses' delays and reverbs, the master section and the master limiter
     S2rPostChain post;
     float pitch_table[256];
     hipEvent_t t0 = nullptr, t1 = nullptr;
@@ -2716,7 +2716,7 @@ int s2r_set_voice_sends(s2r_synth *s, const float *sends, const uint8_t *send_bu
     return S2R_OK;
 }
 
-// ---- the post-mix chain: reverbs, master section, master limiter (s2r_post.h) ----
+// ---- the post-mix chain: delays, reverbs, master section, master limiter (s2r_post.h) ----
 // Every entry below looks at its values first (they are wrong whatever the handle holds), then at the handle, quiesces where it touches
 // the device, and calls into s->post for whatever is more than one value.  `what`: "bus reverbs are", "the master section is", ...
 static int post_handle(const s2r_synth *s, const char *who, const char *what) {
@@ -2782,6 +2782,60 @@ int s2r_set_bus_reverb_history(s2r_synth *s, uint32_t bus, const float *lr, size
     static const float none = 0.0f;                              // (a null lr: refused by fx_history unless K = 1, which has no history)
     return fx_history(s, bus, nullptr, lr ? lr : &none, lr ? count : (count ? (size_t)-1 : 0), "s2r_set_bus_reverb_history");
 }
+
+// ---- per-bus feedback delays: in front of the reverbs ----
+int s2r_set_bus_delay(s2r_synth *s, uint32_t bus, uint32_t delay_frames, float feedback, float cross, float dry, float wet) {
+    if (!delay_mix_in_range(feedback, cross, dry, wet) || delay_frames > S2R_MAX_DELAY_FRAMES || bus >= S2R_MAX_BUSES)
+        return set_err(s, S2R_ERR_PATCH_RANGE, "bus %u: a delay of %u frames, feedback %g, cross %g, dry %g, wet %g: feedback and cross lie in [-1, 1] with "
+                       "|feedback| + |cross| <= 1, dry and wet in [0, 1], at most %u frames, the bus below %u", bus, delay_frames, (double)feedback, (double)cross,
+                       (double)dry, (double)wet, S2R_MAX_DELAY_FRAMES, S2R_MAX_BUSES);
+    S2R_TRY(post_handle(s, "s2r_set_bus_delay", "bus delays are"));
+    if (s->ring_count) return set_err(s, S2R_ERR_INVALID, "s2r_set_bus_delay with fills of s2r_fill_begin in flight: s2r_fill_end first");
+    S2R_QUIESCE(s);
+    S2R_HIP(s, hipSetDevice(s->device));
+    S2R_HIP(s, hipStreamSynchronize(s->stream));
+    const hipError_t e = s->post.set_delay(post_ctx(s), bus, delay_frames, feedback, cross, dry, wet);
+    if (e != hipSuccess) return set_err(s, e == hipErrorOutOfMemory ? S2R_ERR_OUT_OF_MEMORY : S2R_ERR_HIP, "s2r_set_bus_delay: %s", hipGetErrorString(e));
+    return S2R_OK;
+}
+
+int s2r_set_bus_delay_mix(s2r_synth *s, uint32_t bus, float feedback, float cross, float dry, float wet) {
+    if (!delay_mix_in_range(feedback, cross, dry, wet) || bus >= S2R_MAX_BUSES)
+        return set_err(s, S2R_ERR_PATCH_RANGE, "bus %u: feedback %g, cross %g, dry %g, wet %g: feedback and cross lie in [-1, 1] with |feedback| + |cross| <= 1, "
+                       "dry and wet in [0, 1], the bus below %u", bus, (double)feedback, (double)cross, (double)dry, (double)wet, S2R_MAX_BUSES);
+    S2R_TRY(post_handle(s, "s2r_set_bus_delay_mix", "bus delays are"));
+    S2rPostChain::BusDelay &d = s->post.delay[bus];
+    if (!d.delay) return set_err(s, S2R_ERR_INVALID, "bus %u carries no delay", bus);
+    d.feedback = feedback; d.cross = cross; d.dry = dry; d.wet = wet;
+    return S2R_OK;
+}
+
+int s2r_get_bus_delay(const s2r_synth *s, uint32_t bus, uint32_t *delay_frames, float *feedback, float *cross, float *dry, float *wet) {
+    if (bus >= S2R_MAX_BUSES) return S2R_ERR_PATCH_RANGE;
+    if (!s || !s->kids.empty() || s->parent) return S2R_ERR_INVALID;
+    const S2rPostChain::BusDelay &d = s->post.delay[bus];
+    put(delay_frames, d.delay); put(feedback, d.feedback); put(cross, d.cross); put(dry, d.dry); put(wet, d.wet);
+    return S2R_OK;
+}
+
+// the history crosses the boundary as the device keeps it: frames, oldest first, L then R
+static int delay_history(s2r_synth *s, uint32_t bus, float *get, const float *set, size_t count, const char *who) {
+    if (bus >= S2R_MAX_BUSES) return set_err(s, S2R_ERR_PATCH_RANGE, "%s: bus %u, below %u", who, bus, S2R_MAX_BUSES);
+    S2R_TRY(post_handle(s, who, "bus delays are"));
+    if (!s->post.delay[bus].delay) return set_err(s, S2R_ERR_INVALID, "%s: bus %u carries no delay", who, bus);
+    const size_t h = s->post.delay[bus].delay;
+    if (set ? count != 2 * h : count < 2 * h) return set_err(s, S2R_ERR_INVALID, "%s: the history of bus %u is %zu floats, not %zu", who, bus, 2 * h, count);
+    if (!get && !set) return set_err(s, S2R_ERR_INVALID, "%s: null buffer", who);
+    S2R_QUIESCE(s);
+    S2R_HIP(s, hipSetDevice(s->device));
+    S2R_HIP(s, hipStreamSynchronize(s->stream));
+    S2R_HIP(s, s->post.delay_history(post_ctx(s), bus, get, set));
+    return S2R_OK;
+}
+
+int s2r_get_bus_delay_history(s2r_synth *s, uint32_t bus, float *lr, size_t capacity) { return delay_history(s, bus, lr, nullptr, capacity, "s2r_get_bus_delay_history"); }
+
+int s2r_set_bus_delay_history(s2r_synth *s, uint32_t bus, const float *lr, size_t count) { return delay_history(s, bus, nullptr, lr, lr ? count : (size_t)-1, "s2r_set_bus_delay_history"); }
 
 // ---- program faders ----
 int s2r_set_program_fader(s2r_synth *s, uint32_t program, float fader, float pan_shift) {
@@ -3362,6 +3416,8 @@ extern "C" float s2r_debug_pan_mix_ms(const s2r_synth *s) { return s && s->timin
 extern "C" uint32_t s2r_debug_pan_slice(const s2r_synth *s) { return s ? s->pan_slice : 0u; }
 // ... and of the bus mixdown's kernels in the last s2r_fill_buses (tools/bus_time.py)
 extern "C" float s2r_debug_bus_mix_ms(const s2r_synth *s) { return s && s->timing ? s->bus_mix_ms : -1.0f; }
+// ... of the buses' delay kernel in that fill: 0 when it ran none (tools/delay_time.py)
+extern "C" float s2r_debug_bus_delay_ms(const s2r_synth *s) { return s && s->timing ? s->post.delay_timer.ms : -1.0f; }
 // ... and of the buses' reverb kernels in that fill: 0 when it ran none (tools/reverb_time.py)
 extern "C" float s2r_debug_bus_fx_ms(const s2r_synth *s) { return s && s->timing ? s->post.fx_timer.ms : -1.0f; }
 // ... and of the master kernel in the last s2r_fill_master (tools/master_time.py)

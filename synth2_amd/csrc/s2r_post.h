@@ -1,5 +1,5 @@
-// s2r_post.h — the chain behind the bus mixdown of s2r_fill_buses and s2r_fill_master: the buses' convolution reverbs (DESIGN.md
-// 4.16), the master section (4.17) and the master limiter (4.18), in that order.  The chain owns what the three stages own and knows
+// s2r_post.h — the chain behind the bus mixdown of s2r_fill_buses and s2r_fill_master: the buses' feedback delays,
+// their convolution reverbs (4.16), the master section (4.17) and the master limiter (4.18), in that order.  The chain owns what the four stages own and knows
 // nothing of the handle: its functions take a S2rPostCtx and return the HIP error.  Per call: prepare, launch, — the caller's synchronise —
 // commit, read_timers.
 #pragma once
@@ -22,31 +22,50 @@ struct S2rPostTimer {
     void destroy() { for (hipEvent_t &e : ev) if (e) { (void)hipEventDestroy(e); e = nullptr; } }
 };
 
-// every pointer of one call (s2r_post_route): the bus combine's, the reverbs' kernels', the master kernel's and the limiter's
-struct S2rPostRoute { float *combine_out, *fx_in, *fx_out, *master_in, *master_out, *master_stems, *limiter_in, *limiter_out; };
+// every pointer of one call (s2r_post_route): the bus combine's, the delay kernel's, the reverbs' kernels', the master kernel's and the limiter's
+struct S2rPostRoute { float *combine_out, *delay_in, *delay_out, *fx_in, *fx_out, *master_in, *master_out, *master_stems, *limiter_in, *limiter_out; };
 struct S2rPostCall {                                // one fill, as prepare leaves it
     uint32_t n_buses = 0, frames = 0;            // n_buses 0: a panned fill, which runs no stage
     bool master = false, stems = false;          // s2r_fill_master; the caller wants the stems too
+    bool delay_on = false;                       // a delay sits on one of the call's buses
     bool fx_on = false, limited = false;         // a reverb sits on one of the call's buses; a master fill with the limiter set
     S2rPostRoute route{};
 };
 
-// Who reads and writes what, the only place that decides it.  Whichever stage writes the stems LAST writes them where the call wants
-// them: the pinned output in a bus fill; the master's device stage in a master fill, whose kernel must not read pinned memory back
-// and copies them out itself when the caller wants them.  The master kernel's two channels go to the pinned output unless the
-// limiter follows and writes there in its place.  A stage that does not run has null pointers.
-//   call            reverb  limiter | combine_out   fx_in -> fx_out             master_in     master_out    limiter_in -> _out
-//   bus fill        no      -       | bus_out_dev   -                           -             -             -
-//   bus fill        yes     -       | fx_stage      fx_stage -> bus_out_dev     -             -             -
-//   master fill     no      no      | master_stage  -                           master_stage  out_host_dev  -
-//   master fill     yes     no      | fx_stage      fx_stage -> master_stage    master_stage  out_host_dev  -
-//   master fill     no      yes     | master_stage  -                           master_stage  limiter_in    limiter_in -> out_host_dev
-//   master fill     yes     yes     | fx_stage      fx_stage -> master_stage    master_stage  limiter_in    limiter_in -> out_host_dev
-//   master_stems = bus_out_dev in a master fill with stems, else null.  A limiter that is set is idle in a bus fill, a reverb on a
-//   bus past the call's in any; a panned fill (no buses) has no route.
-S2rPostRoute s2r_post_route(const S2rPostCall &call, float *fx_stage, float *master_stage, float *limiter_in, float *bus_out_dev, float *out_host_dev);
+// Who reads and writes what, the only place that decides it.  The combine writes into the first stem stage that runs, each running
+// stage into the next running stage's input, and whichever stage writes the stems LAST writes them where the call wants them: the
+// pinned output in a bus fill; the master's device stage in a master fill, whose kernel must not read pinned memory back and copies
+// them out itself when the caller wants them.  The master kernel's two channels go to the pinned output unless the limiter follows
+// and writes there in its place.  A stage that does not run has null pointers.
+//   call         delay reverb limiter | combine_out   delay_in -> delay_out          fx_in -> fx_out             master_in     master_out    limiter_in -> _out
+//   bus fill     no    no     -       | bus_out_dev   -                              -                           -             -             -
+//   bus fill     no    yes    -       | fx_stage      -                              fx_stage -> bus_out_dev     -             -             -
+//   bus fill     yes   no     -       | delay_stage   delay_stage -> bus_out_dev     -                           -             -             -
+//   bus fill     yes   yes    -       | delay_stage   delay_stage -> fx_stage        fx_stage -> bus_out_dev     -             -             -
+//   master fill  no    no     no      | master_stage  -                              -                           master_stage  out_host_dev  -
+//   master fill  no    yes    no      | fx_stage      -                              fx_stage -> master_stage    master_stage  out_host_dev  -
+//   master fill  yes   no     no      | delay_stage   delay_stage -> master_stage    -                           master_stage  out_host_dev  -
+//   master fill  yes   yes    no      | delay_stage   delay_stage -> fx_stage        fx_stage -> master_stage    master_stage  out_host_dev  -
+//   master fill  no    no     yes     | master_stage  -                              -                           master_stage  limiter_in    limiter_in -> out_host_dev
+//   master fill  no    yes    yes     | fx_stage      -                              fx_stage -> master_stage    master_stage  limiter_in    limiter_in -> out_host_dev
+//   master fill  yes   no     yes     | delay_stage   delay_stage -> master_stage    -                           master_stage  limiter_in    limiter_in -> out_host_dev
+//   master fill  yes   yes    yes     | delay_stage   delay_stage -> fx_stage        fx_stage -> master_stage    master_stage  limiter_in    limiter_in -> out_host_dev
+//   master_stems = bus_out_dev in a master fill with stems, else null.  A limiter that is set is idle in a bus fill, a delay or a
+//   reverb on a bus past the call's in any; a panned fill (no buses) has no route.
+S2rPostRoute s2r_post_route(const S2rPostCall &call, float *delay_stage, float *fx_stage, float *master_stage, float *limiter_in, float *bus_out_dev,
+                            float *out_host_dev);
 
 struct S2rPostChain {
+    // The delays (s2r_set_bus_delay).  Everything of theirs is allocated when a delay is set, never in a fill.
+    struct BusDelay {
+        uint32_t delay = 0;                      // D; 0: the bus has no delay
+        float feedback = 0.0f, cross = 0.0f, dry = 0.0f, wet = 0.0f;
+        float *line[2] = {nullptr, nullptr};     // [D][2] each, oldest frame first, L then R: line[cur] holds the history, the kernel writes the other
+        int cur = 0;
+        void release() { for (float *p : line) if (p) (void)hipFree(p); *this = BusDelay{}; }
+    } delay[S2R_MAX_BUSES];
+    float *delay_stage = nullptr;                // [S2R_MAX_BUSES][2 * max_frames]: where the bus combine writes in a call that runs a delay
+    S2rPostTimer delay_timer;                    // around the delay kernel of the last bus or master fill: 0 when it ran none (tools/delay_time.py)
     // The reverbs (s2r_set_bus_reverb).  Everything of theirs is allocated when a reverb is set, never in a fill.
     struct BusFx {
         uint32_t n_taps = 0;                     // K; 0: the bus has no reverb
@@ -98,6 +117,8 @@ struct S2rPostChain {
     hipError_t read_timers(const S2rPostCall &call);
     void release();
     // what the entry points of s2r_host.cpp do behind their checks, on a quiet stream
+    hipError_t set_delay(const S2rPostCtx &c, uint32_t bus, uint32_t delay_frames, float feedback, float cross, float dry, float wet);
+    hipError_t delay_history(const S2rPostCtx &c, uint32_t bus, float *get, const float *set);      // frames, oldest first, L then R
     hipError_t set_reverb(const S2rPostCtx &c, uint32_t bus, const float *ir_l, const float *ir_r, uint32_t n_taps, float dry, float wet);
     hipError_t reverb_history(const S2rPostCtx &c, uint32_t bus, float *get, const float *set);     // frames, oldest first, L then R
     void snap_master() { for (uint32_t b = 0; b < S2R_MAX_BUSES; b++) master.ret_app[b] = master.ret[b]; master.fader_app = master.fader; }

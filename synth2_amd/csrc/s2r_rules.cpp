@@ -1,5 +1,5 @@
-// s2r_rules.cpp — the rules of libs2r that need neither a handle nor HIP: the voice mixer's gains, and the reverb, the master section
-// and the master limiter in plain host loops (s2r.h states each rule).  Plain C++17, -ffp-contract=off: every operation rounded on its own.
+// s2r_rules.cpp — the rules of libs2r that need neither a handle nor HIP: the voice mixer's gains, and the reverb, the delay, the master
+// section and the master limiter in plain host loops (s2r.h states each rule).  Plain C++17, -ffp-contract=off: every operation rounded on its own.
 #include <cstddef>
 #include <cstring>
 #include <vector>
@@ -35,6 +35,26 @@ int s2r_reverb_reference(const float *ir, uint32_t n_taps, const float *x_with_h
         const float d = dry * x[0], w = wet * r;
         out[i] = d + w;
     }
+    return S2R_OK;
+}
+
+// ---- per-bus feedback delay, both channels: the cross-feed couples them ----
+int s2r_delay_reference(uint32_t delay_frames, float feedback, float cross, float dry, float wet, const float *x_lr, uint32_t frames,
+                        float *history_lr, float *out_lr) {
+    if (!delay_mix_in_range(feedback, cross, dry, wet) || delay_frames == 0 || delay_frames > S2R_MAX_DELAY_FRAMES) return S2R_ERR_PATCH_RANGE;
+    if (!history_lr || (!x_lr && frames)) return S2R_ERR_INVALID;
+    const size_t D = delay_frames, N = frames;
+    std::vector<float> w(2 * (D + N));                           // W[-D .. N): the history, then the call's line signal
+    std::memcpy(w.data(), history_lr, 2 * D * sizeof(float));
+    for (size_t n = 0; n < N; n++)
+        for (size_t c = 0; c < 2; c++) {
+            const float x = x_lr[2 * n + c], t = w[2 * n + c], u = w[2 * n + (1 - c)];     // (frame n - D of W sits at index n)
+            const float p = feedback * t, q = cross * u;
+            const float s = x + p;
+            w[2 * (n + D) + c] = s + q;
+            if (out_lr) { const float d = dry * x, e = wet * t; out_lr[2 * n + c] = d + e; }
+        }
+    std::memcpy(history_lr, w.data() + 2 * N, 2 * D * sizeof(float));
     return S2R_OK;
 }
 

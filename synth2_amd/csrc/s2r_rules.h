@@ -13,6 +13,11 @@ static inline bool limiter_in_range(float ceiling, uint32_t lookahead, uint32_t 
     const float lo = std::ldexp(1.0f, -S2R_LIMITER_CEILING_LOG2), hi = std::ldexp(1.0f, S2R_LIMITER_CEILING_LOG2);
     return ceiling >= lo && ceiling <= hi && lookahead >= 1u && lookahead <= S2R_LIMITER_MAX_LOOKAHEAD && hold <= S2R_LIMITER_MAX_HOLD;
 }
+// a delay's four levels: the sum condition in double, from the two floats
+static inline bool delay_mix_in_range(float feedback, float cross, float dry, float wet) {
+    return pan_in_range(feedback) && pan_in_range(cross) && std::fabs((double)feedback) + std::fabs((double)cross) <= 1.0 && unit_in_range(dry) &&
+           unit_in_range(wet);
+}
 
 // The voice mixer's gain rules, inline: the host's per-voice loops compile them in — a call per voice into s2r_rules.cpp showed as 10
 // to 15 us of host time per fill of 65 536 voices (profiles/r12/post_chain.txt).  s2r_rules.cpp exports them under their s2r.h names.

@@ -35,6 +35,7 @@ S2R_ERR_OFFSET_OVERFLOW = -7
 S2R_ERR_OUT_OF_MEMORY = -8
 MAX_BUSES = 8                               # S2R_MAX_BUSES
 MAX_IR_TAPS = 65536                         # S2R_MAX_IR_TAPS
+MAX_DELAY_FRAMES = 262144                   # S2R_MAX_DELAY_FRAMES
 IR_SEGMENT = 256                            # S2R_IR_SEGMENT
 METER_BLOCK = 256                           # S2R_METER_BLOCK
 LIMITER_MAX_LOOKAHEAD = 1024                # S2R_LIMITER_MAX_LOOKAHEAD
@@ -199,6 +200,12 @@ def load_library():
         "s2r_get_bus_reverb_history": (C.c_int, [H, C.c_uint32, _f32p, C.c_size_t]),
         "s2r_set_bus_reverb_history": (C.c_int, [H, C.c_uint32, _f32p, C.c_size_t]),
         "s2r_reverb_reference": (C.c_int, [_f32p, C.c_uint32, _f32p, C.c_uint32, C.c_float, C.c_float, _f32p]),
+        "s2r_set_bus_delay": (C.c_int, [H, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_float]),
+        "s2r_set_bus_delay_mix": (C.c_int, [H, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_float]),
+        "s2r_get_bus_delay": (C.c_int, [H, C.c_uint32, C.POINTER(C.c_uint32), _f32p, _f32p, _f32p, _f32p]),
+        "s2r_get_bus_delay_history": (C.c_int, [H, C.c_uint32, _f32p, C.c_size_t]),
+        "s2r_set_bus_delay_history": (C.c_int, [H, C.c_uint32, _f32p, C.c_size_t]),
+        "s2r_delay_reference": (C.c_int, [C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_float, _f32p, C.c_uint32, _f32p, _f32p]),
         "s2r_set_bus_return": (C.c_int, [H, C.c_uint32, C.c_float]),
         "s2r_get_bus_return": (C.c_int, [H, C.c_uint32, _f32p, _f32p]),
         "s2r_set_master_fader": (C.c_int, [H, C.c_float]),
@@ -325,6 +332,23 @@ def reverb_reference(ir, x_with_history, frames, dry, wet):
     if rc != S2R_OK:
         raise S2rError(rc, load_library().s2r_status_string(rc).decode())
     return out
+
+
+def delay_reference(delay_frames, feedback, cross, dry, wet, x, history):
+    """the bus delay's rule for both channels on the host (s2r_delay_reference): x [frames, 2] float32 is the bus's signal, history
+    [delay_frames, 2] the line's D frames in front of it, oldest first; returns (out [frames, 2], the history after the call
+    [delay_frames, 2]).  `history` itself is left as it is."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    h = np.array(history, dtype=np.float32, order="C")
+    d = int(delay_frames)
+    if x.ndim != 2 or x.shape[1] != 2 or h.shape != (d, 2):
+        raise ValueError("delay_reference: x is [frames, 2] and history is [delay_frames, 2]")
+    out = np.empty_like(x)
+    rc = load_library().s2r_delay_reference(d, float(feedback), float(cross), float(dry), float(wet), x.ctypes.data_as(_f32p), x.shape[0],
+                                            h.ctypes.data_as(_f32p), out.ctypes.data_as(_f32p))
+    if rc != S2R_OK:
+        raise S2rError(rc, load_library().s2r_status_string(rc).decode())
+    return out, h
 
 
 def master_reference(stems, r0, r1, m0, m1):
@@ -703,6 +727,46 @@ class Synth:
     @staticmethod
     def reverb_reference(ir, x_with_history, frames, dry, wet):
         return reverb_reference(ir, x_with_history, frames, dry, wet)
+
+    # --- per-bus feedback delay (build-defined; s2r.h: s2r_set_bus_delay) ---
+    def set_bus_delay(self, bus, delay_frames, feedback=0.0, cross=0.0, dry=1.0, wet=1.0):
+        """a feedback delay of delay_frames (1 .. MAX_DELAY_FRAMES) on a bus of sample_buses and sample_master, in front of the bus's
+        reverb: feedback and cross (the other channel's feed: ping-pong) in [-1, 1] with |feedback| + |cross| <= 1, dry and wet in
+        [0, 1].  Replaces any earlier delay of the bus and zeroes its history."""
+        if int(delay_frames) < 1:
+            raise ValueError("set_bus_delay: at least one frame (clear_bus_delay removes a delay)")
+        self._check(self.L.s2r_set_bus_delay(self.h, int(bus), int(delay_frames), float(feedback), float(cross), float(dry), float(wet)))
+
+    def clear_bus_delay(self, bus):
+        """removes the bus's delay: the bus returns the combine's signal again, bit for bit"""
+        self._check(self.L.s2r_set_bus_delay(self.h, int(bus), 0, 0.0, 0.0, 0.0, 0.0))
+
+    def set_bus_delay_mix(self, bus, feedback, cross, dry, wet):
+        """the four levels of the bus's delay alone; its time and history stay"""
+        self._check(self.L.s2r_set_bus_delay_mix(self.h, int(bus), float(feedback), float(cross), float(dry), float(wet)))
+
+    def get_bus_delay(self, bus):
+        """(delay_frames, feedback, cross, dry, wet); delay_frames is 0 for a bus without a delay"""
+        n, f, x, d, w = C.c_uint32(), C.c_float(), C.c_float(), C.c_float(), C.c_float()
+        self._check(self.L.s2r_get_bus_delay(self.h, int(bus), C.byref(n), C.byref(f), C.byref(x), C.byref(d), C.byref(w)))
+        return n.value, f.value, x.value, d.value, w.value
+
+    def bus_delay_history(self, bus):
+        """the D stereo frames of the line that the bus's delay carries into the next call, oldest first: (D, 2) float32 (the
+        checkpoint companion of bus_reverb_history)"""
+        out = np.empty((self.get_bus_delay(bus)[0], 2), dtype=np.float32)
+        self._check(self.L.s2r_get_bus_delay_history(self.h, int(bus), out.ctypes.data_as(_f32p), out.size))
+        return out
+
+    def set_bus_delay_history(self, bus, history):
+        h = np.ascontiguousarray(history, dtype=np.float32)
+        if h.ndim != 2 or h.shape[1] != 2:
+            raise ValueError("set_bus_delay_history: history is [D, 2]")
+        self._check(self.L.s2r_set_bus_delay_history(self.h, int(bus), h.ctypes.data_as(_f32p), h.size))
+
+    @staticmethod
+    def delay_reference(delay_frames, feedback, cross, dry, wet, x, history):
+        return delay_reference(delay_frames, feedback, cross, dry, wet, x, history)
 
     # --- the master section (build-defined; s2r.h: s2r_fill_master) ---
     def set_bus_return(self, bus, level=1.0):
