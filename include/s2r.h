@@ -651,6 +651,14 @@ int s2r_set_flat_shortcut(s2r_synth *s, int enabled);
  * untimed events carries them in the render kernel's arguments; 2: tables, but note events always through their
  * own launch; 3 / 4: synonyms of 1 / 2 (earlier rounds' test matrices).  Same bits in every mode. */
 int s2r_set_coeff_stream(s2r_synth *s, int enabled);
+/* Measurement knob (default on): a wavefront whose 64 voices were started together with one patch reads its chunks'
+ * filter coefficients, amplitudes and noise from a window in LDS that it fills once per run, instead of computing them
+ * on every lane (launch-per-fill form, fills of up to 1024 frames, pools of at most one 256-voice
+ * workgroup per compute unit).  Same bits either way. */
+int s2r_set_uniform_window(s2r_synth *s, int enabled);
+/* How many 16-frame chunks (per wavefront) the handle's fills have rendered through that window since it was created:
+ * tells a test, or a profile, whether the path was taken.  Waits for the fills in flight. */
+int s2r_uniform_window_chunks(s2r_synth *s, uint64_t *chunks);
 float s2r_last_render_ms(s2r_synth *s);
 const char *s2r_last_error(const s2r_synth *s);             /* never NULL */
 const char *s2r_status_string(int status);

@@ -168,6 +168,8 @@ struct S2rRenderParams {
     // ... and (tools/gpu_timeline.py) [launches][2] s_memrealtime of this launch's first entry and last exit, slot `tl_slot`
     unsigned long long *timeline;
     uint32_t tl_slot;
+    uint32_t uw_frames;   // the uniform window (uw_count below): frames of a wave's window, set by the launcher: S2R_UW_FRAMES,
+                          // or 0 where there is none (here: the word fills a gap; the kernel arguments are at their 4 KiB)
     // patch bank (bank_size > 1: s2r_render_general_kernel<ANY, true>; the fields above then hold patch 0)
     const S2rBankEntry *bank;
     uint32_t bank_size;
@@ -184,7 +186,13 @@ struct S2rRenderParams {
     uint32_t *arrive;                // rows counter of this fill's parity (device memory; only grows)
     uint32_t arrive_target;          // its value when every workgroup has written its row
     S2rMixTail mt;
+    // The uniform window (the one-pole kernel's launch-per-fill form): a wave whose 64 voices started together
+    // takes its chunks' coefficients, amplitudes and noise from a region of LDS it fills once per run.
+    uint32_t *uw_count;              // the handle's count of chunks rendered that way; nullptr: the window is switched off
 };
+#define S2R_UW_FRAMES 1024u          /* a whole-fill super-chunk's worth: one fill of the window serves any run */
+#define S2R_UW_PLANES 4u             /* x, 1 - x, amplitude, noise */
+#define S2R_UW_MIN_RUN 3u            /* chunks a run must have for the window's fill to pay */
 
 // Coalesced note events, one record per touched voice per fill (host folds the event
 // stream of synth.rs:61-80 between two fills into the voice's final state).

@@ -323,6 +323,8 @@ struct s2r_synth {
     hipEvent_t t0 = nullptr, t1 = nullptr;
     bool timing = false, timed = false, no_flat_shortcut = false;
     uint64_t double_release = 0;
+    bool uniform_window = true;                  // s2r_set_uniform_window
+    uint32_t *uw_count_dev = nullptr;            // chunks rendered through the uniform window (S2rRenderParams.uw_count), one word
     s2r_voice_log_fn voice_log = nullptr;    // synth.rs:118's log::debug!, as a callback
     void *voice_log_user = nullptr;
     // A kernel that gave up a bounded wait for another kernel's (or workgroup's) work left the fill unrendered — it touches
@@ -704,6 +706,7 @@ S2rRenderParams make_params(s2r_synth *s, size_t frames, uint32_t sample_rate) {
       p.noise_tab = off ? nullptr : s->noise_dev; }
     p.bank = s->bank_dev;
     p.bank_size = (uint32_t)s->bank.size();
+    p.uw_count = s->uniform_window ? s->uw_count_dev : nullptr;   // (the launcher decides whether the fill has a window)
     return p;
 }
 
@@ -1897,6 +1900,7 @@ void release_all(s2r_synth *s) {
     }
     if (s->sin_dev) (void)hipFree(s->sin_dev);
     if (s->noise_dev) (void)hipFree(s->noise_dev);
+    if (s->uw_count_dev) (void)hipFree(s->uw_count_dev);
     if (s->res_cmd_vram && s->res_cmd) (void)hipFree(s->res_cmd);
     if (s->res_host) (void)hipHostFree(s->res_host);
     if (s->res_gran) (void)hipHostFree(s->res_gran);
@@ -2126,6 +2130,8 @@ static int create_single(const s2r_config *cfg, std::shared_ptr<S2rVoicePool> po
         CREATE_HIP(hipMemcpy(s->sin_dev, table, sizeof table, hipMemcpyHostToDevice));
         CREATE_HIP(hipMalloc((void **)&s->noise_dev, 65536 * sizeof(float)));
         CREATE_HIP(s2r_launch_noise_table(s->noise_dev, s->stream));
+        CREATE_HIP(hipMalloc((void **)&s->uw_count_dev, sizeof(uint32_t)));
+        CREATE_HIP(hipMemsetAsync(s->uw_count_dev, 0, sizeof(uint32_t), s->stream));
     }
     CREATE_HIP(hipStreamSynchronize(s->stream));
 #undef CREATE_HIP
@@ -3253,6 +3259,34 @@ int s2r_set_flat_shortcut(s2r_synth *s, int enabled) {
     S2R_QUIESCE(s);
     s->no_flat_shortcut = enabled == 0;
     for (s2r_synth *kid : s->kids) kid->no_flat_shortcut = s->no_flat_shortcut;
+    return S2R_OK;
+}
+
+int s2r_set_uniform_window(s2r_synth *s, int enabled) {
+    if (!s) return S2R_ERR_INVALID;
+    S2R_QUIESCE(s);
+    s->uniform_window = enabled != 0;
+    for (s2r_synth *kid : s->kids) kid->uniform_window = s->uniform_window;
+    return S2R_OK;
+}
+
+// chunks the handle's fills have rendered through the uniform window so far (every shard's): waits for the fills in flight
+int s2r_uniform_window_chunks(s2r_synth *s, uint64_t *chunks) {
+    if (!s || !chunks) return S2R_ERR_INVALID;
+    S2R_QUIESCE(s);
+    uint64_t total = 0;
+    auto one = [&](s2r_synth *h) -> int {
+        if (!h->uw_count_dev) return S2R_OK;
+        uint32_t n = 0;
+        S2R_HIP(s, hipSetDevice(h->device));
+        S2R_HIP(s, hipDeviceSynchronize());
+        S2R_HIP(s, hipMemcpy(&n, h->uw_count_dev, sizeof n, hipMemcpyDeviceToHost));
+        total += n;
+        return S2R_OK;
+    };
+    if (s->kids.empty()) { S2R_TRY(one(s)); }
+    else for (s2r_synth *kid : s->kids) { S2R_TRY(one(kid)); }
+    *chunks = total;
     return S2R_OK;
 }
 

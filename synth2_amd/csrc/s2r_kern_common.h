@@ -925,6 +925,14 @@ __device__ __forceinline__ f4 pk_add4(f4 a, f4 b) {
     asm("v_pk_add_f32 %0, %1, %2" : "=v"(hi) : "v"(a.zw), "v"(b.zw));
     return (f4){lo.x, lo.y, hi.x, hi.y};
 }
+// a - b, packed: the add with the second operand's sign flipped on its way in (a source modifier: a + (-b) is the
+// very IEEE subtraction a - b)
+__device__ __forceinline__ f4 pk_sub4(f4 a, f4 b) {
+    fp2 lo, hi;
+    asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(lo) : "v"(a.xy), "v"(b.xy));
+    asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(hi) : "v"(a.zw), "v"(b.zw));
+    return (f4){lo.x, lo.y, hi.x, hi.y};
+}
 
 // The workgroup's cross-wave combine: per frame the block's 16-voice group sums in group (= voice index) order
 // (synth.rs:177-195's order), from sWbuf[n_groups][super_frames] into the block's partial row (and, for a one-workgroup
@@ -1340,18 +1348,34 @@ __device__ __forceinline__ void pool_loop(const S2rRenderArgs &a, const S2rPool 
 //   AFLAT (with SMALL): every started voice of the wave sits in an amplitude stage of slope +-0 (sustain, end) for
 //   the whole run, so slope * (t - base) + y0 is (+-0) + y0 with the product's sign fixed by the slope's (t >= base
 //   inside a stage): one evaluation per chunk, at its first frame, is every frame's value bit for bit.
-template <int OSC, int SRC, int FILT = 0, bool FMV = false, int NZ = 0, bool AFLAT = false>
+//   UW (with SRC == 1, ALIGNED, not AFLAT, the one-pole filter, no FM; every lane live): the wave is a cohort — same offset,
+//   seed, amplitude line and table entry on all 64 lanes — so the chunk's x, 1 - x, amplitude and noise are the same
+//   sixteen numbers on every lane: `win` points at them in the wave's window in LDS (uw_fill below computed them with
+//   this function's own expressions), four planes S2R_UW_FRAMES floats apart, and the chunk reads them with sixteen
+//   16-byte reads at one address for all lanes instead of eight global loads and ~50 instructions of arithmetic per lane.
+template <int OSC, int SRC, int FILT = 0, bool FMV = false, int NZ = 0, bool AFLAT = false, bool UW = false>
 __device__ __forceinline__ void chunk_fast(const S2rRenderParams &p, VoiceRegs &r, const EnvRun &ea, const EnvRun &em,
                                            const FlatCache &fc, const OscK &k, uint32_t o_chunk, const float *tab,
                                            const uint64_t *sT, const float *sSin, bool live, uint32_t tile_m0,
-                                           float *pv_dst, const FiltCoef *fcoef = nullptr, Filt2 *f2 = nullptr) {
+                                           float *pv_dst, const FiltCoef *fcoef = nullptr, Filt2 *f2 = nullptr,
+                                           const float *win = nullptr) {
     constexpr bool SMALL = NZ >= 1, ALIGNED = NZ == 2;
+    static_assert(!UW || (SRC == 1 && FILT == 0 && !FMV && NZ == 2 && !AFLAT), "the uniform window replaces one variant only");
     tile_set_base(tile_m0);
     // table planes: the filter's coefficients (x and 1 - x for the one-pole, alpha / beta / gamma for the others), then
     // under FM pow(2, mod * amt_osc).  Four 16-byte loads per plane (dword-aligned: the index follows the voice's
     // offset), issued first and used last
     f4 xq[4], bq[4], gq[4], pq[4], iq[4];
-    if (SRC == 1) {
+    f4 a0w[4], ampw[4], nzw[4];                                  // UW: the window's 1 - x, amplitudes and noise
+    if (UW) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            xq[q] = *reinterpret_cast<const f4 *>(win + 4 * q);
+            a0w[q] = *reinterpret_cast<const f4 *>(win + S2R_UW_FRAMES + 4 * q);
+            ampw[q] = *reinterpret_cast<const f4 *>(win + 2u * S2R_UW_FRAMES + 4 * q);
+            nzw[q] = *reinterpret_cast<const f4 *>(win + 3u * S2R_UW_FRAMES + 4 * q);
+        }
+    } else if (SRC == 1) {
         const uint32_t plane = p.tab.plane;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -1387,7 +1411,7 @@ __device__ __forceinline__ void chunk_fast(const S2rRenderParams &p, VoiceRegs &
     // holds across the chunk come back as spills in the moving-stage variants, the waves that set the kernel's length:
     // the launch no shorter, 0.0446 against 0.0439 ms.)
     f4 nzt[4];
-    if (ALIGNED) {
+    if (ALIGNED && !UW) {
         const float *np = p.noise_tab + ((r.seed_rot ^ o_chunk) & 0xffffu);
 #pragma unroll
         for (int q = 0; q < 4; ++q) nzt[q] = *reinterpret_cast<const f4 *>(np + 4 * q);
@@ -1395,7 +1419,10 @@ __device__ __forceinline__ void chunk_fast(const S2rRenderParams &p, VoiceRegs &
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         f4 t;
-        if (ALIGNED) {
+        if (UW) {
+            nz[q] = nzw[q]; amp[q] = ampw[q];
+            continue;
+        } else if (ALIGNED) {
             t = t_small;
             t_small = t_small + splat(4.0f);
             nz[q] = nzt[q];
@@ -1441,7 +1468,7 @@ __device__ __forceinline__ void chunk_fast(const S2rRenderParams &p, VoiceRegs &
         // filters.rs:23.  A lane without a started voice must put +0.0 into the mix (synth.rs:178 skips
         // it): with a0 = 0 and last = 0 its y is 0*s + x*0 = +0 for every finite s and x >= 0, and
         // (+0) * (amp = +0) = +0 — no select per frame
-        f4 a0 = splat(1.0f) - xq[q];
+        f4 a0 = UW ? a0w[q] : SRC == 1 ? pk_sub4(splat(1.0f), xq[q]) : splat(1.0f) - xq[q];
         if (SRC == 2 && !live) a0 = splat(0.0f);                 // SRC 1: such a lane reads the tables' x = 1, 1 - x = 0 entries
         // the quad's oscillator constants: the run's (k), or under FM each frame's period and 1 / period (from the
         // tables' pow2 plane) with the rest by exact scalings (make_osck)
@@ -1501,6 +1528,35 @@ __device__ __forceinline__ void chunk_fast(const S2rRenderParams &p, VoiceRegs &
 #pragma unroll
         for (int q = 0; q < 4; ++q) *reinterpret_cast<f4u *>(pv_dst + 4 * q) = outs[q];
     }
+}
+
+// Fills a cohort wave's window for a run of `run` chunks that starts at frame offset o_run (the same on every lane; see UW
+// at chunk_fast): quad Q of the run — frames 4 Q .. 4 Q + 3 — is computed by lane Q mod 64, so that a store's 64 lanes
+// write 1 KiB of consecutive LDS (no bank conflicts) and a load's read consecutive table entries.  Every value is
+// chunk_fast's own expression on the same operands — load_f4u of the coefficient plane, 1 - x, slope * (t - base) + y0
+// with t = the frame offset as f32 (exact below 2^24, as chunk_fast's stepped t is), the noise table's entry — computed
+// once instead of on 64 lanes.  Quads beyond the run are not touched: their table entries need not exist.
+__device__ __forceinline__ void uw_fill(const S2rRenderParams &p, const EnvRun &ea, uint32_t seed_rot, uint32_t o_run, uint32_t run,
+                                        const float *tab_run, float *win, uint32_t lane) {
+    const uint32_t n_quads = 4u * run;
+    for (uint32_t q0 = 0; q0 < n_quads; q0 += 64u) {              // wave-uniform
+        const uint32_t Q = q0 + lane;
+        if (Q < n_quads) {
+            const uint32_t o = o_run + 4u * Q;
+            const f4 x = load_f4u(tab_run + 4u * Q);
+            const f4 a0 = pk_sub4(splat(1.0f), x);
+            const f4 t = splat((float)o) + (f4){0.0f, 1.0f, 2.0f, 3.0f};
+            const f4 amp = splat(ea.s0) * pk_add4(t, splat(-ea.s1)) + splat(ea.s2);
+            // (seed ^ (o + j)) & 0xffff == ((seed ^ oc) & 0xffff) + (o + j - oc) for the chunk start oc = o & ~15: ALIGNED
+            const f4 nz = *reinterpret_cast<const f4 *>(p.noise_tab + ((seed_rot ^ (o & ~15u)) & 0xffffu) + (o & 15u));
+            float *w = win + 4u * Q;
+            *reinterpret_cast<f4 *>(w) = x;
+            *reinterpret_cast<f4 *>(w + S2R_UW_FRAMES) = a0;
+            *reinterpret_cast<f4 *>(w + 2u * S2R_UW_FRAMES) = amp;
+            *reinterpret_cast<f4 *>(w + 3u * S2R_UW_FRAMES) = nz;
+        }
+    }
+    __builtin_amdgcn_wave_barrier();
 }
 
 }  // namespace

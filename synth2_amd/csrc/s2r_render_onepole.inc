@@ -14,7 +14,8 @@ namespace {
 
 // One fill of the workgroup's voices.  `ctl`: what changes from fill to fill — the kernel arguments' own values (one
 // launch per fill), or the command the host has just posted to the resident kernel (below).
-template <int OSC, bool FM, int MODE, int MAXT>
+// UWK: the launch-per-fill form of 256-thread workgroups, the one form that may have a uniform window (S2rRenderParams.uw_frames)
+template <int OSC, bool FM, int MODE, int MAXT, bool UWK = false>
 __device__ __forceinline__ void render_fill(const S2rRenderArgs &a, const FillCtl &ctl) {
     const S2rRenderParams &p = a.p;
     constexpr bool PV = MODE == 1;       // also store every voice's frames (mix-disabled debug/parity output)
@@ -39,7 +40,10 @@ __device__ __forceinline__ void render_fill(const S2rRenderArgs &a, const FillCt
     constexpr uint32_t kTile = kChunk * kTileRow;
     const uint32_t sw_floats = s2r_sw_buffers(p.frames, kSuper) * n_groups * kSuper;
     float *const tile = s_dyn + sw_floats + wave * kTile;
-    float *const wave_scratch = s_dyn + sw_floats + n_waves * kTile + wave * 64u;   // 64 floats per wave
+    // 64 floats per wave, and behind them the wave's uniform window where the launch has one (launch_mode sized it:
+    // S2R_UW_PLANES planes of p.uw_frames floats; the window hangs on the scratch so that no second address is kept)
+    float *const wave_scratch = s_dyn + sw_floats + n_waves * kTile + wave * (64u + (UWK ? S2R_UW_PLANES * p.uw_frames : 0u));
+    uint32_t uw_chunks = 0;                                      // chunks this wave rendered through the window
     // the tile's LDS byte address (the low half of a generic pointer into LDS), for the address-free stores of chunk_fast
     const uint32_t tile_lds = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)tile);
     const uint32_t vi = blockIdx.x * blockDim.x + tid;
@@ -245,11 +249,22 @@ __device__ __forceinline__ void render_fill(const S2rRenderArgs &a, const FillCt
     //   w_aflat   every started voice's amplitude envelope in a zero-slope stage
     //   w_aligned chunk starts are multiples of 16 frames and rotl(seed, 5) has a zero low nibble, on every lane
     //   w_small   no offset passes 2^24 during this fill
-    bool w_flat = false, w_aflat = false, w_aligned = false, w_small = false;
+    //   w_uni     a cohort: all 64 lanes started, with the same offset, seed, amplitude line and mod stage, whose table
+    //             entry advances with the offset (tab_cursor) and is therefore the same too: what chunk_fast<UW> needs
+    bool w_flat = false, w_aflat = false, w_aligned = false, w_small = false, w_uni = false;
+    auto classify_uniform = [&]() {
+        if (!(UWK && !FM) || p.uw_frames == 0u) return;           // (no window: w_uni stays false)
+        const TabCur c = tab_cursor(p.tab, em.s4, r.ro_m > p.mod.sus_off, r.release_u, live);
+        auto differs = [](uint32_t v) { return v != (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
+        const bool odd = !live || c.mask != 0xffffffffu || differs((uint32_t)c.idx) || differs(r.offset) || differs(r.seed_rot) ||
+                         differs(s2r_f2u(ea.s0)) || differs(s2r_f2u(ea.s1)) || differs(s2r_f2u(ea.s2)) || differs(s2r_f2u(em.s4));
+        w_uni = __ballot(odd) == 0ull;
+    };
     auto reclassify_stages = [&]() {                             // what a stage change can move
         w_flat = !p.no_flat_shortcut && __ballot(live && em.s0 != 0.0f) == 0ull &&
                  (!FM || __ballot(!(fc.k.period >= 0x1p-126f && fc.k.period < __builtin_inff())) == 0ull);
         w_aflat = __ballot(live && ea.s0 != 0.0f) == 0ull;
+        classify_uniform();
     };
     auto reclassify = [&]() {
         reclassify_stages();
@@ -345,6 +360,7 @@ __device__ __forceinline__ void render_fill(const S2rRenderArgs &a, const FillCt
         w_flat = !p.no_flat_shortcut && __ballot(live && em.s0 != 0.0f) == 0ull &&
                  (!FM || __ballot(!(fc.k.period >= 0x1p-126f && fc.k.period < __builtin_inff())) == 0ull);
         w_aflat = __ballot(live && ea.s0 != 0.0f) == 0ull;
+        classify_uniform();
     };
 
     // The two stage changes that are as frequent as the note-offs themselves, by hand (the cascade is two dozen compares
@@ -603,10 +619,17 @@ __device__ __forceinline__ void render_fill(const S2rRenderArgs &a, const FillCt
                         // this lane's entry in the coefficient tables for the run's first frame; it advances with the
                         // offset in the attack, decay and release stages and stays put in sustain / after the end
                         const TabCur cur = tab_cursor(p.tab, em.s4, r.ro_m > p.mod.sus_off, r.release_u, live);
-                        auto run_chunks = [&](auto src_tag, auto nz_tag, auto aflat_tag) {
+                        auto run_chunks = [&](auto src_tag, auto nz_tag, auto aflat_tag, auto uw_tag) {
                             constexpr int SRC = decltype(src_tag)::value;
                             constexpr int NZ = decltype(nz_tag)::value;
                             constexpr bool AFLAT = decltype(aflat_tag)::value;
+                            constexpr bool UW = decltype(uw_tag)::value;
+                            if (UW) {
+                                // the run's coefficients, amplitudes and noise, once for the wave (the pending sum reads the tile, not the window)
+                                const uint32_t o_run = (uint32_t)__builtin_amdgcn_readfirstlane((int)o_chunk);
+                                uw_fill(p, ea, r.seed_rot, o_run, run, p.tab.base + (ptrdiff_t)(cur.idx + (int32_t)o_chunk), wave_scratch + 64u, lane);
+                                uw_chunks += run;
+                            }
                             for (uint32_t i = 0; i < run; ++i) {
                                 const uint32_t f0 = c16 + i * kChunk;            // frame inside the super-chunk
                                 // the previous fast chunk's sums, stored unconditionally (into a scratch slot when none is
@@ -615,8 +638,8 @@ __device__ __forceinline__ void render_fill(const S2rRenderArgs &a, const FillCt
                                 float *pvd = (PV && in_range) ? p.per_voice + pv_base + sc0 + f0 : nullptr;
                                 const uint32_t oc = o_chunk + i * kChunk;
                                 const float *tp = p.tab.base + (ptrdiff_t)(cur.idx + (int32_t)(oc & cur.mask));
-                                chunk_fast<OSC, SRC, 0, (FM && SRC == 1), NZ, AFLAT>(p, r, ea, em, fc, FM ? fc.k : k_const, oc, tp, sT, sSin, live,
-                                                                              tile_lds, pvd);
+                                chunk_fast<OSC, SRC, 0, (FM && SRC == 1), NZ, AFLAT, UW>(p, r, ea, em, fc, FM ? fc.k : k_const, oc, tp, sT, sSin, live,
+                                                                              tile_lds, pvd, nullptr, nullptr, wave_scratch + 64u + i * kChunk);
                                 __builtin_amdgcn_wave_barrier();
                                 pend_dst = sw_row + f0;
                             }
@@ -632,20 +655,26 @@ __device__ __forceinline__ void render_fill(const S2rRenderArgs &a, const FillCt
                         const bool aflat = aligned && w_aflat;
                         using T = std::true_type; using F = std::false_type;
                         using N0 = std::integral_constant<int, 0>; using N1 = std::integral_constant<int, 1>; using N2 = std::integral_constant<int, 2>;
+                        // ... and a cohort of 64 voices with a run long enough for the window's fill to pay: about one chunk's
+                        // feed-forward work and 16 LDS stores per 64 chunks' worth of frames, against ~50 instructions and eight
+                        // global loads saved per chunk — from S2R_UW_MIN_RUN chunks on
+                        using UWon = std::integral_constant<bool, UWK && !FM>;
+                        const bool uw = UWon::value && w_uni && run >= S2R_UW_MIN_RUN;
                         if (tab_ok) {
-                            if (aflat) run_chunks(N1{}, N2{}, T{});
-                            else if (aligned) run_chunks(N1{}, N2{}, F{});
-                            else if (small) run_chunks(N1{}, N1{}, F{});
-                            else run_chunks(N1{}, N0{}, F{});
+                            if (aflat) run_chunks(N1{}, N2{}, T{}, F{});
+                            else if (aligned && uw) run_chunks(N1{}, N2{}, F{}, UWon{});
+                            else if (aligned) run_chunks(N1{}, N2{}, F{}, F{});
+                            else if (small) run_chunks(N1{}, N1{}, F{}, F{});
+                            else run_chunks(N1{}, N0{}, F{}, F{});
                         } else if (flat) {
-                            if (aflat) run_chunks(N0{}, N2{}, T{});
-                            else if (aligned) run_chunks(N0{}, N2{}, F{});
-                            else if (small) run_chunks(N0{}, N1{}, F{});
-                            else run_chunks(N0{}, N0{}, F{});
+                            if (aflat) run_chunks(N0{}, N2{}, T{}, F{});
+                            else if (aligned) run_chunks(N0{}, N2{}, F{}, F{});
+                            else if (small) run_chunks(N0{}, N1{}, F{}, F{});
+                            else run_chunks(N0{}, N0{}, F{}, F{});
                         } else if (!FM) {
-                            if (aligned) run_chunks(N2{}, N2{}, F{});
-                            else if (small) run_chunks(N2{}, N1{}, F{});
-                            else run_chunks(N2{}, N0{}, F{});
+                            if (aligned) run_chunks(N2{}, N2{}, F{}, F{});
+                            else if (small) run_chunks(N2{}, N1{}, F{}, F{});
+                            else run_chunks(N2{}, N0{}, F{}, F{});
                         }
                         c16 += (run - 1u) * kChunk;
                         dbg_t_run += S2R_DBG_NOW() - dbg_tr0;
@@ -721,6 +750,8 @@ __device__ __forceinline__ void render_fill(const S2rRenderArgs &a, const FillCt
             }
         }
     }
+    // (one atomic per wave and fill: the handle's count of window chunks, s2r_uniform_window_chunks)
+    if (UWK && uw_chunks != 0u && lane == 0u) __hip_atomic_fetch_add(p.uw_count, uw_chunks, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (p.direct_out && ctl.granules == nullptr) signal_done(ctl.done, 1u);     // (a shard of one workgroup: its output is the fill's)
     if (ctl.ov_render_counter != nullptr) ov_signal(ctl.ov_render_counter);   // (two streams: the mix on the other one waits for every workgroup's row)
 #if defined(S2R_STAMPS)
@@ -740,7 +771,7 @@ __device__ __forceinline__ void render_fill(const S2rRenderArgs &a, const FillCt
 template <int OSC, bool FM, int MODE, int MAXT>
 __global__ void __launch_bounds__(MAXT, (MAXT == 256 ? 2 : 1)) s2r_render_kernel(const S2rRenderArgs a) {
     const FillCtl ctl = fill_ctl_from_args(a);
-    render_fill<OSC, FM, MODE, MAXT>(a, ctl);
+    render_fill<OSC, FM, MODE, MAXT, MAXT == 256>(a, ctl);
 }
 
 // The resident kernel (S2rResident, s2r_device.h): wave 0 polls the command, the workgroup renders the fill it describes
@@ -803,7 +834,16 @@ hipError_t launch_mode(const S2rRenderArgs &a0, uint32_t block_voices, hipStream
     const uint32_t n_waves = block_voices / 64, n_groups = n_waves * 4;
     // keeps the staging (group sums + two transpose tiles per wave) under the 160 KiB of LDS
     p.super_frames = s2r_pick_super_frames(n_groups, grid, p.frames);
-    const size_t lds = sizeof(float) * ((size_t)s2r_sw_buffers(p.frames, p.super_frames) * n_groups * p.super_frames + (size_t)n_waves * (kChunk * kTileRow + 64));
+    size_t lds = sizeof(float) * ((size_t)s2r_sw_buffers(p.frames, p.super_frames) * n_groups * p.super_frames + (size_t)n_waves * (kChunk * kTileRow + 64));
+    // The uniform window: S2R_UW_PLANES x S2R_UW_FRAMES floats per wave behind the rest, only where the workgroup has its compute
+    // unit to itself and the fill is one super-chunk, and only if it fits the 160 KiB beside the group sums, the tiles and
+    // the kernel's static tables (exp2 and sine: at most 8 KiB + 8 * S2R_EXP2F_N + a word).  Otherwise none: the kernel
+    // then runs exactly the variants it ran before there was a window.
+    p.uw_frames = 0u;
+    if (p.uw_count != nullptr && !FM && block_voices <= 256 && p.super_frames == kSuperWhole && s2r_sw_buffers(p.frames, p.super_frames) == 1u) {
+        const size_t with_uw = lds + sizeof(float) * (size_t)n_waves * S2R_UW_PLANES * S2R_UW_FRAMES;
+        if (with_uw + 8192u + 8u * S2R_EXP2F_N + 64u <= 160u * 1024u) { lds = with_uw; p.uw_frames = S2R_UW_FRAMES; }
+    }
     if (lds > 65536) {                                           // (HIP wants to be told about more than 64 KiB of dynamic LDS)
         static thread_local size_t told256 = 0, told1024 = 0;
         if (block_voices <= 256 && told256 < lds) {
@@ -831,6 +871,7 @@ hipError_t launch_resident(const S2rRenderArgs &a0, const S2rResident &rs, uint3
     if (block_voices > 256u || p.n_voices > block_voices || p.direct_out == nullptr || p.per_voice != nullptr || p.tev != nullptr) return hipErrorInvalidValue;
     const uint32_t n_waves = block_voices / 64, n_groups = n_waves * 4;
     p.super_frames = s2r_pick_super_frames(n_groups, 1u, p.frames);
+    p.uw_frames = 0u;                                            // (no uniform window in the resident form)
     const size_t lds = sizeof(float) * ((size_t)s2r_sw_buffers(p.frames, p.super_frames) * n_groups * p.super_frames + (size_t)n_waves * (kChunk * kTileRow + 64));
     if (lds > 65536) {
         static thread_local size_t told = 0;
@@ -853,6 +894,7 @@ hipError_t launch_pool(const S2rRenderArgs &a0, const S2rPool &pl, uint32_t bloc
     const uint32_t grid = (p.n_voices + block_voices - 1) / block_voices;
     const uint32_t n_waves = block_voices / 64, n_groups = n_waves * 4;
     p.super_frames = s2r_pick_super_frames(n_groups, grid, p.frames);
+    p.uw_frames = 0u;                                            // (no uniform window in the pool-resident form)
     const size_t lds = sizeof(float) * ((size_t)s2r_sw_buffers(p.frames, p.super_frames) * n_groups * p.super_frames + (size_t)n_waves * (kChunk * kTileRow + 64));
     if (lds > 65536) {
         static thread_local size_t told = 0;

@@ -244,6 +244,8 @@ def load_library():
         "s2r_exchange_attach": (C.c_int, [H, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t]),
         "s2r_set_flat_shortcut": (C.c_int, [H, C.c_int]),
         "s2r_set_coeff_stream": (C.c_int, [H, C.c_int]),
+        "s2r_set_uniform_window": (C.c_int, [H, C.c_int]),
+        "s2r_uniform_window_chunks": (C.c_int, [H, C.POINTER(C.c_uint64)]),
         "s2r_last_render_ms": (C.c_float, [H]),
         "s2r_last_error": (C.c_char_p, [H]),
         "s2r_parse_patch_text": (C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(Patch), C.c_char_p, C.c_size_t]),
@@ -906,6 +908,16 @@ class Synth:
         events ride in the render kernel's arguments; 2: tables, events always through their own launch; 3 / 4: synonyms
         of 1 / 2"""
         self._check(self.L.s2r_set_coeff_stream(self.h, int(enabled)))
+
+    def set_uniform_window(self, enabled=True):
+        """measurement aid (default on): cohort waves read their chunks' uniform inputs from an LDS window; same bits"""
+        self._check(self.L.s2r_set_uniform_window(self.h, 1 if enabled else 0))
+
+    def uniform_window_chunks(self):
+        """16-frame chunks rendered through the uniform window since the handle was created"""
+        n = C.c_uint64(0)
+        self._check(self.L.s2r_uniform_window_chunks(self.h, C.byref(n)))
+        return int(n.value)
 
     def set_low_latency(self, enabled=True):
         """a resident render kernel between sample() calls (small pools, s2r.h: s2r_set_low_latency): the reference's own
