@@ -153,6 +153,27 @@ class Synth {
                                float *out_lr) {
         return s2r_delay_reference(delay_frames, feedback, cross, dry, wet, x_lr, frames, history_lr, out_lr);
     }
+    // per-bus chorus in front of the bus's delay (build-defined; s2r.h: s2r_set_bus_chorus): voices in 1 .. S2R_CHORUS_MAX_VOICES, base >= 1 and
+    // depth >= 0 frames with float(base + depth) <= S2R_CHORUS_MAX_DELAY, phase_inc (chorus_rate) and spread in 2^-32 turns, dry and wet in
+    // [0, 1] (1 / voices goes into wet); in sample_buses and sample_master only
+    void set_bus_chorus(uint32_t bus, uint32_t voices, float base, float depth, uint32_t phase_inc, uint32_t spread = 0, float dry = 1.0f, float wet = 1.0f) {
+        check(s2r_set_bus_chorus(h_, bus, voices, base, depth, phase_inc, spread, dry, wet));
+    }
+    void clear_bus_chorus(uint32_t bus) { check(s2r_set_bus_chorus(h_, bus, 0, 0.0f, 0.0f, 0, 0, 0.0f, 0.0f)); }
+    void set_bus_chorus_mix(uint32_t bus, float dry, float wet) { check(s2r_set_bus_chorus_mix(h_, bus, dry, wet)); }
+    void set_bus_chorus_rate(uint32_t bus, uint32_t phase_inc, uint32_t spread) { check(s2r_set_bus_chorus_rate(h_, bus, phase_inc, spread)); }     // phase and history stay
+    void get_bus_chorus(uint32_t bus, uint32_t *voices, float *base, float *depth, uint32_t *phase_inc, uint32_t *spread, float *dry, float *wet) const {
+        check(s2r_get_bus_chorus(h_, bus, voices, base, depth, phase_inc, spread, dry, wet));
+    }
+    // 2 * chorus_history_frames(base, depth) floats, oldest first, L R, and the LFO's phase
+    void bus_chorus_state(uint32_t bus, float *lr, size_t capacity, uint32_t *phase) { check(s2r_get_bus_chorus_state(h_, bus, lr, capacity, phase)); }
+    void set_bus_chorus_state(uint32_t bus, const float *lr, size_t count, uint32_t phase) { check(s2r_set_bus_chorus_state(h_, bus, lr, count, phase)); }
+    static uint32_t chorus_history_frames(float base, float depth) { return s2r_chorus_history_frames(base, depth); }
+    static uint32_t chorus_rate(double hz, double sample_rate) { return (uint32_t)(uint64_t)(hz * 4294967296.0 / sample_rate + 0.5); }
+    static int chorus_reference(uint32_t voices, float base, float depth, uint32_t phase_inc, uint32_t spread, float dry, float wet, const float *x_lr,
+                                uint32_t frames, float *history_lr, uint32_t *phase, float *out_lr) {
+        return s2r_chorus_reference(voices, base, depth, phase_inc, spread, dry, wet, x_lr, frames, history_lr, phase, out_lr);
+    }
 
     // the master section (build-defined; s2r.h: s2r_fill_master): a return level per bus and a master fader, each in [0, 1] and each
     // reaching its target as a ramp across the next sample_master call, and the meters of that call — in sample_master only

@@ -40,7 +40,9 @@ extern "C" {
  * s2r_get_bus_return, s2r_set_master_fader, s2r_get_master_fader, s2r_snap_master, s2r_fill_master, s2r_get_meters,
  * s2r_master_reference, s2r_set_master_limiter, s2r_clear_master_limiter, s2r_get_master_limiter, s2r_get_limiter_state,
  * s2r_set_limiter_state, s2r_get_limiter_meters, s2r_limiter_reference, s2r_set_bus_delay, s2r_set_bus_delay_mix,
- * s2r_get_bus_delay, s2r_get_bus_delay_history, s2r_set_bus_delay_history, s2r_delay_reference. */
+ * s2r_get_bus_delay, s2r_get_bus_delay_history, s2r_set_bus_delay_history, s2r_delay_reference, s2r_chorus_history_frames,
+ * s2r_set_bus_chorus, s2r_set_bus_chorus_mix, s2r_set_bus_chorus_rate, s2r_get_bus_chorus, s2r_get_bus_chorus_state,
+ * s2r_set_bus_chorus_state, s2r_chorus_reference. */
 #define S2R_ABI_VERSION 4
 
 typedef enum {
@@ -430,6 +432,66 @@ int s2r_get_bus_delay_history(s2r_synth *s, uint32_t bus, float *lr, size_t capa
 int s2r_set_bus_delay_history(s2r_synth *s, uint32_t bus, const float *lr, size_t count);
 int s2r_delay_reference(uint32_t delay_frames, float feedback, float cross, float dry, float wet, const float *x_lr, uint32_t frames,
                         float *history_lr, float *out_lr);
+
+/* BUILD-DEFINED per-bus chorus (an ensemble: a modulated multi-voice delay; the reference has no effects), computed on
+ * the device in front of the bus's delay: combine -> chorus -> delay -> reverb -> master -> limiter.  A bus b in [0, S2R_MAX_BUSES)
+ * may carry a chorus: V voices (1 .. S2R_CHORUS_MAX_VOICES); a `base` >= 1 and a `depth` >= 0 in frames, finite, with
+ * fl(base + depth) <= S2R_CHORUS_MAX_DELAY (the sum rounded to binary32); a `phase_inc` and a `spread`, any uint32_t, in units of
+ * 2^-32 turns: the LFO's step per frame, round(hz * 2^32 / sample_rate), and the right channel's lead over the left; a `dry` and a
+ * `wet` in [0, 1].  Its state: a `phase` (uint32_t), and a history of H = floor(fl(base + depth)) + 1 stereo frames of the INPUT;
+ * 0 and +0.0 right after the chorus is set.  With x_c[n] what the bus combine writes for bus b, channel c (0 left, 1 right), frame n
+ * of a call of N frames, and x_c[n] for n < 0 the history, for voice v = 0 .. V - 1:
+ *   off = (uint32)(((uint64)v << 32) / V) + c * spread         (mod 2^32)
+ *   p   = phase + off + phase_inc * (uint32)n                  (mod 2^32: uint32 arithmetic throughout)
+ *   q   = p >> 8                                               (0 .. 2^24 - 1)
+ *   h   = q < 2^23 ? q : 2^24 - q                              (0 .. 2^23: a triangle)
+ *   m   = (float)h * 2^-23                                     (exact, in [0, 1])
+ *   d   = base + (depth * m)                                   (the product rounded, then the sum)
+ *   i   = (uint32)d                                            (d >= 1: truncation is floor)
+ *   f   = d - (float)i                                         (exact, in [0, 1))
+ *   a   = x_c[n - i]      bb = x_c[n - i - 1]
+ *   e   = bb - a          g = f * e          tap_v = a + g
+ * then acc = tap_0, acc = acc + tap_v in voice order, and y_c[n] = (dry * x_c[n]) + (wet * acc): binary32 throughout, every product
+ * and every sum rounded on its own (no fma), denormals kept, no operation skipped for a zero coefficient or for f == 0 (a + g may
+ * turn a -0.0 into +0.0, and the rule says so).  1 / V is the caller's business: it goes into `wet`.  Rounding is monotonic, so
+ * depth * m <= depth, d <= fl(base + depth) and i + 1 <= H: no tap leaves the history.  Non-finite bus samples are outside the
+ * contract.  After a call that returns S2R_OK the history is the last H frames of (old history, then x[0 .. N)) and the phase is
+ * phase + phase_inc * N (mod 2^32): calls of any lengths concatenate.  y is the bus's signal from there on: a delay on the same bus
+ * takes it as its x, otherwise a reverb as its dry signal, otherwise the stems and the master section.  The chorus runs once per
+ * call over all N frames, after every event segment and rows slice of the call has been mixed.  A chorus on a bus >= the call's
+ * n_buses is idle in that call (no output, state untouched).  A bus without a chorus passes through bit for bit, -0.0 included.  A
+ * refused or failed call leaves history and phase untouched.  ONLY s2r_fill_buses and s2r_fill_master apply choruses; every other
+ * fill ignores them.  A chorus is a property of the bus: s2r_set_patch_bank, program changes and s2r_import_state leave it alone.  A
+ * handle on which no chorus was ever set launches what it launched before and allocates nothing for one.  The two copies of the
+ * history and a staging buffer for the combined buses live in device memory allocated when a chorus is set (S2R_ERR_OUT_OF_MEMORY
+ * when that fails, and the earlier chorus is kept), never inside a fill, and released with the handle.
+ *   s2r_chorus_history_frames: H for a (base, depth) in range, 0 otherwise; needs no handle.
+ *   s2r_set_bus_chorus: replaces any earlier chorus of the bus, zeroes its history and its phase; voices == 0 removes it (the other
+ *   values are then not looked at).  S2R_ERR_PATCH_RANGE for a NaN, a value outside its range, voices > S2R_CHORUS_MAX_VOICES or
+ *   bus >= S2R_MAX_BUSES (checked before the handle is looked at; nothing is changed).
+ *   s2r_set_bus_chorus_mix: dry and wet alone.  s2r_set_bus_chorus_rate: phase_inc and spread alone — the phase and the history stay,
+ *   so the LFO bends without a click.  S2R_ERR_INVALID on a bus without a chorus.
+ *   s2r_get_bus_chorus: voices is 0 for a bus without one; any pointer may be NULL.
+ *   s2r_get_bus_chorus_state / s2r_set_bus_chorus_state: the 2 * H floats of the history, oldest frame first, L then R inside a
+ *   frame, and the phase: the checkpoint companions of the delay's pair.  S2R_ERR_INVALID for a capacity below, or a count other
+ *   than, 2 * H, a NULL lr, and on a bus without a chorus; `phase` may be NULL in the getter.
+ *   Single-device handles (a NULL or a device-list handle: S2R_ERR_INVALID from all six).
+ *   s2r_chorus_reference: the rule above for both channels on the host (no device, no handle): x_lr is [frames][2]; history_lr is
+ *   [H][2], oldest frame first, and *phase the phase: both are updated in place to the state after the call; out_lr, [frames][2], may
+ *   be NULL.  Range checks as above (and voices >= 1); S2R_ERR_INVALID for a NULL history_lr or phase, or a NULL x_lr with frames > 0. */
+#define S2R_CHORUS_MAX_VOICES 8u
+#define S2R_CHORUS_MAX_DELAY  4095.0f
+uint32_t s2r_chorus_history_frames(float base, float depth);
+int s2r_set_bus_chorus(s2r_synth *s, uint32_t bus, uint32_t voices, float base, float depth, uint32_t phase_inc, uint32_t spread, float dry,
+                       float wet);
+int s2r_set_bus_chorus_mix(s2r_synth *s, uint32_t bus, float dry, float wet);
+int s2r_set_bus_chorus_rate(s2r_synth *s, uint32_t bus, uint32_t phase_inc, uint32_t spread);
+int s2r_get_bus_chorus(const s2r_synth *s, uint32_t bus, uint32_t *voices, float *base, float *depth, uint32_t *phase_inc, uint32_t *spread,
+                       float *dry, float *wet);
+int s2r_get_bus_chorus_state(s2r_synth *s, uint32_t bus, float *lr, size_t capacity, uint32_t *phase);
+int s2r_set_bus_chorus_state(s2r_synth *s, uint32_t bus, const float *lr, size_t count, uint32_t phase);
+int s2r_chorus_reference(uint32_t voices, float base, float depth, uint32_t phase_inc, uint32_t spread, float dry, float wet, const float *x_lr,
+                         uint32_t frames, float *history_lr, uint32_t *phase, float *out_lr);
 
 /* BUILD-DEFINED master section (the reference's Synth::sample returns one stream; DESIGN.md 4.17 gives the op sequence): the last stage
  * of the chain send -> effect -> return -> master, on the device the bus signals are already on.  Every bus b in [0, S2R_MAX_BUSES) has

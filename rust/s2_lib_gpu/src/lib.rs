@@ -175,6 +175,17 @@ pub mod ffi {
         pub fn s2r_set_bus_delay_history(s: *mut S2rSynth, bus: u32, lr: *const f32, count: usize) -> c_int;
         pub fn s2r_delay_reference(delay_frames: u32, feedback: f32, cross: f32, dry: f32, wet: f32, x_lr: *const f32, frames: u32,
                                    history_lr: *mut f32, out_lr: *mut f32) -> c_int;
+        pub fn s2r_chorus_history_frames(base: f32, depth: f32) -> u32;
+        pub fn s2r_set_bus_chorus(s: *mut S2rSynth, bus: u32, voices: u32, base: f32, depth: f32, phase_inc: u32, spread: u32, dry: f32,
+                                  wet: f32) -> c_int;
+        pub fn s2r_set_bus_chorus_mix(s: *mut S2rSynth, bus: u32, dry: f32, wet: f32) -> c_int;
+        pub fn s2r_set_bus_chorus_rate(s: *mut S2rSynth, bus: u32, phase_inc: u32, spread: u32) -> c_int;
+        pub fn s2r_get_bus_chorus(s: *const S2rSynth, bus: u32, voices: *mut u32, base: *mut f32, depth: *mut f32, phase_inc: *mut u32,
+                                  spread: *mut u32, dry: *mut f32, wet: *mut f32) -> c_int;
+        pub fn s2r_get_bus_chorus_state(s: *mut S2rSynth, bus: u32, lr: *mut f32, capacity: usize, phase: *mut u32) -> c_int;
+        pub fn s2r_set_bus_chorus_state(s: *mut S2rSynth, bus: u32, lr: *const f32, count: usize, phase: u32) -> c_int;
+        pub fn s2r_chorus_reference(voices: u32, base: f32, depth: f32, phase_inc: u32, spread: u32, dry: f32, wet: f32, x_lr: *const f32,
+                                    frames: u32, history_lr: *mut f32, phase: *mut u32, out_lr: *mut f32) -> c_int;
         pub fn s2r_set_bus_return(s: *mut S2rSynth, bus: u32, level: f32) -> c_int;
         pub fn s2r_get_bus_return(s: *const S2rSynth, bus: u32, level: *mut f32, applied: *mut f32) -> c_int;
         pub fn s2r_set_master_fader(s: *mut S2rSynth, level: f32) -> c_int;
@@ -230,6 +241,10 @@ pub const MAX_IR_TAPS: u32 = 65536;
 pub const IR_SEGMENT: u32 = 256;
 /// `S2R_MAX_DELAY_FRAMES`: the longest time of a bus delay, in frames.
 pub const MAX_DELAY_FRAMES: u32 = 262144;
+/// `S2R_CHORUS_MAX_VOICES`, `S2R_CHORUS_MAX_DELAY`: the most voices of a bus chorus, and the largest `base + depth` (rounded to f32) in
+/// frames.
+pub const CHORUS_MAX_VOICES: u32 = 8;
+pub const CHORUS_MAX_DELAY: f32 = 4095.0;
 /// `S2R_METER_BLOCK`: the frames of one block of the meters' energy tree (part of the master section's rule).
 pub const METER_BLOCK: u32 = 256;
 /// `S2R_LIMITER_MAX_LOOKAHEAD`, `S2R_LIMITER_MAX_HOLD`: the master limiter's longest lookahead and hold in frames, and
@@ -271,6 +286,31 @@ pub fn delay_reference(delay_frames: u32, feedback: f32, cross: f32, dry: f32, w
     let rc = unsafe {
         ffi::s2r_delay_reference(delay_frames, feedback, cross, dry, wet, x_lr.as_ptr(), (x_lr.len() / 2) as u32, history_lr.as_mut_ptr(),
                                  out.as_mut_ptr())
+    };
+    if rc == 0 { Ok(out) } else { Err(rc) }
+}
+
+/// `s2r_chorus_history_frames`: the stereo frames of history a chorus of (`base`, `depth`) keeps, or 0 for a pair out of range.
+pub fn chorus_history_frames(base: f32, depth: f32) -> u32 {
+    unsafe { ffi::s2r_chorus_history_frames(base, depth) }
+}
+
+/// An LFO rate in Hz as a `phase_inc`: `round(hz * 2^32 / sample_rate)` modulo 2^32.
+pub fn chorus_rate(hz: f64, sample_rate: f64) -> u32 {
+    ((hz * 4294967296.0 / sample_rate).round() as u64 & 0xffff_ffff) as u32
+}
+
+/// Host-only: the bus chorus's rule for both channels (`s2r_chorus_reference`).  `x_lr`: L, R pairs; `history_lr`: the
+/// `2 * chorus_history_frames(base, depth)` floats of input in front of them, oldest frame first, and `phase` the LFO's at the first
+/// pair: both updated in place to the state after the call; returns one output pair per input pair, or the status.
+pub fn chorus_reference(voices: u32, base: f32, depth: f32, phase_inc: u32, spread: u32, dry: f32, wet: f32, x_lr: &[f32], history_lr: &mut [f32],
+                        phase: &mut u32) -> Result<Vec<f32>, i32> {
+    let h = chorus_history_frames(base, depth) as usize;
+    assert!(x_lr.len() % 2 == 0 && (h == 0 || history_lr.len() == 2 * h));
+    let mut out = vec![0.0f32; x_lr.len()];
+    let rc = unsafe {
+        ffi::s2r_chorus_reference(voices, base, depth, phase_inc, spread, dry, wet, x_lr.as_ptr(), (x_lr.len() / 2) as u32, history_lr.as_mut_ptr(),
+                                  phase as *mut u32, out.as_mut_ptr())
     };
     if rc == 0 { Ok(out) } else { Err(rc) }
 }
@@ -642,6 +682,51 @@ pub mod synth {
 
         pub fn set_bus_delay_history(&mut self, bus: u32, lr: &[f32]) {
             self.check(unsafe { ffi::s2r_set_bus_delay_history(self.handle, bus, lr.as_ptr(), lr.len()) });
+        }
+
+        /// Build-defined per-bus chorus (`s2r_set_bus_chorus`, include/s2r.h) in front of the bus's delay: `voices` in
+        /// 1 ..= CHORUS_MAX_VOICES, `base >= 1` and `depth >= 0` frames with `base + depth` (rounded to f32) at most CHORUS_MAX_DELAY,
+        /// `phase_inc` (`chorus_rate`) and `spread` in 2^-32 turns, dry and wet in [0, 1]; replaces any earlier chorus of the bus and
+        /// zeroes its history and phase.  In `sample_buses` and `sample_master` only.
+        pub fn set_bus_chorus(&mut self, bus: u32, voices: u32, base: f32, depth: f32, phase_inc: u32, spread: u32, dry: f32, wet: f32) {
+            assert!(voices >= 1, "clear_bus_chorus removes a chorus");
+            self.check(unsafe { ffi::s2r_set_bus_chorus(self.handle, bus, voices, base, depth, phase_inc, spread, dry, wet) });
+        }
+
+        pub fn clear_bus_chorus(&mut self, bus: u32) {
+            self.check(unsafe { ffi::s2r_set_bus_chorus(self.handle, bus, 0, 0.0, 0.0, 0, 0, 0.0, 0.0) });
+        }
+
+        /// The two levels alone; the chorus's state stays.
+        pub fn set_bus_chorus_mix(&mut self, bus: u32, dry: f32, wet: f32) {
+            self.check(unsafe { ffi::s2r_set_bus_chorus_mix(self.handle, bus, dry, wet) });
+        }
+
+        /// The LFO's step and the channels' spread alone; phase and history stay, so nothing clicks.
+        pub fn set_bus_chorus_rate(&mut self, bus: u32, phase_inc: u32, spread: u32) {
+            self.check(unsafe { ffi::s2r_set_bus_chorus_rate(self.handle, bus, phase_inc, spread) });
+        }
+
+        /// (voices, base, depth, phase_inc, spread, dry, wet); voices is 0 for a bus without a chorus.
+        pub fn get_bus_chorus(&self, bus: u32) -> (u32, f32, f32, u32, u32, f32, f32) {
+            let (mut v, mut pi, mut sp) = (0u32, 0u32, 0u32);
+            let (mut base, mut depth, mut dry, mut wet) = (0.0f32, 0.0f32, 0.0f32, 0.0f32);
+            self.check(unsafe { ffi::s2r_get_bus_chorus(self.handle, bus, &mut v, &mut base, &mut depth, &mut pi, &mut sp, &mut dry, &mut wet) });
+            (v, base, depth, pi, sp, dry, wet)
+        }
+
+        /// The `2 * chorus_history_frames(base, depth)` floats of the chorus's history, oldest frame first, L then R, and the LFO's
+        /// phase: checkpoint companion of `bus_delay_history`.
+        pub fn bus_chorus_state(&mut self, bus: u32) -> (Vec<f32>, u32) {
+            let c = self.get_bus_chorus(bus);
+            let mut lr = vec![0.0f32; 2 * super::chorus_history_frames(c.1, c.2) as usize];
+            let mut phase = 0u32;
+            self.check(unsafe { ffi::s2r_get_bus_chorus_state(self.handle, bus, lr.as_mut_ptr(), lr.len(), &mut phase) });
+            (lr, phase)
+        }
+
+        pub fn set_bus_chorus_state(&mut self, bus: u32, lr: &[f32], phase: u32) {
+            self.check(unsafe { ffi::s2r_set_bus_chorus_state(self.handle, bus, lr.as_ptr(), lr.len(), phase) });
         }
 
         /// Build-defined master section (`s2r_fill_master`, include/s2r.h): the target of a bus's return level (in [0, 1]), reached

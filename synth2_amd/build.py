@@ -19,7 +19,7 @@ LIB = os.path.join(HERE, "libs2r.so")
 SOURCES = ["s2r_render_onepole_square.hip", "s2r_render_onepole_saw.hip", "s2r_render_onepole_triangle.hip",
            "s2r_render_onepole_sine.hip", "s2r_render_general_square.hip", "s2r_render_general_saw.hip",
            "s2r_render_general_triangle.hip", "s2r_render_general_sine.hip", "s2r_render_general_bank.hip",
-           "s2r_aux.hip", "s2r_delay.hip", "s2r_fx.hip", "s2r_master.hip", "s2r_limiter.hip", "s2r_host.cpp", "s2r_post.cpp", "s2r_rules.cpp", "s2r_patch.cpp",
+           "s2r_aux.hip", "s2r_chorus.hip", "s2r_delay.hip", "s2r_fx.hip", "s2r_master.hip", "s2r_limiter.hip", "s2r_host.cpp", "s2r_post.cpp", "s2r_rules.cpp", "s2r_patch.cpp",
            "s2r_stream.cpp"]
 HEADERS = ["s2r_device.h", "s2r_math.h", "s2r_patch.h", "s2r_voices.h", "s2r_kern_common.h", "s2r_render_onepole.inc",
            "s2r_render_general.inc", "s2r_post.h", "s2r_rules.h"]
@@ -50,7 +50,7 @@ PER_FILE_FLAGS = {}
 for _f in ("s2r_render_general_square.hip", "s2r_render_general_saw.hip", "s2r_render_general_triangle.hip", "s2r_render_general_sine.hip",
            "s2r_render_general_bank.hip"):
     PER_FILE_FLAGS[_f] = ["-ftrivial-auto-var-init=zero"]
-# Five translation units are compiled with the back end's resource-usage remarks, and _check_resources() fails the build when a
+# Six translation units are compiled with the back end's resource-usage remarks, and _check_resources() fails the build when a
 # kernel named here went to scratch or spilled, or when fewer kernels report than the file instantiates.  Per source file: the
 # substrings that name its checked kernels; how many reports are expected — ("at least", n), ("exactly", n), or ("each", None):
 # one or more of every name — and why so many; the figures that must be "0"; and what the kernels keep where it belongs.  (The
@@ -65,6 +65,9 @@ RESOURCE_CHECKS = {
     "s2r_fx.hip": (("s2r_fx_stage_kernel", "s2r_fx_convolve_kernel", "s2r_fx_finish_kernel"), ("each", None), "the reverb's three kernels",
                    (_SCRATCH, _VSPILL, _SSPILL), "its windows and sums must stay in registers"),
     # up to sixteen stem samples and eighteen meter values per thread
+    # one frame of the chorus per thread: both channels, up to eight voices, two taps each
+    "s2r_chorus.hip": (("s2r_chorus_kernel",), ("exactly", 1), "one kernel",
+                       (_SCRATCH, _VSPILL, _SSPILL), "its phases, taps and sums must stay in registers"),
     # one residue of the delay per thread: both channels of the line and the loads issued ahead
     "s2r_delay.hip": (("s2r_delay_kernel",), ("exactly", 1), "one kernel",
                       (_SCRATCH, _VSPILL, _SSPILL), "its line pair and the pairs loaded ahead must stay in registers"),

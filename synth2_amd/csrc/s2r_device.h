@@ -453,6 +453,28 @@ struct S2rDelay {
 // a D past S2R_MAX_DELAY_FRAMES, line == next, n_buses past S2R_MAX_BUSES or no delay at all among the call's buses
 hipError_t s2r_launch_bus_delay(const S2rDelay &a, hipStream_t stream);
 
+// The per-bus chorus in front of the delays.  A bus's line holds its H frames of history of the INPUT, oldest first,
+// L, R interleaved; `next` receives the history the next call starts from (the host swaps the two and moves the phase on).
+struct S2rChorusBus {
+    const float *line;            // [H][2]
+    float *next;                  // [H][2], not `line`
+    uint32_t voices;              // V (0: no chorus on this bus: it is copied from `in` to `out`)
+    uint32_t history;             // H = floor(fl(base + depth)) + 1, 2 .. S2R_CHORUS_MAX_DELAY + 1
+    uint32_t phase, phase_inc, spread;
+    float base, depth, dry, wet;
+    uint32_t off[S2R_CHORUS_MAX_VOICES];     // floor(v * 2^32 / V): the left channel's offset of voice v
+};
+struct S2rChorus {
+    S2rChorusBus bus[S2R_MAX_BUSES];
+    const float *in;              // [n_buses][2 * frames]: what the bus combine wrote, bus-major, L, R interleaved inside a bus
+    float *out;                   // the same layout, not `in`: what the next stage, or the caller, reads
+    uint32_t n_buses, frames;
+};
+// one kernel: the choruses' outputs and next histories, the other buses unchanged; hipErrorInvalidValue for a null pointer, in == out,
+// line == next, a V past S2R_CHORUS_MAX_VOICES, an H below 2 or past S2R_CHORUS_MAX_DELAY + 1, n_buses past S2R_MAX_BUSES or no chorus at
+// all among the call's buses
+hipError_t s2r_launch_bus_chorus(const S2rChorus &a, hipStream_t stream);
+
 // The master section of s2r_fill_master: the stems of a call, post-effect, each times its return's ramp, added in
 // bus order from +0.0, times the master fader's ramp; and the call's meters.  gain at frame i of the CALL: r0 + (float)i * dr (the
 // product rounded, then the sum); a pair that did not move has dr = +0.0.

@@ -317,7 +317,7 @@ struct s2r_synth {
     float *bus_out = nullptr, *bus_out_dev = nullptr;            // pinned and device-mapped: S2R_MAX_BUSES * 2 * max_frames floats
     float bus_mix_ms = -1.0f;                    // pan_mix_ms of the last s2r_fill_buses (tools/bus_time.py)
     bool bus_dev_ramped = false;                 // what bus_gains_dev holds was sent for a ramped fill: (G0, step), not the static gains
-    // What runs behind the bus mixdown (s2r_post.h): the buses' delays and reverbs, the master section and the master limiter
+    // What runs behind the bus mixdown (s2r_post.h): the buses' choruses, delays and reverbs, the master section and the master limiter
     S2rPostChain post;
     float pitch_table[256];
     hipEvent_t t0 = nullptr, t1 = nullptr;
@@ -2722,7 +2722,7 @@ int s2r_set_voice_sends(s2r_synth *s, const float *sends, const uint8_t *send_bu
     return S2R_OK;
 }
 
-// ---- the post-mix chain: delays, reverbs, master section, master limiter (s2r_post.h) ----
+// ---- the post-mix chain: choruses, delays, reverbs, master section, master limiter (s2r_post.h) ----
 // Every entry below looks at its values first (they are wrong whatever the handle holds), then at the handle, quiesces where it touches
 // the device, and calls into s->post for whatever is more than one value.  `what`: "bus reverbs are", "the master section is", ...
 static int post_handle(const s2r_synth *s, const char *who, const char *what) {
@@ -2787,6 +2787,77 @@ int s2r_get_bus_reverb_history(s2r_synth *s, uint32_t bus, float *lr, size_t cap
 int s2r_set_bus_reverb_history(s2r_synth *s, uint32_t bus, const float *lr, size_t count) {
     static const float none = 0.0f;                              // (a null lr: refused by fx_history unless K = 1, which has no history)
     return fx_history(s, bus, nullptr, lr ? lr : &none, lr ? count : (count ? (size_t)-1 : 0), "s2r_set_bus_reverb_history");
+}
+
+// ---- per-bus choruses: in front of the delays ----
+int s2r_set_bus_chorus(s2r_synth *s, uint32_t bus, uint32_t voices, float base, float depth, uint32_t phase_inc, uint32_t spread, float dry, float wet) {
+    if ((voices && !chorus_in_range(voices, base, depth, dry, wet)) || bus >= S2R_MAX_BUSES)
+        return set_err(s, S2R_ERR_PATCH_RANGE, "bus %u: a chorus of %u voices, base %g, depth %g, dry %g, wet %g: at most %u voices, base >= 1 and depth >= 0 with "
+                       "base + depth <= %g frames, dry and wet in [0, 1], the bus below %u", bus, voices, (double)base, (double)depth, (double)dry, (double)wet,
+                       S2R_CHORUS_MAX_VOICES, (double)S2R_CHORUS_MAX_DELAY, S2R_MAX_BUSES);
+    S2R_TRY(post_handle(s, "s2r_set_bus_chorus", "bus choruses are"));
+    if (s->ring_count) return set_err(s, S2R_ERR_INVALID, "s2r_set_bus_chorus with fills of s2r_fill_begin in flight: s2r_fill_end first");
+    S2R_QUIESCE(s);
+    S2R_HIP(s, hipSetDevice(s->device));
+    S2R_HIP(s, hipStreamSynchronize(s->stream));
+    const hipError_t e = s->post.set_chorus(post_ctx(s), bus, voices, base, depth, phase_inc, spread, dry, wet);
+    if (e != hipSuccess) return set_err(s, e == hipErrorOutOfMemory ? S2R_ERR_OUT_OF_MEMORY : S2R_ERR_HIP, "s2r_set_bus_chorus: %s", hipGetErrorString(e));
+    return S2R_OK;
+}
+
+int s2r_set_bus_chorus_mix(s2r_synth *s, uint32_t bus, float dry, float wet) {
+    if (!chorus_mix_in_range(dry, wet) || bus >= S2R_MAX_BUSES)
+        return set_err(s, S2R_ERR_PATCH_RANGE, "bus %u: dry %g, wet %g: dry and wet lie in [0, 1], the bus below %u", bus, (double)dry, (double)wet, S2R_MAX_BUSES);
+    S2R_TRY(post_handle(s, "s2r_set_bus_chorus_mix", "bus choruses are"));
+    S2rPostChain::BusChorus &d = s->post.chorus[bus];
+    if (!d.voices) return set_err(s, S2R_ERR_INVALID, "bus %u carries no chorus", bus);
+    d.dry = dry; d.wet = wet;
+    return S2R_OK;
+}
+
+int s2r_set_bus_chorus_rate(s2r_synth *s, uint32_t bus, uint32_t phase_inc, uint32_t spread) {
+    if (bus >= S2R_MAX_BUSES) return set_err(s, S2R_ERR_PATCH_RANGE, "s2r_set_bus_chorus_rate: bus %u, below %u", bus, S2R_MAX_BUSES);
+    S2R_TRY(post_handle(s, "s2r_set_bus_chorus_rate", "bus choruses are"));
+    S2rPostChain::BusChorus &d = s->post.chorus[bus];
+    if (!d.voices) return set_err(s, S2R_ERR_INVALID, "bus %u carries no chorus", bus);
+    d.phase_inc = phase_inc; d.spread = spread;                  // (the phase and the history stay: the LFO bends, nothing clicks)
+    return S2R_OK;
+}
+
+int s2r_get_bus_chorus(const s2r_synth *s, uint32_t bus, uint32_t *voices, float *base, float *depth, uint32_t *phase_inc, uint32_t *spread, float *dry,
+                       float *wet) {
+    if (bus >= S2R_MAX_BUSES) return S2R_ERR_PATCH_RANGE;
+    if (!s || !s->kids.empty() || s->parent) return S2R_ERR_INVALID;
+    const S2rPostChain::BusChorus &d = s->post.chorus[bus];
+    put(voices, d.voices); put(base, d.base); put(depth, d.depth); put(phase_inc, d.phase_inc); put(spread, d.spread); put(dry, d.dry); put(wet, d.wet);
+    return S2R_OK;
+}
+
+// the history crosses the boundary as the device keeps it: frames, oldest first, L then R; the phase lives on the host
+static int chorus_state(s2r_synth *s, uint32_t bus, float *get, const float *set, size_t count, const char *who) {
+    if (bus >= S2R_MAX_BUSES) return set_err(s, S2R_ERR_PATCH_RANGE, "%s: bus %u, below %u", who, bus, S2R_MAX_BUSES);
+    S2R_TRY(post_handle(s, who, "bus choruses are"));
+    if (!s->post.chorus[bus].voices) return set_err(s, S2R_ERR_INVALID, "%s: bus %u carries no chorus", who, bus);
+    const size_t h = s->post.chorus[bus].history;
+    if (set ? count != 2 * h : count < 2 * h) return set_err(s, S2R_ERR_INVALID, "%s: the history of bus %u is %zu floats, not %zu", who, bus, 2 * h, count);
+    if (!get && !set) return set_err(s, S2R_ERR_INVALID, "%s: null buffer", who);
+    S2R_QUIESCE(s);
+    S2R_HIP(s, hipSetDevice(s->device));
+    S2R_HIP(s, hipStreamSynchronize(s->stream));
+    S2R_HIP(s, s->post.chorus_state(post_ctx(s), bus, get, set));
+    return S2R_OK;
+}
+
+int s2r_get_bus_chorus_state(s2r_synth *s, uint32_t bus, float *lr, size_t capacity, uint32_t *phase) {
+    S2R_TRY(chorus_state(s, bus, lr, nullptr, capacity, "s2r_get_bus_chorus_state"));
+    put(phase, s->post.chorus[bus].phase);
+    return S2R_OK;
+}
+
+int s2r_set_bus_chorus_state(s2r_synth *s, uint32_t bus, const float *lr, size_t count, uint32_t phase) {
+    S2R_TRY(chorus_state(s, bus, nullptr, lr, lr ? count : (size_t)-1, "s2r_set_bus_chorus_state"));
+    s->post.chorus[bus].phase = phase;
+    return S2R_OK;
 }
 
 // ---- per-bus feedback delays: in front of the reverbs ----
@@ -3450,6 +3521,8 @@ extern "C" float s2r_debug_pan_mix_ms(const s2r_synth *s) { return s && s->timin
 extern "C" uint32_t s2r_debug_pan_slice(const s2r_synth *s) { return s ? s->pan_slice : 0u; }
 // ... and of the bus mixdown's kernels in the last s2r_fill_buses (tools/bus_time.py)
 extern "C" float s2r_debug_bus_mix_ms(const s2r_synth *s) { return s && s->timing ? s->bus_mix_ms : -1.0f; }
+// ... of the buses' chorus kernel in that fill: 0 when it ran none (tools/chorus_time.py)
+extern "C" float s2r_debug_bus_chorus_ms(const s2r_synth *s) { return s && s->timing ? s->post.chorus_timer.ms : -1.0f; }
 // ... of the buses' delay kernel in that fill: 0 when it ran none (tools/delay_time.py)
 extern "C" float s2r_debug_bus_delay_ms(const s2r_synth *s) { return s && s->timing ? s->post.delay_timer.ms : -1.0f; }
 // ... and of the buses' reverb kernels in that fill: 0 when it ran none (tools/reverb_time.py)

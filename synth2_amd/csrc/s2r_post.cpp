@@ -1,5 +1,6 @@
-// s2r_post.cpp — the post-mix chain (s2r_post.h): delays, reverbs, master section, master limiter.  Compiled with hipcc, -ffp-contract=off.
+// s2r_post.cpp — the post-mix chain (s2r_post.h): choruses, delays, reverbs, master section, master limiter.  Compiled with hipcc, -ffp-contract=off.
 #include "s2r_post.h"
+#include "s2r_rules.h"
 
 #include <cstring>
 
@@ -29,13 +30,15 @@ hipError_t S2rPostTimer::begin(hipStream_t stream) {
     return hipEventRecord(ev[0], stream);
 }
 
-S2rPostRoute s2r_post_route(const S2rPostCall &call, float *delay_stage, float *fx_stage, float *master_stage, float *limiter_in, float *bus_out_dev,
+S2rPostRoute s2r_post_route(const S2rPostCall &call, float *chorus_stage, float *delay_stage, float *fx_stage, float *master_stage, float *limiter_in, float *bus_out_dev,
                             float *out_host_dev) {
     S2rPostRoute r{};
     if (!call.n_buses) return r;
     float *last_stems = call.master ? master_stage : bus_out_dev;
     float *behind_delay = call.fx_on ? fx_stage : last_stems;    // where the stems go when no delay stands in front
-    r.combine_out = call.delay_on ? delay_stage : behind_delay;
+    float *behind_chorus = call.delay_on ? delay_stage : behind_delay;   // ... and when no chorus does
+    r.combine_out = call.chorus_on ? chorus_stage : behind_chorus;
+    if (call.chorus_on) { r.chorus_in = chorus_stage; r.chorus_out = behind_chorus; }
     if (call.delay_on) { r.delay_in = delay_stage; r.delay_out = behind_delay; }
     if (call.fx_on) { r.fx_in = fx_stage; r.fx_out = last_stems; }
     if (call.master) { r.master_in = master_stage; r.master_out = call.limited ? limiter_in : out_host_dev; r.master_stems = call.stems ? bus_out_dev : nullptr; }
@@ -46,7 +49,8 @@ S2rPostRoute s2r_post_route(const S2rPostCall &call, float *delay_stage, float *
 hipError_t S2rPostChain::prepare(const S2rPostCtx &c, uint32_t n_buses, uint32_t frames, bool master_fill, bool stems, S2rPostCall &call) {
     call = S2rPostCall{};
     call.n_buses = n_buses; call.frames = frames; call.master = master_fill; call.stems = stems;
-    for (uint32_t b = 0; b < n_buses; b++) if (delay[b].delay) call.delay_on = true; // (a delay on a bus past the call's is idle in it)
+    for (uint32_t b = 0; b < n_buses; b++) if (chorus[b].voices) call.chorus_on = true;      // (a chorus on a bus past the call's is idle in it)
+    for (uint32_t b = 0; b < n_buses; b++) if (delay[b].delay) call.delay_on = true; // (and so is a delay)
     for (uint32_t b = 0; b < n_buses; b++) if (fx[b].n_taps) call.fx_on = true;      // (and so is a reverb)
     call.limited = master_fill && limiter.lookahead != 0;
     if (call.master) {                                           // the device copy of the stems and the pinned rows of block partials
@@ -58,13 +62,27 @@ hipError_t S2rPostChain::prepare(const S2rPostCtx &c, uint32_t n_buses, uint32_t
         for (float *&p : limiter.state) if (!p) POST_HIP(hipMalloc((void **)&p, kLimState * sizeof(float)));
         POST_HIP(pinned_rows(limiter.partials, limiter.partials_dev, (size_t)((c.max_frames + S2R_LIMITER_BLOCK - 1u) / S2R_LIMITER_BLOCK) * 2u));
     }
-    call.route = s2r_post_route(call, delay_stage, fx_stage, master.stage, limiter.in, c.bus_out_dev, c.out_host_dev);
+    call.route = s2r_post_route(call, chorus_stage, delay_stage, fx_stage, master.stage, limiter.in, c.bus_out_dev, c.out_host_dev);
     return hipSuccess;
 }
 
 hipError_t S2rPostChain::launch(const S2rPostCtx &c, const S2rPostCall &call) {
     const S2rPostRoute &r = call.route; const float fn = (float)call.frames;
-    if (call.delay_on) {                                         // once per call, over all of its frames, in front of the reverbs
+    if (call.chorus_on) {                                        // once per call, over all of its frames, in front of the delays
+        S2rChorus a{};
+        for (uint32_t b = 0; b < call.n_buses; b++) {
+            const BusChorus &f = chorus[b];
+            if (!f.voices) continue;
+            S2rChorusBus &d = a.bus[b];
+            d.line = f.line[f.cur]; d.next = f.line[f.cur ^ 1]; d.voices = f.voices; d.history = f.history;
+            d.phase = f.phase; d.phase_inc = f.phase_inc; d.spread = f.spread;
+            d.base = f.base; d.depth = f.depth; d.dry = f.dry; d.wet = f.wet;
+            for (uint32_t v = 0; v < f.voices; v++) d.off[v] = chorus_voice_offset(v, f.voices);
+        }
+        a.in = r.chorus_in; a.out = r.chorus_out; a.n_buses = call.n_buses; a.frames = call.frames;
+        POST_TIMED(c, chorus_timer, s2r_launch_bus_chorus(a, c.stream));
+    }
+    if (call.delay_on) {                                         // likewise, in front of the reverbs
         S2rDelay a{};
         for (uint32_t b = 0; b < call.n_buses; b++) {
             const BusDelay &f = delay[b];
@@ -117,7 +135,10 @@ hipError_t S2rPostChain::launch(const S2rPostCtx &c, const S2rPostCall &call) {
 }
 
 void S2rPostChain::commit(const S2rPostCall &call) {
-    if (call.delay_on) for (uint32_t b = 0; b < call.n_buses; b++) if (delay[b].delay) delay[b].cur ^= 1;     // the histories have moved on
+    if (call.chorus_on) for (uint32_t b = 0; b < call.n_buses; b++) if (chorus[b].voices) {                   // the histories have moved on, and the phases
+        chorus[b].cur ^= 1; chorus[b].phase += chorus[b].phase_inc * call.frames;
+    }
+    if (call.delay_on) for (uint32_t b = 0; b < call.n_buses; b++) if (delay[b].delay) delay[b].cur ^= 1;
     if (call.fx_on) for (uint32_t b = 0; b < call.n_buses; b++) if (fx[b].n_taps) fx[b].cur ^= 1;
     if (call.master) {                                           // the block partials in block order, and applied = target
         Master &ms = master;
@@ -147,8 +168,9 @@ void S2rPostChain::commit(const S2rPostCall &call) {
     }
 }
 
-// a stage that the fill could have run and did not reads 0; a panned fill leaves all four values alone, a bus fill the master's two
+// a stage that the fill could have run and did not reads 0; a panned fill leaves all five values alone, a bus fill the master's two
 hipError_t S2rPostChain::read_timers(const S2rPostCall &call) {
+    if (call.n_buses) { chorus_timer.ms = 0.0f; if (call.chorus_on) POST_HIP(chorus_timer.read()); }
     if (call.n_buses) { delay_timer.ms = 0.0f; if (call.delay_on) POST_HIP(delay_timer.read()); }
     if (call.n_buses) { fx_timer.ms = 0.0f; if (call.fx_on) POST_HIP(fx_timer.read()); }
     if (call.master) {
@@ -160,11 +182,39 @@ hipError_t S2rPostChain::read_timers(const S2rPostCall &call) {
 }
 
 void S2rPostChain::release() {
+    for (BusChorus &f : chorus) f.release();
     for (BusDelay &f : delay) f.release();
     for (BusFx &f : fx) f.release();
-    for (float *p : {delay_stage, fx_stage, master.stage, limiter.state[0], limiter.state[1], limiter.in}) if (p) (void)hipFree(p);
+    for (float *p : {chorus_stage, delay_stage, fx_stage, master.stage, limiter.state[0], limiter.state[1], limiter.in}) if (p) (void)hipFree(p);
     for (float *p : {master.partials, limiter.partials}) if (p) (void)hipHostFree(p);
-    for (S2rPostTimer *t : {&delay_timer, &fx_timer, &master.timer, &limiter.timer}) t->destroy();
+    for (S2rPostTimer *t : {&chorus_timer, &delay_timer, &fx_timer, &master.timer, &limiter.timer}) t->destroy();
+}
+
+hipError_t S2rPostChain::set_chorus(const S2rPostCtx &c, uint32_t bus, uint32_t voices, float base, float depth, uint32_t phase_inc, uint32_t spread, float dry,
+                                    float wet) {
+    if (voices == 0) { chorus[bus].release(); return hipSuccess; }
+    BusChorus f;
+    f.voices = voices; f.history = chorus_history(base, depth); f.base = base; f.depth = depth; f.dry = dry; f.wet = wet;
+    f.phase_inc = phase_inc; f.spread = spread;
+    const size_t line_bytes = 2u * (size_t)f.history * sizeof(float);
+    hipError_t e = hipSuccess;
+    if (!chorus_stage) e = hipMalloc((void **)&chorus_stage, (size_t)2 * S2R_MAX_BUSES * c.max_frames * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void **)&f.line[0], line_bytes);
+    if (e == hipSuccess) e = hipMalloc((void **)&f.line[1], line_bytes);
+    if (e == hipSuccess) e = hipMemsetAsync(f.line[0], 0, line_bytes, c.stream);     // the history: +0.0 everywhere (the other line is written whole by the first call)
+    { const hipError_t e2 = hipStreamSynchronize(c.stream); if (e == hipSuccess) e = e2; }
+    if (e != hipSuccess) { f.release(); return e; }              // (the earlier chorus of the bus is kept)
+    chorus[bus].release();                                       // replaces any earlier chorus of the bus
+    chorus[bus] = f;
+    return hipSuccess;
+}
+
+hipError_t S2rPostChain::chorus_state(const S2rPostCtx &c, uint32_t bus, float *get, const float *set) {
+    const BusChorus &f = chorus[bus];
+    const size_t bytes = 2u * (size_t)f.history * sizeof(float);
+    if (get) POST_HIP(hipMemcpyAsync(get, f.line[f.cur], bytes, hipMemcpyDeviceToHost, c.stream));
+    else POST_HIP(hipMemcpyAsync(f.line[f.cur], set, bytes, hipMemcpyHostToDevice, c.stream));
+    return hipStreamSynchronize(c.stream);
 }
 
 hipError_t S2rPostChain::set_delay(const S2rPostCtx &c, uint32_t bus, uint32_t delay_frames, float feedback, float cross, float dry, float wet) {

@@ -1,5 +1,5 @@
-// s2r_post.h — the chain behind the bus mixdown of s2r_fill_buses and s2r_fill_master: the buses' feedback delays,
-// their convolution reverbs (4.16), the master section (4.17) and the master limiter (4.18), in that order.  The chain owns what the four stages own and knows
+// s2r_post.h — the chain behind the bus mixdown of s2r_fill_buses and s2r_fill_master: the buses' choruses, their
+// feedback delays (4.19), their convolution reverbs (4.16), the master section (4.17) and the master limiter (4.18), in that order.  The chain owns what the five stages own and knows
 // nothing of the handle: its functions take a S2rPostCtx and return the HIP error.  Per call: prepare, launch, — the caller's synchronise —
 // commit, read_timers.
 #pragma once
@@ -22,11 +22,12 @@ struct S2rPostTimer {
     void destroy() { for (hipEvent_t &e : ev) if (e) { (void)hipEventDestroy(e); e = nullptr; } }
 };
 
-// every pointer of one call (s2r_post_route): the bus combine's, the delay kernel's, the reverbs' kernels', the master kernel's and the limiter's
-struct S2rPostRoute { float *combine_out, *delay_in, *delay_out, *fx_in, *fx_out, *master_in, *master_out, *master_stems, *limiter_in, *limiter_out; };
+// every pointer of one call (s2r_post_route): the bus combine's, the chorus kernel's, the delay kernel's, the reverbs' kernels', the master kernel's and the limiter's
+struct S2rPostRoute { float *combine_out, *chorus_in, *chorus_out, *delay_in, *delay_out, *fx_in, *fx_out, *master_in, *master_out, *master_stems, *limiter_in, *limiter_out; };
 struct S2rPostCall {                                // one fill, as prepare leaves it
     uint32_t n_buses = 0, frames = 0;            // n_buses 0: a panned fill, which runs no stage
     bool master = false, stems = false;          // s2r_fill_master; the caller wants the stems too
+    bool chorus_on = false;                      // a chorus sits on one of the call's buses
     bool delay_on = false;                       // a delay sits on one of the call's buses
     bool fx_on = false, limited = false;         // a reverb sits on one of the call's buses; a master fill with the limiter set
     S2rPostRoute route{};
@@ -37,25 +38,50 @@ struct S2rPostCall {                                // one fill, as prepare leav
 // pinned output in a bus fill; the master's device stage in a master fill, whose kernel must not read pinned memory back and copies
 // them out itself when the caller wants them.  The master kernel's two channels go to the pinned output unless the limiter follows
 // and writes there in its place.  A stage that does not run has null pointers.
-//   call         delay reverb limiter | combine_out   delay_in -> delay_out          fx_in -> fx_out             master_in     master_out    limiter_in -> _out
-//   bus fill     no    no     -       | bus_out_dev   -                              -                           -             -             -
-//   bus fill     no    yes    -       | fx_stage      -                              fx_stage -> bus_out_dev     -             -             -
-//   bus fill     yes   no     -       | delay_stage   delay_stage -> bus_out_dev     -                           -             -             -
-//   bus fill     yes   yes    -       | delay_stage   delay_stage -> fx_stage        fx_stage -> bus_out_dev     -             -             -
-//   master fill  no    no     no      | master_stage  -                              -                           master_stage  out_host_dev  -
-//   master fill  no    yes    no      | fx_stage      -                              fx_stage -> master_stage    master_stage  out_host_dev  -
-//   master fill  yes   no     no      | delay_stage   delay_stage -> master_stage    -                           master_stage  out_host_dev  -
-//   master fill  yes   yes    no      | delay_stage   delay_stage -> fx_stage        fx_stage -> master_stage    master_stage  out_host_dev  -
-//   master fill  no    no     yes     | master_stage  -                              -                           master_stage  limiter_in    limiter_in -> out_host_dev
-//   master fill  no    yes    yes     | fx_stage      -                              fx_stage -> master_stage    master_stage  limiter_in    limiter_in -> out_host_dev
-//   master fill  yes   no     yes     | delay_stage   delay_stage -> master_stage    -                           master_stage  limiter_in    limiter_in -> out_host_dev
-//   master fill  yes   yes    yes     | delay_stage   delay_stage -> fx_stage        fx_stage -> master_stage    master_stage  limiter_in    limiter_in -> out_host_dev
-//   master_stems = bus_out_dev in a master fill with stems, else null.  A limiter that is set is idle in a bus fill, a delay or a
-//   reverb on a bus past the call's in any; a panned fill (no buses) has no route.
-S2rPostRoute s2r_post_route(const S2rPostCall &call, float *delay_stage, float *fx_stage, float *master_stage, float *limiter_in, float *bus_out_dev,
+//   call         chorus delay reverb limiter | combine_out   chorus_in -> chorus_out       delay_in -> delay_out          fx_in -> fx_out             master_in     master_out    limiter_in -> _out
+//   bus fill     no     no    no     -       | bus_out_dev   -                             -                              -                           -             -             -
+//   bus fill     no     no    yes    -       | fx_stage      -                             -                              fx_stage -> bus_out_dev     -             -             -
+//   bus fill     no     yes   no     -       | delay_stage   -                             delay_stage -> bus_out_dev     -                           -             -             -
+//   bus fill     no     yes   yes    -       | delay_stage   -                             delay_stage -> fx_stage        fx_stage -> bus_out_dev     -             -             -
+//   master fill  no     no    no     no      | master_stage  -                             -                              -                           master_stage  out_host_dev  -
+//   master fill  no     no    yes    no      | fx_stage      -                             -                              fx_stage -> master_stage    master_stage  out_host_dev  -
+//   master fill  no     yes   no     no      | delay_stage   -                             delay_stage -> master_stage    -                           master_stage  out_host_dev  -
+//   master fill  no     yes   yes    no      | delay_stage   -                             delay_stage -> fx_stage        fx_stage -> master_stage    master_stage  out_host_dev  -
+//   master fill  no     no    no     yes     | master_stage  -                             -                              -                           master_stage  limiter_in    limiter_in -> out_host_dev
+//   master fill  no     no    yes    yes     | fx_stage      -                             -                              fx_stage -> master_stage    master_stage  limiter_in    limiter_in -> out_host_dev
+//   master fill  no     yes   no     yes     | delay_stage   -                             delay_stage -> master_stage    -                           master_stage  limiter_in    limiter_in -> out_host_dev
+//   master fill  no     yes   yes    yes     | delay_stage   -                             delay_stage -> fx_stage        fx_stage -> master_stage    master_stage  limiter_in    limiter_in -> out_host_dev
+//   bus fill     yes    no    no     -       | chorus_stage  chorus_stage -> bus_out_dev   -                              -                           -             -             -
+//   bus fill     yes    no    yes    -       | chorus_stage  chorus_stage -> fx_stage      -                              fx_stage -> bus_out_dev     -             -             -
+//   bus fill     yes    yes   no     -       | chorus_stage  chorus_stage -> delay_stage   delay_stage -> bus_out_dev     -                           -             -             -
+//   bus fill     yes    yes   yes    -       | chorus_stage  chorus_stage -> delay_stage   delay_stage -> fx_stage        fx_stage -> bus_out_dev     -             -             -
+//   master fill  yes    no    no     no      | chorus_stage  chorus_stage -> master_stage  -                              -                           master_stage  out_host_dev  -
+//   master fill  yes    no    yes    no      | chorus_stage  chorus_stage -> fx_stage      -                              fx_stage -> master_stage    master_stage  out_host_dev  -
+//   master fill  yes    yes   no     no      | chorus_stage  chorus_stage -> delay_stage   delay_stage -> master_stage    -                           master_stage  out_host_dev  -
+//   master fill  yes    yes   yes    no      | chorus_stage  chorus_stage -> delay_stage   delay_stage -> fx_stage        fx_stage -> master_stage    master_stage  out_host_dev  -
+//   master fill  yes    no    no     yes     | chorus_stage  chorus_stage -> master_stage  -                              -                           master_stage  limiter_in    limiter_in -> out_host_dev
+//   master fill  yes    no    yes    yes     | chorus_stage  chorus_stage -> fx_stage      -                              fx_stage -> master_stage    master_stage  limiter_in    limiter_in -> out_host_dev
+//   master fill  yes    yes   no     yes     | chorus_stage  chorus_stage -> delay_stage   delay_stage -> master_stage    -                           master_stage  limiter_in    limiter_in -> out_host_dev
+//   master fill  yes    yes   yes    yes     | chorus_stage  chorus_stage -> delay_stage   delay_stage -> fx_stage        fx_stage -> master_stage    master_stage  limiter_in    limiter_in -> out_host_dev
+//   master_stems = bus_out_dev in a master fill with stems, else null.  A limiter that is set is idle in a bus fill, a chorus, a
+//   delay or a reverb on a bus past the call's in any; a panned fill (no buses) has no route.
+S2rPostRoute s2r_post_route(const S2rPostCall &call, float *chorus_stage, float *delay_stage, float *fx_stage, float *master_stage, float *limiter_in, float *bus_out_dev,
                             float *out_host_dev);
 
 struct S2rPostChain {
+    // The choruses (s2r_set_bus_chorus).  Everything of theirs is allocated when a chorus is set, never in a fill.
+    struct BusChorus {
+        uint32_t voices = 0;                     // V; 0: the bus has no chorus
+        uint32_t history = 0;                    // H = floor(fl(base + depth)) + 1
+        float base = 0.0f, depth = 0.0f, dry = 0.0f, wet = 0.0f;
+        uint32_t phase_inc = 0, spread = 0;
+        uint32_t phase = 0;                      // the LFO's phase at frame 0 of the next call: moved on by the commit
+        float *line[2] = {nullptr, nullptr};     // [H][2] each, oldest frame first, L then R: line[cur] holds the history of the input, the kernel writes the other
+        int cur = 0;
+        void release() { for (float *p : line) if (p) (void)hipFree(p); *this = BusChorus{}; }
+    } chorus[S2R_MAX_BUSES];
+    float *chorus_stage = nullptr;               // [S2R_MAX_BUSES][2 * max_frames]: where the bus combine writes in a call that runs a chorus
+    S2rPostTimer chorus_timer;                   // around the chorus kernel of the last bus or master fill: 0 when it ran none (tools/chorus_time.py)
     // The delays (s2r_set_bus_delay).  Everything of theirs is allocated when a delay is set, never in a fill.
     struct BusDelay {
         uint32_t delay = 0;                      // D; 0: the bus has no delay
@@ -117,6 +143,8 @@ struct S2rPostChain {
     hipError_t read_timers(const S2rPostCall &call);
     void release();
     // what the entry points of s2r_host.cpp do behind their checks, on a quiet stream
+    hipError_t set_chorus(const S2rPostCtx &c, uint32_t bus, uint32_t voices, float base, float depth, uint32_t phase_inc, uint32_t spread, float dry, float wet);
+    hipError_t chorus_state(const S2rPostCtx &c, uint32_t bus, float *get, const float *set);       // the history: frames, oldest first, L then R
     hipError_t set_delay(const S2rPostCtx &c, uint32_t bus, uint32_t delay_frames, float feedback, float cross, float dry, float wet);
     hipError_t delay_history(const S2rPostCtx &c, uint32_t bus, float *get, const float *set);      // frames, oldest first, L then R
     hipError_t set_reverb(const S2rPostCtx &c, uint32_t bus, const float *ir_l, const float *ir_r, uint32_t n_taps, float dry, float wet);

@@ -58,6 +58,45 @@ int s2r_delay_reference(uint32_t delay_frames, float feedback, float cross, floa
     return S2R_OK;
 }
 
+// ---- per-bus chorus: V taps at triangle-modulated fractional delays into the INPUT's history; no recursion ----
+uint32_t s2r_chorus_history_frames(float base, float depth) { return chorus_delay_in_range(base, depth) ? chorus_history(base, depth) : 0u; }
+
+int s2r_chorus_reference(uint32_t voices, float base, float depth, uint32_t phase_inc, uint32_t spread, float dry, float wet, const float *x_lr,
+                         uint32_t frames, float *history_lr, uint32_t *phase, float *out_lr) {
+    if (!chorus_in_range(voices, base, depth, dry, wet)) return S2R_ERR_PATCH_RANGE;
+    if (!history_lr || !phase || (!x_lr && frames)) return S2R_ERR_INVALID;
+    const size_t H = chorus_history(base, depth), N = frames;
+    std::vector<float> s(2 * (H + N));                           // x[-H .. N): the history, then the call's input
+    std::memcpy(s.data(), history_lr, 2 * H * sizeof(float));
+    if (N) std::memcpy(s.data() + 2 * H, x_lr, 2 * N * sizeof(float));
+    const uint32_t phase0 = *phase;
+    for (size_t n = 0; n < N && out_lr; n++)
+        for (uint32_t c = 0; c < 2; c++) {
+            float acc = 0.0f;
+            for (uint32_t v = 0; v < voices; v++) {
+                const uint32_t off = chorus_voice_offset(v, voices) + c * spread;
+                const uint32_t p = phase0 + off + phase_inc * (uint32_t)n;
+                const uint32_t q = p >> 8;
+                const uint32_t h = q < (1u << 23) ? q : (1u << 24) - q;
+                const float m = (float)h * 0x1p-23f;
+                const float dm = depth * m;
+                const float d = base + dm;
+                const uint32_t i = (uint32_t)d;                  // (i + 1 <= H: d <= fl(base + depth) by monotonic rounding)
+                const float f = d - (float)i;
+                const float a = s[2 * (H + n - i) + c], bb = s[2 * (H + n - i - 1) + c];
+                const float e = bb - a;
+                const float g = f * e;
+                const float tap = a + g;
+                acc = v ? acc + tap : tap;
+            }
+            const float dx = dry * s[2 * (H + n) + c], wa = wet * acc;
+            out_lr[2 * n + c] = dx + wa;
+        }
+    std::memcpy(history_lr, s.data() + 2 * N, 2 * H * sizeof(float));
+    *phase = phase0 + phase_inc * (uint32_t)N;
+    return S2R_OK;
+}
+
 // ---- the master section: energies by the adjacent-pair tree over blocks of S2R_METER_BLOCK frames ----
 static float master_energy(const float *v, uint32_t frames) {     // v: one channel of an interleaved pair (stride 2)
     float total = 0.0f;

@@ -18,6 +18,21 @@ static inline bool delay_mix_in_range(float feedback, float cross, float dry, fl
     return pan_in_range(feedback) && pan_in_range(cross) && std::fabs((double)feedback) + std::fabs((double)cross) <= 1.0 && unit_in_range(dry) &&
            unit_in_range(wet);
 }
+// a chorus's two levels, and its delay range: base >= 1, depth >= 0 and fl(base + depth) <= S2R_CHORUS_MAX_DELAY, the sum
+// rounded to binary32 (-ffp-contract=off; the volatile keeps a build with excess precision honest).  A NaN or an infinity fails a comparison.
+static inline bool chorus_mix_in_range(float dry, float wet) { return unit_in_range(dry) && unit_in_range(wet); }
+static inline bool chorus_delay_in_range(float base, float depth) {
+    if (!(base >= 1.0f) || !(depth >= 0.0f)) return false;
+    volatile float top = base + depth;
+    return top <= S2R_CHORUS_MAX_DELAY;
+}
+static inline bool chorus_in_range(uint32_t voices, float base, float depth, float dry, float wet) {
+    return voices >= 1u && voices <= S2R_CHORUS_MAX_VOICES && chorus_delay_in_range(base, depth) && chorus_mix_in_range(dry, wet);
+}
+// H = floor(fl(base + depth)) + 1 for a pair in range
+static inline uint32_t chorus_history(float base, float depth) { volatile float top = base + depth; return (uint32_t)top + 1u; }
+// voice v's offset on the left channel: floor(v * 2^32 / V)
+static inline uint32_t chorus_voice_offset(uint32_t v, uint32_t voices) { return (uint32_t)(((uint64_t)v << 32) / voices); }
 
 // The voice mixer's gain rules, inline: the host's per-voice loops compile them in — a call per voice into s2r_rules.cpp showed as 10
 // to 15 us of host time per fill of 65 536 voices (profiles/r12/post_chain.txt).  s2r_rules.cpp exports them under their s2r.h names.

@@ -36,6 +36,8 @@ S2R_ERR_OUT_OF_MEMORY = -8
 MAX_BUSES = 8                               # S2R_MAX_BUSES
 MAX_IR_TAPS = 65536                         # S2R_MAX_IR_TAPS
 MAX_DELAY_FRAMES = 262144                   # S2R_MAX_DELAY_FRAMES
+CHORUS_MAX_VOICES = 8                       # S2R_CHORUS_MAX_VOICES
+CHORUS_MAX_DELAY = 4095.0                   # S2R_CHORUS_MAX_DELAY
 IR_SEGMENT = 256                            # S2R_IR_SEGMENT
 METER_BLOCK = 256                           # S2R_METER_BLOCK
 LIMITER_MAX_LOOKAHEAD = 1024                # S2R_LIMITER_MAX_LOOKAHEAD
@@ -206,6 +208,15 @@ def load_library():
         "s2r_get_bus_delay_history": (C.c_int, [H, C.c_uint32, _f32p, C.c_size_t]),
         "s2r_set_bus_delay_history": (C.c_int, [H, C.c_uint32, _f32p, C.c_size_t]),
         "s2r_delay_reference": (C.c_int, [C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_float, _f32p, C.c_uint32, _f32p, _f32p]),
+        "s2r_chorus_history_frames": (C.c_uint32, [C.c_float, C.c_float]),
+        "s2r_set_bus_chorus": (C.c_int, [H, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.c_float, C.c_float]),
+        "s2r_set_bus_chorus_mix": (C.c_int, [H, C.c_uint32, C.c_float, C.c_float]),
+        "s2r_set_bus_chorus_rate": (C.c_int, [H, C.c_uint32, C.c_uint32, C.c_uint32]),
+        "s2r_get_bus_chorus": (C.c_int, [H, C.c_uint32, C.POINTER(C.c_uint32), _f32p, _f32p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _f32p, _f32p]),
+        "s2r_get_bus_chorus_state": (C.c_int, [H, C.c_uint32, _f32p, C.c_size_t, C.POINTER(C.c_uint32)]),
+        "s2r_set_bus_chorus_state": (C.c_int, [H, C.c_uint32, _f32p, C.c_size_t, C.c_uint32]),
+        "s2r_chorus_reference": (C.c_int, [C.c_uint32, C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.c_float, C.c_float, _f32p, C.c_uint32, _f32p,
+                                           C.POINTER(C.c_uint32), _f32p]),
         "s2r_set_bus_return": (C.c_int, [H, C.c_uint32, C.c_float]),
         "s2r_get_bus_return": (C.c_int, [H, C.c_uint32, _f32p, _f32p]),
         "s2r_set_master_fader": (C.c_int, [H, C.c_float]),
@@ -351,6 +362,39 @@ def delay_reference(delay_frames, feedback, cross, dry, wet, x, history):
     if rc != S2R_OK:
         raise S2rError(rc, load_library().s2r_status_string(rc).decode())
     return out, h
+
+
+def chorus_history_frames(base, depth):
+    """H, the stereo frames of history a chorus of (base, depth) keeps: floor(float32(base + depth)) + 1, or 0 for a pair out of range
+    (s2r_chorus_history_frames)"""
+    return int(load_library().s2r_chorus_history_frames(float(base), float(depth)))
+
+
+def chorus_rate(hz, sample_rate):
+    """an LFO rate in Hz as a phase_inc: round(hz * 2^32 / sample_rate) modulo 2^32 (the spread of a chorus is in the same units:
+    2^-32 turns)"""
+    return int(round(float(hz) * 4294967296.0 / float(sample_rate))) & 0xFFFFFFFF
+
+
+def chorus_reference(voices, base, depth, phase_inc, spread, dry, wet, x, history, phase):
+    """the bus chorus's rule for both channels on the host (s2r_chorus_reference): x [frames, 2] float32 is the bus's signal, history
+    [H, 2] the H frames of input in front of it, oldest first, phase the LFO's at frame 0; returns (out [frames, 2], the history after
+    the call [H, 2], the phase after the call).  `history` itself is left as it is."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    h = np.array(history, dtype=np.float32, order="C")
+    if x.ndim != 2 or x.shape[1] != 2 or h.ndim != 2 or h.shape[1] != 2:
+        raise ValueError("chorus_reference: x is [frames, 2] and history is [H, 2]")
+    hf = chorus_history_frames(base, depth)
+    if hf and h.shape[0] != hf:                 # (a pair out of range is the library's to refuse)
+        raise ValueError("chorus_reference: history is [chorus_history_frames(base, depth), 2]")
+    out = np.empty_like(x)
+    ph = C.c_uint32(int(phase) & 0xFFFFFFFF)
+    rc = load_library().s2r_chorus_reference(int(voices), float(base), float(depth), int(phase_inc) & 0xFFFFFFFF, int(spread) & 0xFFFFFFFF, float(dry),
+                                             float(wet), x.ctypes.data_as(_f32p), x.shape[0], h.ctypes.data_as(_f32p), C.byref(ph),
+                                             out.ctypes.data_as(_f32p))
+    if rc != S2R_OK:
+        raise S2rError(rc, load_library().s2r_status_string(rc).decode())
+    return out, h, ph.value
 
 
 def master_reference(stems, r0, r1, m0, m1):
@@ -769,6 +813,63 @@ class Synth:
     @staticmethod
     def delay_reference(delay_frames, feedback, cross, dry, wet, x, history):
         return delay_reference(delay_frames, feedback, cross, dry, wet, x, history)
+
+    # --- per-bus chorus (build-defined; s2r.h: s2r_set_bus_chorus) ---
+    def set_bus_chorus(self, bus, voices, base, depth, phase_inc, spread=0, dry=1.0, wet=1.0):
+        """a chorus of `voices` (1 .. CHORUS_MAX_VOICES) taps on a bus of sample_buses and sample_master, in front of the bus's delay:
+        each tap base + depth * triangle frames late (base >= 1, depth >= 0, float32(base + depth) <= CHORUS_MAX_DELAY), the LFO
+        stepping phase_inc per frame (chorus_rate(hz, sample_rate)), the right channel `spread` ahead of the left, both in 2^-32 turns;
+        dry and wet in [0, 1] (1 / voices goes into wet).  Replaces any earlier chorus of the bus and zeroes its history and phase."""
+        if int(voices) < 1:
+            raise ValueError("set_bus_chorus: at least one voice (clear_bus_chorus removes a chorus)")
+        self._check(self.L.s2r_set_bus_chorus(self.h, int(bus), int(voices), float(base), float(depth), int(phase_inc) & 0xFFFFFFFF,
+                                              int(spread) & 0xFFFFFFFF, float(dry), float(wet)))
+
+    def clear_bus_chorus(self, bus):
+        """removes the bus's chorus: the bus returns the combine's signal again, bit for bit"""
+        self._check(self.L.s2r_set_bus_chorus(self.h, int(bus), 0, 0.0, 0.0, 0, 0, 0.0, 0.0))
+
+    def set_bus_chorus_mix(self, bus, dry, wet):
+        """the two levels of the bus's chorus alone; its state stays"""
+        self._check(self.L.s2r_set_bus_chorus_mix(self.h, int(bus), float(dry), float(wet)))
+
+    def set_bus_chorus_rate(self, bus, phase_inc, spread=0):
+        """the LFO's step and the channels' spread alone; phase and history stay, so nothing clicks"""
+        self._check(self.L.s2r_set_bus_chorus_rate(self.h, int(bus), int(phase_inc) & 0xFFFFFFFF, int(spread) & 0xFFFFFFFF))
+
+    def get_bus_chorus(self, bus):
+        """(voices, base, depth, phase_inc, spread, dry, wet); voices is 0 for a bus without a chorus"""
+        v, pi, sp = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        b, dp, d, w = C.c_float(), C.c_float(), C.c_float(), C.c_float()
+        self._check(self.L.s2r_get_bus_chorus(self.h, int(bus), C.byref(v), C.byref(b), C.byref(dp), C.byref(pi), C.byref(sp), C.byref(d), C.byref(w)))
+        return v.value, b.value, dp.value, pi.value, sp.value, d.value, w.value
+
+    def bus_chorus_state(self, bus):
+        """what the bus's chorus carries into the next call: (the H stereo frames of its input's history, oldest first: (H, 2)
+        float32, the LFO's phase) — the checkpoint companion of bus_delay_history"""
+        _, base, depth = self.get_bus_chorus(bus)[:3]
+        out = np.empty((chorus_history_frames(base, depth), 2), dtype=np.float32)
+        ph = C.c_uint32()
+        self._check(self.L.s2r_get_bus_chorus_state(self.h, int(bus), out.ctypes.data_as(_f32p), out.size, C.byref(ph)))
+        return out, ph.value
+
+    def set_bus_chorus_state(self, bus, history, phase):
+        h = np.ascontiguousarray(history, dtype=np.float32)
+        if h.ndim != 2 or h.shape[1] != 2:
+            raise ValueError("set_bus_chorus_state: history is [H, 2]")
+        self._check(self.L.s2r_set_bus_chorus_state(self.h, int(bus), h.ctypes.data_as(_f32p), h.size, int(phase) & 0xFFFFFFFF))
+
+    @staticmethod
+    def chorus_reference(voices, base, depth, phase_inc, spread, dry, wet, x, history, phase):
+        return chorus_reference(voices, base, depth, phase_inc, spread, dry, wet, x, history, phase)
+
+    @staticmethod
+    def chorus_history_frames(base, depth):
+        return chorus_history_frames(base, depth)
+
+    @staticmethod
+    def chorus_rate(hz, sample_rate):
+        return chorus_rate(hz, sample_rate)
 
     # --- the master section (build-defined; s2r.h: s2r_fill_master) ---
     def set_bus_return(self, bus, level=1.0):
