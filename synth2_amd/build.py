@@ -22,7 +22,7 @@ SOURCES = ["s2r_render_onepole_square.hip", "s2r_render_onepole_saw.hip", "s2r_r
            "s2r_aux.hip", "s2r_chorus.hip", "s2r_delay.hip", "s2r_fx.hip", "s2r_master.hip", "s2r_limiter.hip", "s2r_host.cpp", "s2r_post.cpp", "s2r_rules.cpp", "s2r_patch.cpp",
            "s2r_stream.cpp"]
 HEADERS = ["s2r_device.h", "s2r_math.h", "s2r_patch.h", "s2r_voices.h", "s2r_kern_common.h", "s2r_render_onepole.inc",
-           "s2r_render_general.inc", "s2r_post.h", "s2r_rules.h"]
+           "s2r_render_general.inc", "s2r_post.h", "s2r_post_route.h", "s2r_rules.h"]
 
 # -amdgpu-sched-strategy=max-ilp: the render kernels run one wavefront per SIMD (64 k voices =
 # 1024 waves), so nothing hides a dependent instruction's latency except independent work of the

@@ -12,6 +12,7 @@
 #include <cstring>
 #include <ctime>
 #include <atomic>
+#include <functional>
 #include <memory>
 #include <new>
 #include <string>
@@ -2731,6 +2732,49 @@ static int post_handle(const s2r_synth *s, const char *who, const char *what) {
     return S2R_OK;
 }
 
+// the words in which the entries of a stem stage differ
+static const struct { const char *one, *are; } kStemWords[S2R_STEM_STAGES] = {{"chorus", "bus choruses are"}, {"delay", "bus delays are"}, {"reverb", "bus reverbs are"}};
+
+// The guard of an entry that reads or changes the effect one bus carries: the bus in range, a single-device handle, and the bus
+// carries one.  `who` null: a getter, which answers for a bus without one too and leaves the handle's error text alone; `named`:
+// the refusal of a bus without one begins with `who`.
+static int stem_bus(const s2r_synth *s, S2rStemStage k, uint32_t bus, const char *who, bool named) {
+    if (!who) return bus >= S2R_MAX_BUSES ? S2R_ERR_PATCH_RANGE : (!s || !s->kids.empty() || s->parent) ? S2R_ERR_INVALID : S2R_OK;
+    s2r_synth *m = const_cast<s2r_synth *>(s);
+    if (bus >= S2R_MAX_BUSES) return set_err(m, S2R_ERR_PATCH_RANGE, "%s: bus %u, below %u", who, bus, S2R_MAX_BUSES);
+    S2R_TRY(post_handle(s, who, kStemWords[k].are));
+    if (s->post.bus(k, bus).present()) return S2R_OK;
+    if (named) return set_err(m, S2R_ERR_INVALID, "%s: bus %u carries no %s", who, bus, kStemWords[k].one);
+    return set_err(m, S2R_ERR_INVALID, "bus %u carries no %s", bus, kStemWords[k].one);
+}
+
+// The common tail of the entries that set or clear an effect, behind their checks of the values and the handle: no fills in
+// flight, a quiet stream, the chain's setter, and its error.
+static int stem_set(s2r_synth *s, const char *who, const std::function<hipError_t(const S2rPostCtx &)> &set) {
+    if (s->ring_count) return set_err(s, S2R_ERR_INVALID, "%s with fills of s2r_fill_begin in flight: s2r_fill_end first", who);
+    S2R_QUIESCE(s);
+    S2R_HIP(s, hipSetDevice(s->device));
+    S2R_HIP(s, hipStreamSynchronize(s->stream));
+    const hipError_t e = set(post_ctx(s));
+    if (e != hipSuccess) return set_err(s, e == hipErrorOutOfMemory ? S2R_ERR_OUT_OF_MEMORY : S2R_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    return S2R_OK;
+}
+
+// An effect's history out (`get`, `count` the capacity) or in (`set`, `count` exact): it crosses the boundary as frames, oldest
+// first, L then R.  A reverb of one tap has none, and nothing to copy.
+static int stem_history(s2r_synth *s, S2rStemStage k, uint32_t bus, float *get, const float *set, size_t count, const char *who) {
+    S2R_TRY(stem_bus(s, k, bus, who, true));
+    const size_t h = s->post.bus(k, bus).history;
+    if (set ? count != 2 * h : count < 2 * h) return set_err(s, S2R_ERR_INVALID, "%s: the history of bus %u is %zu floats, not %zu", who, bus, 2 * h, count);
+    if (h == 0) return S2R_OK;
+    if (!get && !set) return set_err(s, S2R_ERR_INVALID, "%s: null buffer", who);
+    S2R_QUIESCE(s);
+    S2R_HIP(s, hipSetDevice(s->device));
+    S2R_HIP(s, hipStreamSynchronize(s->stream));
+    S2R_HIP(s, s->post.history(post_ctx(s), k, bus, get, set));
+    return S2R_OK;
+}
+
 int s2r_set_bus_reverb(s2r_synth *s, uint32_t bus, const float *ir_l, const float *ir_r, uint32_t n_taps, float dry, float wet) {
     if (!unit_in_range(dry) || !unit_in_range(wet) || n_taps > S2R_MAX_IR_TAPS || bus >= S2R_MAX_BUSES)
         return set_err(s, S2R_ERR_PATCH_RANGE, "bus %u: %u taps, dry %g, wet %g: dry and wet lie in [0, 1], at most %u taps, the bus below %u", bus, n_taps,
@@ -2741,52 +2785,30 @@ int s2r_set_bus_reverb(s2r_synth *s, uint32_t bus, const float *ir_l, const floa
             if (!std::isfinite(ir_l[k]) || !std::isfinite(ir_r[k])) return set_err(s, S2R_ERR_PATCH_RANGE, "bus %u: tap %u is not finite", bus, k);
     S2R_TRY(post_handle(s, "s2r_set_bus_reverb", "bus reverbs are"));
     if (n_taps && !ir_l) return set_err(s, S2R_ERR_INVALID, "s2r_set_bus_reverb: %u taps and no response", n_taps);
-    if (s->ring_count) return set_err(s, S2R_ERR_INVALID, "s2r_set_bus_reverb with fills of s2r_fill_begin in flight: s2r_fill_end first");
-    S2R_QUIESCE(s);
-    S2R_HIP(s, hipSetDevice(s->device));
-    S2R_HIP(s, hipStreamSynchronize(s->stream));
-    const hipError_t e = s->post.set_reverb(post_ctx(s), bus, ir_l, ir_r, n_taps, dry, wet);
-    if (e != hipSuccess) return set_err(s, e == hipErrorOutOfMemory ? S2R_ERR_OUT_OF_MEMORY : S2R_ERR_HIP, "s2r_set_bus_reverb: %s", hipGetErrorString(e));
-    return S2R_OK;
+    return stem_set(s, "s2r_set_bus_reverb", [&](const S2rPostCtx &c) { return s->post.set_reverb(c, bus, ir_l, ir_r, n_taps, dry, wet); });
 }
 
 int s2r_set_bus_reverb_mix(s2r_synth *s, uint32_t bus, float dry, float wet) {
     if (!unit_in_range(dry) || !unit_in_range(wet) || bus >= S2R_MAX_BUSES)
         return set_err(s, S2R_ERR_PATCH_RANGE, "bus %u: dry %g, wet %g: both lie in [0, 1], the bus below %u", bus, (double)dry, (double)wet, S2R_MAX_BUSES);
-    S2R_TRY(post_handle(s, "s2r_set_bus_reverb_mix", "bus reverbs are"));
-    if (!s->post.fx[bus].n_taps) return set_err(s, S2R_ERR_INVALID, "bus %u carries no reverb", bus);
+    S2R_TRY(stem_bus(s, S2R_STEM_REVERB, bus, "s2r_set_bus_reverb_mix", false));
     s->post.fx[bus].dry = dry; s->post.fx[bus].wet = wet;
     return S2R_OK;
 }
 
 int s2r_get_bus_reverb(const s2r_synth *s, uint32_t bus, uint32_t *n_taps, float *dry, float *wet) {
-    if (bus >= S2R_MAX_BUSES) return S2R_ERR_PATCH_RANGE;
-    if (!s || !s->kids.empty() || s->parent) return S2R_ERR_INVALID;
+    S2R_TRY(stem_bus(s, S2R_STEM_REVERB, bus, nullptr, false));
     put(n_taps, s->post.fx[bus].n_taps); put(dry, s->post.fx[bus].dry); put(wet, s->post.fx[bus].wet);
     return S2R_OK;
 }
 
-// the history crosses the boundary as frames, oldest first, L then R
-static int fx_history(s2r_synth *s, uint32_t bus, float *get, const float *set, size_t count, const char *who) {
-    if (bus >= S2R_MAX_BUSES) return set_err(s, S2R_ERR_PATCH_RANGE, "%s: bus %u, below %u", who, bus, S2R_MAX_BUSES);
-    S2R_TRY(post_handle(s, who, "bus reverbs are"));
-    if (!s->post.fx[bus].n_taps) return set_err(s, S2R_ERR_INVALID, "%s: bus %u carries no reverb", who, bus);
-    const size_t h = s->post.fx[bus].n_taps - 1u;
-    if (set ? count != 2 * h : count < 2 * h) return set_err(s, S2R_ERR_INVALID, "%s: the history of bus %u is %zu floats, not %zu", who, bus, 2 * h, count);
-    if (h == 0) return S2R_OK;
-    if (!get && !set) return set_err(s, S2R_ERR_INVALID, "%s: null buffer", who);
-    S2R_QUIESCE(s);
-    S2R_HIP(s, hipSetDevice(s->device));
-    S2R_HIP(s, hipStreamSynchronize(s->stream));
-    S2R_HIP(s, s->post.reverb_history(post_ctx(s), bus, get, set));
-    return S2R_OK;
+int s2r_get_bus_reverb_history(s2r_synth *s, uint32_t bus, float *lr, size_t capacity) {
+    return stem_history(s, S2R_STEM_REVERB, bus, lr, nullptr, capacity, "s2r_get_bus_reverb_history");
 }
 
-int s2r_get_bus_reverb_history(s2r_synth *s, uint32_t bus, float *lr, size_t capacity) { return fx_history(s, bus, lr, nullptr, capacity, "s2r_get_bus_reverb_history"); }
-
 int s2r_set_bus_reverb_history(s2r_synth *s, uint32_t bus, const float *lr, size_t count) {
-    static const float none = 0.0f;                              // (a null lr: refused by fx_history unless K = 1, which has no history)
-    return fx_history(s, bus, nullptr, lr ? lr : &none, lr ? count : (count ? (size_t)-1 : 0), "s2r_set_bus_reverb_history");
+    static const float none = 0.0f;                              // (a null lr: refused by stem_history unless K = 1, which has no history)
+    return stem_history(s, S2R_STEM_REVERB, bus, nullptr, lr ? lr : &none, lr ? count : (count ? (size_t)-1 : 0), "s2r_set_bus_reverb_history");
 }
 
 // ---- per-bus choruses: in front of the delays ----
@@ -2796,66 +2818,40 @@ int s2r_set_bus_chorus(s2r_synth *s, uint32_t bus, uint32_t voices, float base, 
                        "base + depth <= %g frames, dry and wet in [0, 1], the bus below %u", bus, voices, (double)base, (double)depth, (double)dry, (double)wet,
                        S2R_CHORUS_MAX_VOICES, (double)S2R_CHORUS_MAX_DELAY, S2R_MAX_BUSES);
     S2R_TRY(post_handle(s, "s2r_set_bus_chorus", "bus choruses are"));
-    if (s->ring_count) return set_err(s, S2R_ERR_INVALID, "s2r_set_bus_chorus with fills of s2r_fill_begin in flight: s2r_fill_end first");
-    S2R_QUIESCE(s);
-    S2R_HIP(s, hipSetDevice(s->device));
-    S2R_HIP(s, hipStreamSynchronize(s->stream));
-    const hipError_t e = s->post.set_chorus(post_ctx(s), bus, voices, base, depth, phase_inc, spread, dry, wet);
-    if (e != hipSuccess) return set_err(s, e == hipErrorOutOfMemory ? S2R_ERR_OUT_OF_MEMORY : S2R_ERR_HIP, "s2r_set_bus_chorus: %s", hipGetErrorString(e));
-    return S2R_OK;
+    return stem_set(s, "s2r_set_bus_chorus", [&](const S2rPostCtx &c) { return s->post.set_chorus(c, bus, voices, base, depth, phase_inc, spread, dry, wet); });
 }
 
 int s2r_set_bus_chorus_mix(s2r_synth *s, uint32_t bus, float dry, float wet) {
     if (!chorus_mix_in_range(dry, wet) || bus >= S2R_MAX_BUSES)
         return set_err(s, S2R_ERR_PATCH_RANGE, "bus %u: dry %g, wet %g: dry and wet lie in [0, 1], the bus below %u", bus, (double)dry, (double)wet, S2R_MAX_BUSES);
-    S2R_TRY(post_handle(s, "s2r_set_bus_chorus_mix", "bus choruses are"));
-    S2rPostChain::BusChorus &d = s->post.chorus[bus];
-    if (!d.voices) return set_err(s, S2R_ERR_INVALID, "bus %u carries no chorus", bus);
-    d.dry = dry; d.wet = wet;
+    S2R_TRY(stem_bus(s, S2R_STEM_CHORUS, bus, "s2r_set_bus_chorus_mix", false));
+    s->post.chorus[bus].dry = dry; s->post.chorus[bus].wet = wet;
     return S2R_OK;
 }
 
 int s2r_set_bus_chorus_rate(s2r_synth *s, uint32_t bus, uint32_t phase_inc, uint32_t spread) {
-    if (bus >= S2R_MAX_BUSES) return set_err(s, S2R_ERR_PATCH_RANGE, "s2r_set_bus_chorus_rate: bus %u, below %u", bus, S2R_MAX_BUSES);
-    S2R_TRY(post_handle(s, "s2r_set_bus_chorus_rate", "bus choruses are"));
-    S2rPostChain::BusChorus &d = s->post.chorus[bus];
-    if (!d.voices) return set_err(s, S2R_ERR_INVALID, "bus %u carries no chorus", bus);
-    d.phase_inc = phase_inc; d.spread = spread;                  // (the phase and the history stay: the LFO bends, nothing clicks)
+    S2R_TRY(stem_bus(s, S2R_STEM_CHORUS, bus, "s2r_set_bus_chorus_rate", false));
+    s->post.chorus[bus].phase_inc = phase_inc; s->post.chorus[bus].spread = spread;      // (the phase and the history stay: the LFO bends, nothing clicks)
     return S2R_OK;
 }
 
 int s2r_get_bus_chorus(const s2r_synth *s, uint32_t bus, uint32_t *voices, float *base, float *depth, uint32_t *phase_inc, uint32_t *spread, float *dry,
                        float *wet) {
-    if (bus >= S2R_MAX_BUSES) return S2R_ERR_PATCH_RANGE;
-    if (!s || !s->kids.empty() || s->parent) return S2R_ERR_INVALID;
+    S2R_TRY(stem_bus(s, S2R_STEM_CHORUS, bus, nullptr, false));
     const S2rPostChain::BusChorus &d = s->post.chorus[bus];
     put(voices, d.voices); put(base, d.base); put(depth, d.depth); put(phase_inc, d.phase_inc); put(spread, d.spread); put(dry, d.dry); put(wet, d.wet);
     return S2R_OK;
 }
 
-// the history crosses the boundary as the device keeps it: frames, oldest first, L then R; the phase lives on the host
-static int chorus_state(s2r_synth *s, uint32_t bus, float *get, const float *set, size_t count, const char *who) {
-    if (bus >= S2R_MAX_BUSES) return set_err(s, S2R_ERR_PATCH_RANGE, "%s: bus %u, below %u", who, bus, S2R_MAX_BUSES);
-    S2R_TRY(post_handle(s, who, "bus choruses are"));
-    if (!s->post.chorus[bus].voices) return set_err(s, S2R_ERR_INVALID, "%s: bus %u carries no chorus", who, bus);
-    const size_t h = s->post.chorus[bus].history;
-    if (set ? count != 2 * h : count < 2 * h) return set_err(s, S2R_ERR_INVALID, "%s: the history of bus %u is %zu floats, not %zu", who, bus, 2 * h, count);
-    if (!get && !set) return set_err(s, S2R_ERR_INVALID, "%s: null buffer", who);
-    S2R_QUIESCE(s);
-    S2R_HIP(s, hipSetDevice(s->device));
-    S2R_HIP(s, hipStreamSynchronize(s->stream));
-    S2R_HIP(s, s->post.chorus_state(post_ctx(s), bus, get, set));
-    return S2R_OK;
-}
-
+// (the chorus's phase lives on the host)
 int s2r_get_bus_chorus_state(s2r_synth *s, uint32_t bus, float *lr, size_t capacity, uint32_t *phase) {
-    S2R_TRY(chorus_state(s, bus, lr, nullptr, capacity, "s2r_get_bus_chorus_state"));
+    S2R_TRY(stem_history(s, S2R_STEM_CHORUS, bus, lr, nullptr, capacity, "s2r_get_bus_chorus_state"));
     put(phase, s->post.chorus[bus].phase);
     return S2R_OK;
 }
 
 int s2r_set_bus_chorus_state(s2r_synth *s, uint32_t bus, const float *lr, size_t count, uint32_t phase) {
-    S2R_TRY(chorus_state(s, bus, nullptr, lr, lr ? count : (size_t)-1, "s2r_set_bus_chorus_state"));
+    S2R_TRY(stem_history(s, S2R_STEM_CHORUS, bus, nullptr, lr, lr ? count : (size_t)-1, "s2r_set_bus_chorus_state"));
     s->post.chorus[bus].phase = phase;
     return S2R_OK;
 }
@@ -2867,52 +2863,33 @@ int s2r_set_bus_delay(s2r_synth *s, uint32_t bus, uint32_t delay_frames, float f
                        "|feedback| + |cross| <= 1, dry and wet in [0, 1], at most %u frames, the bus below %u", bus, delay_frames, (double)feedback, (double)cross,
                        (double)dry, (double)wet, S2R_MAX_DELAY_FRAMES, S2R_MAX_BUSES);
     S2R_TRY(post_handle(s, "s2r_set_bus_delay", "bus delays are"));
-    if (s->ring_count) return set_err(s, S2R_ERR_INVALID, "s2r_set_bus_delay with fills of s2r_fill_begin in flight: s2r_fill_end first");
-    S2R_QUIESCE(s);
-    S2R_HIP(s, hipSetDevice(s->device));
-    S2R_HIP(s, hipStreamSynchronize(s->stream));
-    const hipError_t e = s->post.set_delay(post_ctx(s), bus, delay_frames, feedback, cross, dry, wet);
-    if (e != hipSuccess) return set_err(s, e == hipErrorOutOfMemory ? S2R_ERR_OUT_OF_MEMORY : S2R_ERR_HIP, "s2r_set_bus_delay: %s", hipGetErrorString(e));
-    return S2R_OK;
+    return stem_set(s, "s2r_set_bus_delay", [&](const S2rPostCtx &c) { return s->post.set_delay(c, bus, delay_frames, feedback, cross, dry, wet); });
 }
 
 int s2r_set_bus_delay_mix(s2r_synth *s, uint32_t bus, float feedback, float cross, float dry, float wet) {
     if (!delay_mix_in_range(feedback, cross, dry, wet) || bus >= S2R_MAX_BUSES)
         return set_err(s, S2R_ERR_PATCH_RANGE, "bus %u: feedback %g, cross %g, dry %g, wet %g: feedback and cross lie in [-1, 1] with |feedback| + |cross| <= 1, "
                        "dry and wet in [0, 1], the bus below %u", bus, (double)feedback, (double)cross, (double)dry, (double)wet, S2R_MAX_BUSES);
-    S2R_TRY(post_handle(s, "s2r_set_bus_delay_mix", "bus delays are"));
+    S2R_TRY(stem_bus(s, S2R_STEM_DELAY, bus, "s2r_set_bus_delay_mix", false));
     S2rPostChain::BusDelay &d = s->post.delay[bus];
-    if (!d.delay) return set_err(s, S2R_ERR_INVALID, "bus %u carries no delay", bus);
     d.feedback = feedback; d.cross = cross; d.dry = dry; d.wet = wet;
     return S2R_OK;
 }
 
 int s2r_get_bus_delay(const s2r_synth *s, uint32_t bus, uint32_t *delay_frames, float *feedback, float *cross, float *dry, float *wet) {
-    if (bus >= S2R_MAX_BUSES) return S2R_ERR_PATCH_RANGE;
-    if (!s || !s->kids.empty() || s->parent) return S2R_ERR_INVALID;
+    S2R_TRY(stem_bus(s, S2R_STEM_DELAY, bus, nullptr, false));
     const S2rPostChain::BusDelay &d = s->post.delay[bus];
-    put(delay_frames, d.delay); put(feedback, d.feedback); put(cross, d.cross); put(dry, d.dry); put(wet, d.wet);
+    put(delay_frames, d.history); put(feedback, d.feedback); put(cross, d.cross); put(dry, d.dry); put(wet, d.wet);
     return S2R_OK;
 }
 
-// the history crosses the boundary as the device keeps it: frames, oldest first, L then R
-static int delay_history(s2r_synth *s, uint32_t bus, float *get, const float *set, size_t count, const char *who) {
-    if (bus >= S2R_MAX_BUSES) return set_err(s, S2R_ERR_PATCH_RANGE, "%s: bus %u, below %u", who, bus, S2R_MAX_BUSES);
-    S2R_TRY(post_handle(s, who, "bus delays are"));
-    if (!s->post.delay[bus].delay) return set_err(s, S2R_ERR_INVALID, "%s: bus %u carries no delay", who, bus);
-    const size_t h = s->post.delay[bus].delay;
-    if (set ? count != 2 * h : count < 2 * h) return set_err(s, S2R_ERR_INVALID, "%s: the history of bus %u is %zu floats, not %zu", who, bus, 2 * h, count);
-    if (!get && !set) return set_err(s, S2R_ERR_INVALID, "%s: null buffer", who);
-    S2R_QUIESCE(s);
-    S2R_HIP(s, hipSetDevice(s->device));
-    S2R_HIP(s, hipStreamSynchronize(s->stream));
-    S2R_HIP(s, s->post.delay_history(post_ctx(s), bus, get, set));
-    return S2R_OK;
+int s2r_get_bus_delay_history(s2r_synth *s, uint32_t bus, float *lr, size_t capacity) {
+    return stem_history(s, S2R_STEM_DELAY, bus, lr, nullptr, capacity, "s2r_get_bus_delay_history");
 }
 
-int s2r_get_bus_delay_history(s2r_synth *s, uint32_t bus, float *lr, size_t capacity) { return delay_history(s, bus, lr, nullptr, capacity, "s2r_get_bus_delay_history"); }
-
-int s2r_set_bus_delay_history(s2r_synth *s, uint32_t bus, const float *lr, size_t count) { return delay_history(s, bus, nullptr, lr, lr ? count : (size_t)-1, "s2r_set_bus_delay_history"); }
+int s2r_set_bus_delay_history(s2r_synth *s, uint32_t bus, const float *lr, size_t count) {
+    return stem_history(s, S2R_STEM_DELAY, bus, nullptr, lr, lr ? count : (size_t)-1, "s2r_set_bus_delay_history");
+}
 
 // ---- program faders ----
 int s2r_set_program_fader(s2r_synth *s, uint32_t program, float fader, float pan_shift) {
@@ -3522,11 +3499,11 @@ extern "C" uint32_t s2r_debug_pan_slice(const s2r_synth *s) { return s ? s->pan_
 // ... and of the bus mixdown's kernels in the last s2r_fill_buses (tools/bus_time.py)
 extern "C" float s2r_debug_bus_mix_ms(const s2r_synth *s) { return s && s->timing ? s->bus_mix_ms : -1.0f; }
 // ... of the buses' chorus kernel in that fill: 0 when it ran none (tools/chorus_time.py)
-extern "C" float s2r_debug_bus_chorus_ms(const s2r_synth *s) { return s && s->timing ? s->post.chorus_timer.ms : -1.0f; }
+extern "C" float s2r_debug_bus_chorus_ms(const s2r_synth *s) { return s && s->timing ? s->post.stem[S2R_STEM_CHORUS].timer.ms : -1.0f; }
 // ... of the buses' delay kernel in that fill: 0 when it ran none (tools/delay_time.py)
-extern "C" float s2r_debug_bus_delay_ms(const s2r_synth *s) { return s && s->timing ? s->post.delay_timer.ms : -1.0f; }
+extern "C" float s2r_debug_bus_delay_ms(const s2r_synth *s) { return s && s->timing ? s->post.stem[S2R_STEM_DELAY].timer.ms : -1.0f; }
 // ... and of the buses' reverb kernels in that fill: 0 when it ran none (tools/reverb_time.py)
-extern "C" float s2r_debug_bus_fx_ms(const s2r_synth *s) { return s && s->timing ? s->post.fx_timer.ms : -1.0f; }
+extern "C" float s2r_debug_bus_fx_ms(const s2r_synth *s) { return s && s->timing ? s->post.stem[S2R_STEM_REVERB].timer.ms : -1.0f; }
 // ... and of the master kernel in the last s2r_fill_master (tools/master_time.py)
 extern "C" float s2r_debug_master_ms(const s2r_synth *s) { return s && s->timing ? s->post.master.timer.ms : -1.0f; }
 // ... and of the limiter kernel in that fill: 0 when it ran none (tools/limiter_time.py)

@@ -1,13 +1,14 @@
-// s2r_post.h — the chain behind the bus mixdown of s2r_fill_buses and s2r_fill_master: the buses' choruses, their
-// feedback delays (4.19), their convolution reverbs (4.16), the master section (4.17) and the master limiter (4.18), in that order.  The chain owns what the five stages own and knows
-// nothing of the handle: its functions take a S2rPostCtx and return the HIP error.  Per call: prepare, launch, — the caller's synchronise —
-// commit, read_timers.
+// s2r_post.h — the chain behind the bus mixdown of s2r_fill_buses and s2r_fill_master: the stem stages (s2r_post_route.h) — the buses'
+// choruses, their feedback delays (4.19), their convolution reverbs (4.16) —, the master section (4.17) and the master
+// limiter (4.18), in that order.  The chain owns what the five stages own and knows nothing of the handle: its functions take a
+// S2rPostCtx and return the HIP error.  Per call: prepare, launch, — the caller's synchronise — commit, read_timers.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <vector>
 
 #include "s2r.h"
 #include "s2r_device.h"
+#include "s2r_post_route.h"
 
 // what the chain is told of its handle: `timing` is s2r_set_timing, the two pointers the device's views of the pinned outputs
 struct S2rPostCtx { hipStream_t stream; uint32_t max_frames; bool timing; float *bus_out_dev, *out_host_dev; };
@@ -22,89 +23,55 @@ struct S2rPostTimer {
     void destroy() { for (hipEvent_t &e : ev) if (e) { (void)hipEventDestroy(e); e = nullptr; } }
 };
 
-// every pointer of one call (s2r_post_route): the bus combine's, the chorus kernel's, the delay kernel's, the reverbs' kernels', the master kernel's and the limiter's
-struct S2rPostRoute { float *combine_out, *chorus_in, *chorus_out, *delay_in, *delay_out, *fx_in, *fx_out, *master_in, *master_out, *master_stems, *limiter_in, *limiter_out; };
-struct S2rPostCall {                                // one fill, as prepare leaves it
-    uint32_t n_buses = 0, frames = 0;            // n_buses 0: a panned fill, which runs no stage
-    bool master = false, stems = false;          // s2r_fill_master; the caller wants the stems too
-    bool chorus_on = false;                      // a chorus sits on one of the call's buses
-    bool delay_on = false;                       // a delay sits on one of the call's buses
-    bool fx_on = false, limited = false;         // a reverb sits on one of the call's buses; a master fill with the limiter set
-    S2rPostRoute route{};
+// A bus effect's history on the device, double-buffered: line[cur] holds it, the call's kernel writes the other and the commit flips,
+// so that a call that fails leaves the history where it was.  Allocated when the effect is set, never in a fill; an effect that is
+// set has its lines, and no other has.
+struct S2rBusLine {
+    float *line[2] = {nullptr, nullptr};         // `floats` each
+    int cur = 0;
+    size_t floats = 0;
+    uint32_t history = 0;                        // the frames of history the effect carries from call to call (s2r_get_bus_*_history)
+    bool present() const { return line[0] != nullptr; }
+    float *now() const { return line[cur]; }
+    float *next() const { return line[cur ^ 1]; }
+    void flip() { cur ^= 1; }
+    hipError_t alloc(size_t n);
+    hipError_t zero(int which, hipStream_t stream) { return hipMemsetAsync(line[which], 0, floats * sizeof(float), stream); }  // +0.0 everywhere
+    // `n` floats at `at` of the current line to `get`, or from `set`; the caller synchronises
+    hipError_t copy(float *get, const float *set, size_t at, size_t n, hipStream_t stream) const;
+    // (not virtual: an effect with more device memory than its lines frees it in a free() of its own, and is dropped by its type)
+    void free() { for (float *&p : line) if (p) { (void)hipFree(p); p = nullptr; } }
 };
 
-// Who reads and writes what, the only place that decides it.  The combine writes into the first stem stage that runs, each running
-// stage into the next running stage's input, and whichever stage writes the stems LAST writes them where the call wants them: the
-// pinned output in a bus fill; the master's device stage in a master fill, whose kernel must not read pinned memory back and copies
-// them out itself when the caller wants them.  The master kernel's two channels go to the pinned output unless the limiter follows
-// and writes there in its place.  A stage that does not run has null pointers.
-//   call         chorus delay reverb limiter | combine_out   chorus_in -> chorus_out       delay_in -> delay_out          fx_in -> fx_out             master_in     master_out    limiter_in -> _out
-//   bus fill     no     no    no     -       | bus_out_dev   -                             -                              -                           -             -             -
-//   bus fill     no     no    yes    -       | fx_stage      -                             -                              fx_stage -> bus_out_dev     -             -             -
-//   bus fill     no     yes   no     -       | delay_stage   -                             delay_stage -> bus_out_dev     -                           -             -             -
-//   bus fill     no     yes   yes    -       | delay_stage   -                             delay_stage -> fx_stage        fx_stage -> bus_out_dev     -             -             -
-//   master fill  no     no    no     no      | master_stage  -                             -                              -                           master_stage  out_host_dev  -
-//   master fill  no     no    yes    no      | fx_stage      -                             -                              fx_stage -> master_stage    master_stage  out_host_dev  -
-//   master fill  no     yes   no     no      | delay_stage   -                             delay_stage -> master_stage    -                           master_stage  out_host_dev  -
-//   master fill  no     yes   yes    no      | delay_stage   -                             delay_stage -> fx_stage        fx_stage -> master_stage    master_stage  out_host_dev  -
-//   master fill  no     no    no     yes     | master_stage  -                             -                              -                           master_stage  limiter_in    limiter_in -> out_host_dev
-//   master fill  no     no    yes    yes     | fx_stage      -                             -                              fx_stage -> master_stage    master_stage  limiter_in    limiter_in -> out_host_dev
-//   master fill  no     yes   no     yes     | delay_stage   -                             delay_stage -> master_stage    -                           master_stage  limiter_in    limiter_in -> out_host_dev
-//   master fill  no     yes   yes    yes     | delay_stage   -                             delay_stage -> fx_stage        fx_stage -> master_stage    master_stage  limiter_in    limiter_in -> out_host_dev
-//   bus fill     yes    no    no     -       | chorus_stage  chorus_stage -> bus_out_dev   -                              -                           -             -             -
-//   bus fill     yes    no    yes    -       | chorus_stage  chorus_stage -> fx_stage      -                              fx_stage -> bus_out_dev     -             -             -
-//   bus fill     yes    yes   no     -       | chorus_stage  chorus_stage -> delay_stage   delay_stage -> bus_out_dev     -                           -             -             -
-//   bus fill     yes    yes   yes    -       | chorus_stage  chorus_stage -> delay_stage   delay_stage -> fx_stage        fx_stage -> bus_out_dev     -             -             -
-//   master fill  yes    no    no     no      | chorus_stage  chorus_stage -> master_stage  -                              -                           master_stage  out_host_dev  -
-//   master fill  yes    no    yes    no      | chorus_stage  chorus_stage -> fx_stage      -                              fx_stage -> master_stage    master_stage  out_host_dev  -
-//   master fill  yes    yes   no     no      | chorus_stage  chorus_stage -> delay_stage   delay_stage -> master_stage    -                           master_stage  out_host_dev  -
-//   master fill  yes    yes   yes    no      | chorus_stage  chorus_stage -> delay_stage   delay_stage -> fx_stage        fx_stage -> master_stage    master_stage  out_host_dev  -
-//   master fill  yes    no    no     yes     | chorus_stage  chorus_stage -> master_stage  -                              -                           master_stage  limiter_in    limiter_in -> out_host_dev
-//   master fill  yes    no    yes    yes     | chorus_stage  chorus_stage -> fx_stage      -                              fx_stage -> master_stage    master_stage  limiter_in    limiter_in -> out_host_dev
-//   master fill  yes    yes   no     yes     | chorus_stage  chorus_stage -> delay_stage   delay_stage -> master_stage    -                           master_stage  limiter_in    limiter_in -> out_host_dev
-//   master fill  yes    yes   yes    yes     | chorus_stage  chorus_stage -> delay_stage   delay_stage -> fx_stage        fx_stage -> master_stage    master_stage  limiter_in    limiter_in -> out_host_dev
-//   master_stems = bus_out_dev in a master fill with stems, else null.  A limiter that is set is idle in a bus fill, a chorus, a
-//   delay or a reverb on a bus past the call's in any; a panned fill (no buses) has no route.
-S2rPostRoute s2r_post_route(const S2rPostCall &call, float *chorus_stage, float *delay_stage, float *fx_stage, float *master_stage, float *limiter_in, float *bus_out_dev,
-                            float *out_host_dev);
-
 struct S2rPostChain {
-    // The choruses (s2r_set_bus_chorus).  Everything of theirs is allocated when a chorus is set, never in a fill.
-    struct BusChorus {
-        uint32_t voices = 0;                     // V; 0: the bus has no chorus
-        uint32_t history = 0;                    // H = floor(fl(base + depth)) + 1
+    // what a stem stage keeps beside its buses' effects
+    struct Stem {
+        float *stage = nullptr;                  // [S2R_MAX_BUSES][2 * max_frames]: the stage's input in a call that runs it, allocated when its effect is first set
+        S2rPostTimer timer;                      // around the stage's kernels of the last bus or master fill: 0 when it ran none (tools/{chorus,delay,reverb}_time.py)
+    } stem[S2R_STEM_STAGES];
+    // The choruses (s2r_set_bus_chorus): lines of [H][2], oldest frame first, L then R, H = history = floor(fl(base + depth)) + 1
+    struct BusChorus : S2rBusLine {
+        uint32_t voices = 0;                     // V
         float base = 0.0f, depth = 0.0f, dry = 0.0f, wet = 0.0f;
         uint32_t phase_inc = 0, spread = 0;
         uint32_t phase = 0;                      // the LFO's phase at frame 0 of the next call: moved on by the commit
-        float *line[2] = {nullptr, nullptr};     // [H][2] each, oldest frame first, L then R: line[cur] holds the history of the input, the kernel writes the other
-        int cur = 0;
-        void release() { for (float *p : line) if (p) (void)hipFree(p); *this = BusChorus{}; }
     } chorus[S2R_MAX_BUSES];
-    float *chorus_stage = nullptr;               // [S2R_MAX_BUSES][2 * max_frames]: where the bus combine writes in a call that runs a chorus
-    S2rPostTimer chorus_timer;                   // around the chorus kernel of the last bus or master fill: 0 when it ran none (tools/chorus_time.py)
-    // The delays (s2r_set_bus_delay).  Everything of theirs is allocated when a delay is set, never in a fill.
-    struct BusDelay {
-        uint32_t delay = 0;                      // D; 0: the bus has no delay
+    // The delays (s2r_set_bus_delay): lines of [D][2], oldest frame first, L then R, D = history
+    struct BusDelay : S2rBusLine {
         float feedback = 0.0f, cross = 0.0f, dry = 0.0f, wet = 0.0f;
-        float *line[2] = {nullptr, nullptr};     // [D][2] each, oldest frame first, L then R: line[cur] holds the history, the kernel writes the other
-        int cur = 0;
-        void release() { for (float *p : line) if (p) (void)hipFree(p); *this = BusDelay{}; }
     } delay[S2R_MAX_BUSES];
-    float *delay_stage = nullptr;                // [S2R_MAX_BUSES][2 * max_frames]: where the bus combine writes in a call that runs a delay
-    S2rPostTimer delay_timer;                    // around the delay kernel of the last bus or master fill: 0 when it ran none (tools/delay_time.py)
-    // The reverbs (s2r_set_bus_reverb).  Everything of theirs is allocated when a reverb is set, never in a fill.
-    struct BusFx {
-        uint32_t n_taps = 0;                     // K; 0: the bus has no reverb
+    // The reverbs (s2r_set_bus_reverb): lines of [2][lstride], history = K - 1 frames per channel in front of a call's dry frames
+    struct BusFx : S2rBusLine {
+        uint32_t n_taps = 0;                     // K
         float dry = 0.0f, wet = 0.0f;
         float *taps = nullptr;                   // [2][tstride]: ir_L, ir_R, padded with +0.0 up to whole segments
-        float *line[2] = {nullptr, nullptr};     // [2][lstride] each: K - 1 frames of history per channel in front of a call's dry frames; line[cur] holds the history
         float *partials = nullptr;               // [2][n_seg][pstride]
         uint32_t tstride = 0, lstride = 0;
-        int cur = 0;
-        void release() { for (float *p : {taps, line[0], line[1], partials}) if (p) (void)hipFree(p); *this = BusFx{}; }
+        void free() { for (float *p : {taps, partials}) if (p) (void)hipFree(p); S2rBusLine::free(); }
     } fx[S2R_MAX_BUSES];
-    float *fx_stage = nullptr;                   // [S2R_MAX_BUSES][2 * max_frames]: where the bus combine writes in a call that runs a reverb
-    S2rPostTimer fx_timer;                          // around the reverbs' kernels of the last bus or master fill: 0 when it ran none (tools/reverb_time.py)
+    // stage k's effect on a bus, as far as the stages are alike
+    S2rBusLine &bus(int k, uint32_t b) { S2rBusLine *const of[S2R_STEM_STAGES] = {&chorus[b], &delay[b], &fx[b]}; return *of[k]; }
+    const S2rBusLine &bus(int k, uint32_t b) const { return const_cast<S2rPostChain *>(this)->bus(k, b); }
     // The master section.  Nothing is allocated before the first master fill.
     struct Master {
         float ret[S2R_MAX_BUSES], ret_app[S2R_MAX_BUSES];        // what the caller last set — the target — and what the last master fill left — the applied
@@ -144,11 +111,10 @@ struct S2rPostChain {
     void release();
     // what the entry points of s2r_host.cpp do behind their checks, on a quiet stream
     hipError_t set_chorus(const S2rPostCtx &c, uint32_t bus, uint32_t voices, float base, float depth, uint32_t phase_inc, uint32_t spread, float dry, float wet);
-    hipError_t chorus_state(const S2rPostCtx &c, uint32_t bus, float *get, const float *set);       // the history: frames, oldest first, L then R
     hipError_t set_delay(const S2rPostCtx &c, uint32_t bus, uint32_t delay_frames, float feedback, float cross, float dry, float wet);
-    hipError_t delay_history(const S2rPostCtx &c, uint32_t bus, float *get, const float *set);      // frames, oldest first, L then R
     hipError_t set_reverb(const S2rPostCtx &c, uint32_t bus, const float *ir_l, const float *ir_r, uint32_t n_taps, float dry, float wet);
-    hipError_t reverb_history(const S2rPostCtx &c, uint32_t bus, float *get, const float *set);     // frames, oldest first, L then R
+    // the history of stage k's effect on a bus, out or in: `history` frames, oldest first, L then R
+    hipError_t history(const S2rPostCtx &c, int k, uint32_t bus, float *get, const float *set);
     void snap_master() { for (uint32_t b = 0; b < S2R_MAX_BUSES; b++) master.ret_app[b] = master.ret[b]; master.fader_app = master.fader; }
     void set_limiter(float ceiling, uint32_t lookahead, uint32_t hold);      // (0, 0, 0): off
     void set_limiter_state(const float *xh, const float *gh);

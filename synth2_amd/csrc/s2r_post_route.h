@@ -1,0 +1,41 @@
+// s2r_post_route.h — who reads and writes what in one call of the post-mix chain (s2r_post.h): plain pointers and integers, nothing of
+// HIP, so that the rule is checked by a program of its own on the CPU (tests/native/post_route.cpp).
+#pragma once
+#include <cstdint>
+
+// the stem stages — per-bus effects that read the buses' stems from one staging buffer and write them to the next — in chain order
+enum S2rStemStage { S2R_STEM_CHORUS, S2R_STEM_DELAY, S2R_STEM_REVERB, S2R_STEM_STAGES };
+
+// every pointer of one call (s2r_post_route): the bus combine's, each stem stage's kernels', the master kernel's and the limiter's
+struct S2rPostRoute {
+    float *combine_out;
+    struct { float *in, *out; } stem[S2R_STEM_STAGES];
+    float *master_in, *master_out, *master_stems, *limiter_in, *limiter_out;
+};
+struct S2rPostCall {                             // one fill, as prepare leaves it
+    uint32_t n_buses = 0, frames = 0;            // n_buses 0: a panned fill, which runs no stage
+    bool master = false, stems = false;          // s2r_fill_master; the caller wants the stems too
+    bool on[S2R_STEM_STAGES] = {};               // the stage's effect sits on one of the call's buses
+    bool limited = false;                        // a master fill with the limiter set
+    S2rPostRoute route{};
+};
+
+// Who reads and writes what, the only place that decides it.  The combine writes into the first stem stage that runs, each running
+// stage into the next running stage's input, and whichever of them writes the stems LAST writes them where the call wants them: the
+// pinned output in a bus fill; the master's device stage in a master fill, whose kernel must not read pinned memory back and copies
+// them out itself when the caller wants them (master_stems = bus_out_dev then, else null).  The master kernel's two channels go to
+// the pinned output unless the limiter follows and writes there in its place.  A stage that does not run has null pointers: a
+// limiter that is set is idle in a bus fill, an effect on a bus past the call's in any; a panned fill (no buses) has no route.
+// `stem_stage[k]`: stage k's staging buffer, which only a call that runs the stage looks at.
+inline S2rPostRoute s2r_post_route(const S2rPostCall &call, float *const stem_stage[S2R_STEM_STAGES], float *master_stage, float *limiter_in, float *bus_out_dev,
+                                   float *out_host_dev) {
+    S2rPostRoute r{};
+    if (!call.n_buses) return r;
+    float **writer = &r.combine_out;                             // the destination of whoever wrote the stems last so far
+    for (int k = 0; k < S2R_STEM_STAGES; k++)
+        if (call.on[k]) { *writer = r.stem[k].in = stem_stage[k]; writer = &r.stem[k].out; }
+    *writer = call.master ? master_stage : bus_out_dev;
+    if (call.master) { r.master_in = master_stage; r.master_out = call.limited ? limiter_in : out_host_dev; r.master_stems = call.stems ? bus_out_dev : nullptr; }
+    if (call.limited) { r.limiter_in = limiter_in; r.limiter_out = out_host_dev; }
+    return r;
+}

@@ -1,6 +1,6 @@
 """The stages behind the bus mixdown — reverb, master section, master limiter — on ONE handle that changes
 its configuration from call to call.  The files of the three stages mostly hold a handle in one configuration; which buffer each
-stage reads and writes is decided per call (s2r_post_route, csrc/s2r_post.h), and what can go wrong there is the step from one route to
+stage reads and writes is decided per call (s2r_post_route, csrc/s2r_post_route.h), and what can go wrong there is the step from one route to
 the next.  Handles, events and the one-pole bank are tests/test_gpu_reverb.py's; the models are the host test files'."""
 import numpy as np
 import pytest

@@ -1,6 +1,7 @@
 """ASan + UBSan over the handle-free rule functions (csrc/s2r_rules.cpp: the reverb, master and limiter references and the mixer's
 gain rules), which need neither a handle nor HIP: the file is compiled by plain g++ beside a small program of its own
-(tests/native/san_rules.cpp) and run as a child process, with no preload of any kind."""
+(tests/native/san_rules.cpp) and run as a child process, with no preload of any kind.  The post-mix chain's route (csrc/s2r_post_route.h)
+goes the same way with tests/native/post_route.cpp."""
 import os
 import shutil
 import subprocess
@@ -24,3 +25,16 @@ def test_rule_functions_under_asan_ubsan(tmp_path):
     out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     assert "rules ok" in out.stdout
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
+def test_post_route_under_asan_ubsan(tmp_path):
+    """who reads and writes what behind the bus mixdown (s2r_post_route, csrc/s2r_post_route.h, a header without HIP): a panned call,
+    bus fills x the 8 subsets of running stem stages, master fills x 8 subsets x limiter on or off x stems wanted or not, each route
+    against the 24 routes written out by hand (the table of tests/native/post_route.cpp) and against the rule stated without it"""
+    exe = str(tmp_path / "post_route")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-I", os.path.join(ROOT, "synth2_amd", "csrc"), os.path.join(ROOT, "tests", "native", "post_route.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-3000:]
+    assert "route ok" in out.stdout
