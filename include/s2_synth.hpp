@@ -174,6 +174,22 @@ class Synth {
                                 uint32_t frames, float *history_lr, uint32_t *phase, float *out_lr) {
         return s2r_chorus_reference(voices, base, depth, phase_inc, spread, dry, wet, x_lr, frames, history_lr, phase, out_lr);
     }
+    // per-bus parametric EQ at the head of the chain, in front of the bus's chorus (build-defined; s2r.h: s2r_set_bus_eq): n_bands in
+    // 1 .. S2R_EQ_MAX_BANDS biquads, coeffs [n_bands][5] as (b0, b1, b2, a1, a2) normalised by a0 (eq_design makes a band), finite, |a2| < 1
+    // and |a1| < 1 + a2; in sample_buses and sample_master only
+    void set_bus_eq(uint32_t bus, uint32_t n_bands, const float *coeffs) { check(s2r_set_bus_eq(h_, bus, n_bands, coeffs)); }
+    void clear_bus_eq(uint32_t bus) { check(s2r_set_bus_eq(h_, bus, 0, nullptr)); }
+    void set_bus_eq_coeffs(uint32_t bus, uint32_t n_bands, const float *coeffs) { check(s2r_set_bus_eq_coeffs(h_, bus, n_bands, coeffs)); }    // the state stays
+    void get_bus_eq(uint32_t bus, uint32_t *n_bands, float *coeffs, size_t capacity) const { check(s2r_get_bus_eq(h_, bus, n_bands, coeffs, capacity)); }
+    // 4 * n_bands floats: [band][s1_L, s1_R, s2_L, s2_R]
+    void bus_eq_state(uint32_t bus, float *state, size_t capacity) { check(s2r_get_bus_eq_state(h_, bus, state, capacity)); }
+    void set_bus_eq_state(uint32_t bus, const float *state, size_t count) { check(s2r_set_bus_eq_state(h_, bus, state, count)); }
+    static int eq_reference(uint32_t n_bands, const float *coeffs, const float *x_lr, uint32_t frames, float *state, float *out_lr) {
+        return s2r_eq_reference(n_bands, coeffs, x_lr, frames, state, out_lr);
+    }
+    static int eq_design(int kind, double freq_hz, double gain_db, double q, double sample_rate, float coeffs[5]) {
+        return s2r_eq_design(kind, freq_hz, gain_db, q, sample_rate, coeffs);
+    }
 
     // the master section (build-defined; s2r.h: s2r_fill_master): a return level per bus and a master fader, each in [0, 1] and each
     // reaching its target as a ramp across the next sample_master call, and the meters of that call — in sample_master only

@@ -42,7 +42,8 @@ extern "C" {
  * s2r_set_limiter_state, s2r_get_limiter_meters, s2r_limiter_reference, s2r_set_bus_delay, s2r_set_bus_delay_mix,
  * s2r_get_bus_delay, s2r_get_bus_delay_history, s2r_set_bus_delay_history, s2r_delay_reference, s2r_chorus_history_frames,
  * s2r_set_bus_chorus, s2r_set_bus_chorus_mix, s2r_set_bus_chorus_rate, s2r_get_bus_chorus, s2r_get_bus_chorus_state,
- * s2r_set_bus_chorus_state, s2r_chorus_reference. */
+ * s2r_set_bus_chorus_state, s2r_chorus_reference, s2r_set_bus_eq, s2r_set_bus_eq_coeffs, s2r_get_bus_eq, s2r_get_bus_eq_state,
+ * s2r_set_bus_eq_state, s2r_eq_reference, s2r_eq_design. */
 #define S2R_ABI_VERSION 4
 
 typedef enum {
@@ -492,6 +493,57 @@ int s2r_get_bus_chorus_state(s2r_synth *s, uint32_t bus, float *lr, size_t capac
 int s2r_set_bus_chorus_state(s2r_synth *s, uint32_t bus, const float *lr, size_t count, uint32_t phase);
 int s2r_chorus_reference(uint32_t voices, float base, float depth, uint32_t phase_inc, uint32_t spread, float dry, float wet, const float *x_lr,
                          uint32_t frames, float *history_lr, uint32_t *phase, float *out_lr);
+
+/* BUILD-DEFINED per-bus parametric equaliser (the reference has no effects), computed on the device at the head of
+ * the chain: combine -> eq -> chorus -> delay -> reverb -> master -> limiter.  A bus b in [0, S2R_MAX_BUSES) may carry an EQ of
+ * n_bands (1 .. S2R_EQ_MAX_BANDS) biquad bands, cascaded in band order.  A band is five binary32 coefficients (b0, b1, b2, a1, a2),
+ * already divided by a0, all finite, inside the stability triangle: |a2| < 1 and |a1| < 1 + a2, evaluated in binary64 from the
+ * binary32 values.  Both channels use the same coefficients.  The state is (s1, s2) per band and channel, 4 * n_bands floats per bus,
+ * laid out [band][s1_L, s1_R, s2_L, s2_R]; +0.0 right after the EQ is set.  Transposed direct form II: per channel c and band k, with
+ * x the previous band's y at the same frame (for band 0: what the bus combine writes for bus b, channel c):
+ *   y   = fl(fl(b0 * x) + s1)
+ *   s1' = fl(fl(fl(b1 * x) - fl(a1 * y)) + s2)
+ *   s2' = fl(fl(b2 * x) - fl(a2 * y))
+ * binary32 throughout, every product and every sum rounded on its own (no fma), denormals kept, no operation skipped for a zero
+ * coefficient.  The last band's y is the bus's signal from there on: a chorus on the same bus takes it as its x, otherwise a delay,
+ * otherwise a reverb as its dry signal, otherwise the stems and the master section.  Non-finite bus samples are outside the
+ * contract.  After a call that returns S2R_OK the state is what the last frame left: calls of any lengths concatenate.  The EQ runs
+ * once per call over all N frames, after every event segment and rows slice of the call has been mixed.  An EQ on a bus >= the
+ * call's n_buses is idle in that call (no output, state untouched).  A bus without an EQ passes through bit for bit, -0.0 included;
+ * a unit band (1, 0, 0, 0, 0) does NOT: y = fl(x + s1) with s1 = +0.0 turns a -0.0 into +0.0, and the rule says so.  A refused or
+ * failed call leaves the state untouched.  ONLY s2r_fill_buses and s2r_fill_master apply EQs; every other fill ignores them.  An EQ
+ * is a property of the bus: s2r_set_patch_bank, program changes and s2r_import_state leave it alone.  A handle on which no EQ was
+ * ever set launches what it launched before and allocates nothing for one.  The two copies of the state and a staging buffer for the
+ * combined buses live in device memory allocated when an EQ is set (S2R_ERR_OUT_OF_MEMORY when that fails, and the earlier EQ is
+ * kept), never inside a fill, and released with the handle.
+ *   s2r_set_bus_eq: coeffs is [n_bands][5]; replaces any earlier EQ of the bus and zeroes its state; n_bands == 0 removes it (coeffs
+ *   is then not looked at).  S2R_ERR_PATCH_RANGE for bus >= S2R_MAX_BUSES, n_bands > S2R_EQ_MAX_BANDS, a coefficient that is not
+ *   finite or a band outside the stability triangle (checked before the handle is looked at; nothing is changed); S2R_ERR_INVALID
+ *   for a NULL coeffs with n_bands > 0.
+ *   s2r_set_bus_eq_coeffs: the coefficients alone — the state stays, so a band moves between calls without a restart.  The same
+ *   range checks; S2R_ERR_INVALID on a bus without an EQ or when n_bands is not the EQ's.
+ *   s2r_get_bus_eq: *n_bands is 0 for a bus without one; coeffs receives 5 * n_bands floats when it is not NULL (S2R_ERR_INVALID
+ *   for a capacity below that); n_bands may be NULL.
+ *   s2r_get_bus_eq_state / s2r_set_bus_eq_state: the 4 * n_bands floats of the state: the checkpoint companions of the chorus's
+ *   pair.  S2R_ERR_INVALID for a capacity below, or a count other than, 4 * n_bands, a NULL buffer, and on a bus without an EQ.
+ *   Single-device handles (a NULL or a device-list handle: S2R_ERR_INVALID from all five).
+ *   s2r_eq_reference: the rule above for both channels on the host (no device, no handle): x_lr is [frames][2]; state is
+ *   [n_bands][4] as above, updated in place to the state after the call; out_lr, [frames][2], may be NULL.  Range checks as above
+ *   (and n_bands >= 1); S2R_ERR_INVALID for a NULL coeffs or state, or a NULL x_lr with frames > 0.
+ *   s2r_eq_design: a band from the usual parameters, by the Audio-EQ-Cookbook (R. Bristow-Johnson) formulas with q as Q (DESIGN.md
+ *   4.21 writes them out): computed in binary64, divided by a0, then rounded once to binary32.  gain_db is looked at by the peak and
+ *   the shelves only (but must not be a NaN).  S2R_ERR_PATCH_RANGE for a NaN, a kind that is none of the five, freq_hz outside
+ *   (0, sample_rate / 2), q <= 0, |gain_db| > 48 or a result that fails the setter's checks; S2R_ERR_INVALID for a NULL coeffs.
+ *   Device parity is always against the stored binary32 coefficients, never against this function. */
+#define S2R_EQ_MAX_BANDS 4u
+typedef enum { S2R_EQ_PEAK = 0, S2R_EQ_LOW_SHELF = 1, S2R_EQ_HIGH_SHELF = 2, S2R_EQ_LOWPASS = 3, S2R_EQ_HIGHPASS = 4 } s2r_eq_kind;
+int s2r_set_bus_eq(s2r_synth *s, uint32_t bus, uint32_t n_bands, const float *coeffs);
+int s2r_set_bus_eq_coeffs(s2r_synth *s, uint32_t bus, uint32_t n_bands, const float *coeffs);
+int s2r_get_bus_eq(const s2r_synth *s, uint32_t bus, uint32_t *n_bands, float *coeffs, size_t capacity);
+int s2r_get_bus_eq_state(s2r_synth *s, uint32_t bus, float *state, size_t capacity);
+int s2r_set_bus_eq_state(s2r_synth *s, uint32_t bus, const float *state, size_t count);
+int s2r_eq_reference(uint32_t n_bands, const float *coeffs, const float *x_lr, uint32_t frames, float *state, float *out_lr);
+int s2r_eq_design(int kind, double freq_hz, double gain_db, double q, double sample_rate, float coeffs[5]);
 
 /* BUILD-DEFINED master section (the reference's Synth::sample returns one stream; DESIGN.md 4.17 gives the op sequence): the last stage
  * of the chain send -> effect -> return -> master, on the device the bus signals are already on.  Every bus b in [0, S2R_MAX_BUSES) has

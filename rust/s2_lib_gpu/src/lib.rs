@@ -186,6 +186,13 @@ pub mod ffi {
         pub fn s2r_set_bus_chorus_state(s: *mut S2rSynth, bus: u32, lr: *const f32, count: usize, phase: u32) -> c_int;
         pub fn s2r_chorus_reference(voices: u32, base: f32, depth: f32, phase_inc: u32, spread: u32, dry: f32, wet: f32, x_lr: *const f32,
                                     frames: u32, history_lr: *mut f32, phase: *mut u32, out_lr: *mut f32) -> c_int;
+        pub fn s2r_set_bus_eq(s: *mut S2rSynth, bus: u32, n_bands: u32, coeffs: *const f32) -> c_int;
+        pub fn s2r_set_bus_eq_coeffs(s: *mut S2rSynth, bus: u32, n_bands: u32, coeffs: *const f32) -> c_int;
+        pub fn s2r_get_bus_eq(s: *const S2rSynth, bus: u32, n_bands: *mut u32, coeffs: *mut f32, capacity: usize) -> c_int;
+        pub fn s2r_get_bus_eq_state(s: *mut S2rSynth, bus: u32, state: *mut f32, capacity: usize) -> c_int;
+        pub fn s2r_set_bus_eq_state(s: *mut S2rSynth, bus: u32, state: *const f32, count: usize) -> c_int;
+        pub fn s2r_eq_reference(n_bands: u32, coeffs: *const f32, x_lr: *const f32, frames: u32, state: *mut f32, out_lr: *mut f32) -> c_int;
+        pub fn s2r_eq_design(kind: c_int, freq_hz: f64, gain_db: f64, q: f64, sample_rate: f64, coeffs: *mut f32) -> c_int;
         pub fn s2r_set_bus_return(s: *mut S2rSynth, bus: u32, level: f32) -> c_int;
         pub fn s2r_get_bus_return(s: *const S2rSynth, bus: u32, level: *mut f32, applied: *mut f32) -> c_int;
         pub fn s2r_set_master_fader(s: *mut S2rSynth, level: f32) -> c_int;
@@ -245,6 +252,13 @@ pub const MAX_DELAY_FRAMES: u32 = 262144;
 /// frames.
 pub const CHORUS_MAX_VOICES: u32 = 8;
 pub const CHORUS_MAX_DELAY: f32 = 4095.0;
+/// `S2R_EQ_MAX_BANDS`: the most biquad bands of a bus EQ, and the kinds of `s2r_eq_kind`.
+pub const EQ_MAX_BANDS: u32 = 4;
+pub const EQ_PEAK: i32 = 0;
+pub const EQ_LOW_SHELF: i32 = 1;
+pub const EQ_HIGH_SHELF: i32 = 2;
+pub const EQ_LOWPASS: i32 = 3;
+pub const EQ_HIGHPASS: i32 = 4;
 /// `S2R_METER_BLOCK`: the frames of one block of the meters' energy tree (part of the master section's rule).
 pub const METER_BLOCK: u32 = 256;
 /// `S2R_LIMITER_MAX_LOOKAHEAD`, `S2R_LIMITER_MAX_HOLD`: the master limiter's longest lookahead and hold in frames, and
@@ -313,6 +327,27 @@ pub fn chorus_reference(voices: u32, base: f32, depth: f32, phase_inc: u32, spre
                                   phase as *mut u32, out.as_mut_ptr())
     };
     if rc == 0 { Ok(out) } else { Err(rc) }
+}
+
+/// Host-only: the bus EQ's rule for both channels (`s2r_eq_reference`).  `coeffs`: `(b0, b1, b2, a1, a2)` per band;
+/// `x_lr`: L, R pairs; `state`: `4 * n_bands` floats, `[band][s1_L, s1_R, s2_L, s2_R]`, updated in place to the state after the call;
+/// returns one output pair per input pair, or the status.
+pub fn eq_reference(coeffs: &[[f32; 5]], x_lr: &[f32], state: &mut [f32]) -> Result<Vec<f32>, i32> {
+    assert!(x_lr.len() % 2 == 0 && state.len() == 4 * coeffs.len());
+    let mut out = vec![0.0f32; x_lr.len()];
+    let rc = unsafe {
+        ffi::s2r_eq_reference(coeffs.len() as u32, coeffs.as_ptr() as *const f32, x_lr.as_ptr(), (x_lr.len() / 2) as u32, state.as_mut_ptr(),
+                              out.as_mut_ptr())
+    };
+    if rc == 0 { Ok(out) } else { Err(rc) }
+}
+
+/// A band `(b0, b1, b2, a1, a2)` from the usual parameters, by the Audio-EQ-Cookbook formulas with `q` as Q (`s2r_eq_design`): `kind`
+/// one of `EQ_PEAK` .. `EQ_HIGHPASS`; computed in f64, divided by a0, rounded once to f32.
+pub fn eq_design(kind: i32, freq_hz: f64, gain_db: f64, q: f64, sample_rate: f64) -> Result<[f32; 5], i32> {
+    let mut c = [0.0f32; 5];
+    let rc = unsafe { ffi::s2r_eq_design(kind, freq_hz, gain_db, q, sample_rate, c.as_mut_ptr()) };
+    if rc == 0 { Ok(c) } else { Err(rc) }
 }
 
 /// Host-only: the master section's rule (`s2r_master_reference`).  `stems`: `r0.len()` buses of `frames` L, R
@@ -727,6 +762,42 @@ pub mod synth {
 
         pub fn set_bus_chorus_state(&mut self, bus: u32, lr: &[f32], phase: u32) {
             self.check(unsafe { ffi::s2r_set_bus_chorus_state(self.handle, bus, lr.as_ptr(), lr.len(), phase) });
+        }
+
+        /// Build-defined per-bus parametric EQ (`s2r_set_bus_eq`, include/s2r.h) at the head of the chain, in front of the bus's
+        /// chorus: 1 ..= EQ_MAX_BANDS biquad bands `(b0, b1, b2, a1, a2)`, normalised by a0, finite, `|a2| < 1` and `|a1| < 1 + a2`
+        /// (`eq_design` makes one); replaces any earlier EQ of the bus and zeroes its state.  In `sample_buses` and `sample_master` only.
+        pub fn set_bus_eq(&mut self, bus: u32, coeffs: &[[f32; 5]]) {
+            assert!(!coeffs.is_empty(), "clear_bus_eq removes an EQ");
+            self.check(unsafe { ffi::s2r_set_bus_eq(self.handle, bus, coeffs.len() as u32, coeffs.as_ptr() as *const f32) });
+        }
+
+        pub fn clear_bus_eq(&mut self, bus: u32) {
+            self.check(unsafe { ffi::s2r_set_bus_eq(self.handle, bus, 0, std::ptr::null()) });
+        }
+
+        /// The coefficients alone, as many bands as the EQ has; the state stays, so a band moves without a restart.
+        pub fn set_bus_eq_coeffs(&mut self, bus: u32, coeffs: &[[f32; 5]]) {
+            self.check(unsafe { ffi::s2r_set_bus_eq_coeffs(self.handle, bus, coeffs.len() as u32, coeffs.as_ptr() as *const f32) });
+        }
+
+        /// The bands of the bus's EQ; empty for a bus without one.
+        pub fn get_bus_eq(&self, bus: u32) -> Vec<[f32; 5]> {
+            let mut n = 0u32;
+            let mut c = [[0.0f32; 5]; super::EQ_MAX_BANDS as usize];
+            self.check(unsafe { ffi::s2r_get_bus_eq(self.handle, bus, &mut n, c.as_mut_ptr() as *mut f32, 5 * c.len()) });
+            c[..n as usize].to_vec()
+        }
+
+        /// The `4 * n_bands` floats of the EQ's state, `[band][s1_L, s1_R, s2_L, s2_R]`: checkpoint companion of `bus_chorus_state`.
+        pub fn bus_eq_state(&mut self, bus: u32) -> Vec<f32> {
+            let mut st = vec![0.0f32; 4 * self.get_bus_eq(bus).len()];
+            self.check(unsafe { ffi::s2r_get_bus_eq_state(self.handle, bus, st.as_mut_ptr(), st.len()) });
+            st
+        }
+
+        pub fn set_bus_eq_state(&mut self, bus: u32, state: &[f32]) {
+            self.check(unsafe { ffi::s2r_set_bus_eq_state(self.handle, bus, state.as_ptr(), state.len()) });
         }
 
         /// Build-defined master section (`s2r_fill_master`, include/s2r.h): the target of a bus's return level (in [0, 1]), reached

@@ -19,7 +19,7 @@ LIB = os.path.join(HERE, "libs2r.so")
 SOURCES = ["s2r_render_onepole_square.hip", "s2r_render_onepole_saw.hip", "s2r_render_onepole_triangle.hip",
            "s2r_render_onepole_sine.hip", "s2r_render_general_square.hip", "s2r_render_general_saw.hip",
            "s2r_render_general_triangle.hip", "s2r_render_general_sine.hip", "s2r_render_general_bank.hip",
-           "s2r_aux.hip", "s2r_chorus.hip", "s2r_delay.hip", "s2r_fx.hip", "s2r_master.hip", "s2r_limiter.hip", "s2r_host.cpp", "s2r_post.cpp", "s2r_rules.cpp", "s2r_patch.cpp",
+           "s2r_aux.hip", "s2r_eq.hip", "s2r_chorus.hip", "s2r_delay.hip", "s2r_fx.hip", "s2r_master.hip", "s2r_limiter.hip", "s2r_host.cpp", "s2r_post.cpp", "s2r_rules.cpp", "s2r_patch.cpp",
            "s2r_stream.cpp"]
 HEADERS = ["s2r_device.h", "s2r_math.h", "s2r_patch.h", "s2r_voices.h", "s2r_kern_common.h", "s2r_render_onepole.inc",
            "s2r_render_general.inc", "s2r_post.h", "s2r_post_route.h", "s2r_rules.h"]
@@ -50,7 +50,7 @@ PER_FILE_FLAGS = {}
 for _f in ("s2r_render_general_square.hip", "s2r_render_general_saw.hip", "s2r_render_general_triangle.hip", "s2r_render_general_sine.hip",
            "s2r_render_general_bank.hip"):
     PER_FILE_FLAGS[_f] = ["-ftrivial-auto-var-init=zero"]
-# Six translation units are compiled with the back end's resource-usage remarks, and _check_resources() fails the build when a
+# Seven translation units are compiled with the back end's resource-usage remarks, and _check_resources() fails the build when a
 # kernel named here went to scratch or spilled, or when fewer kernels report than the file instantiates.  Per source file: the
 # substrings that name its checked kernels; how many reports are expected — ("at least", n), ("exactly", n), or ("each", None):
 # one or more of every name — and why so many; the figures that must be "0"; and what the kernels keep where it belongs.  (The
@@ -65,6 +65,9 @@ RESOURCE_CHECKS = {
     "s2r_fx.hip": (("s2r_fx_stage_kernel", "s2r_fx_convolve_kernel", "s2r_fx_finish_kernel"), ("each", None), "the reverb's three kernels",
                    (_SCRATCH, _VSPILL, _SSPILL), "its windows and sums must stay in registers"),
     # up to sixteen stem samples and eighteen meter values per thread
+    # one band of one channel of one bus per lane: five coefficients, two states, a tile of input loaded ahead
+    "s2r_eq.hip": (("s2r_eq_kernel",), ("exactly", 1), "one kernel",
+                   (_SCRATCH, _VSPILL, _SSPILL), "its coefficients, states and the tile loaded ahead must stay in registers"),
     # one frame of the chorus per thread: both channels, up to eight voices, two taps each
     "s2r_chorus.hip": (("s2r_chorus_kernel",), ("exactly", 1), "one kernel",
                        (_SCRATCH, _VSPILL, _SSPILL), "its phases, taps and sums must stay in registers"),
@@ -81,6 +84,11 @@ for _f in RESOURCE_CHECKS:
 if os.environ.get("S2R_EXPERIMENT_BANK_FLAGS"):                 # (development: extra flags for the patch-bank translation unit)
     PER_FILE_FLAGS["s2r_render_general_bank.hip"] = PER_FILE_FLAGS["s2r_render_general_bank.hip"] + os.environ["S2R_EXPERIMENT_BANK_FLAGS"].split()
 
+# S2R_EQ_SERIAL=1 in the environment builds the EQ kernel's dropped form (one thread runs a channel's whole cascade; csrc/s2r_eq.hip,
+# CHANGELOG) into libs2r_eqserial.so, for tools/eq_time.py to time beside the product through S2R_AB_LIB.  Never the product build.
+_EQ_SERIAL = os.environ.get("S2R_EQ_SERIAL") == "1"
+if _EQ_SERIAL:
+    PER_FILE_FLAGS["s2r_eq.hip"] = PER_FILE_FLAGS["s2r_eq.hip"] + ["-DS2R_EQ_SERIAL"]
 # S2R_OPT=O3 in the environment builds the same sources at -O3 into libs2r_o3.so (tools and tests that compare the two
 # optimisation levels; the product is -O2).
 if os.environ.get("S2R_OPT") == "O3":
@@ -94,6 +102,9 @@ if os.environ.get("S2R_STAMPS") == "1":
     OBJ_DIR_NAME = "_build_stamps"
 elif os.environ.get("S2R_OPT") == "O3":
     OBJ_DIR_NAME = "_build_o3"
+elif _EQ_SERIAL:
+    LIB = os.path.join(HERE, "libs2r_eqserial.so")
+    OBJ_DIR_NAME = "_build_eqserial"
 else:
     OBJ_DIR_NAME = "_build"
 

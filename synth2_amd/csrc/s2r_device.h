@@ -475,6 +475,26 @@ struct S2rChorus {
 // all among the call's buses
 hipError_t s2r_launch_bus_chorus(const S2rChorus &a, hipStream_t stream);
 
+// The per-bus parametric EQ at the head of the chain: a cascade of up to S2R_EQ_MAX_BANDS biquads in transposed
+// direct form II.  A bus's line holds its state, [band][s1_L, s1_R, s2_L, s2_R]; `next` receives the state the next call starts
+// from (the host swaps the two).
+#define S2R_EQ_TILE 64u           // frames the kernel stages at a time: its loads run one tile ahead, its stores one tile behind
+struct S2rEqBus {
+    const float *line;            // [n_bands][4]
+    float *next;                  // [n_bands][4], not `line`
+    uint32_t n_bands;             // 0: no EQ on this bus: it is copied from `in` to `out`
+    float c[S2R_EQ_MAX_BANDS][5]; // (b0, b1, b2, a1, a2) per band
+};
+struct S2rEq {
+    S2rEqBus bus[S2R_MAX_BUSES];
+    const float *in;              // [n_buses][2 * frames]: what the bus combine wrote, bus-major, L, R interleaved inside a bus
+    float *out;                   // the same layout, not `in`: what the next stage, or the caller, reads
+    uint32_t n_buses, frames;
+};
+// one kernel: the EQs' outputs and next states, the other buses unchanged; hipErrorInvalidValue for a null pointer, in == out,
+// line == next, more than S2R_EQ_MAX_BANDS bands, n_buses past S2R_MAX_BUSES or no EQ at all among the call's buses
+hipError_t s2r_launch_bus_eq(const S2rEq &a, hipStream_t stream);
+
 // The master section of s2r_fill_master: the stems of a call, post-effect, each times its return's ramp, added in
 // bus order from +0.0, times the master fader's ramp; and the call's meters.  gain at frame i of the CALL: r0 + (float)i * dr (the
 // product rounded, then the sum); a pair that did not move has dr = +0.0.

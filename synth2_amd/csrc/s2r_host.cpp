@@ -2811,6 +2811,69 @@ int s2r_set_bus_reverb_history(s2r_synth *s, uint32_t bus, const float *lr, size
     return stem_history(s, S2R_STEM_REVERB, bus, nullptr, lr ? lr : &none, lr ? count : (count ? (size_t)-1 : 0), "s2r_set_bus_reverb_history");
 }
 
+// ---- per-bus equalisers: at the head of the chain, in front of the choruses.  Not a stem stage (s2r_post_route.h):
+// stem_set carries the setter's tail, the guard of the other entries is its own ----
+static int eq_values(s2r_synth *s, const char *who, uint32_t bus, uint32_t n_bands, const float *coeffs) {
+    if (bus >= S2R_MAX_BUSES || !eq_in_range(n_bands, coeffs))
+        return set_err(s, S2R_ERR_PATCH_RANGE, "%s: bus %u, %u bands: at most %u bands of finite coefficients (b0, b1, b2, a1, a2) with |a2| < 1 and "
+                       "|a1| < 1 + a2, the bus below %u", who, bus, n_bands, S2R_EQ_MAX_BANDS, S2R_MAX_BUSES);
+    return S2R_OK;
+}
+
+// the bus in range, a single-device handle, and the bus carries an EQ
+static int eq_bus(s2r_synth *s, uint32_t bus, const char *who) {
+    if (bus >= S2R_MAX_BUSES) return set_err(s, S2R_ERR_PATCH_RANGE, "%s: bus %u, below %u", who, bus, S2R_MAX_BUSES);
+    S2R_TRY(post_handle(s, who, "bus equalisers are"));
+    if (!s->post.eq[bus].present()) return set_err(s, S2R_ERR_INVALID, "%s: bus %u carries no EQ", who, bus);
+    return S2R_OK;
+}
+
+int s2r_set_bus_eq(s2r_synth *s, uint32_t bus, uint32_t n_bands, const float *coeffs) {
+    S2R_TRY(eq_values(s, "s2r_set_bus_eq", bus, n_bands, coeffs));
+    S2R_TRY(post_handle(s, "s2r_set_bus_eq", "bus equalisers are"));
+    if (n_bands && !coeffs) return set_err(s, S2R_ERR_INVALID, "s2r_set_bus_eq: %u bands and no coefficients", n_bands);
+    return stem_set(s, "s2r_set_bus_eq", [&](const S2rPostCtx &c) { return s->post.set_eq(c, bus, n_bands, coeffs); });
+}
+
+int s2r_set_bus_eq_coeffs(s2r_synth *s, uint32_t bus, uint32_t n_bands, const float *coeffs) {
+    S2R_TRY(eq_values(s, "s2r_set_bus_eq_coeffs", bus, n_bands, coeffs));
+    S2R_TRY(eq_bus(s, bus, "s2r_set_bus_eq_coeffs"));
+    S2rPostChain::BusEq &d = s->post.eq[bus];
+    if (n_bands != d.n_bands || !coeffs) return set_err(s, S2R_ERR_INVALID, "s2r_set_bus_eq_coeffs: the EQ of bus %u has %u bands, not %u", bus, d.n_bands, n_bands);
+    std::memcpy(d.c, coeffs, (size_t)n_bands * 5u * sizeof(float));          // (the state stays: the band moves without a restart)
+    return S2R_OK;
+}
+
+int s2r_get_bus_eq(const s2r_synth *s, uint32_t bus, uint32_t *n_bands, float *coeffs, size_t capacity) {
+    if (bus >= S2R_MAX_BUSES) return S2R_ERR_PATCH_RANGE;
+    if (!s || !s->kids.empty() || s->parent) return S2R_ERR_INVALID;
+    const S2rPostChain::BusEq &d = s->post.eq[bus];
+    if (coeffs && capacity < 5u * (size_t)d.n_bands) return S2R_ERR_INVALID;
+    put(n_bands, d.n_bands);
+    if (coeffs) std::memcpy(coeffs, d.c, (size_t)d.n_bands * 5u * sizeof(float));
+    return S2R_OK;
+}
+
+static int eq_state(s2r_synth *s, uint32_t bus, float *get, const float *set, size_t count, const char *who) {
+    S2R_TRY(eq_bus(s, bus, who));
+    const size_t n = 4u * (size_t)s->post.eq[bus].n_bands;
+    if (set ? count != n : count < n) return set_err(s, S2R_ERR_INVALID, "%s: the state of bus %u is %zu floats, not %zu", who, bus, n, count);
+    if (!get && !set) return set_err(s, S2R_ERR_INVALID, "%s: null buffer", who);
+    S2R_QUIESCE(s);
+    S2R_HIP(s, hipSetDevice(s->device));
+    S2R_HIP(s, hipStreamSynchronize(s->stream));
+    S2R_HIP(s, s->post.eq_state(post_ctx(s), bus, get, set));
+    return S2R_OK;
+}
+
+int s2r_get_bus_eq_state(s2r_synth *s, uint32_t bus, float *state, size_t capacity) {
+    return eq_state(s, bus, state, nullptr, capacity, "s2r_get_bus_eq_state");
+}
+
+int s2r_set_bus_eq_state(s2r_synth *s, uint32_t bus, const float *state, size_t count) {
+    return eq_state(s, bus, nullptr, state, state ? count : (size_t)-1, "s2r_set_bus_eq_state");
+}
+
 // ---- per-bus choruses: in front of the delays ----
 int s2r_set_bus_chorus(s2r_synth *s, uint32_t bus, uint32_t voices, float base, float depth, uint32_t phase_inc, uint32_t spread, float dry, float wet) {
     if ((voices && !chorus_in_range(voices, base, depth, dry, wet)) || bus >= S2R_MAX_BUSES)
@@ -3498,6 +3561,11 @@ extern "C" float s2r_debug_pan_mix_ms(const s2r_synth *s) { return s && s->timin
 extern "C" uint32_t s2r_debug_pan_slice(const s2r_synth *s) { return s ? s->pan_slice : 0u; }
 // ... and of the bus mixdown's kernels in the last s2r_fill_buses (tools/bus_time.py)
 extern "C" float s2r_debug_bus_mix_ms(const s2r_synth *s) { return s && s->timing ? s->bus_mix_ms : -1.0f; }
+// ... of the buses' EQ kernel in that fill: 0 when it ran none (tools/eq_time.py); whether the handle holds the EQs' staging buffer;
+// and the frames the kernel stages at a time (tests/test_gpu_eq.py picks its call lengths around it)
+extern "C" float s2r_debug_bus_eq_ms(const s2r_synth *s) { return s && s->timing ? s->post.eq_insert.timer.ms : -1.0f; }
+extern "C" int s2r_debug_bus_eq_allocated(const s2r_synth *s) { return s && s->post.eq_insert.stage ? 1 : 0; }
+extern "C" uint32_t s2r_debug_eq_tile(void) { return S2R_EQ_TILE; }
 // ... of the buses' chorus kernel in that fill: 0 when it ran none (tools/chorus_time.py)
 extern "C" float s2r_debug_bus_chorus_ms(const s2r_synth *s) { return s && s->timing ? s->post.stem[S2R_STEM_CHORUS].timer.ms : -1.0f; }
 // ... of the buses' delay kernel in that fill: 0 when it ran none (tools/delay_time.py)

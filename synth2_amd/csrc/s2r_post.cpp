@@ -1,4 +1,4 @@
-// s2r_post.cpp — the post-mix chain (s2r_post.h): the stem stages (choruses, delays, reverbs), master section, master limiter.  Compiled with hipcc, -ffp-contract=off.
+// s2r_post.cpp — the post-mix chain (s2r_post.h): the EQs, the stem stages (choruses, delays, reverbs), master section, master limiter.  Compiled with hipcc, -ffp-contract=off.
 #include "s2r_post.h"
 #include "s2r_rules.h"
 
@@ -67,6 +67,7 @@ hipError_t S2rPostChain::prepare(const S2rPostCtx &c, uint32_t n_buses, uint32_t
     call.n_buses = n_buses; call.frames = frames; call.master = master_fill; call.stems = stems;
     for (int k = 0; k < S2R_STEM_STAGES; k++)
         for (uint32_t b = 0; b < n_buses; b++) if (bus(k, b).present()) call.on[k] = true;       // (an effect on a bus past the call's is idle in it)
+    for (uint32_t b = 0; b < n_buses; b++) if (eq[b].present()) call.eq = true;                      // (and so is an EQ)
     call.limited = master_fill && limiter.lookahead != 0;
     if (call.master) {                                           // the device copy of the stems and the pinned rows of block partials
         if (!master.stage) POST_HIP(hipMalloc((void **)&master.stage, (size_t)2 * S2R_MAX_BUSES * c.max_frames * sizeof(float)));
@@ -79,13 +80,25 @@ hipError_t S2rPostChain::prepare(const S2rPostCtx &c, uint32_t n_buses, uint32_t
     }
     float *stages[S2R_STEM_STAGES];
     for (int k = 0; k < S2R_STEM_STAGES; k++) stages[k] = stem[k].stage;
-    call.route = s2r_post_route(call, stages, master.stage, limiter.in, c.bus_out_dev, c.out_host_dev);
+    call.route = s2r_post_route_eq(call, s2r_post_route(call, stages, master.stage, limiter.in, c.bus_out_dev, c.out_host_dev), eq_insert.stage);
     return hipSuccess;
 }
 
 hipError_t S2rPostChain::launch(const S2rPostCtx &c, const S2rPostCall &call) {
     const S2rPostRoute &r = call.route; const float fn = (float)call.frames;
-    if (call.on[S2R_STEM_CHORUS]) {                              // once per call, over all of its frames, in front of the delays
+    if (call.eq) {                                               // once per call, over all of its frames, in front of every stem stage
+        S2rEq a{};
+        for (uint32_t b = 0; b < call.n_buses; b++) {
+            const BusEq &f = eq[b];
+            if (!f.present()) continue;
+            S2rEqBus &d = a.bus[b];
+            d.line = f.now(); d.next = f.next(); d.n_bands = f.n_bands;
+            std::memcpy(d.c, f.c, sizeof d.c);
+        }
+        a.in = r.eq.in; a.out = r.eq.out; a.n_buses = call.n_buses; a.frames = call.frames;
+        POST_TIMED(c, eq_insert.timer, s2r_launch_bus_eq(a, c.stream));
+    }
+    if (call.on[S2R_STEM_CHORUS]) {                              // likewise, in front of the delays
         S2rChorus a{};
         for (uint32_t b = 0; b < call.n_buses; b++) {
             const BusChorus &f = chorus[b];
@@ -152,6 +165,7 @@ hipError_t S2rPostChain::launch(const S2rPostCtx &c, const S2rPostCall &call) {
 }
 
 void S2rPostChain::commit(const S2rPostCall &call) {
+    if (call.eq) for (uint32_t b = 0; b < call.n_buses; b++) if (eq[b].present()) eq[b].flip();     // the EQs' states have moved on
     for (int k = 0; k < S2R_STEM_STAGES; k++)                    // the histories have moved on
         if (call.on[k]) for (uint32_t b = 0; b < call.n_buses; b++) if (bus(k, b).present()) bus(k, b).flip();
     if (call.on[S2R_STEM_CHORUS])                                // ... and the choruses' phases
@@ -184,8 +198,9 @@ void S2rPostChain::commit(const S2rPostCall &call) {
     }
 }
 
-// a stage that the fill could have run and did not reads 0; a panned fill leaves all five values alone, a bus fill the master's two
+// a stage that the fill could have run and did not reads 0; a panned fill leaves all six values alone, a bus fill the master's two
 hipError_t S2rPostChain::read_timers(const S2rPostCall &call) {
+    if (call.n_buses) { eq_insert.timer.ms = 0.0f; if (call.eq) POST_HIP(eq_insert.timer.read()); }
     if (call.n_buses) for (int k = 0; k < S2R_STEM_STAGES; k++) { stem[k].timer.ms = 0.0f; if (call.on[k]) POST_HIP(stem[k].timer.read()); }
     if (call.master) {
         POST_HIP(master.timer.read());
@@ -196,11 +211,26 @@ hipError_t S2rPostChain::read_timers(const S2rPostCall &call) {
 }
 
 void S2rPostChain::release() {
-    for (uint32_t b = 0; b < S2R_MAX_BUSES; b++) { drop(chorus[b]); drop(delay[b]); drop(fx[b]); }
+    for (uint32_t b = 0; b < S2R_MAX_BUSES; b++) { drop(eq[b]); drop(chorus[b]); drop(delay[b]); drop(fx[b]); }
     for (Stem &st : stem) { if (st.stage) (void)hipFree(st.stage); st.timer.destroy(); }
+    if (eq_insert.stage) (void)hipFree(eq_insert.stage);
+    eq_insert.timer.destroy();
     for (float *p : {master.stage, limiter.state[0], limiter.state[1], limiter.in}) if (p) (void)hipFree(p);
     for (float *p : {master.partials, limiter.partials}) if (p) (void)hipHostFree(p);
     for (S2rPostTimer *t : {&master.timer, &limiter.timer}) t->destroy();
+}
+
+hipError_t S2rPostChain::set_eq(const S2rPostCtx &c, uint32_t bus, uint32_t n_bands, const float *coeffs) {
+    if (n_bands == 0) { drop(eq[bus]); return hipSuccess; }
+    BusEq f;
+    f.n_bands = n_bands; f.history = 2u * n_bands;
+    std::memcpy(f.c, coeffs, (size_t)n_bands * 5u * sizeof(float));
+    return replace(c, eq_insert.stage, eq[bus], f, 4u * (size_t)n_bands, nothing_more);
+}
+
+hipError_t S2rPostChain::eq_state(const S2rPostCtx &c, uint32_t bus, float *get, const float *set) {
+    POST_HIP(eq[bus].copy(get, set, 0, eq[bus].floats, c.stream));
+    return hipStreamSynchronize(c.stream);
 }
 
 hipError_t S2rPostChain::set_chorus(const S2rPostCtx &c, uint32_t bus, uint32_t voices, float base, float depth, uint32_t phase_inc, uint32_t spread, float dry,

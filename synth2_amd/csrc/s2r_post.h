@@ -1,7 +1,7 @@
-// s2r_post.h — the chain behind the bus mixdown of s2r_fill_buses and s2r_fill_master: the stem stages (s2r_post_route.h) — the buses'
-// choruses, their feedback delays (4.19), their convolution reverbs (4.16) —, the master section (4.17) and the master
-// limiter (4.18), in that order.  The chain owns what the five stages own and knows nothing of the handle: its functions take a
-// S2rPostCtx and return the HIP error.  Per call: prepare, launch, — the caller's synchronise — commit, read_timers.
+// s2r_post.h — the chain behind the bus mixdown of s2r_fill_buses and s2r_fill_master: the buses' equalisers, an insert
+// at the head of the stem stages (s2r_post_route.h) — the buses' choruses (4.20), their feedback delays (4.19), their convolution
+// reverbs (4.16) —, the master section (4.17) and the master limiter (4.18), in that order.  The chain owns what the six stages own
+// and knows nothing of the handle: its functions take a S2rPostCtx and return the HIP error.  Per call: prepare, launch, — the caller's synchronise — commit, read_timers.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <vector>
@@ -69,6 +69,13 @@ struct S2rPostChain {
         uint32_t tstride = 0, lstride = 0;
         void free() { for (float *p : {taps, partials}) if (p) (void)hipFree(p); S2rBusLine::free(); }
     } fx[S2R_MAX_BUSES];
+    // The EQs (s2r_set_bus_eq): lines of [n_bands][s1_L, s1_R, s2_L, s2_R], 4 * n_bands floats (history = 2 * n_bands "frames" of two).
+    // Not a stem stage: an insert in front of them (s2r_post_route_eq), with a staging buffer and a timer of its own
+    struct BusEq : S2rBusLine {
+        uint32_t n_bands = 0;
+        float c[S2R_EQ_MAX_BANDS][5] = {};       // (b0, b1, b2, a1, a2) per band
+    } eq[S2R_MAX_BUSES];
+    Stem eq_insert;                              // (its timer: tools/eq_time.py)
     // stage k's effect on a bus, as far as the stages are alike
     S2rBusLine &bus(int k, uint32_t b) { S2rBusLine *const of[S2R_STEM_STAGES] = {&chorus[b], &delay[b], &fx[b]}; return *of[k]; }
     const S2rBusLine &bus(int k, uint32_t b) const { return const_cast<S2rPostChain *>(this)->bus(k, b); }
@@ -110,6 +117,8 @@ struct S2rPostChain {
     hipError_t read_timers(const S2rPostCall &call);
     void release();
     // what the entry points of s2r_host.cpp do behind their checks, on a quiet stream
+    hipError_t set_eq(const S2rPostCtx &c, uint32_t bus, uint32_t n_bands, const float *coeffs);
+    hipError_t eq_state(const S2rPostCtx &c, uint32_t bus, float *get, const float *set);      // the 4 * n_bands floats, out or in
     hipError_t set_chorus(const S2rPostCtx &c, uint32_t bus, uint32_t voices, float base, float depth, uint32_t phase_inc, uint32_t spread, float dry, float wet);
     hipError_t set_delay(const S2rPostCtx &c, uint32_t bus, uint32_t delay_frames, float feedback, float cross, float dry, float wet);
     hipError_t set_reverb(const S2rPostCtx &c, uint32_t bus, const float *ir_l, const float *ir_r, uint32_t n_taps, float dry, float wet);

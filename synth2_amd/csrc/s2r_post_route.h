@@ -10,6 +10,7 @@ enum S2rStemStage { S2R_STEM_CHORUS, S2R_STEM_DELAY, S2R_STEM_REVERB, S2R_STEM_S
 struct S2rPostRoute {
     float *combine_out;
     struct { float *in, *out; } stem[S2R_STEM_STAGES];
+    struct { float *in, *out; } eq;              // the EQ insert at the head of the stem chain (s2r_post_route_eq): null unless the call runs it
     float *master_in, *master_out, *master_stems, *limiter_in, *limiter_out;
 };
 struct S2rPostCall {                             // one fill, as prepare leaves it
@@ -17,6 +18,7 @@ struct S2rPostCall {                             // one fill, as prepare leaves 
     bool master = false, stems = false;          // s2r_fill_master; the caller wants the stems too
     bool on[S2R_STEM_STAGES] = {};               // the stage's effect sits on one of the call's buses
     bool limited = false;                        // a master fill with the limiter set
+    bool eq = false;                             // an EQ sits on one of the call's buses
     S2rPostRoute route{};
 };
 
@@ -37,5 +39,17 @@ inline S2rPostRoute s2r_post_route(const S2rPostCall &call, float *const stem_st
     *writer = call.master ? master_stage : bus_out_dev;
     if (call.master) { r.master_in = master_stage; r.master_out = call.limited ? limiter_in : out_host_dev; r.master_stems = call.stems ? bus_out_dev : nullptr; }
     if (call.limited) { r.limiter_in = limiter_in; r.limiter_out = out_host_dev; }
+    return r;
+}
+
+// The EQ is an insert at the head of the stem chain, not a stem stage: given the finished route of a call that runs it and the EQ's
+// staging buffer, the EQ reads its own buffer and writes where the combine would have written, and the combine is redirected into
+// the EQ's buffer.  The buffer is needed in every route: in a bus fill with no stem stage the combine's destination is pinned host
+// memory, which a kernel must not read back, so the EQ cannot run in place there.  A call without an EQ, or without buses, keeps its
+// route as it is.
+inline S2rPostRoute s2r_post_route_eq(const S2rPostCall &call, S2rPostRoute r, float *eq_stage) {
+    if (!call.eq || !call.n_buses) return r;
+    r.eq.in = eq_stage; r.eq.out = r.combine_out;
+    r.combine_out = eq_stage;
     return r;
 }

@@ -97,6 +97,62 @@ int s2r_chorus_reference(uint32_t voices, float base, float depth, uint32_t phas
     return S2R_OK;
 }
 
+// ---- per-bus parametric EQ: a cascade of biquads in transposed direct form II, both channels the same coefficients ----
+int s2r_eq_reference(uint32_t n_bands, const float *coeffs, const float *x_lr, uint32_t frames, float *state, float *out_lr) {
+    if (n_bands < 1u || !eq_in_range(n_bands, coeffs)) return S2R_ERR_PATCH_RANGE;
+    if (!coeffs || !state || (!x_lr && frames)) return S2R_ERR_INVALID;
+    for (uint32_t n = 0; n < frames; n++)
+        for (uint32_t c = 0; c < 2; c++) {
+            float x = x_lr[2 * (size_t)n + c];
+            for (uint32_t k = 0; k < n_bands; k++) {
+                const float *q = coeffs + 5 * k;
+                float &s1 = state[4 * k + c], &s2 = state[4 * k + 2 + c];
+                const float p0 = q[0] * x;
+                const float y = p0 + s1;
+                const float p1 = q[1] * x, r1 = q[3] * y;
+                const float d1 = p1 - r1;
+                const float p2 = q[2] * x, r2 = q[4] * y;
+                s1 = d1 + s2;
+                s2 = p2 - r2;
+                x = y;
+            }
+            if (out_lr) out_lr[2 * (size_t)n + c] = x;
+        }
+    return S2R_OK;
+}
+
+// the Audio-EQ-Cookbook's bands with q as Q: binary64 throughout, divided by a0, rounded once to binary32
+int s2r_eq_design(int kind, double freq_hz, double gain_db, double q, double sample_rate, float coeffs[5]) {
+    if (std::isnan(freq_hz) || std::isnan(gain_db) || std::isnan(q) || std::isnan(sample_rate)) return S2R_ERR_PATCH_RANGE;
+    if (kind < S2R_EQ_PEAK || kind > S2R_EQ_HIGHPASS || !(freq_hz > 0.0) || !(freq_hz < sample_rate / 2.0) || !(q > 0.0) || !(std::fabs(gain_db) <= 48.0))
+        return S2R_ERR_PATCH_RANGE;
+    if (!coeffs) return S2R_ERR_INVALID;
+    const double w0 = 2.0 * 3.141592653589793 * freq_hz / sample_rate;
+    const double cw = std::cos(w0), alpha = std::sin(w0) / (2.0 * q);
+    const double A = std::pow(10.0, gain_db / 40.0);
+    double b0, b1, b2, a0, a1, a2;
+    if (kind == S2R_EQ_PEAK) {
+        b0 = 1.0 + alpha * A; b1 = -2.0 * cw; b2 = 1.0 - alpha * A;
+        a0 = 1.0 + alpha / A; a1 = -2.0 * cw; a2 = 1.0 - alpha / A;
+    } else if (kind == S2R_EQ_LOW_SHELF) {
+        const double t = 2.0 * std::sqrt(A) * alpha;
+        b0 = A * ((A + 1.0) - (A - 1.0) * cw + t); b1 = 2.0 * A * ((A - 1.0) - (A + 1.0) * cw); b2 = A * ((A + 1.0) - (A - 1.0) * cw - t);
+        a0 = (A + 1.0) + (A - 1.0) * cw + t; a1 = -2.0 * ((A - 1.0) + (A + 1.0) * cw); a2 = (A + 1.0) + (A - 1.0) * cw - t;
+    } else if (kind == S2R_EQ_HIGH_SHELF) {
+        const double t = 2.0 * std::sqrt(A) * alpha;
+        b0 = A * ((A + 1.0) + (A - 1.0) * cw + t); b1 = -2.0 * A * ((A - 1.0) + (A + 1.0) * cw); b2 = A * ((A + 1.0) + (A - 1.0) * cw - t);
+        a0 = (A + 1.0) - (A - 1.0) * cw + t; a1 = 2.0 * ((A - 1.0) - (A + 1.0) * cw); a2 = (A + 1.0) - (A - 1.0) * cw - t;
+    } else {
+        const double e = kind == S2R_EQ_LOWPASS ? 1.0 - cw : 1.0 + cw;
+        b0 = e / 2.0; b1 = kind == S2R_EQ_LOWPASS ? e : -e; b2 = e / 2.0;
+        a0 = 1.0 + alpha; a1 = -2.0 * cw; a2 = 1.0 - alpha;
+    }
+    const float out[5] = {(float)(b0 / a0), (float)(b1 / a0), (float)(b2 / a0), (float)(a1 / a0), (float)(a2 / a0)};
+    if (!eq_band_in_range(out)) return S2R_ERR_PATCH_RANGE;
+    std::memcpy(coeffs, out, sizeof out);
+    return S2R_OK;
+}
+
 // ---- the master section: energies by the adjacent-pair tree over blocks of S2R_METER_BLOCK frames ----
 static float master_energy(const float *v, uint32_t frames) {     // v: one channel of an interleaved pair (stride 2)
     float total = 0.0f;

@@ -33,6 +33,18 @@ static inline bool chorus_in_range(uint32_t voices, float base, float depth, flo
 static inline uint32_t chorus_history(float base, float depth) { volatile float top = base + depth; return (uint32_t)top + 1u; }
 // voice v's offset on the left channel: floor(v * 2^32 / V)
 static inline uint32_t chorus_voice_offset(uint32_t v, uint32_t voices) { return (uint32_t)(((uint64_t)v << 32) / voices); }
+// an EQ's bands, [n_bands][5] as (b0, b1, b2, a1, a2): every coefficient finite and every band inside the stability
+// triangle, |a2| < 1 and |a1| < 1 + a2, in double from the floats
+static inline bool eq_band_in_range(const float *c) {
+    for (int i = 0; i < 5; i++) if (!std::isfinite(c[i])) return false;
+    const double a1 = (double)c[3], a2 = (double)c[4];
+    return std::fabs(a2) < 1.0 && std::fabs(a1) < 1.0 + a2;
+}
+static inline bool eq_in_range(uint32_t n_bands, const float *coeffs) {
+    if (n_bands > S2R_EQ_MAX_BANDS) return false;
+    for (uint32_t k = 0; k < n_bands && coeffs; k++) if (!eq_band_in_range(coeffs + 5 * k)) return false;
+    return true;
+}
 
 // The voice mixer's gain rules, inline: the host's per-voice loops compile them in — a call per voice into s2r_rules.cpp showed as 10
 // to 15 us of host time per fill of 65 536 voices (profiles/r12/post_chain.txt).  s2r_rules.cpp exports them under their s2r.h names.

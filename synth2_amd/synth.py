@@ -38,6 +38,8 @@ MAX_IR_TAPS = 65536                         # S2R_MAX_IR_TAPS
 MAX_DELAY_FRAMES = 262144                   # S2R_MAX_DELAY_FRAMES
 CHORUS_MAX_VOICES = 8                       # S2R_CHORUS_MAX_VOICES
 CHORUS_MAX_DELAY = 4095.0                   # S2R_CHORUS_MAX_DELAY
+EQ_MAX_BANDS = 4                            # S2R_EQ_MAX_BANDS
+EQ_PEAK, EQ_LOW_SHELF, EQ_HIGH_SHELF, EQ_LOWPASS, EQ_HIGHPASS = range(5)     # s2r_eq_kind
 IR_SEGMENT = 256                            # S2R_IR_SEGMENT
 METER_BLOCK = 256                           # S2R_METER_BLOCK
 LIMITER_MAX_LOOKAHEAD = 1024                # S2R_LIMITER_MAX_LOOKAHEAD
@@ -217,6 +219,13 @@ def load_library():
         "s2r_set_bus_chorus_state": (C.c_int, [H, C.c_uint32, _f32p, C.c_size_t, C.c_uint32]),
         "s2r_chorus_reference": (C.c_int, [C.c_uint32, C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.c_float, C.c_float, _f32p, C.c_uint32, _f32p,
                                            C.POINTER(C.c_uint32), _f32p]),
+        "s2r_set_bus_eq": (C.c_int, [H, C.c_uint32, C.c_uint32, _f32p]),
+        "s2r_set_bus_eq_coeffs": (C.c_int, [H, C.c_uint32, C.c_uint32, _f32p]),
+        "s2r_get_bus_eq": (C.c_int, [H, C.c_uint32, C.POINTER(C.c_uint32), _f32p, C.c_size_t]),
+        "s2r_get_bus_eq_state": (C.c_int, [H, C.c_uint32, _f32p, C.c_size_t]),
+        "s2r_set_bus_eq_state": (C.c_int, [H, C.c_uint32, _f32p, C.c_size_t]),
+        "s2r_eq_reference": (C.c_int, [C.c_uint32, _f32p, _f32p, C.c_uint32, _f32p, _f32p]),
+        "s2r_eq_design": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, _f32p]),
         "s2r_set_bus_return": (C.c_int, [H, C.c_uint32, C.c_float]),
         "s2r_get_bus_return": (C.c_int, [H, C.c_uint32, _f32p, _f32p]),
         "s2r_set_master_fader": (C.c_int, [H, C.c_float]),
@@ -395,6 +404,42 @@ def chorus_reference(voices, base, depth, phase_inc, spread, dry, wet, x, histor
     if rc != S2R_OK:
         raise S2rError(rc, load_library().s2r_status_string(rc).decode())
     return out, h, ph.value
+
+
+def _eq_coeffs(coeffs, who):
+    c = np.ascontiguousarray(coeffs, dtype=np.float32)
+    if c.ndim == 1 and c.size == 5:
+        c = c.reshape(1, 5)
+    if c.ndim != 2 or c.shape[1] != 5 or c.shape[0] < 1:
+        raise ValueError(who + ": coeffs is [n_bands, 5]: (b0, b1, b2, a1, a2) per band")
+    return c
+
+
+def eq_reference(coeffs, x, state):
+    """the bus EQ's rule for both channels on the host (s2r_eq_reference): coeffs [n_bands, 5] float32 as (b0, b1, b2, a1, a2), x
+    [frames, 2] float32 the bus's signal, state [n_bands, 4] as (s1_L, s1_R, s2_L, s2_R) per band; returns (out [frames, 2], the state
+    after the call [n_bands, 4]).  `state` itself is left as it is."""
+    c = _eq_coeffs(coeffs, "eq_reference")
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    st = np.array(state, dtype=np.float32, order="C")
+    if x.ndim != 2 or x.shape[1] != 2 or st.shape != (c.shape[0], 4):
+        raise ValueError("eq_reference: x is [frames, 2] and state is [n_bands, 4]")
+    out = np.empty_like(x)
+    rc = load_library().s2r_eq_reference(c.shape[0], c.ctypes.data_as(_f32p), x.ctypes.data_as(_f32p), x.shape[0], st.ctypes.data_as(_f32p),
+                                         out.ctypes.data_as(_f32p))
+    if rc != S2R_OK:
+        raise S2rError(rc, load_library().s2r_status_string(rc).decode())
+    return out, st
+
+
+def eq_design(kind, freq_hz, gain_db, q, sample_rate):
+    """a band (b0, b1, b2, a1, a2), float32 [5], from the usual parameters by the Audio-EQ-Cookbook formulas with q as Q
+    (s2r_eq_design): kind one of EQ_PEAK, EQ_LOW_SHELF, EQ_HIGH_SHELF, EQ_LOWPASS, EQ_HIGHPASS; gain_db is the peak's and the shelves'"""
+    out = np.empty(5, dtype=np.float32)
+    rc = load_library().s2r_eq_design(int(kind), float(freq_hz), float(gain_db), float(q), float(sample_rate), out.ctypes.data_as(_f32p))
+    if rc != S2R_OK:
+        raise S2rError(rc, load_library().s2r_status_string(rc).decode())
+    return out
 
 
 def master_reference(stems, r0, r1, m0, m1):
@@ -870,6 +915,51 @@ class Synth:
     @staticmethod
     def chorus_rate(hz, sample_rate):
         return chorus_rate(hz, sample_rate)
+
+    # --- per-bus parametric EQ (build-defined; s2r.h: s2r_set_bus_eq) ---
+    def set_bus_eq(self, bus, coeffs):
+        """an EQ of 1 .. EQ_MAX_BANDS biquad bands on a bus of sample_buses and sample_master, at the head of the chain: coeffs
+        [n_bands, 5] as (b0, b1, b2, a1, a2) per band (eq_design makes one), normalised by a0, finite, |a2| < 1 and |a1| < 1 + a2.
+        Replaces any earlier EQ of the bus and zeroes its state."""
+        c = _eq_coeffs(coeffs, "set_bus_eq")
+        self._check(self.L.s2r_set_bus_eq(self.h, int(bus), c.shape[0], c.ctypes.data_as(_f32p)))
+
+    def clear_bus_eq(self, bus):
+        """removes the bus's EQ: the bus returns the combine's signal again, bit for bit"""
+        self._check(self.L.s2r_set_bus_eq(self.h, int(bus), 0, None))
+
+    def set_bus_eq_coeffs(self, bus, coeffs):
+        """the coefficients of the bus's EQ alone, as many bands as it has; its state stays, so a band moves without a restart"""
+        c = _eq_coeffs(coeffs, "set_bus_eq_coeffs")
+        self._check(self.L.s2r_set_bus_eq_coeffs(self.h, int(bus), c.shape[0], c.ctypes.data_as(_f32p)))
+
+    def get_bus_eq(self, bus):
+        """the coefficients [n_bands, 5] float32 of the bus's EQ; [0, 5] for a bus without one"""
+        n = C.c_uint32()
+        out = np.empty((EQ_MAX_BANDS, 5), dtype=np.float32)
+        self._check(self.L.s2r_get_bus_eq(self.h, int(bus), C.byref(n), out.ctypes.data_as(_f32p), out.size))
+        return out[:n.value].copy()
+
+    def bus_eq_state(self, bus):
+        """what the bus's EQ carries into the next call: [n_bands, 4] float32 as (s1_L, s1_R, s2_L, s2_R) per band — the checkpoint
+        companion of bus_chorus_state"""
+        out = np.empty((self.get_bus_eq(bus).shape[0], 4), dtype=np.float32)
+        self._check(self.L.s2r_get_bus_eq_state(self.h, int(bus), out.ctypes.data_as(_f32p), out.size))
+        return out
+
+    def set_bus_eq_state(self, bus, state):
+        st = np.ascontiguousarray(state, dtype=np.float32)
+        if st.ndim != 2 or st.shape[1] != 4:
+            raise ValueError("set_bus_eq_state: state is [n_bands, 4]")
+        self._check(self.L.s2r_set_bus_eq_state(self.h, int(bus), st.ctypes.data_as(_f32p), st.size))
+
+    @staticmethod
+    def eq_reference(coeffs, x, state):
+        return eq_reference(coeffs, x, state)
+
+    @staticmethod
+    def eq_design(kind, freq_hz, gain_db, q, sample_rate):
+        return eq_design(kind, freq_hz, gain_db, q, sample_rate)
 
     # --- the master section (build-defined; s2r.h: s2r_fill_master) ---
     def set_bus_return(self, bus, level=1.0):
