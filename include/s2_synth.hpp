@@ -190,6 +190,28 @@ class Synth {
     static int eq_design(int kind, double freq_hz, double gain_db, double q, double sample_rate, float coeffs[5]) {
         return s2r_eq_design(kind, freq_hz, gain_db, q, sample_rate, coeffs);
     }
+    // per-bus dynamics behind the bus's EQ (build-defined; s2r.h: s2r_set_bus_dynamics): a sidechain compressor keyed by key_bus (the bus
+    // itself: a compressor; another: a ducker), curve [S2R_DYN_CURVE_POINTS] gains in [0, 256] (dynamics_curve makes one), a_att and
+    // a_rel in [0, 1) (dynamics_coef); in sample_buses and sample_master only
+    void set_bus_dynamics(uint32_t bus, uint32_t key_bus, const float *curve, float a_att, float a_rel) { check(s2r_set_bus_dynamics(h_, bus, key_bus, curve, a_att, a_rel)); }
+    void clear_bus_dynamics(uint32_t bus) { check(s2r_clear_bus_dynamics(h_, bus)); }
+    void set_bus_dynamics_params(uint32_t bus, uint32_t key_bus, const float *curve, float a_att, float a_rel) { check(s2r_set_bus_dynamics_params(h_, bus, key_bus, curve, a_att, a_rel)); }   // the gain stays
+    bool get_bus_dynamics(uint32_t bus, uint32_t *key_bus, float *curve, size_t capacity, float *a_att, float *a_rel) const {
+        uint32_t present = 0;
+        check(s2r_get_bus_dynamics(h_, bus, &present, key_bus, curve, capacity, a_att, a_rel));
+        return present != 0;
+    }
+    float bus_dynamics_state(uint32_t bus) { float y = 0.0f; check(s2r_get_bus_dynamics_state(h_, bus, &y, 1)); return y; }
+    void set_bus_dynamics_state(uint32_t bus, float y) { check(s2r_set_bus_dynamics_state(h_, bus, &y, 1)); }
+    float bus_dynamics_meter(uint32_t bus) const { float m = 1.0f; check(s2r_get_bus_dynamics_meter(h_, bus, &m)); return m; }
+    static int dynamics_reference(const float *curve, float a_att, float a_rel, const float *key_lr, const float *x_lr, uint32_t frames, float *y, float *out_lr,
+                                  float *min_gain) {
+        return s2r_dynamics_reference(curve, a_att, a_rel, key_lr, x_lr, frames, y, out_lr, min_gain);
+    }
+    static int dynamics_curve(double threshold_db, double ratio, double knee_db, double makeup_db, float *curve) {
+        return s2r_dynamics_curve(threshold_db, ratio, knee_db, makeup_db, curve);
+    }
+    static float dynamics_coef(double ms, double sample_rate) { return s2r_dynamics_coef(ms, sample_rate); }
 
     // the master section (build-defined; s2r.h: s2r_fill_master): a return level per bus and a master fader, each in [0, 1] and each
     // reaching its target as a ramp across the next sample_master call, and the meters of that call — in sample_master only

@@ -43,7 +43,9 @@ extern "C" {
  * s2r_get_bus_delay, s2r_get_bus_delay_history, s2r_set_bus_delay_history, s2r_delay_reference, s2r_chorus_history_frames,
  * s2r_set_bus_chorus, s2r_set_bus_chorus_mix, s2r_set_bus_chorus_rate, s2r_get_bus_chorus, s2r_get_bus_chorus_state,
  * s2r_set_bus_chorus_state, s2r_chorus_reference, s2r_set_bus_eq, s2r_set_bus_eq_coeffs, s2r_get_bus_eq, s2r_get_bus_eq_state,
- * s2r_set_bus_eq_state, s2r_eq_reference, s2r_eq_design. */
+ * s2r_set_bus_eq_state, s2r_eq_reference, s2r_eq_design, s2r_set_bus_dynamics, s2r_clear_bus_dynamics, s2r_set_bus_dynamics_params,
+ * s2r_get_bus_dynamics, s2r_get_bus_dynamics_state, s2r_set_bus_dynamics_state, s2r_get_bus_dynamics_meter, s2r_dynamics_reference,
+ * s2r_dynamics_curve, s2r_dynamics_coef. */
 #define S2R_ABI_VERSION 4
 
 typedef enum {
@@ -544,6 +546,64 @@ int s2r_get_bus_eq_state(s2r_synth *s, uint32_t bus, float *state, size_t capaci
 int s2r_set_bus_eq_state(s2r_synth *s, uint32_t bus, const float *state, size_t count);
 int s2r_eq_reference(uint32_t n_bands, const float *coeffs, const float *x_lr, uint32_t frames, float *state, float *out_lr);
 int s2r_eq_design(int kind, double freq_hz, double gain_db, double q, double sample_rate, float coeffs[5]);
+
+/* BUILD-DEFINED per-bus dynamics (the reference has no effects): a sidechain compressor behind the bus's EQ, computed on
+ * the device: combine -> eq -> dynamics -> chorus -> delay -> reverb -> master -> limiter.  A bus b in [0, S2R_MAX_BUSES) may carry
+ * dynamics: a key bus k in [0, S2R_MAX_BUSES) (k == b: the ordinary compressor; k != b: a ducker, an external sidechain), a transfer
+ * curve of S2R_DYN_CURVE_POINTS gains — 32 octaves of level from 2^-24 to 2^8, 16 linear segments each, and the end point: breakpoint
+ * j sits at the level 2^(-24 + j / 16) * (1 + (j mod 16) / 16), integer division — and two retention coefficients a_att and a_rel in
+ * [0, 1).  The state is one gain y per bus, both channels linked: curve[0], the gain at silence, right after a set.  With x_b the
+ * bus's and x_k the key bus's signal, both as they ENTER the dynamics stage (behind the EQs, in front of every bus's dynamics,
+ * whatever the key bus itself carries), for frame n:
+ *   p = max(|x_kL[n]|, |x_kR[n]|)
+ *   t = curve[0] if p < 2^-24; curve[512] if p >= 2^8; otherwise, with u the bits of p and lo the bits of 2^-24,
+ *       i = (u - lo) >> 19, f = (float)((u - lo) & 0x7ffff) * 2^-19 (both exact), t = fl(curve[i] + fl(f * fl(curve[i + 1] - curve[i])))
+ *   a = (t < y) ? a_att : a_rel;   y = fl(t + fl(a * fl(y - t)))
+ *   out_c[n] = fl(x_bc[n] * y) for both channels
+ * binary32 throughout, every operation rounded on its own (no fma), denormals kept, nothing skipped for a zero.  No transcendental
+ * function: the curve holds gains, makeup included.  With a == 0 the new y is t exactly.  From a finite y >= 0 the rule keeps y >= 0
+ * (every curve entry is >= 0 and a < 1).  The meter of a call is min over n of y[n], the gain reduction a compressor shows.
+ * Non-finite bus samples are outside the contract.  After a call that returns S2R_OK the state is what the last frame left: calls
+ * of any lengths concatenate.  The stage runs once per call over all N frames, after every event segment and rows slice has been
+ * mixed.  Dynamics whose bus OR key bus is >= the call's n_buses are idle in that call: the bus passes, the state stays.  A bus
+ * without dynamics passes bit for bit, -0.0 included.  A refused or failed call leaves the state untouched.  ONLY s2r_fill_buses
+ * and s2r_fill_master apply dynamics; s2r_set_patch_bank, program changes and s2r_import_state leave them alone.  A handle on which
+ * none were ever set launches what it launched before and allocates nothing for them; device memory is allocated when dynamics are
+ * set (S2R_ERR_OUT_OF_MEMORY when that fails, and the earlier dynamics are kept), never inside a fill.
+ *   s2r_set_bus_dynamics: replaces any earlier dynamics of the bus and resets y to curve[0].  S2R_ERR_PATCH_RANGE for a bus or a key
+ *   >= S2R_MAX_BUSES, a curve entry that is not finite or outside [0, 2^8], a coefficient outside [0, 1) or a NaN (checked before
+ *   the handle is looked at; nothing is changed); S2R_ERR_INVALID for a NULL curve.
+ *   s2r_clear_bus_dynamics removes them (S2R_OK on a bus without).
+ *   s2r_set_bus_dynamics_params: the same arguments, y stays: a threshold moves between calls without a restart.  S2R_ERR_INVALID
+ *   on a bus without dynamics.
+ *   s2r_get_bus_dynamics: *present is 0 for a bus without; curve receives S2R_DYN_CURVE_POINTS floats when it is not NULL
+ *   (S2R_ERR_INVALID for a capacity below that); any pointer may be NULL.
+ *   s2r_get_bus_dynamics_state / s2r_set_bus_dynamics_state: the one float y.  S2R_ERR_INVALID for a capacity below, or a count
+ *   other than, 1, a NULL buffer, and on a bus without dynamics; S2R_ERR_PATCH_RANGE for a y to restore that is not finite or < 0.
+ *   s2r_get_bus_dynamics_meter: the minimum of y over the last successful call in which the bus's dynamics ran; 1.0 before any.
+ *   Single-device handles (a NULL or a device-list handle: S2R_ERR_INVALID from all seven).
+ *   s2r_dynamics_reference: the rule on the host (no device, no handle): key_lr and x_lr are [frames][2]; a NULL key_lr keys the
+ *   bus by itself; *y is updated in place; out_lr, [frames][2], and min_gain may be NULL; *min_gain is written when frames > 0.
+ *   Range checks as above, and of *y as the state setter's; S2R_ERR_INVALID for a NULL curve or y, or a NULL x_lr with frames > 0.
+ *   s2r_dynamics_curve: the table of a soft-knee compressor, in binary64: at each breakpoint level l_j, with L = 20 log10(l_j),
+ *   o = L - threshold_db and W = knee_db: G = 0 when 2 o < -W; G = (1 / ratio - 1) (o + W / 2)^2 / (2 W) when W > 0 and 2 |o| <= W;
+ *   G = (1 / ratio - 1) o otherwise; the entry is 10^((G + makeup_db) / 20) rounded once to binary32.  ratio in [1, inf], inf the
+ *   limiter's curve.  S2R_ERR_PATCH_RANGE for a NaN, ratio < 1, knee_db < 0 or an entry the setter would refuse; S2R_ERR_INVALID
+ *   for a NULL curve.  Expanders and gates are curves the caller supplies.
+ *   s2r_dynamics_coef: (float)exp(-1 / (ms * 0.001 * sample_rate)), 0 for ms == 0; a NaN for ms < 0, sample_rate <= 0 or a NaN.
+ *   Device parity is always against the stored table and coefficients, never against the two design functions. */
+#define S2R_DYN_CURVE_POINTS 513u
+int s2r_set_bus_dynamics(s2r_synth *s, uint32_t bus, uint32_t key_bus, const float *curve, float a_att, float a_rel);
+int s2r_clear_bus_dynamics(s2r_synth *s, uint32_t bus);
+int s2r_set_bus_dynamics_params(s2r_synth *s, uint32_t bus, uint32_t key_bus, const float *curve, float a_att, float a_rel);
+int s2r_get_bus_dynamics(const s2r_synth *s, uint32_t bus, uint32_t *present, uint32_t *key_bus, float *curve, size_t capacity, float *a_att, float *a_rel);
+int s2r_get_bus_dynamics_state(s2r_synth *s, uint32_t bus, float *state, size_t capacity);
+int s2r_set_bus_dynamics_state(s2r_synth *s, uint32_t bus, const float *state, size_t count);
+int s2r_get_bus_dynamics_meter(const s2r_synth *s, uint32_t bus, float *min_gain);
+int s2r_dynamics_reference(const float *curve, float a_att, float a_rel, const float *key_lr, const float *x_lr, uint32_t frames, float *y, float *out_lr,
+                           float *min_gain);
+int s2r_dynamics_curve(double threshold_db, double ratio, double knee_db, double makeup_db, float *curve);
+float s2r_dynamics_coef(double ms, double sample_rate);
 
 /* BUILD-DEFINED master section (the reference's Synth::sample returns one stream; DESIGN.md 4.17 gives the op sequence): the last stage
  * of the chain send -> effect -> return -> master, on the device the bus signals are already on.  Every bus b in [0, S2R_MAX_BUSES) has

@@ -495,6 +495,27 @@ struct S2rEq {
 // line == next, more than S2R_EQ_MAX_BANDS bands, n_buses past S2R_MAX_BUSES or no EQ at all among the call's buses
 hipError_t s2r_launch_bus_eq(const S2rEq &a, hipStream_t stream);
 
+// The per-bus dynamics behind the EQ: a sidechain compressor.  A bus's line holds its one gain y; `next` receives
+// the gain the next call starts from (the host swaps the two).
+#define S2R_DYN_TILE 256u         // frames of one stage of the kernel's pipeline: targets a tile ahead of the walk, outputs a tile behind
+struct S2rDynBus {
+    const float *line;            // [1]: y
+    float *next;                  // [1], not `line`
+    const float *curve;           // [S2R_DYN_CURVE_POINTS] in device memory; null: no dynamics on this bus, or idle: it is copied from `in` to `out`
+    uint32_t key;                 // the key bus, among the call's buses
+    float a_att, a_rel;
+};
+struct S2rDyn {
+    S2rDynBus bus[S2R_MAX_BUSES];
+    const float *in;              // [n_buses][2 * frames]: what the EQ, or else the bus combine, wrote; bus-major, L, R interleaved inside a bus
+    float *out;                   // the same layout, not `in`: what the next stage, or the caller, reads
+    float *meter;                 // [S2R_MAX_BUSES], pinned and device-mapped: the call's minimum of y per bus that ran
+    uint32_t n_buses, frames;
+};
+// one kernel: the outputs, next gains and meters of the buses with dynamics, the other buses unchanged; hipErrorInvalidValue for a null
+// pointer, in == out, line == next, a key or n_buses past its range or no dynamics at all among the call's buses
+hipError_t s2r_launch_bus_dyn(const S2rDyn &a, hipStream_t stream);
+
 // The master section of s2r_fill_master: the stems of a call, post-effect, each times its return's ramp, added in
 // bus order from +0.0, times the master fader's ramp; and the call's meters.  gain at frame i of the CALL: r0 + (float)i * dr (the
 // product rounded, then the sum); a pair that did not move has dr = +0.0.

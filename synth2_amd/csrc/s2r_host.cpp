@@ -2874,6 +2874,79 @@ int s2r_set_bus_eq_state(s2r_synth *s, uint32_t bus, const float *state, size_t 
     return eq_state(s, bus, nullptr, state, state ? count : (size_t)-1, "s2r_set_bus_eq_state");
 }
 
+// ---- per-bus dynamics: the second insert, behind the equalisers and in front of the choruses ----
+static int dyn_values(s2r_synth *s, const char *who, uint32_t bus, uint32_t key_bus, const float *curve, float a_att, float a_rel) {
+    if (bus >= S2R_MAX_BUSES || key_bus >= S2R_MAX_BUSES || !dyn_in_range(curve, a_att, a_rel))
+        return set_err(s, S2R_ERR_PATCH_RANGE, "%s: bus %u, key bus %u, attack %g, release %g: %u finite curve entries in [0, 256], both coefficients in "
+                       "[0, 1), both buses below %u", who, bus, key_bus, (double)a_att, (double)a_rel, S2R_DYN_CURVE_POINTS, S2R_MAX_BUSES);
+    return S2R_OK;
+}
+
+// the bus in range, a single-device handle, and the bus carries dynamics
+static int dyn_bus(s2r_synth *s, uint32_t bus, const char *who) {
+    if (bus >= S2R_MAX_BUSES) return set_err(s, S2R_ERR_PATCH_RANGE, "%s: bus %u, below %u", who, bus, S2R_MAX_BUSES);
+    S2R_TRY(post_handle(s, who, "bus dynamics are"));
+    if (!s->post.dyn[bus].present()) return set_err(s, S2R_ERR_INVALID, "%s: bus %u carries no dynamics", who, bus);
+    return S2R_OK;
+}
+
+int s2r_set_bus_dynamics(s2r_synth *s, uint32_t bus, uint32_t key_bus, const float *curve, float a_att, float a_rel) {
+    S2R_TRY(dyn_values(s, "s2r_set_bus_dynamics", bus, key_bus, curve, a_att, a_rel));
+    S2R_TRY(post_handle(s, "s2r_set_bus_dynamics", "bus dynamics are"));
+    if (!curve) return set_err(s, S2R_ERR_INVALID, "s2r_set_bus_dynamics: no curve");
+    return stem_set(s, "s2r_set_bus_dynamics", [&](const S2rPostCtx &c) { return s->post.set_dyn(c, bus, key_bus, curve, a_att, a_rel, false); });
+}
+
+int s2r_clear_bus_dynamics(s2r_synth *s, uint32_t bus) {
+    if (bus >= S2R_MAX_BUSES) return set_err(s, S2R_ERR_PATCH_RANGE, "s2r_clear_bus_dynamics: bus %u, below %u", bus, S2R_MAX_BUSES);
+    S2R_TRY(post_handle(s, "s2r_clear_bus_dynamics", "bus dynamics are"));
+    return stem_set(s, "s2r_clear_bus_dynamics", [&](const S2rPostCtx &c) { return s->post.set_dyn(c, bus, 0, nullptr, 0.0f, 0.0f, false); });
+}
+
+int s2r_set_bus_dynamics_params(s2r_synth *s, uint32_t bus, uint32_t key_bus, const float *curve, float a_att, float a_rel) {
+    S2R_TRY(dyn_values(s, "s2r_set_bus_dynamics_params", bus, key_bus, curve, a_att, a_rel));
+    S2R_TRY(dyn_bus(s, bus, "s2r_set_bus_dynamics_params"));
+    if (!curve) return set_err(s, S2R_ERR_INVALID, "s2r_set_bus_dynamics_params: no curve");
+    return stem_set(s, "s2r_set_bus_dynamics_params", [&](const S2rPostCtx &c) { return s->post.set_dyn(c, bus, key_bus, curve, a_att, a_rel, true); });   // (y stays)
+}
+
+int s2r_get_bus_dynamics(const s2r_synth *s, uint32_t bus, uint32_t *present, uint32_t *key_bus, float *curve, size_t capacity, float *a_att, float *a_rel) {
+    if (bus >= S2R_MAX_BUSES) return S2R_ERR_PATCH_RANGE;
+    if (!s || !s->kids.empty() || s->parent) return S2R_ERR_INVALID;
+    const S2rPostChain::BusDyn &d = s->post.dyn[bus];
+    if (d.present() && curve && capacity < S2R_DYN_CURVE_POINTS) return S2R_ERR_INVALID;
+    put(present, d.present() ? 1u : 0u); put(key_bus, d.key); put(a_att, d.a_att); put(a_rel, d.a_rel);
+    if (d.present() && curve) std::memcpy(curve, d.curve.data(), S2R_DYN_CURVE_POINTS * sizeof(float));
+    return S2R_OK;
+}
+
+static int dyn_state(s2r_synth *s, uint32_t bus, float *get, const float *set, size_t count, const char *who) {
+    if (set && count == 1u && !dyn_state_in_range(set[0])) return set_err(s, S2R_ERR_PATCH_RANGE, "%s: a gain of %g: finite and not below 0", who, (double)set[0]);
+    S2R_TRY(dyn_bus(s, bus, who));
+    if (set ? count != 1u : count < 1u) return set_err(s, S2R_ERR_INVALID, "%s: the state of bus %u is 1 float, not %zu", who, bus, count);
+    if (!get && !set) return set_err(s, S2R_ERR_INVALID, "%s: null buffer", who);
+    S2R_QUIESCE(s);
+    S2R_HIP(s, hipSetDevice(s->device));
+    S2R_HIP(s, hipStreamSynchronize(s->stream));
+    S2R_HIP(s, s->post.dyn_state(post_ctx(s), bus, get, set));
+    return S2R_OK;
+}
+
+int s2r_get_bus_dynamics_state(s2r_synth *s, uint32_t bus, float *state, size_t capacity) {
+    return dyn_state(s, bus, state, nullptr, capacity, "s2r_get_bus_dynamics_state");
+}
+
+int s2r_set_bus_dynamics_state(s2r_synth *s, uint32_t bus, const float *state, size_t count) {
+    return dyn_state(s, bus, nullptr, state, state ? count : (size_t)-1, "s2r_set_bus_dynamics_state");
+}
+
+int s2r_get_bus_dynamics_meter(const s2r_synth *s, uint32_t bus, float *min_gain) {
+    if (bus >= S2R_MAX_BUSES) return S2R_ERR_PATCH_RANGE;
+    if (!s || !s->kids.empty() || s->parent) return S2R_ERR_INVALID;
+    put(min_gain, s->post.dyn[bus].min_gain);
+    return S2R_OK;
+}
+
 // ---- per-bus choruses: in front of the delays ----
 int s2r_set_bus_chorus(s2r_synth *s, uint32_t bus, uint32_t voices, float base, float depth, uint32_t phase_inc, uint32_t spread, float dry, float wet) {
     if ((voices && !chorus_in_range(voices, base, depth, dry, wet)) || bus >= S2R_MAX_BUSES)
@@ -3566,6 +3639,11 @@ extern "C" float s2r_debug_bus_mix_ms(const s2r_synth *s) { return s && s->timin
 extern "C" float s2r_debug_bus_eq_ms(const s2r_synth *s) { return s && s->timing ? s->post.eq_insert.timer.ms : -1.0f; }
 extern "C" int s2r_debug_bus_eq_allocated(const s2r_synth *s) { return s && s->post.eq_insert.stage ? 1 : 0; }
 extern "C" uint32_t s2r_debug_eq_tile(void) { return S2R_EQ_TILE; }
+// ... of the buses' dynamics kernel in that fill: 0 when it ran none (tools/dyn_time.py); whether the handle holds the dynamics' staging
+// buffer; and the frames of one stage of the kernel's pipeline (tests/test_gpu_dyn.py picks its call lengths around it)
+extern "C" float s2r_debug_dyn_ms(const s2r_synth *s) { return s && s->timing ? s->post.dyn_insert.timer.ms : -1.0f; }
+extern "C" int s2r_debug_dyn_allocated(const s2r_synth *s) { return s && (s->post.dyn_insert.stage || s->post.dyn_curves || s->post.dyn_meter) ? 1 : 0; }
+extern "C" uint32_t s2r_debug_dyn_tile(void) { return S2R_DYN_TILE; }
 // ... of the buses' chorus kernel in that fill: 0 when it ran none (tools/chorus_time.py)
 extern "C" float s2r_debug_bus_chorus_ms(const s2r_synth *s) { return s && s->timing ? s->post.stem[S2R_STEM_CHORUS].timer.ms : -1.0f; }
 // ... of the buses' delay kernel in that fill: 0 when it ran none (tools/delay_time.py)

@@ -1,4 +1,4 @@
-// s2r_post.cpp — the post-mix chain (s2r_post.h): the EQs, the stem stages (choruses, delays, reverbs), master section, master limiter.  Compiled with hipcc, -ffp-contract=off.
+// s2r_post.cpp — the post-mix chain (s2r_post.h): the EQs, the dynamics, the stem stages (choruses, delays, reverbs), master section, master limiter.  Compiled with hipcc, -ffp-contract=off.
 #include "s2r_post.h"
 #include "s2r_rules.h"
 
@@ -68,6 +68,7 @@ hipError_t S2rPostChain::prepare(const S2rPostCtx &c, uint32_t n_buses, uint32_t
     for (int k = 0; k < S2R_STEM_STAGES; k++)
         for (uint32_t b = 0; b < n_buses; b++) if (bus(k, b).present()) call.on[k] = true;       // (an effect on a bus past the call's is idle in it)
     for (uint32_t b = 0; b < n_buses; b++) if (eq[b].present()) call.eq = true;                      // (and so is an EQ)
+    for (uint32_t b = 0; b < n_buses; b++) if (dyn_runs(b, n_buses)) call.dyn = true;                // (and dynamics, also when their key bus is past the call's)
     call.limited = master_fill && limiter.lookahead != 0;
     if (call.master) {                                           // the device copy of the stems and the pinned rows of block partials
         if (!master.stage) POST_HIP(hipMalloc((void **)&master.stage, (size_t)2 * S2R_MAX_BUSES * c.max_frames * sizeof(float)));
@@ -80,12 +81,13 @@ hipError_t S2rPostChain::prepare(const S2rPostCtx &c, uint32_t n_buses, uint32_t
     }
     float *stages[S2R_STEM_STAGES];
     for (int k = 0; k < S2R_STEM_STAGES; k++) stages[k] = stem[k].stage;
-    call.route = s2r_post_route_eq(call, s2r_post_route(call, stages, master.stage, limiter.in, c.bus_out_dev, c.out_host_dev), eq_insert.stage);
+    call.route = s2r_post_route_dyn(call, s2r_post_route_eq(call, s2r_post_route(call, stages, master.stage, limiter.in, c.bus_out_dev, c.out_host_dev), eq_insert.stage),
+                                    dyn_insert.stage);
     return hipSuccess;
 }
 
 hipError_t S2rPostChain::launch(const S2rPostCtx &c, const S2rPostCall &call) {
-    const S2rPostRoute &r = call.route; const float fn = (float)call.frames;
+    const S2rPostRouteDyn &r = call.route; const float fn = (float)call.frames;
     if (call.eq) {                                               // once per call, over all of its frames, in front of every stem stage
         S2rEq a{};
         for (uint32_t b = 0; b < call.n_buses; b++) {
@@ -97,6 +99,18 @@ hipError_t S2rPostChain::launch(const S2rPostCtx &c, const S2rPostCall &call) {
         }
         a.in = r.eq.in; a.out = r.eq.out; a.n_buses = call.n_buses; a.frames = call.frames;
         POST_TIMED(c, eq_insert.timer, s2r_launch_bus_eq(a, c.stream));
+    }
+    if (call.dyn) {                                              // likewise, behind the EQs: every bus and every key as the EQs left them
+        S2rDyn a{};
+        for (uint32_t b = 0; b < call.n_buses; b++) {
+            if (!dyn_runs(b, call.n_buses)) continue;
+            const BusDyn &f = dyn[b];
+            S2rDynBus &d = a.bus[b];
+            d.line = f.now(); d.next = f.next(); d.curve = dyn_curves + (size_t)b * S2R_DYN_CURVE_POINTS;
+            d.key = f.key; d.a_att = f.a_att; d.a_rel = f.a_rel;
+        }
+        a.in = r.dyn.in; a.out = r.dyn.out; a.meter = dyn_meter_dev; a.n_buses = call.n_buses; a.frames = call.frames;
+        POST_TIMED(c, dyn_insert.timer, s2r_launch_bus_dyn(a, c.stream));
     }
     if (call.on[S2R_STEM_CHORUS]) {                              // likewise, in front of the delays
         S2rChorus a{};
@@ -166,6 +180,8 @@ hipError_t S2rPostChain::launch(const S2rPostCtx &c, const S2rPostCall &call) {
 
 void S2rPostChain::commit(const S2rPostCall &call) {
     if (call.eq) for (uint32_t b = 0; b < call.n_buses; b++) if (eq[b].present()) eq[b].flip();     // the EQs' states have moved on
+    if (call.dyn)                                                // ... the dynamics' gains, and the kernel's minima are the call's meters
+        for (uint32_t b = 0; b < call.n_buses; b++) if (dyn_runs(b, call.n_buses)) { dyn[b].flip(); dyn[b].min_gain = dyn_meter[b]; }
     for (int k = 0; k < S2R_STEM_STAGES; k++)                    // the histories have moved on
         if (call.on[k]) for (uint32_t b = 0; b < call.n_buses; b++) if (bus(k, b).present()) bus(k, b).flip();
     if (call.on[S2R_STEM_CHORUS])                                // ... and the choruses' phases
@@ -198,9 +214,10 @@ void S2rPostChain::commit(const S2rPostCall &call) {
     }
 }
 
-// a stage that the fill could have run and did not reads 0; a panned fill leaves all six values alone, a bus fill the master's two
+// a stage that the fill could have run and did not reads 0; a panned fill leaves all seven values alone, a bus fill the master's two
 hipError_t S2rPostChain::read_timers(const S2rPostCall &call) {
     if (call.n_buses) { eq_insert.timer.ms = 0.0f; if (call.eq) POST_HIP(eq_insert.timer.read()); }
+    if (call.n_buses) { dyn_insert.timer.ms = 0.0f; if (call.dyn) POST_HIP(dyn_insert.timer.read()); }
     if (call.n_buses) for (int k = 0; k < S2R_STEM_STAGES; k++) { stem[k].timer.ms = 0.0f; if (call.on[k]) POST_HIP(stem[k].timer.read()); }
     if (call.master) {
         POST_HIP(master.timer.read());
@@ -211,10 +228,13 @@ hipError_t S2rPostChain::read_timers(const S2rPostCall &call) {
 }
 
 void S2rPostChain::release() {
-    for (uint32_t b = 0; b < S2R_MAX_BUSES; b++) { drop(eq[b]); drop(chorus[b]); drop(delay[b]); drop(fx[b]); }
+    for (uint32_t b = 0; b < S2R_MAX_BUSES; b++) { drop(eq[b]); drop(dyn[b]); drop(chorus[b]); drop(delay[b]); drop(fx[b]); }
     for (Stem &st : stem) { if (st.stage) (void)hipFree(st.stage); st.timer.destroy(); }
     if (eq_insert.stage) (void)hipFree(eq_insert.stage);
     eq_insert.timer.destroy();
+    for (float *p : {dyn_insert.stage, dyn_curves}) if (p) (void)hipFree(p);
+    if (dyn_meter) (void)hipHostFree(dyn_meter);
+    dyn_insert.timer.destroy();
     for (float *p : {master.stage, limiter.state[0], limiter.state[1], limiter.in}) if (p) (void)hipFree(p);
     for (float *p : {master.partials, limiter.partials}) if (p) (void)hipHostFree(p);
     for (S2rPostTimer *t : {&master.timer, &limiter.timer}) t->destroy();
@@ -230,6 +250,36 @@ hipError_t S2rPostChain::set_eq(const S2rPostCtx &c, uint32_t bus, uint32_t n_ba
 
 hipError_t S2rPostChain::eq_state(const S2rPostCtx &c, uint32_t bus, float *get, const float *set) {
     POST_HIP(eq[bus].copy(get, set, 0, eq[bus].floats, c.stream));
+    return hipStreamSynchronize(c.stream);
+}
+
+// The tables and the pinned meter row come first and once; the bus's row of the tables is written last, by a copy queued behind
+// everything that can fail for want of memory, so that a refused set leaves the earlier dynamics whole.
+hipError_t S2rPostChain::set_dyn(const S2rPostCtx &c, uint32_t bus, uint32_t key, const float *curve, float a_att, float a_rel, bool keep_state) {
+    if (!curve) { drop(dyn[bus]); return hipSuccess; }
+    float *const row = dyn_curves ? dyn_curves + (size_t)bus * S2R_DYN_CURVE_POINTS : nullptr;
+    if (keep_state) {
+        BusDyn &d = dyn[bus];
+        POST_HIP(hipMemcpyAsync(row, curve, S2R_DYN_CURVE_POINTS * sizeof(float), hipMemcpyHostToDevice, c.stream));
+        POST_HIP(hipStreamSynchronize(c.stream));
+        d.key = key; d.a_att = a_att; d.a_rel = a_rel;
+        d.curve.assign(curve, curve + S2R_DYN_CURVE_POINTS);
+        return hipSuccess;
+    }
+    if (!dyn_curves) POST_HIP(hipMalloc((void **)&dyn_curves, (size_t)S2R_MAX_BUSES * S2R_DYN_CURVE_POINTS * sizeof(float)));
+    POST_HIP(pinned_rows(dyn_meter, dyn_meter_dev, S2R_MAX_BUSES));
+    BusDyn f;
+    f.key = key; f.a_att = a_att; f.a_rel = a_rel; f.history = 1u;
+    f.curve.assign(curve, curve + S2R_DYN_CURVE_POINTS);
+    float *const to = dyn_curves + (size_t)bus * S2R_DYN_CURVE_POINTS;
+    return replace(c, dyn_insert.stage, dyn[bus], f, 1u, [&](BusDyn &n) {          // y = curve[0], the gain at silence
+        POST_HIP(hipMemcpyAsync(n.line[0], n.curve.data(), sizeof(float), hipMemcpyHostToDevice, c.stream));
+        return hipMemcpyAsync(to, n.curve.data(), S2R_DYN_CURVE_POINTS * sizeof(float), hipMemcpyHostToDevice, c.stream);
+    });
+}
+
+hipError_t S2rPostChain::dyn_state(const S2rPostCtx &c, uint32_t bus, float *get, const float *set) {
+    POST_HIP(dyn[bus].copy(get, set, 0, 1u, c.stream));
     return hipStreamSynchronize(c.stream);
 }
 

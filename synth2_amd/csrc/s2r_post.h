@@ -1,6 +1,6 @@
-// s2r_post.h — the chain behind the bus mixdown of s2r_fill_buses and s2r_fill_master: the buses' equalisers, an insert
-// at the head of the stem stages (s2r_post_route.h) — the buses' choruses (4.20), their feedback delays (4.19), their convolution
-// reverbs (4.16) —, the master section (4.17) and the master limiter (4.18), in that order.  The chain owns what the six stages own
+// s2r_post.h — the chain behind the bus mixdown of s2r_fill_buses and s2r_fill_master: the buses' equalisers and their
+// dynamics (4.22), two inserts at the head of the stem stages (s2r_post_route.h) — the buses' choruses (4.20), their feedback delays
+// (4.19), their convolution reverbs (4.16) —, the master section (4.17) and the master limiter (4.18), in that order.  The chain owns what the seven stages own
 // and knows nothing of the handle: its functions take a S2rPostCtx and return the HIP error.  Per call: prepare, launch, — the caller's synchronise — commit, read_timers.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -76,6 +76,19 @@ struct S2rPostChain {
         float c[S2R_EQ_MAX_BANDS][5] = {};       // (b0, b1, b2, a1, a2) per band
     } eq[S2R_MAX_BUSES];
     Stem eq_insert;                              // (its timer: tools/eq_time.py)
+    // The dynamics (s2r_set_bus_dynamics): lines of one float, the gain y.  The second insert, behind the EQ (s2r_post_route_dyn), with a
+    // staging buffer and a timer of its own, the curves' tables on the device and a pinned row for the calls' meters
+    struct BusDyn : S2rBusLine {
+        uint32_t key = 0;
+        float a_att = 0.0f, a_rel = 0.0f;
+        float min_gain = 1.0f;                   // the meter of the last successful call that ran these dynamics
+        std::vector<float> curve;                // the host's copy of the table: S2R_DYN_CURVE_POINTS entries
+    } dyn[S2R_MAX_BUSES];
+    Stem dyn_insert;                             // (its timer: tools/dyn_time.py)
+    float *dyn_curves = nullptr;                 // [S2R_MAX_BUSES][S2R_DYN_CURVE_POINTS] in device memory, allocated when dynamics are first set
+    float *dyn_meter = nullptr, *dyn_meter_dev = nullptr;        // pinned and device-mapped: [S2R_MAX_BUSES]
+    // the bus's dynamics run in a call of n_buses buses: both the bus and its key are among them
+    bool dyn_runs(uint32_t b, uint32_t n_buses) const { return b < n_buses && dyn[b].present() && dyn[b].key < n_buses; }
     // stage k's effect on a bus, as far as the stages are alike
     S2rBusLine &bus(int k, uint32_t b) { S2rBusLine *const of[S2R_STEM_STAGES] = {&chorus[b], &delay[b], &fx[b]}; return *of[k]; }
     const S2rBusLine &bus(int k, uint32_t b) const { return const_cast<S2rPostChain *>(this)->bus(k, b); }
@@ -119,6 +132,9 @@ struct S2rPostChain {
     // what the entry points of s2r_host.cpp do behind their checks, on a quiet stream
     hipError_t set_eq(const S2rPostCtx &c, uint32_t bus, uint32_t n_bands, const float *coeffs);
     hipError_t eq_state(const S2rPostCtx &c, uint32_t bus, float *get, const float *set);      // the 4 * n_bands floats, out or in
+    // curve null: removes the bus's dynamics; keep_state: the parameters alone, on a bus that has them
+    hipError_t set_dyn(const S2rPostCtx &c, uint32_t bus, uint32_t key, const float *curve, float a_att, float a_rel, bool keep_state);
+    hipError_t dyn_state(const S2rPostCtx &c, uint32_t bus, float *get, const float *set);     // the one float, out or in
     hipError_t set_chorus(const S2rPostCtx &c, uint32_t bus, uint32_t voices, float base, float depth, uint32_t phase_inc, uint32_t spread, float dry, float wet);
     hipError_t set_delay(const S2rPostCtx &c, uint32_t bus, uint32_t delay_frames, float feedback, float cross, float dry, float wet);
     hipError_t set_reverb(const S2rPostCtx &c, uint32_t bus, const float *ir_l, const float *ir_r, uint32_t n_taps, float dry, float wet);

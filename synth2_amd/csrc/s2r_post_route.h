@@ -13,13 +13,19 @@ struct S2rPostRoute {
     struct { float *in, *out; } eq;              // the EQ insert at the head of the stem chain (s2r_post_route_eq): null unless the call runs it
     float *master_in, *master_out, *master_stems, *limiter_in, *limiter_out;
 };
+// ... and the dynamics insert behind the EQ (s2r_post_route_dyn): null unless the call runs it.  A struct of its own on top of the
+// route, whose layout stays what it was
+struct S2rPostRouteDyn : S2rPostRoute {
+    struct { float *in, *out; } dyn;
+};
 struct S2rPostCall {                             // one fill, as prepare leaves it
     uint32_t n_buses = 0, frames = 0;            // n_buses 0: a panned fill, which runs no stage
     bool master = false, stems = false;          // s2r_fill_master; the caller wants the stems too
     bool on[S2R_STEM_STAGES] = {};               // the stage's effect sits on one of the call's buses
     bool limited = false;                        // a master fill with the limiter set
     bool eq = false;                             // an EQ sits on one of the call's buses
-    S2rPostRoute route{};
+    bool dyn = false;                            // dynamics sit on one of the call's buses, their key bus among them too
+    S2rPostRouteDyn route{};
 };
 
 // Who reads and writes what, the only place that decides it.  The combine writes into the first stem stage that runs, each running
@@ -51,5 +57,19 @@ inline S2rPostRoute s2r_post_route_eq(const S2rPostCall &call, S2rPostRoute r, f
     if (!call.eq || !call.n_buses) return r;
     r.eq.in = eq_stage; r.eq.out = r.combine_out;
     r.combine_out = eq_stage;
+    return r;
+}
+
+// The dynamics are the second insert, behind the EQ and in front of the stem stages, applied to the route after s2r_post_route_eq: the
+// stage reads its own staging buffer and writes where the stage in front of it — the EQ if the call runs it, else the combine —
+// would have written, and that writer is redirected into the dynamics' buffer.  A call without dynamics, or without buses, keeps its
+// route as it is, with a null dyn pair.
+inline S2rPostRouteDyn s2r_post_route_dyn(const S2rPostCall &call, const S2rPostRoute &route, float *dyn_stage) {
+    S2rPostRouteDyn r{};
+    static_cast<S2rPostRoute &>(r) = route;
+    if (!call.dyn || !call.n_buses) return r;
+    float *&writer = call.eq ? r.eq.out : r.combine_out;
+    r.dyn.in = dyn_stage; r.dyn.out = writer;
+    writer = dyn_stage;
     return r;
 }

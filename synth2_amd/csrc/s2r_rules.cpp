@@ -153,6 +153,69 @@ int s2r_eq_design(int kind, double freq_hz, double gain_db, double q, double sam
     return S2R_OK;
 }
 
+// ---- per-bus dynamics: level of the key, target gain by table, attack / release ballistics, both channels one gain ----
+static inline float dyn_target(const float *curve, float p) {
+    const uint32_t lo = 0x33800000u;                             // the bits of 2^-24; 2^8 is lo + (512 << 19)
+    if (!(p >= 5.9604644775390625e-08f)) return curve[0];
+    if (p >= 256.0f) return curve[S2R_DYN_CURVE_POINTS - 1u];
+    uint32_t u;
+    std::memcpy(&u, &p, sizeof u);
+    const uint32_t i = (u - lo) >> 19;
+    const float f = (float)((u - lo) & 0x7ffffu) * 1.9073486328125e-06f;     // exact: 19 bits times 2^-19
+    const float d = curve[i + 1u] - curve[i];
+    const float m = f * d;
+    return curve[i] + m;
+}
+
+int s2r_dynamics_reference(const float *curve, float a_att, float a_rel, const float *key_lr, const float *x_lr, uint32_t frames, float *y, float *out_lr,
+                           float *min_gain) {
+    if (!dyn_in_range(curve, a_att, a_rel) || (y && !dyn_state_in_range(*y))) return S2R_ERR_PATCH_RANGE;
+    if (!curve || !y || (!x_lr && frames)) return S2R_ERR_INVALID;
+    if (!key_lr) key_lr = x_lr;
+    float g = *y, mn = INFINITY;
+    for (uint32_t n = 0; n < frames; n++) {
+        const float kl = std::fabs(key_lr[2 * (size_t)n]), kr = std::fabs(key_lr[2 * (size_t)n + 1]);
+        const float p = kl > kr ? kl : kr;
+        const float t = dyn_target(curve, p);
+        const float a = t < g ? a_att : a_rel;
+        const float d = g - t;
+        const float m = a * d;
+        g = t + m;
+        mn = g < mn ? g : mn;
+        if (out_lr) { out_lr[2 * (size_t)n] = x_lr[2 * (size_t)n] * g; out_lr[2 * (size_t)n + 1] = x_lr[2 * (size_t)n + 1] * g; }
+    }
+    *y = g;
+    if (min_gain && frames) *min_gain = mn;
+    return S2R_OK;
+}
+
+// a soft-knee compressor's table: binary64 throughout, each entry rounded once to binary32
+int s2r_dynamics_curve(double threshold_db, double ratio, double knee_db, double makeup_db, float *curve) {
+    if (std::isnan(threshold_db) || std::isnan(ratio) || std::isnan(knee_db) || std::isnan(makeup_db) || !(ratio >= 1.0) || !(knee_db >= 0.0))
+        return S2R_ERR_PATCH_RANGE;
+    if (!curve) return S2R_ERR_INVALID;
+    const double slope = 1.0 / ratio - 1.0, W = knee_db;
+    float out[S2R_DYN_CURVE_POINTS];
+    for (uint32_t j = 0; j < S2R_DYN_CURVE_POINTS; j++) {
+        const double level = std::ldexp(1.0 + (double)(j % 16u) / 16.0, -24 + (int)(j / 16u));
+        const double o = 20.0 * std::log10(level) - threshold_db;
+        double G;
+        if (2.0 * o < -W) G = 0.0;
+        else if (W > 0.0 && 2.0 * std::fabs(o) <= W) G = slope * (o + W / 2.0) * (o + W / 2.0) / (2.0 * W);
+        else G = slope * o;
+        out[j] = (float)std::pow(10.0, (G + makeup_db) / 20.0);
+        if (!(out[j] >= 0.0f && out[j] <= 256.0f)) return S2R_ERR_PATCH_RANGE;
+    }
+    std::memcpy(curve, out, sizeof out);
+    return S2R_OK;
+}
+
+float s2r_dynamics_coef(double ms, double sample_rate) {
+    if (std::isnan(ms) || std::isnan(sample_rate) || ms < 0.0 || !(sample_rate > 0.0)) return NAN;
+    if (ms == 0.0) return 0.0f;
+    return (float)std::exp(-1.0 / (ms * 0.001 * sample_rate));
+}
+
 // ---- the master section: energies by the adjacent-pair tree over blocks of S2R_METER_BLOCK frames ----
 static float master_energy(const float *v, uint32_t frames) {     // v: one channel of an interleaved pair (stride 2)
     float total = 0.0f;

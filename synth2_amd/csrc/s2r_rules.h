@@ -45,6 +45,14 @@ static inline bool eq_in_range(uint32_t n_bands, const float *coeffs) {
     for (uint32_t k = 0; k < n_bands && coeffs; k++) if (!eq_band_in_range(coeffs + 5 * k)) return false;
     return true;
 }
+// a bus's dynamics: every curve entry finite and in [0, 2^8], both coefficients in [0, 1); a state finite and >= 0
+static inline bool dyn_coef_in_range(float a) { return a >= 0.0f && a < 1.0f; }
+static inline bool dyn_in_range(const float *curve, float a_att, float a_rel) {
+    if (!dyn_coef_in_range(a_att) || !dyn_coef_in_range(a_rel)) return false;
+    for (uint32_t j = 0; j < S2R_DYN_CURVE_POINTS && curve; j++) if (!(curve[j] >= 0.0f && curve[j] <= 256.0f)) return false;
+    return true;
+}
+static inline bool dyn_state_in_range(float y) { return std::isfinite(y) && y >= 0.0f; }
 
 // The voice mixer's gain rules, inline: the host's per-voice loops compile them in — a call per voice into s2r_rules.cpp showed as 10
 // to 15 us of host time per fill of 65 536 voices (profiles/r12/post_chain.txt).  s2r_rules.cpp exports them under their s2r.h names.

@@ -40,6 +40,7 @@ CHORUS_MAX_VOICES = 8                       # S2R_CHORUS_MAX_VOICES
 CHORUS_MAX_DELAY = 4095.0                   # S2R_CHORUS_MAX_DELAY
 EQ_MAX_BANDS = 4                            # S2R_EQ_MAX_BANDS
 EQ_PEAK, EQ_LOW_SHELF, EQ_HIGH_SHELF, EQ_LOWPASS, EQ_HIGHPASS = range(5)     # s2r_eq_kind
+DYN_CURVE_POINTS = 513                      # S2R_DYN_CURVE_POINTS
 IR_SEGMENT = 256                            # S2R_IR_SEGMENT
 METER_BLOCK = 256                           # S2R_METER_BLOCK
 LIMITER_MAX_LOOKAHEAD = 1024                # S2R_LIMITER_MAX_LOOKAHEAD
@@ -226,6 +227,16 @@ def load_library():
         "s2r_set_bus_eq_state": (C.c_int, [H, C.c_uint32, _f32p, C.c_size_t]),
         "s2r_eq_reference": (C.c_int, [C.c_uint32, _f32p, _f32p, C.c_uint32, _f32p, _f32p]),
         "s2r_eq_design": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, _f32p]),
+        "s2r_set_bus_dynamics": (C.c_int, [H, C.c_uint32, C.c_uint32, _f32p, C.c_float, C.c_float]),
+        "s2r_clear_bus_dynamics": (C.c_int, [H, C.c_uint32]),
+        "s2r_set_bus_dynamics_params": (C.c_int, [H, C.c_uint32, C.c_uint32, _f32p, C.c_float, C.c_float]),
+        "s2r_get_bus_dynamics": (C.c_int, [H, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _f32p, C.c_size_t, _f32p, _f32p]),
+        "s2r_get_bus_dynamics_state": (C.c_int, [H, C.c_uint32, _f32p, C.c_size_t]),
+        "s2r_set_bus_dynamics_state": (C.c_int, [H, C.c_uint32, _f32p, C.c_size_t]),
+        "s2r_get_bus_dynamics_meter": (C.c_int, [H, C.c_uint32, _f32p]),
+        "s2r_dynamics_reference": (C.c_int, [_f32p, C.c_float, C.c_float, _f32p, _f32p, C.c_uint32, _f32p, _f32p, _f32p]),
+        "s2r_dynamics_curve": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_double, _f32p]),
+        "s2r_dynamics_coef": (C.c_float, [C.c_double, C.c_double]),
         "s2r_set_bus_return": (C.c_int, [H, C.c_uint32, C.c_float]),
         "s2r_get_bus_return": (C.c_int, [H, C.c_uint32, _f32p, _f32p]),
         "s2r_set_master_fader": (C.c_int, [H, C.c_float]),
@@ -440,6 +451,47 @@ def eq_design(kind, freq_hz, gain_db, q, sample_rate):
     if rc != S2R_OK:
         raise S2rError(rc, load_library().s2r_status_string(rc).decode())
     return out
+
+
+def _dyn_curve(curve, who):
+    c = np.ascontiguousarray(curve, dtype=np.float32)
+    if c.shape != (DYN_CURVE_POINTS,):
+        raise ValueError(who + ": curve is [%d] float32" % DYN_CURVE_POINTS)
+    return c
+
+
+def dynamics_reference(curve, a_att, a_rel, key, x, y):
+    """the bus dynamics' rule on the host (s2r_dynamics_reference): curve [DYN_CURVE_POINTS] float32, the two retention coefficients,
+    key [frames, 2] float32 the key bus's signal (None: x keys itself), x [frames, 2] the bus's, y the gain carried in; returns (out
+    [frames, 2], the gain after the call as np.float32, the minimum of the gain over the call — inf for no frames)"""
+    c = _dyn_curve(curve, "dynamics_reference")
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    k = x if key is None else np.ascontiguousarray(key, dtype=np.float32)
+    if x.ndim != 2 or x.shape[1] != 2 or k.shape != x.shape:
+        raise ValueError("dynamics_reference: key and x are [frames, 2]")
+    out = np.empty_like(x)
+    st = np.array([y], dtype=np.float32)
+    mn = np.array([np.inf], dtype=np.float32)
+    rc = load_library().s2r_dynamics_reference(c.ctypes.data_as(_f32p), C.c_float(float(np.float32(a_att))), C.c_float(float(np.float32(a_rel))),
+                                               k.ctypes.data_as(_f32p), x.ctypes.data_as(_f32p), x.shape[0], st.ctypes.data_as(_f32p),
+                                               out.ctypes.data_as(_f32p), mn.ctypes.data_as(_f32p))
+    if rc != S2R_OK:
+        raise S2rError(rc, load_library().s2r_status_string(rc).decode())
+    return out, st[0], mn[0]
+
+
+def dynamics_curve(threshold_db, ratio, knee_db=0.0, makeup_db=0.0):
+    """the table [DYN_CURVE_POINTS] float32 of a soft-knee compressor (s2r_dynamics_curve): ratio in [1, inf], inf the limiter's curve"""
+    out = np.empty(DYN_CURVE_POINTS, dtype=np.float32)
+    rc = load_library().s2r_dynamics_curve(float(threshold_db), float(ratio), float(knee_db), float(makeup_db), out.ctypes.data_as(_f32p))
+    if rc != S2R_OK:
+        raise S2rError(rc, load_library().s2r_status_string(rc).decode())
+    return out
+
+
+def dynamics_coef(ms, sample_rate):
+    """the retention coefficient of a time constant (s2r_dynamics_coef): float32 exp(-1 / (ms * 0.001 * sample_rate)), 0 for ms == 0"""
+    return np.float32(load_library().s2r_dynamics_coef(float(ms), float(sample_rate)))
 
 
 def master_reference(stems, r0, r1, m0, m1):
@@ -960,6 +1012,61 @@ class Synth:
     @staticmethod
     def eq_design(kind, freq_hz, gain_db, q, sample_rate):
         return eq_design(kind, freq_hz, gain_db, q, sample_rate)
+
+    # --- per-bus dynamics (build-defined; s2r.h: s2r_set_bus_dynamics) ---
+    def set_bus_dynamics(self, bus, key_bus, curve, a_att, a_rel):
+        """a sidechain compressor on a bus of sample_buses and sample_master, behind its EQ: key_bus == bus is the ordinary compressor,
+        another bus a ducker; curve [DYN_CURVE_POINTS] float32 gains in [0, 256] (dynamics_curve makes one), a_att and a_rel in [0, 1)
+        (dynamics_coef).  Replaces any earlier dynamics of the bus and resets the gain to curve[0]."""
+        c = _dyn_curve(curve, "set_bus_dynamics")
+        self._check(self.L.s2r_set_bus_dynamics(self.h, int(bus), int(key_bus), c.ctypes.data_as(_f32p), float(np.float32(a_att)), float(np.float32(a_rel))))
+
+    def clear_bus_dynamics(self, bus):
+        """removes the bus's dynamics: the bus passes again, bit for bit"""
+        self._check(self.L.s2r_clear_bus_dynamics(self.h, int(bus)))
+
+    def set_bus_dynamics_params(self, bus, key_bus, curve, a_att, a_rel):
+        """key, curve and coefficients alone; the gain stays, so a threshold moves between calls without a restart"""
+        c = _dyn_curve(curve, "set_bus_dynamics_params")
+        self._check(self.L.s2r_set_bus_dynamics_params(self.h, int(bus), int(key_bus), c.ctypes.data_as(_f32p), float(np.float32(a_att)),
+                                                       float(np.float32(a_rel))))
+
+    def get_bus_dynamics(self, bus):
+        """(key_bus, curve [DYN_CURVE_POINTS] float32, a_att, a_rel) of the bus's dynamics; None for a bus without"""
+        present, key = C.c_uint32(), C.c_uint32()
+        curve = np.empty(DYN_CURVE_POINTS, dtype=np.float32)
+        a = np.empty(2, dtype=np.float32)
+        self._check(self.L.s2r_get_bus_dynamics(self.h, int(bus), C.byref(present), C.byref(key), curve.ctypes.data_as(_f32p), curve.size,
+                                                a[0:].ctypes.data_as(_f32p), a[1:].ctypes.data_as(_f32p)))
+        return (key.value, curve, a[0], a[1]) if present.value else None
+
+    def bus_dynamics_state(self, bus):
+        """the gain the bus's dynamics carry into the next call, np.float32 — the checkpoint companion of bus_eq_state"""
+        out = np.empty(1, dtype=np.float32)
+        self._check(self.L.s2r_get_bus_dynamics_state(self.h, int(bus), out.ctypes.data_as(_f32p), out.size))
+        return out[0]
+
+    def set_bus_dynamics_state(self, bus, y):
+        st = np.array([y], dtype=np.float32)
+        self._check(self.L.s2r_set_bus_dynamics_state(self.h, int(bus), st.ctypes.data_as(_f32p), st.size))
+
+    def bus_dynamics_meter(self, bus):
+        """the least gain of the last sample_buses / sample_master call that ran the bus's dynamics: 1.0 before any"""
+        out = np.empty(1, dtype=np.float32)
+        self._check(self.L.s2r_get_bus_dynamics_meter(self.h, int(bus), out.ctypes.data_as(_f32p)))
+        return out[0]
+
+    @staticmethod
+    def dynamics_reference(curve, a_att, a_rel, key, x, y):
+        return dynamics_reference(curve, a_att, a_rel, key, x, y)
+
+    @staticmethod
+    def dynamics_curve(threshold_db, ratio, knee_db=0.0, makeup_db=0.0):
+        return dynamics_curve(threshold_db, ratio, knee_db, makeup_db)
+
+    @staticmethod
+    def dynamics_coef(ms, sample_rate):
+        return dynamics_coef(ms, sample_rate)
 
     # --- the master section (build-defined; s2r.h: s2r_fill_master) ---
     def set_bus_return(self, bus, level=1.0):
