@@ -212,6 +212,30 @@ class Synth {
         return s2r_dynamics_curve(threshold_db, ratio, knee_db, makeup_db, curve);
     }
     static float dynamics_coef(double ms, double sample_rate) { return s2r_dynamics_coef(ms, sample_rate); }
+    // per-bus room reverb, the last stem writer (build-defined; s2r.h: s2r_set_bus_room): eight damped feedback combs cd[S2R_ROOM_COMBS]
+    // and four allpasses ad[S2R_ROOM_ALLPASSES] per channel, delays in frames, the right channel's `spread` longer (room_design makes a
+    // set); feedback in [0, 1), damp in [0, 1], g in (-1, 1), gain, dry, wet and cross in [0, 1]; in sample_buses and sample_master only
+    void set_bus_room(uint32_t bus, const uint32_t *cd, const uint32_t *ad, uint32_t spread, float feedback, float damp, float g, float gain, float dry, float wet,
+                      float cross) {
+        check(s2r_set_bus_room(h_, bus, cd, ad, spread, feedback, damp, g, gain, dry, wet, cross));
+    }
+    void clear_bus_room(uint32_t bus) { check(s2r_clear_bus_room(h_, bus)); }
+    void set_bus_room_params(uint32_t bus, float feedback, float damp, float g, float gain, float dry, float wet, float cross) {   // delays and state stay
+        check(s2r_set_bus_room_params(h_, bus, feedback, damp, g, gain, dry, wet, cross));
+    }
+    bool get_bus_room(uint32_t bus, uint32_t *cd, uint32_t *ad, uint32_t *spread, float *levels) const {
+        uint32_t present = 0;
+        check(s2r_get_bus_room(h_, bus, &present, cd, ad, spread, levels));
+        return present != 0;
+    }
+    void bus_room_state(uint32_t bus, float *state, size_t capacity) { check(s2r_get_bus_room_state(h_, bus, state, capacity)); }
+    void set_bus_room_state(uint32_t bus, const float *state, size_t count) { check(s2r_set_bus_room_state(h_, bus, state, count)); }
+    static size_t room_state_floats(const uint32_t *cd, const uint32_t *ad, uint32_t spread) { return s2r_room_state_floats(cd, ad, spread); }
+    static int room_reference(const uint32_t *cd, const uint32_t *ad, uint32_t spread, float feedback, float damp, float g, float gain, float dry, float wet,
+                              float cross, const float *x_lr, uint32_t frames, float *state, float *out_lr) {
+        return s2r_room_reference(cd, ad, spread, feedback, damp, g, gain, dry, wet, cross, x_lr, frames, state, out_lr);
+    }
+    static int room_design(double sample_rate, double size, uint32_t *cd, uint32_t *ad, uint32_t *spread) { return s2r_room_design(sample_rate, size, cd, ad, spread); }
 
     // the master section (build-defined; s2r.h: s2r_fill_master): a return level per bus and a master fader, each in [0, 1] and each
     // reaching its target as a ramp across the next sample_master call, and the meters of that call — in sample_master only

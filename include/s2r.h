@@ -45,7 +45,8 @@ extern "C" {
  * s2r_set_bus_chorus_state, s2r_chorus_reference, s2r_set_bus_eq, s2r_set_bus_eq_coeffs, s2r_get_bus_eq, s2r_get_bus_eq_state,
  * s2r_set_bus_eq_state, s2r_eq_reference, s2r_eq_design, s2r_set_bus_dynamics, s2r_clear_bus_dynamics, s2r_set_bus_dynamics_params,
  * s2r_get_bus_dynamics, s2r_get_bus_dynamics_state, s2r_set_bus_dynamics_state, s2r_get_bus_dynamics_meter, s2r_dynamics_reference,
- * s2r_dynamics_curve, s2r_dynamics_coef. */
+ * s2r_dynamics_curve, s2r_dynamics_coef, s2r_set_bus_room, s2r_clear_bus_room, s2r_set_bus_room_params, s2r_get_bus_room,
+ * s2r_get_bus_room_state, s2r_set_bus_room_state, s2r_room_state_floats, s2r_room_reference, s2r_room_design. */
 #define S2R_ABI_VERSION 4
 
 typedef enum {
@@ -604,6 +605,67 @@ int s2r_dynamics_reference(const float *curve, float a_att, float a_rel, const f
                            float *min_gain);
 int s2r_dynamics_curve(double threshold_db, double ratio, double knee_db, double makeup_db, float *curve);
 float s2r_dynamics_coef(double ms, double sample_rate);
+
+/* BUILD-DEFINED per-bus room reverb (the reference has no effects): the algorithmic reverb of Schroeder and Moorer in
+ * the form Freeverb made standard — eight parallel feedback combs with a one-pole low-pass in the loop, then four allpasses in
+ * series —, computed on the device as the last stem writer:
+ * combine -> eq -> dynamics -> chorus -> delay -> reverb -> room -> master -> limiter.  A bus b in [0, S2R_MAX_BUSES) may carry a
+ * room: comb delays cd[S2R_ROOM_COMBS], allpass delays ad[S2R_ROOM_ALLPASSES] and a spread, all in frames — the right channel's lines
+ * are `spread` frames longer than the left's, D_Li = cd[i], D_Ri = cd[i] + spread, E_Lj = ad[j], E_Rj = ad[j] + spread, every one of
+ * them in [S2R_ROOM_MIN_DELAY, S2R_ROOM_MAX_DELAY] —, feedback in [0, 1), damp in [0, 1], g in (-1, 1), gain, dry, wet and cross in
+ * [0, 1]; d1 = fl(1 - damp), computed once at the set.  State, all +0.0 right after a set: per channel c and comb i a line C_ci of
+ * D_ci frames and one filter value f_ci; per channel and allpass j a line A_cj of E_cj frames.  For frame n of a call of N frames,
+ * with x the bus as it enters the stage (negative indices are history):
+ *   in = fl(fl(xL[n] + xR[n]) * gain)
+ *   per channel c:  acc = +0.0
+ *     for i = 0..7:   o = C_ci[n - D_ci];  f_ci = fl(fl(o * d1) + fl(f_ci * damp));  C_ci[n] = fl(in + fl(f_ci * feedback));  acc = fl(acc + o)
+ *     for j = 0..3:   b = A_cj[n - E_cj];  y = fl(b - acc);  A_cj[n] = fl(acc + fl(b * g));  acc = y
+ *     v_c = acc
+ *   out_c[n] = fl(fl(dry * x_c[n]) + fl(fl(wet * v_c) + fl(cross * v_(1-c))))
+ * binary32 throughout, every operation rounded on its own (no fma), denormals kept, nothing skipped for a zero coefficient.  The rule
+ * claims no bound on the output: feedback < 1 keeps every loop's gain under one in exact arithmetic, and no more is claimed.
+ * Non-finite bus samples are outside the contract.  After a call that returns S2R_OK each line holds its last D frames and each f its
+ * last value: calls of any lengths concatenate.  The stage runs once per call over all N frames, after every event segment and rows
+ * slice has been mixed.  A room on a bus >= the call's n_buses is idle in that call, its state untouched.  A bus without a room
+ * passes bit for bit, -0.0 included.  A refused or failed call leaves the state where it was.  ONLY s2r_fill_buses and
+ * s2r_fill_master apply it.  A handle on which none was ever set launches what it launched before and allocates nothing for it;
+ * device memory is allocated when a room is set (S2R_ERR_OUT_OF_MEMORY when that fails, and the earlier room is kept), never in a fill.
+ * The state as one flat float array (the checkpoint): for c = L, R: for each comb its line, oldest frame first, and then its f; then
+ * for each allpass its line.  s2r_room_state_floats gives the count: 2 * (sum cd + sum ad + 8) + 12 * spread; 0 out of range.
+ *   s2r_set_bus_room: replaces any earlier room of the bus and zeroes the state.  S2R_ERR_PATCH_RANGE for a bus >= S2R_MAX_BUSES, a
+ *   delay or a level outside its range or a NaN (checked before the handle is looked at; nothing is changed); S2R_ERR_INVALID for a
+ *   NULL cd or ad.
+ *   s2r_clear_bus_room removes it (S2R_OK on a bus without).
+ *   s2r_set_bus_room_params: the seven levels alone; delays and state stay, so room size (feedback) and damping move between calls
+ *   with no restart.  S2R_ERR_INVALID on a bus without a room.
+ *   s2r_get_bus_room: *present is 0 for a bus without; cd and ad receive 8 and 4 delays, levels[7] receives feedback, damp, g, gain,
+ *   dry, wet, cross; any pointer may be NULL.
+ *   s2r_get_bus_room_state / s2r_set_bus_room_state: the flat array above.  S2R_ERR_INVALID for a capacity below, or a count other
+ *   than, s2r_room_state_floats, a NULL buffer, and on a bus without a room; S2R_ERR_PATCH_RANGE for a value to restore that is not
+ *   finite.
+ *   Single-device handles (a NULL or a device-list handle: S2R_ERR_INVALID from all six).
+ *   s2r_room_reference: the rule on the host (no device, no handle): x_lr and out_lr are [frames][2]; state, the flat array, is
+ *   updated in place; out_lr may be NULL.  Range checks as above, and of the state as the state setter's; S2R_ERR_INVALID for a NULL
+ *   cd, ad or state, or a NULL x_lr with frames > 0.
+ *   s2r_room_design: the public Freeverb tunings — combs 1116, 1188, 1277, 1356, 1422, 1491, 1557, 1617; allpasses 556, 441, 341,
+ *   225; spread 23, at 44.1 kHz — each times sample_rate / 44100 * size in binary64, rounded to nearest.  S2R_ERR_PATCH_RANGE when a
+ *   result leaves the range or an argument is not a finite number > 0; S2R_ERR_INVALID for a NULL pointer.  Device parity is always
+ *   against the stored delays, never against this function. */
+#define S2R_ROOM_COMBS 8u
+#define S2R_ROOM_ALLPASSES 4u
+#define S2R_ROOM_MIN_DELAY 64u
+#define S2R_ROOM_MAX_DELAY 8192u
+int s2r_set_bus_room(s2r_synth *s, uint32_t bus, const uint32_t *cd, const uint32_t *ad, uint32_t spread, float feedback, float damp, float g, float gain,
+                     float dry, float wet, float cross);
+int s2r_clear_bus_room(s2r_synth *s, uint32_t bus);
+int s2r_set_bus_room_params(s2r_synth *s, uint32_t bus, float feedback, float damp, float g, float gain, float dry, float wet, float cross);
+int s2r_get_bus_room(const s2r_synth *s, uint32_t bus, uint32_t *present, uint32_t *cd, uint32_t *ad, uint32_t *spread, float *levels);
+int s2r_get_bus_room_state(s2r_synth *s, uint32_t bus, float *state, size_t capacity);
+int s2r_set_bus_room_state(s2r_synth *s, uint32_t bus, const float *state, size_t count);
+size_t s2r_room_state_floats(const uint32_t *cd, const uint32_t *ad, uint32_t spread);
+int s2r_room_reference(const uint32_t *cd, const uint32_t *ad, uint32_t spread, float feedback, float damp, float g, float gain, float dry, float wet,
+                       float cross, const float *x_lr, uint32_t frames, float *state, float *out_lr);
+int s2r_room_design(double sample_rate, double size, uint32_t *cd, uint32_t *ad, uint32_t *spread);
 
 /* BUILD-DEFINED master section (the reference's Synth::sample returns one stream; DESIGN.md 4.17 gives the op sequence): the last stage
  * of the chain send -> effect -> return -> master, on the device the bus signals are already on.  Every bus b in [0, S2R_MAX_BUSES) has

@@ -21,7 +21,8 @@ SOURCES = ["s2r_render_onepole_square.hip", "s2r_render_onepole_saw.hip", "s2r_r
            "s2r_render_general_triangle.hip", "s2r_render_general_sine.hip", "s2r_render_general_bank.hip",
            "s2r_aux.hip", "s2r_eq.hip", "s2r_chorus.hip", "s2r_delay.hip", "s2r_fx.hip", "s2r_master.hip", "s2r_limiter.hip", "s2r_host.cpp", "s2r_post.cpp", "s2r_rules.cpp", "s2r_patch.cpp",
            "s2r_stream.cpp",
-           "s2r_dyn.hip"]       # (last: every object in front of it keeps the place in the library it had before the dynamics came)
+           "s2r_dyn.hip",       # (behind the rest: every object in front of it keeps the place in the library it had before the dynamics came)
+           "s2r_room.hip"]      # (last, likewise, since the room came)
 HEADERS = ["s2r_device.h", "s2r_math.h", "s2r_patch.h", "s2r_voices.h", "s2r_kern_common.h", "s2r_render_onepole.inc",
            "s2r_render_general.inc", "s2r_post.h", "s2r_post_route.h", "s2r_rules.h"]
 
@@ -51,7 +52,7 @@ PER_FILE_FLAGS = {}
 for _f in ("s2r_render_general_square.hip", "s2r_render_general_saw.hip", "s2r_render_general_triangle.hip", "s2r_render_general_sine.hip",
            "s2r_render_general_bank.hip"):
     PER_FILE_FLAGS[_f] = ["-ftrivial-auto-var-init=zero"]
-# Eight translation units are compiled with the back end's resource-usage remarks, and _check_resources() fails the build when a
+# Nine translation units are compiled with the back end's resource-usage remarks, and _check_resources() fails the build when a
 # kernel named here went to scratch or spilled, or when fewer kernels report than the file instantiates.  Per source file: the
 # substrings that name its checked kernels; how many reports are expected — ("at least", n), ("exactly", n), or ("each", None):
 # one or more of every name — and why so many; the figures that must be "0"; and what the kernels keep where it belongs.  (The
@@ -72,6 +73,9 @@ RESOURCE_CHECKS = {
     # one walker lane with its gain, minimum and sixteen targets; a frame of the key and a frame of the bus per producer / consumer lane
     "s2r_dyn.hip": (("s2r_dyn_kernel",), ("exactly", 1), "one kernel",
                     (_SCRATCH, _VSPILL, _SSPILL), "its gain and the targets read ahead must stay in registers, curve and tiles in LDS"),
+    # a frame of one line per lane: the line's frame loaded a tile ahead, a walker's f; a consumer lane's four allpass frames loaded ahead
+    "s2r_room.hip": (("s2r_room_kernel",), ("exactly", 1), "one kernel",
+                     (_SCRATCH, _VSPILL, _SSPILL), "its frames loaded ahead and the combs' filter values must stay in registers, tiles in LDS"),
     # one frame of the chorus per thread: both channels, up to eight voices, two taps each
     "s2r_chorus.hip": (("s2r_chorus_kernel",), ("exactly", 1), "one kernel",
                        (_SCRATCH, _VSPILL, _SSPILL), "its phases, taps and sums must stay in registers"),
@@ -98,6 +102,11 @@ if _EQ_SERIAL:
 _DYN_SERIAL = os.environ.get("S2R_DYN_SERIAL") == "1"
 if _DYN_SERIAL:
     PER_FILE_FLAGS["s2r_dyn.hip"] = PER_FILE_FLAGS["s2r_dyn.hip"] + ["-DS2R_DYN_SERIAL"]
+# S2R_ROOM_SERIAL=1 likewise builds the room kernel's obvious form (one thread per comb does its own loads, recursion and stores;
+# csrc/s2r_room.hip, CHANGELOG) into libs2r_roomserial.so, for tools/room_time.py.  Never the product build.
+_ROOM_SERIAL = os.environ.get("S2R_ROOM_SERIAL") == "1"
+if _ROOM_SERIAL:
+    PER_FILE_FLAGS["s2r_room.hip"] = PER_FILE_FLAGS["s2r_room.hip"] + ["-DS2R_ROOM_SERIAL"]
 # S2R_OPT=O3 in the environment builds the same sources at -O3 into libs2r_o3.so (tools and tests that compare the two
 # optimisation levels; the product is -O2).
 if os.environ.get("S2R_OPT") == "O3":
@@ -117,6 +126,9 @@ elif _EQ_SERIAL:
 elif _DYN_SERIAL:
     LIB = os.path.join(HERE, "libs2r_dynserial.so")
     OBJ_DIR_NAME = "_build_dynserial"
+elif _ROOM_SERIAL:
+    LIB = os.path.join(HERE, "libs2r_roomserial.so")
+    OBJ_DIR_NAME = "_build_roomserial"
 else:
     OBJ_DIR_NAME = "_build"
 

@@ -516,6 +516,31 @@ struct S2rDyn {
 // pointer, in == out, line == next, a key or n_buses past its range or no dynamics at all among the call's buses
 hipError_t s2r_launch_bus_dyn(const S2rDyn &a, hipStream_t stream);
 
+// The per-bus room behind the convolution reverb: eight damped combs and four allpasses per channel.  A bus's line
+// holds its state in the checkpoint's layout (s2r.h); `next` receives the state the next call starts from (the host swaps the two).
+// Line l of the 24: comb i of channel c is l = c * 8 + i, allpass j is l = 16 + c * 4 + j; len[l] frames at off[l] of the state, a
+// comb's f behind its line.  The frames a line gains inside the call go to row l of `work`, [24][wstride], and are read from there.
+#define S2R_ROOM_TILE 32u         // frames of one pass of the kernel: half the least delay, so that a tile's reads are a tile old when they are issued
+#define S2R_ROOM_LINES 24u
+struct S2rRoomBus {
+    const float *line;            // the state; null: no room on this bus: it is copied from `in` to `out`
+    float *next;                  // the same size, not `line`
+    float *work;                  // [S2R_ROOM_LINES][wstride]
+    uint32_t len[S2R_ROOM_LINES], off[S2R_ROOM_LINES];
+    uint32_t floats;              // of the state
+    float feedback, damp, d1, g, gain, dry, wet, cross;
+};
+struct S2rRoom {
+    S2rRoomBus bus[S2R_MAX_BUSES];
+    const float *in;              // [n_buses][2 * frames]: what the stage in front wrote; bus-major, L, R interleaved inside a bus
+    float *out;                   // the same layout, not `in`
+    uint32_t n_buses, frames, wstride;
+};
+// one kernel: the outputs and next states of the buses with a room, the other buses unchanged; hipErrorInvalidValue for a null
+// pointer, in == out, line == next, a line outside its range or its state, frames > wstride, n_buses past
+// S2R_MAX_BUSES or no room at all among the call's buses
+hipError_t s2r_launch_bus_room(const S2rRoom &a, hipStream_t stream);
+
 // The master section of s2r_fill_master: the stems of a call, post-effect, each times its return's ramp, added in
 // bus order from +0.0, times the master fader's ramp; and the call's meters.  gain at frame i of the CALL: r0 + (float)i * dr (the
 // product rounded, then the sum); a pair that did not move has dr = +0.0.

@@ -2947,6 +2947,80 @@ int s2r_get_bus_dynamics_meter(const s2r_synth *s, uint32_t bus, float *min_gain
     return S2R_OK;
 }
 
+// ---- per-bus rooms: the third insert, behind the last stem stage ----
+static int room_levels(s2r_synth *s, const char *who, uint32_t bus, float feedback, float damp, float g, float gain, float dry, float wet, float cross) {
+    if (bus >= S2R_MAX_BUSES || !room_levels_in_range(feedback, damp, g, gain, dry, wet, cross))
+        return set_err(s, S2R_ERR_PATCH_RANGE, "%s: bus %u, feedback %g, damp %g, g %g, gain %g, dry %g, wet %g, cross %g: feedback in [0, 1), g in (-1, 1), "
+                       "the others in [0, 1], the bus below %u", who, bus, (double)feedback, (double)damp, (double)g, (double)gain, (double)dry, (double)wet,
+                       (double)cross, S2R_MAX_BUSES);
+    return S2R_OK;
+}
+
+// the bus in range, a single-device handle, and the bus carries a room
+static int room_bus(s2r_synth *s, uint32_t bus, const char *who) {
+    if (bus >= S2R_MAX_BUSES) return set_err(s, S2R_ERR_PATCH_RANGE, "%s: bus %u, below %u", who, bus, S2R_MAX_BUSES);
+    S2R_TRY(post_handle(s, who, "bus rooms are"));
+    if (!s->post.room[bus].present()) return set_err(s, S2R_ERR_INVALID, "%s: bus %u carries no room", who, bus);
+    return S2R_OK;
+}
+
+int s2r_set_bus_room(s2r_synth *s, uint32_t bus, const uint32_t *cd, const uint32_t *ad, uint32_t spread, float feedback, float damp, float g, float gain,
+                     float dry, float wet, float cross) {
+    S2R_TRY(room_levels(s, "s2r_set_bus_room", bus, feedback, damp, g, gain, dry, wet, cross));
+    if (!room_delays_in_range(cd, ad, spread))
+        return set_err(s, S2R_ERR_PATCH_RANGE, "s2r_set_bus_room: bus %u, spread %u: every delay, and every delay plus the spread, in [%u, %u]", bus, spread,
+                       S2R_ROOM_MIN_DELAY, S2R_ROOM_MAX_DELAY);
+    S2R_TRY(post_handle(s, "s2r_set_bus_room", "bus rooms are"));
+    if (!cd || !ad) return set_err(s, S2R_ERR_INVALID, "s2r_set_bus_room: no delays");
+    const float levels[7] = {feedback, damp, g, gain, dry, wet, cross};
+    return stem_set(s, "s2r_set_bus_room", [&](const S2rPostCtx &c) { return s->post.set_room(c, bus, cd, ad, spread, levels); });
+}
+
+int s2r_clear_bus_room(s2r_synth *s, uint32_t bus) {
+    if (bus >= S2R_MAX_BUSES) return set_err(s, S2R_ERR_PATCH_RANGE, "s2r_clear_bus_room: bus %u, below %u", bus, S2R_MAX_BUSES);
+    S2R_TRY(post_handle(s, "s2r_clear_bus_room", "bus rooms are"));
+    return stem_set(s, "s2r_clear_bus_room", [&](const S2rPostCtx &c) { return s->post.set_room(c, bus, nullptr, nullptr, 0, nullptr); });
+}
+
+int s2r_set_bus_room_params(s2r_synth *s, uint32_t bus, float feedback, float damp, float g, float gain, float dry, float wet, float cross) {
+    S2R_TRY(room_levels(s, "s2r_set_bus_room_params", bus, feedback, damp, g, gain, dry, wet, cross));
+    S2R_TRY(room_bus(s, bus, "s2r_set_bus_room_params"));
+    const float levels[7] = {feedback, damp, g, gain, dry, wet, cross};
+    return stem_set(s, "s2r_set_bus_room_params", [&](const S2rPostCtx &) { s->post.set_room_params(bus, levels); return hipSuccess; });   // (the state stays)
+}
+
+int s2r_get_bus_room(const s2r_synth *s, uint32_t bus, uint32_t *present, uint32_t *cd, uint32_t *ad, uint32_t *spread, float *levels) {
+    if (bus >= S2R_MAX_BUSES) return S2R_ERR_PATCH_RANGE;
+    if (!s || !s->kids.empty() || s->parent) return S2R_ERR_INVALID;
+    const S2rPostChain::BusRoom &f = s->post.room[bus];
+    put(present, f.present() ? 1u : 0u); put(spread, f.spread);
+    if (cd) std::memcpy(cd, f.cd, sizeof f.cd);
+    if (ad) std::memcpy(ad, f.ad, sizeof f.ad);
+    if (levels) { const float l[7] = {f.feedback, f.damp, f.g, f.gain, f.dry, f.wet, f.cross}; std::memcpy(levels, l, sizeof l); }
+    return S2R_OK;
+}
+
+static int room_state(s2r_synth *s, uint32_t bus, float *get, const float *set, size_t count, const char *who) {
+    S2R_TRY(room_bus(s, bus, who));
+    const size_t n = s->post.room[bus].floats;
+    if (set ? count != n : count < n) return set_err(s, S2R_ERR_INVALID, "%s: the state of bus %u is %zu floats, not %zu", who, bus, n, count);
+    if (!get && !set) return set_err(s, S2R_ERR_INVALID, "%s: null buffer", who);
+    if (set) for (size_t k = 0; k < n; k++) if (!std::isfinite(set[k])) return set_err(s, S2R_ERR_PATCH_RANGE, "%s: value %zu of the state is not finite", who, k);
+    S2R_QUIESCE(s);
+    S2R_HIP(s, hipSetDevice(s->device));
+    S2R_HIP(s, hipStreamSynchronize(s->stream));
+    S2R_HIP(s, s->post.room_state(post_ctx(s), bus, get, set));
+    return S2R_OK;
+}
+
+int s2r_get_bus_room_state(s2r_synth *s, uint32_t bus, float *state, size_t capacity) {
+    return room_state(s, bus, state, nullptr, capacity, "s2r_get_bus_room_state");
+}
+
+int s2r_set_bus_room_state(s2r_synth *s, uint32_t bus, const float *state, size_t count) {
+    return room_state(s, bus, nullptr, state, state ? count : (size_t)-1, "s2r_set_bus_room_state");
+}
+
 // ---- per-bus choruses: in front of the delays ----
 int s2r_set_bus_chorus(s2r_synth *s, uint32_t bus, uint32_t voices, float base, float depth, uint32_t phase_inc, uint32_t spread, float dry, float wet) {
     if ((voices && !chorus_in_range(voices, base, depth, dry, wet)) || bus >= S2R_MAX_BUSES)
@@ -3644,6 +3718,11 @@ extern "C" uint32_t s2r_debug_eq_tile(void) { return S2R_EQ_TILE; }
 extern "C" float s2r_debug_dyn_ms(const s2r_synth *s) { return s && s->timing ? s->post.dyn_insert.timer.ms : -1.0f; }
 extern "C" int s2r_debug_dyn_allocated(const s2r_synth *s) { return s && (s->post.dyn_insert.stage || s->post.dyn_curves || s->post.dyn_meter) ? 1 : 0; }
 extern "C" uint32_t s2r_debug_dyn_tile(void) { return S2R_DYN_TILE; }
+// ... of the buses' room kernel in that fill: 0 when it ran none (tools/room_time.py); whether the handle holds the rooms' staging buffer;
+// and the frames of one pass of the kernel (tests/test_gpu_room.py picks its call lengths around it)
+extern "C" float s2r_debug_bus_room_ms(const s2r_synth *s) { return s && s->timing ? s->post.room_insert.timer.ms : -1.0f; }
+extern "C" int s2r_debug_room_allocated(const s2r_synth *s) { return s && s->post.room_insert.stage ? 1 : 0; }
+extern "C" uint32_t s2r_debug_room_tile(void) { return S2R_ROOM_TILE; }
 // ... of the buses' chorus kernel in that fill: 0 when it ran none (tools/chorus_time.py)
 extern "C" float s2r_debug_bus_chorus_ms(const s2r_synth *s) { return s && s->timing ? s->post.stem[S2R_STEM_CHORUS].timer.ms : -1.0f; }
 // ... of the buses' delay kernel in that fill: 0 when it ran none (tools/delay_time.py)

@@ -1,4 +1,4 @@
-// s2r_post.cpp — the post-mix chain (s2r_post.h): the EQs, the dynamics, the stem stages (choruses, delays, reverbs), master section, master limiter.  Compiled with hipcc, -ffp-contract=off.
+// s2r_post.cpp — the post-mix chain (s2r_post.h): the EQs, the dynamics, the stem stages (choruses, delays, reverbs), the rooms, master section, master limiter.  Compiled with hipcc, -ffp-contract=off.
 #include "s2r_post.h"
 #include "s2r_rules.h"
 
@@ -69,6 +69,7 @@ hipError_t S2rPostChain::prepare(const S2rPostCtx &c, uint32_t n_buses, uint32_t
         for (uint32_t b = 0; b < n_buses; b++) if (bus(k, b).present()) call.on[k] = true;       // (an effect on a bus past the call's is idle in it)
     for (uint32_t b = 0; b < n_buses; b++) if (eq[b].present()) call.eq = true;                      // (and so is an EQ)
     for (uint32_t b = 0; b < n_buses; b++) if (dyn_runs(b, n_buses)) call.dyn = true;                // (and dynamics, also when their key bus is past the call's)
+    for (uint32_t b = 0; b < n_buses; b++) if (room[b].present()) call.room = true;                  // (and a room)
     call.limited = master_fill && limiter.lookahead != 0;
     if (call.master) {                                           // the device copy of the stems and the pinned rows of block partials
         if (!master.stage) POST_HIP(hipMalloc((void **)&master.stage, (size_t)2 * S2R_MAX_BUSES * c.max_frames * sizeof(float)));
@@ -81,13 +82,13 @@ hipError_t S2rPostChain::prepare(const S2rPostCtx &c, uint32_t n_buses, uint32_t
     }
     float *stages[S2R_STEM_STAGES];
     for (int k = 0; k < S2R_STEM_STAGES; k++) stages[k] = stem[k].stage;
-    call.route = s2r_post_route_dyn(call, s2r_post_route_eq(call, s2r_post_route(call, stages, master.stage, limiter.in, c.bus_out_dev, c.out_host_dev), eq_insert.stage),
-                                    dyn_insert.stage);
+    call.route = s2r_post_route_room(call, s2r_post_route_dyn(call, s2r_post_route_eq(call, s2r_post_route(call, stages, master.stage, limiter.in, c.bus_out_dev, c.out_host_dev),
+                                                                                      eq_insert.stage), dyn_insert.stage), room_insert.stage);
     return hipSuccess;
 }
 
 hipError_t S2rPostChain::launch(const S2rPostCtx &c, const S2rPostCall &call) {
-    const S2rPostRouteDyn &r = call.route; const float fn = (float)call.frames;
+    const S2rPostRouteRoom &r = call.route; const float fn = (float)call.frames;
     if (call.eq) {                                               // once per call, over all of its frames, in front of every stem stage
         S2rEq a{};
         for (uint32_t b = 0; b < call.n_buses; b++) {
@@ -151,6 +152,19 @@ hipError_t S2rPostChain::launch(const S2rPostCtx &c, const S2rPostCall &call) {
         a.stage = r.stem[S2R_STEM_REVERB].in; a.out = r.stem[S2R_STEM_REVERB].out; a.n_buses = call.n_buses; a.frames = call.frames; a.pstride = fx_pstride(c);
         POST_TIMED(c, stem[S2R_STEM_REVERB].timer, s2r_launch_bus_fx(a, c.stream));
     }
+    if (call.room) {                                             // the last stem writer: every bus as the stages in front left it
+        S2rRoom a{};
+        for (uint32_t b = 0; b < call.n_buses; b++) {
+            const BusRoom &f = room[b];
+            if (!f.present()) continue;
+            S2rRoomBus &d = a.bus[b];
+            d.line = f.now(); d.next = f.next(); d.work = f.work; d.floats = (uint32_t)f.floats;
+            room_layout(f.cd, f.ad, f.spread, d.len, d.off);
+            d.feedback = f.feedback; d.damp = f.damp; d.d1 = f.d1; d.g = f.g; d.gain = f.gain; d.dry = f.dry; d.wet = f.wet; d.cross = f.cross;
+        }
+        a.in = r.room.in; a.out = r.room.out; a.n_buses = call.n_buses; a.frames = call.frames; a.wstride = c.max_frames;
+        POST_TIMED(c, room_insert.timer, s2r_launch_bus_room(a, c.stream));
+    }
     if (call.master) {                                           // returns, master fader and the meters' block partials
         S2rMaster m{};
         m.stage = r.master_in; m.out = r.master_out; m.stems = r.master_stems; m.partials = master.partials_dev;
@@ -186,6 +200,7 @@ void S2rPostChain::commit(const S2rPostCall &call) {
         if (call.on[k]) for (uint32_t b = 0; b < call.n_buses; b++) if (bus(k, b).present()) bus(k, b).flip();
     if (call.on[S2R_STEM_CHORUS])                                // ... and the choruses' phases
         for (uint32_t b = 0; b < call.n_buses; b++) if (chorus[b].present()) chorus[b].phase += chorus[b].phase_inc * call.frames;
+    if (call.room) for (uint32_t b = 0; b < call.n_buses; b++) if (room[b].present()) room[b].flip();   // ... and the rooms' lines
     if (call.master) {                                           // the block partials in block order, and applied = target
         Master &ms = master;
         const uint32_t n_ch = (call.n_buses + 1u) * 2u, n_blocks = (call.frames + S2R_METER_BLOCK - 1u) / S2R_METER_BLOCK;
@@ -214,11 +229,12 @@ void S2rPostChain::commit(const S2rPostCall &call) {
     }
 }
 
-// a stage that the fill could have run and did not reads 0; a panned fill leaves all seven values alone, a bus fill the master's two
+// a stage that the fill could have run and did not reads 0; a panned fill leaves all eight values alone, a bus fill the master's two
 hipError_t S2rPostChain::read_timers(const S2rPostCall &call) {
     if (call.n_buses) { eq_insert.timer.ms = 0.0f; if (call.eq) POST_HIP(eq_insert.timer.read()); }
     if (call.n_buses) { dyn_insert.timer.ms = 0.0f; if (call.dyn) POST_HIP(dyn_insert.timer.read()); }
     if (call.n_buses) for (int k = 0; k < S2R_STEM_STAGES; k++) { stem[k].timer.ms = 0.0f; if (call.on[k]) POST_HIP(stem[k].timer.read()); }
+    if (call.n_buses) { room_insert.timer.ms = 0.0f; if (call.room) POST_HIP(room_insert.timer.read()); }
     if (call.master) {
         POST_HIP(master.timer.read());
         limiter.timer.ms = 0.0f;
@@ -228,13 +244,15 @@ hipError_t S2rPostChain::read_timers(const S2rPostCall &call) {
 }
 
 void S2rPostChain::release() {
-    for (uint32_t b = 0; b < S2R_MAX_BUSES; b++) { drop(eq[b]); drop(dyn[b]); drop(chorus[b]); drop(delay[b]); drop(fx[b]); }
+    for (uint32_t b = 0; b < S2R_MAX_BUSES; b++) { drop(eq[b]); drop(dyn[b]); drop(chorus[b]); drop(delay[b]); drop(fx[b]); drop(room[b]); }
     for (Stem &st : stem) { if (st.stage) (void)hipFree(st.stage); st.timer.destroy(); }
     if (eq_insert.stage) (void)hipFree(eq_insert.stage);
     eq_insert.timer.destroy();
     for (float *p : {dyn_insert.stage, dyn_curves}) if (p) (void)hipFree(p);
     if (dyn_meter) (void)hipHostFree(dyn_meter);
     dyn_insert.timer.destroy();
+    if (room_insert.stage) (void)hipFree(room_insert.stage);
+    room_insert.timer.destroy();
     for (float *p : {master.stage, limiter.state[0], limiter.state[1], limiter.in}) if (p) (void)hipFree(p);
     for (float *p : {master.partials, limiter.partials}) if (p) (void)hipHostFree(p);
     for (S2rPostTimer *t : {&master.timer, &limiter.timer}) t->destroy();
@@ -280,6 +298,33 @@ hipError_t S2rPostChain::set_dyn(const S2rPostCtx &c, uint32_t bus, uint32_t key
 
 hipError_t S2rPostChain::dyn_state(const S2rPostCtx &c, uint32_t bus, float *get, const float *set) {
     POST_HIP(dyn[bus].copy(get, set, 0, 1u, c.stream));
+    return hipStreamSynchronize(c.stream);
+}
+
+// The work area is the room's own: allocated with its lines, so that a refused set leaves the earlier room whole.  The kernel writes a
+// work row before it reads it, and writes the state's other copy whole: only the current copy needs its +0.0.
+hipError_t S2rPostChain::set_room(const S2rPostCtx &c, uint32_t bus, const uint32_t *cd, const uint32_t *ad, uint32_t spread, const float levels[7]) {
+    if (!cd) { drop(room[bus]); return hipSuccess; }
+    BusRoom f;
+    std::memcpy(f.cd, cd, sizeof f.cd); std::memcpy(f.ad, ad, sizeof f.ad); f.spread = spread;
+    f.history = 0;
+    const size_t floats = room_state_count(cd, ad, spread);
+    const hipError_t e = replace(c, room_insert.stage, room[bus], f, floats, [&](BusRoom &n) {
+        return hipMalloc((void **)&n.work, (size_t)S2R_ROOM_LINES * c.max_frames * sizeof(float));
+    });
+    if (e == hipSuccess) set_room_params(bus, levels);
+    return e;
+}
+
+void S2rPostChain::set_room_params(uint32_t bus, const float levels[7]) {
+    BusRoom &f = room[bus];
+    f.feedback = levels[0]; f.damp = levels[1]; f.g = levels[2]; f.gain = levels[3]; f.dry = levels[4]; f.wet = levels[5]; f.cross = levels[6];
+    volatile float d1 = 1.0f - f.damp;                           // rounded to binary32, once
+    f.d1 = d1;
+}
+
+hipError_t S2rPostChain::room_state(const S2rPostCtx &c, uint32_t bus, float *get, const float *set) {
+    POST_HIP(room[bus].copy(get, set, 0, room[bus].floats, c.stream));
     return hipStreamSynchronize(c.stream);
 }
 

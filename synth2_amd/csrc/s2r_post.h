@@ -1,6 +1,6 @@
 // s2r_post.h — the chain behind the bus mixdown of s2r_fill_buses and s2r_fill_master: the buses' equalisers and their
 // dynamics (4.22), two inserts at the head of the stem stages (s2r_post_route.h) — the buses' choruses (4.20), their feedback delays
-// (4.19), their convolution reverbs (4.16) —, the master section (4.17) and the master limiter (4.18), in that order.  The chain owns what the seven stages own
+// (4.19), their convolution reverbs (4.16) —, the buses' rooms (4.23), an insert behind them, the master section (4.17) and the master limiter (4.18), in that order.  The chain owns what the eight stages own
 // and knows nothing of the handle: its functions take a S2rPostCtx and return the HIP error.  Per call: prepare, launch, — the caller's synchronise — commit, read_timers.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -89,6 +89,16 @@ struct S2rPostChain {
     float *dyn_meter = nullptr, *dyn_meter_dev = nullptr;        // pinned and device-mapped: [S2R_MAX_BUSES]
     // the bus's dynamics run in a call of n_buses buses: both the bus and its key are among them
     bool dyn_runs(uint32_t b, uint32_t n_buses) const { return b < n_buses && dyn[b].present() && dyn[b].key < n_buses; }
+    // The rooms (s2r_set_bus_room): lines in the checkpoint's layout (s2r.h): per channel each comb's line and its f, then each allpass's
+    // line.  The third insert, behind the last stem stage (s2r_post_route_room), with a staging buffer and a timer of its own; a room also
+    // owns the work area its kernel keeps a call's frames of the 24 lines in
+    struct BusRoom : S2rBusLine {
+        uint32_t cd[S2R_ROOM_COMBS] = {}, ad[S2R_ROOM_ALLPASSES] = {}, spread = 0;
+        float feedback = 0.0f, damp = 0.0f, d1 = 0.0f, g = 0.0f, gain = 0.0f, dry = 0.0f, wet = 0.0f, cross = 0.0f;
+        float *work = nullptr;                   // [S2R_ROOM_LINES][max_frames]
+        void free() { if (work) (void)hipFree(work); work = nullptr; S2rBusLine::free(); }
+    } room[S2R_MAX_BUSES];
+    Stem room_insert;                            // (its timer: tools/room_time.py)
     // stage k's effect on a bus, as far as the stages are alike
     S2rBusLine &bus(int k, uint32_t b) { S2rBusLine *const of[S2R_STEM_STAGES] = {&chorus[b], &delay[b], &fx[b]}; return *of[k]; }
     const S2rBusLine &bus(int k, uint32_t b) const { return const_cast<S2rPostChain *>(this)->bus(k, b); }
@@ -135,6 +145,10 @@ struct S2rPostChain {
     // curve null: removes the bus's dynamics; keep_state: the parameters alone, on a bus that has them
     hipError_t set_dyn(const S2rPostCtx &c, uint32_t bus, uint32_t key, const float *curve, float a_att, float a_rel, bool keep_state);
     hipError_t dyn_state(const S2rPostCtx &c, uint32_t bus, float *get, const float *set);     // the one float, out or in
+    // cd null: removes the bus's room; the levels alone on a bus that has one: set_room_params
+    hipError_t set_room(const S2rPostCtx &c, uint32_t bus, const uint32_t *cd, const uint32_t *ad, uint32_t spread, const float levels[7]);
+    void set_room_params(uint32_t bus, const float levels[7]);
+    hipError_t room_state(const S2rPostCtx &c, uint32_t bus, float *get, const float *set);    // the whole state, out or in
     hipError_t set_chorus(const S2rPostCtx &c, uint32_t bus, uint32_t voices, float base, float depth, uint32_t phase_inc, uint32_t spread, float dry, float wet);
     hipError_t set_delay(const S2rPostCtx &c, uint32_t bus, uint32_t delay_frames, float feedback, float cross, float dry, float wet);
     hipError_t set_reverb(const S2rPostCtx &c, uint32_t bus, const float *ir_l, const float *ir_r, uint32_t n_taps, float dry, float wet);

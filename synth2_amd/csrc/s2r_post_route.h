@@ -18,6 +18,11 @@ struct S2rPostRoute {
 struct S2rPostRouteDyn : S2rPostRoute {
     struct { float *in, *out; } dyn;
 };
+// ... and the room insert at the other end, behind the last stem stage (s2r_post_route_room): null unless the call runs it.  Again a
+// struct of its own on top
+struct S2rPostRouteRoom : S2rPostRouteDyn {
+    struct { float *in, *out; } room;
+};
 struct S2rPostCall {                             // one fill, as prepare leaves it
     uint32_t n_buses = 0, frames = 0;            // n_buses 0: a panned fill, which runs no stage
     bool master = false, stems = false;          // s2r_fill_master; the caller wants the stems too
@@ -25,7 +30,8 @@ struct S2rPostCall {                             // one fill, as prepare leaves 
     bool limited = false;                        // a master fill with the limiter set
     bool eq = false;                             // an EQ sits on one of the call's buses
     bool dyn = false;                            // dynamics sit on one of the call's buses, their key bus among them too
-    S2rPostRouteDyn route{};
+    bool room = false;                           // a room sits on one of the call's buses
+    S2rPostRouteRoom route{};
 };
 
 // Who reads and writes what, the only place that decides it.  The combine writes into the first stem stage that runs, each running
@@ -71,5 +77,21 @@ inline S2rPostRouteDyn s2r_post_route_dyn(const S2rPostCall &call, const S2rPost
     float *&writer = call.eq ? r.eq.out : r.combine_out;
     r.dyn.in = dyn_stage; r.dyn.out = writer;
     writer = dyn_stage;
+    return r;
+}
+
+// The room is the third insert, at the other end of the stem chain: the last stem writer of a call that runs it.  Applied to the route
+// after s2r_post_route_dyn: the room reads its own staging buffer and writes where the last stem writer would have written — the call's
+// destination: the pinned output in a bus fill, the master's device stage in a master fill —, and that writer — the last running stem
+// stage, else the dynamics, else the EQ, else the combine — is redirected into the room's buffer.  A call without a room, or without
+// buses, keeps its route as it is, with a null room pair.
+inline S2rPostRouteRoom s2r_post_route_room(const S2rPostCall &call, const S2rPostRouteDyn &route, float *room_stage) {
+    S2rPostRouteRoom r{};
+    static_cast<S2rPostRouteDyn &>(r) = route;
+    if (!call.room || !call.n_buses) return r;
+    float **writer = call.dyn ? &r.dyn.out : call.eq ? &r.eq.out : &r.combine_out;
+    for (int k = 0; k < S2R_STEM_STAGES; k++) if (call.on[k]) writer = &r.stem[k].out;
+    r.room.in = room_stage; r.room.out = *writer;
+    *writer = room_stage;
     return r;
 }

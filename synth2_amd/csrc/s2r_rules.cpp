@@ -216,6 +216,93 @@ float s2r_dynamics_coef(double ms, double sample_rate) {
     return (float)std::exp(-1.0 / (ms * 0.001 * sample_rate));
 }
 
+// ---- per-bus room reverb: eight damped feedback combs in parallel, four allpasses in series, per channel ----
+size_t s2r_room_state_floats(const uint32_t *cd, const uint32_t *ad, uint32_t spread) {
+    if (!cd || !ad || !room_delays_in_range(cd, ad, spread)) return 0;
+    return room_state_count(cd, ad, spread);
+}
+
+int s2r_room_reference(const uint32_t *cd, const uint32_t *ad, uint32_t spread, float feedback, float damp, float g, float gain, float dry, float wet,
+                       float cross, const float *x_lr, uint32_t frames, float *state, float *out_lr) {
+    if (!room_delays_in_range(cd, ad, spread) || !room_levels_in_range(feedback, damp, g, gain, dry, wet, cross)) return S2R_ERR_PATCH_RANGE;
+    if (!cd || !ad || !state || (!x_lr && frames)) return S2R_ERR_INVALID;
+    const size_t total = room_state_count(cd, ad, spread);
+    for (size_t k = 0; k < total; k++) if (!std::isfinite(state[k])) return S2R_ERR_PATCH_RANGE;
+    uint32_t len[24], off[24];
+    room_layout(cd, ad, spread, len, off);
+    const float d1 = 1.0f - damp;
+    // every line as history followed by the call's frames: frame n sits at len + n, what it reads at n
+    std::vector<float> w[24];
+    float f[16];
+    for (uint32_t l = 0; l < 24u; l++) {
+        w[l].assign((size_t)len[l] + frames, 0.0f);
+        std::memcpy(w[l].data(), state + off[l], (size_t)len[l] * sizeof(float));
+        if (l < 16u) f[l] = state[off[l] + len[l]];
+    }
+    for (uint32_t n = 0; n < frames; n++) {
+        const float xl = x_lr[2 * (size_t)n], xr = x_lr[2 * (size_t)n + 1];
+        const float s = xl + xr;
+        const float in = s * gain;
+        float v[2];
+        for (uint32_t c = 0; c < 2u; c++) {
+            float acc = 0.0f;
+            for (uint32_t i = 0; i < S2R_ROOM_COMBS; i++) {
+                const uint32_t l = c * 8u + i;
+                const float o = w[l][n];
+                const float p = o * d1;
+                const float q = f[l] * damp;
+                f[l] = p + q;
+                const float r = f[l] * feedback;
+                w[l][(size_t)len[l] + n] = in + r;
+                acc = acc + o;
+            }
+            for (uint32_t j = 0; j < S2R_ROOM_ALLPASSES; j++) {
+                const uint32_t l = 16u + c * 4u + j;
+                const float b = w[l][n];
+                const float y = b - acc;
+                const float m = b * g;
+                w[l][(size_t)len[l] + n] = acc + m;
+                acc = y;
+            }
+            v[c] = acc;
+        }
+        if (out_lr) {
+            const float x[2] = {xl, xr};
+            for (uint32_t c = 0; c < 2u; c++) {
+                const float a = dry * x[c];
+                const float p = wet * v[c];
+                const float q = cross * v[1u - c];
+                const float t = p + q;
+                out_lr[2 * (size_t)n + c] = a + t;
+            }
+        }
+    }
+    for (uint32_t l = 0; l < 24u; l++) {
+        std::memcpy(state + off[l], w[l].data() + frames, (size_t)len[l] * sizeof(float));
+        if (l < 16u) state[off[l] + len[l]] = f[l];
+    }
+    return S2R_OK;
+}
+
+int s2r_room_design(double sample_rate, double size, uint32_t *cd, uint32_t *ad, uint32_t *spread) {
+    static const double kComb[S2R_ROOM_COMBS] = {1116, 1188, 1277, 1356, 1422, 1491, 1557, 1617}, kAll[S2R_ROOM_ALLPASSES] = {556, 441, 341, 225};
+    if (!(sample_rate > 0.0) || !(size > 0.0) || !std::isfinite(sample_rate) || !std::isfinite(size)) return S2R_ERR_PATCH_RANGE;
+    if (!cd || !ad || !spread) return S2R_ERR_INVALID;
+    const double k = sample_rate / 44100.0 * size;
+    auto scaled = [&](double v, uint32_t &to) {                  // to nearest, ties to even, as the host rounds
+        const double r = std::nearbyint(v * k);
+        if (!(r >= 0.0 && r <= (double)S2R_ROOM_MAX_DELAY)) return false;
+        to = (uint32_t)r;
+        return true;
+    };
+    uint32_t c[S2R_ROOM_COMBS], a[S2R_ROOM_ALLPASSES], sp;
+    for (uint32_t i = 0; i < S2R_ROOM_COMBS; i++) if (!scaled(kComb[i], c[i])) return S2R_ERR_PATCH_RANGE;
+    for (uint32_t j = 0; j < S2R_ROOM_ALLPASSES; j++) if (!scaled(kAll[j], a[j])) return S2R_ERR_PATCH_RANGE;
+    if (!scaled(23.0, sp) || !room_delays_in_range(c, a, sp)) return S2R_ERR_PATCH_RANGE;
+    std::memcpy(cd, c, sizeof c); std::memcpy(ad, a, sizeof a); *spread = sp;
+    return S2R_OK;
+}
+
 // ---- the master section: energies by the adjacent-pair tree over blocks of S2R_METER_BLOCK frames ----
 static float master_energy(const float *v, uint32_t frames) {     // v: one channel of an interleaved pair (stride 2)
     float total = 0.0f;

@@ -53,6 +53,38 @@ static inline bool dyn_in_range(const float *curve, float a_att, float a_rel) {
     return true;
 }
 static inline bool dyn_state_in_range(float y) { return std::isfinite(y) && y >= 0.0f; }
+// a bus's room: every effective delay — cd[i], cd[i] + spread, ad[j], ad[j] + spread — in [S2R_ROOM_MIN_DELAY,
+// S2R_ROOM_MAX_DELAY]; feedback in [0, 1), damp in [0, 1], g in (-1, 1), gain, dry, wet and cross in [0, 1].  Null delays pass: the
+// caller refuses them by another name.
+static inline bool room_delay_in_range(uint32_t d, uint32_t spread) {
+    return spread <= S2R_ROOM_MAX_DELAY && d >= S2R_ROOM_MIN_DELAY && d <= S2R_ROOM_MAX_DELAY && d + spread <= S2R_ROOM_MAX_DELAY;
+}
+static inline bool room_delays_in_range(const uint32_t *cd, const uint32_t *ad, uint32_t spread) {
+    if (spread > S2R_ROOM_MAX_DELAY) return false;
+    for (uint32_t i = 0; i < S2R_ROOM_COMBS && cd; i++) if (!room_delay_in_range(cd[i], spread)) return false;
+    for (uint32_t j = 0; j < S2R_ROOM_ALLPASSES && ad; j++) if (!room_delay_in_range(ad[j], spread)) return false;
+    return true;
+}
+static inline bool room_levels_in_range(float feedback, float damp, float g, float gain, float dry, float wet, float cross) {
+    return feedback >= 0.0f && feedback < 1.0f && unit_in_range(damp) && g > -1.0f && g < 1.0f && unit_in_range(gain) && unit_in_range(dry) &&
+           unit_in_range(wet) && unit_in_range(cross);
+}
+// the floats of a room's state, for delays in range
+static inline size_t room_state_count(const uint32_t *cd, const uint32_t *ad, uint32_t spread) {
+    size_t n = 0;
+    for (uint32_t i = 0; i < S2R_ROOM_COMBS; i++) n += 2u * (size_t)cd[i] + spread + 2u;
+    for (uint32_t j = 0; j < S2R_ROOM_ALLPASSES; j++) n += 2u * (size_t)ad[j] + spread;
+    return n;
+}
+// Where the 24 lines sit in that array and how long they are.  Line c * 8 + i is comb i of channel c, line 16 + c * 4 + j allpass j;
+// a comb's f follows its line.
+static inline void room_layout(const uint32_t *cd, const uint32_t *ad, uint32_t spread, uint32_t len[24], uint32_t off[24]) {
+    uint32_t at = 0;
+    for (uint32_t c = 0; c < 2u; c++) {
+        for (uint32_t i = 0; i < S2R_ROOM_COMBS; i++) { const uint32_t l = c * 8u + i; len[l] = cd[i] + c * spread; off[l] = at; at += len[l] + 1u; }
+        for (uint32_t j = 0; j < S2R_ROOM_ALLPASSES; j++) { const uint32_t l = 16u + c * 4u + j; len[l] = ad[j] + c * spread; off[l] = at; at += len[l]; }
+    }
+}
 
 // The voice mixer's gain rules, inline: the host's per-voice loops compile them in — a call per voice into s2r_rules.cpp showed as 10
 // to 15 us of host time per fill of 65 536 voices (profiles/r12/post_chain.txt).  s2r_rules.cpp exports them under their s2r.h names.

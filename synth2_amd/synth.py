@@ -41,6 +41,10 @@ CHORUS_MAX_DELAY = 4095.0                   # S2R_CHORUS_MAX_DELAY
 EQ_MAX_BANDS = 4                            # S2R_EQ_MAX_BANDS
 EQ_PEAK, EQ_LOW_SHELF, EQ_HIGH_SHELF, EQ_LOWPASS, EQ_HIGHPASS = range(5)     # s2r_eq_kind
 DYN_CURVE_POINTS = 513                      # S2R_DYN_CURVE_POINTS
+ROOM_COMBS = 8                              # S2R_ROOM_COMBS
+ROOM_ALLPASSES = 4                          # S2R_ROOM_ALLPASSES
+ROOM_MIN_DELAY = 64                         # S2R_ROOM_MIN_DELAY
+ROOM_MAX_DELAY = 8192                       # S2R_ROOM_MAX_DELAY
 IR_SEGMENT = 256                            # S2R_IR_SEGMENT
 METER_BLOCK = 256                           # S2R_METER_BLOCK
 LIMITER_MAX_LOOKAHEAD = 1024                # S2R_LIMITER_MAX_LOOKAHEAD
@@ -125,6 +129,7 @@ class SampleRateKhz(int):
 
 _lib = None
 _f32p = C.POINTER(C.c_float)
+_u32p = C.POINTER(C.c_uint32)
 
 
 def lib_path():
@@ -237,6 +242,15 @@ def load_library():
         "s2r_dynamics_reference": (C.c_int, [_f32p, C.c_float, C.c_float, _f32p, _f32p, C.c_uint32, _f32p, _f32p, _f32p]),
         "s2r_dynamics_curve": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_double, _f32p]),
         "s2r_dynamics_coef": (C.c_float, [C.c_double, C.c_double]),
+        "s2r_set_bus_room": (C.c_int, [H, C.c_uint32, _u32p, _u32p, C.c_uint32] + [C.c_float] * 7),
+        "s2r_clear_bus_room": (C.c_int, [H, C.c_uint32]),
+        "s2r_set_bus_room_params": (C.c_int, [H, C.c_uint32] + [C.c_float] * 7),
+        "s2r_get_bus_room": (C.c_int, [H, C.c_uint32, _u32p, _u32p, _u32p, _u32p, _f32p]),
+        "s2r_get_bus_room_state": (C.c_int, [H, C.c_uint32, _f32p, C.c_size_t]),
+        "s2r_set_bus_room_state": (C.c_int, [H, C.c_uint32, _f32p, C.c_size_t]),
+        "s2r_room_state_floats": (C.c_size_t, [_u32p, _u32p, C.c_uint32]),
+        "s2r_room_reference": (C.c_int, [_u32p, _u32p, C.c_uint32] + [C.c_float] * 7 + [_f32p, C.c_uint32, _f32p, _f32p]),
+        "s2r_room_design": (C.c_int, [C.c_double, C.c_double, _u32p, _u32p, _u32p]),
         "s2r_set_bus_return": (C.c_int, [H, C.c_uint32, C.c_float]),
         "s2r_get_bus_return": (C.c_int, [H, C.c_uint32, _f32p, _f32p]),
         "s2r_set_master_fader": (C.c_int, [H, C.c_float]),
@@ -492,6 +506,56 @@ def dynamics_curve(threshold_db, ratio, knee_db=0.0, makeup_db=0.0):
 def dynamics_coef(ms, sample_rate):
     """the retention coefficient of a time constant (s2r_dynamics_coef): float32 exp(-1 / (ms * 0.001 * sample_rate)), 0 for ms == 0"""
     return np.float32(load_library().s2r_dynamics_coef(float(ms), float(sample_rate)))
+
+
+def _room_delays(cd, ad, who):
+    c = np.ascontiguousarray(cd, dtype=np.uint32)
+    a = np.ascontiguousarray(ad, dtype=np.uint32)
+    if c.shape != (ROOM_COMBS,) or a.shape != (ROOM_ALLPASSES,):
+        raise ValueError(who + ": cd is [%d] and ad [%d] uint32" % (ROOM_COMBS, ROOM_ALLPASSES))
+    return c, a
+
+
+def _room_levels(feedback, damp, g, gain, dry, wet, cross):
+    return [C.c_float(float(np.float32(v))) for v in (feedback, damp, g, gain, dry, wet, cross)]
+
+
+def room_state_floats(cd, ad, spread):
+    """the floats of a room's state (s2r_room_state_floats): 0 for delays out of range"""
+    c, a = _room_delays(cd, ad, "room_state_floats")
+    return int(load_library().s2r_room_state_floats(c.ctypes.data_as(_u32p), a.ctypes.data_as(_u32p), int(spread)))
+
+
+def room_reference(cd, ad, spread, feedback, damp, g, gain, dry, wet, cross, x, state=None):
+    """the bus room's rule on the host (s2r_room_reference): cd [8] and ad [4] delays and the spread in frames, the seven levels, x
+    [frames, 2] float32, state the flat float32 array of room_state_floats entries carried in (None: +0.0, as after a set); returns
+    (out [frames, 2], the state after the call)"""
+    c, a = _room_delays(cd, ad, "room_reference")
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    if x.ndim != 2 or x.shape[1] != 2:
+        raise ValueError("room_reference: x is [frames, 2]")
+    L = load_library()
+    n = int(L.s2r_room_state_floats(c.ctypes.data_as(_u32p), a.ctypes.data_as(_u32p), int(spread)))
+    st = np.zeros(n, dtype=np.float32) if state is None else np.array(state, dtype=np.float32).ravel()
+    if n and st.size != n:
+        raise ValueError("room_reference: the state is %d floats, not %d" % (n, st.size))
+    out = np.empty_like(x)
+    rc = L.s2r_room_reference(c.ctypes.data_as(_u32p), a.ctypes.data_as(_u32p), int(spread), *_room_levels(feedback, damp, g, gain, dry, wet, cross),
+                              x.ctypes.data_as(_f32p), x.shape[0], st.ctypes.data_as(_f32p), out.ctypes.data_as(_f32p))
+    if rc != S2R_OK:
+        raise S2rError(rc, L.s2r_status_string(rc).decode())
+    return out, st
+
+
+def room_design(sample_rate, size=1.0):
+    """the public Freeverb tunings scaled by sample_rate / 44100 * size (s2r_room_design): (cd [8] uint32, ad [4] uint32, spread)"""
+    c = np.empty(ROOM_COMBS, dtype=np.uint32)
+    a = np.empty(ROOM_ALLPASSES, dtype=np.uint32)
+    sp = C.c_uint32()
+    rc = load_library().s2r_room_design(float(sample_rate), float(size), c.ctypes.data_as(_u32p), a.ctypes.data_as(_u32p), C.byref(sp))
+    if rc != S2R_OK:
+        raise S2rError(rc, load_library().s2r_status_string(rc).decode())
+    return c, a, sp.value
 
 
 def master_reference(stems, r0, r1, m0, m1):
@@ -1067,6 +1131,55 @@ class Synth:
     @staticmethod
     def dynamics_coef(ms, sample_rate):
         return dynamics_coef(ms, sample_rate)
+
+    # --- per-bus room reverb (build-defined; s2r.h: s2r_set_bus_room) ---
+    def set_bus_room(self, bus, cd, ad, spread, feedback, damp, g=0.5, gain=0.015, dry=1.0, wet=1.0, cross=0.0):
+        """an algorithmic reverb on a bus of sample_buses and sample_master, the last stem writer: eight damped feedback combs cd [8]
+        and four allpasses ad [4] per channel, delays in frames in [ROOM_MIN_DELAY, ROOM_MAX_DELAY], the right channel's `spread`
+        frames longer (room_design makes a set); feedback in [0, 1), damp in [0, 1], g in (-1, 1), the others in [0, 1].  Replaces any
+        earlier room of the bus and zeroes its state."""
+        c, a = _room_delays(cd, ad, "set_bus_room")
+        self._check(self.L.s2r_set_bus_room(self.h, int(bus), c.ctypes.data_as(_u32p), a.ctypes.data_as(_u32p), int(spread),
+                                            *_room_levels(feedback, damp, g, gain, dry, wet, cross)))
+
+    def clear_bus_room(self, bus):
+        """removes the bus's room: the bus passes again, bit for bit"""
+        self._check(self.L.s2r_clear_bus_room(self.h, int(bus)))
+
+    def set_bus_room_params(self, bus, feedback, damp, g, gain, dry, wet, cross):
+        """the seven levels alone; delays and state stay, so room size and damping move between calls with no restart"""
+        self._check(self.L.s2r_set_bus_room_params(self.h, int(bus), *_room_levels(feedback, damp, g, gain, dry, wet, cross)))
+
+    def get_bus_room(self, bus):
+        """(cd [8] uint32, ad [4] uint32, spread, feedback, damp, g, gain, dry, wet, cross) of the bus's room; None for a bus without"""
+        present, sp = C.c_uint32(), C.c_uint32()
+        c = np.empty(ROOM_COMBS, dtype=np.uint32)
+        a = np.empty(ROOM_ALLPASSES, dtype=np.uint32)
+        lv = np.empty(7, dtype=np.float32)
+        self._check(self.L.s2r_get_bus_room(self.h, int(bus), C.byref(present), c.ctypes.data_as(_u32p), a.ctypes.data_as(_u32p), C.byref(sp),
+                                            lv.ctypes.data_as(_f32p)))
+        return (c, a, sp.value) + tuple(lv) if present.value else None
+
+    def bus_room_state(self, bus):
+        """the state the bus's room carries into the next call, flat float32 (s2r.h gives the layout) — the checkpoint companion of
+        bus_eq_state"""
+        r = self.get_bus_room(bus)
+        n = room_state_floats(r[0], r[1], r[2]) if r else 1
+        out = np.empty(n, dtype=np.float32)
+        self._check(self.L.s2r_get_bus_room_state(self.h, int(bus), out.ctypes.data_as(_f32p), out.size))
+        return out
+
+    def set_bus_room_state(self, bus, state):
+        st = np.ascontiguousarray(state, dtype=np.float32).ravel()
+        self._check(self.L.s2r_set_bus_room_state(self.h, int(bus), st.ctypes.data_as(_f32p), st.size))
+
+    @staticmethod
+    def room_reference(cd, ad, spread, feedback, damp, g, gain, dry, wet, cross, x, state=None):
+        return room_reference(cd, ad, spread, feedback, damp, g, gain, dry, wet, cross, x, state)
+
+    @staticmethod
+    def room_design(sample_rate, size=1.0):
+        return room_design(sample_rate, size)
 
     # --- the master section (build-defined; s2r.h: s2r_fill_master) ---
     def set_bus_return(self, bus, level=1.0):
