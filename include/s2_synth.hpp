@@ -236,6 +236,26 @@ class Synth {
         return s2r_room_reference(cd, ad, spread, feedback, damp, g, gain, dry, wet, cross, x_lr, frames, state, out_lr);
     }
     static int room_design(double sample_rate, double size, uint32_t *cd, uint32_t *ad, uint32_t *spread) { return s2r_room_design(sample_rate, size, cd, ad, spread); }
+    // per-bus drive behind the dynamics (build-defined; s2r.h: s2r_set_bus_drive): a waveshaper at four times the bus rate — a table
+    // curve[S2R_DRIVE_CURVE_POINTS], finite, entry 512 its value at 0 (drive_curve makes one), pre in [0, S2R_DRIVE_MAX_PRE], dry and wet
+    // in [0, 1]; the bus comes out S2R_DRIVE_LATENCY frames late; in sample_buses and sample_master only
+    void set_bus_drive(uint32_t bus, const float *curve, float pre, float dry, float wet) { check(s2r_set_bus_drive(h_, bus, curve, pre, dry, wet)); }
+    void clear_bus_drive(uint32_t bus) { check(s2r_clear_bus_drive(h_, bus)); }
+    void set_bus_drive_params(uint32_t bus, const float *curve_or_null, float pre, float dry, float wet) {   // the history stays
+        check(s2r_set_bus_drive_params(h_, bus, curve_or_null, pre, dry, wet));
+    }
+    bool get_bus_drive(uint32_t bus, float *curve, size_t capacity, float *pre, float *dry, float *wet) const {
+        uint32_t present = 0;
+        check(s2r_get_bus_drive(h_, bus, &present, curve, capacity, pre, dry, wet));
+        return present != 0;
+    }
+    void bus_drive_history(uint32_t bus, float *lr, size_t capacity) { check(s2r_get_bus_drive_history(h_, bus, lr, capacity)); }
+    void set_bus_drive_history(uint32_t bus, const float *lr, size_t count) { check(s2r_set_bus_drive_history(h_, bus, lr, count)); }
+    static int drive_reference(const float *curve, float pre, float dry, float wet, const float *x_lr, uint32_t frames, float *history, float *out_lr) {
+        return s2r_drive_reference(curve, pre, dry, wet, x_lr, frames, history, out_lr);
+    }
+    static int drive_curve(uint32_t kind, double amount, float *table) { return s2r_drive_curve(kind, amount, table); }
+    static int drive_taps(float *h) { return s2r_drive_taps(h); }
 
     // the master section (build-defined; s2r.h: s2r_fill_master): a return level per bus and a master fader, each in [0, 1] and each
     // reaching its target as a ramp across the next sample_master call, and the meters of that call — in sample_master only

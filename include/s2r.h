@@ -46,7 +46,9 @@ extern "C" {
  * s2r_set_bus_eq_state, s2r_eq_reference, s2r_eq_design, s2r_set_bus_dynamics, s2r_clear_bus_dynamics, s2r_set_bus_dynamics_params,
  * s2r_get_bus_dynamics, s2r_get_bus_dynamics_state, s2r_set_bus_dynamics_state, s2r_get_bus_dynamics_meter, s2r_dynamics_reference,
  * s2r_dynamics_curve, s2r_dynamics_coef, s2r_set_bus_room, s2r_clear_bus_room, s2r_set_bus_room_params, s2r_get_bus_room,
- * s2r_get_bus_room_state, s2r_set_bus_room_state, s2r_room_state_floats, s2r_room_reference, s2r_room_design. */
+ * s2r_get_bus_room_state, s2r_set_bus_room_state, s2r_room_state_floats, s2r_room_reference, s2r_room_design, s2r_set_bus_drive,
+ * s2r_clear_bus_drive, s2r_set_bus_drive_params, s2r_get_bus_drive, s2r_get_bus_drive_history, s2r_set_bus_drive_history,
+ * s2r_drive_reference, s2r_drive_taps, s2r_drive_curve. */
 #define S2R_ABI_VERSION 4
 
 typedef enum {
@@ -666,6 +668,74 @@ size_t s2r_room_state_floats(const uint32_t *cd, const uint32_t *ad, uint32_t sp
 int s2r_room_reference(const uint32_t *cd, const uint32_t *ad, uint32_t spread, float feedback, float damp, float g, float gain, float dry, float wet,
                        float cross, const float *x_lr, uint32_t frames, float *state, float *out_lr);
 int s2r_room_design(double sample_rate, double size, uint32_t *cd, uint32_t *ad, uint32_t *spread);
+
+/* BUILD-DEFINED per-bus drive (the reference has no effects): a waveshaper — overdrive, saturation, a clipper, a
+ * wavefolder — behind the dynamics, oversampled so that the harmonics it makes above the bus rate's Nyquist do not fold back:
+ * combine -> eq -> dynamics -> drive -> chorus -> delay -> reverb -> room -> master -> limiter.  The bus goes up to
+ * S2R_DRIVE_OVERSAMPLE = 4 times its rate through the interpolator g, through a table there, and back down through the decimator h.
+ * h[0 .. 64] is the library's one prototype, S2R_DRIVE_TAPS = 65 taps: the design of s2r_fill_oversampled's decimator — a
+ * Blackman-windowed sinc, cutoff 0.115 cycles per oversampled sample, unit DC gain, computed in binary64 and rounded once — and
+ * symmetric on bits; s2r_drive_taps reports it; g[k] = 4 h[k], exact.  The two filters' delays add up to 64 oversampled samples:
+ * S2R_DRIVE_LATENCY = 16 frames.  A bus b in [0, S2R_MAX_BUSES) may carry a drive: a table curve[S2R_DRIVE_CURVE_POINTS = 1025], finite
+ * — entry 512 is the curve's value at 0, entry 512 +- i its value at +- i / 512 —, pre in [0, S2R_DRIVE_MAX_PRE], dry and wet in
+ * [0, 1].  State: the bus's last S2R_DRIVE_HISTORY = 32 input frames, [32][2], oldest first, L then R, +0.0 right after a set.  For
+ * frame n of a call and channel c, with x the bus as it enters the stage (negative indices are history), every sum from +0.0 in the
+ * index order written:
+ *   m = 4 q + p, p = 0..3:   u[m] = sum over j = 0.. while p + 4 j <= 64 of  fl(g[p + 4 j] * x_c[q - j])
+ *   t = fl(pre * u[m]);  a = fl(min(|t|, 1) * 512);  i = min((uint32)a, 511);  fr = fl(a - (float)i)
+ *   s = (t < 0) ? -1 : +1;  c0 = curve[512 + s * i];  c1 = curve[512 + s * (i + 1)]
+ *   w[m] = fl(c0 + fl(fr * fl(c1 - c0)))
+ *   v[n] = sum over k = 0..64 of fl(h[k] * w[4 n - k])
+ *   out_c[n] = fl(fl(dry * x_c[n - 16]) + fl(wet * v[n]))
+ * binary32 throughout, every operation rounded on its own (no fma), denormals kept, nothing skipped for a zero coefficient.
+ * Non-finite bus samples are outside the contract.  The table is indexed by sign and magnitude, so that a small signal keeps its
+ * relative precision.  v[n] reads w[4 n - 64 .. 4 n], that is x[n - 32 .. n]: a frame depends on 33 input frames and on nothing the
+ * stage wrote.  The dry path is delayed by S2R_DRIVE_LATENCY with the wet: a bus with a drive is 16 frames late against a bus without
+ * one, and nothing compensates the others.  After a call that returns S2R_OK the state is the last 32 frames of history ++ call: calls
+ * of any lengths concatenate.  The stage runs once per call over all its frames, after every event segment and rows slice has been
+ * mixed.  A drive on a bus >= the call's n_buses is idle in that call, its state untouched.  A bus without a drive passes bit for bit,
+ * -0.0 included.  A refused or failed call leaves the state where it was.  ONLY s2r_fill_buses and s2r_fill_master apply it.  A handle
+ * on which none was ever set launches what it launched before and allocates nothing for it; device memory is allocated when a drive is
+ * set (S2R_ERR_OUT_OF_MEMORY when that fails, and the earlier drive is kept), never in a fill.
+ *   s2r_set_bus_drive: replaces any earlier drive of the bus and zeroes the history.  S2R_ERR_PATCH_RANGE for a bus >= S2R_MAX_BUSES,
+ *   a level outside its range, a NaN or a table entry that is not finite (checked before the handle is looked at; nothing is
+ *   changed); S2R_ERR_INVALID for a NULL curve.
+ *   s2r_clear_bus_drive removes it (S2R_OK on a bus without).
+ *   s2r_set_bus_drive_params: the levels, and the table unless curve is NULL; the history stays, so a curve or a level moves between
+ *   calls with no restart.  S2R_ERR_INVALID on a bus without a drive.
+ *   s2r_get_bus_drive: *present is 0 for a bus without; curve, when not NULL, receives the table (S2R_ERR_INVALID for a capacity
+ *   below S2R_DRIVE_CURVE_POINTS on a bus with a drive); any pointer may be NULL.
+ *   s2r_get_bus_drive_history / s2r_set_bus_drive_history: the state above, 64 floats.  S2R_ERR_INVALID for a capacity below, or a
+ *   count other than, 64, a NULL buffer, and on a bus without a drive; S2R_ERR_PATCH_RANGE for a value to restore that is not finite.
+ *   Single-device handles (a NULL or a device-list handle: S2R_ERR_INVALID from all six).
+ *   s2r_drive_reference: the rule on the host (no device, no handle): x_lr and out_lr are [frames][2]; history, [32][2], is updated in
+ *   place; out_lr may be NULL.  Range checks as above, and of the history as its setter's; S2R_ERR_INVALID for a NULL curve or
+ *   history, or a NULL x_lr with frames > 0.
+ *   s2r_drive_taps: h[65].  S2R_ERR_INVALID for NULL.
+ *   s2r_drive_curve: a table by design, with u = i / 512 - 1, in binary64 and rounded once — S2R_DRIVE_LINEAR: u, exact, whatever the
+ *   amount; S2R_DRIVE_TANH: tanh(a u) / tanh(a); S2R_DRIVE_HARD: clamp(a u) to [-1, 1]; S2R_DRIVE_CUBIC: 1.5 v - 0.5 v^3 with v =
+ *   clamp(a u); S2R_DRIVE_FOLD: the triangle of period 4 and height 1 through 0 at a u, 1 - |((a u + 1) mod 4) - 2|, the mod in [0, 4).
+ *   S2R_ERR_PATCH_RANGE for another kind or, but for the linear kind, an amount outside [S2R_DRIVE_MIN_AMOUNT, S2R_DRIVE_MAX_AMOUNT]
+ *   or a NaN; S2R_ERR_INVALID for a NULL table.  tanh is the host's.  Device parity is always against the stored table, never against
+ *   this function. */
+#define S2R_DRIVE_OVERSAMPLE 4u
+#define S2R_DRIVE_TAPS 65u
+#define S2R_DRIVE_LATENCY 16u
+#define S2R_DRIVE_HISTORY 32u
+#define S2R_DRIVE_CURVE_POINTS 1025u
+#define S2R_DRIVE_MAX_PRE 1024.0f
+#define S2R_DRIVE_MIN_AMOUNT 0.015625
+#define S2R_DRIVE_MAX_AMOUNT 64.0
+typedef enum { S2R_DRIVE_LINEAR = 0, S2R_DRIVE_TANH = 1, S2R_DRIVE_HARD = 2, S2R_DRIVE_CUBIC = 3, S2R_DRIVE_FOLD = 4 } s2r_drive_kind;
+int s2r_set_bus_drive(s2r_synth *s, uint32_t bus, const float *curve, float pre, float dry, float wet);
+int s2r_clear_bus_drive(s2r_synth *s, uint32_t bus);
+int s2r_set_bus_drive_params(s2r_synth *s, uint32_t bus, const float *curve, float pre, float dry, float wet);
+int s2r_get_bus_drive(const s2r_synth *s, uint32_t bus, uint32_t *present, float *curve, size_t capacity, float *pre, float *dry, float *wet);
+int s2r_get_bus_drive_history(s2r_synth *s, uint32_t bus, float *lr, size_t capacity);
+int s2r_set_bus_drive_history(s2r_synth *s, uint32_t bus, const float *lr, size_t count);
+int s2r_drive_reference(const float *curve, float pre, float dry, float wet, const float *x_lr, uint32_t frames, float *history, float *out_lr);
+int s2r_drive_taps(float *h);
+int s2r_drive_curve(uint32_t kind, double amount, float *table);
 
 /* BUILD-DEFINED master section (the reference's Synth::sample returns one stream; DESIGN.md 4.17 gives the op sequence): the last stage
  * of the chain send -> effect -> return -> master, on the device the bus signals are already on.  Every bus b in [0, S2R_MAX_BUSES) has

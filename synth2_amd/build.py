@@ -22,7 +22,8 @@ SOURCES = ["s2r_render_onepole_square.hip", "s2r_render_onepole_saw.hip", "s2r_r
            "s2r_aux.hip", "s2r_eq.hip", "s2r_chorus.hip", "s2r_delay.hip", "s2r_fx.hip", "s2r_master.hip", "s2r_limiter.hip", "s2r_host.cpp", "s2r_post.cpp", "s2r_rules.cpp", "s2r_patch.cpp",
            "s2r_stream.cpp",
            "s2r_dyn.hip",       # (behind the rest: every object in front of it keeps the place in the library it had before the dynamics came)
-           "s2r_room.hip"]      # (last, likewise, since the room came)
+           "s2r_room.hip",      # (likewise, since the room came)
+           "s2r_drive.hip"]     # (last, likewise, since the drive came)
 HEADERS = ["s2r_device.h", "s2r_math.h", "s2r_patch.h", "s2r_voices.h", "s2r_kern_common.h", "s2r_render_onepole.inc",
            "s2r_render_general.inc", "s2r_post.h", "s2r_post_route.h", "s2r_rules.h"]
 
@@ -52,7 +53,7 @@ PER_FILE_FLAGS = {}
 for _f in ("s2r_render_general_square.hip", "s2r_render_general_saw.hip", "s2r_render_general_triangle.hip", "s2r_render_general_sine.hip",
            "s2r_render_general_bank.hip"):
     PER_FILE_FLAGS[_f] = ["-ftrivial-auto-var-init=zero"]
-# Nine translation units are compiled with the back end's resource-usage remarks, and _check_resources() fails the build when a
+# Ten translation units are compiled with the back end's resource-usage remarks, and _check_resources() fails the build when a
 # kernel named here went to scratch or spilled, or when fewer kernels report than the file instantiates.  Per source file: the
 # substrings that name its checked kernels; how many reports are expected — ("at least", n), ("exactly", n), or ("each", None):
 # one or more of every name — and why so many; the figures that must be "0"; and what the kernels keep where it belongs.  (The
@@ -76,6 +77,10 @@ RESOURCE_CHECKS = {
     # a frame of one line per lane: the line's frame loaded a tile ahead, a walker's f; a consumer lane's four allpass frames loaded ahead
     "s2r_room.hip": (("s2r_room_kernel",), ("exactly", 1), "one kernel",
                      (_SCRATCH, _VSPILL, _SSPILL), "its frames loaded ahead and the combs' filter values must stay in registers, tiles in LDS"),
+    # a frame per lane: both channels' seventeen inputs and four sums in phase 1, two sums in phase 2, half of each filter's taps in
+    # SGPRs (156 VGPRs, 102 SGPRs, 14 480 bytes of LDS)
+    "s2r_drive.hip": (("s2r_drive_kernel",), ("exactly", 1), "one kernel",
+                      (_SCRATCH, _VSPILL, _SSPILL), "its inputs and sums must stay in registers, tiles, table and phase planes in LDS"),
     # one frame of the chorus per thread: both channels, up to eight voices, two taps each
     "s2r_chorus.hip": (("s2r_chorus_kernel",), ("exactly", 1), "one kernel",
                        (_SCRATCH, _VSPILL, _SSPILL), "its phases, taps and sums must stay in registers"),
@@ -107,6 +112,16 @@ if _DYN_SERIAL:
 _ROOM_SERIAL = os.environ.get("S2R_ROOM_SERIAL") == "1"
 if _ROOM_SERIAL:
     PER_FILE_FLAGS["s2r_room.hip"] = PER_FILE_FLAGS["s2r_room.hip"] + ["-DS2R_ROOM_SERIAL"]
+# S2R_DRIVE_SERIAL=1 likewise builds the drive kernel's obvious form (one lane per output frame recomputes its own 65 oversampled
+# samples from global memory, no LDS; csrc/s2r_drive.hip, CHANGELOG) into libs2r_driveserial.so, for tools/drive_time.py; and
+# S2R_DRIVE_INTERLEAVED=1 the tiled form with w[] interleaved in LDS instead of in four phase planes, into libs2r_driveinterleaved.so,
+# timed once to show what the planes buy.  Never the product build.
+_DRIVE_SERIAL = os.environ.get("S2R_DRIVE_SERIAL") == "1"
+_DRIVE_INTERLEAVED = not _DRIVE_SERIAL and os.environ.get("S2R_DRIVE_INTERLEAVED") == "1"
+if _DRIVE_SERIAL:
+    PER_FILE_FLAGS["s2r_drive.hip"] = PER_FILE_FLAGS["s2r_drive.hip"] + ["-DS2R_DRIVE_SERIAL"]
+if _DRIVE_INTERLEAVED:
+    PER_FILE_FLAGS["s2r_drive.hip"] = PER_FILE_FLAGS["s2r_drive.hip"] + ["-DS2R_DRIVE_INTERLEAVED"]
 # S2R_OPT=O3 in the environment builds the same sources at -O3 into libs2r_o3.so (tools and tests that compare the two
 # optimisation levels; the product is -O2).
 if os.environ.get("S2R_OPT") == "O3":
@@ -129,6 +144,12 @@ elif _DYN_SERIAL:
 elif _ROOM_SERIAL:
     LIB = os.path.join(HERE, "libs2r_roomserial.so")
     OBJ_DIR_NAME = "_build_roomserial"
+elif _DRIVE_SERIAL:
+    LIB = os.path.join(HERE, "libs2r_driveserial.so")
+    OBJ_DIR_NAME = "_build_driveserial"
+elif _DRIVE_INTERLEAVED:
+    LIB = os.path.join(HERE, "libs2r_driveinterleaved.so")
+    OBJ_DIR_NAME = "_build_driveinterleaved"
 else:
     OBJ_DIR_NAME = "_build"
 

@@ -541,6 +541,28 @@ struct S2rRoom {
 // S2R_MAX_BUSES or no room at all among the call's buses
 hipError_t s2r_launch_bus_room(const S2rRoom &a, hipStream_t stream);
 
+// The per-bus drive behind the dynamics: 4x up through g, a table, back down through h.  A bus's line holds its last
+// S2R_DRIVE_HISTORY input frames, [32][2]; `next` receives the state the next call starts from (the host swaps the two).  Feed-forward:
+// a tile of S2R_DRIVE_TILE output frames needs the 32 input frames in front of it and nothing another tile wrote.
+#define S2R_DRIVE_HALF_TAPS 33u   // (S2R_DRIVE_TAPS + 1) / 2
+#define S2R_DRIVE_TILE 240u       // output frames of one workgroup: with the S2R_DRIVE_LATENCY frames in front of them, a frame per lane
+struct S2rDriveBus {
+    const float *curve;           // [S2R_DRIVE_CURVE_POINTS] in device memory; null: no drive on this bus: it is copied from `in` to `out`
+    const float *line;            // [S2R_DRIVE_HISTORY][2]
+    float *next;                  // the same size, not `line`
+    float pre, dry, wet;
+};
+struct S2rDrive {
+    S2rDriveBus bus[S2R_MAX_BUSES];
+    float h[S2R_DRIVE_HALF_TAPS], g[S2R_DRIVE_HALF_TAPS];    // taps 0 .. 32 of each filter, which is symmetric on bits; in the kernel's arguments: wave-uniform, read with scalar loads
+    const float *in;              // [n_buses][2 * frames]: what the stage in front wrote; bus-major, L, R interleaved inside a bus
+    float *out;                   // the same layout, not `in`
+    uint32_t n_buses, frames;
+};
+// one kernel, (tiles, n_buses) workgroups: the outputs and next states of the buses with a drive, the other buses unchanged;
+// hipErrorInvalidValue for a null pointer, in == out, line == next, n_buses past S2R_MAX_BUSES or no drive at all among the call's buses
+hipError_t s2r_launch_bus_drive(const S2rDrive &a, hipStream_t stream);
+
 // The master section of s2r_fill_master: the stems of a call, post-effect, each times its return's ramp, added in
 // bus order from +0.0, times the master fader's ramp; and the call's meters.  gain at frame i of the CALL: r0 + (float)i * dr (the
 // product rounded, then the sum); a pair that did not move has dr = +0.0.

@@ -2733,7 +2733,10 @@ static int post_handle(const s2r_synth *s, const char *who, const char *what) {
 }
 
 // the words in which the entries of a stem stage differ
-static const struct { const char *one, *are; } kStemWords[S2R_STEM_STAGES] = {{"chorus", "bus choruses are"}, {"delay", "bus delays are"}, {"reverb", "bus reverbs are"}};
+static const struct { const char *one, *are; } kStemWords[S2R_STEM_STAGES + 1] = {{"chorus", "bus choruses are"}, {"delay", "bus delays are"}, {"reverb", "bus reverbs are"},
+                                                                                  {"drive", "bus drives are"}};
+// (the drive is no stem stage — s2r_post_route.h —, but its entries are guarded like theirs: S2rPostChain::bus answers for it at this index)
+static const S2rStemStage kDriveEntry = S2R_STEM_STAGES;
 
 // The guard of an entry that reads or changes the effect one bus carries: the bus in range, a single-device handle, and the bus
 // carries one.  `who` null: a getter, which answers for a bus without one too and leaves the handle's error text alone; `named`:
@@ -3723,6 +3726,11 @@ extern "C" uint32_t s2r_debug_dyn_tile(void) { return S2R_DYN_TILE; }
 extern "C" float s2r_debug_bus_room_ms(const s2r_synth *s) { return s && s->timing ? s->post.room_insert.timer.ms : -1.0f; }
 extern "C" int s2r_debug_room_allocated(const s2r_synth *s) { return s && s->post.room_insert.stage ? 1 : 0; }
 extern "C" uint32_t s2r_debug_room_tile(void) { return S2R_ROOM_TILE; }
+// ... of the buses' drive kernel in that fill: 0 when it ran none (tools/drive_time.py); whether the handle holds the drives' staging
+// buffer or their tables; and the output frames of one workgroup of the kernel (tests/test_gpu_drive.py picks its call lengths around it)
+extern "C" float s2r_debug_bus_drive_ms(const s2r_synth *s) { return s && s->timing ? s->post.drive_insert.timer.ms : -1.0f; }
+extern "C" int s2r_debug_drive_allocated(const s2r_synth *s) { return s && (s->post.drive_insert.stage || s->post.drive_curves) ? 1 : 0; }
+extern "C" uint32_t s2r_debug_drive_tile(void) { return S2R_DRIVE_TILE; }
 // ... of the buses' chorus kernel in that fill: 0 when it ran none (tools/chorus_time.py)
 extern "C" float s2r_debug_bus_chorus_ms(const s2r_synth *s) { return s && s->timing ? s->post.stem[S2R_STEM_CHORUS].timer.ms : -1.0f; }
 // ... of the buses' delay kernel in that fill: 0 when it ran none (tools/delay_time.py)
@@ -3815,3 +3823,58 @@ int s2r_voice_pool_query(const s2r_voice_pool *p, uint32_t voice_index, s2r_voic
 }
 
 }  // extern "C"
+
+// ---- per-bus drives: the fourth insert, behind the dynamics and in front of the choruses.  At the end of the file, like
+// the kernel at the end of the link order: every function in front keeps the place it had ----
+static int drive_values(s2r_synth *s, const char *who, uint32_t bus, const float *curve, float pre, float dry, float wet) {
+    if (bus >= S2R_MAX_BUSES || !drive_in_range(curve, pre, dry, wet))
+        return set_err(s, S2R_ERR_PATCH_RANGE, "%s: bus %u, pre %g, dry %g, wet %g: %u finite curve entries, pre in [0, %g], dry and wet in [0, 1], the bus below %u",
+                       who, bus, (double)pre, (double)dry, (double)wet, S2R_DRIVE_CURVE_POINTS, (double)S2R_DRIVE_MAX_PRE, S2R_MAX_BUSES);
+    return S2R_OK;
+}
+
+int s2r_set_bus_drive(s2r_synth *s, uint32_t bus, const float *curve, float pre, float dry, float wet) {
+    S2R_TRY(drive_values(s, "s2r_set_bus_drive", bus, curve, pre, dry, wet));
+    S2R_TRY(post_handle(s, "s2r_set_bus_drive", kStemWords[kDriveEntry].are));
+    if (!curve) return set_err(s, S2R_ERR_INVALID, "s2r_set_bus_drive: no curve");
+    return stem_set(s, "s2r_set_bus_drive", [&](const S2rPostCtx &c) { return s->post.set_drive(c, bus, curve, pre, dry, wet, false); });
+}
+
+int s2r_clear_bus_drive(s2r_synth *s, uint32_t bus) {
+    if (bus >= S2R_MAX_BUSES) return set_err(s, S2R_ERR_PATCH_RANGE, "s2r_clear_bus_drive: bus %u, below %u", bus, S2R_MAX_BUSES);
+    S2R_TRY(post_handle(s, "s2r_clear_bus_drive", kStemWords[kDriveEntry].are));
+    return stem_set(s, "s2r_clear_bus_drive", [&](const S2rPostCtx &c) { return s->post.set_drive(c, bus, nullptr, -1.0f, 0.0f, 0.0f, false); });
+}
+
+int s2r_set_bus_drive_params(s2r_synth *s, uint32_t bus, const float *curve, float pre, float dry, float wet) {
+    S2R_TRY(drive_values(s, "s2r_set_bus_drive_params", bus, curve, pre, dry, wet));
+    S2R_TRY(stem_bus(s, kDriveEntry, bus, "s2r_set_bus_drive_params", true));
+    return stem_set(s, "s2r_set_bus_drive_params", [&](const S2rPostCtx &c) { return s->post.set_drive(c, bus, curve, pre, dry, wet, true); });   // (the history stays)
+}
+
+int s2r_get_bus_drive(const s2r_synth *s, uint32_t bus, uint32_t *present, float *curve, size_t capacity, float *pre, float *dry, float *wet) {
+    S2R_TRY(stem_bus(s, kDriveEntry, bus, nullptr, false));
+    const S2rPostChain::BusDrive &d = s->post.drive[bus];
+    if (d.present() && curve && capacity < S2R_DRIVE_CURVE_POINTS) return S2R_ERR_INVALID;
+    put(present, d.present() ? 1u : 0u); put(pre, d.pre); put(dry, d.dry); put(wet, d.wet);
+    if (d.present() && curve) std::memcpy(curve, d.curve.data(), S2R_DRIVE_CURVE_POINTS * sizeof(float));
+    return S2R_OK;
+}
+
+// the checkpoint pair: the room's state pair's checks, then the stem stages' copy
+static int drive_history(s2r_synth *s, uint32_t bus, float *get, const float *set, size_t count, const char *who) {
+    S2R_TRY(stem_bus(s, kDriveEntry, bus, who, true));
+    const size_t n = 2u * S2R_DRIVE_HISTORY;
+    if (set ? count != n : count < n) return set_err(s, S2R_ERR_INVALID, "%s: the history of bus %u is %zu floats, not %zu", who, bus, n, count);
+    if (!get && !set) return set_err(s, S2R_ERR_INVALID, "%s: null buffer", who);
+    if (set) for (size_t k = 0; k < n; k++) if (!std::isfinite(set[k])) return set_err(s, S2R_ERR_PATCH_RANGE, "%s: value %zu of the history is not finite", who, k);
+    return stem_history(s, kDriveEntry, bus, get, set, count, who);
+}
+
+int s2r_get_bus_drive_history(s2r_synth *s, uint32_t bus, float *lr, size_t capacity) {
+    return drive_history(s, bus, lr, nullptr, capacity, "s2r_get_bus_drive_history");
+}
+
+int s2r_set_bus_drive_history(s2r_synth *s, uint32_t bus, const float *lr, size_t count) {
+    return drive_history(s, bus, nullptr, lr, lr ? count : (size_t)-1, "s2r_set_bus_drive_history");
+}

@@ -1,4 +1,4 @@
-// s2r_post.cpp — the post-mix chain (s2r_post.h): the EQs, the dynamics, the stem stages (choruses, delays, reverbs), the rooms, master section, master limiter.  Compiled with hipcc, -ffp-contract=off.
+// s2r_post.cpp — the post-mix chain (s2r_post.h): the EQs, the dynamics, the drives, the stem stages (choruses, delays, reverbs), the rooms, master section, master limiter.  Compiled with hipcc, -ffp-contract=off.
 #include "s2r_post.h"
 #include "s2r_rules.h"
 
@@ -70,6 +70,7 @@ hipError_t S2rPostChain::prepare(const S2rPostCtx &c, uint32_t n_buses, uint32_t
     for (uint32_t b = 0; b < n_buses; b++) if (eq[b].present()) call.eq = true;                      // (and so is an EQ)
     for (uint32_t b = 0; b < n_buses; b++) if (dyn_runs(b, n_buses)) call.dyn = true;                // (and dynamics, also when their key bus is past the call's)
     for (uint32_t b = 0; b < n_buses; b++) if (room[b].present()) call.room = true;                  // (and a room)
+    for (uint32_t b = 0; b < n_buses; b++) if (drive[b].present()) call.drive = true;                // (and a drive)
     call.limited = master_fill && limiter.lookahead != 0;
     if (call.master) {                                           // the device copy of the stems and the pinned rows of block partials
         if (!master.stage) POST_HIP(hipMalloc((void **)&master.stage, (size_t)2 * S2R_MAX_BUSES * c.max_frames * sizeof(float)));
@@ -82,13 +83,13 @@ hipError_t S2rPostChain::prepare(const S2rPostCtx &c, uint32_t n_buses, uint32_t
     }
     float *stages[S2R_STEM_STAGES];
     for (int k = 0; k < S2R_STEM_STAGES; k++) stages[k] = stem[k].stage;
-    call.route = s2r_post_route_room(call, s2r_post_route_dyn(call, s2r_post_route_eq(call, s2r_post_route(call, stages, master.stage, limiter.in, c.bus_out_dev, c.out_host_dev),
-                                                                                      eq_insert.stage), dyn_insert.stage), room_insert.stage);
+    call.route = s2r_post_route_drive(call, s2r_post_route_room(call, s2r_post_route_dyn(call, s2r_post_route_eq(call, s2r_post_route(call, stages, master.stage, limiter.in, c.bus_out_dev, c.out_host_dev),
+                                                                                      eq_insert.stage), dyn_insert.stage), room_insert.stage), drive_insert.stage);
     return hipSuccess;
 }
 
 hipError_t S2rPostChain::launch(const S2rPostCtx &c, const S2rPostCall &call) {
-    const S2rPostRouteRoom &r = call.route; const float fn = (float)call.frames;
+    const S2rPostRouteDrive &r = call.route; const float fn = (float)call.frames;
     if (call.eq) {                                               // once per call, over all of its frames, in front of every stem stage
         S2rEq a{};
         for (uint32_t b = 0; b < call.n_buses; b++) {
@@ -113,6 +114,7 @@ hipError_t S2rPostChain::launch(const S2rPostCtx &c, const S2rPostCall &call) {
         a.in = r.dyn.in; a.out = r.dyn.out; a.meter = dyn_meter_dev; a.n_buses = call.n_buses; a.frames = call.frames;
         POST_TIMED(c, dyn_insert.timer, s2r_launch_bus_dyn(a, c.stream));
     }
+    if (call.drive) POST_HIP(launch_drive(c, call));             // likewise, behind the dynamics: tiles x buses workgroups, none waiting for another
     if (call.on[S2R_STEM_CHORUS]) {                              // likewise, in front of the delays
         S2rChorus a{};
         for (uint32_t b = 0; b < call.n_buses; b++) {
@@ -196,6 +198,7 @@ void S2rPostChain::commit(const S2rPostCall &call) {
     if (call.eq) for (uint32_t b = 0; b < call.n_buses; b++) if (eq[b].present()) eq[b].flip();     // the EQs' states have moved on
     if (call.dyn)                                                // ... the dynamics' gains, and the kernel's minima are the call's meters
         for (uint32_t b = 0; b < call.n_buses; b++) if (dyn_runs(b, call.n_buses)) { dyn[b].flip(); dyn[b].min_gain = dyn_meter[b]; }
+    if (call.drive) for (uint32_t b = 0; b < call.n_buses; b++) if (drive[b].present()) drive[b].flip();   // ... the drives' histories
     for (int k = 0; k < S2R_STEM_STAGES; k++)                    // the histories have moved on
         if (call.on[k]) for (uint32_t b = 0; b < call.n_buses; b++) if (bus(k, b).present()) bus(k, b).flip();
     if (call.on[S2R_STEM_CHORUS])                                // ... and the choruses' phases
@@ -229,10 +232,11 @@ void S2rPostChain::commit(const S2rPostCall &call) {
     }
 }
 
-// a stage that the fill could have run and did not reads 0; a panned fill leaves all eight values alone, a bus fill the master's two
+// a stage that the fill could have run and did not reads 0; a panned fill leaves all nine values alone, a bus fill the master's two
 hipError_t S2rPostChain::read_timers(const S2rPostCall &call) {
     if (call.n_buses) { eq_insert.timer.ms = 0.0f; if (call.eq) POST_HIP(eq_insert.timer.read()); }
     if (call.n_buses) { dyn_insert.timer.ms = 0.0f; if (call.dyn) POST_HIP(dyn_insert.timer.read()); }
+    if (call.n_buses) { drive_insert.timer.ms = 0.0f; if (call.drive) POST_HIP(drive_insert.timer.read()); }
     if (call.n_buses) for (int k = 0; k < S2R_STEM_STAGES; k++) { stem[k].timer.ms = 0.0f; if (call.on[k]) POST_HIP(stem[k].timer.read()); }
     if (call.n_buses) { room_insert.timer.ms = 0.0f; if (call.room) POST_HIP(room_insert.timer.read()); }
     if (call.master) {
@@ -244,7 +248,7 @@ hipError_t S2rPostChain::read_timers(const S2rPostCall &call) {
 }
 
 void S2rPostChain::release() {
-    for (uint32_t b = 0; b < S2R_MAX_BUSES; b++) { drop(eq[b]); drop(dyn[b]); drop(chorus[b]); drop(delay[b]); drop(fx[b]); drop(room[b]); }
+    for (uint32_t b = 0; b < S2R_MAX_BUSES; b++) { drop(eq[b]); drop(dyn[b]); drop(chorus[b]); drop(delay[b]); drop(fx[b]); drop(room[b]); drop(drive[b]); }
     for (Stem &st : stem) { if (st.stage) (void)hipFree(st.stage); st.timer.destroy(); }
     if (eq_insert.stage) (void)hipFree(eq_insert.stage);
     eq_insert.timer.destroy();
@@ -253,6 +257,8 @@ void S2rPostChain::release() {
     dyn_insert.timer.destroy();
     if (room_insert.stage) (void)hipFree(room_insert.stage);
     room_insert.timer.destroy();
+    for (float *p : {drive_insert.stage, drive_curves}) if (p) (void)hipFree(p);
+    drive_insert.timer.destroy();
     for (float *p : {master.stage, limiter.state[0], limiter.state[1], limiter.in}) if (p) (void)hipFree(p);
     for (float *p : {master.partials, limiter.partials}) if (p) (void)hipHostFree(p);
     for (S2rPostTimer *t : {&master.timer, &limiter.timer}) t->destroy();
@@ -410,4 +416,48 @@ hipError_t S2rPostChain::fetch_limiter_state(const S2rPostCtx &c) {
     lm.host.swap(st);
     lm.host_valid = true;
     return hipSuccess;
+}
+
+// The drive's launch and its setter, at the end of the file and out of line, like the kernel at the end of the link order: the code in
+// front keeps the place it had.
+__attribute__((noinline)) hipError_t S2rPostChain::launch_drive(const S2rPostCtx &c, const S2rPostCall &call) {
+    const S2rPostRouteDrive &r = call.route;
+    S2rDrive a{};
+    for (uint32_t b = 0; b < call.n_buses; b++) {
+        const BusDrive &f = drive[b];
+        if (!f.present()) continue;
+        S2rDriveBus &d = a.bus[b];
+        d.curve = drive_curves + (size_t)b * S2R_DRIVE_CURVE_POINTS; d.line = f.now(); d.next = f.next();
+        d.pre = f.pre; d.dry = f.dry; d.wet = f.wet;
+    }
+    const S2rDriveTaps &taps = drive_taps();
+    std::memcpy(a.h, taps.h, sizeof a.h); std::memcpy(a.g, taps.g, sizeof a.g);
+    a.in = r.drive.in; a.out = r.drive.out; a.n_buses = call.n_buses; a.frames = call.frames;
+    POST_TIMED(c, drive_insert.timer, s2r_launch_bus_drive(a, c.stream));
+    return hipSuccess;
+}
+
+// As set_dyn: the tables come first and once, the bus's row of them is written last, behind everything that can fail for want of
+// memory, so that a refused set leaves the earlier drive whole.  The history starts as +0.0 (replace).
+hipError_t S2rPostChain::set_drive(const S2rPostCtx &c, uint32_t bus, const float *curve, float pre, float dry, float wet, bool keep_state) {
+    if (pre < 0.0f) { drop(drive[bus]); return hipSuccess; }
+    constexpr size_t kRow = S2R_DRIVE_CURVE_POINTS;
+    if (keep_state) {
+        BusDrive &d = drive[bus];
+        if (curve) {
+            POST_HIP(hipMemcpyAsync(drive_curves + bus * kRow, curve, kRow * sizeof(float), hipMemcpyHostToDevice, c.stream));
+            POST_HIP(hipStreamSynchronize(c.stream));
+            d.curve.assign(curve, curve + kRow);
+        }
+        d.pre = pre; d.dry = dry; d.wet = wet;
+        return hipSuccess;
+    }
+    if (!drive_curves) POST_HIP(hipMalloc((void **)&drive_curves, (size_t)S2R_MAX_BUSES * kRow * sizeof(float)));
+    BusDrive f;
+    f.pre = pre; f.dry = dry; f.wet = wet; f.history = S2R_DRIVE_HISTORY;
+    f.curve.assign(curve, curve + kRow);
+    float *const to = drive_curves + bus * kRow;
+    return replace(c, drive_insert.stage, drive[bus], f, 2u * (size_t)S2R_DRIVE_HISTORY, [&](BusDrive &n) {
+        return hipMemcpyAsync(to, n.curve.data(), kRow * sizeof(float), hipMemcpyHostToDevice, c.stream);
+    });
 }

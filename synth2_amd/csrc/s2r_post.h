@@ -1,6 +1,7 @@
 // s2r_post.h — the chain behind the bus mixdown of s2r_fill_buses and s2r_fill_master: the buses' equalisers and their
 // dynamics (4.22), two inserts at the head of the stem stages (s2r_post_route.h) — the buses' choruses (4.20), their feedback delays
-// (4.19), their convolution reverbs (4.16) —, the buses' rooms (4.23), an insert behind them, the master section (4.17) and the master limiter (4.18), in that order.  The chain owns what the eight stages own
+// (4.19), their convolution reverbs (4.16) —, the buses' rooms (4.23), an insert behind them, the master section (4.17) and the master limiter (4.18), in that order; the
+// buses' drives (4.24) are a fourth insert, behind the dynamics.  The chain owns what the nine stages own
 // and knows nothing of the handle: its functions take a S2rPostCtx and return the HIP error.  Per call: prepare, launch, — the caller's synchronise — commit, read_timers.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -99,8 +100,9 @@ struct S2rPostChain {
         void free() { if (work) (void)hipFree(work); work = nullptr; S2rBusLine::free(); }
     } room[S2R_MAX_BUSES];
     Stem room_insert;                            // (its timer: tools/room_time.py)
-    // stage k's effect on a bus, as far as the stages are alike
-    S2rBusLine &bus(int k, uint32_t b) { S2rBusLine *const of[S2R_STEM_STAGES] = {&chorus[b], &delay[b], &fx[b]}; return *of[k]; }
+    // stage k's effect on a bus, as far as the stages are alike; behind the stem stages, at S2R_STEM_STAGES, the drive, whose history
+    // has their form (the loops over the stem stages do not reach it)
+    S2rBusLine &bus(int k, uint32_t b) { S2rBusLine *const of[S2R_STEM_STAGES + 1] = {&chorus[b], &delay[b], &fx[b], &drive[b]}; return *of[k]; }
     const S2rBusLine &bus(int k, uint32_t b) const { return const_cast<S2rPostChain *>(this)->bus(k, b); }
     // The master section.  Nothing is allocated before the first master fill.
     struct Master {
@@ -136,6 +138,7 @@ struct S2rPostChain {
     // the synchronise that succeeded, and only then, histories, applied values and state move on and the meters fold
     hipError_t prepare(const S2rPostCtx &c, uint32_t n_buses, uint32_t frames, bool master_fill, bool stems, S2rPostCall &call);
     hipError_t launch(const S2rPostCtx &c, const S2rPostCall &call);
+    hipError_t launch_drive(const S2rPostCtx &c, const S2rPostCall &call);      // the drive's part of launch, out of line
     void commit(const S2rPostCall &call);
     hipError_t read_timers(const S2rPostCall &call);
     void release();
@@ -149,6 +152,9 @@ struct S2rPostChain {
     hipError_t set_room(const S2rPostCtx &c, uint32_t bus, const uint32_t *cd, const uint32_t *ad, uint32_t spread, const float levels[7]);
     void set_room_params(uint32_t bus, const float levels[7]);
     hipError_t room_state(const S2rPostCtx &c, uint32_t bus, float *get, const float *set);    // the whole state, out or in
+    // pre < 0: removes the bus's drive; keep_state: the levels, and the table unless curve is null, on a bus that has one.  Its
+    // history goes through history() at k = S2R_STEM_STAGES
+    hipError_t set_drive(const S2rPostCtx &c, uint32_t bus, const float *curve, float pre, float dry, float wet, bool keep_state);
     hipError_t set_chorus(const S2rPostCtx &c, uint32_t bus, uint32_t voices, float base, float depth, uint32_t phase_inc, uint32_t spread, float dry, float wet);
     hipError_t set_delay(const S2rPostCtx &c, uint32_t bus, uint32_t delay_frames, float feedback, float cross, float dry, float wet);
     hipError_t set_reverb(const S2rPostCtx &c, uint32_t bus, const float *ir_l, const float *ir_r, uint32_t n_taps, float dry, float wet);
@@ -158,4 +164,13 @@ struct S2rPostChain {
     void set_limiter(float ceiling, uint32_t lookahead, uint32_t hold);      // (0, 0, 0): off
     void set_limiter_state(const float *xh, const float *gh);
     hipError_t fetch_limiter_state(const S2rPostCtx &c);            // the device's copy into `host`, kept until the next fill
+    // The drives (s2r_set_bus_drive): lines of [S2R_DRIVE_HISTORY][2], the bus's last input frames, oldest first, L then R.  The fourth
+    // insert, behind the dynamics (s2r_post_route_drive), with a staging buffer and a timer of its own and the tables on the device.
+    // (Behind everything else, so that the members in front keep their places in the handle.)
+    struct BusDrive : S2rBusLine {
+        float pre = 0.0f, dry = 0.0f, wet = 0.0f;
+        std::vector<float> curve;                // the host's copy of the table: S2R_DRIVE_CURVE_POINTS entries
+    } drive[S2R_MAX_BUSES];
+    Stem drive_insert;                           // (its timer: tools/drive_time.py)
+    float *drive_curves = nullptr;               // [S2R_MAX_BUSES][S2R_DRIVE_CURVE_POINTS] in device memory, allocated when a drive is first set
 };

@@ -23,6 +23,10 @@ struct S2rPostRouteDyn : S2rPostRoute {
 struct S2rPostRouteRoom : S2rPostRouteDyn {
     struct { float *in, *out; } room;
 };
+// ... and the drive insert behind the dynamics (s2r_post_route_drive): null unless the call runs it.  Again a struct of its own on top
+struct S2rPostRouteDrive : S2rPostRouteRoom {
+    struct { float *in, *out; } drive;
+};
 struct S2rPostCall {                             // one fill, as prepare leaves it
     uint32_t n_buses = 0, frames = 0;            // n_buses 0: a panned fill, which runs no stage
     bool master = false, stems = false;          // s2r_fill_master; the caller wants the stems too
@@ -31,7 +35,8 @@ struct S2rPostCall {                             // one fill, as prepare leaves 
     bool eq = false;                             // an EQ sits on one of the call's buses
     bool dyn = false;                            // dynamics sit on one of the call's buses, their key bus among them too
     bool room = false;                           // a room sits on one of the call's buses
-    S2rPostRouteRoom route{};
+    bool drive = false;                          // a drive sits on one of the call's buses
+    S2rPostRouteDrive route{};
 };
 
 // Who reads and writes what, the only place that decides it.  The combine writes into the first stem stage that runs, each running
@@ -93,5 +98,19 @@ inline S2rPostRouteRoom s2r_post_route_room(const S2rPostCall &call, const S2rPo
     for (int k = 0; k < S2R_STEM_STAGES; k++) if (call.on[k]) writer = &r.stem[k].out;
     r.room.in = room_stage; r.room.out = *writer;
     *writer = room_stage;
+    return r;
+}
+
+// The drive is the fourth insert, behind the dynamics and in front of the stem stages.  Applied to the route after s2r_post_route_room:
+// the drive reads its own staging buffer and writes where the stage in front of it — the dynamics if the call runs them, else the EQ,
+// else the combine — writes by now, which may already be the room's buffer, and that writer is redirected into the drive's buffer.  A
+// call without a drive, or without buses, keeps its route as it is, with a null drive pair.
+inline S2rPostRouteDrive s2r_post_route_drive(const S2rPostCall &call, const S2rPostRouteRoom &route, float *drive_stage) {
+    S2rPostRouteDrive r{};
+    static_cast<S2rPostRouteRoom &>(r) = route;
+    if (!call.drive || !call.n_buses) return r;
+    float *&writer = call.dyn ? r.dyn.out : call.eq ? r.eq.out : r.combine_out;
+    r.drive.in = drive_stage; r.drive.out = writer;
+    writer = drive_stage;
     return r;
 }

@@ -303,6 +303,91 @@ int s2r_room_design(double sample_rate, double size, uint32_t *cd, uint32_t *ad,
     return S2R_OK;
 }
 
+// ---- per-bus drive: up to 4x, the table there, filtered and back down ----
+}  // extern "C"
+
+// the decimator's design of s2r_fill_oversampled (s2r_host.cpp) at S2R_DRIVE_TAPS taps: a Blackman-windowed sinc, cutoff 0.115 cycles per
+// oversampled sample, unit DC gain; binary64, rounded once
+const S2rDriveTaps &drive_taps() {
+    static const S2rDriveTaps taps = [] {
+        S2rDriveTaps t;
+        double d[S2R_DRIVE_TAPS], sum = 0.0;
+        const double PI = 3.14159265358979323846, fc = 0.115;
+        for (uint32_t k = 0; k <= S2R_DRIVE_TAPS / 2u; k++) {            // the first half and the centre; the second half is its mirror, on bits
+            const double at = (double)((int)k - (int)(S2R_DRIVE_TAPS - 1u) / 2);
+            const double ideal = at == 0.0 ? 2.0 * fc : std::sin(2.0 * PI * fc * at) / (PI * at);
+            const double w = 0.42 - 0.5 * std::cos(2.0 * PI * k / (S2R_DRIVE_TAPS - 1u)) + 0.08 * std::cos(4.0 * PI * k / (S2R_DRIVE_TAPS - 1u));
+            d[k] = d[S2R_DRIVE_TAPS - 1u - k] = ideal * w;
+        }
+        for (uint32_t k = 0; k < S2R_DRIVE_TAPS; k++) sum += d[k];
+        for (uint32_t k = 0; k < S2R_DRIVE_TAPS; k++) { t.h[k] = (float)(d[k] / sum); t.g[k] = 4.0f * t.h[k]; }
+        return t;
+    }();
+    return taps;
+}
+
+extern "C" {
+
+int s2r_drive_taps(float *h) {
+    if (!h) return S2R_ERR_INVALID;
+    std::memcpy(h, drive_taps().h, sizeof drive_taps().h);
+    return S2R_OK;
+}
+
+int s2r_drive_reference(const float *curve, float pre, float dry, float wet, const float *x_lr, uint32_t frames, float *history, float *out_lr) {
+    if (!drive_in_range(curve, pre, dry, wet)) return S2R_ERR_PATCH_RANGE;
+    if (!curve || !history || (!x_lr && frames)) return S2R_ERR_INVALID;
+    for (uint32_t k = 0; k < 2u * S2R_DRIVE_HISTORY; k++) if (!std::isfinite(history[k])) return S2R_ERR_PATCH_RANGE;
+    const S2rDriveTaps &taps = drive_taps();
+    constexpr uint32_t H = S2R_DRIVE_HISTORY, L = S2R_DRIVE_LATENCY;
+    // per channel: x as history followed by the call (frame q at H + q), w for frames q >= -L (sample 4 q + p at 4 (L + q) + p)
+    std::vector<float> x((size_t)H + frames), w(4u * ((size_t)L + frames));
+    for (uint32_t c = 0; c < 2u; c++) {
+        for (uint32_t k = 0; k < H; k++) x[k] = history[2u * k + c];
+        for (uint32_t n = 0; n < frames; n++) x[(size_t)H + n] = x_lr[2u * (size_t)n + c];
+        for (size_t f = 0; f < (size_t)L + frames; f++) {              // frame q = f - L: x[q - j] sits at f + L - j
+            for (uint32_t p = 0; p < S2R_DRIVE_OVERSAMPLE; p++) {
+                float u = 0.0f;
+                for (uint32_t j = 0; p + 4u * j < S2R_DRIVE_TAPS; j++) {
+                    const float t = taps.g[p + 4u * j] * x[f + L - j];
+                    u = u + t;
+                }
+                w[4u * f + p] = drive_shape(curve, pre, u);
+            }
+        }
+        for (uint32_t n = 0; n < frames && out_lr; n++) {
+            float v = 0.0f;
+            for (uint32_t k = 0; k < S2R_DRIVE_TAPS; k++) {                // w[4 n - k] sits at 4 (L + n) - k
+                const float t = taps.h[k] * w[4u * ((size_t)L + n) - k];
+                v = v + t;
+            }
+            const float a = dry * x[(size_t)H + n - L];
+            const float b = wet * v;
+            out_lr[2u * (size_t)n + c] = a + b;
+        }
+        for (uint32_t k = 0; k < H; k++) history[2u * k + c] = x[(size_t)frames + k];
+    }
+    return S2R_OK;
+}
+
+int s2r_drive_curve(uint32_t kind, double amount, float *table) {
+    if (kind > S2R_DRIVE_FOLD) return S2R_ERR_PATCH_RANGE;
+    if (kind != S2R_DRIVE_LINEAR && !(amount >= S2R_DRIVE_MIN_AMOUNT && amount <= S2R_DRIVE_MAX_AMOUNT)) return S2R_ERR_PATCH_RANGE;
+    if (!table) return S2R_ERR_INVALID;
+    auto clamp = [](double z) { return z < -1.0 ? -1.0 : z > 1.0 ? 1.0 : z; };
+    const double th = kind == S2R_DRIVE_TANH ? std::tanh(amount) : 1.0;
+    for (uint32_t i = 0; i < S2R_DRIVE_CURVE_POINTS; i++) {
+        const double u = (double)i / 512.0 - 1.0, z = amount * u;
+        double y = u;
+        if (kind == S2R_DRIVE_TANH) y = std::tanh(z) / th;
+        else if (kind == S2R_DRIVE_HARD) y = clamp(z);
+        else if (kind == S2R_DRIVE_CUBIC) { const double v = clamp(z); y = 1.5 * v - 0.5 * (v * v * v); }
+        else if (kind == S2R_DRIVE_FOLD) { double r = std::fmod(z + 1.0, 4.0); if (r < 0.0) r += 4.0; y = r < 2.0 ? r - 1.0 : 3.0 - r; }
+        table[i] = (float)y;
+    }
+    return S2R_OK;
+}
+
 // ---- the master section: energies by the adjacent-pair tree over blocks of S2R_METER_BLOCK frames ----
 static float master_energy(const float *v, uint32_t frames) {     // v: one channel of an interleaved pair (stride 2)
     float total = 0.0f;

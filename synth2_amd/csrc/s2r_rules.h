@@ -86,6 +86,34 @@ static inline void room_layout(const uint32_t *cd, const uint32_t *ad, uint32_t 
     }
 }
 
+// a bus's drive: every curve entry finite, pre in [0, S2R_DRIVE_MAX_PRE], dry and wet in [0, 1].  A null curve passes:
+// the caller refuses it by another name, or keeps the table it has.
+static inline bool drive_in_range(const float *curve, float pre, float dry, float wet) {
+    if (!(pre >= 0.0f && pre <= S2R_DRIVE_MAX_PRE) || !unit_in_range(dry) || !unit_in_range(wet)) return false;
+    for (uint32_t j = 0; j < S2R_DRIVE_CURVE_POINTS && curve; j++) if (!std::isfinite(curve[j])) return false;
+    return true;
+}
+// The library's one prototype filter, h[S2R_DRIVE_TAPS], and the interpolator's g = 4 h (exact): computed at the first call, once per
+// process (s2r_rules.cpp), never inside a fill.
+struct S2rDriveTaps { float h[S2R_DRIVE_TAPS], g[S2R_DRIVE_TAPS]; };
+const S2rDriveTaps &drive_taps();
+// One oversampled sample through the table: the rule's second and third lines.  Sign and magnitude, so that a small signal keeps its
+// relative precision; a NaN, outside the contract, reads inside the table like everything else.
+static inline float drive_shape(const float *curve, float pre, float u) {
+    const float t = pre * u;
+    const float at = std::fabs(t);
+    const float m = at < 1.0f ? at : 1.0f;
+    const float a = m * 512.0f;
+    const uint32_t ia = (uint32_t)a;
+    const uint32_t i = ia < 511u ? ia : 511u;
+    const float fr = a - (float)i;
+    const bool neg = t < 0.0f;
+    const float c0 = curve[neg ? 512u - i : 512u + i], c1 = curve[neg ? 511u - i : 513u + i];
+    const float d = c1 - c0;
+    const float e = fr * d;
+    return c0 + e;
+}
+
 // The voice mixer's gain rules, inline: the host's per-voice loops compile them in — a call per voice into s2r_rules.cpp showed as 10
 // to 15 us of host time per fill of 65 536 voices (profiles/r12/post_chain.txt).  s2r_rules.cpp exports them under their s2r.h names.
 static inline float rule_voice_pan(float pan, float key_spread, uint8_t note) {

@@ -45,6 +45,13 @@ ROOM_COMBS = 8                              # S2R_ROOM_COMBS
 ROOM_ALLPASSES = 4                          # S2R_ROOM_ALLPASSES
 ROOM_MIN_DELAY = 64                         # S2R_ROOM_MIN_DELAY
 ROOM_MAX_DELAY = 8192                       # S2R_ROOM_MAX_DELAY
+DRIVE_OVERSAMPLE = 4                        # S2R_DRIVE_OVERSAMPLE
+DRIVE_TAPS = 65                             # S2R_DRIVE_TAPS
+DRIVE_LATENCY = 16                          # S2R_DRIVE_LATENCY
+DRIVE_HISTORY = 32                          # S2R_DRIVE_HISTORY
+DRIVE_CURVE_POINTS = 1025                   # S2R_DRIVE_CURVE_POINTS
+DRIVE_MAX_PRE = 1024.0                      # S2R_DRIVE_MAX_PRE
+DRIVE_LINEAR, DRIVE_TANH, DRIVE_HARD, DRIVE_CUBIC, DRIVE_FOLD = range(5)     # s2r_drive_kind
 IR_SEGMENT = 256                            # S2R_IR_SEGMENT
 METER_BLOCK = 256                           # S2R_METER_BLOCK
 LIMITER_MAX_LOOKAHEAD = 1024                # S2R_LIMITER_MAX_LOOKAHEAD
@@ -251,6 +258,15 @@ def load_library():
         "s2r_room_state_floats": (C.c_size_t, [_u32p, _u32p, C.c_uint32]),
         "s2r_room_reference": (C.c_int, [_u32p, _u32p, C.c_uint32] + [C.c_float] * 7 + [_f32p, C.c_uint32, _f32p, _f32p]),
         "s2r_room_design": (C.c_int, [C.c_double, C.c_double, _u32p, _u32p, _u32p]),
+        "s2r_set_bus_drive": (C.c_int, [H, C.c_uint32, _f32p, C.c_float, C.c_float, C.c_float]),
+        "s2r_clear_bus_drive": (C.c_int, [H, C.c_uint32]),
+        "s2r_set_bus_drive_params": (C.c_int, [H, C.c_uint32, _f32p, C.c_float, C.c_float, C.c_float]),
+        "s2r_get_bus_drive": (C.c_int, [H, C.c_uint32, _u32p, _f32p, C.c_size_t, _f32p, _f32p, _f32p]),
+        "s2r_get_bus_drive_history": (C.c_int, [H, C.c_uint32, _f32p, C.c_size_t]),
+        "s2r_set_bus_drive_history": (C.c_int, [H, C.c_uint32, _f32p, C.c_size_t]),
+        "s2r_drive_reference": (C.c_int, [_f32p, C.c_float, C.c_float, C.c_float, _f32p, C.c_uint32, _f32p, _f32p]),
+        "s2r_drive_taps": (C.c_int, [_f32p]),
+        "s2r_drive_curve": (C.c_int, [C.c_uint32, C.c_double, _f32p]),
         "s2r_set_bus_return": (C.c_int, [H, C.c_uint32, C.c_float]),
         "s2r_get_bus_return": (C.c_int, [H, C.c_uint32, _f32p, _f32p]),
         "s2r_set_master_fader": (C.c_int, [H, C.c_float]),
@@ -556,6 +572,56 @@ def room_design(sample_rate, size=1.0):
     if rc != S2R_OK:
         raise S2rError(rc, load_library().s2r_status_string(rc).decode())
     return c, a, sp.value
+
+
+def _drive_curve(curve, who):
+    c = np.ascontiguousarray(curve, dtype=np.float32)
+    if c.shape != (DRIVE_CURVE_POINTS,):
+        raise ValueError(who + ": curve is [%d] float32" % DRIVE_CURVE_POINTS)
+    return c
+
+
+def _f32(v):
+    return C.c_float(float(np.float32(v)))
+
+
+def drive_reference(curve, pre, dry, wet, x, history=None):
+    """the bus drive's rule on the host (s2r_drive_reference): curve [DRIVE_CURVE_POINTS] float32, the three levels, x [frames, 2]
+    float32, history [DRIVE_HISTORY, 2] float32 carried in (None: +0.0, as after a set); returns (out [frames, 2], the history after
+    the call)"""
+    c = _drive_curve(curve, "drive_reference")
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    if x.ndim != 2 or x.shape[1] != 2:
+        raise ValueError("drive_reference: x is [frames, 2]")
+    h = np.zeros((DRIVE_HISTORY, 2), dtype=np.float32) if history is None else np.array(history, dtype=np.float32)
+    if h.shape != (DRIVE_HISTORY, 2):
+        raise ValueError("drive_reference: the history is [%d, 2]" % DRIVE_HISTORY)
+    out = np.empty_like(x)
+    L = load_library()
+    rc = L.s2r_drive_reference(c.ctypes.data_as(_f32p), _f32(pre), _f32(dry), _f32(wet), x.ctypes.data_as(_f32p), x.shape[0], h.ctypes.data_as(_f32p),
+                               out.ctypes.data_as(_f32p))
+    if rc != S2R_OK:
+        raise S2rError(rc, L.s2r_status_string(rc).decode())
+    return out, h
+
+
+def drive_curve(kind, amount=1.0):
+    """a table [DRIVE_CURVE_POINTS] float32 by design (s2r_drive_curve): DRIVE_LINEAR, DRIVE_TANH, DRIVE_HARD, DRIVE_CUBIC or DRIVE_FOLD
+    at `amount`, the gain in front of the shape"""
+    out = np.empty(DRIVE_CURVE_POINTS, dtype=np.float32)
+    rc = load_library().s2r_drive_curve(int(kind), float(amount), out.ctypes.data_as(_f32p))
+    if rc != S2R_OK:
+        raise S2rError(rc, load_library().s2r_status_string(rc).decode())
+    return out
+
+
+def drive_taps():
+    """the library's prototype filter h [DRIVE_TAPS] float32 (s2r_drive_taps): the decimator's taps; the interpolator's are 4 h"""
+    out = np.empty(DRIVE_TAPS, dtype=np.float32)
+    rc = load_library().s2r_drive_taps(out.ctypes.data_as(_f32p))
+    if rc != S2R_OK:
+        raise S2rError(rc, load_library().s2r_status_string(rc).decode())
+    return out
 
 
 def master_reference(stems, r0, r1, m0, m1):
@@ -1180,6 +1246,55 @@ class Synth:
     @staticmethod
     def room_design(sample_rate, size=1.0):
         return room_design(sample_rate, size)
+
+    # --- per-bus drive (build-defined; s2r.h: s2r_set_bus_drive) ---
+    def set_bus_drive(self, bus, curve, pre=1.0, dry=0.0, wet=1.0):
+        """an oversampled waveshaper on a bus of sample_buses and sample_master, behind the dynamics: curve [DRIVE_CURVE_POINTS] float32,
+        finite, entry 512 its value at 0 and entry 512 +- i at +- i / 512 (drive_curve makes one); pre in [0, DRIVE_MAX_PRE], dry and
+        wet in [0, 1].  The bus comes out DRIVE_LATENCY frames late.  Replaces any earlier drive of the bus and zeroes its history."""
+        c = _drive_curve(curve, "set_bus_drive")
+        self._check(self.L.s2r_set_bus_drive(self.h, int(bus), c.ctypes.data_as(_f32p), _f32(pre), _f32(dry), _f32(wet)))
+
+    def clear_bus_drive(self, bus):
+        """removes the bus's drive: the bus passes again, bit for bit"""
+        self._check(self.L.s2r_clear_bus_drive(self.h, int(bus)))
+
+    def set_bus_drive_params(self, bus, curve, pre, dry, wet):
+        """the levels, and the table unless curve is None; the history stays, so a curve or a level moves between calls with no restart"""
+        c = None if curve is None else _drive_curve(curve, "set_bus_drive_params")
+        self._check(self.L.s2r_set_bus_drive_params(self.h, int(bus), None if c is None else c.ctypes.data_as(_f32p), _f32(pre), _f32(dry), _f32(wet)))
+
+    def get_bus_drive(self, bus):
+        """(curve [DRIVE_CURVE_POINTS] float32, pre, dry, wet) of the bus's drive; None for a bus without"""
+        present = C.c_uint32()
+        curve = np.empty(DRIVE_CURVE_POINTS, dtype=np.float32)
+        pre, dry, wet = C.c_float(), C.c_float(), C.c_float()
+        self._check(self.L.s2r_get_bus_drive(self.h, int(bus), C.byref(present), curve.ctypes.data_as(_f32p), curve.size, C.byref(pre), C.byref(dry),
+                                             C.byref(wet)))
+        return (curve, np.float32(pre.value), np.float32(dry.value), np.float32(wet.value)) if present.value else None
+
+    def bus_drive_history(self, bus):
+        """the [DRIVE_HISTORY, 2] float32 input frames the bus's drive carries into the next call, oldest first — the checkpoint
+        companion of bus_delay_history"""
+        out = np.empty((DRIVE_HISTORY, 2), dtype=np.float32)
+        self._check(self.L.s2r_get_bus_drive_history(self.h, int(bus), out.ctypes.data_as(_f32p), out.size))
+        return out
+
+    def set_bus_drive_history(self, bus, history):
+        st = np.ascontiguousarray(history, dtype=np.float32).ravel()
+        self._check(self.L.s2r_set_bus_drive_history(self.h, int(bus), st.ctypes.data_as(_f32p), st.size))
+
+    @staticmethod
+    def drive_reference(curve, pre, dry, wet, x, history=None):
+        return drive_reference(curve, pre, dry, wet, x, history)
+
+    @staticmethod
+    def drive_curve(kind, amount=1.0):
+        return drive_curve(kind, amount)
+
+    @staticmethod
+    def drive_taps():
+        return drive_taps()
 
     # --- the master section (build-defined; s2r.h: s2r_fill_master) ---
     def set_bus_return(self, bus, level=1.0):

@@ -1,0 +1,39 @@
+"""ASan + UBSan over the bus drive's host side, which needs neither a handle nor HIP: s2r_drive_reference,
+s2r_drive_taps and s2r_drive_curve (csrc/s2r_rules.cpp) beside tests/native/san_drive.cpp, and the drive's insert into the post-mix
+chain's route (s2r_post_route_drive, csrc/s2r_post_route.h) with tests/native/post_route_drive.cpp.  Each is compiled by plain g++ and
+run as a child process, with no preload of any kind — as tests/test_room_native.py does."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SAN = ["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
+def test_drive_reference_under_asan_ubsan(tmp_path):
+    """the reference at the edges of its shapes — no frames, one, 31, 32, 33, a thousand; every designed curve and a table of huge
+    entries; pre 0 and 1024; a null output; in place; one call against two — on buffers of exactly the stated sizes, the answers that
+    need no model (dry alone is the input 16 frames late, the history is the last 32 frames, the taps are symmetric) and refusals that
+    touch nothing"""
+    exe = str(tmp_path / "san_drive")
+    subprocess.check_call(SAN + ["-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "synth2_amd", "csrc"),
+                                 os.path.join(ROOT, "tests", "native", "san_drive.cpp"),
+                                 os.path.join(ROOT, "synth2_amd", "csrc", "s2r_rules.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-3000:]
+    assert "drive ok" in out.stdout
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
+def test_post_route_with_the_drive_under_asan_ubsan(tmp_path):
+    """the 24 routes x EQ off / on x dynamics off / on x room off / on x drive off / on, in bus and master fills: every buffer is
+    written before it is read, the combine writes first, the last writer hits the call's destination, and no kernel reads a pinned
+    output"""
+    exe = str(tmp_path / "post_route_drive")
+    subprocess.check_call(SAN + ["-I", os.path.join(ROOT, "synth2_amd", "csrc"), os.path.join(ROOT, "tests", "native", "post_route_drive.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-3000:]
+    assert "route drive ok" in out.stdout
