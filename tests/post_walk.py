@@ -1,0 +1,563 @@
+"""Seeded walks over the post-mix chain and the chain's host model, with no GPU in it: tests/test_gpu_post_fuzz.py
+plays a walk on a pair of twin handles, tests/test_post_walk_host.py holds the walks themselves to coverage conditions and runs them
+through the model alone.
+
+walk(seed) is a pure function of the seed and returns plain data — numbers, names and seeds, no arrays: Chain.apply makes the
+coefficients, tables and responses from them with the helpers of the per-stage files, whose edge sets the draws are taken from.  Chain is
+the models of those files composed in chain order; no arithmetic of its own is in it: every rule is the one a tests/test_*_host.py file
+pins to numpy on bits."""
+import numpy as np
+
+import synth2_amd as s2
+from synth2_amd import synth as s2s
+from test_delay_host import FEEDS
+from test_drive_host import KINDS, random_table
+from test_gpu_buses import ubits
+from test_gpu_chorus import INCS, SHAPES, VOICES, ChorusModel
+from test_gpu_delay import DELAYS, DelayModel
+from test_gpu_drive import DriveModel, oversampled
+from test_gpu_dyn import COEFS, RATIOS, DynModel
+from test_gpu_eq import EqModel, _coeffs
+from test_gpu_limiter import Lim
+from test_gpu_master import Master
+from test_gpu_reverb import MIXES, Model, _ir
+from test_gpu_room import LEVELS, RoomModel
+from test_limiter_host import PAIRS
+from test_master_host import np_meters
+from test_room_host import FLAT, SMALL
+
+F = np.float32
+# the default sweep of tests/test_gpu_post_fuzz.py and tests/test_post_walk_host.py: S2R_POST_FUZZ_BASE moves it, S2R_POST_FUZZ_SEEDS widens it
+DEFAULT_BASE, DEFAULT_SEEDS = 5000, 24
+STAGES = ("eq", "dyn", "drive", "chorus", "delay", "reverb", "room")        # chain order
+INSERTS = ("eq", "dyn", "drive", "room")
+STEMS = ("chorus", "delay", "reverb")
+FILLS = ("bus", "master_stems", "master", "panned")
+KINDS_OF_ACTION = ("set", "clear", "params", "limiter_set", "limiter_clear", "limiter_ceiling", "limiter_reset", "return", "fader", "snap",
+                   "fill", "roundtrip", "handover")
+MAX_FRAMES = (1024, 1000, 1031, 300, 64, 2048)
+# around the kernels' tiles (room 32, EQ 64, drive 240, dynamics 256, the 256-frame blocks of the meters and the limiter) and the drive's
+# latency of 16 and history of 32 frames; a walk adds max_frames - 1 and max_frames and cuts the list to max_frames
+FRAMES = (1, 2, 15, 16, 17, 31, 32, 33, 63, 64, 65, 239, 240, 241, 255, 256, 257, 300, 485, 513)
+# The peak of the twin's buses: the largest magnitude of sample_buses(1024, 48000, 8) on test_gpu_reverb._handles(32) after _events
+# fill 0, measured on an MI355X at commit bdd609a (the per-bus drive).  The host file scales its synthetic input to it and the
+# dynamics' thresholds are set below it.
+TWIN_PEAK = 2.1742098331451416
+ROOMS = {"flat": FLAT, "small": SMALL}
+CHORUS_H = tuple(h for h in sorted(SHAPES) if h <= 257)
+DELAY_D = tuple(d for d in DELAYS if d <= 1025)
+REVERB_K = (1, 40, 255, 256, 257)
+# |feedback| + |cross| stays below 1, so that no line grows without bound over a walk: the host file's pairs that keep to 0.9, and two more
+DELAY_FEEDS = tuple(fc for fc in FEEDS if abs(fc[0]) + abs(fc[1]) <= 0.9) + ((-0.5, 0.25), (0.3, -0.6))
+DELAY_MIX = ((0.5, 1.0), (1.0, 0.5), (0.0, 1.0))
+CHORUS_MIX = ((0.5, 0.25), (0.75, 0.5), (1.0, 1.0))
+CHORUS_SPREAD = (0, 5, 0x40000000)
+DRIVE_MIX = ((0.0, 1.0), (0.5, 0.75), (0.25, 1.0))
+DRIVE_PRE = (1.0, 4.0, 0.5)
+DYN_BELOW_PEAK_DB = (6.0, 14.0, 24.0)                            # a threshold this far below TWIN_PEAK
+LEVELS_MOVED = (1.0, 0.75, 0.5, 0.25)                            # bus returns and the master fader: never silent
+BUS_WEIGHTS = np.array([5, 4, 3, 2, 1, 1, 1, 1], dtype=np.float64) / 18.0     # the low buses more often: they are in more calls
+
+
+def _pick(rng, seq):
+    return seq[int(rng.randint(len(seq)))]
+
+
+def _shape(rng, stage):
+    """what a set of `stage` is given, as names and numbers"""
+    if stage == "eq":
+        return dict(bands=int(rng.randint(1, 5)), seed=int(rng.randint(0, 12)))
+    if stage == "dyn":
+        return dict(key=int(rng.randint(0, 8)), ratio=int(rng.randint(len(RATIOS))), below=float(_pick(rng, DYN_BELOW_PEAK_DB)),
+                    coefs=str(_pick(rng, sorted(COEFS))))
+    if stage == "drive":
+        k = int(rng.randint(len(KINDS) + 1))                     # the last one: a random table
+        dry, wet = _pick(rng, DRIVE_MIX)
+        return dict(curve=KINDS[k][0] if k < len(KINDS) else "random", seed=int(rng.randint(1, 20)), pre=float(_pick(rng, DRIVE_PRE)), dry=dry, wet=wet)
+    if stage == "room":
+        return dict(delays=str(_pick(rng, sorted(ROOMS))), levels=str(_pick(rng, sorted(LEVELS))))
+    if stage == "chorus":
+        dry, wet = _pick(rng, CHORUS_MIX)
+        return dict(H=int(_pick(rng, CHORUS_H)), voices=int(_pick(rng, VOICES)), inc=int(_pick(rng, INCS)), spread=int(_pick(rng, CHORUS_SPREAD)), dry=dry, wet=wet)
+    if stage == "delay":
+        fb, cross = _pick(rng, DELAY_FEEDS)
+        dry, wet = _pick(rng, DELAY_MIX)
+        return dict(D=int(_pick(rng, DELAY_D)), feedback=float(fb), cross=float(cross), dry=dry, wet=wet)
+    dry, wet = _pick(rng, MIXES)
+    return dict(K=int(_pick(rng, REVERB_K)), stereo=bool(rng.randint(2)), seed=int(rng.randint(1, 1000)), dry=dry, wet=wet)
+
+
+def _params(rng, stage, shape):
+    """(entry, the shape after it): what a kept-state entry of `stage` is given; what it cannot move — the band count, the delays, the
+    history's length, the response — stays"""
+    new = _shape(rng, stage)
+    if stage == "eq":
+        return "set_bus_eq_coeffs", dict(new, bands=shape["bands"])
+    if stage == "dyn":
+        return "set_bus_dynamics_params", new
+    if stage == "drive":
+        return "set_bus_drive_params", (new if rng.randint(2) else dict(new, curve=shape["curve"], seed=shape["seed"], table=False))
+    if stage == "room":
+        return "set_bus_room_params", dict(new, delays=shape["delays"])
+    if stage == "chorus":
+        if rng.randint(2):
+            return "set_bus_chorus_rate", dict(shape, inc=new["inc"], spread=new["spread"])
+        return "set_bus_chorus_mix", dict(shape, dry=new["dry"], wet=new["wet"])
+    if stage == "delay":
+        return "set_bus_delay_mix", dict(new, D=shape["D"])
+    return "set_bus_reverb_mix", dict(shape, dry=new["dry"], wet=new["wet"])
+
+
+def walk(seed):
+    """-> (setup, steps): setup = {"max_frames", "timing"}, steps a list of actions, each a dict with a "kind" of KINDS_OF_ACTION.  20 to
+    30 steps, at least 12 of them fills.  The generator keeps book of what is present, so that a clear or a kept-state entry always
+    meets an effect, the limiter's ceiling always has a master fill behind it to be taken from, and a handover happens once at most.
+    The last step is a master fill, so that a walk ends with every return and the master fader arrived (Master.check_committed)."""
+    rng = np.random.RandomState(seed)
+    max_frames = int(_pick(rng, MAX_FRAMES))
+    setup = dict(max_frames=max_frames, timing=bool(rng.rand() < 0.35))
+    frames = sorted({min(n, max_frames) for n in FRAMES + (max_frames - 1, max_frames)})
+    n_steps = int(rng.randint(20, 31))
+    fills_due = 12
+    present = {st: {} for st in STAGES}                          # stage -> bus -> shape
+    limiter = None
+    handed = False
+    steps = []
+    # the opening: the subset of the inserts that the seed's last four bits name and the subset of the stem stages that its last three
+    # name, on the low buses, then a bus fill and a master fill wide enough to run them — so that any 16 seeds in a row run every subset
+    # of the inserts, and any 8 every subset of the stem stages in both kinds of fill
+    opening = [st for j, st in enumerate(INSERTS) if seed >> j & 1] + [st for j, st in enumerate(STEMS) if seed >> j & 1]
+    widest = 0
+    for st in sorted(opening, key=STAGES.index):
+        bus = int(rng.randint(3))
+        shape = _shape(rng, st)
+        if st == "dyn":
+            shape["key"] = int(rng.randint(bus + 1))
+        steps.append(dict(kind="set", stage=st, bus=bus, replaces=False, shape=shape))
+        present[st][bus] = shape
+        widest = max(widest, bus)
+    for fk in (("bus", "master_stems"), ("master", "bus"))[int(rng.randint(2))]:
+        n = int(_pick(rng, [q for q in frames if q >= 16]))
+        steps.append(dict(kind="fill", fill=fk, n_buses=int(rng.randint(widest + 1, 9)), frames=n, tune=bool(rng.randint(2))))
+        fills_due -= 1
+    for k in range(len(steps), n_steps):
+        left = n_steps - k
+        n_present = sum(len(v) for v in present.values())
+        have = [(st, bus) for st in STAGES for bus in sorted(present[st])]
+        w = dict(fill=0.42, set=0.45 if n_present < 4 else 0.22 if n_present < 8 else 0.10, clear=0.10 if have else 0.0, params=0.09 if have else 0.0, master=0.12, limiter=0.10,
+                 roundtrip=0.04 if have else 0.0, handover=0.05 if not handed and k >= 10 and have else 0.0)
+        if left <= max(fills_due, 1):
+            w = dict(fill=1.0)
+        names = sorted(w)
+        p = np.array([w[q] for q in names])
+        kind = names[int(rng.choice(len(names), p=p / p.sum()))]
+        if kind == "fill":
+            fk = FILLS[int(rng.choice(4, p=[0.34, 0.28, 0.30, 0.08]))] if left > 1 else FILLS[1 + int(rng.randint(2))]
+            n = int(_pick(rng, frames))
+            steps.append(dict(kind="fill", fill=fk, n_buses=0 if fk == "panned" else int(rng.randint(1, 9)), frames=n, tune=bool(rng.randint(2))))
+            fills_due = max(0, fills_due - 1)
+        elif kind == "set":
+            if have and rng.rand() < 0.3:                        # replaced while present, in mid-tail
+                st, bus = have[int(rng.randint(len(have)))]
+            else:
+                st, bus = STAGES[int(rng.randint(len(STAGES)))], int(rng.choice(8, p=BUS_WEIGHTS))
+            shape = _shape(rng, st)
+            steps.append(dict(kind="set", stage=st, bus=bus, replaces=bus in present[st], shape=shape))
+            present[st][bus] = shape
+        elif kind == "clear":
+            st, bus = have[int(rng.randint(len(have)))]
+            steps.append(dict(kind="clear", stage=st, bus=bus))
+            del present[st][bus]
+        elif kind == "params":
+            st, bus = have[int(rng.randint(len(have)))]
+            entry, shape = _params(rng, st, present[st][bus])
+            steps.append(dict(kind="params", stage=st, bus=bus, entry=entry, shape=shape))
+            present[st][bus] = shape
+        elif kind == "master":
+            which = int(rng.randint(3))
+            if which == 0:
+                steps.append(dict(kind="return", bus=int(rng.randint(8)), level=float(_pick(rng, LEVELS_MOVED))))
+            elif which == 1:
+                steps.append(dict(kind="fader", level=float(_pick(rng, LEVELS_MOVED))))
+            else:
+                steps.append(dict(kind="snap"))
+        elif kind == "limiter":
+            if limiter is None:                                  # (the opening has made a master fill to take a ceiling from)
+                limiter = PAIRS[int(rng.randint(len(PAIRS)))]
+                steps.append(dict(kind="limiter_set", lookahead=limiter[0], hold=limiter[1]))
+            else:
+                which = int(rng.randint(4))
+                if which == 0:
+                    steps.append(dict(kind="limiter_clear"))
+                    limiter = None
+                elif which == 1:
+                    other = [q for q in PAIRS if q != limiter]
+                    limiter = other[int(rng.randint(len(other)))]
+                    steps.append(dict(kind="limiter_reset", lookahead=limiter[0], hold=limiter[1]))
+                else:
+                    steps.append(dict(kind="limiter_ceiling", scale=float(_pick(rng, (0.5, 0.75, 1.5)))))
+        elif kind == "roundtrip":
+            steps.append(dict(kind="roundtrip"))
+        else:
+            steps.append(dict(kind="handover"))
+            handed = True
+    return setup, steps
+
+
+class _Fan:
+    """one call on every handle of a tuple, which may be empty: the host file runs the models alone"""
+
+    def __init__(self, handles):
+        self._h = tuple(handles)
+
+    def __getattr__(self, name):
+        def call(*args, **kw):
+            for syn in self._h:
+                getattr(syn, name)(*args, **kw)
+        return call
+
+
+class Chain:
+    """The chain on the host: per bus EqModel, DynModel, DriveModel, ChorusModel, DelayModel, the reverb's Model, RoomModel; behind them
+    Master and Lim.  `handles`: who else every action is performed on — (a,) on the device, () on the host."""
+
+    def __init__(self, handles=()):
+        self.handles = tuple(handles)
+        self.m = dict(eq=EqModel(), dyn=DynModel(), drive=DriveModel(), chorus=ChorusModel(), delay=DelayModel(), reverb=Model(), room=RoomModel())
+        self.mm, self.lim = Master(), None
+        self.lims = []                                           # every Lim the walk has had
+        self.irs = {}                                            # the responses: no entry of the library reads one back
+        self.peaks = []                                          # the peak of every master of 16 frames and more so far, before the limiter
+        self.lim_meters = None                                   # of the last fill that ran the limiter on the handle in hand
+
+    def of(self, stage):
+        """bus -> the model's record of `stage`"""
+        return getattr(self.m[stage], dict(eq="e", dyn="d", drive="d", chorus="c", delay="d", reverb="fx", room="r")[stage])
+
+    def present(self):
+        return " ".join("%s:%s" % (st, ",".join(str(b) for b in sorted(self.of(st)))) for st in STAGES if self.of(st)) + \
+            (" limiter:%d,%d" % (self.lim.L, self.lim.H) if self.lim else "")
+
+    def active(self, stage, n_buses):
+        """the buses on which S2rPostChain::prepare lets `stage` run in a call of n_buses"""
+        if stage == "dyn":
+            return [b for b in sorted(self.of(stage)) if self.m["dyn"].runs(b, n_buses)]
+        return [b for b in sorted(self.of(stage)) if b < n_buses]
+
+    # --- the actions ---
+    def _args(self, stage, bus, s):
+        """the arguments of `stage`'s setter and of its model's set from a shape"""
+        if stage == "eq":
+            c = _coeffs(s["bands"], s["seed"])
+            return (c,), (c,)
+        if stage == "dyn":
+            ratio, knee, makeup = RATIOS[s["ratio"]]
+            curve = s2.dynamics_curve(20.0 * np.log10(TWIN_PEAK) - s["below"], ratio, knee, makeup)
+            return ((s["key"], curve) + COEFS[s["coefs"]](),) * 2
+        if stage == "drive":
+            curve = random_table(s["seed"]) if s["curve"] == "random" else s2.drive_curve(*[k for k in KINDS if k[0] == s["curve"]][0][1:])
+            return ((curve, s["pre"], s["dry"], s["wet"]),) * 2
+        if stage == "room":
+            return ROOMS[s["delays"]] + LEVELS[s["levels"]], (ROOMS[s["delays"]], LEVELS[s["levels"]])
+        if stage == "chorus":
+            return ((s["voices"],) + SHAPES[s["H"]] + (s["inc"], s["spread"], s["dry"], s["wet"]),) * 2
+        if stage == "delay":
+            return ((s["D"], s["feedback"], s["cross"], s["dry"], s["wet"]),) * 2
+        ir = _ir(s["K"], s["seed"], s["stereo"])
+        self.irs[bus] = ir
+        return ((ir, s["dry"], s["wet"]),) * 2
+
+    def apply(self, action, handles=None):
+        """one action other than a fill or a handover, on the handles and on the models"""
+        if handles is not None:
+            self.handles = tuple(handles)
+        fan, kind = _Fan(self.handles), action["kind"]
+        if kind == "set":
+            st, bus = action["stage"], action["bus"]
+            dev, mod = self._args(st, bus, action["shape"])
+            getattr(fan, "set_bus_" + dict(dyn="dynamics").get(st, st))(bus, *dev)
+            self.m[st].set(bus, *mod)                            # (a set while present starts afresh, in the model too)
+        elif kind == "clear":
+            st, bus = action["stage"], action["bus"]
+            getattr(fan, "clear_bus_" + dict(dyn="dynamics").get(st, st))(bus)
+            del self.of(st)[bus]
+        elif kind == "params":
+            st, bus, s = action["stage"], action["bus"], action["shape"]
+            f = self.of(st)[bus]
+            if st == "eq":
+                c = _coeffs(s["bands"], s["seed"])
+                fan.set_bus_eq_coeffs(bus, c)
+                f["c"] = np.array(c, dtype=F).reshape(-1, 5)
+            elif st == "dyn":
+                key, curve, att, rel = self._args(st, bus, s)[0]
+                fan.set_bus_dynamics_params(bus, key, curve, att, rel)
+                f.update(key=key, curve=np.array(curve, dtype=F), a=(F(att), F(rel)))
+            elif st == "drive":
+                curve, pre, dry, wet = self._args(st, bus, s)[0]
+                table = s.get("table", True)
+                fan.set_bus_drive_params(bus, curve if table else None, pre, dry, wet)
+                f.update(pre=F(pre), dry=F(dry), wet=F(wet))
+                if table:
+                    f["curve"] = np.array(curve, dtype=F)
+            elif st == "room":
+                fan.set_bus_room_params(bus, *LEVELS[s["levels"]])
+                f["lv"] = tuple(LEVELS[s["levels"]])
+            elif st == "chorus" and action["entry"] == "set_bus_chorus_rate":
+                fan.set_bus_chorus_rate(bus, s["inc"], s["spread"])
+                f.update(inc=s["inc"], spread=s["spread"])
+            elif st == "chorus":
+                fan.set_bus_chorus_mix(bus, s["dry"], s["wet"])
+                f.update(dry=s["dry"], wet=s["wet"])
+            elif st == "delay":
+                fan.set_bus_delay_mix(bus, s["feedback"], s["cross"], s["dry"], s["wet"])
+                f["mix"] = (s["feedback"], s["cross"], s["dry"], s["wet"])
+            else:
+                fan.set_bus_reverb_mix(bus, s["dry"], s["wet"])
+                f.update(dry=s["dry"], wet=s["wet"])
+        elif kind in ("limiter_set", "limiter_reset"):
+            if self.lim is None:
+                self.lim = Lim(action["lookahead"], action["hold"], self.ceiling())
+                self.lims.append(self.lim)
+                self.lim.set(self.handles)
+            else:
+                self.lim.set(self.handles, L=action["lookahead"], H=action["hold"])
+        elif kind == "limiter_ceiling":
+            self.lim.set(self.handles, ceiling=self.ceiling() * action["scale"])
+        elif kind == "limiter_clear":
+            fan.clear_master_limiter()
+            self.lim = None
+        elif kind == "return":
+            self.mm.ret(self.handles, action["bus"], action["level"])
+        elif kind == "fader":
+            self.mm.fader(self.handles, action["level"])
+        elif kind == "snap":
+            self.mm.snap(self.handles)
+        elif kind == "roundtrip":
+            for syn in self.handles:
+                roundtrip(self, syn)
+        else:
+            raise ValueError(kind)
+
+    def ceiling(self):
+        """half the least peak among the masters the model has computed that sounded — the limiter works on the quietest of them too —,
+        and half the twin's peak while none has (behind a delay with no dry path, say)"""
+        c = min(self.peaks or [TWIN_PEAK]) / 2.0
+        assert 2.0 ** -20 < c < 2.0 ** 20, c
+        return c
+
+    # --- the fills ---
+    def _tune(self, x, what):
+        """DriveModel.tune over the drives whose bus gives it something to tune on: most of the oversampled samples are not zero, and
+        their median is within reach of the largest pre"""
+        view = DriveModel()
+        for b, f in self.m["drive"].d.items():
+            if b < x.shape[0]:
+                au = np.abs(oversampled(x[b], f["hist"]))
+                if (au > 0.0).mean() > 0.5 and float(np.median(au)) > 1.0 / s2.DRIVE_MAX_PRE:
+                    view.d[b] = f
+        view.tune(_Fan(self.handles), x, what)
+
+    @staticmethod
+    def _room_age(f, x):
+        """the frames a room has run behind the first frame that was not +0.0 since it was set, this call of x [N, 2] included (its
+        model's record starts without one): what its lines hold is +0.0 until then"""
+        age = f.get("age", 0)
+        if age:
+            return age + x.shape[0]
+        sounding = np.nonzero(ubits(x).any(axis=1))[0]
+        return x.shape[0] - int(sounding[0]) if sounding.size else 0
+
+    def _excused(self, stage, f, x):
+        """the cases a stage's own file documents as changing no bit (tests/test_gpu_chorus.py, _delay.py, _reverb.py: _fill;
+        tests/test_gpu_room.py: the matrix's comment and the test with gain 0): taps that land in a history of zeros under a dry of 1, a
+        response of one tap with dry 0 and wet 1 is not looked at, lines that have not turned over under a dry of 1.  Every one of those
+        files asks first that the bus is not silent as it enters: expect excuses a stage whose input is +0.0 throughout too — the first
+        frames behind a delay with no dry path, say"""
+        n = x.shape[0]
+        if stage == "chorus":                                    # (a tap is base frames late at the least)
+            line = np.concatenate([f["hist"], x], axis=0)
+            return f["dry"] == 1.0 and not ubits(line[:line.shape[0] - int(np.floor(f["base"]))]).any()
+        if stage == "delay":
+            return f["mix"][2] == 1.0 and not ubits(f["hist"][:min(n, f["D"])]).any()
+        if stage == "reverb":
+            return f["ir"].shape[0] == 1 and (f["dry"], f["wet"]) == (0.0, 1.0)
+        if stage == "room":
+            # no line is shorter than ROOM_MIN_DELAY and a set starts them as +0.0: under a dry of 1 nothing comes back before that many
+            # frames have sounded, and what the first frames behind the turn bring back — a fade-in, the drive's pre-ringing — may lie
+            # below half an ulp of the dry signal: excused until the shortest line has turned over twice
+            return f["lv"][4] == 1.0 and self._room_age(f, x) <= 2 * s2.ROOM_MIN_DELAY
+        return False
+
+    def expect(self, x, action, what=""):
+        """what the call of a fill action must return over the twin's dry buses x [n_buses, N, 2] (a panned fill: the twin's panned
+        output, which every model leaves alone): a dict of "buses", or of "master", "stems" (where asked for), "peaks", "energies" and
+        "limiter" — the limiter's meters, or the status limiter_meters() must give when no fill has run it —, with "dyn_meters", bus ->
+        the least gain, of the dynamics that ran.  "trace" is for the host file: (stage, bus, changed a bit, excused) of every stage
+        that ran, and "gain" the limiter's s' where it ran."""
+        if action["fill"] == "panned":
+            return dict(panned=x, dyn_meters={}, trace=[])
+        nb, n = x.shape[0], x.shape[1]
+        assert nb == action["n_buses"] and n == action["frames"]
+        y, trace = x, []
+        for st in STAGES:
+            act = self.active(st, nb)
+            if st == "drive" and act and action["tune"]:
+                self._tune(y, what)
+            excused = {b: self._excused(st, self.of(st)[b], y[b]) or not ubits(y[b]).any() for b in act}     # (or the bus enters as +0.0 throughout)
+            z = self.m[st].expect(y)
+            if st == "room":
+                for b in act:
+                    self.of(st)[b]["age"] = self._room_age(self.of(st)[b], y[b])
+            for b in range(nb):
+                if b in act:
+                    trace.append((st, b, not np.array_equal(ubits(z[b]), ubits(y[b])), excused[b]))
+                else:
+                    assert np.array_equal(ubits(z[b]), ubits(y[b])), (st, b)       # an idle stage's model passes the bus
+            y = z
+        out = dict(dyn_meters={b: self.of("dyn")[b]["mn"] for b in self.active("dyn", nb)}, trace=trace)
+        if action["fill"] == "bus":
+            out["buses"] = y
+            return out
+        m = self.mm.expect(y)
+        if n >= 16 and float(np.abs(m).max()) > TWIN_PEAK / 64.0:
+            self.peaks.append(float(np.abs(m).max()))
+        want = m
+        if self.lim is not None and 2.0 ** -19 < float(np.abs(m).max()) <= self.lim.c:
+            # the ceiling the way the per-stage walks choose it — half the peak of a master the model has computed, this one —, so that
+            # every limited fill that sounds is limited: a new ceiling alone keeps the limiter's state
+            self.lim.set(self.handles, ceiling=float(np.abs(m).max()) / 2.0)
+        if self.lim is not None:
+            want, sp = self.lim.expect(m)
+            self.lim_meters = np.array([sp.min(), np.abs(want).max()], dtype=F)
+            out["gain"] = sp
+        out["master"] = want
+        if action["fill"] == "master_stems":
+            out["stems"] = y
+        out["peaks"], out["energies"] = np_meters(y, m)          # (the master's entry is over the limiter's input)
+        out["limiter"] = s2s.S2R_ERR_INVALID if self.lim_meters is None else self.lim_meters
+        return out
+
+    def states(self):
+        """name -> the state every present effect and the limiter carry, as the getters of a handle give them (states_of)"""
+        out = {}
+        for st in STAGES:
+            for b, f in self.of(st).items():
+                if st == "chorus":
+                    out["chorus %d history" % b], out["chorus %d phase" % b] = f["hist"], _halves(f["phase"])
+                else:
+                    out["%s %d" % (st, b)] = np.array(f[dict(eq="st", dyn="y", drive="hist", delay="hist", reverb="hist", room="st")[st]], dtype=F)
+        if self.lim is not None:
+            out["limiter xh"], out["limiter gh"] = self.lim.xh, self.lim.gh
+        return out
+
+
+def _halves(phase):
+    """a 32-bit phase as two floats that hold it exactly"""
+    return np.array([int(phase) >> 16, int(phase) & 0xFFFF], dtype=F)
+
+
+GETTERS = dict(eq="bus_eq_state", dyn="bus_dynamics_state", drive="bus_drive_history", room="bus_room_state", chorus="bus_chorus_state",
+               delay="bus_delay_history", reverb="bus_reverb_history")
+
+
+def states_of(chain, syn):
+    """Chain.states read from a handle"""
+    out = {}
+    for st in STAGES:
+        for b in chain.of(st):
+            got = getattr(syn, GETTERS[st])(b)
+            if st == "chorus":
+                out["chorus %d history" % b], out["chorus %d phase" % b] = got[0], _halves(got[1])
+            else:
+                out["%s %d" % (st, b)] = np.array(got, dtype=F)
+    if chain.lim is not None:
+        out["limiter xh"], out["limiter gh"] = syn.limiter_state()
+    return out
+
+
+def _restore(chain, syn, st, b, state):
+    if st == "chorus":
+        syn.set_bus_chorus_state(b, *state)
+    else:
+        getattr(syn, "set_" + GETTERS[st])(b, state)
+
+
+def roundtrip(chain, syn):
+    """every present effect's state and the limiter's out through its getter and back in through its setter"""
+    for st in STAGES:
+        for b in chain.of(st):
+            _restore(chain, syn, st, b, getattr(syn, GETTERS[st])(b))
+    if chain.lim is not None:
+        syn.set_limiter_state(*syn.limiter_state())
+
+
+def copy_voices(src, dst):
+    """the voices of `src`, their pans, mix and sends onto `dst`"""
+    dst.import_state(src.export_state())
+    dst.set_voice_pans(src.voice_pans())
+    dst.set_voice_mix(*src.voice_mix())
+    dst.set_voice_sends(*src.voice_sends())
+
+
+def handover(chain, src, dst):
+    """`dst`, a fresh handle, becomes what `src` is: the voices, every effect as src's getters give it (the reverb's response from the
+    chain: no entry reads one back) with its state, the limiter with its state, the master section's applied positions and targets"""
+    copy_voices(src, dst)
+    for st in STAGES:
+        for b in chain.of(st):
+            if st == "eq":
+                dst.set_bus_eq(b, src.get_bus_eq(b))
+            elif st == "dyn":
+                dst.set_bus_dynamics(b, *src.get_bus_dynamics(b))
+            elif st == "drive":
+                dst.set_bus_drive(b, *src.get_bus_drive(b))
+            elif st == "room":
+                dst.set_bus_room(b, *src.get_bus_room(b))
+            elif st == "chorus":
+                dst.set_bus_chorus(b, *src.get_bus_chorus(b))
+            elif st == "delay":
+                dst.set_bus_delay(b, *src.get_bus_delay(b))
+            else:
+                dst.set_bus_reverb(b, chain.irs[b], *src.get_bus_reverb(b)[1:])
+            _restore(chain, dst, st, b, getattr(src, GETTERS[st])(b))
+    for b in range(s2.MAX_BUSES):                                # applied first, snapped, then the targets (s2r.h: s2r_snap_master)
+        dst.set_bus_return(b, src.get_bus_return(b)[1])
+    dst.set_master_fader(src.get_master_fader()[1])
+    dst.snap_master()
+    for b in range(s2.MAX_BUSES):
+        dst.set_bus_return(b, src.get_bus_return(b)[0])
+    dst.set_master_fader(src.get_master_fader()[0])
+    ceiling, look, hold = src.get_master_limiter()
+    if look:
+        dst.set_master_limiter(ceiling, look, hold)
+        dst.set_limiter_state(*src.limiter_state())
+    chain.lim_meters = None                                      # the new handle's limiter has not run yet
+    chain.handles = (dst,)
+
+
+def subset_walk():
+    """the systematic complement of the seeded walks: the 16 subsets of the four inserts in Gray-code order — each step sets or clears
+    exactly one insert, on two of three buses, while the others are in mid-state —, each with a bus fill, a master fill with stems and a
+    master fill under the limiter, 33 frames a call; a chorus on bus 2 and a reverb on bus 1 stay on throughout, so the inserts sit in
+    front of and behind running stem stages"""
+    where = dict(eq=(0, 1), dyn=(1, 2), drive=(0, 2), room=(1, 2))
+    shapes = dict(eq=[dict(bands=2, seed=1), dict(bands=4, seed=3)],
+                  dyn=[dict(key=0, ratio=0, below=14.0, coefs="1ms-100ms"), dict(key=2, ratio=2, below=6.0, coefs="zero")],
+                  drive=[dict(curve="hard", seed=1, pre=1.0, dry=0.0, wet=1.0), dict(curve="random", seed=5, pre=1.0, dry=0.5, wet=0.75)],
+                  room=[dict(delays="small", levels="dark"), dict(delays="flat", levels="hall")])
+    steps = [dict(kind="set", stage="chorus", bus=2, replaces=False, shape=dict(H=145, voices=3, inc=89478 * 20, spread=0x40000000, dry=0.5, wet=0.25)),
+             dict(kind="set", stage="reverb", bus=1, replaces=False, shape=dict(K=40, stereo=True, seed=77, dry=0.25, wet=1.0))]
+    on = 0
+    for i in range(16):
+        gray = i ^ (i >> 1)
+        for j, st in enumerate(INSERTS):
+            if (gray ^ on) >> j & 1:
+                for bus, shape in zip(where[st], shapes[st]):
+                    steps.append(dict(kind="set", stage=st, bus=bus, replaces=False, shape=shape) if gray >> j & 1 else dict(kind="clear", stage=st, bus=bus))
+        on = gray
+        steps.append(dict(kind="fill", fill="bus", n_buses=3, frames=33, tune=True))
+        steps.append(dict(kind="fill", fill="master_stems", n_buses=3, frames=33, tune=True))
+        steps.append(dict(kind="limiter_set", lookahead=5, hold=3))
+        steps.append(dict(kind="fill", fill="master", n_buses=3, frames=33, tune=False))
+        steps.append(dict(kind="limiter_clear"))
+    return dict(max_frames=1024, timing=False), steps
