@@ -257,6 +257,32 @@ class Synth {
     static int drive_curve(uint32_t kind, double amount, float *table) { return s2r_drive_curve(kind, amount, table); }
     static int drive_taps(float *h) { return s2r_drive_taps(h); }
 
+    // per-bus flanger behind the drive (build-defined; s2r.h: s2r_set_bus_flanger): one tap base + depth * triangle frames late into the
+    // stage's own line signal, fed back — base >= S2R_FLANGER_MIN_DELAY, depth >= 0, fl(base + depth) <= S2R_FLANGER_MAX_DELAY; phase_inc
+    // and spread in 2^-32 turns; feedback and cross in [-1, 1] with |feedback| + |cross| <= 1; dry and wet in [0, 1]; in sample_buses and
+    // sample_master only
+    void set_bus_flanger(uint32_t bus, float base, float depth, uint32_t phase_inc, uint32_t spread, float feedback, float cross, float dry, float wet) {
+        check(s2r_set_bus_flanger(h_, bus, base, depth, phase_inc, spread, feedback, cross, dry, wet));
+    }
+    void clear_bus_flanger(uint32_t bus) { check(s2r_clear_bus_flanger(h_, bus)); }
+    void set_bus_flanger_params(uint32_t bus, uint32_t phase_inc, uint32_t spread, float feedback, float cross, float dry, float wet) {   // line and phase stay
+        check(s2r_set_bus_flanger_params(h_, bus, phase_inc, spread, feedback, cross, dry, wet));
+    }
+    bool get_bus_flanger(uint32_t bus, float *base, float *depth, uint32_t *phase_inc, uint32_t *spread, float *feedback, float *cross, float *dry, float *wet) const {
+        float b = 0.0f;
+        check(s2r_get_bus_flanger(h_, bus, &b, depth, phase_inc, spread, feedback, cross, dry, wet));
+        if (base) *base = b;
+        return b != 0.0f;
+    }
+    void bus_flanger_state(uint32_t bus, float *lr, size_t capacity, uint32_t *phase) { check(s2r_get_bus_flanger_state(h_, bus, lr, capacity, phase)); }
+    void set_bus_flanger_state(uint32_t bus, const float *lr, size_t count, uint32_t phase) { check(s2r_set_bus_flanger_state(h_, bus, lr, count, phase)); }
+    static uint32_t flanger_history_frames(float base, float depth) { return s2r_flanger_history_frames(base, depth); }
+    static int flanger_reference(float base, float depth, uint32_t phase_inc, uint32_t spread, float feedback, float cross, float dry, float wet, const float *x_lr,
+                                 uint32_t frames, float *history_lr, uint32_t *phase, float *out_lr) {
+        return s2r_flanger_reference(base, depth, phase_inc, spread, feedback, cross, dry, wet, x_lr, frames, history_lr, phase, out_lr);
+    }
+    static constexpr float FLANGER_MIN_DELAY = S2R_FLANGER_MIN_DELAY, FLANGER_MAX_DELAY = S2R_FLANGER_MAX_DELAY;
+
     // the master section (build-defined; s2r.h: s2r_fill_master): a return level per bus and a master fader, each in [0, 1] and each
     // reaching its target as a ramp across the next sample_master call, and the meters of that call — in sample_master only
     void set_bus_return(uint32_t bus, float level) { check(s2r_set_bus_return(h_, bus, level)); }

@@ -48,7 +48,8 @@ extern "C" {
  * s2r_dynamics_curve, s2r_dynamics_coef, s2r_set_bus_room, s2r_clear_bus_room, s2r_set_bus_room_params, s2r_get_bus_room,
  * s2r_get_bus_room_state, s2r_set_bus_room_state, s2r_room_state_floats, s2r_room_reference, s2r_room_design, s2r_set_bus_drive,
  * s2r_clear_bus_drive, s2r_set_bus_drive_params, s2r_get_bus_drive, s2r_get_bus_drive_history, s2r_set_bus_drive_history,
- * s2r_drive_reference, s2r_drive_taps, s2r_drive_curve. */
+ * s2r_drive_reference, s2r_drive_taps, s2r_drive_curve, s2r_flanger_history_frames, s2r_set_bus_flanger, s2r_clear_bus_flanger,
+ * s2r_set_bus_flanger_params, s2r_get_bus_flanger, s2r_get_bus_flanger_state, s2r_set_bus_flanger_state, s2r_flanger_reference. */
 #define S2R_ABI_VERSION 4
 
 typedef enum {
@@ -736,6 +737,61 @@ int s2r_set_bus_drive_history(s2r_synth *s, uint32_t bus, const float *lr, size_
 int s2r_drive_reference(const float *curve, float pre, float dry, float wet, const float *x_lr, uint32_t frames, float *history, float *out_lr);
 int s2r_drive_taps(float *h);
 int s2r_drive_curve(uint32_t kind, double amount, float *table);
+
+/* BUILD-DEFINED per-bus flanger (the reference has no effects): a modulated feedback comb — one tap at a
+ * triangle-modulated fractional delay into the stage's OWN line signal, fed back — behind the drive and in front of the chorus:
+ * combine -> eq -> dynamics -> drive -> flanger -> chorus -> delay -> reverb -> room -> master -> limiter.  A bus b in
+ * [0, S2R_MAX_BUSES) may carry a flanger: a `base` and a `depth` in frames, finite, with base >= S2R_FLANGER_MIN_DELAY = 32,
+ * depth >= 0 and fl(base + depth) <= S2R_FLANGER_MAX_DELAY = 4095 (the sum rounded to binary32); a `phase_inc` and a `spread`, any
+ * uint32_t, in 2^-32 turns — the LFO's step per frame and the right channel's lead, the chorus's units (s2r_set_bus_chorus); a
+ * `feedback` and a `cross`, each in [-1, 1], with |feedback| + |cross| <= 1 (in double, from the two floats, as the bus delay's);
+ * a `dry` and a `wet` in [0, 1].  State: a `phase` (uint32_t) and a history of H = floor(fl(base + depth)) + 1 stereo frames of the
+ * line signal w — not of the input —, oldest frame first, L then R; 0 and +0.0 right after a set.  With x_c[n] what the stage in front
+ * writes for channel c (0 left, 1 right), frame n of a call of N frames, and w_c[n] for n < 0 the history, per frame, first for both
+ * channels
+ *   p    = phase + c * spread + phase_inc * (uint32)n        (mod 2^32)
+ *   q    = p >> 8;   h = q < 2^23 ? q : 2^24 - q;   m = (float)h * 2^-23         (exact: the chorus's triangle)
+ *   d    = fl(base + fl(depth * m))
+ *   i    = (uint32)d;   f = d - (float)i                      (32 <= i <= H - 1; f exact, in [0, 1))
+ *   a    = w_c[n - i];   bb = w_c[n - i - 1];   tap_c = fl(a + fl(f * fl(bb - a)))
+ * then for both channels
+ *   w_c[n] = fl(x_c[n] + fl(fl(feedback * tap_c) + fl(cross * tap_(1-c))))
+ *   y_c[n] = fl(fl(dry * x_c[n]) + fl(wet * tap_c))
+ * binary32 throughout, every product and sum rounded on its own (no fma), denormals kept, nothing skipped for a zero coefficient or
+ * for f == 0.  Non-finite bus samples are outside the contract.  No tap leaves the history (d <= fl(base + depth) by monotonic
+ * rounding, so i <= H - 1) and none is younger than 32 frames (d >= base >= 32).  After a call that returns S2R_OK the history is the
+ * last H frames of (old history, then w[0 .. N)) and the phase is phase + phase_inc * N: calls of any lengths concatenate.  The stage
+ * runs once per call over all N frames, after every event segment and rows slice has been mixed.  A flanger on a bus >= the call's
+ * n_buses is idle in that call (no output, state untouched).  A bus without a flanger passes through bit for bit, -0.0 included.  A
+ * refused or failed call leaves history and phase untouched.  ONLY s2r_fill_buses and s2r_fill_master apply it; every other fill
+ * ignores it.  A handle on which none was ever set launches what it launched before and allocates nothing for one; device memory is
+ * allocated when a flanger is set (S2R_ERR_OUT_OF_MEMORY when that fails, and the earlier flanger is kept), never in a fill.
+ *   s2r_flanger_history_frames: H for a (base, depth) in range, 0 otherwise; needs no handle.
+ *   s2r_set_bus_flanger: replaces any earlier flanger of the bus, zeroes its history and its phase.  S2R_ERR_PATCH_RANGE for a value
+ *   outside its range, a NaN or bus >= S2R_MAX_BUSES (checked before the handle is looked at; nothing is changed).
+ *   s2r_clear_bus_flanger removes it (S2R_OK on a bus without).
+ *   s2r_set_bus_flanger_params: everything but the two values that fix H; history and phase stay, so rate and resonance move
+ *   without a click.  S2R_ERR_INVALID on a bus without a flanger.
+ *   s2r_get_bus_flanger: base is 0 for a bus without one; any pointer may be NULL.
+ *   s2r_get_bus_flanger_state / s2r_set_bus_flanger_state: the 2 * H floats of the history and the phase.  S2R_ERR_INVALID for a
+ *   capacity below, or a count other than, 2 * H, a NULL lr, and on a bus without a flanger; `phase` may be NULL in the getter.
+ *   Single-device handles (a NULL or a device-list handle: S2R_ERR_INVALID from all six).
+ *   s2r_flanger_reference: the rule above on the host (no device, no handle): x_lr is [frames][2]; history_lr, [H][2], and *phase are
+ *   updated in place; out_lr may be NULL.  Range checks as above; S2R_ERR_INVALID for a NULL history_lr or phase, or a NULL x_lr
+ *   with frames > 0. */
+#define S2R_FLANGER_MIN_DELAY 32.0f
+#define S2R_FLANGER_MAX_DELAY 4095.0f
+uint32_t s2r_flanger_history_frames(float base, float depth);
+int s2r_set_bus_flanger(s2r_synth *s, uint32_t bus, float base, float depth, uint32_t phase_inc, uint32_t spread, float feedback, float cross,
+                        float dry, float wet);
+int s2r_clear_bus_flanger(s2r_synth *s, uint32_t bus);
+int s2r_set_bus_flanger_params(s2r_synth *s, uint32_t bus, uint32_t phase_inc, uint32_t spread, float feedback, float cross, float dry, float wet);
+int s2r_get_bus_flanger(const s2r_synth *s, uint32_t bus, float *base, float *depth, uint32_t *phase_inc, uint32_t *spread, float *feedback,
+                        float *cross, float *dry, float *wet);
+int s2r_get_bus_flanger_state(s2r_synth *s, uint32_t bus, float *lr, size_t capacity, uint32_t *phase);
+int s2r_set_bus_flanger_state(s2r_synth *s, uint32_t bus, const float *lr, size_t count, uint32_t phase);
+int s2r_flanger_reference(float base, float depth, uint32_t phase_inc, uint32_t spread, float feedback, float cross, float dry, float wet,
+                          const float *x_lr, uint32_t frames, float *history_lr, uint32_t *phase, float *out_lr);
 
 /* BUILD-DEFINED master section (the reference's Synth::sample returns one stream; DESIGN.md 4.17 gives the op sequence): the last stage
  * of the chain send -> effect -> return -> master, on the device the bus signals are already on.  Every bus b in [0, S2R_MAX_BUSES) has

@@ -186,6 +186,18 @@ pub mod ffi {
         pub fn s2r_set_bus_chorus_state(s: *mut S2rSynth, bus: u32, lr: *const f32, count: usize, phase: u32) -> c_int;
         pub fn s2r_chorus_reference(voices: u32, base: f32, depth: f32, phase_inc: u32, spread: u32, dry: f32, wet: f32, x_lr: *const f32,
                                     frames: u32, history_lr: *mut f32, phase: *mut u32, out_lr: *mut f32) -> c_int;
+        pub fn s2r_flanger_history_frames(base: f32, depth: f32) -> u32;
+        pub fn s2r_set_bus_flanger(s: *mut S2rSynth, bus: u32, base: f32, depth: f32, phase_inc: u32, spread: u32, feedback: f32, cross: f32,
+                                   dry: f32, wet: f32) -> c_int;
+        pub fn s2r_clear_bus_flanger(s: *mut S2rSynth, bus: u32) -> c_int;
+        pub fn s2r_set_bus_flanger_params(s: *mut S2rSynth, bus: u32, phase_inc: u32, spread: u32, feedback: f32, cross: f32, dry: f32,
+                                          wet: f32) -> c_int;
+        pub fn s2r_get_bus_flanger(s: *const S2rSynth, bus: u32, base: *mut f32, depth: *mut f32, phase_inc: *mut u32, spread: *mut u32,
+                                   feedback: *mut f32, cross: *mut f32, dry: *mut f32, wet: *mut f32) -> c_int;
+        pub fn s2r_get_bus_flanger_state(s: *mut S2rSynth, bus: u32, lr: *mut f32, capacity: usize, phase: *mut u32) -> c_int;
+        pub fn s2r_set_bus_flanger_state(s: *mut S2rSynth, bus: u32, lr: *const f32, count: usize, phase: u32) -> c_int;
+        pub fn s2r_flanger_reference(base: f32, depth: f32, phase_inc: u32, spread: u32, feedback: f32, cross: f32, dry: f32, wet: f32,
+                                     x_lr: *const f32, frames: u32, history_lr: *mut f32, phase: *mut u32, out_lr: *mut f32) -> c_int;
         pub fn s2r_set_bus_eq(s: *mut S2rSynth, bus: u32, n_bands: u32, coeffs: *const f32) -> c_int;
         pub fn s2r_set_bus_eq_coeffs(s: *mut S2rSynth, bus: u32, n_bands: u32, coeffs: *const f32) -> c_int;
         pub fn s2r_get_bus_eq(s: *const S2rSynth, bus: u32, n_bands: *mut u32, coeffs: *mut f32, capacity: usize) -> c_int;
@@ -252,6 +264,10 @@ pub const MAX_DELAY_FRAMES: u32 = 262144;
 /// frames.
 pub const CHORUS_MAX_VOICES: u32 = 8;
 pub const CHORUS_MAX_DELAY: f32 = 4095.0;
+/// `S2R_FLANGER_MIN_DELAY`, `S2R_FLANGER_MAX_DELAY`: the least `base` of a bus flanger, and the largest `base + depth` (rounded to f32),
+/// in frames.
+pub const FLANGER_MIN_DELAY: f32 = 32.0;
+pub const FLANGER_MAX_DELAY: f32 = 4095.0;
 /// `S2R_EQ_MAX_BANDS`: the most biquad bands of a bus EQ, and the kinds of `s2r_eq_kind`.
 pub const EQ_MAX_BANDS: u32 = 4;
 pub const EQ_PEAK: i32 = 0;
@@ -325,6 +341,26 @@ pub fn chorus_reference(voices: u32, base: f32, depth: f32, phase_inc: u32, spre
     let rc = unsafe {
         ffi::s2r_chorus_reference(voices, base, depth, phase_inc, spread, dry, wet, x_lr.as_ptr(), (x_lr.len() / 2) as u32, history_lr.as_mut_ptr(),
                                   phase as *mut u32, out.as_mut_ptr())
+    };
+    if rc == 0 { Ok(out) } else { Err(rc) }
+}
+
+/// `s2r_flanger_history_frames`: the stereo frames of its line signal a flanger of (`base`, `depth`) keeps, or 0 for a pair out of range.
+pub fn flanger_history_frames(base: f32, depth: f32) -> u32 {
+    unsafe { ffi::s2r_flanger_history_frames(base, depth) }
+}
+
+/// Host-only: the bus flanger's rule (`s2r_flanger_reference`).  `x_lr`: L, R pairs; `history_lr`: the
+/// `2 * flanger_history_frames(base, depth)` floats of the stage's line signal in front of them, oldest frame first, and `phase` the
+/// LFO's at the first pair: both updated in place to the state after the call; returns one output pair per input pair, or the status.
+pub fn flanger_reference(base: f32, depth: f32, phase_inc: u32, spread: u32, feedback: f32, cross: f32, dry: f32, wet: f32, x_lr: &[f32],
+                         history_lr: &mut [f32], phase: &mut u32) -> Result<Vec<f32>, i32> {
+    let h = flanger_history_frames(base, depth) as usize;
+    assert!(x_lr.len() % 2 == 0 && (h == 0 || history_lr.len() == 2 * h));
+    let mut out = vec![0.0f32; x_lr.len()];
+    let rc = unsafe {
+        ffi::s2r_flanger_reference(base, depth, phase_inc, spread, feedback, cross, dry, wet, x_lr.as_ptr(), (x_lr.len() / 2) as u32,
+                                   history_lr.as_mut_ptr(), phase as *mut u32, out.as_mut_ptr())
     };
     if rc == 0 { Ok(out) } else { Err(rc) }
 }
@@ -762,6 +798,46 @@ pub mod synth {
 
         pub fn set_bus_chorus_state(&mut self, bus: u32, lr: &[f32], phase: u32) {
             self.check(unsafe { ffi::s2r_set_bus_chorus_state(self.handle, bus, lr.as_ptr(), lr.len(), phase) });
+        }
+
+        /// Build-defined per-bus flanger (`s2r_set_bus_flanger`, include/s2r.h) behind the bus's drive and in front of its chorus: one
+        /// tap `base + depth * triangle` frames late (`base >= FLANGER_MIN_DELAY`, `depth >= 0`, `base + depth` rounded to f32
+        /// `<= FLANGER_MAX_DELAY`) into the stage's own line signal, fed back by `feedback` and into the other channel by `cross` (each
+        /// in [-1, 1], `|feedback| + |cross| <= 1`); `phase_inc` (`chorus_rate`) and `spread` in 2^-32 turns, dry and wet in [0, 1];
+        /// replaces any earlier flanger of the bus and zeroes its line and phase.  In `sample_buses` and `sample_master` only.
+        pub fn set_bus_flanger(&mut self, bus: u32, base: f32, depth: f32, phase_inc: u32, spread: u32, feedback: f32, cross: f32, dry: f32, wet: f32) {
+            self.check(unsafe { ffi::s2r_set_bus_flanger(self.handle, bus, base, depth, phase_inc, spread, feedback, cross, dry, wet) });
+        }
+
+        pub fn clear_bus_flanger(&mut self, bus: u32) {
+            self.check(unsafe { ffi::s2r_clear_bus_flanger(self.handle, bus) });
+        }
+
+        /// Everything but `base` and `depth`; line and phase stay, so rate and resonance move without a click.
+        pub fn set_bus_flanger_params(&mut self, bus: u32, phase_inc: u32, spread: u32, feedback: f32, cross: f32, dry: f32, wet: f32) {
+            self.check(unsafe { ffi::s2r_set_bus_flanger_params(self.handle, bus, phase_inc, spread, feedback, cross, dry, wet) });
+        }
+
+        /// (base, depth, phase_inc, spread, feedback, cross, dry, wet); base is 0 for a bus without a flanger.
+        pub fn get_bus_flanger(&self, bus: u32) -> (f32, f32, u32, u32, f32, f32, f32, f32) {
+            let (mut base, mut depth, mut fb, mut cr, mut dry, mut wet) = (0.0f32, 0.0f32, 0.0f32, 0.0f32, 0.0f32, 0.0f32);
+            let (mut pi, mut sp) = (0u32, 0u32);
+            self.check(unsafe { ffi::s2r_get_bus_flanger(self.handle, bus, &mut base, &mut depth, &mut pi, &mut sp, &mut fb, &mut cr, &mut dry, &mut wet) });
+            (base, depth, pi, sp, fb, cr, dry, wet)
+        }
+
+        /// The `2 * flanger_history_frames(base, depth)` floats of the flanger's line, oldest frame first, L then R, and the LFO's
+        /// phase: checkpoint companion of `bus_chorus_state`.
+        pub fn bus_flanger_state(&mut self, bus: u32) -> (Vec<f32>, u32) {
+            let c = self.get_bus_flanger(bus);
+            let mut lr = vec![0.0f32; 2 * super::flanger_history_frames(c.0, c.1) as usize];
+            let mut phase = 0u32;
+            self.check(unsafe { ffi::s2r_get_bus_flanger_state(self.handle, bus, lr.as_mut_ptr(), lr.len(), &mut phase) });
+            (lr, phase)
+        }
+
+        pub fn set_bus_flanger_state(&mut self, bus: u32, lr: &[f32], phase: u32) {
+            self.check(unsafe { ffi::s2r_set_bus_flanger_state(self.handle, bus, lr.as_ptr(), lr.len(), phase) });
         }
 
         /// Build-defined per-bus parametric EQ (`s2r_set_bus_eq`, include/s2r.h) at the head of the chain, in front of the bus's

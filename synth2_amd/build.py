@@ -23,7 +23,8 @@ SOURCES = ["s2r_render_onepole_square.hip", "s2r_render_onepole_saw.hip", "s2r_r
            "s2r_stream.cpp",
            "s2r_dyn.hip",       # (behind the rest: every object in front of it keeps the place in the library it had before the dynamics came)
            "s2r_room.hip",      # (likewise, since the room came)
-           "s2r_drive.hip"]     # (last, likewise, since the drive came)
+           "s2r_drive.hip",     # (likewise, since the drive came)
+           "s2r_flanger.hip"]   # (last, likewise, since the flanger came)
 HEADERS = ["s2r_device.h", "s2r_math.h", "s2r_patch.h", "s2r_voices.h", "s2r_kern_common.h", "s2r_render_onepole.inc",
            "s2r_render_general.inc", "s2r_post.h", "s2r_post_route.h", "s2r_rules.h"]
 
@@ -53,7 +54,7 @@ PER_FILE_FLAGS = {}
 for _f in ("s2r_render_general_square.hip", "s2r_render_general_saw.hip", "s2r_render_general_triangle.hip", "s2r_render_general_sine.hip",
            "s2r_render_general_bank.hip"):
     PER_FILE_FLAGS[_f] = ["-ftrivial-auto-var-init=zero"]
-# Ten translation units are compiled with the back end's resource-usage remarks, and _check_resources() fails the build when a
+# Eleven translation units are compiled with the back end's resource-usage remarks, and _check_resources() fails the build when a
 # kernel named here went to scratch or spilled, or when fewer kernels report than the file instantiates.  Per source file: the
 # substrings that name its checked kernels; how many reports are expected — ("at least", n), ("exactly", n), or ("each", None):
 # one or more of every name — and why so many; the figures that must be "0"; and what the kernels keep where it belongs.  (The
@@ -81,6 +82,10 @@ RESOURCE_CHECKS = {
     # SGPRs (156 VGPRs, 102 SGPRs, 14 480 bytes of LDS)
     "s2r_drive.hip": (("s2r_drive_kernel",), ("exactly", 1), "one kernel",
                       (_SCRATCH, _VSPILL, _SSPILL), "its inputs and sums must stay in registers, tiles, table and phase planes in LDS"),
+    # a frame of one channel per lane: its two tap addresses, fraction and write address computed a tile ahead, its input loaded
+    # four tiles ahead; the line's window of 4096 frames in LDS
+    "s2r_flanger.hip": (("s2r_flanger_kernel",), ("exactly", 1), "one kernel",
+                        (_SCRATCH, _VSPILL, _SSPILL), "its addresses, fractions and the inputs loaded ahead must stay in registers, the line's window in LDS"),
     # one frame of the chorus per thread: both channels, up to eight voices, two taps each
     "s2r_chorus.hip": (("s2r_chorus_kernel",), ("exactly", 1), "one kernel",
                        (_SCRATCH, _VSPILL, _SSPILL), "its phases, taps and sums must stay in registers"),
@@ -122,6 +127,11 @@ if _DRIVE_SERIAL:
     PER_FILE_FLAGS["s2r_drive.hip"] = PER_FILE_FLAGS["s2r_drive.hip"] + ["-DS2R_DRIVE_SERIAL"]
 if _DRIVE_INTERLEAVED:
     PER_FILE_FLAGS["s2r_drive.hip"] = PER_FILE_FLAGS["s2r_drive.hip"] + ["-DS2R_DRIVE_INTERLEAVED"]
+# S2R_FLANGER_SERIAL=1 likewise builds the flanger kernel's obvious form (one lane per bus and channel steps frame by frame, the line in
+# global memory; csrc/s2r_flanger.hip, CHANGELOG) into libs2r_flangerserial.so, for tools/flanger_time.py.  Never the product build.
+_FLANGER_SERIAL = os.environ.get("S2R_FLANGER_SERIAL") == "1"
+if _FLANGER_SERIAL:
+    PER_FILE_FLAGS["s2r_flanger.hip"] = PER_FILE_FLAGS["s2r_flanger.hip"] + ["-DS2R_FLANGER_SERIAL"]
 # S2R_OPT=O3 in the environment builds the same sources at -O3 into libs2r_o3.so (tools and tests that compare the two
 # optimisation levels; the product is -O2).
 if os.environ.get("S2R_OPT") == "O3":
@@ -150,6 +160,9 @@ elif _DRIVE_SERIAL:
 elif _DRIVE_INTERLEAVED:
     LIB = os.path.join(HERE, "libs2r_driveinterleaved.so")
     OBJ_DIR_NAME = "_build_driveinterleaved"
+elif _FLANGER_SERIAL:
+    LIB = os.path.join(HERE, "libs2r_flangerserial.so")
+    OBJ_DIR_NAME = "_build_flangerserial"
 else:
     OBJ_DIR_NAME = "_build"
 

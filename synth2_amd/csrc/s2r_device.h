@@ -563,6 +563,30 @@ struct S2rDrive {
 // hipErrorInvalidValue for a null pointer, in == out, line == next, n_buses past S2R_MAX_BUSES or no drive at all among the call's buses
 hipError_t s2r_launch_bus_drive(const S2rDrive &a, hipStream_t stream);
 
+// The per-bus flanger behind the drive: one tap at a modulated fractional delay of at least S2R_FLANGER_MIN_DELAY = 32
+// frames into the stage's own line signal w, fed back.  A bus's line holds the last `history` frames of w, [H][2], oldest first; `next`
+// receives the line the next call starts from (the host swaps the two).  No frame reads a frame of w younger than 32 frames: the frames
+// of a tile of S2R_FLANGER_TILE are independent of one another.
+#define S2R_FLANGER_TILE 32u
+struct S2rFlangerBus {
+    const float *line;            // [history][2]; null: no flanger on this bus: it is copied from `in` to `out`
+    float *next;                  // the same size, not `line`
+    uint32_t history;             // H: 33 .. 4096
+    uint32_t phase, phase_inc, spread;
+    float base, depth, feedback, cross, dry, wet;
+};
+struct S2rFlanger {
+    S2rFlangerBus bus[S2R_MAX_BUSES];
+    float *in;                    // [n_buses][2 * frames]: what the stage in front wrote; bus-major, L, R interleaved inside a bus (the
+                                  // product's kernel only reads it; the serial form keeps the call's w in it)
+    float *out;                   // the same layout, not `in`
+    uint32_t n_buses, frames;
+};
+// one kernel, one wavefront per bus with a flanger and further workgroups that copy the buses without: the outputs and next lines of the
+// buses with a flanger, the other buses unchanged; hipErrorInvalidValue for a null pointer, in == out, line == next, a history outside
+// [33, 4096], n_buses past S2R_MAX_BUSES or no flanger at all among the call's buses
+hipError_t s2r_launch_bus_flanger(const S2rFlanger &a, hipStream_t stream);
+
 // The master section of s2r_fill_master: the stems of a call, post-effect, each times its return's ramp, added in
 // bus order from +0.0, times the master fader's ramp; and the call's meters.  gain at frame i of the CALL: r0 + (float)i * dr (the
 // product rounded, then the sum); a pair that did not move has dr = +0.0.

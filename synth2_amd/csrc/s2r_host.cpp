@@ -2733,10 +2733,11 @@ static int post_handle(const s2r_synth *s, const char *who, const char *what) {
 }
 
 // the words in which the entries of a stem stage differ
-static const struct { const char *one, *are; } kStemWords[S2R_STEM_STAGES + 1] = {{"chorus", "bus choruses are"}, {"delay", "bus delays are"}, {"reverb", "bus reverbs are"},
-                                                                                  {"drive", "bus drives are"}};
+static const struct { const char *one, *are; } kStemWords[S2R_STEM_STAGES + 2] = {{"chorus", "bus choruses are"}, {"delay", "bus delays are"}, {"reverb", "bus reverbs are"},
+                                                                                  {"drive", "bus drives are"}, {"flanger", "bus flangers are"}};
 // (the drive is no stem stage — s2r_post_route.h —, but its entries are guarded like theirs: S2rPostChain::bus answers for it at this index)
 static const S2rStemStage kDriveEntry = S2R_STEM_STAGES;
+static const S2rStemStage kFlangerEntry = (S2rStemStage)(S2R_STEM_STAGES + 1);     // (and so is the flanger, behind it)
 
 // The guard of an entry that reads or changes the effect one bus carries: the bus in range, a single-device handle, and the bus
 // carries one.  `who` null: a getter, which answers for a bus without one too and leaves the handle's error text alone; `named`:
@@ -3731,6 +3732,11 @@ extern "C" uint32_t s2r_debug_room_tile(void) { return S2R_ROOM_TILE; }
 extern "C" float s2r_debug_bus_drive_ms(const s2r_synth *s) { return s && s->timing ? s->post.drive_insert.timer.ms : -1.0f; }
 extern "C" int s2r_debug_drive_allocated(const s2r_synth *s) { return s && (s->post.drive_insert.stage || s->post.drive_curves) ? 1 : 0; }
 extern "C" uint32_t s2r_debug_drive_tile(void) { return S2R_DRIVE_TILE; }
+// ... of the buses' flanger kernel in that fill: 0 when it ran none (tools/flanger_time.py); whether the handle holds the flangers'
+// staging buffer; and the frames of one tile of the kernel (tests/test_gpu_flanger.py picks its call lengths around it)
+extern "C" float s2r_debug_bus_flanger_ms(const s2r_synth *s) { return s && s->timing ? s->post.flanger_insert.timer.ms : -1.0f; }
+extern "C" int s2r_debug_flanger_allocated(const s2r_synth *s) { return s && s->post.flanger_insert.stage ? 1 : 0; }
+extern "C" uint32_t s2r_debug_flanger_tile(void) { return S2R_FLANGER_TILE; }
 // ... of the buses' chorus kernel in that fill: 0 when it ran none (tools/chorus_time.py)
 extern "C" float s2r_debug_bus_chorus_ms(const s2r_synth *s) { return s && s->timing ? s->post.stem[S2R_STEM_CHORUS].timer.ms : -1.0f; }
 // ... of the buses' delay kernel in that fill: 0 when it ran none (tools/delay_time.py)
@@ -3877,4 +3883,58 @@ int s2r_get_bus_drive_history(s2r_synth *s, uint32_t bus, float *lr, size_t capa
 
 int s2r_set_bus_drive_history(s2r_synth *s, uint32_t bus, const float *lr, size_t count) {
     return drive_history(s, bus, nullptr, lr, lr ? count : (size_t)-1, "s2r_set_bus_drive_history");
+}
+
+// ---- per-bus flangers: the fifth insert, behind the drives and in front of the choruses.  At the end of the file, likewise ----
+static int flanger_levels(s2r_synth *s, const char *who, uint32_t bus, float feedback, float cross, float dry, float wet) {
+    if (bus >= S2R_MAX_BUSES || !delay_mix_in_range(feedback, cross, dry, wet))
+        return set_err(s, S2R_ERR_PATCH_RANGE, "%s: bus %u, feedback %g, cross %g, dry %g, wet %g: feedback and cross in [-1, 1] with |feedback| + |cross| <= 1, dry and "
+                       "wet in [0, 1], the bus below %u", who, bus, (double)feedback, (double)cross, (double)dry, (double)wet, S2R_MAX_BUSES);
+    return S2R_OK;
+}
+
+int s2r_set_bus_flanger(s2r_synth *s, uint32_t bus, float base, float depth, uint32_t phase_inc, uint32_t spread, float feedback, float cross, float dry,
+                        float wet) {
+    if (!flanger_delay_in_range(base, depth))
+        return set_err(s, S2R_ERR_PATCH_RANGE, "s2r_set_bus_flanger: bus %u, base %g, depth %g: base >= %g and depth >= 0 with base + depth <= %g frames", bus,
+                       (double)base, (double)depth, (double)S2R_FLANGER_MIN_DELAY, (double)S2R_FLANGER_MAX_DELAY);
+    S2R_TRY(flanger_levels(s, "s2r_set_bus_flanger", bus, feedback, cross, dry, wet));
+    S2R_TRY(post_handle(s, "s2r_set_bus_flanger", kStemWords[kFlangerEntry].are));
+    return stem_set(s, "s2r_set_bus_flanger", [&](const S2rPostCtx &c) { return s->post.set_flanger(c, bus, base, depth, phase_inc, spread, feedback, cross, dry, wet); });
+}
+
+int s2r_clear_bus_flanger(s2r_synth *s, uint32_t bus) {
+    if (bus >= S2R_MAX_BUSES) return set_err(s, S2R_ERR_PATCH_RANGE, "s2r_clear_bus_flanger: bus %u, below %u", bus, S2R_MAX_BUSES);
+    S2R_TRY(post_handle(s, "s2r_clear_bus_flanger", kStemWords[kFlangerEntry].are));
+    return stem_set(s, "s2r_clear_bus_flanger", [&](const S2rPostCtx &c) { return s->post.set_flanger(c, bus, -1.0f, 0.0f, 0, 0, 0.0f, 0.0f, 0.0f, 0.0f); });
+}
+
+int s2r_set_bus_flanger_params(s2r_synth *s, uint32_t bus, uint32_t phase_inc, uint32_t spread, float feedback, float cross, float dry, float wet) {
+    S2R_TRY(flanger_levels(s, "s2r_set_bus_flanger_params", bus, feedback, cross, dry, wet));
+    S2R_TRY(stem_bus(s, kFlangerEntry, bus, "s2r_set_bus_flanger_params", true));
+    S2rPostChain::BusFlanger &d = s->post.flanger[bus];          // (the phase and the line stay: the LFO bends, the comb retunes, nothing clicks)
+    d.phase_inc = phase_inc; d.spread = spread; d.feedback = feedback; d.cross = cross; d.dry = dry; d.wet = wet;
+    return S2R_OK;
+}
+
+int s2r_get_bus_flanger(const s2r_synth *s, uint32_t bus, float *base, float *depth, uint32_t *phase_inc, uint32_t *spread, float *feedback, float *cross,
+                        float *dry, float *wet) {
+    S2R_TRY(stem_bus(s, kFlangerEntry, bus, nullptr, false));
+    const S2rPostChain::BusFlanger &d = s->post.flanger[bus];
+    put(base, d.base); put(depth, d.depth); put(phase_inc, d.phase_inc); put(spread, d.spread); put(feedback, d.feedback); put(cross, d.cross);
+    put(dry, d.dry); put(wet, d.wet);
+    return S2R_OK;
+}
+
+// (the flanger's phase lives on the host, as the chorus's)
+int s2r_get_bus_flanger_state(s2r_synth *s, uint32_t bus, float *lr, size_t capacity, uint32_t *phase) {
+    S2R_TRY(stem_history(s, kFlangerEntry, bus, lr, nullptr, capacity, "s2r_get_bus_flanger_state"));
+    put(phase, s->post.flanger[bus].phase);
+    return S2R_OK;
+}
+
+int s2r_set_bus_flanger_state(s2r_synth *s, uint32_t bus, const float *lr, size_t count, uint32_t phase) {
+    S2R_TRY(stem_history(s, kFlangerEntry, bus, nullptr, lr, lr ? count : (size_t)-1, "s2r_set_bus_flanger_state"));
+    s->post.flanger[bus].phase = phase;
+    return S2R_OK;
 }

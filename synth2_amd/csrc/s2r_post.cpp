@@ -1,4 +1,4 @@
-// s2r_post.cpp — the post-mix chain (s2r_post.h): the EQs, the dynamics, the drives, the stem stages (choruses, delays, reverbs), the rooms, master section, master limiter.  Compiled with hipcc, -ffp-contract=off.
+// s2r_post.cpp — the post-mix chain (s2r_post.h): the EQs, the dynamics, the drives, the flangers, the stem stages (choruses, delays, reverbs), the rooms, master section, master limiter.  Compiled with hipcc, -ffp-contract=off.
 #include "s2r_post.h"
 #include "s2r_rules.h"
 
@@ -71,6 +71,7 @@ hipError_t S2rPostChain::prepare(const S2rPostCtx &c, uint32_t n_buses, uint32_t
     for (uint32_t b = 0; b < n_buses; b++) if (dyn_runs(b, n_buses)) call.dyn = true;                // (and dynamics, also when their key bus is past the call's)
     for (uint32_t b = 0; b < n_buses; b++) if (room[b].present()) call.room = true;                  // (and a room)
     for (uint32_t b = 0; b < n_buses; b++) if (drive[b].present()) call.drive = true;                // (and a drive)
+    for (uint32_t b = 0; b < n_buses; b++) if (flanger[b].present()) call.flanger = true;            // (and a flanger)
     call.limited = master_fill && limiter.lookahead != 0;
     if (call.master) {                                           // the device copy of the stems and the pinned rows of block partials
         if (!master.stage) POST_HIP(hipMalloc((void **)&master.stage, (size_t)2 * S2R_MAX_BUSES * c.max_frames * sizeof(float)));
@@ -83,13 +84,13 @@ hipError_t S2rPostChain::prepare(const S2rPostCtx &c, uint32_t n_buses, uint32_t
     }
     float *stages[S2R_STEM_STAGES];
     for (int k = 0; k < S2R_STEM_STAGES; k++) stages[k] = stem[k].stage;
-    call.route = s2r_post_route_drive(call, s2r_post_route_room(call, s2r_post_route_dyn(call, s2r_post_route_eq(call, s2r_post_route(call, stages, master.stage, limiter.in, c.bus_out_dev, c.out_host_dev),
-                                                                                      eq_insert.stage), dyn_insert.stage), room_insert.stage), drive_insert.stage);
+    call.route = s2r_post_route_flanger(call, s2r_post_route_drive(call, s2r_post_route_room(call, s2r_post_route_dyn(call, s2r_post_route_eq(call, s2r_post_route(call, stages, master.stage, limiter.in, c.bus_out_dev, c.out_host_dev),
+                                                                                      eq_insert.stage), dyn_insert.stage), room_insert.stage), drive_insert.stage), flanger_insert.stage);
     return hipSuccess;
 }
 
 hipError_t S2rPostChain::launch(const S2rPostCtx &c, const S2rPostCall &call) {
-    const S2rPostRouteDrive &r = call.route; const float fn = (float)call.frames;
+    const S2rPostRouteFlanger &r = call.route; const float fn = (float)call.frames;
     if (call.eq) {                                               // once per call, over all of its frames, in front of every stem stage
         S2rEq a{};
         for (uint32_t b = 0; b < call.n_buses; b++) {
@@ -115,6 +116,7 @@ hipError_t S2rPostChain::launch(const S2rPostCtx &c, const S2rPostCall &call) {
         POST_TIMED(c, dyn_insert.timer, s2r_launch_bus_dyn(a, c.stream));
     }
     if (call.drive) POST_HIP(launch_drive(c, call));             // likewise, behind the dynamics: tiles x buses workgroups, none waiting for another
+    if (call.flanger) POST_HIP(launch_flanger(c, call));         // likewise, behind the drive: a wavefront per bus, tile by tile
     if (call.on[S2R_STEM_CHORUS]) {                              // likewise, in front of the delays
         S2rChorus a{};
         for (uint32_t b = 0; b < call.n_buses; b++) {
@@ -199,6 +201,8 @@ void S2rPostChain::commit(const S2rPostCall &call) {
     if (call.dyn)                                                // ... the dynamics' gains, and the kernel's minima are the call's meters
         for (uint32_t b = 0; b < call.n_buses; b++) if (dyn_runs(b, call.n_buses)) { dyn[b].flip(); dyn[b].min_gain = dyn_meter[b]; }
     if (call.drive) for (uint32_t b = 0; b < call.n_buses; b++) if (drive[b].present()) drive[b].flip();   // ... the drives' histories
+    if (call.flanger)                                            // ... the flangers' lines and their phases
+        for (uint32_t b = 0; b < call.n_buses; b++) if (flanger[b].present()) { flanger[b].flip(); flanger[b].phase += flanger[b].phase_inc * call.frames; }
     for (int k = 0; k < S2R_STEM_STAGES; k++)                    // the histories have moved on
         if (call.on[k]) for (uint32_t b = 0; b < call.n_buses; b++) if (bus(k, b).present()) bus(k, b).flip();
     if (call.on[S2R_STEM_CHORUS])                                // ... and the choruses' phases
@@ -232,11 +236,12 @@ void S2rPostChain::commit(const S2rPostCall &call) {
     }
 }
 
-// a stage that the fill could have run and did not reads 0; a panned fill leaves all nine values alone, a bus fill the master's two
+// a stage that the fill could have run and did not reads 0; a panned fill leaves all ten values alone, a bus fill the master's two
 hipError_t S2rPostChain::read_timers(const S2rPostCall &call) {
     if (call.n_buses) { eq_insert.timer.ms = 0.0f; if (call.eq) POST_HIP(eq_insert.timer.read()); }
     if (call.n_buses) { dyn_insert.timer.ms = 0.0f; if (call.dyn) POST_HIP(dyn_insert.timer.read()); }
     if (call.n_buses) { drive_insert.timer.ms = 0.0f; if (call.drive) POST_HIP(drive_insert.timer.read()); }
+    if (call.n_buses) { flanger_insert.timer.ms = 0.0f; if (call.flanger) POST_HIP(flanger_insert.timer.read()); }
     if (call.n_buses) for (int k = 0; k < S2R_STEM_STAGES; k++) { stem[k].timer.ms = 0.0f; if (call.on[k]) POST_HIP(stem[k].timer.read()); }
     if (call.n_buses) { room_insert.timer.ms = 0.0f; if (call.room) POST_HIP(room_insert.timer.read()); }
     if (call.master) {
@@ -248,7 +253,7 @@ hipError_t S2rPostChain::read_timers(const S2rPostCall &call) {
 }
 
 void S2rPostChain::release() {
-    for (uint32_t b = 0; b < S2R_MAX_BUSES; b++) { drop(eq[b]); drop(dyn[b]); drop(chorus[b]); drop(delay[b]); drop(fx[b]); drop(room[b]); drop(drive[b]); }
+    for (uint32_t b = 0; b < S2R_MAX_BUSES; b++) { drop(eq[b]); drop(dyn[b]); drop(chorus[b]); drop(delay[b]); drop(fx[b]); drop(room[b]); drop(drive[b]); drop(flanger[b]); }
     for (Stem &st : stem) { if (st.stage) (void)hipFree(st.stage); st.timer.destroy(); }
     if (eq_insert.stage) (void)hipFree(eq_insert.stage);
     eq_insert.timer.destroy();
@@ -259,6 +264,8 @@ void S2rPostChain::release() {
     room_insert.timer.destroy();
     for (float *p : {drive_insert.stage, drive_curves}) if (p) (void)hipFree(p);
     drive_insert.timer.destroy();
+    if (flanger_insert.stage) (void)hipFree(flanger_insert.stage);
+    flanger_insert.timer.destroy();
     for (float *p : {master.stage, limiter.state[0], limiter.state[1], limiter.in}) if (p) (void)hipFree(p);
     for (float *p : {master.partials, limiter.partials}) if (p) (void)hipHostFree(p);
     for (S2rPostTimer *t : {&master.timer, &limiter.timer}) t->destroy();
@@ -372,7 +379,7 @@ hipError_t S2rPostChain::set_reverb(const S2rPostCtx &c, uint32_t bus, const flo
 hipError_t S2rPostChain::history(const S2rPostCtx &c, int k, uint32_t bus, float *get, const float *set) {
     const S2rBusLine &f = this->bus(k, bus);
     const size_t h = f.history;
-    if (k != S2R_STEM_REVERB) {
+    if (k != S2R_STEM_REVERB) {                                  // (the drive and the flanger, behind the stem stages, among them)
         POST_HIP(f.copy(get, set, 0, 2 * h, c.stream));
         return hipStreamSynchronize(c.stream);
     }
@@ -460,4 +467,31 @@ hipError_t S2rPostChain::set_drive(const S2rPostCtx &c, uint32_t bus, const floa
     return replace(c, drive_insert.stage, drive[bus], f, 2u * (size_t)S2R_DRIVE_HISTORY, [&](BusDrive &n) {
         return hipMemcpyAsync(to, n.curve.data(), kRow * sizeof(float), hipMemcpyHostToDevice, c.stream);
     });
+}
+
+// The flanger's launch and its setter, likewise at the end and out of line.
+__attribute__((noinline)) hipError_t S2rPostChain::launch_flanger(const S2rPostCtx &c, const S2rPostCall &call) {
+    const S2rPostRouteFlanger &r = call.route;
+    S2rFlanger a{};
+    for (uint32_t b = 0; b < call.n_buses; b++) {
+        const BusFlanger &f = flanger[b];
+        if (!f.present()) continue;
+        S2rFlangerBus &d = a.bus[b];
+        d.line = f.now(); d.next = f.next(); d.history = f.history;
+        d.phase = f.phase; d.phase_inc = f.phase_inc; d.spread = f.spread;
+        d.base = f.base; d.depth = f.depth; d.feedback = f.feedback; d.cross = f.cross; d.dry = f.dry; d.wet = f.wet;
+    }
+    a.in = r.flanger.in; a.out = r.flanger.out; a.n_buses = call.n_buses; a.frames = call.frames;
+    POST_TIMED(c, flanger_insert.timer, s2r_launch_bus_flanger(a, c.stream));
+    return hipSuccess;
+}
+
+// the line starts as +0.0 and the phase as 0 (replace); the other copy is written whole by the first call
+hipError_t S2rPostChain::set_flanger(const S2rPostCtx &c, uint32_t bus, float base, float depth, uint32_t phase_inc, uint32_t spread, float feedback, float cross,
+                                     float dry, float wet) {
+    if (base < 0.0f) { drop(flanger[bus]); return hipSuccess; }
+    BusFlanger f;
+    f.history = flanger_history(base, depth); f.base = base; f.depth = depth; f.feedback = feedback; f.cross = cross; f.dry = dry; f.wet = wet;
+    f.phase_inc = phase_inc; f.spread = spread;
+    return replace(c, flanger_insert.stage, flanger[bus], f, 2u * (size_t)f.history, nothing_more);
 }

@@ -1,7 +1,7 @@
 // s2r_post.h — the chain behind the bus mixdown of s2r_fill_buses and s2r_fill_master: the buses' equalisers and their
 // dynamics (4.22), two inserts at the head of the stem stages (s2r_post_route.h) — the buses' choruses (4.20), their feedback delays
 // (4.19), their convolution reverbs (4.16) —, the buses' rooms (4.23), an insert behind them, the master section (4.17) and the master limiter (4.18), in that order; the
-// buses' drives (4.24) are a fourth insert, behind the dynamics.  The chain owns what the nine stages own
+// buses' drives (4.24) are a fourth insert, behind the dynamics, and their flangers (4.25) a fifth, behind the drives.  The chain owns what the ten stages own
 // and knows nothing of the handle: its functions take a S2rPostCtx and return the HIP error.  Per call: prepare, launch, — the caller's synchronise — commit, read_timers.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -100,9 +100,9 @@ struct S2rPostChain {
         void free() { if (work) (void)hipFree(work); work = nullptr; S2rBusLine::free(); }
     } room[S2R_MAX_BUSES];
     Stem room_insert;                            // (its timer: tools/room_time.py)
-    // stage k's effect on a bus, as far as the stages are alike; behind the stem stages, at S2R_STEM_STAGES, the drive, whose history
-    // has their form (the loops over the stem stages do not reach it)
-    S2rBusLine &bus(int k, uint32_t b) { S2rBusLine *const of[S2R_STEM_STAGES + 1] = {&chorus[b], &delay[b], &fx[b], &drive[b]}; return *of[k]; }
+    // stage k's effect on a bus, as far as the stages are alike; behind the stem stages, at S2R_STEM_STAGES, the drive, and behind it
+    // the flanger, whose histories have their form (the loops over the stem stages do not reach them)
+    S2rBusLine &bus(int k, uint32_t b) { S2rBusLine *const of[S2R_STEM_STAGES + 2] = {&chorus[b], &delay[b], &fx[b], &drive[b], &flanger[b]}; return *of[k]; }
     const S2rBusLine &bus(int k, uint32_t b) const { return const_cast<S2rPostChain *>(this)->bus(k, b); }
     // The master section.  Nothing is allocated before the first master fill.
     struct Master {
@@ -139,6 +139,7 @@ struct S2rPostChain {
     hipError_t prepare(const S2rPostCtx &c, uint32_t n_buses, uint32_t frames, bool master_fill, bool stems, S2rPostCall &call);
     hipError_t launch(const S2rPostCtx &c, const S2rPostCall &call);
     hipError_t launch_drive(const S2rPostCtx &c, const S2rPostCall &call);      // the drive's part of launch, out of line
+    hipError_t launch_flanger(const S2rPostCtx &c, const S2rPostCall &call);    // the flanger's, likewise
     void commit(const S2rPostCall &call);
     hipError_t read_timers(const S2rPostCall &call);
     void release();
@@ -173,4 +174,16 @@ struct S2rPostChain {
     } drive[S2R_MAX_BUSES];
     Stem drive_insert;                           // (its timer: tools/drive_time.py)
     float *drive_curves = nullptr;               // [S2R_MAX_BUSES][S2R_DRIVE_CURVE_POINTS] in device memory, allocated when a drive is first set
+    // The flangers (s2r_set_bus_flanger): lines of [H][2], the last frames of the stage's line signal w, oldest first, L then R, H =
+    // history = floor(fl(base + depth)) + 1.  The fifth insert, behind the drive (s2r_post_route_flanger), with a staging buffer and a
+    // timer of its own.  (Again behind everything else.)  Its history goes through history() at k = S2R_STEM_STAGES + 1
+    struct BusFlanger : S2rBusLine {
+        float base = 0.0f, depth = 0.0f, feedback = 0.0f, cross = 0.0f, dry = 0.0f, wet = 0.0f;
+        uint32_t phase_inc = 0, spread = 0;
+        uint32_t phase = 0;                      // the LFO's phase at frame 0 of the next call: moved on by the commit
+    } flanger[S2R_MAX_BUSES];
+    Stem flanger_insert;                         // (its timer: tools/flanger_time.py)
+    // base < 0: removes the bus's flanger
+    hipError_t set_flanger(const S2rPostCtx &c, uint32_t bus, float base, float depth, uint32_t phase_inc, uint32_t spread, float feedback, float cross, float dry,
+                           float wet);
 };

@@ -1,5 +1,7 @@
 // s2r_post_route.h — who reads and writes what in one call of the post-mix chain (s2r_post.h): plain pointers and integers, nothing of
-// HIP, so that the rule is checked by a program of its own on the CPU (tests/native/post_route.cpp).
+// HIP, so that the rule is checked by a program of its own on the CPU (tests/native/post_route.cpp).  The route grows by inserts, each a
+// struct on top of the last and a function applied after the last: the EQ, the dynamics, the room, the drive and the flanger, in the
+// order they came; the chain launches combine, EQ, dynamics, drive, flanger, the stem stages, room, master, limiter.
 #pragma once
 #include <cstdint>
 
@@ -27,6 +29,10 @@ struct S2rPostRouteRoom : S2rPostRouteDyn {
 struct S2rPostRouteDrive : S2rPostRouteRoom {
     struct { float *in, *out; } drive;
 };
+// ... and the flanger insert behind the drive (s2r_post_route_flanger): null unless the call runs it.  Again a struct of its own on top
+struct S2rPostRouteFlanger : S2rPostRouteDrive {
+    struct { float *in, *out; } flanger;
+};
 struct S2rPostCall {                             // one fill, as prepare leaves it
     uint32_t n_buses = 0, frames = 0;            // n_buses 0: a panned fill, which runs no stage
     bool master = false, stems = false;          // s2r_fill_master; the caller wants the stems too
@@ -36,7 +42,8 @@ struct S2rPostCall {                             // one fill, as prepare leaves 
     bool dyn = false;                            // dynamics sit on one of the call's buses, their key bus among them too
     bool room = false;                           // a room sits on one of the call's buses
     bool drive = false;                          // a drive sits on one of the call's buses
-    S2rPostRouteDrive route{};
+    bool flanger = false;                        // a flanger sits on one of the call's buses
+    S2rPostRouteFlanger route{};
 };
 
 // Who reads and writes what, the only place that decides it.  The combine writes into the first stem stage that runs, each running
@@ -112,5 +119,19 @@ inline S2rPostRouteDrive s2r_post_route_drive(const S2rPostCall &call, const S2r
     float *&writer = call.dyn ? r.dyn.out : call.eq ? r.eq.out : r.combine_out;
     r.drive.in = drive_stage; r.drive.out = writer;
     writer = drive_stage;
+    return r;
+}
+
+// The flanger is the fifth insert, behind the drive and in front of the stem stages.  Applied to the route after s2r_post_route_drive:
+// the flanger reads its own staging buffer and writes where the stage in front of it — the drive if the call runs it, else the dynamics,
+// else the EQ, else the combine — writes by now, and that writer is redirected into the flanger's buffer.  A call without a flanger, or
+// without buses, keeps its route as it is, with a null flanger pair.
+inline S2rPostRouteFlanger s2r_post_route_flanger(const S2rPostCall &call, const S2rPostRouteDrive &route, float *flanger_stage) {
+    S2rPostRouteFlanger r{};
+    static_cast<S2rPostRouteDrive &>(r) = route;
+    if (!call.flanger || !call.n_buses) return r;
+    float *&writer = call.drive ? r.drive.out : call.dyn ? r.dyn.out : call.eq ? r.eq.out : r.combine_out;
+    r.flanger.in = flanger_stage; r.flanger.out = writer;
+    writer = flanger_stage;
     return r;
 }

@@ -485,3 +485,48 @@ int s2r_limiter_reference(const float *x, uint32_t frames, float ceiling, uint32
 }
 
 }  // extern "C"
+
+// ---- per-bus flanger: one tap at a triangle-modulated fractional delay into the stage's own line signal, fed back.
+// At the end of the file, like the kernel at the end of the link order ----
+extern "C" {
+
+uint32_t s2r_flanger_history_frames(float base, float depth) { return flanger_delay_in_range(base, depth) ? flanger_history(base, depth) : 0u; }
+
+int s2r_flanger_reference(float base, float depth, uint32_t phase_inc, uint32_t spread, float feedback, float cross, float dry, float wet,
+                          const float *x_lr, uint32_t frames, float *history_lr, uint32_t *phase, float *out_lr) {
+    if (!flanger_in_range(base, depth, feedback, cross, dry, wet)) return S2R_ERR_PATCH_RANGE;
+    if (!history_lr || !phase || (!x_lr && frames)) return S2R_ERR_INVALID;
+    const size_t H = flanger_history(base, depth), N = frames;
+    std::vector<float> w(2 * (H + N));                           // w[-H .. N): the history, then the call's line signal
+    std::memcpy(w.data(), history_lr, 2 * H * sizeof(float));
+    const uint32_t phase0 = *phase;
+    for (size_t n = 0; n < N; n++) {
+        float tap[2];
+        for (uint32_t c = 0; c < 2; c++) {
+            const uint32_t p = phase0 + c * spread + phase_inc * (uint32_t)n;
+            const uint32_t q = p >> 8;
+            const uint32_t h = q < (1u << 23) ? q : (1u << 24) - q;
+            const float m = (float)h * 0x1p-23f;
+            const float dm = depth * m;
+            const float d = base + dm;
+            const uint32_t i = (uint32_t)d;                      // (32 <= i and i + 1 <= H: base <= d <= fl(base + depth) by monotonic rounding)
+            const float f = d - (float)i;
+            const float a = w[2 * (H + n - i) + c], bb = w[2 * (H + n - i - 1) + c];
+            const float e = bb - a;
+            const float g = f * e;
+            tap[c] = a + g;
+        }
+        for (uint32_t c = 0; c < 2; c++) {
+            const float x = x_lr[2 * n + c];
+            const float pf = feedback * tap[c], pc = cross * tap[1u - c];
+            const float s = pf + pc;
+            w[2 * (H + n) + c] = x + s;
+            if (out_lr) { const float dx = dry * x, wt = wet * tap[c]; out_lr[2 * n + c] = dx + wt; }
+        }
+    }
+    std::memcpy(history_lr, w.data() + 2 * N, 2 * H * sizeof(float));
+    *phase = phase0 + phase_inc * (uint32_t)N;
+    return S2R_OK;
+}
+
+}  // extern "C"

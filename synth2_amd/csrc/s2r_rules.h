@@ -114,6 +114,19 @@ static inline float drive_shape(const float *curve, float pre, float u) {
     return c0 + e;
 }
 
+// a bus's flanger: base >= S2R_FLANGER_MIN_DELAY, depth >= 0 and fl(base + depth) <= S2R_FLANGER_MAX_DELAY, the sum
+// rounded to binary32 as the chorus's; the four levels are the bus delay's, the sum condition in double.  False for a NaN or an infinity.
+static inline bool flanger_delay_in_range(float base, float depth) {
+    if (!(base >= S2R_FLANGER_MIN_DELAY) || !(depth >= 0.0f)) return false;
+    volatile float top = base + depth;
+    return top <= S2R_FLANGER_MAX_DELAY;
+}
+static inline bool flanger_in_range(float base, float depth, float feedback, float cross, float dry, float wet) {
+    return flanger_delay_in_range(base, depth) && delay_mix_in_range(feedback, cross, dry, wet);
+}
+// H = floor(fl(base + depth)) + 1 for a pair in range: 33 .. 4096
+static inline uint32_t flanger_history(float base, float depth) { volatile float top = base + depth; return (uint32_t)top + 1u; }
+
 // The voice mixer's gain rules, inline: the host's per-voice loops compile them in — a call per voice into s2r_rules.cpp showed as 10
 // to 15 us of host time per fill of 65 536 voices (profiles/r12/post_chain.txt).  s2r_rules.cpp exports them under their s2r.h names.
 static inline float rule_voice_pan(float pan, float key_spread, uint8_t note) {

@@ -52,6 +52,8 @@ DRIVE_HISTORY = 32                          # S2R_DRIVE_HISTORY
 DRIVE_CURVE_POINTS = 1025                   # S2R_DRIVE_CURVE_POINTS
 DRIVE_MAX_PRE = 1024.0                      # S2R_DRIVE_MAX_PRE
 DRIVE_LINEAR, DRIVE_TANH, DRIVE_HARD, DRIVE_CUBIC, DRIVE_FOLD = range(5)     # s2r_drive_kind
+FLANGER_MIN_DELAY = 32.0                    # S2R_FLANGER_MIN_DELAY
+FLANGER_MAX_DELAY = 4095.0                  # S2R_FLANGER_MAX_DELAY
 IR_SEGMENT = 256                            # S2R_IR_SEGMENT
 METER_BLOCK = 256                           # S2R_METER_BLOCK
 LIMITER_MAX_LOOKAHEAD = 1024                # S2R_LIMITER_MAX_LOOKAHEAD
@@ -267,6 +269,15 @@ def load_library():
         "s2r_drive_reference": (C.c_int, [_f32p, C.c_float, C.c_float, C.c_float, _f32p, C.c_uint32, _f32p, _f32p]),
         "s2r_drive_taps": (C.c_int, [_f32p]),
         "s2r_drive_curve": (C.c_int, [C.c_uint32, C.c_double, _f32p]),
+        "s2r_flanger_history_frames": (C.c_uint32, [C.c_float, C.c_float]),
+        "s2r_set_bus_flanger": (C.c_int, [H, C.c_uint32, C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_float]),
+        "s2r_clear_bus_flanger": (C.c_int, [H, C.c_uint32]),
+        "s2r_set_bus_flanger_params": (C.c_int, [H, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_float]),
+        "s2r_get_bus_flanger": (C.c_int, [H, C.c_uint32, _f32p, _f32p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _f32p, _f32p, _f32p, _f32p]),
+        "s2r_get_bus_flanger_state": (C.c_int, [H, C.c_uint32, _f32p, C.c_size_t, C.POINTER(C.c_uint32)]),
+        "s2r_set_bus_flanger_state": (C.c_int, [H, C.c_uint32, _f32p, C.c_size_t, C.c_uint32]),
+        "s2r_flanger_reference": (C.c_int, [C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_float, _f32p, C.c_uint32, _f32p,
+                                            C.POINTER(C.c_uint32), _f32p]),
         "s2r_set_bus_return": (C.c_int, [H, C.c_uint32, C.c_float]),
         "s2r_get_bus_return": (C.c_int, [H, C.c_uint32, _f32p, _f32p]),
         "s2r_set_master_fader": (C.c_int, [H, C.c_float]),
@@ -622,6 +633,33 @@ def drive_taps():
     if rc != S2R_OK:
         raise S2rError(rc, load_library().s2r_status_string(rc).decode())
     return out
+
+
+def flanger_history_frames(base, depth):
+    """H, the stereo frames of its line signal a flanger of (base, depth) keeps: floor(float32(base + depth)) + 1, or 0 for a pair out
+    of range (s2r_flanger_history_frames)"""
+    return int(load_library().s2r_flanger_history_frames(float(base), float(depth)))
+
+
+def flanger_reference(base, depth, phase_inc, spread, feedback, cross, dry, wet, x, history, phase):
+    """the bus flanger's rule on the host (s2r_flanger_reference): x [frames, 2] float32 is the bus's signal, history [H, 2] the last H
+    frames of the stage's line signal w, oldest first, phase the LFO's at frame 0; returns (out [frames, 2], the history after the call
+    [H, 2], the phase after the call).  `history` itself is left as it is."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    h = np.array(history, dtype=np.float32, order="C")
+    if x.ndim != 2 or x.shape[1] != 2 or h.ndim != 2 or h.shape[1] != 2:
+        raise ValueError("flanger_reference: x is [frames, 2] and history is [H, 2]")
+    hf = flanger_history_frames(base, depth)
+    if hf and h.shape[0] != hf:                 # (a pair out of range is the library's to refuse)
+        raise ValueError("flanger_reference: history is [flanger_history_frames(base, depth), 2]")
+    out = np.empty_like(x)
+    ph = C.c_uint32(int(phase) & 0xFFFFFFFF)
+    rc = load_library().s2r_flanger_reference(float(base), float(depth), int(phase_inc) & 0xFFFFFFFF, int(spread) & 0xFFFFFFFF, float(feedback),
+                                              float(cross), float(dry), float(wet), x.ctypes.data_as(_f32p), x.shape[0], h.ctypes.data_as(_f32p),
+                                              C.byref(ph), out.ctypes.data_as(_f32p))
+    if rc != S2R_OK:
+        raise S2rError(rc, load_library().s2r_status_string(rc).decode())
+    return out, h, ph.value
 
 
 def master_reference(stems, r0, r1, m0, m1):
@@ -1295,6 +1333,57 @@ class Synth:
     @staticmethod
     def drive_taps():
         return drive_taps()
+
+    # --- per-bus flanger (build-defined; s2r.h: s2r_set_bus_flanger) ---
+    def set_bus_flanger(self, bus, base, depth, phase_inc, spread=0, feedback=0.0, cross=0.0, dry=1.0, wet=1.0):
+        """a flanger on a bus of sample_buses and sample_master, behind the drive and in front of the chorus: one tap base + depth *
+        triangle frames late (base >= FLANGER_MIN_DELAY, depth >= 0, float32(base + depth) <= FLANGER_MAX_DELAY) into the stage's own line
+        signal, fed back by `feedback` and into the other channel by `cross` (each in [-1, 1], |feedback| + |cross| <= 1); the LFO steps
+        phase_inc per frame (chorus_rate(hz, sample_rate)), the right channel `spread` ahead of the left, both in 2^-32 turns; dry and
+        wet in [0, 1].  Replaces any earlier flanger of the bus and zeroes its history and phase."""
+        self._check(self.L.s2r_set_bus_flanger(self.h, int(bus), float(base), float(depth), int(phase_inc) & 0xFFFFFFFF, int(spread) & 0xFFFFFFFF,
+                                               float(feedback), float(cross), float(dry), float(wet)))
+
+    def clear_bus_flanger(self, bus):
+        """removes the bus's flanger: the bus passes again, bit for bit"""
+        self._check(self.L.s2r_clear_bus_flanger(self.h, int(bus)))
+
+    def set_bus_flanger_params(self, bus, phase_inc, spread, feedback, cross, dry, wet):
+        """everything but base and depth; history and phase stay, so rate and resonance move between calls without a click"""
+        self._check(self.L.s2r_set_bus_flanger_params(self.h, int(bus), int(phase_inc) & 0xFFFFFFFF, int(spread) & 0xFFFFFFFF, float(feedback), float(cross),
+                                                      float(dry), float(wet)))
+
+    def get_bus_flanger(self, bus):
+        """(base, depth, phase_inc, spread, feedback, cross, dry, wet); base is 0 for a bus without a flanger"""
+        b, dp, fb, cr, d, w = (C.c_float() for _ in range(6))
+        pi, sp = C.c_uint32(), C.c_uint32()
+        self._check(self.L.s2r_get_bus_flanger(self.h, int(bus), C.byref(b), C.byref(dp), C.byref(pi), C.byref(sp), C.byref(fb), C.byref(cr), C.byref(d),
+                                               C.byref(w)))
+        return (np.float32(b.value), np.float32(dp.value), pi.value, sp.value, np.float32(fb.value), np.float32(cr.value), np.float32(d.value),
+                np.float32(w.value))
+
+    def bus_flanger_state(self, bus):
+        """what the bus's flanger carries into the next call: (the H stereo frames of its line signal, oldest first: (H, 2) float32, the
+        LFO's phase) — the checkpoint companion of bus_chorus_state"""
+        base, depth = self.get_bus_flanger(bus)[:2]
+        out = np.empty((flanger_history_frames(base, depth), 2), dtype=np.float32)
+        ph = C.c_uint32()
+        self._check(self.L.s2r_get_bus_flanger_state(self.h, int(bus), out.ctypes.data_as(_f32p), out.size, C.byref(ph)))
+        return out, ph.value
+
+    def set_bus_flanger_state(self, bus, history, phase):
+        h = np.ascontiguousarray(history, dtype=np.float32)
+        if h.ndim != 2 or h.shape[1] != 2:
+            raise ValueError("set_bus_flanger_state: history is [H, 2]")
+        self._check(self.L.s2r_set_bus_flanger_state(self.h, int(bus), h.ctypes.data_as(_f32p), h.size, int(phase) & 0xFFFFFFFF))
+
+    @staticmethod
+    def flanger_reference(base, depth, phase_inc, spread, feedback, cross, dry, wet, x, history, phase):
+        return flanger_reference(base, depth, phase_inc, spread, feedback, cross, dry, wet, x, history, phase)
+
+    @staticmethod
+    def flanger_history_frames(base, depth):
+        return flanger_history_frames(base, depth)
 
     # --- the master section (build-defined; s2r.h: s2r_fill_master) ---
     def set_bus_return(self, bus, level=1.0):
