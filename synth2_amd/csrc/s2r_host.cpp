@@ -318,7 +318,7 @@ struct s2r_synth {
     float *bus_out = nullptr, *bus_out_dev = nullptr;            // pinned and device-mapped: S2R_MAX_BUSES * 2 * max_frames floats
     float bus_mix_ms = -1.0f;                    // pan_mix_ms of the last s2r_fill_buses (tools/bus_time.py)
     bool bus_dev_ramped = false;                 // what bus_gains_dev holds was sent for a ramped fill: (G0, step), not the static gains
-    // What runs behind the bus mixdown (s2r_post.h): the buses' choruses, delays and reverbs, the master section and the master limiter
+    // What runs behind the bus mixdown (s2r_post.h): the eight bus stages, the master section and the master limiter
     S2rPostChain post;
     float pitch_table[256];
     hipEvent_t t0 = nullptr, t1 = nullptr;
@@ -2723,7 +2723,7 @@ int s2r_set_voice_sends(s2r_synth *s, const float *sends, const uint8_t *send_bu
     return S2R_OK;
 }
 
-// ---- the post-mix chain: choruses, delays, reverbs, master section, master limiter (s2r_post.h) ----
+// ---- the post-mix chain: the eight bus stages, master section, master limiter (s2r_post.h) ----
 // Every entry below looks at its values first (they are wrong whatever the handle holds), then at the handle, quiesces where it touches
 // the device, and calls into s->post for whatever is more than one value.  `what`: "bus reverbs are", "the master section is", ...
 static int post_handle(const s2r_synth *s, const char *who, const char *what) {
@@ -2732,17 +2732,15 @@ static int post_handle(const s2r_synth *s, const char *who, const char *what) {
     return S2R_OK;
 }
 
-// the words in which the entries of a stem stage differ
-static const struct { const char *one, *are; } kStemWords[S2R_STEM_STAGES + 2] = {{"chorus", "bus choruses are"}, {"delay", "bus delays are"}, {"reverb", "bus reverbs are"},
-                                                                                  {"drive", "bus drives are"}, {"flanger", "bus flangers are"}};
-// (the drive is no stem stage — s2r_post_route.h —, but its entries are guarded like theirs: S2rPostChain::bus answers for it at this index)
-static const S2rStemStage kDriveEntry = S2R_STEM_STAGES;
-static const S2rStemStage kFlangerEntry = (S2rStemStage)(S2R_STEM_STAGES + 1);     // (and so is the flanger, behind it)
+// the words in which the entries of a bus stage differ, by S2rBusStage
+static const struct { const char *one, *are; } kStemWords[S2R_BUS_STAGES] = {{"EQ", "bus equalisers are"}, {"dynamics", "bus dynamics are"}, {"drive", "bus drives are"},
+                                                                             {"flanger", "bus flangers are"}, {"chorus", "bus choruses are"}, {"delay", "bus delays are"},
+                                                                             {"reverb", "bus reverbs are"}, {"room", "bus rooms are"}};
 
 // The guard of an entry that reads or changes the effect one bus carries: the bus in range, a single-device handle, and the bus
 // carries one.  `who` null: a getter, which answers for a bus without one too and leaves the handle's error text alone; `named`:
 // the refusal of a bus without one begins with `who`.
-static int stem_bus(const s2r_synth *s, S2rStemStage k, uint32_t bus, const char *who, bool named) {
+static int stem_bus(const s2r_synth *s, S2rBusStage k, uint32_t bus, const char *who, bool named) {
     if (!who) return bus >= S2R_MAX_BUSES ? S2R_ERR_PATCH_RANGE : (!s || !s->kids.empty() || s->parent) ? S2R_ERR_INVALID : S2R_OK;
     s2r_synth *m = const_cast<s2r_synth *>(s);
     if (bus >= S2R_MAX_BUSES) return set_err(m, S2R_ERR_PATCH_RANGE, "%s: bus %u, below %u", who, bus, S2R_MAX_BUSES);
@@ -2766,7 +2764,7 @@ static int stem_set(s2r_synth *s, const char *who, const std::function<hipError_
 
 // An effect's history out (`get`, `count` the capacity) or in (`set`, `count` exact): it crosses the boundary as frames, oldest
 // first, L then R.  A reverb of one tap has none, and nothing to copy.
-static int stem_history(s2r_synth *s, S2rStemStage k, uint32_t bus, float *get, const float *set, size_t count, const char *who) {
+static int stem_history(s2r_synth *s, S2rBusStage k, uint32_t bus, float *get, const float *set, size_t count, const char *who) {
     S2R_TRY(stem_bus(s, k, bus, who, true));
     const size_t h = s->post.bus(k, bus).history;
     if (set ? count != 2 * h : count < 2 * h) return set_err(s, S2R_ERR_INVALID, "%s: the history of bus %u is %zu floats, not %zu", who, bus, 2 * h, count);
@@ -2776,6 +2774,25 @@ static int stem_history(s2r_synth *s, S2rStemStage k, uint32_t bus, float *get, 
     S2R_HIP(s, hipSetDevice(s->device));
     S2R_HIP(s, hipStreamSynchronize(s->stream));
     S2R_HIP(s, s->post.history(post_ctx(s), k, bus, get, set));
+    return S2R_OK;
+}
+
+// An effect's whole state out (`get`, `count` the capacity) or in (`set`, `count` exact), for the stages whose checkpoint is every
+// float of their line.  `values`: the stage's own check of a state coming in, behind the count's and in front of the device.
+static int stem_state(s2r_synth *s, S2rBusStage k, uint32_t bus, float *get, const float *set, size_t count, const char *who,
+                      int (*values)(s2r_synth *, const float *, size_t, const char *) = nullptr) {
+    S2R_TRY(stem_bus(s, k, bus, who, true));
+    const size_t n = s->post.bus(k, bus).floats;
+    if (set ? count != n : count < n) {                          // (the dynamics' state is one float, and their text says so)
+        if (n == 1u) return set_err(s, S2R_ERR_INVALID, "%s: the state of bus %u is 1 float, not %zu", who, bus, count);
+        return set_err(s, S2R_ERR_INVALID, "%s: the state of bus %u is %zu floats, not %zu", who, bus, n, count);
+    }
+    if (!get && !set) return set_err(s, S2R_ERR_INVALID, "%s: null buffer", who);
+    if (set && values) S2R_TRY(values(s, set, n, who));
+    S2R_QUIESCE(s);
+    S2R_HIP(s, hipSetDevice(s->device));
+    S2R_HIP(s, hipStreamSynchronize(s->stream));
+    S2R_HIP(s, s->post.state(post_ctx(s), k, bus, get, set));
     return S2R_OK;
 }
 
@@ -2795,40 +2812,31 @@ int s2r_set_bus_reverb(s2r_synth *s, uint32_t bus, const float *ir_l, const floa
 int s2r_set_bus_reverb_mix(s2r_synth *s, uint32_t bus, float dry, float wet) {
     if (!unit_in_range(dry) || !unit_in_range(wet) || bus >= S2R_MAX_BUSES)
         return set_err(s, S2R_ERR_PATCH_RANGE, "bus %u: dry %g, wet %g: both lie in [0, 1], the bus below %u", bus, (double)dry, (double)wet, S2R_MAX_BUSES);
-    S2R_TRY(stem_bus(s, S2R_STEM_REVERB, bus, "s2r_set_bus_reverb_mix", false));
+    S2R_TRY(stem_bus(s, S2R_BUS_REVERB, bus, "s2r_set_bus_reverb_mix", false));
     s->post.fx[bus].dry = dry; s->post.fx[bus].wet = wet;
     return S2R_OK;
 }
 
 int s2r_get_bus_reverb(const s2r_synth *s, uint32_t bus, uint32_t *n_taps, float *dry, float *wet) {
-    S2R_TRY(stem_bus(s, S2R_STEM_REVERB, bus, nullptr, false));
+    S2R_TRY(stem_bus(s, S2R_BUS_REVERB, bus, nullptr, false));
     put(n_taps, s->post.fx[bus].n_taps); put(dry, s->post.fx[bus].dry); put(wet, s->post.fx[bus].wet);
     return S2R_OK;
 }
 
 int s2r_get_bus_reverb_history(s2r_synth *s, uint32_t bus, float *lr, size_t capacity) {
-    return stem_history(s, S2R_STEM_REVERB, bus, lr, nullptr, capacity, "s2r_get_bus_reverb_history");
+    return stem_history(s, S2R_BUS_REVERB, bus, lr, nullptr, capacity, "s2r_get_bus_reverb_history");
 }
 
 int s2r_set_bus_reverb_history(s2r_synth *s, uint32_t bus, const float *lr, size_t count) {
     static const float none = 0.0f;                              // (a null lr: refused by stem_history unless K = 1, which has no history)
-    return stem_history(s, S2R_STEM_REVERB, bus, nullptr, lr ? lr : &none, lr ? count : (count ? (size_t)-1 : 0), "s2r_set_bus_reverb_history");
+    return stem_history(s, S2R_BUS_REVERB, bus, nullptr, lr ? lr : &none, lr ? count : (count ? (size_t)-1 : 0), "s2r_set_bus_reverb_history");
 }
 
-// ---- per-bus equalisers: at the head of the chain, in front of the choruses.  Not a stem stage (s2r_post_route.h):
-// stem_set carries the setter's tail, the guard of the other entries is its own ----
+// ---- per-bus equalisers: the first bus stage, at the head of the chain ----
 static int eq_values(s2r_synth *s, const char *who, uint32_t bus, uint32_t n_bands, const float *coeffs) {
     if (bus >= S2R_MAX_BUSES || !eq_in_range(n_bands, coeffs))
         return set_err(s, S2R_ERR_PATCH_RANGE, "%s: bus %u, %u bands: at most %u bands of finite coefficients (b0, b1, b2, a1, a2) with |a2| < 1 and "
                        "|a1| < 1 + a2, the bus below %u", who, bus, n_bands, S2R_EQ_MAX_BANDS, S2R_MAX_BUSES);
-    return S2R_OK;
-}
-
-// the bus in range, a single-device handle, and the bus carries an EQ
-static int eq_bus(s2r_synth *s, uint32_t bus, const char *who) {
-    if (bus >= S2R_MAX_BUSES) return set_err(s, S2R_ERR_PATCH_RANGE, "%s: bus %u, below %u", who, bus, S2R_MAX_BUSES);
-    S2R_TRY(post_handle(s, who, "bus equalisers are"));
-    if (!s->post.eq[bus].present()) return set_err(s, S2R_ERR_INVALID, "%s: bus %u carries no EQ", who, bus);
     return S2R_OK;
 }
 
@@ -2841,7 +2849,7 @@ int s2r_set_bus_eq(s2r_synth *s, uint32_t bus, uint32_t n_bands, const float *co
 
 int s2r_set_bus_eq_coeffs(s2r_synth *s, uint32_t bus, uint32_t n_bands, const float *coeffs) {
     S2R_TRY(eq_values(s, "s2r_set_bus_eq_coeffs", bus, n_bands, coeffs));
-    S2R_TRY(eq_bus(s, bus, "s2r_set_bus_eq_coeffs"));
+    S2R_TRY(stem_bus(s, S2R_BUS_EQ, bus, "s2r_set_bus_eq_coeffs", true));
     S2rPostChain::BusEq &d = s->post.eq[bus];
     if (n_bands != d.n_bands || !coeffs) return set_err(s, S2R_ERR_INVALID, "s2r_set_bus_eq_coeffs: the EQ of bus %u has %u bands, not %u", bus, d.n_bands, n_bands);
     std::memcpy(d.c, coeffs, (size_t)n_bands * 5u * sizeof(float));          // (the state stays: the band moves without a restart)
@@ -2858,39 +2866,19 @@ int s2r_get_bus_eq(const s2r_synth *s, uint32_t bus, uint32_t *n_bands, float *c
     return S2R_OK;
 }
 
-static int eq_state(s2r_synth *s, uint32_t bus, float *get, const float *set, size_t count, const char *who) {
-    S2R_TRY(eq_bus(s, bus, who));
-    const size_t n = 4u * (size_t)s->post.eq[bus].n_bands;
-    if (set ? count != n : count < n) return set_err(s, S2R_ERR_INVALID, "%s: the state of bus %u is %zu floats, not %zu", who, bus, n, count);
-    if (!get && !set) return set_err(s, S2R_ERR_INVALID, "%s: null buffer", who);
-    S2R_QUIESCE(s);
-    S2R_HIP(s, hipSetDevice(s->device));
-    S2R_HIP(s, hipStreamSynchronize(s->stream));
-    S2R_HIP(s, s->post.eq_state(post_ctx(s), bus, get, set));
-    return S2R_OK;
-}
-
 int s2r_get_bus_eq_state(s2r_synth *s, uint32_t bus, float *state, size_t capacity) {
-    return eq_state(s, bus, state, nullptr, capacity, "s2r_get_bus_eq_state");
+    return stem_state(s, S2R_BUS_EQ, bus, state, nullptr, capacity, "s2r_get_bus_eq_state");
 }
 
 int s2r_set_bus_eq_state(s2r_synth *s, uint32_t bus, const float *state, size_t count) {
-    return eq_state(s, bus, nullptr, state, state ? count : (size_t)-1, "s2r_set_bus_eq_state");
+    return stem_state(s, S2R_BUS_EQ, bus, nullptr, state, state ? count : (size_t)-1, "s2r_set_bus_eq_state");
 }
 
-// ---- per-bus dynamics: the second insert, behind the equalisers and in front of the choruses ----
+// ---- per-bus dynamics: the second bus stage, behind the equalisers ----
 static int dyn_values(s2r_synth *s, const char *who, uint32_t bus, uint32_t key_bus, const float *curve, float a_att, float a_rel) {
     if (bus >= S2R_MAX_BUSES || key_bus >= S2R_MAX_BUSES || !dyn_in_range(curve, a_att, a_rel))
         return set_err(s, S2R_ERR_PATCH_RANGE, "%s: bus %u, key bus %u, attack %g, release %g: %u finite curve entries in [0, 256], both coefficients in "
                        "[0, 1), both buses below %u", who, bus, key_bus, (double)a_att, (double)a_rel, S2R_DYN_CURVE_POINTS, S2R_MAX_BUSES);
-    return S2R_OK;
-}
-
-// the bus in range, a single-device handle, and the bus carries dynamics
-static int dyn_bus(s2r_synth *s, uint32_t bus, const char *who) {
-    if (bus >= S2R_MAX_BUSES) return set_err(s, S2R_ERR_PATCH_RANGE, "%s: bus %u, below %u", who, bus, S2R_MAX_BUSES);
-    S2R_TRY(post_handle(s, who, "bus dynamics are"));
-    if (!s->post.dyn[bus].present()) return set_err(s, S2R_ERR_INVALID, "%s: bus %u carries no dynamics", who, bus);
     return S2R_OK;
 }
 
@@ -2909,7 +2897,7 @@ int s2r_clear_bus_dynamics(s2r_synth *s, uint32_t bus) {
 
 int s2r_set_bus_dynamics_params(s2r_synth *s, uint32_t bus, uint32_t key_bus, const float *curve, float a_att, float a_rel) {
     S2R_TRY(dyn_values(s, "s2r_set_bus_dynamics_params", bus, key_bus, curve, a_att, a_rel));
-    S2R_TRY(dyn_bus(s, bus, "s2r_set_bus_dynamics_params"));
+    S2R_TRY(stem_bus(s, S2R_BUS_DYN, bus, "s2r_set_bus_dynamics_params", true));
     if (!curve) return set_err(s, S2R_ERR_INVALID, "s2r_set_bus_dynamics_params: no curve");
     return stem_set(s, "s2r_set_bus_dynamics_params", [&](const S2rPostCtx &c) { return s->post.set_dyn(c, bus, key_bus, curve, a_att, a_rel, true); });   // (y stays)
 }
@@ -2926,14 +2914,7 @@ int s2r_get_bus_dynamics(const s2r_synth *s, uint32_t bus, uint32_t *present, ui
 
 static int dyn_state(s2r_synth *s, uint32_t bus, float *get, const float *set, size_t count, const char *who) {
     if (set && count == 1u && !dyn_state_in_range(set[0])) return set_err(s, S2R_ERR_PATCH_RANGE, "%s: a gain of %g: finite and not below 0", who, (double)set[0]);
-    S2R_TRY(dyn_bus(s, bus, who));
-    if (set ? count != 1u : count < 1u) return set_err(s, S2R_ERR_INVALID, "%s: the state of bus %u is 1 float, not %zu", who, bus, count);
-    if (!get && !set) return set_err(s, S2R_ERR_INVALID, "%s: null buffer", who);
-    S2R_QUIESCE(s);
-    S2R_HIP(s, hipSetDevice(s->device));
-    S2R_HIP(s, hipStreamSynchronize(s->stream));
-    S2R_HIP(s, s->post.dyn_state(post_ctx(s), bus, get, set));
-    return S2R_OK;
+    return stem_state(s, S2R_BUS_DYN, bus, get, set, count, who);
 }
 
 int s2r_get_bus_dynamics_state(s2r_synth *s, uint32_t bus, float *state, size_t capacity) {
@@ -2951,20 +2932,120 @@ int s2r_get_bus_dynamics_meter(const s2r_synth *s, uint32_t bus, float *min_gain
     return S2R_OK;
 }
 
-// ---- per-bus rooms: the third insert, behind the last stem stage ----
+// ---- per-bus drives: the third bus stage, behind the dynamics ----
+static int drive_values(s2r_synth *s, const char *who, uint32_t bus, const float *curve, float pre, float dry, float wet) {
+    if (bus >= S2R_MAX_BUSES || !drive_in_range(curve, pre, dry, wet))
+        return set_err(s, S2R_ERR_PATCH_RANGE, "%s: bus %u, pre %g, dry %g, wet %g: %u finite curve entries, pre in [0, %g], dry and wet in [0, 1], the bus below %u",
+                       who, bus, (double)pre, (double)dry, (double)wet, S2R_DRIVE_CURVE_POINTS, (double)S2R_DRIVE_MAX_PRE, S2R_MAX_BUSES);
+    return S2R_OK;
+}
+
+int s2r_set_bus_drive(s2r_synth *s, uint32_t bus, const float *curve, float pre, float dry, float wet) {
+    S2R_TRY(drive_values(s, "s2r_set_bus_drive", bus, curve, pre, dry, wet));
+    S2R_TRY(post_handle(s, "s2r_set_bus_drive", kStemWords[S2R_BUS_DRIVE].are));
+    if (!curve) return set_err(s, S2R_ERR_INVALID, "s2r_set_bus_drive: no curve");
+    return stem_set(s, "s2r_set_bus_drive", [&](const S2rPostCtx &c) { return s->post.set_drive(c, bus, curve, pre, dry, wet, false); });
+}
+
+int s2r_clear_bus_drive(s2r_synth *s, uint32_t bus) {
+    if (bus >= S2R_MAX_BUSES) return set_err(s, S2R_ERR_PATCH_RANGE, "s2r_clear_bus_drive: bus %u, below %u", bus, S2R_MAX_BUSES);
+    S2R_TRY(post_handle(s, "s2r_clear_bus_drive", kStemWords[S2R_BUS_DRIVE].are));
+    return stem_set(s, "s2r_clear_bus_drive", [&](const S2rPostCtx &c) { return s->post.set_drive(c, bus, nullptr, -1.0f, 0.0f, 0.0f, false); });
+}
+
+int s2r_set_bus_drive_params(s2r_synth *s, uint32_t bus, const float *curve, float pre, float dry, float wet) {
+    S2R_TRY(drive_values(s, "s2r_set_bus_drive_params", bus, curve, pre, dry, wet));
+    S2R_TRY(stem_bus(s, S2R_BUS_DRIVE, bus, "s2r_set_bus_drive_params", true));
+    return stem_set(s, "s2r_set_bus_drive_params", [&](const S2rPostCtx &c) { return s->post.set_drive(c, bus, curve, pre, dry, wet, true); });   // (the history stays)
+}
+
+int s2r_get_bus_drive(const s2r_synth *s, uint32_t bus, uint32_t *present, float *curve, size_t capacity, float *pre, float *dry, float *wet) {
+    S2R_TRY(stem_bus(s, S2R_BUS_DRIVE, bus, nullptr, false));
+    const S2rPostChain::BusDrive &d = s->post.drive[bus];
+    if (d.present() && curve && capacity < S2R_DRIVE_CURVE_POINTS) return S2R_ERR_INVALID;
+    put(present, d.present() ? 1u : 0u); put(pre, d.pre); put(dry, d.dry); put(wet, d.wet);
+    if (d.present() && curve) std::memcpy(curve, d.curve.data(), S2R_DRIVE_CURVE_POINTS * sizeof(float));
+    return S2R_OK;
+}
+
+// the checkpoint pair: the room's state pair's checks, then the stem stages' copy
+static int drive_history(s2r_synth *s, uint32_t bus, float *get, const float *set, size_t count, const char *who) {
+    S2R_TRY(stem_bus(s, S2R_BUS_DRIVE, bus, who, true));
+    const size_t n = 2u * S2R_DRIVE_HISTORY;
+    if (set ? count != n : count < n) return set_err(s, S2R_ERR_INVALID, "%s: the history of bus %u is %zu floats, not %zu", who, bus, n, count);
+    if (!get && !set) return set_err(s, S2R_ERR_INVALID, "%s: null buffer", who);
+    if (set) for (size_t k = 0; k < n; k++) if (!std::isfinite(set[k])) return set_err(s, S2R_ERR_PATCH_RANGE, "%s: value %zu of the history is not finite", who, k);
+    return stem_history(s, S2R_BUS_DRIVE, bus, get, set, count, who);
+}
+
+int s2r_get_bus_drive_history(s2r_synth *s, uint32_t bus, float *lr, size_t capacity) {
+    return drive_history(s, bus, lr, nullptr, capacity, "s2r_get_bus_drive_history");
+}
+
+int s2r_set_bus_drive_history(s2r_synth *s, uint32_t bus, const float *lr, size_t count) {
+    return drive_history(s, bus, nullptr, lr, lr ? count : (size_t)-1, "s2r_set_bus_drive_history");
+}
+
+// ---- per-bus flangers: the fourth bus stage, behind the drives and in front of the choruses ----
+static int flanger_levels(s2r_synth *s, const char *who, uint32_t bus, float feedback, float cross, float dry, float wet) {
+    if (bus >= S2R_MAX_BUSES || !delay_mix_in_range(feedback, cross, dry, wet))
+        return set_err(s, S2R_ERR_PATCH_RANGE, "%s: bus %u, feedback %g, cross %g, dry %g, wet %g: feedback and cross in [-1, 1] with |feedback| + |cross| <= 1, dry and "
+                       "wet in [0, 1], the bus below %u", who, bus, (double)feedback, (double)cross, (double)dry, (double)wet, S2R_MAX_BUSES);
+    return S2R_OK;
+}
+
+int s2r_set_bus_flanger(s2r_synth *s, uint32_t bus, float base, float depth, uint32_t phase_inc, uint32_t spread, float feedback, float cross, float dry,
+                        float wet) {
+    if (!flanger_delay_in_range(base, depth))
+        return set_err(s, S2R_ERR_PATCH_RANGE, "s2r_set_bus_flanger: bus %u, base %g, depth %g: base >= %g and depth >= 0 with base + depth <= %g frames", bus,
+                       (double)base, (double)depth, (double)S2R_FLANGER_MIN_DELAY, (double)S2R_FLANGER_MAX_DELAY);
+    S2R_TRY(flanger_levels(s, "s2r_set_bus_flanger", bus, feedback, cross, dry, wet));
+    S2R_TRY(post_handle(s, "s2r_set_bus_flanger", kStemWords[S2R_BUS_FLANGER].are));
+    return stem_set(s, "s2r_set_bus_flanger", [&](const S2rPostCtx &c) { return s->post.set_flanger(c, bus, base, depth, phase_inc, spread, feedback, cross, dry, wet); });
+}
+
+int s2r_clear_bus_flanger(s2r_synth *s, uint32_t bus) {
+    if (bus >= S2R_MAX_BUSES) return set_err(s, S2R_ERR_PATCH_RANGE, "s2r_clear_bus_flanger: bus %u, below %u", bus, S2R_MAX_BUSES);
+    S2R_TRY(post_handle(s, "s2r_clear_bus_flanger", kStemWords[S2R_BUS_FLANGER].are));
+    return stem_set(s, "s2r_clear_bus_flanger", [&](const S2rPostCtx &c) { return s->post.set_flanger(c, bus, -1.0f, 0.0f, 0, 0, 0.0f, 0.0f, 0.0f, 0.0f); });
+}
+
+int s2r_set_bus_flanger_params(s2r_synth *s, uint32_t bus, uint32_t phase_inc, uint32_t spread, float feedback, float cross, float dry, float wet) {
+    S2R_TRY(flanger_levels(s, "s2r_set_bus_flanger_params", bus, feedback, cross, dry, wet));
+    S2R_TRY(stem_bus(s, S2R_BUS_FLANGER, bus, "s2r_set_bus_flanger_params", true));
+    S2rPostChain::BusFlanger &d = s->post.flanger[bus];          // (the phase and the line stay: the LFO bends, the comb retunes, nothing clicks)
+    d.phase_inc = phase_inc; d.spread = spread; d.feedback = feedback; d.cross = cross; d.dry = dry; d.wet = wet;
+    return S2R_OK;
+}
+
+int s2r_get_bus_flanger(const s2r_synth *s, uint32_t bus, float *base, float *depth, uint32_t *phase_inc, uint32_t *spread, float *feedback, float *cross,
+                        float *dry, float *wet) {
+    S2R_TRY(stem_bus(s, S2R_BUS_FLANGER, bus, nullptr, false));
+    const S2rPostChain::BusFlanger &d = s->post.flanger[bus];
+    put(base, d.base); put(depth, d.depth); put(phase_inc, d.phase_inc); put(spread, d.spread); put(feedback, d.feedback); put(cross, d.cross);
+    put(dry, d.dry); put(wet, d.wet);
+    return S2R_OK;
+}
+
+// (the flanger's phase lives on the host, as the chorus's)
+int s2r_get_bus_flanger_state(s2r_synth *s, uint32_t bus, float *lr, size_t capacity, uint32_t *phase) {
+    S2R_TRY(stem_history(s, S2R_BUS_FLANGER, bus, lr, nullptr, capacity, "s2r_get_bus_flanger_state"));
+    put(phase, s->post.flanger[bus].phase);
+    return S2R_OK;
+}
+
+int s2r_set_bus_flanger_state(s2r_synth *s, uint32_t bus, const float *lr, size_t count, uint32_t phase) {
+    S2R_TRY(stem_history(s, S2R_BUS_FLANGER, bus, nullptr, lr, lr ? count : (size_t)-1, "s2r_set_bus_flanger_state"));
+    s->post.flanger[bus].phase = phase;
+    return S2R_OK;
+}
+
+// ---- per-bus rooms: the last bus stage, behind the reverbs ----
 static int room_levels(s2r_synth *s, const char *who, uint32_t bus, float feedback, float damp, float g, float gain, float dry, float wet, float cross) {
     if (bus >= S2R_MAX_BUSES || !room_levels_in_range(feedback, damp, g, gain, dry, wet, cross))
         return set_err(s, S2R_ERR_PATCH_RANGE, "%s: bus %u, feedback %g, damp %g, g %g, gain %g, dry %g, wet %g, cross %g: feedback in [0, 1), g in (-1, 1), "
                        "the others in [0, 1], the bus below %u", who, bus, (double)feedback, (double)damp, (double)g, (double)gain, (double)dry, (double)wet,
                        (double)cross, S2R_MAX_BUSES);
-    return S2R_OK;
-}
-
-// the bus in range, a single-device handle, and the bus carries a room
-static int room_bus(s2r_synth *s, uint32_t bus, const char *who) {
-    if (bus >= S2R_MAX_BUSES) return set_err(s, S2R_ERR_PATCH_RANGE, "%s: bus %u, below %u", who, bus, S2R_MAX_BUSES);
-    S2R_TRY(post_handle(s, who, "bus rooms are"));
-    if (!s->post.room[bus].present()) return set_err(s, S2R_ERR_INVALID, "%s: bus %u carries no room", who, bus);
     return S2R_OK;
 }
 
@@ -2988,7 +3069,7 @@ int s2r_clear_bus_room(s2r_synth *s, uint32_t bus) {
 
 int s2r_set_bus_room_params(s2r_synth *s, uint32_t bus, float feedback, float damp, float g, float gain, float dry, float wet, float cross) {
     S2R_TRY(room_levels(s, "s2r_set_bus_room_params", bus, feedback, damp, g, gain, dry, wet, cross));
-    S2R_TRY(room_bus(s, bus, "s2r_set_bus_room_params"));
+    S2R_TRY(stem_bus(s, S2R_BUS_ROOM, bus, "s2r_set_bus_room_params", true));
     const float levels[7] = {feedback, damp, g, gain, dry, wet, cross};
     return stem_set(s, "s2r_set_bus_room_params", [&](const S2rPostCtx &) { s->post.set_room_params(bus, levels); return hipSuccess; });   // (the state stays)
 }
@@ -3004,25 +3085,18 @@ int s2r_get_bus_room(const s2r_synth *s, uint32_t bus, uint32_t *present, uint32
     return S2R_OK;
 }
 
-static int room_state(s2r_synth *s, uint32_t bus, float *get, const float *set, size_t count, const char *who) {
-    S2R_TRY(room_bus(s, bus, who));
-    const size_t n = s->post.room[bus].floats;
-    if (set ? count != n : count < n) return set_err(s, S2R_ERR_INVALID, "%s: the state of bus %u is %zu floats, not %zu", who, bus, n, count);
-    if (!get && !set) return set_err(s, S2R_ERR_INVALID, "%s: null buffer", who);
-    if (set) for (size_t k = 0; k < n; k++) if (!std::isfinite(set[k])) return set_err(s, S2R_ERR_PATCH_RANGE, "%s: value %zu of the state is not finite", who, k);
-    S2R_QUIESCE(s);
-    S2R_HIP(s, hipSetDevice(s->device));
-    S2R_HIP(s, hipStreamSynchronize(s->stream));
-    S2R_HIP(s, s->post.room_state(post_ctx(s), bus, get, set));
+// a room's state coming in is finite throughout
+static int room_state_finite(s2r_synth *s, const float *set, size_t n, const char *who) {
+    for (size_t k = 0; k < n; k++) if (!std::isfinite(set[k])) return set_err(s, S2R_ERR_PATCH_RANGE, "%s: value %zu of the state is not finite", who, k);
     return S2R_OK;
 }
 
 int s2r_get_bus_room_state(s2r_synth *s, uint32_t bus, float *state, size_t capacity) {
-    return room_state(s, bus, state, nullptr, capacity, "s2r_get_bus_room_state");
+    return stem_state(s, S2R_BUS_ROOM, bus, state, nullptr, capacity, "s2r_get_bus_room_state");
 }
 
 int s2r_set_bus_room_state(s2r_synth *s, uint32_t bus, const float *state, size_t count) {
-    return room_state(s, bus, nullptr, state, state ? count : (size_t)-1, "s2r_set_bus_room_state");
+    return stem_state(s, S2R_BUS_ROOM, bus, nullptr, state, state ? count : (size_t)-1, "s2r_set_bus_room_state", room_state_finite);
 }
 
 // ---- per-bus choruses: in front of the delays ----
@@ -3038,20 +3112,20 @@ int s2r_set_bus_chorus(s2r_synth *s, uint32_t bus, uint32_t voices, float base, 
 int s2r_set_bus_chorus_mix(s2r_synth *s, uint32_t bus, float dry, float wet) {
     if (!chorus_mix_in_range(dry, wet) || bus >= S2R_MAX_BUSES)
         return set_err(s, S2R_ERR_PATCH_RANGE, "bus %u: dry %g, wet %g: dry and wet lie in [0, 1], the bus below %u", bus, (double)dry, (double)wet, S2R_MAX_BUSES);
-    S2R_TRY(stem_bus(s, S2R_STEM_CHORUS, bus, "s2r_set_bus_chorus_mix", false));
+    S2R_TRY(stem_bus(s, S2R_BUS_CHORUS, bus, "s2r_set_bus_chorus_mix", false));
     s->post.chorus[bus].dry = dry; s->post.chorus[bus].wet = wet;
     return S2R_OK;
 }
 
 int s2r_set_bus_chorus_rate(s2r_synth *s, uint32_t bus, uint32_t phase_inc, uint32_t spread) {
-    S2R_TRY(stem_bus(s, S2R_STEM_CHORUS, bus, "s2r_set_bus_chorus_rate", false));
+    S2R_TRY(stem_bus(s, S2R_BUS_CHORUS, bus, "s2r_set_bus_chorus_rate", false));
     s->post.chorus[bus].phase_inc = phase_inc; s->post.chorus[bus].spread = spread;      // (the phase and the history stay: the LFO bends, nothing clicks)
     return S2R_OK;
 }
 
 int s2r_get_bus_chorus(const s2r_synth *s, uint32_t bus, uint32_t *voices, float *base, float *depth, uint32_t *phase_inc, uint32_t *spread, float *dry,
                        float *wet) {
-    S2R_TRY(stem_bus(s, S2R_STEM_CHORUS, bus, nullptr, false));
+    S2R_TRY(stem_bus(s, S2R_BUS_CHORUS, bus, nullptr, false));
     const S2rPostChain::BusChorus &d = s->post.chorus[bus];
     put(voices, d.voices); put(base, d.base); put(depth, d.depth); put(phase_inc, d.phase_inc); put(spread, d.spread); put(dry, d.dry); put(wet, d.wet);
     return S2R_OK;
@@ -3059,13 +3133,13 @@ int s2r_get_bus_chorus(const s2r_synth *s, uint32_t bus, uint32_t *voices, float
 
 // (the chorus's phase lives on the host)
 int s2r_get_bus_chorus_state(s2r_synth *s, uint32_t bus, float *lr, size_t capacity, uint32_t *phase) {
-    S2R_TRY(stem_history(s, S2R_STEM_CHORUS, bus, lr, nullptr, capacity, "s2r_get_bus_chorus_state"));
+    S2R_TRY(stem_history(s, S2R_BUS_CHORUS, bus, lr, nullptr, capacity, "s2r_get_bus_chorus_state"));
     put(phase, s->post.chorus[bus].phase);
     return S2R_OK;
 }
 
 int s2r_set_bus_chorus_state(s2r_synth *s, uint32_t bus, const float *lr, size_t count, uint32_t phase) {
-    S2R_TRY(stem_history(s, S2R_STEM_CHORUS, bus, nullptr, lr, lr ? count : (size_t)-1, "s2r_set_bus_chorus_state"));
+    S2R_TRY(stem_history(s, S2R_BUS_CHORUS, bus, nullptr, lr, lr ? count : (size_t)-1, "s2r_set_bus_chorus_state"));
     s->post.chorus[bus].phase = phase;
     return S2R_OK;
 }
@@ -3084,25 +3158,25 @@ int s2r_set_bus_delay_mix(s2r_synth *s, uint32_t bus, float feedback, float cros
     if (!delay_mix_in_range(feedback, cross, dry, wet) || bus >= S2R_MAX_BUSES)
         return set_err(s, S2R_ERR_PATCH_RANGE, "bus %u: feedback %g, cross %g, dry %g, wet %g: feedback and cross lie in [-1, 1] with |feedback| + |cross| <= 1, "
                        "dry and wet in [0, 1], the bus below %u", bus, (double)feedback, (double)cross, (double)dry, (double)wet, S2R_MAX_BUSES);
-    S2R_TRY(stem_bus(s, S2R_STEM_DELAY, bus, "s2r_set_bus_delay_mix", false));
+    S2R_TRY(stem_bus(s, S2R_BUS_DELAY, bus, "s2r_set_bus_delay_mix", false));
     S2rPostChain::BusDelay &d = s->post.delay[bus];
     d.feedback = feedback; d.cross = cross; d.dry = dry; d.wet = wet;
     return S2R_OK;
 }
 
 int s2r_get_bus_delay(const s2r_synth *s, uint32_t bus, uint32_t *delay_frames, float *feedback, float *cross, float *dry, float *wet) {
-    S2R_TRY(stem_bus(s, S2R_STEM_DELAY, bus, nullptr, false));
+    S2R_TRY(stem_bus(s, S2R_BUS_DELAY, bus, nullptr, false));
     const S2rPostChain::BusDelay &d = s->post.delay[bus];
     put(delay_frames, d.history); put(feedback, d.feedback); put(cross, d.cross); put(dry, d.dry); put(wet, d.wet);
     return S2R_OK;
 }
 
 int s2r_get_bus_delay_history(s2r_synth *s, uint32_t bus, float *lr, size_t capacity) {
-    return stem_history(s, S2R_STEM_DELAY, bus, lr, nullptr, capacity, "s2r_get_bus_delay_history");
+    return stem_history(s, S2R_BUS_DELAY, bus, lr, nullptr, capacity, "s2r_get_bus_delay_history");
 }
 
 int s2r_set_bus_delay_history(s2r_synth *s, uint32_t bus, const float *lr, size_t count) {
-    return stem_history(s, S2R_STEM_DELAY, bus, nullptr, lr, lr ? count : (size_t)-1, "s2r_set_bus_delay_history");
+    return stem_history(s, S2R_BUS_DELAY, bus, nullptr, lr, lr ? count : (size_t)-1, "s2r_set_bus_delay_history");
 }
 
 // ---- program faders ----
@@ -3714,35 +3788,35 @@ extern "C" uint32_t s2r_debug_pan_slice(const s2r_synth *s) { return s ? s->pan_
 extern "C" float s2r_debug_bus_mix_ms(const s2r_synth *s) { return s && s->timing ? s->bus_mix_ms : -1.0f; }
 // ... of the buses' EQ kernel in that fill: 0 when it ran none (tools/eq_time.py); whether the handle holds the EQs' staging buffer;
 // and the frames the kernel stages at a time (tests/test_gpu_eq.py picks its call lengths around it)
-extern "C" float s2r_debug_bus_eq_ms(const s2r_synth *s) { return s && s->timing ? s->post.eq_insert.timer.ms : -1.0f; }
-extern "C" int s2r_debug_bus_eq_allocated(const s2r_synth *s) { return s && s->post.eq_insert.stage ? 1 : 0; }
+extern "C" float s2r_debug_bus_eq_ms(const s2r_synth *s) { return s && s->timing ? s->post.stage[S2R_BUS_EQ].timer.ms : -1.0f; }
+extern "C" int s2r_debug_bus_eq_allocated(const s2r_synth *s) { return s && s->post.stage[S2R_BUS_EQ].buffer ? 1 : 0; }
 extern "C" uint32_t s2r_debug_eq_tile(void) { return S2R_EQ_TILE; }
 // ... of the buses' dynamics kernel in that fill: 0 when it ran none (tools/dyn_time.py); whether the handle holds the dynamics' staging
 // buffer; and the frames of one stage of the kernel's pipeline (tests/test_gpu_dyn.py picks its call lengths around it)
-extern "C" float s2r_debug_dyn_ms(const s2r_synth *s) { return s && s->timing ? s->post.dyn_insert.timer.ms : -1.0f; }
-extern "C" int s2r_debug_dyn_allocated(const s2r_synth *s) { return s && (s->post.dyn_insert.stage || s->post.dyn_curves || s->post.dyn_meter) ? 1 : 0; }
+extern "C" float s2r_debug_dyn_ms(const s2r_synth *s) { return s && s->timing ? s->post.stage[S2R_BUS_DYN].timer.ms : -1.0f; }
+extern "C" int s2r_debug_dyn_allocated(const s2r_synth *s) { return s && (s->post.stage[S2R_BUS_DYN].buffer || s->post.dyn_curves || s->post.dyn_meter) ? 1 : 0; }
 extern "C" uint32_t s2r_debug_dyn_tile(void) { return S2R_DYN_TILE; }
 // ... of the buses' room kernel in that fill: 0 when it ran none (tools/room_time.py); whether the handle holds the rooms' staging buffer;
 // and the frames of one pass of the kernel (tests/test_gpu_room.py picks its call lengths around it)
-extern "C" float s2r_debug_bus_room_ms(const s2r_synth *s) { return s && s->timing ? s->post.room_insert.timer.ms : -1.0f; }
-extern "C" int s2r_debug_room_allocated(const s2r_synth *s) { return s && s->post.room_insert.stage ? 1 : 0; }
+extern "C" float s2r_debug_bus_room_ms(const s2r_synth *s) { return s && s->timing ? s->post.stage[S2R_BUS_ROOM].timer.ms : -1.0f; }
+extern "C" int s2r_debug_room_allocated(const s2r_synth *s) { return s && s->post.stage[S2R_BUS_ROOM].buffer ? 1 : 0; }
 extern "C" uint32_t s2r_debug_room_tile(void) { return S2R_ROOM_TILE; }
 // ... of the buses' drive kernel in that fill: 0 when it ran none (tools/drive_time.py); whether the handle holds the drives' staging
 // buffer or their tables; and the output frames of one workgroup of the kernel (tests/test_gpu_drive.py picks its call lengths around it)
-extern "C" float s2r_debug_bus_drive_ms(const s2r_synth *s) { return s && s->timing ? s->post.drive_insert.timer.ms : -1.0f; }
-extern "C" int s2r_debug_drive_allocated(const s2r_synth *s) { return s && (s->post.drive_insert.stage || s->post.drive_curves) ? 1 : 0; }
+extern "C" float s2r_debug_bus_drive_ms(const s2r_synth *s) { return s && s->timing ? s->post.stage[S2R_BUS_DRIVE].timer.ms : -1.0f; }
+extern "C" int s2r_debug_drive_allocated(const s2r_synth *s) { return s && (s->post.stage[S2R_BUS_DRIVE].buffer || s->post.drive_curves) ? 1 : 0; }
 extern "C" uint32_t s2r_debug_drive_tile(void) { return S2R_DRIVE_TILE; }
 // ... of the buses' flanger kernel in that fill: 0 when it ran none (tools/flanger_time.py); whether the handle holds the flangers'
 // staging buffer; and the frames of one tile of the kernel (tests/test_gpu_flanger.py picks its call lengths around it)
-extern "C" float s2r_debug_bus_flanger_ms(const s2r_synth *s) { return s && s->timing ? s->post.flanger_insert.timer.ms : -1.0f; }
-extern "C" int s2r_debug_flanger_allocated(const s2r_synth *s) { return s && s->post.flanger_insert.stage ? 1 : 0; }
+extern "C" float s2r_debug_bus_flanger_ms(const s2r_synth *s) { return s && s->timing ? s->post.stage[S2R_BUS_FLANGER].timer.ms : -1.0f; }
+extern "C" int s2r_debug_flanger_allocated(const s2r_synth *s) { return s && s->post.stage[S2R_BUS_FLANGER].buffer ? 1 : 0; }
 extern "C" uint32_t s2r_debug_flanger_tile(void) { return S2R_FLANGER_TILE; }
 // ... of the buses' chorus kernel in that fill: 0 when it ran none (tools/chorus_time.py)
-extern "C" float s2r_debug_bus_chorus_ms(const s2r_synth *s) { return s && s->timing ? s->post.stem[S2R_STEM_CHORUS].timer.ms : -1.0f; }
+extern "C" float s2r_debug_bus_chorus_ms(const s2r_synth *s) { return s && s->timing ? s->post.stage[S2R_BUS_CHORUS].timer.ms : -1.0f; }
 // ... of the buses' delay kernel in that fill: 0 when it ran none (tools/delay_time.py)
-extern "C" float s2r_debug_bus_delay_ms(const s2r_synth *s) { return s && s->timing ? s->post.stem[S2R_STEM_DELAY].timer.ms : -1.0f; }
+extern "C" float s2r_debug_bus_delay_ms(const s2r_synth *s) { return s && s->timing ? s->post.stage[S2R_BUS_DELAY].timer.ms : -1.0f; }
 // ... and of the buses' reverb kernels in that fill: 0 when it ran none (tools/reverb_time.py)
-extern "C" float s2r_debug_bus_fx_ms(const s2r_synth *s) { return s && s->timing ? s->post.stem[S2R_STEM_REVERB].timer.ms : -1.0f; }
+extern "C" float s2r_debug_bus_fx_ms(const s2r_synth *s) { return s && s->timing ? s->post.stage[S2R_BUS_REVERB].timer.ms : -1.0f; }
 // ... and of the master kernel in the last s2r_fill_master (tools/master_time.py)
 extern "C" float s2r_debug_master_ms(const s2r_synth *s) { return s && s->timing ? s->post.master.timer.ms : -1.0f; }
 // ... and of the limiter kernel in that fill: 0 when it ran none (tools/limiter_time.py)
@@ -3829,112 +3903,3 @@ int s2r_voice_pool_query(const s2r_voice_pool *p, uint32_t voice_index, s2r_voic
 }
 
 }  // extern "C"
-
-// ---- per-bus drives: the fourth insert, behind the dynamics and in front of the choruses.  At the end of the file, like
-// the kernel at the end of the link order: every function in front keeps the place it had ----
-static int drive_values(s2r_synth *s, const char *who, uint32_t bus, const float *curve, float pre, float dry, float wet) {
-    if (bus >= S2R_MAX_BUSES || !drive_in_range(curve, pre, dry, wet))
-        return set_err(s, S2R_ERR_PATCH_RANGE, "%s: bus %u, pre %g, dry %g, wet %g: %u finite curve entries, pre in [0, %g], dry and wet in [0, 1], the bus below %u",
-                       who, bus, (double)pre, (double)dry, (double)wet, S2R_DRIVE_CURVE_POINTS, (double)S2R_DRIVE_MAX_PRE, S2R_MAX_BUSES);
-    return S2R_OK;
-}
-
-int s2r_set_bus_drive(s2r_synth *s, uint32_t bus, const float *curve, float pre, float dry, float wet) {
-    S2R_TRY(drive_values(s, "s2r_set_bus_drive", bus, curve, pre, dry, wet));
-    S2R_TRY(post_handle(s, "s2r_set_bus_drive", kStemWords[kDriveEntry].are));
-    if (!curve) return set_err(s, S2R_ERR_INVALID, "s2r_set_bus_drive: no curve");
-    return stem_set(s, "s2r_set_bus_drive", [&](const S2rPostCtx &c) { return s->post.set_drive(c, bus, curve, pre, dry, wet, false); });
-}
-
-int s2r_clear_bus_drive(s2r_synth *s, uint32_t bus) {
-    if (bus >= S2R_MAX_BUSES) return set_err(s, S2R_ERR_PATCH_RANGE, "s2r_clear_bus_drive: bus %u, below %u", bus, S2R_MAX_BUSES);
-    S2R_TRY(post_handle(s, "s2r_clear_bus_drive", kStemWords[kDriveEntry].are));
-    return stem_set(s, "s2r_clear_bus_drive", [&](const S2rPostCtx &c) { return s->post.set_drive(c, bus, nullptr, -1.0f, 0.0f, 0.0f, false); });
-}
-
-int s2r_set_bus_drive_params(s2r_synth *s, uint32_t bus, const float *curve, float pre, float dry, float wet) {
-    S2R_TRY(drive_values(s, "s2r_set_bus_drive_params", bus, curve, pre, dry, wet));
-    S2R_TRY(stem_bus(s, kDriveEntry, bus, "s2r_set_bus_drive_params", true));
-    return stem_set(s, "s2r_set_bus_drive_params", [&](const S2rPostCtx &c) { return s->post.set_drive(c, bus, curve, pre, dry, wet, true); });   // (the history stays)
-}
-
-int s2r_get_bus_drive(const s2r_synth *s, uint32_t bus, uint32_t *present, float *curve, size_t capacity, float *pre, float *dry, float *wet) {
-    S2R_TRY(stem_bus(s, kDriveEntry, bus, nullptr, false));
-    const S2rPostChain::BusDrive &d = s->post.drive[bus];
-    if (d.present() && curve && capacity < S2R_DRIVE_CURVE_POINTS) return S2R_ERR_INVALID;
-    put(present, d.present() ? 1u : 0u); put(pre, d.pre); put(dry, d.dry); put(wet, d.wet);
-    if (d.present() && curve) std::memcpy(curve, d.curve.data(), S2R_DRIVE_CURVE_POINTS * sizeof(float));
-    return S2R_OK;
-}
-
-// the checkpoint pair: the room's state pair's checks, then the stem stages' copy
-static int drive_history(s2r_synth *s, uint32_t bus, float *get, const float *set, size_t count, const char *who) {
-    S2R_TRY(stem_bus(s, kDriveEntry, bus, who, true));
-    const size_t n = 2u * S2R_DRIVE_HISTORY;
-    if (set ? count != n : count < n) return set_err(s, S2R_ERR_INVALID, "%s: the history of bus %u is %zu floats, not %zu", who, bus, n, count);
-    if (!get && !set) return set_err(s, S2R_ERR_INVALID, "%s: null buffer", who);
-    if (set) for (size_t k = 0; k < n; k++) if (!std::isfinite(set[k])) return set_err(s, S2R_ERR_PATCH_RANGE, "%s: value %zu of the history is not finite", who, k);
-    return stem_history(s, kDriveEntry, bus, get, set, count, who);
-}
-
-int s2r_get_bus_drive_history(s2r_synth *s, uint32_t bus, float *lr, size_t capacity) {
-    return drive_history(s, bus, lr, nullptr, capacity, "s2r_get_bus_drive_history");
-}
-
-int s2r_set_bus_drive_history(s2r_synth *s, uint32_t bus, const float *lr, size_t count) {
-    return drive_history(s, bus, nullptr, lr, lr ? count : (size_t)-1, "s2r_set_bus_drive_history");
-}
-
-// ---- per-bus flangers: the fifth insert, behind the drives and in front of the choruses.  At the end of the file, likewise ----
-static int flanger_levels(s2r_synth *s, const char *who, uint32_t bus, float feedback, float cross, float dry, float wet) {
-    if (bus >= S2R_MAX_BUSES || !delay_mix_in_range(feedback, cross, dry, wet))
-        return set_err(s, S2R_ERR_PATCH_RANGE, "%s: bus %u, feedback %g, cross %g, dry %g, wet %g: feedback and cross in [-1, 1] with |feedback| + |cross| <= 1, dry and "
-                       "wet in [0, 1], the bus below %u", who, bus, (double)feedback, (double)cross, (double)dry, (double)wet, S2R_MAX_BUSES);
-    return S2R_OK;
-}
-
-int s2r_set_bus_flanger(s2r_synth *s, uint32_t bus, float base, float depth, uint32_t phase_inc, uint32_t spread, float feedback, float cross, float dry,
-                        float wet) {
-    if (!flanger_delay_in_range(base, depth))
-        return set_err(s, S2R_ERR_PATCH_RANGE, "s2r_set_bus_flanger: bus %u, base %g, depth %g: base >= %g and depth >= 0 with base + depth <= %g frames", bus,
-                       (double)base, (double)depth, (double)S2R_FLANGER_MIN_DELAY, (double)S2R_FLANGER_MAX_DELAY);
-    S2R_TRY(flanger_levels(s, "s2r_set_bus_flanger", bus, feedback, cross, dry, wet));
-    S2R_TRY(post_handle(s, "s2r_set_bus_flanger", kStemWords[kFlangerEntry].are));
-    return stem_set(s, "s2r_set_bus_flanger", [&](const S2rPostCtx &c) { return s->post.set_flanger(c, bus, base, depth, phase_inc, spread, feedback, cross, dry, wet); });
-}
-
-int s2r_clear_bus_flanger(s2r_synth *s, uint32_t bus) {
-    if (bus >= S2R_MAX_BUSES) return set_err(s, S2R_ERR_PATCH_RANGE, "s2r_clear_bus_flanger: bus %u, below %u", bus, S2R_MAX_BUSES);
-    S2R_TRY(post_handle(s, "s2r_clear_bus_flanger", kStemWords[kFlangerEntry].are));
-    return stem_set(s, "s2r_clear_bus_flanger", [&](const S2rPostCtx &c) { return s->post.set_flanger(c, bus, -1.0f, 0.0f, 0, 0, 0.0f, 0.0f, 0.0f, 0.0f); });
-}
-
-int s2r_set_bus_flanger_params(s2r_synth *s, uint32_t bus, uint32_t phase_inc, uint32_t spread, float feedback, float cross, float dry, float wet) {
-    S2R_TRY(flanger_levels(s, "s2r_set_bus_flanger_params", bus, feedback, cross, dry, wet));
-    S2R_TRY(stem_bus(s, kFlangerEntry, bus, "s2r_set_bus_flanger_params", true));
-    S2rPostChain::BusFlanger &d = s->post.flanger[bus];          // (the phase and the line stay: the LFO bends, the comb retunes, nothing clicks)
-    d.phase_inc = phase_inc; d.spread = spread; d.feedback = feedback; d.cross = cross; d.dry = dry; d.wet = wet;
-    return S2R_OK;
-}
-
-int s2r_get_bus_flanger(const s2r_synth *s, uint32_t bus, float *base, float *depth, uint32_t *phase_inc, uint32_t *spread, float *feedback, float *cross,
-                        float *dry, float *wet) {
-    S2R_TRY(stem_bus(s, kFlangerEntry, bus, nullptr, false));
-    const S2rPostChain::BusFlanger &d = s->post.flanger[bus];
-    put(base, d.base); put(depth, d.depth); put(phase_inc, d.phase_inc); put(spread, d.spread); put(feedback, d.feedback); put(cross, d.cross);
-    put(dry, d.dry); put(wet, d.wet);
-    return S2R_OK;
-}
-
-// (the flanger's phase lives on the host, as the chorus's)
-int s2r_get_bus_flanger_state(s2r_synth *s, uint32_t bus, float *lr, size_t capacity, uint32_t *phase) {
-    S2R_TRY(stem_history(s, kFlangerEntry, bus, lr, nullptr, capacity, "s2r_get_bus_flanger_state"));
-    put(phase, s->post.flanger[bus].phase);
-    return S2R_OK;
-}
-
-int s2r_set_bus_flanger_state(s2r_synth *s, uint32_t bus, const float *lr, size_t count, uint32_t phase) {
-    S2R_TRY(stem_history(s, kFlangerEntry, bus, nullptr, lr, lr ? count : (size_t)-1, "s2r_set_bus_flanger_state"));
-    s->post.flanger[bus].phase = phase;
-    return S2R_OK;
-}

@@ -1,4 +1,4 @@
-// s2r_post.cpp — the post-mix chain (s2r_post.h): the EQs, the dynamics, the drives, the flangers, the stem stages (choruses, delays, reverbs), the rooms, master section, master limiter.  Compiled with hipcc, -ffp-contract=off.
+// s2r_post.cpp — the post-mix chain (s2r_post.h): the eight bus stages (EQs, dynamics, drives, flangers, choruses, delays, reverbs, rooms), master section, master limiter.  Compiled with hipcc, -ffp-contract=off.
 #include "s2r_post.h"
 #include "s2r_rules.h"
 
@@ -44,6 +44,11 @@ hipError_t replace(const S2rPostCtx &c, float *&stage, F &slot, F f, size_t line
 }
 hipError_t nothing_more(S2rBusLine &) { return hipSuccess; }
 
+// each bus stage's part of launch, by S2rBusStage
+using StageLaunch = hipError_t (S2rPostChain::*)(const S2rPostCtx &, const S2rPostCall &) const;
+const StageLaunch kStageLaunch[S2R_BUS_STAGES] = {&S2rPostChain::launch_eq,     &S2rPostChain::launch_dyn,   &S2rPostChain::launch_drive,  &S2rPostChain::launch_flanger,
+                                                  &S2rPostChain::launch_chorus, &S2rPostChain::launch_delay, &S2rPostChain::launch_reverb, &S2rPostChain::launch_room};
+
 }  // namespace
 
 hipError_t S2rBusLine::alloc(size_t n) {
@@ -65,13 +70,8 @@ hipError_t S2rPostTimer::begin(hipStream_t stream) {
 hipError_t S2rPostChain::prepare(const S2rPostCtx &c, uint32_t n_buses, uint32_t frames, bool master_fill, bool stems, S2rPostCall &call) {
     call = S2rPostCall{};
     call.n_buses = n_buses; call.frames = frames; call.master = master_fill; call.stems = stems;
-    for (int k = 0; k < S2R_STEM_STAGES; k++)
-        for (uint32_t b = 0; b < n_buses; b++) if (bus(k, b).present()) call.on[k] = true;       // (an effect on a bus past the call's is idle in it)
-    for (uint32_t b = 0; b < n_buses; b++) if (eq[b].present()) call.eq = true;                      // (and so is an EQ)
-    for (uint32_t b = 0; b < n_buses; b++) if (dyn_runs(b, n_buses)) call.dyn = true;                // (and dynamics, also when their key bus is past the call's)
-    for (uint32_t b = 0; b < n_buses; b++) if (room[b].present()) call.room = true;                  // (and a room)
-    for (uint32_t b = 0; b < n_buses; b++) if (drive[b].present()) call.drive = true;                // (and a drive)
-    for (uint32_t b = 0; b < n_buses; b++) if (flanger[b].present()) call.flanger = true;            // (and a flanger)
+    for (int k = 0; k < S2R_BUS_STAGES; k++)
+        for (uint32_t b = 0; b < n_buses; b++) if (runs(k, b, n_buses)) call.on[k] = true;
     call.limited = master_fill && limiter.lookahead != 0;
     if (call.master) {                                           // the device copy of the stems and the pinned rows of block partials
         if (!master.stage) POST_HIP(hipMalloc((void **)&master.stage, (size_t)2 * S2R_MAX_BUSES * c.max_frames * sizeof(float)));
@@ -82,93 +82,16 @@ hipError_t S2rPostChain::prepare(const S2rPostCtx &c, uint32_t n_buses, uint32_t
         for (float *&p : limiter.state) if (!p) POST_HIP(hipMalloc((void **)&p, kLimState * sizeof(float)));
         POST_HIP(pinned_rows(limiter.partials, limiter.partials_dev, (size_t)((c.max_frames + S2R_LIMITER_BLOCK - 1u) / S2R_LIMITER_BLOCK) * 2u));
     }
-    float *stages[S2R_STEM_STAGES];
-    for (int k = 0; k < S2R_STEM_STAGES; k++) stages[k] = stem[k].stage;
-    call.route = s2r_post_route_flanger(call, s2r_post_route_drive(call, s2r_post_route_room(call, s2r_post_route_dyn(call, s2r_post_route_eq(call, s2r_post_route(call, stages, master.stage, limiter.in, c.bus_out_dev, c.out_host_dev),
-                                                                                      eq_insert.stage), dyn_insert.stage), room_insert.stage), drive_insert.stage), flanger_insert.stage);
+    float *own[S2R_BUS_STAGES];
+    for (int k = 0; k < S2R_BUS_STAGES; k++) own[k] = stage[k].buffer;
+    call.route = s2r_post_route(call, own, master.stage, limiter.in, c.bus_out_dev, c.out_host_dev);
     return hipSuccess;
 }
 
 hipError_t S2rPostChain::launch(const S2rPostCtx &c, const S2rPostCall &call) {
-    const S2rPostRouteFlanger &r = call.route; const float fn = (float)call.frames;
-    if (call.eq) {                                               // once per call, over all of its frames, in front of every stem stage
-        S2rEq a{};
-        for (uint32_t b = 0; b < call.n_buses; b++) {
-            const BusEq &f = eq[b];
-            if (!f.present()) continue;
-            S2rEqBus &d = a.bus[b];
-            d.line = f.now(); d.next = f.next(); d.n_bands = f.n_bands;
-            std::memcpy(d.c, f.c, sizeof d.c);
-        }
-        a.in = r.eq.in; a.out = r.eq.out; a.n_buses = call.n_buses; a.frames = call.frames;
-        POST_TIMED(c, eq_insert.timer, s2r_launch_bus_eq(a, c.stream));
-    }
-    if (call.dyn) {                                              // likewise, behind the EQs: every bus and every key as the EQs left them
-        S2rDyn a{};
-        for (uint32_t b = 0; b < call.n_buses; b++) {
-            if (!dyn_runs(b, call.n_buses)) continue;
-            const BusDyn &f = dyn[b];
-            S2rDynBus &d = a.bus[b];
-            d.line = f.now(); d.next = f.next(); d.curve = dyn_curves + (size_t)b * S2R_DYN_CURVE_POINTS;
-            d.key = f.key; d.a_att = f.a_att; d.a_rel = f.a_rel;
-        }
-        a.in = r.dyn.in; a.out = r.dyn.out; a.meter = dyn_meter_dev; a.n_buses = call.n_buses; a.frames = call.frames;
-        POST_TIMED(c, dyn_insert.timer, s2r_launch_bus_dyn(a, c.stream));
-    }
-    if (call.drive) POST_HIP(launch_drive(c, call));             // likewise, behind the dynamics: tiles x buses workgroups, none waiting for another
-    if (call.flanger) POST_HIP(launch_flanger(c, call));         // likewise, behind the drive: a wavefront per bus, tile by tile
-    if (call.on[S2R_STEM_CHORUS]) {                              // likewise, in front of the delays
-        S2rChorus a{};
-        for (uint32_t b = 0; b < call.n_buses; b++) {
-            const BusChorus &f = chorus[b];
-            if (!f.present()) continue;
-            S2rChorusBus &d = a.bus[b];
-            d.line = f.now(); d.next = f.next(); d.voices = f.voices; d.history = f.history;
-            d.phase = f.phase; d.phase_inc = f.phase_inc; d.spread = f.spread;
-            d.base = f.base; d.depth = f.depth; d.dry = f.dry; d.wet = f.wet;
-            for (uint32_t v = 0; v < f.voices; v++) d.off[v] = chorus_voice_offset(v, f.voices);
-        }
-        a.in = r.stem[S2R_STEM_CHORUS].in; a.out = r.stem[S2R_STEM_CHORUS].out; a.n_buses = call.n_buses; a.frames = call.frames;
-        POST_TIMED(c, stem[S2R_STEM_CHORUS].timer, s2r_launch_bus_chorus(a, c.stream));
-    }
-    if (call.on[S2R_STEM_DELAY]) {                               // likewise, in front of the reverbs
-        S2rDelay a{};
-        for (uint32_t b = 0; b < call.n_buses; b++) {
-            const BusDelay &f = delay[b];
-            if (!f.present()) continue;
-            S2rDelayBus &d = a.bus[b];
-            d.line = f.now(); d.next = f.next(); d.delay = f.history;
-            d.feedback = f.feedback; d.cross = f.cross; d.dry = f.dry; d.wet = f.wet;
-        }
-        a.in = r.stem[S2R_STEM_DELAY].in; a.out = r.stem[S2R_STEM_DELAY].out; a.n_buses = call.n_buses; a.frames = call.frames;
-        POST_TIMED(c, stem[S2R_STEM_DELAY].timer, s2r_launch_bus_delay(a, c.stream));
-    }
-    if (call.on[S2R_STEM_REVERB]) {                              // likewise
-        S2rFx a{};
-        for (uint32_t b = 0; b < call.n_buses; b++) {
-            const BusFx &f = fx[b];
-            if (!f.present()) continue;
-            S2rFxBus &d = a.bus[b];
-            d.taps = f.taps; d.line = f.now(); d.next = f.next(); d.partials = f.partials;
-            d.n_taps = f.n_taps; d.n_seg = (f.n_taps + S2R_IR_SEGMENT - 1u) / S2R_IR_SEGMENT;
-            d.tstride = f.tstride; d.lstride = f.lstride; d.dry = f.dry; d.wet = f.wet;
-        }
-        a.stage = r.stem[S2R_STEM_REVERB].in; a.out = r.stem[S2R_STEM_REVERB].out; a.n_buses = call.n_buses; a.frames = call.frames; a.pstride = fx_pstride(c);
-        POST_TIMED(c, stem[S2R_STEM_REVERB].timer, s2r_launch_bus_fx(a, c.stream));
-    }
-    if (call.room) {                                             // the last stem writer: every bus as the stages in front left it
-        S2rRoom a{};
-        for (uint32_t b = 0; b < call.n_buses; b++) {
-            const BusRoom &f = room[b];
-            if (!f.present()) continue;
-            S2rRoomBus &d = a.bus[b];
-            d.line = f.now(); d.next = f.next(); d.work = f.work; d.floats = (uint32_t)f.floats;
-            room_layout(f.cd, f.ad, f.spread, d.len, d.off);
-            d.feedback = f.feedback; d.damp = f.damp; d.d1 = f.d1; d.g = f.g; d.gain = f.gain; d.dry = f.dry; d.wet = f.wet; d.cross = f.cross;
-        }
-        a.in = r.room.in; a.out = r.room.out; a.n_buses = call.n_buses; a.frames = call.frames; a.wstride = c.max_frames;
-        POST_TIMED(c, room_insert.timer, s2r_launch_bus_room(a, c.stream));
-    }
+    const S2rPostRoute &r = call.route; const float fn = (float)call.frames;
+    for (int k = 0; k < S2R_BUS_STAGES; k++)                     // each once per call, over all of its frames, every bus as the stages in front left it
+        if (call.on[k]) POST_TIMED(c, stage[k].timer, (this->*kStageLaunch[k])(c, call));
     if (call.master) {                                           // returns, master fader and the meters' block partials
         S2rMaster m{};
         m.stage = r.master_in; m.out = r.master_out; m.stems = r.master_stems; m.partials = master.partials_dev;
@@ -196,18 +119,125 @@ hipError_t S2rPostChain::launch(const S2rPostCtx &c, const S2rPostCall &call) {
     return hipSuccess;
 }
 
+hipError_t S2rPostChain::launch_eq(const S2rPostCtx &c, const S2rPostCall &call) const {
+    S2rEq a{};
+    for (uint32_t b = 0; b < call.n_buses; b++) {
+        const BusEq &f = eq[b];
+        if (!f.present()) continue;
+        S2rEqBus &d = a.bus[b];
+        d.line = f.now(); d.next = f.next(); d.n_bands = f.n_bands;
+        std::memcpy(d.c, f.c, sizeof d.c);
+    }
+    a.in = call.route.stage[S2R_BUS_EQ].in; a.out = call.route.stage[S2R_BUS_EQ].out; a.n_buses = call.n_buses; a.frames = call.frames;
+    return s2r_launch_bus_eq(a, c.stream);
+}
+
+hipError_t S2rPostChain::launch_dyn(const S2rPostCtx &c, const S2rPostCall &call) const {       // every bus and every key as the EQs left them
+    S2rDyn a{};
+    for (uint32_t b = 0; b < call.n_buses; b++) {
+        if (!runs(S2R_BUS_DYN, b, call.n_buses)) continue;
+        const BusDyn &f = dyn[b];
+        S2rDynBus &d = a.bus[b];
+        d.line = f.now(); d.next = f.next(); d.curve = dyn_curves + (size_t)b * S2R_DYN_CURVE_POINTS;
+        d.key = f.key; d.a_att = f.a_att; d.a_rel = f.a_rel;
+    }
+    a.in = call.route.stage[S2R_BUS_DYN].in; a.out = call.route.stage[S2R_BUS_DYN].out; a.meter = dyn_meter_dev; a.n_buses = call.n_buses; a.frames = call.frames;
+    return s2r_launch_bus_dyn(a, c.stream);
+}
+
+hipError_t S2rPostChain::launch_drive(const S2rPostCtx &c, const S2rPostCall &call) const {     // tiles x buses workgroups, none waiting for another
+    S2rDrive a{};
+    for (uint32_t b = 0; b < call.n_buses; b++) {
+        const BusDrive &f = drive[b];
+        if (!f.present()) continue;
+        S2rDriveBus &d = a.bus[b];
+        d.curve = drive_curves + (size_t)b * S2R_DRIVE_CURVE_POINTS; d.line = f.now(); d.next = f.next();
+        d.pre = f.pre; d.dry = f.dry; d.wet = f.wet;
+    }
+    const S2rDriveTaps &taps = drive_taps();
+    std::memcpy(a.h, taps.h, sizeof a.h); std::memcpy(a.g, taps.g, sizeof a.g);
+    a.in = call.route.stage[S2R_BUS_DRIVE].in; a.out = call.route.stage[S2R_BUS_DRIVE].out; a.n_buses = call.n_buses; a.frames = call.frames;
+    return s2r_launch_bus_drive(a, c.stream);
+}
+
+hipError_t S2rPostChain::launch_flanger(const S2rPostCtx &c, const S2rPostCall &call) const {   // a wavefront per bus, tile by tile
+    S2rFlanger a{};
+    for (uint32_t b = 0; b < call.n_buses; b++) {
+        const BusFlanger &f = flanger[b];
+        if (!f.present()) continue;
+        S2rFlangerBus &d = a.bus[b];
+        d.line = f.now(); d.next = f.next(); d.history = f.history;
+        d.phase = f.phase; d.phase_inc = f.phase_inc; d.spread = f.spread;
+        d.base = f.base; d.depth = f.depth; d.feedback = f.feedback; d.cross = f.cross; d.dry = f.dry; d.wet = f.wet;
+    }
+    a.in = call.route.stage[S2R_BUS_FLANGER].in; a.out = call.route.stage[S2R_BUS_FLANGER].out; a.n_buses = call.n_buses; a.frames = call.frames;
+    return s2r_launch_bus_flanger(a, c.stream);
+}
+
+hipError_t S2rPostChain::launch_chorus(const S2rPostCtx &c, const S2rPostCall &call) const {
+    S2rChorus a{};
+    for (uint32_t b = 0; b < call.n_buses; b++) {
+        const BusChorus &f = chorus[b];
+        if (!f.present()) continue;
+        S2rChorusBus &d = a.bus[b];
+        d.line = f.now(); d.next = f.next(); d.voices = f.voices; d.history = f.history;
+        d.phase = f.phase; d.phase_inc = f.phase_inc; d.spread = f.spread;
+        d.base = f.base; d.depth = f.depth; d.dry = f.dry; d.wet = f.wet;
+        for (uint32_t v = 0; v < f.voices; v++) d.off[v] = chorus_voice_offset(v, f.voices);
+    }
+    a.in = call.route.stage[S2R_BUS_CHORUS].in; a.out = call.route.stage[S2R_BUS_CHORUS].out; a.n_buses = call.n_buses; a.frames = call.frames;
+    return s2r_launch_bus_chorus(a, c.stream);
+}
+
+hipError_t S2rPostChain::launch_delay(const S2rPostCtx &c, const S2rPostCall &call) const {
+    S2rDelay a{};
+    for (uint32_t b = 0; b < call.n_buses; b++) {
+        const BusDelay &f = delay[b];
+        if (!f.present()) continue;
+        S2rDelayBus &d = a.bus[b];
+        d.line = f.now(); d.next = f.next(); d.delay = f.history;
+        d.feedback = f.feedback; d.cross = f.cross; d.dry = f.dry; d.wet = f.wet;
+    }
+    a.in = call.route.stage[S2R_BUS_DELAY].in; a.out = call.route.stage[S2R_BUS_DELAY].out; a.n_buses = call.n_buses; a.frames = call.frames;
+    return s2r_launch_bus_delay(a, c.stream);
+}
+
+hipError_t S2rPostChain::launch_reverb(const S2rPostCtx &c, const S2rPostCall &call) const {
+    S2rFx a{};
+    for (uint32_t b = 0; b < call.n_buses; b++) {
+        const BusFx &f = fx[b];
+        if (!f.present()) continue;
+        S2rFxBus &d = a.bus[b];
+        d.taps = f.taps; d.line = f.now(); d.next = f.next(); d.partials = f.partials;
+        d.n_taps = f.n_taps; d.n_seg = (f.n_taps + S2R_IR_SEGMENT - 1u) / S2R_IR_SEGMENT;
+        d.tstride = f.tstride; d.lstride = f.lstride; d.dry = f.dry; d.wet = f.wet;
+    }
+    a.stage = call.route.stage[S2R_BUS_REVERB].in; a.out = call.route.stage[S2R_BUS_REVERB].out; a.n_buses = call.n_buses; a.frames = call.frames; a.pstride = fx_pstride(c);
+    return s2r_launch_bus_fx(a, c.stream);
+}
+
+hipError_t S2rPostChain::launch_room(const S2rPostCtx &c, const S2rPostCall &call) const {      // the last of the bus stages
+    S2rRoom a{};
+    for (uint32_t b = 0; b < call.n_buses; b++) {
+        const BusRoom &f = room[b];
+        if (!f.present()) continue;
+        S2rRoomBus &d = a.bus[b];
+        d.line = f.now(); d.next = f.next(); d.work = f.work; d.floats = (uint32_t)f.floats;
+        room_layout(f.cd, f.ad, f.spread, d.len, d.off);
+        d.feedback = f.feedback; d.damp = f.damp; d.d1 = f.d1; d.g = f.g; d.gain = f.gain; d.dry = f.dry; d.wet = f.wet; d.cross = f.cross;
+    }
+    a.in = call.route.stage[S2R_BUS_ROOM].in; a.out = call.route.stage[S2R_BUS_ROOM].out; a.n_buses = call.n_buses; a.frames = call.frames; a.wstride = c.max_frames;
+    return s2r_launch_bus_room(a, c.stream);
+}
+
 void S2rPostChain::commit(const S2rPostCall &call) {
-    if (call.eq) for (uint32_t b = 0; b < call.n_buses; b++) if (eq[b].present()) eq[b].flip();     // the EQs' states have moved on
-    if (call.dyn)                                                // ... the dynamics' gains, and the kernel's minima are the call's meters
-        for (uint32_t b = 0; b < call.n_buses; b++) if (dyn_runs(b, call.n_buses)) { dyn[b].flip(); dyn[b].min_gain = dyn_meter[b]; }
-    if (call.drive) for (uint32_t b = 0; b < call.n_buses; b++) if (drive[b].present()) drive[b].flip();   // ... the drives' histories
-    if (call.flanger)                                            // ... the flangers' lines and their phases
-        for (uint32_t b = 0; b < call.n_buses; b++) if (flanger[b].present()) { flanger[b].flip(); flanger[b].phase += flanger[b].phase_inc * call.frames; }
-    for (int k = 0; k < S2R_STEM_STAGES; k++)                    // the histories have moved on
-        if (call.on[k]) for (uint32_t b = 0; b < call.n_buses; b++) if (bus(k, b).present()) bus(k, b).flip();
-    if (call.on[S2R_STEM_CHORUS])                                // ... and the choruses' phases
-        for (uint32_t b = 0; b < call.n_buses; b++) if (chorus[b].present()) chorus[b].phase += chorus[b].phase_inc * call.frames;
-    if (call.room) for (uint32_t b = 0; b < call.n_buses; b++) if (room[b].present()) room[b].flip();   // ... and the rooms' lines
+    for (int k = 0; k < S2R_BUS_STAGES; k++)                     // the histories and states have moved on
+        for (uint32_t b = 0; b < call.n_buses; b++) if (runs(k, b, call.n_buses)) bus(k, b).flip();
+    for (uint32_t b = 0; b < call.n_buses; b++) {                // ... and what is no flip: the LFOs' phases, and the dynamics kernel's minima are the call's meters
+        if (chorus[b].present()) chorus[b].phase += chorus[b].phase_inc * call.frames;
+        if (flanger[b].present()) flanger[b].phase += flanger[b].phase_inc * call.frames;
+        if (runs(S2R_BUS_DYN, b, call.n_buses)) dyn[b].min_gain = dyn_meter[b];
+    }
     if (call.master) {                                           // the block partials in block order, and applied = target
         Master &ms = master;
         const uint32_t n_ch = (call.n_buses + 1u) * 2u, n_blocks = (call.frames + S2R_METER_BLOCK - 1u) / S2R_METER_BLOCK;
@@ -238,12 +268,7 @@ void S2rPostChain::commit(const S2rPostCall &call) {
 
 // a stage that the fill could have run and did not reads 0; a panned fill leaves all ten values alone, a bus fill the master's two
 hipError_t S2rPostChain::read_timers(const S2rPostCall &call) {
-    if (call.n_buses) { eq_insert.timer.ms = 0.0f; if (call.eq) POST_HIP(eq_insert.timer.read()); }
-    if (call.n_buses) { dyn_insert.timer.ms = 0.0f; if (call.dyn) POST_HIP(dyn_insert.timer.read()); }
-    if (call.n_buses) { drive_insert.timer.ms = 0.0f; if (call.drive) POST_HIP(drive_insert.timer.read()); }
-    if (call.n_buses) { flanger_insert.timer.ms = 0.0f; if (call.flanger) POST_HIP(flanger_insert.timer.read()); }
-    if (call.n_buses) for (int k = 0; k < S2R_STEM_STAGES; k++) { stem[k].timer.ms = 0.0f; if (call.on[k]) POST_HIP(stem[k].timer.read()); }
-    if (call.n_buses) { room_insert.timer.ms = 0.0f; if (call.room) POST_HIP(room_insert.timer.read()); }
+    if (call.n_buses) for (int k = 0; k < S2R_BUS_STAGES; k++) { stage[k].timer.ms = 0.0f; if (call.on[k]) POST_HIP(stage[k].timer.read()); }
     if (call.master) {
         POST_HIP(master.timer.read());
         limiter.timer.ms = 0.0f;
@@ -253,21 +278,11 @@ hipError_t S2rPostChain::read_timers(const S2rPostCall &call) {
 }
 
 void S2rPostChain::release() {
-    for (uint32_t b = 0; b < S2R_MAX_BUSES; b++) { drop(eq[b]); drop(dyn[b]); drop(chorus[b]); drop(delay[b]); drop(fx[b]); drop(room[b]); drop(drive[b]); drop(flanger[b]); }
-    for (Stem &st : stem) { if (st.stage) (void)hipFree(st.stage); st.timer.destroy(); }
-    if (eq_insert.stage) (void)hipFree(eq_insert.stage);
-    eq_insert.timer.destroy();
-    for (float *p : {dyn_insert.stage, dyn_curves}) if (p) (void)hipFree(p);
-    if (dyn_meter) (void)hipHostFree(dyn_meter);
-    dyn_insert.timer.destroy();
-    if (room_insert.stage) (void)hipFree(room_insert.stage);
-    room_insert.timer.destroy();
-    for (float *p : {drive_insert.stage, drive_curves}) if (p) (void)hipFree(p);
-    drive_insert.timer.destroy();
-    if (flanger_insert.stage) (void)hipFree(flanger_insert.stage);
-    flanger_insert.timer.destroy();
-    for (float *p : {master.stage, limiter.state[0], limiter.state[1], limiter.in}) if (p) (void)hipFree(p);
-    for (float *p : {master.partials, limiter.partials}) if (p) (void)hipHostFree(p);
+    for (uint32_t b = 0; b < S2R_MAX_BUSES; b++) { drop(eq[b]); drop(dyn[b]); drop(drive[b]); drop(flanger[b]); drop(chorus[b]); drop(delay[b]); drop(fx[b]); drop(room[b]); }
+    for (Stem &st : stage) { if (st.buffer) (void)hipFree(st.buffer); st.timer.destroy(); }
+    // ... and what is neither a line nor a stage's buffer
+    for (float *p : {dyn_curves, drive_curves, master.stage, limiter.state[0], limiter.state[1], limiter.in}) if (p) (void)hipFree(p);
+    for (float *p : {dyn_meter, master.partials, limiter.partials}) if (p) (void)hipHostFree(p);
     for (S2rPostTimer *t : {&master.timer, &limiter.timer}) t->destroy();
 }
 
@@ -276,12 +291,7 @@ hipError_t S2rPostChain::set_eq(const S2rPostCtx &c, uint32_t bus, uint32_t n_ba
     BusEq f;
     f.n_bands = n_bands; f.history = 2u * n_bands;
     std::memcpy(f.c, coeffs, (size_t)n_bands * 5u * sizeof(float));
-    return replace(c, eq_insert.stage, eq[bus], f, 4u * (size_t)n_bands, nothing_more);
-}
-
-hipError_t S2rPostChain::eq_state(const S2rPostCtx &c, uint32_t bus, float *get, const float *set) {
-    POST_HIP(eq[bus].copy(get, set, 0, eq[bus].floats, c.stream));
-    return hipStreamSynchronize(c.stream);
+    return replace(c, stage[S2R_BUS_EQ].buffer, eq[bus], f, 4u * (size_t)n_bands, nothing_more);
 }
 
 // The tables and the pinned meter row come first and once; the bus's row of the tables is written last, by a copy queued behind
@@ -303,15 +313,79 @@ hipError_t S2rPostChain::set_dyn(const S2rPostCtx &c, uint32_t bus, uint32_t key
     f.key = key; f.a_att = a_att; f.a_rel = a_rel; f.history = 1u;
     f.curve.assign(curve, curve + S2R_DYN_CURVE_POINTS);
     float *const to = dyn_curves + (size_t)bus * S2R_DYN_CURVE_POINTS;
-    return replace(c, dyn_insert.stage, dyn[bus], f, 1u, [&](BusDyn &n) {          // y = curve[0], the gain at silence
+    return replace(c, stage[S2R_BUS_DYN].buffer, dyn[bus], f, 1u, [&](BusDyn &n) {          // y = curve[0], the gain at silence
         POST_HIP(hipMemcpyAsync(n.line[0], n.curve.data(), sizeof(float), hipMemcpyHostToDevice, c.stream));
         return hipMemcpyAsync(to, n.curve.data(), S2R_DYN_CURVE_POINTS * sizeof(float), hipMemcpyHostToDevice, c.stream);
     });
 }
 
-hipError_t S2rPostChain::dyn_state(const S2rPostCtx &c, uint32_t bus, float *get, const float *set) {
-    POST_HIP(dyn[bus].copy(get, set, 0, 1u, c.stream));
-    return hipStreamSynchronize(c.stream);
+// As set_dyn: the tables come first and once, the bus's row of them is written last, behind everything that can fail for want of
+// memory, so that a refused set leaves the earlier drive whole.  The history starts as +0.0 (replace).
+hipError_t S2rPostChain::set_drive(const S2rPostCtx &c, uint32_t bus, const float *curve, float pre, float dry, float wet, bool keep_state) {
+    if (pre < 0.0f) { drop(drive[bus]); return hipSuccess; }
+    constexpr size_t kRow = S2R_DRIVE_CURVE_POINTS;
+    if (keep_state) {
+        BusDrive &d = drive[bus];
+        if (curve) {
+            POST_HIP(hipMemcpyAsync(drive_curves + bus * kRow, curve, kRow * sizeof(float), hipMemcpyHostToDevice, c.stream));
+            POST_HIP(hipStreamSynchronize(c.stream));
+            d.curve.assign(curve, curve + kRow);
+        }
+        d.pre = pre; d.dry = dry; d.wet = wet;
+        return hipSuccess;
+    }
+    if (!drive_curves) POST_HIP(hipMalloc((void **)&drive_curves, (size_t)S2R_MAX_BUSES * kRow * sizeof(float)));
+    BusDrive f;
+    f.pre = pre; f.dry = dry; f.wet = wet; f.history = S2R_DRIVE_HISTORY;
+    f.curve.assign(curve, curve + kRow);
+    float *const to = drive_curves + bus * kRow;
+    return replace(c, stage[S2R_BUS_DRIVE].buffer, drive[bus], f, 2u * (size_t)S2R_DRIVE_HISTORY, [&](BusDrive &n) {
+        return hipMemcpyAsync(to, n.curve.data(), kRow * sizeof(float), hipMemcpyHostToDevice, c.stream);
+    });
+}
+
+// the line starts as +0.0 and the phase as 0 (replace); the other copy is written whole by the first call
+hipError_t S2rPostChain::set_flanger(const S2rPostCtx &c, uint32_t bus, float base, float depth, uint32_t phase_inc, uint32_t spread, float feedback, float cross,
+                                     float dry, float wet) {
+    if (base < 0.0f) { drop(flanger[bus]); return hipSuccess; }
+    BusFlanger f;
+    f.history = flanger_history(base, depth); f.base = base; f.depth = depth; f.feedback = feedback; f.cross = cross; f.dry = dry; f.wet = wet;
+    f.phase_inc = phase_inc; f.spread = spread;
+    return replace(c, stage[S2R_BUS_FLANGER].buffer, flanger[bus], f, 2u * (size_t)f.history, nothing_more);
+}
+
+hipError_t S2rPostChain::set_chorus(const S2rPostCtx &c, uint32_t bus, uint32_t voices, float base, float depth, uint32_t phase_inc, uint32_t spread, float dry,
+                                    float wet) {
+    if (voices == 0) { drop(chorus[bus]); return hipSuccess; }
+    BusChorus f;
+    f.voices = voices; f.history = chorus_history(base, depth); f.base = base; f.depth = depth; f.dry = dry; f.wet = wet;
+    f.phase_inc = phase_inc; f.spread = spread;
+    return replace(c, stage[S2R_BUS_CHORUS].buffer, chorus[bus], f, 2u * (size_t)f.history, nothing_more);
+}
+
+hipError_t S2rPostChain::set_delay(const S2rPostCtx &c, uint32_t bus, uint32_t delay_frames, float feedback, float cross, float dry, float wet) {
+    if (delay_frames == 0) { drop(delay[bus]); return hipSuccess; }
+    BusDelay f;
+    f.history = delay_frames; f.feedback = feedback; f.cross = cross; f.dry = dry; f.wet = wet;
+    return replace(c, stage[S2R_BUS_DELAY].buffer, delay[bus], f, 2u * (size_t)delay_frames, nothing_more);
+}
+
+hipError_t S2rPostChain::set_reverb(const S2rPostCtx &c, uint32_t bus, const float *ir_l, const float *ir_r, uint32_t n_taps, float dry, float wet) {
+    if (n_taps == 0) { drop(fx[bus]); return hipSuccess; }
+    BusFx f;
+    const uint32_t n_seg = (n_taps + S2R_IR_SEGMENT - 1u) / S2R_IR_SEGMENT;
+    f.n_taps = n_taps; f.history = n_taps - 1u; f.dry = dry; f.wet = wet;
+    f.tstride = n_seg * S2R_IR_SEGMENT;
+    f.lstride = (n_taps - 1u + c.max_frames + 3u) & ~3u;
+    std::vector<float> padded(2u * (size_t)f.tstride, 0.0f);
+    std::memcpy(padded.data(), ir_l, (size_t)n_taps * sizeof(float));
+    std::memcpy(padded.data() + f.tstride, ir_r, (size_t)n_taps * sizeof(float));
+    return replace(c, stage[S2R_BUS_REVERB].buffer, fx[bus], f, 2u * (size_t)f.lstride, [&](BusFx &n) {      // the padded taps, the partials, and both lines +0.0
+        POST_HIP(hipMalloc((void **)&n.taps, padded.size() * sizeof(float)));
+        POST_HIP(hipMalloc((void **)&n.partials, (size_t)2 * n_seg * fx_pstride(c) * sizeof(float)));
+        POST_HIP(hipMemcpyAsync(n.taps, padded.data(), padded.size() * sizeof(float), hipMemcpyHostToDevice, c.stream));
+        return n.zero(1, c.stream);
+    });
 }
 
 // The work area is the room's own: allocated with its lines, so that a refused set leaves the earlier room whole.  The kernel writes a
@@ -322,7 +396,7 @@ hipError_t S2rPostChain::set_room(const S2rPostCtx &c, uint32_t bus, const uint3
     std::memcpy(f.cd, cd, sizeof f.cd); std::memcpy(f.ad, ad, sizeof f.ad); f.spread = spread;
     f.history = 0;
     const size_t floats = room_state_count(cd, ad, spread);
-    const hipError_t e = replace(c, room_insert.stage, room[bus], f, floats, [&](BusRoom &n) {
+    const hipError_t e = replace(c, stage[S2R_BUS_ROOM].buffer, room[bus], f, floats, [&](BusRoom &n) {
         return hipMalloc((void **)&n.work, (size_t)S2R_ROOM_LINES * c.max_frames * sizeof(float));
     });
     if (e == hipSuccess) set_room_params(bus, levels);
@@ -336,50 +410,17 @@ void S2rPostChain::set_room_params(uint32_t bus, const float levels[7]) {
     f.d1 = d1;
 }
 
-hipError_t S2rPostChain::room_state(const S2rPostCtx &c, uint32_t bus, float *get, const float *set) {
-    POST_HIP(room[bus].copy(get, set, 0, room[bus].floats, c.stream));
+hipError_t S2rPostChain::state(const S2rPostCtx &c, int k, uint32_t bus, float *get, const float *set) {
+    const S2rBusLine &f = this->bus(k, bus);
+    POST_HIP(f.copy(get, set, 0, f.floats, c.stream));
     return hipStreamSynchronize(c.stream);
 }
 
-hipError_t S2rPostChain::set_chorus(const S2rPostCtx &c, uint32_t bus, uint32_t voices, float base, float depth, uint32_t phase_inc, uint32_t spread, float dry,
-                                    float wet) {
-    if (voices == 0) { drop(chorus[bus]); return hipSuccess; }
-    BusChorus f;
-    f.voices = voices; f.history = chorus_history(base, depth); f.base = base; f.depth = depth; f.dry = dry; f.wet = wet;
-    f.phase_inc = phase_inc; f.spread = spread;
-    return replace(c, stem[S2R_STEM_CHORUS].stage, chorus[bus], f, 2u * (size_t)f.history, nothing_more);
-}
-
-hipError_t S2rPostChain::set_delay(const S2rPostCtx &c, uint32_t bus, uint32_t delay_frames, float feedback, float cross, float dry, float wet) {
-    if (delay_frames == 0) { drop(delay[bus]); return hipSuccess; }
-    BusDelay f;
-    f.history = delay_frames; f.feedback = feedback; f.cross = cross; f.dry = dry; f.wet = wet;
-    return replace(c, stem[S2R_STEM_DELAY].stage, delay[bus], f, 2u * (size_t)delay_frames, nothing_more);
-}
-
-hipError_t S2rPostChain::set_reverb(const S2rPostCtx &c, uint32_t bus, const float *ir_l, const float *ir_r, uint32_t n_taps, float dry, float wet) {
-    if (n_taps == 0) { drop(fx[bus]); return hipSuccess; }
-    BusFx f;
-    const uint32_t n_seg = (n_taps + S2R_IR_SEGMENT - 1u) / S2R_IR_SEGMENT;
-    f.n_taps = n_taps; f.history = n_taps - 1u; f.dry = dry; f.wet = wet;
-    f.tstride = n_seg * S2R_IR_SEGMENT;
-    f.lstride = (n_taps - 1u + c.max_frames + 3u) & ~3u;
-    std::vector<float> padded(2u * (size_t)f.tstride, 0.0f);
-    std::memcpy(padded.data(), ir_l, (size_t)n_taps * sizeof(float));
-    std::memcpy(padded.data() + f.tstride, ir_r, (size_t)n_taps * sizeof(float));
-    return replace(c, stem[S2R_STEM_REVERB].stage, fx[bus], f, 2u * (size_t)f.lstride, [&](BusFx &n) {      // the padded taps, the partials, and both lines +0.0
-        POST_HIP(hipMalloc((void **)&n.taps, padded.size() * sizeof(float)));
-        POST_HIP(hipMalloc((void **)&n.partials, (size_t)2 * n_seg * fx_pstride(c) * sizeof(float)));
-        POST_HIP(hipMemcpyAsync(n.taps, padded.data(), padded.size() * sizeof(float), hipMemcpyHostToDevice, c.stream));
-        return n.zero(1, c.stream);
-    });
-}
-
-// the history crosses the boundary as frames; the chorus and the delay keep it so, the reverb keeps it planar
+// the history crosses the boundary as frames; every stage keeps it so but the reverb, which keeps it planar
 hipError_t S2rPostChain::history(const S2rPostCtx &c, int k, uint32_t bus, float *get, const float *set) {
     const S2rBusLine &f = this->bus(k, bus);
     const size_t h = f.history;
-    if (k != S2R_STEM_REVERB) {                                  // (the drive and the flanger, behind the stem stages, among them)
+    if (k != S2R_BUS_REVERB) {
         POST_HIP(f.copy(get, set, 0, 2 * h, c.stream));
         return hipStreamSynchronize(c.stream);
     }
@@ -423,75 +464,4 @@ hipError_t S2rPostChain::fetch_limiter_state(const S2rPostCtx &c) {
     lm.host.swap(st);
     lm.host_valid = true;
     return hipSuccess;
-}
-
-// The drive's launch and its setter, at the end of the file and out of line, like the kernel at the end of the link order: the code in
-// front keeps the place it had.
-__attribute__((noinline)) hipError_t S2rPostChain::launch_drive(const S2rPostCtx &c, const S2rPostCall &call) {
-    const S2rPostRouteDrive &r = call.route;
-    S2rDrive a{};
-    for (uint32_t b = 0; b < call.n_buses; b++) {
-        const BusDrive &f = drive[b];
-        if (!f.present()) continue;
-        S2rDriveBus &d = a.bus[b];
-        d.curve = drive_curves + (size_t)b * S2R_DRIVE_CURVE_POINTS; d.line = f.now(); d.next = f.next();
-        d.pre = f.pre; d.dry = f.dry; d.wet = f.wet;
-    }
-    const S2rDriveTaps &taps = drive_taps();
-    std::memcpy(a.h, taps.h, sizeof a.h); std::memcpy(a.g, taps.g, sizeof a.g);
-    a.in = r.drive.in; a.out = r.drive.out; a.n_buses = call.n_buses; a.frames = call.frames;
-    POST_TIMED(c, drive_insert.timer, s2r_launch_bus_drive(a, c.stream));
-    return hipSuccess;
-}
-
-// As set_dyn: the tables come first and once, the bus's row of them is written last, behind everything that can fail for want of
-// memory, so that a refused set leaves the earlier drive whole.  The history starts as +0.0 (replace).
-hipError_t S2rPostChain::set_drive(const S2rPostCtx &c, uint32_t bus, const float *curve, float pre, float dry, float wet, bool keep_state) {
-    if (pre < 0.0f) { drop(drive[bus]); return hipSuccess; }
-    constexpr size_t kRow = S2R_DRIVE_CURVE_POINTS;
-    if (keep_state) {
-        BusDrive &d = drive[bus];
-        if (curve) {
-            POST_HIP(hipMemcpyAsync(drive_curves + bus * kRow, curve, kRow * sizeof(float), hipMemcpyHostToDevice, c.stream));
-            POST_HIP(hipStreamSynchronize(c.stream));
-            d.curve.assign(curve, curve + kRow);
-        }
-        d.pre = pre; d.dry = dry; d.wet = wet;
-        return hipSuccess;
-    }
-    if (!drive_curves) POST_HIP(hipMalloc((void **)&drive_curves, (size_t)S2R_MAX_BUSES * kRow * sizeof(float)));
-    BusDrive f;
-    f.pre = pre; f.dry = dry; f.wet = wet; f.history = S2R_DRIVE_HISTORY;
-    f.curve.assign(curve, curve + kRow);
-    float *const to = drive_curves + bus * kRow;
-    return replace(c, drive_insert.stage, drive[bus], f, 2u * (size_t)S2R_DRIVE_HISTORY, [&](BusDrive &n) {
-        return hipMemcpyAsync(to, n.curve.data(), kRow * sizeof(float), hipMemcpyHostToDevice, c.stream);
-    });
-}
-
-// The flanger's launch and its setter, likewise at the end and out of line.
-__attribute__((noinline)) hipError_t S2rPostChain::launch_flanger(const S2rPostCtx &c, const S2rPostCall &call) {
-    const S2rPostRouteFlanger &r = call.route;
-    S2rFlanger a{};
-    for (uint32_t b = 0; b < call.n_buses; b++) {
-        const BusFlanger &f = flanger[b];
-        if (!f.present()) continue;
-        S2rFlangerBus &d = a.bus[b];
-        d.line = f.now(); d.next = f.next(); d.history = f.history;
-        d.phase = f.phase; d.phase_inc = f.phase_inc; d.spread = f.spread;
-        d.base = f.base; d.depth = f.depth; d.feedback = f.feedback; d.cross = f.cross; d.dry = f.dry; d.wet = f.wet;
-    }
-    a.in = r.flanger.in; a.out = r.flanger.out; a.n_buses = call.n_buses; a.frames = call.frames;
-    POST_TIMED(c, flanger_insert.timer, s2r_launch_bus_flanger(a, c.stream));
-    return hipSuccess;
-}
-
-// the line starts as +0.0 and the phase as 0 (replace); the other copy is written whole by the first call
-hipError_t S2rPostChain::set_flanger(const S2rPostCtx &c, uint32_t bus, float base, float depth, uint32_t phase_inc, uint32_t spread, float feedback, float cross,
-                                     float dry, float wet) {
-    if (base < 0.0f) { drop(flanger[bus]); return hipSuccess; }
-    BusFlanger f;
-    f.history = flanger_history(base, depth); f.base = base; f.depth = depth; f.feedback = feedback; f.cross = cross; f.dry = dry; f.wet = wet;
-    f.phase_inc = phase_inc; f.spread = spread;
-    return replace(c, flanger_insert.stage, flanger[bus], f, 2u * (size_t)f.history, nothing_more);
 }

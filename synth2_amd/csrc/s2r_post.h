@@ -1,8 +1,8 @@
-// s2r_post.h — the chain behind the bus mixdown of s2r_fill_buses and s2r_fill_master: the buses' equalisers and their
-// dynamics (4.22), two inserts at the head of the stem stages (s2r_post_route.h) — the buses' choruses (4.20), their feedback delays
-// (4.19), their convolution reverbs (4.16) —, the buses' rooms (4.23), an insert behind them, the master section (4.17) and the master limiter (4.18), in that order; the
-// buses' drives (4.24) are a fourth insert, behind the dynamics, and their flangers (4.25) a fifth, behind the drives.  The chain owns what the ten stages own
-// and knows nothing of the handle: its functions take a S2rPostCtx and return the HIP error.  Per call: prepare, launch, — the caller's synchronise — commit, read_timers.
+// s2r_post.h — the chain behind the bus mixdown of s2r_fill_buses and s2r_fill_master: the eight bus stages in the order of
+// S2rBusStage (s2r_post_route.h) — the buses' equalisers, their dynamics (4.22), drives (4.24), flangers (4.25),
+// choruses (4.20), feedback delays (4.19), convolution reverbs (4.16) and rooms (4.23) —, then the master section (4.17) and the master
+// limiter (4.18).  The chain owns what the ten stages own and knows nothing of the handle: its functions take a S2rPostCtx and return
+// the HIP error.  Per call: prepare, launch, — the caller's synchronise — commit, read_timers.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <vector>
@@ -45,11 +45,41 @@ struct S2rBusLine {
 };
 
 struct S2rPostChain {
-    // what a stem stage keeps beside its buses' effects
+    // what a bus stage keeps beside its buses' effects
     struct Stem {
-        float *stage = nullptr;                  // [S2R_MAX_BUSES][2 * max_frames]: the stage's input in a call that runs it, allocated when its effect is first set
-        S2rPostTimer timer;                      // around the stage's kernels of the last bus or master fill: 0 when it ran none (tools/{chorus,delay,reverb}_time.py)
-    } stem[S2R_STEM_STAGES];
+        float *buffer = nullptr;                 // [S2R_MAX_BUSES][2 * max_frames]: the stage's input in a call that runs it, allocated when its effect is first set
+        S2rPostTimer timer;                      // around the stage's kernels of the last bus or master fill: 0 when it ran none (tools/*_time.py)
+    } stage[S2R_BUS_STAGES];
+    // The effects, in chain order.
+    // The EQs (s2r_set_bus_eq): lines of [n_bands][s1_L, s1_R, s2_L, s2_R], 4 * n_bands floats (history = 2 * n_bands "frames" of two)
+    struct BusEq : S2rBusLine {
+        uint32_t n_bands = 0;
+        float c[S2R_EQ_MAX_BANDS][5] = {};       // (b0, b1, b2, a1, a2) per band
+    } eq[S2R_MAX_BUSES];
+    // The dynamics (s2r_set_bus_dynamics): lines of one float, the gain y; beside them the curves' tables on the device and a pinned row
+    // for the calls' meters
+    struct BusDyn : S2rBusLine {
+        uint32_t key = 0;
+        float a_att = 0.0f, a_rel = 0.0f;
+        float min_gain = 1.0f;                   // the meter of the last successful call that ran these dynamics
+        std::vector<float> curve;                // the host's copy of the table: S2R_DYN_CURVE_POINTS entries
+    } dyn[S2R_MAX_BUSES];
+    float *dyn_curves = nullptr;                 // [S2R_MAX_BUSES][S2R_DYN_CURVE_POINTS] in device memory, allocated when dynamics are first set
+    float *dyn_meter = nullptr, *dyn_meter_dev = nullptr;        // pinned and device-mapped: [S2R_MAX_BUSES]
+    // The drives (s2r_set_bus_drive): lines of [S2R_DRIVE_HISTORY][2], the bus's last input frames, oldest first, L then R; beside them
+    // the tables on the device
+    struct BusDrive : S2rBusLine {
+        float pre = 0.0f, dry = 0.0f, wet = 0.0f;
+        std::vector<float> curve;                // the host's copy of the table: S2R_DRIVE_CURVE_POINTS entries
+    } drive[S2R_MAX_BUSES];
+    float *drive_curves = nullptr;               // [S2R_MAX_BUSES][S2R_DRIVE_CURVE_POINTS] in device memory, allocated when a drive is first set
+    // The flangers (s2r_set_bus_flanger): lines of [H][2], the last frames of the stage's line signal w, oldest first, L then R, H =
+    // history = floor(fl(base + depth)) + 1
+    struct BusFlanger : S2rBusLine {
+        float base = 0.0f, depth = 0.0f, feedback = 0.0f, cross = 0.0f, dry = 0.0f, wet = 0.0f;
+        uint32_t phase_inc = 0, spread = 0;
+        uint32_t phase = 0;                      // the LFO's phase at frame 0 of the next call: moved on by the commit
+    } flanger[S2R_MAX_BUSES];
     // The choruses (s2r_set_bus_chorus): lines of [H][2], oldest frame first, L then R, H = history = floor(fl(base + depth)) + 1
     struct BusChorus : S2rBusLine {
         uint32_t voices = 0;                     // V
@@ -70,40 +100,24 @@ struct S2rPostChain {
         uint32_t tstride = 0, lstride = 0;
         void free() { for (float *p : {taps, partials}) if (p) (void)hipFree(p); S2rBusLine::free(); }
     } fx[S2R_MAX_BUSES];
-    // The EQs (s2r_set_bus_eq): lines of [n_bands][s1_L, s1_R, s2_L, s2_R], 4 * n_bands floats (history = 2 * n_bands "frames" of two).
-    // Not a stem stage: an insert in front of them (s2r_post_route_eq), with a staging buffer and a timer of its own
-    struct BusEq : S2rBusLine {
-        uint32_t n_bands = 0;
-        float c[S2R_EQ_MAX_BANDS][5] = {};       // (b0, b1, b2, a1, a2) per band
-    } eq[S2R_MAX_BUSES];
-    Stem eq_insert;                              // (its timer: tools/eq_time.py)
-    // The dynamics (s2r_set_bus_dynamics): lines of one float, the gain y.  The second insert, behind the EQ (s2r_post_route_dyn), with a
-    // staging buffer and a timer of its own, the curves' tables on the device and a pinned row for the calls' meters
-    struct BusDyn : S2rBusLine {
-        uint32_t key = 0;
-        float a_att = 0.0f, a_rel = 0.0f;
-        float min_gain = 1.0f;                   // the meter of the last successful call that ran these dynamics
-        std::vector<float> curve;                // the host's copy of the table: S2R_DYN_CURVE_POINTS entries
-    } dyn[S2R_MAX_BUSES];
-    Stem dyn_insert;                             // (its timer: tools/dyn_time.py)
-    float *dyn_curves = nullptr;                 // [S2R_MAX_BUSES][S2R_DYN_CURVE_POINTS] in device memory, allocated when dynamics are first set
-    float *dyn_meter = nullptr, *dyn_meter_dev = nullptr;        // pinned and device-mapped: [S2R_MAX_BUSES]
-    // the bus's dynamics run in a call of n_buses buses: both the bus and its key are among them
-    bool dyn_runs(uint32_t b, uint32_t n_buses) const { return b < n_buses && dyn[b].present() && dyn[b].key < n_buses; }
     // The rooms (s2r_set_bus_room): lines in the checkpoint's layout (s2r.h): per channel each comb's line and its f, then each allpass's
-    // line.  The third insert, behind the last stem stage (s2r_post_route_room), with a staging buffer and a timer of its own; a room also
-    // owns the work area its kernel keeps a call's frames of the 24 lines in
+    // line; a room also owns the work area its kernel keeps a call's frames of the 24 lines in
     struct BusRoom : S2rBusLine {
         uint32_t cd[S2R_ROOM_COMBS] = {}, ad[S2R_ROOM_ALLPASSES] = {}, spread = 0;
         float feedback = 0.0f, damp = 0.0f, d1 = 0.0f, g = 0.0f, gain = 0.0f, dry = 0.0f, wet = 0.0f, cross = 0.0f;
         float *work = nullptr;                   // [S2R_ROOM_LINES][max_frames]
         void free() { if (work) (void)hipFree(work); work = nullptr; S2rBusLine::free(); }
     } room[S2R_MAX_BUSES];
-    Stem room_insert;                            // (its timer: tools/room_time.py)
-    // stage k's effect on a bus, as far as the stages are alike; behind the stem stages, at S2R_STEM_STAGES, the drive, and behind it
-    // the flanger, whose histories have their form (the loops over the stem stages do not reach them)
-    S2rBusLine &bus(int k, uint32_t b) { S2rBusLine *const of[S2R_STEM_STAGES + 2] = {&chorus[b], &delay[b], &fx[b], &drive[b], &flanger[b]}; return *of[k]; }
-    const S2rBusLine &bus(int k, uint32_t b) const { return const_cast<S2rPostChain *>(this)->bus(k, b); }
+    // stage k's effect on a bus, as far as the stages are alike
+    template <class Line, class Chain> static Line &bus_of(Chain &c, int k, uint32_t b) {
+        Line *const of[S2R_BUS_STAGES] = {&c.eq[b], &c.dyn[b], &c.drive[b], &c.flanger[b], &c.chorus[b], &c.delay[b], &c.fx[b], &c.room[b]};
+        return *of[k];
+    }
+    S2rBusLine &bus(int k, uint32_t b) { return bus_of<S2rBusLine>(*this, k, b); }
+    const S2rBusLine &bus(int k, uint32_t b) const { return bus_of<const S2rBusLine>(*this, k, b); }
+    // the bus's effect of stage k runs in a call of n_buses buses: the bus is among them (an effect on a bus past the call's is idle in
+    // it), and for the dynamics their key bus too
+    bool runs(int k, uint32_t b, uint32_t n_buses) const { return b < n_buses && bus(k, b).present() && (k != S2R_BUS_DYN || dyn[b].key < n_buses); }
     // The master section.  Nothing is allocated before the first master fill.
     struct Master {
         float ret[S2R_MAX_BUSES], ret_app[S2R_MAX_BUSES];        // what the caller last set — the target — and what the last master fill left — the applied
@@ -138,52 +152,39 @@ struct S2rPostChain {
     // the synchronise that succeeded, and only then, histories, applied values and state move on and the meters fold
     hipError_t prepare(const S2rPostCtx &c, uint32_t n_buses, uint32_t frames, bool master_fill, bool stems, S2rPostCall &call);
     hipError_t launch(const S2rPostCtx &c, const S2rPostCall &call);
-    hipError_t launch_drive(const S2rPostCtx &c, const S2rPostCall &call);      // the drive's part of launch, out of line
-    hipError_t launch_flanger(const S2rPostCtx &c, const S2rPostCall &call);    // the flanger's, likewise
+    // a bus stage's part of launch: its kernels' arguments from the buses' effects and route.stage[k], and the launch
+    hipError_t launch_eq(const S2rPostCtx &c, const S2rPostCall &call) const;
+    hipError_t launch_dyn(const S2rPostCtx &c, const S2rPostCall &call) const;
+    hipError_t launch_drive(const S2rPostCtx &c, const S2rPostCall &call) const;
+    hipError_t launch_flanger(const S2rPostCtx &c, const S2rPostCall &call) const;
+    hipError_t launch_chorus(const S2rPostCtx &c, const S2rPostCall &call) const;
+    hipError_t launch_delay(const S2rPostCtx &c, const S2rPostCall &call) const;
+    hipError_t launch_reverb(const S2rPostCtx &c, const S2rPostCall &call) const;
+    hipError_t launch_room(const S2rPostCtx &c, const S2rPostCall &call) const;
     void commit(const S2rPostCall &call);
     hipError_t read_timers(const S2rPostCall &call);
     void release();
-    // what the entry points of s2r_host.cpp do behind their checks, on a quiet stream
+    // what the entry points of s2r_host.cpp do behind their checks, on a quiet stream; in chain order
     hipError_t set_eq(const S2rPostCtx &c, uint32_t bus, uint32_t n_bands, const float *coeffs);
-    hipError_t eq_state(const S2rPostCtx &c, uint32_t bus, float *get, const float *set);      // the 4 * n_bands floats, out or in
     // curve null: removes the bus's dynamics; keep_state: the parameters alone, on a bus that has them
     hipError_t set_dyn(const S2rPostCtx &c, uint32_t bus, uint32_t key, const float *curve, float a_att, float a_rel, bool keep_state);
-    hipError_t dyn_state(const S2rPostCtx &c, uint32_t bus, float *get, const float *set);     // the one float, out or in
-    // cd null: removes the bus's room; the levels alone on a bus that has one: set_room_params
-    hipError_t set_room(const S2rPostCtx &c, uint32_t bus, const uint32_t *cd, const uint32_t *ad, uint32_t spread, const float levels[7]);
-    void set_room_params(uint32_t bus, const float levels[7]);
-    hipError_t room_state(const S2rPostCtx &c, uint32_t bus, float *get, const float *set);    // the whole state, out or in
-    // pre < 0: removes the bus's drive; keep_state: the levels, and the table unless curve is null, on a bus that has one.  Its
-    // history goes through history() at k = S2R_STEM_STAGES
+    // pre < 0: removes the bus's drive; keep_state: the levels, and the table unless curve is null, on a bus that has one
     hipError_t set_drive(const S2rPostCtx &c, uint32_t bus, const float *curve, float pre, float dry, float wet, bool keep_state);
+    // base < 0: removes the bus's flanger
+    hipError_t set_flanger(const S2rPostCtx &c, uint32_t bus, float base, float depth, uint32_t phase_inc, uint32_t spread, float feedback, float cross, float dry,
+                           float wet);
     hipError_t set_chorus(const S2rPostCtx &c, uint32_t bus, uint32_t voices, float base, float depth, uint32_t phase_inc, uint32_t spread, float dry, float wet);
     hipError_t set_delay(const S2rPostCtx &c, uint32_t bus, uint32_t delay_frames, float feedback, float cross, float dry, float wet);
     hipError_t set_reverb(const S2rPostCtx &c, uint32_t bus, const float *ir_l, const float *ir_r, uint32_t n_taps, float dry, float wet);
+    // cd null: removes the bus's room; the levels alone on a bus that has one: set_room_params
+    hipError_t set_room(const S2rPostCtx &c, uint32_t bus, const uint32_t *cd, const uint32_t *ad, uint32_t spread, const float levels[7]);
+    void set_room_params(uint32_t bus, const float levels[7]);
+    // the whole state of stage k's effect on a bus — all the floats of its line —, out or in (the EQ's, the dynamics', the room's)
+    hipError_t state(const S2rPostCtx &c, int k, uint32_t bus, float *get, const float *set);
     // the history of stage k's effect on a bus, out or in: `history` frames, oldest first, L then R
     hipError_t history(const S2rPostCtx &c, int k, uint32_t bus, float *get, const float *set);
     void snap_master() { for (uint32_t b = 0; b < S2R_MAX_BUSES; b++) master.ret_app[b] = master.ret[b]; master.fader_app = master.fader; }
     void set_limiter(float ceiling, uint32_t lookahead, uint32_t hold);      // (0, 0, 0): off
     void set_limiter_state(const float *xh, const float *gh);
     hipError_t fetch_limiter_state(const S2rPostCtx &c);            // the device's copy into `host`, kept until the next fill
-    // The drives (s2r_set_bus_drive): lines of [S2R_DRIVE_HISTORY][2], the bus's last input frames, oldest first, L then R.  The fourth
-    // insert, behind the dynamics (s2r_post_route_drive), with a staging buffer and a timer of its own and the tables on the device.
-    // (Behind everything else, so that the members in front keep their places in the handle.)
-    struct BusDrive : S2rBusLine {
-        float pre = 0.0f, dry = 0.0f, wet = 0.0f;
-        std::vector<float> curve;                // the host's copy of the table: S2R_DRIVE_CURVE_POINTS entries
-    } drive[S2R_MAX_BUSES];
-    Stem drive_insert;                           // (its timer: tools/drive_time.py)
-    float *drive_curves = nullptr;               // [S2R_MAX_BUSES][S2R_DRIVE_CURVE_POINTS] in device memory, allocated when a drive is first set
-    // The flangers (s2r_set_bus_flanger): lines of [H][2], the last frames of the stage's line signal w, oldest first, L then R, H =
-    // history = floor(fl(base + depth)) + 1.  The fifth insert, behind the drive (s2r_post_route_flanger), with a staging buffer and a
-    // timer of its own.  (Again behind everything else.)  Its history goes through history() at k = S2R_STEM_STAGES + 1
-    struct BusFlanger : S2rBusLine {
-        float base = 0.0f, depth = 0.0f, feedback = 0.0f, cross = 0.0f, dry = 0.0f, wet = 0.0f;
-        uint32_t phase_inc = 0, spread = 0;
-        uint32_t phase = 0;                      // the LFO's phase at frame 0 of the next call: moved on by the commit
-    } flanger[S2R_MAX_BUSES];
-    Stem flanger_insert;                         // (its timer: tools/flanger_time.py)
-    // base < 0: removes the bus's flanger
-    hipError_t set_flanger(const S2rPostCtx &c, uint32_t bus, float base, float depth, uint32_t phase_inc, uint32_t spread, float feedback, float cross, float dry,
-                           float wet);
 };

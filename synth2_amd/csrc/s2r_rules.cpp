@@ -486,8 +486,7 @@ int s2r_limiter_reference(const float *x, uint32_t frames, float ceiling, uint32
 
 }  // extern "C"
 
-// ---- per-bus flanger: one tap at a triangle-modulated fractional delay into the stage's own line signal, fed back.
-// At the end of the file, like the kernel at the end of the link order ----
+// ---- per-bus flanger: one tap at a triangle-modulated fractional delay into the stage's own line signal, fed back ----
 extern "C" {
 
 uint32_t s2r_flanger_history_frames(float base, float depth) { return flanger_delay_in_range(base, depth) ? flanger_history(base, depth) : 0u; }

@@ -1,7 +1,7 @@
 """ASan + UBSan over the bus drive's host side, which needs neither a handle nor HIP: s2r_drive_reference,
-s2r_drive_taps and s2r_drive_curve (csrc/s2r_rules.cpp) beside tests/native/san_drive.cpp, and the drive's insert into the post-mix
-chain's route (s2r_post_route_drive, csrc/s2r_post_route.h) with tests/native/post_route_drive.cpp.  Each is compiled by plain g++ and
-run as a child process, with no preload of any kind — as tests/test_room_native.py does."""
+s2r_drive_taps and s2r_drive_curve (csrc/s2r_rules.cpp) beside tests/native/san_drive.cpp, compiled by plain g++ and run as a child
+process, with no preload of any kind — as tests/test_room_native.py does.  (The drive's place in the post-mix chain's route is checked
+with every other stage's by tests/native/post_route.cpp, tests/test_rules_native.py.)"""
 import os
 import shutil
 import subprocess
@@ -25,15 +25,3 @@ def test_drive_reference_under_asan_ubsan(tmp_path):
     out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     assert "drive ok" in out.stdout
-
-
-@pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
-def test_post_route_with_the_drive_under_asan_ubsan(tmp_path):
-    """the 24 routes x EQ off / on x dynamics off / on x room off / on x drive off / on, in bus and master fills: every buffer is
-    written before it is read, the combine writes first, the last writer hits the call's destination, and no kernel reads a pinned
-    output"""
-    exe = str(tmp_path / "post_route_drive")
-    subprocess.check_call(SAN + ["-I", os.path.join(ROOT, "synth2_amd", "csrc"), os.path.join(ROOT, "tests", "native", "post_route_drive.cpp"), "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-3000:]
-    assert "route drive ok" in out.stdout

@@ -1,7 +1,7 @@
 """ASan + UBSan over the bus dynamics' host side, which needs neither a handle nor HIP: s2r_dynamics_reference,
-s2r_dynamics_curve and s2r_dynamics_coef (csrc/s2r_rules.cpp) beside tests/native/san_dyn.cpp, and the dynamics' insert into the
-post-mix chain's route (s2r_post_route_dyn, csrc/s2r_post_route.h) with tests/native/post_route_dyn.cpp.  Each is compiled by plain g++
-and run as a child process, with no preload of any kind — as tests/test_eq_native.py does."""
+s2r_dynamics_curve and s2r_dynamics_coef (csrc/s2r_rules.cpp) beside tests/native/san_dyn.cpp, compiled by plain g++ and run as a
+child process, with no preload of any kind — as tests/test_eq_native.py does.  (The dynamics' place in the post-mix chain's route is
+checked with every other stage's by tests/native/post_route.cpp, tests/test_rules_native.py.)"""
 import os
 import shutil
 import subprocess
@@ -24,14 +24,3 @@ def test_dynamics_reference_under_asan_ubsan(tmp_path):
     out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     assert "dyn ok" in out.stdout
-
-
-@pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
-def test_post_route_with_the_dynamics_under_asan_ubsan(tmp_path):
-    """the 24 routes x EQ off / on x dynamics off / on, in bus and master fills: every buffer a stage reads was written by the stage in
-    front of it, the combine writes first, the last writer hits the call's destination, and no kernel reads a pinned output"""
-    exe = str(tmp_path / "post_route_dyn")
-    subprocess.check_call(SAN + ["-I", os.path.join(ROOT, "synth2_amd", "csrc"), os.path.join(ROOT, "tests", "native", "post_route_dyn.cpp"), "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-3000:]
-    assert "route dyn ok" in out.stdout

@@ -1,7 +1,7 @@
 """ASan + UBSan over the bus EQ's host side, which needs neither a handle nor HIP: s2r_eq_reference and s2r_eq_design
-(csrc/s2r_rules.cpp) beside tests/native/san_eq.cpp, and the EQ's insert into the post-mix chain's route (s2r_post_route_eq,
-csrc/s2r_post_route.h) with tests/native/post_route_eq.cpp.  Each is compiled by plain g++ and run as a child process, with no preload
-of any kind — as tests/test_chorus_native.py and tests/test_rules_native.py do."""
+(csrc/s2r_rules.cpp) beside tests/native/san_eq.cpp, compiled by plain g++ and run as a child process, with no preload of any kind —
+as tests/test_chorus_native.py and tests/test_rules_native.py do.  (The EQ's place in the post-mix chain's route is checked with
+every other stage's by tests/native/post_route.cpp, tests/test_rules_native.py.)"""
 import os
 import shutil
 import subprocess
@@ -24,14 +24,3 @@ def test_eq_reference_under_asan_ubsan(tmp_path):
     out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     assert "eq ok" in out.stdout
-
-
-@pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
-def test_post_route_with_the_eq_under_asan_ubsan(tmp_path):
-    """the 24 routes without and with the EQ: without it s2r_post_route_eq changes nothing; with it eq.in is the EQ's buffer,
-    combine_out equals eq.in, eq.out is what combine_out was, and every other pointer is unchanged"""
-    exe = str(tmp_path / "post_route_eq")
-    subprocess.check_call(SAN + ["-I", os.path.join(ROOT, "synth2_amd", "csrc"), os.path.join(ROOT, "tests", "native", "post_route_eq.cpp"), "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-3000:]
-    assert "route eq ok" in out.stdout

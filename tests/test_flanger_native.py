@@ -1,7 +1,7 @@
 """ASan + UBSan over the bus flanger's host side, which needs neither a handle nor HIP: s2r_flanger_reference and
-s2r_flanger_history_frames (csrc/s2r_rules.cpp) beside tests/native/san_flanger.cpp, and the flanger's insert into the post-mix chain's
-route (s2r_post_route_flanger, csrc/s2r_post_route.h) with tests/native/post_route_flanger.cpp.  Each is compiled by plain g++ and run
-as a child process, with no preload of any kind — as tests/test_drive_native.py does."""
+s2r_flanger_history_frames (csrc/s2r_rules.cpp) beside tests/native/san_flanger.cpp, compiled by plain g++ and run as a child process,
+with no preload of any kind — as tests/test_drive_native.py does.  (The flanger's place in the post-mix chain's route is checked with
+every other stage's by tests/native/post_route.cpp, tests/test_rules_native.py.)"""
 import os
 import shutil
 import subprocess
@@ -24,15 +24,3 @@ def test_flanger_reference_under_asan_ubsan(tmp_path):
     out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     assert "flanger ok" in out.stdout
-
-
-@pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
-def test_post_route_with_the_flanger_under_asan_ubsan(tmp_path):
-    """the 24 routes x EQ, dynamics, room, drive and flanger off / on, in bus and master fills: every buffer is written before it is
-    read, the combine writes first, the last writer hits the call's destination, no kernel reads a pinned output, and a call without a
-    flanger is pointer for pointer the drive's route"""
-    exe = str(tmp_path / "post_route_flanger")
-    subprocess.check_call(SAN + ["-I", os.path.join(ROOT, "synth2_amd", "csrc"), os.path.join(ROOT, "tests", "native", "post_route_flanger.cpp"), "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-3000:]
-    assert "route flanger ok" in out.stdout

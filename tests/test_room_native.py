@@ -1,7 +1,7 @@
 """ASan + UBSan over the bus room's host side, which needs neither a handle nor HIP: s2r_room_reference,
-s2r_room_state_floats and s2r_room_design (csrc/s2r_rules.cpp) beside tests/native/san_room.cpp, and the room's insert into the
-post-mix chain's route (s2r_post_route_room, csrc/s2r_post_route.h) with tests/native/post_route_room.cpp.  Each is compiled by plain
-g++ and run as a child process, with no preload of any kind — as tests/test_dyn_native.py does."""
+s2r_room_state_floats and s2r_room_design (csrc/s2r_rules.cpp) beside tests/native/san_room.cpp, compiled by plain g++ and run as a
+child process, with no preload of any kind — as tests/test_dyn_native.py does.  (The room's place in the post-mix chain's route is
+checked with every other stage's by tests/native/post_route.cpp, tests/test_rules_native.py.)"""
 import os
 import shutil
 import subprocess
@@ -24,15 +24,3 @@ def test_room_reference_under_asan_ubsan(tmp_path):
     out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     assert "room ok" in out.stdout
-
-
-@pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
-def test_post_route_with_the_room_under_asan_ubsan(tmp_path):
-    """the 24 routes x EQ off / on x dynamics off / on x room off / on, in bus and master fills: every buffer a stage reads was written
-    by the stage in front of it, the combine writes first, the last writer hits the call's destination, and no kernel reads a pinned
-    output"""
-    exe = str(tmp_path / "post_route_room")
-    subprocess.check_call(SAN + ["-I", os.path.join(ROOT, "synth2_amd", "csrc"), os.path.join(ROOT, "tests", "native", "post_route_room.cpp"), "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-3000:]
-    assert "route room ok" in out.stdout

@@ -30,8 +30,11 @@ def test_rule_functions_under_asan_ubsan(tmp_path):
 @pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
 def test_post_route_under_asan_ubsan(tmp_path):
     """who reads and writes what behind the bus mixdown (s2r_post_route, csrc/s2r_post_route.h, a header without HIP): a panned call,
-    bus fills x the 8 subsets of running stem stages, master fills x 8 subsets x limiter on or off x stems wanted or not, each route
-    against the 24 routes written out by hand (the table of tests/native/post_route.cpp) and against the rule stated without it"""
+    bus fills x the 256 subsets of running bus stages, master fills x 256 subsets x limiter on or off x stems wanted or not, each route
+    against the 24 routes written out by hand (the table of tests/native/post_route.cpp) where it names the call, against the rule
+    walked in launch order without it — every buffer is written before it is read, the combine writes first, the last writer hits
+    the call's destination, no kernel reads a pinned output — and against the route of the same call with one more stage on, which
+    differs by exactly the pointer that stage takes over"""
     exe = str(tmp_path / "post_route")
     subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
                            "-I", os.path.join(ROOT, "synth2_amd", "csrc"), os.path.join(ROOT, "tests", "native", "post_route.cpp"), "-o", exe])
