@@ -1,4 +1,4 @@
-"""Seeded walks over the post-mix chain (DESIGN.md 4.16 to 4.24) and the chain's host model, with no GPU in it: tests/test_gpu_post_fuzz.py
+"""Seeded walks over the post-mix chain (DESIGN.md 4.16 to 4.25) and the chain's host model, with no GPU in it: tests/test_gpu_post_fuzz.py
 plays a walk on a pair of twin handles, tests/test_post_walk_host.py holds the walks themselves to coverage conditions and runs them
 through the model alone.
 
@@ -12,12 +12,14 @@ import synth2_amd as s2
 from synth2_amd import synth as s2s
 from test_delay_host import FEEDS
 from test_drive_host import KINDS, random_table
+from test_flanger_host import INCS as FLANGER_INCS, MIXES as FLANGER_FEEDS_HOST
 from test_gpu_buses import ubits
 from test_gpu_chorus import INCS, SHAPES, VOICES, ChorusModel
 from test_gpu_delay import DELAYS, DelayModel
 from test_gpu_drive import DriveModel, oversampled
 from test_gpu_dyn import COEFS, RATIOS, DynModel
 from test_gpu_eq import EqModel, _coeffs
+from test_gpu_flanger import SHAPE as FLANGER_SHAPE, FlangerModel
 from test_gpu_limiter import Lim
 from test_gpu_master import Master
 from test_gpu_reverb import MIXES, Model, _ir
@@ -28,17 +30,19 @@ from test_room_host import FLAT, SMALL
 
 F = np.float32
 # the default sweep of tests/test_gpu_post_fuzz.py and tests/test_post_walk_host.py: S2R_POST_FUZZ_BASE moves it, S2R_POST_FUZZ_SEEDS widens it
-DEFAULT_BASE, DEFAULT_SEEDS = 5000, 24
-STAGES = ("eq", "dyn", "drive", "chorus", "delay", "reverb", "room")        # chain order
-INSERTS = ("eq", "dyn", "drive", "room")
+DEFAULT_BASE, DEFAULT_SEEDS = 5000, 32
+STAGES = ("eq", "dyn", "drive", "flanger", "chorus", "delay", "reverb", "room")        # chain order
+INSERTS = ("eq", "dyn", "drive", "flanger", "room")
 STEMS = ("chorus", "delay", "reverb")
 FILLS = ("bus", "master_stems", "master", "panned")
 KINDS_OF_ACTION = ("set", "clear", "params", "limiter_set", "limiter_clear", "limiter_ceiling", "limiter_reset", "return", "fader", "snap",
                    "fill", "roundtrip", "handover")
 MAX_FRAMES = (1024, 1000, 1031, 300, 64, 2048)
-# around the kernels' tiles (room 32, EQ 64, drive 240, dynamics 256, the 256-frame blocks of the meters and the limiter) and the drive's
-# latency of 16 and history of 32 frames; a walk adds max_frames - 1 and max_frames and cuts the list to max_frames
-FRAMES = (1, 2, 15, 16, 17, 31, 32, 33, 63, 64, 65, 239, 240, 241, 255, 256, 257, 300, 485, 513)
+# around the kernels' tiles (room 32, EQ 64, drive 240, dynamics 256, the 256-frame blocks of the meters and the limiter), the drive's
+# latency of 16 and history of 32 frames, and the flanger's tile of 32 and its group of 256 frames, eight tiles whose input is loaded
+# ahead: a group that ends the call and a group and one whole tile, each a frame less and a frame more too; a walk adds
+# max_frames - 1 and max_frames and cuts the list to max_frames
+FRAMES = (1, 2, 15, 16, 17, 31, 32, 33, 63, 64, 65, 239, 240, 241, 255, 256, 257, 287, 288, 289, 300, 485, 513)
 # The peak of the twin's buses: the largest magnitude of sample_buses(1024, 48000, 8) on test_gpu_reverb._handles(32) after _events
 # fill 0, measured on an MI355X at commit bdd609a (the per-bus drive).  The host file scales its synthetic input to it and the
 # dynamics' thresholds are set below it.
@@ -52,6 +56,12 @@ DELAY_FEEDS = tuple(fc for fc in FEEDS if abs(fc[0]) + abs(fc[1]) <= 0.9) + ((-0
 DELAY_MIX = ((0.5, 1.0), (1.0, 0.5), (0.0, 1.0))
 CHORUS_MIX = ((0.5, 0.25), (0.75, 0.5), (1.0, 1.0))
 CHORUS_SPREAD = (0, 5, 0x40000000)
+FLANGER_H = tuple(sorted(FLANGER_SHAPE))                         # every one: 33 with no depth (every tap exactly one tile old) to 4096, the ring
+FLANGER_SPREAD = (0, 7, 0x40000000, 0x80000001)                  # the spreads tests/test_flanger_host.py runs its rule at
+# as DELAY_FEEDS: |feedback| + |cross| stays at 0.9 or below (the per-stage file keeps its pairs at 1 over a dozen calls; a walk's line
+# must not grow without bound): the host file's pairs that keep to it, (0, 0) among them, and three more, negative and both non-zero
+FLANGER_FEEDS = tuple(fc for fc in FLANGER_FEEDS_HOST if abs(fc[0]) + abs(fc[1]) <= 0.9) + ((-0.5, 0.25), (0.3, -0.6), (0.0, -0.9))
+FLANGER_MIX = ((0.0, 1.0), (0.5, 0.75), (1.0, 1.0), (0.25, 1.0))  # never (1, 0), an identity
 DRIVE_MIX = ((0.0, 1.0), (0.5, 0.75), (0.25, 1.0))
 DRIVE_PRE = (1.0, 4.0, 0.5)
 DYN_BELOW_PEAK_DB = (6.0, 14.0, 24.0)                            # a threshold this far below TWIN_PEAK
@@ -76,6 +86,11 @@ def _shape(rng, stage):
         return dict(curve=KINDS[k][0] if k < len(KINDS) else "random", seed=int(rng.randint(1, 20)), pre=float(_pick(rng, DRIVE_PRE)), dry=dry, wet=wet)
     if stage == "room":
         return dict(delays=str(_pick(rng, sorted(ROOMS))), levels=str(_pick(rng, sorted(LEVELS))))
+    if stage == "flanger":
+        fb, cross = _pick(rng, FLANGER_FEEDS)
+        dry, wet = _pick(rng, FLANGER_MIX)
+        return dict(H=int(_pick(rng, FLANGER_H)), inc=int(_pick(rng, FLANGER_INCS)), spread=int(_pick(rng, FLANGER_SPREAD)), feedback=float(fb), cross=float(cross),
+                    dry=dry, wet=wet)
     if stage == "chorus":
         dry, wet = _pick(rng, CHORUS_MIX)
         return dict(H=int(_pick(rng, CHORUS_H)), voices=int(_pick(rng, VOICES)), inc=int(_pick(rng, INCS)), spread=int(_pick(rng, CHORUS_SPREAD)), dry=dry, wet=wet)
@@ -99,6 +114,8 @@ def _params(rng, stage, shape):
         return "set_bus_drive_params", (new if rng.randint(2) else dict(new, curve=shape["curve"], seed=shape["seed"], table=False))
     if stage == "room":
         return "set_bus_room_params", dict(new, delays=shape["delays"])
+    if stage == "flanger":                                       # (base and depth stay, and with them the line's length)
+        return "set_bus_flanger_params", dict(new, H=shape["H"])
     if stage == "chorus":
         if rng.randint(2):
             return "set_bus_chorus_rate", dict(shape, inc=new["inc"], spread=new["spread"])
@@ -112,7 +129,9 @@ def walk(seed):
     """-> (setup, steps): setup = {"max_frames", "timing"}, steps a list of actions, each a dict with a "kind" of KINDS_OF_ACTION.  20 to
     30 steps, at least 12 of them fills.  The generator keeps book of what is present, so that a clear or a kept-state entry always
     meets an effect, the limiter's ceiling always has a master fill behind it to be taken from, and a handover happens once at most.
-    The last step is a master fill, so that a walk ends with every return and the master fader arrived (Master.check_committed)."""
+    The last step is a master fill, so that a walk ends with every return and the master fader arrived (Master.check_committed).
+    The opening takes the inserts from the seed's low five bits and the stem stages from its low three, and DEFAULT_SEEDS is 32: the
+    default sweep opens on every subset of the five inserts (tests/test_post_walk_host.py asserts that all 32 are active in some fill)."""
     rng = np.random.RandomState(seed)
     max_frames = int(_pick(rng, MAX_FRAMES))
     setup = dict(max_frames=max_frames, timing=bool(rng.rand() < 0.35))
@@ -123,9 +142,9 @@ def walk(seed):
     limiter = None
     handed = False
     steps = []
-    # the opening: the subset of the inserts that the seed's last four bits name and the subset of the stem stages that its last three
-    # name, on the low buses, then a bus fill and a master fill wide enough to run them — so that any 16 seeds in a row run every subset
-    # of the inserts, and any 8 every subset of the stem stages in both kinds of fill
+    # the opening: the subset of the inserts that the seed's last five bits name and the subset of the stem stages that its last three
+    # name, on the low buses, then a bus fill and a master fill wide enough to run them — so that any 32 seeds in a row run every subset
+    # of the five inserts (DEFAULT_SEEDS is 32 for that), and any 8 every subset of the stem stages in both kinds of fill
     opening = [st for j, st in enumerate(INSERTS) if seed >> j & 1] + [st for j, st in enumerate(STEMS) if seed >> j & 1]
     widest = 0
     for st in sorted(opening, key=STAGES.index):
@@ -218,21 +237,23 @@ class _Fan:
 
 
 class Chain:
-    """The chain on the host: per bus EqModel, DynModel, DriveModel, ChorusModel, DelayModel, the reverb's Model, RoomModel; behind them
-    Master and Lim.  `handles`: who else every action is performed on — (a,) on the device, () on the host."""
+    """The chain on the host: per bus EqModel, DynModel, DriveModel, FlangerModel, ChorusModel, DelayModel, the reverb's Model, RoomModel;
+    behind them Master and Lim.  `handles`: who else every action is performed on — (a,) on the device, () on the host."""
 
     def __init__(self, handles=()):
         self.handles = tuple(handles)
-        self.m = dict(eq=EqModel(), dyn=DynModel(), drive=DriveModel(), chorus=ChorusModel(), delay=DelayModel(), reverb=Model(), room=RoomModel())
+        self.m = dict(eq=EqModel(), dyn=DynModel(), drive=DriveModel(), flanger=FlangerModel(), chorus=ChorusModel(), delay=DelayModel(), reverb=Model(), room=RoomModel())
         self.mm, self.lim = Master(), None
         self.lims = []                                           # every Lim the walk has had
         self.irs = {}                                            # the responses: no entry of the library reads one back
         self.peaks = []                                          # the peak of every master of 16 frames and more so far, before the limiter
         self.lim_meters = None                                   # of the last fill that ran the limiter on the handle in hand
+        # [frames in which a flanger with a feedback or a cross differed on bits from its twin without (FlangerModel), frames it ran]
+        self.recursion = [0, 0]
 
     def of(self, stage):
         """bus -> the model's record of `stage`"""
-        return getattr(self.m[stage], dict(eq="e", dyn="d", drive="d", chorus="c", delay="d", reverb="fx", room="r")[stage])
+        return getattr(self.m[stage], dict(eq="e", dyn="d", drive="d", flanger="f", chorus="c", delay="d", reverb="fx", room="r")[stage])
 
     def present(self):
         return " ".join("%s:%s" % (st, ",".join(str(b) for b in sorted(self.of(st)))) for st in STAGES if self.of(st)) + \
@@ -259,6 +280,8 @@ class Chain:
             return ((curve, s["pre"], s["dry"], s["wet"]),) * 2
         if stage == "room":
             return ROOMS[s["delays"]] + LEVELS[s["levels"]], (ROOMS[s["delays"]], LEVELS[s["levels"]])
+        if stage == "flanger":
+            return (FLANGER_SHAPE[s["H"]] + (s["inc"], s["spread"], s["feedback"], s["cross"], s["dry"], s["wet"]),) * 2
         if stage == "chorus":
             return ((s["voices"],) + SHAPES[s["H"]] + (s["inc"], s["spread"], s["dry"], s["wet"]),) * 2
         if stage == "delay":
@@ -302,6 +325,9 @@ class Chain:
             elif st == "room":
                 fan.set_bus_room_params(bus, *LEVELS[s["levels"]])
                 f["lv"] = tuple(LEVELS[s["levels"]])
+            elif st == "flanger":                                # (base, depth, line and phase stay)
+                fan.set_bus_flanger_params(bus, s["inc"], s["spread"], s["feedback"], s["cross"], s["dry"], s["wet"])
+                f.update(inc=s["inc"], spread=s["spread"], mix=(s["feedback"], s["cross"], s["dry"], s["wet"]))
             elif st == "chorus" and action["entry"] == "set_bus_chorus_rate":
                 fan.set_bus_chorus_rate(bus, s["inc"], s["spread"])
                 f.update(inc=s["inc"], spread=s["spread"])
@@ -358,9 +384,9 @@ class Chain:
         view.tune(_Fan(self.handles), x, what)
 
     @staticmethod
-    def _room_age(f, x):
-        """the frames a room has run behind the first frame that was not +0.0 since it was set, this call of x [N, 2] included (its
-        model's record starts without one): what its lines hold is +0.0 until then"""
+    def _age(f, x):
+        """the frames a room or a flanger has run behind the first frame that was not +0.0 since it was set, this call of x [N, 2]
+        included (its model's record starts without one): what its lines hold is +0.0 until then"""
         age = f.get("age", 0)
         if age:
             return age + x.shape[0]
@@ -370,13 +396,29 @@ class Chain:
     def _excused(self, stage, f, x):
         """the cases a stage's own file documents as changing no bit (tests/test_gpu_chorus.py, _delay.py, _reverb.py: _fill;
         tests/test_gpu_room.py: the matrix's comment and the test with gain 0): taps that land in a history of zeros under a dry of 1, a
-        response of one tap with dry 0 and wet 1 is not looked at, lines that have not turned over under a dry of 1.  Every one of those
+        response of one tap with dry 0 and wet 1 is not looked at, lines that have not turned over under a dry of 1.  The flanger has
+        the chorus's case: under a dry of 1, a call whose every tap lands in a line that is +0.0 throughout — then every
+        tap is +0.0, whatever feedback and cross are the line takes the bus itself, and the output is (1 * x) + (wet * +0.0), the bus.
+        The chorus's bound, everything a tap of `base` frames could reach, is not enough here: a flanger's depth reaches 4063 frames
+        and a phase_inc of 2^31 sends every other frame's tap to the far end of a line that is still +0.0 there while the near end
+        sounds.  So the taps themselves are asked for — the rule's own (s2.flanger_reference) from the same line and phase at dry 0
+        and wet 1, which returns (0 * x) + (1 * tap) — and the call is excused when none of them has a bit set.  And the room's
+        case of the first turn is the flanger's too, for the room's reason, which no per-stage file meets because none puts a
+        drive in front of a dry of 1: the first frames a bus sounds behind a drive are its pre-ringing, 1e-37 against a signal of
+        1 (sweep seeds 200158, 200335 and 300143: a first call of 33 frames whose one tap with a bit set reads frame 0), so
+        (1 * x) + (wet * tap) is x on bits by the rule.  Excused under a dry of 1 until the shortest tap, `base` frames, has
+        turned over twice.  Every one of those
         files asks first that the bus is not silent as it enters: expect excuses a stage whose input is +0.0 throughout too — the first
         frames behind a delay with no dry path, say"""
         n = x.shape[0]
         if stage == "chorus":                                    # (a tap is base frames late at the least)
             line = np.concatenate([f["hist"], x], axis=0)
             return f["dry"] == 1.0 and not ubits(line[:line.shape[0] - int(np.floor(f["base"]))]).any()
+        if stage == "flanger":
+            if f["mix"][2] != 1.0:
+                return False
+            taps = s2.flanger_reference(*f["shape"], f["inc"], f["spread"], *f["mix"][:2], 0.0, 1.0, x, f["hist"], f["phase"])[0]
+            return not ubits(taps).any() or self._age(f, x) <= 2 * int(np.floor(f["shape"][0]))
         if stage == "delay":
             return f["mix"][2] == 1.0 and not ubits(f["hist"][:min(n, f["D"])]).any()
         if stage == "reverb":
@@ -385,7 +427,7 @@ class Chain:
             # no line is shorter than ROOM_MIN_DELAY and a set starts them as +0.0: under a dry of 1 nothing comes back before that many
             # frames have sounded, and what the first frames behind the turn bring back — a fade-in, the drive's pre-ringing — may lie
             # below half an ulp of the dry signal: excused until the shortest line has turned over twice
-            return f["lv"][4] == 1.0 and self._room_age(f, x) <= 2 * s2.ROOM_MIN_DELAY
+            return f["lv"][4] == 1.0 and self._age(f, x) <= 2 * s2.ROOM_MIN_DELAY
         return False
 
     def expect(self, x, action, what=""):
@@ -404,10 +446,14 @@ class Chain:
             if st == "drive" and act and action["tune"]:
                 self._tune(y, what)
             excused = {b: self._excused(st, self.of(st)[b], y[b]) or not ubits(y[b]).any() for b in act}     # (or the bus enters as +0.0 throughout)
+            fed = {b: (self.of(st)[b]["differs"], self.of(st)[b]["frames"]) for b in act if self.of(st)[b]["mix"][:2] != (0.0, 0.0)} if st == "flanger" else {}
             z = self.m[st].expect(y)
-            if st == "room":
+            for b, (differs, ran) in fed.items():
+                self.recursion[0] += self.of(st)[b]["differs"] - differs
+                self.recursion[1] += self.of(st)[b]["frames"] - ran
+            if st in ("flanger", "room"):
                 for b in act:
-                    self.of(st)[b]["age"] = self._room_age(self.of(st)[b], y[b])
+                    self.of(st)[b]["age"] = self._age(self.of(st)[b], y[b])
             for b in range(nb):
                 if b in act:
                     trace.append((st, b, not np.array_equal(ubits(z[b]), ubits(y[b])), excused[b]))
@@ -442,8 +488,8 @@ class Chain:
         out = {}
         for st in STAGES:
             for b, f in self.of(st).items():
-                if st == "chorus":
-                    out["chorus %d history" % b], out["chorus %d phase" % b] = f["hist"], _halves(f["phase"])
+                if st in PAIRED:
+                    out["%s %d history" % (st, b)], out["%s %d phase" % (st, b)] = f["hist"], _halves(f["phase"])
                 else:
                     out["%s %d" % (st, b)] = np.array(f[dict(eq="st", dyn="y", drive="hist", delay="hist", reverb="hist", room="st")[st]], dtype=F)
         if self.lim is not None:
@@ -456,8 +502,9 @@ def _halves(phase):
     return np.array([int(phase) >> 16, int(phase) & 0xFFFF], dtype=F)
 
 
-GETTERS = dict(eq="bus_eq_state", dyn="bus_dynamics_state", drive="bus_drive_history", room="bus_room_state", chorus="bus_chorus_state",
-               delay="bus_delay_history", reverb="bus_reverb_history")
+GETTERS = dict(eq="bus_eq_state", dyn="bus_dynamics_state", drive="bus_drive_history", flanger="bus_flanger_state", room="bus_room_state",
+               chorus="bus_chorus_state", delay="bus_delay_history", reverb="bus_reverb_history")
+PAIRED = ("flanger", "chorus")                                   # their state is a pair: (line, the LFO's phase)
 
 
 def states_of(chain, syn):
@@ -466,8 +513,8 @@ def states_of(chain, syn):
     for st in STAGES:
         for b in chain.of(st):
             got = getattr(syn, GETTERS[st])(b)
-            if st == "chorus":
-                out["chorus %d history" % b], out["chorus %d phase" % b] = got[0], _halves(got[1])
+            if st in PAIRED:
+                out["%s %d history" % (st, b)], out["%s %d phase" % (st, b)] = got[0], _halves(got[1])
             else:
                 out["%s %d" % (st, b)] = np.array(got, dtype=F)
     if chain.lim is not None:
@@ -476,8 +523,8 @@ def states_of(chain, syn):
 
 
 def _restore(chain, syn, st, b, state):
-    if st == "chorus":
-        syn.set_bus_chorus_state(b, *state)
+    if st in PAIRED:
+        getattr(syn, "set_" + GETTERS[st])(b, *state)
     else:
         getattr(syn, "set_" + GETTERS[st])(b, state)
 
@@ -511,6 +558,8 @@ def handover(chain, src, dst):
                 dst.set_bus_dynamics(b, *src.get_bus_dynamics(b))
             elif st == "drive":
                 dst.set_bus_drive(b, *src.get_bus_drive(b))
+            elif st == "flanger":
+                dst.set_bus_flanger(b, *src.get_bus_flanger(b))
             elif st == "room":
                 dst.set_bus_room(b, *src.get_bus_room(b))
             elif st == "chorus":
@@ -536,19 +585,23 @@ def handover(chain, src, dst):
 
 
 def subset_walk():
-    """the systematic complement of the seeded walks: the 16 subsets of the four inserts in Gray-code order — each step sets or clears
+    """the systematic complement of the seeded walks: the 32 subsets of the five inserts in Gray-code order — each step sets or clears
     exactly one insert, on two of three buses, while the others are in mid-state —, each with a bus fill, a master fill with stems and a
-    master fill under the limiter, 33 frames a call; a chorus on bus 2 and a reverb on bus 1 stay on throughout, so the inserts sit in
-    front of and behind running stem stages"""
-    where = dict(eq=(0, 1), dyn=(1, 2), drive=(0, 2), room=(1, 2))
+    master fill under the limiter, 33 frames a call, 96 calls; a chorus on bus 2 and a reverb on bus 1 stay on throughout, so the
+    inserts sit in front of and behind running stem stages.  The flanger sits on bus 2 with H = 33 — every tap exactly one tile old —,
+    behind a drive and in front of the chorus and a room, and on bus 1 with a feedback and a cross, in front of the reverb and a room;
+    bus 0 carries none, so its launch copies that bus"""
+    where = dict(eq=(0, 1), dyn=(1, 2), drive=(0, 2), flanger=(2, 1), room=(1, 2))
     shapes = dict(eq=[dict(bands=2, seed=1), dict(bands=4, seed=3)],
                   dyn=[dict(key=0, ratio=0, below=14.0, coefs="1ms-100ms"), dict(key=2, ratio=2, below=6.0, coefs="zero")],
                   drive=[dict(curve="hard", seed=1, pre=1.0, dry=0.0, wet=1.0), dict(curve="random", seed=5, pre=1.0, dry=0.5, wet=0.75)],
+                  flanger=[dict(H=33, inc=89478 * 4, spread=0x40000000, feedback=0.7, cross=0.0, dry=0.0, wet=1.0),
+                           dict(H=65, inc=89478 * 20, spread=7, feedback=-0.5, cross=0.25, dry=0.5, wet=0.75)],
                   room=[dict(delays="small", levels="dark"), dict(delays="flat", levels="hall")])
     steps = [dict(kind="set", stage="chorus", bus=2, replaces=False, shape=dict(H=145, voices=3, inc=89478 * 20, spread=0x40000000, dry=0.5, wet=0.25)),
              dict(kind="set", stage="reverb", bus=1, replaces=False, shape=dict(K=40, stereo=True, seed=77, dry=0.25, wet=1.0))]
     on = 0
-    for i in range(16):
+    for i in range(1 << len(INSERTS)):
         gray = i ^ (i >> 1)
         for j, st in enumerate(INSERTS):
             if (gray ^ on) >> j & 1:

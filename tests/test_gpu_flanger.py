@@ -165,6 +165,46 @@ def test_flangers_are_the_rule_over_the_twins_buses(n_buses, flangers):
             assert not f["frames"] and not bits(f["hist"]).any()
 
 
+GROUP = 8 * T                                                    # kFlAhead tiles: the frames whose input the wave loads ahead, a group at a time
+EDGES = [2048, GROUP - 1, GROUP, GROUP + 1, GROUP + T - 1, GROUP + T, GROUP + T + 1, 2 * GROUP - 1, 2 * GROUP, 2 * GROUP + 1, 1025, 2047, 2048]
+EDGE_FLANGERS = {0: (33, FB, (0.0, 1.0)), 1: (145, NEG, (0.5, 0.75)), 2: (4096, CROSS, (0.25, 1.0))}
+
+
+@pytest.mark.parametrize("n_buses", [4, 3])
+def test_the_group_edges_and_calls_past_1024_frames(n_buses):
+    """The wave walks groups of eight whole tiles, 256 frames, loading the next group's input first, clamped to the call's last frame,
+    then a tail of fewer than eight whole tiles and a partial one: calls of 255, 256, 257, 287, 288, 289, 511, 512 and 513 frames are a
+    group that ends the call (every load of the next group clamped), one frame less and more, a group and one whole tile, and the
+    same around two groups.  Calls of 1025, 2047 and 2048 frames on handles of max_frames = 2048 are past the staging buffer's first
+    1024 frames of a bus, and N + H walks the ring of 4096 once and a half at H = 4096.  With four buses the fourth carries no
+    flanger and is copied by workgroups (1 + g, 3) of 1024 frames each, two of them; with three every bus of the call carries one,
+    the grid is (1, 3) and no copy workgroup exists.  Line and phase are read back after the call of 256 frames and at the end.  The
+    twin's buses and the model come first, then the condition on them, then the device; everything it returns is collected first,
+    then compared."""
+    assert EDGES == [2048, 255, 256, 257, 287, 288, 289, 511, 512, 513, 1025, 2047, 2048]
+    a, b = _handles(max_frames=2048)
+    model = FlangerModel()
+    for bus, (H, mix, level) in EDGE_FLANGERS.items():
+        _set(a, model, bus, H, mix, level)
+    assert (n_buses - len(model.f)) == (1 if n_buses == 4 else 0)
+    steps = []
+    for fill, n in enumerate(EDGES):
+        _events((a, b), V, fill)
+        what = "%d buses, fill %d of %d frames" % (n_buses, fill, n)
+        x = b.sample_buses(n, SR, n_buses)
+        want = model.expect(x)
+        got = a.sample_buses(n, SR, n_buses)
+        st = {bus: (a.bus_flanger_state(bus), (f["hist"].copy(), f["phase"])) for bus, f in model.f.items()} if fill in (2, len(EDGES) - 1) else {}
+        steps.append((what, x, want, got, st))
+    model.busy("%d buses, the group edges" % n_buses)
+    assert sum(1 for _, _, _, _, st in steps if st) == 2 and steps[2][1].shape[1] == GROUP
+    for what, x, want, got, st in steps:
+        _check(x, want, got, model, what)
+        for bus, (g, w) in st.items():
+            assert_bits_equal_finite(g[0], w[0], "%s: line of bus %d" % (what, bus))
+            assert g[1] == w[1], "%s: phase of bus %d" % (what, bus)
+
+
 def test_a_crafted_history_at_the_shortest_delay():
     """base 32, depth 0, feedback 1, wet alone: tap[n] = w[n - 32], every tap exactly one tile old.  The line goes in as a ramp of
     distinct values, comes back, and the first tile returns 32 of its 33 frames in order; a tile that read its own frames, or the

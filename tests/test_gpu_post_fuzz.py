@@ -1,21 +1,25 @@
-"""Differential fuzzing of the post-mix chain (DESIGN.md 4.16 to 4.24) against the composed host models: the seeded walks of
+"""Differential fuzzing of the post-mix chain (DESIGN.md 4.16 to 4.25) against the composed host models: the seeded walks of
 tests/post_walk.py, played on twin handles.  Handle `a` makes the walk's calls; its twin `b` is fed the same events and makes a plain bus
 fill of the same frames and buses every time (a panned one for a panned fill), so its output is the dry signal; the expectation is
-post_walk.Chain over it — per bus the EQ's, the dynamics', the drive's, the chorus's, the delay's, the reverb's and the room's model, then
-the master section's and the limiter's, each the one its tests/test_*_host.py file pins to numpy on bits.  The device is never compared
+post_walk.Chain over it — per bus the EQ's, the dynamics', the drive's, the flanger's, the chorus's, the delay's, the reverb's and the
+room's model, eight of them, then the master section's and the limiter's, each the one its tests/test_*_host.py file pins to numpy on bits.  The device is never compared
 with itself.  What a walk varies: which effects sit on which of eight buses and in what shape, n_buses and frames from call to call,
 max_frames, the kind of fill, kept-state parameter moves, sets in mid-tail, state round trips, timing, and one handover of the whole
-chain onto a fresh handle.  tests/test_post_walk_host.py asserts on the CPU that the default seeds cover all of that.
+chain onto a fresh handle — the flanger's line and phase go through the round trip, the handover and the final comparison as the
+chorus's do.  tests/test_post_walk_host.py asserts on the CPU that the default seeds cover all of that, and that a flanger runs in
+calls of more than 1024 frames, at H = 4096, in calls of 255, 256 and 257 frames, and idles between two fills that run it.
 
 Deterministic: the seeds are fixed and a failure names its seed, step and action and the effects present at that step;
 S2R_POST_FUZZ_BASE=<that seed> S2R_POST_FUZZ_SEEDS=1 runs it again.  Every comparison is on bits with no NaN allowance
 (helpers.assert_bits_equal_finite).
 
-S2R_POST_FUZZ_SEEDS=N widens the sweep, S2R_POST_FUZZ_BASE moves it.  History: 1200 walks at bases 100000, 200000 and 300000 beside the default 24 at
-base 5000 have run equal on bits: no seed has found a fault in the chain yet (a seed that does goes here, as a regression).  What the
+S2R_POST_FUZZ_SEEDS=N widens the sweep, S2R_POST_FUZZ_BASE moves it.  History: 1200 walks at bases 100000, 200000 and 300000 beside the default 32 at
+base 5000 have run equal on bits, before the flanger joined the walks and again with it: no seed has found a fault in the chain yet (a seed that does goes here, as a regression).  What the
 first sweeps did find was in the walks: seeds 100022 and 100037 (a walk that ended on a fader move with no master fill behind it; a
 limiter whose ceiling, taken from an earlier and louder master, never worked), and on the host seed 300349 (a room under a dry of 1
-whose first turn of the lines lies below half an ulp of the bus: post_walk.Chain._excused)."""
+whose first turn of the lines lies below half an ulp of the bus: post_walk.Chain._excused) and, with the flanger, seeds 5001, 200158,
+200335 and 300143 (a flanger under a dry of 1 whose taps of the call are all +0.0 at the far end of its line, or read the first
+frame behind a drive, 1e-37: the same place)."""
 import os
 
 import numpy as np
@@ -109,11 +113,13 @@ def test_post_fuzz(seed):
 
 
 def test_every_insert_subset_on_every_kind_of_call():
-    """The systematic complement (post_walk.subset_walk): one pair of handles, three buses, 33 frames a call, 48 calls — the 16 subsets of
-    {EQ, dynamics, drive, room} in Gray-code order, so that each step sets or clears exactly one insert while the others are in
-    mid-state, each subset with a bus fill, a master fill with stems and a master fill under the limiter; a chorus on bus 2 and a reverb
-    on bus 1 stay on throughout.  An insert that is cleared and set again starts afresh in the model too.  The per-stage files run each
-    insert alone, {EQ, dyn}, {EQ, dyn, room} and all four; the other nine subsets launch no kernel anywhere else."""
+    """The systematic complement (post_walk.subset_walk): one pair of handles, three buses, 33 frames a call, 96 calls — the 32 subsets of
+    {EQ, dynamics, drive, flanger, room} in Gray-code order, so that each step sets or clears exactly one insert while the others are
+    in mid-state, each subset with a bus fill, a master fill with stems and a master fill under the limiter; a chorus on bus 2 and a
+    reverb on bus 1 stay on throughout.  An insert that is cleared and set again starts afresh in the model too.  The per-stage files
+    run each insert alone, {EQ, dyn}, {EQ, dyn, room}, {EQ, dyn, drive, room} and all five; the seeded walks open on all 32 subsets,
+    each on a fresh handle, and this is the one test that goes from subset to subset on one handle, so that the set of a flanger's
+    neighbours changes while its line and phase are in mid-state, and every other insert's while a flanger is."""
     setup, steps = pw.subset_walk()
     chain, got = play(setup, steps, "the subset walk")
-    assert len(got) == 48 and all("gain" in want and (want["gain"] < 1.0).any() for _, _, want, _ in got[2::3])
+    assert len(got) == 96 and all("gain" in want and (want["gain"] < 1.0).any() for _, _, want, _ in got[2::3])

@@ -23,7 +23,8 @@ def _subsets(names):
 def survey(seeds):
     """the walks on the books alone — which effect is present when, no arithmetic — -> what the conditions below ask about"""
     s = dict(kinds=set(), fills=set(), stage_events={st: set() for st in STAGES}, inserts=set(), stems={"bus": set(), "master": set()}, n_buses=set(),
-             frames=set(), max_frames=set(), timing=set(), handovers=0, roundtrips=0, idle_between_runs=False, entries=set(), big_room=False)
+             frames=set(), max_frames=set(), timing=set(), handovers=0, roundtrips=0, idle_between_runs=False, entries=set(), big_room=False,
+             flanger=dict(frames=set(), H=set(), idle_between_runs=False, roundtrips=0, handovers=0))
     for seed in seeds:
         setup, steps = walk(seed)
         assert 20 <= len(steps) <= 30 and sum(a["kind"] == "fill" for a in steps) >= 12, seed
@@ -32,6 +33,7 @@ def survey(seeds):
         s["timing"].add(setup["timing"])
         present = {st: {} for st in STAGES}                      # stage -> bus -> the key bus (dynamics) or None
         ran, idled = set(), set()                                # (stage, bus) that some fill ran; that a later fill then left idle
+        shapes = {}                                              # bus -> the shape its flanger was set with
         for a in steps:
             kind = a["kind"]
             s["kinds"].add(kind)
@@ -39,6 +41,8 @@ def survey(seeds):
                 assert a["replaces"] == (a["bus"] in present[a["stage"]]), seed
                 s["stage_events"][a["stage"]].add("replace" if a["replaces"] else "set")
                 present[a["stage"]][a["bus"]] = a["shape"].get("key")
+                if a["stage"] == "flanger":
+                    shapes[a["bus"]] = a["shape"]
                 ran.discard((a["stage"], a["bus"])); idled.discard((a["stage"], a["bus"]))      # a new effect: nothing carried
             elif kind == "clear":
                 s["stage_events"][a["stage"]].add("clear")
@@ -52,8 +56,10 @@ def survey(seeds):
                     present["dyn"][a["bus"]] = a["shape"]["key"]
             elif kind == "handover":
                 s["handovers"] += 1
+                s["flanger"]["handovers"] += bool(present["flanger"])
             elif kind == "roundtrip":
                 s["roundtrips"] += 1
+                s["flanger"]["roundtrips"] += bool(present["flanger"])
             elif kind == "fill":
                 s["fills"].add(a["fill"])
                 assert 1 <= a["frames"] <= setup["max_frames"], seed
@@ -76,6 +82,11 @@ def survey(seeds):
                         if active(st, b):
                             if (st, b) in idled:
                                 s["idle_between_runs"] = True
+                                if st == "flanger":
+                                    s["flanger"]["idle_between_runs"] = True
+                            if st == "flanger":
+                                s["flanger"]["frames"].add(a["frames"])
+                                s["flanger"]["H"].add(shapes[b]["H"])
                             ran.add((st, b))
                         elif (st, b) in ran and b >= nb:         # present on a bus past the call's, after a fill that ran it
                             idled.add((st, b))
@@ -98,8 +109,9 @@ def test_the_default_walks_cover_what_they_are_for():
     for st in STAGES:
         assert s["stage_events"][st] == {"set", "clear", "replace", "params"}, (st, s["stage_events"][st])
     assert s["entries"] == {"set_bus_eq_coeffs", "set_bus_dynamics_params", "set_bus_drive_params", "set_bus_room_params", "set_bus_chorus_rate",
-                            "set_bus_chorus_mix", "set_bus_delay_mix", "set_bus_reverb_mix"}
-    # 3. all 16 subsets of the inserts are active in some fill; all 8 of the stem stages in a bus fill and in a master fill
+                            "set_bus_chorus_mix", "set_bus_delay_mix", "set_bus_reverb_mix", "set_bus_flanger_params"}
+    # 3. all 32 subsets of the five inserts are active in some fill; all 8 of the stem stages in a bus fill and in a master fill
+    assert len(_subsets(INSERTS)) == 32
     assert s["inserts"] == set(_subsets(INSERTS)), sorted(map(sorted, set(_subsets(INSERTS)) - s["inserts"]))
     for kind in ("bus", "master"):
         assert s["stems"][kind] == set(_subsets(STEMS)), (kind, sorted(map(sorted, set(_subsets(STEMS)) - s["stems"][kind])))
@@ -114,9 +126,18 @@ def test_the_default_walks_cover_what_they_are_for():
     assert s["handovers"] >= 1 and s["roundtrips"] >= 3
     # and a room runs in a call of more than 1024 frames: its work area's stride is max_frames, not 1024
     assert s["big_room"]
+    # 7. the flanger where its kernel can go wrong by itself (s2r_flanger.hip): past the first copy workgroup's 1024 frames and the
+    # staging buffer's first 1024; the whole ring; a group of eight tiles that ends the call, one frame less and one more; and between
+    # two fills that run it, a fill whose buses end before its bus: no phase advanced, no line flipped (s2r_post.cpp: commit)
+    fl = s["flanger"]
+    assert any(n > 1024 for n in fl["frames"]), "no flanger runs in a call of more than 1024 frames"
+    assert 4096 in fl["H"], "no flanger of H = 4096 runs"
+    assert fl["frames"] >= {255, 256, 257}, "no flanger runs in a call of %s frames" % sorted({255, 256, 257} - fl["frames"])
+    assert fl["idle_between_runs"], "no flanger idles past the call's buses between two fills that run it"
+    assert fl["roundtrips"] >= 1 and fl["handovers"] >= 1, "a flanger's state goes through %d round trips and %d handovers" % (fl["roundtrips"], fl["handovers"])
 
 
-def test_the_subset_walk_makes_48_calls_over_the_16_subsets():
+def test_the_subset_walk_makes_96_calls_over_the_32_subsets():
     setup, steps = pw.subset_walk()
     on, seen, calls = {st: set() for st in INSERTS}, [], 0
     for a in steps:
@@ -130,9 +151,15 @@ def test_the_subset_walk_makes_48_calls_over_the_16_subsets():
             if not seen or seen[-1] != now:
                 seen.append(now)
             assert (a["n_buses"], a["frames"]) == (3, 33)
-    assert calls == 48 and len(seen) == 16 and set(seen) == set(_subsets(INSERTS))
+    assert calls == 96 and len(seen) == 32 and set(seen) == set(_subsets(INSERTS))
     assert all(len(p ^ q) == 1 for p, q in zip(seen, seen[1:]))  # Gray-code order: one insert set or cleared per step
-    assert [a["fill"] for a in steps if a["kind"] == "fill"] == ["bus", "master_stems", "master"] * 16
+    assert [a["fill"] for a in steps if a["kind"] == "fill"] == ["bus", "master_stems", "master"] * 32
+    # the flanger: on two of the three buses, one with H = 33, the other with a feedback and a cross, one beside the drive, one beside the room
+    fl = {a["bus"]: a["shape"] for a in steps if a["kind"] == "set" and a["stage"] == "flanger"}
+    beside = {st: {a["bus"] for a in steps if a["kind"] == "set" and a["stage"] == st} for st in ("drive", "room")}
+    assert len(fl) == 2 and sorted(q["H"] == 33 for q in fl.values()) == [False, True]
+    assert any(q["H"] != 33 and q["feedback"] != 0.0 and q["cross"] != 0.0 for q in fl.values())
+    assert set(fl) & beside["drive"] and set(fl) & beside["room"]
 
 
 def _dry(rng, nb, n):
@@ -182,5 +209,17 @@ def test_the_model_alone_is_well_behaved_over_the_subset_walk():
     setup, steps = pw.subset_walk()
     chain, fills = run_on_the_model(setup, steps, 1)
     _check_model_run(chain, fills, "the subset walk")
-    assert any(len(e["trace"]) == 10 for _, _, e in fills)       # all four inserts on two buses each, the chorus and the reverb
+    assert any(len(e["trace"]) == 12 for _, _, e in fills)       # all five inserts on two buses each, the chorus and the reverb
+    assert chain.recursion[1] == 2 * 48 * 33 and chain.recursion[0] >= chain.recursion[1] / 10.0, chain.recursion
     assert all((e["gain"] < 1.0).any() for _, a, e in fills if a["fill"] == "master")
+
+
+def test_the_flangers_recursion_shows_over_the_default_walks():
+    """FlangerModel carries beside each flanger the same flanger at feedback = cross = 0, fed the same input: over the default seeds the
+    flangers with a feedback or a cross differ from that twin on bits in at least a tenth of the frames they ran — the per-stage
+    file's threshold (FlangerModel.busy), over the sweep as a whole: a walk's flanger may live for two short calls"""
+    differs = frames = 0
+    for seed in DEFAULTS:
+        chain, _ = run_on_the_model(*walk(seed), seed)
+        differs, frames = differs + chain.recursion[0], frames + chain.recursion[1]
+    assert frames > 0 and differs >= frames / 10.0, "the recursion shows in %d of %d frames" % (differs, frames)
