@@ -316,6 +316,30 @@ class Synth {
         return s2r_limiter_reference(x, frames, ceiling, lookahead, hold, xh, gh, y, gain);
     }
 
+    // the loudness and true-peak meters (build-defined; s2r.h: s2r_set_master_loudness): BS.1770 loudness of every bus and the master and
+    // the master's true peak, behind the limiter, in sample_master only; master_lr and the stems are the same bits with the meter on or off
+    void set_master_loudness(const float coeffs[10], uint32_t hop, uint32_t max_hops) { check(s2r_set_master_loudness(h_, coeffs, hop, max_hops)); }
+    void clear_master_loudness() { check(s2r_clear_master_loudness(h_)); }
+    // a hop of 0 means off; n_hops: the hop rows stored
+    void get_master_loudness(float coeffs[10], uint32_t *hop, uint32_t *max_hops, size_t *n_hops) const { check(s2r_get_master_loudness(h_, coeffs, hop, max_hops, n_hops)); }
+    void reset_master_loudness() { check(s2r_reset_master_loudness(h_)); }
+    // out: momentary, short-term, integrated in LKFS; programme S2R_MAX_BUSES is the master
+    void loudness(uint32_t programme, double out[3]) const { check(s2r_get_loudness(h_, programme, out)); }
+    void true_peak(float last[2], float held[2]) const { check(s2r_get_true_peak(h_, last, held)); }
+    // state: S2R_LOUDNESS_STATE floats; rows: [n_hops][S2R_LOUDNESS_CHANNELS] (checkpoints)
+    void loudness_state(float *state, size_t capacity, uint32_t *pos) { check(s2r_get_loudness_state(h_, state, capacity, pos)); }
+    void set_loudness_state(const float *state, size_t count, uint32_t pos) { check(s2r_set_loudness_state(h_, state, count, pos)); }
+    void loudness_hops(float *rows, size_t capacity, size_t *n_hops) const { check(s2r_get_loudness_hops(h_, rows, capacity, n_hops)); }
+    void set_loudness_hops(const float *rows, size_t n_hops, size_t count) { check(s2r_set_loudness_hops(h_, rows, n_hops, count)); }
+    static int loudness_reference(const float coeffs[10], uint32_t hop, const float *stems, uint32_t n_buses, const float *master_lr, uint32_t frames,
+                                  float *state, uint32_t *pos, float *rows, size_t rows_capacity, size_t *n_rows, float true_peak[2]) {
+        return s2r_loudness_reference(coeffs, hop, stems, n_buses, master_lr, frames, state, pos, rows, rows_capacity, n_rows, true_peak);
+    }
+    static int loudness_readings(const float *rows, size_t n_hops, uint32_t hop, uint32_t programme, double out[3]) {
+        return s2r_loudness_readings(rows, n_hops, hop, programme, out);
+    }
+    static int loudness_design(double sample_rate, float coeffs[10]) { return s2r_loudness_design(sample_rate, coeffs); }
+
     s2r_synth *handle() { return h_; }
 
   private:

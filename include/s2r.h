@@ -49,7 +49,10 @@ extern "C" {
  * s2r_get_bus_room_state, s2r_set_bus_room_state, s2r_room_state_floats, s2r_room_reference, s2r_room_design, s2r_set_bus_drive,
  * s2r_clear_bus_drive, s2r_set_bus_drive_params, s2r_get_bus_drive, s2r_get_bus_drive_history, s2r_set_bus_drive_history,
  * s2r_drive_reference, s2r_drive_taps, s2r_drive_curve, s2r_flanger_history_frames, s2r_set_bus_flanger, s2r_clear_bus_flanger,
- * s2r_set_bus_flanger_params, s2r_get_bus_flanger, s2r_get_bus_flanger_state, s2r_set_bus_flanger_state, s2r_flanger_reference. */
+ * s2r_set_bus_flanger_params, s2r_get_bus_flanger, s2r_get_bus_flanger_state, s2r_set_bus_flanger_state, s2r_flanger_reference,
+ * s2r_set_master_loudness, s2r_clear_master_loudness, s2r_get_master_loudness, s2r_reset_master_loudness, s2r_get_loudness,
+ * s2r_get_true_peak, s2r_get_loudness_state, s2r_set_loudness_state, s2r_get_loudness_hops, s2r_set_loudness_hops,
+ * s2r_loudness_reference, s2r_loudness_readings, s2r_loudness_design. */
 #define S2R_ABI_VERSION 4
 
 typedef enum {
@@ -882,6 +885,86 @@ int s2r_set_limiter_state(s2r_synth *s, const float *xh, size_t n_x, const float
 int s2r_get_limiter_meters(const s2r_synth *s, float *min_gain, float *out_peak);
 int s2r_limiter_reference(const float *x, uint32_t frames, float ceiling, uint32_t lookahead, uint32_t hold, float *xh, float *gh,
                           float *y, float *gain);
+
+/* BUILD-DEFINED loudness and true-peak meters (the reference has none; DESIGN.md 4.26 gives the op sequence): ITU-R BS.1770 / EBU R128
+ * momentary, short-term and gated integrated loudness of every bus and of the master, and the master's true peak, behind the master
+ * limiter, in s2r_fill_master only, on the device the stems and the master are already on.  Off by default, and a handle on which the
+ * meter was never set launches exactly what it launched before; master_lr and the stems are the same bits with the meter on or off.
+ * PROGRAMMES: P = S2R_LOUDNESS_PROGRAMMES = S2R_MAX_BUSES + 1 = 9.  Programme b < 8 is bus b as the stems hold it — post-effect,
+ * pre-return, as for s2r_get_meters —, programme 8 the master as the caller receives it, behind the limiter when one is set.  18
+ * channels, channel q = 2 p + c.  A bus at or past the call's n_buses is fed +0.0 for every frame of the call: its filters run on
+ * zeros, and the hop position is common to all programmes.
+ * PARAMETERS: `coeffs`, two biquads (b0, b1, b2, a1, a2), finite: the K-weighting pre-filter, a high shelf and then a high-pass
+ * (s2r_loudness_design); `hop`, the frames of 100 ms, 16 .. S2R_LOUDNESS_MAX_HOP; `max_hops`, the hop rows the handle keeps for the
+ * integrated value, 30 .. S2R_LOUDNESS_MAX_HOPS: a sliding window, whose oldest row drops when a new one would exceed it.
+ * STATE carried from call to call, S2R_LOUDNESS_STATE = 122 floats and `pos`: the filters' values [18][2][2] (channel, stage,
+ * (s1, s2)), the partial hop sums e[18], the last 16 master frames [16][2], oldest first, L then R; pos < hop, the frames of the hop
+ * under way.  All +0.0 / 0 right after a set or a reset.
+ * DEVICE RULE, binary32, every operation rounded on its own, no fma, denormals kept.  For each channel q and each frame n of the
+ * call, in frame order, v[n] the channel's sample:
+ *   1. y1 = stage 1 on v[n], y2 = stage 2 on y1; a stage with x its input and its own (s1, s2) is one band of s2r_eq_reference:
+ *      y = (b0 * x) + s1;   s1' = ((b1 * x) - (a1 * y)) + s2;   s2' = (b2 * x) - (a2 * y)
+ *   2. z = y2 * y2;   e_q = e_q + z
+ *   3. after the frame pos = pos + 1; when pos == hop the 18 values e_q become one HOP ROW, every e_q = +0.0 and pos = 0.
+ * The hop sum is sequential, so every reading is independent of how a stream is cut into calls.
+ * TRUE PEAK, master only: with g[k] = 4 h[k] the drive's interpolator (s2r_drive_taps, S2R_DRIVE_OVERSAMPLE = 4) and x_c[n] for n < 0
+ * from the state, u_p[n] = sum over j with p + 4 j < S2R_DRIVE_TAPS of g[p + 4 j] * x_c[n - j], from +0.0 in ascending j, p = 0 .. 3;
+ * tp_c of a call = max over its frames of |x_c[n]| and the four |u_p[n]|.  The handle keeps the maximum since the last reset.  The
+ * prototype's passband ends near 0.29 of the sample rate: PEAKS OF CONTENT ABOVE THAT ARE UNDERESTIMATED.
+ * HOST RULE, binary64 (s2r_loudness_readings), over hop rows [n_hops][18] and one programme p, with t_i = (double)row_i[2 p] +
+ * (double)row_i[2 p + 1]: block j >= 3 has the mean square m_j = (((t_(j-3) + t_(j-2)) + t_(j-1)) + t_j) / (4.0 * hop) and the
+ * loudness l_j = -0.691 + 10 log10(m_j).  out[0], momentary: l of the last block.  out[1], short-term: the same over the last 30
+ * hops, summed in order from 0.0, divided by 30.0 * hop.  out[2], integrated, BS.1770's two gates: keep the blocks with l_j > -70; the
+ * relative threshold is the loudness of the mean of their m_j (summed in order from 0.0), minus 10; the reading is the loudness of
+ * the mean of the m_j of the blocks with l_j above both.  A reading is -inf where there are too few hops or nothing passes.
+ * A refused or failed call leaves state, rows and readings as they were; s2r_fill_buses and every other fill ignore the meter.
+ * Single-device handles (a device list refuses every entry).  The first master fill that finds the meter set allocates a device
+ * buffer of 2 * max_frames floats, the two copies of the state and pinned rows for max_frames / 16 + 1 hops.
+ *   s2r_set_master_loudness: S2R_ERR_PATCH_RANGE for a coefficient that is not finite, hop or max_hops out of range (checked before
+ *   the handle is looked at; nothing is changed); S2R_ERR_INVALID for NULL coeffs.  Resets state, rows and the held true peak.
+ *   s2r_clear_master_loudness: off.  s2r_get_master_loudness: any pointer may be NULL; a hop of 0 means off; n_hops the stored rows.
+ *   s2r_reset_master_loudness: state, rows and held true peak cleared, parameters kept; S2R_ERR_INVALID with the meter off.
+ *   s2r_get_loudness: out[3] = momentary, short-term, integrated of `programme` (< 9, else S2R_ERR_PATCH_RANGE) over the stored rows.
+ *   s2r_get_true_peak: last[2] of the last successful master fill with the meter (0 before one), held[2] since the last reset; L, R.
+ *   s2r_get_loudness_state / s2r_set_loudness_state (checkpoints): the 122 floats and pos.  The getter takes a capacity of at least
+ *   122, the setter exactly 122 and a pos below hop (S2R_ERR_PATCH_RANGE).  s2r_get_loudness_hops / s2r_set_loudness_hops: the stored
+ *   rows, oldest first, [n_hops][18]; the getter takes a capacity in floats, the setter exactly count == 18 * n_hops, n_hops <=
+ *   max_hops (S2R_ERR_PATCH_RANGE past it).  S2R_ERR_INVALID for a wrong size, a NULL buffer or with the meter off.
+ *   s2r_loudness_reference: the device rule on the host (no device, no handle).  stems [n_buses][frames][2] (NULL with n_buses 0),
+ *   master_lr [frames][2]; state[122] and *pos updated in place; the call's hop rows written to rows[0 .. 18 * *n_rows), which holds
+ *   rows_capacity floats (checked before anything is changed); true_peak[2] the call's (may be NULL).  S2R_ERR_PATCH_RANGE as the
+ *   setter's, for n_buses > 8 or *pos >= hop; S2R_ERR_INVALID for a NULL or a capacity too small.
+ *   s2r_loudness_readings: the host rule.  S2R_ERR_PATCH_RANGE for a hop out of range or programme >= 9, S2R_ERR_INVALID for NULL.
+ *   s2r_loudness_design: BS.1770's pre-filter at any rate, by the bilinear form with K = tan(pi f0 / sample_rate), binary64, rounded
+ *   once.  Stage 1, a high shelf: f0 = 1681.974450955533 Hz, G = 3.999843853973347 dB, Q = 0.7071752369554196, Vh = 10^(G / 20),
+ *   Vb = Vh^0.4996667741545416; a0 = 1 + K / Q + K^2, b0 = (Vh + Vb K / Q + K^2) / a0, b1 = 2 (K^2 - Vh) / a0, b2 = (Vh - Vb K / Q +
+ *   K^2) / a0, a1 = 2 (K^2 - 1) / a0, a2 = (1 - K / Q + K^2) / a0.  Stage 2, a high-pass: f0 = 38.13547087602444 Hz, Q =
+ *   0.5003270373238773; b = (1, -2, 1), a1 and a2 as above.  At 48 kHz this is the table BS.1770 prints.  S2R_ERR_PATCH_RANGE for
+ *   a sample_rate that is a NaN or outside [S2R_LOUDNESS_MIN_RATE, S2R_LOUDNESS_MAX_RATE], S2R_ERR_INVALID for NULL coeffs. */
+#define S2R_LOUDNESS_PROGRAMMES 9u
+#define S2R_LOUDNESS_CHANNELS 18u
+#define S2R_LOUDNESS_STATE 122u
+#define S2R_LOUDNESS_MIN_HOP 16u
+#define S2R_LOUDNESS_MAX_HOP (1u << 20)
+#define S2R_LOUDNESS_MIN_HOPS 30u
+#define S2R_LOUDNESS_MAX_HOPS (1u << 18)
+#define S2R_LOUDNESS_MIN_RATE 8000.0
+#define S2R_LOUDNESS_MAX_RATE 768000.0
+int s2r_set_master_loudness(s2r_synth *s, const float coeffs[10], uint32_t hop, uint32_t max_hops);
+int s2r_clear_master_loudness(s2r_synth *s);
+int s2r_get_master_loudness(const s2r_synth *s, float coeffs[10], uint32_t *hop, uint32_t *max_hops, size_t *n_hops);
+int s2r_reset_master_loudness(s2r_synth *s);
+int s2r_get_loudness(const s2r_synth *s, uint32_t programme, double out[3]);
+int s2r_get_true_peak(const s2r_synth *s, float last[2], float held[2]);
+int s2r_get_loudness_state(s2r_synth *s, float *state, size_t capacity, uint32_t *pos);
+int s2r_set_loudness_state(s2r_synth *s, const float *state, size_t count, uint32_t pos);
+int s2r_get_loudness_hops(const s2r_synth *s, float *rows, size_t capacity, size_t *n_hops);
+int s2r_set_loudness_hops(s2r_synth *s, const float *rows, size_t n_hops, size_t count);
+int s2r_loudness_reference(const float coeffs[10], uint32_t hop, const float *stems, uint32_t n_buses, const float *master_lr,
+                           uint32_t frames, float *state, uint32_t *pos, float *rows, size_t rows_capacity, size_t *n_rows,
+                           float true_peak[2]);
+int s2r_loudness_readings(const float *rows, size_t n_hops, uint32_t hop, uint32_t programme, double out[3]);
+int s2r_loudness_design(double sample_rate, float coeffs[10]);
 
 /* BUILD-DEFINED 4x oversampling (the reference has none; BASELINE config [4]): renders 4 * frames at
  * 4 * sample_rate_hz through the same path and decimates the mix by a 63-tap windowed sinc whose history

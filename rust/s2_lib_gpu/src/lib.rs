@@ -223,6 +223,21 @@ pub mod ffi {
         pub fn s2r_get_limiter_meters(s: *const S2rSynth, min_gain: *mut f32, out_peak: *mut f32) -> c_int;
         pub fn s2r_limiter_reference(x: *const f32, frames: u32, ceiling: f32, lookahead: u32, hold: u32, xh: *mut f32, gh: *mut f32,
                                      y: *mut f32, gain: *mut f32) -> c_int;
+        pub fn s2r_set_master_loudness(s: *mut S2rSynth, coeffs: *const f32, hop: u32, max_hops: u32) -> c_int;
+        pub fn s2r_clear_master_loudness(s: *mut S2rSynth) -> c_int;
+        pub fn s2r_get_master_loudness(s: *const S2rSynth, coeffs: *mut f32, hop: *mut u32, max_hops: *mut u32, n_hops: *mut usize) -> c_int;
+        pub fn s2r_reset_master_loudness(s: *mut S2rSynth) -> c_int;
+        pub fn s2r_get_loudness(s: *const S2rSynth, programme: u32, out: *mut f64) -> c_int;
+        pub fn s2r_get_true_peak(s: *const S2rSynth, last: *mut f32, held: *mut f32) -> c_int;
+        pub fn s2r_get_loudness_state(s: *mut S2rSynth, state: *mut f32, capacity: usize, pos: *mut u32) -> c_int;
+        pub fn s2r_set_loudness_state(s: *mut S2rSynth, state: *const f32, count: usize, pos: u32) -> c_int;
+        pub fn s2r_get_loudness_hops(s: *const S2rSynth, rows: *mut f32, capacity: usize, n_hops: *mut usize) -> c_int;
+        pub fn s2r_set_loudness_hops(s: *mut S2rSynth, rows: *const f32, n_hops: usize, count: usize) -> c_int;
+        pub fn s2r_loudness_reference(coeffs: *const f32, hop: u32, stems: *const f32, n_buses: u32, master_lr: *const f32, frames: u32,
+                                      state: *mut f32, pos: *mut u32, rows: *mut f32, rows_capacity: usize, n_rows: *mut usize,
+                                      true_peak: *mut f32) -> c_int;
+        pub fn s2r_loudness_readings(rows: *const f32, n_hops: usize, hop: u32, programme: u32, out: *mut f64) -> c_int;
+        pub fn s2r_loudness_design(sample_rate: f64, coeffs: *mut f32) -> c_int;
         pub fn s2r_shard_voices(s: *const S2rSynth) -> u32;
         pub fn s2r_fill_device(s: *mut S2rSynth, dev_out: *mut f32, frames: usize, sample_rate_hz: u32,
                                hip_stream: *mut c_void) -> c_int;

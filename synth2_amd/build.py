@@ -24,7 +24,8 @@ SOURCES = ["s2r_render_onepole_square.hip", "s2r_render_onepole_saw.hip", "s2r_r
            "s2r_dyn.hip",       # (behind the rest: every object in front of it keeps the place in the library it had before the dynamics came)
            "s2r_room.hip",      # (likewise, since the room came)
            "s2r_drive.hip",     # (likewise, since the drive came)
-           "s2r_flanger.hip"]   # (last, likewise, since the flanger came)
+           "s2r_flanger.hip",   # (likewise, since the flanger came)
+           "s2r_loudness.hip"]  # (last, likewise, since the loudness meters came)
 HEADERS = ["s2r_device.h", "s2r_math.h", "s2r_patch.h", "s2r_voices.h", "s2r_kern_common.h", "s2r_render_onepole.inc",
            "s2r_render_general.inc", "s2r_post.h", "s2r_post_route.h", "s2r_rules.h"]
 
@@ -96,9 +97,18 @@ RESOURCE_CHECKS = {
                        (_SCRATCH, _VSPILL, _SSPILL), "its stems and meter values must stay in registers"),
     "s2r_limiter.hip": (("s2r_limiter_kernel",), ("exactly", 1), "one kernel",
                         (_SCRATCH, _VSPILL, _SSPILL), "its windows live in LDS, the rest in registers"),
+    # a channel per walker lane: ten coefficients, four filter values, the hop sum and sixteen samples read ahead; nine frames of a tile
+    # per stager lane; seventeen master frames and two sums per true-peak lane, the taps in SGPRs
+    "s2r_loudness.hip": (("s2r_loudness_kernel",), ("exactly", 1), "one kernel",
+                         (_SCRATCH, _VSPILL, _SSPILL), "its filter values, sums and the samples read ahead must stay in registers, the tiles in LDS"),
 }
 for _f in RESOURCE_CHECKS:
     PER_FILE_FLAGS[_f] = ["-Rpass-analysis=kernel-resource-usage"]
+# s2r_loudness.hip is compiled at -O1.  At -O2 this compiler's code for the kernel's tiled walk computes wrong hop sums and filter values on
+# an MI355X — the first frame of a block of eight takes b2 * x where the rule has s1, as far as the assembly was read — with and without
+# SLP vectorisation, -fno-strict-aliasing or the max-ilp scheduler, while the optimised IR is the rule's, and the -O1 object and the
+# serial form at -O2 are right in every bit (tests/test_gpu_loudness.py).  The cause has NOT been found (CHANGELOG); until it is, -O1.
+PER_FILE_FLAGS["s2r_loudness.hip"] = ["drop:-O2", "-O1"] + PER_FILE_FLAGS["s2r_loudness.hip"]
 if os.environ.get("S2R_EXPERIMENT_BANK_FLAGS"):                 # (development: extra flags for the patch-bank translation unit)
     PER_FILE_FLAGS["s2r_render_general_bank.hip"] = PER_FILE_FLAGS["s2r_render_general_bank.hip"] + os.environ["S2R_EXPERIMENT_BANK_FLAGS"].split()
 
@@ -132,6 +142,11 @@ if _DRIVE_INTERLEAVED:
 _FLANGER_SERIAL = os.environ.get("S2R_FLANGER_SERIAL") == "1"
 if _FLANGER_SERIAL:
     PER_FILE_FLAGS["s2r_flanger.hip"] = PER_FILE_FLAGS["s2r_flanger.hip"] + ["-DS2R_FLANGER_SERIAL"]
+# S2R_LOUDNESS_SERIAL=1 likewise builds the loudness kernel's obvious form (a lane per channel steps through global memory frame by
+# frame; csrc/s2r_loudness.hip, CHANGELOG) into libs2r_loudnessserial.so, for tools/loudness_time.py.  Never the product build.
+_LOUDNESS_SERIAL = os.environ.get("S2R_LOUDNESS_SERIAL") == "1"
+if _LOUDNESS_SERIAL:
+    PER_FILE_FLAGS["s2r_loudness.hip"] = PER_FILE_FLAGS["s2r_loudness.hip"] + ["-DS2R_LOUDNESS_SERIAL"]
 # S2R_OPT=O3 in the environment builds the same sources at -O3 into libs2r_o3.so (tools and tests that compare the two
 # optimisation levels; the product is -O2).
 if os.environ.get("S2R_OPT") == "O3":
@@ -163,6 +178,9 @@ elif _DRIVE_INTERLEAVED:
 elif _FLANGER_SERIAL:
     LIB = os.path.join(HERE, "libs2r_flangerserial.so")
     OBJ_DIR_NAME = "_build_flangerserial"
+elif _LOUDNESS_SERIAL:
+    LIB = os.path.join(HERE, "libs2r_loudnessserial.so")
+    OBJ_DIR_NAME = "_build_loudnessserial"
 else:
     OBJ_DIR_NAME = "_build"
 

@@ -618,3 +618,25 @@ struct S2rLimiter {
     float ceiling;
 };
 hipError_t s2r_launch_limiter(const S2rLimiter &a, hipStream_t stream);
+
+// The loudness and true-peak meters of s2r_fill_master: one launch behind the limiter (or the master kernel), the last
+// of a master fill that finds the meter set.  It reads the stems from the master's device stage and the master from device memory —
+// whoever writes the master last writes it there in such a call, never into the pinned output —, copies the master to the pinned
+// output itself, and writes the call's hop rows, its true-peak partials and the OTHER copy of the state; the host flips the copies
+// after a synchronise that succeeded.  `pos` is the host's: the frames of the hop under way when the call starts.
+#define S2R_LOUDNESS_TILE 256u                      // frames the walk's workgroup stages at a time, one tile ahead of the walk
+#define S2R_LOUDNESS_BLOCK 256u                     // frames of one true-peak workgroup, one per thread
+#define S2R_LOUDNESS_HALF_TAPS 33u                  // (S2R_DRIVE_TAPS + 1) / 2
+struct S2rLoudness {
+    const float *stems;           // [n_buses][2 * frames] in device memory: the master kernel's input
+    const float *master;          // [frames][2] in device memory: what the limiter, or without one the master kernel, wrote
+    float *out;                   // interleaved L, R: 2 * frames floats (mapped host memory)
+    const float *state;           // [S2R_LOUDNESS_STATE]: the state the call starts from
+    float *next;                  // ... and the state it leaves (never the buffer above)
+    float *rows;                  // [(pos + frames) / hop][S2R_LOUDNESS_CHANNELS] (mapped host memory): the hops the call completes
+    float *peaks;                 // [ceil(frames / S2R_LOUDNESS_BLOCK)][2] (mapped host memory): each workgroup's true peak, L and R
+    float c[10];                  // the two biquads, (b0, b1, b2, a1, a2) each
+    float g[S2R_LOUDNESS_HALF_TAPS];                 // taps 0 .. 32 of the interpolator g = 4 h, which is symmetric on bits
+    uint32_t n_buses, frames, hop, pos;
+};
+hipError_t s2r_launch_loudness(const S2rLoudness &a, hipStream_t stream);

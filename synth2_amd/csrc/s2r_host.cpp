@@ -3334,6 +3334,104 @@ int s2r_get_limiter_meters(const s2r_synth *s, float *min_gain, float *out_peak)
     return S2R_OK;
 }
 
+// ---- the loudness and true-peak meters behind the limiter ----
+int s2r_set_master_loudness(s2r_synth *s, const float coeffs[10], uint32_t hop, uint32_t max_hops) {
+    if (!loudness_in_range(coeffs, hop, max_hops))
+        return set_err(s, S2R_ERR_PATCH_RANGE, "master loudness: hop %u, %u hops: ten finite coefficients, the hop in %u .. %u, the hops kept in %u .. %u", hop, max_hops,
+                       S2R_LOUDNESS_MIN_HOP, S2R_LOUDNESS_MAX_HOP, S2R_LOUDNESS_MIN_HOPS, S2R_LOUDNESS_MAX_HOPS);
+    S2R_TRY(post_handle(s, "s2r_set_master_loudness", "the loudness meter is"));
+    if (!coeffs) return set_err(s, S2R_ERR_INVALID, "s2r_set_master_loudness: no coefficients");
+    s->post.set_loudness(coeffs, hop, max_hops);
+    return S2R_OK;
+}
+
+int s2r_clear_master_loudness(s2r_synth *s) {
+    S2R_TRY(post_handle(s, "s2r_clear_master_loudness", "the loudness meter is"));
+    s->post.set_loudness(nullptr, 0, 0);
+    return S2R_OK;
+}
+
+int s2r_get_master_loudness(const s2r_synth *s, float coeffs[10], uint32_t *hop, uint32_t *max_hops, size_t *n_hops) {
+    if (!s || !s->kids.empty() || s->parent) return S2R_ERR_INVALID;
+    const S2rPostChain::Loudness &ld = s->post.loud;
+    if (coeffs) std::memcpy(coeffs, ld.c, sizeof ld.c);
+    put(hop, ld.hop); put(max_hops, ld.max_hops); put(n_hops, ld.n_hops());
+    return S2R_OK;
+}
+
+// the guard of the entries that need the meter set
+static int loudness_on(const s2r_synth *s, const char *who) {
+    S2R_TRY(post_handle(s, who, "the loudness meter is"));
+    if (!s->post.loud.hop) return set_err(const_cast<s2r_synth *>(s), S2R_ERR_INVALID, "%s: no loudness meter is set", who);
+    return S2R_OK;
+}
+
+int s2r_reset_master_loudness(s2r_synth *s) {
+    S2R_TRY(loudness_on(s, "s2r_reset_master_loudness"));
+    s->post.reset_loudness();
+    return S2R_OK;
+}
+
+int s2r_get_loudness(const s2r_synth *s, uint32_t programme, double out[3]) {
+    if (programme >= S2R_LOUDNESS_PROGRAMMES) return S2R_ERR_PATCH_RANGE;
+    if (!s || !s->kids.empty() || s->parent || !s->post.loud.hop || !out) return S2R_ERR_INVALID;
+    const S2rPostChain::Loudness &ld = s->post.loud;
+    return s2r_loudness_readings(ld.stored(), ld.n_hops(), ld.hop, programme, out);
+}
+
+int s2r_get_true_peak(const s2r_synth *s, float last[2], float held[2]) {
+    if (!s || !s->kids.empty() || s->parent || !s->post.loud.hop) return S2R_ERR_INVALID;
+    const S2rPostChain::Loudness &ld = s->post.loud;
+    if (last) { last[0] = ld.tp_last[0]; last[1] = ld.tp_last[1]; }
+    if (held) { held[0] = ld.tp_held[0]; held[1] = ld.tp_held[1]; }
+    return S2R_OK;
+}
+
+int s2r_get_loudness_state(s2r_synth *s, float *state, size_t capacity, uint32_t *pos) {
+    S2R_TRY(loudness_on(s, "s2r_get_loudness_state"));
+    S2rPostChain::Loudness &ld = s->post.loud;
+    if (capacity < S2R_LOUDNESS_STATE) return set_err(s, S2R_ERR_INVALID, "s2r_get_loudness_state: the state is %u floats, not %zu", S2R_LOUDNESS_STATE, capacity);
+    if (!state) return set_err(s, S2R_ERR_INVALID, "s2r_get_loudness_state: null buffer");
+    if (!ld.host_valid) {                                        // the device holds it: fetch it once, and keep it until the next fill
+        if (s->ring_count) return set_err(s, S2R_ERR_INVALID, "s2r_get_loudness_state with fills of s2r_fill_begin in flight: s2r_fill_end first");
+        S2R_QUIESCE(s);
+        S2R_HIP(s, hipSetDevice(s->device));
+        S2R_HIP(s, s->post.fetch_loudness_state(post_ctx(s)));
+    }
+    std::memcpy(state, ld.host.data(), S2R_LOUDNESS_STATE * sizeof(float));
+    put(pos, ld.pos);
+    return S2R_OK;
+}
+
+int s2r_set_loudness_state(s2r_synth *s, const float *state, size_t count, uint32_t pos) {
+    S2R_TRY(loudness_on(s, "s2r_set_loudness_state"));
+    if (count != S2R_LOUDNESS_STATE) return set_err(s, S2R_ERR_INVALID, "s2r_set_loudness_state: the state is %u floats, not %zu", S2R_LOUDNESS_STATE, count);
+    if (!state) return set_err(s, S2R_ERR_INVALID, "s2r_set_loudness_state: null buffer");
+    if (pos >= s->post.loud.hop) return set_err(s, S2R_ERR_PATCH_RANGE, "s2r_set_loudness_state: position %u, below the hop of %u", pos, s->post.loud.hop);
+    s->post.set_loudness_state(state, pos);
+    return S2R_OK;
+}
+
+int s2r_get_loudness_hops(const s2r_synth *s, float *rows, size_t capacity, size_t *n_hops) {
+    S2R_TRY(loudness_on(s, "s2r_get_loudness_hops"));
+    const S2rPostChain::Loudness &ld = s->post.loud;
+    const size_t n = ld.n_hops() * S2R_LOUDNESS_CHANNELS;
+    if (capacity < n || (n && !rows)) return set_err(const_cast<s2r_synth *>(s), S2R_ERR_INVALID, "s2r_get_loudness_hops: the rows are %zu floats, the buffer holds %zu", n, rows ? capacity : (size_t)0);
+    if (n) std::memcpy(rows, ld.stored(), n * sizeof(float));
+    put(n_hops, ld.n_hops());
+    return S2R_OK;
+}
+
+int s2r_set_loudness_hops(s2r_synth *s, const float *rows, size_t n_hops, size_t count) {
+    S2R_TRY(loudness_on(s, "s2r_set_loudness_hops"));
+    S2rPostChain::Loudness &ld = s->post.loud;
+    if (n_hops > ld.max_hops) return set_err(s, S2R_ERR_PATCH_RANGE, "s2r_set_loudness_hops: %zu hops, at most the %u the meter keeps", n_hops, ld.max_hops);
+    if (count != n_hops * S2R_LOUDNESS_CHANNELS || (count && !rows))
+        return set_err(s, S2R_ERR_INVALID, "s2r_set_loudness_hops: %zu hops are %zu floats, not %zu", n_hops, n_hops * S2R_LOUDNESS_CHANNELS, rows ? count : (size_t)0);
+    ld.hops.assign(rows, rows + count); ld.first = 0;
+    return S2R_OK;
+}
+
 int s2r_fill_oversampled(s2r_synth *s, float *mono_out, size_t frames, uint32_t sample_rate_hz) {
     if (!s) return S2R_ERR_INVALID;
     if (sample_rate_hz > 0xffffffffu / S2R_OVERSAMPLE) return set_err(s, S2R_ERR_INVALID, "sample rate too high to oversample");
@@ -3821,6 +3919,8 @@ extern "C" float s2r_debug_bus_fx_ms(const s2r_synth *s) { return s && s->timing
 extern "C" float s2r_debug_master_ms(const s2r_synth *s) { return s && s->timing ? s->post.master.timer.ms : -1.0f; }
 // ... and of the limiter kernel in that fill: 0 when it ran none (tools/limiter_time.py)
 extern "C" float s2r_debug_limiter_ms(const s2r_synth *s) { return s && s->timing ? s->post.limiter.timer.ms : -1.0f; }
+// ... and of the loudness kernel in that fill: 0 when it ran none (tools/loudness_time.py)
+extern "C" float s2r_debug_loudness_ms(const s2r_synth *s) { return s && s->timing ? s->post.loud.timer.ms : -1.0f; }
 
 extern "C" uint32_t s2r_debug_read_stamps(s2r_synth *s, unsigned long long *out, uint32_t max_waves) {
 #if defined(S2R_STAMPS)

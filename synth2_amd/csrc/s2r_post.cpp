@@ -1,4 +1,4 @@
-// s2r_post.cpp — the post-mix chain (s2r_post.h): the eight bus stages (EQs, dynamics, drives, flangers, choruses, delays, reverbs, rooms), master section, master limiter.  Compiled with hipcc, -ffp-contract=off.
+// s2r_post.cpp — the post-mix chain (s2r_post.h): the eight bus stages (EQs, dynamics, drives, flangers, choruses, delays, reverbs, rooms), master section, master limiter, loudness meters.  Compiled with hipcc, -ffp-contract=off.
 #include "s2r_post.h"
 #include "s2r_rules.h"
 
@@ -82,9 +82,16 @@ hipError_t S2rPostChain::prepare(const S2rPostCtx &c, uint32_t n_buses, uint32_t
         for (float *&p : limiter.state) if (!p) POST_HIP(hipMalloc((void **)&p, kLimState * sizeof(float)));
         POST_HIP(pinned_rows(limiter.partials, limiter.partials_dev, (size_t)((c.max_frames + S2R_LIMITER_BLOCK - 1u) / S2R_LIMITER_BLOCK) * 2u));
     }
+    if (metered(call)) {                                         // the meter's input, the two copies of its state, its pinned hop rows and peaks
+        if (!loud.in) POST_HIP(hipMalloc((void **)&loud.in, (size_t)2 * c.max_frames * sizeof(float)));
+        for (float *&p : loud.state) if (!p) POST_HIP(hipMalloc((void **)&p, S2R_LOUDNESS_STATE * sizeof(float)));
+        POST_HIP(pinned_rows(loud.rows, loud.rows_dev, (size_t)(c.max_frames / S2R_LOUDNESS_MIN_HOP + 1u) * S2R_LOUDNESS_CHANNELS));
+        POST_HIP(pinned_rows(loud.peaks, loud.peaks_dev, (size_t)((c.max_frames + S2R_LOUDNESS_BLOCK - 1u) / S2R_LOUDNESS_BLOCK) * 2u));
+    }
     float *own[S2R_BUS_STAGES];
     for (int k = 0; k < S2R_BUS_STAGES; k++) own[k] = stage[k].buffer;
-    call.route = s2r_post_route(call, own, master.stage, limiter.in, c.bus_out_dev, c.out_host_dev);
+    // (with the meter on, whoever writes the master last writes it into the meter's input, and the meter's kernel writes the pinned output)
+    call.route = s2r_post_route(call, own, master.stage, limiter.in, c.bus_out_dev, metered(call) ? loud.in : c.out_host_dev);
     return hipSuccess;
 }
 
@@ -115,6 +122,16 @@ hipError_t S2rPostChain::launch(const S2rPostCtx &c, const S2rPostCall &call) {
         a.x = r.limiter_in; a.out = r.limiter_out; a.xh = cur; a.gh = cur + kLimXh; a.xh_next = next; a.gh_next = next + kLimXh;
         a.partials = lm.partials_dev; a.frames = call.frames; a.lookahead = lm.lookahead; a.hold = lm.hold; a.ceiling = lm.ceiling;
         POST_TIMED(c, lm.timer, s2r_launch_limiter(a, c.stream));
+    }
+    if (metered(call)) {                                         // behind whoever wrote the master last: the next state goes into the other copy
+        Loudness &ld = loud;
+        float *cur = ld.state[ld.cur], *next = ld.state[ld.cur ^ 1];
+        if (ld.host_valid) POST_HIP(hipMemcpyAsync(cur, ld.host.data(), S2R_LOUDNESS_STATE * sizeof(float), hipMemcpyHostToDevice, c.stream));
+        S2rLoudness a{};
+        a.stems = r.master_in; a.master = call.limited ? r.limiter_out : r.master_out; a.out = c.out_host_dev; a.state = cur; a.next = next;
+        a.rows = ld.rows_dev; a.peaks = ld.peaks_dev; a.n_buses = call.n_buses; a.frames = call.frames; a.hop = ld.hop; a.pos = ld.pos;
+        std::memcpy(a.c, ld.c, sizeof a.c); std::memcpy(a.g, drive_taps().g, sizeof a.g);
+        POST_TIMED(c, ld.timer, s2r_launch_loudness(a, c.stream));
     }
     return hipSuccess;
 }
@@ -264,6 +281,26 @@ void S2rPostChain::commit(const S2rPostCall &call) {
         }
         lm.min_gain = mn; lm.out_peak = pk; lm.metered = true;
     }
+    if (metered(call)) {                                         // the state has moved on; the call's hops join the rows, its peaks the held ones
+        Loudness &ld = loud;
+        ld.cur ^= 1; ld.host_valid = false;
+        const uint64_t at = (uint64_t)ld.pos + call.frames;
+        ld.append(ld.rows, (size_t)(at / ld.hop));
+        ld.pos = (uint32_t)(at % ld.hop);
+        const uint32_t n_blocks = (call.frames + S2R_LOUDNESS_BLOCK - 1u) / S2R_LOUDNESS_BLOCK;
+        for (uint32_t ch = 0; ch < 2u; ch++) {
+            float pk = ld.peaks[ch];
+            for (uint32_t k = 1; k < n_blocks; k++) pk = ld.peaks[(size_t)k * 2u + ch] > pk ? ld.peaks[(size_t)k * 2u + ch] : pk;
+            ld.tp_last[ch] = pk;
+            ld.tp_held[ch] = pk > ld.tp_held[ch] ? pk : ld.tp_held[ch];
+        }
+    }
+}
+
+void S2rPostChain::Loudness::append(const float *new_rows, size_t n) {
+    hops.insert(hops.end(), new_rows, new_rows + n * S2R_LOUDNESS_CHANNELS);
+    if (n_hops() > max_hops) first += n_hops() - max_hops;
+    if (first > max_hops) { hops.erase(hops.begin(), hops.begin() + first * S2R_LOUDNESS_CHANNELS); first = 0; }      // (amortised: once per max_hops rows dropped)
 }
 
 // a stage that the fill could have run and did not reads 0; a panned fill leaves all ten values alone, a bus fill the master's two
@@ -273,6 +310,8 @@ hipError_t S2rPostChain::read_timers(const S2rPostCall &call) {
         POST_HIP(master.timer.read());
         limiter.timer.ms = 0.0f;
         if (call.limited) POST_HIP(limiter.timer.read());
+        loud.timer.ms = 0.0f;
+        if (metered(call)) POST_HIP(loud.timer.read());
     }
     return hipSuccess;
 }
@@ -281,9 +320,9 @@ void S2rPostChain::release() {
     for (uint32_t b = 0; b < S2R_MAX_BUSES; b++) { drop(eq[b]); drop(dyn[b]); drop(drive[b]); drop(flanger[b]); drop(chorus[b]); drop(delay[b]); drop(fx[b]); drop(room[b]); }
     for (Stem &st : stage) { if (st.buffer) (void)hipFree(st.buffer); st.timer.destroy(); }
     // ... and what is neither a line nor a stage's buffer
-    for (float *p : {dyn_curves, drive_curves, master.stage, limiter.state[0], limiter.state[1], limiter.in}) if (p) (void)hipFree(p);
-    for (float *p : {dyn_meter, master.partials, limiter.partials}) if (p) (void)hipHostFree(p);
-    for (S2rPostTimer *t : {&master.timer, &limiter.timer}) t->destroy();
+    for (float *p : {dyn_curves, drive_curves, master.stage, limiter.state[0], limiter.state[1], limiter.in, loud.state[0], loud.state[1], loud.in}) if (p) (void)hipFree(p);
+    for (float *p : {dyn_meter, master.partials, limiter.partials, loud.rows, loud.peaks}) if (p) (void)hipHostFree(p);
+    for (S2rPostTimer *t : {&master.timer, &limiter.timer, &loud.timer}) t->destroy();
 }
 
 hipError_t S2rPostChain::set_eq(const S2rPostCtx &c, uint32_t bus, uint32_t n_bands, const float *coeffs) {
@@ -463,5 +502,34 @@ hipError_t S2rPostChain::fetch_limiter_state(const S2rPostCtx &c) {
     POST_HIP(hipStreamSynchronize(c.stream));
     lm.host.swap(st);
     lm.host_valid = true;
+    return hipSuccess;
+}
+
+void S2rPostChain::set_loudness(const float *coeffs, uint32_t hop, uint32_t max_hops) {
+    Loudness &ld = loud;
+    if (!coeffs) { ld.hop = ld.max_hops = 0; std::memset(ld.c, 0, sizeof ld.c); }
+    else { std::memcpy(ld.c, coeffs, sizeof ld.c); ld.hop = hop; ld.max_hops = max_hops; }
+    reset_loudness();
+    if (!coeffs) { ld.host.clear(); ld.host_valid = false; }
+}
+
+void S2rPostChain::reset_loudness() {
+    Loudness &ld = loud;
+    ld.host.assign(S2R_LOUDNESS_STATE, 0.0f); ld.host_valid = true; ld.pos = 0;
+    ld.hops.clear(); ld.first = 0;
+    for (int ch = 0; ch < 2; ch++) ld.tp_last[ch] = ld.tp_held[ch] = 0.0f;
+}
+
+void S2rPostChain::set_loudness_state(const float *state, uint32_t pos) {
+    loud.host.assign(state, state + S2R_LOUDNESS_STATE);
+    loud.host_valid = true; loud.pos = pos;
+}
+
+hipError_t S2rPostChain::fetch_loudness_state(const S2rPostCtx &c) {
+    std::vector<float> st(S2R_LOUDNESS_STATE);
+    POST_HIP(hipMemcpyAsync(st.data(), loud.state[loud.cur], S2R_LOUDNESS_STATE * sizeof(float), hipMemcpyDeviceToHost, c.stream));
+    POST_HIP(hipStreamSynchronize(c.stream));
+    loud.host.swap(st);
+    loud.host_valid = true;
     return hipSuccess;
 }

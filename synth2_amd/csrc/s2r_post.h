@@ -1,7 +1,7 @@
 // s2r_post.h — the chain behind the bus mixdown of s2r_fill_buses and s2r_fill_master: the eight bus stages in the order of
 // S2rBusStage (s2r_post_route.h) — the buses' equalisers, their dynamics (4.22), drives (4.24), flangers (4.25),
 // choruses (4.20), feedback delays (4.19), convolution reverbs (4.16) and rooms (4.23) —, then the master section (4.17) and the master
-// limiter (4.18).  The chain owns what the ten stages own and knows nothing of the handle: its functions take a S2rPostCtx and return
+// limiter (4.18), and behind it the loudness and true-peak meters (4.26).  The chain owns what these stages own and knows nothing of the handle: its functions take a S2rPostCtx and return
 // the HIP error.  Per call: prepare, launch, — the caller's synchronise — commit, read_timers.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -148,6 +148,30 @@ struct S2rPostChain {
         size_t n_x() const { return 2u * (size_t)lookahead; }
         size_t n_g() const { return 2u * (size_t)lookahead + hold; }
     } limiter;
+    // The loudness and true-peak meters (s2r_set_master_loudness).  Nothing is allocated before the first master fill
+    // that finds the meter set, and a handle on which it never was passes the pointers and makes the launches it always did.
+    struct Loudness {
+        float c[10] = {};
+        uint32_t hop = 0, max_hops = 0;          // hop 0: off
+        // The state's S2R_LOUDNESS_STATE floats live in `host` while host_valid (set, reset or restored since the last fill) and in
+        // state[cur] otherwise, as the limiter's; `pos`, the frames of the hop under way, is the host's alone and a kernel argument.
+        std::vector<float> host;
+        bool host_valid = false;
+        uint32_t pos = 0;
+        float *state[2] = {nullptr, nullptr};    // device memory, S2R_LOUDNESS_STATE floats each
+        int cur = 0;
+        float *in = nullptr;                     // [2 * max_frames] in device memory: where the master's last writer writes when the meter is on
+        float *rows = nullptr, *rows_dev = nullptr;              // pinned and device-mapped: [max_frames / 16 + 1][S2R_LOUDNESS_CHANNELS]
+        float *peaks = nullptr, *peaks_dev = nullptr;            // pinned and device-mapped: [ceil(max_frames / S2R_LOUDNESS_BLOCK)][2]
+        std::vector<float> hops;                 // the hop rows kept, oldest first, from row `first` on: at most max_hops of them
+        size_t first = 0;
+        float tp_last[2] = {0.0f, 0.0f}, tp_held[2] = {0.0f, 0.0f};
+        S2rPostTimer timer;                      // around the loudness kernel of the last master fill: 0 when it ran none (tools/loudness_time.py)
+        size_t n_hops() const { return hops.size() / S2R_LOUDNESS_CHANNELS - first; }
+        const float *stored() const { return hops.data() + first * S2R_LOUDNESS_CHANNELS; }
+        void append(const float *new_rows, size_t n);            // ... and drop the oldest past max_hops
+    } loud;
+    bool metered(const S2rPostCall &call) const { return call.master && loud.hop != 0; }
     // one fill: what it runs, its once-only allocations and its route; the launches in order, each between its timer's marks; after
     // the synchronise that succeeded, and only then, histories, applied values and state move on and the meters fold
     hipError_t prepare(const S2rPostCtx &c, uint32_t n_buses, uint32_t frames, bool master_fill, bool stems, S2rPostCall &call);
@@ -187,4 +211,8 @@ struct S2rPostChain {
     void set_limiter(float ceiling, uint32_t lookahead, uint32_t hold);      // (0, 0, 0): off
     void set_limiter_state(const float *xh, const float *gh);
     hipError_t fetch_limiter_state(const S2rPostCtx &c);            // the device's copy into `host`, kept until the next fill
+    void set_loudness(const float *coeffs, uint32_t hop, uint32_t max_hops);  // coeffs null: off; else on, from the initial state
+    void reset_loudness();                                          // state, rows and held true peak; the parameters stay
+    void set_loudness_state(const float *state, uint32_t pos);
+    hipError_t fetch_loudness_state(const S2rPostCtx &c);           // the device's copy into `host`, kept until the next fill
 };

@@ -529,3 +529,125 @@ int s2r_flanger_reference(float base, float depth, uint32_t phase_inc, uint32_t 
 }
 
 }  // extern "C"
+
+// ---- the master's loudness and true-peak meters: BS.1770's pre-filter, hop sums, and the readings from the hop rows ----
+extern "C" {
+
+int s2r_loudness_design(double sample_rate, float coeffs[10]) {
+    if (!(sample_rate >= S2R_LOUDNESS_MIN_RATE && sample_rate <= S2R_LOUDNESS_MAX_RATE)) return S2R_ERR_PATCH_RANGE;
+    if (!coeffs) return S2R_ERR_INVALID;
+    const double PI = 3.14159265358979323846;
+    {                                                            // stage 1: the high shelf
+        const double f0 = 1681.974450955533, G = 3.999843853973347, Q = 0.7071752369554196;
+        const double K = std::tan(PI * f0 / sample_rate), Vh = std::pow(10.0, G / 20.0), Vb = std::pow(Vh, 0.4996667741545416);
+        const double a0 = 1.0 + K / Q + K * K;
+        coeffs[0] = (float)((Vh + Vb * K / Q + K * K) / a0);
+        coeffs[1] = (float)(2.0 * (K * K - Vh) / a0);
+        coeffs[2] = (float)((Vh - Vb * K / Q + K * K) / a0);
+        coeffs[3] = (float)(2.0 * (K * K - 1.0) / a0);
+        coeffs[4] = (float)((1.0 - K / Q + K * K) / a0);
+    }
+    {                                                            // stage 2: the high-pass
+        const double f0 = 38.13547087602444, Q = 0.5003270373238773;
+        const double K = std::tan(PI * f0 / sample_rate);
+        const double a0 = 1.0 + K / Q + K * K;
+        coeffs[5] = 1.0f; coeffs[6] = -2.0f; coeffs[7] = 1.0f;
+        coeffs[8] = (float)(2.0 * (K * K - 1.0) / a0);
+        coeffs[9] = (float)((1.0 - K / Q + K * K) / a0);
+    }
+    return S2R_OK;
+}
+
+// one stage, one frame: the nine operations of a band of s2r_eq_reference
+static inline float loudness_stage(const float *q, float x, float &s1, float &s2) {
+    const float p0 = q[0] * x;
+    const float y = p0 + s1;
+    const float p1 = q[1] * x, r1 = q[3] * y;
+    const float d1 = p1 - r1;
+    const float p2 = q[2] * x, r2 = q[4] * y;
+    s1 = d1 + s2;
+    s2 = p2 - r2;
+    return y;
+}
+
+int s2r_loudness_reference(const float coeffs[10], uint32_t hop, const float *stems, uint32_t n_buses, const float *master_lr, uint32_t frames,
+                           float *state, uint32_t *pos, float *rows, size_t rows_capacity, size_t *n_rows, float true_peak[2]) {
+    if (!loudness_in_range(coeffs, hop, S2R_LOUDNESS_MIN_HOPS) || n_buses > S2R_MAX_BUSES || (pos && *pos >= hop)) return S2R_ERR_PATCH_RANGE;
+    if (!coeffs || !state || !pos || !n_rows || (frames && (!master_lr || (n_buses && !stems)))) return S2R_ERR_INVALID;
+    const size_t made = ((size_t)*pos + frames) / hop;
+    if (made && (!rows || rows_capacity < made * S2R_LOUDNESS_CHANNELS)) return S2R_ERR_INVALID;
+    const size_t N = frames;
+    float *const filt = state + S2R_LOUD_FILT, *const e = state + S2R_LOUD_SUMS, *const hist = state + S2R_LOUD_HIST;
+    uint32_t at = *pos;
+    size_t row = 0;
+    for (size_t n = 0; n < N; n++) {
+        for (uint32_t q = 0; q < S2R_LOUDNESS_CHANNELS; q++) {
+            const uint32_t p = q >> 1, c = q & 1u;
+            const float v = p == S2R_MAX_BUSES ? master_lr[2 * n + c] : (p < n_buses ? stems[2 * (p * N + n) + c] : 0.0f);
+            float *const f = filt + 4 * q;
+            const float y1 = loudness_stage(coeffs, v, f[0], f[1]);
+            const float y2 = loudness_stage(coeffs + 5, y1, f[2], f[3]);
+            const float z = y2 * y2;
+            e[q] = e[q] + z;
+        }
+        if (++at == hop) {
+            for (uint32_t q = 0; q < S2R_LOUDNESS_CHANNELS; q++) { rows[row * S2R_LOUDNESS_CHANNELS + q] = e[q]; e[q] = 0.0f; }
+            row++;
+            at = 0;
+        }
+    }
+    // the true peak: x as the state's 16 frames followed by the call (frame n at 16 + n)
+    const S2rDriveTaps &taps = drive_taps();
+    constexpr size_t H = S2R_LOUD_HIST_FRAMES;
+    float tp[2] = {0.0f, 0.0f};
+    std::vector<float> x(H + N);
+    for (uint32_t c = 0; c < 2u; c++) {
+        for (size_t k = 0; k < H; k++) x[k] = hist[2 * k + c];
+        for (size_t n = 0; n < N; n++) x[H + n] = master_lr[2 * n + c];
+        for (size_t n = 0; n < N; n++) {
+            const float a = std::fabs(x[H + n]);
+            tp[c] = a > tp[c] ? a : tp[c];
+            for (uint32_t p = 0; p < S2R_DRIVE_OVERSAMPLE; p++) {
+                float u = 0.0f;
+                for (uint32_t j = 0; p + 4u * j < S2R_DRIVE_TAPS; j++) {
+                    const float t = taps.g[p + 4u * j] * x[H + n - j];
+                    u = u + t;
+                }
+                const float au = std::fabs(u);
+                tp[c] = au > tp[c] ? au : tp[c];
+            }
+        }
+        for (size_t k = 0; k < H; k++) hist[2 * k + c] = x[N + k];
+    }
+    if (true_peak) { true_peak[0] = tp[0]; true_peak[1] = tp[1]; }
+    *pos = at;
+    *n_rows = row;
+    return S2R_OK;
+}
+
+int s2r_loudness_readings(const float *rows, size_t n_hops, uint32_t hop, uint32_t programme, double out[3]) {
+    if (!loudness_hop_in_range(hop) || programme >= S2R_LOUDNESS_PROGRAMMES) return S2R_ERR_PATCH_RANGE;
+    if (!out || (n_hops && !rows)) return S2R_ERR_INVALID;
+    const double ninf = -HUGE_VAL;
+    auto t = [&](size_t i) { const float *r = rows + i * S2R_LOUDNESS_CHANNELS + 2u * programme; return (double)r[0] + (double)r[1]; };
+    auto loud = [](double m) { return -0.691 + 10.0 * std::log10(m); };          // (log10(0) is -inf: silence reads -inf)
+    auto block = [&](size_t j) { return (((t(j - 3) + t(j - 2)) + t(j - 1)) + t(j)) / (4.0 * hop); };
+    out[0] = out[1] = out[2] = ninf;
+    if (n_hops >= 4) out[0] = loud(block(n_hops - 1));
+    if (n_hops >= 30) {
+        double s = 0.0;
+        for (size_t i = n_hops - 30; i < n_hops; i++) s = s + t(i);
+        out[1] = loud(s / (30.0 * hop));
+    }
+    double sum = 0.0; size_t kept = 0;
+    for (size_t j = 3; j < n_hops; j++) { const double m = block(j); if (loud(m) > -70.0) { sum = sum + m; kept++; } }
+    if (kept) {
+        const double rel = loud(sum / (double)kept) - 10.0;
+        sum = 0.0; kept = 0;
+        for (size_t j = 3; j < n_hops; j++) { const double m = block(j), l = loud(m); if (l > -70.0 && l > rel) { sum = sum + m; kept++; } }
+        if (kept) out[2] = loud(sum / (double)kept);
+    }
+    return S2R_OK;
+}
+
+}  // extern "C"

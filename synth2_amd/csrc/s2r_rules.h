@@ -127,6 +127,18 @@ static inline bool flanger_in_range(float base, float depth, float feedback, flo
 // H = floor(fl(base + depth)) + 1 for a pair in range: 33 .. 4096
 static inline uint32_t flanger_history(float base, float depth) { volatile float top = base + depth; return (uint32_t)top + 1u; }
 
+// the master's loudness meter: ten finite coefficients, the hop and the window of hop rows in their ranges.  Null
+// coefficients pass: the caller refuses them by another name.
+static inline bool loudness_hop_in_range(uint32_t hop) { return hop >= S2R_LOUDNESS_MIN_HOP && hop <= S2R_LOUDNESS_MAX_HOP; }
+static inline bool loudness_in_range(const float *coeffs, uint32_t hop, uint32_t max_hops) {
+    for (uint32_t i = 0; i < 10u && coeffs; i++) if (!std::isfinite(coeffs[i])) return false;
+    return loudness_hop_in_range(hop) && max_hops >= S2R_LOUDNESS_MIN_HOPS && max_hops <= S2R_LOUDNESS_MAX_HOPS;
+}
+// where the state's parts sit among its S2R_LOUDNESS_STATE floats: filters [18][2][2], hop sums [18], the master's last frames [16][2]
+enum { S2R_LOUD_FILT = 0, S2R_LOUD_SUMS = 72, S2R_LOUD_HIST = 90, S2R_LOUD_HIST_FRAMES = 16 };
+static_assert(S2R_LOUD_HIST + 2 * S2R_LOUD_HIST_FRAMES == S2R_LOUDNESS_STATE && S2R_LOUD_SUMS == 4 * S2R_LOUDNESS_CHANNELS, "the layout s2r.h states");
+static_assert(4 * S2R_LOUD_HIST_FRAMES + 1 == S2R_DRIVE_TAPS, "phase 0 of the interpolator reaches 16 frames back");
+
 // The voice mixer's gain rules, inline: the host's per-voice loops compile them in — a call per voice into s2r_rules.cpp showed as 10
 // to 15 us of host time per fill of 65 536 voices (profiles/r12/post_chain.txt).  s2r_rules.cpp exports them under their s2r.h names.
 static inline float rule_voice_pan(float pan, float key_spread, uint8_t note) {

@@ -59,6 +59,11 @@ METER_BLOCK = 256                           # S2R_METER_BLOCK
 LIMITER_MAX_LOOKAHEAD = 1024                # S2R_LIMITER_MAX_LOOKAHEAD
 LIMITER_MAX_HOLD = 4096                     # S2R_LIMITER_MAX_HOLD
 LIMITER_CEILING_LOG2 = 20                   # S2R_LIMITER_CEILING_LOG2
+LOUDNESS_PROGRAMMES = 9                     # S2R_LOUDNESS_PROGRAMMES: the buses, then the master
+LOUDNESS_CHANNELS = 18                      # S2R_LOUDNESS_CHANNELS
+LOUDNESS_STATE = 122                        # S2R_LOUDNESS_STATE
+LOUDNESS_MIN_HOP, LOUDNESS_MAX_HOP = 16, 1 << 20      # S2R_LOUDNESS_MIN_HOP, S2R_LOUDNESS_MAX_HOP
+LOUDNESS_MIN_HOPS, LOUDNESS_MAX_HOPS = 30, 1 << 18    # S2R_LOUDNESS_MIN_HOPS, S2R_LOUDNESS_MAX_HOPS
 
 
 class S2rError(RuntimeError):
@@ -293,6 +298,20 @@ def load_library():
         "s2r_set_limiter_state": (C.c_int, [H, _f32p, C.c_size_t, _f32p, C.c_size_t]),
         "s2r_get_limiter_meters": (C.c_int, [H, _f32p, _f32p]),
         "s2r_limiter_reference": (C.c_int, [_f32p, C.c_uint32, C.c_float, C.c_uint32, C.c_uint32, _f32p, _f32p, _f32p, _f32p]),
+        "s2r_set_master_loudness": (C.c_int, [H, _f32p, C.c_uint32, C.c_uint32]),
+        "s2r_clear_master_loudness": (C.c_int, [H]),
+        "s2r_get_master_loudness": (C.c_int, [H, _f32p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_size_t)]),
+        "s2r_reset_master_loudness": (C.c_int, [H]),
+        "s2r_get_loudness": (C.c_int, [H, C.c_uint32, C.POINTER(C.c_double)]),
+        "s2r_get_true_peak": (C.c_int, [H, _f32p, _f32p]),
+        "s2r_get_loudness_state": (C.c_int, [H, _f32p, C.c_size_t, C.POINTER(C.c_uint32)]),
+        "s2r_set_loudness_state": (C.c_int, [H, _f32p, C.c_size_t, C.c_uint32]),
+        "s2r_get_loudness_hops": (C.c_int, [H, _f32p, C.c_size_t, C.POINTER(C.c_size_t)]),
+        "s2r_set_loudness_hops": (C.c_int, [H, _f32p, C.c_size_t, C.c_size_t]),
+        "s2r_loudness_reference": (C.c_int, [_f32p, C.c_uint32, _f32p, C.c_uint32, _f32p, C.c_uint32, _f32p, C.POINTER(C.c_uint32), _f32p, C.c_size_t,
+                                             C.POINTER(C.c_size_t), _f32p]),
+        "s2r_loudness_readings": (C.c_int, [_f32p, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(C.c_double)]),
+        "s2r_loudness_design": (C.c_int, [C.c_double, _f32p]),
         "s2r_fill_device": (C.c_int, [H, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
         "s2r_fill_device_root": (C.c_int, [H, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
         "s2r_sum_partials_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_size_t, C.c_void_p, C.c_void_p]),
@@ -702,6 +721,54 @@ def limiter_reference(x, ceiling, lookahead, hold, xh=None, gh=None):
     if rc != S2R_OK:
         raise S2rError(rc, load_library().s2r_status_string(rc).decode())
     return y, gain, xh, gh
+
+
+def _rule_check(rc):
+    if rc != S2R_OK:
+        raise S2rError(rc, load_library().s2r_status_string(rc).decode())
+
+
+def loudness_design(sample_rate=48000.0):
+    """BS.1770's K-weighting pre-filter at `sample_rate` (s2r_loudness_design): [2, 5] float32, the high shelf and the high-pass, each
+    (b0, b1, b2, a1, a2)"""
+    c = np.empty((2, 5), dtype=np.float32)
+    _rule_check(load_library().s2r_loudness_design(float(sample_rate), c.ctypes.data_as(_f32p)))
+    return c
+
+
+def loudness_reference(coeffs, hop, stems, master, state=None, pos=0):
+    """the loudness meter's device rule on the host (s2r_loudness_reference): stems [n_buses, frames, 2] float32 (None: no buses),
+    master [frames, 2]; state [LOUDNESS_STATE] and pos what the call starts from (None: the initial state).  Returns (rows [k, 18] —
+    the hops the call completes —, state, pos, true_peak [2]); the arguments are not modified."""
+    coeffs = np.ascontiguousarray(coeffs, dtype=np.float32).reshape(-1)
+    master = np.ascontiguousarray(master, dtype=np.float32)
+    if coeffs.size != 10 or master.ndim != 2 or master.shape[1] != 2:
+        raise ValueError("loudness_reference: coeffs is [2, 5], master is [frames, 2]")
+    frames = master.shape[0]
+    if stems is None:
+        stems = np.zeros((0, frames, 2), dtype=np.float32)
+    stems = np.ascontiguousarray(stems, dtype=np.float32)
+    if stems.ndim != 3 or stems.shape[1:] != (frames, 2):
+        raise ValueError("loudness_reference: stems is [n_buses, frames, 2]")
+    state = np.zeros(LOUDNESS_STATE, dtype=np.float32) if state is None else np.array(state, dtype=np.float32, order="C").reshape(-1)
+    if state.size != LOUDNESS_STATE:
+        raise ValueError("loudness_reference: state is [LOUDNESS_STATE]")
+    hop, at = int(hop), C.c_uint32(int(pos))
+    cap = (frames // max(hop, LOUDNESS_MIN_HOP) + 1) * LOUDNESS_CHANNELS
+    rows, n, tp = np.zeros(cap, dtype=np.float32), C.c_size_t(0), np.zeros(2, dtype=np.float32)
+    _rule_check(load_library().s2r_loudness_reference(coeffs.ctypes.data_as(_f32p), hop, stems.ctypes.data_as(_f32p) if stems.shape[0] else None,
+                                                      stems.shape[0], master.ctypes.data_as(_f32p), frames, state.ctypes.data_as(_f32p), C.byref(at),
+                                                      rows.ctypes.data_as(_f32p), rows.size, C.byref(n), tp.ctypes.data_as(_f32p)))
+    return rows[:n.value * LOUDNESS_CHANNELS].reshape(-1, LOUDNESS_CHANNELS).copy(), state, at.value, tp
+
+
+def loudness_readings(rows, hop, programme):
+    """(momentary, short-term, integrated) in LKFS of one programme from hop rows [n_hops, 18] (s2r_loudness_readings): binary64, -inf
+    where there is too little data or nothing passes the gates"""
+    rows = np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, LOUDNESS_CHANNELS)
+    out = (C.c_double * 3)()
+    _rule_check(load_library().s2r_loudness_readings(rows.ctypes.data_as(_f32p) if rows.shape[0] else None, rows.shape[0], int(hop), int(programme), out))
+    return out[0], out[1], out[2]
 
 
 def stream_frame_json(samples):
@@ -1471,6 +1538,78 @@ class Synth:
     @staticmethod
     def limiter_reference(x, ceiling, lookahead, hold, xh=None, gh=None):
         return limiter_reference(x, ceiling, lookahead, hold, xh, gh)
+
+    # --- the loudness and true-peak meters (build-defined; s2r.h: s2r_set_master_loudness) ---
+    def set_master_loudness(self, sample_rate=48000, hop=None, max_hops=None, coeffs=None):
+        """BS.1770 loudness meters on every bus and the master, and the master's true peak, behind the limiter, in sample_master only.
+        `hop`: the frames of 100 ms (None: sample_rate / 10); `max_hops`: the hop rows kept for the integrated value (None: an hour's);
+        `coeffs`: the two biquads [2, 5] (None: loudness_design(sample_rate)).  Starts from the initial state with no rows."""
+        hop = int(round(float(sample_rate) / 10.0)) if hop is None else int(hop)
+        max_hops = 36000 if max_hops is None else int(max_hops)
+        c = loudness_design(sample_rate) if coeffs is None else np.ascontiguousarray(coeffs, dtype=np.float32)
+        if c.size != 10:
+            raise ValueError("set_master_loudness: coeffs is [2, 5]")
+        self._check(self.L.s2r_set_master_loudness(self.h, c.ctypes.data_as(_f32p), hop, max_hops))
+
+    def clear_master_loudness(self):
+        self._check(self.L.s2r_clear_master_loudness(self.h))
+
+    def get_master_loudness(self):
+        """(coeffs [2, 5], hop, max_hops, n_hops): a hop of 0 means off; n_hops the hop rows stored"""
+        c, h, m, n = np.empty((2, 5), dtype=np.float32), C.c_uint32(), C.c_uint32(), C.c_size_t()
+        self._check(self.L.s2r_get_master_loudness(self.h, c.ctypes.data_as(_f32p), C.byref(h), C.byref(m), C.byref(n)))
+        return c, h.value, m.value, n.value
+
+    def reset_master_loudness(self):
+        """state, rows and the held true peak cleared; the parameters stay"""
+        self._check(self.L.s2r_reset_master_loudness(self.h))
+
+    def loudness(self, programme=MAX_BUSES):
+        """(momentary, short-term, integrated) in LKFS of bus `programme`, or of the master (MAX_BUSES), over the stored hop rows"""
+        out = (C.c_double * 3)()
+        self._check(self.L.s2r_get_loudness(self.h, int(programme), out))
+        return out[0], out[1], out[2]
+
+    def true_peak(self):
+        """(last [2], held [2]): the master's true peak, L and R, of the last sample_master call and since the last reset"""
+        last, held = np.empty(2, dtype=np.float32), np.empty(2, dtype=np.float32)
+        self._check(self.L.s2r_get_true_peak(self.h, last.ctypes.data_as(_f32p), held.ctypes.data_as(_f32p)))
+        return last, held
+
+    def loudness_state(self):
+        """(state [LOUDNESS_STATE], pos): the filters' values, the partial hop sums, the master's last 16 frames; the frames of the hop
+        under way (checkpoints)"""
+        st, pos = np.empty(LOUDNESS_STATE, dtype=np.float32), C.c_uint32()
+        self._check(self.L.s2r_get_loudness_state(self.h, st.ctypes.data_as(_f32p), st.size, C.byref(pos)))
+        return st, pos.value
+
+    def set_loudness_state(self, state, pos):
+        st = np.ascontiguousarray(state, dtype=np.float32)
+        self._check(self.L.s2r_set_loudness_state(self.h, st.ctypes.data_as(_f32p), st.size, int(pos)))
+
+    def loudness_hops(self):
+        """the stored hop rows, oldest first: [n_hops, 18] float32 (checkpoints)"""
+        n = self.get_master_loudness()[3]
+        rows, got = np.empty((n, LOUDNESS_CHANNELS), dtype=np.float32), C.c_size_t()
+        self._check(self.L.s2r_get_loudness_hops(self.h, rows.ctypes.data_as(_f32p) if n else None, rows.size, C.byref(got)))
+        return rows[:got.value]
+
+    def set_loudness_hops(self, rows):
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        n = rows.shape[0] if rows.ndim == 2 else rows.size // LOUDNESS_CHANNELS
+        self._check(self.L.s2r_set_loudness_hops(self.h, rows.ctypes.data_as(_f32p) if rows.size else None, n, rows.size))
+
+    @staticmethod
+    def loudness_reference(coeffs, hop, stems, master, state=None, pos=0):
+        return loudness_reference(coeffs, hop, stems, master, state, pos)
+
+    @staticmethod
+    def loudness_readings(rows, hop, programme):
+        return loudness_readings(rows, hop, programme)
+
+    @staticmethod
+    def loudness_design(sample_rate=48000.0):
+        return loudness_design(sample_rate)
 
     def render_voices(self, frames, sample_rate=SampleRateKhz(48000)):
         """Mix disabled: (shard_voices, frames) float32."""
