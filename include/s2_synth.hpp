@@ -340,6 +340,41 @@ class Synth {
     }
     static int loudness_design(double sample_rate, float coeffs[10]) { return s2r_loudness_design(sample_rate, coeffs); }
 
+    // the spectrum meters (build-defined; s2r.h: s2r_set_master_spectrum): a windowed power-of-two FFT of every bus and the master, behind
+    // the loudness meters, in sample_master only; master_lr, the stems and the loudness rows are the same bits with the meter on or off
+    void set_master_spectrum(uint32_t n_fft, uint32_t hop, const float *window, uint32_t max_rows) { check(s2r_set_master_spectrum(h_, n_fft, hop, window, max_rows)); }
+    void clear_master_spectrum() { check(s2r_clear_master_spectrum(h_)); }
+    // an n_fft of 0 means off; n_rows: the rows stored; window: n_fft values when window_capacity holds them
+    void get_master_spectrum(uint32_t *n_fft, uint32_t *hop, uint32_t *max_rows, size_t *n_rows, float *window = nullptr, size_t window_capacity = 0) const {
+        check(s2r_get_master_spectrum(h_, n_fft, hop, max_rows, n_rows, window, window_capacity));
+    }
+    void reset_master_spectrum() { check(s2r_reset_master_spectrum(h_)); }
+    // out_db: n_fft / 2 + 1 values in dB over the last n_avg stored rows; programme S2R_MAX_BUSES is the master
+    void spectrum(uint32_t programme, uint32_t n_avg, double *out_db, size_t capacity) const { check(s2r_get_spectrum(h_, programme, n_avg, out_db, capacity)); }
+    void spectrum_bands(uint32_t programme, uint32_t n_avg, double sample_rate, uint32_t bands_per_octave, double *out_db, double *centres, size_t capacity,
+                        size_t *n_bands) const {
+        check(s2r_get_spectrum_bands(h_, programme, n_avg, sample_rate, bands_per_octave, out_db, centres, capacity, n_bands));
+    }
+    // rows: [n_rows][9][n_fft / 2 + 1]; state: 18 * n_fft floats (checkpoints)
+    void spectrum_rows(float *rows, size_t capacity, size_t *n_rows) const { check(s2r_get_spectrum_rows(h_, rows, capacity, n_rows)); }
+    void set_spectrum_rows(const float *rows, size_t n_rows, size_t count) { check(s2r_set_spectrum_rows(h_, rows, n_rows, count)); }
+    void spectrum_state(float *state, size_t capacity, uint32_t *pos) { check(s2r_get_spectrum_state(h_, state, capacity, pos)); }
+    void set_spectrum_state(const float *state, size_t count, uint32_t pos) { check(s2r_set_spectrum_state(h_, state, count, pos)); }
+    static int spectrum_reference(uint32_t n_fft, uint32_t hop, const float *window, const float *stems, uint32_t n_buses, const float *master_lr, uint32_t frames,
+                                  float *state, uint32_t *pos, float *rows, size_t rows_capacity, size_t *n_rows) {
+        return s2r_spectrum_reference(n_fft, hop, window, stems, n_buses, master_lr, frames, state, pos, rows, rows_capacity, n_rows);
+    }
+    static int spectrum_readings(const float *rows, size_t n_rows, uint32_t n_fft, const float *window, uint32_t programme, uint32_t n_avg, double *out_db,
+                                 size_t capacity) {
+        return s2r_spectrum_readings(rows, n_rows, n_fft, window, programme, n_avg, out_db, capacity);
+    }
+    static int spectrum_band_readings(const float *rows, size_t n_rows, uint32_t n_fft, const float *window, uint32_t programme, uint32_t n_avg, double sample_rate,
+                                      uint32_t bands_per_octave, double *out_db, double *centres, size_t capacity, size_t *n_bands) {
+        return s2r_spectrum_band_readings(rows, n_rows, n_fft, window, programme, n_avg, sample_rate, bands_per_octave, out_db, centres, capacity, n_bands);
+    }
+    static int spectrum_window(uint32_t kind, uint32_t n_fft, float *window) { return s2r_spectrum_window(kind, n_fft, window); }
+    static int spectrum_twiddles(uint32_t n_fft, float *twiddles) { return s2r_spectrum_twiddles(n_fft, twiddles); }
+
     s2r_synth *handle() { return h_; }
 
   private:

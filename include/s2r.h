@@ -52,7 +52,10 @@ extern "C" {
  * s2r_set_bus_flanger_params, s2r_get_bus_flanger, s2r_get_bus_flanger_state, s2r_set_bus_flanger_state, s2r_flanger_reference,
  * s2r_set_master_loudness, s2r_clear_master_loudness, s2r_get_master_loudness, s2r_reset_master_loudness, s2r_get_loudness,
  * s2r_get_true_peak, s2r_get_loudness_state, s2r_set_loudness_state, s2r_get_loudness_hops, s2r_set_loudness_hops,
- * s2r_loudness_reference, s2r_loudness_readings, s2r_loudness_design. */
+ * s2r_loudness_reference, s2r_loudness_readings, s2r_loudness_design, s2r_set_master_spectrum, s2r_clear_master_spectrum,
+ * s2r_get_master_spectrum, s2r_reset_master_spectrum, s2r_get_spectrum, s2r_get_spectrum_bands, s2r_get_spectrum_rows,
+ * s2r_set_spectrum_rows, s2r_get_spectrum_state, s2r_set_spectrum_state, s2r_spectrum_reference, s2r_spectrum_readings,
+ * s2r_spectrum_band_readings, s2r_spectrum_window, s2r_spectrum_twiddles. */
 #define S2R_ABI_VERSION 4
 
 typedef enum {
@@ -965,6 +968,111 @@ int s2r_loudness_reference(const float coeffs[10], uint32_t hop, const float *st
                            float true_peak[2]);
 int s2r_loudness_readings(const float *rows, size_t n_hops, uint32_t hop, uint32_t programme, double out[3]);
 int s2r_loudness_design(double sample_rate, float coeffs[10]);
+
+/* BUILD-DEFINED spectrum meters (the reference has none): a windowed power-of-two FFT of every bus and of the master,
+ * behind the loudness meters, in s2r_fill_master only, on the device the stems and the master are already on.  Off by default, and a
+ * handle on which the meter was never set launches exactly what it launched before; master_lr, the stems and the loudness rows are the
+ * same bits with the meter on or off.
+ * PROGRAMMES: S2R_SPECTRUM_PROGRAMMES = 9, the loudness meters': programme b < 8 is bus b as the stems hold it (post-effect,
+ * pre-return), programme 8 the master as the caller receives it, behind the limiter when one is set.  A bus at or past the call's
+ * n_buses is fed +0.0 for every frame of the call.
+ * PARAMETERS: n_fft = N, a power of two in S2R_SPECTRUM_MIN_FFT .. S2R_SPECTRUM_MAX_FFT (256 .. 8192); hop in max(16, N / 8) ..
+ * S2R_SPECTRUM_MAX_HOP (a hop longer than N skips frames); window[N], finite floats; max_rows in 1 .. S2R_SPECTRUM_MAX_ROWS, the rows
+ * the handle keeps: a sliding window whose oldest row drops when a new one would exceed it.
+ * STREAM AND ROWS: each programme is a stream of stereo frames; the frames before the first fill, a reset or a set are +0.0.  `pos`
+ * counts the frames of the hop under way.  When a frame makes pos + 1 == hop, pos returns to 0 and a ROW is taken over the N most
+ * recent frames ending at that frame, oldest first: z[i] = (window[i] * L[i], window[i] * R[i]), one complex transform for both
+ * channels.  A row is [9][N / 2 + 1] floats, S2R_SPECTRUM_ROW(N) of them.
+ * STATE carried from call to call: the last N frames of all nine programmes, [9][N][2] floats (programme, frame oldest first, L then
+ * R), 18 * N of them, and pos < hop.  All +0.0 / 0 right after a set or a reset.
+ * DEVICE RULE, binary32, every operation rounded on its own, no fma, denormals kept.
+ *   TWIDDLES T[j], j < N / 2 (s2r_spectrum_twiddles), computed by the host, read by the device:
+ *     j <= N / 8:          T[j] = (cos(2 pi j / N), -sin(2 pi j / N)) in binary64, each rounded to nearest binary32; T[0].im is +0.0
+ *     N / 8 < j <= N / 4:  T[j] = (-T[N / 4 - j].im, -T[N / 4 - j].re)
+ *     N / 4 < j < N / 2:   T[j] = (T[j - N / 4].im, -T[j - N / 4].re)
+ *   so T[0] = (1, 0) and T[N / 4] = (0, -1) exactly, and the table is symmetric on bits.
+ *   TRANSFORM, radix-2 decimation in time: v[i] = z[bitrev(i)] (bitrev over log2 N bits); for s = 1 .. log2 N, m = 2^s, h = m / 2, for
+ *   every block base g (a multiple of m) and j < h:
+ *     w = T[j * (N / m)];   a = v[g + j];   b = v[g + j + h]
+ *     t = (w.re * b.re - w.im * b.im,  w.re * b.im + w.im * b.re)
+ *     v'[g + j] = a + t;   v'[g + j + h] = a - t
+ *   The rule fixes the arithmetic graph, not the storage: any layout, any number of layers held in registers, is the rule when every
+ *   value comes from the same operations.  The products with T[0] and T[N / 4] change only the signs of zeros, which cannot reach a
+ *   row for finite input; an implementation may skip them.  FOR NON-FINITE INPUT THE CONTRACT IS ONLY THAT A ROW VALUE IS NON-FINITE
+ *   WHERE THE RULE'S IS.
+ *   POWER, k = 0 .. N / 2, a = v[k], b = v[(N - k) mod N]:
+ *     p[k] = ((a.re * a.re + a.im * a.im) + (b.re * b.re + b.im * b.im)) * 0.5f
+ *   which is |X_L[k]|^2 + |X_R[k]|^2 without an untangling pass.  A programme at or past the call's n_buses gets p[k] = +0.0.
+ * Rows and state do not depend on how a stream is cut into calls.
+ * HOST RULE, binary64, pure functions of the rows.  s2r_spectrum_readings, over the last n_avg rows (1 .. n_rows) of one programme:
+ *   q[k] = c_k * (sum over those rows, oldest first, from 0.0, of (double)p_r[k]) / n_avg / (S1 * S1),   dB[k] = 10 log10(q[k])
+ *   with S1 the sum of (double)window[i] in index order from 0.0, c_k = 2 for 0 < k < N / 2 and 0.5 at k = 0 and k = N / 2.  Silence
+ *   reads -inf.  A bin-centred sine of amplitude 1 on both channels reads 0 dB, on one channel -3.01 dB, DC of 1 on both 0 dB.
+ *   s2r_spectrum_band_readings: fractional-octave bands, bands_per_octave one of 1, 3, 6, 12.  Centres 1000 * 2^(i / bpo) Hz for
+ *   integer i, ascending; edges the centre times 2^(-1 / (2 bpo)) and 2^(+1 / (2 bpo)); a band is kept when its lower edge is at or
+ *   above sample_rate / N and its upper edge at or below sample_rate / 2.  Bin k covers [(k - 1/2), (k + 1/2)] * sample_rate / N; a
+ *   band's power is the sum, in ascending k from 0.0, of q[k] times the fraction of bin k inside the band; dB = 10 log10 of it.
+ * A refused or failed call leaves state, rows and readings as they were; every fill but s2r_fill_master ignores the meter.
+ * Single-device handles (a device list refuses every entry).  The first master fill that finds the meter set allocates the two
+ * copies of the state, the window and twiddles on the device, and pinned rows for max_frames / hop + 1 rows.
+ *   s2r_set_master_spectrum: S2R_ERR_PATCH_RANGE for n_fft, hop or max_rows out of range or a window value that is not finite
+ *   (checked before the handle is looked at; nothing is changed); S2R_ERR_INVALID for a NULL window.  Resets state and rows.
+ *   s2r_clear_master_spectrum: off.  s2r_get_master_spectrum: any pointer may be NULL; an n_fft of 0 means off; n_rows the stored
+ *   rows; `window` receives the N values when window_capacity >= N (S2R_ERR_INVALID when it is non-NULL and smaller).
+ *   s2r_reset_master_spectrum: state and rows cleared, parameters kept; S2R_ERR_INVALID with the meter off.
+ *   s2r_get_spectrum: out_db[N / 2 + 1] of `programme` (< 9, else S2R_ERR_PATCH_RANGE) over the last n_avg stored rows
+ *   (S2R_ERR_PATCH_RANGE for n_avg == 0 or more than the stored rows); capacity in doubles, at least N / 2 + 1.
+ *   s2r_get_spectrum_bands: the same per band; out_db and centres hold `capacity` doubles each (centres may be NULL), *n_bands the
+ *   bands kept; S2R_ERR_INVALID for a capacity below them.
+ *   s2r_get_spectrum_rows / s2r_set_spectrum_rows (checkpoints): the stored rows, oldest first, [n_rows][9][N / 2 + 1]; the getter
+ *   takes a capacity in floats, the setter exactly count == n_rows * S2R_SPECTRUM_ROW(N), n_rows <= max_rows (S2R_ERR_PATCH_RANGE
+ *   past it).  s2r_get_spectrum_state / s2r_set_spectrum_state: the 18 * N floats and pos; the getter takes a capacity of at least
+ *   18 * N, the setter exactly 18 * N and a pos below hop (S2R_ERR_PATCH_RANGE).  S2R_ERR_INVALID for a wrong size, a NULL buffer or
+ *   with the meter off.
+ *   s2r_spectrum_reference: the device rule on the host (no device, no handle).  stems [n_buses][frames][2] (NULL with n_buses 0),
+ *   master_lr [frames][2]; state[18 * N] and *pos updated in place; the call's rows written to rows[0 .. *n_rows * S2R_SPECTRUM_ROW(N)),
+ *   which holds rows_capacity floats (checked before anything is changed).  S2R_ERR_PATCH_RANGE as the setter's, for n_buses > 8 or
+ *   *pos >= hop; S2R_ERR_INVALID for a NULL or a capacity too small.
+ *   s2r_spectrum_readings / s2r_spectrum_band_readings: the host rule over rows [n_rows][9][N / 2 + 1].  S2R_ERR_PATCH_RANGE for an
+ *   n_fft out of range, programme >= 9, n_avg == 0 or > n_rows, a bands_per_octave not of the four, a sample_rate that is not
+ *   finite and positive; S2R_ERR_INVALID for NULL or a capacity too small.
+ *   s2r_spectrum_window: the periodic form of `kind`, binary64 rounded to binary32, x = 2 pi i / N: S2R_WINDOW_RECT 1; S2R_WINDOW_HANN
+ *   0.5 - 0.5 cos x; S2R_WINDOW_HAMMING 0.54 - 0.46 cos x; S2R_WINDOW_BLACKMAN_HARRIS 0.35875 - 0.48829 cos x + 0.14128 cos 2x -
+ *   0.01168 cos 3x.  S2R_ERR_PATCH_RANGE for an unknown kind or n_fft out of range, S2R_ERR_INVALID for NULL.
+ *   s2r_spectrum_twiddles: twiddles[N / 2][2] (re, im), the table above.  The same refusals. */
+#define S2R_SPECTRUM_PROGRAMMES 9u
+#define S2R_SPECTRUM_MIN_FFT 256u
+#define S2R_SPECTRUM_MAX_FFT 8192u
+#define S2R_SPECTRUM_MIN_HOP 16u
+#define S2R_SPECTRUM_MAX_HOP (1u << 20)
+#define S2R_SPECTRUM_MAX_ROWS 256u
+#define S2R_SPECTRUM_ROW(n_fft) ((size_t)S2R_SPECTRUM_PROGRAMMES * ((size_t)(n_fft) / 2u + 1u))
+#define S2R_WINDOW_RECT 0u
+#define S2R_WINDOW_HANN 1u
+#define S2R_WINDOW_HAMMING 2u
+#define S2R_WINDOW_BLACKMAN_HARRIS 3u
+int s2r_set_master_spectrum(s2r_synth *s, uint32_t n_fft, uint32_t hop, const float *window, uint32_t max_rows);
+int s2r_clear_master_spectrum(s2r_synth *s);
+int s2r_get_master_spectrum(const s2r_synth *s, uint32_t *n_fft, uint32_t *hop, uint32_t *max_rows, size_t *n_rows, float *window,
+                            size_t window_capacity);
+int s2r_reset_master_spectrum(s2r_synth *s);
+int s2r_get_spectrum(const s2r_synth *s, uint32_t programme, uint32_t n_avg, double *out_db, size_t capacity);
+int s2r_get_spectrum_bands(const s2r_synth *s, uint32_t programme, uint32_t n_avg, double sample_rate, uint32_t bands_per_octave,
+                           double *out_db, double *centres, size_t capacity, size_t *n_bands);
+int s2r_get_spectrum_rows(const s2r_synth *s, float *rows, size_t capacity, size_t *n_rows);
+int s2r_set_spectrum_rows(s2r_synth *s, const float *rows, size_t n_rows, size_t count);
+int s2r_get_spectrum_state(s2r_synth *s, float *state, size_t capacity, uint32_t *pos);
+int s2r_set_spectrum_state(s2r_synth *s, const float *state, size_t count, uint32_t pos);
+int s2r_spectrum_reference(uint32_t n_fft, uint32_t hop, const float *window, const float *stems, uint32_t n_buses,
+                           const float *master_lr, uint32_t frames, float *state, uint32_t *pos, float *rows, size_t rows_capacity,
+                           size_t *n_rows);
+int s2r_spectrum_readings(const float *rows, size_t n_rows, uint32_t n_fft, const float *window, uint32_t programme, uint32_t n_avg,
+                          double *out_db, size_t capacity);
+int s2r_spectrum_band_readings(const float *rows, size_t n_rows, uint32_t n_fft, const float *window, uint32_t programme,
+                               uint32_t n_avg, double sample_rate, uint32_t bands_per_octave, double *out_db, double *centres,
+                               size_t capacity, size_t *n_bands);
+int s2r_spectrum_window(uint32_t kind, uint32_t n_fft, float *window);
+int s2r_spectrum_twiddles(uint32_t n_fft, float *twiddles);
 
 /* BUILD-DEFINED 4x oversampling (the reference has none; BASELINE config [4]): renders 4 * frames at
  * 4 * sample_rate_hz through the same path and decimates the mix by a 63-tap windowed sinc whose history

@@ -238,6 +238,28 @@ pub mod ffi {
                                       true_peak: *mut f32) -> c_int;
         pub fn s2r_loudness_readings(rows: *const f32, n_hops: usize, hop: u32, programme: u32, out: *mut f64) -> c_int;
         pub fn s2r_loudness_design(sample_rate: f64, coeffs: *mut f32) -> c_int;
+        pub fn s2r_set_master_spectrum(s: *mut S2rSynth, n_fft: u32, hop: u32, window: *const f32, max_rows: u32) -> c_int;
+        pub fn s2r_clear_master_spectrum(s: *mut S2rSynth) -> c_int;
+        pub fn s2r_get_master_spectrum(s: *const S2rSynth, n_fft: *mut u32, hop: *mut u32, max_rows: *mut u32, n_rows: *mut usize,
+                                       window: *mut f32, window_capacity: usize) -> c_int;
+        pub fn s2r_reset_master_spectrum(s: *mut S2rSynth) -> c_int;
+        pub fn s2r_get_spectrum(s: *const S2rSynth, programme: u32, n_avg: u32, out_db: *mut f64, capacity: usize) -> c_int;
+        pub fn s2r_get_spectrum_bands(s: *const S2rSynth, programme: u32, n_avg: u32, sample_rate: f64, bands_per_octave: u32,
+                                      out_db: *mut f64, centres: *mut f64, capacity: usize, n_bands: *mut usize) -> c_int;
+        pub fn s2r_get_spectrum_rows(s: *const S2rSynth, rows: *mut f32, capacity: usize, n_rows: *mut usize) -> c_int;
+        pub fn s2r_set_spectrum_rows(s: *mut S2rSynth, rows: *const f32, n_rows: usize, count: usize) -> c_int;
+        pub fn s2r_get_spectrum_state(s: *mut S2rSynth, state: *mut f32, capacity: usize, pos: *mut u32) -> c_int;
+        pub fn s2r_set_spectrum_state(s: *mut S2rSynth, state: *const f32, count: usize, pos: u32) -> c_int;
+        pub fn s2r_spectrum_reference(n_fft: u32, hop: u32, window: *const f32, stems: *const f32, n_buses: u32, master_lr: *const f32,
+                                      frames: u32, state: *mut f32, pos: *mut u32, rows: *mut f32, rows_capacity: usize,
+                                      n_rows: *mut usize) -> c_int;
+        pub fn s2r_spectrum_readings(rows: *const f32, n_rows: usize, n_fft: u32, window: *const f32, programme: u32, n_avg: u32,
+                                     out_db: *mut f64, capacity: usize) -> c_int;
+        pub fn s2r_spectrum_band_readings(rows: *const f32, n_rows: usize, n_fft: u32, window: *const f32, programme: u32, n_avg: u32,
+                                          sample_rate: f64, bands_per_octave: u32, out_db: *mut f64, centres: *mut f64, capacity: usize,
+                                          n_bands: *mut usize) -> c_int;
+        pub fn s2r_spectrum_window(kind: u32, n_fft: u32, window: *mut f32) -> c_int;
+        pub fn s2r_spectrum_twiddles(n_fft: u32, twiddles: *mut f32) -> c_int;
         pub fn s2r_shard_voices(s: *const S2rSynth) -> u32;
         pub fn s2r_fill_device(s: *mut S2rSynth, dev_out: *mut f32, frames: usize, sample_rate_hz: u32,
                                hip_stream: *mut c_void) -> c_int;

@@ -25,7 +25,8 @@ SOURCES = ["s2r_render_onepole_square.hip", "s2r_render_onepole_saw.hip", "s2r_r
            "s2r_room.hip",      # (likewise, since the room came)
            "s2r_drive.hip",     # (likewise, since the drive came)
            "s2r_flanger.hip",   # (likewise, since the flanger came)
-           "s2r_loudness.hip"]  # (last, likewise, since the loudness meters came)
+           "s2r_loudness.hip",  # (likewise, since the loudness meters came)
+           "s2r_spectrum.hip"]  # (last, likewise, since the spectrum meters came)
 HEADERS = ["s2r_device.h", "s2r_math.h", "s2r_patch.h", "s2r_voices.h", "s2r_kern_common.h", "s2r_render_onepole.inc",
            "s2r_render_general.inc", "s2r_post.h", "s2r_post_route.h", "s2r_rules.h"]
 
@@ -55,7 +56,7 @@ PER_FILE_FLAGS = {}
 for _f in ("s2r_render_general_square.hip", "s2r_render_general_saw.hip", "s2r_render_general_triangle.hip", "s2r_render_general_sine.hip",
            "s2r_render_general_bank.hip"):
     PER_FILE_FLAGS[_f] = ["-ftrivial-auto-var-init=zero"]
-# Eleven translation units are compiled with the back end's resource-usage remarks, and _check_resources() fails the build when a
+# Twelve translation units are compiled with the back end's resource-usage remarks, and _check_resources() fails the build when a
 # kernel named here went to scratch or spilled, or when fewer kernels report than the file instantiates.  Per source file: the
 # substrings that name its checked kernels; how many reports are expected — ("at least", n), ("exactly", n), or ("each", None):
 # one or more of every name — and why so many; the figures that must be "0"; and what the kernels keep where it belongs.  (The
@@ -101,6 +102,9 @@ RESOURCE_CHECKS = {
     # per stager lane; seventeen master frames and two sums per true-peak lane, the taps in SGPRs
     "s2r_loudness.hip": (("s2r_loudness_kernel",), ("exactly", 1), "one kernel",
                          (_SCRATCH, _VSPILL, _SSPILL), "its filter values, sums and the samples read ahead must stay in registers, the tiles in LDS"),
+    # eight or sixteen points of one pass per lane and the twiddles of its layers; the transform and the twiddle table in LDS
+    "s2r_spectrum.hip": (("s2r_spectrum_kernel",), ("exactly", 1), "one kernel",
+                         (_SCRATCH, _VSPILL, _SSPILL), "the points of a pass must stay in registers, the transform and its twiddles in LDS"),
 }
 for _f in RESOURCE_CHECKS:
     PER_FILE_FLAGS[_f] = ["-Rpass-analysis=kernel-resource-usage"]
@@ -147,6 +151,11 @@ if _FLANGER_SERIAL:
 _LOUDNESS_SERIAL = os.environ.get("S2R_LOUDNESS_SERIAL") == "1"
 if _LOUDNESS_SERIAL:
     PER_FILE_FLAGS["s2r_loudness.hip"] = PER_FILE_FLAGS["s2r_loudness.hip"] + ["-DS2R_LOUDNESS_SERIAL"]
+# S2R_SPECTRUM_SERIAL=1 likewise builds the spectrum kernel's obvious form (a barrier per radix-2 layer, no padding, one point pair per
+# thread and layer; csrc/s2r_spectrum.hip, CHANGELOG) into libs2r_spectrumserial.so, for tools/spectrum_time.py.  Never the product build.
+_SPECTRUM_SERIAL = os.environ.get("S2R_SPECTRUM_SERIAL") == "1"
+if _SPECTRUM_SERIAL:
+    PER_FILE_FLAGS["s2r_spectrum.hip"] = PER_FILE_FLAGS["s2r_spectrum.hip"] + ["-DS2R_SPECTRUM_SERIAL"]
 # S2R_OPT=O3 in the environment builds the same sources at -O3 into libs2r_o3.so (tools and tests that compare the two
 # optimisation levels; the product is -O2).
 if os.environ.get("S2R_OPT") == "O3":
@@ -181,6 +190,9 @@ elif _FLANGER_SERIAL:
 elif _LOUDNESS_SERIAL:
     LIB = os.path.join(HERE, "libs2r_loudnessserial.so")
     OBJ_DIR_NAME = "_build_loudnessserial"
+elif _SPECTRUM_SERIAL:
+    LIB = os.path.join(HERE, "libs2r_spectrumserial.so")
+    OBJ_DIR_NAME = "_build_spectrumserial"
 else:
     OBJ_DIR_NAME = "_build"
 

@@ -640,3 +640,22 @@ struct S2rLoudness {
     uint32_t n_buses, frames, hop, pos;
 };
 hipError_t s2r_launch_loudness(const S2rLoudness &a, hipStream_t stream);
+
+// The spectrum meters of s2r_fill_master: one launch behind the loudness kernel (or, without that meter, behind whoever
+// wrote the master last), the last of a master fill that finds the meter set.  It reads the stems from the master's device stage and
+// the master from device memory, writes the call's power rows and the OTHER copy of the state, and — only when no loudness kernel did
+// it — copies the master to the pinned output (`out` null: somebody else has).  The host flips the copies after a synchronise that
+// succeeded.  `pos` is the host's: the frames of the hop under way when the call starts.
+#define S2R_SPECTRUM_COPY_BLOCKS 16u                // workgroups that write the next state and the copy, behind the transforms'
+struct S2rSpectrum {
+    const float *stems;           // [n_buses][2 * frames] in device memory: the master kernel's input
+    const float *master;          // [frames][2] in device memory
+    float *out;                   // interleaved L, R: 2 * frames floats (mapped host memory), or null
+    const float *state;           // [9][n_fft][2]: the state the call starts from
+    float *next;                  // ... and the state it leaves (never the buffer above)
+    const float *window;          // [n_fft] in device memory
+    const float *twiddles;        // [n_fft / 2][2] in device memory
+    float *rows;                  // [(pos + frames) / hop][9][n_fft / 2 + 1] (mapped host memory): the rows the call completes
+    uint32_t n_buses, frames, n_fft, hop, pos;
+};
+hipError_t s2r_launch_spectrum(const S2rSpectrum &a, hipStream_t stream);

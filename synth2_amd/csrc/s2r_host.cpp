@@ -3432,6 +3432,110 @@ int s2r_set_loudness_hops(s2r_synth *s, const float *rows, size_t n_hops, size_t
     return S2R_OK;
 }
 
+// ---- the spectrum meters behind the loudness meters ----
+int s2r_set_master_spectrum(s2r_synth *s, uint32_t n_fft, uint32_t hop, const float *window, uint32_t max_rows) {
+    if (!spectrum_in_range(n_fft, hop, window, max_rows))
+        return set_err(s, S2R_ERR_PATCH_RANGE, "master spectrum: size %u, hop %u, %u rows: a power of two in %u .. %u, the hop in max(%u, size / 8) .. %u, the rows kept in 1 .. %u, a finite window",
+                       n_fft, hop, max_rows, S2R_SPECTRUM_MIN_FFT, S2R_SPECTRUM_MAX_FFT, S2R_SPECTRUM_MIN_HOP, S2R_SPECTRUM_MAX_HOP, S2R_SPECTRUM_MAX_ROWS);
+    S2R_TRY(post_handle(s, "s2r_set_master_spectrum", "the spectrum meter is"));
+    if (!window) return set_err(s, S2R_ERR_INVALID, "s2r_set_master_spectrum: no window");
+    s->post.set_spectrum(n_fft, hop, window, max_rows);
+    return S2R_OK;
+}
+
+int s2r_clear_master_spectrum(s2r_synth *s) {
+    S2R_TRY(post_handle(s, "s2r_clear_master_spectrum", "the spectrum meter is"));
+    s->post.set_spectrum(0, 0, nullptr, 0);
+    return S2R_OK;
+}
+
+int s2r_get_master_spectrum(const s2r_synth *s, uint32_t *n_fft, uint32_t *hop, uint32_t *max_rows, size_t *n_rows, float *window, size_t window_capacity) {
+    if (!s || !s->kids.empty() || s->parent) return S2R_ERR_INVALID;
+    const S2rPostChain::Spectrum &sp = s->post.spec;
+    if (window && window_capacity < sp.n_fft) return S2R_ERR_INVALID;
+    if (window && sp.n_fft) std::memcpy(window, sp.window.data(), sp.n_fft * sizeof(float));
+    put(n_fft, sp.n_fft); put(hop, sp.hop); put(max_rows, sp.max_rows); put(n_rows, sp.n_rows());
+    return S2R_OK;
+}
+
+// the guard of the entries that need the meter set
+static int spectrum_on(const s2r_synth *s, const char *who) {
+    S2R_TRY(post_handle(s, who, "the spectrum meter is"));
+    if (!s->post.spec.n_fft) return set_err(const_cast<s2r_synth *>(s), S2R_ERR_INVALID, "%s: no spectrum meter is set", who);
+    return S2R_OK;
+}
+
+int s2r_reset_master_spectrum(s2r_synth *s) {
+    S2R_TRY(spectrum_on(s, "s2r_reset_master_spectrum"));
+    s->post.reset_spectrum();
+    return S2R_OK;
+}
+
+int s2r_get_spectrum(const s2r_synth *s, uint32_t programme, uint32_t n_avg, double *out_db, size_t capacity) {
+    if (programme >= S2R_SPECTRUM_PROGRAMMES) return S2R_ERR_PATCH_RANGE;
+    if (!s || !s->kids.empty() || s->parent || !s->post.spec.n_fft || !out_db) return S2R_ERR_INVALID;
+    const S2rPostChain::Spectrum &sp = s->post.spec;
+    if (n_avg == 0u || n_avg > sp.n_rows()) return S2R_ERR_PATCH_RANGE;
+    return s2r_spectrum_readings(sp.stored(), sp.n_rows(), sp.n_fft, sp.window.data(), programme, n_avg, out_db, capacity);
+}
+
+int s2r_get_spectrum_bands(const s2r_synth *s, uint32_t programme, uint32_t n_avg, double sample_rate, uint32_t bands_per_octave, double *out_db, double *centres,
+                           size_t capacity, size_t *n_bands) {
+    if (programme >= S2R_SPECTRUM_PROGRAMMES) return S2R_ERR_PATCH_RANGE;
+    if (!s || !s->kids.empty() || s->parent || !s->post.spec.n_fft || !out_db || !n_bands) return S2R_ERR_INVALID;
+    const S2rPostChain::Spectrum &sp = s->post.spec;
+    if (n_avg == 0u || n_avg > sp.n_rows()) return S2R_ERR_PATCH_RANGE;
+    return s2r_spectrum_band_readings(sp.stored(), sp.n_rows(), sp.n_fft, sp.window.data(), programme, n_avg, sample_rate, bands_per_octave, out_db, centres, capacity,
+                                      n_bands);
+}
+
+int s2r_get_spectrum_rows(const s2r_synth *s, float *rows, size_t capacity, size_t *n_rows) {
+    S2R_TRY(spectrum_on(s, "s2r_get_spectrum_rows"));
+    const S2rPostChain::Spectrum &sp = s->post.spec;
+    const size_t n = sp.n_rows() * sp.row_floats();
+    if (capacity < n || (n && !rows)) return set_err(const_cast<s2r_synth *>(s), S2R_ERR_INVALID, "s2r_get_spectrum_rows: the rows are %zu floats, the buffer holds %zu", n, rows ? capacity : (size_t)0);
+    if (n) std::memcpy(rows, sp.stored(), n * sizeof(float));
+    put(n_rows, sp.n_rows());
+    return S2R_OK;
+}
+
+int s2r_set_spectrum_rows(s2r_synth *s, const float *rows, size_t n_rows, size_t count) {
+    S2R_TRY(spectrum_on(s, "s2r_set_spectrum_rows"));
+    S2rPostChain::Spectrum &sp = s->post.spec;
+    if (n_rows > sp.max_rows) return set_err(s, S2R_ERR_PATCH_RANGE, "s2r_set_spectrum_rows: %zu rows, at most the %u the meter keeps", n_rows, sp.max_rows);
+    if (count != n_rows * sp.row_floats() || (count && !rows))
+        return set_err(s, S2R_ERR_INVALID, "s2r_set_spectrum_rows: %zu rows are %zu floats, not %zu", n_rows, n_rows * sp.row_floats(), rows ? count : (size_t)0);
+    sp.kept.assign(rows, rows + count); sp.first = 0;
+    return S2R_OK;
+}
+
+int s2r_get_spectrum_state(s2r_synth *s, float *state, size_t capacity, uint32_t *pos) {
+    S2R_TRY(spectrum_on(s, "s2r_get_spectrum_state"));
+    S2rPostChain::Spectrum &sp = s->post.spec;
+    const size_t n = 18u * (size_t)sp.n_fft;
+    if (capacity < n) return set_err(s, S2R_ERR_INVALID, "s2r_get_spectrum_state: the state is %zu floats, not %zu", n, capacity);
+    if (!state) return set_err(s, S2R_ERR_INVALID, "s2r_get_spectrum_state: null buffer");
+    if (!sp.host_valid) {                                        // the device holds it: fetch it once, and keep it until the next fill
+        if (s->ring_count) return set_err(s, S2R_ERR_INVALID, "s2r_get_spectrum_state with fills of s2r_fill_begin in flight: s2r_fill_end first");
+        S2R_QUIESCE(s);
+        S2R_HIP(s, hipSetDevice(s->device));
+        S2R_HIP(s, s->post.fetch_spectrum_state(post_ctx(s)));
+    }
+    std::memcpy(state, sp.host.data(), n * sizeof(float));
+    put(pos, sp.pos);
+    return S2R_OK;
+}
+
+int s2r_set_spectrum_state(s2r_synth *s, const float *state, size_t count, uint32_t pos) {
+    S2R_TRY(spectrum_on(s, "s2r_set_spectrum_state"));
+    const size_t n = 18u * (size_t)s->post.spec.n_fft;
+    if (count != n) return set_err(s, S2R_ERR_INVALID, "s2r_set_spectrum_state: the state is %zu floats, not %zu", n, count);
+    if (!state) return set_err(s, S2R_ERR_INVALID, "s2r_set_spectrum_state: null buffer");
+    if (pos >= s->post.spec.hop) return set_err(s, S2R_ERR_PATCH_RANGE, "s2r_set_spectrum_state: position %u, below the hop of %u", pos, s->post.spec.hop);
+    s->post.set_spectrum_state(state, pos);
+    return S2R_OK;
+}
+
 int s2r_fill_oversampled(s2r_synth *s, float *mono_out, size_t frames, uint32_t sample_rate_hz) {
     if (!s) return S2R_ERR_INVALID;
     if (sample_rate_hz > 0xffffffffu / S2R_OVERSAMPLE) return set_err(s, S2R_ERR_INVALID, "sample rate too high to oversample");
@@ -3921,6 +4025,8 @@ extern "C" float s2r_debug_master_ms(const s2r_synth *s) { return s && s->timing
 extern "C" float s2r_debug_limiter_ms(const s2r_synth *s) { return s && s->timing ? s->post.limiter.timer.ms : -1.0f; }
 // ... and of the loudness kernel in that fill: 0 when it ran none (tools/loudness_time.py)
 extern "C" float s2r_debug_loudness_ms(const s2r_synth *s) { return s && s->timing ? s->post.loud.timer.ms : -1.0f; }
+// ... and of the spectrum kernel in that fill: 0 when it ran none (tools/spectrum_time.py)
+extern "C" float s2r_debug_spectrum_ms(const s2r_synth *s) { return s && s->timing ? s->post.spec.timer.ms : -1.0f; }
 
 extern "C" uint32_t s2r_debug_read_stamps(s2r_synth *s, unsigned long long *out, uint32_t max_waves) {
 #if defined(S2R_STAMPS)

@@ -1,4 +1,4 @@
-// s2r_post.cpp — the post-mix chain (s2r_post.h): the eight bus stages (EQs, dynamics, drives, flangers, choruses, delays, reverbs, rooms), master section, master limiter, loudness meters.  Compiled with hipcc, -ffp-contract=off.
+// s2r_post.cpp — the post-mix chain (s2r_post.h): the eight bus stages (EQs, dynamics, drives, flangers, choruses, delays, reverbs, rooms), master section, master limiter, loudness meters, spectrum meters.  Compiled with hipcc, -ffp-contract=off.
 #include "s2r_post.h"
 #include "s2r_rules.h"
 
@@ -82,8 +82,30 @@ hipError_t S2rPostChain::prepare(const S2rPostCtx &c, uint32_t n_buses, uint32_t
         for (float *&p : limiter.state) if (!p) POST_HIP(hipMalloc((void **)&p, kLimState * sizeof(float)));
         POST_HIP(pinned_rows(limiter.partials, limiter.partials_dev, (size_t)((c.max_frames + S2R_LIMITER_BLOCK - 1u) / S2R_LIMITER_BLOCK) * 2u));
     }
-    if (metered(call)) {                                         // the meter's input, the two copies of its state, its pinned hop rows and peaks
-        if (!loud.in) POST_HIP(hipMalloc((void **)&loud.in, (size_t)2 * c.max_frames * sizeof(float)));
+    if (metered(call) && !loud.in) POST_HIP(hipMalloc((void **)&loud.in, (size_t)2 * c.max_frames * sizeof(float)));      // the meters' input
+    if (spec_on(call)) {                                         // the two copies of the state, the tables and the pinned rows, by n_fft and hop
+        Spectrum &sp = spec;
+        const size_t n = sp.n_fft, need_state = 18u * n, need_tables = 2u * n, need_rows = (size_t)(c.max_frames / sp.hop + 1u) * sp.row_floats();
+        if (sp.state_floats < need_state) {                      // (only behind a set: the state is the host's then, and the device's copies hold nothing)
+            for (float *&p : sp.state) { if (p) (void)hipFree(p); p = nullptr; }
+            sp.state_floats = 0;
+            for (float *&p : sp.state) POST_HIP(hipMalloc((void **)&p, need_state * sizeof(float)));
+            sp.state_floats = need_state;
+        }
+        if (sp.tables_floats < need_tables) {
+            if (sp.tables) (void)hipFree(sp.tables);
+            sp.tables = nullptr; sp.tables_floats = 0; sp.tables_valid = false;
+            POST_HIP(hipMalloc((void **)&sp.tables, need_tables * sizeof(float)));
+            sp.tables_floats = need_tables;
+        }
+        if (sp.rows_floats < need_rows) {
+            if (sp.rows) (void)hipHostFree(sp.rows);
+            sp.rows = sp.rows_dev = nullptr; sp.rows_floats = 0;
+            POST_HIP(pinned_rows(sp.rows, sp.rows_dev, need_rows));
+            sp.rows_floats = need_rows;
+        }
+    }
+    if (loud_on(call)) {                                         // the two copies of its state, its pinned hop rows and peaks
         for (float *&p : loud.state) if (!p) POST_HIP(hipMalloc((void **)&p, S2R_LOUDNESS_STATE * sizeof(float)));
         POST_HIP(pinned_rows(loud.rows, loud.rows_dev, (size_t)(c.max_frames / S2R_LOUDNESS_MIN_HOP + 1u) * S2R_LOUDNESS_CHANNELS));
         POST_HIP(pinned_rows(loud.peaks, loud.peaks_dev, (size_t)((c.max_frames + S2R_LOUDNESS_BLOCK - 1u) / S2R_LOUDNESS_BLOCK) * 2u));
@@ -123,7 +145,7 @@ hipError_t S2rPostChain::launch(const S2rPostCtx &c, const S2rPostCall &call) {
         a.partials = lm.partials_dev; a.frames = call.frames; a.lookahead = lm.lookahead; a.hold = lm.hold; a.ceiling = lm.ceiling;
         POST_TIMED(c, lm.timer, s2r_launch_limiter(a, c.stream));
     }
-    if (metered(call)) {                                         // behind whoever wrote the master last: the next state goes into the other copy
+    if (loud_on(call)) {                                         // behind whoever wrote the master last: the next state goes into the other copy
         Loudness &ld = loud;
         float *cur = ld.state[ld.cur], *next = ld.state[ld.cur ^ 1];
         if (ld.host_valid) POST_HIP(hipMemcpyAsync(cur, ld.host.data(), S2R_LOUDNESS_STATE * sizeof(float), hipMemcpyHostToDevice, c.stream));
@@ -132,6 +154,21 @@ hipError_t S2rPostChain::launch(const S2rPostCtx &c, const S2rPostCall &call) {
         a.rows = ld.rows_dev; a.peaks = ld.peaks_dev; a.n_buses = call.n_buses; a.frames = call.frames; a.hop = ld.hop; a.pos = ld.pos;
         std::memcpy(a.c, ld.c, sizeof a.c); std::memcpy(a.g, drive_taps().g, sizeof a.g);
         POST_TIMED(c, ld.timer, s2r_launch_loudness(a, c.stream));
+    }
+    if (spec_on(call)) {                                         // last: it copies the master out only when the loudness kernel has not
+        Spectrum &sp = spec;
+        const size_t n = sp.n_fft;
+        float *cur = sp.state[sp.cur], *next = sp.state[sp.cur ^ 1];
+        if (!sp.tables_valid) {                                  // (stays so until the commit)
+            POST_HIP(hipMemcpyAsync(sp.tables, sp.window.data(), n * sizeof(float), hipMemcpyHostToDevice, c.stream));
+            POST_HIP(hipMemcpyAsync(sp.tables + n, sp.twiddles.data(), n * sizeof(float), hipMemcpyHostToDevice, c.stream));
+        }
+        if (sp.host_valid) POST_HIP(hipMemcpyAsync(cur, sp.host.data(), 18u * n * sizeof(float), hipMemcpyHostToDevice, c.stream));
+        S2rSpectrum a{};
+        a.stems = r.master_in; a.master = call.limited ? r.limiter_out : r.master_out; a.out = loud_on(call) ? nullptr : c.out_host_dev;
+        a.state = cur; a.next = next; a.window = sp.tables; a.twiddles = sp.tables + n; a.rows = sp.rows_dev;
+        a.n_buses = call.n_buses; a.frames = call.frames; a.n_fft = sp.n_fft; a.hop = sp.hop; a.pos = sp.pos;
+        POST_TIMED(c, sp.timer, s2r_launch_spectrum(a, c.stream));
     }
     return hipSuccess;
 }
@@ -281,7 +318,14 @@ void S2rPostChain::commit(const S2rPostCall &call) {
         }
         lm.min_gain = mn; lm.out_peak = pk; lm.metered = true;
     }
-    if (metered(call)) {                                         // the state has moved on; the call's hops join the rows, its peaks the held ones
+    if (spec_on(call)) {                                         // the state has moved on, and the call's rows join the rows kept
+        Spectrum &sp = spec;
+        sp.cur ^= 1; sp.host_valid = false; sp.tables_valid = true;
+        const uint64_t at = (uint64_t)sp.pos + call.frames;
+        sp.append(sp.rows, (size_t)(at / sp.hop));
+        sp.pos = (uint32_t)(at % sp.hop);
+    }
+    if (loud_on(call)) {                                         // the state has moved on; the call's hops join the rows, its peaks the held ones
         Loudness &ld = loud;
         ld.cur ^= 1; ld.host_valid = false;
         const uint64_t at = (uint64_t)ld.pos + call.frames;
@@ -303,6 +347,13 @@ void S2rPostChain::Loudness::append(const float *new_rows, size_t n) {
     if (first > max_hops) { hops.erase(hops.begin(), hops.begin() + first * S2R_LOUDNESS_CHANNELS); first = 0; }      // (amortised: once per max_hops rows dropped)
 }
 
+void S2rPostChain::Spectrum::append(const float *new_rows, size_t n) {
+    const size_t rf = row_floats();
+    kept.insert(kept.end(), new_rows, new_rows + n * rf);
+    if (n_rows() > max_rows) first += n_rows() - max_rows;
+    if (first > max_rows) { kept.erase(kept.begin(), kept.begin() + first * rf); first = 0; }        // (amortised: once per max_rows rows dropped)
+}
+
 // a stage that the fill could have run and did not reads 0; a panned fill leaves all ten values alone, a bus fill the master's two
 hipError_t S2rPostChain::read_timers(const S2rPostCall &call) {
     if (call.n_buses) for (int k = 0; k < S2R_BUS_STAGES; k++) { stage[k].timer.ms = 0.0f; if (call.on[k]) POST_HIP(stage[k].timer.read()); }
@@ -311,7 +362,9 @@ hipError_t S2rPostChain::read_timers(const S2rPostCall &call) {
         limiter.timer.ms = 0.0f;
         if (call.limited) POST_HIP(limiter.timer.read());
         loud.timer.ms = 0.0f;
-        if (metered(call)) POST_HIP(loud.timer.read());
+        if (loud_on(call)) POST_HIP(loud.timer.read());
+        spec.timer.ms = 0.0f;
+        if (spec_on(call)) POST_HIP(spec.timer.read());
     }
     return hipSuccess;
 }
@@ -320,9 +373,9 @@ void S2rPostChain::release() {
     for (uint32_t b = 0; b < S2R_MAX_BUSES; b++) { drop(eq[b]); drop(dyn[b]); drop(drive[b]); drop(flanger[b]); drop(chorus[b]); drop(delay[b]); drop(fx[b]); drop(room[b]); }
     for (Stem &st : stage) { if (st.buffer) (void)hipFree(st.buffer); st.timer.destroy(); }
     // ... and what is neither a line nor a stage's buffer
-    for (float *p : {dyn_curves, drive_curves, master.stage, limiter.state[0], limiter.state[1], limiter.in, loud.state[0], loud.state[1], loud.in}) if (p) (void)hipFree(p);
-    for (float *p : {dyn_meter, master.partials, limiter.partials, loud.rows, loud.peaks}) if (p) (void)hipHostFree(p);
-    for (S2rPostTimer *t : {&master.timer, &limiter.timer, &loud.timer}) t->destroy();
+    for (float *p : {dyn_curves, drive_curves, master.stage, limiter.state[0], limiter.state[1], limiter.in, loud.state[0], loud.state[1], loud.in, spec.state[0], spec.state[1], spec.tables}) if (p) (void)hipFree(p);
+    for (float *p : {dyn_meter, master.partials, limiter.partials, loud.rows, loud.peaks, spec.rows}) if (p) (void)hipHostFree(p);
+    for (S2rPostTimer *t : {&master.timer, &limiter.timer, &loud.timer, &spec.timer}) t->destroy();
 }
 
 hipError_t S2rPostChain::set_eq(const S2rPostCtx &c, uint32_t bus, uint32_t n_bands, const float *coeffs) {
@@ -531,5 +584,39 @@ hipError_t S2rPostChain::fetch_loudness_state(const S2rPostCtx &c) {
     POST_HIP(hipStreamSynchronize(c.stream));
     loud.host.swap(st);
     loud.host_valid = true;
+    return hipSuccess;
+}
+
+void S2rPostChain::set_spectrum(uint32_t n_fft, uint32_t hop, const float *window, uint32_t max_rows) {
+    Spectrum &sp = spec;
+    sp.tables_valid = false;
+    if (!window) { sp.n_fft = sp.hop = sp.max_rows = 0; sp.window.clear(); sp.twiddles.clear(); }
+    else {
+        sp.n_fft = n_fft; sp.hop = hop; sp.max_rows = max_rows;
+        sp.window.assign(window, window + n_fft);
+        sp.twiddles.assign(n_fft, 0.0f);
+        (void)s2r_spectrum_twiddles(n_fft, sp.twiddles.data());
+    }
+    reset_spectrum();
+    if (!window) { sp.host.clear(); sp.host_valid = false; }
+}
+
+void S2rPostChain::reset_spectrum() {
+    Spectrum &sp = spec;
+    sp.host.assign(18u * (size_t)sp.n_fft, 0.0f); sp.host_valid = true; sp.pos = 0;
+    sp.kept.clear(); sp.first = 0;
+}
+
+void S2rPostChain::set_spectrum_state(const float *state, uint32_t pos) {
+    spec.host.assign(state, state + 18u * (size_t)spec.n_fft);
+    spec.host_valid = true; spec.pos = pos;
+}
+
+hipError_t S2rPostChain::fetch_spectrum_state(const S2rPostCtx &c) {
+    std::vector<float> st(18u * (size_t)spec.n_fft);
+    POST_HIP(hipMemcpyAsync(st.data(), spec.state[spec.cur], st.size() * sizeof(float), hipMemcpyDeviceToHost, c.stream));
+    POST_HIP(hipStreamSynchronize(c.stream));
+    spec.host.swap(st);
+    spec.host_valid = true;
     return hipSuccess;
 }

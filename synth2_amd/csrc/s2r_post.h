@@ -1,7 +1,7 @@
 // s2r_post.h — the chain behind the bus mixdown of s2r_fill_buses and s2r_fill_master: the eight bus stages in the order of
 // S2rBusStage (s2r_post_route.h) — the buses' equalisers, their dynamics (4.22), drives (4.24), flangers (4.25),
 // choruses (4.20), feedback delays (4.19), convolution reverbs (4.16) and rooms (4.23) —, then the master section (4.17) and the master
-// limiter (4.18), and behind it the loudness and true-peak meters (4.26).  The chain owns what these stages own and knows nothing of the handle: its functions take a S2rPostCtx and return
+// limiter (4.18), and behind it the loudness and true-peak meters (4.26) and the spectrum meters (4.27).  The chain owns what these stages own and knows nothing of the handle: its functions take a S2rPostCtx and return
 // the HIP error.  Per call: prepare, launch, — the caller's synchronise — commit, read_timers.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -171,7 +171,37 @@ struct S2rPostChain {
         const float *stored() const { return hops.data() + first * S2R_LOUDNESS_CHANNELS; }
         void append(const float *new_rows, size_t n);            // ... and drop the oldest past max_hops
     } loud;
-    bool metered(const S2rPostCall &call) const { return call.master && loud.hop != 0; }
+    // The spectrum meters (s2r_set_master_spectrum), behind the loudness meters.  As theirs: nothing is allocated before
+    // the first master fill that finds the meter set — and what is allocated then is sized by n_fft and hop, and grown by a later fill
+    // that finds them larger —, and a handle on which it never was set makes the launches it always did.
+    struct Spectrum {
+        uint32_t n_fft = 0, hop = 0, max_rows = 0;               // n_fft 0: off
+        std::vector<float> window, twiddles;     // [n_fft] and [n_fft / 2][2], the host's; the device's copy is good while tables_valid
+        bool tables_valid = false;
+        // The state's 18 * n_fft floats live in `host` while host_valid (set, reset or restored since the last fill) and in state[cur]
+        // otherwise; `pos`, the frames of the hop under way, is the host's alone and a kernel argument.
+        std::vector<float> host;
+        bool host_valid = false;
+        uint32_t pos = 0;
+        float *state[2] = {nullptr, nullptr};    // device memory, state_floats each
+        size_t state_floats = 0;
+        int cur = 0;
+        float *tables = nullptr;                 // device memory: window [n_fft], then twiddles [n_fft / 2][2]; tables_floats in all
+        size_t tables_floats = 0;
+        float *rows = nullptr, *rows_dev = nullptr;              // pinned and device-mapped: [max_frames / hop + 1][9][n_fft / 2 + 1], rows_floats
+        size_t rows_floats = 0;
+        std::vector<float> kept;                 // the rows kept, oldest first, from row `first` on: at most max_rows of them
+        size_t first = 0;
+        S2rPostTimer timer;                      // around the spectrum kernel of the last master fill: 0 when it ran none (tools/spectrum_time.py)
+        size_t row_floats() const { return S2R_SPECTRUM_ROW(n_fft); }
+        size_t n_rows() const { return n_fft ? kept.size() / row_floats() - first : 0; }
+        const float *stored() const { return kept.data() + first * row_floats(); }
+        void append(const float *new_rows, size_t n);            // ... and drop the oldest past max_rows
+    } spec;
+    bool loud_on(const S2rPostCall &call) const { return call.master && loud.hop != 0; }
+    bool spec_on(const S2rPostCall &call) const { return call.master && spec.n_fft != 0; }
+    // a meter behind the master: whoever writes the master last writes it to device memory (loud.in), and the first meter kernel copies it out
+    bool metered(const S2rPostCall &call) const { return loud_on(call) || spec_on(call); }
     // one fill: what it runs, its once-only allocations and its route; the launches in order, each between its timer's marks; after
     // the synchronise that succeeded, and only then, histories, applied values and state move on and the meters fold
     hipError_t prepare(const S2rPostCtx &c, uint32_t n_buses, uint32_t frames, bool master_fill, bool stems, S2rPostCall &call);
@@ -215,4 +245,8 @@ struct S2rPostChain {
     void reset_loudness();                                          // state, rows and held true peak; the parameters stay
     void set_loudness_state(const float *state, uint32_t pos);
     hipError_t fetch_loudness_state(const S2rPostCtx &c);           // the device's copy into `host`, kept until the next fill
+    void set_spectrum(uint32_t n_fft, uint32_t hop, const float *window, uint32_t max_rows);   // window null: off; else on, from the initial state
+    void reset_spectrum();                                          // state and rows; the parameters stay
+    void set_spectrum_state(const float *state, uint32_t pos);
+    hipError_t fetch_spectrum_state(const S2rPostCtx &c);           // the device's copy into `host`, kept until the next fill
 };

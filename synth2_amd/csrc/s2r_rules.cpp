@@ -651,3 +651,151 @@ int s2r_loudness_readings(const float *rows, size_t n_hops, uint32_t hop, uint32
 }
 
 }  // extern "C"
+
+// ---- the master's spectrum meter: window and twiddle tables, the radix-2 transform, and the readings from the rows ----
+extern "C" {
+
+int s2r_spectrum_window(uint32_t kind, uint32_t n_fft, float *window) {
+    if (kind > S2R_WINDOW_BLACKMAN_HARRIS || !spectrum_fft_in_range(n_fft)) return S2R_ERR_PATCH_RANGE;
+    if (!window) return S2R_ERR_INVALID;
+    const double PI = 3.14159265358979323846;
+    for (uint32_t i = 0; i < n_fft; i++) {
+        const double x = 2.0 * PI * ((double)i / (double)n_fft);
+        double w = 1.0;
+        if (kind == S2R_WINDOW_HANN) w = 0.5 - 0.5 * std::cos(x);
+        else if (kind == S2R_WINDOW_HAMMING) w = 0.54 - 0.46 * std::cos(x);
+        else if (kind == S2R_WINDOW_BLACKMAN_HARRIS) w = 0.35875 - 0.48829 * std::cos(x) + 0.14128 * std::cos(2.0 * x) - 0.01168 * std::cos(3.0 * x);
+        window[i] = (float)w;
+    }
+    return S2R_OK;
+}
+
+int s2r_spectrum_twiddles(uint32_t n_fft, float *tw) {
+    if (!spectrum_fft_in_range(n_fft)) return S2R_ERR_PATCH_RANGE;
+    if (!tw) return S2R_ERR_INVALID;
+    const double PI = 3.14159265358979323846;
+    const uint32_t N = n_fft, q = N / 4u, e = N / 8u;
+    for (uint32_t j = 0; j <= e; j++) {                          // the first octant from libm, the rest from it by symmetry
+        const double x = 2.0 * PI * ((double)j / (double)N);
+        tw[2 * j] = (float)std::cos(x);
+        tw[2 * j + 1] = j ? (float)-std::sin(x) : 0.0f;
+    }
+    for (uint32_t j = e + 1u; j <= q; j++) { tw[2 * j] = -tw[2 * (q - j) + 1]; tw[2 * j + 1] = -tw[2 * (q - j)]; }
+    for (uint32_t j = q + 1u; j < N / 2u; j++) { tw[2 * j] = tw[2 * (j - q) + 1]; tw[2 * j + 1] = -tw[2 * (j - q)]; }
+    return S2R_OK;
+}
+
+// one row of one programme: x holds the N frames, oldest first; v is [N][2] of scratch; p receives N / 2 + 1 values
+static void spectrum_row(uint32_t N, uint32_t L, const float *window, const float *tw, const float *x, float *v, float *p) {
+    for (uint32_t i = 0; i < N; i++) {
+        uint32_t r = 0;
+        for (uint32_t b = 0; b < L; b++) r |= ((i >> b) & 1u) << (L - 1u - b);
+        v[2 * r] = window[i] * x[2 * i];
+        v[2 * r + 1] = window[i] * x[2 * i + 1];
+    }
+    for (uint32_t s = 1; s <= L; s++) {
+        const uint32_t m = 1u << s, h = m >> 1, step = N / m;
+        for (uint32_t g = 0; g < N; g += m)
+            for (uint32_t j = 0; j < h; j++) {
+                const float wr = tw[2 * (j * step)], wi = tw[2 * (j * step) + 1];
+                float *const a = v + 2 * (g + j), *const b = v + 2 * (g + j + h);
+                const float p0 = wr * b[0], p1 = wi * b[1], p2 = wr * b[1], p3 = wi * b[0];
+                const float tr = p0 - p1, ti = p2 + p3;
+                const float ar = a[0], ai = a[1];
+                a[0] = ar + tr; a[1] = ai + ti;
+                b[0] = ar - tr; b[1] = ai - ti;
+            }
+    }
+    for (uint32_t k = 0; k <= N / 2u; k++) {
+        const float *const a = v + 2 * k, *const b = v + 2 * ((N - k) & (N - 1u));
+        const float a0 = a[0] * a[0], a1 = a[1] * a[1], b0 = b[0] * b[0], b1 = b[1] * b[1];
+        const float sa = a0 + a1, sb = b0 + b1;
+        const float t = sa + sb;
+        p[k] = t * 0.5f;
+    }
+}
+
+int s2r_spectrum_reference(uint32_t n_fft, uint32_t hop, const float *window, const float *stems, uint32_t n_buses, const float *master_lr,
+                           uint32_t frames, float *state, uint32_t *pos, float *rows, size_t rows_capacity, size_t *n_rows) {
+    if (!spectrum_in_range(n_fft, hop, window, 1u) || n_buses > S2R_MAX_BUSES || (pos && *pos >= hop)) return S2R_ERR_PATCH_RANGE;
+    if (!window || !state || !pos || !n_rows || (frames && (!master_lr || (n_buses && !stems)))) return S2R_ERR_INVALID;
+    const size_t N = n_fft, F = frames, bins = N / 2u + 1u, row_floats = S2R_SPECTRUM_ROW(N);
+    const size_t made = ((size_t)*pos + F) / hop;
+    if (made && (!rows || rows_capacity < made * row_floats)) return S2R_ERR_INVALID;
+    const uint32_t L = spectrum_log2(n_fft);
+    std::vector<float> tw(N), x(2u * (N + F)), v(2u * N);
+    (void)s2r_spectrum_twiddles(n_fft, tw.data());
+    for (uint32_t p = 0; p < S2R_SPECTRUM_PROGRAMMES; p++) {
+        float *const st = state + (size_t)p * 2u * N;
+        const bool master = p == S2R_MAX_BUSES, fed = master || p < n_buses;
+        std::memcpy(x.data(), st, 2u * N * sizeof(float));       // the stream: the state's N frames, then the call's
+        const float *const src = master ? master_lr : (fed ? stems + (size_t)p * 2u * F : nullptr);
+        for (size_t i = 0; i < 2u * F; i++) x[2u * N + i] = fed ? src[i] : 0.0f;
+        for (size_t r = 0; r < made; r++) {
+            float *const out = rows + r * row_floats + (size_t)p * bins;
+            const size_t first = (r + 1u) * hop - *pos;          // the row's oldest frame in x: it ends at frame (r + 1) hop - pos - 1 of the call
+            if (fed) spectrum_row(n_fft, L, window, tw.data(), x.data() + 2u * first, v.data(), out);
+            else for (size_t k = 0; k < bins; k++) out[k] = 0.0f;
+        }
+        std::memcpy(st, x.data() + 2u * F, 2u * N * sizeof(float));
+    }
+    *pos = (uint32_t)(((size_t)*pos + F) % hop);
+    *n_rows = made;
+    return S2R_OK;
+}
+
+// q[k] of the host rule over the last n_avg rows of one programme
+static int spectrum_q(const float *rows, size_t n_rows, uint32_t n_fft, const float *window, uint32_t programme, uint32_t n_avg, std::vector<double> &q) {
+    if (!spectrum_fft_in_range(n_fft) || programme >= S2R_SPECTRUM_PROGRAMMES || n_avg == 0u || n_avg > n_rows) return S2R_ERR_PATCH_RANGE;
+    if (!rows || !window) return S2R_ERR_INVALID;
+    const size_t N = n_fft, bins = N / 2u + 1u, row_floats = S2R_SPECTRUM_ROW(N);
+    double s1 = 0.0;
+    for (size_t i = 0; i < N; i++) s1 = s1 + (double)window[i];
+    q.resize(bins);
+    for (size_t k = 0; k < bins; k++) {
+        double sum = 0.0;
+        for (size_t r = n_rows - n_avg; r < n_rows; r++) sum = sum + (double)rows[r * row_floats + (size_t)programme * bins + k];
+        const double c = (k == 0 || k == N / 2u) ? 0.5 : 2.0;
+        q[k] = c * (sum / (double)n_avg) / (s1 * s1);
+    }
+    return S2R_OK;
+}
+
+int s2r_spectrum_readings(const float *rows, size_t n_rows, uint32_t n_fft, const float *window, uint32_t programme, uint32_t n_avg, double *out_db,
+                          size_t capacity) {
+    std::vector<double> q;
+    const int rc = spectrum_q(rows, n_rows, n_fft, window, programme, n_avg, q);
+    if (rc != S2R_OK) return rc;
+    if (!out_db || capacity < q.size()) return S2R_ERR_INVALID;
+    for (size_t k = 0; k < q.size(); k++) out_db[k] = 10.0 * std::log10(q[k]);     // (log10(0) is -inf: silence reads -inf)
+    return S2R_OK;
+}
+
+int s2r_spectrum_band_readings(const float *rows, size_t n_rows, uint32_t n_fft, const float *window, uint32_t programme, uint32_t n_avg, double sample_rate,
+                               uint32_t bands_per_octave, double *out_db, double *centres, size_t capacity, size_t *n_bands) {
+    const uint32_t bpo = bands_per_octave;
+    if ((bpo != 1u && bpo != 3u && bpo != 6u && bpo != 12u) || !(sample_rate > 0.0) || !std::isfinite(sample_rate)) return S2R_ERR_PATCH_RANGE;
+    std::vector<double> q;
+    const int rc = spectrum_q(rows, n_rows, n_fft, window, programme, n_avg, q);
+    if (rc != S2R_OK) return rc;
+    if (!out_db || !n_bands) return S2R_ERR_INVALID;
+    const double df = sample_rate / (double)n_fft, down = std::exp2(-1.0 / (2.0 * bpo)), up = std::exp2(1.0 / (2.0 * bpo));
+    std::vector<double> db, fc;
+    for (int i = -64 * (int)bpo; i <= 64 * (int)bpo; i++) {
+        const double centre = 1000.0 * std::exp2((double)i / (double)bpo), lo = centre * down, hi = centre * up;
+        if (!(lo >= df && hi <= sample_rate / 2.0)) continue;
+        double power = 0.0;
+        for (size_t k = 0; k < q.size(); k++) {
+            const double b0 = ((double)k - 0.5) * df, b1 = ((double)k + 0.5) * df;
+            const double a = lo > b0 ? lo : b0, b = hi < b1 ? hi : b1;
+            if (b > a) power = power + q[k] * ((b - a) / df);
+        }
+        db.push_back(10.0 * std::log10(power)); fc.push_back(centre);
+    }
+    if (capacity < db.size()) return S2R_ERR_INVALID;
+    for (size_t i = 0; i < db.size(); i++) { out_db[i] = db[i]; if (centres) centres[i] = fc[i]; }
+    *n_bands = db.size();
+    return S2R_OK;
+}
+
+}  // extern "C"

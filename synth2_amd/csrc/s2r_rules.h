@@ -139,6 +139,20 @@ enum { S2R_LOUD_FILT = 0, S2R_LOUD_SUMS = 72, S2R_LOUD_HIST = 90, S2R_LOUD_HIST_
 static_assert(S2R_LOUD_HIST + 2 * S2R_LOUD_HIST_FRAMES == S2R_LOUDNESS_STATE && S2R_LOUD_SUMS == 4 * S2R_LOUDNESS_CHANNELS, "the layout s2r.h states");
 static_assert(4 * S2R_LOUD_HIST_FRAMES + 1 == S2R_DRIVE_TAPS, "phase 0 of the interpolator reaches 16 frames back");
 
+// the master's spectrum meter: a power-of-two size, the hop and the rows kept in their ranges, a finite window.  A null
+// window passes: the caller refuses it by another name.
+static inline bool spectrum_fft_in_range(uint32_t n) { return n >= S2R_SPECTRUM_MIN_FFT && n <= S2R_SPECTRUM_MAX_FFT && (n & (n - 1u)) == 0u; }
+static inline bool spectrum_hop_in_range(uint32_t n, uint32_t hop) {
+    const uint32_t lo = n / 8u > S2R_SPECTRUM_MIN_HOP ? n / 8u : S2R_SPECTRUM_MIN_HOP;
+    return hop >= lo && hop <= S2R_SPECTRUM_MAX_HOP;
+}
+static inline bool spectrum_in_range(uint32_t n, uint32_t hop, const float *window, uint32_t max_rows) {
+    if (!spectrum_fft_in_range(n) || !spectrum_hop_in_range(n, hop) || max_rows < 1u || max_rows > S2R_SPECTRUM_MAX_ROWS) return false;
+    for (uint32_t i = 0; i < n && window; i++) if (!std::isfinite(window[i])) return false;
+    return true;
+}
+static inline uint32_t spectrum_log2(uint32_t n) { uint32_t l = 0; while ((1u << l) < n) l++; return l; }
+
 // The voice mixer's gain rules, inline: the host's per-voice loops compile them in — a call per voice into s2r_rules.cpp showed as 10
 // to 15 us of host time per fill of 65 536 voices (profiles/r12/post_chain.txt).  s2r_rules.cpp exports them under their s2r.h names.
 static inline float rule_voice_pan(float pan, float key_spread, uint8_t note) {

@@ -64,6 +64,13 @@ LOUDNESS_CHANNELS = 18                      # S2R_LOUDNESS_CHANNELS
 LOUDNESS_STATE = 122                        # S2R_LOUDNESS_STATE
 LOUDNESS_MIN_HOP, LOUDNESS_MAX_HOP = 16, 1 << 20      # S2R_LOUDNESS_MIN_HOP, S2R_LOUDNESS_MAX_HOP
 LOUDNESS_MIN_HOPS, LOUDNESS_MAX_HOPS = 30, 1 << 18    # S2R_LOUDNESS_MIN_HOPS, S2R_LOUDNESS_MAX_HOPS
+SPECTRUM_PROGRAMMES = 9                     # S2R_SPECTRUM_PROGRAMMES: the buses, then the master
+SPECTRUM_MIN_FFT, SPECTRUM_MAX_FFT = 256, 8192        # S2R_SPECTRUM_MIN_FFT, S2R_SPECTRUM_MAX_FFT
+SPECTRUM_MIN_HOP, SPECTRUM_MAX_HOP = 16, 1 << 20      # S2R_SPECTRUM_MIN_HOP, S2R_SPECTRUM_MAX_HOP (and at least n_fft / 8)
+SPECTRUM_MAX_ROWS = 256                     # S2R_SPECTRUM_MAX_ROWS
+WINDOW_RECT, WINDOW_HANN, WINDOW_HAMMING, WINDOW_BLACKMAN_HARRIS = 0, 1, 2, 3      # S2R_WINDOW_*
+_WINDOW_KINDS = {"rect": WINDOW_RECT, "rectangular": WINDOW_RECT, "hann": WINDOW_HANN, "hamming": WINDOW_HAMMING,
+                 "blackman-harris": WINDOW_BLACKMAN_HARRIS, "blackmanharris": WINDOW_BLACKMAN_HARRIS}
 
 
 class S2rError(RuntimeError):
@@ -312,6 +319,24 @@ def load_library():
                                              C.POINTER(C.c_size_t), _f32p]),
         "s2r_loudness_readings": (C.c_int, [_f32p, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(C.c_double)]),
         "s2r_loudness_design": (C.c_int, [C.c_double, _f32p]),
+        "s2r_set_master_spectrum": (C.c_int, [H, C.c_uint32, C.c_uint32, _f32p, C.c_uint32]),
+        "s2r_clear_master_spectrum": (C.c_int, [H]),
+        "s2r_get_master_spectrum": (C.c_int, [H, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_size_t), _f32p, C.c_size_t]),
+        "s2r_reset_master_spectrum": (C.c_int, [H]),
+        "s2r_get_spectrum": (C.c_int, [H, C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.c_size_t]),
+        "s2r_get_spectrum_bands": (C.c_int, [H, C.c_uint32, C.c_uint32, C.c_double, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_size_t,
+                                             C.POINTER(C.c_size_t)]),
+        "s2r_get_spectrum_rows": (C.c_int, [H, _f32p, C.c_size_t, C.POINTER(C.c_size_t)]),
+        "s2r_set_spectrum_rows": (C.c_int, [H, _f32p, C.c_size_t, C.c_size_t]),
+        "s2r_get_spectrum_state": (C.c_int, [H, _f32p, C.c_size_t, C.POINTER(C.c_uint32)]),
+        "s2r_set_spectrum_state": (C.c_int, [H, _f32p, C.c_size_t, C.c_uint32]),
+        "s2r_spectrum_reference": (C.c_int, [C.c_uint32, C.c_uint32, _f32p, _f32p, C.c_uint32, _f32p, C.c_uint32, _f32p, C.POINTER(C.c_uint32), _f32p, C.c_size_t,
+                                             C.POINTER(C.c_size_t)]),
+        "s2r_spectrum_readings": (C.c_int, [_f32p, C.c_size_t, C.c_uint32, _f32p, C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.c_size_t]),
+        "s2r_spectrum_band_readings": (C.c_int, [_f32p, C.c_size_t, C.c_uint32, _f32p, C.c_uint32, C.c_uint32, C.c_double, C.c_uint32, C.POINTER(C.c_double),
+                                                 C.POINTER(C.c_double), C.c_size_t, C.POINTER(C.c_size_t)]),
+        "s2r_spectrum_window": (C.c_int, [C.c_uint32, C.c_uint32, _f32p]),
+        "s2r_spectrum_twiddles": (C.c_int, [C.c_uint32, _f32p]),
         "s2r_fill_device": (C.c_int, [H, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
         "s2r_fill_device_root": (C.c_int, [H, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
         "s2r_sum_partials_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_size_t, C.c_void_p, C.c_void_p]),
@@ -769,6 +794,92 @@ def loudness_readings(rows, hop, programme):
     out = (C.c_double * 3)()
     _rule_check(load_library().s2r_loudness_readings(rows.ctypes.data_as(_f32p) if rows.shape[0] else None, rows.shape[0], int(hop), int(programme), out))
     return out[0], out[1], out[2]
+
+
+def spectrum_window(kind, n_fft):
+    """the periodic window `kind` ('rect', 'hann', 'hamming', 'blackman-harris' or a WINDOW_* value) of n_fft points
+    (s2r_spectrum_window): float32 [n_fft]"""
+    k = _WINDOW_KINDS.get(kind.lower(), -1) if isinstance(kind, str) else int(kind)
+    if k < 0:
+        raise ValueError("spectrum_window: kind is one of %s" % sorted(_WINDOW_KINDS))
+    w = np.empty(max(int(n_fft), 0), dtype=np.float32)
+    _rule_check(load_library().s2r_spectrum_window(k, int(n_fft), w.ctypes.data_as(_f32p)))
+    return w
+
+
+def spectrum_twiddles(n_fft):
+    """the spectrum meter's twiddle table (s2r_spectrum_twiddles): float32 [n_fft / 2, 2], (re, im)"""
+    t = np.empty((max(int(n_fft), 0) // 2, 2), dtype=np.float32)
+    _rule_check(load_library().s2r_spectrum_twiddles(int(n_fft), t.ctypes.data_as(_f32p)))
+    return t
+
+
+def _spectrum_window_arg(window, n_fft):
+    if isinstance(window, str) or np.isscalar(window):
+        return spectrum_window(window, n_fft)
+    w = np.ascontiguousarray(window, dtype=np.float32).reshape(-1)
+    if w.size != int(n_fft):
+        raise ValueError("the window holds n_fft values")
+    return w
+
+
+def spectrum_reference(n_fft, hop, window, stems, master, state=None, pos=0):
+    """the spectrum meter's device rule on the host (s2r_spectrum_reference): stems [n_buses, frames, 2] float32 (None: no buses),
+    master [frames, 2]; state [9, n_fft, 2] and pos what the call starts from (None: the initial state).  Returns (rows
+    [k, 9, n_fft / 2 + 1] — the rows the call completes —, state, pos); the arguments are not modified."""
+    n_fft, hop = int(n_fft), int(hop)
+    window = _spectrum_window_arg(window, n_fft)
+    master = np.ascontiguousarray(master, dtype=np.float32)
+    if master.ndim != 2 or master.shape[1] != 2:
+        raise ValueError("spectrum_reference: master is [frames, 2]")
+    frames = master.shape[0]
+    if stems is None:
+        stems = np.zeros((0, frames, 2), dtype=np.float32)
+    stems = np.ascontiguousarray(stems, dtype=np.float32)
+    if stems.ndim != 3 or stems.shape[1:] != (frames, 2):
+        raise ValueError("spectrum_reference: stems is [n_buses, frames, 2]")
+    state = np.zeros(18 * n_fft, dtype=np.float32) if state is None else np.array(state, dtype=np.float32, order="C").reshape(-1)
+    if state.size != 18 * n_fft:
+        raise ValueError("spectrum_reference: state is [9, n_fft, 2]")
+    bins, at = n_fft // 2 + 1, C.c_uint32(int(pos))
+    cap = ((int(pos) + frames) // max(hop, 1) + 1) * SPECTRUM_PROGRAMMES * bins
+    rows, n = np.zeros(cap, dtype=np.float32), C.c_size_t(0)
+    _rule_check(load_library().s2r_spectrum_reference(n_fft, hop, window.ctypes.data_as(_f32p), stems.ctypes.data_as(_f32p) if stems.shape[0] else None,
+                                                      stems.shape[0], master.ctypes.data_as(_f32p), frames, state.ctypes.data_as(_f32p), C.byref(at),
+                                                      rows.ctypes.data_as(_f32p), rows.size, C.byref(n)))
+    return rows[:n.value * SPECTRUM_PROGRAMMES * bins].reshape(-1, SPECTRUM_PROGRAMMES, bins).copy(), state.reshape(SPECTRUM_PROGRAMMES, n_fft, 2), at.value
+
+
+def _spectrum_rows_arg(rows, n_fft):
+    bins = int(n_fft) // 2 + 1
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    if bins < 2 or rows.size % (SPECTRUM_PROGRAMMES * bins):
+        raise ValueError("the rows are [n_rows, 9, n_fft / 2 + 1]")
+    return rows.reshape(-1, SPECTRUM_PROGRAMMES, bins)
+
+
+def spectrum_readings(rows, window, programme, n_avg=1):
+    """dB per bin of one programme over the last n_avg of rows [n_rows, 9, n_fft / 2 + 1] (s2r_spectrum_readings): float64
+    [n_fft / 2 + 1]; 0 dB is a bin-centred sine of amplitude 1 on both channels; silence reads -inf"""
+    window = np.ascontiguousarray(window, dtype=np.float32).reshape(-1)
+    rows = _spectrum_rows_arg(rows, window.size)
+    out = np.empty(window.size // 2 + 1, dtype=np.float64)
+    _rule_check(load_library().s2r_spectrum_readings(rows.ctypes.data_as(_f32p) if rows.shape[0] else None, rows.shape[0], window.size,
+                                                     window.ctypes.data_as(_f32p), int(programme), int(n_avg), out.ctypes.data_as(C.POINTER(C.c_double)), out.size))
+    return out
+
+
+def spectrum_band_readings(rows, window, programme, sample_rate, bands_per_octave, n_avg=1):
+    """(dB [n_bands], centres in Hz [n_bands]) of one programme over the last n_avg rows (s2r_spectrum_band_readings)"""
+    window = np.ascontiguousarray(window, dtype=np.float32).reshape(-1)
+    rows = _spectrum_rows_arg(rows, window.size)
+    cap = 256
+    db, fc, n = np.empty(cap, dtype=np.float64), np.empty(cap, dtype=np.float64), C.c_size_t(0)
+    dp = C.POINTER(C.c_double)
+    _rule_check(load_library().s2r_spectrum_band_readings(rows.ctypes.data_as(_f32p) if rows.shape[0] else None, rows.shape[0], window.size,
+                                                          window.ctypes.data_as(_f32p), int(programme), int(n_avg), float(sample_rate), int(bands_per_octave),
+                                                          db.ctypes.data_as(dp), fc.ctypes.data_as(dp), cap, C.byref(n)))
+    return db[:n.value].copy(), fc[:n.value].copy()
 
 
 def stream_frame_json(samples):
@@ -1610,6 +1721,87 @@ class Synth:
     @staticmethod
     def loudness_design(sample_rate=48000.0):
         return loudness_design(sample_rate)
+
+    # --- the spectrum meters (build-defined; s2r.h: s2r_set_master_spectrum) ---
+    def set_master_spectrum(self, n_fft, hop, window="hann", max_rows=16):
+        """a windowed power spectrum of every bus and the master, behind the loudness meters, in sample_master only.  `n_fft`: a power
+        of two, 256 .. 8192; `hop`: frames between rows, at least n_fft / 8; `window`: a kind for spectrum_window or n_fft values;
+        `max_rows`: the rows kept (1 .. 256).  Starts from the initial state with no rows."""
+        w = _spectrum_window_arg(window, n_fft) if 0 < int(n_fft) <= (1 << 20) else np.zeros(1, dtype=np.float32)
+        self._check(self.L.s2r_set_master_spectrum(self.h, int(n_fft), int(hop), w.ctypes.data_as(_f32p), int(max_rows)))
+
+    def clear_master_spectrum(self):
+        self._check(self.L.s2r_clear_master_spectrum(self.h))
+
+    def get_master_spectrum(self):
+        """(n_fft, hop, max_rows, n_rows, window [n_fft]): an n_fft of 0 means off; n_rows the rows stored"""
+        n, h, m, k = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_size_t()
+        self._check(self.L.s2r_get_master_spectrum(self.h, C.byref(n), C.byref(h), C.byref(m), C.byref(k), None, 0))
+        w = np.empty(n.value, dtype=np.float32)
+        if n.value:
+            self._check(self.L.s2r_get_master_spectrum(self.h, None, None, None, None, w.ctypes.data_as(_f32p), w.size))
+        return n.value, h.value, m.value, k.value, w
+
+    def reset_master_spectrum(self):
+        """state and rows cleared; the parameters stay"""
+        self._check(self.L.s2r_reset_master_spectrum(self.h))
+
+    def spectrum(self, programme=MAX_BUSES, n_avg=1):
+        """dB per bin [n_fft / 2 + 1] of bus `programme`, or of the master (MAX_BUSES), over the last n_avg stored rows"""
+        out = np.empty(self.get_master_spectrum()[0] // 2 + 1, dtype=np.float64)
+        self._check(self.L.s2r_get_spectrum(self.h, int(programme), int(n_avg), out.ctypes.data_as(C.POINTER(C.c_double)), out.size))
+        return out
+
+    def spectrum_bands(self, programme, sample_rate, bands_per_octave, n_avg=1):
+        """(dB [n_bands], centres in Hz [n_bands]) per fractional-octave band over the last n_avg stored rows"""
+        cap = 256
+        db, fc, n = np.empty(cap, dtype=np.float64), np.empty(cap, dtype=np.float64), C.c_size_t(0)
+        dp = C.POINTER(C.c_double)
+        self._check(self.L.s2r_get_spectrum_bands(self.h, int(programme), int(n_avg), float(sample_rate), int(bands_per_octave), db.ctypes.data_as(dp),
+                                                  fc.ctypes.data_as(dp), cap, C.byref(n)))
+        return db[:n.value].copy(), fc[:n.value].copy()
+
+    def spectrum_rows(self):
+        """the stored rows, oldest first: [n_rows, 9, n_fft / 2 + 1] float32 (checkpoints)"""
+        n_fft, _, _, n, _ = self.get_master_spectrum()
+        rows, got = np.empty((n, SPECTRUM_PROGRAMMES, n_fft // 2 + 1), dtype=np.float32), C.c_size_t()
+        self._check(self.L.s2r_get_spectrum_rows(self.h, rows.ctypes.data_as(_f32p) if n else None, rows.size, C.byref(got)))
+        return rows[:got.value]
+
+    def set_spectrum_rows(self, rows):
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        self._check(self.L.s2r_set_spectrum_rows(self.h, rows.ctypes.data_as(_f32p) if rows.size else None, rows.shape[0] if rows.ndim == 3 else 0, rows.size))
+
+    def spectrum_state(self):
+        """(state [9, n_fft, 2], pos): the last n_fft frames of every programme, oldest first; the frames of the hop under way"""
+        n_fft = self.get_master_spectrum()[0]
+        st, pos = np.empty((SPECTRUM_PROGRAMMES, n_fft, 2), dtype=np.float32), C.c_uint32()
+        self._check(self.L.s2r_get_spectrum_state(self.h, st.ctypes.data_as(_f32p), st.size, C.byref(pos)))
+        return st, pos.value
+
+    def set_spectrum_state(self, state, pos):
+        st = np.ascontiguousarray(state, dtype=np.float32)
+        self._check(self.L.s2r_set_spectrum_state(self.h, st.ctypes.data_as(_f32p), st.size, int(pos)))
+
+    @staticmethod
+    def spectrum_reference(n_fft, hop, window, stems, master, state=None, pos=0):
+        return spectrum_reference(n_fft, hop, window, stems, master, state, pos)
+
+    @staticmethod
+    def spectrum_readings(rows, window, programme, n_avg=1):
+        return spectrum_readings(rows, window, programme, n_avg)
+
+    @staticmethod
+    def spectrum_band_readings(rows, window, programme, sample_rate, bands_per_octave, n_avg=1):
+        return spectrum_band_readings(rows, window, programme, sample_rate, bands_per_octave, n_avg)
+
+    @staticmethod
+    def spectrum_window(kind, n_fft):
+        return spectrum_window(kind, n_fft)
+
+    @staticmethod
+    def spectrum_twiddles(n_fft):
+        return spectrum_twiddles(n_fft)
 
     def render_voices(self, frames, sample_rate=SampleRateKhz(48000)):
         """Mix disabled: (shard_voices, frames) float32."""
