@@ -355,7 +355,7 @@ class Synth {
                         size_t *n_bands) const {
         check(s2r_get_spectrum_bands(h_, programme, n_avg, sample_rate, bands_per_octave, out_db, centres, capacity, n_bands));
     }
-    // rows: [n_rows][9][n_fft / 2 + 1]; state: 18 * n_fft floats (checkpoints)
+    // rows: [n_rows][9][n_fft / 2 + 1]; state: S2R_SPECTRUM_STATE(n_fft) floats (checkpoints)
     void spectrum_rows(float *rows, size_t capacity, size_t *n_rows) const { check(s2r_get_spectrum_rows(h_, rows, capacity, n_rows)); }
     void set_spectrum_rows(const float *rows, size_t n_rows, size_t count) { check(s2r_set_spectrum_rows(h_, rows, n_rows, count)); }
     void spectrum_state(float *state, size_t capacity, uint32_t *pos) { check(s2r_get_spectrum_state(h_, state, capacity, pos)); }

@@ -984,7 +984,7 @@ int s2r_loudness_design(double sample_rate, float coeffs[10]);
  * recent frames ending at that frame, oldest first: z[i] = (window[i] * L[i], window[i] * R[i]), one complex transform for both
  * channels.  A row is [9][N / 2 + 1] floats, S2R_SPECTRUM_ROW(N) of them.
  * STATE carried from call to call: the last N frames of all nine programmes, [9][N][2] floats (programme, frame oldest first, L then
- * R), 18 * N of them, and pos < hop.  All +0.0 / 0 right after a set or a reset.
+ * R), S2R_SPECTRUM_STATE(N) = 18 * N of them, and pos < hop.  All +0.0 / 0 right after a set or a reset.
  * DEVICE RULE, binary32, every operation rounded on its own, no fma, denormals kept.
  *   TWIDDLES T[j], j < N / 2 (s2r_spectrum_twiddles), computed by the host, read by the device:
  *     j <= N / 8:          T[j] = (cos(2 pi j / N), -sin(2 pi j / N)) in binary64, each rounded to nearest binary32; T[0].im is +0.0
@@ -1047,6 +1047,7 @@ int s2r_loudness_design(double sample_rate, float coeffs[10]);
 #define S2R_SPECTRUM_MAX_HOP (1u << 20)
 #define S2R_SPECTRUM_MAX_ROWS 256u
 #define S2R_SPECTRUM_ROW(n_fft) ((size_t)S2R_SPECTRUM_PROGRAMMES * ((size_t)(n_fft) / 2u + 1u))
+#define S2R_SPECTRUM_STATE(n_fft) ((size_t)S2R_SPECTRUM_PROGRAMMES * 2u * (size_t)(n_fft))
 #define S2R_WINDOW_RECT 0u
 #define S2R_WINDOW_HANN 1u
 #define S2R_WINDOW_HAMMING 2u

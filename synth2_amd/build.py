@@ -28,7 +28,7 @@ SOURCES = ["s2r_render_onepole_square.hip", "s2r_render_onepole_saw.hip", "s2r_r
            "s2r_loudness.hip",  # (likewise, since the loudness meters came)
            "s2r_spectrum.hip"]  # (last, likewise, since the spectrum meters came)
 HEADERS = ["s2r_device.h", "s2r_math.h", "s2r_patch.h", "s2r_voices.h", "s2r_kern_common.h", "s2r_render_onepole.inc",
-           "s2r_render_general.inc", "s2r_post.h", "s2r_post_route.h", "s2r_rules.h"]
+           "s2r_render_general.inc", "s2r_post.h", "s2r_post_route.h", "s2r_post_keep.h", "s2r_rules.h"]
 
 # -amdgpu-sched-strategy=max-ilp: the render kernels run one wavefront per SIMD (64 k voices =
 # 1024 waves), so nothing hides a dependent instruction's latency except independent work of the

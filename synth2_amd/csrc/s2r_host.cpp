@@ -3294,6 +3294,16 @@ int s2r_get_master_limiter(const s2r_synth *s, float *ceiling, uint32_t *lookahe
     return S2R_OK;
 }
 
+// A master stage's state for a getter: where the device holds it, it is fetched once into the stage's host copy, and kept until the next fill.
+static int mirror_fetch(s2r_synth *s, S2rMirror &m, const char *who) {
+    if (m.host_valid) return S2R_OK;
+    if (s->ring_count) return set_err(s, S2R_ERR_INVALID, "%s with fills of s2r_fill_begin in flight: s2r_fill_end first", who);
+    S2R_QUIESCE(s);
+    S2R_HIP(s, hipSetDevice(s->device));
+    S2R_HIP(s, m.fetch(s->stream));
+    return S2R_OK;
+}
+
 static int limiter_state(s2r_synth *s, float *get_x, float *get_g, const float *set_x, const float *set_g, size_t n_x, size_t n_g, const char *who) {
     S2R_TRY(post_handle(s, who, "the master limiter is"));
     S2rPostChain::Limiter &lm = s->post.limiter;
@@ -3309,14 +3319,9 @@ static int limiter_state(s2r_synth *s, float *get_x, float *get_g, const float *
         s->post.set_limiter_state(set_x, set_g);
         return S2R_OK;
     }
-    if (!lm.host_valid) {                                        // the device holds it: fetch it once, and keep it until the next fill
-        if (s->ring_count) return set_err(s, S2R_ERR_INVALID, "%s with fills of s2r_fill_begin in flight: s2r_fill_end first", who);
-        S2R_QUIESCE(s);
-        S2R_HIP(s, hipSetDevice(s->device));
-        S2R_HIP(s, s->post.fetch_limiter_state(post_ctx(s)));
-    }
-    std::memcpy(get_x, lm.host.data(), nx * sizeof(float));
-    std::memcpy(get_g, lm.host.data() + nx, ng * sizeof(float));
+    S2R_TRY(mirror_fetch(s, lm.state, who));
+    std::memcpy(get_x, lm.state.host.data(), nx * sizeof(float));
+    std::memcpy(get_g, lm.state.host.data() + nx, ng * sizeof(float));
     return S2R_OK;
 }
 
@@ -3331,6 +3336,67 @@ int s2r_set_limiter_state(s2r_synth *s, const float *xh, size_t n_x, const float
 int s2r_get_limiter_meters(const s2r_synth *s, float *min_gain, float *out_peak) {
     if (!s || !s->kids.empty() || s->parent || !s->post.limiter.metered) return S2R_ERR_INVALID;
     put(min_gain, s->post.limiter.min_gain); put(out_peak, s->post.limiter.out_peak);
+    return S2R_OK;
+}
+
+// ---- what the entries of the two meters behind the limiter share: their guard, their state pair and their rows pair ----
+enum { kLoudness, kSpectrum };
+static const struct { const char *are, *none, *rows; } kMeterWords[2] = {{"the loudness meter is", "no loudness meter is set", "hops"},
+                                                                         {"the spectrum meter is", "no spectrum meter is set", "rows"}};
+struct Meter { S2rMirror *state; S2rRowStore *kept; size_t floats; uint32_t *pos, hop; };        // a meter that is set, as far as the two are alike
+
+// the guard of the entries that need the meter set
+static int meter_on(const s2r_synth *s, int which, const char *who, Meter *m = nullptr) {
+    S2R_TRY(post_handle(s, who, kMeterWords[which].are));
+    S2rPostChain &p = const_cast<s2r_synth *>(s)->post;
+    const Meter is = which == kLoudness ? Meter{&p.loud.state, &p.loud.kept, S2R_LOUDNESS_STATE, &p.loud.pos, p.loud.hop}
+                                        : Meter{&p.spec.state, &p.spec.kept, S2R_SPECTRUM_STATE(p.spec.n_fft), &p.spec.pos, p.spec.hop};
+    if (!is.hop) return set_err(const_cast<s2r_synth *>(s), S2R_ERR_INVALID, "%s: %s", who, kMeterWords[which].none);
+    if (m) *m = is;
+    return S2R_OK;
+}
+
+static int meter_get_state(s2r_synth *s, int which, float *state, size_t capacity, uint32_t *pos, const char *who) {
+    Meter m;
+    S2R_TRY(meter_on(s, which, who, &m));
+    if (capacity < m.floats) return set_err(s, S2R_ERR_INVALID, "%s: the state is %zu floats, not %zu", who, m.floats, capacity);
+    if (!state) return set_err(s, S2R_ERR_INVALID, "%s: null buffer", who);
+    S2R_TRY(mirror_fetch(s, *m.state, who));
+    std::memcpy(state, m.state->host.data(), m.floats * sizeof(float));
+    put(pos, *m.pos);
+    return S2R_OK;
+}
+
+static int meter_set_state(s2r_synth *s, int which, const float *state, size_t count, uint32_t pos, const char *who) {
+    Meter m;
+    S2R_TRY(meter_on(s, which, who, &m));
+    if (count != m.floats) return set_err(s, S2R_ERR_INVALID, "%s: the state is %zu floats, not %zu", who, m.floats, count);
+    if (!state) return set_err(s, S2R_ERR_INVALID, "%s: null buffer", who);
+    if (pos >= m.hop) return set_err(s, S2R_ERR_PATCH_RANGE, "%s: position %u, below the hop of %u", who, pos, m.hop);
+    m.state->set(state, m.floats);
+    *m.pos = pos;
+    return S2R_OK;
+}
+
+static int meter_get_rows(const s2r_synth *s, int which, float *rows, size_t capacity, size_t *n_rows, const char *who) {
+    Meter m;
+    S2R_TRY(meter_on(s, which, who, &m));
+    const size_t n = m.kept->n_rows() * m.kept->width;
+    if (capacity < n || (n && !rows))
+        return set_err(const_cast<s2r_synth *>(s), S2R_ERR_INVALID, "%s: the rows are %zu floats, the buffer holds %zu", who, n, rows ? capacity : (size_t)0);
+    if (n) std::memcpy(rows, m.kept->stored(), n * sizeof(float));
+    put(n_rows, m.kept->n_rows());
+    return S2R_OK;
+}
+
+static int meter_set_rows(s2r_synth *s, int which, const float *rows, size_t n_rows, size_t count, const char *who) {
+    Meter m;
+    S2R_TRY(meter_on(s, which, who, &m));
+    const char *const word = kMeterWords[which].rows;
+    if (n_rows > m.kept->max_rows) return set_err(s, S2R_ERR_PATCH_RANGE, "%s: %zu %s, at most the %u the meter keeps", who, n_rows, word, m.kept->max_rows);
+    if (count != n_rows * m.kept->width || (count && !rows))
+        return set_err(s, S2R_ERR_INVALID, "%s: %zu %s are %zu floats, not %zu", who, n_rows, word, n_rows * m.kept->width, rows ? count : (size_t)0);
+    m.kept->assign(rows, n_rows);
     return S2R_OK;
 }
 
@@ -3355,19 +3421,12 @@ int s2r_get_master_loudness(const s2r_synth *s, float coeffs[10], uint32_t *hop,
     if (!s || !s->kids.empty() || s->parent) return S2R_ERR_INVALID;
     const S2rPostChain::Loudness &ld = s->post.loud;
     if (coeffs) std::memcpy(coeffs, ld.c, sizeof ld.c);
-    put(hop, ld.hop); put(max_hops, ld.max_hops); put(n_hops, ld.n_hops());
-    return S2R_OK;
-}
-
-// the guard of the entries that need the meter set
-static int loudness_on(const s2r_synth *s, const char *who) {
-    S2R_TRY(post_handle(s, who, "the loudness meter is"));
-    if (!s->post.loud.hop) return set_err(const_cast<s2r_synth *>(s), S2R_ERR_INVALID, "%s: no loudness meter is set", who);
+    put(hop, ld.hop); put(max_hops, ld.kept.max_rows); put(n_hops, ld.kept.n_rows());
     return S2R_OK;
 }
 
 int s2r_reset_master_loudness(s2r_synth *s) {
-    S2R_TRY(loudness_on(s, "s2r_reset_master_loudness"));
+    S2R_TRY(meter_on(s, kLoudness, "s2r_reset_master_loudness"));
     s->post.reset_loudness();
     return S2R_OK;
 }
@@ -3376,7 +3435,7 @@ int s2r_get_loudness(const s2r_synth *s, uint32_t programme, double out[3]) {
     if (programme >= S2R_LOUDNESS_PROGRAMMES) return S2R_ERR_PATCH_RANGE;
     if (!s || !s->kids.empty() || s->parent || !s->post.loud.hop || !out) return S2R_ERR_INVALID;
     const S2rPostChain::Loudness &ld = s->post.loud;
-    return s2r_loudness_readings(ld.stored(), ld.n_hops(), ld.hop, programme, out);
+    return s2r_loudness_readings(ld.kept.stored(), ld.kept.n_rows(), ld.hop, programme, out);
 }
 
 int s2r_get_true_peak(const s2r_synth *s, float last[2], float held[2]) {
@@ -3387,50 +3446,10 @@ int s2r_get_true_peak(const s2r_synth *s, float last[2], float held[2]) {
     return S2R_OK;
 }
 
-int s2r_get_loudness_state(s2r_synth *s, float *state, size_t capacity, uint32_t *pos) {
-    S2R_TRY(loudness_on(s, "s2r_get_loudness_state"));
-    S2rPostChain::Loudness &ld = s->post.loud;
-    if (capacity < S2R_LOUDNESS_STATE) return set_err(s, S2R_ERR_INVALID, "s2r_get_loudness_state: the state is %u floats, not %zu", S2R_LOUDNESS_STATE, capacity);
-    if (!state) return set_err(s, S2R_ERR_INVALID, "s2r_get_loudness_state: null buffer");
-    if (!ld.host_valid) {                                        // the device holds it: fetch it once, and keep it until the next fill
-        if (s->ring_count) return set_err(s, S2R_ERR_INVALID, "s2r_get_loudness_state with fills of s2r_fill_begin in flight: s2r_fill_end first");
-        S2R_QUIESCE(s);
-        S2R_HIP(s, hipSetDevice(s->device));
-        S2R_HIP(s, s->post.fetch_loudness_state(post_ctx(s)));
-    }
-    std::memcpy(state, ld.host.data(), S2R_LOUDNESS_STATE * sizeof(float));
-    put(pos, ld.pos);
-    return S2R_OK;
-}
-
-int s2r_set_loudness_state(s2r_synth *s, const float *state, size_t count, uint32_t pos) {
-    S2R_TRY(loudness_on(s, "s2r_set_loudness_state"));
-    if (count != S2R_LOUDNESS_STATE) return set_err(s, S2R_ERR_INVALID, "s2r_set_loudness_state: the state is %u floats, not %zu", S2R_LOUDNESS_STATE, count);
-    if (!state) return set_err(s, S2R_ERR_INVALID, "s2r_set_loudness_state: null buffer");
-    if (pos >= s->post.loud.hop) return set_err(s, S2R_ERR_PATCH_RANGE, "s2r_set_loudness_state: position %u, below the hop of %u", pos, s->post.loud.hop);
-    s->post.set_loudness_state(state, pos);
-    return S2R_OK;
-}
-
-int s2r_get_loudness_hops(const s2r_synth *s, float *rows, size_t capacity, size_t *n_hops) {
-    S2R_TRY(loudness_on(s, "s2r_get_loudness_hops"));
-    const S2rPostChain::Loudness &ld = s->post.loud;
-    const size_t n = ld.n_hops() * S2R_LOUDNESS_CHANNELS;
-    if (capacity < n || (n && !rows)) return set_err(const_cast<s2r_synth *>(s), S2R_ERR_INVALID, "s2r_get_loudness_hops: the rows are %zu floats, the buffer holds %zu", n, rows ? capacity : (size_t)0);
-    if (n) std::memcpy(rows, ld.stored(), n * sizeof(float));
-    put(n_hops, ld.n_hops());
-    return S2R_OK;
-}
-
-int s2r_set_loudness_hops(s2r_synth *s, const float *rows, size_t n_hops, size_t count) {
-    S2R_TRY(loudness_on(s, "s2r_set_loudness_hops"));
-    S2rPostChain::Loudness &ld = s->post.loud;
-    if (n_hops > ld.max_hops) return set_err(s, S2R_ERR_PATCH_RANGE, "s2r_set_loudness_hops: %zu hops, at most the %u the meter keeps", n_hops, ld.max_hops);
-    if (count != n_hops * S2R_LOUDNESS_CHANNELS || (count && !rows))
-        return set_err(s, S2R_ERR_INVALID, "s2r_set_loudness_hops: %zu hops are %zu floats, not %zu", n_hops, n_hops * S2R_LOUDNESS_CHANNELS, rows ? count : (size_t)0);
-    ld.hops.assign(rows, rows + count); ld.first = 0;
-    return S2R_OK;
-}
+int s2r_get_loudness_state(s2r_synth *s, float *state, size_t capacity, uint32_t *pos) { return meter_get_state(s, kLoudness, state, capacity, pos, "s2r_get_loudness_state"); }
+int s2r_set_loudness_state(s2r_synth *s, const float *state, size_t count, uint32_t pos) { return meter_set_state(s, kLoudness, state, count, pos, "s2r_set_loudness_state"); }
+int s2r_get_loudness_hops(const s2r_synth *s, float *rows, size_t capacity, size_t *n_hops) { return meter_get_rows(s, kLoudness, rows, capacity, n_hops, "s2r_get_loudness_hops"); }
+int s2r_set_loudness_hops(s2r_synth *s, const float *rows, size_t n_hops, size_t count) { return meter_set_rows(s, kLoudness, rows, n_hops, count, "s2r_set_loudness_hops"); }
 
 // ---- the spectrum meters behind the loudness meters ----
 int s2r_set_master_spectrum(s2r_synth *s, uint32_t n_fft, uint32_t hop, const float *window, uint32_t max_rows) {
@@ -3454,19 +3473,12 @@ int s2r_get_master_spectrum(const s2r_synth *s, uint32_t *n_fft, uint32_t *hop, 
     const S2rPostChain::Spectrum &sp = s->post.spec;
     if (window && window_capacity < sp.n_fft) return S2R_ERR_INVALID;
     if (window && sp.n_fft) std::memcpy(window, sp.window.data(), sp.n_fft * sizeof(float));
-    put(n_fft, sp.n_fft); put(hop, sp.hop); put(max_rows, sp.max_rows); put(n_rows, sp.n_rows());
-    return S2R_OK;
-}
-
-// the guard of the entries that need the meter set
-static int spectrum_on(const s2r_synth *s, const char *who) {
-    S2R_TRY(post_handle(s, who, "the spectrum meter is"));
-    if (!s->post.spec.n_fft) return set_err(const_cast<s2r_synth *>(s), S2R_ERR_INVALID, "%s: no spectrum meter is set", who);
+    put(n_fft, sp.n_fft); put(hop, sp.hop); put(max_rows, sp.kept.max_rows); put(n_rows, sp.kept.n_rows());
     return S2R_OK;
 }
 
 int s2r_reset_master_spectrum(s2r_synth *s) {
-    S2R_TRY(spectrum_on(s, "s2r_reset_master_spectrum"));
+    S2R_TRY(meter_on(s, kSpectrum, "s2r_reset_master_spectrum"));
     s->post.reset_spectrum();
     return S2R_OK;
 }
@@ -3475,8 +3487,8 @@ int s2r_get_spectrum(const s2r_synth *s, uint32_t programme, uint32_t n_avg, dou
     if (programme >= S2R_SPECTRUM_PROGRAMMES) return S2R_ERR_PATCH_RANGE;
     if (!s || !s->kids.empty() || s->parent || !s->post.spec.n_fft || !out_db) return S2R_ERR_INVALID;
     const S2rPostChain::Spectrum &sp = s->post.spec;
-    if (n_avg == 0u || n_avg > sp.n_rows()) return S2R_ERR_PATCH_RANGE;
-    return s2r_spectrum_readings(sp.stored(), sp.n_rows(), sp.n_fft, sp.window.data(), programme, n_avg, out_db, capacity);
+    if (n_avg == 0u || n_avg > sp.kept.n_rows()) return S2R_ERR_PATCH_RANGE;
+    return s2r_spectrum_readings(sp.kept.stored(), sp.kept.n_rows(), sp.n_fft, sp.window.data(), programme, n_avg, out_db, capacity);
 }
 
 int s2r_get_spectrum_bands(const s2r_synth *s, uint32_t programme, uint32_t n_avg, double sample_rate, uint32_t bands_per_octave, double *out_db, double *centres,
@@ -3484,57 +3496,15 @@ int s2r_get_spectrum_bands(const s2r_synth *s, uint32_t programme, uint32_t n_av
     if (programme >= S2R_SPECTRUM_PROGRAMMES) return S2R_ERR_PATCH_RANGE;
     if (!s || !s->kids.empty() || s->parent || !s->post.spec.n_fft || !out_db || !n_bands) return S2R_ERR_INVALID;
     const S2rPostChain::Spectrum &sp = s->post.spec;
-    if (n_avg == 0u || n_avg > sp.n_rows()) return S2R_ERR_PATCH_RANGE;
-    return s2r_spectrum_band_readings(sp.stored(), sp.n_rows(), sp.n_fft, sp.window.data(), programme, n_avg, sample_rate, bands_per_octave, out_db, centres, capacity,
+    if (n_avg == 0u || n_avg > sp.kept.n_rows()) return S2R_ERR_PATCH_RANGE;
+    return s2r_spectrum_band_readings(sp.kept.stored(), sp.kept.n_rows(), sp.n_fft, sp.window.data(), programme, n_avg, sample_rate, bands_per_octave, out_db, centres, capacity,
                                       n_bands);
 }
 
-int s2r_get_spectrum_rows(const s2r_synth *s, float *rows, size_t capacity, size_t *n_rows) {
-    S2R_TRY(spectrum_on(s, "s2r_get_spectrum_rows"));
-    const S2rPostChain::Spectrum &sp = s->post.spec;
-    const size_t n = sp.n_rows() * sp.row_floats();
-    if (capacity < n || (n && !rows)) return set_err(const_cast<s2r_synth *>(s), S2R_ERR_INVALID, "s2r_get_spectrum_rows: the rows are %zu floats, the buffer holds %zu", n, rows ? capacity : (size_t)0);
-    if (n) std::memcpy(rows, sp.stored(), n * sizeof(float));
-    put(n_rows, sp.n_rows());
-    return S2R_OK;
-}
-
-int s2r_set_spectrum_rows(s2r_synth *s, const float *rows, size_t n_rows, size_t count) {
-    S2R_TRY(spectrum_on(s, "s2r_set_spectrum_rows"));
-    S2rPostChain::Spectrum &sp = s->post.spec;
-    if (n_rows > sp.max_rows) return set_err(s, S2R_ERR_PATCH_RANGE, "s2r_set_spectrum_rows: %zu rows, at most the %u the meter keeps", n_rows, sp.max_rows);
-    if (count != n_rows * sp.row_floats() || (count && !rows))
-        return set_err(s, S2R_ERR_INVALID, "s2r_set_spectrum_rows: %zu rows are %zu floats, not %zu", n_rows, n_rows * sp.row_floats(), rows ? count : (size_t)0);
-    sp.kept.assign(rows, rows + count); sp.first = 0;
-    return S2R_OK;
-}
-
-int s2r_get_spectrum_state(s2r_synth *s, float *state, size_t capacity, uint32_t *pos) {
-    S2R_TRY(spectrum_on(s, "s2r_get_spectrum_state"));
-    S2rPostChain::Spectrum &sp = s->post.spec;
-    const size_t n = 18u * (size_t)sp.n_fft;
-    if (capacity < n) return set_err(s, S2R_ERR_INVALID, "s2r_get_spectrum_state: the state is %zu floats, not %zu", n, capacity);
-    if (!state) return set_err(s, S2R_ERR_INVALID, "s2r_get_spectrum_state: null buffer");
-    if (!sp.host_valid) {                                        // the device holds it: fetch it once, and keep it until the next fill
-        if (s->ring_count) return set_err(s, S2R_ERR_INVALID, "s2r_get_spectrum_state with fills of s2r_fill_begin in flight: s2r_fill_end first");
-        S2R_QUIESCE(s);
-        S2R_HIP(s, hipSetDevice(s->device));
-        S2R_HIP(s, s->post.fetch_spectrum_state(post_ctx(s)));
-    }
-    std::memcpy(state, sp.host.data(), n * sizeof(float));
-    put(pos, sp.pos);
-    return S2R_OK;
-}
-
-int s2r_set_spectrum_state(s2r_synth *s, const float *state, size_t count, uint32_t pos) {
-    S2R_TRY(spectrum_on(s, "s2r_set_spectrum_state"));
-    const size_t n = 18u * (size_t)s->post.spec.n_fft;
-    if (count != n) return set_err(s, S2R_ERR_INVALID, "s2r_set_spectrum_state: the state is %zu floats, not %zu", n, count);
-    if (!state) return set_err(s, S2R_ERR_INVALID, "s2r_set_spectrum_state: null buffer");
-    if (pos >= s->post.spec.hop) return set_err(s, S2R_ERR_PATCH_RANGE, "s2r_set_spectrum_state: position %u, below the hop of %u", pos, s->post.spec.hop);
-    s->post.set_spectrum_state(state, pos);
-    return S2R_OK;
-}
+int s2r_get_spectrum_rows(const s2r_synth *s, float *rows, size_t capacity, size_t *n_rows) { return meter_get_rows(s, kSpectrum, rows, capacity, n_rows, "s2r_get_spectrum_rows"); }
+int s2r_set_spectrum_rows(s2r_synth *s, const float *rows, size_t n_rows, size_t count) { return meter_set_rows(s, kSpectrum, rows, n_rows, count, "s2r_set_spectrum_rows"); }
+int s2r_get_spectrum_state(s2r_synth *s, float *state, size_t capacity, uint32_t *pos) { return meter_get_state(s, kSpectrum, state, capacity, pos, "s2r_get_spectrum_state"); }
+int s2r_set_spectrum_state(s2r_synth *s, const float *state, size_t count, uint32_t pos) { return meter_set_state(s, kSpectrum, state, count, pos, "s2r_set_spectrum_state"); }
 
 int s2r_fill_oversampled(s2r_synth *s, float *mono_out, size_t frames, uint32_t sample_rate_hz) {
     if (!s) return S2R_ERR_INVALID;

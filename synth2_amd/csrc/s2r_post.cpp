@@ -1,4 +1,5 @@
-// s2r_post.cpp — the post-mix chain (s2r_post.h): the eight bus stages (EQs, dynamics, drives, flangers, choruses, delays, reverbs, rooms), master section, master limiter, loudness meters, spectrum meters.  Compiled with hipcc, -ffp-contract=off.
+// s2r_post.cpp — the post-mix chain (s2r_post.h): the eight bus stages (EQs, dynamics, drives, flangers, choruses, delays, reverbs, rooms), master section, master limiter, loudness meters, spectrum meters —
+// the last three on the device side of s2r_post_keep.h (S2rMirror).  Compiled with hipcc, -ffp-contract=off.
 #include "s2r_post.h"
 #include "s2r_rules.h"
 
@@ -8,7 +9,7 @@ namespace {
 
 // mapped host memory the host reads behind a synchronise: coherent and portable, as every pinned buffer of s2r_host.cpp
 constexpr unsigned kHostPolled = hipHostMallocMapped | hipHostMallocCoherent | hipHostMallocPortable;
-constexpr size_t kLimXh = 2u * S2R_LIMITER_MAX_LOOKAHEAD, kLimState = kLimXh + 2u * S2R_LIMITER_MAX_LOOKAHEAD + S2R_LIMITER_MAX_HOLD;
+constexpr size_t kLimState = 2u * S2R_LIMITER_MAX_LOOKAHEAD + 2u * S2R_LIMITER_MAX_LOOKAHEAD + S2R_LIMITER_MAX_HOLD;     // the largest xh, then the largest gh
 
 #define POST_HIP(call) do { const hipError_t e_ = (call); if (e_ != hipSuccess) return e_; } while (0)
 // a stage's launch between its timer's marks
@@ -62,6 +63,26 @@ hipError_t S2rBusLine::copy(float *get, const float *set, size_t at, size_t n, h
     return hipMemcpyAsync(now() + at, set, n * sizeof(float), hipMemcpyHostToDevice, stream);
 }
 
+hipError_t S2rMirror::reserve(size_t n) {
+    if (n > floats) { free(); floats = n; }                      // (only behind a set: the state is the host's then, and the device's copies hold nothing)
+    for (float *&p : dev) if (!p) POST_HIP(hipMalloc((void **)&p, floats * sizeof(float)));
+    return hipSuccess;
+}
+
+hipError_t S2rMirror::upload(hipStream_t stream) const {
+    if (!host_valid) return hipSuccess;
+    return hipMemcpyAsync(now(), host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice, stream);
+}
+
+hipError_t S2rMirror::fetch(hipStream_t stream) {
+    std::vector<float> st(host.size());
+    POST_HIP(hipMemcpyAsync(st.data(), now(), st.size() * sizeof(float), hipMemcpyDeviceToHost, stream));
+    POST_HIP(hipStreamSynchronize(stream));
+    host.swap(st);
+    host_valid = true;
+    return hipSuccess;
+}
+
 hipError_t S2rPostTimer::begin(hipStream_t stream) {
     for (hipEvent_t &e : ev) if (!e) POST_HIP(hipEventCreate(&e));
     return hipEventRecord(ev[0], stream);
@@ -79,19 +100,14 @@ hipError_t S2rPostChain::prepare(const S2rPostCtx &c, uint32_t n_buses, uint32_t
     }
     if (call.limited) {                                          // the limiter's input, the two copies of its state, its pinned rows of meter partials
         if (!limiter.in) POST_HIP(hipMalloc((void **)&limiter.in, (size_t)2 * c.max_frames * sizeof(float)));
-        for (float *&p : limiter.state) if (!p) POST_HIP(hipMalloc((void **)&p, kLimState * sizeof(float)));
+        POST_HIP(limiter.state.reserve(kLimState));
         POST_HIP(pinned_rows(limiter.partials, limiter.partials_dev, (size_t)((c.max_frames + S2R_LIMITER_BLOCK - 1u) / S2R_LIMITER_BLOCK) * 2u));
     }
     if (metered(call) && !loud.in) POST_HIP(hipMalloc((void **)&loud.in, (size_t)2 * c.max_frames * sizeof(float)));      // the meters' input
     if (spec_on(call)) {                                         // the two copies of the state, the tables and the pinned rows, by n_fft and hop
         Spectrum &sp = spec;
-        const size_t n = sp.n_fft, need_state = 18u * n, need_tables = 2u * n, need_rows = (size_t)(c.max_frames / sp.hop + 1u) * sp.row_floats();
-        if (sp.state_floats < need_state) {                      // (only behind a set: the state is the host's then, and the device's copies hold nothing)
-            for (float *&p : sp.state) { if (p) (void)hipFree(p); p = nullptr; }
-            sp.state_floats = 0;
-            for (float *&p : sp.state) POST_HIP(hipMalloc((void **)&p, need_state * sizeof(float)));
-            sp.state_floats = need_state;
-        }
+        const size_t need_tables = 2u * (size_t)sp.n_fft, need_rows = (size_t)(c.max_frames / sp.hop + 1u) * sp.kept.width;
+        POST_HIP(sp.state.reserve(S2R_SPECTRUM_STATE(sp.n_fft)));
         if (sp.tables_floats < need_tables) {
             if (sp.tables) (void)hipFree(sp.tables);
             sp.tables = nullptr; sp.tables_floats = 0; sp.tables_valid = false;
@@ -106,7 +122,7 @@ hipError_t S2rPostChain::prepare(const S2rPostCtx &c, uint32_t n_buses, uint32_t
         }
     }
     if (loud_on(call)) {                                         // the two copies of its state, its pinned hop rows and peaks
-        for (float *&p : loud.state) if (!p) POST_HIP(hipMalloc((void **)&p, S2R_LOUDNESS_STATE * sizeof(float)));
+        POST_HIP(loud.state.reserve(S2R_LOUDNESS_STATE));
         POST_HIP(pinned_rows(loud.rows, loud.rows_dev, (size_t)(c.max_frames / S2R_LOUDNESS_MIN_HOP + 1u) * S2R_LOUDNESS_CHANNELS));
         POST_HIP(pinned_rows(loud.peaks, loud.peaks_dev, (size_t)((c.max_frames + S2R_LOUDNESS_BLOCK - 1u) / S2R_LOUDNESS_BLOCK) * 2u));
     }
@@ -135,22 +151,18 @@ hipError_t S2rPostChain::launch(const S2rPostCtx &c, const S2rPostCall &call) {
     }
     if (call.limited) {                                          // the next state goes into the copy that is not the current one
         Limiter &lm = limiter;
-        float *cur = lm.state[lm.cur], *next = lm.state[lm.cur ^ 1];
-        if (lm.host_valid) {                                     // (stays valid until the commit: a failed call leaves the state where it was)
-            POST_HIP(hipMemcpyAsync(cur, lm.host.data(), lm.n_x() * sizeof(float), hipMemcpyHostToDevice, c.stream));
-            POST_HIP(hipMemcpyAsync(cur + kLimXh, lm.host.data() + lm.n_x(), lm.n_g() * sizeof(float), hipMemcpyHostToDevice, c.stream));
-        }
+        float *cur = lm.state.now(), *next = lm.state.next();
+        POST_HIP(lm.state.upload(c.stream));                     // (a host copy stays valid until the commit: a failed call leaves the state where it was)
         S2rLimiter a{};
-        a.x = r.limiter_in; a.out = r.limiter_out; a.xh = cur; a.gh = cur + kLimXh; a.xh_next = next; a.gh_next = next + kLimXh;
+        a.x = r.limiter_in; a.out = r.limiter_out; a.xh = cur; a.gh = cur + lm.n_x(); a.xh_next = next; a.gh_next = next + lm.n_x();
         a.partials = lm.partials_dev; a.frames = call.frames; a.lookahead = lm.lookahead; a.hold = lm.hold; a.ceiling = lm.ceiling;
         POST_TIMED(c, lm.timer, s2r_launch_limiter(a, c.stream));
     }
     if (loud_on(call)) {                                         // behind whoever wrote the master last: the next state goes into the other copy
         Loudness &ld = loud;
-        float *cur = ld.state[ld.cur], *next = ld.state[ld.cur ^ 1];
-        if (ld.host_valid) POST_HIP(hipMemcpyAsync(cur, ld.host.data(), S2R_LOUDNESS_STATE * sizeof(float), hipMemcpyHostToDevice, c.stream));
+        POST_HIP(ld.state.upload(c.stream));
         S2rLoudness a{};
-        a.stems = r.master_in; a.master = call.limited ? r.limiter_out : r.master_out; a.out = c.out_host_dev; a.state = cur; a.next = next;
+        a.stems = r.master_in; a.master = call.limited ? r.limiter_out : r.master_out; a.out = c.out_host_dev; a.state = ld.state.now(); a.next = ld.state.next();
         a.rows = ld.rows_dev; a.peaks = ld.peaks_dev; a.n_buses = call.n_buses; a.frames = call.frames; a.hop = ld.hop; a.pos = ld.pos;
         std::memcpy(a.c, ld.c, sizeof a.c); std::memcpy(a.g, drive_taps().g, sizeof a.g);
         POST_TIMED(c, ld.timer, s2r_launch_loudness(a, c.stream));
@@ -158,15 +170,14 @@ hipError_t S2rPostChain::launch(const S2rPostCtx &c, const S2rPostCall &call) {
     if (spec_on(call)) {                                         // last: it copies the master out only when the loudness kernel has not
         Spectrum &sp = spec;
         const size_t n = sp.n_fft;
-        float *cur = sp.state[sp.cur], *next = sp.state[sp.cur ^ 1];
         if (!sp.tables_valid) {                                  // (stays so until the commit)
             POST_HIP(hipMemcpyAsync(sp.tables, sp.window.data(), n * sizeof(float), hipMemcpyHostToDevice, c.stream));
             POST_HIP(hipMemcpyAsync(sp.tables + n, sp.twiddles.data(), n * sizeof(float), hipMemcpyHostToDevice, c.stream));
         }
-        if (sp.host_valid) POST_HIP(hipMemcpyAsync(cur, sp.host.data(), 18u * n * sizeof(float), hipMemcpyHostToDevice, c.stream));
+        POST_HIP(sp.state.upload(c.stream));
         S2rSpectrum a{};
         a.stems = r.master_in; a.master = call.limited ? r.limiter_out : r.master_out; a.out = loud_on(call) ? nullptr : c.out_host_dev;
-        a.state = cur; a.next = next; a.window = sp.tables; a.twiddles = sp.tables + n; a.rows = sp.rows_dev;
+        a.state = sp.state.now(); a.next = sp.state.next(); a.window = sp.tables; a.twiddles = sp.tables + n; a.rows = sp.rows_dev;
         a.n_buses = call.n_buses; a.frames = call.frames; a.n_fft = sp.n_fft; a.hop = sp.hop; a.pos = sp.pos;
         POST_TIMED(c, sp.timer, s2r_launch_spectrum(a, c.stream));
     }
@@ -308,7 +319,7 @@ void S2rPostChain::commit(const S2rPostCall &call) {
     }
     if (call.limited) {                                          // the state has moved on, and the workgroups' rows give the call's meters
         Limiter &lm = limiter;
-        lm.cur ^= 1; lm.host_valid = false;
+        lm.state.committed();
         const uint32_t n_blocks = (call.frames + S2R_LIMITER_BLOCK - 1u) / S2R_LIMITER_BLOCK;
         float mn = lm.partials[0], pk = lm.partials[1];
         for (uint32_t k = 1; k < n_blocks; k++) {
@@ -320,17 +331,13 @@ void S2rPostChain::commit(const S2rPostCall &call) {
     }
     if (spec_on(call)) {                                         // the state has moved on, and the call's rows join the rows kept
         Spectrum &sp = spec;
-        sp.cur ^= 1; sp.host_valid = false; sp.tables_valid = true;
-        const uint64_t at = (uint64_t)sp.pos + call.frames;
-        sp.append(sp.rows, (size_t)(at / sp.hop));
-        sp.pos = (uint32_t)(at % sp.hop);
+        sp.state.committed(); sp.tables_valid = true;
+        sp.kept.take(sp.rows, sp.pos, call.frames, sp.hop);
     }
     if (loud_on(call)) {                                         // the state has moved on; the call's hops join the rows, its peaks the held ones
         Loudness &ld = loud;
-        ld.cur ^= 1; ld.host_valid = false;
-        const uint64_t at = (uint64_t)ld.pos + call.frames;
-        ld.append(ld.rows, (size_t)(at / ld.hop));
-        ld.pos = (uint32_t)(at % ld.hop);
+        ld.state.committed();
+        ld.kept.take(ld.rows, ld.pos, call.frames, ld.hop);
         const uint32_t n_blocks = (call.frames + S2R_LOUDNESS_BLOCK - 1u) / S2R_LOUDNESS_BLOCK;
         for (uint32_t ch = 0; ch < 2u; ch++) {
             float pk = ld.peaks[ch];
@@ -339,19 +346,6 @@ void S2rPostChain::commit(const S2rPostCall &call) {
             ld.tp_held[ch] = pk > ld.tp_held[ch] ? pk : ld.tp_held[ch];
         }
     }
-}
-
-void S2rPostChain::Loudness::append(const float *new_rows, size_t n) {
-    hops.insert(hops.end(), new_rows, new_rows + n * S2R_LOUDNESS_CHANNELS);
-    if (n_hops() > max_hops) first += n_hops() - max_hops;
-    if (first > max_hops) { hops.erase(hops.begin(), hops.begin() + first * S2R_LOUDNESS_CHANNELS); first = 0; }      // (amortised: once per max_hops rows dropped)
-}
-
-void S2rPostChain::Spectrum::append(const float *new_rows, size_t n) {
-    const size_t rf = row_floats();
-    kept.insert(kept.end(), new_rows, new_rows + n * rf);
-    if (n_rows() > max_rows) first += n_rows() - max_rows;
-    if (first > max_rows) { kept.erase(kept.begin(), kept.begin() + first * rf); first = 0; }        // (amortised: once per max_rows rows dropped)
 }
 
 // a stage that the fill could have run and did not reads 0; a panned fill leaves all ten values alone, a bus fill the master's two
@@ -373,7 +367,8 @@ void S2rPostChain::release() {
     for (uint32_t b = 0; b < S2R_MAX_BUSES; b++) { drop(eq[b]); drop(dyn[b]); drop(drive[b]); drop(flanger[b]); drop(chorus[b]); drop(delay[b]); drop(fx[b]); drop(room[b]); }
     for (Stem &st : stage) { if (st.buffer) (void)hipFree(st.buffer); st.timer.destroy(); }
     // ... and what is neither a line nor a stage's buffer
-    for (float *p : {dyn_curves, drive_curves, master.stage, limiter.state[0], limiter.state[1], limiter.in, loud.state[0], loud.state[1], loud.in, spec.state[0], spec.state[1], spec.tables}) if (p) (void)hipFree(p);
+    for (S2rMirror *m : {&limiter.state, &loud.state, &spec.state}) m->free();
+    for (float *p : {dyn_curves, drive_curves, master.stage, limiter.in, loud.in, spec.tables}) if (p) (void)hipFree(p);
     for (float *p : {dyn_meter, master.partials, limiter.partials, loud.rows, loud.peaks, spec.rows}) if (p) (void)hipHostFree(p);
     for (S2rPostTimer *t : {&master.timer, &limiter.timer, &loud.timer, &spec.timer}) t->destroy();
 }
@@ -532,91 +527,54 @@ void S2rPostChain::set_limiter(float ceiling, uint32_t lookahead, uint32_t hold)
     Limiter &lm = limiter;
     const bool reset = lm.lookahead != lookahead || lm.hold != hold;
     lm.ceiling = ceiling; lm.lookahead = lookahead; lm.hold = hold;
-    if (!lookahead) { lm.host.clear(); lm.host_valid = false; }
+    if (!lookahead) lm.state.off();
     else if (reset) {
-        lm.host.assign(lm.n_x(), 0.0f);
-        lm.host.resize(lm.n_x() + lm.n_g(), 1.0f);
-        lm.host_valid = true;
+        std::vector<float> st(lm.n_x(), 0.0f);
+        st.resize(lm.n_x() + lm.n_g(), 1.0f);
+        lm.state.set(st.data(), st.size());
     }
 }
 
 void S2rPostChain::set_limiter_state(const float *xh, const float *gh) {
-    limiter.host.assign(xh, xh + limiter.n_x());
-    limiter.host.insert(limiter.host.end(), gh, gh + limiter.n_g());
-    limiter.host_valid = true;
-}
-
-hipError_t S2rPostChain::fetch_limiter_state(const S2rPostCtx &c) {
-    Limiter &lm = limiter;
-    std::vector<float> st(lm.n_x() + lm.n_g());
-    const float *cur = lm.state[lm.cur];
-    POST_HIP(hipMemcpyAsync(st.data(), cur, lm.n_x() * sizeof(float), hipMemcpyDeviceToHost, c.stream));
-    POST_HIP(hipMemcpyAsync(st.data() + lm.n_x(), cur + kLimXh, lm.n_g() * sizeof(float), hipMemcpyDeviceToHost, c.stream));
-    POST_HIP(hipStreamSynchronize(c.stream));
-    lm.host.swap(st);
-    lm.host_valid = true;
-    return hipSuccess;
+    std::vector<float> st(xh, xh + limiter.n_x());
+    st.insert(st.end(), gh, gh + limiter.n_g());
+    limiter.state.set(st.data(), st.size());
 }
 
 void S2rPostChain::set_loudness(const float *coeffs, uint32_t hop, uint32_t max_hops) {
     Loudness &ld = loud;
-    if (!coeffs) { ld.hop = ld.max_hops = 0; std::memset(ld.c, 0, sizeof ld.c); }
-    else { std::memcpy(ld.c, coeffs, sizeof ld.c); ld.hop = hop; ld.max_hops = max_hops; }
+    if (!coeffs) { ld.hop = 0; std::memset(ld.c, 0, sizeof ld.c); }
+    else { std::memcpy(ld.c, coeffs, sizeof ld.c); ld.hop = hop; }
+    ld.kept.shape(S2R_LOUDNESS_CHANNELS, coeffs ? max_hops : 0u);
     reset_loudness();
-    if (!coeffs) { ld.host.clear(); ld.host_valid = false; }
+    if (!coeffs) ld.state.off();
 }
 
 void S2rPostChain::reset_loudness() {
     Loudness &ld = loud;
-    ld.host.assign(S2R_LOUDNESS_STATE, 0.0f); ld.host_valid = true; ld.pos = 0;
-    ld.hops.clear(); ld.first = 0;
+    ld.state.zero(S2R_LOUDNESS_STATE); ld.pos = 0;
+    ld.kept.clear();
     for (int ch = 0; ch < 2; ch++) ld.tp_last[ch] = ld.tp_held[ch] = 0.0f;
-}
-
-void S2rPostChain::set_loudness_state(const float *state, uint32_t pos) {
-    loud.host.assign(state, state + S2R_LOUDNESS_STATE);
-    loud.host_valid = true; loud.pos = pos;
-}
-
-hipError_t S2rPostChain::fetch_loudness_state(const S2rPostCtx &c) {
-    std::vector<float> st(S2R_LOUDNESS_STATE);
-    POST_HIP(hipMemcpyAsync(st.data(), loud.state[loud.cur], S2R_LOUDNESS_STATE * sizeof(float), hipMemcpyDeviceToHost, c.stream));
-    POST_HIP(hipStreamSynchronize(c.stream));
-    loud.host.swap(st);
-    loud.host_valid = true;
-    return hipSuccess;
 }
 
 void S2rPostChain::set_spectrum(uint32_t n_fft, uint32_t hop, const float *window, uint32_t max_rows) {
     Spectrum &sp = spec;
     sp.tables_valid = false;
-    if (!window) { sp.n_fft = sp.hop = sp.max_rows = 0; sp.window.clear(); sp.twiddles.clear(); }
+    if (!window) { sp.n_fft = sp.hop = 0; sp.window.clear(); sp.twiddles.clear(); }
     else {
-        sp.n_fft = n_fft; sp.hop = hop; sp.max_rows = max_rows;
+        sp.n_fft = n_fft; sp.hop = hop;
         sp.window.assign(window, window + n_fft);
         sp.twiddles.assign(n_fft, 0.0f);
         (void)s2r_spectrum_twiddles(n_fft, sp.twiddles.data());
     }
+    sp.kept.shape(window ? S2R_SPECTRUM_ROW(n_fft) : 0u, window ? max_rows : 0u);
     reset_spectrum();
-    if (!window) { sp.host.clear(); sp.host_valid = false; }
+    if (!window) sp.state.off();
 }
 
 void S2rPostChain::reset_spectrum() {
     Spectrum &sp = spec;
-    sp.host.assign(18u * (size_t)sp.n_fft, 0.0f); sp.host_valid = true; sp.pos = 0;
-    sp.kept.clear(); sp.first = 0;
+    sp.state.zero(S2R_SPECTRUM_STATE(sp.n_fft)); sp.pos = 0;
+    sp.kept.clear();
 }
 
-void S2rPostChain::set_spectrum_state(const float *state, uint32_t pos) {
-    spec.host.assign(state, state + 18u * (size_t)spec.n_fft);
-    spec.host_valid = true; spec.pos = pos;
-}
-
-hipError_t S2rPostChain::fetch_spectrum_state(const S2rPostCtx &c) {
-    std::vector<float> st(18u * (size_t)spec.n_fft);
-    POST_HIP(hipMemcpyAsync(st.data(), spec.state[spec.cur], st.size() * sizeof(float), hipMemcpyDeviceToHost, c.stream));
-    POST_HIP(hipStreamSynchronize(c.stream));
-    spec.host.swap(st);
-    spec.host_valid = true;
-    return hipSuccess;
-}

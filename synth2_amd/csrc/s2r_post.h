@@ -1,14 +1,17 @@
 // s2r_post.h — the chain behind the bus mixdown of s2r_fill_buses and s2r_fill_master: the eight bus stages in the order of
 // S2rBusStage (s2r_post_route.h) — the buses' equalisers, their dynamics (4.22), drives (4.24), flangers (4.25),
 // choruses (4.20), feedback delays (4.19), convolution reverbs (4.16) and rooms (4.23) —, then the master section (4.17) and the master
-// limiter (4.18), and behind it the loudness and true-peak meters (4.26) and the spectrum meters (4.27).  The chain owns what these stages own and knows nothing of the handle: its functions take a S2rPostCtx and return
-// the HIP error.  Per call: prepare, launch, — the caller's synchronise — commit, read_timers.
+// limiter (4.18), and behind it the loudness and true-peak meters (4.26) and the spectrum meters (4.27).  The bus stages keep their
+// histories in a S2rBusLine each; the three stages behind the master fader keep their state in a S2rMirror each, and the two meters
+// their rows in a S2rRowStore each (s2r_post_keep.h).  The chain owns what these stages own and knows nothing of the handle: its
+// functions take a S2rPostCtx and return the HIP error.  Per call: prepare, launch, — the caller's synchronise — commit, read_timers.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <vector>
 
 #include "s2r.h"
 #include "s2r_device.h"
+#include "s2r_post_keep.h"
 #include "s2r_post_route.h"
 
 // what the chain is told of its handle: `timing` is s2r_set_timing, the two pointers the device's views of the pinned outputs
@@ -42,6 +45,19 @@ struct S2rBusLine {
     hipError_t copy(float *get, const float *set, size_t at, size_t n, hipStream_t stream) const;
     // (not virtual: an effect with more device memory than its lines frees it in a free() of its own, and is dropped by its type)
     void free() { for (float *&p : line) if (p) { (void)hipFree(p); p = nullptr; } }
+};
+
+// The device side of a master stage's state (S2rMirrorHost, s2r_post_keep.h): the two copies, allocated by the first master fill that
+// finds the stage set.  A fill reads now() — behind upload(), which sends a valid host copy there — and writes next(); committed() flips.
+struct S2rMirror : S2rMirrorHost {
+    float *dev[2] = {nullptr, nullptr};          // device memory, `floats` each
+    size_t floats = 0;
+    float *now() const { return dev[cur]; }
+    float *next() const { return dev[cur ^ 1]; }
+    hipError_t reserve(size_t n);                // at least n floats each: allocates what is missing, and regrows only while the host copy is valid
+    hipError_t upload(hipStream_t stream) const; // nothing unless the host copy is valid; it stays so until the commit
+    hipError_t fetch(hipStream_t stream);        // the device's copy into `host`, kept until the next fill; synchronises; a failure leaves `host` as it was
+    void free() { for (float *&p : dev) if (p) { (void)hipFree(p); p = nullptr; } floats = 0; }
 };
 
 struct S2rPostChain {
@@ -134,12 +150,9 @@ struct S2rPostChain {
     struct Limiter {
         float ceiling = 0.0f;
         uint32_t lookahead = 0, hold = 0;        // lookahead 0: off
-        // The state — xh [lookahead][2], then gh [2 * lookahead + hold] — lives in `host` while host_valid (set, reset or restored since
-        // the last fill) and in state[cur] otherwise: a fill uploads a valid host copy, the kernel writes state[cur ^ 1], the commit flips.
-        std::vector<float> host;
-        bool host_valid = false;
-        float *state[2] = {nullptr, nullptr};    // device memory, each 2 * S2R_LIMITER_MAX_LOOKAHEAD + (2 * S2R_LIMITER_MAX_LOOKAHEAD + S2R_LIMITER_MAX_HOLD) floats
-        int cur = 0;
+        // xh [lookahead][2], then gh [2 * lookahead + hold], on the host and on the device alike: n_x() + n_g() floats, in copies
+        // sized for the largest lookahead and hold
+        S2rMirror state;
         float *in = nullptr;                     // [2 * max_frames] in device memory: where the master kernel writes when the limiter is on
         float *partials = nullptr, *partials_dev = nullptr;      // pinned and device-mapped: [ceil(max_frames / S2R_LIMITER_BLOCK)][2]
         bool metered = false;                    // a master fill has run the limiter: the meters below are its
@@ -152,51 +165,31 @@ struct S2rPostChain {
     // that finds the meter set, and a handle on which it never was passes the pointers and makes the launches it always did.
     struct Loudness {
         float c[10] = {};
-        uint32_t hop = 0, max_hops = 0;          // hop 0: off
-        // The state's S2R_LOUDNESS_STATE floats live in `host` while host_valid (set, reset or restored since the last fill) and in
-        // state[cur] otherwise, as the limiter's; `pos`, the frames of the hop under way, is the host's alone and a kernel argument.
-        std::vector<float> host;
-        bool host_valid = false;
-        uint32_t pos = 0;
-        float *state[2] = {nullptr, nullptr};    // device memory, S2R_LOUDNESS_STATE floats each
-        int cur = 0;
+        uint32_t hop = 0;                        // 0: off
+        S2rMirror state;                         // S2R_LOUDNESS_STATE floats
+        uint32_t pos = 0;                        // the frames of the hop under way: the host's alone, and a kernel argument
         float *in = nullptr;                     // [2 * max_frames] in device memory: where the master's last writer writes when the meter is on
         float *rows = nullptr, *rows_dev = nullptr;              // pinned and device-mapped: [max_frames / 16 + 1][S2R_LOUDNESS_CHANNELS]
         float *peaks = nullptr, *peaks_dev = nullptr;            // pinned and device-mapped: [ceil(max_frames / S2R_LOUDNESS_BLOCK)][2]
-        std::vector<float> hops;                 // the hop rows kept, oldest first, from row `first` on: at most max_hops of them
-        size_t first = 0;
+        S2rRowStore kept;                        // the hop rows kept: S2R_LOUDNESS_CHANNELS floats each, at most max_hops of them
         float tp_last[2] = {0.0f, 0.0f}, tp_held[2] = {0.0f, 0.0f};
         S2rPostTimer timer;                      // around the loudness kernel of the last master fill: 0 when it ran none (tools/loudness_time.py)
-        size_t n_hops() const { return hops.size() / S2R_LOUDNESS_CHANNELS - first; }
-        const float *stored() const { return hops.data() + first * S2R_LOUDNESS_CHANNELS; }
-        void append(const float *new_rows, size_t n);            // ... and drop the oldest past max_hops
     } loud;
     // The spectrum meters (s2r_set_master_spectrum), behind the loudness meters.  As theirs: nothing is allocated before
     // the first master fill that finds the meter set — and what is allocated then is sized by n_fft and hop, and grown by a later fill
     // that finds them larger —, and a handle on which it never was set makes the launches it always did.
     struct Spectrum {
-        uint32_t n_fft = 0, hop = 0, max_rows = 0;               // n_fft 0: off
+        uint32_t n_fft = 0, hop = 0;             // both 0: off
         std::vector<float> window, twiddles;     // [n_fft] and [n_fft / 2][2], the host's; the device's copy is good while tables_valid
         bool tables_valid = false;
-        // The state's 18 * n_fft floats live in `host` while host_valid (set, reset or restored since the last fill) and in state[cur]
-        // otherwise; `pos`, the frames of the hop under way, is the host's alone and a kernel argument.
-        std::vector<float> host;
-        bool host_valid = false;
-        uint32_t pos = 0;
-        float *state[2] = {nullptr, nullptr};    // device memory, state_floats each
-        size_t state_floats = 0;
-        int cur = 0;
+        S2rMirror state;                         // S2R_SPECTRUM_STATE(n_fft) floats
+        uint32_t pos = 0;                        // the frames of the hop under way: the host's alone, and a kernel argument
         float *tables = nullptr;                 // device memory: window [n_fft], then twiddles [n_fft / 2][2]; tables_floats in all
         size_t tables_floats = 0;
         float *rows = nullptr, *rows_dev = nullptr;              // pinned and device-mapped: [max_frames / hop + 1][9][n_fft / 2 + 1], rows_floats
         size_t rows_floats = 0;
-        std::vector<float> kept;                 // the rows kept, oldest first, from row `first` on: at most max_rows of them
-        size_t first = 0;
+        S2rRowStore kept;                        // the rows kept: S2R_SPECTRUM_ROW(n_fft) floats each, at most max_rows of them
         S2rPostTimer timer;                      // around the spectrum kernel of the last master fill: 0 when it ran none (tools/spectrum_time.py)
-        size_t row_floats() const { return S2R_SPECTRUM_ROW(n_fft); }
-        size_t n_rows() const { return n_fft ? kept.size() / row_floats() - first : 0; }
-        const float *stored() const { return kept.data() + first * row_floats(); }
-        void append(const float *new_rows, size_t n);            // ... and drop the oldest past max_rows
     } spec;
     bool loud_on(const S2rPostCall &call) const { return call.master && loud.hop != 0; }
     bool spec_on(const S2rPostCall &call) const { return call.master && spec.n_fft != 0; }
@@ -240,13 +233,8 @@ struct S2rPostChain {
     void snap_master() { for (uint32_t b = 0; b < S2R_MAX_BUSES; b++) master.ret_app[b] = master.ret[b]; master.fader_app = master.fader; }
     void set_limiter(float ceiling, uint32_t lookahead, uint32_t hold);      // (0, 0, 0): off
     void set_limiter_state(const float *xh, const float *gh);
-    hipError_t fetch_limiter_state(const S2rPostCtx &c);            // the device's copy into `host`, kept until the next fill
     void set_loudness(const float *coeffs, uint32_t hop, uint32_t max_hops);  // coeffs null: off; else on, from the initial state
     void reset_loudness();                                          // state, rows and held true peak; the parameters stay
-    void set_loudness_state(const float *state, uint32_t pos);
-    hipError_t fetch_loudness_state(const S2rPostCtx &c);           // the device's copy into `host`, kept until the next fill
     void set_spectrum(uint32_t n_fft, uint32_t hop, const float *window, uint32_t max_rows);   // window null: off; else on, from the initial state
     void reset_spectrum();                                          // state and rows; the parameters stay
-    void set_spectrum_state(const float *state, uint32_t pos);
-    hipError_t fetch_spectrum_state(const S2rPostCtx &c);           // the device's copy into `host`, kept until the next fill
 };

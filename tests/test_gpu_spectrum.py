@@ -281,6 +281,26 @@ def test_reset_and_clear():
     assert m.made == 5 and len(m.rows) == 3
 
 
+def test_a_larger_size_and_the_smaller_one_again():
+    """the state's two device copies are sized by the first fill, regrown by the fill behind a set at a larger size and used as they
+    are behind a set at the smaller size again: sizes 256 (hop 32), 512 (hop 64) and 256 on one handle, two master fills of two buses
+    each.  Every set leaves no rows and a state of +0.0 at position 0; every fill returns the bits of a twin that never had a meter,
+    and rows and state are the reference's bits, compared as in test_rows_and_state_are_the_reference"""
+    a, b = _handles(V, max_frames=512)
+    fill = 0
+    for n, hop in ((256, 32), (512, 64), (256, 32)):
+        m = Meter(n, hop)
+        m.set(a)
+        assert a.spectrum_rows().size == 0
+        st, pos = a.spectrum_state()
+        assert pos == 0 and st.size == 2 * P * n and not ubits(st).any()
+        for frames in (300, 301):
+            _events((a, b), V, fill)
+            _mfill(a, b, m, frames, 2, "N %d, fill %d of %d frames" % (n, fill, frames), stems=fill % 2 == 0, state=True)
+            fill += 1
+        assert m.made == 601 // hop and len(m.rows) == 8 and (m.rows[-1, [0, 1, MASTER]] > 0.0).any(axis=1).all()
+
+
 def test_refusals_change_nothing():
     """refused master fills and refused setters leave parameters, state, rows and readings as they were, and the next fill equals the
     reference as if they had not happened; a device-list handle refuses every entry"""

@@ -1,7 +1,8 @@
 """ASan + UBSan over the handle-free rule functions (csrc/s2r_rules.cpp: the reverb, master and limiter references and the mixer's
 gain rules), which need neither a handle nor HIP: the file is compiled by plain g++ beside a small program of its own
 (tests/native/san_rules.cpp) and run as a child process, with no preload of any kind.  The post-mix chain's route (csrc/s2r_post_route.h)
-goes the same way with tests/native/post_route.cpp."""
+goes the same way with tests/native/post_route.cpp, and what its master stages keep on the host (csrc/s2r_post_keep.h) with
+tests/native/post_keep.cpp."""
 import os
 import shutil
 import subprocess
@@ -41,3 +42,19 @@ def test_post_route_under_asan_ubsan(tmp_path):
     out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     assert "route ok" in out.stdout
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
+def test_post_keep_under_asan_ubsan(tmp_path):
+    """what the stages behind the master fader keep on the host (csrc/s2r_post_keep.h, a header without HIP): the row store against a
+    std::deque of the last max_rows rows — count and every float after each step — at row widths 1, 18 and S2R_SPECTRUM_ROW(256),
+    max_rows 1, 2 and 5, appends of 0 .. 3 max_rows + 1 rows, runs of single rows across more than one compaction, assign and clear
+    followed by appends; the position step against quotient and remainder in 64 bits, past 2^32; and each transition of a mirrored
+    state's host side — set, zero, committed, off, set after committed — on its own"""
+    exe = str(tmp_path / "post_keep")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "synth2_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "native", "post_keep.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-3000:]
+    assert "keep ok" in out.stdout
