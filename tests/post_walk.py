@@ -5,7 +5,16 @@ through the model alone.
 walk(seed) is a pure function of the seed and returns plain data — numbers, names and seeds, no arrays: Chain.apply makes the
 coefficients, tables and responses from them with the helpers of the per-stage files, whose edge sets the draws are taken from.  Chain is
 the models of those files composed in chain order; no arithmetic of its own is in it: every rule is the one a tests/test_*_host.py file
-pins to numpy on bits."""
+pins to numpy on bits.
+
+Behind the limiter Chain carries the two meters of DESIGN.md 4.26 and 4.27 as test_gpu_loudness.Meter and test_gpu_spectrum.Meter
+(s2r_loudness_reference and s2r_spectrum_reference with state, position and rows carried in numpy).  Their actions — METER_KINDS: set,
+also while present, reset, clear, and a master fill that must be refused — come from a second generator and are spliced between the
+chain's steps (_splice), which stay the ones a seed gave before the meters joined: the seeds with a history keep naming their walks.
+A master fill feeds each meter that is on; Chain.meter_readings is what the getters that move nothing must then give, behind any kind
+of fill, and Chain.meter_states what the getters that fetch the state's device copy give — read at a round trip, at a handover,
+behind every other bus fill and panned fill (peeks) and at the end of a walk, so that master fills meet the copies both flipped
+unread and fetched."""
 import numpy as np
 
 import synth2_amd as s2
@@ -21,9 +30,11 @@ from test_gpu_dyn import COEFS, RATIOS, DynModel
 from test_gpu_eq import EqModel, _coeffs
 from test_gpu_flanger import SHAPE as FLANGER_SHAPE, FlangerModel
 from test_gpu_limiter import Lim
+from test_gpu_loudness import Meter as LoudnessMeter
 from test_gpu_master import Master
-from test_gpu_reverb import MIXES, Model, _ir
+from test_gpu_reverb import MIXES, SR, Model, _ir
 from test_gpu_room import LEVELS, RoomModel
+from test_gpu_spectrum import Meter as SpectrumMeter
 from test_limiter_host import PAIRS
 from test_master_host import np_meters
 from test_room_host import FLAT, SMALL
@@ -35,8 +46,23 @@ STAGES = ("eq", "dyn", "drive", "flanger", "chorus", "delay", "reverb", "room") 
 INSERTS = ("eq", "dyn", "drive", "flanger", "room")
 STEMS = ("chorus", "delay", "reverb")
 FILLS = ("bus", "master_stems", "master", "panned")
-KINDS_OF_ACTION = ("set", "clear", "params", "limiter_set", "limiter_clear", "limiter_ceiling", "limiter_reset", "return", "fader", "snap",
-                   "fill", "roundtrip", "handover")
+CHAIN_KINDS = ("set", "clear", "params", "limiter_set", "limiter_clear", "limiter_ceiling", "limiter_reset", "return", "fader", "snap",
+               "fill", "roundtrip", "handover")
+# the meters behind the limiter and a master fill that is refused: what a second generator splices between the
+# steps above (_splice), which stay what they were before the meters joined the walks
+METER_KINDS = ("loudness_set", "loudness_reset", "loudness_clear", "spectrum_set", "spectrum_reset", "spectrum_clear", "refused_fill")
+KINDS_OF_ACTION = CHAIN_KINDS + METER_KINDS
+METER_SALT = 0x6D657472                                          # the second generator's seed is seed ^ METER_SALT
+# hop 17 most often: the one hop here that ends on the last frame of a walker's block of eight (test_gpu_loudness.walker_distances)
+LOUDNESS_HOPS, LOUDNESS_HOP_P = (16, 17, 48, 100, 4800), (0.17, 0.33, 0.2, 0.2, 0.1)
+LOUDNESS_MAX_HOPS = (30, 32, 200)
+# every size the spectrum kernel takes, each its own split into passes; the large ones rarely: their rows are long and their hops,
+# n_fft / 8 at the least, need a walk's worth of frames
+SPECTRUM_N, SPECTRUM_N_P = (256, 512, 1024, 2048, 4096, 8192), (0.24, 0.2, 0.2, 0.14, 0.14, 0.08)
+SPECTRUM_WINDOWS = ("hann", "random")                            # (test_gpu_spectrum._window)
+SPECTRUM_MAX_ROWS = (1, 8)
+# per step and meter: an absent one is set, a present one is replaced, reset or cleared; per step: a refused fill
+P_SET, P_REPLACE, P_RESET, P_CLEAR, P_REFUSED = 0.6, 0.03, 0.03, 0.02, 0.04
 MAX_FRAMES = (1024, 1000, 1031, 300, 64, 2048)
 # around the kernels' tiles (room 32, EQ 64, drive 240, dynamics 256, the 256-frame blocks of the meters and the limiter), the drive's
 # latency of 16 and history of 32 frames, and the flanger's tile of 32 and its group of 256 frames, eight tiles whose input is loaded
@@ -127,7 +153,7 @@ def _params(rng, stage, shape):
 
 def walk(seed):
     """-> (setup, steps): setup = {"max_frames", "timing"}, steps a list of actions, each a dict with a "kind" of KINDS_OF_ACTION.  20 to
-    30 steps, at least 12 of them fills.  The generator keeps book of what is present, so that a clear or a kept-state entry always
+    30 steps of CHAIN_KINDS, at least 12 of them fills, and between them the meters' actions and refused fills of METER_KINDS (_splice).  The generator keeps book of what is present, so that a clear or a kept-state entry always
     meets an effect, the limiter's ceiling always has a master fill behind it to be taken from, and a handover happens once at most.
     The last step is a master fill, so that a walk ends with every return and the master fader arrived (Master.check_committed).
     The opening takes the inserts from the seed's low five bits and the stem stages from its low three, and DEFAULT_SEEDS is 32: the
@@ -220,7 +246,64 @@ def walk(seed):
         else:
             steps.append(dict(kind="handover"))
             handed = True
-    return setup, steps
+    return setup, _splice(seed, setup, steps)
+
+
+def _spectrum_hops(n_fft):
+    return (max(16, n_fft // 8), n_fft // 2, n_fft + 37)
+
+
+def _splice(seed, setup, steps):
+    """the steps with the actions of METER_KINDS between them, drawn by a generator of its own (seed ^ METER_SALT), so that the steps
+    of CHAIN_KINDS are the ones the seed has always given, in their order (tests/test_post_walk_host.py holds them to a digest).
+    Nothing goes behind the last step, which stays a master fill.  A meter that is absent is set soon and one that is present mostly
+    stays: the walks are short, and a meter is worth its frames.  A spectrum meter that is set while one is present takes another
+    n_fft two times in three — the state's device copies are then reserved anew at another size (S2rMirror)."""
+    rng = np.random.RandomState(seed ^ METER_SALT)
+    loud = spec = None
+    out = []
+    masters = [a["frames"] if a["kind"] == "fill" and a["fill"] in ("master", "master_stems") else 0 for a in steps]
+    ahead = np.cumsum(masters[::-1])[::-1]                       # the frames of the master fills from step k on: never 0, the last step is one
+
+    def loudness():
+        return dict(kind="loudness_set", replaces=loud is not None, hop=int(LOUDNESS_HOPS[int(rng.choice(len(LOUDNESS_HOPS), p=LOUDNESS_HOP_P))]),
+                    max_hops=int(_pick(rng, LOUDNESS_MAX_HOPS)))
+
+    def spectrum(k):
+        # a size whose shortest hop the master fills still to come cannot complete is not drawn: its rows would never be compared
+        p = np.array(SPECTRUM_N_P) * [_spectrum_hops(n)[0] <= ahead[k] for n in SPECTRUM_N]
+        if spec is not None and rng.rand() < 2.0 / 3.0:
+            p[SPECTRUM_N.index(spec["n_fft"])] = 0.0
+        if not p.any():
+            return None
+        n_fft = int(SPECTRUM_N[int(rng.choice(len(SPECTRUM_N), p=p / p.sum()))])
+        return dict(kind="spectrum_set", replaces=spec is not None, n_fft=n_fft, hop=int(_pick(rng, _spectrum_hops(n_fft))),
+                    window=str(_pick(rng, SPECTRUM_WINDOWS)), max_rows=int(_pick(rng, SPECTRUM_MAX_ROWS)))
+
+    for k, a in enumerate(steps):
+        u = rng.rand(3)
+        if loud is None and u[0] < P_SET or loud is not None and u[0] < P_REPLACE:
+            loud = loudness()
+            out.append(loud)
+        elif loud is not None and u[0] < P_REPLACE + P_RESET:
+            out.append(dict(kind="loudness_reset"))
+        elif loud is not None and u[0] < P_REPLACE + P_RESET + P_CLEAR:
+            out.append(dict(kind="loudness_clear"))
+            loud = None
+        if spec is None and u[1] < P_SET or spec is not None and u[1] < P_REPLACE:
+            new = spectrum(k)
+            if new is not None:
+                spec = new
+                out.append(spec)
+        elif spec is not None and u[1] < P_REPLACE + P_RESET:
+            out.append(dict(kind="spectrum_reset"))
+        elif spec is not None and u[1] < P_REPLACE + P_RESET + P_CLEAR:
+            out.append(dict(kind="spectrum_clear"))
+            spec = None
+        if u[2] < P_REFUSED:                                     # one frame more than the handle takes: refused, and nothing moves
+            out.append(dict(kind="refused_fill", n_buses=int(rng.randint(1, 9)), frames=setup["max_frames"] + 1))
+        out.append(a)
+    return out
 
 
 class _Fan:
@@ -248,6 +331,8 @@ class Chain:
         self.irs = {}                                            # the responses: no entry of the library reads one back
         self.peaks = []                                          # the peak of every master of 16 frames and more so far, before the limiter
         self.lim_meters = None                                   # of the last fill that ran the limiter on the handle in hand
+        self.loud, self.spec = None, None                        # the meters behind the limiter: test_gpu_loudness.Meter, test_gpu_spectrum.Meter
+        self.meter_serial = 0                                    # counts the meters that started afresh: sets and resets
         # [frames in which a flanger with a feedback or a cross differed on bits from its twin without (FlangerModel), frames it ran]
         self.recursion = [0, 0]
 
@@ -257,7 +342,9 @@ class Chain:
 
     def present(self):
         return " ".join("%s:%s" % (st, ",".join(str(b) for b in sorted(self.of(st)))) for st in STAGES if self.of(st)) + \
-            (" limiter:%d,%d" % (self.lim.L, self.lim.H) if self.lim else "")
+            (" limiter:%d,%d" % (self.lim.L, self.lim.H) if self.lim else "") + \
+            (" loudness:%d,%d" % (self.loud.hop, self.loud.max_hops) if self.loud else "") + \
+            (" spectrum:%d,%d,%d" % (self.spec.n, self.spec.hop, self.spec.max_rows) if self.spec else "")
 
     def active(self, stage, n_buses):
         """the buses on which S2rPostChain::prepare lets `stage` run in a call of n_buses"""
@@ -361,6 +448,31 @@ class Chain:
         elif kind == "roundtrip":
             for syn in self.handles:
                 roundtrip(self, syn)
+        elif kind == "loudness_set":                             # (while one is present too: it starts afresh, in the model as on the handle)
+            self.loud = LoudnessMeter(action["hop"], action["max_hops"])
+            self.loud.set(*self.handles)
+            self.meter_serial += 1
+        elif kind == "loudness_reset":
+            fan.reset_master_loudness()
+            self.loud.reset()
+            self.meter_serial += 1
+        elif kind == "loudness_clear":
+            fan.clear_master_loudness()
+            self.loud = None
+        elif kind == "spectrum_set":
+            self.spec = SpectrumMeter(action["n_fft"], action["hop"], action["window"], action["max_rows"])
+            self.spec.set(*self.handles)
+            self.meter_serial += 1
+        elif kind == "spectrum_reset":
+            fan.reset_master_spectrum()
+            self.spec.reset()
+            self.meter_serial += 1
+        elif kind == "spectrum_clear":
+            fan.clear_master_spectrum()
+            self.spec = None
+        elif kind == "refused_fill":                             # the model does nothing: the call must leave everything as it was
+            for syn in self.handles:
+                refused_fill(syn, action)
         else:
             raise ValueError(kind)
 
@@ -437,7 +549,7 @@ class Chain:
         the least gain, of the dynamics that ran.  "trace" is for the host file: (stage, bus, changed a bit, excused) of every stage
         that ran, and "gain" the limiter's s' where it ran."""
         if action["fill"] == "panned":
-            return dict(panned=x, dyn_meters={}, trace=[])
+            return dict(self.meter_readings(), panned=x, dyn_meters={}, trace=[])
         nb, n = x.shape[0], x.shape[1]
         assert nb == action["n_buses"] and n == action["frames"]
         y, trace = x, []
@@ -463,6 +575,7 @@ class Chain:
         out = dict(dyn_meters={b: self.of("dyn")[b]["mn"] for b in self.active("dyn", nb)}, trace=trace)
         if action["fill"] == "bus":
             out["buses"] = y
+            out.update(self.meter_readings())                    # a bus fill and a panned fill move no meter
             return out
         m = self.mm.expect(y)
         if n >= 16 and float(np.abs(m).max()) > TWIN_PEAK / 64.0:
@@ -481,7 +594,53 @@ class Chain:
             out["stems"] = y
         out["peaks"], out["energies"] = np_meters(y, m)          # (the master's entry is over the limiter's input)
         out["limiter"] = s2s.S2R_ERR_INVALID if self.lim_meters is None else self.lim_meters
+        # the meters: the stems as the chain leaves them, n_buses of them, and the master as the caller receives it — behind the
+        # limiter where one is on —, whether or not the call asks for stems (s2r.h: s2r_set_master_loudness, s2r_set_master_spectrum)
+        out["meters"] = []                                       # for the host file: which programmes each meter heard, and which it read above 0.0
+        for name, meter in (("loudness", self.loud), ("spectrum", self.spec)):
+            if meter is not None:
+                before, pos = meter.made, meter.pos
+                meter.expect(y, want)
+                made = meter.made - before
+                new = meter.rows[len(meter.rows) - min(made, len(meter.rows)):]
+                # the frames of the call that the rows it completed are taken over: up to the end of the last hop, for a spectrum the last n_fft of them
+                end = made * meter.hop - pos
+                heard = [q[max(0, end - meter.n) if name == "spectrum" else 0:max(0, end)] for q in list(y) + [want]]
+                sounding = {p if p < nb else s2.MAX_BUSES for p, q in enumerate(heard) if q.size and float(np.abs(q).max()) > 2.0 ** -10}
+                positive = {p for p in range(s2.MAX_BUSES + 1) if len(new) and (new.reshape(len(new), s2.MAX_BUSES + 1, -1)[:, p] > 0.0).any()}
+                out["meters"].append(dict(name=name, instance=(self.meter_serial, id(meter)), made=made, sounding=sounding, positive=positive))
+        out.update(self.meter_readings())
         return out
+
+    def meter_readings(self):
+        """what the getters that move nothing must give for the meters that are on: the stored rows and their count, and for the
+        loudness meter the true peak of the last master fill and the held one"""
+        out = {}
+        if self.loud is not None:
+            out.update({"loudness hops": len(self.loud.rows), "loudness rows": self.loud.rows.copy(), "true peak": self.loud.last.copy(),
+                        "true peak held": self.loud.held.copy()})
+        if self.spec is not None:
+            out.update({"spectrum count": len(self.spec.rows), "spectrum rows": self.spec.rows.copy()})
+        return out
+
+    def meter_states(self):
+        """name -> state and position of the meters that are on.  On a handle these are read through getters that fetch the state's
+        device copy, which the next master fill then uploads again (S2rMirror): a walk reads them at a round trip, at a handover,
+        behind every other bus fill or panned fill and at its end, and not between two master fills in a row"""
+        out = {}
+        for name, meter in (("loudness", self.loud), ("spectrum", self.spec)):
+            if meter is not None:
+                out[name + " state"], out[name + " position"] = np.array(meter.state, dtype=F), np.array([meter.pos], dtype=F)
+        return out
+
+    def handed_over(self):
+        """what a handover leaves on the model: the new handle's limiter has not run yet, and the held true peak is no part of a
+        checkpoint (test_gpu_loudness.test_checkpoint_in_the_middle_of_a_hop), so the new handle holds +0.0 — and has made no master
+        fill yet, so the true peak of its last call is +0.0 too until it makes one (seeds 5001, 5015 and 5020: a bus fill or a
+        panned fill directly behind the handover)"""
+        self.lim_meters = None
+        if self.loud is not None:
+            self.loud.held, self.loud.last = np.zeros(2, dtype=F), np.zeros(2, dtype=F)
 
     def states(self):
         """name -> the state every present effect and the limiter carry, as the getters of a handle give them (states_of)"""
@@ -494,7 +653,14 @@ class Chain:
                     out["%s %d" % (st, b)] = np.array(f[dict(eq="st", dyn="y", drive="hist", delay="hist", reverb="hist", room="st")[st]], dtype=F)
         if self.lim is not None:
             out["limiter xh"], out["limiter gh"] = self.lim.xh, self.lim.gh
+        out.update(self.meter_states())
         return out
+
+
+def peeks(k):
+    """whether the walk's step k, a bus fill or a panned fill, has the meters' state and position read behind it: every other one, so
+    that a walk holds master fills directly behind a read and master fills with nothing read since the last one"""
+    return k % 2 == 0
 
 
 def _halves(phase):
@@ -519,7 +685,38 @@ def states_of(chain, syn):
                 out["%s %d" % (st, b)] = np.array(got, dtype=F)
     if chain.lim is not None:
         out["limiter xh"], out["limiter gh"] = syn.limiter_state()
+    out.update(meter_states_of(chain, syn))
     return out
+
+
+def meter_states_of(chain, syn):
+    """Chain.meter_states read from a handle"""
+    out = {}
+    for name, meter, get in (("loudness", chain.loud, "loudness_state"), ("spectrum", chain.spec, "spectrum_state")):
+        if meter is not None:
+            state, pos = getattr(syn, get)()
+            out[name + " state"], out[name + " position"] = np.array(state, dtype=F), np.array([pos], dtype=F)
+    return out
+
+
+def meter_readings_of(chain, syn):
+    """Chain.meter_readings read from a handle: none of these getters touches the state's copies"""
+    out = {}
+    if chain.loud is not None:
+        out["loudness hops"], out["loudness rows"] = int(syn.get_master_loudness()[3]), syn.loudness_hops()
+        out["true peak"], out["true peak held"] = syn.true_peak()
+    if chain.spec is not None:
+        out["spectrum count"], out["spectrum rows"] = int(syn.get_master_spectrum()[3]), syn.spectrum_rows()
+    return out
+
+
+def refused_fill(syn, action):
+    """s2r_fill_master with one frame more than the handle takes: S2R_ERR_TOO_MANY_FRAMES, and neither buffer is written"""
+    n, nb = action["frames"], action["n_buses"]
+    out, st = np.full(2 * n, 7.0, dtype=F), np.full(2 * nb * n, 7.0, dtype=F)
+    rc = syn.L.s2r_fill_master(syn.h, out.ctypes.data_as(s2s._f32p), st.ctypes.data_as(s2s._f32p), st.size, nb, n, SR)
+    assert rc == s2s.S2R_ERR_TOO_MANY_FRAMES, "a master fill of %d frames returns %d" % (n, rc)
+    assert (out == 7.0).all() and (st == 7.0).all(), "a refused master fill wrote its buffers"
 
 
 def _restore(chain, syn, st, b, state):
@@ -536,6 +733,12 @@ def roundtrip(chain, syn):
             _restore(chain, syn, st, b, getattr(syn, GETTERS[st])(b))
     if chain.lim is not None:
         syn.set_limiter_state(*syn.limiter_state())
+    if chain.loud is not None:
+        syn.set_loudness_state(*syn.loudness_state())
+        syn.set_loudness_hops(syn.loudness_hops())
+    if chain.spec is not None:
+        syn.set_spectrum_state(*syn.spectrum_state())
+        syn.set_spectrum_rows(syn.spectrum_rows())
 
 
 def copy_voices(src, dst):
@@ -580,7 +783,17 @@ def handover(chain, src, dst):
     if look:
         dst.set_master_limiter(ceiling, look, hold)
         dst.set_limiter_state(*src.limiter_state())
-    chain.lim_meters = None                                      # the new handle's limiter has not run yet
+    if chain.loud is not None:                                   # parameters as src's getter gives them, then state, position and rows
+        c, hop, max_hops, _ = src.get_master_loudness()
+        dst.set_master_loudness(SR, hop, max_hops, c)
+        dst.set_loudness_state(*src.loudness_state())
+        dst.set_loudness_hops(src.loudness_hops())
+    if chain.spec is not None:
+        n_fft, hop, max_rows, _, window = src.get_master_spectrum()
+        dst.set_master_spectrum(n_fft, hop, window, max_rows)
+        dst.set_spectrum_state(*src.spectrum_state())
+        dst.set_spectrum_rows(src.spectrum_rows())
+    chain.handed_over()
     chain.handles = (dst,)
 
 
@@ -590,7 +803,9 @@ def subset_walk():
     master fill under the limiter, 33 frames a call, 96 calls; a chorus on bus 2 and a reverb on bus 1 stay on throughout, so the
     inserts sit in front of and behind running stem stages.  The flanger sits on bus 2 with H = 33 — every tap exactly one tile old —,
     behind a drive and in front of the chorus and a room, and on bus 1 with a feedback and a cross, in front of the reverb and a room;
-    bus 0 carries none, so its launch copies that bus"""
+    bus 0 carries none, so its launch copies that bus.  Both meters are on from the start, a loudness meter at hop 17 — the hop that
+    ends on the last frame of a walker's block — and a spectrum meter at N = 1024 with a hop of 128: the 64 master fills feed them
+    2112 frames through every change of inserts, with a limiter in front of them in every other one"""
     where = dict(eq=(0, 1), dyn=(1, 2), drive=(0, 2), flanger=(2, 1), room=(1, 2))
     shapes = dict(eq=[dict(bands=2, seed=1), dict(bands=4, seed=3)],
                   dyn=[dict(key=0, ratio=0, below=14.0, coefs="1ms-100ms"), dict(key=2, ratio=2, below=6.0, coefs="zero")],
@@ -599,7 +814,9 @@ def subset_walk():
                            dict(H=65, inc=89478 * 20, spread=7, feedback=-0.5, cross=0.25, dry=0.5, wet=0.75)],
                   room=[dict(delays="small", levels="dark"), dict(delays="flat", levels="hall")])
     steps = [dict(kind="set", stage="chorus", bus=2, replaces=False, shape=dict(H=145, voices=3, inc=89478 * 20, spread=0x40000000, dry=0.5, wet=0.25)),
-             dict(kind="set", stage="reverb", bus=1, replaces=False, shape=dict(K=40, stereo=True, seed=77, dry=0.25, wet=1.0))]
+             dict(kind="set", stage="reverb", bus=1, replaces=False, shape=dict(K=40, stereo=True, seed=77, dry=0.25, wet=1.0)),
+             dict(kind="loudness_set", replaces=False, hop=17, max_hops=32),
+             dict(kind="spectrum_set", replaces=False, n_fft=1024, hop=128, window="hann", max_rows=8)]
     on = 0
     for i in range(1 << len(INSERTS)):
         gray = i ^ (i >> 1)

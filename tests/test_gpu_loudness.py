@@ -23,6 +23,30 @@ F = np.float32
 V = 32
 T = 256                                                          # S2R_LOUDNESS_TILE and S2R_LOUDNESS_BLOCK
 MASTER = s2.MAX_BUSES
+BLOCK = 8                                                        # frames a walker takes at a time (s2r_loudness.hip: kLdBlock)
+# the parity matrix: the frames of its calls, and the (n_buses, hop) it runs them at.  Hop 17 is there for the walkers' fast path: a
+# block of eight frames runs without a hop test when hop - pos > 8, and over CALLS hop 17 starts a block at every distance from 1 to
+# 9 — 8, where the hop ends on the block's last frame and `>` and `>=` part, among them; the hops 16, 48, 100 and 4800 never meet 8
+# (tests/test_loudness_host.py asserts both through walker_distances).  (8, 16) feeds all 18 walker lanes at the smallest hop.
+CALLS = (1, 2, 3, 4, 5, T - 1, T, T + 1, 1023, 1024, 2047, 2048)
+PARITY = ((1, 16), (2, 48), (3, 100), (8, 4800), (8, 17), (8, 16))
+
+
+def walker_distances(hop, calls, pos=0):
+    """the schedule of the kernel's walkers (s2r_loudness.hip, workgroup 0) replayed on the books, no arithmetic on samples: a call is
+    walked in tiles of T frames, a tile in full blocks of BLOCK frames and then a tail of fewer, frame by frame; `pos`, the frames into
+    the hop, is carried from call to call.  -> (the set of hop - pos met at the start of a full block, the number of full blocks, pos)"""
+    met, blocks = set(), 0
+    for n in calls:
+        for t0 in range(0, n, T):
+            cnt = min(T, n - t0)
+            full = cnt // BLOCK
+            for _ in range(full):
+                met.add(hop - pos)
+                pos = (pos + BLOCK) % hop                        # (hop >= 16: at most one hop ends inside a block)
+            blocks += full
+            pos = (pos + cnt - full * BLOCK) % hop
+    return met, blocks, pos
 
 
 class Meter:
@@ -129,16 +153,17 @@ def test_output_is_unchanged_and_rows_follow_the_reference(limiter):
         assert a.limiter_meters()[0] < 1.0 and np.abs(x).max() <= F(ceiling)
 
 
-@pytest.mark.parametrize("nb,hop", [(1, 16), (2, 48), (3, 100), (8, 4800)])
+@pytest.mark.parametrize("nb,hop", PARITY)
 def test_rows_state_and_true_peak_are_the_reference(nb, hop):
-    """the parity matrix, max_frames 2048: calls of 1 to 5 frames, of T - 1, T and T + 1, of 1023, 1024, 2047 and 2048 frames, then
-    calls that end exactly on a hop, one frame before one and one frame after one; events between the calls, every other call without
-    stems, the state compared after the short calls, the tile edges and at the end"""
+    """the parity matrix, max_frames 2048: CALLS — calls of 1 to 5 frames, of T - 1, T and T + 1, of 1023, 1024, 2047 and 2048
+    frames —, then calls that end exactly on a hop, one frame before one and one frame after one; events between the calls, every
+    other call without stems, the state compared after the short calls, the tile edges and at the end.  With eight buses at hops 17
+    and 16 every walker lane is fed while a hop ends inside most blocks, at hop 17 on a block's last frame too (walker_distances)"""
     a, b = _handles(V, max_frames=2048)
     m = Meter(hop)
     m.set(a)
     what = "%d buses, hop %d" % (nb, hop)
-    calls = [1, 2, 3, 4, 5, T - 1, T, T + 1, 1023, 1024, 2047, 2048]
+    calls = list(CALLS)
     for fill, n in enumerate(calls):
         _events((a, b), V, fill)
         _mfill(a, b, m, n, nb, "%s, fill %d of %d frames" % (what, fill, n), stems=fill % 2 == 0, state=fill in (4, 7))

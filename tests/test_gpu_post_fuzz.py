@@ -2,12 +2,21 @@
 tests/post_walk.py, played on twin handles.  Handle `a` makes the walk's calls; its twin `b` is fed the same events and makes a plain bus
 fill of the same frames and buses every time (a panned one for a panned fill), so its output is the dry signal; the expectation is
 post_walk.Chain over it — per bus the EQ's, the dynamics', the drive's, the flanger's, the chorus's, the delay's, the reverb's and the
-room's model, eight of them, then the master section's and the limiter's, each the one its tests/test_*_host.py file pins to numpy on bits.  The device is never compared
-with itself.  What a walk varies: which effects sit on which of eight buses and in what shape, n_buses and frames from call to call,
+room's model, eight of them, then the master section's and the limiter's, and behind the limiter the loudness meter's and the spectrum
+meter's (test_gpu_loudness.Meter, test_gpu_spectrum.Meter), each the one its tests/test_*_host.py file pins to numpy on bits.  The device
+is never compared with itself.  What a walk varies: which effects sit on which of eight buses and in what shape, n_buses and frames from call to call,
 max_frames, the kind of fill, kept-state parameter moves, sets in mid-tail, state round trips, timing, and one handover of the whole
 chain onto a fresh handle — the flanger's line and phase go through the round trip, the handover and the final comparison as the
-chorus's do.  tests/test_post_walk_host.py asserts on the CPU that the default seeds cover all of that, and that a flanger runs in
-calls of more than 1024 frames, at H = 4096, in calls of 255, 256 and 257 frames, and idles between two fills that run it.
+chorus's do.  The meters are set, replaced — a spectrum meter at another of its six sizes —, reset and
+cleared between the chain's steps, by a second generator that leaves those steps what they were; a master fill feeds each meter that
+is on the stems as the chain leaves them and the master as the caller receives it, and its rows, their count and the true peaks are
+compared behind every fill, a bus fill and a panned fill having to leave them alone; state, position and rows go through the round
+trip and the handover, in the middle of a hop, and state and position are compared there, behind every other bus fill and panned
+fill and at the end of the walk — not between two master fills in a row, so that the state's device copies flip unread as well as being
+fetched and uploaded again (S2rMirror).  A master fill of max_frames + 1 frames must be refused and move nothing.
+tests/test_post_walk_host.py asserts on the CPU that the default seeds cover all of that, and that a flanger runs in
+calls of more than 1024 frames, at H = 4096, in calls of 255, 256 and 257 frames, and idles between two fills that run it, and
+what the meters meet: its conditions 8 to 16.
 
 Deterministic: the seeds are fixed and a failure names its seed, step and action and the effects present at that step;
 S2R_POST_FUZZ_BASE=<that seed> S2R_POST_FUZZ_SEEDS=1 runs it again.  Every comparison is on bits with no NaN allowance
@@ -19,7 +28,14 @@ first sweeps did find was in the walks: seeds 100022 and 100037 (a walk that end
 limiter whose ceiling, taken from an earlier and louder master, never worked), and on the host seed 300349 (a room under a dry of 1
 whose first turn of the lines lies below half an ulp of the bus: post_walk.Chain._excused) and, with the flanger, seeds 5001, 200158,
 200335 and 300143 (a flanger under a dry of 1 whose taps of the call are all +0.0 at the far end of its line, or read the first
-frame behind a drive, 1e-37: the same place)."""
+frame behind a drive, 1e-37: the same place).
+With the meters in the walks, 400 walks at base 400000 beside the default 32 have run equal on bits, and the model alone was well behaved
+over the same 400 (tests/test_post_walk_host.py): no seed has found a fault in the meters, in their mirrors' transitions or in the
+chain in front of them.  What the first run found was in the walk's model: seeds 5001, 5015 and 5020 (a bus fill or a panned fill
+directly behind the handover: the fresh handle has made no master fill, so the true peak of its last call reads +0.0, not the old
+handle's: post_walk.Chain.handed_over).  Tried once against a library with two defects put in — the walkers' block test turned from >
+to >=, and one wrong twiddle in the four-layer pass at s0 = 8 that N = 4096 alone runs —, 31 of the default seeds and the subset
+walk failed."""
 import os
 
 import numpy as np
@@ -45,6 +61,8 @@ def play(setup, steps, name):
     got, fill = [], 0                                            # (what, what the device returned, what Chain.expect returned, the twin's output)
     for k, action in enumerate(steps):
         what = "%s, step %d %r [present: %s]" % (name, k, action, chain.present())
+        if action["kind"] in ("roundtrip", "handover"):          # what the meters carry into it: these steps read their state anyway
+            got.append((what + ", on the way in", pw.meter_states_of(chain, a), chain.meter_states(), None))
         if action["kind"] == "handover":
             # The whole chain onto a fresh handle, and the walk goes on there.  The twin is handed over the same way, voices alone: which
             # voice the next note_on takes is the pool's, not part of an exported state, and only handles made alike choose alike.
@@ -80,12 +98,19 @@ def play(setup, steps, name):
                     except s2.S2rError as err:
                         dev["limiter"] = err.status
                 dev["dyn_meters"] = {bus: a.bus_dynamics_meter(bus) for bus in want["dyn_meters"]}
+            # the meters that are on: rows, their count and the true peaks behind every fill — a bus fill and a panned fill must leave
+            # them as they were —, through getters that leave the state's copies alone.  State and position, whose getter fetches the
+            # device copy for the next master fill to upload again, behind every other bus fill and panned fill only (post_walk.peeks)
+            dev.update(pw.meter_readings_of(chain, a))
+            if action["fill"] in ("bus", "panned") and pw.peeks(k):
+                dev.update(pw.meter_states_of(chain, a))
+                want.update(chain.meter_states())
             got.append((what, dev, want, x))
     final = pw.states_of(chain, a)
     # on the model and the twin, before anything is compared: the dry signal is finite and sounds, and a walk that limits does limit
     for what, dev, want, x in got:
-        assert np.isfinite(x).all(), what + ": the twin's output is not finite"
-        assert ubits(x).any() or x.shape[-2] == 1, what + ": the twin is silent"      # (a voice's first frame is +0.0)
+        assert x is None or np.isfinite(x).all(), what + ": the twin's output is not finite"
+        assert x is None or ubits(x).any() or x.shape[-2] == 1, what + ": the twin is silent"      # (a voice's first frame is +0.0)
     for what, dev, want, x in got:                               # (Chain.expect lowers the ceiling where a master would stay under it)
         assert "gain" not in want or (want["gain"] < 1.0).any() or float(want["peaks"][-1].max()) <= 2.0 ** -19, what + ": the limiter does not work"
     for what, dev, want, x in got:
@@ -119,7 +144,13 @@ def test_every_insert_subset_on_every_kind_of_call():
     reverb on bus 1 stay on throughout.  An insert that is cleared and set again starts afresh in the model too.  The per-stage files
     run each insert alone, {EQ, dyn}, {EQ, dyn, room}, {EQ, dyn, drive, room} and all five; the seeded walks open on all 32 subsets,
     each on a fresh handle, and this is the one test that goes from subset to subset on one handle, so that the set of a flanger's
-    neighbours changes while its line and phase are in mid-state, and every other insert's while a flanger is."""
+    neighbours changes while its line and phase are in mid-state, and every other insert's while a flanger is.  A loudness meter at
+    hop 17 and a spectrum meter at N = 1024 are on throughout: what they are fed changes with every insert, and every other master
+    fill reaches them through the limiter."""
     setup, steps = pw.subset_walk()
     chain, got = play(setup, steps, "the subset walk")
     assert len(got) == 96 and all("gain" in want and (want["gain"] < 1.0).any() for _, _, want, _ in got[2::3])
+    # both meters from the first call to the last: every call compares rows and true peak, and the 64 master fills make 124 hops of 17
+    # frames and 16 spectrum rows
+    assert all({"loudness rows", "true peak", "true peak held", "spectrum rows"} <= set(dev) for _, dev, _, _ in got)
+    assert chain.loud.made == 64 * 33 // 17 and chain.spec.made == 64 * 33 // 128 and len(chain.loud.rows) == 32 and len(chain.spec.rows) == 8

@@ -6,7 +6,10 @@ numpy (tests/test_spectrum_host.py holds that function to a numpy model of the r
 Handles, events and the one-pole bank are tests/test_gpu_reverb.py's on 32-voice pools, max_frames 1024 or 2048.  Every comparison is
 on bits with no NaN allowance.  The kernel runs one workgroup per row and programme, whatever the call's length, so its edges are the
 hop's (a call that ends one frame before, on and after one), the size's (a row that lies in the history alone, across both sources,
-in the call alone) and the passes' (log2 N of 8, 9, 11 and 13: two to four passes of three or four layers)."""
+in the call alone) and the passes': every log2 N of 8 .. 13, whose layers the kernel splits into passes of 4 4 | 3 3 3 | 4 3 3 |
+4 4 3 | 4 4 4 | 4 3 3 3 — N = 1024 alone runs with 128 threads, N = 4096 alone with 512 and alone runs a pass of four layers at
+s0 = 8.  The matrix, the crafted histories and the walk from size to size on one handle run all six; tests/test_gpu_post_fuzz.py
+sets, replaces and checkpoints meters of all six behind a chain in mid-state."""
 import ctypes as C
 
 import numpy as np
@@ -117,7 +120,8 @@ def test_output_is_unchanged(limiter, loudness):
         assert a.limiter_meters()[0] < 1.0
 
 
-MATRIX = [(1, 256, 32), (2, 512, 384), (3, 2048, 512), (8, 8192, 1024), (2, 256, 1000)]
+# every log2 N of 8 .. 13: N = 1024 is the one size of 128 threads and passes 4, 3, 3; N = 4096 the one of 512 threads and passes 4, 4, 4
+MATRIX = [(1, 256, 32), (2, 512, 384), (2, 1024, 128), (3, 2048, 512), (3, 4096, 512), (8, 8192, 1024), (2, 256, 1000)]
 
 
 @pytest.mark.parametrize("window", ["hann", "random"])
@@ -139,7 +143,7 @@ def test_rows_and_state_are_the_reference(nb, n, hop, window):
     assert (last[:nb] > 0.0).any(axis=1).all() and not ubits(m.rows[:, nb:MASTER]).any() and (last[MASTER] > 0.0).any()
 
 
-@pytest.mark.parametrize("n,hop", [(256, 64), (2048, 512), (8192, 1024)])
+@pytest.mark.parametrize("n,hop", [(256, 64), (1024, 128), (2048, 512), (4096, 512), (8192, 1024)])
 def test_crafted_histories(n, hop):
     """set_spectrum_state loads a unit impulse at several positions of several programmes, then random finite values, then denormals;
     one silent frame completes a hop.  Rows are the reference's bits; an impulse of 1 on L at frame i of the row reads
@@ -283,12 +287,15 @@ def test_reset_and_clear():
 
 def test_a_larger_size_and_the_smaller_one_again():
     """the state's two device copies are sized by the first fill, regrown by the fill behind a set at a larger size and used as they
-    are behind a set at the smaller size again: sizes 256 (hop 32), 512 (hop 64) and 256 on one handle, two master fills of two buses
-    each.  Every set leaves no rows and a state of +0.0 at position 0; every fill returns the bits of a twin that never had a meter,
-    and rows and state are the reference's bits, compared as in test_rows_and_state_are_the_reference"""
+    are behind a set at the smaller size again: sizes 256 (hop 32), 512 (hop 64), 1024 (hop 128), 4096 (hop 512), 1024 and 256 on one
+    handle, two master fills of two buses each — so the two sizes whose split into passes no other size shares (4 3 3 and 4 4 4) run
+    on copies that were sized for another transform, growing and as they are.  Every set leaves no rows and a state of +0.0 at
+    position 0; every fill returns the bits of a twin that never had a meter, and rows and state are the reference's bits, compared
+    as in test_rows_and_state_are_the_reference.  601 frames make 18 and 9 rows at the two small sizes, which fill the window of 8,
+    4 at 1024 and one at 4096."""
     a, b = _handles(V, max_frames=512)
     fill = 0
-    for n, hop in ((256, 32), (512, 64), (256, 32)):
+    for n, hop in ((256, 32), (512, 64), (1024, 128), (4096, 512), (1024, 128), (256, 32)):
         m = Meter(n, hop)
         m.set(a)
         assert a.spectrum_rows().size == 0
@@ -298,7 +305,8 @@ def test_a_larger_size_and_the_smaller_one_again():
             _events((a, b), V, fill)
             _mfill(a, b, m, frames, 2, "N %d, fill %d of %d frames" % (n, fill, frames), stems=fill % 2 == 0, state=True)
             fill += 1
-        assert m.made == 601 // hop and len(m.rows) == 8 and (m.rows[-1, [0, 1, MASTER]] > 0.0).any(axis=1).all()
+        assert m.made == 601 // hop >= 1 and len(m.rows) == min(8, m.made) and (m.rows[-1, [0, 1, MASTER]] > 0.0).any(axis=1).all()
+        assert n > 512 or len(m.rows) == 8
 
 
 def test_refusals_change_nothing():

@@ -15,6 +15,7 @@ import pytest
 from helpers import assert_bits_equal_finite
 import synth2_amd as s2
 from synth2_amd import synth as s2s
+from test_gpu_loudness import BLOCK, CALLS, PARITY, T, walker_distances       # (the device file imports without a device)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TRUTH = os.path.join(ROOT, "profiles", "truth", "loudness_deviation.json")
@@ -318,6 +319,27 @@ def test_reference_refusals_touch_nothing():
         assert call(**kw) == s2s.S2R_ERR_INVALID, kw
     assert (state == 3.0).all() and (rows == 3.0).all() and (tp == 3.0).all() and pos.value == 5 and n.value == 77
     assert call() == s2s.S2R_OK and n.value == 1 and pos.value == 5 and not (rows == 3.0).any()
+
+
+# ---------------------------------------------------------------- what the device matrix meets of the walkers' schedule
+
+def test_the_parity_matrix_meets_the_walkers_block_boundary():
+    """The kernel's walkers take a block of eight frames without a hop test when hop - pos > 8 (s2r_loudness.hip).  A distance of
+    exactly 8 — the hop ends on the block's last frame — is the one value at which `>` and `>=` differ, and a wrong comparison there
+    loses the hop for good: pos steps past hop.  Replayed on the books over the matrix's calls (test_gpu_loudness.walker_distances),
+    hop 17 starts a full block at every distance from 1 to 9 and at some beyond, and the matrix runs it with all eight buses fed; the
+    matrix's other hops never meet 8, which is why 17 is in it."""
+    met = {hop: walker_distances(hop, CALLS)[0] for _, hop in PARITY}
+    assert met[17] >= set(range(1, 10)) and max(met[17]) > 9, sorted(met[17])
+    assert any(nb == s2.MAX_BUSES and BLOCK in met[hop] for nb, hop in PARITY)
+    assert all(BLOCK not in met[hop] for hop in (16, 48, 100, 4800))
+    assert (s2.MAX_BUSES, 16) in PARITY                          # the smallest hop with all 18 lanes fed
+    # the replay itself: a call shorter than a block has none, a tile's tail is walked frame by frame, pos is carried
+    assert walker_distances(17, [7]) == (set(), 0, 7)
+    assert walker_distances(17, [8, 8, 8]) == ({17, 9, 1}, 3, 7)
+    assert walker_distances(16, [T + 9]) == ({16, 8}, T // BLOCK + 1, 9) and walker_distances(100, [T + 9], 99)[0] >= {1, 93, 5}
+    blocks = sum(n // T * (T // BLOCK) + n % T // BLOCK for n in CALLS)
+    assert all(walker_distances(hop, CALLS)[1:] == (blocks, sum(CALLS) % hop) for _, hop in PARITY)
 
 
 # ---------------------------------------------------------------- the readings against the float64 model

@@ -1,7 +1,9 @@
 """What the seeded walks of tests/post_walk.py cover, and that the chain's host model alone is well behaved over them — on the CPU, over
 the default seeds of tests/test_gpu_post_fuzz.py.  The coverage conditions are conditions on the inputs: the generator's weights and the
 default seed count are chosen so that they hold, and this file asserts them."""
+import hashlib
 import itertools
+import json
 import os
 
 import numpy as np
@@ -9,6 +11,7 @@ import pytest
 
 import post_walk as pw
 from post_walk import FILLS, INSERTS, STAGES, STEMS, TWIN_PEAK, Chain, walk
+from test_gpu_loudness import BLOCK, walker_distances
 
 F = np.float32
 BASE = int(os.environ.get("S2R_POST_FUZZ_BASE", str(pw.DEFAULT_BASE)))
@@ -27,7 +30,9 @@ def survey(seeds):
              flanger=dict(frames=set(), H=set(), idle_between_runs=False, roundtrips=0, handovers=0))
     for seed in seeds:
         setup, steps = walk(seed)
-        assert 20 <= len(steps) <= 30 and sum(a["kind"] == "fill" for a in steps) >= 12, seed
+        chain_steps = [a for a in steps if a["kind"] in pw.CHAIN_KINDS]      # (the counts are of these, as before the meters joined)
+        assert 20 <= len(chain_steps) <= 30 and sum(a["kind"] == "fill" for a in chain_steps) >= 12, seed
+        assert steps[-1]["kind"] == "fill" and steps[-1]["fill"] in ("master", "master_stems"), seed
         assert sum(a["kind"] == "handover" for a in steps) <= 1, seed
         s["max_frames"].add(setup["max_frames"])
         s["timing"].add(setup["timing"])
@@ -137,6 +142,164 @@ def test_the_default_walks_cover_what_they_are_for():
     assert fl["roundtrips"] >= 1 and fl["handovers"] >= 1, "a flanger's state goes through %d round trips and %d handovers" % (fl["roundtrips"], fl["handovers"])
 
 
+# sha256 of json.dumps([setup, steps], sort_keys=True), its first 12 digits, of walk(seed) for the 32 default seeds, computed at commit
+# f757cfa — the last one before the meters joined the walks, when every step was of CHAIN_KINDS
+CHAIN_STEPS_DIGESTS = (
+    "59a64a533536", "4e6d7eeda456", "3cfe4c0845c7", "a9f5c0d130ed", "65a61f0d9ba0", "b774507e0f50", "51ef85b77561", "2fb401e058dc",
+    "20f0f8799722", "ec95aa516ca7", "72020063398b", "f3a6b3acb4b0", "482a164a904c", "c626d0658bf6", "3d76e8420cd1", "020a99b66ca9",
+    "4c20ec6603af", "3779fed92e31", "a33b17dfab49", "05f509eb309c", "20135c851ec2", "a68f720aa7ce", "eacc442e1e10", "f746b734883b",
+    "1e61c9ab1d37", "816e3ba3820b", "4187f5fa702d", "41668bf85699", "a3becf003b90", "e2959b7bc2c1", "867942b89cf3", "fd880923ac8f")
+
+
+def test_the_chain_steps_of_the_default_seeds_are_what_they_were():
+    """the meters' actions are spliced between the steps a seed has always given: with them taken out, walk(seed) is the walk of the
+    commit before, step for step — the seeds with a history in tests/test_gpu_post_fuzz.py's docstring, and the 1200 recorded there as
+    clean, still name the walks they named"""
+    assert len(CHAIN_STEPS_DIGESTS) == len(DEFAULTS) == 32
+    for seed, want in zip(DEFAULTS, CHAIN_STEPS_DIGESTS):
+        setup, steps = walk(seed)
+        assert any(a["kind"] in pw.METER_KINDS for a in steps), seed
+        chain_steps = [a for a in steps if a["kind"] in pw.CHAIN_KINDS]
+        assert hashlib.sha256(json.dumps([setup, chain_steps], sort_keys=True).encode()).hexdigest()[:12] == want, seed
+
+
+class Book:
+    """a meter on the books: what its position, its stored rows and the rows it has made are after calls of given lengths"""
+
+    def __init__(self, name, action, serial):
+        self.name, self.hop, self.serial = name, action["hop"], serial
+        self.keep = action["max_hops"] if name == "loudness" else action["max_rows"]
+        self.n_fft = action.get("n_fft")
+        self.replaced_another_size = False
+        self.restart()
+
+    def restart(self):
+        self.pos = self.stored = self.made = 0
+        self.calls = []                                          # the frames of the master fills since it started afresh
+        self.sat = set()                                         # the fills it has sat through since the last master fill
+
+    def feed(self, frames):
+        k = (self.pos + frames) // self.hop
+        self.pos, self.made, self.stored = (self.pos + frames) % self.hop, self.made + k, min(self.keep, self.stored + k)
+        self.calls.append(frames)
+        return k
+
+
+def meter_survey(seeds):
+    """the meters of the walks on the books alone -> what the conditions of test_the_default_walks_cover_the_meters ask about"""
+    both = ("loudness", "spectrum")
+    s = dict(sizes_with_a_row=set(), replaced_and_compared=False, limiter_and_both=False, without_stems=set(), roundtrips={m: 0 for m in both},
+             handovers={m: 0 for m in both}, big={m: False for m in both}, overflow=False, short=False, sat_through_both=False, blocks_at_17=0,
+             met_at_17=set(), fill_behind_fill=False, fill_behind_read=set(), refused_with_a_meter=0, hops=set(), max_hops=set(), spectrum_hops=set(),
+             windows=set(), max_rows=set(), replaced={m: 0 for m in both}, reset_with_rows={m: 0 for m in both})
+    for seed in seeds:
+        setup, steps = walk(seed)
+        on, limiter, serial = {}, False, 0                       # name -> Book
+        last = None                                              # what the state's copies met last: a master "fill", the kind of step that read them, or None
+        for k, a in enumerate(steps):
+            kind = a["kind"]
+            now = None
+            if kind in ("loudness_set", "spectrum_set"):
+                name = kind.split("_")[0]
+                assert a["replaces"] == (name in on), seed
+                serial += 1
+                book = Book(name, a, serial)
+                if name in on:
+                    s["replaced"][name] += 1
+                    book.replaced_another_size = name == "spectrum" and on[name].n_fft != a["n_fft"]
+                on[name] = book
+                if name == "loudness":
+                    s["hops"].add(a["hop"]); s["max_hops"].add(a["max_hops"])
+                else:
+                    assert a["hop"] in pw._spectrum_hops(a["n_fft"]) and a["hop"] >= max(32, a["n_fft"] // 8), seed
+                    s["spectrum_hops"].add(pw._spectrum_hops(a["n_fft"]).index(a["hop"])); s["windows"].add(a["window"]); s["max_rows"].add(a["max_rows"])
+            elif kind in ("loudness_reset", "spectrum_reset"):
+                name = kind.split("_")[0]
+                s["reset_with_rows"][name] += on[name].stored > 0
+                on[name].restart()
+            elif kind in ("loudness_clear", "spectrum_clear"):
+                del on[kind.split("_")[0]]
+            elif kind == "refused_fill":
+                assert a["frames"] == setup["max_frames"] + 1 and 1 <= a["n_buses"] <= 8, seed
+                s["refused_with_a_meter"] += bool(on)
+                now = last                                       # (it must move nothing: what the next fill meets is what it would have met)
+            elif kind in ("limiter_set", "limiter_clear"):
+                limiter = kind == "limiter_set"
+            elif kind in ("roundtrip", "handover"):
+                for name, book in on.items():
+                    if book.pos != 0 and book.stored >= 1:
+                        s[kind + "s"][name] += 1
+                now = kind if on else None
+            elif kind == "fill" and a["fill"] in ("bus", "panned"):
+                for book in on.values():
+                    if book.calls:
+                        book.sat.add(a["fill"])
+                now = a["fill"] if on and pw.peeks(k) else last
+            elif kind == "fill":
+                n = a["frames"]
+                if on and last == "fill":
+                    s["fill_behind_fill"] = True
+                if on and last not in (None, "fill"):
+                    s["fill_behind_read"].add(last)
+                if limiter and len(on) == 2:
+                    s["limiter_and_both"] = True
+                for name, book in on.items():
+                    if a["fill"] == "master":
+                        s["without_stems"].add(name)
+                    if book.sat >= {"bus", "panned"}:
+                        s["sat_through_both"] = True
+                    book.sat = set()
+                    made = book.feed(n)
+                    s["big"][name] |= n > 1024
+                    s["overflow"] |= made > book.keep
+                    s["short"] |= n < book.hop and made == 0
+                    if name == "spectrum" and made:
+                        s["sizes_with_a_row"].add(book.n_fft)
+                        s["replaced_and_compared"] |= book.replaced_another_size
+                    if name == "loudness" and book.hop == 17:
+                        met, blocks, pos = walker_distances(17, book.calls)
+                        assert pos == book.pos
+                        if blocks > s["blocks_at_17"]:
+                            s["blocks_at_17"], s["met_at_17"] = blocks, met
+                now = "fill" if on else None
+            else:
+                now = last                                       # (no entry of the chain in front touches the meters' copies)
+            last = now
+    return s
+
+
+def test_the_default_walks_cover_the_meters():
+    """the conditions on the second generator (post_walk._splice), asserted the way the chain's are: its weights are chosen so that they
+    hold over the default seeds"""
+    s = meter_survey(DEFAULTS)
+    # 8. every shape the meters are drawn in; each of the six transform sizes is set in some walk and completes a row there
+    assert s["hops"] == set(pw.LOUDNESS_HOPS) and s["max_hops"] == set(pw.LOUDNESS_MAX_HOPS)
+    assert s["spectrum_hops"] == {0, 1, 2} and s["windows"] == set(pw.SPECTRUM_WINDOWS) and s["max_rows"] == set(pw.SPECTRUM_MAX_ROWS)
+    assert s["sizes_with_a_row"] == set(pw.SPECTRUM_N), set(pw.SPECTRUM_N) - s["sizes_with_a_row"]
+    # 9. a meter is set while one is present, reset with rows stored, and a spectrum meter is replaced by one of another size, whose rows
+    # a master fill then completes: the state's copies are reserved anew (s2r_post_keep.h: S2rMirror)
+    assert all(s["replaced"].values()) and all(s["reset_with_rows"].values()), (s["replaced"], s["reset_with_rows"])
+    assert s["replaced_and_compared"]
+    # 10. the limiter and both meters in one master fill; a meter in a master fill without stems
+    assert s["limiter_and_both"] and s["without_stems"] == {"loudness", "spectrum"}
+    # 11. each meter goes through a round trip and a handover in the middle of a hop with rows stored
+    assert all(s["roundtrips"].values()) and all(s["handovers"].values()), (s["roundtrips"], s["handovers"])
+    # 12. each meter in a call of more than 1024 frames; a call that completes more rows than the window keeps; a call shorter than the
+    # hop that completes none
+    assert all(s["big"].values()), s["big"]
+    assert s["overflow"] and s["short"]
+    # 13. a meter that has run sits through a bus fill and a panned fill before the next master fill
+    assert s["sat_through_both"]
+    # 14. one loudness meter at hop 17 runs at least 17 full blocks of eight frames, and starts one eight frames before the hop's end
+    assert s["blocks_at_17"] >= 17 and BLOCK in s["met_at_17"], (s["blocks_at_17"], sorted(s["met_at_17"]))
+    # 15. both orders of read and fill: a master fill directly behind a master fill — the state's device copies flip —, and one
+    # directly behind a read of the state, which fetched it: the fill uploads it again.  Behind a round trip and behind a fill that
+    # test_gpu_post_fuzz.py reads the state after (post_walk.peeks)
+    assert s["fill_behind_fill"] and s["fill_behind_read"] >= {"roundtrip", "bus"}, s["fill_behind_read"]
+    # 16. three refused fills with a meter on
+    assert s["refused_with_a_meter"] >= 3
+
+
 def test_the_subset_walk_makes_96_calls_over_the_32_subsets():
     setup, steps = pw.subset_walk()
     on, seen, calls = {st: set() for st in INSERTS}, [], 0
@@ -172,7 +335,7 @@ def run_on_the_model(setup, steps, seed):
     chain, rng, out = Chain(), np.random.RandomState(seed ^ 0x5EED), []
     for k, a in enumerate(steps):
         if a["kind"] == "handover":
-            chain.lim_meters = None                              # what post_walk.handover leaves of it on the model
+            chain.handed_over()                                  # what post_walk.handover leaves on the model
         elif a["kind"] != "fill":
             chain.apply(a)
         else:
@@ -191,6 +354,20 @@ def _check_model_run(chain, fills, what):
                     assert float(np.abs(e[name]).max()) <= limit, "%s, step %d %r: %s reaches %g" % (what, k, a, name, float(np.abs(e[name]).max()))
         for st, bus, changed, excused in e["trace"]:
             assert changed or excused, "%s, step %d %r: the %s on bus %d changes no bit of its input" % (what, k, a, st, bus)
+        for name in ("loudness rows", "true peak", "true peak held", "spectrum rows"):
+            if name in e:
+                assert np.isfinite(e[name]).all(), "%s, step %d %r: the %s are not finite" % (what, k, a, name)
+    # a meter that reads silence throughout tests nothing: of every meter, from the set or reset that started it, every programme that
+    # sounded (above 2^-10) in the frames a completed row is taken over has a row entry above 0.0
+    sounded, positive = {}, {}
+    for k, a, e in fills:
+        for m in e.get("meters", ()):
+            key = (m["name"],) + m["instance"]
+            sounded.setdefault(key, set()).update(m["sounding"])
+            positive.setdefault(key, set()).update(m["positive"])
+    for key, programmes in sounded.items():
+        assert programmes <= positive[key], "%s: the %s meter (the %dth to start) reads silence on programmes %s" % (
+            what, key[0], key[1], sorted(programmes - positive[key]))
     for name, v in chain.states().items():
         assert np.isfinite(v).all(), "%s: the state of %s" % (what, name)
 
@@ -212,6 +389,12 @@ def test_the_model_alone_is_well_behaved_over_the_subset_walk():
     assert any(len(e["trace"]) == 12 for _, _, e in fills)       # all five inserts on two buses each, the chorus and the reverb
     assert chain.recursion[1] == 2 * 48 * 33 and chain.recursion[0] >= chain.recursion[1] / 10.0, chain.recursion
     assert all((e["gain"] < 1.0).any() for _, a, e in fills if a["fill"] == "master")
+    # both meters from the start to the end: 64 master fills of 33 frames are 2112 frames, 124 hops of 17 and 16 of 128
+    metered = [e for _, a, e in fills if a["fill"] != "bus"]
+    assert len(metered) == 64 and all([m["name"] for m in e["meters"]] == ["loudness", "spectrum"] for e in metered)
+    assert chain.loud.made == 2112 // 17 and chain.spec.made == 2112 // 128 and (chain.loud.pos, chain.spec.pos) == (2112 % 17, 2112 % 128)
+    assert all(e["loudness hops"] == min(32, (33 * (i + 1)) // 17) for i, e in enumerate(metered))
+    assert (chain.loud.rows[:, :6] > 0.0).all() and (chain.loud.rows[:, 16:] > 0.0).all() and (chain.spec.rows[:, [0, 1, 2, 8]] > 0.0).any(axis=2).all()
 
 
 def test_the_flangers_recursion_shows_over_the_default_walks():

@@ -17,6 +17,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEVIATION = os.path.join(ROOT, "profiles", "truth", "spectrum_deviation.json")
 
 
+SIZES = (256, 512, 1024, 2048, 4096, 8192)                       # every size the meter takes: log2 N of 8 .. 13, each its own split into passes on the device
+
+
 def bits(x):
     return np.ascontiguousarray(x, dtype=F).view(np.uint32)
 
@@ -106,7 +109,7 @@ def run_reference(n, hop, window, stems, master, cuts):
     return np.concatenate(rows), state, pos
 
 
-@pytest.mark.parametrize("n", [256, 512, 2048, 8192])
+@pytest.mark.parametrize("n", SIZES)
 def test_twiddles(n):
     t = s2.spectrum_twiddles(n)
     assert t.shape == (n // 2, 2) and t.dtype == F
@@ -141,7 +144,7 @@ def test_windows(n):
     same_bits(s2.spectrum_window(s2.WINDOW_HANN, n), s2.spectrum_window("hann", n), "kinds by number")
 
 
-CASES = [(n, hop) for n in (256, 512, 2048, 8192) for hop in (n // 8, n // 2, n, n + 37)]
+CASES = [(n, hop) for n in SIZES for hop in (n // 8, n // 2, n, n + 37)]
 
 
 @pytest.mark.parametrize("n,hop", CASES)
