@@ -26,9 +26,13 @@ SOURCES = ["s2r_render_onepole_square.hip", "s2r_render_onepole_saw.hip", "s2r_r
            "s2r_drive.hip",     # (likewise, since the drive came)
            "s2r_flanger.hip",   # (likewise, since the flanger came)
            "s2r_loudness.hip",  # (likewise, since the loudness meters came)
-           "s2r_spectrum.hip"]  # (last, likewise, since the spectrum meters came)
+           "s2r_spectrum.hip",  # (likewise, since the spectrum meters came)
+           "s2r_mixer.cpp",     # (likewise, since the voice mixer got a type of its own: host code only, no kernel)
+           "s2r_host_mix.cpp",  # (likewise, since the host file was split: host code only, no kernel)
+           "s2r_host_post.cpp"] # (last, likewise)
 HEADERS = ["s2r_device.h", "s2r_math.h", "s2r_patch.h", "s2r_voices.h", "s2r_kern_common.h", "s2r_render_onepole.inc",
-           "s2r_render_general.inc", "s2r_post.h", "s2r_post_route.h", "s2r_post_keep.h", "s2r_rules.h"]
+           "s2r_render_general.inc", "s2r_post.h", "s2r_post_route.h", "s2r_post_keep.h", "s2r_rules.h", "s2r_handle.h", "s2r_mixer.h",
+           "s2r_mixer_keep.h"]
 
 # -amdgpu-sched-strategy=max-ilp: the render kernels run one wavefront per SIMD (64 k voices =
 # 1024 waves), so nothing hides a dependent instruction's latency except independent work of the

@@ -1,5 +1,6 @@
-// s2r_host.cpp — the C ABI of libs2r (include/s2r.h): handle, device memory, voice pool,
-// event folding, launches.  Compiled with hipcc, -ffp-contract=off.
+// s2r_host.cpp — the C ABI of libs2r (include/s2r.h): handle (s2r_handle.h), device memory, voice pool,
+// event folding, launches.  The panned, bus and master fills with the voice mixer's entries are s2r_host_mix.cpp, the entries
+// in front of the post-mix chain s2r_host_post.cpp.  Compiled with hipcc, -ffp-contract=off.
 //
 // Reference boundary being replaced: s2_lib::try3::synth::Synth
 // (/root/reference/components/s2_lib/src/try3/synth.rs:9-203).
@@ -12,13 +13,13 @@
 #include <cstring>
 #include <ctime>
 #include <atomic>
-#include <functional>
 #include <memory>
 #include <new>
 #include <string>
 #include <vector>
 
 #include "s2r.h"
+#include "s2r_handle.h"
 #include "s2r_device.h"
 #include "s2r_math.h"
 #include "s2r_patch.h"
@@ -26,9 +27,10 @@
 #include "s2r_rules.h"
 #include "s2r_voices.h"
 
+using namespace s2r_host;
+
 namespace {
 
-constexpr int kEventSlots = 4;
 constexpr size_t kVoiceWords = S2R_VOICE_WORDS;    // 32-bit words of per-voice state (S2rVoiceArrays)
 
 // components/s2_bin/src/tables.rs:6-10 regenerated; see oracle/s2_oracle.c for the note on
@@ -112,27 +114,10 @@ bool fast_div_rate(uint32_t sr) {
     return false;
 }
 
-struct EventSlot {
-    S2rVoiceEvent *host = nullptr;   // pinned
-    S2rVoiceEvent *dev = nullptr;
-    S2rTimedEvent *thost = nullptr;  // pinned, mapped: timed events of one fill
-    S2rTimedEvent *tdev = nullptr;
-    // Who still reads the slot's pinned records: nobody (0); the kernels in front of `done`, a HIP event recorded behind
-    // them (1); or a fill whose completion word — index `idx`, value `seq` — the host can look at (2).  An event record
-    // between two kernels of a stream costs the GPU ~3 us of idle time at that boundary (measured, tools/gpu_timeline.py:
-    // boundaries of 4.5-5.0 us with the records, 1.7-2.4 without), so the fills that are tracked by a completion word
-    // record none.
-    hipEvent_t done = nullptr;
-    int state = 0;
-    volatile uint32_t *word = nullptr;   // state 2: the completion word (host view) ...
-    uint32_t seq = 0;                    // ... and the value it shows once the fill is done
-};
 
 // mapped host memory the host polls, or reads behind a flag the device sets: coherent (fine-grained) whatever the
 // runtime's default or HIP_HOST_COHERENT say, and visible to every device of a device list
 constexpr unsigned kHostPolled = hipHostMallocMapped | hipHostMallocCoherent | hipHostMallocPortable;
-constexpr unsigned kGainsPan = 1u, kGainsBus = 2u, kGainsAll = 3u;   // s2r_synth::gains_dirty: the panned fill's device arrays, the bus fill's
-constexpr uint32_t kMixPan = 1u, kMixLevel = 2u, kMixFader = 4u, kMixSend = 8u;   // s2r_synth::Mixer::used
 
 }  // namespace
 
@@ -146,200 +131,12 @@ static std::atomic<int> g_two_stream_handles[64];
 // a workgroup's partial row starts on a 16-byte boundary (combine_groups stores four frames at a time)
 static inline uint32_t partials_stride(uint32_t max_frames) { return (max_frames + 3u) & ~3u; }
 
-struct s2r_synth {
-    s2r_config cfg{};
-    int device = 0;
-    uint32_t shard_begin = 0, shard_voices = 0, padded_voices = 0, block_voices = 256, n_blocks = 0, mix_groups = 1;
-    uint32_t interleave = 0, shard_index = 0, shard_count = 1;   // round-robin sharding (s2r_config.shard_interleave)
-    FastDiv div_interleave, div_count, div_per_kid;              // ... and its divisions (interleave, shard count, voices per contiguous shard)
-    std::vector<s2r_patch> bank;                 // bank[0] is "the" patch of the reference's Synth
-    uint32_t program = 0;                        // current program: the patch the next note_on gives its voice
-    S2rBankEntry *bank_dev = nullptr;            // S2R_MAX_BANK entries, resolved for bank_rate
-    bool bank_dirty = true; uint32_t bank_rate = 0;
-    std::shared_ptr<S2rVoicePool> pool;          // one per Synth: the shards of a device-list handle share their parent's
-    // Device list (s2r_config.n_devices > 1): this handle is the PARENT — it owns the pool, runs the allocation policy
-    // once per event and routes the event to the shard (`kids[k]`, an ordinary single-device handle on devices[k])
-    // that holds the voice; per fill every shard writes its partial mix into row k of `rows_dev` on the parent's
-    // device (peer-to-peer where the devices differ) and the parent adds the rows in shard order rooted at +0.0.
-    s2r_synth *parent = nullptr;
-    std::vector<s2r_synth *> kids;
-    float *rows_dev[2] = {nullptr, nullptr};     // [n kids][max_frames], one per fill in flight
-    std::vector<float *> kid_stage;              // per kid: a row on ITS device when it cannot write the parent's rows directly
-    std::vector<hipEvent_t> kid_done[2];         // per slot, per kid: its partial row is in rows_dev[slot]
-    uint32_t rows_slot = 0;
-    std::vector<uint32_t> seed_override;         // per pool voice; 0 = reference behaviour
-    // event folding (one record per touched shard voice between two fills)
-    std::vector<S2rVoiceEvent> pending;
-    std::vector<int32_t> pending_slot;           // shard-local voice -> index in pending, -1
-    EventSlot slots[kEventSlots];
-    int next_slot = 0;
-    // timed events (take effect inside the next fill at a 16-frame boundary)
-    std::vector<S2rTimedEvent> tpending;
-    std::vector<int32_t> tlast;                  // shard-local voice -> its last timed event this fill, -1
-    std::vector<int32_t> tfirst;                 // scratch of flush_events: shard-local voice -> its first timed event, -1
-    uint32_t fill_time = 0;                      // frames of the next fill the pool clock has already moved
-    uint32_t tev_capacity = 0;
-    int32_t *voice_ev_head = nullptr;
-    S2rTimedEvent *tev_copy = nullptr;           // the fill's timed events in HBM (copied from the mapped slot by the heads kernel)
-    // device
-    hipStream_t stream = nullptr;
-    S2rVoiceArrays v{};
-    void *voice_mem = nullptr;
-    float *block_partials = nullptr;
-    float *out_dev = nullptr;
-    float *out_host = nullptr;                   // pinned and device-mapped, 2*max_frames
-    float *out_host_dev = nullptr;               // the device's view of out_host
-    // Completion words (S2rDone): mapped host memory the last kernel of a fill writes its sequence number to — [0], [1]
-    // the two ring slots of s2r_fill_begin / s2r_fill_end, [2] the synchronous fills — and the arrival counter in HBM
-    uint32_t *done_host = nullptr, *done_dev = nullptr, *done_counter = nullptr;
-    uint32_t done_seq = 0;                       // last value handed out
-    uint32_t ring_seq[2] = {0, 0};               // what done_host[slot] must show before s2r_fill_end copies slot's buffer (0: wait on the event)
-    // s2r_fill_begin / s2r_fill_end: two more mapped output buffers, the fills in flight (oldest first)
-    float *ring_host[2] = {nullptr, nullptr}, *ring_dev[2] = {nullptr, nullptr};
-    hipEvent_t ring_done[2] = {nullptr, nullptr};
-    size_t ring_frames[2] = {0, 0};
-    uint32_t ring_head = 0, ring_count = 0;
-    // s2r_fill_begin leaves its fill's mix to the NEXT s2r_fill_begin, which launches it together with its own chain
-    // heads (s2r_mix_and_heads_kernel: one launch boundary less per buffer), or to s2r_fill_end, whichever comes first
-    struct DeferredMix { bool active = false; bool overlap = false; S2rMixParams m{}; int ring_slot = -1; } dmix;
-    // Two streams for the fills of s2r_fill_begin (S2rOverlapWords, s2r_device.h): the mixes and the chain heads run on
-    // stream_b beside the render kernels on `stream`; [1] of each pair is the second buffer (by the fill's parity)
-    hipStream_t stream_b = nullptr;
-    bool ov_enabled = false;                     // stream_b and the second buffers exist (S2R_OVERLAP=0 leaves them out)
-    bool ov_registered = false;                  // ... and this handle holds its device's two-stream slot (g_two_stream_handles)
-    bool ov_busy = false;                        // kernels of an overlapped fill may still be running on stream_b
-    float *partials2[2] = {nullptr, nullptr};
-    int32_t *heads2[2] = {nullptr, nullptr};
-    S2rTimedEvent *tevcopy2[2] = {nullptr, nullptr};
-    S2rOverlapWords *ov_words = nullptr;         // device memory
-    uint32_t ov_render_target[2] = {0, 0}, ov_heads_target[2] = {0, 0};
-    uint32_t ov_fill = 0;                        // overlapped fills begun so far: the next one's parity is its low bit
-    // One launch per fill (S2rMixTail, s2r_device.h): the render kernel builds its own chain heads from the fill's records grouped
-    // by workgroup and the last workgroups to finish add the rows up.  S2R_FUSED=0: the three-launch form (heads, render, mix)
-    int fused_mode = 1;                          // 0 never; 1 everything but the two-stream fills of s2r_fill_begin; 2 those too
-    uint32_t *fz_arrive = nullptr;               // device memory [2]: rows written, by parity (launches per fill use [0])
-    uint32_t fz_target[2] = {0, 0};
-    FastDiv div_block;                           // local voice -> workgroup
-    std::vector<S2rTimedEvent> tsorted;          // the fill's records grouped by workgroup ...
-    std::vector<uint32_t> tperm, tbounds;        // ... arrival index -> grouped index; workgroup b's records are [tbounds[b], tbounds[b + 1])
-    // exchange of partial rows between the shards of a device list: a counter per rows slot in the parent's device memory
-    uint32_t *rows_done = nullptr;
-    uint32_t rows_target[2] = {0, 0};
-    // exchange between PROCESSES (one process per GPU; s2r_exchange_create / _attach): the ranks' rows and the counters live in
-    // one block of the root's device memory that the other ranks map through an IPC handle
-    bool xg_on = false;
-    uint32_t xg_rank = 0, xg_n = 0, xg_target[2] = {0, 0};
-    float *xg_rows = nullptr;                    // [2][xg_n][max_frames]
-    uint32_t *xg_done = nullptr;                 // [2] counters behind the rows, then [2] words `consumed` (the root's: fused_tail)
-    void *xg_block = nullptr; bool xg_owner = false;
-    bool force_stage = false, force_peer = false;   // S2R_FORCE_STAGE / S2R_FORCE_PEER: the multi-device branches on one device (tests)
-    // The pool-resident render kernel (S2rPool, s2r_device.h; s2r_set_resident): running on `stream` between fills while
-    // pool_running; stopped by every entry point that touches the device or what the kernel's arguments were built from
-    bool resident = false, pool_running = false;
-    uint32_t pool_seq = 0, pool_launch_id = 0, pool_rate = 0, pool_fills = 0;
-    uint32_t *pool_cmd = nullptr, *pool_cmd_dev = nullptr; bool pool_cmd_vram = false;
-    uint32_t *pool_slices = nullptr, *pool_slices_dev = nullptr;   // mapped host memory [S2R_POOL_CMD_SLOTS][n_blocks + 1]
-    uint32_t *pool_host = nullptr, *pool_host_dev = nullptr;       // mapped host memory: [0] the kernel's "exited" word
-    uint32_t *pool_decided = nullptr;                              // device memory
-    bool pool_gran_pending = false;                                // the fill just posted comes back as granules (fill_host reads them)
-    EventSlot *pool_gran_slot = nullptr;                           // ... and this event slot's records are free again once it has
-    volatile uint32_t *pool_staged = nullptr; uint32_t pool_staged_seq = 0;   // a command whose payload is written and whose sequence words
-                                                                   // the caller (a device list's parent) writes with its other shards'
-    uint32_t pool_idle_ticks = 200000u;                            // 2 ms without a command
-    int n_cu = 0;
-    float *os_buf = nullptr, *os_taps = nullptr; // 4x oversampling: [62 history + max_frames] mix at 4x rate, 63 taps
-    float *sin_dev = nullptr;
-    float *noise_dev = nullptr;                  // the noise table (S2rRenderParams.noise_tab), 65 536 floats
-    float *per_voice_dev = nullptr; size_t per_voice_cap = 0;
-    // coefficient tables of the patch (S2rTabRef): rebuilt on the device when the patch or the sample
-    // rate changes
-    float *tab_dev = nullptr; size_t tab_cap = 0;        // floats
-    S2rTabRef tab{};
-    bool tab_dirty = true; uint32_t tab_rate = 0;
-    float *bank_tab_dev = nullptr; size_t bank_tab_cap = 0;      // the patch bank's coefficient tables (floats)
-    unsigned long long *stamps_dev = nullptr;            // diagnostic builds (-DS2R_STAMPS): per-wave phase stamps of the last fill
-    unsigned long long *timeline_dev = nullptr; uint32_t timeline_n = 0, timeline_cap = 0;   // ... and the launches' timeline
-    bool use_tab = true, use_arg_events = true;
-    // s2r_set_low_latency: the resident kernel (S2rResident, s2r_device.h) — running on `stream` between fills while
-    // res_running; every entry point that touches the device or what the kernel's arguments were built from stops it first
-    bool low_latency = false, res_running = false, res_stereo = false;
-    uint32_t res_rate = 0, res_seq = 0, res_launch_id = 0;
-    uint32_t *res_host = nullptr, *res_dev = nullptr;    // mapped host memory: [32] the kernel's "exited" word, and, where the CPU cannot
-                                                         // write device memory, [0 .. 31] the command
-    unsigned long long *res_gran = nullptr, *res_gran_dev = nullptr;   // mapped: the granules of fills of up to S2R_RES_GRANULE_FRAMES frames
-    uint32_t *res_cmd = nullptr;                         // the command as the CPU writes it: res_host, or 32 words of fine-grained
-    uint32_t *res_cmd_dev = nullptr;                     // DEVICE memory (large BAR) that the kernel polls without crossing the link
-    bool res_cmd_vram = false;
-    // The voice mixer (s2r_fill_panned, s2r_fill_buses): what a program gives the voices started under it,
-    // beside the bank — the defaults are a handle that never heard of the mixer.
-    struct ProgramMix {
-        float pan = 0.0f, spread = 0.0f;                         // s2r_set_program_pan
-        float level = 1.0f, sens = 0.0f; uint8_t bus = 0;        // s2r_set_program_mix
-        float send = 0.0f; uint8_t send_bus = 0;                 // s2r_set_program_send
-        // s2r_set_program_fader: the pair the caller last set — the target — and the pair the last bus fill left — the applied
-        // one; a bus fill ramps every voice's gains from the one to the other
-        float fader = 1.0f, shift = 0.0f, fader_app = 1.0f, shift_app = 0.0f;
-        bool moving() const { return fader != fader_app || shift != shift_app; }
-    };
-    // ... and what every shard voice got at its note_on (local order).  One bit of `used` per attribute — pan, level (gain and
-    // bus), fader (the program the voice was started with: a voice follows that program's fader) and send (send and send bus) —
-    // set by the first call that leaves the attribute's default (mixer_begin); an attribute's arrays exist from then on, and
-    // until then every voice has its default (pan 0, gain 1 on bus 0, send 0 to bus 0), nothing of it is staged or launched, and
-    // with used == 0 the note_on paths pay one test.
-    struct Mixer {
-        uint32_t used = 0;                                       // kMixPan | kMixLevel | kMixFader | kMixSend
-        std::vector<ProgramMix> prog;                            // one entry per bank patch
-        std::vector<float> pan, gain, send;                      // [shard_voices] each, once its bit is set
-        std::vector<uint8_t> bus, send_bus, program;
-        // a note_on at a frame INSIDE the next fill: what it gives its voice takes effect there (`mask`: the attributes in use
-        // when it came; the other fields hold nothing)
-        struct Record { uint32_t local, frame, mask; float pan, gain, send; uint8_t bus, send_bus, program; };
-        std::vector<Record> timed;                               // in non-decreasing frame order, event order within a frame
-        // the only place that writes the voices' arrays from a record
-        void apply(const Record &r) {
-            if (r.mask & kMixPan) pan[r.local] = r.pan;
-            if (r.mask & kMixLevel) { gain[r.local] = r.gain; bus[r.local] = r.bus; }
-            if (r.mask & kMixFader) program[r.local] = r.program;
-            if (r.mask & kMixSend) { send[r.local] = r.send; send_bus[r.local] = r.send_bus; }
-        }
-    } mixer;
-    unsigned gains_dirty = kGainsAll;            // the voices' arrays changed since the gains were last sent to the device: kGainsPan | kGainsBus
-    float *gains_host = nullptr, *gains_dev = nullptr;   // the panned fill's [2][padded_voices]: gL then gR (pinned / device); entries past the shard hold 0
-    hipEvent_t gains_sent = nullptr;             // behind the last copy out of gains_host
-    float *pan_rows = nullptr;                   // [shard_voices][pan_slice]: the voices' rows of one slice (allocated by the first panned or bus fill)
-    uint32_t pan_slice = 0;                      // frames per slice, a multiple of 16
-    float *pan_partials = nullptr;               // [n_blocks][2][pan_slice]
-    std::vector<hipEvent_t> pan_ev;              // s2r_set_timing: a pair of events around every slice's mixdown of the last panned or bus fill
-    size_t pan_ev_used = 0;
-    float pan_mix_ms = -1.0f;                    // ... and their sum (tools/pan_time.py reads it through s2r_debug_pan_mix_ms)
-    char *bus_gains_host = nullptr, *bus_gains_dev = nullptr;    // the bus fill's staging buffer (BusLayout)
-    hipEvent_t bus_gains_sent = nullptr;
-    float *bus_partials = nullptr;               // [n_blocks][S2R_MAX_BUSES][2][pan_slice], allocated by the first bus fill
-    float *bus_out = nullptr, *bus_out_dev = nullptr;            // pinned and device-mapped: S2R_MAX_BUSES * 2 * max_frames floats
-    float bus_mix_ms = -1.0f;                    // pan_mix_ms of the last s2r_fill_buses (tools/bus_time.py)
-    bool bus_dev_ramped = false;                 // what bus_gains_dev holds was sent for a ramped fill: (G0, step), not the static gains
-    // What runs behind the bus mixdown (s2r_post.h): the eight bus stages, the master section and the master limiter
-    S2rPostChain post;
-    float pitch_table[256];
-    hipEvent_t t0 = nullptr, t1 = nullptr;
-    bool timing = false, timed = false, no_flat_shortcut = false;
-    uint64_t double_release = 0;
-    bool uniform_window = true;                  // s2r_set_uniform_window
-    uint32_t *uw_count_dev = nullptr;            // chunks rendered through the uniform window (S2rRenderParams.uw_count), one word
-    s2r_voice_log_fn voice_log = nullptr;    // synth.rs:118's log::debug!, as a callback
-    void *voice_log_user = nullptr;
-    // A kernel that gave up a bounded wait for another kernel's (or workgroup's) work left the fill unrendered — it touches
-    // neither the voices' state nor the chain heads then — while the host's pool clock and event bookkeeping had moved on:
-    // the handle says so from then on instead of rendering something else than what its caller believes (import a checkpoint
-    // into a new handle to go on).
-    bool broken = false;
-    std::string err = "";
-};
-
-
 namespace {
+int resident_stop(s2r_synth *s);
+int pool_stop(s2r_synth *s);
+}  // namespace
 
-int set_err(s2r_synth *s, int code, const char *fmt, ...) {
+int s2r_host::set_err(s2r_synth *s, int code, const char *fmt, ...) {
     if (s) {
         char buf[512];
         va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
@@ -348,18 +145,66 @@ int set_err(s2r_synth *s, int code, const char *fmt, ...) {
     return code;
 }
 
-// every entry point that touches the device, or anything a running resident kernel's arguments were built from, first
-#define S2R_TRY(call) do { const int rc_t_ = (call); if (rc_t_ != S2R_OK) return rc_t_; } while (0)     // any step that returns a status
-#define S2R_QUIESCE(s) S2R_TRY(quiesce(s))
-int resident_stop(s2r_synth *s);
-int pool_stop(s2r_synth *s);
-int quiesce(s2r_synth *s) { int rc = resident_stop(s); return rc != S2R_OK ? rc : pool_stop(s); }
+int s2r_host::quiesce(s2r_synth *s) { int rc = resident_stop(s); return rc != S2R_OK ? rc : pool_stop(s); }
 
-#define S2R_HIP(s, call)                                                                              \
-    do {                                                                                              \
-        hipError_t e_ = (call);                                                                       \
-        if (e_ != hipSuccess) return set_err((s), S2R_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); \
-    } while (0)
+// one more event into the folded record of shard voice `local` (one record per touched voice between two fills)
+void s2r_host::fold_event(s2r_synth *s, uint32_t local, uint32_t flags, float pitch, uint32_t seed, uint32_t program) {
+    int32_t slot = s->pending_slot[local];
+    if (slot < 0) {
+        slot = (int32_t)s->pending.size();
+        s->pending_slot[local] = slot;
+        s->pending.push_back(S2rVoiceEvent{local, 0u, 0.0f, 0u});
+    }
+    S2rVoiceEvent &e = s->pending[(size_t)slot];
+    if (flags & S2R_EV_RESTART) { e.flags = S2R_EV_RESTART | (program << S2R_EV_PROGRAM_SHIFT); e.pitch = pitch; e.seed = seed; }     // wipes an earlier release
+    if (flags & S2R_EV_RELEASE) e.flags |= S2R_EV_RELEASE;
+}
+
+// The other way round, for the entry points that take no chains (per-voice rows, checkpoints, seeds): while no event has a frame
+// inside the fill (fill_time == 0: every record waiting is a frame-0 one) the records are folded back, in their order, behind
+// whatever was folded before them.
+void s2r_host::fold_frame0_records(s2r_synth *top) {
+    for (s2r_synth *kid : top->kids) fold_frame0_records(kid);
+    s2r_synth *root = top->parent ? top->parent : top;
+    if (top->tpending.empty() || root->fill_time != 0) return;
+    for (const S2rTimedEvent &te : top->tpending) fold_event(top, te.voice, te.flags, te.pitch, te.seed, te.program);
+    for (const S2rTimedEvent &te : top->tpending) top->tlast[te.voice] = -1;
+    top->tpending.clear();
+}
+
+int s2r_host::check_fill(s2r_synth *s, size_t frames, uint32_t sample_rate) {
+    if (!s) return S2R_ERR_INVALID;
+    S2R_REFUSE_BROKEN(s);
+    if (frames > s->cfg.max_frames) return set_err(s, S2R_ERR_TOO_MANY_FRAMES, "frames %zu > max_frames %u", frames, s->cfg.max_frames);
+    if (sample_rate == 0) return set_err(s, S2R_ERR_INVALID, "sample_rate_hz must be > 0");
+    // process.rs:36,71: offset.checked_add(..).expect("overflow") — the reference panics once a
+    // voice's offset would pass u32::MAX; report it instead of rendering garbage.
+    if (s->fill_time && s->fill_time >= frames)
+        return set_err(s, S2R_ERR_INVALID, "a timed event at frame %u does not fall inside this %zu-frame fill", s->fill_time, frames);
+    if (s->pool->oldest_offset() + (frames - s->fill_time) > 0xffffffffull)
+        return set_err(s, S2R_ERR_OFFSET_OVERFLOW, "a voice's frame offset would overflow u32 (the reference panics here)");
+    for (size_t k = 0; k < s->bank.size(); k++) {
+        const s2r_patch &pt = s->bank[k];
+        if (pt.lpf_kind == S2R_FILT_ONEPOLE) continue;
+        // dsp_filters.rs evaluates sin/cos of theta = 2 pi f / sr.  The device restatement of the libm
+        // routines is exact for every finite argument; only an overflowing 2 pi f (inf -> NaN, whose
+        // sign bit differs between x86 and the GPU) is refused.
+        const double amt = pt.mod_env_to_lpf_freq > 0.0f ? (double)pt.mod_env_to_lpf_freq : 0.0;
+        const double num_max = 2.0 * 3.14159265358979323846 * (double)pt.lpf_freq * std::exp2(amt) * 1.000001;
+        if (!(num_max < 3.4028234e38))
+            return set_err(s, S2R_ERR_PATCH_RANGE, "patch %zu, lpf.kind %d: 2 pi * lpf.freq * 2^mod_env_to_lpf_freq overflows f32",
+                           k, pt.lpf_kind);
+        // dsp_filters.rs:205-207: tan(theta / (2 Q)); Q = 0 makes that tan(inf) = NaN (same sign caveat)
+        if (pt.lpf_kind == S2R_FILT_BP2 &&
+            !(pt.lpf_q > 0.0f && num_max / (double)sample_rate / (2.0 * (double)pt.lpf_q) < 3.4028234e38))
+            return set_err(s, S2R_ERR_PATCH_RANGE, "patch %zu: lpf.kind bp2 needs lpf.q > 0 (tan(theta / (2 q)) must stay finite)", k);
+        if (pt.lpf_kind >= S2R_FILT_SVF_LP && !(pt.lpf_q >= 0x1p-100f))
+            return set_err(s, S2R_ERR_PATCH_RANGE, "patch %zu: the state-variable filter needs lpf.q > 0 (k = 1 / q)", k);
+    }
+    return S2R_OK;
+}
+
+namespace {
 
 // pool index -> this handle's local voice index, or -1 when another handle renders it
 inline int64_t to_local(const s2r_synth *s, uint32_t pool_index) {
@@ -391,19 +236,6 @@ inline s2r_synth *shard_of(s2r_synth *s, uint32_t pool_index, uint32_t *local) {
     return s;
 }
 
-// one more event into the folded record of shard voice `local` (one record per touched voice between two fills)
-void fold_event(s2r_synth *s, uint32_t local, uint32_t flags, float pitch, uint32_t seed, uint32_t program) {
-    int32_t slot = s->pending_slot[local];
-    if (slot < 0) {
-        slot = (int32_t)s->pending.size();
-        s->pending_slot[local] = slot;
-        s->pending.push_back(S2rVoiceEvent{local, 0u, 0.0f, 0u});
-    }
-    S2rVoiceEvent &e = s->pending[(size_t)slot];
-    if (flags & S2R_EV_RESTART) { e.flags = S2R_EV_RESTART | (program << S2R_EV_PROGRAM_SHIFT); e.pitch = pitch; e.seed = seed; }     // wipes an earlier release
-    if (flags & S2R_EV_RELEASE) e.flags |= S2R_EV_RELEASE;
-}
-
 void push_event(s2r_synth *top, uint32_t pool_index, uint32_t flags, float pitch, uint32_t seed, uint32_t program = 0) {
     uint32_t local = 0;
     if (s2r_synth *s = shard_of(top, pool_index, &local)) fold_event(s, local, flags, pitch, seed, program);
@@ -423,18 +255,6 @@ bool append_frame0_record(s2r_synth *top, uint32_t pool_index, uint32_t flags, f
     sh->tlast[local] = idx;
     sh->tpending.push_back(te);
     return true;
-}
-
-// The other way round, for the entry points that take no chains (per-voice rows, checkpoints, seeds): while no event has a frame
-// inside the fill (fill_time == 0: every record waiting is a frame-0 one) the records are folded back, in their order, behind
-// whatever was folded before them.
-void fold_frame0_records(s2r_synth *top) {
-    for (s2r_synth *kid : top->kids) fold_frame0_records(kid);
-    s2r_synth *root = top->parent ? top->parent : top;
-    if (top->tpending.empty() || root->fill_time != 0) return;
-    for (const S2rTimedEvent &te : top->tpending) fold_event(top, te.voice, te.flags, te.pitch, te.seed, te.program);
-    for (const S2rTimedEvent &te : top->tpending) top->tlast[te.voice] = -1;
-    top->tpending.clear();
 }
 
 // upload the folded events and apply them on `stream`; publish the timed ones.  Returns the slot
@@ -588,40 +408,6 @@ int flush_events(s2r_synth *s, hipStream_t stream, EventSlot **timed_slot, const
     }
     for (const S2rVoiceEvent &e : s->pending) s->pending_slot[e.voice] = -1;
     s->pending.clear();
-    return S2R_OK;
-}
-
-#define S2R_REFUSE_BROKEN(s) do { if ((s)->broken) return set_err((s), S2R_ERR_HIP, "an earlier fill failed on the device (a bounded wait between kernels ran out): the device's voices no longer match the host's bookkeeping; destroy the handle"); } while (0)
-
-int check_fill(s2r_synth *s, size_t frames, uint32_t sample_rate) {
-    if (!s) return S2R_ERR_INVALID;
-    S2R_REFUSE_BROKEN(s);
-    if (frames > s->cfg.max_frames) return set_err(s, S2R_ERR_TOO_MANY_FRAMES, "frames %zu > max_frames %u", frames, s->cfg.max_frames);
-    if (sample_rate == 0) return set_err(s, S2R_ERR_INVALID, "sample_rate_hz must be > 0");
-    // process.rs:36,71: offset.checked_add(..).expect("overflow") — the reference panics once a
-    // voice's offset would pass u32::MAX; report it instead of rendering garbage.
-    if (s->fill_time && s->fill_time >= frames)
-        return set_err(s, S2R_ERR_INVALID, "a timed event at frame %u does not fall inside this %zu-frame fill", s->fill_time, frames);
-    if (s->pool->oldest_offset() + (frames - s->fill_time) > 0xffffffffull)
-        return set_err(s, S2R_ERR_OFFSET_OVERFLOW, "a voice's frame offset would overflow u32 (the reference panics here)");
-    for (size_t k = 0; k < s->bank.size(); k++) {
-        const s2r_patch &pt = s->bank[k];
-        if (pt.lpf_kind == S2R_FILT_ONEPOLE) continue;
-        // dsp_filters.rs evaluates sin/cos of theta = 2 pi f / sr.  The device restatement of the libm
-        // routines is exact for every finite argument; only an overflowing 2 pi f (inf -> NaN, whose
-        // sign bit differs between x86 and the GPU) is refused.
-        const double amt = pt.mod_env_to_lpf_freq > 0.0f ? (double)pt.mod_env_to_lpf_freq : 0.0;
-        const double num_max = 2.0 * 3.14159265358979323846 * (double)pt.lpf_freq * std::exp2(amt) * 1.000001;
-        if (!(num_max < 3.4028234e38))
-            return set_err(s, S2R_ERR_PATCH_RANGE, "patch %zu, lpf.kind %d: 2 pi * lpf.freq * 2^mod_env_to_lpf_freq overflows f32",
-                           k, pt.lpf_kind);
-        // dsp_filters.rs:205-207: tan(theta / (2 Q)); Q = 0 makes that tan(inf) = NaN (same sign caveat)
-        if (pt.lpf_kind == S2R_FILT_BP2 &&
-            !(pt.lpf_q > 0.0f && num_max / (double)sample_rate / (2.0 * (double)pt.lpf_q) < 3.4028234e38))
-            return set_err(s, S2R_ERR_PATCH_RANGE, "patch %zu: lpf.kind bp2 needs lpf.q > 0 (tan(theta / (2 q)) must stay finite)", k);
-        if (pt.lpf_kind >= S2R_FILT_SVF_LP && !(pt.lpf_q >= 0x1p-100f))
-            return set_err(s, S2R_ERR_PATCH_RANGE, "patch %zu: the state-variable filter needs lpf.q > 0 (k = 1 / q)", k);
-    }
     return S2R_OK;
 }
 
@@ -1601,213 +1387,14 @@ int resident_fill(s2r_synth *s, float *out, size_t frames, uint32_t sample_rate,
     return S2R_OK;
 }
 
-// ---- the voice mixer's bookkeeping ----
 
-// The bus fill's staging buffer, once: byte offsets of the [padded_voices] arrays in bus_gains_host / bus_gains_dev.  gL, gR
-// (floats: pan gain times voice gain, times the applied fader), the bus bytes, — once sends are in use — the sends (floats) and
-// the send bus bytes, and behind them, sent with a ramped fill only, the gains' steps per frame dL, dR (floats).
-constexpr size_t kBusGainBytes = 4 * sizeof(float) + 1 + sizeof(float) + 1;     // per padded voice, everything in use
-struct BusLayout { size_t gl, gr, bus, send, send_bus, dl, dr, end; };
-inline BusLayout bus_layout(const s2r_synth *s) {
-    const size_t pv = s->padded_voices, f = pv * sizeof(float);
-    BusLayout o{};
-    o.gr = f; o.bus = 2 * f; o.send = o.bus + pv; o.send_bus = o.send + f;
-    o.dl = (s->mixer.used & kMixSend) ? o.send_bus + pv : o.send;
-    o.dr = o.dl + f; o.end = o.dr + f;
-    return o;
+}  // namespace
+
+int s2r_host::render_rows(s2r_synth *s, uint32_t frames, uint32_t sample_rate, float *rows) {
+    return enqueue_fill(s, frames, sample_rate, s->stream, nullptr, false, false, rows);
 }
 
-// Records of note_ons that had a frame inside a fill which has been rendered since (by any fill: fill_time is back at 0) are the
-// voices' values now.  Called before anything reads or writes the voices' arrays.
-void mixer_settle(s2r_synth *s) {
-    s2r_synth::Mixer &m = s->mixer;
-    if (m.timed.empty() || s->fill_time != 0) return;
-    for (const s2r_synth::Mixer::Record &r : m.timed) m.apply(r);
-    m.timed.clear();
-    s->gains_dirty = kGainsAll;
-}
-
-// The first call that takes attribute `bit` off its default: its arrays, and from here on the note_on paths record it.
-int mixer_begin(s2r_synth *s, uint32_t bit) {
-    s2r_synth::Mixer &m = s->mixer;
-    if (m.used & bit) return S2R_OK;
-    if (bit == kMixFader) {
-        // The host mirrors every shard voice's program from now on.  What the voices hold NOW is on the device (the render
-        // kernels keep it); on top of it come the events the host still holds for the next fill, in their order — the timed
-        // ones as records of their own beside what the queue already holds for those note_ons (a stable sort by frame: the
-        // fields are disjoint, and the order within a frame is the events').
-        S2R_QUIESCE(s);
-        S2R_HIP(s, hipSetDevice(s->device));
-        std::vector<uint32_t> h(s->padded_voices);
-        S2R_HIP(s, hipMemcpyAsync(h.data(), s->v.program, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
-        S2R_HIP(s, hipStreamSynchronize(s->stream));
-        m.program.resize(s->shard_voices);
-        for (uint32_t i = 0; i < s->shard_voices; i++) m.program[i] = (uint8_t)h[i];
-        for (const S2rVoiceEvent &e : s->pending) if (e.flags & S2R_EV_RESTART) m.program[e.voice] = (uint8_t)(e.flags >> S2R_EV_PROGRAM_SHIFT);
-        for (const S2rTimedEvent &te : s->tpending) {
-            if (!(te.flags & S2R_EV_RESTART)) continue;
-            if (te.frame == 0) m.program[te.voice] = (uint8_t)te.program;
-            else m.timed.push_back(s2r_synth::Mixer::Record{te.voice, te.frame, kMixFader, 0.0f, 0.0f, 0.0f, 0u, 0u, (uint8_t)te.program});
-        }
-        std::stable_sort(m.timed.begin(), m.timed.end(), [](const s2r_synth::Mixer::Record &a, const s2r_synth::Mixer::Record &b) { return a.frame < b.frame; });
-    }
-    if (bit == kMixSend && s->bus_gains_host) {                  // the staging buffer is laid out anew (bus_layout): nothing stale in it
-        S2R_HIP(s, hipEventSynchronize(s->bus_gains_sent));
-        std::memset(s->bus_gains_host, 0, s->padded_voices * kBusGainBytes);
-    }
-    if (bit == kMixPan) m.pan.assign(s->shard_voices, 0.0f);
-    if (bit == kMixLevel) { m.gain.assign(s->shard_voices, 1.0f); m.bus.assign(s->shard_voices, 0u); }
-    if (bit == kMixSend) { m.send.assign(s->shard_voices, 0.0f); m.send_bus.assign(s->shard_voices, 0u); }
-    m.used |= bit; s->gains_dirty = kGainsAll;
-    return S2R_OK;
-}
-
-// a note_on took shard voice `local` (the caller has settled): what the program in force gives it, now or at its frame
-inline void mixer_note_on(s2r_synth *s, uint32_t local, uint8_t note, float velocity, uint32_t frame) {
-    s2r_synth::Mixer &m = s->mixer;
-    const s2r_synth::ProgramMix &p = m.prog[s->program];
-    s2r_synth::Mixer::Record r{local, frame, m.used, 0.0f, 0.0f, p.send, p.bus, p.send_bus, (uint8_t)s->program};
-    if (m.used & kMixPan) r.pan = rule_voice_pan(p.pan, p.spread, note);
-    if (m.used & kMixLevel) r.gain = rule_voice_gain(p.level, p.sens, velocity);      // (the other fields are copies: apply looks at r.mask)
-    if (frame == 0) { m.apply(r); s->gains_dirty = kGainsAll; }
-    else m.timed.push_back(r);
-}
-
-inline void snap_faders(s2r_synth *s) {
-    for (s2r_synth::ProgramMix &p : s->mixer.prog) { p.fader_app = p.fader; p.shift_app = p.shift; }
-}
-
-inline bool faders_moving(const s2r_synth *s) {
-    if (!(s->mixer.used & kMixFader)) return false;
-    for (const s2r_synth::ProgramMix &p : s->mixer.prog) if (p.moving()) return true;
-    return false;
-}
-
-// the gains of the voices' pans, from pinned memory to the device on the handle's stream (when a pan changed)
-int pan_send_gains(s2r_synth *s) {
-    if (!(s->gains_dirty & kGainsPan)) return S2R_OK;
-    const size_t pv = s->padded_voices;
-    const s2r_synth::Mixer &m = s->mixer;
-    if (!s->gains_host) {
-        S2R_HIP(s, hipHostMalloc((void **)&s->gains_host, 2 * pv * sizeof(float), hipHostMallocDefault));
-        std::memset(s->gains_host, 0, 2 * pv * sizeof(float));
-        S2R_HIP(s, hipMalloc((void **)&s->gains_dev, 2 * pv * sizeof(float)));
-        S2R_HIP(s, hipEventCreateWithFlags(&s->gains_sent, hipEventDisableTiming));
-    } else S2R_HIP(s, hipEventSynchronize(s->gains_sent));       // (the last copy may still be reading the pinned buffer)
-    for (uint32_t i = 0; i < s->shard_voices; i++) rule_pan_gains((m.used & kMixPan) ? m.pan[i] : 0.0f, s->gains_host + i, s->gains_host + pv + i);
-    S2R_HIP(s, hipMemcpyAsync(s->gains_dev, s->gains_host, 2 * pv * sizeof(float), hipMemcpyHostToDevice, s->stream));
-    S2R_HIP(s, hipEventRecord(s->gains_sent, s->stream));
-    s->gains_dirty &= ~kGainsPan;
-    return S2R_OK;
-}
-
-// What the bus mixdown reads per voice (BusLayout) — both pan gains times the voice's gain (one rounded multiply each), times its
-// program's applied fader once faders are in use, the bus byte, the send and its bus byte once sends are in use — from pinned memory
-// to the device on the handle's stream (when a pan, a mix, a send or a fader changed).  `ramp`: a bus fill of `total` frames with a
-// fader on its way: the gains under the applied pairs and their steps per frame towards the gains under the targets — one staging
-// buffer, one copy.
-int bus_send_gains(s2r_synth *s, bool ramp, uint32_t total) {
-    if (!(s->gains_dirty & kGainsBus) && s->bus_dev_ramped == ramp) return S2R_OK;
-    const size_t pv = s->padded_voices;
-    const BusLayout o = bus_layout(s);
-    const s2r_synth::Mixer &m = s->mixer;
-    if (!s->bus_gains_host) {
-        S2R_HIP(s, hipHostMalloc((void **)&s->bus_gains_host, pv * kBusGainBytes, hipHostMallocDefault));
-        std::memset(s->bus_gains_host, 0, pv * kBusGainBytes);
-        S2R_HIP(s, hipMalloc((void **)&s->bus_gains_dev, pv * kBusGainBytes));
-        S2R_HIP(s, hipEventCreateWithFlags(&s->bus_gains_sent, hipEventDisableTiming));
-    } else S2R_HIP(s, hipEventSynchronize(s->bus_gains_sent));
-    char *host = s->bus_gains_host;
-    float *gl = reinterpret_cast<float *>(host + o.gl), *gr = reinterpret_cast<float *>(host + o.gr);
-    float *dl = reinterpret_cast<float *>(host + o.dl), *dr = reinterpret_cast<float *>(host + o.dr);
-    uint8_t *b = reinterpret_cast<uint8_t *>(host + o.bus);
-    const size_t n_prog = m.prog.size();
-    const float fn = (float)total;
-    if (m.used & kMixSend) {
-        std::memcpy(host + o.send, m.send.data(), (size_t)s->shard_voices * sizeof(float));
-        std::memcpy(host + o.send_bus, m.send_bus.data(), (size_t)s->shard_voices);
-    }
-    for (uint32_t i = 0; i < s->shard_voices; i++) {
-        const float pan = (m.used & kMixPan) ? m.pan[i] : 0.0f, w = (m.used & kMixLevel) ? m.gain[i] : 1.0f;
-        b[i] = (m.used & kMixLevel) ? m.bus[i] : (uint8_t)0;
-        if (!(m.used & kMixFader)) {
-            float l, r;
-            rule_pan_gains(pan, &l, &r);
-            gl[i] = l * w; gr[i] = r * w;
-            continue;
-        }
-        const s2r_synth::ProgramMix &p = m.prog[m.program[i] < n_prog ? m.program[i] : 0u];      // (past a later, smaller bank: program 0, as its patch is)
-        float g0l, g0r;
-        rule_fader_gains(pan, w, p.fader_app, p.shift_app, &g0l, &g0r);
-        gl[i] = g0l; gr[i] = g0r;
-        if (!ramp) continue;
-        if (p.moving()) {
-            float g1l, g1r;
-            rule_fader_gains(pan, w, p.fader, p.shift, &g1l, &g1r);
-            const float sl = g1l - g0l, sr = g1r - g0r;
-            dl[i] = sl / fn; dr[i] = sr / fn;
-        } else { dl[i] = 0.0f; dr[i] = 0.0f; }
-    }
-    S2R_HIP(s, hipMemcpyAsync(s->bus_gains_dev, host, ramp ? o.end : o.dl, hipMemcpyHostToDevice, s->stream));
-    S2R_HIP(s, hipEventRecord(s->bus_gains_sent, s->stream));
-    s->gains_dirty &= ~kGainsBus;
-    s->bus_dev_ramped = ramp;
-    return S2R_OK;
-}
-
-// Frames [at, at + n) of a panned fill (n_buses == 0) or of a bus fill of `total` frames, the events of frame `at` already folded
-// into `pending`: slice after slice the MODE 1 launch into the rows buffer and the mixdown into the mapped output.  `last_event`:
-// the frame the pool's clock has already been moved to by the fill's events (fill_time at entry) — the slices from there on move
-// it further.
-// `ramp`: a bus fill under moving faders — the ramped mixdown, told where in the CALL each slice begins.  `bus_dst`: the route's combine_out.
-int pan_segment(s2r_synth *s, uint32_t at, uint32_t n, uint32_t last_event, uint32_t sample_rate, uint32_t n_buses, uint32_t total, bool ramp,
-                float *bus_dst) {
-    S2R_TRY(n_buses ? bus_send_gains(s, ramp, total) : pan_send_gains(s));
-    for (uint32_t done = 0; done < n;) {
-        const uint32_t len = n - done < s->pan_slice ? n - done : s->pan_slice;
-        s->fill_time = at + done >= last_event ? 0u : len;       // enqueue_fill moves the clock by len - fill_time
-        S2R_TRY(enqueue_fill(s, len, sample_rate, s->stream, nullptr, false, false, s->pan_rows));
-        const uint32_t n_groups = s->mix_groups, blocks_per_group = (s->n_blocks + n_groups - 1) / n_groups;
-        if (s->timing) {
-            while (s->pan_ev.size() < s->pan_ev_used + 2) { hipEvent_t e; S2R_HIP(s, hipEventCreate(&e)); s->pan_ev.push_back(e); }
-            S2R_HIP(s, hipEventRecord(s->pan_ev[s->pan_ev_used], s->stream));
-        }
-        if (n_buses) {
-            S2rBusMix m{};
-            const BusLayout o = bus_layout(s);
-            const char *dev = s->bus_gains_dev;
-            m.rows = s->pan_rows;
-            m.gain_l = reinterpret_cast<const float *>(dev + o.gl); m.gain_r = reinterpret_cast<const float *>(dev + o.gr);
-            m.bus = reinterpret_cast<const uint8_t *>(dev + o.bus);
-            m.n_voices = s->shard_voices; m.block_voices = s->block_voices; m.n_blocks = s->n_blocks;
-            m.frames = len; m.stride = len;                      // (the render kernel's rows are `frames` apart)
-            m.partials = s->bus_partials; m.pstride = s->pan_slice;
-            m.n_groups = n_groups; m.blocks_per_group = blocks_per_group;
-            m.out = bus_dst + 2u * (size_t)(at + done); m.ostride = 2u * (size_t)total;
-            m.n_buses = n_buses;
-            if (ramp) {
-                m.d_l = reinterpret_cast<const float *>(dev + o.dl); m.d_r = reinterpret_cast<const float *>(dev + o.dr);
-                m.frame_base = at + done;
-            }
-            if (s->mixer.used & kMixSend) {
-                m.send = reinterpret_cast<const float *>(dev + o.send); m.send_bus = reinterpret_cast<const uint8_t *>(dev + o.send_bus);
-            }
-            S2R_HIP(s, s2r_launch_bus_mix(m, s->stream));
-        } else {
-            S2rPanMix m{};
-            m.rows = s->pan_rows; m.gain_l = s->gains_dev; m.gain_r = s->gains_dev + s->padded_voices;
-            m.n_voices = s->shard_voices; m.block_voices = s->block_voices; m.n_blocks = s->n_blocks;
-            m.frames = len; m.stride = len;                      // (the render kernel's rows are `frames` apart)
-            m.partials = s->pan_partials; m.pstride = s->pan_slice;
-            m.n_groups = n_groups; m.blocks_per_group = blocks_per_group;
-            m.out = s->out_host_dev + 2u * (size_t)(at + done);
-            S2R_HIP(s, s2r_launch_pan_mix(m, s->stream));
-        }
-        if (s->timing) { S2R_HIP(s, hipEventRecord(s->pan_ev[s->pan_ev_used + 1], s->stream)); s->pan_ev_used += 2; }
-        done += len;
-    }
-    return S2R_OK;
-}
+namespace {
 
 int fill_host(s2r_synth *s, float *out, size_t frames, uint32_t sample_rate, bool stereo) {
     S2R_TRY(check_fill(s, frames, sample_rate));
@@ -1857,10 +1444,6 @@ int fill_host(s2r_synth *s, float *out, size_t frames, uint32_t sample_rate, boo
     return S2R_OK;
 }
 
-// what the post-mix chain is told of the handle
-template <class T> inline void put(T *to, T v) { if (to) *to = v; }             // an optional output of a getter
-inline S2rPostCtx post_ctx(const s2r_synth *s) { return S2rPostCtx{s->stream, s->cfg.max_frames, s->timing, s->bus_out_dev, s->out_host_dev}; }
-
 void release_all(s2r_synth *s) {
     if (!s) return;
     (void)quiesce(s);
@@ -1906,18 +1489,8 @@ void release_all(s2r_synth *s) {
     if (s->res_host) (void)hipHostFree(s->res_host);
     if (s->res_gran) (void)hipHostFree(s->res_gran);
     if (s->per_voice_dev) (void)hipFree(s->per_voice_dev);
-    if (s->gains_host) (void)hipHostFree(s->gains_host);
-    if (s->gains_dev) (void)hipFree(s->gains_dev);
-    if (s->gains_sent) (void)hipEventDestroy(s->gains_sent);
-    if (s->pan_rows) (void)hipFree(s->pan_rows);
-    if (s->pan_partials) (void)hipFree(s->pan_partials);
-    if (s->bus_gains_host) (void)hipHostFree(s->bus_gains_host);
-    if (s->bus_gains_dev) (void)hipFree(s->bus_gains_dev);
-    if (s->bus_gains_sent) (void)hipEventDestroy(s->bus_gains_sent);
-    if (s->bus_partials) (void)hipFree(s->bus_partials);
-    if (s->bus_out) (void)hipHostFree(s->bus_out);
+    s->mixer_dev.release();
     s->post.release();
-    for (hipEvent_t e : s->pan_ev) (void)hipEventDestroy(e);
     if (s->voice_ev_head) (void)hipFree(s->voice_ev_head);
     if (s->tev_copy) (void)hipFree(s->tev_copy);
     if (s->partials2[1]) (void)hipFree(s->partials2[1]);
@@ -2022,6 +1595,7 @@ static int create_single(const s2r_config *cfg, std::shared_ptr<S2rVoicePool> po
     s->parent = parent;
     s->bank.resize(1);
     s->mixer.prog.resize(1);
+    s->mixer.shape(shard_voices, s->padded_voices);
     s2r_default_patch(&s->bank[0]);
     if (pool) s->pool = pool;
     else { s->pool.reset(new S2rVoicePool(cfg->total_voices)); s->seed_override.assign(cfg->total_voices, 0u); configure_policy_threads(s->pool.get(), cfg->total_voices); }
@@ -2275,8 +1849,7 @@ int s2r_set_patch_bank(s2r_synth *s, const s2r_patch *patches, uint32_t n) {
     }
     S2R_QUIESCE(s);
     s->bank.assign(patches, patches + n);
-    s->mixer.prog.resize(n);                                     // the surviving programs keep their pans, mix, sends and faders
-    if (s->mixer.used & kMixFader) s->gains_dirty = kGainsAll;   // (a voice whose program fell off the bank follows program 0 now)
+    s->mixer.resize_bank(n);
     if (s->program >= n) s->program = 0;
     s->bank_dirty = true; s->tab_dirty = true;
     for (s2r_synth *kid : s->kids) { kid->bank = s->bank; kid->bank_dirty = true; kid->tab_dirty = true; }
@@ -2328,8 +1901,8 @@ int s2r_note_on_ex(s2r_synth *s, uint8_t note, float velocity, uint32_t *voice_i
     if (s->voice_log) s->voice_log(s->voice_log_user, i, note);
     if (s->mixer.used && s->kids.empty()) {
         const int64_t mine = to_local(s, i);
-        mixer_settle(s);
-        if (mine >= 0) mixer_note_on(s, (uint32_t)mine, note, velocity, 0u);
+        s->mixer.settle(s->fill_time);
+        if (mine >= 0) s->mixer.note_on((uint32_t)mine, s->program, note, velocity, 0u);
     }
     if (!append_frame0_record(s, i, S2R_EV_RESTART, s->pitch_table[note], s->seed_override[i], s->program))
         push_event(s, i, S2R_EV_RESTART, s->pitch_table[note], s->seed_override[i], s->program);
@@ -2377,7 +1950,7 @@ int s2r_note_events(s2r_synth *s, const s2r_note_event *events, size_t n) {
     // and note_off over the events computes — on several threads for a multi-GPU-sized batch): the voice every event takes or
     // releases.  An event inside the next fill first moves the pool's clock to its frame (the policy sees the offsets every
     // voice has AT that frame, like the reference between two 16-frame calls); frame-0 events take effect before the fill.
-    if (s->mixer.used) mixer_settle(s);                          // (while fill_time still says whether the last fill's events are behind us)
+    if (s->mixer.used) s->mixer.settle(s->fill_time);                        // (while fill_time still says whether the last fill's events are behind us)
     static thread_local std::vector<int64_t> chosen;
     if (chosen.size() < n) chosen.resize(n);
     static_assert(sizeof(S2rPolicyEvent) == 4 && S2R_NOTE_ON == S2R_POLICY_NOTE_ON && S2R_NOTE_OFF == S2R_POLICY_NOTE_OFF, "s2r_note_event's first four bytes");
@@ -2418,7 +1991,7 @@ int s2r_note_events(s2r_synth *s, const s2r_note_event *events, size_t n) {
         }
         const uint32_t frame = e.frame;
         const bool on = e.kind == S2R_NOTE_ON;
-        if (on && one && one->mixer.used) mixer_note_on(one, local, e.note, e.velocity, frame);
+        if (on && one && one->mixer.used) one->mixer.note_on(local, one->program, e.note, e.velocity, frame);
         if (frame == 0 && may_fold && sh->tpending.empty()) {
             if (on) push_event(s, (uint32_t)vi, S2R_EV_RESTART, pitch_of[e.note], seed_of[(size_t)vi], s->program);
             else push_event(s, (uint32_t)vi, S2R_EV_RELEASE, 0.0f, 0u);
@@ -2497,1014 +2070,6 @@ int s2r_fill_end(s2r_synth *s, float *mono_out, size_t capacity) {
 int s2r_fill_stereo(s2r_synth *s, float *interleaved_lr_out, size_t frames, uint32_t sample_rate_hz) {
     return fill_host(s, interleaved_lr_out, frames, sample_rate_hz, true);
 }
-
-// ---- true stereo ----
-int s2r_set_program_pan(s2r_synth *s, uint32_t program, float pan, float key_spread) {
-    // (the values first: they are wrong whatever the handle holds — and a front-end can ask without a device)
-    if (!pan_in_range(pan) || !pan_in_range(key_spread))
-        return set_err(s, S2R_ERR_PATCH_RANGE, "program %u: pan %g, key_spread %g: both lie in [-1, 1]", program, (double)pan, (double)key_spread);
-    if (!s) return S2R_ERR_INVALID;
-    if (program >= s->bank.size()) return set_err(s, S2R_ERR_INVALID, "program %u: the bank holds %zu patches", program, s->bank.size());
-    if (pan != 0.0f || key_spread != 0.0f) { (void)mixer_begin(s, kMixPan); mixer_settle(s); }
-    s->mixer.prog[program].pan = pan; s->mixer.prog[program].spread = key_spread;
-    return S2R_OK;
-}
-
-int s2r_get_program_pan(const s2r_synth *s, uint32_t program, float *pan, float *key_spread) {
-    if (!s) return S2R_ERR_INVALID;
-    if (program >= s->bank.size()) return S2R_ERR_INVALID;
-    if (pan) *pan = s->mixer.prog[program].pan;
-    if (key_spread) *key_spread = s->mixer.prog[program].spread;
-    return S2R_OK;
-}
-
-int s2r_get_voice_pans(s2r_synth *s, float *pans) {
-    if (!s || !pans) return S2R_ERR_INVALID;
-    if (!s->kids.empty()) return set_err(s, S2R_ERR_INVALID, "voice pans are kept by single-device handles, not by a device list");
-    if (!(s->mixer.used & kMixPan)) { std::fill(pans, pans + s->shard_voices, 0.0f); return S2R_OK; }
-    // (pans of note_ons inside a fill not rendered yet are not the voices' yet)
-    mixer_settle(s);
-    std::memcpy(pans, s->mixer.pan.data(), (size_t)s->shard_voices * sizeof(float));
-    return S2R_OK;
-}
-
-int s2r_set_voice_pans(s2r_synth *s, const float *pans) {
-    if (!s || !pans) return S2R_ERR_INVALID;
-    if (!s->kids.empty()) return set_err(s, S2R_ERR_INVALID, "voice pans are kept by single-device handles, not by a device list");
-    for (uint32_t i = 0; i < s->shard_voices; i++)
-        if (!pan_in_range(pans[i])) return set_err(s, S2R_ERR_PATCH_RANGE, "voice %u: pan %g does not lie in [-1, 1]", i, (double)pans[i]);
-    (void)mixer_begin(s, kMixPan);
-    mixer_settle(s);
-    std::memcpy(s->mixer.pan.data(), pans, (size_t)s->shard_voices * sizeof(float));
-    s->gains_dirty = kGainsAll;
-    return S2R_OK;
-}
-
-// s2r_fill_panned (n_buses == 0: two channels into `out`), s2r_fill_buses (n_buses stereo buses, bus-major, `capacity` floats) and
-// s2r_fill_master (`master`: the master section behind the buses, its two channels into `master_lr`; `out` — the stems — may be null)
-static int fill_rows_mixed(s2r_synth *s, float *out, size_t capacity, uint32_t n_buses, size_t frames, uint32_t sample_rate_hz, const char *who,
-                           bool master = false, float *master_lr = nullptr) {
-    if (!s) return S2R_ERR_INVALID;
-    if (!s->kids.empty() || s->parent) return set_err(s, S2R_ERR_INVALID, "%s takes a single-device handle, not a device list", who);
-    if (s->xg_on) return set_err(s, S2R_ERR_INVALID, "%s takes a handle without an exchange attached", who);
-    S2R_TRY(check_fill(s, frames, sample_rate_hz));
-    if (frames == 0) return S2R_OK;
-    if (master ? !master_lr : !out) return set_err(s, S2R_ERR_INVALID, "null output buffer");
-    if (n_buses && out && capacity < 2 * frames * n_buses)
-        return set_err(s, S2R_ERR_INVALID, "%s: %u buses of %zu frames take %zu floats, the buffer holds %zu", who, n_buses, frames, 2 * frames * n_buses, capacity);
-    if (s->ring_count) return set_err(s, S2R_ERR_INVALID, "%s with fills of s2r_fill_begin in flight: s2r_fill_end first", who);
-    S2R_QUIESCE(s);
-    S2R_HIP(s, hipSetDevice(s->device));
-    if (!s->pan_rows) {
-        // The rows buffer, sized ONCE (s2r.h): whole fills where they fit into 256 MiB, else slices of a multiple of 16 frames —
-        // a fill split at a multiple of 16 renders the same bits (s2r.h, s2r_note_events).  (Shorter slices, whose rows would
-        // stay closer to the compute units, were measured and are slower: profiles/r05/pan_mix.txt)
-        uint32_t slice = (uint32_t)std::min<size_t>((((size_t)256 << 20) / sizeof(float) / s->shard_voices) & ~(size_t)15, 1u << 30);
-        if (const char *e = std::getenv("S2R_PAN_SLICE")) slice = (uint32_t)std::atol(e) & ~15u;      // (measurement: tools/pan_time.py)
-        const uint32_t whole = (s->cfg.max_frames + 15u) & ~15u;
-        if (slice < 16u) slice = 16u;
-        if (slice > whole) slice = whole;
-        S2R_HIP(s, hipMalloc((void **)&s->pan_rows, (size_t)s->shard_voices * slice * sizeof(float)));
-        s->pan_slice = slice;
-    }
-    // the workgroups' partial rows of the mixdown asked for (and the bus fill's pinned output), once each
-    if (!n_buses && !s->pan_partials) S2R_HIP(s, hipMalloc((void **)&s->pan_partials, (size_t)s->n_blocks * 2u * s->pan_slice * sizeof(float)));
-    if (n_buses && !s->bus_partials) S2R_HIP(s, hipMalloc((void **)&s->bus_partials, (size_t)s->n_blocks * 2u * S2R_MAX_BUSES * s->pan_slice * sizeof(float)));
-    if (n_buses && out && !s->bus_out) {
-        S2R_HIP(s, hipHostMalloc((void **)&s->bus_out, (size_t)2 * S2R_MAX_BUSES * s->cfg.max_frames * sizeof(float), kHostPolled));
-        S2R_HIP(s, hipHostGetDevicePointer((void **)&s->bus_out_dev, s->bus_out, 0));
-    }
-    // what runs behind the mixdown in this call, its once-only allocations and who writes where (s2r_post.h)
-    const S2rPostCtx pc = post_ctx(s); S2rPostCall call;
-    S2R_HIP(s, s->post.prepare(pc, n_buses, (uint32_t)frames, master, out != nullptr, call));
-    fold_frame0_records(s);
-    mixer_settle(s);
-    s->pan_ev_used = 0;
-    const uint32_t last_event = s->fill_time;
-    // a bus fill with a program fader away from where the last one left it ramps; whatever the device holds from
-    // an earlier ramp is stale, and what this one sends is no static gain either (bus_dev_ramped)
-    const bool ramp = n_buses && faders_moving(s);
-    if (ramp) s->gains_dirty |= kGainsBus;
-    if (s->tpending.empty()) S2R_TRY(pan_segment(s, 0u, (uint32_t)frames, last_event, sample_rate_hz, n_buses, (uint32_t)frames, ramp, call.route.combine_out));
-    else {
-        // Events inside the fill: the per-voice rows and the event chains exclude each other in the render kernels, and an
-        // event at frame f acts "exactly as if the caller had split the fill there" (s2r.h) — so the fill IS split there: the
-        // records of one frame are folded like untimed ones (fold_frame0_records), what their note_ons give becomes the voices', and
-        // the segment up to the next event frame is rendered.  (Records arrive in non-decreasing frame order.)
-        std::vector<S2rTimedEvent> recs;
-        recs.swap(s->tpending);
-        for (const S2rTimedEvent &te : recs) s->tlast[te.voice] = -1;
-        std::vector<s2r_synth::Mixer::Record> mrecs;
-        mrecs.swap(s->mixer.timed);
-        size_t k = 0, km = 0;
-        uint32_t at = 0;
-        while (at < frames) {
-            for (; k < recs.size() && recs[k].frame <= at; k++) fold_event(s, recs[k].voice, recs[k].flags, recs[k].pitch, recs[k].seed, recs[k].program);
-            for (; km < mrecs.size() && mrecs[km].frame <= at; km++) { s->mixer.apply(mrecs[km]); s->gains_dirty = kGainsAll; }
-            const uint32_t next = k < recs.size() && recs[k].frame < frames ? recs[k].frame : (uint32_t)frames;
-            const int rc = pan_segment(s, at, next - at, last_event, sample_rate_hz, n_buses, (uint32_t)frames, ramp, call.route.combine_out);
-            if (rc != S2R_OK) { s->fill_time = 0; return rc; }
-            at = next;
-        }
-    }
-    S2R_HIP(s, s->post.launch(pc, call));
-    S2R_HIP(s, hipStreamSynchronize(s->stream));
-    if (n_buses && (s->mixer.used & kMixFader)) snap_faders(s);  // the faders have arrived
-    s->post.commit(call);                                        // ... and so has everything behind the mixdown
-    if (n_buses && out) std::memcpy(out, s->bus_out, 2 * frames * n_buses * sizeof(float));
-    if (master) std::memcpy(master_lr, s->out_host, 2 * frames * sizeof(float));
-    else if (!n_buses) std::memcpy(out, s->out_host, 2 * frames * sizeof(float));
-    if (s->timing) {
-        float sum = 0.0f;
-        for (size_t k = 0; k < s->pan_ev_used; k += 2) { float ms = 0.0f; S2R_HIP(s, hipEventElapsedTime(&ms, s->pan_ev[k], s->pan_ev[k + 1])); sum += ms; }
-        (n_buses ? s->bus_mix_ms : s->pan_mix_ms) = sum;
-        S2R_HIP(s, s->post.read_timers(call));
-    }
-    return S2R_OK;
-}
-
-int s2r_fill_panned(s2r_synth *s, float *interleaved_lr_out, size_t frames, uint32_t sample_rate_hz) {
-    return fill_rows_mixed(s, interleaved_lr_out, 0, 0u, frames, sample_rate_hz, "s2r_fill_panned");
-}
-
-// ---- the voice mixer ----
-int s2r_set_program_mix(s2r_synth *s, uint32_t program, float level, float velocity_sens, uint32_t bus) {
-    // (the values first, like s2r_set_program_pan)
-    if (!unit_in_range(level) || !unit_in_range(velocity_sens) || bus >= S2R_MAX_BUSES)
-        return set_err(s, S2R_ERR_PATCH_RANGE, "program %u: level %g, velocity_sens %g, bus %u: both values lie in [0, 1], the bus below %u", program,
-                       (double)level, (double)velocity_sens, bus, S2R_MAX_BUSES);
-    if (!s) return S2R_ERR_INVALID;
-    if (program >= s->bank.size()) return set_err(s, S2R_ERR_INVALID, "program %u: the bank holds %zu patches", program, s->bank.size());
-    if (level != 1.0f || velocity_sens != 0.0f || bus != 0u) { (void)mixer_begin(s, kMixLevel); mixer_settle(s); }
-    s2r_synth::ProgramMix &p = s->mixer.prog[program];
-    p.level = level; p.sens = velocity_sens; p.bus = (uint8_t)bus;
-    return S2R_OK;
-}
-
-int s2r_get_program_mix(const s2r_synth *s, uint32_t program, float *level, float *velocity_sens, uint32_t *bus) {
-    if (!s) return S2R_ERR_INVALID;
-    if (program >= s->bank.size()) return S2R_ERR_INVALID;
-    const s2r_synth::ProgramMix &p = s->mixer.prog[program];
-    if (level) *level = p.level;
-    if (velocity_sens) *velocity_sens = p.sens;
-    if (bus) *bus = p.bus;
-    return S2R_OK;
-}
-
-int s2r_get_voice_mix(s2r_synth *s, float *gains, uint8_t *buses) {
-    if (!s || !gains || !buses) return S2R_ERR_INVALID;
-    if (!s->kids.empty()) return set_err(s, S2R_ERR_INVALID, "voice mixes are kept by single-device handles, not by a device list");
-    if (!(s->mixer.used & kMixLevel)) { std::fill(gains, gains + s->shard_voices, 1.0f); std::memset(buses, 0, s->shard_voices); return S2R_OK; }
-    mixer_settle(s);
-    std::memcpy(gains, s->mixer.gain.data(), (size_t)s->shard_voices * sizeof(float));
-    std::memcpy(buses, s->mixer.bus.data(), (size_t)s->shard_voices);
-    return S2R_OK;
-}
-
-int s2r_set_voice_mix(s2r_synth *s, const float *gains, const uint8_t *buses) {
-    if (!s || !gains || !buses) return S2R_ERR_INVALID;
-    if (!s->kids.empty()) return set_err(s, S2R_ERR_INVALID, "voice mixes are kept by single-device handles, not by a device list");
-    for (uint32_t i = 0; i < s->shard_voices; i++)
-        if (!unit_in_range(gains[i]) || buses[i] >= S2R_MAX_BUSES)
-            return set_err(s, S2R_ERR_PATCH_RANGE, "voice %u: gain %g, bus %u: the gain lies in [0, 1], the bus below %u", i, (double)gains[i], (unsigned)buses[i], S2R_MAX_BUSES);
-    (void)mixer_begin(s, kMixLevel);
-    mixer_settle(s);
-    std::memcpy(s->mixer.gain.data(), gains, (size_t)s->shard_voices * sizeof(float));
-    std::memcpy(s->mixer.bus.data(), buses, (size_t)s->shard_voices);
-    s->gains_dirty = kGainsAll;
-    return S2R_OK;
-}
-
-// ---- aux sends ----
-int s2r_set_program_send(s2r_synth *s, uint32_t program, float send, uint32_t send_bus) {
-    // (the values first, like s2r_set_program_mix)
-    if (!unit_in_range(send) || send_bus >= S2R_MAX_BUSES)
-        return set_err(s, S2R_ERR_PATCH_RANGE, "program %u: send %g, send bus %u: the send lies in [0, 1], the bus below %u", program, (double)send, send_bus, S2R_MAX_BUSES);
-    if (!s) return S2R_ERR_INVALID;
-    if (!s->kids.empty() || s->parent) return set_err(s, S2R_ERR_INVALID, "program sends are kept by single-device handles, not by a device list");
-    if (program >= s->bank.size()) return set_err(s, S2R_ERR_INVALID, "program %u: the bank holds %zu patches", program, s->bank.size());
-    if (send != 0.0f || send_bus != 0u) {
-        S2R_TRY(mixer_begin(s, kMixSend));
-        mixer_settle(s);
-    }
-    s->mixer.prog[program].send = send; s->mixer.prog[program].send_bus = (uint8_t)send_bus;
-    return S2R_OK;
-}
-
-int s2r_get_program_send(const s2r_synth *s, uint32_t program, float *send, uint32_t *send_bus) {
-    if (!s) return S2R_ERR_INVALID;
-    if (!s->kids.empty() || s->parent || program >= s->bank.size()) return S2R_ERR_INVALID;
-    if (send) *send = s->mixer.prog[program].send;
-    if (send_bus) *send_bus = s->mixer.prog[program].send_bus;
-    return S2R_OK;
-}
-
-int s2r_get_voice_sends(s2r_synth *s, float *sends, uint8_t *send_buses) {
-    if (!s || !sends || !send_buses) return S2R_ERR_INVALID;
-    if (!s->kids.empty() || s->parent) return set_err(s, S2R_ERR_INVALID, "voice sends are kept by single-device handles, not by a device list");
-    if (!(s->mixer.used & kMixSend)) { std::fill(sends, sends + s->shard_voices, 0.0f); std::memset(send_buses, 0, s->shard_voices); return S2R_OK; }
-    mixer_settle(s);
-    std::memcpy(sends, s->mixer.send.data(), (size_t)s->shard_voices * sizeof(float));
-    std::memcpy(send_buses, s->mixer.send_bus.data(), (size_t)s->shard_voices);
-    return S2R_OK;
-}
-
-int s2r_set_voice_sends(s2r_synth *s, const float *sends, const uint8_t *send_buses) {
-    if (!s || !sends || !send_buses) return S2R_ERR_INVALID;
-    if (!s->kids.empty() || s->parent) return set_err(s, S2R_ERR_INVALID, "voice sends are kept by single-device handles, not by a device list");
-    for (uint32_t i = 0; i < s->shard_voices; i++)
-        if (!unit_in_range(sends[i]) || send_buses[i] >= S2R_MAX_BUSES)
-            return set_err(s, S2R_ERR_PATCH_RANGE, "voice %u: send %g, send bus %u: the send lies in [0, 1], the bus below %u", i, (double)sends[i], (unsigned)send_buses[i], S2R_MAX_BUSES);
-    S2R_TRY(mixer_begin(s, kMixSend));
-    mixer_settle(s);
-    std::memcpy(s->mixer.send.data(), sends, (size_t)s->shard_voices * sizeof(float));
-    std::memcpy(s->mixer.send_bus.data(), send_buses, (size_t)s->shard_voices);
-    s->gains_dirty = kGainsAll;
-    return S2R_OK;
-}
-
-// ---- the post-mix chain: the eight bus stages, master section, master limiter (s2r_post.h) ----
-// Every entry below looks at its values first (they are wrong whatever the handle holds), then at the handle, quiesces where it touches
-// the device, and calls into s->post for whatever is more than one value.  `what`: "bus reverbs are", "the master section is", ...
-static int post_handle(const s2r_synth *s, const char *who, const char *what) {
-    if (!s) return S2R_ERR_INVALID;
-    if (!s->kids.empty() || s->parent) return set_err(const_cast<s2r_synth *>(s), S2R_ERR_INVALID, "%s: %s kept by single-device handles, not by a device list", who, what);
-    return S2R_OK;
-}
-
-// the words in which the entries of a bus stage differ, by S2rBusStage
-static const struct { const char *one, *are; } kStemWords[S2R_BUS_STAGES] = {{"EQ", "bus equalisers are"}, {"dynamics", "bus dynamics are"}, {"drive", "bus drives are"},
-                                                                             {"flanger", "bus flangers are"}, {"chorus", "bus choruses are"}, {"delay", "bus delays are"},
-                                                                             {"reverb", "bus reverbs are"}, {"room", "bus rooms are"}};
-
-// The guard of an entry that reads or changes the effect one bus carries: the bus in range, a single-device handle, and the bus
-// carries one.  `who` null: a getter, which answers for a bus without one too and leaves the handle's error text alone; `named`:
-// the refusal of a bus without one begins with `who`.
-static int stem_bus(const s2r_synth *s, S2rBusStage k, uint32_t bus, const char *who, bool named) {
-    if (!who) return bus >= S2R_MAX_BUSES ? S2R_ERR_PATCH_RANGE : (!s || !s->kids.empty() || s->parent) ? S2R_ERR_INVALID : S2R_OK;
-    s2r_synth *m = const_cast<s2r_synth *>(s);
-    if (bus >= S2R_MAX_BUSES) return set_err(m, S2R_ERR_PATCH_RANGE, "%s: bus %u, below %u", who, bus, S2R_MAX_BUSES);
-    S2R_TRY(post_handle(s, who, kStemWords[k].are));
-    if (s->post.bus(k, bus).present()) return S2R_OK;
-    if (named) return set_err(m, S2R_ERR_INVALID, "%s: bus %u carries no %s", who, bus, kStemWords[k].one);
-    return set_err(m, S2R_ERR_INVALID, "bus %u carries no %s", bus, kStemWords[k].one);
-}
-
-// The common tail of the entries that set or clear an effect, behind their checks of the values and the handle: no fills in
-// flight, a quiet stream, the chain's setter, and its error.
-static int stem_set(s2r_synth *s, const char *who, const std::function<hipError_t(const S2rPostCtx &)> &set) {
-    if (s->ring_count) return set_err(s, S2R_ERR_INVALID, "%s with fills of s2r_fill_begin in flight: s2r_fill_end first", who);
-    S2R_QUIESCE(s);
-    S2R_HIP(s, hipSetDevice(s->device));
-    S2R_HIP(s, hipStreamSynchronize(s->stream));
-    const hipError_t e = set(post_ctx(s));
-    if (e != hipSuccess) return set_err(s, e == hipErrorOutOfMemory ? S2R_ERR_OUT_OF_MEMORY : S2R_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    return S2R_OK;
-}
-
-// An effect's history out (`get`, `count` the capacity) or in (`set`, `count` exact): it crosses the boundary as frames, oldest
-// first, L then R.  A reverb of one tap has none, and nothing to copy.
-static int stem_history(s2r_synth *s, S2rBusStage k, uint32_t bus, float *get, const float *set, size_t count, const char *who) {
-    S2R_TRY(stem_bus(s, k, bus, who, true));
-    const size_t h = s->post.bus(k, bus).history;
-    if (set ? count != 2 * h : count < 2 * h) return set_err(s, S2R_ERR_INVALID, "%s: the history of bus %u is %zu floats, not %zu", who, bus, 2 * h, count);
-    if (h == 0) return S2R_OK;
-    if (!get && !set) return set_err(s, S2R_ERR_INVALID, "%s: null buffer", who);
-    S2R_QUIESCE(s);
-    S2R_HIP(s, hipSetDevice(s->device));
-    S2R_HIP(s, hipStreamSynchronize(s->stream));
-    S2R_HIP(s, s->post.history(post_ctx(s), k, bus, get, set));
-    return S2R_OK;
-}
-
-// An effect's whole state out (`get`, `count` the capacity) or in (`set`, `count` exact), for the stages whose checkpoint is every
-// float of their line.  `values`: the stage's own check of a state coming in, behind the count's and in front of the device.
-static int stem_state(s2r_synth *s, S2rBusStage k, uint32_t bus, float *get, const float *set, size_t count, const char *who,
-                      int (*values)(s2r_synth *, const float *, size_t, const char *) = nullptr) {
-    S2R_TRY(stem_bus(s, k, bus, who, true));
-    const size_t n = s->post.bus(k, bus).floats;
-    if (set ? count != n : count < n) {                          // (the dynamics' state is one float, and their text says so)
-        if (n == 1u) return set_err(s, S2R_ERR_INVALID, "%s: the state of bus %u is 1 float, not %zu", who, bus, count);
-        return set_err(s, S2R_ERR_INVALID, "%s: the state of bus %u is %zu floats, not %zu", who, bus, n, count);
-    }
-    if (!get && !set) return set_err(s, S2R_ERR_INVALID, "%s: null buffer", who);
-    if (set && values) S2R_TRY(values(s, set, n, who));
-    S2R_QUIESCE(s);
-    S2R_HIP(s, hipSetDevice(s->device));
-    S2R_HIP(s, hipStreamSynchronize(s->stream));
-    S2R_HIP(s, s->post.state(post_ctx(s), k, bus, get, set));
-    return S2R_OK;
-}
-
-int s2r_set_bus_reverb(s2r_synth *s, uint32_t bus, const float *ir_l, const float *ir_r, uint32_t n_taps, float dry, float wet) {
-    if (!unit_in_range(dry) || !unit_in_range(wet) || n_taps > S2R_MAX_IR_TAPS || bus >= S2R_MAX_BUSES)
-        return set_err(s, S2R_ERR_PATCH_RANGE, "bus %u: %u taps, dry %g, wet %g: dry and wet lie in [0, 1], at most %u taps, the bus below %u", bus, n_taps,
-                       (double)dry, (double)wet, S2R_MAX_IR_TAPS, S2R_MAX_BUSES);
-    if (!ir_r) ir_r = ir_l;
-    if (ir_l)
-        for (uint32_t k = 0; k < n_taps; k++)
-            if (!std::isfinite(ir_l[k]) || !std::isfinite(ir_r[k])) return set_err(s, S2R_ERR_PATCH_RANGE, "bus %u: tap %u is not finite", bus, k);
-    S2R_TRY(post_handle(s, "s2r_set_bus_reverb", "bus reverbs are"));
-    if (n_taps && !ir_l) return set_err(s, S2R_ERR_INVALID, "s2r_set_bus_reverb: %u taps and no response", n_taps);
-    return stem_set(s, "s2r_set_bus_reverb", [&](const S2rPostCtx &c) { return s->post.set_reverb(c, bus, ir_l, ir_r, n_taps, dry, wet); });
-}
-
-int s2r_set_bus_reverb_mix(s2r_synth *s, uint32_t bus, float dry, float wet) {
-    if (!unit_in_range(dry) || !unit_in_range(wet) || bus >= S2R_MAX_BUSES)
-        return set_err(s, S2R_ERR_PATCH_RANGE, "bus %u: dry %g, wet %g: both lie in [0, 1], the bus below %u", bus, (double)dry, (double)wet, S2R_MAX_BUSES);
-    S2R_TRY(stem_bus(s, S2R_BUS_REVERB, bus, "s2r_set_bus_reverb_mix", false));
-    s->post.fx[bus].dry = dry; s->post.fx[bus].wet = wet;
-    return S2R_OK;
-}
-
-int s2r_get_bus_reverb(const s2r_synth *s, uint32_t bus, uint32_t *n_taps, float *dry, float *wet) {
-    S2R_TRY(stem_bus(s, S2R_BUS_REVERB, bus, nullptr, false));
-    put(n_taps, s->post.fx[bus].n_taps); put(dry, s->post.fx[bus].dry); put(wet, s->post.fx[bus].wet);
-    return S2R_OK;
-}
-
-int s2r_get_bus_reverb_history(s2r_synth *s, uint32_t bus, float *lr, size_t capacity) {
-    return stem_history(s, S2R_BUS_REVERB, bus, lr, nullptr, capacity, "s2r_get_bus_reverb_history");
-}
-
-int s2r_set_bus_reverb_history(s2r_synth *s, uint32_t bus, const float *lr, size_t count) {
-    static const float none = 0.0f;                              // (a null lr: refused by stem_history unless K = 1, which has no history)
-    return stem_history(s, S2R_BUS_REVERB, bus, nullptr, lr ? lr : &none, lr ? count : (count ? (size_t)-1 : 0), "s2r_set_bus_reverb_history");
-}
-
-// ---- per-bus equalisers: the first bus stage, at the head of the chain ----
-static int eq_values(s2r_synth *s, const char *who, uint32_t bus, uint32_t n_bands, const float *coeffs) {
-    if (bus >= S2R_MAX_BUSES || !eq_in_range(n_bands, coeffs))
-        return set_err(s, S2R_ERR_PATCH_RANGE, "%s: bus %u, %u bands: at most %u bands of finite coefficients (b0, b1, b2, a1, a2) with |a2| < 1 and "
-                       "|a1| < 1 + a2, the bus below %u", who, bus, n_bands, S2R_EQ_MAX_BANDS, S2R_MAX_BUSES);
-    return S2R_OK;
-}
-
-int s2r_set_bus_eq(s2r_synth *s, uint32_t bus, uint32_t n_bands, const float *coeffs) {
-    S2R_TRY(eq_values(s, "s2r_set_bus_eq", bus, n_bands, coeffs));
-    S2R_TRY(post_handle(s, "s2r_set_bus_eq", "bus equalisers are"));
-    if (n_bands && !coeffs) return set_err(s, S2R_ERR_INVALID, "s2r_set_bus_eq: %u bands and no coefficients", n_bands);
-    return stem_set(s, "s2r_set_bus_eq", [&](const S2rPostCtx &c) { return s->post.set_eq(c, bus, n_bands, coeffs); });
-}
-
-int s2r_set_bus_eq_coeffs(s2r_synth *s, uint32_t bus, uint32_t n_bands, const float *coeffs) {
-    S2R_TRY(eq_values(s, "s2r_set_bus_eq_coeffs", bus, n_bands, coeffs));
-    S2R_TRY(stem_bus(s, S2R_BUS_EQ, bus, "s2r_set_bus_eq_coeffs", true));
-    S2rPostChain::BusEq &d = s->post.eq[bus];
-    if (n_bands != d.n_bands || !coeffs) return set_err(s, S2R_ERR_INVALID, "s2r_set_bus_eq_coeffs: the EQ of bus %u has %u bands, not %u", bus, d.n_bands, n_bands);
-    std::memcpy(d.c, coeffs, (size_t)n_bands * 5u * sizeof(float));          // (the state stays: the band moves without a restart)
-    return S2R_OK;
-}
-
-int s2r_get_bus_eq(const s2r_synth *s, uint32_t bus, uint32_t *n_bands, float *coeffs, size_t capacity) {
-    if (bus >= S2R_MAX_BUSES) return S2R_ERR_PATCH_RANGE;
-    if (!s || !s->kids.empty() || s->parent) return S2R_ERR_INVALID;
-    const S2rPostChain::BusEq &d = s->post.eq[bus];
-    if (coeffs && capacity < 5u * (size_t)d.n_bands) return S2R_ERR_INVALID;
-    put(n_bands, d.n_bands);
-    if (coeffs) std::memcpy(coeffs, d.c, (size_t)d.n_bands * 5u * sizeof(float));
-    return S2R_OK;
-}
-
-int s2r_get_bus_eq_state(s2r_synth *s, uint32_t bus, float *state, size_t capacity) {
-    return stem_state(s, S2R_BUS_EQ, bus, state, nullptr, capacity, "s2r_get_bus_eq_state");
-}
-
-int s2r_set_bus_eq_state(s2r_synth *s, uint32_t bus, const float *state, size_t count) {
-    return stem_state(s, S2R_BUS_EQ, bus, nullptr, state, state ? count : (size_t)-1, "s2r_set_bus_eq_state");
-}
-
-// ---- per-bus dynamics: the second bus stage, behind the equalisers ----
-static int dyn_values(s2r_synth *s, const char *who, uint32_t bus, uint32_t key_bus, const float *curve, float a_att, float a_rel) {
-    if (bus >= S2R_MAX_BUSES || key_bus >= S2R_MAX_BUSES || !dyn_in_range(curve, a_att, a_rel))
-        return set_err(s, S2R_ERR_PATCH_RANGE, "%s: bus %u, key bus %u, attack %g, release %g: %u finite curve entries in [0, 256], both coefficients in "
-                       "[0, 1), both buses below %u", who, bus, key_bus, (double)a_att, (double)a_rel, S2R_DYN_CURVE_POINTS, S2R_MAX_BUSES);
-    return S2R_OK;
-}
-
-int s2r_set_bus_dynamics(s2r_synth *s, uint32_t bus, uint32_t key_bus, const float *curve, float a_att, float a_rel) {
-    S2R_TRY(dyn_values(s, "s2r_set_bus_dynamics", bus, key_bus, curve, a_att, a_rel));
-    S2R_TRY(post_handle(s, "s2r_set_bus_dynamics", "bus dynamics are"));
-    if (!curve) return set_err(s, S2R_ERR_INVALID, "s2r_set_bus_dynamics: no curve");
-    return stem_set(s, "s2r_set_bus_dynamics", [&](const S2rPostCtx &c) { return s->post.set_dyn(c, bus, key_bus, curve, a_att, a_rel, false); });
-}
-
-int s2r_clear_bus_dynamics(s2r_synth *s, uint32_t bus) {
-    if (bus >= S2R_MAX_BUSES) return set_err(s, S2R_ERR_PATCH_RANGE, "s2r_clear_bus_dynamics: bus %u, below %u", bus, S2R_MAX_BUSES);
-    S2R_TRY(post_handle(s, "s2r_clear_bus_dynamics", "bus dynamics are"));
-    return stem_set(s, "s2r_clear_bus_dynamics", [&](const S2rPostCtx &c) { return s->post.set_dyn(c, bus, 0, nullptr, 0.0f, 0.0f, false); });
-}
-
-int s2r_set_bus_dynamics_params(s2r_synth *s, uint32_t bus, uint32_t key_bus, const float *curve, float a_att, float a_rel) {
-    S2R_TRY(dyn_values(s, "s2r_set_bus_dynamics_params", bus, key_bus, curve, a_att, a_rel));
-    S2R_TRY(stem_bus(s, S2R_BUS_DYN, bus, "s2r_set_bus_dynamics_params", true));
-    if (!curve) return set_err(s, S2R_ERR_INVALID, "s2r_set_bus_dynamics_params: no curve");
-    return stem_set(s, "s2r_set_bus_dynamics_params", [&](const S2rPostCtx &c) { return s->post.set_dyn(c, bus, key_bus, curve, a_att, a_rel, true); });   // (y stays)
-}
-
-int s2r_get_bus_dynamics(const s2r_synth *s, uint32_t bus, uint32_t *present, uint32_t *key_bus, float *curve, size_t capacity, float *a_att, float *a_rel) {
-    if (bus >= S2R_MAX_BUSES) return S2R_ERR_PATCH_RANGE;
-    if (!s || !s->kids.empty() || s->parent) return S2R_ERR_INVALID;
-    const S2rPostChain::BusDyn &d = s->post.dyn[bus];
-    if (d.present() && curve && capacity < S2R_DYN_CURVE_POINTS) return S2R_ERR_INVALID;
-    put(present, d.present() ? 1u : 0u); put(key_bus, d.key); put(a_att, d.a_att); put(a_rel, d.a_rel);
-    if (d.present() && curve) std::memcpy(curve, d.curve.data(), S2R_DYN_CURVE_POINTS * sizeof(float));
-    return S2R_OK;
-}
-
-static int dyn_state(s2r_synth *s, uint32_t bus, float *get, const float *set, size_t count, const char *who) {
-    if (set && count == 1u && !dyn_state_in_range(set[0])) return set_err(s, S2R_ERR_PATCH_RANGE, "%s: a gain of %g: finite and not below 0", who, (double)set[0]);
-    return stem_state(s, S2R_BUS_DYN, bus, get, set, count, who);
-}
-
-int s2r_get_bus_dynamics_state(s2r_synth *s, uint32_t bus, float *state, size_t capacity) {
-    return dyn_state(s, bus, state, nullptr, capacity, "s2r_get_bus_dynamics_state");
-}
-
-int s2r_set_bus_dynamics_state(s2r_synth *s, uint32_t bus, const float *state, size_t count) {
-    return dyn_state(s, bus, nullptr, state, state ? count : (size_t)-1, "s2r_set_bus_dynamics_state");
-}
-
-int s2r_get_bus_dynamics_meter(const s2r_synth *s, uint32_t bus, float *min_gain) {
-    if (bus >= S2R_MAX_BUSES) return S2R_ERR_PATCH_RANGE;
-    if (!s || !s->kids.empty() || s->parent) return S2R_ERR_INVALID;
-    put(min_gain, s->post.dyn[bus].min_gain);
-    return S2R_OK;
-}
-
-// ---- per-bus drives: the third bus stage, behind the dynamics ----
-static int drive_values(s2r_synth *s, const char *who, uint32_t bus, const float *curve, float pre, float dry, float wet) {
-    if (bus >= S2R_MAX_BUSES || !drive_in_range(curve, pre, dry, wet))
-        return set_err(s, S2R_ERR_PATCH_RANGE, "%s: bus %u, pre %g, dry %g, wet %g: %u finite curve entries, pre in [0, %g], dry and wet in [0, 1], the bus below %u",
-                       who, bus, (double)pre, (double)dry, (double)wet, S2R_DRIVE_CURVE_POINTS, (double)S2R_DRIVE_MAX_PRE, S2R_MAX_BUSES);
-    return S2R_OK;
-}
-
-int s2r_set_bus_drive(s2r_synth *s, uint32_t bus, const float *curve, float pre, float dry, float wet) {
-    S2R_TRY(drive_values(s, "s2r_set_bus_drive", bus, curve, pre, dry, wet));
-    S2R_TRY(post_handle(s, "s2r_set_bus_drive", kStemWords[S2R_BUS_DRIVE].are));
-    if (!curve) return set_err(s, S2R_ERR_INVALID, "s2r_set_bus_drive: no curve");
-    return stem_set(s, "s2r_set_bus_drive", [&](const S2rPostCtx &c) { return s->post.set_drive(c, bus, curve, pre, dry, wet, false); });
-}
-
-int s2r_clear_bus_drive(s2r_synth *s, uint32_t bus) {
-    if (bus >= S2R_MAX_BUSES) return set_err(s, S2R_ERR_PATCH_RANGE, "s2r_clear_bus_drive: bus %u, below %u", bus, S2R_MAX_BUSES);
-    S2R_TRY(post_handle(s, "s2r_clear_bus_drive", kStemWords[S2R_BUS_DRIVE].are));
-    return stem_set(s, "s2r_clear_bus_drive", [&](const S2rPostCtx &c) { return s->post.set_drive(c, bus, nullptr, -1.0f, 0.0f, 0.0f, false); });
-}
-
-int s2r_set_bus_drive_params(s2r_synth *s, uint32_t bus, const float *curve, float pre, float dry, float wet) {
-    S2R_TRY(drive_values(s, "s2r_set_bus_drive_params", bus, curve, pre, dry, wet));
-    S2R_TRY(stem_bus(s, S2R_BUS_DRIVE, bus, "s2r_set_bus_drive_params", true));
-    return stem_set(s, "s2r_set_bus_drive_params", [&](const S2rPostCtx &c) { return s->post.set_drive(c, bus, curve, pre, dry, wet, true); });   // (the history stays)
-}
-
-int s2r_get_bus_drive(const s2r_synth *s, uint32_t bus, uint32_t *present, float *curve, size_t capacity, float *pre, float *dry, float *wet) {
-    S2R_TRY(stem_bus(s, S2R_BUS_DRIVE, bus, nullptr, false));
-    const S2rPostChain::BusDrive &d = s->post.drive[bus];
-    if (d.present() && curve && capacity < S2R_DRIVE_CURVE_POINTS) return S2R_ERR_INVALID;
-    put(present, d.present() ? 1u : 0u); put(pre, d.pre); put(dry, d.dry); put(wet, d.wet);
-    if (d.present() && curve) std::memcpy(curve, d.curve.data(), S2R_DRIVE_CURVE_POINTS * sizeof(float));
-    return S2R_OK;
-}
-
-// the checkpoint pair: the room's state pair's checks, then the stem stages' copy
-static int drive_history(s2r_synth *s, uint32_t bus, float *get, const float *set, size_t count, const char *who) {
-    S2R_TRY(stem_bus(s, S2R_BUS_DRIVE, bus, who, true));
-    const size_t n = 2u * S2R_DRIVE_HISTORY;
-    if (set ? count != n : count < n) return set_err(s, S2R_ERR_INVALID, "%s: the history of bus %u is %zu floats, not %zu", who, bus, n, count);
-    if (!get && !set) return set_err(s, S2R_ERR_INVALID, "%s: null buffer", who);
-    if (set) for (size_t k = 0; k < n; k++) if (!std::isfinite(set[k])) return set_err(s, S2R_ERR_PATCH_RANGE, "%s: value %zu of the history is not finite", who, k);
-    return stem_history(s, S2R_BUS_DRIVE, bus, get, set, count, who);
-}
-
-int s2r_get_bus_drive_history(s2r_synth *s, uint32_t bus, float *lr, size_t capacity) {
-    return drive_history(s, bus, lr, nullptr, capacity, "s2r_get_bus_drive_history");
-}
-
-int s2r_set_bus_drive_history(s2r_synth *s, uint32_t bus, const float *lr, size_t count) {
-    return drive_history(s, bus, nullptr, lr, lr ? count : (size_t)-1, "s2r_set_bus_drive_history");
-}
-
-// ---- per-bus flangers: the fourth bus stage, behind the drives and in front of the choruses ----
-static int flanger_levels(s2r_synth *s, const char *who, uint32_t bus, float feedback, float cross, float dry, float wet) {
-    if (bus >= S2R_MAX_BUSES || !delay_mix_in_range(feedback, cross, dry, wet))
-        return set_err(s, S2R_ERR_PATCH_RANGE, "%s: bus %u, feedback %g, cross %g, dry %g, wet %g: feedback and cross in [-1, 1] with |feedback| + |cross| <= 1, dry and "
-                       "wet in [0, 1], the bus below %u", who, bus, (double)feedback, (double)cross, (double)dry, (double)wet, S2R_MAX_BUSES);
-    return S2R_OK;
-}
-
-int s2r_set_bus_flanger(s2r_synth *s, uint32_t bus, float base, float depth, uint32_t phase_inc, uint32_t spread, float feedback, float cross, float dry,
-                        float wet) {
-    if (!flanger_delay_in_range(base, depth))
-        return set_err(s, S2R_ERR_PATCH_RANGE, "s2r_set_bus_flanger: bus %u, base %g, depth %g: base >= %g and depth >= 0 with base + depth <= %g frames", bus,
-                       (double)base, (double)depth, (double)S2R_FLANGER_MIN_DELAY, (double)S2R_FLANGER_MAX_DELAY);
-    S2R_TRY(flanger_levels(s, "s2r_set_bus_flanger", bus, feedback, cross, dry, wet));
-    S2R_TRY(post_handle(s, "s2r_set_bus_flanger", kStemWords[S2R_BUS_FLANGER].are));
-    return stem_set(s, "s2r_set_bus_flanger", [&](const S2rPostCtx &c) { return s->post.set_flanger(c, bus, base, depth, phase_inc, spread, feedback, cross, dry, wet); });
-}
-
-int s2r_clear_bus_flanger(s2r_synth *s, uint32_t bus) {
-    if (bus >= S2R_MAX_BUSES) return set_err(s, S2R_ERR_PATCH_RANGE, "s2r_clear_bus_flanger: bus %u, below %u", bus, S2R_MAX_BUSES);
-    S2R_TRY(post_handle(s, "s2r_clear_bus_flanger", kStemWords[S2R_BUS_FLANGER].are));
-    return stem_set(s, "s2r_clear_bus_flanger", [&](const S2rPostCtx &c) { return s->post.set_flanger(c, bus, -1.0f, 0.0f, 0, 0, 0.0f, 0.0f, 0.0f, 0.0f); });
-}
-
-int s2r_set_bus_flanger_params(s2r_synth *s, uint32_t bus, uint32_t phase_inc, uint32_t spread, float feedback, float cross, float dry, float wet) {
-    S2R_TRY(flanger_levels(s, "s2r_set_bus_flanger_params", bus, feedback, cross, dry, wet));
-    S2R_TRY(stem_bus(s, S2R_BUS_FLANGER, bus, "s2r_set_bus_flanger_params", true));
-    S2rPostChain::BusFlanger &d = s->post.flanger[bus];          // (the phase and the line stay: the LFO bends, the comb retunes, nothing clicks)
-    d.phase_inc = phase_inc; d.spread = spread; d.feedback = feedback; d.cross = cross; d.dry = dry; d.wet = wet;
-    return S2R_OK;
-}
-
-int s2r_get_bus_flanger(const s2r_synth *s, uint32_t bus, float *base, float *depth, uint32_t *phase_inc, uint32_t *spread, float *feedback, float *cross,
-                        float *dry, float *wet) {
-    S2R_TRY(stem_bus(s, S2R_BUS_FLANGER, bus, nullptr, false));
-    const S2rPostChain::BusFlanger &d = s->post.flanger[bus];
-    put(base, d.base); put(depth, d.depth); put(phase_inc, d.phase_inc); put(spread, d.spread); put(feedback, d.feedback); put(cross, d.cross);
-    put(dry, d.dry); put(wet, d.wet);
-    return S2R_OK;
-}
-
-// (the flanger's phase lives on the host, as the chorus's)
-int s2r_get_bus_flanger_state(s2r_synth *s, uint32_t bus, float *lr, size_t capacity, uint32_t *phase) {
-    S2R_TRY(stem_history(s, S2R_BUS_FLANGER, bus, lr, nullptr, capacity, "s2r_get_bus_flanger_state"));
-    put(phase, s->post.flanger[bus].phase);
-    return S2R_OK;
-}
-
-int s2r_set_bus_flanger_state(s2r_synth *s, uint32_t bus, const float *lr, size_t count, uint32_t phase) {
-    S2R_TRY(stem_history(s, S2R_BUS_FLANGER, bus, nullptr, lr, lr ? count : (size_t)-1, "s2r_set_bus_flanger_state"));
-    s->post.flanger[bus].phase = phase;
-    return S2R_OK;
-}
-
-// ---- per-bus rooms: the last bus stage, behind the reverbs ----
-static int room_levels(s2r_synth *s, const char *who, uint32_t bus, float feedback, float damp, float g, float gain, float dry, float wet, float cross) {
-    if (bus >= S2R_MAX_BUSES || !room_levels_in_range(feedback, damp, g, gain, dry, wet, cross))
-        return set_err(s, S2R_ERR_PATCH_RANGE, "%s: bus %u, feedback %g, damp %g, g %g, gain %g, dry %g, wet %g, cross %g: feedback in [0, 1), g in (-1, 1), "
-                       "the others in [0, 1], the bus below %u", who, bus, (double)feedback, (double)damp, (double)g, (double)gain, (double)dry, (double)wet,
-                       (double)cross, S2R_MAX_BUSES);
-    return S2R_OK;
-}
-
-int s2r_set_bus_room(s2r_synth *s, uint32_t bus, const uint32_t *cd, const uint32_t *ad, uint32_t spread, float feedback, float damp, float g, float gain,
-                     float dry, float wet, float cross) {
-    S2R_TRY(room_levels(s, "s2r_set_bus_room", bus, feedback, damp, g, gain, dry, wet, cross));
-    if (!room_delays_in_range(cd, ad, spread))
-        return set_err(s, S2R_ERR_PATCH_RANGE, "s2r_set_bus_room: bus %u, spread %u: every delay, and every delay plus the spread, in [%u, %u]", bus, spread,
-                       S2R_ROOM_MIN_DELAY, S2R_ROOM_MAX_DELAY);
-    S2R_TRY(post_handle(s, "s2r_set_bus_room", "bus rooms are"));
-    if (!cd || !ad) return set_err(s, S2R_ERR_INVALID, "s2r_set_bus_room: no delays");
-    const float levels[7] = {feedback, damp, g, gain, dry, wet, cross};
-    return stem_set(s, "s2r_set_bus_room", [&](const S2rPostCtx &c) { return s->post.set_room(c, bus, cd, ad, spread, levels); });
-}
-
-int s2r_clear_bus_room(s2r_synth *s, uint32_t bus) {
-    if (bus >= S2R_MAX_BUSES) return set_err(s, S2R_ERR_PATCH_RANGE, "s2r_clear_bus_room: bus %u, below %u", bus, S2R_MAX_BUSES);
-    S2R_TRY(post_handle(s, "s2r_clear_bus_room", "bus rooms are"));
-    return stem_set(s, "s2r_clear_bus_room", [&](const S2rPostCtx &c) { return s->post.set_room(c, bus, nullptr, nullptr, 0, nullptr); });
-}
-
-int s2r_set_bus_room_params(s2r_synth *s, uint32_t bus, float feedback, float damp, float g, float gain, float dry, float wet, float cross) {
-    S2R_TRY(room_levels(s, "s2r_set_bus_room_params", bus, feedback, damp, g, gain, dry, wet, cross));
-    S2R_TRY(stem_bus(s, S2R_BUS_ROOM, bus, "s2r_set_bus_room_params", true));
-    const float levels[7] = {feedback, damp, g, gain, dry, wet, cross};
-    return stem_set(s, "s2r_set_bus_room_params", [&](const S2rPostCtx &) { s->post.set_room_params(bus, levels); return hipSuccess; });   // (the state stays)
-}
-
-int s2r_get_bus_room(const s2r_synth *s, uint32_t bus, uint32_t *present, uint32_t *cd, uint32_t *ad, uint32_t *spread, float *levels) {
-    if (bus >= S2R_MAX_BUSES) return S2R_ERR_PATCH_RANGE;
-    if (!s || !s->kids.empty() || s->parent) return S2R_ERR_INVALID;
-    const S2rPostChain::BusRoom &f = s->post.room[bus];
-    put(present, f.present() ? 1u : 0u); put(spread, f.spread);
-    if (cd) std::memcpy(cd, f.cd, sizeof f.cd);
-    if (ad) std::memcpy(ad, f.ad, sizeof f.ad);
-    if (levels) { const float l[7] = {f.feedback, f.damp, f.g, f.gain, f.dry, f.wet, f.cross}; std::memcpy(levels, l, sizeof l); }
-    return S2R_OK;
-}
-
-// a room's state coming in is finite throughout
-static int room_state_finite(s2r_synth *s, const float *set, size_t n, const char *who) {
-    for (size_t k = 0; k < n; k++) if (!std::isfinite(set[k])) return set_err(s, S2R_ERR_PATCH_RANGE, "%s: value %zu of the state is not finite", who, k);
-    return S2R_OK;
-}
-
-int s2r_get_bus_room_state(s2r_synth *s, uint32_t bus, float *state, size_t capacity) {
-    return stem_state(s, S2R_BUS_ROOM, bus, state, nullptr, capacity, "s2r_get_bus_room_state");
-}
-
-int s2r_set_bus_room_state(s2r_synth *s, uint32_t bus, const float *state, size_t count) {
-    return stem_state(s, S2R_BUS_ROOM, bus, nullptr, state, state ? count : (size_t)-1, "s2r_set_bus_room_state", room_state_finite);
-}
-
-// ---- per-bus choruses: in front of the delays ----
-int s2r_set_bus_chorus(s2r_synth *s, uint32_t bus, uint32_t voices, float base, float depth, uint32_t phase_inc, uint32_t spread, float dry, float wet) {
-    if ((voices && !chorus_in_range(voices, base, depth, dry, wet)) || bus >= S2R_MAX_BUSES)
-        return set_err(s, S2R_ERR_PATCH_RANGE, "bus %u: a chorus of %u voices, base %g, depth %g, dry %g, wet %g: at most %u voices, base >= 1 and depth >= 0 with "
-                       "base + depth <= %g frames, dry and wet in [0, 1], the bus below %u", bus, voices, (double)base, (double)depth, (double)dry, (double)wet,
-                       S2R_CHORUS_MAX_VOICES, (double)S2R_CHORUS_MAX_DELAY, S2R_MAX_BUSES);
-    S2R_TRY(post_handle(s, "s2r_set_bus_chorus", "bus choruses are"));
-    return stem_set(s, "s2r_set_bus_chorus", [&](const S2rPostCtx &c) { return s->post.set_chorus(c, bus, voices, base, depth, phase_inc, spread, dry, wet); });
-}
-
-int s2r_set_bus_chorus_mix(s2r_synth *s, uint32_t bus, float dry, float wet) {
-    if (!chorus_mix_in_range(dry, wet) || bus >= S2R_MAX_BUSES)
-        return set_err(s, S2R_ERR_PATCH_RANGE, "bus %u: dry %g, wet %g: dry and wet lie in [0, 1], the bus below %u", bus, (double)dry, (double)wet, S2R_MAX_BUSES);
-    S2R_TRY(stem_bus(s, S2R_BUS_CHORUS, bus, "s2r_set_bus_chorus_mix", false));
-    s->post.chorus[bus].dry = dry; s->post.chorus[bus].wet = wet;
-    return S2R_OK;
-}
-
-int s2r_set_bus_chorus_rate(s2r_synth *s, uint32_t bus, uint32_t phase_inc, uint32_t spread) {
-    S2R_TRY(stem_bus(s, S2R_BUS_CHORUS, bus, "s2r_set_bus_chorus_rate", false));
-    s->post.chorus[bus].phase_inc = phase_inc; s->post.chorus[bus].spread = spread;      // (the phase and the history stay: the LFO bends, nothing clicks)
-    return S2R_OK;
-}
-
-int s2r_get_bus_chorus(const s2r_synth *s, uint32_t bus, uint32_t *voices, float *base, float *depth, uint32_t *phase_inc, uint32_t *spread, float *dry,
-                       float *wet) {
-    S2R_TRY(stem_bus(s, S2R_BUS_CHORUS, bus, nullptr, false));
-    const S2rPostChain::BusChorus &d = s->post.chorus[bus];
-    put(voices, d.voices); put(base, d.base); put(depth, d.depth); put(phase_inc, d.phase_inc); put(spread, d.spread); put(dry, d.dry); put(wet, d.wet);
-    return S2R_OK;
-}
-
-// (the chorus's phase lives on the host)
-int s2r_get_bus_chorus_state(s2r_synth *s, uint32_t bus, float *lr, size_t capacity, uint32_t *phase) {
-    S2R_TRY(stem_history(s, S2R_BUS_CHORUS, bus, lr, nullptr, capacity, "s2r_get_bus_chorus_state"));
-    put(phase, s->post.chorus[bus].phase);
-    return S2R_OK;
-}
-
-int s2r_set_bus_chorus_state(s2r_synth *s, uint32_t bus, const float *lr, size_t count, uint32_t phase) {
-    S2R_TRY(stem_history(s, S2R_BUS_CHORUS, bus, nullptr, lr, lr ? count : (size_t)-1, "s2r_set_bus_chorus_state"));
-    s->post.chorus[bus].phase = phase;
-    return S2R_OK;
-}
-
-// ---- per-bus feedback delays: in front of the reverbs ----
-int s2r_set_bus_delay(s2r_synth *s, uint32_t bus, uint32_t delay_frames, float feedback, float cross, float dry, float wet) {
-    if (!delay_mix_in_range(feedback, cross, dry, wet) || delay_frames > S2R_MAX_DELAY_FRAMES || bus >= S2R_MAX_BUSES)
-        return set_err(s, S2R_ERR_PATCH_RANGE, "bus %u: a delay of %u frames, feedback %g, cross %g, dry %g, wet %g: feedback and cross lie in [-1, 1] with "
-                       "|feedback| + |cross| <= 1, dry and wet in [0, 1], at most %u frames, the bus below %u", bus, delay_frames, (double)feedback, (double)cross,
-                       (double)dry, (double)wet, S2R_MAX_DELAY_FRAMES, S2R_MAX_BUSES);
-    S2R_TRY(post_handle(s, "s2r_set_bus_delay", "bus delays are"));
-    return stem_set(s, "s2r_set_bus_delay", [&](const S2rPostCtx &c) { return s->post.set_delay(c, bus, delay_frames, feedback, cross, dry, wet); });
-}
-
-int s2r_set_bus_delay_mix(s2r_synth *s, uint32_t bus, float feedback, float cross, float dry, float wet) {
-    if (!delay_mix_in_range(feedback, cross, dry, wet) || bus >= S2R_MAX_BUSES)
-        return set_err(s, S2R_ERR_PATCH_RANGE, "bus %u: feedback %g, cross %g, dry %g, wet %g: feedback and cross lie in [-1, 1] with |feedback| + |cross| <= 1, "
-                       "dry and wet in [0, 1], the bus below %u", bus, (double)feedback, (double)cross, (double)dry, (double)wet, S2R_MAX_BUSES);
-    S2R_TRY(stem_bus(s, S2R_BUS_DELAY, bus, "s2r_set_bus_delay_mix", false));
-    S2rPostChain::BusDelay &d = s->post.delay[bus];
-    d.feedback = feedback; d.cross = cross; d.dry = dry; d.wet = wet;
-    return S2R_OK;
-}
-
-int s2r_get_bus_delay(const s2r_synth *s, uint32_t bus, uint32_t *delay_frames, float *feedback, float *cross, float *dry, float *wet) {
-    S2R_TRY(stem_bus(s, S2R_BUS_DELAY, bus, nullptr, false));
-    const S2rPostChain::BusDelay &d = s->post.delay[bus];
-    put(delay_frames, d.history); put(feedback, d.feedback); put(cross, d.cross); put(dry, d.dry); put(wet, d.wet);
-    return S2R_OK;
-}
-
-int s2r_get_bus_delay_history(s2r_synth *s, uint32_t bus, float *lr, size_t capacity) {
-    return stem_history(s, S2R_BUS_DELAY, bus, lr, nullptr, capacity, "s2r_get_bus_delay_history");
-}
-
-int s2r_set_bus_delay_history(s2r_synth *s, uint32_t bus, const float *lr, size_t count) {
-    return stem_history(s, S2R_BUS_DELAY, bus, nullptr, lr, lr ? count : (size_t)-1, "s2r_set_bus_delay_history");
-}
-
-// ---- program faders ----
-int s2r_set_program_fader(s2r_synth *s, uint32_t program, float fader, float pan_shift) {
-    // (the values first, like s2r_set_program_pan)
-    if (!fader_in_range(fader, pan_shift))
-        return set_err(s, S2R_ERR_PATCH_RANGE, "program %u: fader %g, pan_shift %g: the fader lies in [0, 1], the shift in [-2, 2]", program, (double)fader, (double)pan_shift);
-    if (!s) return S2R_ERR_INVALID;
-    if (!s->kids.empty() || s->parent) return set_err(s, S2R_ERR_INVALID, "program faders are kept by single-device handles, not by a device list");
-    if (program >= s->bank.size()) return set_err(s, S2R_ERR_INVALID, "program %u: the bank holds %zu patches", program, s->bank.size());
-    if (fader != 1.0f || pan_shift != 0.0f) {
-        S2R_REFUSE_BROKEN(s);
-        S2R_TRY(mixer_begin(s, kMixFader));
-    }
-    s->mixer.prog[program].fader = fader; s->mixer.prog[program].shift = pan_shift;
-    return S2R_OK;
-}
-
-int s2r_get_program_fader(const s2r_synth *s, uint32_t program, float *fader, float *pan_shift, float *applied_fader, float *applied_pan_shift) {
-    if (!s) return S2R_ERR_INVALID;
-    if (!s->kids.empty() || s->parent || program >= s->bank.size()) return S2R_ERR_INVALID;
-    const s2r_synth::ProgramMix &p = s->mixer.prog[program];
-    if (fader) *fader = p.fader;
-    if (pan_shift) *pan_shift = p.shift;
-    if (applied_fader) *applied_fader = p.fader_app;
-    if (applied_pan_shift) *applied_pan_shift = p.shift_app;
-    return S2R_OK;
-}
-
-int s2r_snap_program_faders(s2r_synth *s) {
-    if (!s) return S2R_ERR_INVALID;
-    if (!s->kids.empty() || s->parent) return set_err(s, S2R_ERR_INVALID, "program faders are kept by single-device handles, not by a device list");
-    snap_faders(s);
-    s->gains_dirty |= kGainsBus;
-    return S2R_OK;
-}
-
-int s2r_fill_buses(s2r_synth *s, float *out, size_t capacity, uint32_t n_buses, size_t frames, uint32_t sample_rate_hz) {
-    if (!s) return S2R_ERR_INVALID;
-    if (n_buses == 0 || n_buses > S2R_MAX_BUSES) return set_err(s, S2R_ERR_INVALID, "s2r_fill_buses: %u buses (1 .. %u)", n_buses, S2R_MAX_BUSES);
-    return fill_rows_mixed(s, out, capacity, n_buses, frames, sample_rate_hz, "s2r_fill_buses");
-}
-
-// ---- the master section ----
-int s2r_set_bus_return(s2r_synth *s, uint32_t bus, float level) {
-    if (!unit_in_range(level) || bus >= S2R_MAX_BUSES)
-        return set_err(s, S2R_ERR_PATCH_RANGE, "bus %u: return %g: the level lies in [0, 1], the bus below %u", bus, (double)level, S2R_MAX_BUSES);
-    S2R_TRY(post_handle(s, "s2r_set_bus_return", "the master section is"));
-    s->post.master.ret[bus] = level;
-    return S2R_OK;
-}
-
-int s2r_get_bus_return(const s2r_synth *s, uint32_t bus, float *level, float *applied) {
-    if (bus >= S2R_MAX_BUSES) return S2R_ERR_PATCH_RANGE;
-    if (!s || !s->kids.empty() || s->parent) return S2R_ERR_INVALID;
-    put(level, s->post.master.ret[bus]); put(applied, s->post.master.ret_app[bus]);
-    return S2R_OK;
-}
-
-int s2r_set_master_fader(s2r_synth *s, float level) {
-    if (!unit_in_range(level)) return set_err(s, S2R_ERR_PATCH_RANGE, "master fader %g: the level lies in [0, 1]", (double)level);
-    S2R_TRY(post_handle(s, "s2r_set_master_fader", "the master section is"));
-    s->post.master.fader = level;
-    return S2R_OK;
-}
-
-int s2r_get_master_fader(const s2r_synth *s, float *level, float *applied) {
-    if (!s || !s->kids.empty() || s->parent) return S2R_ERR_INVALID;
-    put(level, s->post.master.fader); put(applied, s->post.master.fader_app);
-    return S2R_OK;
-}
-
-int s2r_snap_master(s2r_synth *s) {
-    S2R_TRY(post_handle(s, "s2r_snap_master", "the master section is"));
-    s->post.snap_master();
-    return S2R_OK;
-}
-
-int s2r_fill_master(s2r_synth *s, float *master_lr, float *stems, size_t stems_capacity, uint32_t n_buses, size_t frames, uint32_t sample_rate_hz) {
-    if (!s) return S2R_ERR_INVALID;
-    if (n_buses == 0 || n_buses > S2R_MAX_BUSES) return set_err(s, S2R_ERR_INVALID, "s2r_fill_master: %u buses (1 .. %u)", n_buses, S2R_MAX_BUSES);
-    return fill_rows_mixed(s, stems, stems_capacity, n_buses, frames, sample_rate_hz, "s2r_fill_master", true, master_lr);
-}
-
-int s2r_get_meters(const s2r_synth *s, uint32_t *n_buses, float *peak, float *energy, size_t capacity) {
-    if (!s || !s->kids.empty() || s->parent || !s->post.master.metered) return S2R_ERR_INVALID;
-    const S2rPostChain::Master &ms = s->post.master;
-    const size_t n = ((size_t)ms.meter_buses + 1u) * 2u;
-    if (capacity < n) return S2R_ERR_INVALID;
-    if (n_buses) *n_buses = ms.meter_buses;
-    if (peak) std::memcpy(peak, ms.peak, n * sizeof(float));
-    if (energy) std::memcpy(energy, ms.energy, n * sizeof(float));
-    return S2R_OK;
-}
-
-// ---- the master limiter ----
-int s2r_set_master_limiter(s2r_synth *s, float ceiling, uint32_t lookahead, uint32_t hold) {
-    if (!limiter_in_range(ceiling, lookahead, hold))
-        return set_err(s, S2R_ERR_PATCH_RANGE, "master limiter: ceiling %g, lookahead %u, hold %u: the ceiling lies in [2^-%d, 2^%d], the lookahead in 1 .. %u, the hold in 0 .. %u",
-                       (double)ceiling, lookahead, hold, S2R_LIMITER_CEILING_LOG2, S2R_LIMITER_CEILING_LOG2, S2R_LIMITER_MAX_LOOKAHEAD, S2R_LIMITER_MAX_HOLD);
-    S2R_TRY(post_handle(s, "s2r_set_master_limiter", "the master limiter is"));
-    s->post.set_limiter(ceiling, lookahead, hold);
-    return S2R_OK;
-}
-
-int s2r_clear_master_limiter(s2r_synth *s) {
-    S2R_TRY(post_handle(s, "s2r_clear_master_limiter", "the master limiter is"));
-    s->post.set_limiter(0.0f, 0, 0);
-    return S2R_OK;
-}
-
-int s2r_get_master_limiter(const s2r_synth *s, float *ceiling, uint32_t *lookahead, uint32_t *hold) {
-    if (!s || !s->kids.empty() || s->parent) return S2R_ERR_INVALID;
-    put(ceiling, s->post.limiter.ceiling); put(lookahead, s->post.limiter.lookahead); put(hold, s->post.limiter.hold);
-    return S2R_OK;
-}
-
-// A master stage's state for a getter: where the device holds it, it is fetched once into the stage's host copy, and kept until the next fill.
-static int mirror_fetch(s2r_synth *s, S2rMirror &m, const char *who) {
-    if (m.host_valid) return S2R_OK;
-    if (s->ring_count) return set_err(s, S2R_ERR_INVALID, "%s with fills of s2r_fill_begin in flight: s2r_fill_end first", who);
-    S2R_QUIESCE(s);
-    S2R_HIP(s, hipSetDevice(s->device));
-    S2R_HIP(s, m.fetch(s->stream));
-    return S2R_OK;
-}
-
-static int limiter_state(s2r_synth *s, float *get_x, float *get_g, const float *set_x, const float *set_g, size_t n_x, size_t n_g, const char *who) {
-    S2R_TRY(post_handle(s, who, "the master limiter is"));
-    S2rPostChain::Limiter &lm = s->post.limiter;
-    if (!lm.lookahead) return set_err(s, S2R_ERR_INVALID, "%s: no master limiter is set", who);
-    const size_t nx = lm.n_x(), ng = lm.n_g();
-    const bool set = set_x || set_g;
-    if (set ? (n_x != nx || n_g != ng) : (n_x < nx || n_g < ng))
-        return set_err(s, S2R_ERR_INVALID, "%s: the state is %zu and %zu floats, not %zu and %zu", who, nx, ng, n_x, n_g);
-    if (set ? (!set_x || !set_g) : (!get_x || !get_g)) return set_err(s, S2R_ERR_INVALID, "%s: null buffer", who);
-    if (set) {
-        for (size_t i = 0; i < ng; i++)
-            if (!unit_in_range(set_g[i])) return set_err(s, S2R_ERR_PATCH_RANGE, "%s: gain %zu is %g, outside [0, 1]", who, i, (double)set_g[i]);
-        s->post.set_limiter_state(set_x, set_g);
-        return S2R_OK;
-    }
-    S2R_TRY(mirror_fetch(s, lm.state, who));
-    std::memcpy(get_x, lm.state.host.data(), nx * sizeof(float));
-    std::memcpy(get_g, lm.state.host.data() + nx, ng * sizeof(float));
-    return S2R_OK;
-}
-
-int s2r_get_limiter_state(s2r_synth *s, float *xh, size_t n_x, float *gh, size_t n_g) { return limiter_state(s, xh, gh, nullptr, nullptr, n_x, n_g, "s2r_get_limiter_state"); }
-
-int s2r_set_limiter_state(s2r_synth *s, const float *xh, size_t n_x, const float *gh, size_t n_g) {
-    if (!s) return S2R_ERR_INVALID;
-    if (!xh || !gh) return set_err(s, S2R_ERR_INVALID, "s2r_set_limiter_state: null buffer");
-    return limiter_state(s, nullptr, nullptr, xh, gh, n_x, n_g, "s2r_set_limiter_state");
-}
-
-int s2r_get_limiter_meters(const s2r_synth *s, float *min_gain, float *out_peak) {
-    if (!s || !s->kids.empty() || s->parent || !s->post.limiter.metered) return S2R_ERR_INVALID;
-    put(min_gain, s->post.limiter.min_gain); put(out_peak, s->post.limiter.out_peak);
-    return S2R_OK;
-}
-
-// ---- what the entries of the two meters behind the limiter share: their guard, their state pair and their rows pair ----
-enum { kLoudness, kSpectrum };
-static const struct { const char *are, *none, *rows; } kMeterWords[2] = {{"the loudness meter is", "no loudness meter is set", "hops"},
-                                                                         {"the spectrum meter is", "no spectrum meter is set", "rows"}};
-struct Meter { S2rMirror *state; S2rRowStore *kept; size_t floats; uint32_t *pos, hop; };        // a meter that is set, as far as the two are alike
-
-// the guard of the entries that need the meter set
-static int meter_on(const s2r_synth *s, int which, const char *who, Meter *m = nullptr) {
-    S2R_TRY(post_handle(s, who, kMeterWords[which].are));
-    S2rPostChain &p = const_cast<s2r_synth *>(s)->post;
-    const Meter is = which == kLoudness ? Meter{&p.loud.state, &p.loud.kept, S2R_LOUDNESS_STATE, &p.loud.pos, p.loud.hop}
-                                        : Meter{&p.spec.state, &p.spec.kept, S2R_SPECTRUM_STATE(p.spec.n_fft), &p.spec.pos, p.spec.hop};
-    if (!is.hop) return set_err(const_cast<s2r_synth *>(s), S2R_ERR_INVALID, "%s: %s", who, kMeterWords[which].none);
-    if (m) *m = is;
-    return S2R_OK;
-}
-
-static int meter_get_state(s2r_synth *s, int which, float *state, size_t capacity, uint32_t *pos, const char *who) {
-    Meter m;
-    S2R_TRY(meter_on(s, which, who, &m));
-    if (capacity < m.floats) return set_err(s, S2R_ERR_INVALID, "%s: the state is %zu floats, not %zu", who, m.floats, capacity);
-    if (!state) return set_err(s, S2R_ERR_INVALID, "%s: null buffer", who);
-    S2R_TRY(mirror_fetch(s, *m.state, who));
-    std::memcpy(state, m.state->host.data(), m.floats * sizeof(float));
-    put(pos, *m.pos);
-    return S2R_OK;
-}
-
-static int meter_set_state(s2r_synth *s, int which, const float *state, size_t count, uint32_t pos, const char *who) {
-    Meter m;
-    S2R_TRY(meter_on(s, which, who, &m));
-    if (count != m.floats) return set_err(s, S2R_ERR_INVALID, "%s: the state is %zu floats, not %zu", who, m.floats, count);
-    if (!state) return set_err(s, S2R_ERR_INVALID, "%s: null buffer", who);
-    if (pos >= m.hop) return set_err(s, S2R_ERR_PATCH_RANGE, "%s: position %u, below the hop of %u", who, pos, m.hop);
-    m.state->set(state, m.floats);
-    *m.pos = pos;
-    return S2R_OK;
-}
-
-static int meter_get_rows(const s2r_synth *s, int which, float *rows, size_t capacity, size_t *n_rows, const char *who) {
-    Meter m;
-    S2R_TRY(meter_on(s, which, who, &m));
-    const size_t n = m.kept->n_rows() * m.kept->width;
-    if (capacity < n || (n && !rows))
-        return set_err(const_cast<s2r_synth *>(s), S2R_ERR_INVALID, "%s: the rows are %zu floats, the buffer holds %zu", who, n, rows ? capacity : (size_t)0);
-    if (n) std::memcpy(rows, m.kept->stored(), n * sizeof(float));
-    put(n_rows, m.kept->n_rows());
-    return S2R_OK;
-}
-
-static int meter_set_rows(s2r_synth *s, int which, const float *rows, size_t n_rows, size_t count, const char *who) {
-    Meter m;
-    S2R_TRY(meter_on(s, which, who, &m));
-    const char *const word = kMeterWords[which].rows;
-    if (n_rows > m.kept->max_rows) return set_err(s, S2R_ERR_PATCH_RANGE, "%s: %zu %s, at most the %u the meter keeps", who, n_rows, word, m.kept->max_rows);
-    if (count != n_rows * m.kept->width || (count && !rows))
-        return set_err(s, S2R_ERR_INVALID, "%s: %zu %s are %zu floats, not %zu", who, n_rows, word, n_rows * m.kept->width, rows ? count : (size_t)0);
-    m.kept->assign(rows, n_rows);
-    return S2R_OK;
-}
-
-// ---- the loudness and true-peak meters behind the limiter ----
-int s2r_set_master_loudness(s2r_synth *s, const float coeffs[10], uint32_t hop, uint32_t max_hops) {
-    if (!loudness_in_range(coeffs, hop, max_hops))
-        return set_err(s, S2R_ERR_PATCH_RANGE, "master loudness: hop %u, %u hops: ten finite coefficients, the hop in %u .. %u, the hops kept in %u .. %u", hop, max_hops,
-                       S2R_LOUDNESS_MIN_HOP, S2R_LOUDNESS_MAX_HOP, S2R_LOUDNESS_MIN_HOPS, S2R_LOUDNESS_MAX_HOPS);
-    S2R_TRY(post_handle(s, "s2r_set_master_loudness", "the loudness meter is"));
-    if (!coeffs) return set_err(s, S2R_ERR_INVALID, "s2r_set_master_loudness: no coefficients");
-    s->post.set_loudness(coeffs, hop, max_hops);
-    return S2R_OK;
-}
-
-int s2r_clear_master_loudness(s2r_synth *s) {
-    S2R_TRY(post_handle(s, "s2r_clear_master_loudness", "the loudness meter is"));
-    s->post.set_loudness(nullptr, 0, 0);
-    return S2R_OK;
-}
-
-int s2r_get_master_loudness(const s2r_synth *s, float coeffs[10], uint32_t *hop, uint32_t *max_hops, size_t *n_hops) {
-    if (!s || !s->kids.empty() || s->parent) return S2R_ERR_INVALID;
-    const S2rPostChain::Loudness &ld = s->post.loud;
-    if (coeffs) std::memcpy(coeffs, ld.c, sizeof ld.c);
-    put(hop, ld.hop); put(max_hops, ld.kept.max_rows); put(n_hops, ld.kept.n_rows());
-    return S2R_OK;
-}
-
-int s2r_reset_master_loudness(s2r_synth *s) {
-    S2R_TRY(meter_on(s, kLoudness, "s2r_reset_master_loudness"));
-    s->post.reset_loudness();
-    return S2R_OK;
-}
-
-int s2r_get_loudness(const s2r_synth *s, uint32_t programme, double out[3]) {
-    if (programme >= S2R_LOUDNESS_PROGRAMMES) return S2R_ERR_PATCH_RANGE;
-    if (!s || !s->kids.empty() || s->parent || !s->post.loud.hop || !out) return S2R_ERR_INVALID;
-    const S2rPostChain::Loudness &ld = s->post.loud;
-    return s2r_loudness_readings(ld.kept.stored(), ld.kept.n_rows(), ld.hop, programme, out);
-}
-
-int s2r_get_true_peak(const s2r_synth *s, float last[2], float held[2]) {
-    if (!s || !s->kids.empty() || s->parent || !s->post.loud.hop) return S2R_ERR_INVALID;
-    const S2rPostChain::Loudness &ld = s->post.loud;
-    if (last) { last[0] = ld.tp_last[0]; last[1] = ld.tp_last[1]; }
-    if (held) { held[0] = ld.tp_held[0]; held[1] = ld.tp_held[1]; }
-    return S2R_OK;
-}
-
-int s2r_get_loudness_state(s2r_synth *s, float *state, size_t capacity, uint32_t *pos) { return meter_get_state(s, kLoudness, state, capacity, pos, "s2r_get_loudness_state"); }
-int s2r_set_loudness_state(s2r_synth *s, const float *state, size_t count, uint32_t pos) { return meter_set_state(s, kLoudness, state, count, pos, "s2r_set_loudness_state"); }
-int s2r_get_loudness_hops(const s2r_synth *s, float *rows, size_t capacity, size_t *n_hops) { return meter_get_rows(s, kLoudness, rows, capacity, n_hops, "s2r_get_loudness_hops"); }
-int s2r_set_loudness_hops(s2r_synth *s, const float *rows, size_t n_hops, size_t count) { return meter_set_rows(s, kLoudness, rows, n_hops, count, "s2r_set_loudness_hops"); }
-
-// ---- the spectrum meters behind the loudness meters ----
-int s2r_set_master_spectrum(s2r_synth *s, uint32_t n_fft, uint32_t hop, const float *window, uint32_t max_rows) {
-    if (!spectrum_in_range(n_fft, hop, window, max_rows))
-        return set_err(s, S2R_ERR_PATCH_RANGE, "master spectrum: size %u, hop %u, %u rows: a power of two in %u .. %u, the hop in max(%u, size / 8) .. %u, the rows kept in 1 .. %u, a finite window",
-                       n_fft, hop, max_rows, S2R_SPECTRUM_MIN_FFT, S2R_SPECTRUM_MAX_FFT, S2R_SPECTRUM_MIN_HOP, S2R_SPECTRUM_MAX_HOP, S2R_SPECTRUM_MAX_ROWS);
-    S2R_TRY(post_handle(s, "s2r_set_master_spectrum", "the spectrum meter is"));
-    if (!window) return set_err(s, S2R_ERR_INVALID, "s2r_set_master_spectrum: no window");
-    s->post.set_spectrum(n_fft, hop, window, max_rows);
-    return S2R_OK;
-}
-
-int s2r_clear_master_spectrum(s2r_synth *s) {
-    S2R_TRY(post_handle(s, "s2r_clear_master_spectrum", "the spectrum meter is"));
-    s->post.set_spectrum(0, 0, nullptr, 0);
-    return S2R_OK;
-}
-
-int s2r_get_master_spectrum(const s2r_synth *s, uint32_t *n_fft, uint32_t *hop, uint32_t *max_rows, size_t *n_rows, float *window, size_t window_capacity) {
-    if (!s || !s->kids.empty() || s->parent) return S2R_ERR_INVALID;
-    const S2rPostChain::Spectrum &sp = s->post.spec;
-    if (window && window_capacity < sp.n_fft) return S2R_ERR_INVALID;
-    if (window && sp.n_fft) std::memcpy(window, sp.window.data(), sp.n_fft * sizeof(float));
-    put(n_fft, sp.n_fft); put(hop, sp.hop); put(max_rows, sp.kept.max_rows); put(n_rows, sp.kept.n_rows());
-    return S2R_OK;
-}
-
-int s2r_reset_master_spectrum(s2r_synth *s) {
-    S2R_TRY(meter_on(s, kSpectrum, "s2r_reset_master_spectrum"));
-    s->post.reset_spectrum();
-    return S2R_OK;
-}
-
-int s2r_get_spectrum(const s2r_synth *s, uint32_t programme, uint32_t n_avg, double *out_db, size_t capacity) {
-    if (programme >= S2R_SPECTRUM_PROGRAMMES) return S2R_ERR_PATCH_RANGE;
-    if (!s || !s->kids.empty() || s->parent || !s->post.spec.n_fft || !out_db) return S2R_ERR_INVALID;
-    const S2rPostChain::Spectrum &sp = s->post.spec;
-    if (n_avg == 0u || n_avg > sp.kept.n_rows()) return S2R_ERR_PATCH_RANGE;
-    return s2r_spectrum_readings(sp.kept.stored(), sp.kept.n_rows(), sp.n_fft, sp.window.data(), programme, n_avg, out_db, capacity);
-}
-
-int s2r_get_spectrum_bands(const s2r_synth *s, uint32_t programme, uint32_t n_avg, double sample_rate, uint32_t bands_per_octave, double *out_db, double *centres,
-                           size_t capacity, size_t *n_bands) {
-    if (programme >= S2R_SPECTRUM_PROGRAMMES) return S2R_ERR_PATCH_RANGE;
-    if (!s || !s->kids.empty() || s->parent || !s->post.spec.n_fft || !out_db || !n_bands) return S2R_ERR_INVALID;
-    const S2rPostChain::Spectrum &sp = s->post.spec;
-    if (n_avg == 0u || n_avg > sp.kept.n_rows()) return S2R_ERR_PATCH_RANGE;
-    return s2r_spectrum_band_readings(sp.kept.stored(), sp.kept.n_rows(), sp.n_fft, sp.window.data(), programme, n_avg, sample_rate, bands_per_octave, out_db, centres, capacity,
-                                      n_bands);
-}
-
-int s2r_get_spectrum_rows(const s2r_synth *s, float *rows, size_t capacity, size_t *n_rows) { return meter_get_rows(s, kSpectrum, rows, capacity, n_rows, "s2r_get_spectrum_rows"); }
-int s2r_set_spectrum_rows(s2r_synth *s, const float *rows, size_t n_rows, size_t count) { return meter_set_rows(s, kSpectrum, rows, n_rows, count, "s2r_set_spectrum_rows"); }
-int s2r_get_spectrum_state(s2r_synth *s, float *state, size_t capacity, uint32_t *pos) { return meter_get_state(s, kSpectrum, state, capacity, pos, "s2r_get_spectrum_state"); }
-int s2r_set_spectrum_state(s2r_synth *s, const float *state, size_t count, uint32_t pos) { return meter_set_state(s, kSpectrum, state, count, pos, "s2r_set_spectrum_state"); }
 
 int s2r_fill_oversampled(s2r_synth *s, float *mono_out, size_t frames, uint32_t sample_rate_hz) {
     if (!s) return S2R_ERR_INVALID;
@@ -3679,18 +2244,12 @@ int s2r_import_state(s2r_synth *s, const s2r_voice_state *voices) {
         h[7 * pv + i] = s2r_f2u(in.filt_x1); h[8 * pv + i] = s2r_f2u(in.filt_x2);
         h[9 * pv + i] = s2r_f2u(in.filt_y1); h[10 * pv + i] = s2r_f2u(in.filt_y2);
         h[11 * pv + i] = in.program;
-        if (s->mixer.used & kMixFader) s->mixer.program[i] = in.program;
         h[12 * pv + i] = s2r_f2u(in.osc_z);
         s->pool->set_voice(to_pool(s, i), in.note, in.started != 0, in.released != 0,
                            in.current_frame_offset, in.release_frame_offset, in.velocity);
     }
     s->pool->rebuild();
-    if (s->mixer.used & kMixFader) {                             // (programs still queued belong to the state that was replaced)
-        std::vector<s2r_synth::Mixer::Record> &q = s->mixer.timed;
-        for (s2r_synth::Mixer::Record &r : q) r.mask &= ~kMixFader;
-        q.erase(std::remove_if(q.begin(), q.end(), [](const s2r_synth::Mixer::Record &r) { return r.mask == 0; }), q.end());
-        s->gains_dirty = kGainsAll;
-    }
+    if (s->mixer.used & kMixFader) s->mixer.restore_programs([voices](uint32_t i) { return voices[i].program; });
     S2R_HIP(s, hipMemcpyAsync(s->voice_mem, h.data(), pv * kVoiceWords * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
     S2R_HIP(s, hipStreamSynchronize(s->stream));
     return S2R_OK;
@@ -3952,51 +2511,6 @@ const char *s2r_last_error(const s2r_synth *s) { return s ? s->err.c_str() : "nu
 
 // Diagnostic builds only (-DS2R_STAMPS; tools/stamps.py): copies the last fill's per-wave phase stamps ([waves][16]
 // s_memtime ticks) to `out`; returns the number of waves, 0 in a product build.  Not declared in s2r.h.
-// measurement (tools/pan_time.py): device time of the panned mixdown's kernels in the last s2r_fill_panned, summed over its
-// slices, in milliseconds (s2r_set_timing on; < 0 otherwise); and the frames per slice of the rows buffer (0: not allocated yet)
-extern "C" float s2r_debug_pan_mix_ms(const s2r_synth *s) { return s && s->timing ? s->pan_mix_ms : -1.0f; }
-extern "C" uint32_t s2r_debug_pan_slice(const s2r_synth *s) { return s ? s->pan_slice : 0u; }
-// ... and of the bus mixdown's kernels in the last s2r_fill_buses (tools/bus_time.py)
-extern "C" float s2r_debug_bus_mix_ms(const s2r_synth *s) { return s && s->timing ? s->bus_mix_ms : -1.0f; }
-// ... of the buses' EQ kernel in that fill: 0 when it ran none (tools/eq_time.py); whether the handle holds the EQs' staging buffer;
-// and the frames the kernel stages at a time (tests/test_gpu_eq.py picks its call lengths around it)
-extern "C" float s2r_debug_bus_eq_ms(const s2r_synth *s) { return s && s->timing ? s->post.stage[S2R_BUS_EQ].timer.ms : -1.0f; }
-extern "C" int s2r_debug_bus_eq_allocated(const s2r_synth *s) { return s && s->post.stage[S2R_BUS_EQ].buffer ? 1 : 0; }
-extern "C" uint32_t s2r_debug_eq_tile(void) { return S2R_EQ_TILE; }
-// ... of the buses' dynamics kernel in that fill: 0 when it ran none (tools/dyn_time.py); whether the handle holds the dynamics' staging
-// buffer; and the frames of one stage of the kernel's pipeline (tests/test_gpu_dyn.py picks its call lengths around it)
-extern "C" float s2r_debug_dyn_ms(const s2r_synth *s) { return s && s->timing ? s->post.stage[S2R_BUS_DYN].timer.ms : -1.0f; }
-extern "C" int s2r_debug_dyn_allocated(const s2r_synth *s) { return s && (s->post.stage[S2R_BUS_DYN].buffer || s->post.dyn_curves || s->post.dyn_meter) ? 1 : 0; }
-extern "C" uint32_t s2r_debug_dyn_tile(void) { return S2R_DYN_TILE; }
-// ... of the buses' room kernel in that fill: 0 when it ran none (tools/room_time.py); whether the handle holds the rooms' staging buffer;
-// and the frames of one pass of the kernel (tests/test_gpu_room.py picks its call lengths around it)
-extern "C" float s2r_debug_bus_room_ms(const s2r_synth *s) { return s && s->timing ? s->post.stage[S2R_BUS_ROOM].timer.ms : -1.0f; }
-extern "C" int s2r_debug_room_allocated(const s2r_synth *s) { return s && s->post.stage[S2R_BUS_ROOM].buffer ? 1 : 0; }
-extern "C" uint32_t s2r_debug_room_tile(void) { return S2R_ROOM_TILE; }
-// ... of the buses' drive kernel in that fill: 0 when it ran none (tools/drive_time.py); whether the handle holds the drives' staging
-// buffer or their tables; and the output frames of one workgroup of the kernel (tests/test_gpu_drive.py picks its call lengths around it)
-extern "C" float s2r_debug_bus_drive_ms(const s2r_synth *s) { return s && s->timing ? s->post.stage[S2R_BUS_DRIVE].timer.ms : -1.0f; }
-extern "C" int s2r_debug_drive_allocated(const s2r_synth *s) { return s && (s->post.stage[S2R_BUS_DRIVE].buffer || s->post.drive_curves) ? 1 : 0; }
-extern "C" uint32_t s2r_debug_drive_tile(void) { return S2R_DRIVE_TILE; }
-// ... of the buses' flanger kernel in that fill: 0 when it ran none (tools/flanger_time.py); whether the handle holds the flangers'
-// staging buffer; and the frames of one tile of the kernel (tests/test_gpu_flanger.py picks its call lengths around it)
-extern "C" float s2r_debug_bus_flanger_ms(const s2r_synth *s) { return s && s->timing ? s->post.stage[S2R_BUS_FLANGER].timer.ms : -1.0f; }
-extern "C" int s2r_debug_flanger_allocated(const s2r_synth *s) { return s && s->post.stage[S2R_BUS_FLANGER].buffer ? 1 : 0; }
-extern "C" uint32_t s2r_debug_flanger_tile(void) { return S2R_FLANGER_TILE; }
-// ... of the buses' chorus kernel in that fill: 0 when it ran none (tools/chorus_time.py)
-extern "C" float s2r_debug_bus_chorus_ms(const s2r_synth *s) { return s && s->timing ? s->post.stage[S2R_BUS_CHORUS].timer.ms : -1.0f; }
-// ... of the buses' delay kernel in that fill: 0 when it ran none (tools/delay_time.py)
-extern "C" float s2r_debug_bus_delay_ms(const s2r_synth *s) { return s && s->timing ? s->post.stage[S2R_BUS_DELAY].timer.ms : -1.0f; }
-// ... and of the buses' reverb kernels in that fill: 0 when it ran none (tools/reverb_time.py)
-extern "C" float s2r_debug_bus_fx_ms(const s2r_synth *s) { return s && s->timing ? s->post.stage[S2R_BUS_REVERB].timer.ms : -1.0f; }
-// ... and of the master kernel in the last s2r_fill_master (tools/master_time.py)
-extern "C" float s2r_debug_master_ms(const s2r_synth *s) { return s && s->timing ? s->post.master.timer.ms : -1.0f; }
-// ... and of the limiter kernel in that fill: 0 when it ran none (tools/limiter_time.py)
-extern "C" float s2r_debug_limiter_ms(const s2r_synth *s) { return s && s->timing ? s->post.limiter.timer.ms : -1.0f; }
-// ... and of the loudness kernel in that fill: 0 when it ran none (tools/loudness_time.py)
-extern "C" float s2r_debug_loudness_ms(const s2r_synth *s) { return s && s->timing ? s->post.loud.timer.ms : -1.0f; }
-// ... and of the spectrum kernel in that fill: 0 when it ran none (tools/spectrum_time.py)
-extern "C" float s2r_debug_spectrum_ms(const s2r_synth *s) { return s && s->timing ? s->post.spec.timer.ms : -1.0f; }
 
 extern "C" uint32_t s2r_debug_read_stamps(s2r_synth *s, unsigned long long *out, uint32_t max_waves) {
 #if defined(S2R_STAMPS)

@@ -211,7 +211,7 @@ struct S2rPostChain {
     void commit(const S2rPostCall &call);
     hipError_t read_timers(const S2rPostCall &call);
     void release();
-    // what the entry points of s2r_host.cpp do behind their checks, on a quiet stream; in chain order
+    // what the entry points of s2r_host_post.cpp do behind their checks, on a quiet stream; in chain order
     hipError_t set_eq(const S2rPostCtx &c, uint32_t bus, uint32_t n_bands, const float *coeffs);
     // curve null: removes the bus's dynamics; keep_state: the parameters alone, on a bus that has them
     hipError_t set_dyn(const S2rPostCtx &c, uint32_t bus, uint32_t key, const float *curve, float a_att, float a_rel, bool keep_state);

@@ -1,4 +1,4 @@
-// s2r_rules.h — the ranges that the entry points (s2r_host.cpp) and the handle-free rule functions (s2r_rules.cpp) share, so that a
+// s2r_rules.h — the ranges that the entry points (s2r_host_mix.cpp, s2r_host_post.cpp) and the handle-free rule functions (s2r_rules.cpp) share, so that a
 // setter and its reference cannot disagree on one.  No HIP.  Every predicate is false for a NaN.
 #pragma once
 #include <cmath>

@@ -190,10 +190,10 @@ def _every_note(fr, bank, sr, what, programs=None):
 def test_every_midi_note(osc, sr):
     """Notes 0 .. 127 (the suite renders 20 .. 119): periods from 0.6 to 47 000 samples, with the oscillator's frequency swept
     over 2^[-10, 10] by the mod envelope down to 6e-4 and up to 5e7 samples.  Per-voice rows and the mix, one-pole patch, every
-    oscillator kind, FM 0, +-10 and 0.37.  Sites: build_pitch_table (s2r_host.cpp:57); the period and its reciprocal, `off`
+    oscillator kind, FM 0, +-10 and 0.37.  Sites: build_pitch_table (s2r_host.cpp); the period and its reciprocal, `off`
     returned for fmodf(off, period) under one unsigned compare, and -2 / period as -2 * RN(1 / period) (s2r_fmod_period, osc_value,
     dpw_value, s2r_kern_common.h); the sine lookup's index that rounding takes to 1024 (gather_or_default); the division by a sample
-    rate in three operations or, at 37123 Hz, a true division (fast_div_rate, s2r_host.cpp:105)."""
+    rate in three operations or, at 37123 Hz, a true division (fast_div_rate, s2r_host.cpp)."""
     for fm in FMS:
         fr = _Forms(128, BUF, [ROWS, MIX])
         _every_note(fr, [_note_patch(osc, fm)], sr, "every note, osc %d, FM %s" % (osc, _hx(fm)))
@@ -205,7 +205,7 @@ def test_every_midi_note(osc, sr):
 def test_every_midi_note_at_the_abi_s_rate_extremes(osc, sr):
     """The same at sample rates of 1, 7, 4 000 000 and 0xffffffff Hz (any u32 > 0 is accepted): periods from 8e-5 samples (note 127
     at 1 Hz; with FM, 8e-8) to 5e8 (note 0 at 0xffffffff Hz); envelopes of a fraction of a sample and of 8.6e8 samples (no table:
-    plan_tables, s2r_host.cpp:587); (float)sample_rate rounding 0xffffffff up to 2^32 (make_params, s2r_host.cpp:644)."""
+    plan_tables, s2r_host.cpp); (float)sample_rate rounding 0xffffffff up to 2^32 (make_params, s2r_host.cpp)."""
     for fm in FMS:
         fr = _Forms(128, BUF, [ROWS, MIX])
         _every_note(fr, [_note_patch(osc, fm)], sr, "every note, osc %d, FM %s" % (osc, _hx(fm)))
@@ -216,9 +216,9 @@ def test_every_midi_note_at_the_abi_s_rate_extremes(osc, sr):
 @pytest.mark.parametrize("osc", OSCS)
 def test_every_midi_note_in_the_other_render_forms(osc, sr):
     """Every note with FM +-10 through the forms a fill can take besides a launch per fill on one workgroup: the pool-resident
-    kernel and the one-launch fill on two 64-voice workgroups (s2r_host.cpp:837, 919), filter and FM coefficients computed in-lane
+    kernel and the one-launch fill on two 64-voice workgroups (pool_fill and enqueue_fused, s2r_host.cpp), filter and FM coefficients computed in-lane
     instead of read from the patch's tables (s2r_set_coeff_stream(0)), and a two-patch bank with the notes dealt to both patches
-    (the per-lane-patch kernel, ensure_bank, s2r_host.cpp:667)."""
+    (the per-lane-patch kernel, ensure_bank, s2r_host.cpp)."""
     for fm in (10.0, -10.0):
         what = "every note, osc %d, FM %s" % (osc, _hx(fm))
         fr = _Forms(128, BUF, [_form("pool-resident", "mix", block=64, resident=True), _form("one-launch fill", "mix", block=64),
@@ -519,7 +519,7 @@ CUTOFFS = [F32(0.0), F32(-0.0), DENORM_MIN, F32(1e-38), _pred(2.0 ** -30), F32(2
 def test_onepole_cutoff_from_zero_to_flt_max(amount, sr):
     """The one-pole filter's lpf_freq at 0, -0.0 (accepted: the check is `< 0.0f`, s2r_patch.cpp:83), the smallest denormal,
     1e-38, the three floats at 2^-30 and at 2^30 — the window inside which the host switches the three-operation quotient by the
-    sample rate on (make_params, s2r_host.cpp:648; never at 37123 Hz) — 1e30 and FLT_MAX, with mod_env_to_lpf_freq 0 and +-10 and
+    sample rate on (make_params, s2r_host.cpp; never at 37123 Hz) — 1e30 and FLT_MAX, with mod_env_to_lpf_freq 0 and +-10 and
     a mod envelope that decays for 20 ms and then sits flat (refresh_flat's `slope == 0.0f`).  All 128 notes, three buffers, every
     second note released; coefficients from the patch's table (s2r_set_coeff_stream 1) and computed in-lane (0), and once more as
     entry 1 of a bank.  Catches a quotient used outside its verified window, a flat envelope taken for one that moves, and a table
@@ -584,9 +584,9 @@ def test_envelope_times_and_sustain_at_their_ends(timed, sr):
     """Attack, decay and release of both envelopes from 0 to FLT_MAX ms (the suite: 0 or 0.25 .. 375 ms) and sustains of 0, 2^-149,
     1e-39, 1 - 2^-24 and 1, both modulation amounts non-zero, 32 notes of which every second is released in the second buffer —
     by untimed events (per-voice rows and the mix) or by timed ones at 16-frame boundaries (the mix) — with the flat-envelope
-    shortcut on and off.  Sites: resolve_env (s2r_host.cpp:88-100: 1 / A, (S - 1) / D, -S / R with A, D, R of 0, of a fraction of
+    shortcut on and off.  Sites: resolve_env (s2r_host.cpp: 1 / A, (S - 1) / D, -S / R with A, D, R of 0, of a fraction of
     a sample, of 1 and 16 samples exactly, of more than 2^32 samples and of inf); refresh_flat's `slope == 0.0f` with a value of S or
-    +0; plan_tables' cut (s2r_host.cpp:587).  Catches a slope or a product flushed to zero, an envelope taken for flat one chunk
+    +0; plan_tables' cut (s2r_host.cpp).  Catches a slope or a product flushed to zero, an envelope taken for flat one chunk
     early or late, a one-sample attack off by one frame, and a frame count beyond 2^32 wrapped.
 
     A denormal sustain makes denormal slopes and denormal output.  Where the amp envelope reaches it within 16 samples (attack +
@@ -692,7 +692,7 @@ Q_FLOOR = F32(2.0 ** -100)
 
 @pytest.mark.parametrize("kind", [s2.FILT_SVF_LP, s2.FILT_SVF_BP, s2.FILT_SVF_HP])
 def test_svf_at_the_smallest_q_and_below_it(kind):
-    """lpf_q = 2^-100 is the smallest the fill accepts for the SVF (check_fill, s2r_host.cpp:573: k = 1 / q stays finite): rendered
+    """lpf_q = 2^-100 is the smallest the fill accepts for the SVF (check_fill, s2r_host.cpp: k = 1 / q stays finite): rendered
     over both sweeps.  The float below it passes s2r_set_patch (Unipolar<10>) and is refused by every fill with
     S2R_ERR_PATCH_RANGE; once a valid patch is set again the handle renders on from where it was, bit for bit."""
     ws = s2.Synth(N_SWEEP, max_frames=16)
@@ -739,9 +739,9 @@ def test_values_next_to_each_range_are_refused_and_the_handle_renders_on():
     """For every float field of the patch: the nearest float outside its range (-2^-149 below a range that starts at 0), NaN and
     +-Inf are refused by s2r_set_patch and s2r_set_patch_bank with S2R_ERR_PATCH_RANGE (s2r_validate_patch, s2r_patch.cpp:79-99),
     and the next fill of the same handle equals the oracle's with the old patch.  A sample rate of 0 stays S2R_ERR_INVALID
-    (check_fill, s2r_host.cpp:551).  (The borders themselves are rendered by the tests above: -0.0, 0 and FLT_MAX, sustains 0 and
+    (check_fill, s2r_host.cpp).  (The borders themselves are rendered by the tests above: -0.0, 0 and FLT_MAX, sustains 0 and
     1, amounts of +-10.)  The MIDI note range has no outside: s2r_note_on takes a u8 like the reference's Note, and notes 128 ..
-    255 get note_to_pitch's value (build_pitch_table, s2r_host.cpp:57, has 256 entries); 128 and 255 are rendered here."""
+    255 get note_to_pitch's value (build_pitch_table, s2r_host.cpp, has 256 entries); 128 and 255 are rendered here."""
     good = make_patch(osc_kind=s2.OSC_TRIANGLE, lpf_freq=700.0, mod_env_to_lpf_freq=3.0, mod_env_to_osc_freq=0.5, noise=0.1)
     pr = Pair(16, good, max_frames=64)
     for n in (0, 33, 69, 101, 127):

@@ -230,7 +230,7 @@ LONG_FRAMES = 70001
 def test_buffer_lengths_every_fill_form(kind, max_frames):
     """A caller's buffer of any length, through every form a handle offers (sample, two begun fills in flight, stereo, per-voice
     rows, 4x oversampled, process_layers), for both render kernels and the bank kernel; 70 voices in 64-voice workgroups (a
-    ragged second one).  Sites: the partial rows' stride rounded up to 4 (partials_stride, s2r_host.cpp:141) and the row zeroing
+    ragged second one).  Sites: the partial rows' stride rounded up to 4 (partials_stride, s2r_host.cpp) and the row zeroing
     that stops at (frames + 3) & ~3 (s2r_render_onepole.inc:92, s2r_render_general.inc:308) at max_frames that are no
     multiple of 4; the one-super-chunk threshold on both sides (s2r_pick_super_frames, s2r_kern_common.h:746-755); offsets
     that are no multiple of 16 leaving the branch-free chunk (s2r_render_onepole.inc:461); timed events at a fill's last
@@ -268,9 +268,9 @@ def test_buffer_lengths_every_fill_form(kind, max_frames):
 def test_pool_resident_kernel_at_odd_lengths(kind, max_frames):
     """s2r_set_resident on a pool of eight (70001: two) 64-voice workgroups: fills that alternate between short ones and
     max_frames, ring and synchronous, timed events at the last 16-aligned frame and at 65 520; at 70 001 frames the fills
-    cross the pool-resident limit of 0xffff frames (pool_eligible, s2r_host.cpp:923) both ways on one handle.  Sites: the
-    resident kernel's LDS and staging sized from max_frames, not from the fill (s2r_host.cpp:1025); the super-chunk choice per
-    fill (s2r_kern_common.h:746-755); the partial-row stride (s2r_host.cpp:141).  Catches staging sized or indexed by the wrong
+    cross the pool-resident limit of 0xffff frames (pool_eligible, s2r_host.cpp) both ways on one handle.  Sites: the
+    resident kernel's LDS and staging sized from max_frames, not from the fill (pool_launch, s2r_host.cpp); the super-chunk choice per
+    fill (s2r_kern_common.h:746-755); the partial-row stride (s2r_host.cpp).  Catches staging sized or indexed by the wrong
     length, a form switch that loses or repeats state, and a fill length carried over from the previous command.  The exported
     state is compared with the oracle's at the end."""
     rng = np.random.RandomState(1000 + max_frames + len(kind))
@@ -299,7 +299,7 @@ def test_pool_resident_kernel_at_odd_lengths(kind, max_frames):
 def test_low_latency_kernel_at_odd_lengths(max_frames):
     """s2r_set_low_latency on a pool of one workgroup (60 voices, a one-pole patch) at max_frames that are no multiple of 16 or 4:
     the reference's 16-frame calls, ragged calls of 1, 15 and 17 frames, and whole buffers.  Sites: the resident kernel's
-    staging sized from max_frames (s2r_host.cpp:1025), the row zeroing at (frames + 3) & ~3 (s2r_render_onepole.inc:92), the
+    staging sized from max_frames (pool_launch and resident_launch, s2r_host.cpp), the row zeroing at (frames + 3) & ~3 (s2r_render_onepole.inc:92), the
     tail past the last whole chunk.  Catches a tail or a bound that assumes max_frames a multiple of 16."""
     rng = np.random.RandomState(max_frames)
     pr = _pair("onepole", 60, max_frames)
@@ -327,7 +327,7 @@ def test_low_latency_kernel_at_odd_lengths(max_frames):
 @pytest.mark.parametrize("n", [2, 3])
 def test_device_list_exchange_at_odd_max_frames(n, max_frames, interleave, resident):
     """A device list of n shards on one card at max_frames 1000 and 1023: the shards' rows go through the root's exchange rows,
-    laid out at a stride of max_frames itself, unrounded (s2r_host.cpp:1051-1060, 1301-1305, 1347, 1417; read at
+    laid out at a stride of max_frames itself, unrounded (pool_launch, enqueue_multi and enqueue_root, s2r_host.cpp; read at
     s2r_kern_common.h:1171) — at 1023 a stride that is no multiple of 4.  Ring and synchronous fills of max_frames, 17 and
     max_frames - 1 frames, contiguous shards or runs of 16 / 64 voices dealt out, launch per fill or resident.  Expects the
     rank-ordered sum of the shards' trees over the oracle's rows.  Catches a writer and a reader of the exchange rows that
@@ -438,7 +438,7 @@ def test_bank_of_256_patches(resident):
     """A bank of S2R_MAX_BANK distinct patches (every oscillator kind, DPW included, every filter kind), voices on programs 0,
     1, 254 and 255 and on the rest, program changes inside timed event batches; launch per fill: per-voice rows after untimed
     batches (s2r_render_voices takes no timed events) and mixes after timed ones; pool-resident: ring and synchronous mixes;
-    then the exported state.  Site: ensure_bank (s2r_host.cpp:667-716) packing 256 patches'
+    then the exported state.  Site: ensure_bank (s2r_host.cpp) packing 256 patches'
     four table planes at tab_off, the last patch's table ending the buffer.  Catches a patch read from or tabulated for a
     neighbour's entry, a tab_off past patch 7, and a program index truncated below 8 bits."""
     rng = np.random.RandomState(256 + int(resident))
@@ -496,7 +496,7 @@ def _ms_at_cut(base_samples, below):
 
 def _edge_patch(below, osc=s2.OSC_SAW, kind=s2.FILT_LP2, fm=0.5):
     """a patch whose mod envelope reaches sustain (attack + decay) and ends its release just below S2R_TAB_MAX_ENTRIES frames
-    (tabulated) or at it (computed in-lane: plan_tables, s2r_host.cpp:587-596), asserted with the oracle's Ms::as_samples;
+    (tabulated) or at it (computed in-lane: plan_tables, s2r_host.cpp), asserted with the oracle's Ms::as_samples;
     the amp envelope's release twice as long, so that the filter coefficients stay audible through the whole release"""
     p = make_patch(osc_kind=osc, lpf_kind=kind, lpf_freq=800.0, lpf_damping=0.7, lpf_q=1.4, mod_env_to_lpf_freq=3.0,
                    mod_env_to_osc_freq=fm, noise=0.05)
@@ -548,8 +548,8 @@ def test_table_region_edges(case, resident):
     whose mod envelope sits just below S2R_TAB_MAX_ENTRIES frames: the single-patch table (one-pole and general kernels), the
     last patch of a bank — its table ends the bank's buffer, next to a patch at the limit that computes in-lane — and a bank of
     six such patches that passes the 2^28-float budget, so that the sixth computes in-lane beside five tabled ones in one wave
-    (this allocates about 1 GiB of tables).  Sites: plan_tables (s2r_host.cpp:587-596: the cut and the regions' lengths),
-    ensure_bank (s2r_host.cpp:667-716: tab_off and the budget), the chunk's reads up to S2R_TAB_PAD entries past a region's last
+    (this allocates about 1 GiB of tables).  Sites: plan_tables (s2r_host.cpp: the cut and the regions' lengths),
+    ensure_bank (s2r_host.cpp: tab_off and the budget), the chunk's reads up to S2R_TAB_PAD entries past a region's last
     used entry (s2r_device.h:97).  Catches a region one entry short, a pad read from the next region or past the buffer, the
     cut on the wrong side, and tabled and in-lane lanes of one wave mixed up."""
     voices = 640 if case == "over_budget" else 256

@@ -1,8 +1,8 @@
 """ASan + UBSan over the handle-free rule functions (csrc/s2r_rules.cpp: the reverb, master and limiter references and the mixer's
 gain rules), which need neither a handle nor HIP: the file is compiled by plain g++ beside a small program of its own
 (tests/native/san_rules.cpp) and run as a child process, with no preload of any kind.  The post-mix chain's route (csrc/s2r_post_route.h)
-goes the same way with tests/native/post_route.cpp, and what its master stages keep on the host (csrc/s2r_post_keep.h) with
-tests/native/post_keep.cpp."""
+goes the same way with tests/native/post_route.cpp, what its master stages keep on the host (csrc/s2r_post_keep.h) with
+tests/native/post_keep.cpp, and the voice mixer's bookkeeping (csrc/s2r_mixer_keep.h) with tests/native/mixer_keep.cpp."""
 import os
 import shutil
 import subprocess
@@ -58,3 +58,23 @@ def test_post_keep_under_asan_ubsan(tmp_path):
     out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     assert "keep ok" in out.stdout
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
+def test_mixer_keep_under_asan_ubsan(tmp_path):
+    """the voice mixer's bookkeeping (S2rMixerKeep, csrc/s2r_mixer_keep.h, a header without HIP) against a naive model — per-voice
+    arrays updated in place, gains recomputed voice by voice with the rule_* functions — over 320 seeded walks of 48 steps: program
+    pan / mix / send / fader sets, the first use of each attribute in every order, note_ons at frame 0 and inside a fill, fills
+    that settle late, panned and bus fills split at their event frames, snap, bank shrink and regrow with voices on a program that
+    fell off, checkpoint programs with the queue filtered.  After a step both staging buffers are filled, in allocations of exactly
+    2 * padded_voices floats and padded_voices * kBusGainBytes bytes, and compared in BITS: every byte the layout defines, zeros past
+    the shard, the per-voice getters, and the dirty bits against the model's.  Shard voices 1, 63, 64 and 65; sends never used and
+    used; ramps over 1 and 48 frames; one program and eight"""
+    exe = str(tmp_path / "mixer_keep")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "synth2_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "native", "mixer_keep.cpp"),
+                           os.path.join(ROOT, "synth2_amd", "csrc", "s2r_rules.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-3000:]
+    assert "mixer ok" in out.stdout
