@@ -375,6 +375,27 @@ class Synth {
     static int spectrum_window(uint32_t kind, uint32_t n_fft, float *window) { return s2r_spectrum_window(kind, n_fft, window); }
     static int spectrum_twiddles(uint32_t n_fft, float *twiddles) { return s2r_spectrum_twiddles(n_fft, twiddles); }
 
+    // the PCM stage (build-defined; s2r.h: s2r_set_master_pcm): every bus and the master as integers of 8 .. 24 bits, with dither and
+    // error-feedback noise shaping, behind the spectrum meters, in fill_master only
+    void set_master_pcm(uint32_t bits, uint32_t dither, const float *taps, uint32_t n_taps, uint32_t seed) { check(s2r_set_master_pcm(h_, bits, dither, taps, n_taps, seed)); }
+    void clear_master_pcm() { check(s2r_clear_master_pcm(h_)); }
+    // any pointer may be null; bits of 0 means off; taps receives S2R_PCM_MAX_TAPS floats
+    void get_master_pcm(uint32_t *bits, uint32_t *dither, float *taps, uint32_t *n_taps, uint32_t *seed) const { check(s2r_get_master_pcm(h_, bits, dither, taps, n_taps, seed)); }
+    void reset_master_pcm() { check(s2r_reset_master_pcm(h_)); }
+    // the [frames][2] samples of a programme (bus b, or S2R_MAX_BUSES for the master) of the last fill_master
+    void pcm(uint32_t programme, int32_t *pcm_lr, size_t capacity, size_t *frames) const { check(s2r_get_pcm(h_, programme, pcm_lr, capacity, frames)); }
+    void pcm_clips(uint32_t *last, uint32_t *held) const { check(s2r_get_pcm_clips(h_, last, held)); }
+    // checkpoints: the S2R_PCM_STATE errors and the frame count
+    void pcm_state(float *state, size_t capacity, uint32_t *t) { check(s2r_get_pcm_state(h_, state, capacity, t)); }
+    void set_pcm_state(const float *state, size_t count, uint32_t t) { check(s2r_set_pcm_state(h_, state, count, t)); }
+    static int pcm_reference(uint32_t bits, uint32_t dither, const float *taps, uint32_t n_taps, uint32_t seed, const float *stems, uint32_t n_buses,
+                             const float *master_lr, uint32_t frames, float *state, uint32_t *t, int32_t *pcm, uint32_t *clips) {
+        return s2r_pcm_reference(bits, dither, taps, n_taps, seed, stems, n_buses, master_lr, frames, state, t, pcm, clips);
+    }
+    static int pcm_dither(uint32_t seed, uint32_t t, uint32_t q, uint32_t kind, float *d) { return s2r_pcm_dither(seed, t, q, kind, d); }
+    static int pcm_pack(const int32_t *pcm, size_t count, uint32_t bits, uint32_t bytes_per_sample, uint8_t *out) { return s2r_pcm_pack(pcm, count, bits, bytes_per_sample, out); }
+    static int pcm_shaper(uint32_t kind, float *taps, uint32_t *n_taps) { return s2r_pcm_shaper(kind, taps, n_taps); }
+
     s2r_synth *handle() { return h_; }
 
   private:

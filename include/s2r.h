@@ -55,7 +55,9 @@ extern "C" {
  * s2r_loudness_reference, s2r_loudness_readings, s2r_loudness_design, s2r_set_master_spectrum, s2r_clear_master_spectrum,
  * s2r_get_master_spectrum, s2r_reset_master_spectrum, s2r_get_spectrum, s2r_get_spectrum_bands, s2r_get_spectrum_rows,
  * s2r_set_spectrum_rows, s2r_get_spectrum_state, s2r_set_spectrum_state, s2r_spectrum_reference, s2r_spectrum_readings,
- * s2r_spectrum_band_readings, s2r_spectrum_window, s2r_spectrum_twiddles. */
+ * s2r_spectrum_band_readings, s2r_spectrum_window, s2r_spectrum_twiddles, s2r_set_master_pcm, s2r_clear_master_pcm,
+ * s2r_get_master_pcm, s2r_reset_master_pcm, s2r_get_pcm, s2r_get_pcm_clips, s2r_get_pcm_state, s2r_set_pcm_state,
+ * s2r_pcm_reference, s2r_pcm_dither, s2r_pcm_pack, s2r_pcm_shaper. */
 #define S2R_ABI_VERSION 4
 
 typedef enum {
@@ -1074,6 +1076,95 @@ int s2r_spectrum_band_readings(const float *rows, size_t n_rows, uint32_t n_fft,
                                size_t capacity, size_t *n_bands);
 int s2r_spectrum_window(uint32_t kind, uint32_t n_fft, float *window);
 int s2r_spectrum_twiddles(uint32_t n_fft, float *twiddles);
+
+/* BUILD-DEFINED PCM output stage (the reference's player lets its audio host truncate, audio_player.rs:73-105): the
+ * word-length reduction of every bus and of the master to B-bit integers, with dither and error-feedback noise shaping, behind the
+ * spectrum meters, the last stage of s2r_fill_master and of no other fill.  Off by default, and a handle on which the stage was never
+ * set launches exactly what it launched before and allocates nothing; master_lr, the stems, the loudness rows and the spectrum rows are
+ * the same bits with the stage on or off.
+ * PROGRAMMES: S2R_PCM_PROGRAMMES = 9, the meters': programme b < 8 is bus b as the stems hold it, programme 8 the master as the caller
+ * receives it.  Channel q = 2 p + c, S2R_PCM_CHANNELS = 18 of them.  A bus at or past the call's n_buses is fed +0.0.
+ * PARAMETERS: bits = B in S2R_PCM_MIN_BITS .. S2R_PCM_MAX_BITS (8 .. 24); dither S2R_DITHER_NONE, S2R_DITHER_RECT (1 LSB peak to peak)
+ * or S2R_DITHER_TRI (2 LSB); taps h[0 .. K), K = n_taps in 0 .. S2R_PCM_MAX_TAPS (9), each finite with |h| <= 16: the noise transfer
+ * is 1 - sum h[k-1] z^-k; seed: any value.  One set of parameters serves all 18 channels.
+ * STATE carried from call to call: S2R_PCM_STATE = 18 * 9 floats, row q = e_q[n-1], e_q[n-2], ...: the channel's last nine shaped
+ * errors, newest first, every one in [-2, 2]; and t, the frames converted since the set or reset, mod 2^32.  All +0.0 / 0 right after
+ * a set or a reset.  The rule reads the first K entries of a row; a call of one frame or more leaves the entries past K as +0.0.
+ * DEVICE RULE, binary32, every operation rounded on its own, no fma, denormals kept.  Per channel q and frame n of the call, in frame
+ * order, G = 2^(B-1), x the channel's sample:
+ *   1. xc = +0.0 if x is a NaN, else min(max(x, -2.0f), 2.0f);   s = xc * G   (exact)
+ *   2. f = the sum over k = K, K-1, ..., 1 of h[k-1] * e[n-k], from +0.0, in that DESCENDING order: the newest error enters last
+ *      (the transposed form — acc[n+k] += h[k-1] * e[n] for every k once e[n] is known — is the same operations)
+ *   3. w = s - f
+ *   4. the dither d, from integers alone.  mix(u) on uint32_t: u ^= u >> 16; u *= 0x7feb352d; u ^= u >> 15; u *= 0x846ca68b;
+ *      u ^= u >> 16.  k = mix(mix(t_n ^ seed) + q), t_n = t + n mod 2^32; r1 = k >> 16, r2 = k & 0xffff.
+ *        S2R_DITHER_TRI:   d = (float)((int)r1 - (int)r2) * 2^-16
+ *        S2R_DITHER_RECT:  d = (float)(2 * (int)r1 - 65535) * 2^-17
+ *        S2R_DITHER_NONE:  d = +0.0
+ *      (all exact in binary32)
+ *   5. v = w + d;   r = rint(v), ties to even;   y = min(max(r, -G), G - 1);   the sample is (int32_t)y;   y != r counts as a clip
+ *      of channel q
+ *   6. e[n] = min(max(y - w, -2.0f), 2.0f)
+ * Without a clip |y - w| < 1.5 and the clamp of step 6 is idle; with clips it keeps |f| <= 2 sum |h| and lets the loop recover
+ * within K frames.  Every sample, the state and the clip counts are independent of how a stream is cut into calls.
+ * A refused or failed call leaves state, t, samples and counts as they were.  Single-device handles (a device list refuses every
+ * entry).  The first master fill that finds the stage set allocates the two copies of the state and pinned samples for
+ * [9][max_frames][2] int32_t.
+ *   s2r_set_master_pcm: S2R_ERR_PATCH_RANGE for bits, dither or n_taps out of range or a tap that is not finite or past 16 in
+ *   magnitude (checked before the handle is looked at; nothing is changed); S2R_ERR_INVALID for NULL taps with n_taps > 0.  Resets
+ *   state, t and counts, and drops the last samples.  s2r_clear_master_pcm: off.
+ *   s2r_get_master_pcm: any pointer may be NULL; bits of 0 means off; taps receives S2R_PCM_MAX_TAPS floats, +0.0 past n_taps.
+ *   s2r_reset_master_pcm: state, t and counts cleared and the last samples dropped, parameters kept; S2R_ERR_INVALID with the stage off.
+ *   s2r_get_pcm: the [frames][2] samples of `programme` (< 9, else S2R_ERR_PATCH_RANGE) of the last successful master fill that
+ *   ran the stage, into pcm_lr, which holds `capacity` int32_t (at least 2 * frames, else S2R_ERR_INVALID); *frames that fill's
+ *   frames.  S2R_ERR_INVALID before any such fill, with the stage off or for NULL pcm_lr.
+ *   s2r_get_pcm_clips: per channel, the clips of that fill (`last`) and since the set or reset (`held`, saturating); either may be NULL.
+ *   s2r_get_pcm_state / s2r_set_pcm_state (checkpoints): the 162 floats and t; the getter takes a capacity of at least
+ *   S2R_PCM_STATE, the setter exactly S2R_PCM_STATE, every value within [-2, 2] (S2R_ERR_PATCH_RANGE otherwise, for a NaN too);
+ *   it keeps the first K entries of a row and stores +0.0 past them.
+ *   S2R_ERR_INVALID for a wrong size, a NULL buffer or with the stage off.
+ *   s2r_pcm_reference: the device rule on the host (no device, no handle).  stems [n_buses][frames][2] (NULL with n_buses 0),
+ *   master_lr [frames][2]; state[S2R_PCM_STATE] and *t updated in place; pcm [9][frames][2]; clips[18] receives the call's counts
+ *   (may be NULL).  S2R_ERR_PATCH_RANGE as the two setters', and for n_buses > 8; S2R_ERR_INVALID for a NULL.
+ *   s2r_pcm_dither: step 4 alone, *d for one t_n and q (< 18) and kind.
+ *   s2r_pcm_pack: `count` samples of `bits` bits into containers of bytes_per_sample 2, 3 or 4 bytes: little-endian, two's
+ *   complement, left-justified in the container (sample << (8 * bytes_per_sample - bits)) as WAV wants; out holds
+ *   count * bytes_per_sample bytes.  S2R_ERR_PATCH_RANGE for bits out of range, another container, one narrower than bits, or a
+ *   sample outside [-2^(bits-1), 2^(bits-1) - 1] (nothing is written past the samples in front of it).
+ *   s2r_pcm_shaper: the taps of `kind` into taps[S2R_PCM_MAX_TAPS] (+0.0 past *n_taps): S2R_SHAPER_FLAT {}; S2R_SHAPER_FIRST {1};
+ *   S2R_SHAPER_SECOND {2, -1}; S2R_SHAPER_3TAP {1.623, -0.982, 0.109}; S2R_SHAPER_5TAP {2.033, -2.165, 1.959, -1.590, 0.6149};
+ *   S2R_SHAPER_9TAP {2.412, -3.370, 3.937, -4.174, 3.353, -2.205, 1.281, -0.569, 0.0847} — the last three the commonly quoted
+ *   psychoacoustic error-feedback sets for 44.1 kHz, each decimal rounded to nearest binary32. */
+#define S2R_PCM_PROGRAMMES 9u
+#define S2R_PCM_CHANNELS 18u
+#define S2R_PCM_MAX_TAPS 9u
+#define S2R_PCM_STATE (S2R_PCM_CHANNELS * S2R_PCM_MAX_TAPS)
+#define S2R_PCM_MIN_BITS 8u
+#define S2R_PCM_MAX_BITS 24u
+#define S2R_PCM_MAX_TAP 16.0f
+#define S2R_DITHER_NONE 0u
+#define S2R_DITHER_RECT 1u
+#define S2R_DITHER_TRI 2u
+#define S2R_SHAPER_FLAT 0u
+#define S2R_SHAPER_FIRST 1u
+#define S2R_SHAPER_SECOND 2u
+#define S2R_SHAPER_3TAP 3u
+#define S2R_SHAPER_5TAP 4u
+#define S2R_SHAPER_9TAP 5u
+int s2r_set_master_pcm(s2r_synth *s, uint32_t bits, uint32_t dither, const float *taps, uint32_t n_taps, uint32_t seed);
+int s2r_clear_master_pcm(s2r_synth *s);
+int s2r_get_master_pcm(const s2r_synth *s, uint32_t *bits, uint32_t *dither, float *taps, uint32_t *n_taps, uint32_t *seed);
+int s2r_reset_master_pcm(s2r_synth *s);
+int s2r_get_pcm(const s2r_synth *s, uint32_t programme, int32_t *pcm_lr, size_t capacity, size_t *frames);
+int s2r_get_pcm_clips(const s2r_synth *s, uint32_t *last, uint32_t *held);
+int s2r_get_pcm_state(s2r_synth *s, float *state, size_t capacity, uint32_t *t);
+int s2r_set_pcm_state(s2r_synth *s, const float *state, size_t count, uint32_t t);
+int s2r_pcm_reference(uint32_t bits, uint32_t dither, const float *taps, uint32_t n_taps, uint32_t seed, const float *stems,
+                      uint32_t n_buses, const float *master_lr, uint32_t frames, float *state, uint32_t *t, int32_t *pcm,
+                      uint32_t *clips);
+int s2r_pcm_dither(uint32_t seed, uint32_t t, uint32_t q, uint32_t kind, float *d);
+int s2r_pcm_pack(const int32_t *pcm, size_t count, uint32_t bits, uint32_t bytes_per_sample, uint8_t *out);
+int s2r_pcm_shaper(uint32_t kind, float *taps, uint32_t *n_taps);
 
 /* BUILD-DEFINED 4x oversampling (the reference has none; BASELINE config [4]): renders 4 * frames at
  * 4 * sample_rate_hz through the same path and decimates the mix by a 63-tap windowed sinc whose history

@@ -260,6 +260,19 @@ pub mod ffi {
                                           n_bands: *mut usize) -> c_int;
         pub fn s2r_spectrum_window(kind: u32, n_fft: u32, window: *mut f32) -> c_int;
         pub fn s2r_spectrum_twiddles(n_fft: u32, twiddles: *mut f32) -> c_int;
+        pub fn s2r_set_master_pcm(s: *mut S2rSynth, bits: u32, dither: u32, taps: *const f32, n_taps: u32, seed: u32) -> c_int;
+        pub fn s2r_clear_master_pcm(s: *mut S2rSynth) -> c_int;
+        pub fn s2r_get_master_pcm(s: *const S2rSynth, bits: *mut u32, dither: *mut u32, taps: *mut f32, n_taps: *mut u32, seed: *mut u32) -> c_int;
+        pub fn s2r_reset_master_pcm(s: *mut S2rSynth) -> c_int;
+        pub fn s2r_get_pcm(s: *const S2rSynth, programme: u32, pcm_lr: *mut i32, capacity: usize, frames: *mut usize) -> c_int;
+        pub fn s2r_get_pcm_clips(s: *const S2rSynth, last: *mut u32, held: *mut u32) -> c_int;
+        pub fn s2r_get_pcm_state(s: *mut S2rSynth, state: *mut f32, capacity: usize, t: *mut u32) -> c_int;
+        pub fn s2r_set_pcm_state(s: *mut S2rSynth, state: *const f32, count: usize, t: u32) -> c_int;
+        pub fn s2r_pcm_reference(bits: u32, dither: u32, taps: *const f32, n_taps: u32, seed: u32, stems: *const f32, n_buses: u32,
+                                 master_lr: *const f32, frames: u32, state: *mut f32, t: *mut u32, pcm: *mut i32, clips: *mut u32) -> c_int;
+        pub fn s2r_pcm_dither(seed: u32, t: u32, q: u32, kind: u32, d: *mut f32) -> c_int;
+        pub fn s2r_pcm_pack(pcm: *const i32, count: usize, bits: u32, bytes_per_sample: u32, out: *mut u8) -> c_int;
+        pub fn s2r_pcm_shaper(kind: u32, taps: *mut f32, n_taps: *mut u32) -> c_int;
         pub fn s2r_shard_voices(s: *const S2rSynth) -> u32;
         pub fn s2r_fill_device(s: *mut S2rSynth, dev_out: *mut f32, frames: usize, sample_rate_hz: u32,
                                hip_stream: *mut c_void) -> c_int;

@@ -29,7 +29,8 @@ SOURCES = ["s2r_render_onepole_square.hip", "s2r_render_onepole_saw.hip", "s2r_r
            "s2r_spectrum.hip",  # (likewise, since the spectrum meters came)
            "s2r_mixer.cpp",     # (likewise, since the voice mixer got a type of its own: host code only, no kernel)
            "s2r_host_mix.cpp",  # (likewise, since the host file was split: host code only, no kernel)
-           "s2r_host_post.cpp"] # (last, likewise)
+           "s2r_host_post.cpp", # (likewise)
+           "s2r_pcm.hip"]       # (last, likewise, since the PCM stage came)
 HEADERS = ["s2r_device.h", "s2r_math.h", "s2r_patch.h", "s2r_voices.h", "s2r_kern_common.h", "s2r_render_onepole.inc",
            "s2r_render_general.inc", "s2r_post.h", "s2r_post_route.h", "s2r_post_keep.h", "s2r_rules.h", "s2r_handle.h", "s2r_mixer.h",
            "s2r_mixer_keep.h"]
@@ -60,7 +61,7 @@ PER_FILE_FLAGS = {}
 for _f in ("s2r_render_general_square.hip", "s2r_render_general_saw.hip", "s2r_render_general_triangle.hip", "s2r_render_general_sine.hip",
            "s2r_render_general_bank.hip"):
     PER_FILE_FLAGS[_f] = ["-ftrivial-auto-var-init=zero"]
-# Twelve translation units are compiled with the back end's resource-usage remarks, and _check_resources() fails the build when a
+# Thirteen translation units are compiled with the back end's resource-usage remarks, and _check_resources() fails the build when a
 # kernel named here went to scratch or spilled, or when fewer kernels report than the file instantiates.  Per source file: the
 # substrings that name its checked kernels; how many reports are expected — ("at least", n), ("exactly", n), or ("each", None):
 # one or more of every name — and why so many; the figures that must be "0"; and what the kernels keep where it belongs.  (The
@@ -109,6 +110,10 @@ RESOURCE_CHECKS = {
     # eight or sixteen points of one pass per lane and the twiddles of its layers; the transform and the twiddle table in LDS
     "s2r_spectrum.hip": (("s2r_spectrum_kernel",), ("exactly", 1), "one kernel",
                          (_SCRATCH, _VSPILL, _SSPILL), "the points of a pass must stay in registers, the transform and its twiddles in LDS"),
+    # a channel per walker lane: nine taps, nine sums and nine errors, sixteen values read ahead; a frame per stager lane: nine frames of
+    # a tile, their eighteen dither values
+    "s2r_pcm.hip": (("s2r_pcm_kernel",), ("exactly", 1), "one kernel",
+                    (_SCRATCH, _VSPILL, _SSPILL), "its sums, errors and the values read ahead must stay in registers, the tiles in LDS"),
 }
 for _f in RESOURCE_CHECKS:
     PER_FILE_FLAGS[_f] = ["-Rpass-analysis=kernel-resource-usage"]
@@ -160,6 +165,11 @@ if _LOUDNESS_SERIAL:
 _SPECTRUM_SERIAL = os.environ.get("S2R_SPECTRUM_SERIAL") == "1"
 if _SPECTRUM_SERIAL:
     PER_FILE_FLAGS["s2r_spectrum.hip"] = PER_FILE_FLAGS["s2r_spectrum.hip"] + ["-DS2R_SPECTRUM_SERIAL"]
+# S2R_PCM_SERIAL=1 likewise builds the PCM kernel's obvious form (a lane per channel steps through global memory frame by frame, step 2
+# as the rule's loop; csrc/s2r_pcm.hip, CHANGELOG) into libs2r_pcmserial.so, for tools/pcm_time.py.  Never the product build.
+_PCM_SERIAL = os.environ.get("S2R_PCM_SERIAL") == "1"
+if _PCM_SERIAL:
+    PER_FILE_FLAGS["s2r_pcm.hip"] = PER_FILE_FLAGS["s2r_pcm.hip"] + ["-DS2R_PCM_SERIAL"]
 # S2R_OPT=O3 in the environment builds the same sources at -O3 into libs2r_o3.so (tools and tests that compare the two
 # optimisation levels; the product is -O2).
 if os.environ.get("S2R_OPT") == "O3":
@@ -197,6 +207,9 @@ elif _LOUDNESS_SERIAL:
 elif _SPECTRUM_SERIAL:
     LIB = os.path.join(HERE, "libs2r_spectrumserial.so")
     OBJ_DIR_NAME = "_build_spectrumserial"
+elif _PCM_SERIAL:
+    LIB = os.path.join(HERE, "libs2r_pcmserial.so")
+    OBJ_DIR_NAME = "_build_pcmserial"
 else:
     OBJ_DIR_NAME = "_build"
 

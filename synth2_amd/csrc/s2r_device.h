@@ -659,3 +659,23 @@ struct S2rSpectrum {
     uint32_t n_buses, frames, n_fft, hop, pos;
 };
 hipError_t s2r_launch_spectrum(const S2rSpectrum &a, hipStream_t stream);
+
+// The PCM stage of s2r_fill_master: one launch behind the spectrum kernel (or, without the meters, behind whoever wrote
+// the master last), the last of a master fill that finds the stage set.  It reads the stems from the master's device stage and the
+// master from device memory, writes the call's samples of all nine programmes, the channels' clip counts and the OTHER copy of the
+// state, and — only when no meter kernel did it — copies the master to the pinned output (`out` null: somebody else has).  The host
+// flips the copies after a synchronise that succeeded.  `t` is the host's: the frames converted when the call starts.
+#define S2R_PCM_TILE 128u                           // frames the walk's workgroup stages at a time, one tile ahead of the walk
+#define S2R_PCM_COPY_BLOCK 1024u                    // frames of one copying workgroup
+struct S2rPcm {
+    const float *stems;           // [n_buses][2 * frames] in device memory: the master kernel's input
+    const float *master;          // [frames][2] in device memory
+    float *out;                   // interleaved L, R: 2 * frames floats (mapped host memory), or null
+    const float *state;           // [S2R_PCM_STATE]: the state the call starts from
+    float *next;                  // ... and the state it leaves (never the buffer above)
+    int32_t *pcm;                 // [9][pstride][2] (mapped host memory): the call's samples, programme-major
+    uint32_t *clips;              // [S2R_PCM_CHANNELS] (mapped host memory): the call's clips per channel
+    float h[S2R_PCM_MAX_TAPS];    // the taps, +0.0 past n_taps
+    uint32_t n_buses, frames, pstride, bits, dither, n_taps, seed, t;
+};
+hipError_t s2r_launch_pcm(const S2rPcm &a, hipStream_t stream);

@@ -1,5 +1,5 @@
 // s2r_host_post.cpp — the C entries of libs2r in front of the post-mix chain (s2r_post.h; include/s2r.h): the eight bus stages, bus
-// returns, master fader, limiter and both meters, and the chain's measurement getters.  The chain owns what they set; what is
+// returns, master fader, limiter, both meters and the PCM stage, and the chain's measurement getters.  The chain owns what they set; what is
 // here checks the caller's values and the handle (s2r_handle.h).  Compiled with hipcc, -ffp-contract=off.
 #include "s2r_handle.h"
 
@@ -748,6 +748,82 @@ int s2r_set_spectrum_rows(s2r_synth *s, const float *rows, size_t n_rows, size_t
 int s2r_get_spectrum_state(s2r_synth *s, float *state, size_t capacity, uint32_t *pos) { return meter_get_state(s, kSpectrum, state, capacity, pos, "s2r_get_spectrum_state"); }
 int s2r_set_spectrum_state(s2r_synth *s, const float *state, size_t count, uint32_t pos) { return meter_set_state(s, kSpectrum, state, count, pos, "s2r_set_spectrum_state"); }
 
+// ---- the PCM stage behind the spectrum meters ----
+// the guard of the entries that need the stage set
+static int pcm_set(const s2r_synth *s, const char *who) {
+    S2R_TRY(post_handle(s, who, "the PCM stage is"));
+    if (!s->post.pcm.bits) return set_err(const_cast<s2r_synth *>(s), S2R_ERR_INVALID, "%s: no PCM stage is set", who);
+    return S2R_OK;
+}
+
+int s2r_set_master_pcm(s2r_synth *s, uint32_t bits, uint32_t dither, const float *taps, uint32_t n_taps, uint32_t seed) {
+    if (!pcm_in_range(bits, dither, taps, n_taps))
+        return set_err(s, S2R_ERR_PATCH_RANGE, "master pcm: %u bits, dither %u, %u taps: the bits in %u .. %u, the dither one of 0, 1, 2, at most %u finite taps of at most %g", bits,
+                       dither, n_taps, S2R_PCM_MIN_BITS, S2R_PCM_MAX_BITS, S2R_PCM_MAX_TAPS, (double)S2R_PCM_MAX_TAP);
+    S2R_TRY(post_handle(s, "s2r_set_master_pcm", "the PCM stage is"));
+    if (n_taps && !taps) return set_err(s, S2R_ERR_INVALID, "s2r_set_master_pcm: no taps");
+    s->post.set_pcm(bits, dither, taps, n_taps, seed);
+    return S2R_OK;
+}
+
+int s2r_clear_master_pcm(s2r_synth *s) {
+    S2R_TRY(post_handle(s, "s2r_clear_master_pcm", "the PCM stage is"));
+    s->post.set_pcm(0, 0, nullptr, 0, 0);
+    return S2R_OK;
+}
+
+int s2r_get_master_pcm(const s2r_synth *s, uint32_t *bits, uint32_t *dither, float *taps, uint32_t *n_taps, uint32_t *seed) {
+    if (!s || !s->kids.empty() || s->parent) return S2R_ERR_INVALID;
+    const S2rPostChain::Pcm &pm = s->post.pcm;
+    if (taps) std::memcpy(taps, pm.h, sizeof pm.h);
+    put(bits, pm.bits); put(dither, pm.dither); put(n_taps, pm.n_taps); put(seed, pm.seed);
+    return S2R_OK;
+}
+
+int s2r_reset_master_pcm(s2r_synth *s) {
+    S2R_TRY(pcm_set(s, "s2r_reset_master_pcm"));
+    s->post.reset_pcm();
+    return S2R_OK;
+}
+
+int s2r_get_pcm(const s2r_synth *s, uint32_t programme, int32_t *pcm_lr, size_t capacity, size_t *frames) {
+    if (programme >= S2R_PCM_PROGRAMMES) return S2R_ERR_PATCH_RANGE;
+    if (!s || !s->kids.empty() || s->parent || !s->post.pcm.bits || !s->post.pcm.frames || !pcm_lr) return S2R_ERR_INVALID;
+    const S2rPostChain::Pcm &pm = s->post.pcm;
+    if (capacity < 2u * (size_t)pm.frames) return S2R_ERR_INVALID;
+    std::memcpy(pcm_lr, pm.samples + (size_t)programme * 2u * s->cfg.max_frames, 2u * (size_t)pm.frames * sizeof(int32_t));
+    put(frames, (size_t)pm.frames);
+    return S2R_OK;
+}
+
+int s2r_get_pcm_clips(const s2r_synth *s, uint32_t *last, uint32_t *held) {
+    if (!s || !s->kids.empty() || s->parent || !s->post.pcm.bits) return S2R_ERR_INVALID;
+    const S2rPostChain::Pcm &pm = s->post.pcm;
+    if (last) std::memcpy(last, pm.clips_last, sizeof pm.clips_last);
+    if (held) std::memcpy(held, pm.clips_held, sizeof pm.clips_held);
+    return S2R_OK;
+}
+
+int s2r_get_pcm_state(s2r_synth *s, float *state, size_t capacity, uint32_t *t) {
+    S2R_TRY(pcm_set(s, "s2r_get_pcm_state"));
+    if (capacity < S2R_PCM_STATE) return set_err(s, S2R_ERR_INVALID, "s2r_get_pcm_state: the state is %u floats, not %zu", S2R_PCM_STATE, capacity);
+    if (!state) return set_err(s, S2R_ERR_INVALID, "s2r_get_pcm_state: null buffer");
+    S2rPostChain::Pcm &pm = s->post.pcm;
+    S2R_TRY(mirror_fetch(s, pm.state, "s2r_get_pcm_state"));
+    std::memcpy(state, pm.state.host.data(), S2R_PCM_STATE * sizeof(float));
+    put(t, pm.t);
+    return S2R_OK;
+}
+
+int s2r_set_pcm_state(s2r_synth *s, const float *state, size_t count, uint32_t t) {
+    S2R_TRY(pcm_set(s, "s2r_set_pcm_state"));
+    if (count != S2R_PCM_STATE) return set_err(s, S2R_ERR_INVALID, "s2r_set_pcm_state: the state is %u floats, not %zu", S2R_PCM_STATE, count);
+    if (!state) return set_err(s, S2R_ERR_INVALID, "s2r_set_pcm_state: null buffer");
+    if (!pcm_state_in_range(state)) return set_err(s, S2R_ERR_PATCH_RANGE, "s2r_set_pcm_state: an error outside [-2, 2]");
+    s->post.set_pcm_state(state, t);
+    return S2R_OK;
+}
+
 // ---- measurement (tools/*_time.py load these by name; not declared in s2r.h) ----
 // device time of one stage's kernels in the last bus or master fill, in milliseconds (s2r_set_timing on; < 0 otherwise)
 #define POST_MS(timer) (s && s->timing ? s->post.timer.ms : -1.0f)
@@ -790,5 +866,10 @@ float s2r_debug_limiter_ms(const s2r_synth *s) { return POST_MS(limiter.timer); 
 float s2r_debug_loudness_ms(const s2r_synth *s) { return POST_MS(loud.timer); }
 // ... and of the spectrum kernel in that fill: 0 when it ran none (tools/spectrum_time.py)
 float s2r_debug_spectrum_ms(const s2r_synth *s) { return POST_MS(spec.timer); }
+// ... and of the PCM kernel in that fill: 0 when it ran none (tools/pcm_time.py); whether the handle holds anything of the stage's; and
+// the frames the kernel stages at a time (tests/test_gpu_pcm.py picks its call lengths around it)
+float s2r_debug_pcm_ms(const s2r_synth *s) { return POST_MS(pcm.timer); }
+int s2r_debug_pcm_allocated(const s2r_synth *s) { return s && (s->post.pcm.samples || s->post.pcm.counts || s->post.pcm.state.dev[0] || s->post.loud.in) ? 1 : 0; }
+uint32_t s2r_debug_pcm_tile(void) { return S2R_PCM_TILE; }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
-// s2r_post.cpp — the post-mix chain (s2r_post.h): the eight bus stages (EQs, dynamics, drives, flangers, choruses, delays, reverbs, rooms), master section, master limiter, loudness meters, spectrum meters —
-// the last three on the device side of s2r_post_keep.h (S2rMirror).  Compiled with hipcc, -ffp-contract=off.
+// s2r_post.cpp — the post-mix chain (s2r_post.h): the eight bus stages (EQs, dynamics, drives, flangers, choruses, delays, reverbs, rooms), master section, master limiter, loudness meters, spectrum meters, PCM stage —
+// the last four on the device side of s2r_post_keep.h (S2rMirror).  Compiled with hipcc, -ffp-contract=off.
 #include "s2r_post.h"
 #include "s2r_rules.h"
 
@@ -18,9 +18,9 @@ constexpr size_t kLimState = 2u * S2R_LIMITER_MAX_LOOKAHEAD + 2u * S2R_LIMITER_M
 inline uint32_t fx_pstride(const S2rPostCtx &c) { return (c.max_frames + 7u) & ~7u; }
 
 // pinned rows of partials, once; `host` survives a failed hipHostGetDevicePointer, and the next call goes on from there
-hipError_t pinned_rows(float *&host, float *&dev, size_t floats) {
+template <class T> hipError_t pinned_rows(T *&host, T *&dev, size_t floats) {
     if (dev) return hipSuccess;
-    if (!host) POST_HIP(hipHostMalloc((void **)&host, floats * sizeof(float), kHostPolled));
+    if (!host) POST_HIP(hipHostMalloc((void **)&host, floats * sizeof(T), kHostPolled));
     return hipHostGetDevicePointer((void **)&dev, host, 0);
 }
 
@@ -126,6 +126,11 @@ hipError_t S2rPostChain::prepare(const S2rPostCtx &c, uint32_t n_buses, uint32_t
         POST_HIP(pinned_rows(loud.rows, loud.rows_dev, (size_t)(c.max_frames / S2R_LOUDNESS_MIN_HOP + 1u) * S2R_LOUDNESS_CHANNELS));
         POST_HIP(pinned_rows(loud.peaks, loud.peaks_dev, (size_t)((c.max_frames + S2R_LOUDNESS_BLOCK - 1u) / S2R_LOUDNESS_BLOCK) * 2u));
     }
+    if (pcm_on(call)) {                                          // the two copies of its state, its pinned samples and counts
+        POST_HIP(pcm.state.reserve(S2R_PCM_STATE));
+        POST_HIP(pinned_rows(pcm.samples, pcm.samples_dev, (size_t)S2R_PCM_PROGRAMMES * 2u * c.max_frames));
+        POST_HIP(pinned_rows(pcm.counts, pcm.counts_dev, S2R_PCM_CHANNELS));
+    }
     float *own[S2R_BUS_STAGES];
     for (int k = 0; k < S2R_BUS_STAGES; k++) own[k] = stage[k].buffer;
     // (with the meter on, whoever writes the master last writes it into the meter's input, and the meter's kernel writes the pinned output)
@@ -180,6 +185,17 @@ hipError_t S2rPostChain::launch(const S2rPostCtx &c, const S2rPostCall &call) {
         a.state = sp.state.now(); a.next = sp.state.next(); a.window = sp.tables; a.twiddles = sp.tables + n; a.rows = sp.rows_dev;
         a.n_buses = call.n_buses; a.frames = call.frames; a.n_fft = sp.n_fft; a.hop = sp.hop; a.pos = sp.pos;
         POST_TIMED(c, sp.timer, s2r_launch_spectrum(a, c.stream));
+    }
+    if (pcm_on(call)) {                                          // last of all: it copies the master out only when no meter kernel has
+        Pcm &pm = pcm;
+        POST_HIP(pm.state.upload(c.stream));
+        S2rPcm a{};
+        a.stems = r.master_in; a.master = call.limited ? r.limiter_out : r.master_out; a.out = loud_on(call) || spec_on(call) ? nullptr : c.out_host_dev;
+        a.state = pm.state.now(); a.next = pm.state.next(); a.pcm = pm.samples_dev; a.clips = pm.counts_dev;
+        std::memcpy(a.h, pm.h, sizeof a.h);
+        a.n_buses = call.n_buses; a.frames = call.frames; a.pstride = c.max_frames; a.bits = pm.bits; a.dither = pm.dither; a.n_taps = pm.n_taps;
+        a.seed = pm.seed; a.t = pm.t;
+        POST_TIMED(c, pm.timer, s2r_launch_pcm(a, c.stream));
     }
     return hipSuccess;
 }
@@ -334,6 +350,14 @@ void S2rPostChain::commit(const S2rPostCall &call) {
         sp.state.committed(); sp.tables_valid = true;
         sp.kept.take(sp.rows, sp.pos, call.frames, sp.hop);
     }
+    if (pcm_on(call)) {                                          // the state and t have moved on; the call's clips join the held ones
+        Pcm &pm = pcm;
+        pm.state.committed(); pm.t += call.frames; pm.frames = call.frames;
+        for (uint32_t q = 0; q < S2R_PCM_CHANNELS; q++) {
+            pm.clips_last[q] = pm.counts[q];
+            pm.clips_held[q] = pm.clips_held[q] + pm.counts[q] < pm.clips_held[q] ? UINT32_MAX : pm.clips_held[q] + pm.counts[q];
+        }
+    }
     if (loud_on(call)) {                                         // the state has moved on; the call's hops join the rows, its peaks the held ones
         Loudness &ld = loud;
         ld.state.committed();
@@ -359,6 +383,8 @@ hipError_t S2rPostChain::read_timers(const S2rPostCall &call) {
         if (loud_on(call)) POST_HIP(loud.timer.read());
         spec.timer.ms = 0.0f;
         if (spec_on(call)) POST_HIP(spec.timer.read());
+        pcm.timer.ms = 0.0f;
+        if (pcm_on(call)) POST_HIP(pcm.timer.read());
     }
     return hipSuccess;
 }
@@ -367,10 +393,12 @@ void S2rPostChain::release() {
     for (uint32_t b = 0; b < S2R_MAX_BUSES; b++) { drop(eq[b]); drop(dyn[b]); drop(drive[b]); drop(flanger[b]); drop(chorus[b]); drop(delay[b]); drop(fx[b]); drop(room[b]); }
     for (Stem &st : stage) { if (st.buffer) (void)hipFree(st.buffer); st.timer.destroy(); }
     // ... and what is neither a line nor a stage's buffer
-    for (S2rMirror *m : {&limiter.state, &loud.state, &spec.state}) m->free();
+    for (S2rMirror *m : {&limiter.state, &loud.state, &spec.state, &pcm.state}) m->free();
     for (float *p : {dyn_curves, drive_curves, master.stage, limiter.in, loud.in, spec.tables}) if (p) (void)hipFree(p);
     for (float *p : {dyn_meter, master.partials, limiter.partials, loud.rows, loud.peaks, spec.rows}) if (p) (void)hipHostFree(p);
-    for (S2rPostTimer *t : {&master.timer, &limiter.timer, &loud.timer, &spec.timer}) t->destroy();
+    if (pcm.samples) (void)hipHostFree(pcm.samples);
+    if (pcm.counts) (void)hipHostFree(pcm.counts);
+    for (S2rPostTimer *t : {&master.timer, &limiter.timer, &loud.timer, &spec.timer, &pcm.timer}) t->destroy();
 }
 
 hipError_t S2rPostChain::set_eq(const S2rPostCtx &c, uint32_t bus, uint32_t n_bands, const float *coeffs) {
@@ -578,3 +606,24 @@ void S2rPostChain::reset_spectrum() {
     sp.kept.clear();
 }
 
+void S2rPostChain::set_pcm(uint32_t bits, uint32_t dither, const float *taps, uint32_t n_taps, uint32_t seed) {
+    Pcm &pm = pcm;
+    pm.bits = bits; pm.dither = dither; pm.n_taps = bits ? n_taps : 0u; pm.seed = seed;
+    for (uint32_t k = 0; k < S2R_PCM_MAX_TAPS; k++) pm.h[k] = k < pm.n_taps ? taps[k] : 0.0f;
+    reset_pcm();
+    if (!bits) pm.state.off();
+}
+
+void S2rPostChain::reset_pcm() {
+    Pcm &pm = pcm;
+    pm.state.zero(S2R_PCM_STATE); pm.t = 0; pm.frames = 0;
+    for (uint32_t q = 0; q < S2R_PCM_CHANNELS; q++) pm.clips_last[q] = pm.clips_held[q] = 0u;
+}
+
+void S2rPostChain::set_pcm_state(const float *state, uint32_t t) {
+    Pcm &pm = pcm;
+    float st[S2R_PCM_STATE];
+    for (uint32_t i = 0; i < S2R_PCM_STATE; i++) st[i] = i % S2R_PCM_MAX_TAPS < pm.n_taps ? state[i] : 0.0f;
+    pm.state.set(st, S2R_PCM_STATE);
+    pm.t = t;
+}

@@ -1,7 +1,7 @@
 // s2r_post.h — the chain behind the bus mixdown of s2r_fill_buses and s2r_fill_master: the eight bus stages in the order of
 // S2rBusStage (s2r_post_route.h) — the buses' equalisers, their dynamics (4.22), drives (4.24), flangers (4.25),
 // choruses (4.20), feedback delays (4.19), convolution reverbs (4.16) and rooms (4.23) —, then the master section (4.17) and the master
-// limiter (4.18), and behind it the loudness and true-peak meters (4.26) and the spectrum meters (4.27).  The bus stages keep their
+// limiter (4.18), and behind it the loudness and true-peak meters (4.26), the spectrum meters (4.27) and the PCM stage (4.28).  The bus stages keep their
 // histories in a S2rBusLine each; the three stages behind the master fader keep their state in a S2rMirror each, and the two meters
 // their rows in a S2rRowStore each (s2r_post_keep.h).  The chain owns what these stages own and knows nothing of the handle: its
 // functions take a S2rPostCtx and return the HIP error.  Per call: prepare, launch, — the caller's synchronise — commit, read_timers.
@@ -191,10 +191,25 @@ struct S2rPostChain {
         S2rRowStore kept;                        // the rows kept: S2R_SPECTRUM_ROW(n_fft) floats each, at most max_rows of them
         S2rPostTimer timer;                      // around the spectrum kernel of the last master fill: 0 when it ran none (tools/spectrum_time.py)
     } spec;
+    // The PCM stage (s2r_set_master_pcm), behind the spectrum meters, the last of a master fill.  As theirs: nothing is
+    // allocated before the first master fill that finds the stage set, and a handle on which it never was set makes the launches it
+    // always did.
+    struct Pcm {
+        uint32_t bits = 0, dither = 0, n_taps = 0, seed = 0;     // bits 0: off
+        float h[S2R_PCM_MAX_TAPS] = {};          // +0.0 past n_taps
+        S2rMirror state;                         // S2R_PCM_STATE floats
+        uint32_t t = 0;                          // the frames converted since the set or reset, mod 2^32: the host's alone, and a kernel argument
+        int32_t *samples = nullptr, *samples_dev = nullptr;      // pinned and device-mapped: [9][max_frames][2]
+        uint32_t *counts = nullptr, *counts_dev = nullptr;       // pinned and device-mapped: [S2R_PCM_CHANNELS], the call's clips
+        uint32_t frames = 0;                     // the frames of the last successful fill that ran the stage: 0 before any
+        uint32_t clips_last[S2R_PCM_CHANNELS] = {}, clips_held[S2R_PCM_CHANNELS] = {};
+        S2rPostTimer timer;                      // around the PCM kernel of the last master fill: 0 when it ran none (tools/pcm_time.py)
+    } pcm;
     bool loud_on(const S2rPostCall &call) const { return call.master && loud.hop != 0; }
     bool spec_on(const S2rPostCall &call) const { return call.master && spec.n_fft != 0; }
-    // a meter behind the master: whoever writes the master last writes it to device memory (loud.in), and the first meter kernel copies it out
-    bool metered(const S2rPostCall &call) const { return loud_on(call) || spec_on(call); }
+    bool pcm_on(const S2rPostCall &call) const { return call.master && pcm.bits != 0; }
+    // a stage behind the master: whoever writes the master last writes it to device memory (loud.in), and the first kernel behind it copies it out
+    bool metered(const S2rPostCall &call) const { return loud_on(call) || spec_on(call) || pcm_on(call); }
     // one fill: what it runs, its once-only allocations and its route; the launches in order, each between its timer's marks; after
     // the synchronise that succeeded, and only then, histories, applied values and state move on and the meters fold
     hipError_t prepare(const S2rPostCtx &c, uint32_t n_buses, uint32_t frames, bool master_fill, bool stems, S2rPostCall &call);
@@ -237,4 +252,7 @@ struct S2rPostChain {
     void reset_loudness();                                          // state, rows and held true peak; the parameters stay
     void set_spectrum(uint32_t n_fft, uint32_t hop, const float *window, uint32_t max_rows);   // window null: off; else on, from the initial state
     void reset_spectrum();                                          // state and rows; the parameters stay
+    void set_pcm(uint32_t bits, uint32_t dither, const float *taps, uint32_t n_taps, uint32_t seed);     // bits 0: off; else on, from the initial state
+    void reset_pcm();                                               // state, t, counts and the last samples; the parameters stay
+    void set_pcm_state(const float *state, uint32_t t);             // the first n_taps errors of every row, +0.0 past them
 };

@@ -799,3 +799,83 @@ int s2r_spectrum_band_readings(const float *rows, size_t n_rows, uint32_t n_fft,
 }
 
 }  // extern "C"
+
+// ---- the master's PCM stage: dither, error-feedback noise shaping and rounding to B-bit integers ----
+extern "C" {
+
+static inline float pcm_clamp(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+int s2r_pcm_reference(uint32_t bits, uint32_t dither, const float *taps, uint32_t n_taps, uint32_t seed, const float *stems, uint32_t n_buses,
+                      const float *master_lr, uint32_t frames, float *state, uint32_t *t, int32_t *pcm, uint32_t *clips) {
+    if (!pcm_in_range(bits, dither, taps, n_taps) || n_buses > S2R_MAX_BUSES || !pcm_state_in_range(state)) return S2R_ERR_PATCH_RANGE;
+    if ((n_taps && !taps) || !state || !t || (frames && (!master_lr || !pcm || (n_buses && !stems)))) return S2R_ERR_INVALID;
+    const size_t N = frames;
+    const uint32_t K = n_taps;
+    const float G = std::ldexp(1.0f, (int)bits - 1), top = G - 1.0f;
+    for (uint32_t q = 0; q < S2R_PCM_CHANNELS; q++) {
+        const uint32_t p = q >> 1, c = q & 1u;
+        float *const e = state + (size_t)q * S2R_PCM_MAX_TAPS;   // e[k - 1] = e[n - k]
+        uint32_t n_clips = 0;
+        for (size_t n = 0; n < N; n++) {
+            const float x = p == S2R_MAX_BUSES ? master_lr[2 * n + c] : (p < n_buses ? stems[2 * (p * N + n) + c] : 0.0f);
+            const float xc = x != x ? 0.0f : pcm_clamp(x, -2.0f, 2.0f);
+            const float s = xc * G;
+            float f = 0.0f;
+            for (uint32_t k = K; k >= 1u; k--) {
+                const float h = taps[k - 1u] * e[k - 1u];
+                f = f + h;
+            }
+            const float w = s - f;
+            const float d = pcm_dither_value(seed, *t + (uint32_t)n, q, dither);
+            const float v = w + d;
+            const float r = std::nearbyint(v);                   // (the default rounding mode: to nearest, ties to even)
+            const float y = pcm_clamp(r, -G, top);
+            if (y != r) n_clips++;
+            pcm[2 * (p * N + n) + c] = (int32_t)y;
+            const float diff = y - w;
+            for (uint32_t k = S2R_PCM_MAX_TAPS - 1u; k >= 1u; k--) e[k] = k < K ? e[k - 1u] : 0.0f;
+            e[0] = K ? pcm_clamp(diff, -2.0f, 2.0f) : 0.0f;
+        }
+        if (clips) clips[q] = n_clips;
+    }
+    *t += frames;
+    return S2R_OK;
+}
+
+int s2r_pcm_dither(uint32_t seed, uint32_t t, uint32_t q, uint32_t kind, float *d) {
+    if (q >= S2R_PCM_CHANNELS || kind > S2R_DITHER_TRI) return S2R_ERR_PATCH_RANGE;
+    if (!d) return S2R_ERR_INVALID;
+    *d = pcm_dither_value(seed, t, q, kind);
+    return S2R_OK;
+}
+
+int s2r_pcm_pack(const int32_t *pcm, size_t count, uint32_t bits, uint32_t bytes_per_sample, uint8_t *out) {
+    const uint32_t B = bytes_per_sample;
+    if (bits < S2R_PCM_MIN_BITS || bits > S2R_PCM_MAX_BITS || B < 2u || B > 4u || 8u * B < bits) return S2R_ERR_PATCH_RANGE;
+    if (count && (!pcm || !out)) return S2R_ERR_INVALID;
+    const int32_t lo = -(int32_t)(1u << (bits - 1u)), hi = (int32_t)(1u << (bits - 1u)) - 1;
+    for (size_t i = 0; i < count; i++) {
+        if (pcm[i] < lo || pcm[i] > hi) return S2R_ERR_PATCH_RANGE;
+        const uint32_t u = (uint32_t)pcm[i] << (8u * B - bits);  // two's complement, left-justified; the bytes past the container fall away
+        for (uint32_t b = 0; b < B; b++) out[i * B + b] = (uint8_t)(u >> (8u * b));
+    }
+    return S2R_OK;
+}
+
+int s2r_pcm_shaper(uint32_t kind, float *taps, uint32_t *n_taps) {
+    static const float kSets[6][S2R_PCM_MAX_TAPS] = {
+        {},
+        {1.0f},
+        {2.0f, -1.0f},
+        {1.623f, -0.982f, 0.109f},
+        {2.033f, -2.165f, 1.959f, -1.590f, 0.6149f},
+        {2.412f, -3.370f, 3.937f, -4.174f, 3.353f, -2.205f, 1.281f, -0.569f, 0.0847f}};
+    static const uint32_t kCount[6] = {0u, 1u, 2u, 3u, 5u, 9u};
+    if (kind > S2R_SHAPER_9TAP) return S2R_ERR_PATCH_RANGE;
+    if (!taps || !n_taps) return S2R_ERR_INVALID;
+    std::memcpy(taps, kSets[kind], sizeof kSets[kind]);
+    *n_taps = kCount[kind];
+    return S2R_OK;
+}
+
+}  // extern "C"

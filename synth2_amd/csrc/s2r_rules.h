@@ -153,6 +153,31 @@ static inline bool spectrum_in_range(uint32_t n, uint32_t hop, const float *wind
 }
 static inline uint32_t spectrum_log2(uint32_t n) { uint32_t l = 0; while ((1u << l) < n) l++; return l; }
 
+// the master's PCM stage: the word length, the dither kind and the tap count in their ranges, every tap finite and at
+// most S2R_PCM_MAX_TAP in magnitude.  Null taps pass: the caller refuses them by another name.
+static inline bool pcm_in_range(uint32_t bits, uint32_t dither, const float *taps, uint32_t n_taps) {
+    if (bits < S2R_PCM_MIN_BITS || bits > S2R_PCM_MAX_BITS || dither > S2R_DITHER_TRI || n_taps > S2R_PCM_MAX_TAPS) return false;
+    for (uint32_t k = 0; k < n_taps && taps; k++) if (!(std::fabs(taps[k]) <= S2R_PCM_MAX_TAP)) return false;
+    return true;
+}
+// ... and a state of it: every shaped error within the clamp of the rule's step 6
+static inline bool pcm_state_in_range(const float *state) {
+    for (uint32_t i = 0; i < S2R_PCM_STATE && state; i++) if (!(std::fabs(state[i]) <= 2.0f)) return false;
+    return true;
+}
+// the rule's integer hash and its step 4: the dither of frame t_n and channel q, exact in binary32
+static inline uint32_t pcm_mix(uint32_t u) {
+    u ^= u >> 16; u *= 0x7feb352du; u ^= u >> 15; u *= 0x846ca68bu; u ^= u >> 16;
+    return u;
+}
+static inline float pcm_dither_value(uint32_t seed, uint32_t t_n, uint32_t q, uint32_t kind) {
+    const uint32_t k = pcm_mix(pcm_mix(t_n ^ seed) + q);
+    const int r1 = (int)(k >> 16), r2 = (int)(k & 0xffffu);
+    if (kind == S2R_DITHER_TRI) return (float)(r1 - r2) * 0x1p-16f;
+    if (kind == S2R_DITHER_RECT) return (float)(2 * r1 - 65535) * 0x1p-17f;
+    return 0.0f;
+}
+
 // The voice mixer's gain rules, inline: the host's per-voice loops compile them in — a call per voice into s2r_rules.cpp showed as 10
 // to 15 us of host time per fill of 65 536 voices (profiles/r12/post_chain.txt).  s2r_rules.cpp exports them under their s2r.h names.
 static inline float rule_voice_pan(float pan, float key_spread, uint8_t note) {

@@ -69,6 +69,12 @@ SPECTRUM_MIN_FFT, SPECTRUM_MAX_FFT = 256, 8192        # S2R_SPECTRUM_MIN_FFT, S2
 SPECTRUM_MIN_HOP, SPECTRUM_MAX_HOP = 16, 1 << 20      # S2R_SPECTRUM_MIN_HOP, S2R_SPECTRUM_MAX_HOP (and at least n_fft / 8)
 SPECTRUM_MAX_ROWS = 256                     # S2R_SPECTRUM_MAX_ROWS
 WINDOW_RECT, WINDOW_HANN, WINDOW_HAMMING, WINDOW_BLACKMAN_HARRIS = 0, 1, 2, 3      # S2R_WINDOW_*
+PCM_PROGRAMMES, PCM_CHANNELS, PCM_MAX_TAPS, PCM_STATE = 9, 18, 9, 162         # S2R_PCM_PROGRAMMES, S2R_PCM_CHANNELS, S2R_PCM_MAX_TAPS, S2R_PCM_STATE
+PCM_MIN_BITS, PCM_MAX_BITS, PCM_MAX_TAP = 8, 24, 16.0                    # S2R_PCM_MIN_BITS, S2R_PCM_MAX_BITS, S2R_PCM_MAX_TAP
+DITHER_NONE, DITHER_RECT, DITHER_TRI = 0, 1, 2                           # S2R_DITHER_*
+SHAPER_FLAT, SHAPER_FIRST, SHAPER_SECOND, SHAPER_3TAP, SHAPER_5TAP, SHAPER_9TAP = 0, 1, 2, 3, 4, 5       # S2R_SHAPER_*
+_DITHER_KINDS = {"none": DITHER_NONE, "rect": DITHER_RECT, "rpdf": DITHER_RECT, "rectangular": DITHER_RECT, "tri": DITHER_TRI, "tpdf": DITHER_TRI,
+                 "triangular": DITHER_TRI}
 _WINDOW_KINDS = {"rect": WINDOW_RECT, "rectangular": WINDOW_RECT, "hann": WINDOW_HANN, "hamming": WINDOW_HAMMING,
                  "blackman-harris": WINDOW_BLACKMAN_HARRIS, "blackmanharris": WINDOW_BLACKMAN_HARRIS}
 
@@ -337,6 +343,19 @@ def load_library():
                                                  C.POINTER(C.c_double), C.c_size_t, C.POINTER(C.c_size_t)]),
         "s2r_spectrum_window": (C.c_int, [C.c_uint32, C.c_uint32, _f32p]),
         "s2r_spectrum_twiddles": (C.c_int, [C.c_uint32, _f32p]),
+        "s2r_set_master_pcm": (C.c_int, [H, C.c_uint32, C.c_uint32, _f32p, C.c_uint32, C.c_uint32]),
+        "s2r_clear_master_pcm": (C.c_int, [H]),
+        "s2r_get_master_pcm": (C.c_int, [H, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _f32p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+        "s2r_reset_master_pcm": (C.c_int, [H]),
+        "s2r_get_pcm": (C.c_int, [H, C.c_uint32, C.POINTER(C.c_int32), C.c_size_t, C.POINTER(C.c_size_t)]),
+        "s2r_get_pcm_clips": (C.c_int, [H, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+        "s2r_get_pcm_state": (C.c_int, [H, _f32p, C.c_size_t, C.POINTER(C.c_uint32)]),
+        "s2r_set_pcm_state": (C.c_int, [H, _f32p, C.c_size_t, C.c_uint32]),
+        "s2r_pcm_reference": (C.c_int, [C.c_uint32, C.c_uint32, _f32p, C.c_uint32, C.c_uint32, _f32p, C.c_uint32, _f32p, C.c_uint32, _f32p, C.POINTER(C.c_uint32),
+                                        C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]),
+        "s2r_pcm_dither": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]),
+        "s2r_pcm_pack": (C.c_int, [C.POINTER(C.c_int32), C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint8)]),
+        "s2r_pcm_shaper": (C.c_int, [C.c_uint32, _f32p, C.POINTER(C.c_uint32)]),
         "s2r_fill_device": (C.c_int, [H, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
         "s2r_fill_device_root": (C.c_int, [H, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
         "s2r_sum_partials_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_size_t, C.c_void_p, C.c_void_p]),
@@ -794,6 +813,69 @@ def loudness_readings(rows, hop, programme):
     out = (C.c_double * 3)()
     _rule_check(load_library().s2r_loudness_readings(rows.ctypes.data_as(_f32p) if rows.shape[0] else None, rows.shape[0], int(hop), int(programme), out))
     return out[0], out[1], out[2]
+
+
+def _dither_arg(kind):
+    k = _DITHER_KINDS.get(kind.lower(), -1) if isinstance(kind, str) else int(kind)
+    if k < 0:
+        raise ValueError("dither is one of %s" % sorted(_DITHER_KINDS))
+    return k
+
+
+def pcm_shaper(kind):
+    """the error-feedback taps of shaper `kind` (a SHAPER_* value, 0 .. 5; s2r_pcm_shaper): float32 [n_taps]"""
+    taps, n = np.empty(PCM_MAX_TAPS, dtype=np.float32), C.c_uint32()
+    _rule_check(load_library().s2r_pcm_shaper(int(kind), taps.ctypes.data_as(_f32p), C.byref(n)))
+    return taps[:n.value].copy()
+
+
+def _shaper_arg(shaper):
+    if np.isscalar(shaper):
+        return pcm_shaper(shaper)
+    return np.ascontiguousarray(shaper, dtype=np.float32).reshape(-1)
+
+
+def pcm_dither(seed, t, q, kind="tpdf"):
+    """the PCM stage's dither of frame `t` and channel `q` in LSB (s2r_pcm_dither): a float"""
+    d = C.c_float()
+    _rule_check(load_library().s2r_pcm_dither(int(seed) & 0xffffffff, int(t) & 0xffffffff, int(q), _dither_arg(kind), C.byref(d)))
+    return d.value
+
+
+def pcm_pack(pcm, bits, bytes_per_sample):
+    """samples of `bits` bits into little-endian containers of 2, 3 or 4 bytes, left-justified (s2r_pcm_pack): uint8 [pcm.size *
+    bytes_per_sample], in the samples' C order"""
+    pcm = np.ascontiguousarray(pcm, dtype=np.int32)
+    out = np.zeros(pcm.size * max(int(bytes_per_sample), 0), dtype=np.uint8)
+    _rule_check(load_library().s2r_pcm_pack(pcm.ctypes.data_as(C.POINTER(C.c_int32)), pcm.size, int(bits), int(bytes_per_sample),
+                                            out.ctypes.data_as(C.POINTER(C.c_uint8))))
+    return out
+
+
+def pcm_reference(stems, master, bits=16, dither="tpdf", shaper=0, seed=0, state=None, t=0):
+    """the PCM stage's device rule on the host (s2r_pcm_reference): stems [n_buses, frames, 2] float32 (None: no buses), master
+    [frames, 2]; state [18, 9] and t what the call starts from (None: the initial state).  Returns (pcm int32 [9, frames, 2], state,
+    t, clips uint32 [18]); the arguments are not modified."""
+    taps = _shaper_arg(shaper)
+    master = np.ascontiguousarray(master, dtype=np.float32)
+    if master.ndim != 2 or master.shape[1] != 2:
+        raise ValueError("pcm_reference: master is [frames, 2]")
+    frames = master.shape[0]
+    if stems is None:
+        stems = np.zeros((0, frames, 2), dtype=np.float32)
+    stems = np.ascontiguousarray(stems, dtype=np.float32)
+    if stems.ndim != 3 or stems.shape[1:] != (frames, 2):
+        raise ValueError("pcm_reference: stems is [n_buses, frames, 2]")
+    state = np.zeros(PCM_STATE, dtype=np.float32) if state is None else np.array(state, dtype=np.float32, order="C").reshape(-1)
+    if state.size != PCM_STATE:
+        raise ValueError("pcm_reference: state is [18, 9]")
+    at = C.c_uint32(int(t) & 0xffffffff)
+    pcm, clips = np.zeros((PCM_PROGRAMMES, frames, 2), dtype=np.int32), np.zeros(PCM_CHANNELS, dtype=np.uint32)
+    _rule_check(load_library().s2r_pcm_reference(int(bits), _dither_arg(dither), taps.ctypes.data_as(_f32p) if taps.size else None, taps.size, int(seed) & 0xffffffff,
+                                                 stems.ctypes.data_as(_f32p) if stems.shape[0] else None, stems.shape[0], master.ctypes.data_as(_f32p), frames,
+                                                 state.ctypes.data_as(_f32p), C.byref(at), pcm.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                 clips.ctypes.data_as(C.POINTER(C.c_uint32))))
+    return pcm, state.reshape(PCM_CHANNELS, PCM_MAX_TAPS), at.value, clips
 
 
 def spectrum_window(kind, n_fft):
@@ -1802,6 +1884,68 @@ class Synth:
     @staticmethod
     def spectrum_twiddles(n_fft):
         return spectrum_twiddles(n_fft)
+
+    # --- the PCM stage (build-defined; s2r.h: s2r_set_master_pcm) ---
+    def set_master_pcm(self, bits=16, dither="tpdf", shaper=0, seed=0):
+        """integers of `bits` bits (8 .. 24) of every bus and the master, behind the spectrum meters, in sample_master only.  `dither`:
+        'none', 'rect' or 'tpdf' (or a DITHER_* value); `shaper`: a SHAPER_* kind or up to nine error-feedback taps; `seed`: the
+        dither's.  Starts from the initial state."""
+        taps = _shaper_arg(shaper)
+        self._check(self.L.s2r_set_master_pcm(self.h, int(bits), _dither_arg(dither), taps.ctypes.data_as(_f32p) if taps.size else None, taps.size,
+                                              int(seed) & 0xffffffff))
+
+    def clear_master_pcm(self):
+        self._check(self.L.s2r_clear_master_pcm(self.h))
+
+    def get_master_pcm(self):
+        """(bits, dither, taps [n_taps], seed): bits of 0 means off"""
+        b, d, n, sd = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+        taps = np.empty(PCM_MAX_TAPS, dtype=np.float32)
+        self._check(self.L.s2r_get_master_pcm(self.h, C.byref(b), C.byref(d), taps.ctypes.data_as(_f32p), C.byref(n), C.byref(sd)))
+        return b.value, d.value, taps[:n.value].copy(), sd.value
+
+    def reset_master_pcm(self):
+        """state, frame count and clip counts cleared; the parameters stay"""
+        self._check(self.L.s2r_reset_master_pcm(self.h))
+
+    def pcm(self, programme=MAX_BUSES):
+        """int32 [frames, 2]: the samples of bus `programme`, or of the master (MAX_BUSES), of the last sample_master call"""
+        out, n = np.empty((self.max_frames, 2), dtype=np.int32), C.c_size_t()
+        self._check(self.L.s2r_get_pcm(self.h, int(programme), out.ctypes.data_as(C.POINTER(C.c_int32)), out.size, C.byref(n)))
+        return out[:n.value].copy()
+
+    def pcm_clips(self):
+        """(last [18], held [18]) uint32: the clips per channel of the last sample_master call and since the set or reset"""
+        last, held = np.empty(PCM_CHANNELS, dtype=np.uint32), np.empty(PCM_CHANNELS, dtype=np.uint32)
+        u32p = C.POINTER(C.c_uint32)
+        self._check(self.L.s2r_get_pcm_clips(self.h, last.ctypes.data_as(u32p), held.ctypes.data_as(u32p)))
+        return last, held
+
+    def pcm_state(self):
+        """(state [18, 9], t): every channel's last nine shaped errors, newest first; the frames converted (checkpoints)"""
+        st, t = np.empty((PCM_CHANNELS, PCM_MAX_TAPS), dtype=np.float32), C.c_uint32()
+        self._check(self.L.s2r_get_pcm_state(self.h, st.ctypes.data_as(_f32p), st.size, C.byref(t)))
+        return st, t.value
+
+    def set_pcm_state(self, state, t):
+        st = np.ascontiguousarray(state, dtype=np.float32)
+        self._check(self.L.s2r_set_pcm_state(self.h, st.ctypes.data_as(_f32p), st.size, int(t) & 0xffffffff))
+
+    @staticmethod
+    def pcm_reference(stems, master, bits=16, dither="tpdf", shaper=0, seed=0, state=None, t=0):
+        return pcm_reference(stems, master, bits, dither, shaper, seed, state, t)
+
+    @staticmethod
+    def pcm_dither(seed, t, q, kind="tpdf"):
+        return pcm_dither(seed, t, q, kind)
+
+    @staticmethod
+    def pcm_pack(pcm, bits, bytes_per_sample):
+        return pcm_pack(pcm, bits, bytes_per_sample)
+
+    @staticmethod
+    def pcm_shaper(kind):
+        return pcm_shaper(kind)
 
     def render_voices(self, frames, sample_rate=SampleRateKhz(48000)):
         """Mix disabled: (shard_voices, frames) float32."""
