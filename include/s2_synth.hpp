@@ -396,6 +396,25 @@ class Synth {
     static int pcm_pack(const int32_t *pcm, size_t count, uint32_t bits, uint32_t bytes_per_sample, uint8_t *out) { return s2r_pcm_pack(pcm, count, bits, bytes_per_sample, out); }
     static int pcm_shaper(uint32_t kind, float *taps, uint32_t *n_taps) { return s2r_pcm_shaper(kind, taps, n_taps); }
 
+    // the sample-rate converter (build-defined; s2r.h: s2r_set_master_resampler): every bus and the master resampled by L / M through a
+    // polyphase table h[L][T], behind the spectrum meters and in front of the PCM stage, in fill_master only
+    void set_master_resampler(uint32_t L, uint32_t M, uint32_t T, const float *table) { check(s2r_set_master_resampler(h_, L, M, T, table)); }
+    void clear_master_resampler() { check(s2r_clear_master_resampler(h_)); }
+    // any pointer may be null; L of 0 means off; table receives L * T floats
+    void get_master_resampler(uint32_t *L, uint32_t *M, uint32_t *T, float *table) const { check(s2r_get_master_resampler(h_, L, M, T, table)); }
+    void reset_master_resampler() { check(s2r_reset_master_resampler(h_)); }
+    // the [frames][2] output frames of a programme (bus b, or S2R_MAX_BUSES for the master) of the last fill_master
+    void resampled(uint32_t programme, float *out_lr, size_t capacity, size_t *frames) const { check(s2r_get_resampled(h_, programme, out_lr, capacity, frames)); }
+    // checkpoints: the S2R_RESAMPLER_STATE(T) floats of history and the position
+    void resampler_state(float *state, size_t capacity, uint32_t *ph) { check(s2r_get_resampler_state(h_, state, capacity, ph)); }
+    void set_resampler_state(const float *state, size_t count, uint32_t ph) { check(s2r_set_resampler_state(h_, state, count, ph)); }
+    static int resampler_reference(uint32_t L, uint32_t M, uint32_t T, const float *table, const float *stems, uint32_t n_buses, const float *master_lr,
+                                   uint32_t frames, float *state, uint32_t *ph, float *out, size_t capacity, size_t *count) {
+        return s2r_resampler_reference(L, M, T, table, stems, n_buses, master_lr, frames, state, ph, out, capacity, count);
+    }
+    static int resampler_count(uint32_t L, uint32_t M, uint32_t ph, uint32_t frames, size_t *count) { return s2r_resampler_count(L, M, ph, frames, count); }
+    static int resampler_design(uint32_t L, uint32_t M, uint32_t T, double beta, double rolloff, float *table) { return s2r_resampler_design(L, M, T, beta, rolloff, table); }
+
     s2r_synth *handle() { return h_; }
 
   private:

@@ -57,7 +57,9 @@ extern "C" {
  * s2r_set_spectrum_rows, s2r_get_spectrum_state, s2r_set_spectrum_state, s2r_spectrum_reference, s2r_spectrum_readings,
  * s2r_spectrum_band_readings, s2r_spectrum_window, s2r_spectrum_twiddles, s2r_set_master_pcm, s2r_clear_master_pcm,
  * s2r_get_master_pcm, s2r_reset_master_pcm, s2r_get_pcm, s2r_get_pcm_clips, s2r_get_pcm_state, s2r_set_pcm_state,
- * s2r_pcm_reference, s2r_pcm_dither, s2r_pcm_pack, s2r_pcm_shaper. */
+ * s2r_pcm_reference, s2r_pcm_dither, s2r_pcm_pack, s2r_pcm_shaper, s2r_set_master_resampler, s2r_clear_master_resampler,
+ * s2r_get_master_resampler, s2r_reset_master_resampler, s2r_get_resampled, s2r_get_resampler_state, s2r_set_resampler_state,
+ * s2r_resampler_reference, s2r_resampler_count, s2r_resampler_design. */
 #define S2R_ABI_VERSION 4
 
 typedef enum {
@@ -1165,6 +1167,83 @@ int s2r_pcm_reference(uint32_t bits, uint32_t dither, const float *taps, uint32_
 int s2r_pcm_dither(uint32_t seed, uint32_t t, uint32_t q, uint32_t kind, float *d);
 int s2r_pcm_pack(const int32_t *pcm, size_t count, uint32_t bits, uint32_t bytes_per_sample, uint8_t *out);
 int s2r_pcm_shaper(uint32_t kind, float *taps, uint32_t *n_taps);
+
+/* BUILD-DEFINED master sample-rate converter (the reference renders at one rate): a polyphase FIR resampler by the
+ * rational ratio L / M of every bus and of the master, behind the spectrum meters and in front of the PCM stage, in s2r_fill_master
+ * and in no other fill.  Off by default, and a handle on which the stage was never set launches exactly what it launched before and
+ * allocates nothing; master_lr, the stems, the loudness rows and the spectrum rows are the same bits with the stage on or off.
+ * PROGRAMMES: S2R_RESAMPLER_PROGRAMMES = 9, the meters' and the PCM stage's: programme b < 8 is bus b as the stems hold it, programme 8
+ * the master as the caller receives it.  Channel q = 2 p + c, 18 of them.  A bus at or past the call's n_buses is fed +0.0; its
+ * history still rings out.
+ * PARAMETERS: L and M each in 1 .. S2R_RESAMPLER_MAX_FACTOR (320), gcd(L, M) == 1, L <= 4 M and M <= 4 L: the output rate is L / M
+ * of the input's.  T, the taps per phase: a multiple of 4 in 4 .. S2R_RESAMPLER_MAX_TAPS (128), with L * T <= S2R_RESAMPLER_MAX_TABLE
+ * (24 576).  The table h[L][T] is the caller's (s2r_resampler_design makes one): every entry finite and at most 4 in magnitude.  One
+ * table serves all 18 channels.
+ * STATE carried from call to call: S2R_RESAMPLER_STATE(T) = 18 * (T - 1) floats, row q = the channel's last T - 1 input frames,
+ * NEWEST first; and ph, the position of the next output in units of 1 / L input frame, counted from the first frame of the next
+ * call: 0 <= ph < M after any call.  All +0.0 / 0 right after a set or a reset.
+ * DEVICE RULE, binary32, every operation rounded on its own, no fma, denormals kept, NaN and infinities as the operations have them.
+ * Per call of F frames, x[n] the channel's frame n of the call and x[-j] its history's entry j - 1:
+ *   1. count = 0 if F * L <= ph, else ceil((F * L - ph) / M): the call's output frames
+ *   2. for output i < count: u = ph + i * M;  n = u / L;  p = u % L   (64-bit integers)
+ *   3. four accumulators a_0 .. a_3 from +0.0; for k = 0, 1, ..., T - 1 in ascending order: a_(k % 4) = a_(k % 4) + h[p][k] * x[n - k]
+ *   4. y[i] = (a_0 + a_1) + (a_2 + a_3)
+ *   5. ph' = ph + count * M - F * L; the new history is the last T - 1 frames of the history followed by the call
+ * The four chains and the final tree are part of the rule: they are four independent dependency chains for the kernel.  Every output
+ * frame, the state and ph are independent of how a stream is cut into calls.  A call makes at most
+ * S2R_RESAMPLER_MAX_OUT(frames, L, M) = ceil(frames * L / M) + 1 output frames.
+ * A resampled signal can exceed the limiter's ceiling between the original samples: the limiter bounds the samples it is given, not
+ * the band-limited curve through them.  The PCM stage behind clamps such a sample and counts it as a clip.
+ * WITH THE PCM STAGE ON TOO, its kernel runs on the resampler's output: all eight buses and the master, `count` frames a call, t
+ * counting output frames; its integers, state, t and clips are exactly s2r_pcm_reference over s2r_resampler_reference's nine
+ * programmes with n_buses = 8.  A call with count == 0 launches no PCM kernel: its state, t and held clips stay, and s2r_get_pcm
+ * answers 0 frames.  The PCM stage's pinned samples are sized for S2R_RESAMPLER_MAX_OUT(max_frames, L, M) frames then, and grown by a
+ * later fill that finds them short (which drops the samples of the last fill).  With the resampler off the PCM stage is as it was.
+ * A refused or failed call leaves table, state, ph and the last outputs as they were.  Single-device handles (a device list refuses
+ * every entry).  The first master fill that finds the stage set allocates the device's copy of the table, the two copies of the state
+ * and pinned outputs for [9][S2R_RESAMPLER_MAX_OUT(max_frames, L, M)][2] floats; a later fill that finds them short grows them.
+ *   s2r_set_master_resampler: S2R_ERR_PATCH_RANGE for L, M or T out of range or a table entry that is not finite or past 4 in
+ *   magnitude (checked before the handle is looked at; nothing is changed); S2R_ERR_INVALID for a NULL table.  Resets state and ph
+ *   and drops the last outputs.  s2r_clear_master_resampler: off.
+ *   s2r_get_master_resampler: any pointer may be NULL; L of 0 means off; table receives L * T floats (at most
+ *   S2R_RESAMPLER_MAX_TABLE: ask for L and T first).
+ *   s2r_reset_master_resampler: state and ph cleared and the last outputs dropped, parameters kept; S2R_ERR_INVALID with the stage off.
+ *   s2r_get_resampled: the [frames][2] outputs of `programme` (< 9, else S2R_ERR_PATCH_RANGE) of the last successful master fill that
+ *   ran the stage, into out_lr, which holds `capacity` floats (at least 2 * frames, else S2R_ERR_INVALID); *frames that fill's count,
+ *   which may be 0.  S2R_ERR_INVALID before any such fill, with the stage off or for NULL out_lr.
+ *   s2r_get_resampler_state / s2r_set_resampler_state (checkpoints): the floats and ph; the getter takes a capacity of at least
+ *   S2R_RESAMPLER_STATE(T), the setter exactly that many floats — any values, non-finite ones too — and ph < M (S2R_ERR_PATCH_RANGE
+ *   otherwise).  S2R_ERR_INVALID for a wrong size, a NULL buffer or with the stage off.
+ *   s2r_resampler_reference: the device rule on the host (no device, no handle).  stems [n_buses][frames][2] (NULL with n_buses 0),
+ *   master_lr [frames][2]; state[S2R_RESAMPLER_STATE(T)] and *ph updated in place; out [9][capacity][2] receives *count frames of
+ *   every programme.  S2R_ERR_PATCH_RANGE as the setter's, for n_buses > 8 and for *ph >= M; S2R_ERR_INVALID for a NULL or a
+ *   capacity below the call's count (nothing is written or changed then).
+ *   s2r_resampler_count: step 1 alone into *count; S2R_ERR_PATCH_RANGE for L or M out of range or ph >= M.
+ *   s2r_resampler_design: a Kaiser-windowed sinc, computed in binary64.  N = L T, c = (N - 1) / 2, fc = rolloff * 0.5 / max(L, M);
+ *   g[i] = 2 fc L sinc(2 fc (i - c)) * kaiser(i; N, beta), sinc(x) = sin(pi x) / (pi x), kaiser(i) = I0(beta sqrt(1 - ((i - c) / c)^2))
+ *   / I0(beta); h[p][k] = g[k L + p]; every row is divided by its own sum, so that no phase has a DC error, and then rounded to
+ *   binary32.  The filter delays by (L T - 1) / (2 L) input frames.  beta in [0, 20], rolloff in (0, 1], else S2R_ERR_PATCH_RANGE. */
+#define S2R_RESAMPLER_PROGRAMMES 9u
+#define S2R_RESAMPLER_CHANNELS 18u
+#define S2R_RESAMPLER_MAX_FACTOR 320u
+#define S2R_RESAMPLER_MIN_TAPS 4u
+#define S2R_RESAMPLER_MAX_TAPS 128u
+#define S2R_RESAMPLER_MAX_TABLE 24576u
+#define S2R_RESAMPLER_MAX_TAP 4.0f
+#define S2R_RESAMPLER_STATE(T) (S2R_RESAMPLER_CHANNELS * ((T) - 1u))
+#define S2R_RESAMPLER_MAX_OUT(frames, L, M) (((uint64_t)(frames) * (L) + (M) - 1u) / (M) + 1u)
+int s2r_set_master_resampler(s2r_synth *s, uint32_t L, uint32_t M, uint32_t T, const float *table);
+int s2r_clear_master_resampler(s2r_synth *s);
+int s2r_get_master_resampler(const s2r_synth *s, uint32_t *L, uint32_t *M, uint32_t *T, float *table);
+int s2r_reset_master_resampler(s2r_synth *s);
+int s2r_get_resampled(const s2r_synth *s, uint32_t programme, float *out_lr, size_t capacity, size_t *frames);
+int s2r_get_resampler_state(s2r_synth *s, float *state, size_t capacity, uint32_t *ph);
+int s2r_set_resampler_state(s2r_synth *s, const float *state, size_t count, uint32_t ph);
+int s2r_resampler_reference(uint32_t L, uint32_t M, uint32_t T, const float *table, const float *stems, uint32_t n_buses,
+                            const float *master_lr, uint32_t frames, float *state, uint32_t *ph, float *out, size_t capacity,
+                            size_t *count);
+int s2r_resampler_count(uint32_t L, uint32_t M, uint32_t ph, uint32_t frames, size_t *count);
+int s2r_resampler_design(uint32_t L, uint32_t M, uint32_t T, double beta, double rolloff, float *table);
 
 /* BUILD-DEFINED 4x oversampling (the reference has none; BASELINE config [4]): renders 4 * frames at
  * 4 * sample_rate_hz through the same path and decimates the mix by a 63-tap windowed sinc whose history

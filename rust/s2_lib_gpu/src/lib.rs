@@ -273,6 +273,17 @@ pub mod ffi {
         pub fn s2r_pcm_dither(seed: u32, t: u32, q: u32, kind: u32, d: *mut f32) -> c_int;
         pub fn s2r_pcm_pack(pcm: *const i32, count: usize, bits: u32, bytes_per_sample: u32, out: *mut u8) -> c_int;
         pub fn s2r_pcm_shaper(kind: u32, taps: *mut f32, n_taps: *mut u32) -> c_int;
+        pub fn s2r_set_master_resampler(s: *mut S2rSynth, l: u32, m: u32, t: u32, table: *const f32) -> c_int;
+        pub fn s2r_clear_master_resampler(s: *mut S2rSynth) -> c_int;
+        pub fn s2r_get_master_resampler(s: *const S2rSynth, l: *mut u32, m: *mut u32, t: *mut u32, table: *mut f32) -> c_int;
+        pub fn s2r_reset_master_resampler(s: *mut S2rSynth) -> c_int;
+        pub fn s2r_get_resampled(s: *const S2rSynth, programme: u32, out_lr: *mut f32, capacity: usize, frames: *mut usize) -> c_int;
+        pub fn s2r_get_resampler_state(s: *mut S2rSynth, state: *mut f32, capacity: usize, ph: *mut u32) -> c_int;
+        pub fn s2r_set_resampler_state(s: *mut S2rSynth, state: *const f32, count: usize, ph: u32) -> c_int;
+        pub fn s2r_resampler_reference(l: u32, m: u32, t: u32, table: *const f32, stems: *const f32, n_buses: u32, master_lr: *const f32,
+                                       frames: u32, state: *mut f32, ph: *mut u32, out: *mut f32, capacity: usize, count: *mut usize) -> c_int;
+        pub fn s2r_resampler_count(l: u32, m: u32, ph: u32, frames: u32, count: *mut usize) -> c_int;
+        pub fn s2r_resampler_design(l: u32, m: u32, t: u32, beta: f64, rolloff: f64, table: *mut f32) -> c_int;
         pub fn s2r_shard_voices(s: *const S2rSynth) -> u32;
         pub fn s2r_fill_device(s: *mut S2rSynth, dev_out: *mut f32, frames: usize, sample_rate_hz: u32,
                                hip_stream: *mut c_void) -> c_int;

@@ -30,7 +30,8 @@ SOURCES = ["s2r_render_onepole_square.hip", "s2r_render_onepole_saw.hip", "s2r_r
            "s2r_mixer.cpp",     # (likewise, since the voice mixer got a type of its own: host code only, no kernel)
            "s2r_host_mix.cpp",  # (likewise, since the host file was split: host code only, no kernel)
            "s2r_host_post.cpp", # (likewise)
-           "s2r_pcm.hip"]       # (last, likewise, since the PCM stage came)
+           "s2r_pcm.hip",       # (likewise, since the PCM stage came)
+           "s2r_resampler.hip"] # (last, likewise, since the sample-rate converter came)
 HEADERS = ["s2r_device.h", "s2r_math.h", "s2r_patch.h", "s2r_voices.h", "s2r_kern_common.h", "s2r_render_onepole.inc",
            "s2r_render_general.inc", "s2r_post.h", "s2r_post_route.h", "s2r_post_keep.h", "s2r_rules.h", "s2r_handle.h", "s2r_mixer.h",
            "s2r_mixer_keep.h"]
@@ -61,7 +62,7 @@ PER_FILE_FLAGS = {}
 for _f in ("s2r_render_general_square.hip", "s2r_render_general_saw.hip", "s2r_render_general_triangle.hip", "s2r_render_general_sine.hip",
            "s2r_render_general_bank.hip"):
     PER_FILE_FLAGS[_f] = ["-ftrivial-auto-var-init=zero"]
-# Thirteen translation units are compiled with the back end's resource-usage remarks, and _check_resources() fails the build when a
+# Fourteen translation units are compiled with the back end's resource-usage remarks, and _check_resources() fails the build when a
 # kernel named here went to scratch or spilled, or when fewer kernels report than the file instantiates.  Per source file: the
 # substrings that name its checked kernels; how many reports are expected — ("at least", n), ("exactly", n), or ("each", None):
 # one or more of every name — and why so many; the figures that must be "0"; and what the kernels keep where it belongs.  (The
@@ -114,6 +115,9 @@ RESOURCE_CHECKS = {
     # a tile, their eighteen dither values
     "s2r_pcm.hip": (("s2r_pcm_kernel",), ("exactly", 1), "one kernel",
                     (_SCRATCH, _VSPILL, _SSPILL), "its sums, errors and the values read ahead must stay in registers, the tiles in LDS"),
+    # an output frame per lane: eight accumulators, four taps and four frames of a step
+    "s2r_resampler.hip": (("s2r_resampler_kernel",), ("exactly", 1), "one kernel",
+                          (_SCRATCH, _VSPILL, _SSPILL), "the four chains of both channels must stay in registers, the rows and the span in LDS"),
 }
 for _f in RESOURCE_CHECKS:
     PER_FILE_FLAGS[_f] = ["-Rpass-analysis=kernel-resource-usage"]
@@ -170,6 +174,11 @@ if _SPECTRUM_SERIAL:
 _PCM_SERIAL = os.environ.get("S2R_PCM_SERIAL") == "1"
 if _PCM_SERIAL:
     PER_FILE_FLAGS["s2r_pcm.hip"] = PER_FILE_FLAGS["s2r_pcm.hip"] + ["-DS2R_PCM_SERIAL"]
+# S2R_RESAMPLER_SERIAL=1 likewise builds the resampler kernel's obvious form (every lane reads its table row and its input frames from
+# global memory; csrc/s2r_resampler.hip, CHANGELOG) into libs2r_resamplerserial.so, for tools/resampler_time.py.  Never the product build.
+_RESAMPLER_SERIAL = os.environ.get("S2R_RESAMPLER_SERIAL") == "1"
+if _RESAMPLER_SERIAL:
+    PER_FILE_FLAGS["s2r_resampler.hip"] = PER_FILE_FLAGS["s2r_resampler.hip"] + ["-DS2R_RESAMPLER_SERIAL"]
 # S2R_OPT=O3 in the environment builds the same sources at -O3 into libs2r_o3.so (tools and tests that compare the two
 # optimisation levels; the product is -O2).
 if os.environ.get("S2R_OPT") == "O3":
@@ -210,6 +219,9 @@ elif _SPECTRUM_SERIAL:
 elif _PCM_SERIAL:
     LIB = os.path.join(HERE, "libs2r_pcmserial.so")
     OBJ_DIR_NAME = "_build_pcmserial"
+elif _RESAMPLER_SERIAL:
+    LIB = os.path.join(HERE, "libs2r_resamplerserial.so")
+    OBJ_DIR_NAME = "_build_resamplerserial"
 else:
     OBJ_DIR_NAME = "_build"
 

@@ -679,3 +679,24 @@ struct S2rPcm {
     uint32_t n_buses, frames, pstride, bits, dither, n_taps, seed, t;
 };
 hipError_t s2r_launch_pcm(const S2rPcm &a, hipStream_t stream);
+
+// The sample-rate converter of s2r_fill_master: one launch behind the spectrum kernel (or, without the meters, behind
+// whoever wrote the master last) and in front of the PCM kernel.  It reads the stems from the master's device stage and the master from
+// device memory, writes the call's `count` output frames of all nine programmes to the pinned outputs — and, when the PCM stage runs
+// behind it, to device memory in the layout that kernel's launch reads — and the OTHER copy of the state, and — only when no meter kernel
+// did it — copies the master to the pinned output (`out` null: somebody else has).  The host flips the copies after a synchronise that
+// succeeded.  `ph` and `count` are the host's.
+#define S2R_RESAMPLER_TILE 64u                      // output frames of one workgroup, a lane each
+#define S2R_RESAMPLER_COPY_BLOCK 1024u              // frames of one copying workgroup
+struct S2rResampler {
+    const float *stems;           // [n_buses][2 * frames] in device memory: the master kernel's input
+    const float *master;          // [frames][2] in device memory
+    float *out;                   // interleaved L, R: 2 * frames floats (mapped host memory), or null
+    const float *state;           // [S2R_RESAMPLER_STATE(T)]: the state the call starts from
+    float *next;                  // ... and the state it leaves (never the buffer above)
+    const float *table;           // [L][T] in device memory
+    float *res;                   // [9][out_cap][2] (mapped host memory): the call's outputs, programme-major
+    float *res_dev;               // [9][count][2] in device memory: the same for the PCM kernel, or null
+    uint32_t n_buses, frames, L, M, T, ph, count, out_cap;
+};
+hipError_t s2r_launch_resampler(const S2rResampler &a, hipStream_t stream);

@@ -1,5 +1,5 @@
 // s2r_host_post.cpp — the C entries of libs2r in front of the post-mix chain (s2r_post.h; include/s2r.h): the eight bus stages, bus
-// returns, master fader, limiter, both meters and the PCM stage, and the chain's measurement getters.  The chain owns what they set; what is
+// returns, master fader, limiter, both meters, the sample-rate converter and the PCM stage, and the chain's measurement getters.  The chain owns what they set; what is
 // here checks the caller's values and the handle (s2r_handle.h).  Compiled with hipcc, -ffp-contract=off.
 #include "s2r_handle.h"
 
@@ -788,10 +788,10 @@ int s2r_reset_master_pcm(s2r_synth *s) {
 
 int s2r_get_pcm(const s2r_synth *s, uint32_t programme, int32_t *pcm_lr, size_t capacity, size_t *frames) {
     if (programme >= S2R_PCM_PROGRAMMES) return S2R_ERR_PATCH_RANGE;
-    if (!s || !s->kids.empty() || s->parent || !s->post.pcm.bits || !s->post.pcm.frames || !pcm_lr) return S2R_ERR_INVALID;
+    if (!s || !s->kids.empty() || s->parent || !s->post.pcm.bits || !s->post.pcm.have || !pcm_lr) return S2R_ERR_INVALID;
     const S2rPostChain::Pcm &pm = s->post.pcm;
     if (capacity < 2u * (size_t)pm.frames) return S2R_ERR_INVALID;
-    std::memcpy(pcm_lr, pm.samples + (size_t)programme * 2u * s->cfg.max_frames, 2u * (size_t)pm.frames * sizeof(int32_t));
+    if (pm.frames) std::memcpy(pcm_lr, pm.samples + (size_t)programme * 2u * pm.cap, 2u * (size_t)pm.frames * sizeof(int32_t));
     put(frames, (size_t)pm.frames);
     return S2R_OK;
 }
@@ -821,6 +821,77 @@ int s2r_set_pcm_state(s2r_synth *s, const float *state, size_t count, uint32_t t
     if (!state) return set_err(s, S2R_ERR_INVALID, "s2r_set_pcm_state: null buffer");
     if (!pcm_state_in_range(state)) return set_err(s, S2R_ERR_PATCH_RANGE, "s2r_set_pcm_state: an error outside [-2, 2]");
     s->post.set_pcm_state(state, t);
+    return S2R_OK;
+}
+
+// ---- the sample-rate converter behind the spectrum meters and in front of the PCM stage ----
+// the guard of the entries that need the stage set
+static int resampler_set(const s2r_synth *s, const char *who) {
+    S2R_TRY(post_handle(s, who, "the sample-rate converter is"));
+    if (!s->post.res.L) return set_err(const_cast<s2r_synth *>(s), S2R_ERR_INVALID, "%s: no master resampler is set", who);
+    return S2R_OK;
+}
+
+int s2r_set_master_resampler(s2r_synth *s, uint32_t L, uint32_t M, uint32_t T, const float *table) {
+    if (!resampler_in_range(L, M, T, table))
+        return set_err(s, S2R_ERR_PATCH_RANGE, "master resampler: %u / %u with %u taps a phase: coprime factors of 1 .. %u within 1/4 .. 4, taps a multiple of 4 in %u .. %u, at most %u finite entries of at most %g",
+                       L, M, T, S2R_RESAMPLER_MAX_FACTOR, S2R_RESAMPLER_MIN_TAPS, S2R_RESAMPLER_MAX_TAPS, S2R_RESAMPLER_MAX_TABLE, (double)S2R_RESAMPLER_MAX_TAP);
+    S2R_TRY(post_handle(s, "s2r_set_master_resampler", "the sample-rate converter is"));
+    if (!table) return set_err(s, S2R_ERR_INVALID, "s2r_set_master_resampler: no table");
+    s->post.set_resampler(L, M, T, table);
+    return S2R_OK;
+}
+
+int s2r_clear_master_resampler(s2r_synth *s) {
+    S2R_TRY(post_handle(s, "s2r_clear_master_resampler", "the sample-rate converter is"));
+    s->post.set_resampler(0, 0, 0, nullptr);
+    return S2R_OK;
+}
+
+int s2r_get_master_resampler(const s2r_synth *s, uint32_t *L, uint32_t *M, uint32_t *T, float *table) {
+    if (!s || !s->kids.empty() || s->parent) return S2R_ERR_INVALID;
+    const S2rPostChain::Resampler &rs = s->post.res;
+    if (table && !rs.table.empty()) std::memcpy(table, rs.table.data(), rs.table.size() * sizeof(float));
+    put(L, rs.L); put(M, rs.M); put(T, rs.T);
+    return S2R_OK;
+}
+
+int s2r_reset_master_resampler(s2r_synth *s) {
+    S2R_TRY(resampler_set(s, "s2r_reset_master_resampler"));
+    s->post.reset_resampler();
+    return S2R_OK;
+}
+
+int s2r_get_resampled(const s2r_synth *s, uint32_t programme, float *out_lr, size_t capacity, size_t *frames) {
+    if (programme >= S2R_RESAMPLER_PROGRAMMES) return S2R_ERR_PATCH_RANGE;
+    if (!s || !s->kids.empty() || s->parent || !s->post.res.L || !s->post.res.have || !out_lr) return S2R_ERR_INVALID;
+    const S2rPostChain::Resampler &rs = s->post.res;
+    if (capacity < 2u * (size_t)rs.count) return S2R_ERR_INVALID;
+    if (rs.count) std::memcpy(out_lr, rs.res + (size_t)programme * 2u * rs.cap, 2u * (size_t)rs.count * sizeof(float));
+    put(frames, (size_t)rs.count);
+    return S2R_OK;
+}
+
+int s2r_get_resampler_state(s2r_synth *s, float *state, size_t capacity, uint32_t *ph) {
+    S2R_TRY(resampler_set(s, "s2r_get_resampler_state"));
+    S2rPostChain::Resampler &rs = s->post.res;
+    const size_t n = S2R_RESAMPLER_STATE(rs.T);
+    if (capacity < n) return set_err(s, S2R_ERR_INVALID, "s2r_get_resampler_state: the state is %zu floats, not %zu", n, capacity);
+    if (!state) return set_err(s, S2R_ERR_INVALID, "s2r_get_resampler_state: null buffer");
+    S2R_TRY(mirror_fetch(s, rs.state, "s2r_get_resampler_state"));
+    std::memcpy(state, rs.state.host.data(), n * sizeof(float));
+    put(ph, rs.ph);
+    return S2R_OK;
+}
+
+int s2r_set_resampler_state(s2r_synth *s, const float *state, size_t count, uint32_t ph) {
+    S2R_TRY(resampler_set(s, "s2r_set_resampler_state"));
+    const S2rPostChain::Resampler &rs = s->post.res;
+    const size_t n = S2R_RESAMPLER_STATE(rs.T);
+    if (count != n) return set_err(s, S2R_ERR_INVALID, "s2r_set_resampler_state: the state is %zu floats, not %zu", n, count);
+    if (!state) return set_err(s, S2R_ERR_INVALID, "s2r_set_resampler_state: null buffer");
+    if (ph >= rs.M) return set_err(s, S2R_ERR_PATCH_RANGE, "s2r_set_resampler_state: a position of %u at M = %u", ph, rs.M);
+    s->post.set_resampler_state(state, ph);
     return S2R_OK;
 }
 
@@ -871,5 +942,10 @@ float s2r_debug_spectrum_ms(const s2r_synth *s) { return POST_MS(spec.timer); }
 float s2r_debug_pcm_ms(const s2r_synth *s) { return POST_MS(pcm.timer); }
 int s2r_debug_pcm_allocated(const s2r_synth *s) { return s && (s->post.pcm.samples || s->post.pcm.counts || s->post.pcm.state.dev[0] || s->post.loud.in) ? 1 : 0; }
 uint32_t s2r_debug_pcm_tile(void) { return S2R_PCM_TILE; }
+// ... and of the resampler kernel in that fill: 0 when it ran none (tools/resampler_time.py); whether the handle holds anything of the
+// stage's; and the output frames of one of the kernel's workgroups (tests/test_gpu_resampler.py picks its call lengths around it)
+float s2r_debug_resampler_ms(const s2r_synth *s) { return POST_MS(res.timer); }
+int s2r_debug_resampler_allocated(const s2r_synth *s) { return s && (s->post.res.res || s->post.res.res_dev || s->post.res.table_dev || s->post.res.state.dev[0] || s->post.loud.in) ? 1 : 0; }
+uint32_t s2r_debug_resampler_tile(void) { return S2R_RESAMPLER_TILE; }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
-// s2r_post.cpp — the post-mix chain (s2r_post.h): the eight bus stages (EQs, dynamics, drives, flangers, choruses, delays, reverbs, rooms), master section, master limiter, loudness meters, spectrum meters, PCM stage —
-// the last four on the device side of s2r_post_keep.h (S2rMirror).  Compiled with hipcc, -ffp-contract=off.
+// s2r_post.cpp — the post-mix chain (s2r_post.h): the eight bus stages (EQs, dynamics, drives, flangers, choruses, delays, reverbs, rooms), master section, master limiter, loudness meters, spectrum meters, sample-rate converter, PCM stage —
+// the last five on the device side of s2r_post_keep.h (S2rMirror).  Compiled with hipcc, -ffp-contract=off.
 #include "s2r_post.h"
 #include "s2r_rules.h"
 
@@ -126,9 +126,40 @@ hipError_t S2rPostChain::prepare(const S2rPostCtx &c, uint32_t n_buses, uint32_t
         POST_HIP(pinned_rows(loud.rows, loud.rows_dev, (size_t)(c.max_frames / S2R_LOUDNESS_MIN_HOP + 1u) * S2R_LOUDNESS_CHANNELS));
         POST_HIP(pinned_rows(loud.peaks, loud.peaks_dev, (size_t)((c.max_frames + S2R_LOUDNESS_BLOCK - 1u) / S2R_LOUDNESS_BLOCK) * 2u));
     }
+    if (res_on(call)) {                                          // the two copies of its state, the table and the outputs, by L, M and T
+        Resampler &rs = res;
+        const size_t need_table = (size_t)rs.L * rs.T;
+        const uint32_t need_cap = (uint32_t)S2R_RESAMPLER_MAX_OUT(c.max_frames, rs.L, rs.M);
+        rs.call_count = (uint32_t)resampler_count(rs.L, rs.M, rs.ph, frames);
+        POST_HIP(rs.state.reserve(S2R_RESAMPLER_STATE(rs.T)));
+        if (rs.table_floats < need_table) {
+            if (rs.table_dev) (void)hipFree(rs.table_dev);
+            rs.table_dev = nullptr; rs.table_floats = 0; rs.table_valid = false;
+            POST_HIP(hipMalloc((void **)&rs.table_dev, need_table * sizeof(float)));
+            rs.table_floats = need_table;
+        }
+        if (rs.cap < need_cap) {
+            if (rs.res) (void)hipHostFree(rs.res);
+            rs.res = rs.res_map = nullptr; rs.cap = 0; rs.have = false; rs.count = 0;
+            POST_HIP(pinned_rows(rs.res, rs.res_map, (size_t)S2R_RESAMPLER_PROGRAMMES * 2u * need_cap));
+            rs.cap = need_cap;
+        }
+        if (pcm_on(call) && rs.dev_cap < need_cap) {             // what the PCM kernel reads behind it
+            if (rs.res_dev) (void)hipFree(rs.res_dev);
+            rs.res_dev = nullptr; rs.dev_cap = 0;
+            POST_HIP(hipMalloc((void **)&rs.res_dev, (size_t)S2R_RESAMPLER_PROGRAMMES * 2u * need_cap * sizeof(float)));
+            rs.dev_cap = need_cap;
+        }
+    }
     if (pcm_on(call)) {                                          // the two copies of its state, its pinned samples and counts
+        const uint32_t need = res_on(call) ? (uint32_t)S2R_RESAMPLER_MAX_OUT(c.max_frames, res.L, res.M) : c.max_frames;
         POST_HIP(pcm.state.reserve(S2R_PCM_STATE));
-        POST_HIP(pinned_rows(pcm.samples, pcm.samples_dev, (size_t)S2R_PCM_PROGRAMMES * 2u * c.max_frames));
+        if (pcm.cap < need) {                                    // (a regrowth drops the last fill's samples)
+            if (pcm.samples) (void)hipHostFree(pcm.samples);
+            pcm.samples = pcm.samples_dev = nullptr; pcm.cap = 0; pcm.have = false; pcm.frames = 0;
+            POST_HIP(pinned_rows(pcm.samples, pcm.samples_dev, (size_t)S2R_PCM_PROGRAMMES * 2u * need));
+            pcm.cap = need;
+        }
         POST_HIP(pinned_rows(pcm.counts, pcm.counts_dev, S2R_PCM_CHANNELS));
     }
     float *own[S2R_BUS_STAGES];
@@ -186,15 +217,30 @@ hipError_t S2rPostChain::launch(const S2rPostCtx &c, const S2rPostCall &call) {
         a.n_buses = call.n_buses; a.frames = call.frames; a.n_fft = sp.n_fft; a.hop = sp.hop; a.pos = sp.pos;
         POST_TIMED(c, sp.timer, s2r_launch_spectrum(a, c.stream));
     }
-    if (pcm_on(call)) {                                          // last of all: it copies the master out only when no meter kernel has
+    if (res_on(call)) {                                          // behind the meters: it copies the master out only when no meter kernel has
+        Resampler &rs = res;
+        if (!rs.table_valid)                                     // (stays so until the commit)
+            POST_HIP(hipMemcpyAsync(rs.table_dev, rs.table.data(), rs.table.size() * sizeof(float), hipMemcpyHostToDevice, c.stream));
+        POST_HIP(rs.state.upload(c.stream));
+        S2rResampler a{};
+        a.stems = r.master_in; a.master = call.limited ? r.limiter_out : r.master_out; a.out = loud_on(call) || spec_on(call) ? nullptr : c.out_host_dev;
+        a.state = rs.state.now(); a.next = rs.state.next(); a.table = rs.table_dev; a.res = rs.res_map; a.res_dev = pcm_runs(call) ? rs.res_dev : nullptr;
+        a.n_buses = call.n_buses; a.frames = call.frames; a.L = rs.L; a.M = rs.M; a.T = rs.T; a.ph = rs.ph; a.count = rs.call_count; a.out_cap = rs.cap;
+        POST_TIMED(c, rs.timer, s2r_launch_resampler(a, c.stream));
+    }
+    if (pcm_runs(call)) {                                        // last of all: it copies the master out only when no kernel behind the master has
         Pcm &pm = pcm;
         POST_HIP(pm.state.upload(c.stream));
         S2rPcm a{};
         a.stems = r.master_in; a.master = call.limited ? r.limiter_out : r.master_out; a.out = loud_on(call) || spec_on(call) ? nullptr : c.out_host_dev;
         a.state = pm.state.now(); a.next = pm.state.next(); a.pcm = pm.samples_dev; a.clips = pm.counts_dev;
         std::memcpy(a.h, pm.h, sizeof a.h);
-        a.n_buses = call.n_buses; a.frames = call.frames; a.pstride = c.max_frames; a.bits = pm.bits; a.dither = pm.dither; a.n_taps = pm.n_taps;
+        a.n_buses = call.n_buses; a.frames = call.frames; a.pstride = pm.cap; a.bits = pm.bits; a.dither = pm.dither; a.n_taps = pm.n_taps;
         a.seed = pm.seed; a.t = pm.t;
+        if (res_on(call)) {                                      // the resampler's output: all eight buses, then the master, `count` frames each
+            a.stems = res.res_dev; a.master = res.res_dev + (size_t)2 * S2R_MAX_BUSES * res.call_count; a.out = nullptr;
+            a.n_buses = S2R_MAX_BUSES; a.frames = res.call_count;
+        }
         POST_TIMED(c, pm.timer, s2r_launch_pcm(a, c.stream));
     }
     return hipSuccess;
@@ -350,13 +396,24 @@ void S2rPostChain::commit(const S2rPostCall &call) {
         sp.state.committed(); sp.tables_valid = true;
         sp.kept.take(sp.rows, sp.pos, call.frames, sp.hop);
     }
-    if (pcm_on(call)) {                                          // the state and t have moved on; the call's clips join the held ones
+    if (pcm_runs(call)) {                                        // the state and t have moved on; the call's clips join the held ones
         Pcm &pm = pcm;
-        pm.state.committed(); pm.t += call.frames; pm.frames = call.frames;
+        const uint32_t made = res_on(call) ? res.call_count : call.frames;
+        pm.state.committed(); pm.t += made; pm.frames = made; pm.have = true;
         for (uint32_t q = 0; q < S2R_PCM_CHANNELS; q++) {
             pm.clips_last[q] = pm.counts[q];
             pm.clips_held[q] = pm.clips_held[q] + pm.counts[q] < pm.clips_held[q] ? UINT32_MAX : pm.clips_held[q] + pm.counts[q];
         }
+    } else if (pcm_on(call)) {                                   // the resampler made no frame: no kernel ran, state, t and the held clips stay
+        Pcm &pm = pcm;
+        pm.frames = 0; pm.have = true;
+        for (uint32_t q = 0; q < S2R_PCM_CHANNELS; q++) pm.clips_last[q] = 0u;
+    }
+    if (res_on(call)) {                                          // the state and ph have moved on
+        Resampler &rs = res;
+        rs.state.committed(); rs.table_valid = true;
+        rs.ph = (uint32_t)((uint64_t)rs.ph + (uint64_t)rs.call_count * rs.M - (uint64_t)call.frames * rs.L);
+        rs.count = rs.call_count; rs.have = true;
     }
     if (loud_on(call)) {                                         // the state has moved on; the call's hops join the rows, its peaks the held ones
         Loudness &ld = loud;
@@ -383,8 +440,10 @@ hipError_t S2rPostChain::read_timers(const S2rPostCall &call) {
         if (loud_on(call)) POST_HIP(loud.timer.read());
         spec.timer.ms = 0.0f;
         if (spec_on(call)) POST_HIP(spec.timer.read());
+        res.timer.ms = 0.0f;
+        if (res_on(call)) POST_HIP(res.timer.read());
         pcm.timer.ms = 0.0f;
-        if (pcm_on(call)) POST_HIP(pcm.timer.read());
+        if (pcm_runs(call)) POST_HIP(pcm.timer.read());
     }
     return hipSuccess;
 }
@@ -393,12 +452,12 @@ void S2rPostChain::release() {
     for (uint32_t b = 0; b < S2R_MAX_BUSES; b++) { drop(eq[b]); drop(dyn[b]); drop(drive[b]); drop(flanger[b]); drop(chorus[b]); drop(delay[b]); drop(fx[b]); drop(room[b]); }
     for (Stem &st : stage) { if (st.buffer) (void)hipFree(st.buffer); st.timer.destroy(); }
     // ... and what is neither a line nor a stage's buffer
-    for (S2rMirror *m : {&limiter.state, &loud.state, &spec.state, &pcm.state}) m->free();
-    for (float *p : {dyn_curves, drive_curves, master.stage, limiter.in, loud.in, spec.tables}) if (p) (void)hipFree(p);
-    for (float *p : {dyn_meter, master.partials, limiter.partials, loud.rows, loud.peaks, spec.rows}) if (p) (void)hipHostFree(p);
+    for (S2rMirror *m : {&limiter.state, &loud.state, &spec.state, &pcm.state, &res.state}) m->free();
+    for (float *p : {dyn_curves, drive_curves, master.stage, limiter.in, loud.in, spec.tables, res.table_dev, res.res_dev}) if (p) (void)hipFree(p);
+    for (float *p : {dyn_meter, master.partials, limiter.partials, loud.rows, loud.peaks, spec.rows, res.res}) if (p) (void)hipHostFree(p);
     if (pcm.samples) (void)hipHostFree(pcm.samples);
     if (pcm.counts) (void)hipHostFree(pcm.counts);
-    for (S2rPostTimer *t : {&master.timer, &limiter.timer, &loud.timer, &spec.timer, &pcm.timer}) t->destroy();
+    for (S2rPostTimer *t : {&master.timer, &limiter.timer, &loud.timer, &spec.timer, &pcm.timer, &res.timer}) t->destroy();
 }
 
 hipError_t S2rPostChain::set_eq(const S2rPostCtx &c, uint32_t bus, uint32_t n_bands, const float *coeffs) {
@@ -616,7 +675,7 @@ void S2rPostChain::set_pcm(uint32_t bits, uint32_t dither, const float *taps, ui
 
 void S2rPostChain::reset_pcm() {
     Pcm &pm = pcm;
-    pm.state.zero(S2R_PCM_STATE); pm.t = 0; pm.frames = 0;
+    pm.state.zero(S2R_PCM_STATE); pm.t = 0; pm.frames = 0; pm.have = false;
     for (uint32_t q = 0; q < S2R_PCM_CHANNELS; q++) pm.clips_last[q] = pm.clips_held[q] = 0u;
 }
 
@@ -626,4 +685,24 @@ void S2rPostChain::set_pcm_state(const float *state, uint32_t t) {
     for (uint32_t i = 0; i < S2R_PCM_STATE; i++) st[i] = i % S2R_PCM_MAX_TAPS < pm.n_taps ? state[i] : 0.0f;
     pm.state.set(st, S2R_PCM_STATE);
     pm.t = t;
+}
+
+void S2rPostChain::set_resampler(uint32_t L, uint32_t M, uint32_t T, const float *table) {
+    Resampler &rs = res;
+    rs.L = table ? L : 0u; rs.M = table ? M : 0u; rs.T = table ? T : 0u;
+    if (table) rs.table.assign(table, table + (size_t)L * T);
+    else rs.table.clear();
+    rs.table_valid = false;
+    if (table) reset_resampler();
+    else { rs.state.off(); rs.ph = 0; rs.have = false; rs.count = 0; }
+}
+
+void S2rPostChain::reset_resampler() {
+    Resampler &rs = res;
+    rs.state.zero(S2R_RESAMPLER_STATE(rs.T)); rs.ph = 0; rs.have = false; rs.count = 0;
+}
+
+void S2rPostChain::set_resampler_state(const float *state, uint32_t ph) {
+    res.state.set(state, S2R_RESAMPLER_STATE(res.T));
+    res.ph = ph;
 }

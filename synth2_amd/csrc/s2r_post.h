@@ -1,7 +1,7 @@
 // s2r_post.h — the chain behind the bus mixdown of s2r_fill_buses and s2r_fill_master: the eight bus stages in the order of
 // S2rBusStage (s2r_post_route.h) — the buses' equalisers, their dynamics (4.22), drives (4.24), flangers (4.25),
 // choruses (4.20), feedback delays (4.19), convolution reverbs (4.16) and rooms (4.23) —, then the master section (4.17) and the master
-// limiter (4.18), and behind it the loudness and true-peak meters (4.26), the spectrum meters (4.27) and the PCM stage (4.28).  The bus stages keep their
+// limiter (4.18), and behind it the loudness and true-peak meters (4.26), the spectrum meters (4.27), the sample-rate converter (4.29) and the PCM stage (4.28).  The bus stages keep their
 // histories in a S2rBusLine each; the three stages behind the master fader keep their state in a S2rMirror each, and the two meters
 // their rows in a S2rRowStore each (s2r_post_keep.h).  The chain owns what these stages own and knows nothing of the handle: its
 // functions take a S2rPostCtx and return the HIP error.  Per call: prepare, launch, — the caller's synchronise — commit, read_timers.
@@ -199,17 +199,41 @@ struct S2rPostChain {
         float h[S2R_PCM_MAX_TAPS] = {};          // +0.0 past n_taps
         S2rMirror state;                         // S2R_PCM_STATE floats
         uint32_t t = 0;                          // the frames converted since the set or reset, mod 2^32: the host's alone, and a kernel argument
-        int32_t *samples = nullptr, *samples_dev = nullptr;      // pinned and device-mapped: [9][max_frames][2]
+        int32_t *samples = nullptr, *samples_dev = nullptr;      // pinned and device-mapped: [9][cap][2]
+        uint32_t cap = 0;                        // max_frames, or the resampler's S2R_RESAMPLER_MAX_OUT when a fill found that set: grown, never shrunk
+        bool have = false;                       // a master fill has run the stage since the set or reset: `frames` (0 with the resampler in front) is its
         uint32_t *counts = nullptr, *counts_dev = nullptr;       // pinned and device-mapped: [S2R_PCM_CHANNELS], the call's clips
-        uint32_t frames = 0;                     // the frames of the last successful fill that ran the stage: 0 before any
+        uint32_t frames = 0;                     // the frames of the last successful fill that ran the stage
         uint32_t clips_last[S2R_PCM_CHANNELS] = {}, clips_held[S2R_PCM_CHANNELS] = {};
         S2rPostTimer timer;                      // around the PCM kernel of the last master fill: 0 when it ran none (tools/pcm_time.py)
     } pcm;
+    // The sample-rate converter (s2r_set_master_resampler), behind the spectrum meters and in front of the PCM stage.  As
+    // theirs: nothing is allocated before the first master fill that finds the stage set — and what is allocated then is sized by L, M
+    // and T, and grown by a later fill that finds them larger —, and a handle on which it never was set makes the launches it always did.
+    struct Resampler {
+        uint32_t L = 0, M = 0, T = 0;            // L 0: off
+        std::vector<float> table;                // [L][T], the host's; the device's copy is good while table_valid
+        bool table_valid = false;
+        float *table_dev = nullptr;              // device memory, table_floats
+        size_t table_floats = 0;
+        S2rMirror state;                         // S2R_RESAMPLER_STATE(T) floats
+        uint32_t ph = 0;                         // the next output's position in 1 / L input frames: the host's alone, and a kernel argument
+        float *res = nullptr, *res_map = nullptr;                // pinned and device-mapped: [9][cap][2], the call's outputs
+        float *res_dev = nullptr;                // device memory, [9][cap][2]: the PCM kernel's input, allocated when a fill finds both stages set
+        uint32_t cap = 0, dev_cap = 0;           // S2R_RESAMPLER_MAX_OUT(max_frames, L, M) when they were allocated
+        uint32_t call_count = 0;                 // the output frames of the call under way (prepare)
+        bool have = false;                       // a master fill has run the stage since the set or reset: `count` is its
+        uint32_t count = 0;
+        S2rPostTimer timer;                      // around the resampler kernel of the last master fill: 0 when it ran none (tools/resampler_time.py)
+    } res;
     bool loud_on(const S2rPostCall &call) const { return call.master && loud.hop != 0; }
     bool spec_on(const S2rPostCall &call) const { return call.master && spec.n_fft != 0; }
+    bool res_on(const S2rPostCall &call) const { return call.master && res.L != 0; }
     bool pcm_on(const S2rPostCall &call) const { return call.master && pcm.bits != 0; }
+    // the PCM kernel runs in the call: behind the resampler only when that makes a frame
+    bool pcm_runs(const S2rPostCall &call) const { return pcm_on(call) && (!res_on(call) || res.call_count != 0); }
     // a stage behind the master: whoever writes the master last writes it to device memory (loud.in), and the first kernel behind it copies it out
-    bool metered(const S2rPostCall &call) const { return loud_on(call) || spec_on(call) || pcm_on(call); }
+    bool metered(const S2rPostCall &call) const { return loud_on(call) || spec_on(call) || res_on(call) || pcm_on(call); }
     // one fill: what it runs, its once-only allocations and its route; the launches in order, each between its timer's marks; after
     // the synchronise that succeeded, and only then, histories, applied values and state move on and the meters fold
     hipError_t prepare(const S2rPostCtx &c, uint32_t n_buses, uint32_t frames, bool master_fill, bool stems, S2rPostCall &call);
@@ -255,4 +279,7 @@ struct S2rPostChain {
     void set_pcm(uint32_t bits, uint32_t dither, const float *taps, uint32_t n_taps, uint32_t seed);     // bits 0: off; else on, from the initial state
     void reset_pcm();                                               // state, t, counts and the last samples; the parameters stay
     void set_pcm_state(const float *state, uint32_t t);             // the first n_taps errors of every row, +0.0 past them
+    void set_resampler(uint32_t L, uint32_t M, uint32_t T, const float *table);        // table null: off; else on, from the initial state
+    void reset_resampler();                                         // state, ph and the last outputs; the parameters stay
+    void set_resampler_state(const float *state, uint32_t ph);
 };

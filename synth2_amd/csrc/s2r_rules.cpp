@@ -879,3 +879,81 @@ int s2r_pcm_shaper(uint32_t kind, float *taps, uint32_t *n_taps) {
 }
 
 }  // extern "C"
+
+// ---- the master's sample-rate converter: a polyphase FIR by the rational ratio L / M ----
+extern "C" {
+
+int s2r_resampler_count(uint32_t L, uint32_t M, uint32_t ph, uint32_t frames, size_t *count) {
+    if (!resampler_ratio_in_range(L, M) || ph >= M) return S2R_ERR_PATCH_RANGE;
+    if (!count) return S2R_ERR_INVALID;
+    *count = (size_t)resampler_count(L, M, ph, frames);
+    return S2R_OK;
+}
+
+int s2r_resampler_reference(uint32_t L, uint32_t M, uint32_t T, const float *table, const float *stems, uint32_t n_buses, const float *master_lr,
+                            uint32_t frames, float *state, uint32_t *ph, float *out, size_t capacity, size_t *count) {
+    if (!resampler_in_range(L, M, T, table) || n_buses > S2R_MAX_BUSES || (ph && *ph >= M)) return S2R_ERR_PATCH_RANGE;
+    if (!table || !state || !ph || !count || (frames && (!master_lr || (n_buses && !stems)))) return S2R_ERR_INVALID;
+    const size_t N = frames, H = T - 1u;
+    const uint64_t made = resampler_count(L, M, *ph, frames);
+    if (made > capacity || (made && !out)) return S2R_ERR_INVALID;
+    std::vector<float> xs(H + N);                                // the channel's history, oldest first, then the call: x[n] = xs[H + n]
+    for (uint32_t q = 0; q < S2R_RESAMPLER_CHANNELS; q++) {
+        const uint32_t p = q >> 1, c = q & 1u;
+        float *const hist = state + (size_t)q * H;               // hist[j - 1] = x[-j]
+        for (size_t j = 0; j < H; j++) xs[H - 1u - j] = hist[j];
+        for (size_t n = 0; n < N; n++) xs[H + n] = p == S2R_MAX_BUSES ? master_lr[2 * n + c] : (p < n_buses ? stems[2 * (p * N + n) + c] : 0.0f);
+        for (uint64_t i = 0; i < made; i++) {
+            const uint64_t u = (uint64_t)*ph + i * M;
+            const size_t n = (size_t)(u / L);
+            const float *const h = table + (size_t)(u % L) * T;
+            const float *const x = xs.data() + H + n;            // x[-k]: the frame k in front of frame n
+            float a[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            for (uint32_t k = 0; k < T; k++) {
+                const float t = h[k] * x[-(ptrdiff_t)k];
+                a[k & 3u] = a[k & 3u] + t;
+            }
+            const float lo = a[0] + a[1], hi = a[2] + a[3];
+            out[2 * ((size_t)p * capacity + (size_t)i) + c] = lo + hi;
+        }
+        for (size_t j = 0; j < H; j++) hist[j] = xs[H + N - 1u - j];
+    }
+    *ph = (uint32_t)((uint64_t)*ph + made * M - (uint64_t)frames * L);
+    *count = (size_t)made;
+    return S2R_OK;
+}
+
+// the modified Bessel function of the first kind and order 0, by its power series: every term positive, so no cancellation
+static double resampler_i0(double x) {
+    const double q = x * x * 0.25;
+    double term = 1.0, sum = 1.0;
+    for (int k = 1; k < 500; k++) {
+        term *= q / ((double)k * (double)k);
+        sum += term;
+        if (term < sum * 1e-18) break;
+    }
+    return sum;
+}
+
+int s2r_resampler_design(uint32_t L, uint32_t M, uint32_t T, double beta, double rolloff, float *table) {
+    if (!resampler_in_range(L, M, T, nullptr) || !(beta >= 0.0 && beta <= 20.0) || !(rolloff > 0.0 && rolloff <= 1.0)) return S2R_ERR_PATCH_RANGE;
+    if (!table) return S2R_ERR_INVALID;
+    const double kPi = 3.14159265358979323846;
+    const size_t N = (size_t)L * T;
+    const double c = ((double)N - 1.0) * 0.5, fc = rolloff * 0.5 / (double)(L > M ? L : M), i0b = resampler_i0(beta);
+    std::vector<double> g(N);
+    for (size_t i = 0; i < N; i++) {
+        const double d = (double)i - c, x = 2.0 * fc * d, r = d / c;
+        const double sinc = x == 0.0 ? 1.0 : std::sin(kPi * x) / (kPi * x);
+        const double inside = 1.0 - r * r;
+        g[i] = 2.0 * fc * (double)L * sinc * (resampler_i0(beta * std::sqrt(inside > 0.0 ? inside : 0.0)) / i0b);
+    }
+    for (uint32_t p = 0; p < L; p++) {
+        double sum = 0.0;
+        for (uint32_t k = 0; k < T; k++) sum += g[(size_t)k * L + p];
+        for (uint32_t k = 0; k < T; k++) table[(size_t)p * T + k] = (float)(g[(size_t)k * L + p] / sum);
+    }
+    return S2R_OK;
+}
+
+}  // extern "C"

@@ -178,6 +178,25 @@ static inline float pcm_dither_value(uint32_t seed, uint32_t t_n, uint32_t q, ui
     return 0.0f;
 }
 
+// the master's sample-rate converter: the ratio, the taps per phase and the table's size in their ranges, every entry of
+// the table finite and at most S2R_RESAMPLER_MAX_TAP in magnitude.  A null table passes: the caller refuses it by another name.
+static inline bool resampler_ratio_in_range(uint32_t L, uint32_t M) {
+    if (L < 1u || L > S2R_RESAMPLER_MAX_FACTOR || M < 1u || M > S2R_RESAMPLER_MAX_FACTOR || L > 4u * M || M > 4u * L) return false;
+    uint32_t a = L, b = M;
+    while (b) { const uint32_t r = a % b; a = b; b = r; }
+    return a == 1u;
+}
+static inline bool resampler_in_range(uint32_t L, uint32_t M, uint32_t T, const float *table) {
+    if (!resampler_ratio_in_range(L, M) || T < S2R_RESAMPLER_MIN_TAPS || T > S2R_RESAMPLER_MAX_TAPS || T % 4u || L * T > S2R_RESAMPLER_MAX_TABLE) return false;
+    for (uint32_t i = 0; i < L * T && table; i++) if (!(std::fabs(table[i]) <= S2R_RESAMPLER_MAX_TAP)) return false;
+    return true;
+}
+// the rule's step 1: the output frames of a call of `frames` frames that starts at ph
+static inline uint64_t resampler_count(uint32_t L, uint32_t M, uint32_t ph, uint32_t frames) {
+    const uint64_t span = (uint64_t)frames * L;
+    return span <= ph ? 0u : (span - ph + M - 1u) / M;
+}
+
 // The voice mixer's gain rules, inline: the host's per-voice loops compile them in — a call per voice into s2r_rules.cpp showed as 10
 // to 15 us of host time per fill of 65 536 voices (profiles/r12/post_chain.txt).  s2r_rules.cpp exports them under their s2r.h names.
 static inline float rule_voice_pan(float pan, float key_spread, uint8_t note) {

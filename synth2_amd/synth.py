@@ -73,6 +73,9 @@ PCM_PROGRAMMES, PCM_CHANNELS, PCM_MAX_TAPS, PCM_STATE = 9, 18, 9, 162         # 
 PCM_MIN_BITS, PCM_MAX_BITS, PCM_MAX_TAP = 8, 24, 16.0                    # S2R_PCM_MIN_BITS, S2R_PCM_MAX_BITS, S2R_PCM_MAX_TAP
 DITHER_NONE, DITHER_RECT, DITHER_TRI = 0, 1, 2                           # S2R_DITHER_*
 SHAPER_FLAT, SHAPER_FIRST, SHAPER_SECOND, SHAPER_3TAP, SHAPER_5TAP, SHAPER_9TAP = 0, 1, 2, 3, 4, 5       # S2R_SHAPER_*
+RESAMPLER_PROGRAMMES, RESAMPLER_CHANNELS = 9, 18                         # S2R_RESAMPLER_PROGRAMMES, S2R_RESAMPLER_CHANNELS
+RESAMPLER_MAX_FACTOR, RESAMPLER_MIN_TAPS, RESAMPLER_MAX_TAPS = 320, 4, 128         # S2R_RESAMPLER_MAX_FACTOR, S2R_RESAMPLER_MIN_TAPS, S2R_RESAMPLER_MAX_TAPS
+RESAMPLER_MAX_TABLE, RESAMPLER_MAX_TAP = 24576, 4.0                      # S2R_RESAMPLER_MAX_TABLE, S2R_RESAMPLER_MAX_TAP
 _DITHER_KINDS = {"none": DITHER_NONE, "rect": DITHER_RECT, "rpdf": DITHER_RECT, "rectangular": DITHER_RECT, "tri": DITHER_TRI, "tpdf": DITHER_TRI,
                  "triangular": DITHER_TRI}
 _WINDOW_KINDS = {"rect": WINDOW_RECT, "rectangular": WINDOW_RECT, "hann": WINDOW_HANN, "hamming": WINDOW_HAMMING,
@@ -356,6 +359,17 @@ def load_library():
         "s2r_pcm_dither": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]),
         "s2r_pcm_pack": (C.c_int, [C.POINTER(C.c_int32), C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint8)]),
         "s2r_pcm_shaper": (C.c_int, [C.c_uint32, _f32p, C.POINTER(C.c_uint32)]),
+        "s2r_set_master_resampler": (C.c_int, [H, C.c_uint32, C.c_uint32, C.c_uint32, _f32p]),
+        "s2r_clear_master_resampler": (C.c_int, [H]),
+        "s2r_get_master_resampler": (C.c_int, [H, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _f32p]),
+        "s2r_reset_master_resampler": (C.c_int, [H]),
+        "s2r_get_resampled": (C.c_int, [H, C.c_uint32, _f32p, C.c_size_t, C.POINTER(C.c_size_t)]),
+        "s2r_get_resampler_state": (C.c_int, [H, _f32p, C.c_size_t, C.POINTER(C.c_uint32)]),
+        "s2r_set_resampler_state": (C.c_int, [H, _f32p, C.c_size_t, C.c_uint32]),
+        "s2r_resampler_reference": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, _f32p, _f32p, C.c_uint32, _f32p, C.c_uint32, _f32p, C.POINTER(C.c_uint32), _f32p,
+                                              C.c_size_t, C.POINTER(C.c_size_t)]),
+        "s2r_resampler_count": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t)]),
+        "s2r_resampler_design": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_double, _f32p]),
         "s2r_fill_device": (C.c_int, [H, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
         "s2r_fill_device_root": (C.c_int, [H, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
         "s2r_sum_partials_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_size_t, C.c_void_p, C.c_void_p]),
@@ -876,6 +890,59 @@ def pcm_reference(stems, master, bits=16, dither="tpdf", shaper=0, seed=0, state
                                                  state.ctypes.data_as(_f32p), C.byref(at), pcm.ctypes.data_as(C.POINTER(C.c_int32)),
                                                  clips.ctypes.data_as(C.POINTER(C.c_uint32))))
     return pcm, state.reshape(PCM_CHANNELS, PCM_MAX_TAPS), at.value, clips
+
+
+def resampler_state_floats(T):
+    """S2R_RESAMPLER_STATE(T): 18 rows of T - 1 frames"""
+    return RESAMPLER_CHANNELS * (int(T) - 1)
+
+
+def resampler_max_out(frames, L, M):
+    """S2R_RESAMPLER_MAX_OUT: the most output frames of a call of `frames` frames"""
+    return (int(frames) * int(L) + int(M) - 1) // int(M) + 1
+
+
+def resampler_count(L, M, ph, frames):
+    """the output frames of a call of `frames` frames that starts at position ph (s2r_resampler_count)"""
+    n = C.c_size_t()
+    _rule_check(load_library().s2r_resampler_count(int(L), int(M), int(ph), int(frames), C.byref(n)))
+    return n.value
+
+
+def resampler_design(L, M, T, beta=10.0, rolloff=0.9):
+    """a Kaiser-windowed sinc for the ratio L / M with T taps a phase (s2r_resampler_design): float32 [L, T], every row of sum 1"""
+    table = np.zeros((max(int(L), 0), max(int(T), 0)), dtype=np.float32)
+    _rule_check(load_library().s2r_resampler_design(int(L), int(M), int(T), float(beta), float(rolloff), table.ctypes.data_as(_f32p)))
+    return table
+
+
+def resampler_reference(stems, master, L, M, table, state=None, ph=0):
+    """the resampler's device rule on the host (s2r_resampler_reference): stems [n_buses, frames, 2] float32 (None: no buses), master
+    [frames, 2]; table [L, T]; state [18, T - 1] and ph what the call starts from (None: the initial state).  Returns (out float32
+    [9, count, 2], state, ph); the arguments are not modified."""
+    table = np.ascontiguousarray(table, dtype=np.float32)
+    if table.ndim != 2:
+        raise ValueError("resampler_reference: table is [L, T]")
+    T = table.shape[1]
+    master = np.ascontiguousarray(master, dtype=np.float32)
+    if master.ndim != 2 or master.shape[1] != 2:
+        raise ValueError("resampler_reference: master is [frames, 2]")
+    frames = master.shape[0]
+    if stems is None:
+        stems = np.zeros((0, frames, 2), dtype=np.float32)
+    stems = np.ascontiguousarray(stems, dtype=np.float32)
+    if stems.ndim != 3 or stems.shape[1:] != (frames, 2):
+        raise ValueError("resampler_reference: stems is [n_buses, frames, 2]")
+    n_state = max(resampler_state_floats(T), 0)
+    state = np.zeros(n_state, dtype=np.float32) if state is None else np.array(state, dtype=np.float32, order="C").reshape(-1)
+    if state.size != n_state or table.shape[0] != int(L):
+        raise ValueError("resampler_reference: table is [L, T] and state [18, T - 1]")
+    cap = resampler_max_out(frames, L, max(int(M), 1))
+    out, at, n = np.zeros((RESAMPLER_PROGRAMMES, cap, 2), dtype=np.float32), C.c_uint32(int(ph)), C.c_size_t()
+    _rule_check(load_library().s2r_resampler_reference(int(L), int(M), T, table.ctypes.data_as(_f32p), stems.ctypes.data_as(_f32p) if stems.shape[0] else None,
+                                                       stems.shape[0], master.ctypes.data_as(_f32p), frames, state.ctypes.data_as(_f32p), C.byref(at),
+                                                       out.ctypes.data_as(_f32p), cap, C.byref(n)))
+    return out[:, :n.value].copy(), state.reshape(RESAMPLER_CHANNELS, T - 1), at.value
 
 
 def spectrum_window(kind, n_fft):
@@ -1910,7 +1977,10 @@ class Synth:
 
     def pcm(self, programme=MAX_BUSES):
         """int32 [frames, 2]: the samples of bus `programme`, or of the master (MAX_BUSES), of the last sample_master call"""
-        out, n = np.empty((self.max_frames, 2), dtype=np.int32), C.c_size_t()
+        l, m = C.c_uint32(), C.c_uint32()                        # (behind the resampler a call can make more frames than it was given)
+        self._check(self.L.s2r_get_master_resampler(self.h, C.byref(l), C.byref(m), None, None))
+        most = max(self.max_frames, resampler_max_out(self.max_frames, l.value, m.value) if l.value else 0)
+        out, n = np.empty((most, 2), dtype=np.int32), C.c_size_t()
         self._check(self.L.s2r_get_pcm(self.h, int(programme), out.ctypes.data_as(C.POINTER(C.c_int32)), out.size, C.byref(n)))
         return out[:n.value].copy()
 
@@ -1946,6 +2016,64 @@ class Synth:
     @staticmethod
     def pcm_shaper(kind):
         return pcm_shaper(kind)
+
+    # --- the sample-rate converter (build-defined; s2r.h: s2r_set_master_resampler) ---
+    def set_master_resampler(self, L, M, table):
+        """every bus and the master resampled by L / M through the polyphase table [L, T] (resampler_design makes one), behind the
+        spectrum meters and in front of the PCM stage, in sample_master only.  Starts from the initial state."""
+        table = np.ascontiguousarray(table, dtype=np.float32)
+        if table.ndim != 2 or table.shape[0] != int(L):
+            raise ValueError("set_master_resampler: table is [L, T]")
+        self._check(self.L.s2r_set_master_resampler(self.h, int(L), int(M), table.shape[1], table.ctypes.data_as(_f32p)))
+
+    def clear_master_resampler(self):
+        self._check(self.L.s2r_clear_master_resampler(self.h))
+
+    def get_master_resampler(self):
+        """(L, M, table [L, T]): L of 0 means off (and the table is None)"""
+        l, m, t = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        self._check(self.L.s2r_get_master_resampler(self.h, C.byref(l), C.byref(m), C.byref(t), None))
+        if not l.value:
+            return 0, 0, None
+        table = np.empty((l.value, t.value), dtype=np.float32)
+        self._check(self.L.s2r_get_master_resampler(self.h, None, None, None, table.ctypes.data_as(_f32p)))
+        return l.value, m.value, table
+
+    def reset_master_resampler(self):
+        """history and position cleared; the parameters stay"""
+        self._check(self.L.s2r_reset_master_resampler(self.h))
+
+    def resampled(self, programme=MAX_BUSES):
+        """float32 [count, 2]: the resampled frames of bus `programme`, or of the master (MAX_BUSES), of the last sample_master call"""
+        l, m = C.c_uint32(), C.c_uint32()
+        self._check(self.L.s2r_get_master_resampler(self.h, C.byref(l), C.byref(m), None, None))
+        out, n = np.empty((resampler_max_out(self.max_frames, l.value, max(m.value, 1)), 2), dtype=np.float32), C.c_size_t()
+        self._check(self.L.s2r_get_resampled(self.h, int(programme), out.ctypes.data_as(_f32p), out.size, C.byref(n)))
+        return out[:n.value].copy()
+
+    def resampler_state(self):
+        """(state [18, T - 1], ph): every channel's last T - 1 input frames, newest first; the next output's position (checkpoints)"""
+        t, ph = C.c_uint32(), C.c_uint32()
+        self._check(self.L.s2r_get_master_resampler(self.h, None, None, C.byref(t), None))
+        st = np.empty((RESAMPLER_CHANNELS, max(t.value, 1) - 1), dtype=np.float32)
+        self._check(self.L.s2r_get_resampler_state(self.h, st.ctypes.data_as(_f32p), st.size, C.byref(ph)))
+        return st, ph.value
+
+    def set_resampler_state(self, state, ph):
+        st = np.ascontiguousarray(state, dtype=np.float32)
+        self._check(self.L.s2r_set_resampler_state(self.h, st.ctypes.data_as(_f32p), st.size, int(ph)))
+
+    @staticmethod
+    def resampler_reference(stems, master, L, M, table, state=None, ph=0):
+        return resampler_reference(stems, master, L, M, table, state, ph)
+
+    @staticmethod
+    def resampler_count(L, M, ph, frames):
+        return resampler_count(L, M, ph, frames)
+
+    @staticmethod
+    def resampler_design(L, M, T, beta=10.0, rolloff=0.9):
+        return resampler_design(L, M, T, beta, rolloff)
 
     def render_voices(self, frames, sample_rate=SampleRateKhz(48000)):
         """Mix disabled: (shard_voices, frames) float32."""
