@@ -304,6 +304,12 @@ class Synth {
     // the master limiter (build-defined; s2r.h: s2r_set_master_limiter): a look-ahead limiter behind the master fader, in sample_master
     // only — no sample of master_lr exceeds `ceiling`, and master_lr is delayed by `lookahead` frames (the stems are not)
     void set_master_limiter(float ceiling, uint32_t lookahead, uint32_t hold = 0) { check(s2r_set_master_limiter(h_, ceiling, lookahead, hold)); }
+    // ... with the true-peak detector (s2r.h: s2r_set_master_limiter_ex): the gain follows the 4x-interpolated magnitude, master_lr is
+    // delayed by lookahead + S2R_LIMITER_TP_LATENCY frames, and xh below is 2 * (lookahead + S2R_LIMITER_TP_HISTORY) floats
+    void set_master_limiter_true_peak(float ceiling, uint32_t lookahead, uint32_t hold = 0) {
+        check(s2r_set_master_limiter_ex(h_, ceiling, lookahead, hold, S2R_LIMITER_TRUE_PEAK));
+    }
+    uint32_t get_master_limiter_detector() const { uint32_t d = 0; check(s2r_get_master_limiter_detector(h_, &d)); return d; }
     void clear_master_limiter() { check(s2r_clear_master_limiter(h_)); }
     // a lookahead of 0 means off
     void get_master_limiter(float *ceiling, uint32_t *lookahead, uint32_t *hold) const { check(s2r_get_master_limiter(h_, ceiling, lookahead, hold)); }

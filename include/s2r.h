@@ -59,7 +59,8 @@ extern "C" {
  * s2r_get_master_pcm, s2r_reset_master_pcm, s2r_get_pcm, s2r_get_pcm_clips, s2r_get_pcm_state, s2r_set_pcm_state,
  * s2r_pcm_reference, s2r_pcm_dither, s2r_pcm_pack, s2r_pcm_shaper, s2r_set_master_resampler, s2r_clear_master_resampler,
  * s2r_get_master_resampler, s2r_reset_master_resampler, s2r_get_resampled, s2r_get_resampler_state, s2r_set_resampler_state,
- * s2r_resampler_reference, s2r_resampler_count, s2r_resampler_design. */
+ * s2r_resampler_reference, s2r_resampler_count, s2r_resampler_design, s2r_set_master_limiter_ex, s2r_get_master_limiter_detector,
+ * s2r_limiter_tp_reference. */
 #define S2R_ABI_VERSION 4
 
 typedef enum {
@@ -893,6 +894,43 @@ int s2r_get_limiter_meters(const s2r_synth *s, float *min_gain, float *out_peak)
 int s2r_limiter_reference(const float *x, uint32_t frames, float ceiling, uint32_t lookahead, uint32_t hold, float *xh, float *gh,
                           float *y, float *gain);
 
+/* BUILD-DEFINED true-peak detector of the master limiter (DESIGN.md 4.30 gives the op sequence).  The limiter above bounds the samples
+ * it is given; with `detector` S2R_LIMITER_TRUE_PEAK it takes the magnitude of step 1 from the 4x interpolation of its input through
+ * the drive's prototype g = 4 h (s2r_drive_taps) — the interpolator and the operation sequence of the loudness meter's true peak —, so
+ * that what the meter reads and what the converter makes of the master stay near the ceiling.  S2R_LIMITER_SAMPLE_PEAK, the default
+ * and what s2r_set_master_limiter sets, is the rule above: the same kernel, bits and launches.  With C, L, H, W = L + 1, G = 2 L + H
+ * as above: STATE carried from call to call: xh, the last L + S2R_LIMITER_TP_HISTORY stereo frames of the limiter's input, oldest
+ * first, initially +0.0; gh, the last G values of g, oldest first, initially 1.0.  A call of N frames (x[n], g[n] for n < 0 from xh,
+ * gh):
+ *   1'. for channel c and phase p in 0 .. 3: u_{p,c}[n] = sum over j of g4[p + 4 j] * x_c[n - j], from +0.0 in ascending j, while
+ *       p + 4 j < S2R_DRIVE_TAPS (17 terms for phase 0, 16 for the others), g4 = 4 h;
+ *       d[n] = max(|x_L[n - 8]|, |x_R[n - 8]|, |u_{p,c}[n]| over all p and c)           (any order: a maximum has one value)
+ *       g[n] = d[n] > C ? C / d[n] : 1.0f
+ *   2. - 4. as above, over this g
+ *   5'. y_c[n] = min(max(x_c[n - L - 8] * s'[n], -C), C)
+ * binary32, every operation rounded on its own, no fma, denormals kept, the division correctly rounded.  The interpolator is centred
+ * S2R_LIMITER_TP_LATENCY = 8 frames back, so g[n - L] is centred on x[n - L - 8]: the master comes out L + 8 frames late — in every
+ * bit under an input whose d never exceeds C.  No output sample exceeds C in magnitude.  Every frame, xh and gh are independent of how
+ * a stream is cut into calls, calls shorter than 8 or 16 frames included.  THE TRUE PEAK OF THE OUTPUT IS NOT BOUNDED EXACTLY: the
+ * gain moves inside the interpolator's span, so the interpolation of the product is not the product of the interpolation.  What was
+ * measured (float64, tools/limiter_tp_truth.py, profiles/truth/limiter_tp_deviation.json): at most 1.0026 C by the project's meter on
+ * an fs/4 sine at 45 degrees, noise and a naive square at (48, 0) and (16, 8), where the sample-peak rule reads 1.24 to 1.43 C.  A
+ * lookahead of a few frames leaves more (1.0083 C at (5, 3)).  The interpolator's passband ends near 0.29 of the rate, as the
+ * meter's.  The stems are not delayed; meters, refusals and allocations as above.
+ *   s2r_set_master_limiter_ex: s2r_set_master_limiter with the detector.  S2R_ERR_PATCH_RANGE also for a detector above 1, checked
+ *   with the other ranges before the handle is looked at.  Another detector resets the state as another lookahead or hold does.
+ *   s2r_get_master_limiter_detector: the detector (0 with the limiter off); S2R_ERR_INVALID for a NULL pointer.
+ *   s2r_get_limiter_state / s2r_set_limiter_state: with the true-peak detector xh is 2 * (L + 16) floats; gh is G floats.
+ *   s2r_limiter_tp_reference: the rule on the host, as s2r_limiter_reference: xh [L + 16][2] and gh [G] updated in place. */
+#define S2R_LIMITER_SAMPLE_PEAK 0u
+#define S2R_LIMITER_TRUE_PEAK 1u
+#define S2R_LIMITER_TP_LATENCY 8u
+#define S2R_LIMITER_TP_HISTORY 16u
+int s2r_set_master_limiter_ex(s2r_synth *s, float ceiling, uint32_t lookahead, uint32_t hold, uint32_t detector);
+int s2r_get_master_limiter_detector(const s2r_synth *s, uint32_t *detector);
+int s2r_limiter_tp_reference(const float *x, uint32_t frames, float ceiling, uint32_t lookahead, uint32_t hold, float *xh, float *gh,
+                             float *y, float *gain);
+
 /* BUILD-DEFINED loudness and true-peak meters (the reference has none; DESIGN.md 4.26 gives the op sequence): ITU-R BS.1770 / EBU R128
  * momentary, short-term and gated integrated loudness of every bus and of the master, and the master's true peak, behind the master
  * limiter, in s2r_fill_master only, on the device the stems and the master are already on.  Off by default, and a handle on which the
@@ -1192,8 +1230,10 @@ int s2r_pcm_shaper(uint32_t kind, float *taps, uint32_t *n_taps);
  * The four chains and the final tree are part of the rule: they are four independent dependency chains for the kernel.  Every output
  * frame, the state and ph are independent of how a stream is cut into calls.  A call makes at most
  * S2R_RESAMPLER_MAX_OUT(frames, L, M) = ceil(frames * L / M) + 1 output frames.
- * A resampled signal can exceed the limiter's ceiling between the original samples: the limiter bounds the samples it is given, not
- * the band-limited curve through them.  The PCM stage behind clamps such a sample and counts it as a clip.
+ * A resampled signal can exceed the limiter's ceiling between the original samples: with the sample-peak detector the limiter bounds
+ * the samples it is given, not the band-limited curve through them, and the excess can be several dB; with the true-peak detector
+ * (s2r_set_master_limiter_ex) it bounds a 4x interpolation of them, and the excess is what that section records, under a percent
+ * at a lookahead of 16 frames or more.  The PCM stage behind clamps a sample past full scale and counts it as a clip.
  * WITH THE PCM STAGE ON TOO, its kernel runs on the resampler's output: all eight buses and the master, `count` frames a call, t
  * counting output frames; its integers, state, t and clips are exactly s2r_pcm_reference over s2r_resampler_reference's nine
  * programmes with n_buses = 8.  A call with count == 0 launches no PCM kernel: its state, t and held clips stay, and s2r_get_pcm

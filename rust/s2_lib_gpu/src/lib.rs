@@ -223,6 +223,8 @@ pub mod ffi {
         pub fn s2r_get_limiter_meters(s: *const S2rSynth, min_gain: *mut f32, out_peak: *mut f32) -> c_int;
         pub fn s2r_limiter_reference(x: *const f32, frames: u32, ceiling: f32, lookahead: u32, hold: u32, xh: *mut f32, gh: *mut f32,
                                      y: *mut f32, gain: *mut f32) -> c_int;
+        pub fn s2r_set_master_limiter_ex(s: *mut S2rSynth, ceiling: f32, lookahead: u32, hold: u32, detector: u32) -> c_int;
+        pub fn s2r_get_master_limiter_detector(s: *const S2rSynth, detector: *mut u32) -> c_int;
         pub fn s2r_set_master_loudness(s: *mut S2rSynth, coeffs: *const f32, hop: u32, max_hops: u32) -> c_int;
         pub fn s2r_clear_master_loudness(s: *mut S2rSynth) -> c_int;
         pub fn s2r_get_master_loudness(s: *const S2rSynth, coeffs: *mut f32, hop: *mut u32, max_hops: *mut u32, n_hops: *mut usize) -> c_int;
@@ -994,6 +996,19 @@ pub mod synth {
             self.check(unsafe { ffi::s2r_set_master_limiter(self.handle, ceiling, lookahead, hold) });
         }
 
+        /// ... with the true-peak detector (`s2r_set_master_limiter_ex`, detector 1): the gain follows the 4x-interpolated magnitude,
+        /// and the master is delayed by `lookahead + 8` frames.
+        pub fn set_master_limiter_true_peak(&mut self, ceiling: f32, lookahead: u32, hold: u32) {
+            self.check(unsafe { ffi::s2r_set_master_limiter_ex(self.handle, ceiling, lookahead, hold, 1) });
+        }
+
+        /// 0: the sample peak (and off); 1: the true peak.
+        pub fn get_master_limiter_detector(&self) -> u32 {
+            let mut d = 0u32;
+            self.check(unsafe { ffi::s2r_get_master_limiter_detector(self.handle, &mut d) });
+            d
+        }
+
         pub fn clear_master_limiter(&mut self) {
             self.check(unsafe { ffi::s2r_clear_master_limiter(self.handle) });
         }
@@ -1005,10 +1020,12 @@ pub mod synth {
             (c, l, h)
         }
 
-        /// (xh, gh): the limiter's carried input (`2 * lookahead` floats) and gains (`2 * lookahead + hold`), oldest first.
+        /// (xh, gh): the limiter's carried input (`2 * lookahead` floats, `2 * (lookahead + 16)` with the true-peak detector) and gains
+        /// (`2 * lookahead + hold`), oldest first.
         pub fn limiter_state(&mut self) -> (Vec<f32>, Vec<f32>) {
             let (_, l, h) = self.get_master_limiter();
-            let (mut xh, mut gh) = (vec![0.0f32; 2 * l as usize], vec![0.0f32; 2 * l as usize + h as usize]);
+            let more = if self.get_master_limiter_detector() == 1 { 16usize } else { 0usize };
+            let (mut xh, mut gh) = (vec![0.0f32; 2 * (l as usize + more)], vec![0.0f32; 2 * l as usize + h as usize]);
             self.check(unsafe { ffi::s2r_get_limiter_state(self.handle, xh.as_mut_ptr(), xh.len(), gh.as_mut_ptr(), gh.len()) });
             (xh, gh)
         }

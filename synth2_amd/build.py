@@ -31,7 +31,8 @@ SOURCES = ["s2r_render_onepole_square.hip", "s2r_render_onepole_saw.hip", "s2r_r
            "s2r_host_mix.cpp",  # (likewise, since the host file was split: host code only, no kernel)
            "s2r_host_post.cpp", # (likewise)
            "s2r_pcm.hip",       # (likewise, since the PCM stage came)
-           "s2r_resampler.hip"] # (last, likewise, since the sample-rate converter came)
+           "s2r_resampler.hip", # (likewise, since the sample-rate converter came)
+           "s2r_limiter_tp.hip"]    # (last, likewise, since the limiter's true-peak detector came)
 HEADERS = ["s2r_device.h", "s2r_math.h", "s2r_patch.h", "s2r_voices.h", "s2r_kern_common.h", "s2r_render_onepole.inc",
            "s2r_render_general.inc", "s2r_post.h", "s2r_post_route.h", "s2r_post_keep.h", "s2r_rules.h", "s2r_handle.h", "s2r_mixer.h",
            "s2r_mixer_keep.h"]
@@ -62,7 +63,7 @@ PER_FILE_FLAGS = {}
 for _f in ("s2r_render_general_square.hip", "s2r_render_general_saw.hip", "s2r_render_general_triangle.hip", "s2r_render_general_sine.hip",
            "s2r_render_general_bank.hip"):
     PER_FILE_FLAGS[_f] = ["-ftrivial-auto-var-init=zero"]
-# Fourteen translation units are compiled with the back end's resource-usage remarks, and _check_resources() fails the build when a
+# Fifteen translation units are compiled with the back end's resource-usage remarks, and _check_resources() fails the build when a
 # kernel named here went to scratch or spilled, or when fewer kernels report than the file instantiates.  Per source file: the
 # substrings that name its checked kernels; how many reports are expected — ("at least", n), ("exactly", n), or ("each", None):
 # one or more of every name — and why so many; the figures that must be "0"; and what the kernels keep where it belongs.  (The
@@ -104,6 +105,9 @@ RESOURCE_CHECKS = {
                        (_SCRATCH, _VSPILL, _SSPILL), "its stems and meter values must stay in registers"),
     "s2r_limiter.hip": (("s2r_limiter_kernel",), ("exactly", 1), "one kernel",
                         (_SCRATCH, _VSPILL, _SSPILL), "its windows live in LDS, the rest in registers"),
+    # a frame per lane: seventeen input frames and two sums per gain, the taps in SGPRs; the gain windows and the input window in LDS
+    "s2r_limiter_tp.hip": (("s2r_limiter_tp_kernel",), ("exactly", 1), "one kernel",
+                           (_SCRATCH, _VSPILL, _SSPILL), "its frames and sums must stay in registers, its windows in LDS"),
     # a channel per walker lane: ten coefficients, four filter values, the hop sum and sixteen samples read ahead; nine frames of a tile
     # per stager lane; seventeen master frames and two sums per true-peak lane, the taps in SGPRs
     "s2r_loudness.hip": (("s2r_loudness_kernel",), ("exactly", 1), "one kernel",
@@ -179,6 +183,12 @@ if _PCM_SERIAL:
 _RESAMPLER_SERIAL = os.environ.get("S2R_RESAMPLER_SERIAL") == "1"
 if _RESAMPLER_SERIAL:
     PER_FILE_FLAGS["s2r_resampler.hip"] = PER_FILE_FLAGS["s2r_resampler.hip"] + ["-DS2R_RESAMPLER_SERIAL"]
+# S2R_LIMITER_TP_NAIVE=1 likewise builds the true-peak limiter's obvious form (each thread sums its gains straight from global memory, no
+# input window in LDS; csrc/s2r_limiter_tp.hip, CHANGELOG) into libs2r_limitertpnaive.so, for tools/limiter_time.py --true-peak.  Never
+# the product build.
+_LIMITER_TP_NAIVE = os.environ.get("S2R_LIMITER_TP_NAIVE") == "1"
+if _LIMITER_TP_NAIVE:
+    PER_FILE_FLAGS["s2r_limiter_tp.hip"] = PER_FILE_FLAGS["s2r_limiter_tp.hip"] + ["-DS2R_LIMITER_TP_NAIVE"]
 # S2R_OPT=O3 in the environment builds the same sources at -O3 into libs2r_o3.so (tools and tests that compare the two
 # optimisation levels; the product is -O2).
 if os.environ.get("S2R_OPT") == "O3":
@@ -222,6 +232,9 @@ elif _PCM_SERIAL:
 elif _RESAMPLER_SERIAL:
     LIB = os.path.join(HERE, "libs2r_resamplerserial.so")
     OBJ_DIR_NAME = "_build_resamplerserial"
+elif _LIMITER_TP_NAIVE:
+    LIB = os.path.join(HERE, "libs2r_limitertpnaive.so")
+    OBJ_DIR_NAME = "_build_limitertpnaive"
 else:
     OBJ_DIR_NAME = "_build"
 

@@ -619,6 +619,14 @@ struct S2rLimiter {
 };
 hipError_t s2r_launch_limiter(const S2rLimiter &a, hipStream_t stream);
 
+// ... with the true-peak detector: a kernel and a block of its own, so that the sample-peak kernel and its arguments
+// stay what they were.  One launch, in the same place; `l.xh`, `l.xh_next` are [lookahead + S2R_LIMITER_TP_HISTORY][2] here.
+struct S2rLimiterTp {
+    S2rLimiter l;
+    float g[33];                  // taps 0 .. 32 of the interpolator g = 4 h, which is symmetric on bits (as S2rLoudness::g)
+};
+hipError_t s2r_launch_limiter_tp(const S2rLimiterTp &a, hipStream_t stream);
+
 // The loudness and true-peak meters of s2r_fill_master: one launch behind the limiter (or the master kernel), the last
 // of a master fill that finds the meter set.  It reads the stems from the master's device stage and the master from device memory —
 // whoever writes the master last writes it there in such a call, never into the pinned output —, copies the master to the pinned

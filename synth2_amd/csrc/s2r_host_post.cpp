@@ -515,24 +515,32 @@ int s2r_get_meters(const s2r_synth *s, uint32_t *n_buses, float *peak, float *en
 }
 
 // ---- the master limiter ----
-int s2r_set_master_limiter(s2r_synth *s, float ceiling, uint32_t lookahead, uint32_t hold) {
-    if (!limiter_in_range(ceiling, lookahead, hold))
-        return set_err(s, S2R_ERR_PATCH_RANGE, "master limiter: ceiling %g, lookahead %u, hold %u: the ceiling lies in [2^-%d, 2^%d], the lookahead in 1 .. %u, the hold in 0 .. %u",
-                       (double)ceiling, lookahead, hold, S2R_LIMITER_CEILING_LOG2, S2R_LIMITER_CEILING_LOG2, S2R_LIMITER_MAX_LOOKAHEAD, S2R_LIMITER_MAX_HOLD);
+int s2r_set_master_limiter_ex(s2r_synth *s, float ceiling, uint32_t lookahead, uint32_t hold, uint32_t detector) {
+    if (!limiter_in_range(ceiling, lookahead, hold) || detector > S2R_LIMITER_TRUE_PEAK)
+        return set_err(s, S2R_ERR_PATCH_RANGE, "master limiter: ceiling %g, lookahead %u, hold %u, detector %u: the ceiling lies in [2^-%d, 2^%d], the lookahead in 1 .. %u, the hold in 0 .. %u, the detector is 0 or 1",
+                       (double)ceiling, lookahead, hold, detector, S2R_LIMITER_CEILING_LOG2, S2R_LIMITER_CEILING_LOG2, S2R_LIMITER_MAX_LOOKAHEAD, S2R_LIMITER_MAX_HOLD);
     S2R_TRY(post_handle(s, "s2r_set_master_limiter", "the master limiter is"));
-    s->post.set_limiter(ceiling, lookahead, hold);
+    s->post.set_limiter(ceiling, lookahead, hold, detector);
     return S2R_OK;
 }
 
+int s2r_set_master_limiter(s2r_synth *s, float ceiling, uint32_t lookahead, uint32_t hold) { return s2r_set_master_limiter_ex(s, ceiling, lookahead, hold, S2R_LIMITER_SAMPLE_PEAK); }
+
 int s2r_clear_master_limiter(s2r_synth *s) {
     S2R_TRY(post_handle(s, "s2r_clear_master_limiter", "the master limiter is"));
-    s->post.set_limiter(0.0f, 0, 0);
+    s->post.set_limiter(0.0f, 0, 0, S2R_LIMITER_SAMPLE_PEAK);
     return S2R_OK;
 }
 
 int s2r_get_master_limiter(const s2r_synth *s, float *ceiling, uint32_t *lookahead, uint32_t *hold) {
     if (!s || !s->kids.empty() || s->parent) return S2R_ERR_INVALID;
     put(ceiling, s->post.limiter.ceiling); put(lookahead, s->post.limiter.lookahead); put(hold, s->post.limiter.hold);
+    return S2R_OK;
+}
+
+int s2r_get_master_limiter_detector(const s2r_synth *s, uint32_t *detector) {
+    if (!s || !s->kids.empty() || s->parent || !detector) return S2R_ERR_INVALID;
+    *detector = s->post.limiter.detector;
     return S2R_OK;
 }
 

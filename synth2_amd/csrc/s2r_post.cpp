@@ -9,7 +9,7 @@ namespace {
 
 // mapped host memory the host reads behind a synchronise: coherent and portable, as every pinned buffer of s2r_host.cpp
 constexpr unsigned kHostPolled = hipHostMallocMapped | hipHostMallocCoherent | hipHostMallocPortable;
-constexpr size_t kLimState = 2u * S2R_LIMITER_MAX_LOOKAHEAD + 2u * S2R_LIMITER_MAX_LOOKAHEAD + S2R_LIMITER_MAX_HOLD;     // the largest xh, then the largest gh
+constexpr size_t kLimState = 2u * (S2R_LIMITER_MAX_LOOKAHEAD + S2R_LIMITER_TP_HISTORY) + 2u * S2R_LIMITER_MAX_LOOKAHEAD + S2R_LIMITER_MAX_HOLD;     // the largest xh (the true-peak detector's), then the largest gh
 
 #define POST_HIP(call) do { const hipError_t e_ = (call); if (e_ != hipSuccess) return e_; } while (0)
 // a stage's launch between its timer's marks
@@ -192,7 +192,12 @@ hipError_t S2rPostChain::launch(const S2rPostCtx &c, const S2rPostCall &call) {
         S2rLimiter a{};
         a.x = r.limiter_in; a.out = r.limiter_out; a.xh = cur; a.gh = cur + lm.n_x(); a.xh_next = next; a.gh_next = next + lm.n_x();
         a.partials = lm.partials_dev; a.frames = call.frames; a.lookahead = lm.lookahead; a.hold = lm.hold; a.ceiling = lm.ceiling;
-        POST_TIMED(c, lm.timer, s2r_launch_limiter(a, c.stream));
+        if (lm.detector == S2R_LIMITER_TRUE_PEAK) {              // the same block, the interpolator's taps beside it, its own kernel
+            S2rLimiterTp t{};
+            t.l = a; std::memcpy(t.g, drive_taps().g, sizeof t.g);
+            POST_TIMED(c, lm.timer, s2r_launch_limiter_tp(t, c.stream));
+        } else
+            POST_TIMED(c, lm.timer, s2r_launch_limiter(a, c.stream));
     }
     if (loud_on(call)) {                                         // behind whoever wrote the master last: the next state goes into the other copy
         Loudness &ld = loud;
@@ -609,11 +614,11 @@ hipError_t S2rPostChain::history(const S2rPostCtx &c, int k, uint32_t bus, float
     return hipSuccess;
 }
 
-// another lookahead or hold (off is a lookahead of 0: it differs) resets the state — xh +0.0, gh 1.0 —, another ceiling keeps it
-void S2rPostChain::set_limiter(float ceiling, uint32_t lookahead, uint32_t hold) {
+// another lookahead, hold or detector (off is a lookahead of 0: it differs) resets the state — xh +0.0, gh 1.0 —, another ceiling keeps it
+void S2rPostChain::set_limiter(float ceiling, uint32_t lookahead, uint32_t hold, uint32_t detector) {
     Limiter &lm = limiter;
-    const bool reset = lm.lookahead != lookahead || lm.hold != hold;
-    lm.ceiling = ceiling; lm.lookahead = lookahead; lm.hold = hold;
+    const bool reset = lm.lookahead != lookahead || lm.hold != hold || lm.detector != detector;
+    lm.ceiling = ceiling; lm.lookahead = lookahead; lm.hold = hold; lm.detector = detector;
     if (!lookahead) lm.state.off();
     else if (reset) {
         std::vector<float> st(lm.n_x(), 0.0f);

@@ -150,15 +150,16 @@ struct S2rPostChain {
     struct Limiter {
         float ceiling = 0.0f;
         uint32_t lookahead = 0, hold = 0;        // lookahead 0: off
-        // xh [lookahead][2], then gh [2 * lookahead + hold], on the host and on the device alike: n_x() + n_g() floats, in copies
-        // sized for the largest lookahead and hold
+        uint32_t detector = 0;                   // S2R_LIMITER_SAMPLE_PEAK, or S2R_LIMITER_TRUE_PEAK: its own kernel, 16 frames more of xh
+        // xh [lookahead][2] ([lookahead + 16][2] with the true-peak detector), then gh [2 * lookahead + hold], on the host and on the
+        // device alike: n_x() + n_g() floats, in copies sized for the largest lookahead and hold
         S2rMirror state;
         float *in = nullptr;                     // [2 * max_frames] in device memory: where the master kernel writes when the limiter is on
         float *partials = nullptr, *partials_dev = nullptr;      // pinned and device-mapped: [ceil(max_frames / S2R_LIMITER_BLOCK)][2]
         bool metered = false;                    // a master fill has run the limiter: the meters below are its
         float min_gain = 1.0f, out_peak = 0.0f;
         S2rPostTimer timer;                         // around the limiter kernel of the last master fill: 0 when it ran none (tools/limiter_time.py)
-        size_t n_x() const { return 2u * (size_t)lookahead; }
+        size_t n_x() const { return 2u * ((size_t)lookahead + (detector == S2R_LIMITER_TRUE_PEAK ? S2R_LIMITER_TP_HISTORY : 0u)); }
         size_t n_g() const { return 2u * (size_t)lookahead + hold; }
     } limiter;
     // The loudness and true-peak meters (s2r_set_master_loudness).  Nothing is allocated before the first master fill
@@ -270,7 +271,7 @@ struct S2rPostChain {
     // the history of stage k's effect on a bus, out or in: `history` frames, oldest first, L then R
     hipError_t history(const S2rPostCtx &c, int k, uint32_t bus, float *get, const float *set);
     void snap_master() { for (uint32_t b = 0; b < S2R_MAX_BUSES; b++) master.ret_app[b] = master.ret[b]; master.fader_app = master.fader; }
-    void set_limiter(float ceiling, uint32_t lookahead, uint32_t hold);      // (0, 0, 0): off
+    void set_limiter(float ceiling, uint32_t lookahead, uint32_t hold, uint32_t detector);      // (0, 0, 0, 0): off
     void set_limiter_state(const float *xh, const float *gh);
     void set_loudness(const float *coeffs, uint32_t hop, uint32_t max_hops);  // coeffs null: off; else on, from the initial state
     void reset_loudness();                                          // state, rows and held true peak; the parameters stay

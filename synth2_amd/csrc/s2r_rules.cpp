@@ -484,6 +484,57 @@ int s2r_limiter_reference(const float *x, uint32_t frames, float ceiling, uint32
     return S2R_OK;
 }
 
+// ---- its true-peak detector: it shares the constants and drive_taps() with the kernel, nothing else ----
+int s2r_limiter_tp_reference(const float *x, uint32_t frames, float ceiling, uint32_t lookahead, uint32_t hold, float *xh, float *gh,
+                             float *y, float *gain) {
+    if (!limiter_in_range(ceiling, lookahead, hold)) return S2R_ERR_PATCH_RANGE;
+    if ((!x && frames) || !xh || !gh) return S2R_ERR_INVALID;
+    constexpr size_t D = S2R_LIMITER_TP_LATENCY, P = S2R_LIMITER_TP_HISTORY;
+    const size_t L = lookahead, H = hold, G = 2 * L + H, N = frames, X = L + P;
+    const float c = ceiling, w = (float)(lookahead + 1u);
+    const S2rDriveTaps &taps = drive_taps();
+    std::vector<float> ge(G + N), xe(2 * (X + N)), m(L + N);      // frame n of the call at xe[X + n]
+    std::memcpy(ge.data(), gh, G * sizeof(float));
+    std::memcpy(xe.data(), xh, 2 * X * sizeof(float));
+    if (N) std::memcpy(xe.data() + 2 * X, x, 2 * N * sizeof(float));
+    for (size_t n = 0; n < N; n++) {
+        const float al = std::fabs(xe[2 * (X + n - D)]), ar = std::fabs(xe[2 * (X + n - D) + 1]);
+        float d = al > ar ? al : ar;
+        for (uint32_t ch = 0; ch < 2u; ch++)
+            for (uint32_t p = 0; p < S2R_DRIVE_OVERSAMPLE; p++) {
+                float u = 0.0f;
+                for (uint32_t j = 0; p + 4u * j < S2R_DRIVE_TAPS; j++) {
+                    const float t = taps.g[p + 4u * j] * xe[2 * (X + n - j) + ch];
+                    u = u + t;
+                }
+                const float au = std::fabs(u);
+                d = au > d ? au : d;
+            }
+        ge[G + n] = d > c ? c / d : 1.0f;
+    }
+    for (size_t j = 0; j < L + N; j++) {
+        float v = ge[j];
+        for (size_t k = 1; k <= L + H; k++) v = ge[j + k] < v ? ge[j + k] : v;
+        m[j] = v;
+    }
+    for (size_t n = 0; n < N; n++) {
+        float acc = 0.0f;
+        for (size_t k = 0; k <= L; k++) acc = acc + m[n + L - k];
+        const float s = acc / w, gd = ge[G - L + n];
+        const float sp = s < gd ? s : gd;
+        if (gain) gain[n] = sp;
+        if (y)
+            for (size_t ch = 0; ch < 2; ch++) {                  // x[n - L - 8]
+                float v = xe[2 * (n + P - D) + ch] * sp;
+                v = v < -c ? -c : v;
+                y[2 * n + ch] = v > c ? c : v;
+            }
+    }
+    std::memcpy(gh, ge.data() + N, G * sizeof(float));
+    std::memcpy(xh, xe.data() + 2 * N, 2 * X * sizeof(float));
+    return S2R_OK;
+}
+
 }  // extern "C"
 
 // ---- per-bus flanger: one tap at a triangle-modulated fractional delay into the stage's own line signal, fed back ----

@@ -59,6 +59,10 @@ METER_BLOCK = 256                           # S2R_METER_BLOCK
 LIMITER_MAX_LOOKAHEAD = 1024                # S2R_LIMITER_MAX_LOOKAHEAD
 LIMITER_MAX_HOLD = 4096                     # S2R_LIMITER_MAX_HOLD
 LIMITER_CEILING_LOG2 = 20                   # S2R_LIMITER_CEILING_LOG2
+LIMITER_SAMPLE_PEAK = 0                     # S2R_LIMITER_SAMPLE_PEAK
+LIMITER_TRUE_PEAK = 1                       # S2R_LIMITER_TRUE_PEAK
+LIMITER_TP_LATENCY = 8                      # S2R_LIMITER_TP_LATENCY
+LIMITER_TP_HISTORY = 16                     # S2R_LIMITER_TP_HISTORY
 LOUDNESS_PROGRAMMES = 9                     # S2R_LOUDNESS_PROGRAMMES: the buses, then the master
 LOUDNESS_CHANNELS = 18                      # S2R_LOUDNESS_CHANNELS
 LOUDNESS_STATE = 122                        # S2R_LOUDNESS_STATE
@@ -314,6 +318,9 @@ def load_library():
         "s2r_set_limiter_state": (C.c_int, [H, _f32p, C.c_size_t, _f32p, C.c_size_t]),
         "s2r_get_limiter_meters": (C.c_int, [H, _f32p, _f32p]),
         "s2r_limiter_reference": (C.c_int, [_f32p, C.c_uint32, C.c_float, C.c_uint32, C.c_uint32, _f32p, _f32p, _f32p, _f32p]),
+        "s2r_set_master_limiter_ex": (C.c_int, [H, C.c_float, C.c_uint32, C.c_uint32, C.c_uint32]),
+        "s2r_get_master_limiter_detector": (C.c_int, [H, C.POINTER(C.c_uint32)]),
+        "s2r_limiter_tp_reference": (C.c_int, [_f32p, C.c_uint32, C.c_float, C.c_uint32, C.c_uint32, _f32p, _f32p, _f32p, _f32p]),
         "s2r_set_master_loudness": (C.c_int, [H, _f32p, C.c_uint32, C.c_uint32]),
         "s2r_clear_master_loudness": (C.c_int, [H]),
         "s2r_get_master_loudness": (C.c_int, [H, _f32p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_size_t)]),
@@ -776,6 +783,28 @@ def limiter_reference(x, ceiling, lookahead, hold, xh=None, gh=None):
     gain = np.empty(frames, dtype=np.float32)
     rc = load_library().s2r_limiter_reference(x.ctypes.data_as(_f32p), frames, float(ceiling), max(L, 0), max(Hd, 0), xh.ctypes.data_as(_f32p),
                                               gh.ctypes.data_as(_f32p), y.ctypes.data_as(_f32p), gain.ctypes.data_as(_f32p))
+    if rc != S2R_OK:
+        raise S2rError(rc, load_library().s2r_status_string(rc).decode())
+    return y, gain, xh, gh
+
+
+def limiter_tp_reference(x, ceiling, lookahead, hold, xh=None, gh=None):
+    """the master limiter's rule with the true-peak detector on the host (s2r_limiter_tp_reference): as limiter_reference, with xh
+    [lookahead + LIMITER_TP_HISTORY, 2].  Returns (y [frames, 2], gain [frames], xh, gh); y is x delayed by lookahead +
+    LIMITER_TP_LATENCY frames times the gain; the arguments are not modified."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    L, Hd = int(lookahead), int(hold)
+    if x.ndim != 2 or x.shape[1] != 2:
+        raise ValueError("limiter_tp_reference: x is [frames, 2]")
+    xh = np.zeros((max(L, 0) + LIMITER_TP_HISTORY, 2), dtype=np.float32) if xh is None else np.array(xh, dtype=np.float32, order="C")
+    gh = np.ones(max(2 * L + Hd, 0), dtype=np.float32) if gh is None else np.array(gh, dtype=np.float32, order="C")
+    if 0 < L <= LIMITER_MAX_LOOKAHEAD and 0 <= Hd <= LIMITER_MAX_HOLD and (xh.shape != (L + LIMITER_TP_HISTORY, 2) or gh.shape != (2 * L + Hd,)):
+        raise ValueError("limiter_tp_reference: xh is [lookahead + 16, 2], gh is [2 * lookahead + hold]")
+    frames = x.shape[0]
+    y = np.empty((frames, 2), dtype=np.float32)
+    gain = np.empty(frames, dtype=np.float32)
+    rc = load_library().s2r_limiter_tp_reference(x.ctypes.data_as(_f32p), frames, float(ceiling), max(L, 0), max(Hd, 0), xh.ctypes.data_as(_f32p),
+                                                 gh.ctypes.data_as(_f32p), y.ctypes.data_as(_f32p), gain.ctypes.data_as(_f32p))
     if rc != S2R_OK:
         raise S2rError(rc, load_library().s2r_status_string(rc).decode())
     return y, gain, xh, gh
@@ -1762,11 +1791,15 @@ class Synth:
         return master_reference(stems, r0, r1, m0, m1)
 
     # --- the master limiter (build-defined; s2r.h: s2r_set_master_limiter) ---
-    def set_master_limiter(self, ceiling, lookahead, hold=0):
+    def set_master_limiter(self, ceiling, lookahead, hold=0, true_peak=False):
         """a look-ahead limiter behind the master fader, in sample_master only: no sample of the master exceeds `ceiling`, and the
-        master is delayed by `lookahead` frames (the stems are not).  A new lookahead or hold resets the state; a new ceiling alone
-        keeps it."""
-        self._check(self.L.s2r_set_master_limiter(self.h, float(ceiling), int(lookahead), int(hold)))
+        master is delayed by `lookahead` frames (the stems are not).  true_peak: the gain follows the 4x-interpolated magnitude of the
+        master, not its samples' (s2r.h: s2r_set_master_limiter_ex), and the delay is LIMITER_TP_LATENCY frames longer.  A new
+        lookahead, hold or detector resets the state; a new ceiling alone keeps it."""
+        if true_peak:
+            self._check(self.L.s2r_set_master_limiter_ex(self.h, float(ceiling), int(lookahead), int(hold), LIMITER_TRUE_PEAK))
+        else:
+            self._check(self.L.s2r_set_master_limiter(self.h, float(ceiling), int(lookahead), int(hold)))
 
     def clear_master_limiter(self):
         self._check(self.L.s2r_clear_master_limiter(self.h))
@@ -1777,10 +1810,18 @@ class Synth:
         self._check(self.L.s2r_get_master_limiter(self.h, C.byref(c), C.byref(l), C.byref(h)))
         return c.value, l.value, h.value
 
+    def get_master_limiter_detector(self):
+        """LIMITER_SAMPLE_PEAK or LIMITER_TRUE_PEAK; 0 with the limiter off"""
+        d = C.c_uint32()
+        self._check(self.L.s2r_get_master_limiter_detector(self.h, C.byref(d)))
+        return d.value
+
     def limiter_state(self):
-        """(xh [lookahead, 2], gh [2 * lookahead + hold]): the limiter's carried input frames and gains, oldest first (checkpoints)"""
+        """(xh [lookahead, 2], gh [2 * lookahead + hold]): the limiter's carried input frames and gains, oldest first (checkpoints);
+        xh is [lookahead + LIMITER_TP_HISTORY, 2] with the true-peak detector"""
         _, l, h = self.get_master_limiter()
-        xh, gh = np.empty((l, 2), dtype=np.float32), np.empty(2 * l + h, dtype=np.float32)
+        more = LIMITER_TP_HISTORY if self.get_master_limiter_detector() == LIMITER_TRUE_PEAK else 0
+        xh, gh = np.empty((l + more, 2), dtype=np.float32), np.empty(2 * l + h, dtype=np.float32)
         self._check(self.L.s2r_get_limiter_state(self.h, xh.ctypes.data_as(_f32p), xh.size, gh.ctypes.data_as(_f32p), gh.size))
         return xh, gh
 
@@ -1798,6 +1839,10 @@ class Synth:
     @staticmethod
     def limiter_reference(x, ceiling, lookahead, hold, xh=None, gh=None):
         return limiter_reference(x, ceiling, lookahead, hold, xh, gh)
+
+    @staticmethod
+    def limiter_tp_reference(x, ceiling, lookahead, hold, xh=None, gh=None):
+        return limiter_tp_reference(x, ceiling, lookahead, hold, xh, gh)
 
     # --- the loudness and true-peak meters (build-defined; s2r.h: s2r_set_master_loudness) ---
     def set_master_loudness(self, sample_rate=48000, hop=None, max_hops=None, coeffs=None):

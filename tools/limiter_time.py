@@ -16,6 +16,10 @@ loaded library has — a library without s2r_set_master_limiter is timed on the 
 it; run the two libraries in turn, one process each, three rounds, and compare this build's no-limiter median with the other
 library's min .. max.
 
+--true-peak times the true-peak detector beside the sample-peak rule: the three pairs with each detector, on the same
+handle, into profiles/r26/limiter_true_peak.txt.  The comparison form of its kernel (S2R_LIMITER_TP_NAIVE=1 python -m synth2_amd.build,
+then S2R_AB_LIB=synth2_amd/libs2r_limitertpnaive.so) goes beside it with --true-peak --ab naive.
+
 No pass threshold."""
 import argparse
 import ctypes as C
@@ -40,9 +44,12 @@ PAIRS = [(48, 0), (240, 480), (1024, 4096)]
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "r11", "limiter.txt"))
+    ap.add_argument("--out", default=None)
     ap.add_argument("--ab", default=None, help="a label for this library: append one line per kind to --out")
+    ap.add_argument("--true-peak", action="store_true", help="the three pairs with the true-peak detector too (default --out: profiles/r26/limiter_true_peak.txt)")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", *(("r26", "limiter_true_peak.txt") if a.true_peak else ("r11", "limiter.txt")))
     L = s2.load_library()
     has_limiter = hasattr(L, "s2r_debug_limiter_ms")
     for name in ("s2r_debug_master_ms",) + (("s2r_debug_limiter_ms",) if has_limiter else ()):
@@ -76,12 +83,14 @@ def main():
     kinds = [(None, "s2r_fill_master, no limiter         ")]
     if has_limiter:
         kinds += [(p, "s2r_fill_master, limiter (%4d, %4d)" % p) for p in PAIRS]
+    if a.true_peak:                                       # a kind of three: the true-peak detector
+        kinds += [(p + (True,), "s2r_fill_master, true-peak (%4d, %4d)" % p) for p in PAIRS]
     wall, mst, lim, gain = ({kd[0]: [] for kd in kinds} for _ in range(4))
     k = period + 2
     peak = 0.0
     for kind, _ in kinds:
         if kind is not None:
-            s.set_master_limiter(peak / 2.0, *kind)
+            s.set_master_limiter(peak / 2.0, *kind[:2], **({"true_peak": True} if len(kind) == 3 else {}))
         for i in range(N + 2):
             s.note_events(events(k))
             k += 1
@@ -118,11 +127,16 @@ def main():
         w = {kind: np.median(wall[kind][2:]) for kind, _ in kinds}
         lines.append("  host wall per call against the fill without a limiter: " + ", ".join("(%d, %d) %+.3f ms" % (p + (w[p] - w[None],)) for p in PAIRS)
                      + "; smallest min_gain seen: " + ", ".join("%.4f" % min(gain[p]) for p in PAIRS))
-        res = os.path.join(s2build.OBJ_DIR, "s2r_limiter.resources.txt")
-        if os.path.exists(res):
-            lines.append("compiler resource usage (s2r_limiter.hip, -Rpass-analysis=kernel-resource-usage; plus 2 * (256 + 2 L + H) floats of dynamic LDS):")
-            for l in open(res):
-                lines.append("  " + l.strip())
+        if a.true_peak:
+            lines.append("  the true-peak detector against the sample-peak rule, limiter kernel: " + ", ".join(
+                "(%d, %d) %+.4f ms" % (p + (np.median(lim[p + (True,)][2:]) - np.median(lim[p][2:]),)) for p in PAIRS)
+                + "; smallest min_gain seen: " + ", ".join("%.4f" % min(gain[p + (True,)]) for p in PAIRS))
+        for src, more in (("s2r_limiter", "2 * (256 + 2 L + H) floats"),) + ((("s2r_limiter_tp", "2 * (256 + 2 L + H) floats and 256 + 2 L + H + 16 frames"),) if a.true_peak else ()):
+            res = os.path.join(s2build.OBJ_DIR, src + ".resources.txt")
+            if os.path.exists(res):
+                lines.append("compiler resource usage (%s.hip, -Rpass-analysis=kernel-resource-usage; plus %s of dynamic LDS):" % (src, more))
+                for l in open(res):
+                    lines.append("  " + l.strip())
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "a" if a.ab is not None else "w") as out:
         for l in lines:
