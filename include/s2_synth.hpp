@@ -322,6 +322,35 @@ class Synth {
         return s2r_limiter_reference(x, frames, ceiling, lookahead, hold, xh, gh, y, gain);
     }
 
+    // the master multiband compressor (build-defined; s2r.h: s2r_set_master_multiband): the master split into n_bands (1 .. 4) bands between
+    // the master fader and the limiter, each compressed by its own curve, and added back, in sample_master only.  lp, hp: [n_bands - 1][5];
+    // ap: [n_bands - 2][5]; curves: [n_bands][S2R_DYN_CURVE_POINTS]; a_att, a_rel: [n_bands]; an array of no rows may be null
+    void set_master_multiband(uint32_t n_bands, const float *lp, const float *hp, const float *ap, const float *curves, const float *a_att, const float *a_rel) {
+        check(s2r_set_master_multiband(h_, n_bands, lp, hp, ap, curves, a_att, a_rel));
+    }
+    // ... the parameters alone, with the band count that is set: the state stays
+    void set_master_multiband_params(uint32_t n_bands, const float *lp, const float *hp, const float *ap, const float *curves, const float *a_att,
+                                     const float *a_rel) {
+        check(s2r_set_master_multiband_params(h_, n_bands, lp, hp, ap, curves, a_att, a_rel));
+    }
+    void clear_master_multiband() { check(s2r_clear_master_multiband(h_)); }
+    // *n_bands is 0 when off; every array may be null
+    void get_master_multiband(uint32_t *n_bands, float *lp, float *hp, float *ap, float *curves, float *a_att, float *a_rel) const {
+        check(s2r_get_master_multiband(h_, n_bands, lp, hp, ap, curves, a_att, a_rel));
+    }
+    void reset_master_multiband() { check(s2r_reset_master_multiband(h_)); }
+    // state: S2R_MULTIBAND_STATE(n_bands) floats (checkpoints); min_gain: n_bands floats
+    void multiband_state(float *state, size_t capacity) { check(s2r_get_multiband_state(h_, state, capacity)); }
+    void set_multiband_state(const float *state, size_t count) { check(s2r_set_multiband_state(h_, state, count)); }
+    void multiband_meters(float *min_gain, size_t capacity) const { check(s2r_get_multiband_meters(h_, min_gain, capacity)); }
+    static int multiband_reference(uint32_t n_bands, const float *lp, const float *hp, const float *ap, const float *curves, const float *a_att,
+                                   const float *a_rel, const float *x_lr, uint32_t frames, float *state, float *out_lr, float *bands, float *min_gain) {
+        return s2r_multiband_reference(n_bands, lp, hp, ap, curves, a_att, a_rel, x_lr, frames, state, out_lr, bands, min_gain);
+    }
+    static int multiband_design(double sample_rate, const double *freqs_hz, uint32_t n_splits, float *lp, float *hp, float *ap) {
+        return s2r_multiband_design(sample_rate, freqs_hz, n_splits, lp, hp, ap);
+    }
+
     // the loudness and true-peak meters (build-defined; s2r.h: s2r_set_master_loudness): BS.1770 loudness of every bus and the master and
     // the master's true peak, behind the limiter, in sample_master only; master_lr and the stems are the same bits with the meter on or off
     void set_master_loudness(const float coeffs[10], uint32_t hop, uint32_t max_hops) { check(s2r_set_master_loudness(h_, coeffs, hop, max_hops)); }

@@ -60,7 +60,9 @@ extern "C" {
  * s2r_pcm_reference, s2r_pcm_dither, s2r_pcm_pack, s2r_pcm_shaper, s2r_set_master_resampler, s2r_clear_master_resampler,
  * s2r_get_master_resampler, s2r_reset_master_resampler, s2r_get_resampled, s2r_get_resampler_state, s2r_set_resampler_state,
  * s2r_resampler_reference, s2r_resampler_count, s2r_resampler_design, s2r_set_master_limiter_ex, s2r_get_master_limiter_detector,
- * s2r_limiter_tp_reference. */
+ * s2r_limiter_tp_reference, s2r_set_master_multiband, s2r_set_master_multiband_params, s2r_clear_master_multiband,
+ * s2r_get_master_multiband, s2r_reset_master_multiband, s2r_get_multiband_state, s2r_set_multiband_state, s2r_get_multiband_meters,
+ * s2r_multiband_reference, s2r_multiband_design. */
 #define S2R_ABI_VERSION 4
 
 typedef enum {
@@ -930,6 +932,60 @@ int s2r_set_master_limiter_ex(s2r_synth *s, float ceiling, uint32_t lookahead, u
 int s2r_get_master_limiter_detector(const s2r_synth *s, uint32_t *detector);
 int s2r_limiter_tp_reference(const float *x, uint32_t frames, float ceiling, uint32_t lookahead, uint32_t hold, float *xh, float *gh,
                              float *y, float *gain);
+
+/* BUILD-DEFINED master multiband compressor (the reference has none; DESIGN.md 4.31 gives the op sequence): the master insert, behind
+ * the master kernel (returns, bus-order sum, master fader) and in front of the limiter, in s2r_fill_master only.  It splits the master
+ * into B = n_bands (1 .. S2R_MULTIBAND_MAX_BANDS) frequency bands, gives each band a gain of its own by the rule of the bus dynamics,
+ * and adds the bands in band order.  Off by default, no latency, the stems untouched; the limiter, both meters, the converter and the
+ * PCM stage see the processed master; a handle on which it was never set launches what it launched before and allocates nothing.
+ * A SECTION is one band of s2r_eq_reference with its own (s1, s2) per channel: transposed direct form II, the nine rounded operations
+ * of the bus EQ, no fma, denormals kept, nothing skipped for a zero, both channels the same five coefficients (b0, b1, b2, a1, a2).
+ * Split k (0 .. B - 2) owns four sections: LPa_k and LPb_k with the coefficients lp[k], HPa_k and HPb_k with hp[k]; for k >= 1 there
+ * is also an allpass row ap[k - 1].  Per channel:
+ *   1. r_0 = x;  for k = 0 .. B - 2: band_k = LPb_k(LPa_k(r_k)), r_{k+1} = HPb_k(HPa_k(r_k));  band_{B-1} = r_{B-1}
+ *   2. band j <= B - 3 then passes, in ascending k, through an allpass section AP_{j,k} for k = j + 1 .. B - 2, each with a state of
+ *      its own and the coefficients ap[k - 1]                                  (S(B) = 4 (B-1) + (B-1)(B-2)/2 sections: 0, 4, 9, 15)
+ *   3. band j has a curve of S2R_DYN_CURVE_POINTS gains, a_att[j], a_rel[j] and a gain y_j shared by both channels; per frame
+ *      p = max(|band_jL|, |band_jR|), then steps 2 and 3 of the bus dynamics verbatim (the table lookup, t < y ? a_att : a_rel,
+ *      y = t + (a * (y - t))), then o_jc = band_jc * y_j
+ *   4. out_c = o_0c, then out_c = out_c + o_jc for j = 1 .. B - 1 in band order (no zero in front: B = 1 is the bus dynamics keyed by
+ *      itself, in every bit)
+ * binary32, every operation rounded on its own.  STATE, S2R_MULTIBAND_STATE(B) = 4 S(B) + B floats: [section][s1_L, s1_R, s2_L, s2_R]
+ * in the order LPa_0, LPb_0, HPa_0, HPb_0, LPa_1, ..., then AP_{0,1}, AP_{0,2}, AP_{1,2}, then the B gains.  Right after a set the
+ * filters hold +0.0 and y_j = curves[j][0].  Calls of any lengths concatenate; a refused or failed call leaves the state untouched.
+ * The meter of a call is min over n of y_j[n] per band; s2r_get_meters stays what the master kernel measured, in front of the stage.
+ *   s2r_set_master_multiband: lp and hp are [B - 1][5], ap [B - 2][5] (NULL is accepted for an array of no rows), curves
+ *   [B][S2R_DYN_CURVE_POINTS], a_att and a_rel [B].  S2R_ERR_PATCH_RANGE for n_bands outside 1 .. 4, coefficients as s2r_set_bus_eq
+ *   refuses them, curves and retention coefficients as s2r_set_bus_dynamics does — all before the handle is looked at;
+ *   S2R_ERR_INVALID for a NULL or device-list handle or a NULL array that has rows.  A refusal changes nothing.
+ *   s2r_set_master_multiband_params: the same arguments with the n_bands that is set (another: S2R_ERR_INVALID); the state stays.
+ *   s2r_clear_master_multiband: off.  s2r_get_master_multiband: *n_bands is 0 when off; every array may be NULL.
+ *   s2r_reset_master_multiband: the state right after a set; the parameters stay.
+ *   s2r_get_multiband_state / s2r_set_multiband_state: S2R_MULTIBAND_STATE(B) floats (a capacity of at least that; a count of exactly
+ *   that, every float finite, the gains >= 0: else S2R_ERR_PATCH_RANGE).
+ *   s2r_get_multiband_meters: min_gain [B] of the last successful master fill that ran the stage; S2R_ERR_INVALID before one.
+ *   s2r_multiband_reference: the rule on the host: state [S2R_MULTIBAND_STATE(B)] in place; out_lr [frames][2], bands
+ *   [B][frames][2] (the band signals in front of the gains) and min_gain [B] (written when frames > 0) may each be NULL.
+ *   s2r_multiband_design: n_splits (0 .. 3) second-order Butterworth (Q = 1/sqrt 2) cookbook low-pass, high-pass and allpass rows at
+ *   freqs_hz, binary64, rounded once: lp, hp [n_splits][5], ap [n_splits - 1][5] for splits 1 ..; two low-passes and two high-passes
+ *   in series are a fourth-order Linkwitz-Riley split, whose two bands add to that allpass.  S2R_ERR_PATCH_RANGE unless the
+ *   frequencies ascend strictly inside (0, sample_rate / 2). */
+#define S2R_MULTIBAND_MAX_BANDS 4u
+#define S2R_MULTIBAND_SECTIONS(B) (4u * ((B) - 1u) + ((B) - 1u) * ((B) - 2u) / 2u)
+#define S2R_MULTIBAND_STATE(B) (4u * S2R_MULTIBAND_SECTIONS(B) + (B))
+int s2r_set_master_multiband(s2r_synth *s, uint32_t n_bands, const float *lp, const float *hp, const float *ap, const float *curves,
+                             const float *a_att, const float *a_rel);
+int s2r_set_master_multiband_params(s2r_synth *s, uint32_t n_bands, const float *lp, const float *hp, const float *ap, const float *curves,
+                                    const float *a_att, const float *a_rel);
+int s2r_clear_master_multiband(s2r_synth *s);
+int s2r_get_master_multiband(const s2r_synth *s, uint32_t *n_bands, float *lp, float *hp, float *ap, float *curves, float *a_att, float *a_rel);
+int s2r_reset_master_multiband(s2r_synth *s);
+int s2r_get_multiband_state(s2r_synth *s, float *state, size_t capacity);
+int s2r_set_multiband_state(s2r_synth *s, const float *state, size_t count);
+int s2r_get_multiband_meters(const s2r_synth *s, float *min_gain, size_t capacity);
+int s2r_multiband_reference(uint32_t n_bands, const float *lp, const float *hp, const float *ap, const float *curves, const float *a_att,
+                            const float *a_rel, const float *x_lr, uint32_t frames, float *state, float *out_lr, float *bands, float *min_gain);
+int s2r_multiband_design(double sample_rate, const double *freqs_hz, uint32_t n_splits, float *lp, float *hp, float *ap);
 
 /* BUILD-DEFINED loudness and true-peak meters (the reference has none; DESIGN.md 4.26 gives the op sequence): ITU-R BS.1770 / EBU R128
  * momentary, short-term and gated integrated loudness of every bus and of the master, and the master's true peak, behind the master

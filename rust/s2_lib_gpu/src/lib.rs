@@ -225,6 +225,21 @@ pub mod ffi {
                                      y: *mut f32, gain: *mut f32) -> c_int;
         pub fn s2r_set_master_limiter_ex(s: *mut S2rSynth, ceiling: f32, lookahead: u32, hold: u32, detector: u32) -> c_int;
         pub fn s2r_get_master_limiter_detector(s: *const S2rSynth, detector: *mut u32) -> c_int;
+        pub fn s2r_set_master_multiband(s: *mut S2rSynth, n_bands: u32, lp: *const f32, hp: *const f32, ap: *const f32, curves: *const f32,
+                                        a_att: *const f32, a_rel: *const f32) -> c_int;
+        pub fn s2r_set_master_multiband_params(s: *mut S2rSynth, n_bands: u32, lp: *const f32, hp: *const f32, ap: *const f32, curves: *const f32,
+                                               a_att: *const f32, a_rel: *const f32) -> c_int;
+        pub fn s2r_clear_master_multiband(s: *mut S2rSynth) -> c_int;
+        pub fn s2r_reset_master_multiband(s: *mut S2rSynth) -> c_int;
+        pub fn s2r_get_multiband_state(s: *mut S2rSynth, state: *mut f32, capacity: usize) -> c_int;
+        pub fn s2r_set_multiband_state(s: *mut S2rSynth, state: *const f32, count: usize) -> c_int;
+        pub fn s2r_get_multiband_meters(s: *const S2rSynth, min_gain: *mut f32, capacity: usize) -> c_int;
+        pub fn s2r_get_master_multiband(s: *const S2rSynth, n_bands: *mut u32, lp: *mut f32, hp: *mut f32, ap: *mut f32, curves: *mut f32,
+                                        a_att: *mut f32, a_rel: *mut f32) -> c_int;
+        pub fn s2r_multiband_reference(n_bands: u32, lp: *const f32, hp: *const f32, ap: *const f32, curves: *const f32, a_att: *const f32,
+                                       a_rel: *const f32, x_lr: *const f32, frames: u32, state: *mut f32, out_lr: *mut f32, bands: *mut f32,
+                                       min_gain: *mut f32) -> c_int;
+        pub fn s2r_multiband_design(sample_rate: f64, freqs_hz: *const f64, n_splits: u32, lp: *mut f32, hp: *mut f32, ap: *mut f32) -> c_int;
         pub fn s2r_set_master_loudness(s: *mut S2rSynth, coeffs: *const f32, hop: u32, max_hops: u32) -> c_int;
         pub fn s2r_clear_master_loudness(s: *mut S2rSynth) -> c_int;
         pub fn s2r_get_master_loudness(s: *const S2rSynth, coeffs: *mut f32, hop: *mut u32, max_hops: *mut u32, n_hops: *mut usize) -> c_int;
@@ -462,6 +477,51 @@ pub fn master_reference(stems: &[f32], r0: &[f32], r1: &[f32], m0: f32, m1: f32)
                                   peak.as_mut_ptr(), energy.as_mut_ptr())
     };
     if rc == 0 { Ok((out, peak, energy)) } else { Err(rc) }
+}
+
+/// `S2R_MULTIBAND_STATE(n_bands)`: 4 floats per crossover section, then the bands' gains; 0 for no band.
+pub fn multiband_state_floats(n_bands: usize) -> usize {
+    if n_bands == 0 {
+        return 0;
+    }
+    4 * (4 * (n_bands - 1) + (n_bands - 1) * n_bands.saturating_sub(2) / 2) + n_bands
+}
+
+/// Host-only: the master multiband compressor's crossover rows (`s2r_multiband_design`) for split frequencies strictly
+/// ascending inside (0, sample_rate / 2): (lp, hp, ap), 5 floats per split, ap for the splits behind the first.
+pub fn multiband_design(sample_rate: f64, splits_hz: &[f64]) -> Result<(Vec<f32>, Vec<f32>, Vec<f32>), i32> {
+    let n = splits_hz.len();
+    let (mut lp, mut hp, mut ap) = (vec![0.0f32; 5 * n], vec![0.0f32; 5 * n], vec![0.0f32; 5 * n.saturating_sub(1)]);
+    let p = |v: &mut Vec<f32>| if v.is_empty() { std::ptr::null_mut() } else { v.as_mut_ptr() };
+    let f = if n == 0 { std::ptr::null() } else { splits_hz.as_ptr() };
+    let rc = unsafe { ffi::s2r_multiband_design(sample_rate, f, n as u32, p(&mut lp), p(&mut hp), p(&mut ap)) };
+    if rc != 0 {
+        return Err(rc);
+    }
+    Ok((lp, hp, ap))
+}
+
+/// Host-only: the master multiband compressor's rule (`s2r_multiband_reference`).  `a_att.len()` bands; `x`: L, R pairs;
+/// `state` (`multiband_state_floats` floats) is updated in place.  Returns (out, the bands' minimum gains — infinity for no frames).
+#[allow(clippy::too_many_arguments)]
+pub fn multiband_reference(lp: &[f32], hp: &[f32], ap: &[f32], curves: &[f32], a_att: &[f32], a_rel: &[f32], x: &[f32], state: &mut [f32]) -> Result<(Vec<f32>, Vec<f32>), i32> {
+    let b = a_att.len();
+    let frames = x.len() / 2;
+    if b == 0 || b > 4 || a_rel.len() != b || curves.len() != 513 * b || lp.len() != 5 * (b - 1) || hp.len() != lp.len() || ap.len() != 5 * b.saturating_sub(2)
+        || state.len() != multiband_state_floats(b)
+    {
+        return Err(-1);
+    }
+    let p = |v: &[f32]| if v.is_empty() { std::ptr::null() } else { v.as_ptr() };
+    let (mut out, mut mn) = (vec![0.0f32; 2 * frames], vec![f32::INFINITY; b]);
+    let rc = unsafe {
+        ffi::s2r_multiband_reference(b as u32, p(lp), p(hp), p(ap), curves.as_ptr(), a_att.as_ptr(), a_rel.as_ptr(), p(x), frames as u32, state.as_mut_ptr(),
+                                     if frames == 0 { std::ptr::null_mut() } else { out.as_mut_ptr() }, std::ptr::null_mut(), mn.as_mut_ptr())
+    };
+    if rc != 0 {
+        return Err(rc);
+    }
+    Ok((out, mn))
 }
 
 /// Host-only: the master limiter's rule (`s2r_limiter_reference`).  `x`: L, R pairs; `xh` (`2 * lookahead`
@@ -1039,6 +1099,80 @@ pub mod synth {
             let (mut g, mut p) = (0.0f32, 0.0f32);
             self.check(unsafe { ffi::s2r_get_limiter_meters(self.handle, &mut g, &mut p) });
             (g, p)
+        }
+
+        /// Build-defined master multiband compressor (`s2r_set_master_multiband`, include/s2r.h): the master split into `a_att.len()`
+        /// bands (1 .. 4) between the master fader and the limiter, each compressed by its own curve of 513 gains, and added back.
+        /// `lp`, `hp`: 5 floats per split; `ap`: 5 floats per split behind the first; empty slices for arrays of no rows.
+        pub fn set_master_multiband(&mut self, lp: &[f32], hp: &[f32], ap: &[f32], curves: &[f32], a_att: &[f32], a_rel: &[f32]) {
+            let b = a_att.len();
+            assert!(a_rel.len() == b && curves.len() == b * 513 && lp.len() + 5 == b * 5 && hp.len() == lp.len() && ap.len() + 10 == (b.max(2)) * 5);
+            let p = |v: &[f32]| if v.is_empty() { std::ptr::null() } else { v.as_ptr() };
+            self.check(unsafe { ffi::s2r_set_master_multiband(self.handle, b as u32, p(lp), p(hp), p(ap), curves.as_ptr(), a_att.as_ptr(), a_rel.as_ptr()) });
+        }
+
+        /// ... the parameters alone, with the band count that is set: the state stays.
+        pub fn set_master_multiband_params(&mut self, lp: &[f32], hp: &[f32], ap: &[f32], curves: &[f32], a_att: &[f32], a_rel: &[f32]) {
+            let b = a_att.len();
+            assert!(a_rel.len() == b && curves.len() == b * 513 && lp.len() + 5 == b * 5 && hp.len() == lp.len() && ap.len() + 10 == (b.max(2)) * 5);
+            let p = |v: &[f32]| if v.is_empty() { std::ptr::null() } else { v.as_ptr() };
+            self.check(unsafe { ffi::s2r_set_master_multiband_params(self.handle, b as u32, p(lp), p(hp), p(ap), curves.as_ptr(), a_att.as_ptr(), a_rel.as_ptr()) });
+        }
+
+        pub fn clear_master_multiband(&mut self) {
+            self.check(unsafe { ffi::s2r_clear_master_multiband(self.handle) });
+        }
+
+        /// Filters and gains as right after a set; the parameters stay.
+        pub fn reset_master_multiband(&mut self) {
+            self.check(unsafe { ffi::s2r_reset_master_multiband(self.handle) });
+        }
+
+        /// The band count that is set; 0 when the stage is off.
+        pub fn master_multiband_bands(&self) -> usize {
+            let mut b = 0u32;
+            let null = std::ptr::null_mut();
+            self.check(unsafe { ffi::s2r_get_master_multiband(self.handle, &mut b, null, null, null, null, null, null) });
+            b as usize
+        }
+
+        /// (lp, hp, ap, curves, a_att, a_rel) as they are set; `None` when the stage is off.
+        #[allow(clippy::type_complexity)]
+        pub fn get_master_multiband(&self) -> Option<(Vec<f32>, Vec<f32>, Vec<f32>, Vec<f32>, Vec<f32>, Vec<f32>)> {
+            let b = self.master_multiband_bands();
+            if b == 0 {
+                return None;
+            }
+            let (mut lp, mut hp, mut ap) = (vec![0.0f32; 5 * (b - 1)], vec![0.0f32; 5 * (b - 1)], vec![0.0f32; 5 * b.saturating_sub(2)]);
+            let (mut curves, mut att, mut rel) = (vec![0.0f32; 513 * b], vec![0.0f32; b], vec![0.0f32; b]);
+            let p = |v: &mut Vec<f32>| if v.is_empty() { std::ptr::null_mut() } else { v.as_mut_ptr() };
+            self.check(unsafe {
+                ffi::s2r_get_master_multiband(self.handle, std::ptr::null_mut(), p(&mut lp), p(&mut hp), p(&mut ap), curves.as_mut_ptr(), att.as_mut_ptr(), rel.as_mut_ptr())
+            });
+            Some((lp, hp, ap, curves, att, rel))
+        }
+
+        /// The stage's state (checkpoints): 4 floats per section — 0, 4, 9, 15 sections for 1 .. 4 bands —, then the bands' gains.  The
+        /// band count is the handle's; with the stage off the library refuses the call.
+        pub fn multiband_state(&mut self) -> Vec<f32> {
+            let b = self.master_multiband_bands();
+            let mut st = vec![0.0f32; multiband_state_floats(b).max(1)];
+            self.check(unsafe { ffi::s2r_get_multiband_state(self.handle, st.as_mut_ptr(), st.len()) });
+            st.truncate(multiband_state_floats(b));
+            st
+        }
+
+        pub fn set_multiband_state(&mut self, state: &[f32]) {
+            self.check(unsafe { ffi::s2r_set_multiband_state(self.handle, state.as_ptr(), state.len()) });
+        }
+
+        /// Every band's minimum gain over the last successful `sample_master` call that ran the stage.
+        pub fn multiband_meters(&self) -> Vec<f32> {
+            let b = self.master_multiband_bands();
+            let mut g = vec![0.0f32; 4];
+            self.check(unsafe { ffi::s2r_get_multiband_meters(self.handle, g.as_mut_ptr(), g.len()) });
+            g.truncate(b);
+            g
         }
 
         /// Every voice's send and send bus: checkpoint companions of `voice_mix`.

@@ -5,7 +5,7 @@ synth.py is the ctypes mirror of the reference's ``Synth`` used by tests and ben
 """
 from .synth import (Adsr, Note, Patch, S2rError, SampleRateKhz, Synth, Velocity, VoicePool,  # noqa: F401
                     default_patch, load_library, parse_patch, shard_pool_indices, stream_frame_json, sum_partials_device,
-                    voice_pan, pan_gains, voice_gain, fader_gains, send_gain, reverb_reference, delay_reference, chorus_reference, chorus_history_frames, chorus_rate, eq_reference, eq_design, dynamics_reference, dynamics_curve, dynamics_coef, room_reference, room_design, room_state_floats, drive_reference, drive_curve, drive_taps, flanger_reference, flanger_history_frames, master_reference, limiter_reference, loudness_reference, loudness_readings, loudness_design, spectrum_reference, spectrum_readings, spectrum_band_readings, spectrum_window, spectrum_twiddles, pcm_reference, pcm_dither, pcm_pack, pcm_shaper, resampler_reference, resampler_count, resampler_design, resampler_state_floats, resampler_max_out, MAX_BUSES, MAX_IR_TAPS, MAX_DELAY_FRAMES, CHORUS_MAX_VOICES, CHORUS_MAX_DELAY, EQ_MAX_BANDS, DYN_CURVE_POINTS, ROOM_COMBS, ROOM_ALLPASSES, ROOM_MIN_DELAY, ROOM_MAX_DELAY, DRIVE_OVERSAMPLE, DRIVE_TAPS, DRIVE_LATENCY, DRIVE_HISTORY, DRIVE_CURVE_POINTS, DRIVE_MAX_PRE, DRIVE_LINEAR, DRIVE_TANH, DRIVE_HARD, DRIVE_CUBIC, DRIVE_FOLD, FLANGER_MIN_DELAY, FLANGER_MAX_DELAY, EQ_PEAK, EQ_LOW_SHELF, EQ_HIGH_SHELF, EQ_LOWPASS, EQ_HIGHPASS, IR_SEGMENT, METER_BLOCK,
+                    voice_pan, pan_gains, voice_gain, fader_gains, send_gain, reverb_reference, delay_reference, chorus_reference, chorus_history_frames, chorus_rate, eq_reference, eq_design, dynamics_reference, dynamics_curve, dynamics_coef, room_reference, room_design, room_state_floats, drive_reference, drive_curve, drive_taps, flanger_reference, flanger_history_frames, master_reference, limiter_reference, loudness_reference, loudness_readings, loudness_design, spectrum_reference, spectrum_readings, spectrum_band_readings, spectrum_window, spectrum_twiddles, pcm_reference, pcm_dither, pcm_pack, pcm_shaper, resampler_reference, resampler_count, resampler_design, resampler_state_floats, resampler_max_out, multiband_reference, multiband_design, multiband_sections, multiband_state_floats, MULTIBAND_MAX_BANDS, MAX_BUSES, MAX_IR_TAPS, MAX_DELAY_FRAMES, CHORUS_MAX_VOICES, CHORUS_MAX_DELAY, EQ_MAX_BANDS, DYN_CURVE_POINTS, ROOM_COMBS, ROOM_ALLPASSES, ROOM_MIN_DELAY, ROOM_MAX_DELAY, DRIVE_OVERSAMPLE, DRIVE_TAPS, DRIVE_LATENCY, DRIVE_HISTORY, DRIVE_CURVE_POINTS, DRIVE_MAX_PRE, DRIVE_LINEAR, DRIVE_TANH, DRIVE_HARD, DRIVE_CUBIC, DRIVE_FOLD, FLANGER_MIN_DELAY, FLANGER_MAX_DELAY, EQ_PEAK, EQ_LOW_SHELF, EQ_HIGH_SHELF, EQ_LOWPASS, EQ_HIGHPASS, IR_SEGMENT, METER_BLOCK,
                     LIMITER_MAX_LOOKAHEAD, LIMITER_MAX_HOLD, LIMITER_CEILING_LOG2,
                     limiter_tp_reference, LIMITER_SAMPLE_PEAK, LIMITER_TRUE_PEAK, LIMITER_TP_LATENCY, LIMITER_TP_HISTORY,
                     LOUDNESS_PROGRAMMES, LOUDNESS_CHANNELS, LOUDNESS_STATE, LOUDNESS_MIN_HOP, LOUDNESS_MAX_HOP, LOUDNESS_MIN_HOPS, LOUDNESS_MAX_HOPS,

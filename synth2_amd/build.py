@@ -32,7 +32,8 @@ SOURCES = ["s2r_render_onepole_square.hip", "s2r_render_onepole_saw.hip", "s2r_r
            "s2r_host_post.cpp", # (likewise)
            "s2r_pcm.hip",       # (likewise, since the PCM stage came)
            "s2r_resampler.hip", # (likewise, since the sample-rate converter came)
-           "s2r_limiter_tp.hip"]    # (last, likewise, since the limiter's true-peak detector came)
+           "s2r_limiter_tp.hip",    # (likewise, since the limiter's true-peak detector came)
+           "s2r_multiband.hip"]     # (last, likewise, since the master's multiband compressor came)
 HEADERS = ["s2r_device.h", "s2r_math.h", "s2r_patch.h", "s2r_voices.h", "s2r_kern_common.h", "s2r_render_onepole.inc",
            "s2r_render_general.inc", "s2r_post.h", "s2r_post_route.h", "s2r_post_keep.h", "s2r_rules.h", "s2r_handle.h", "s2r_mixer.h",
            "s2r_mixer_keep.h"]
@@ -122,6 +123,10 @@ RESOURCE_CHECKS = {
     # an output frame per lane: eight accumulators, four taps and four frames of a step
     "s2r_resampler.hip": (("s2r_resampler_kernel",), ("exactly", 1), "one kernel",
                           (_SCRATCH, _VSPILL, _SSPILL), "the four chains of both channels must stay in registers, the rows and the span in LDS"),
+    # a section of one channel per crossover lane: five coefficients, two states, eight inputs read ahead, two values on their way; a
+    # band per walker lane: its gain, minimum and sixteen targets; a frame per worker lane
+    "s2r_multiband.hip": (("s2r_multiband_kernel",), ("exactly", 1), "one kernel",
+                          (_SCRATCH, _VSPILL, _SSPILL), "its coefficients, states, gains and the values read ahead must stay in registers, curves, tiles and the bands' ring in LDS"),
 }
 for _f in RESOURCE_CHECKS:
     PER_FILE_FLAGS[_f] = ["-Rpass-analysis=kernel-resource-usage"]
@@ -189,6 +194,14 @@ if _RESAMPLER_SERIAL:
 _LIMITER_TP_NAIVE = os.environ.get("S2R_LIMITER_TP_NAIVE") == "1"
 if _LIMITER_TP_NAIVE:
     PER_FILE_FLAGS["s2r_limiter_tp.hip"] = PER_FILE_FLAGS["s2r_limiter_tp.hip"] + ["-DS2R_LIMITER_TP_NAIVE"]
+# S2R_MULTIBAND_SERIAL=1 likewise builds the multiband kernel's obvious form (a lane per channel runs every section of a frame and then
+# the four gains, from global memory; csrc/s2r_multiband.hip, CHANGELOG) into libs2r_multibandserial.so, for tools/multiband_time.py.
+# Never the product build.
+_MULTIBAND_SERIAL = os.environ.get("S2R_MULTIBAND_SERIAL") == "1"
+if _MULTIBAND_SERIAL:
+    PER_FILE_FLAGS["s2r_multiband.hip"] = PER_FILE_FLAGS["s2r_multiband.hip"] + ["-DS2R_MULTIBAND_SERIAL"]
+    # (the comparison form reads 75 uniform coefficients at its head and spills 8 SGPRs there, outside its frame loop: no SGPR condition)
+    RESOURCE_CHECKS["s2r_multiband.hip"] = RESOURCE_CHECKS["s2r_multiband.hip"][:3] + ((_SCRATCH, _VSPILL),) + RESOURCE_CHECKS["s2r_multiband.hip"][4:]
 # S2R_OPT=O3 in the environment builds the same sources at -O3 into libs2r_o3.so (tools and tests that compare the two
 # optimisation levels; the product is -O2).
 if os.environ.get("S2R_OPT") == "O3":
@@ -235,6 +248,9 @@ elif _RESAMPLER_SERIAL:
 elif _LIMITER_TP_NAIVE:
     LIB = os.path.join(HERE, "libs2r_limitertpnaive.so")
     OBJ_DIR_NAME = "_build_limitertpnaive"
+elif _MULTIBAND_SERIAL:
+    LIB = os.path.join(HERE, "libs2r_multibandserial.so")
+    OBJ_DIR_NAME = "_build_multibandserial"
 else:
     OBJ_DIR_NAME = "_build"
 

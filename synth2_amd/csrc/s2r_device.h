@@ -627,6 +627,28 @@ struct S2rLimiterTp {
 };
 hipError_t s2r_launch_limiter_tp(const S2rLimiterTp &a, hipStream_t stream);
 
+// The master's multiband compressor: one launch behind the master kernel and in front of the limiter, in a master fill
+// that finds the stage set.  The master kernel writes the stage's own device buffer in such a call; this kernel reads it and writes
+// where the master kernel would have written.  The sections come as the rule's graph (multiband_graph, s2r_rules.h) with their
+// coefficients beside them; the state is the checkpoint's (s2r.h), `next` receives what the next call starts from.
+#define S2R_MULTIBAND_TILE 128u   // frames of one stage of the kernel's pipeline
+struct S2rMultiband {
+    const float *in;              // [frames][2] in device memory: what the master kernel wrote
+    float *out;                   // [frames][2], not `in`: the limiter's input, the meters' input or the pinned output
+    const float *state;           // [S2R_MULTIBAND_STATE(n_bands)]
+    float *next;                  // the same size, not `state`
+    const float *curves;          // [n_bands][S2R_DYN_CURVE_POINTS] in device memory
+    float *meter;                 // [S2R_MULTIBAND_MAX_BANDS], pinned and device-mapped: the call's minimum of y per band
+    float c[15][5];               // (b0, b1, b2, a1, a2) of every section, in the state's order
+    int32_t src[15];              // the section in front of it; -1: the stage's input
+    uint32_t depth[15];           // the sections in front of it
+    int32_t leaf[S2R_MULTIBAND_MAX_BANDS];       // the section that leaves band j; -1: the stage's input (one band)
+    float a_att[S2R_MULTIBAND_MAX_BANDS], a_rel[S2R_MULTIBAND_MAX_BANDS];
+    uint32_t n_bands, n_sections, frames;
+};
+// hipErrorInvalidValue for a null pointer, in == out, state == next, a band count outside 1 .. 4 or a graph that is not the rule's
+hipError_t s2r_launch_multiband(const S2rMultiband &a, hipStream_t stream);
+
 // The loudness and true-peak meters of s2r_fill_master: one launch behind the limiter (or the master kernel), the last
 // of a master fill that finds the meter set.  It reads the stems from the master's device stage and the master from device memory —
 // whoever writes the master last writes it there in such a call, never into the pinned output —, copies the master to the pinned

@@ -1,5 +1,5 @@
 // s2r_host_post.cpp — the C entries of libs2r in front of the post-mix chain (s2r_post.h; include/s2r.h): the eight bus stages, bus
-// returns, master fader, limiter, both meters, the sample-rate converter and the PCM stage, and the chain's measurement getters.  The chain owns what they set; what is
+// returns, master fader, multiband compressor, limiter, both meters, the sample-rate converter and the PCM stage, and the chain's measurement getters.  The chain owns what they set; what is
 // here checks the caller's values and the handle (s2r_handle.h).  Compiled with hipcc, -ffp-contract=off.
 #include "s2r_handle.h"
 
@@ -589,6 +589,100 @@ int s2r_get_limiter_meters(const s2r_synth *s, float *min_gain, float *out_peak)
     return S2R_OK;
 }
 
+// ---- the master's multiband compressor, between the master fader and the limiter ----
+// the values of a set, wrong whatever the handle holds: the ranges first, then the arrays that have rows
+static int multiband_values(s2r_synth *s, const char *who, uint32_t B, const float *lp, const float *hp, const float *ap, const float *curves, const float *a_att,
+                            const float *a_rel) {
+    if (!multiband_in_range(B, lp, hp, ap, curves, a_att, a_rel))
+        return set_err(s, S2R_ERR_PATCH_RANGE, "%s: %u bands: 1 .. %u bands, every coefficient finite and every section inside the stability triangle, every curve entry in [0, 256], every retention coefficient in [0, 1)",
+                       who, B, S2R_MULTIBAND_MAX_BANDS);
+    S2R_TRY(post_handle(s, who, "the master multiband compressor is"));
+    if (!curves || !a_att || !a_rel || (B >= 2u && (!lp || !hp)) || (B >= 3u && !ap)) return set_err(s, S2R_ERR_INVALID, "%s: null array", who);
+    return S2R_OK;
+}
+
+// the guard of the entries that need the stage set
+static int multiband_set(const s2r_synth *s, const char *who) {
+    S2R_TRY(post_handle(s, who, "the master multiband compressor is"));
+    if (!s->post.mb.n_bands) return set_err(const_cast<s2r_synth *>(s), S2R_ERR_INVALID, "%s: no master multiband compressor is set", who);
+    return S2R_OK;
+}
+
+int s2r_set_master_multiband(s2r_synth *s, uint32_t n_bands, const float *lp, const float *hp, const float *ap, const float *curves, const float *a_att,
+                             const float *a_rel) {
+    S2R_TRY(multiband_values(s, "s2r_set_master_multiband", n_bands, lp, hp, ap, curves, a_att, a_rel));
+    s->post.set_multiband(n_bands, lp, hp, ap, curves, a_att, a_rel, false);
+    return S2R_OK;
+}
+
+int s2r_set_master_multiband_params(s2r_synth *s, uint32_t n_bands, const float *lp, const float *hp, const float *ap, const float *curves,
+                                    const float *a_att, const float *a_rel) {
+    S2R_TRY(multiband_values(s, "s2r_set_master_multiband_params", n_bands, lp, hp, ap, curves, a_att, a_rel));
+    S2R_TRY(multiband_set(s, "s2r_set_master_multiband_params"));
+    if (n_bands != s->post.mb.n_bands)
+        return set_err(s, S2R_ERR_INVALID, "s2r_set_master_multiband_params: %u bands where %u are set: s2r_set_master_multiband changes the count", n_bands, s->post.mb.n_bands);
+    s->post.set_multiband(n_bands, lp, hp, ap, curves, a_att, a_rel, true);
+    return S2R_OK;
+}
+
+int s2r_clear_master_multiband(s2r_synth *s) {
+    S2R_TRY(post_handle(s, "s2r_clear_master_multiband", "the master multiband compressor is"));
+    s->post.set_multiband(0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false);
+    return S2R_OK;
+}
+
+int s2r_get_master_multiband(const s2r_synth *s, uint32_t *n_bands, float *lp, float *hp, float *ap, float *curves, float *a_att, float *a_rel) {
+    if (!s || !s->kids.empty() || s->parent) return S2R_ERR_INVALID;
+    const S2rPostChain::Multiband &f = s->post.mb;
+    const uint32_t B = f.n_bands;
+    put(n_bands, B);
+    if (B >= 2u) {
+        if (lp) std::memcpy(lp, f.lp, (size_t)(B - 1u) * 5u * sizeof(float));
+        if (hp) std::memcpy(hp, f.hp, (size_t)(B - 1u) * 5u * sizeof(float));
+    }
+    if (B >= 3u && ap) std::memcpy(ap, f.ap, (size_t)(B - 2u) * 5u * sizeof(float));
+    if (B && curves) std::memcpy(curves, f.curves.data(), f.curves.size() * sizeof(float));
+    if (B && a_att) std::memcpy(a_att, f.a_att, B * sizeof(float));
+    if (B && a_rel) std::memcpy(a_rel, f.a_rel, B * sizeof(float));
+    return S2R_OK;
+}
+
+int s2r_reset_master_multiband(s2r_synth *s) {
+    S2R_TRY(multiband_set(s, "s2r_reset_master_multiband"));
+    s->post.reset_multiband();
+    return S2R_OK;
+}
+
+int s2r_get_multiband_state(s2r_synth *s, float *state, size_t capacity) {
+    S2R_TRY(multiband_set(s, "s2r_get_multiband_state"));
+    S2rPostChain::Multiband &f = s->post.mb;
+    const size_t n = S2R_MULTIBAND_STATE(f.n_bands);
+    if (capacity < n) return set_err(s, S2R_ERR_INVALID, "s2r_get_multiband_state: the state is %zu floats, not %zu", n, capacity);
+    if (!state) return set_err(s, S2R_ERR_INVALID, "s2r_get_multiband_state: null buffer");
+    S2R_TRY(mirror_fetch(s, f.state, "s2r_get_multiband_state"));
+    std::memcpy(state, f.state.host.data(), n * sizeof(float));
+    return S2R_OK;
+}
+
+int s2r_set_multiband_state(s2r_synth *s, const float *state, size_t count) {
+    S2R_TRY(multiband_set(s, "s2r_set_multiband_state"));
+    S2rPostChain::Multiband &f = s->post.mb;
+    const size_t n = S2R_MULTIBAND_STATE(f.n_bands), n_filt = 4u * (size_t)S2R_MULTIBAND_SECTIONS(f.n_bands);
+    if (count != n) return set_err(s, S2R_ERR_INVALID, "s2r_set_multiband_state: the state is %zu floats, not %zu", n, count);
+    if (!state) return set_err(s, S2R_ERR_INVALID, "s2r_set_multiband_state: null buffer");
+    for (size_t i = 0; i < n; i++)
+        if (!std::isfinite(state[i]) || (i >= n_filt && !dyn_state_in_range(state[i])))
+            return set_err(s, S2R_ERR_PATCH_RANGE, "s2r_set_multiband_state: float %zu is %g: every float finite, the gains not below 0", i, (double)state[i]);
+    f.state.set(state, n);
+    return S2R_OK;
+}
+
+int s2r_get_multiband_meters(const s2r_synth *s, float *min_gain, size_t capacity) {
+    if (!s || !s->kids.empty() || s->parent || !s->post.mb.n_bands || !s->post.mb.metered || !min_gain || capacity < s->post.mb.n_bands) return S2R_ERR_INVALID;
+    std::memcpy(min_gain, s->post.mb.min_gain, s->post.mb.n_bands * sizeof(float));
+    return S2R_OK;
+}
+
 // ---- what the entries of the two meters behind the limiter share: their guard, their state pair and their rows pair ----
 enum { kLoudness, kSpectrum };
 static const struct { const char *are, *none, *rows; } kMeterWords[2] = {{"the loudness meter is", "no loudness meter is set", "hops"},
@@ -955,5 +1049,10 @@ uint32_t s2r_debug_pcm_tile(void) { return S2R_PCM_TILE; }
 float s2r_debug_resampler_ms(const s2r_synth *s) { return POST_MS(res.timer); }
 int s2r_debug_resampler_allocated(const s2r_synth *s) { return s && (s->post.res.res || s->post.res.res_dev || s->post.res.table_dev || s->post.res.state.dev[0] || s->post.loud.in) ? 1 : 0; }
 uint32_t s2r_debug_resampler_tile(void) { return S2R_RESAMPLER_TILE; }
+// ... and of the multiband kernel in that fill: 0 when it ran none (tools/multiband_time.py); whether the handle holds anything of the
+// stage's; and the frames of one stage of the kernel's pipeline (tests/test_gpu_multiband.py picks its call lengths around it)
+float s2r_debug_multiband_ms(const s2r_synth *s) { return POST_MS(mb.timer); }
+int s2r_debug_multiband_allocated(const s2r_synth *s) { return s && (s->post.mb.in || s->post.mb.curves_dev || s->post.mb.meter || s->post.mb.state.dev[0]) ? 1 : 0; }
+uint32_t s2r_debug_multiband_tile(void) { return S2R_MULTIBAND_TILE; }
 
 }  // extern "C"

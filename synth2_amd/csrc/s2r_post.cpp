@@ -1,4 +1,4 @@
-// s2r_post.cpp — the post-mix chain (s2r_post.h): the eight bus stages (EQs, dynamics, drives, flangers, choruses, delays, reverbs, rooms), master section, master limiter, loudness meters, spectrum meters, sample-rate converter, PCM stage —
+// s2r_post.cpp — the post-mix chain (s2r_post.h): the eight bus stages (EQs, dynamics, drives, flangers, choruses, delays, reverbs, rooms), master section, master multiband compressor, master limiter, loudness meters, spectrum meters, sample-rate converter, PCM stage —
 // the last five on the device side of s2r_post_keep.h (S2rMirror).  Compiled with hipcc, -ffp-contract=off.
 #include "s2r_post.h"
 #include "s2r_rules.h"
@@ -103,6 +103,12 @@ hipError_t S2rPostChain::prepare(const S2rPostCtx &c, uint32_t n_buses, uint32_t
         POST_HIP(limiter.state.reserve(kLimState));
         POST_HIP(pinned_rows(limiter.partials, limiter.partials_dev, (size_t)((c.max_frames + S2R_LIMITER_BLOCK - 1u) / S2R_LIMITER_BLOCK) * 2u));
     }
+    if (mb_on(call)) {                                           // its input, the tables, the two copies of its state, its pinned meter row
+        if (!mb.in) POST_HIP(hipMalloc((void **)&mb.in, (size_t)2 * c.max_frames * sizeof(float)));
+        if (!mb.curves_dev) { POST_HIP(hipMalloc((void **)&mb.curves_dev, (size_t)S2R_MULTIBAND_MAX_BANDS * S2R_DYN_CURVE_POINTS * sizeof(float))); mb.curves_valid = false; }
+        POST_HIP(mb.state.reserve(S2R_MULTIBAND_STATE(S2R_MULTIBAND_MAX_BANDS)));
+        POST_HIP(pinned_rows(mb.meter, mb.meter_dev, S2R_MULTIBAND_MAX_BANDS));
+    }
     if (metered(call) && !loud.in) POST_HIP(hipMalloc((void **)&loud.in, (size_t)2 * c.max_frames * sizeof(float)));      // the meters' input
     if (spec_on(call)) {                                         // the two copies of the state, the tables and the pinned rows, by n_fft and hop
         Spectrum &sp = spec;
@@ -175,7 +181,7 @@ hipError_t S2rPostChain::launch(const S2rPostCtx &c, const S2rPostCall &call) {
         if (call.on[k]) POST_TIMED(c, stage[k].timer, (this->*kStageLaunch[k])(c, call));
     if (call.master) {                                           // returns, master fader and the meters' block partials
         S2rMaster m{};
-        m.stage = r.master_in; m.out = r.master_out; m.stems = r.master_stems; m.partials = master.partials_dev;
+        m.stage = r.master_in; m.out = mb_on(call) ? mb.in : r.master_out; m.stems = r.master_stems; m.partials = master.partials_dev;
         m.n_buses = call.n_buses; m.frames = call.frames;
         for (uint32_t b = 0; b < call.n_buses; b++) {
             const float d = master.ret[b] - master.ret_app[b];   // (+0.0 for a pair that did not move, and so is its step)
@@ -184,6 +190,23 @@ hipError_t S2rPostChain::launch(const S2rPostCtx &c, const S2rPostCall &call) {
         const float d = master.fader - master.fader_app;
         m.m0 = master.fader_app; m.dm = d / fn;
         POST_TIMED(c, master.timer, s2r_launch_master(m, c.stream));
+    }
+    if (mb_on(call)) {                                           // between the master kernel and whoever reads the master next: it writes where the route sent the master
+        Multiband &f = mb;
+        if (!f.curves_valid)                                     // (stays so until the commit)
+            POST_HIP(hipMemcpyAsync(f.curves_dev, f.curves.data(), f.curves.size() * sizeof(float), hipMemcpyHostToDevice, c.stream));
+        POST_HIP(f.state.upload(c.stream));
+        const S2rMultibandGraph g = multiband_graph(f.n_bands);
+        S2rMultiband a{};
+        a.in = f.in; a.out = r.master_out; a.state = f.state.now(); a.next = f.state.next(); a.curves = f.curves_dev; a.meter = f.meter_dev;
+        for (uint32_t i = 0; i < g.n; i++) {
+            const float *q = g.kind[i] == 0u ? f.lp[g.row[i]] : (g.kind[i] == 1u ? f.hp[g.row[i]] : f.ap[g.row[i]]);
+            std::memcpy(a.c[i], q, sizeof a.c[i]);
+            a.src[i] = g.src[i]; a.depth[i] = g.depth[i];
+        }
+        for (uint32_t j = 0; j < f.n_bands; j++) { a.leaf[j] = g.leaf[j]; a.a_att[j] = f.a_att[j]; a.a_rel[j] = f.a_rel[j]; }
+        a.n_bands = f.n_bands; a.n_sections = g.n; a.frames = call.frames;
+        POST_TIMED(c, f.timer, s2r_launch_multiband(a, c.stream));
     }
     if (call.limited) {                                          // the next state goes into the copy that is not the current one
         Limiter &lm = limiter;
@@ -384,6 +407,11 @@ void S2rPostChain::commit(const S2rPostCall &call) {
         }
         ms.metered = true; ms.meter_buses = call.n_buses; snap_master();
     }
+    if (mb_on(call)) {                                           // the state has moved on, and the walkers' minima are the call's meters
+        Multiband &f = mb;
+        f.state.committed(); f.curves_valid = true; f.metered = true;
+        for (uint32_t j = 0; j < f.n_bands; j++) f.min_gain[j] = f.meter[j];
+    }
     if (call.limited) {                                          // the state has moved on, and the workgroups' rows give the call's meters
         Limiter &lm = limiter;
         lm.state.committed();
@@ -439,6 +467,8 @@ hipError_t S2rPostChain::read_timers(const S2rPostCall &call) {
     if (call.n_buses) for (int k = 0; k < S2R_BUS_STAGES; k++) { stage[k].timer.ms = 0.0f; if (call.on[k]) POST_HIP(stage[k].timer.read()); }
     if (call.master) {
         POST_HIP(master.timer.read());
+        mb.timer.ms = 0.0f;
+        if (mb_on(call)) POST_HIP(mb.timer.read());
         limiter.timer.ms = 0.0f;
         if (call.limited) POST_HIP(limiter.timer.read());
         loud.timer.ms = 0.0f;
@@ -457,12 +487,12 @@ void S2rPostChain::release() {
     for (uint32_t b = 0; b < S2R_MAX_BUSES; b++) { drop(eq[b]); drop(dyn[b]); drop(drive[b]); drop(flanger[b]); drop(chorus[b]); drop(delay[b]); drop(fx[b]); drop(room[b]); }
     for (Stem &st : stage) { if (st.buffer) (void)hipFree(st.buffer); st.timer.destroy(); }
     // ... and what is neither a line nor a stage's buffer
-    for (S2rMirror *m : {&limiter.state, &loud.state, &spec.state, &pcm.state, &res.state}) m->free();
-    for (float *p : {dyn_curves, drive_curves, master.stage, limiter.in, loud.in, spec.tables, res.table_dev, res.res_dev}) if (p) (void)hipFree(p);
-    for (float *p : {dyn_meter, master.partials, limiter.partials, loud.rows, loud.peaks, spec.rows, res.res}) if (p) (void)hipHostFree(p);
+    for (S2rMirror *m : {&limiter.state, &loud.state, &spec.state, &pcm.state, &res.state, &mb.state}) m->free();
+    for (float *p : {dyn_curves, drive_curves, master.stage, limiter.in, loud.in, spec.tables, res.table_dev, res.res_dev, mb.in, mb.curves_dev}) if (p) (void)hipFree(p);
+    for (float *p : {dyn_meter, master.partials, limiter.partials, loud.rows, loud.peaks, spec.rows, res.res, mb.meter}) if (p) (void)hipHostFree(p);
     if (pcm.samples) (void)hipHostFree(pcm.samples);
     if (pcm.counts) (void)hipHostFree(pcm.counts);
-    for (S2rPostTimer *t : {&master.timer, &limiter.timer, &loud.timer, &spec.timer, &pcm.timer, &res.timer}) t->destroy();
+    for (S2rPostTimer *t : {&master.timer, &limiter.timer, &loud.timer, &spec.timer, &pcm.timer, &res.timer, &mb.timer}) t->destroy();
 }
 
 hipError_t S2rPostChain::set_eq(const S2rPostCtx &c, uint32_t bus, uint32_t n_bands, const float *coeffs) {
@@ -631,6 +661,30 @@ void S2rPostChain::set_limiter_state(const float *xh, const float *gh) {
     std::vector<float> st(xh, xh + limiter.n_x());
     st.insert(st.end(), gh, gh + limiter.n_g());
     limiter.state.set(st.data(), st.size());
+}
+
+// a set starts from the rule's initial state — the filters +0.0, y_j = curves[j][0] —; the parameters alone keep the state
+void S2rPostChain::set_multiband(uint32_t n_bands, const float *lp, const float *hp, const float *ap, const float *curves, const float *a_att, const float *a_rel,
+                                 bool keep_state) {
+    Multiband &f = mb;
+    f.curves_valid = false;
+    if (!n_bands) { f.n_bands = 0; f.curves.clear(); f.state.off(); f.metered = false; return; }
+    f.n_bands = n_bands;
+    if (n_bands >= 2u) { std::memcpy(f.lp, lp, (size_t)(n_bands - 1u) * 5u * sizeof(float)); std::memcpy(f.hp, hp, (size_t)(n_bands - 1u) * 5u * sizeof(float)); }
+    if (n_bands >= 3u) std::memcpy(f.ap, ap, (size_t)(n_bands - 2u) * 5u * sizeof(float));
+    std::memcpy(f.a_att, a_att, n_bands * sizeof(float)); std::memcpy(f.a_rel, a_rel, n_bands * sizeof(float));
+    f.curves.assign(curves, curves + (size_t)n_bands * S2R_DYN_CURVE_POINTS);
+    if (!keep_state) reset_multiband();
+}
+
+void S2rPostChain::reset_multiband() {
+    Multiband &f = mb;
+    const uint32_t S = S2R_MULTIBAND_SECTIONS(f.n_bands);
+    std::vector<float> st(4u * (size_t)S + f.n_bands, 0.0f);
+    for (uint32_t j = 0; j < f.n_bands; j++) st[4u * (size_t)S + j] = f.curves[(size_t)j * S2R_DYN_CURVE_POINTS];
+    f.state.set(st.data(), st.size());
+    f.metered = false;
+    for (float &g : f.min_gain) g = 1.0f;
 }
 
 void S2rPostChain::set_loudness(const float *coeffs, uint32_t hop, uint32_t max_hops) {

@@ -1,8 +1,8 @@
 // s2r_post.h — the chain behind the bus mixdown of s2r_fill_buses and s2r_fill_master: the eight bus stages in the order of
 // S2rBusStage (s2r_post_route.h) — the buses' equalisers, their dynamics (4.22), drives (4.24), flangers (4.25),
-// choruses (4.20), feedback delays (4.19), convolution reverbs (4.16) and rooms (4.23) —, then the master section (4.17) and the master
+// choruses (4.20), feedback delays (4.19), convolution reverbs (4.16) and rooms (4.23) —, then the master section (4.17), the master's multiband compressor (4.31) and the master
 // limiter (4.18), and behind it the loudness and true-peak meters (4.26), the spectrum meters (4.27), the sample-rate converter (4.29) and the PCM stage (4.28).  The bus stages keep their
-// histories in a S2rBusLine each; the three stages behind the master fader keep their state in a S2rMirror each, and the two meters
+// histories in a S2rBusLine each; the stages behind the master fader keep their state in a S2rMirror each, and the two meters
 // their rows in a S2rRowStore each (s2r_post_keep.h).  The chain owns what these stages own and knows nothing of the handle: its
 // functions take a S2rPostCtx and return the HIP error.  Per call: prepare, launch, — the caller's synchronise — commit, read_timers.
 #pragma once
@@ -227,6 +227,25 @@ struct S2rPostChain {
         uint32_t count = 0;
         S2rPostTimer timer;                      // around the resampler kernel of the last master fill: 0 when it ran none (tools/resampler_time.py)
     } res;
+    // The master's multiband compressor (s2r_set_master_multiband), behind the master kernel and in front of the limiter.
+    // As the stages above: nothing is allocated before the first master fill that finds the stage set, and a handle on which it never was
+    // set makes the launches it always did.  In a call that runs it the master kernel writes `in` instead of route.master_out, and the
+    // stage's kernel writes there in its place: the route itself (s2r_post_route.h) knows nothing of the stage.
+    struct Multiband {
+        uint32_t n_bands = 0;                    // B; 0: off
+        float lp[S2R_MULTIBAND_MAX_BANDS - 1u][5] = {}, hp[S2R_MULTIBAND_MAX_BANDS - 1u][5] = {}, ap[S2R_MULTIBAND_MAX_BANDS - 2u][5] = {};
+        float a_att[S2R_MULTIBAND_MAX_BANDS] = {}, a_rel[S2R_MULTIBAND_MAX_BANDS] = {};
+        std::vector<float> curves;               // the host's copy of the tables: [B][S2R_DYN_CURVE_POINTS]; the device's is good while curves_valid
+        bool curves_valid = false;
+        float *curves_dev = nullptr;             // [S2R_MULTIBAND_MAX_BANDS][S2R_DYN_CURVE_POINTS] in device memory
+        S2rMirror state;                         // S2R_MULTIBAND_STATE(B) floats, in copies sized for four bands
+        float *in = nullptr;                     // [2 * max_frames] in device memory: where the master kernel writes when the stage is on
+        float *meter = nullptr, *meter_dev = nullptr;            // pinned and device-mapped: [S2R_MULTIBAND_MAX_BANDS], the call's minima
+        bool metered = false;                    // a master fill has run the stage since the set or reset: the minima below are its
+        float min_gain[S2R_MULTIBAND_MAX_BANDS] = {1.0f, 1.0f, 1.0f, 1.0f};
+        S2rPostTimer timer;                      // around the stage's kernel of the last master fill: 0 when it ran none (tools/multiband_time.py)
+    } mb;
+    bool mb_on(const S2rPostCall &call) const { return call.master && mb.n_bands != 0; }
     bool loud_on(const S2rPostCall &call) const { return call.master && loud.hop != 0; }
     bool spec_on(const S2rPostCall &call) const { return call.master && spec.n_fft != 0; }
     bool res_on(const S2rPostCall &call) const { return call.master && res.L != 0; }
@@ -273,6 +292,10 @@ struct S2rPostChain {
     void snap_master() { for (uint32_t b = 0; b < S2R_MAX_BUSES; b++) master.ret_app[b] = master.ret[b]; master.fader_app = master.fader; }
     void set_limiter(float ceiling, uint32_t lookahead, uint32_t hold, uint32_t detector);      // (0, 0, 0, 0): off
     void set_limiter_state(const float *xh, const float *gh);
+    // n_bands 0: off; keep_state: the parameters alone, with the n_bands that is set; else on, from the initial state
+    void set_multiband(uint32_t n_bands, const float *lp, const float *hp, const float *ap, const float *curves, const float *a_att, const float *a_rel,
+                       bool keep_state);
+    void reset_multiband();                                         // state and meters; the parameters stay
     void set_loudness(const float *coeffs, uint32_t hop, uint32_t max_hops);  // coeffs null: off; else on, from the initial state
     void reset_loudness();                                          // state, rows and held true peak; the parameters stay
     void set_spectrum(uint32_t n_fft, uint32_t hop, const float *window, uint32_t max_rows);   // window null: off; else on, from the initial state

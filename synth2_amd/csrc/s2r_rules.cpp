@@ -1,5 +1,5 @@
 // s2r_rules.cpp — the rules of libs2r that need neither a handle nor HIP: the voice mixer's gains, and the reverb, the delay, the master
-// section and the master limiter in plain host loops (s2r.h states each rule).  Plain C++17, -ffp-contract=off: every operation rounded on its own.
+// section, the master's multiband compressor and the master limiter in plain host loops (s2r.h states each rule).  Plain C++17, -ffp-contract=off: every operation rounded on its own.
 #include <cstddef>
 #include <cstring>
 #include <vector>
@@ -1003,6 +1003,95 @@ int s2r_resampler_design(uint32_t L, uint32_t M, uint32_t T, double beta, double
         double sum = 0.0;
         for (uint32_t k = 0; k < T; k++) sum += g[(size_t)k * L + p];
         for (uint32_t k = 0; k < T; k++) table[(size_t)p * T + k] = (float)(g[(size_t)k * L + p] / sum);
+    }
+    return S2R_OK;
+}
+
+}  // extern "C"
+
+// ---- the master's multiband compressor: a tree of crossover sections, a gain per band by the dynamics' rule, the bands
+// added in band order ----
+extern "C" {
+
+// one section, one frame: the nine operations of s2r_eq_reference
+static inline float multiband_section(const float *q, float x, float &s1, float &s2) {
+    const float p0 = q[0] * x;
+    const float y = p0 + s1;
+    const float p1 = q[1] * x, r1 = q[3] * y;
+    const float d1 = p1 - r1;
+    const float p2 = q[2] * x, r2 = q[4] * y;
+    s1 = d1 + s2;
+    s2 = p2 - r2;
+    return y;
+}
+
+int s2r_multiband_reference(uint32_t n_bands, const float *lp, const float *hp, const float *ap, const float *curves, const float *a_att,
+                            const float *a_rel, const float *x_lr, uint32_t frames, float *state, float *out_lr, float *bands, float *min_gain) {
+    const uint32_t B = n_bands;
+    if (!multiband_in_range(B, lp, hp, ap, curves, a_att, a_rel)) return S2R_ERR_PATCH_RANGE;
+    const uint32_t S = S2R_MULTIBAND_SECTIONS(B);
+    if (state) {
+        for (uint32_t i = 0; i < 4u * S; i++) if (!std::isfinite(state[i])) return S2R_ERR_PATCH_RANGE;
+        for (uint32_t j = 0; j < B; j++) if (!dyn_state_in_range(state[4u * S + j])) return S2R_ERR_PATCH_RANGE;
+    }
+    if (!curves || !a_att || !a_rel || !state || (!x_lr && frames) || (B >= 2u && (!lp || !hp)) || (B >= 3u && !ap)) return S2R_ERR_INVALID;
+    const S2rMultibandGraph g = multiband_graph(B);
+    const float *rows[3] = {lp, hp, ap};
+    float *y = state + 4u * S;
+    float mn[S2R_MULTIBAND_MAX_BANDS] = {INFINITY, INFINITY, INFINITY, INFINITY};
+    for (uint32_t n = 0; n < frames; n++) {
+        float band[S2R_MULTIBAND_MAX_BANDS][2];
+        for (uint32_t c = 0; c < 2u; c++) {
+            const float x = x_lr[2 * (size_t)n + c];
+            float v[15];
+            for (uint32_t i = 0; i < g.n; i++)
+                v[i] = multiband_section(rows[g.kind[i]] + 5u * g.row[i], g.src[i] < 0 ? x : v[g.src[i]], state[4u * i + c], state[4u * i + 2u + c]);
+            for (uint32_t j = 0; j < B; j++) band[j][c] = g.leaf[j] < 0 ? x : v[g.leaf[j]];
+        }
+        float out[2] = {0.0f, 0.0f};
+        for (uint32_t j = 0; j < B; j++) {
+            const float l = std::fabs(band[j][0]), r = std::fabs(band[j][1]);
+            const float p = l > r ? l : r;
+            const float t = dyn_target(curves + (size_t)j * S2R_DYN_CURVE_POINTS, p);
+            const float a = t < y[j] ? a_att[j] : a_rel[j];
+            const float d = y[j] - t;
+            const float m = a * d;
+            y[j] = t + m;
+            mn[j] = y[j] < mn[j] ? y[j] : mn[j];
+            for (uint32_t c = 0; c < 2u; c++) {
+                const float o = band[j][c] * y[j];
+                out[c] = j ? out[c] + o : o;
+                if (bands) bands[((size_t)j * frames + n) * 2u + c] = band[j][c];
+            }
+        }
+        if (out_lr) { out_lr[2 * (size_t)n] = out[0]; out_lr[2 * (size_t)n + 1] = out[1]; }
+    }
+    if (min_gain && frames) for (uint32_t j = 0; j < B; j++) min_gain[j] = mn[j];
+    return S2R_OK;
+}
+
+// the Audio-EQ-Cookbook's low-pass, high-pass and allpass at Q = 1 / sqrt 2: binary64 throughout, divided by a0, rounded once
+int s2r_multiband_design(double sample_rate, const double *freqs_hz, uint32_t n_splits, float *lp, float *hp, float *ap) {
+    if (n_splits > S2R_MULTIBAND_MAX_BANDS - 1u || !(sample_rate > 0.0) || !std::isfinite(sample_rate)) return S2R_ERR_PATCH_RANGE;
+    for (uint32_t k = 0; k < n_splits && freqs_hz; k++)
+        if (!(freqs_hz[k] > (k ? freqs_hz[k - 1u] : 0.0)) || !(freqs_hz[k] < sample_rate / 2.0)) return S2R_ERR_PATCH_RANGE;
+    if (n_splits && (!freqs_hz || !lp || !hp || (n_splits >= 2u && !ap))) return S2R_ERR_INVALID;
+    float out[3][S2R_MULTIBAND_MAX_BANDS - 1u][5];
+    for (uint32_t k = 0; k < n_splits; k++) {
+        const double w0 = 2.0 * 3.141592653589793 * freqs_hz[k] / sample_rate;
+        const double cw = std::cos(w0), alpha = std::sin(w0) / (2.0 * 0.70710678118654752440);
+        const double a0 = 1.0 + alpha, a1 = -2.0 * cw, a2 = 1.0 - alpha;
+        const double b[3][3] = {{(1.0 - cw) / 2.0, 1.0 - cw, (1.0 - cw) / 2.0}, {(1.0 + cw) / 2.0, -(1.0 + cw), (1.0 + cw) / 2.0}, {a2, a1, a0}};
+        for (uint32_t f = 0; f < 3u; f++) {
+            float *q = out[f][k];
+            q[0] = (float)(b[f][0] / a0); q[1] = (float)(b[f][1] / a0); q[2] = (float)(b[f][2] / a0); q[3] = (float)(a1 / a0); q[4] = (float)(a2 / a0);
+            if (!eq_band_in_range(q)) return S2R_ERR_PATCH_RANGE;
+        }
+    }
+    for (uint32_t k = 0; k < n_splits; k++) {
+        std::memcpy(lp + 5u * k, out[0][k], sizeof out[0][k]);
+        std::memcpy(hp + 5u * k, out[1][k], sizeof out[1][k]);
+        if (k >= 1u) std::memcpy(ap + 5u * (k - 1u), out[2][k], sizeof out[2][k]);
     }
     return S2R_OK;
 }

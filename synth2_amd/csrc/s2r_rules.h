@@ -197,6 +197,50 @@ static inline uint64_t resampler_count(uint32_t L, uint32_t M, uint32_t ph, uint
     return span <= ph ? 0u : (span - ph + M - 1u) / M;
 }
 
+// the master's multiband compressor: 1 .. 4 bands, every coefficient row as an EQ band's, every band's curve and
+// retention coefficients as a bus's dynamics'.  Null arrays pass: the caller refuses them by another name.
+static inline bool multiband_in_range(uint32_t B, const float *lp, const float *hp, const float *ap, const float *curves, const float *a_att, const float *a_rel) {
+    if (B < 1u || B > S2R_MULTIBAND_MAX_BANDS) return false;
+    for (uint32_t k = 0; k + 1u < B; k++) {
+        if (lp && !eq_band_in_range(lp + 5u * k)) return false;
+        if (hp && !eq_band_in_range(hp + 5u * k)) return false;
+        if (ap && k >= 1u && !eq_band_in_range(ap + 5u * (k - 1u))) return false;
+    }
+    for (uint32_t j = 0; j < B; j++) {
+        if (a_att && !dyn_coef_in_range(a_att[j])) return false;
+        if (a_rel && !dyn_coef_in_range(a_rel[j])) return false;
+        if (curves && !dyn_in_range(curves + (size_t)j * S2R_DYN_CURVE_POINTS, 0.0f, 0.0f)) return false;
+    }
+    return true;
+}
+// The crossover's sections in the state's order — LPa_0, LPb_0, HPa_0, HPb_0, LPa_1, ..., then AP_{0,1}, AP_{0,2}, AP_{1,2} —: where a
+// section takes its input (-1: the stage's input x, else an earlier section), whose coefficients it uses (kind 0: lp[row], 1: hp[row],
+// 2: ap[row]), how many sections lie in front of it, and the section that leaves band j (-1: x itself, at B = 1).
+struct S2rMultibandGraph {
+    uint32_t n;
+    int32_t src[15], leaf[S2R_MULTIBAND_MAX_BANDS];
+    uint32_t kind[15], row[15], depth[15];
+};
+static inline S2rMultibandGraph multiband_graph(uint32_t B) {
+    S2rMultibandGraph g{};
+    for (uint32_t k = 0; k + 1u < B; k++) {
+        const int32_t r = k ? (int32_t)(4u * (k - 1u) + 3u) : -1;
+        const uint32_t dr = k ? g.depth[r] + 1u : 0u;
+        const uint32_t at = 4u * k;
+        g.src[at] = r; g.src[at + 1u] = (int32_t)at; g.src[at + 2u] = r; g.src[at + 3u] = (int32_t)(at + 2u);
+        for (uint32_t i = 0; i < 4u; i++) { g.kind[at + i] = i >> 1; g.row[at + i] = k; g.depth[at + i] = dr + (i & 1u); }
+    }
+    uint32_t at = 4u * (B - 1u);
+    for (uint32_t j = 0; j < B; j++) g.leaf[j] = j + 1u < B ? (int32_t)(4u * j + 1u) : (B > 1u ? (int32_t)(4u * (B - 2u) + 3u) : -1);
+    for (uint32_t j = 0; j + 2u < B; j++)
+        for (uint32_t k = j + 1u; k + 1u < B; k++) {
+            g.src[at] = g.leaf[j]; g.kind[at] = 2u; g.row[at] = k - 1u; g.depth[at] = g.depth[g.leaf[j]] + 1u;
+            g.leaf[j] = (int32_t)at++;
+        }
+    g.n = at;
+    return g;
+}
+
 // The voice mixer's gain rules, inline: the host's per-voice loops compile them in — a call per voice into s2r_rules.cpp showed as 10
 // to 15 us of host time per fill of 65 536 voices (profiles/r12/post_chain.txt).  s2r_rules.cpp exports them under their s2r.h names.
 static inline float rule_voice_pan(float pan, float key_spread, uint8_t note) {

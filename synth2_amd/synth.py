@@ -377,6 +377,16 @@ def load_library():
                                               C.c_size_t, C.POINTER(C.c_size_t)]),
         "s2r_resampler_count": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t)]),
         "s2r_resampler_design": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_double, _f32p]),
+        "s2r_set_master_multiband": (C.c_int, [H, C.c_uint32, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p]),
+        "s2r_set_master_multiband_params": (C.c_int, [H, C.c_uint32, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p]),
+        "s2r_clear_master_multiband": (C.c_int, [H]),
+        "s2r_get_master_multiband": (C.c_int, [H, C.POINTER(C.c_uint32), _f32p, _f32p, _f32p, _f32p, _f32p, _f32p]),
+        "s2r_reset_master_multiband": (C.c_int, [H]),
+        "s2r_get_multiband_state": (C.c_int, [H, _f32p, C.c_size_t]),
+        "s2r_set_multiband_state": (C.c_int, [H, _f32p, C.c_size_t]),
+        "s2r_get_multiband_meters": (C.c_int, [H, _f32p, C.c_size_t]),
+        "s2r_multiband_reference": (C.c_int, [C.c_uint32, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_uint32, _f32p, _f32p, _f32p, _f32p]),
+        "s2r_multiband_design": (C.c_int, [C.c_double, C.POINTER(C.c_double), C.c_uint32, _f32p, _f32p, _f32p]),
         "s2r_fill_device": (C.c_int, [H, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
         "s2r_fill_device_root": (C.c_int, [H, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
         "s2r_sum_partials_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_size_t, C.c_void_p, C.c_void_p]),
@@ -603,6 +613,75 @@ def dynamics_reference(curve, a_att, a_rel, key, x, y):
     if rc != S2R_OK:
         raise S2rError(rc, load_library().s2r_status_string(rc).decode())
     return out, st[0], mn[0]
+
+
+MULTIBAND_MAX_BANDS = 4                     # S2R_MULTIBAND_MAX_BANDS
+
+
+def multiband_sections(n_bands):
+    """S2R_MULTIBAND_SECTIONS: the crossover's sections per channel, 0, 4, 9, 15 for 1 .. 4 bands"""
+    b = int(n_bands)
+    return 4 * (b - 1) + (b - 1) * (b - 2) // 2
+
+
+def multiband_state_floats(n_bands):
+    """S2R_MULTIBAND_STATE: [section][s1_L, s1_R, s2_L, s2_R], then the bands' gains"""
+    return 4 * multiband_sections(n_bands) + int(n_bands)
+
+
+def multiband_design(sample_rate, splits_hz):
+    """the crossover's rows for split frequencies strictly ascending inside (0, sample_rate / 2) (s2r_multiband_design): second-order
+    Butterworth cookbook rows, float32 (lp [n, 5], hp [n, 5], ap [max(n - 1, 0), 5]) as (b0, b1, b2, a1, a2)"""
+    f = np.ascontiguousarray(splits_hz, dtype=np.float64).reshape(-1)
+    n = f.size
+    lp, hp, ap = np.zeros((n, 5), np.float32), np.zeros((n, 5), np.float32), np.zeros((max(n - 1, 0), 5), np.float32)
+    _rule_check(load_library().s2r_multiband_design(float(sample_rate), f.ctypes.data_as(C.POINTER(C.c_double)), n, _f32_or_null(lp),
+                                                    _f32_or_null(hp), _f32_or_null(ap)))
+    return lp, hp, ap
+
+
+def _f32_or_null(a):
+    return a.ctypes.data_as(_f32p) if a.size else None
+
+
+def _multiband_args(who, coeffs, curves, attack, release):
+    """(B, lp, hp, ap, curves, a_att, a_rel) as contiguous float32 arrays, B taken from the curves"""
+    cv = np.ascontiguousarray(curves, dtype=np.float32)
+    if cv.ndim != 2 or cv.shape[1] != DYN_CURVE_POINTS:
+        raise ValueError(who + ": curves is [n_bands, %d] float32" % DYN_CURVE_POINTS)
+    B = cv.shape[0]
+    lp, hp, ap = (np.ascontiguousarray(c, dtype=np.float32).reshape(-1, 5) for c in (coeffs if coeffs is not None else ((), (), ())))
+    att, rel = np.ascontiguousarray(attack, dtype=np.float32).reshape(-1), np.ascontiguousarray(release, dtype=np.float32).reshape(-1)
+    if lp.shape[0] != max(B - 1, 0) or hp.shape[0] != max(B - 1, 0) or ap.shape[0] != max(B - 2, 0) or att.size != B or rel.size != B:
+        raise ValueError(who + ": %d curves need %d low-pass and high-pass rows, %d allpass rows and %d attack and release coefficients"
+                         % (B, max(B - 1, 0), max(B - 2, 0), B))
+    return B, lp, hp, ap, cv, att, rel
+
+
+def multiband_reference(coeffs, curves, attack, release, x, state=None, want_bands=False):
+    """the master multiband compressor's rule on the host (s2r_multiband_reference): coeffs (lp, hp, ap) as multiband_design returns
+    them (None for one band), curves [B, DYN_CURVE_POINTS], the bands' retention coefficients, x [frames, 2] float32, state
+    [multiband_state_floats(B)] (None: the state right after a set).  Returns (out [frames, 2], the state after the call, the bands'
+    minima of y — inf for no frames) and, with want_bands, the band signals in front of the gains [B, frames, 2] as a fourth value"""
+    B, lp, hp, ap, cv, att, rel = _multiband_args("multiband_reference", coeffs, curves, attack, release)
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    if x.ndim != 2 or x.shape[1] != 2:
+        raise ValueError("multiband_reference: x is [frames, 2]")
+    n_state = multiband_state_floats(B) if 1 <= B <= MULTIBAND_MAX_BANDS else 0
+    if state is None:
+        st = np.zeros(n_state, dtype=np.float32)
+        if n_state:
+            st[n_state - B:] = cv[:, 0]
+    else:
+        st = np.array(state, dtype=np.float32).reshape(-1)
+        if st.size != n_state:
+            raise ValueError("multiband_reference: the state is %d floats" % n_state)
+    out, mn = np.empty_like(x), np.full(max(B, 1), np.inf, dtype=np.float32)
+    bands = np.empty((B, x.shape[0], 2), dtype=np.float32) if want_bands else None
+    _rule_check(load_library().s2r_multiband_reference(B, _f32_or_null(lp), _f32_or_null(hp), _f32_or_null(ap), cv.ctypes.data_as(_f32p), att.ctypes.data_as(_f32p),
+                                                       rel.ctypes.data_as(_f32p), x.ctypes.data_as(_f32p), x.shape[0], st.ctypes.data_as(_f32p),
+                                                       out.ctypes.data_as(_f32p), bands.ctypes.data_as(_f32p) if want_bands else None, mn.ctypes.data_as(_f32p)))
+    return (out, st, mn[:B], bands) if want_bands else (out, st, mn[:B])
 
 
 def dynamics_curve(threshold_db, ratio, knee_db=0.0, makeup_db=0.0):
@@ -2119,6 +2198,75 @@ class Synth:
     @staticmethod
     def resampler_design(L, M, T, beta=10.0, rolloff=0.9):
         return resampler_design(L, M, T, beta, rolloff)
+
+    # --- the master multiband compressor (build-defined; s2r.h: s2r_set_master_multiband) ---
+    def _multiband(self, who, entry, splits_hz, coeffs, curves, attack, release, sample_rate):
+        if splits_hz is not None and coeffs is not None:
+            raise ValueError(who + ": give splits_hz or coeffs, not both")
+        if splits_hz is not None:
+            coeffs = multiband_design(sample_rate, splits_hz)
+        B, lp, hp, ap, cv, att, rel = _multiband_args(who, coeffs, curves, attack, release)
+        self._check(entry(self.h, B, _f32_or_null(lp), _f32_or_null(hp), _f32_or_null(ap), cv.ctypes.data_as(_f32p), att.ctypes.data_as(_f32p),
+                          rel.ctypes.data_as(_f32p)))
+
+    def set_master_multiband(self, curves, attack, release, splits_hz=None, coeffs=None, sample_rate=48000.0):
+        """the master split into len(curves) bands between the master fader and the limiter, each compressed by its own curve
+        [DYN_CURVE_POINTS] and retention coefficients, and added back (s2r.h): splits_hz designs the crossover at `sample_rate`
+        (multiband_design), or coeffs = (lp, hp, ap) gives its rows; one band needs neither.  The state starts afresh."""
+        self._multiband("set_master_multiband", self.L.s2r_set_master_multiband, splits_hz, coeffs, curves, attack, release, sample_rate)
+
+    def set_master_multiband_params(self, curves, attack, release, splits_hz=None, coeffs=None, sample_rate=48000.0):
+        """the same arguments with the band count that is set: the parameters change, the state stays"""
+        self._multiband("set_master_multiband_params", self.L.s2r_set_master_multiband_params, splits_hz, coeffs, curves, attack, release, sample_rate)
+
+    def clear_master_multiband(self):
+        self._check(self.L.s2r_clear_master_multiband(self.h))
+
+    def _multiband_bands(self):
+        b = C.c_uint32()
+        self._check(self.L.s2r_get_master_multiband(self.h, C.byref(b), None, None, None, None, None, None))
+        return b.value
+
+    def get_master_multiband(self):
+        """None when off, else dict(n_bands, lp, hp, ap, curves, attack, release)"""
+        B = self._multiband_bands()
+        if not B:
+            return None
+        lp, hp, ap = np.zeros((B - 1, 5), np.float32), np.zeros((B - 1, 5), np.float32), np.zeros((max(B - 2, 0), 5), np.float32)
+        cv, att, rel = np.zeros((B, DYN_CURVE_POINTS), np.float32), np.zeros(B, np.float32), np.zeros(B, np.float32)
+        self._check(self.L.s2r_get_master_multiband(self.h, None, _f32_or_null(lp), _f32_or_null(hp), _f32_or_null(ap), cv.ctypes.data_as(_f32p),
+                                                    att.ctypes.data_as(_f32p), rel.ctypes.data_as(_f32p)))
+        return dict(n_bands=B, lp=lp, hp=hp, ap=ap, curves=cv, attack=att, release=rel)
+
+    def reset_master_multiband(self):
+        """filters and gains as right after a set; the parameters stay"""
+        self._check(self.L.s2r_reset_master_multiband(self.h))
+
+    def multiband_state(self):
+        """float32 [multiband_state_floats(B)]: every section's (s1_L, s1_R, s2_L, s2_R), then the bands' gains (checkpoints)"""
+        B = self._multiband_bands()
+        st = np.empty(multiband_state_floats(B) if B else 1, dtype=np.float32)
+        self._check(self.L.s2r_get_multiband_state(self.h, st.ctypes.data_as(_f32p), st.size))
+        return st
+
+    def set_multiband_state(self, state):
+        st = np.ascontiguousarray(state, dtype=np.float32).reshape(-1)
+        self._check(self.L.s2r_set_multiband_state(self.h, st.ctypes.data_as(_f32p), st.size))
+
+    def multiband_meters(self):
+        """float32 [B]: every band's minimum of y over the last sample_master call that ran the stage"""
+        mn = np.empty(MULTIBAND_MAX_BANDS, dtype=np.float32)
+        B = self._multiband_bands()
+        self._check(self.L.s2r_get_multiband_meters(self.h, mn.ctypes.data_as(_f32p), mn.size))
+        return mn[:B].copy()
+
+    @staticmethod
+    def multiband_reference(coeffs, curves, attack, release, x, state=None, want_bands=False):
+        return multiband_reference(coeffs, curves, attack, release, x, state, want_bands)
+
+    @staticmethod
+    def multiband_design(sample_rate, splits_hz):
+        return multiband_design(sample_rate, splits_hz)
 
     def render_voices(self, frames, sample_rate=SampleRateKhz(48000)):
         """Mix disabled: (shard_voices, frames) float32."""
