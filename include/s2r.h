@@ -962,7 +962,8 @@ int s2r_limiter_tp_reference(const float *x, uint32_t frames, float ceiling, uin
  *   s2r_clear_master_multiband: off.  s2r_get_master_multiband: *n_bands is 0 when off; every array may be NULL.
  *   s2r_reset_master_multiband: the state right after a set; the parameters stay.
  *   s2r_get_multiband_state / s2r_set_multiband_state: S2R_MULTIBAND_STATE(B) floats (a capacity of at least that; a count of exactly
- *   that, every float finite, the gains >= 0: else S2R_ERR_PATCH_RANGE).
+ *   that, every float finite, the gains >= 0: else S2R_ERR_PATCH_RANGE).  The setter and s2r_set_master_multiband_params leave the
+ *   meters of the last fill as they are; a set, a reset and a fresh handle that is given a checkpoint hold none.
  *   s2r_get_multiband_meters: min_gain [B] of the last successful master fill that ran the stage; S2R_ERR_INVALID before one.
  *   s2r_multiband_reference: the rule on the host: state [S2R_MULTIBAND_STATE(B)] in place; out_lr [frames][2], bands
  *   [B][frames][2] (the band signals in front of the gains) and min_gain [B] (written when frames > 0) may each be NULL.
@@ -1217,7 +1218,8 @@ int s2r_spectrum_twiddles(uint32_t n_fft, float *twiddles);
  *   s2r_get_pcm_clips: per channel, the clips of that fill (`last`) and since the set or reset (`held`, saturating); either may be NULL.
  *   s2r_get_pcm_state / s2r_set_pcm_state (checkpoints): the 162 floats and t; the getter takes a capacity of at least
  *   S2R_PCM_STATE, the setter exactly S2R_PCM_STATE, every value within [-2, 2] (S2R_ERR_PATCH_RANGE otherwise, for a NaN too);
- *   it keeps the first K entries of a row and stores +0.0 past them.
+ *   it keeps the first K entries of a row and stores +0.0 past them.  The setter moves the state and t alone: the last samples and
+ *   both clip counts stay as they are, and a fresh handle that is given a checkpoint holds no samples and counts of 0.
  *   S2R_ERR_INVALID for a wrong size, a NULL buffer or with the stage off.
  *   s2r_pcm_reference: the device rule on the host (no device, no handle).  stems [n_buses][frames][2] (NULL with n_buses 0),
  *   master_lr [frames][2]; state[S2R_PCM_STATE] and *t updated in place; pcm [9][frames][2]; clips[18] receives the call's counts
@@ -1309,7 +1311,8 @@ int s2r_pcm_shaper(uint32_t kind, float *taps, uint32_t *n_taps);
  *   which may be 0.  S2R_ERR_INVALID before any such fill, with the stage off or for NULL out_lr.
  *   s2r_get_resampler_state / s2r_set_resampler_state (checkpoints): the floats and ph; the getter takes a capacity of at least
  *   S2R_RESAMPLER_STATE(T), the setter exactly that many floats — any values, non-finite ones too — and ph < M (S2R_ERR_PATCH_RANGE
- *   otherwise).  S2R_ERR_INVALID for a wrong size, a NULL buffer or with the stage off.
+ *   otherwise).  S2R_ERR_INVALID for a wrong size, a NULL buffer or with the stage off.  The setter moves the state and ph alone: the
+ *   last outputs stay as they are, and a fresh handle that is given a checkpoint holds none.
  *   s2r_resampler_reference: the device rule on the host (no device, no handle).  stems [n_buses][frames][2] (NULL with n_buses 0),
  *   master_lr [frames][2]; state[S2R_RESAMPLER_STATE(T)] and *ph updated in place; out [9][capacity][2] receives *count frames of
  *   every programme.  S2R_ERR_PATCH_RANGE as the setter's, for n_buses > 8 and for *ph >= M; S2R_ERR_INVALID for a NULL or a

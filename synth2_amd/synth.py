@@ -80,6 +80,7 @@ SHAPER_FLAT, SHAPER_FIRST, SHAPER_SECOND, SHAPER_3TAP, SHAPER_5TAP, SHAPER_9TAP 
 RESAMPLER_PROGRAMMES, RESAMPLER_CHANNELS = 9, 18                         # S2R_RESAMPLER_PROGRAMMES, S2R_RESAMPLER_CHANNELS
 RESAMPLER_MAX_FACTOR, RESAMPLER_MIN_TAPS, RESAMPLER_MAX_TAPS = 320, 4, 128         # S2R_RESAMPLER_MAX_FACTOR, S2R_RESAMPLER_MIN_TAPS, S2R_RESAMPLER_MAX_TAPS
 RESAMPLER_MAX_TABLE, RESAMPLER_MAX_TAP = 24576, 4.0                      # S2R_RESAMPLER_MAX_TABLE, S2R_RESAMPLER_MAX_TAP
+RESAMPLER_MAX_RATIO = 4                                          # s2r.h, s2r_set_master_resampler: L / M within 1/4 .. 4
 _DITHER_KINDS = {"none": DITHER_NONE, "rect": DITHER_RECT, "rpdf": DITHER_RECT, "rectangular": DITHER_RECT, "tri": DITHER_TRI, "tpdf": DITHER_TRI,
                  "triangular": DITHER_TRI}
 _WINDOW_KINDS = {"rect": WINDOW_RECT, "rectangular": WINDOW_RECT, "hann": WINDOW_HANN, "hamming": WINDOW_HAMMING,
@@ -2101,9 +2102,10 @@ class Synth:
 
     def pcm(self, programme=MAX_BUSES):
         """int32 [frames, 2]: the samples of bus `programme`, or of the master (MAX_BUSES), of the last sample_master call"""
-        l, m = C.c_uint32(), C.c_uint32()                        # (behind the resampler a call can make more frames than it was given)
-        self._check(self.L.s2r_get_master_resampler(self.h, C.byref(l), C.byref(m), None, None))
-        most = max(self.max_frames, resampler_max_out(self.max_frames, l.value, m.value) if l.value else 0)
+        # Behind the resampler a call can make more frames than it was given, and the samples stay held when that resampler is
+        # cleared or replaced by one of a smaller ratio: the buffer is sized by the largest ratio a resampler can have, 4, not by
+        # the one that is set now
+        most = resampler_max_out(self.max_frames, RESAMPLER_MAX_RATIO, 1)
         out, n = np.empty((most, 2), dtype=np.int32), C.c_size_t()
         self._check(self.L.s2r_get_pcm(self.h, int(programme), out.ctypes.data_as(C.POINTER(C.c_int32)), out.size, C.byref(n)))
         return out[:n.value].copy()

@@ -1,4 +1,4 @@
-"""Seeded walks over the post-mix chain (DESIGN.md 4.16 to 4.25) and the chain's host model, with no GPU in it: tests/test_gpu_post_fuzz.py
+"""Seeded walks over the post-mix chain (DESIGN.md 4.16 to 4.31) and the chain's host model, with no GPU in it: tests/test_gpu_post_fuzz.py
 plays a walk on a pair of twin handles, tests/test_post_walk_host.py holds the walks themselves to coverage conditions and runs them
 through the model alone.
 
@@ -14,7 +14,17 @@ chain's steps (_splice), which stay the ones a seed gave before the meters joine
 A master fill feeds each meter that is on; Chain.meter_readings is what the getters that move nothing must then give, behind any kind
 of fill, and Chain.meter_states what the getters that fetch the state's device copy give — read at a round trip, at a handover,
 behind every other bus fill and panned fill (peeks) and at the end of a walk, so that master fills meet the copies both flipped
-unread and fetched."""
+unread and fetched.
+
+The four stages of DESIGN.md 4.28 to 4.31 are composed the same way: test_gpu_multiband.Mb between the master fader and the limiter,
+test_gpu_limiter_tp.LimTp as the limiter under either detector, test_gpu_resampler.Res over the stems and the master as the caller
+receives it, and test_gpu_pcm.Stage over the converter's nine outputs, or over the stems and the master without one.  Their actions —
+OUTPUT_KINDS — come from a third generator (_splice_outputs) that leaves the steps of the first two what they were.  With a meter on,
+neither the converter's kernel nor the PCM stage's copies the master to the pinned output, and the meters are on nearly all of a
+walk: meters_pause clears the meters that are on in front of a master fill and meters_resume sets the same ones again behind it, in
+front of the second generator's next action of theirs.  Chain.meter_readings carries the multiband's minima, the converter's outputs
+and the PCM stage's integers and clips, Chain.meter_states the four mirrors — the limiter's among them, at its detector's sizes —,
+and master_subset_walk goes through the 16 subsets of the four kernels behind the limiter on one handle."""
 import numpy as np
 
 import synth2_amd as s2
@@ -29,9 +39,12 @@ from test_gpu_drive import DriveModel, oversampled
 from test_gpu_dyn import COEFS, RATIOS, DynModel
 from test_gpu_eq import EqModel, _coeffs
 from test_gpu_flanger import SHAPE as FLANGER_SHAPE, FlangerModel
-from test_gpu_limiter import Lim
+from test_gpu_limiter_tp import LimTp
 from test_gpu_loudness import Meter as LoudnessMeter
 from test_gpu_master import Master
+from test_gpu_multiband import RATIOS as MB_RATIOS, Mb
+from test_gpu_pcm import Stage, _taps
+from test_gpu_resampler import Res
 from test_gpu_reverb import MIXES, SR, Model, _ir
 from test_gpu_room import LEVELS, RoomModel
 from test_gpu_spectrum import Meter as SpectrumMeter
@@ -42,6 +55,10 @@ from test_room_host import FLAT, SMALL
 F = np.float32
 # the default sweep of tests/test_gpu_post_fuzz.py and tests/test_post_walk_host.py: S2R_POST_FUZZ_BASE moves it, S2R_POST_FUZZ_SEEDS widens it
 DEFAULT_BASE, DEFAULT_SEEDS = 5000, 32
+# the seeds that found a fault, run beside the default sweep wherever it has been moved: at step 33 of 500030 and steps 19 and 63 of
+# 500211 a bus fill reads PCM samples of more than max_frames frames behind the clear or the replacement of the converter that made
+# them, which Synth.pcm, sizing its buffer by the converter that is set now, answered with S2R_ERR_INVALID
+REGRESSION_SEEDS = (500030, 500211)
 STAGES = ("eq", "dyn", "drive", "flanger", "chorus", "delay", "reverb", "room")        # chain order
 INSERTS = ("eq", "dyn", "drive", "flanger", "room")
 STEMS = ("chorus", "delay", "reverb")
@@ -51,8 +68,24 @@ CHAIN_KINDS = ("set", "clear", "params", "limiter_set", "limiter_clear", "limite
 # the meters behind the limiter and a master fill that is refused: what a second generator splices between the
 # steps above (_splice), which stay what they were before the meters joined the walks
 METER_KINDS = ("loudness_set", "loudness_reset", "loudness_clear", "spectrum_set", "spectrum_reset", "spectrum_clear", "refused_fill")
-KINDS_OF_ACTION = CHAIN_KINDS + METER_KINDS
+# the multiband compressor in front of the limiter, the limiter's detector, and the converter and the PCM stage behind the meters
+# (DESIGN.md 4.28 to 4.31): what a third generator splices between the steps of the two above (_splice_outputs), which stay what they
+# were.  None of them is a fill: a fill would advance the twin's voices
+OUTPUT_KINDS = ("multiband_set", "multiband_params", "multiband_reset", "multiband_clear", "limiter_detector", "resampler_set", "resampler_reset",
+                "resampler_clear", "pcm_set", "pcm_reset", "pcm_clear", "pcm_wrap", "meters_pause", "meters_resume")
+KINDS_OF_ACTION = CHAIN_KINDS + METER_KINDS + OUTPUT_KINDS
 METER_SALT = 0x6D657472                                          # the second generator's seed is seed ^ METER_SALT
+OUTPUT_SALT = 0x6F757470                                         # the third generator's is seed ^ OUTPUT_SALT
+# (L, M, T): the identity at (1, 1, 4); whole-table staging at L <= 64 and tile-row staging above it; ratios of a quarter and of
+# 147 / 320 that make no frame of a short call; T from 4 to 64
+RESAMPLER_LMT = ((1, 1, 4), (2, 1, 32), (1, 2, 64), (4, 1, 8), (1, 4, 8), (2, 3, 16), (147, 160, 48), (160, 147, 48), (147, 320, 24))
+PCM_BITS, PCM_DITHERS = (8, 16, 24), ("none", "rect", "tpdf")
+PCM_TAPS = (0, 1, 2, 3, 5, 7, 9)                                 # the four compiled counts (0, 1 .. 2, 3 .. 5, 6 .. 9) and those between them
+PCM_T_WRAP = 2 ** 32 - 64                                        # what pcm_wrap reloads t with: the next master fill of 64 frames or more crosses 2^32
+# per step and stage: an absent one is set, a present one is replaced, reset or cleared (the multiband: or given parameters); per step:
+# the other detector, and with a PCM stage on a reload of t.  Chosen so that conditions 17 to 23 of tests/test_post_walk_host.py hold
+P_OUT_SET, P_OUT_REPLACE, P_OUT_RESET, P_OUT_CLEAR, P_OUT_PARAMS, P_DETECTOR, P_WRAP = 0.45, 0.08, 0.04, 0.05, 0.06, 0.12, 0.05
+P_PAUSE = 0.03                                                   # per step with a meter on: a master fill without the meters (meters_pause)
 # hop 17 most often: the one hop here that ends on the last frame of a walker's block of eight (test_gpu_loudness.walker_distances)
 LOUDNESS_HOPS, LOUDNESS_HOP_P = (16, 17, 48, 100, 4800), (0.17, 0.33, 0.2, 0.2, 0.1)
 LOUDNESS_MAX_HOPS = (30, 32, 200)
@@ -153,7 +186,7 @@ def _params(rng, stage, shape):
 
 def walk(seed):
     """-> (setup, steps): setup = {"max_frames", "timing"}, steps a list of actions, each a dict with a "kind" of KINDS_OF_ACTION.  20 to
-    30 steps of CHAIN_KINDS, at least 12 of them fills, and between them the meters' actions and refused fills of METER_KINDS (_splice).  The generator keeps book of what is present, so that a clear or a kept-state entry always
+    30 steps of CHAIN_KINDS, at least 12 of them fills, and between them the meters' actions and refused fills of METER_KINDS (_splice) and the actions of OUTPUT_KINDS (_splice_outputs).  The generator keeps book of what is present, so that a clear or a kept-state entry always
     meets an effect, the limiter's ceiling always has a master fill behind it to be taken from, and a handover happens once at most.
     The last step is a master fill, so that a walk ends with every return and the master fader arrived (Master.check_committed).
     The opening takes the inserts from the seed's low five bits and the stem stages from its low three, and DEFAULT_SEEDS is 32: the
@@ -246,7 +279,133 @@ def walk(seed):
         else:
             steps.append(dict(kind="handover"))
             handed = True
-    return setup, _splice(seed, setup, steps)
+    return setup, _splice_outputs(seed, setup, _splice(seed, setup, steps))
+
+
+def _multiband_shape(rng, B):
+    """B bands, each with a threshold below TWIN_PEAK as the bus dynamics draws it, a (ratio, knee) of test_gpu_multiband.RATIOS and
+    attack and release of test_gpu_dyn.COEFS"""
+    return dict(B=int(B), bands=[dict(below=float(_pick(rng, DYN_BELOW_PEAK_DB)), ratio=int(rng.randint(len(MB_RATIOS))), coefs=str(_pick(rng, sorted(COEFS))))
+                                 for _ in range(B)])
+
+
+def _splice_outputs(seed, setup, steps):
+    """the steps with the actions of OUTPUT_KINDS between them, drawn by a third generator (seed ^ OUTPUT_SALT): the steps of
+    CHAIN_KINDS and METER_KINDS stay the ones the seed gave before (tests/test_post_walk_host.py holds them to a digest).  Nothing
+    goes behind the last step.  As the meters: an absent stage is set soon, a present one mostly stays.  A multiband compressor set
+    while one is present takes another band count, and a resampler another (L, M, T), two times in three.  The detector is a property
+    of the walk: limiter_detector re-sets a present limiter with the other one, which resets its state, and for an absent limiter
+    records it for the next limiter_set — the generator reads the limiter's presence off the chain's steps."""
+    rng = np.random.RandomState(seed ^ OUTPUT_SALT)
+    mb = res = pcm = None
+    limiter, true_peak = False, False
+    loud = spec = until = None                                   # the meters' set actions, read off the steps; the step a pause of theirs ends behind
+    out = []
+
+    def other(seq, now):
+        if now is not None and rng.rand() < 2.0 / 3.0:
+            seq = [q for q in seq if q != now]
+        return _pick(rng, seq)
+
+    def pcm_shape():
+        return dict(kind="pcm_set", replaces=pcm is not None, bits=int(_pick(rng, PCM_BITS)), dither=str(_pick(rng, PCM_DITHERS)),
+                    K=int(other(PCM_TAPS, pcm and pcm["K"])), tap_seed=int(rng.randint(0, 50)), seed=int(rng.randint(0, 2 ** 31)))
+
+    def window(k):
+        """the next master fill from step k on that is not the walk's last step, if no action of the meters' lies in front of it"""
+        for j in range(k, len(steps) - 1):
+            if steps[j]["kind"] in METER_KINDS[:6]:
+                return None
+            if steps[j]["kind"] == "fill" and steps[j]["fill"] in ("master", "master_stems"):
+                return j
+        return None
+
+    for k, a in enumerate(steps):
+        u = rng.rand(6)
+        # The meters are on nearly all of a walk, and with one on neither the converter's kernel nor the PCM stage's ever copies the
+        # master out.  So now and then the meters that are on are cleared, a master fill runs without them, and the same meters are set
+        # again behind it, before the second generator's next action of theirs, whose books stay right: they start afresh there.  The
+        # pause runs the converter first behind the master section, or the PCM stage with no converter in front of it.
+        over = window(k) if until is None and (loud or spec) and u[5] < P_PAUSE else None
+        if over is not None:
+            until = over
+            out.append(dict(kind="meters_pause"))
+            if rng.rand() < 0.5:
+                if res is None:
+                    res = dict(kind="resampler_set", replaces=False, **dict(zip("LMT", map(int, _pick(rng, RESAMPLER_LMT)))))
+                    out.append(res)
+            else:
+                if res is not None:
+                    out.append(dict(kind="resampler_clear"))
+                    res = None
+                if pcm is None:
+                    pcm = pcm_shape()
+                    out.append(pcm)
+        if mb is None and u[0] < P_OUT_SET or mb is not None and u[0] < P_OUT_REPLACE:
+            mb = dict(_multiband_shape(rng, other((1, 2, 3, 4), mb and mb["B"])), kind="multiband_set", replaces=mb is not None)
+            out.append(mb)
+        elif mb is not None and u[0] < P_OUT_REPLACE + P_OUT_PARAMS:
+            mb = dict(_multiband_shape(rng, mb["B"]), kind="multiband_params")
+            out.append(mb)
+        elif mb is not None and u[0] < P_OUT_REPLACE + P_OUT_PARAMS + P_OUT_RESET:
+            out.append(dict(kind="multiband_reset"))
+        elif mb is not None and u[0] < P_OUT_REPLACE + P_OUT_PARAMS + P_OUT_RESET + P_OUT_CLEAR:
+            out.append(dict(kind="multiband_clear"))
+            mb = None
+        if u[1] < P_DETECTOR:
+            true_peak = not true_peak
+            out.append(dict(kind="limiter_detector", true_peak=true_peak, present=limiter))
+        if res is None and u[2] < P_OUT_SET or res is not None and u[2] < P_OUT_REPLACE:
+            L, M, T = other(RESAMPLER_LMT, res and (res["L"], res["M"], res["T"]))
+            res = dict(kind="resampler_set", replaces=res is not None, L=int(L), M=int(M), T=int(T))
+            out.append(res)
+        elif res is not None and u[2] < P_OUT_REPLACE + P_OUT_RESET:
+            out.append(dict(kind="resampler_reset"))
+        elif res is not None and u[2] < P_OUT_REPLACE + P_OUT_RESET + P_OUT_CLEAR:
+            out.append(dict(kind="resampler_clear"))
+            res = None
+        if pcm is None and u[3] < P_OUT_SET or pcm is not None and u[3] < P_OUT_REPLACE:
+            pcm = pcm_shape()
+            out.append(pcm)
+        elif pcm is not None and u[3] < P_OUT_REPLACE + P_OUT_RESET:
+            out.append(dict(kind="pcm_reset"))
+        elif pcm is not None and u[3] < P_OUT_REPLACE + P_OUT_RESET + P_OUT_CLEAR:
+            out.append(dict(kind="pcm_clear"))
+            pcm = None
+        if pcm is not None and u[4] < P_WRAP:
+            out.append(dict(kind="pcm_wrap", t=PCM_T_WRAP))
+        out.append(a)
+        if a["kind"] in ("limiter_set", "limiter_clear"):
+            limiter = a["kind"] == "limiter_set"
+        elif a["kind"] in ("loudness_set", "loudness_clear"):
+            loud = a if a["kind"] == "loudness_set" else None
+        elif a["kind"] in ("spectrum_set", "spectrum_clear"):
+            spec = a if a["kind"] == "spectrum_set" else None
+        if until == k:                                           # the meters again, in the shapes they had, behind the fill that ran without them
+            out.append(dict(kind="meters_resume", loudness=loud and dict(loud, replaces=False), spectrum=spec and dict(spec, replaces=False)))
+            until = None
+    return out
+
+
+def expanded(steps):
+    """(k, action) of a walk's steps with meters_pause and meters_resume written out as the clears and sets of METER_KINDS they stand
+    for, under the index of the step they came from: for the books of tests/test_post_walk_host.py"""
+    loud = spec = False
+    for k, a in enumerate(steps):
+        if a["kind"] == "meters_pause":
+            for name, there in (("loudness", loud), ("spectrum", spec)):
+                if there:
+                    yield k, dict(kind=name + "_clear")
+        elif a["kind"] == "meters_resume":
+            for name in ("loudness", "spectrum"):
+                if a[name]:
+                    yield k, a[name]
+        else:
+            yield k, a
+            if a["kind"] in ("loudness_set", "loudness_clear"):
+                loud = a["kind"] == "loudness_set"
+            elif a["kind"] in ("spectrum_set", "spectrum_clear"):
+                spec = a["kind"] == "spectrum_set"
 
 
 def _spectrum_hops(n_fft):
@@ -321,13 +480,25 @@ class _Fan:
 
 class Chain:
     """The chain on the host: per bus EqModel, DynModel, DriveModel, FlangerModel, ChorusModel, DelayModel, the reverb's Model, RoomModel;
-    behind them Master and Lim.  `handles`: who else every action is performed on — (a,) on the device, () on the host."""
+    behind them Master, the multiband compressor's Mb, the limiter's LimTp with either detector, the two meters, the converter's Res
+    and the PCM stage's Stage.  `handles`: who else every action is performed on — (a,) on the device, () on the host."""
 
     def __init__(self, handles=()):
         self.handles = tuple(handles)
         self.m = dict(eq=EqModel(), dyn=DynModel(), drive=DriveModel(), flanger=FlangerModel(), chorus=ChorusModel(), delay=DelayModel(), reverb=Model(), room=RoomModel())
         self.mm, self.lim = Master(), None
-        self.lims = []                                           # every Lim the walk has had
+        self.lims = []                                           # every LimTp the walk has had
+        self.true_peak = False                                   # the detector the next limiter_set takes (limiter_detector)
+        self.mb, self.res, self.pcm = None, None, None           # test_gpu_multiband.Mb, test_gpu_resampler.Res, test_gpu_pcm.Stage
+        self.pcm_flat = None                                     # beside a PCM stage with taps: the same stage with none, fed the same input
+        self.mbs, self.ress = [], []                             # every Mb and every Res the walk has had
+        self.res_serial = 0                                      # counts the converters that started afresh: sets and resets
+        # what tests/test_post_walk_host.py asks of the model alone, summed over a walk: [frames a PCM stage with taps differed from
+        # its twin without, frames it converted]; [samples of the programmes that were fed that did not clip, those samples]; the
+        # rails met; per resampler that ran, the programmes that sounded and those with a bit set in an output
+        self.shaped, self.unclipped, self.rails, self.resampled = [0, 0], [0, 0], set(), {}
+        # of the fills under the true-peak detector: [frames limited, frames whose d is not the sample magnitude on bits (LimTp.interpolated), frames]
+        self.true_peak_frames = [0, 0, 0]
         self.irs = {}                                            # the responses: no entry of the library reads one back
         self.peaks = []                                          # the peak of every master of 16 frames and more so far, before the limiter
         self.lim_meters = None                                   # of the last fill that ran the limiter on the handle in hand
@@ -342,7 +513,10 @@ class Chain:
 
     def present(self):
         return " ".join("%s:%s" % (st, ",".join(str(b) for b in sorted(self.of(st)))) for st in STAGES if self.of(st)) + \
-            (" limiter:%d,%d" % (self.lim.L, self.lim.H) if self.lim else "") + \
+            (" multiband:%d" % self.mb.B if self.mb else "") + \
+            (" limiter:%d,%d,%s" % (self.lim.L, self.lim.H, "true-peak" if self.lim.tp else "sample-peak") if self.lim else "") + \
+            (" resampler:%d/%d,%d" % (self.res.L, self.res.M, self.res.T) if self.res else "") + \
+            (" pcm:%d,%s,%d" % (self.pcm.bits, self.pcm.dither, self.pcm.taps.size) if self.pcm else "") + \
             (" loudness:%d,%d" % (self.loud.hop, self.loud.max_hops) if self.loud else "") + \
             (" spectrum:%d,%d,%d" % (self.spec.n, self.spec.hop, self.spec.max_rows) if self.spec else "")
 
@@ -428,8 +602,8 @@ class Chain:
                 fan.set_bus_reverb_mix(bus, s["dry"], s["wet"])
                 f.update(dry=s["dry"], wet=s["wet"])
         elif kind in ("limiter_set", "limiter_reset"):
-            if self.lim is None:
-                self.lim = Lim(action["lookahead"], action["hold"], self.ceiling())
+            if self.lim is None:                                 # (with the walk's detector: limiter_detector)
+                self.lim = LimTp(action["lookahead"], action["hold"], self.ceiling(), true_peak=self.true_peak)
                 self.lims.append(self.lim)
                 self.lim.set(self.handles)
             else:
@@ -473,6 +647,65 @@ class Chain:
         elif kind == "refused_fill":                             # the model does nothing: the call must leave everything as it was
             for syn in self.handles:
                 refused_fill(syn, action)
+        elif kind == "meters_pause":                             # the meters that are on, off: the next master fill runs without them
+            for name, meter in (("loudness", self.loud), ("spectrum", self.spec)):
+                if meter is not None:
+                    self.apply(dict(kind=name + "_clear"))
+        elif kind == "meters_resume":                            # ... and on again in the shapes they had: they start afresh
+            for name in ("loudness", "spectrum"):
+                if action[name]:
+                    self.apply(action[name])
+        elif kind == "limiter_detector":                         # a present limiter set again with the other detector: its state resets, in the model too
+            self.true_peak = action["true_peak"]
+            if self.lim is not None:
+                self.lim.set(self.handles, true_peak=self.true_peak)
+        elif kind in ("multiband_set", "multiband_params"):
+            curves = np.stack([s2.dynamics_curve(20.0 * np.log10(TWIN_PEAK) - q["below"], *MB_RATIOS[q["ratio"]], 0.0) for q in action["bands"]])
+            att, rel = [COEFS[q["coefs"]]()[0] for q in action["bands"]], [COEFS[q["coefs"]]()[1] for q in action["bands"]]
+            if kind == "multiband_set":                          # (while one is present too: it starts afresh)
+                self.mb = Mb(action["B"], curves, att, rel)
+                self.mbs.append(self.mb)
+            else:                                                # the band count and the crossover stay, and with them the state
+                assert action["B"] == self.mb.B
+                self.mb.curves, self.mb.att, self.mb.rel = np.array(curves, dtype=F), att, rel
+            for syn in self.handles:
+                self.mb.set(syn, params=kind == "multiband_params")
+        elif kind == "multiband_reset":
+            fan.reset_master_multiband()
+            self.mb.reset()
+        elif kind == "multiband_clear":
+            fan.clear_master_multiband()
+            self.mb = None
+        elif kind == "resampler_set":
+            L, M, T = action["L"], action["M"], action["T"]
+            self.res = Res(L, M, np.array([[1.0, 0.0, 0.0, 0.0]], dtype=F) if (L, M, T) == (1, 1, 4) else s2.resampler_design(L, M, T))
+            self.res.set(*self.handles)
+            self.ress.append(self.res)
+            self.res_serial += 1
+        elif kind == "resampler_reset":
+            fan.reset_master_resampler()
+            self.res.reset()
+            self.res_serial += 1
+        elif kind == "resampler_clear":
+            fan.clear_master_resampler()
+            self.res = None
+        elif kind == "pcm_set":
+            taps = _taps(action["K"], action["tap_seed"])
+            self.pcm = Stage(action["bits"], action["dither"], taps, action["seed"])
+            self.pcm.set(*self.handles)
+            self.pcm_flat = Stage(action["bits"], action["dither"], (), action["seed"]) if action["K"] else None
+        elif kind == "pcm_reset":
+            fan.reset_master_pcm()
+            for stage in (self.pcm, self.pcm_flat):
+                if stage is not None:
+                    stage.reset()
+        elif kind == "pcm_clear":
+            fan.clear_master_pcm()
+            self.pcm = self.pcm_flat = None
+        elif kind == "pcm_wrap":                                 # the present state again, with t just below 2^32: samples, counts and held clips stay
+            self.pcm.load(fan, self.pcm.state.copy(), action["t"])
+            if self.pcm_flat is not None:
+                self.pcm_flat.t = action["t"]
         else:
             raise ValueError(kind)
 
@@ -578,18 +811,29 @@ class Chain:
             out.update(self.meter_readings())                    # a bus fill and a panned fill move no meter
             return out
         m = self.mm.expect(y)
-        if n >= 16 and float(np.abs(m).max()) > TWIN_PEAK / 64.0:
-            self.peaks.append(float(np.abs(m).max()))
-        want = m
-        if self.lim is not None and 2.0 ** -19 < float(np.abs(m).max()) <= self.lim.c:
+        # the multiband compressor between the master fader and the limiter: what it returns is the limiter's input, so the peaks'
+        # bookkeeping and the ceiling read that; the master section's meters stay over m
+        mi = m if self.mb is None else self.mb.expect(m)
+        if n >= 16 and float(np.abs(mi).max()) > TWIN_PEAK / 64.0:
+            self.peaks.append(float(np.abs(mi).max()))
+        want = mi
+        if self.lim is not None and 2.0 ** -19 < float(np.abs(mi).max()) <= self.lim.c:
             # the ceiling the way the per-stage walks choose it — half the peak of a master the model has computed, this one —, so that
             # every limited fill that sounds is limited: a new ceiling alone keeps the limiter's state
-            self.lim.set(self.handles, ceiling=float(np.abs(m).max()) / 2.0)
+            self.lim.set(self.handles, ceiling=float(np.abs(mi).max()) / 2.0)
         if self.lim is not None:
-            want, sp = self.lim.expect(m)
+            want, sp = self.lim.expect(mi)
             self.lim_meters = np.array([sp.min(), np.abs(want).max()], dtype=F)
             out["gain"] = sp
+            # the true-peak detector looks at frame n - 8: a call whose magnitudes, those of the carried frames included, stay under
+            # the ceiling cannot be limited, however loud its last frames are
+            out["idle"] = bool(self.lim.tp and not (self.lim.d[-1] > F(self.lim.c)).any())
+            if self.lim.tp:
+                self.true_peak_frames[0] += int((sp < 1.0).sum())
+                self.true_peak_frames[1] += int((ubits(self.lim.d[-1]) != ubits(self.lim.mag[-1])).sum())
+                self.true_peak_frames[2] += n
         out["master"] = want
+        out["limiter in"] = float(np.abs(mi).max())
         if action["fill"] == "master_stems":
             out["stems"] = y
         out["peaks"], out["energies"] = np_meters(y, m)          # (the master's entry is over the limiter's input)
@@ -609,6 +853,38 @@ class Chain:
                 sounding = {p if p < nb else s2.MAX_BUSES for p, q in enumerate(heard) if q.size and float(np.abs(q).max()) > 2.0 ** -10}
                 positive = {p for p in range(s2.MAX_BUSES + 1) if len(new) and (new.reshape(len(new), s2.MAX_BUSES + 1, -1)[:, p] > 0.0).any()}
                 out["meters"].append(dict(name=name, instance=(self.meter_serial, id(meter)), made=made, sounding=sounding, positive=positive))
+        # the converter over the same nine programmes, and the PCM stage over its outputs as eight buses and the master — over the stems
+        # and the master themselves without it.  A call of which the converter makes no frame runs no PCM kernel: state, t and the
+        # held clips stay, s2r_get_pcm answers 0 frames and the last call's clips are 0 (test_gpu_resampler._rfill)
+        fed = list(range(nb)) + [s2.MAX_BUSES]
+        stems, master = y, want
+        if self.res is not None:
+            ph = self.res.ph
+            self.res.expect(y, want)
+            stems, master = self.res.out[:s2.MAX_BUSES], self.res.out[s2.MAX_BUSES]
+            book = self.resampled.setdefault(self.res_serial, [set(), set()])
+            if master.shape[0]:
+                # a programme has sounded where the outputs could hear it: up to the newest frame the call's last output reads (sweep
+                # seed 500378: a bus behind a delay with no dry path that sounds only behind the one output of a short call)
+                newest = (ph + (master.shape[0] - 1) * self.res.M) // self.res.L
+                book[0] |= {p for p, q in zip(fed, list(y) + [want]) if float(np.abs(q[:newest + 1]).max()) > 2.0 ** -10}
+                book[1] |= {p for p in range(s2.MAX_BUSES + 1) if ubits(self.res.out[p]).any()}
+        out["count"] = master.shape[0]
+        if self.pcm is not None and master.shape[0]:
+            for stage in (self.pcm, self.pcm_flat):
+                if stage is not None:
+                    stage.expect(stems, master)
+            G = 1 << (self.pcm.bits - 1)
+            self.unclipped[0] += 2 * len(fed) * master.shape[0] - int(self.pcm.last.reshape(-1, 2)[fed].sum())
+            self.unclipped[1] += 2 * len(fed) * master.shape[0]
+            self.rails |= {name for name, rail in (("low", -G), ("high", G - 1)) if (self.pcm.pcm == rail).any()}
+            if self.pcm_flat is not None:
+                self.shaped[0] += int((self.pcm.pcm != self.pcm_flat.pcm).any(axis=(0, 2)).sum())
+                self.shaped[1] += master.shape[0]
+        elif self.pcm is not None:
+            for stage in (self.pcm, self.pcm_flat):
+                if stage is not None:
+                    stage.pcm, stage.last = np.zeros((s2.MAX_BUSES + 1, 0, 2), dtype=np.int32), np.zeros(2 * (s2.MAX_BUSES + 1), dtype=np.uint32)
         out.update(self.meter_readings())
         return out
 
@@ -621,6 +897,16 @@ class Chain:
                         "true peak held": self.loud.held.copy()})
         if self.spec is not None:
             out.update({"spectrum count": len(self.spec.rows), "spectrum rows": self.spec.rows.copy()})
+        # the stages of DESIGN.md 4.28 to 4.31: the multiband's minima, the converter's outputs of all nine programmes and the PCM
+        # stage's integers of the last master fill that ran each — S2R_ERR_INVALID where none has since the set or reset, or on this
+        # handle —, and the clips of that fill and the held ones
+        invalid = s2s.S2R_ERR_INVALID
+        if self.mb is not None:
+            out["multiband meters"] = invalid if self.mb.mn is None else np.array(self.mb.mn, dtype=F)
+        if self.res is not None:
+            out["resampled"] = invalid if self.res.out is None else self.res.out.copy()
+        if self.pcm is not None:
+            out.update({"pcm": invalid if self.pcm.pcm is None else self.pcm.pcm.copy(), "pcm clips": self.pcm.last.copy(), "pcm clips held": self.pcm.held.copy()})
         return out
 
     def meter_states(self):
@@ -631,6 +917,16 @@ class Chain:
         for name, meter in (("loudness", self.loud), ("spectrum", self.spec)):
             if meter is not None:
                 out[name + " state"], out[name + " position"] = np.array(meter.state, dtype=F), np.array([meter.pos], dtype=F)
+        # the four mirrors of DESIGN.md 4.28 to 4.31, read at the same places: the multiband's state, the converter's histories and ph,
+        # the PCM stage's errors and t, and the limiter's xh and gh at its detector's sizes
+        if self.mb is not None:
+            out["multiband state"] = np.array(self.mb.state, dtype=F)
+        if self.lim is not None:
+            out["limiter xh"], out["limiter gh"] = self.lim.xh, self.lim.gh
+        if self.res is not None:
+            out["resampler state"], out["resampler ph"] = np.array(self.res.state, dtype=F), np.array([self.res.ph], dtype=F)
+        if self.pcm is not None:
+            out["pcm state"], out["pcm t"] = np.array(self.pcm.state, dtype=F), _halves(self.pcm.t)
         return out
 
     def handed_over(self):
@@ -641,6 +937,16 @@ class Chain:
         self.lim_meters = None
         if self.loud is not None:
             self.loud.held, self.loud.last = np.zeros(2, dtype=F), np.zeros(2, dtype=F)
+        # s2r.h: the checkpoints of the multiband compressor, the converter and the PCM stage are the state (with ph, with t) and
+        # nothing else; s2r_get_multiband_meters, s2r_get_resampled and s2r_get_pcm answer S2R_ERR_INVALID before a master fill of the
+        # handle has run the stage, and the clips are counted since the set: the new handle's are 0, last and held
+        if self.mb is not None:
+            self.mb.mn = None
+        if self.res is not None:
+            self.res.out = None
+        for stage in (self.pcm, self.pcm_flat):
+            if stage is not None:
+                stage.pcm, stage.last, stage.held = None, np.zeros_like(stage.last), np.zeros_like(stage.held)
 
     def states(self):
         """name -> the state every present effect and the limiter carry, as the getters of a handle give them (states_of)"""
@@ -651,9 +957,7 @@ class Chain:
                     out["%s %d history" % (st, b)], out["%s %d phase" % (st, b)] = f["hist"], _halves(f["phase"])
                 else:
                     out["%s %d" % (st, b)] = np.array(f[dict(eq="st", dyn="y", drive="hist", delay="hist", reverb="hist", room="st")[st]], dtype=F)
-        if self.lim is not None:
-            out["limiter xh"], out["limiter gh"] = self.lim.xh, self.lim.gh
-        out.update(self.meter_states())
+        out.update(self.meter_states())                          # (the limiter's xh and gh among them)
         return out
 
 
@@ -683,9 +987,7 @@ def states_of(chain, syn):
                 out["%s %d history" % (st, b)], out["%s %d phase" % (st, b)] = got[0], _halves(got[1])
             else:
                 out["%s %d" % (st, b)] = np.array(got, dtype=F)
-    if chain.lim is not None:
-        out["limiter xh"], out["limiter gh"] = syn.limiter_state()
-    out.update(meter_states_of(chain, syn))
+    out.update(meter_states_of(chain, syn))                      # (the limiter's xh and gh among them)
     return out
 
 
@@ -696,7 +998,26 @@ def meter_states_of(chain, syn):
         if meter is not None:
             state, pos = getattr(syn, get)()
             out[name + " state"], out[name + " position"] = np.array(state, dtype=F), np.array([pos], dtype=F)
+    if chain.mb is not None:
+        out["multiband state"] = syn.multiband_state()
+    if chain.lim is not None:
+        out["limiter xh"], out["limiter gh"] = syn.limiter_state()
+    if chain.res is not None:
+        state, ph = syn.resampler_state()
+        out["resampler state"], out["resampler ph"] = state, np.array([ph], dtype=F)
+    if chain.pcm is not None:
+        state, t = syn.pcm_state()
+        out["pcm state"], out["pcm t"] = state, _halves(t)
     return out
+
+
+def _programmes(get):
+    """all nine programmes of the last master fill through Synth.resampled or Synth.pcm, [9, frames, 2], or the status where the
+    entry refuses"""
+    try:
+        return np.stack([get(p) for p in range(s2.MAX_BUSES + 1)])
+    except s2.S2rError as err:
+        return err.status
 
 
 def meter_readings_of(chain, syn):
@@ -707,6 +1028,16 @@ def meter_readings_of(chain, syn):
         out["true peak"], out["true peak held"] = syn.true_peak()
     if chain.spec is not None:
         out["spectrum count"], out["spectrum rows"] = int(syn.get_master_spectrum()[3]), syn.spectrum_rows()
+    if chain.mb is not None:
+        try:
+            out["multiband meters"] = syn.multiband_meters()
+        except s2.S2rError as err:
+            out["multiband meters"] = err.status
+    if chain.res is not None:
+        out["resampled"] = _programmes(syn.resampled)
+    if chain.pcm is not None:                                    # (the samples stay held when the converter in front is cleared or replaced: Synth.pcm)
+        out["pcm"] = _programmes(syn.pcm)
+        out["pcm clips"], out["pcm clips held"] = syn.pcm_clips()
     return out
 
 
@@ -739,6 +1070,12 @@ def roundtrip(chain, syn):
     if chain.spec is not None:
         syn.set_spectrum_state(*syn.spectrum_state())
         syn.set_spectrum_rows(syn.spectrum_rows())
+    if chain.mb is not None:
+        syn.set_multiband_state(syn.multiband_state())
+    if chain.res is not None:
+        syn.set_resampler_state(*syn.resampler_state())
+    if chain.pcm is not None:                                    # (a state setter keeps the last samples and the clips: s2r.h)
+        syn.set_pcm_state(*syn.pcm_state())
 
 
 def copy_voices(src, dst):
@@ -779,10 +1116,25 @@ def handover(chain, src, dst):
     for b in range(s2.MAX_BUSES):
         dst.set_bus_return(b, src.get_bus_return(b)[0])
     dst.set_master_fader(src.get_master_fader()[0])
+    mb = src.get_master_multiband()
+    assert (mb is not None) == (chain.mb is not None)
+    if mb is not None:                                           # every stage below: the parameters as src's getters give them, then the state
+        dst.set_master_multiband(mb["curves"], mb["attack"], mb["release"], coeffs=(mb["lp"], mb["hp"], mb["ap"]) if mb["n_bands"] > 1 else None)
+        dst.set_multiband_state(src.multiband_state())
     ceiling, look, hold = src.get_master_limiter()
     if look:
-        dst.set_master_limiter(ceiling, look, hold)
+        dst.set_master_limiter(ceiling, look, hold, true_peak=src.get_master_limiter_detector() == s2.LIMITER_TRUE_PEAK)
         dst.set_limiter_state(*src.limiter_state())
+    L, M, table = src.get_master_resampler()
+    assert bool(L) == (chain.res is not None)
+    if L:
+        dst.set_master_resampler(L, M, table)
+        dst.set_resampler_state(*src.resampler_state())
+    bits, dither, taps, seed = src.get_master_pcm()
+    assert bool(bits) == (chain.pcm is not None)
+    if bits:
+        dst.set_master_pcm(bits, dither, taps, seed)
+        dst.set_pcm_state(*src.pcm_state())
     if chain.loud is not None:                                   # parameters as src's getter gives them, then state, position and rows
         c, hop, max_hops, _ = src.get_master_loudness()
         dst.set_master_loudness(SR, hop, max_hops, c)
@@ -831,3 +1183,56 @@ def subset_walk():
         steps.append(dict(kind="fill", fill="master", n_buses=3, frames=33, tune=False))
         steps.append(dict(kind="limiter_clear"))
     return dict(max_frames=1024, timing=False), steps
+
+
+MASTER_STAGES = ("loudness", "spectrum", "resampler", "pcm")     # the four kernels behind the limiter, in launch order
+MASTER_SUBSET_FRAMES = (127, 128, 129, 1, 9, 257, 64, 300)       # the edges of the 128-frame tiles of the PCM and multiband kernels, which FRAMES lacks
+MASTER_SUBSET_FADERS = (1.0, 0.125)                              # three buses at TWIN_PEAK: 0.125 keeps their sum inside full scale
+
+
+def master_subset_walk():
+    """the systematic complement of the third generator: the 16 subsets of {loudness, spectrum, resampler, PCM} in Gray-code order on
+    one pair of handles — each step sets or clears exactly one of the four while the others are in mid-state —, three buses,
+    max_frames 300, an EQ on bus 0 and a room on bus 1 throughout, so that the stems are not the dry buses.  Each subset gets three
+    master fills: the limiter off, with the sample-peak detector, with the true-peak detector (limiter_detector on the present limiter).
+    Fill f of the 48 takes MASTER_SUBSET_FRAMES[f % 8] frames, asks for stems when f / 2 is even, runs a three-band multiband
+    compressor when f % 4 is 1 or 2 (set and cleared as that asks).  The master fader alternates, snapped, between 1 and 0.125 from
+    subset to subset, not from fill to fill: the converter's histories carry the last 47 frames of the fill before into a fill's
+    first outputs, and a subset's last fill is under the limiter, so a subset at 0.125 hears nothing louder than the ceiling from the
+    subset in front of it and clips nothing on the master programme, while a subset at 1 clips there with the limiter off.  The
+    resampler is (147, 160, 48), the PCM stage 16 bits with triangular dither and nine taps.  Behind every fourth subset the states
+    go through a round trip, which is where a walk of master fills alone has them compared."""
+    steps = [dict(kind="set", stage="eq", bus=0, replaces=False, shape=dict(bands=2, seed=1)),
+             dict(kind="set", stage="room", bus=1, replaces=False, shape=dict(delays="small", levels="hall")),
+             # the room rings at many times its input's level: its return brings it back to the level of a dry bus, so that the master
+             # fader's low setting does what it is there for (the stems, in front of the returns, are as loud as they come)
+             dict(kind="return", bus=0, level=0.5), dict(kind="return", bus=1, level=1.0 / 32.0)]
+    sets = dict(loudness=dict(kind="loudness_set", replaces=False, hop=17, max_hops=32),
+                spectrum=dict(kind="spectrum_set", replaces=False, n_fft=256, hop=32, window="hann", max_rows=8),
+                resampler=dict(kind="resampler_set", replaces=False, L=147, M=160, T=48),
+                pcm=dict(kind="pcm_set", replaces=False, bits=16, dither="tpdf", K=9, tap_seed=0, seed=77))
+    band = dict(below=24.0, ratio=0, coefs="1ms-100ms")           # (24 dB below TWIN_PEAK: the bands work at the fader's low setting too)
+    on, mb, f = 0, False, 0
+    for i in range(1 << len(MASTER_STAGES)):
+        gray = i ^ (i >> 1)
+        for j, st in enumerate(MASTER_STAGES):
+            if (gray ^ on) >> j & 1:
+                steps.append(dict(sets[st]) if gray >> j & 1 else dict(kind=st + "_clear"))
+        on = gray
+        steps.append(dict(kind="fader", level=MASTER_SUBSET_FADERS[i % 2]))
+        steps.append(dict(kind="snap"))
+        for mode in ("off", "sample", "true"):
+            if mode != "off":
+                steps.append(dict(kind="limiter_detector", true_peak=mode == "true", present=mode == "true"))
+            if mode == "sample":
+                steps.append(dict(kind="limiter_set", lookahead=48, hold=20))
+            if (f % 4 in (1, 2)) != mb:
+                mb = not mb
+                steps.append(dict(kind="multiband_set", replaces=False, B=3, bands=[dict(band), dict(band, ratio=1, below=14.0), dict(band, ratio=2, coefs="zero")])
+                             if mb else dict(kind="multiband_clear"))
+            steps.append(dict(kind="fill", fill="master_stems" if (f // 2) % 2 == 0 else "master", n_buses=3, frames=MASTER_SUBSET_FRAMES[f % 8], tune=False))
+            f += 1
+        steps.append(dict(kind="limiter_clear"))
+        if i % 4 == 3:
+            steps.append(dict(kind="roundtrip"))
+    return dict(max_frames=300, timing=False), steps

@@ -1,4 +1,4 @@
-"""Differential fuzzing of the post-mix chain (DESIGN.md 4.16 to 4.25) against the composed host models: the seeded walks of
+"""Differential fuzzing of the post-mix chain (DESIGN.md 4.16 to 4.31) against the composed host models: the seeded walks of
 tests/post_walk.py, played on twin handles.  Handle `a` makes the walk's calls; its twin `b` is fed the same events and makes a plain bus
 fill of the same frames and buses every time (a panned one for a panned fill), so its output is the dry signal; the expectation is
 post_walk.Chain over it — per bus the EQ's, the dynamics', the drive's, the flanger's, the chorus's, the delay's, the reverb's and the
@@ -14,9 +14,19 @@ compared behind every fill, a bus fill and a panned fill having to leave them al
 trip and the handover, in the middle of a hop, and state and position are compared there, behind every other bus fill and panned
 fill and at the end of the walk — not between two master fills in a row, so that the state's device copies flip unread as well as being
 fetched and uploaded again (S2rMirror).  A master fill of max_frames + 1 frames must be refused and move nothing.
+The stages of DESIGN.md 4.28 to 4.31 are in the walks too, by a third generator that leaves the steps of the first two what they
+were: the multiband compressor between the master fader and the limiter (test_gpu_multiband.Mb; set at 1 to 4 bands, given new
+parameters that keep its state, reset, cleared), the limiter under either detector (test_gpu_limiter_tp.LimTp; limiter_detector
+switches a present limiter, which resets its state), the converter over nine (L, M, T) (test_gpu_resampler.Res) and the PCM stage
+behind it or without it (test_gpu_pcm.Stage; 8, 16 and 24 bits, the three dithers, 0 to 9 taps, t reloaded just below 2^32).  The
+multiband's minima, the converter's outputs of all nine programmes and the PCM stage's integers, compared as integers in value,
+type and shape, with the clips of the call and the held ones, are read behind every fill, a refused one included; the four states
+— the limiter's xh and gh at its detector's sizes, ph and t beside theirs — where the meters' are.  With a meter on, the converter
+and the PCM stage never copy the master to the pinned output, so a walk now and then pauses its meters over one master fill
+(meters_pause, meters_resume).  The master subset walk goes through the 16 subsets of the four kernels behind the limiter.
 tests/test_post_walk_host.py asserts on the CPU that the default seeds cover all of that, and that a flanger runs in
 calls of more than 1024 frames, at H = 4096, in calls of 255, 256 and 257 frames, and idles between two fills that run it, and
-what the meters meet: its conditions 8 to 16.
+what the meters meet: its conditions 8 to 16; and what the four newer stages meet: its conditions 17 to 23.
 
 Deterministic: the seeds are fixed and a failure names its seed, step and action and the effects present at that step;
 S2R_POST_FUZZ_BASE=<that seed> S2R_POST_FUZZ_SEEDS=1 runs it again.  Every comparison is on bits with no NaN allowance
@@ -35,7 +45,28 @@ chain in front of them.  What the first run found was in the walk's model: seeds
 directly behind the handover: the fresh handle has made no master fill, so the true peak of its last call reads +0.0, not the old
 handle's: post_walk.Chain.handed_over).  Tried once against a library with two defects put in — the walkers' block test turned from >
 to >=, and one wrong twiddle in the four-layer pass at s0 = 8 that N = 4096 alone runs —, 31 of the default seeds and the subset
-walk failed."""
+walk failed.
+With the multiband compressor, the true-peak detector, the converter and the PCM stage in the walks, 400 walks at base 500000 beside
+the default 32 and the two systematic walks have run equal on bits on an MI355X, and the model alone was well behaved over the same
+400: no seed has found a fault in the four kernels, in who copies the master out, in their mirrors or in their counters.  The walks
+did find a fault in the library's Python binding: Synth.pcm sized its buffer by the converter that is set now, and s2r_get_pcm
+refuses a buffer shorter than the samples it holds — so the samples of a fill behind a converter of a ratio above 1, more than
+max_frames of them, could not be read once that converter had been cleared or replaced by one of a smaller ratio, though s2r.h
+keeps them until the next master fill.  Seeds 500030 (step 33, a panned fill) and 500211 (steps 19 and 63, a bus fill and a panned
+fill) read them there, as do others of that sweep and no default seed; Synth.pcm now sizes its buffer by the largest ratio, 4,
+the two seeds, which both fail against the getter as it was and pass with the 400 since, stay as
+test_the_seeds_that_found_a_fault (post_walk.REGRESSION_SEEDS) and tests/test_gpu_resampler.py holds the
+getter to it directly.  What else the first runs found was in the walk and its model, on the host: no master fill of the default seeds ran with both meters off, so the
+converter and the PCM stage never copied the master out (hence meters_pause); the master subset walk's fader, alternating from fill
+to fill, let the converter's histories carry a loud fill into a quiet one, which then clipped (it alternates from subset to subset);
+and seed 500378 (a bus behind a delay with no dry path that sounds only behind the one output of a short call: the converter
+rightly makes +0.0 of it, Chain.expect counts a programme as sounding only up to the newest frame an output reads).  Tried once
+against three libraries with one defect each in S2rPostChain: the PCM launch behind the resampler given the call's frames for its
+count (clamped to the count, so that the defective launch stays inside its buffers: wrong behind a ratio above 1) — 22 of the 32
+default seeds fail, neither systematic walk, whose resampler is 147 / 160; t moved by a refused fill — 13 of the default seeds,
+neither systematic walk, which make no refused fill; the resampler's kernel copying the master out whenever the loudness meter
+alone is off — nothing fails, and nothing can: the spectrum kernel then copies the same frames of the same buffer to the same place,
+so the defect is a second, equal write and not a wrong output."""
 import os
 
 import numpy as np
@@ -73,6 +104,8 @@ def play(setup, steps, name):
             a, b = c, d
         elif action["kind"] != "fill":
             chain.apply(action)
+            if action["kind"] == "refused_fill":                 # it moves no reading: rows, outputs, integers and clips as the last master fill left them
+                got.append((what, pw.meter_readings_of(chain, a), chain.meter_readings(), None))
         else:
             _events((a, b), V, fill)
             fill += 1
@@ -112,7 +145,7 @@ def play(setup, steps, name):
         assert x is None or np.isfinite(x).all(), what + ": the twin's output is not finite"
         assert x is None or ubits(x).any() or x.shape[-2] == 1, what + ": the twin is silent"      # (a voice's first frame is +0.0)
     for what, dev, want, x in got:                               # (Chain.expect lowers the ceiling where a master would stay under it)
-        assert "gain" not in want or (want["gain"] < 1.0).any() or float(want["peaks"][-1].max()) <= 2.0 ** -19, what + ": the limiter does not work"
+        assert "gain" not in want or (want["gain"] < 1.0).any() or want["idle"] or want["limiter in"] <= 2.0 ** -19, what + ": the limiter does not work"
     for what, dev, want, x in got:
         for key, g in dev.items():
             w = want[key]
@@ -120,7 +153,11 @@ def play(setup, steps, name):
                 for bus in w:
                     assert_bits_equal_finite(g[bus], w[bus], "%s: the meter of the dynamics on bus %d" % (what, bus))
             elif isinstance(w, int) or isinstance(g, int):
-                assert isinstance(g, int) and g == w, "%s: %s: %r, not %r" % (what, key, g, w)
+                assert isinstance(g, int) and isinstance(w, int) and g == w, "%s: %s: %r, not %r" % (what, key, g, w)
+            elif np.issubdtype(w.dtype, np.integer):             # the PCM stage's integers and its clip counts: value, type and shape
+                assert g.dtype == w.dtype and g.shape == w.shape, "%s: %s: %s %s, not %s %s" % (what, key, g.dtype, g.shape, w.dtype, w.shape)
+                assert np.array_equal(g, w), "%s: %s: %d of %d integers differ, the first at %s" % (
+                    what, key, int((g != w).sum()), w.size, tuple(int(i[0]) for i in np.nonzero(g != w)))
             else:
                 assert_bits_equal_finite(g, w, "%s: %s" % (what, key))
     model = chain.states()
@@ -133,6 +170,15 @@ def play(setup, steps, name):
 
 @pytest.mark.parametrize("seed", SEEDS)
 def test_post_fuzz(seed):
+    setup, steps = pw.walk(seed)
+    play(setup, steps, "seed %d (max_frames %d, timing %s)" % (seed, setup["max_frames"], "on" if setup["timing"] else "off"))
+
+
+@pytest.mark.parametrize("seed", pw.REGRESSION_SEEDS)
+def test_the_seeds_that_found_a_fault(seed):
+    """post_walk.REGRESSION_SEEDS, beside the sweep wherever it has been moved.  500030 and 500211: Synth.pcm on samples of more than
+    max_frames frames whose converter has been cleared or replaced by one of a smaller ratio since the fill (the history paragraph
+    above; tests/test_post_walk_host.py holds the walks to that on the books)"""
     setup, steps = pw.walk(seed)
     play(setup, steps, "seed %d (max_frames %d, timing %s)" % (seed, setup["max_frames"], "on" if setup["timing"] else "off"))
 
@@ -154,3 +200,25 @@ def test_every_insert_subset_on_every_kind_of_call():
     # frames and 16 spectrum rows
     assert all({"loudness rows", "true peak", "true peak held", "spectrum rows"} <= set(dev) for _, dev, _, _ in got)
     assert chain.loud.made == 64 * 33 // 17 and chain.spec.made == 64 * 33 // 128 and len(chain.loud.rows) == 32 and len(chain.spec.rows) == 8
+
+
+def test_every_subset_of_the_stages_behind_the_limiter():
+    """The systematic complement of the third generator (post_walk.master_subset_walk): one pair of handles, three buses, max_frames
+    300, an EQ and a room on throughout — the 16 subsets of {loudness, spectrum, resampler, PCM} in Gray-code order, so that each step
+    sets or clears exactly one of them while the others are in mid-state, and with it who copies the master to the pinned output.
+    Each subset gets three master fills, the limiter off, with the sample-peak detector and with the true-peak detector, alternately
+    with and without stems and with and without a three-band multiband compressor, in calls of 127, 128, 129, 1, 9, 257, 64 and 300
+    frames — the edges of the 128-frame tiles of the PCM and multiband kernels.  The resampler is (147, 160, 48), the PCM stage 16
+    bits with triangular dither and nine taps; the master fader alternates, snapped, between 1 and 0.125.  Outputs, integers, clips
+    and the multiband's minima are compared behind every fill, the states at every fourth subset's round trip and at the end."""
+    setup, steps = pw.master_subset_walk()
+    chain, got = play(setup, steps, "the master subset walk")
+    fills = [(dev, want) for _, dev, want, x in got if x is not None]
+    assert len(fills) == 48 and all("master" in dev for dev, _ in fills)
+    # each of the four stages is on in 24 of the fills, and each reading is compared there
+    for key in ("loudness rows", "spectrum rows", "resampled", "pcm"):
+        assert sum(key in dev for dev, _ in fills) == 24, key
+    assert sum("multiband meters" in dev for dev, _ in fills) == 24 and sum("gain" in want for _, want in fills) == 32
+    # the PCM stage behind the resampler makes the resampler's count of frames, a call of one frame included
+    both = [(dev, want) for dev, want in fills if "resampled" in dev and "pcm" in dev]
+    assert len(both) == 12 and all(dev["pcm"].shape == (9, want["count"], 2) == dev["resampled"].shape for dev, want in both)

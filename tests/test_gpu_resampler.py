@@ -264,6 +264,28 @@ def test_the_pcm_stage_behind_it(K, L, M, T):
     m.check(a, "the PCM stage alone again", state=True)
 
 
+@pytest.mark.parametrize("then", ["clear", "a smaller ratio"])
+def test_the_pcm_samples_stay_readable_when_their_converter_goes(then):
+    """a fill of max_frames behind 4/1 leaves the PCM stage four times max_frames samples; the converter is then cleared, or replaced
+    by 1/2, and until the next master fill pcm() still returns those samples, of every programme (s2r.h: they are held; Synth.pcm
+    once sized its buffer by the converter that is set now and was refused — found by the post-mix walks, seeds 500030 and 500211)"""
+    (a, b), _ = _quiet(64)
+    r = Res(4, 1, s2.resampler_design(4, 1, 8))
+    m = Stage(16, "tpdf", _taps(5), seed=3)
+    r.set(a)
+    m.set(a)
+    _events((a, b), V, 0)
+    _rfill(a, b, r, 64, 3, "in front of the %s" % then, pcm=m)
+    assert m.pcm.shape == (P, 256, 2)
+    if then == "clear":
+        a.clear_master_resampler()
+    else:
+        a.set_master_resampler(1, 2, s2.resampler_design(1, 2, 8))
+    m.check(a, "behind the %s" % then, state=True)
+    assert_bits_equal_finite(a.sample_buses(64, SR, 3), b.sample_buses(64, SR, 3), "a bus fill behind the %s" % then)
+    m.check(a, "behind the %s and a bus fill" % then)
+
+
 def test_bus_count_stages_events_and_slices(monkeypatch):
     """a bus count that changes between calls (a bus that drops out is fed +0.0 and its history rings out), a reverb, an EQ and a delay
     in front of the stage on both handles, timed events inside the fills, a rows buffer of 48 frames so that the stems arrive in slices"""
