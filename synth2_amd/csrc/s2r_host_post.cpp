@@ -893,7 +893,7 @@ int s2r_get_pcm(const s2r_synth *s, uint32_t programme, int32_t *pcm_lr, size_t 
     if (!s || !s->kids.empty() || s->parent || !s->post.pcm.bits || !s->post.pcm.have || !pcm_lr) return S2R_ERR_INVALID;
     const S2rPostChain::Pcm &pm = s->post.pcm;
     if (capacity < 2u * (size_t)pm.frames) return S2R_ERR_INVALID;
-    if (pm.frames) std::memcpy(pcm_lr, pm.samples + (size_t)programme * 2u * pm.cap, 2u * (size_t)pm.frames * sizeof(int32_t));
+    if (pm.frames) std::memcpy(pcm_lr, pm.samples.host + (size_t)programme * 2u * pm.cap(), 2u * (size_t)pm.frames * sizeof(int32_t));
     put(frames, (size_t)pm.frames);
     return S2R_OK;
 }
@@ -969,7 +969,7 @@ int s2r_get_resampled(const s2r_synth *s, uint32_t programme, float *out_lr, siz
     if (!s || !s->kids.empty() || s->parent || !s->post.res.L || !s->post.res.have || !out_lr) return S2R_ERR_INVALID;
     const S2rPostChain::Resampler &rs = s->post.res;
     if (capacity < 2u * (size_t)rs.count) return S2R_ERR_INVALID;
-    if (rs.count) std::memcpy(out_lr, rs.res + (size_t)programme * 2u * rs.cap, 2u * (size_t)rs.count * sizeof(float));
+    if (rs.count) std::memcpy(out_lr, rs.res.host + (size_t)programme * 2u * rs.cap(), 2u * (size_t)rs.count * sizeof(float));
     put(frames, (size_t)rs.count);
     return S2R_OK;
 }
@@ -1000,6 +1000,7 @@ int s2r_set_resampler_state(s2r_synth *s, const float *state, size_t count, uint
 // ---- measurement (tools/*_time.py load these by name; not declared in s2r.h) ----
 // device time of one stage's kernels in the last bus or master fill, in milliseconds (s2r_set_timing on; < 0 otherwise)
 #define POST_MS(timer) (s && s->timing ? s->post.timer.ms : -1.0f)
+#define MASTER_MS(k) POST_MS(master_timer[k])
 // of the buses' EQ kernel in that fill: 0 when it ran none (tools/eq_time.py); whether the handle holds the EQs' staging buffer;
 // and the frames the kernel stages at a time (tests/test_gpu_eq.py picks its call lengths around it)
 float s2r_debug_bus_eq_ms(const s2r_synth *s) { return POST_MS(stage[S2R_BUS_EQ].timer); }
@@ -1008,7 +1009,7 @@ uint32_t s2r_debug_eq_tile(void) { return S2R_EQ_TILE; }
 // ... of the buses' dynamics kernel in that fill: 0 when it ran none (tools/dyn_time.py); whether the handle holds the dynamics' staging
 // buffer; and the frames of one stage of the kernel's pipeline (tests/test_gpu_dyn.py picks its call lengths around it)
 float s2r_debug_dyn_ms(const s2r_synth *s) { return POST_MS(stage[S2R_BUS_DYN].timer); }
-int s2r_debug_dyn_allocated(const s2r_synth *s) { return s && (s->post.stage[S2R_BUS_DYN].buffer || s->post.dyn_curves || s->post.dyn_meter) ? 1 : 0; }
+int s2r_debug_dyn_allocated(const s2r_synth *s) { return s && (s->post.stage[S2R_BUS_DYN].buffer || s->post.dyn_curves.dev || s->post.dyn_meter.host) ? 1 : 0; }
 uint32_t s2r_debug_dyn_tile(void) { return S2R_DYN_TILE; }
 // ... of the buses' room kernel in that fill: 0 when it ran none (tools/room_time.py); whether the handle holds the rooms' staging buffer;
 // and the frames of one pass of the kernel (tests/test_gpu_room.py picks its call lengths around it)
@@ -1018,7 +1019,7 @@ uint32_t s2r_debug_room_tile(void) { return S2R_ROOM_TILE; }
 // ... of the buses' drive kernel in that fill: 0 when it ran none (tools/drive_time.py); whether the handle holds the drives' staging
 // buffer or their tables; and the output frames of one workgroup of the kernel (tests/test_gpu_drive.py picks its call lengths around it)
 float s2r_debug_bus_drive_ms(const s2r_synth *s) { return POST_MS(stage[S2R_BUS_DRIVE].timer); }
-int s2r_debug_drive_allocated(const s2r_synth *s) { return s && (s->post.stage[S2R_BUS_DRIVE].buffer || s->post.drive_curves) ? 1 : 0; }
+int s2r_debug_drive_allocated(const s2r_synth *s) { return s && (s->post.stage[S2R_BUS_DRIVE].buffer || s->post.drive_curves.dev) ? 1 : 0; }
 uint32_t s2r_debug_drive_tile(void) { return S2R_DRIVE_TILE; }
 // ... of the buses' flanger kernel in that fill: 0 when it ran none (tools/flanger_time.py); whether the handle holds the flangers'
 // staging buffer; and the frames of one tile of the kernel (tests/test_gpu_flanger.py picks its call lengths around it)
@@ -1032,27 +1033,27 @@ float s2r_debug_bus_delay_ms(const s2r_synth *s) { return POST_MS(stage[S2R_BUS_
 // ... and of the buses' reverb kernels in that fill: 0 when it ran none (tools/reverb_time.py)
 float s2r_debug_bus_fx_ms(const s2r_synth *s) { return POST_MS(stage[S2R_BUS_REVERB].timer); }
 // ... and of the master kernel in the last s2r_fill_master (tools/master_time.py)
-float s2r_debug_master_ms(const s2r_synth *s) { return POST_MS(master.timer); }
+float s2r_debug_master_ms(const s2r_synth *s) { return MASTER_MS(S2R_MASTER_MIX); }
 // ... and of the limiter kernel in that fill: 0 when it ran none (tools/limiter_time.py)
-float s2r_debug_limiter_ms(const s2r_synth *s) { return POST_MS(limiter.timer); }
+float s2r_debug_limiter_ms(const s2r_synth *s) { return MASTER_MS(S2R_MASTER_LIMITER); }
 // ... and of the loudness kernel in that fill: 0 when it ran none (tools/loudness_time.py)
-float s2r_debug_loudness_ms(const s2r_synth *s) { return POST_MS(loud.timer); }
+float s2r_debug_loudness_ms(const s2r_synth *s) { return MASTER_MS(S2R_MASTER_LOUDNESS); }
 // ... and of the spectrum kernel in that fill: 0 when it ran none (tools/spectrum_time.py)
-float s2r_debug_spectrum_ms(const s2r_synth *s) { return POST_MS(spec.timer); }
+float s2r_debug_spectrum_ms(const s2r_synth *s) { return MASTER_MS(S2R_MASTER_SPECTRUM); }
 // ... and of the PCM kernel in that fill: 0 when it ran none (tools/pcm_time.py); whether the handle holds anything of the stage's; and
 // the frames the kernel stages at a time (tests/test_gpu_pcm.py picks its call lengths around it)
-float s2r_debug_pcm_ms(const s2r_synth *s) { return POST_MS(pcm.timer); }
-int s2r_debug_pcm_allocated(const s2r_synth *s) { return s && (s->post.pcm.samples || s->post.pcm.counts || s->post.pcm.state.dev[0] || s->post.loud.in) ? 1 : 0; }
+float s2r_debug_pcm_ms(const s2r_synth *s) { return MASTER_MS(S2R_MASTER_PCM); }
+int s2r_debug_pcm_allocated(const s2r_synth *s) { return s && (s->post.pcm.samples.host || s->post.pcm.counts.host || s->post.pcm.state.dev[0] || s->post.loud.in.dev) ? 1 : 0; }
 uint32_t s2r_debug_pcm_tile(void) { return S2R_PCM_TILE; }
 // ... and of the resampler kernel in that fill: 0 when it ran none (tools/resampler_time.py); whether the handle holds anything of the
 // stage's; and the output frames of one of the kernel's workgroups (tests/test_gpu_resampler.py picks its call lengths around it)
-float s2r_debug_resampler_ms(const s2r_synth *s) { return POST_MS(res.timer); }
-int s2r_debug_resampler_allocated(const s2r_synth *s) { return s && (s->post.res.res || s->post.res.res_dev || s->post.res.table_dev || s->post.res.state.dev[0] || s->post.loud.in) ? 1 : 0; }
+float s2r_debug_resampler_ms(const s2r_synth *s) { return MASTER_MS(S2R_MASTER_RESAMPLER); }
+int s2r_debug_resampler_allocated(const s2r_synth *s) { return s && (s->post.res.res.host || s->post.res.res_dev.dev || s->post.res.table_dev.dev || s->post.res.state.dev[0] || s->post.loud.in.dev) ? 1 : 0; }
 uint32_t s2r_debug_resampler_tile(void) { return S2R_RESAMPLER_TILE; }
 // ... and of the multiband kernel in that fill: 0 when it ran none (tools/multiband_time.py); whether the handle holds anything of the
 // stage's; and the frames of one stage of the kernel's pipeline (tests/test_gpu_multiband.py picks its call lengths around it)
-float s2r_debug_multiband_ms(const s2r_synth *s) { return POST_MS(mb.timer); }
-int s2r_debug_multiband_allocated(const s2r_synth *s) { return s && (s->post.mb.in || s->post.mb.curves_dev || s->post.mb.meter || s->post.mb.state.dev[0]) ? 1 : 0; }
+float s2r_debug_multiband_ms(const s2r_synth *s) { return MASTER_MS(S2R_MASTER_MULTIBAND); }
+int s2r_debug_multiband_allocated(const s2r_synth *s) { return s && (s->post.mb.in.dev || s->post.mb.curves_dev.dev || s->post.mb.meter.host || s->post.mb.state.dev[0]) ? 1 : 0; }
 uint32_t s2r_debug_multiband_tile(void) { return S2R_MULTIBAND_TILE; }
 
 }  // extern "C"

@@ -17,14 +17,8 @@ constexpr size_t kLimState = 2u * (S2R_LIMITER_MAX_LOOKAHEAD + S2R_LIMITER_TP_HI
 
 inline uint32_t fx_pstride(const S2rPostCtx &c) { return (c.max_frames + 7u) & ~7u; }
 
-// pinned rows of partials, once; `host` survives a failed hipHostGetDevicePointer, and the next call goes on from there
-template <class T> hipError_t pinned_rows(T *&host, T *&dev, size_t floats) {
-    if (dev) return hipSuccess;
-    if (!host) POST_HIP(hipHostMalloc((void **)&host, floats * sizeof(T), kHostPolled));
-    return hipHostGetDevicePointer((void **)&dev, host, 0);
-}
-
 template <class F> void drop(F &f) { f.free(); f = F{}; }
+template <class... Owner> void free_all(Owner &...o) { (o.free(), ...); }
 
 // The setters' shared sequence.  The new effect `f` is built aside — the stage's staging buffer if this is its first effect, the two
 // lines, the current one +0.0 everywhere (the other is written whole by the first call), then `own(f)`: what else the effect allocates
@@ -49,8 +43,31 @@ hipError_t nothing_more(S2rBusLine &) { return hipSuccess; }
 using StageLaunch = hipError_t (S2rPostChain::*)(const S2rPostCtx &, const S2rPostCall &) const;
 const StageLaunch kStageLaunch[S2R_BUS_STAGES] = {&S2rPostChain::launch_eq,     &S2rPostChain::launch_dyn,   &S2rPostChain::launch_drive,  &S2rPostChain::launch_flanger,
                                                   &S2rPostChain::launch_chorus, &S2rPostChain::launch_delay, &S2rPostChain::launch_reverb, &S2rPostChain::launch_room};
+// ... and each master stage's, by S2rMasterStage
+const StageLaunch kMasterLaunch[S2R_MASTER_STAGES] = {&S2rPostChain::launch_master,   &S2rPostChain::launch_multiband, &S2rPostChain::launch_limiter, &S2rPostChain::launch_loudness,
+                                                      &S2rPostChain::launch_spectrum, &S2rPostChain::launch_resampler, &S2rPostChain::launch_pcm};
 
 }  // namespace
+
+hipError_t S2rDevBuf::reserve(size_t n) {
+    if (n <= floats) return hipSuccess;
+    free();
+    POST_HIP(hipMalloc((void **)&dev, n * sizeof(float)));
+    floats = n;
+    return hipSuccess;
+}
+
+hipError_t S2rDevTable::send(const std::vector<float> &host, size_t at, hipStream_t stream) const {
+    if (valid) return hipSuccess;
+    return hipMemcpyAsync(dev + at, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice, stream);
+}
+
+template <class T> hipError_t S2rPinned<T>::reserve(size_t n) {
+    if (n > count) free();
+    if (!host) { POST_HIP(hipHostMalloc((void **)&host, n * sizeof(T), kHostPolled)); count = n; }
+    if (!dev) POST_HIP(hipHostGetDevicePointer((void **)&dev, host, 0));
+    return hipSuccess;
+}
 
 hipError_t S2rBusLine::alloc(size_t n) {
     floats = n;
@@ -93,185 +110,162 @@ hipError_t S2rPostChain::prepare(const S2rPostCtx &c, uint32_t n_buses, uint32_t
     call.n_buses = n_buses; call.frames = frames; call.master = master_fill; call.stems = stems;
     for (int k = 0; k < S2R_BUS_STAGES; k++)
         for (uint32_t b = 0; b < n_buses; b++) if (runs(k, b, n_buses)) call.on[k] = true;
-    call.limited = master_fill && limiter.lookahead != 0;
-    if (call.master) {                                           // the device copy of the stems and the pinned rows of block partials
-        if (!master.stage) POST_HIP(hipMalloc((void **)&master.stage, (size_t)2 * S2R_MAX_BUSES * c.max_frames * sizeof(float)));
-        POST_HIP(pinned_rows(master.partials, master.partials_dev, (size_t)((c.max_frames + S2R_METER_BLOCK - 1u) / S2R_METER_BLOCK) * S2R_MASTER_ROW));
+    const uint32_t set[S2R_MASTER_STAGES] = {1u, mb.n_bands, limiter.lookahead, loud.hop, spec.n_fft, res.L, pcm.bits};      // 0: the stage is off
+    bool *const run = call.run;
+    for (int k = 0; k < S2R_MASTER_STAGES; k++) run[k] = master_fill && set[k] != 0;
+    if (run[S2R_MASTER_RESAMPLER]) res.call_count = (uint32_t)resampler_count(res.L, res.M, res.ph, frames);
+    call.pcm_idle = run[S2R_MASTER_PCM] && run[S2R_MASTER_RESAMPLER] && res.call_count == 0;    // the PCM kernel runs behind the resampler only when that makes a frame
+    run[S2R_MASTER_PCM] = run[S2R_MASTER_PCM] && !call.pcm_idle;
+    const size_t lr = (size_t)2 * c.max_frames;                  // the master's two channels, or one bus's
+    const auto blocks = [&](uint32_t block) { return (size_t)((c.max_frames + block - 1u) / block); };
+    if (run[S2R_MASTER_MIX]) {                                   // the device copy of the stems and the pinned rows of block partials
+        POST_HIP(master.stage.reserve(S2R_MAX_BUSES * lr));
+        POST_HIP(master.partials.reserve(blocks(S2R_METER_BLOCK) * S2R_MASTER_ROW));
     }
-    if (call.limited) {                                          // the limiter's input, the two copies of its state, its pinned rows of meter partials
-        if (!limiter.in) POST_HIP(hipMalloc((void **)&limiter.in, (size_t)2 * c.max_frames * sizeof(float)));
+    if (run[S2R_MASTER_LIMITER]) {                               // the limiter's input, the two copies of its state, its pinned rows of meter partials
+        POST_HIP(limiter.in.reserve(lr));
         POST_HIP(limiter.state.reserve(kLimState));
-        POST_HIP(pinned_rows(limiter.partials, limiter.partials_dev, (size_t)((c.max_frames + S2R_LIMITER_BLOCK - 1u) / S2R_LIMITER_BLOCK) * 2u));
+        POST_HIP(limiter.partials.reserve(blocks(S2R_LIMITER_BLOCK) * 2u));
     }
-    if (mb_on(call)) {                                           // its input, the tables, the two copies of its state, its pinned meter row
-        if (!mb.in) POST_HIP(hipMalloc((void **)&mb.in, (size_t)2 * c.max_frames * sizeof(float)));
-        if (!mb.curves_dev) { POST_HIP(hipMalloc((void **)&mb.curves_dev, (size_t)S2R_MULTIBAND_MAX_BANDS * S2R_DYN_CURVE_POINTS * sizeof(float))); mb.curves_valid = false; }
+    if (run[S2R_MASTER_MULTIBAND]) {                             // its input, the tables, the two copies of its state, its pinned meter row
+        POST_HIP(mb.in.reserve(lr));
+        POST_HIP(mb.curves_dev.reserve((size_t)S2R_MULTIBAND_MAX_BANDS * S2R_DYN_CURVE_POINTS));
         POST_HIP(mb.state.reserve(S2R_MULTIBAND_STATE(S2R_MULTIBAND_MAX_BANDS)));
-        POST_HIP(pinned_rows(mb.meter, mb.meter_dev, S2R_MULTIBAND_MAX_BANDS));
+        POST_HIP(mb.meter.reserve(S2R_MULTIBAND_MAX_BANDS));
     }
-    if (metered(call) && !loud.in) POST_HIP(hipMalloc((void **)&loud.in, (size_t)2 * c.max_frames * sizeof(float)));      // the meters' input
-    if (spec_on(call)) {                                         // the two copies of the state, the tables and the pinned rows, by n_fft and hop
-        Spectrum &sp = spec;
-        const size_t need_tables = 2u * (size_t)sp.n_fft, need_rows = (size_t)(c.max_frames / sp.hop + 1u) * sp.kept.width;
-        POST_HIP(sp.state.reserve(S2R_SPECTRUM_STATE(sp.n_fft)));
-        if (sp.tables_floats < need_tables) {
-            if (sp.tables) (void)hipFree(sp.tables);
-            sp.tables = nullptr; sp.tables_floats = 0; sp.tables_valid = false;
-            POST_HIP(hipMalloc((void **)&sp.tables, need_tables * sizeof(float)));
-            sp.tables_floats = need_tables;
-        }
-        if (sp.rows_floats < need_rows) {
-            if (sp.rows) (void)hipHostFree(sp.rows);
-            sp.rows = sp.rows_dev = nullptr; sp.rows_floats = 0;
-            POST_HIP(pinned_rows(sp.rows, sp.rows_dev, need_rows));
-            sp.rows_floats = need_rows;
-        }
+    const bool pcm_set = run[S2R_MASTER_PCM] || call.pcm_idle;
+    if (run[S2R_MASTER_LOUDNESS] || run[S2R_MASTER_SPECTRUM] || run[S2R_MASTER_RESAMPLER] || pcm_set) POST_HIP(loud.in.reserve(lr));       // the tail's input
+    if (run[S2R_MASTER_SPECTRUM]) {                              // the two copies of the state, the tables and the pinned rows, by n_fft and hop
+        POST_HIP(spec.state.reserve(S2R_SPECTRUM_STATE(spec.n_fft)));
+        POST_HIP(spec.tables.reserve(2u * (size_t)spec.n_fft));
+        POST_HIP(spec.rows.reserve((size_t)(c.max_frames / spec.hop + 1u) * spec.kept.width));
     }
-    if (loud_on(call)) {                                         // the two copies of its state, its pinned hop rows and peaks
+    if (run[S2R_MASTER_LOUDNESS]) {                              // the two copies of its state, its pinned hop rows and peaks
         POST_HIP(loud.state.reserve(S2R_LOUDNESS_STATE));
-        POST_HIP(pinned_rows(loud.rows, loud.rows_dev, (size_t)(c.max_frames / S2R_LOUDNESS_MIN_HOP + 1u) * S2R_LOUDNESS_CHANNELS));
-        POST_HIP(pinned_rows(loud.peaks, loud.peaks_dev, (size_t)((c.max_frames + S2R_LOUDNESS_BLOCK - 1u) / S2R_LOUDNESS_BLOCK) * 2u));
+        POST_HIP(loud.rows.reserve((size_t)(c.max_frames / S2R_LOUDNESS_MIN_HOP + 1u) * S2R_LOUDNESS_CHANNELS));
+        POST_HIP(loud.peaks.reserve(blocks(S2R_LOUDNESS_BLOCK) * 2u));
     }
-    if (res_on(call)) {                                          // the two copies of its state, the table and the outputs, by L, M and T
-        Resampler &rs = res;
-        const size_t need_table = (size_t)rs.L * rs.T;
-        const uint32_t need_cap = (uint32_t)S2R_RESAMPLER_MAX_OUT(c.max_frames, rs.L, rs.M);
-        rs.call_count = (uint32_t)resampler_count(rs.L, rs.M, rs.ph, frames);
-        POST_HIP(rs.state.reserve(S2R_RESAMPLER_STATE(rs.T)));
-        if (rs.table_floats < need_table) {
-            if (rs.table_dev) (void)hipFree(rs.table_dev);
-            rs.table_dev = nullptr; rs.table_floats = 0; rs.table_valid = false;
-            POST_HIP(hipMalloc((void **)&rs.table_dev, need_table * sizeof(float)));
-            rs.table_floats = need_table;
-        }
-        if (rs.cap < need_cap) {
-            if (rs.res) (void)hipHostFree(rs.res);
-            rs.res = rs.res_map = nullptr; rs.cap = 0; rs.have = false; rs.count = 0;
-            POST_HIP(pinned_rows(rs.res, rs.res_map, (size_t)S2R_RESAMPLER_PROGRAMMES * 2u * need_cap));
-            rs.cap = need_cap;
-        }
-        if (pcm_on(call) && rs.dev_cap < need_cap) {             // what the PCM kernel reads behind it
-            if (rs.res_dev) (void)hipFree(rs.res_dev);
-            rs.res_dev = nullptr; rs.dev_cap = 0;
-            POST_HIP(hipMalloc((void **)&rs.res_dev, (size_t)S2R_RESAMPLER_PROGRAMMES * 2u * need_cap * sizeof(float)));
-            rs.dev_cap = need_cap;
-        }
+    const size_t res_cap = res.L ? (size_t)S2R_RESAMPLER_MAX_OUT(c.max_frames, res.L, res.M) : 0u;
+    if (run[S2R_MASTER_RESAMPLER]) {                             // the two copies of its state, the table and the outputs, by L, M and T
+        const size_t need = (size_t)S2R_RESAMPLER_PROGRAMMES * 2u * res_cap;
+        POST_HIP(res.state.reserve(S2R_RESAMPLER_STATE(res.T)));
+        POST_HIP(res.table_dev.reserve((size_t)res.L * res.T));
+        if (res.res.grows(need)) { res.have = false; res.count = 0; }      // (a regrowth drops the last fill's outputs)
+        POST_HIP(res.res.reserve(need));
+        if (pcm_set) POST_HIP(res.res_dev.reserve(need));        // what the PCM kernel reads behind it
     }
-    if (pcm_on(call)) {                                          // the two copies of its state, its pinned samples and counts
-        const uint32_t need = res_on(call) ? (uint32_t)S2R_RESAMPLER_MAX_OUT(c.max_frames, res.L, res.M) : c.max_frames;
+    if (pcm_set) {                                               // the two copies of its state, its pinned samples and counts
+        const size_t need = (size_t)S2R_PCM_PROGRAMMES * 2u * (run[S2R_MASTER_RESAMPLER] ? res_cap : c.max_frames);
         POST_HIP(pcm.state.reserve(S2R_PCM_STATE));
-        if (pcm.cap < need) {                                    // (a regrowth drops the last fill's samples)
-            if (pcm.samples) (void)hipHostFree(pcm.samples);
-            pcm.samples = pcm.samples_dev = nullptr; pcm.cap = 0; pcm.have = false; pcm.frames = 0;
-            POST_HIP(pinned_rows(pcm.samples, pcm.samples_dev, (size_t)S2R_PCM_PROGRAMMES * 2u * need));
-            pcm.cap = need;
-        }
-        POST_HIP(pinned_rows(pcm.counts, pcm.counts_dev, S2R_PCM_CHANNELS));
+        if (pcm.samples.grows(need)) { pcm.have = false; pcm.frames = 0; }   // (a regrowth drops the last fill's samples)
+        POST_HIP(pcm.samples.reserve(need));
+        POST_HIP(pcm.counts.reserve(S2R_PCM_CHANNELS));
     }
     float *own[S2R_BUS_STAGES];
     for (int k = 0; k < S2R_BUS_STAGES; k++) own[k] = stage[k].buffer;
-    // (with the meter on, whoever writes the master last writes it into the meter's input, and the meter's kernel writes the pinned output)
-    call.route = s2r_post_route(call, own, master.stage, limiter.in, c.bus_out_dev, metered(call) ? loud.in : c.out_host_dev);
+    call.route = s2r_post_route(call, own, master.stage.dev, mb.in.dev, limiter.in.dev, loud.in.dev, res.res_dev.dev, (size_t)2 * S2R_MAX_BUSES * res.call_count,
+                                c.bus_out_dev, c.out_host_dev);
     return hipSuccess;
 }
 
 hipError_t S2rPostChain::launch(const S2rPostCtx &c, const S2rPostCall &call) {
-    const S2rPostRoute &r = call.route; const float fn = (float)call.frames;
     for (int k = 0; k < S2R_BUS_STAGES; k++)                     // each once per call, over all of its frames, every bus as the stages in front left it
         if (call.on[k]) POST_TIMED(c, stage[k].timer, (this->*kStageLaunch[k])(c, call));
-    if (call.master) {                                           // returns, master fader and the meters' block partials
-        S2rMaster m{};
-        m.stage = r.master_in; m.out = mb_on(call) ? mb.in : r.master_out; m.stems = r.master_stems; m.partials = master.partials_dev;
-        m.n_buses = call.n_buses; m.frames = call.frames;
-        for (uint32_t b = 0; b < call.n_buses; b++) {
-            const float d = master.ret[b] - master.ret_app[b];   // (+0.0 for a pair that did not move, and so is its step)
-            m.r0[b] = master.ret_app[b]; m.dr[b] = d / fn;
-        }
-        const float d = master.fader - master.fader_app;
-        m.m0 = master.fader_app; m.dm = d / fn;
-        POST_TIMED(c, master.timer, s2r_launch_master(m, c.stream));
-    }
-    if (mb_on(call)) {                                           // between the master kernel and whoever reads the master next: it writes where the route sent the master
-        Multiband &f = mb;
-        if (!f.curves_valid)                                     // (stays so until the commit)
-            POST_HIP(hipMemcpyAsync(f.curves_dev, f.curves.data(), f.curves.size() * sizeof(float), hipMemcpyHostToDevice, c.stream));
-        POST_HIP(f.state.upload(c.stream));
-        const S2rMultibandGraph g = multiband_graph(f.n_bands);
-        S2rMultiband a{};
-        a.in = f.in; a.out = r.master_out; a.state = f.state.now(); a.next = f.state.next(); a.curves = f.curves_dev; a.meter = f.meter_dev;
-        for (uint32_t i = 0; i < g.n; i++) {
-            const float *q = g.kind[i] == 0u ? f.lp[g.row[i]] : (g.kind[i] == 1u ? f.hp[g.row[i]] : f.ap[g.row[i]]);
-            std::memcpy(a.c[i], q, sizeof a.c[i]);
-            a.src[i] = g.src[i]; a.depth[i] = g.depth[i];
-        }
-        for (uint32_t j = 0; j < f.n_bands; j++) { a.leaf[j] = g.leaf[j]; a.a_att[j] = f.a_att[j]; a.a_rel[j] = f.a_rel[j]; }
-        a.n_bands = f.n_bands; a.n_sections = g.n; a.frames = call.frames;
-        POST_TIMED(c, f.timer, s2r_launch_multiband(a, c.stream));
-    }
-    if (call.limited) {                                          // the next state goes into the copy that is not the current one
-        Limiter &lm = limiter;
-        float *cur = lm.state.now(), *next = lm.state.next();
-        POST_HIP(lm.state.upload(c.stream));                     // (a host copy stays valid until the commit: a failed call leaves the state where it was)
-        S2rLimiter a{};
-        a.x = r.limiter_in; a.out = r.limiter_out; a.xh = cur; a.gh = cur + lm.n_x(); a.xh_next = next; a.gh_next = next + lm.n_x();
-        a.partials = lm.partials_dev; a.frames = call.frames; a.lookahead = lm.lookahead; a.hold = lm.hold; a.ceiling = lm.ceiling;
-        if (lm.detector == S2R_LIMITER_TRUE_PEAK) {              // the same block, the interpolator's taps beside it, its own kernel
-            S2rLimiterTp t{};
-            t.l = a; std::memcpy(t.g, drive_taps().g, sizeof t.g);
-            POST_TIMED(c, lm.timer, s2r_launch_limiter_tp(t, c.stream));
-        } else
-            POST_TIMED(c, lm.timer, s2r_launch_limiter(a, c.stream));
-    }
-    if (loud_on(call)) {                                         // behind whoever wrote the master last: the next state goes into the other copy
-        Loudness &ld = loud;
-        POST_HIP(ld.state.upload(c.stream));
-        S2rLoudness a{};
-        a.stems = r.master_in; a.master = call.limited ? r.limiter_out : r.master_out; a.out = c.out_host_dev; a.state = ld.state.now(); a.next = ld.state.next();
-        a.rows = ld.rows_dev; a.peaks = ld.peaks_dev; a.n_buses = call.n_buses; a.frames = call.frames; a.hop = ld.hop; a.pos = ld.pos;
-        std::memcpy(a.c, ld.c, sizeof a.c); std::memcpy(a.g, drive_taps().g, sizeof a.g);
-        POST_TIMED(c, ld.timer, s2r_launch_loudness(a, c.stream));
-    }
-    if (spec_on(call)) {                                         // last: it copies the master out only when the loudness kernel has not
-        Spectrum &sp = spec;
-        const size_t n = sp.n_fft;
-        if (!sp.tables_valid) {                                  // (stays so until the commit)
-            POST_HIP(hipMemcpyAsync(sp.tables, sp.window.data(), n * sizeof(float), hipMemcpyHostToDevice, c.stream));
-            POST_HIP(hipMemcpyAsync(sp.tables + n, sp.twiddles.data(), n * sizeof(float), hipMemcpyHostToDevice, c.stream));
-        }
-        POST_HIP(sp.state.upload(c.stream));
-        S2rSpectrum a{};
-        a.stems = r.master_in; a.master = call.limited ? r.limiter_out : r.master_out; a.out = loud_on(call) ? nullptr : c.out_host_dev;
-        a.state = sp.state.now(); a.next = sp.state.next(); a.window = sp.tables; a.twiddles = sp.tables + n; a.rows = sp.rows_dev;
-        a.n_buses = call.n_buses; a.frames = call.frames; a.n_fft = sp.n_fft; a.hop = sp.hop; a.pos = sp.pos;
-        POST_TIMED(c, sp.timer, s2r_launch_spectrum(a, c.stream));
-    }
-    if (res_on(call)) {                                          // behind the meters: it copies the master out only when no meter kernel has
-        Resampler &rs = res;
-        if (!rs.table_valid)                                     // (stays so until the commit)
-            POST_HIP(hipMemcpyAsync(rs.table_dev, rs.table.data(), rs.table.size() * sizeof(float), hipMemcpyHostToDevice, c.stream));
-        POST_HIP(rs.state.upload(c.stream));
-        S2rResampler a{};
-        a.stems = r.master_in; a.master = call.limited ? r.limiter_out : r.master_out; a.out = loud_on(call) || spec_on(call) ? nullptr : c.out_host_dev;
-        a.state = rs.state.now(); a.next = rs.state.next(); a.table = rs.table_dev; a.res = rs.res_map; a.res_dev = pcm_runs(call) ? rs.res_dev : nullptr;
-        a.n_buses = call.n_buses; a.frames = call.frames; a.L = rs.L; a.M = rs.M; a.T = rs.T; a.ph = rs.ph; a.count = rs.call_count; a.out_cap = rs.cap;
-        POST_TIMED(c, rs.timer, s2r_launch_resampler(a, c.stream));
-    }
-    if (pcm_runs(call)) {                                        // last of all: it copies the master out only when no kernel behind the master has
-        Pcm &pm = pcm;
-        POST_HIP(pm.state.upload(c.stream));
-        S2rPcm a{};
-        a.stems = r.master_in; a.master = call.limited ? r.limiter_out : r.master_out; a.out = loud_on(call) || spec_on(call) ? nullptr : c.out_host_dev;
-        a.state = pm.state.now(); a.next = pm.state.next(); a.pcm = pm.samples_dev; a.clips = pm.counts_dev;
-        std::memcpy(a.h, pm.h, sizeof a.h);
-        a.n_buses = call.n_buses; a.frames = call.frames; a.pstride = pm.cap; a.bits = pm.bits; a.dither = pm.dither; a.n_taps = pm.n_taps;
-        a.seed = pm.seed; a.t = pm.t;
-        if (res_on(call)) {                                      // the resampler's output: all eight buses, then the master, `count` frames each
-            a.stems = res.res_dev; a.master = res.res_dev + (size_t)2 * S2R_MAX_BUSES * res.call_count; a.out = nullptr;
-            a.n_buses = S2R_MAX_BUSES; a.frames = res.call_count;
-        }
-        POST_TIMED(c, pm.timer, s2r_launch_pcm(a, c.stream));
-    }
+    for (int k = 0; k < S2R_MASTER_STAGES; k++)                  // ... and the master stages behind them, each on what route.writer or route.reader names
+        if (call.run[k]) POST_TIMED(c, master_timer[k], (this->*kMasterLaunch[k])(c, call));
     return hipSuccess;
+}
+
+hipError_t S2rPostChain::launch_master(const S2rPostCtx &c, const S2rPostCall &call) const {    // returns, master fader and the meters' block partials
+    const float fn = (float)call.frames;
+    S2rMaster m{};
+    m.stage = call.route.writer[S2R_MASTER_MIX].in; m.out = call.route.writer[S2R_MASTER_MIX].out; m.stems = call.route.master_stems; m.partials = master.partials.dev;
+    m.n_buses = call.n_buses; m.frames = call.frames;
+    for (uint32_t b = 0; b < call.n_buses; b++) {
+        const float d = master.ret[b] - master.ret_app[b];       // (+0.0 for a pair that did not move, and so is its step)
+        m.r0[b] = master.ret_app[b]; m.dr[b] = d / fn;
+    }
+    const float d = master.fader - master.fader_app;
+    m.m0 = master.fader_app; m.dm = d / fn;
+    return s2r_launch_master(m, c.stream);
+}
+
+hipError_t S2rPostChain::launch_multiband(const S2rPostCtx &c, const S2rPostCall &call) const {
+    const Multiband &f = mb;
+    POST_HIP(f.curves_dev.send(f.curves, 0, c.stream));          // (not valid until the commit)
+    POST_HIP(f.state.upload(c.stream));
+    const S2rMultibandGraph g = multiband_graph(f.n_bands);
+    S2rMultiband a{};
+    a.in = call.route.writer[S2R_MASTER_MULTIBAND].in; a.out = call.route.writer[S2R_MASTER_MULTIBAND].out;
+    a.state = f.state.now(); a.next = f.state.next(); a.curves = f.curves_dev.dev; a.meter = f.meter.dev;
+    for (uint32_t i = 0; i < g.n; i++) {
+        const float *q = g.kind[i] == 0u ? f.lp[g.row[i]] : (g.kind[i] == 1u ? f.hp[g.row[i]] : f.ap[g.row[i]]);
+        std::memcpy(a.c[i], q, sizeof a.c[i]);
+        a.src[i] = g.src[i]; a.depth[i] = g.depth[i];
+    }
+    for (uint32_t j = 0; j < f.n_bands; j++) { a.leaf[j] = g.leaf[j]; a.a_att[j] = f.a_att[j]; a.a_rel[j] = f.a_rel[j]; }
+    a.n_bands = f.n_bands; a.n_sections = g.n; a.frames = call.frames;
+    return s2r_launch_multiband(a, c.stream);
+}
+
+hipError_t S2rPostChain::launch_limiter(const S2rPostCtx &c, const S2rPostCall &call) const {   // the next state goes into the copy that is not the current one
+    const Limiter &lm = limiter;
+    float *cur = lm.state.now(), *next = lm.state.next();
+    POST_HIP(lm.state.upload(c.stream));                         // (a host copy stays valid until the commit: a failed call leaves the state where it was)
+    S2rLimiter a{};
+    a.x = call.route.writer[S2R_MASTER_LIMITER].in; a.out = call.route.writer[S2R_MASTER_LIMITER].out;
+    a.xh = cur; a.gh = cur + lm.n_x(); a.xh_next = next; a.gh_next = next + lm.n_x();
+    a.partials = lm.partials.dev; a.frames = call.frames; a.lookahead = lm.lookahead; a.hold = lm.hold; a.ceiling = lm.ceiling;
+    if (lm.detector != S2R_LIMITER_TRUE_PEAK) return s2r_launch_limiter(a, c.stream);
+    S2rLimiterTp t{};                                            // the same block, the interpolator's taps beside it, its own kernel
+    t.l = a; std::memcpy(t.g, drive_taps().g, sizeof t.g);
+    return s2r_launch_limiter_tp(t, c.stream);
+}
+
+hipError_t S2rPostChain::launch_loudness(const S2rPostCtx &c, const S2rPostCall &call) const {  // behind whoever wrote the master last
+    const Loudness &ld = loud; const auto &r = call.route.reader[S2R_MASTER_LOUDNESS - S2R_MASTER_WRITERS];
+    POST_HIP(ld.state.upload(c.stream));
+    S2rLoudness a{};
+    a.stems = r.stems; a.master = r.in; a.out = r.out; a.state = ld.state.now(); a.next = ld.state.next();
+    a.rows = ld.rows.dev; a.peaks = ld.peaks.dev; a.n_buses = call.n_buses; a.frames = call.frames; a.hop = ld.hop; a.pos = ld.pos;
+    std::memcpy(a.c, ld.c, sizeof a.c); std::memcpy(a.g, drive_taps().g, sizeof a.g);
+    return s2r_launch_loudness(a, c.stream);
+}
+
+hipError_t S2rPostChain::launch_spectrum(const S2rPostCtx &c, const S2rPostCall &call) const {
+    const Spectrum &sp = spec; const auto &r = call.route.reader[S2R_MASTER_SPECTRUM - S2R_MASTER_WRITERS];
+    POST_HIP(sp.tables.send(sp.window, 0, c.stream));            // (not valid until the commit)
+    POST_HIP(sp.tables.send(sp.twiddles, sp.n_fft, c.stream));
+    POST_HIP(sp.state.upload(c.stream));
+    S2rSpectrum a{};
+    a.stems = r.stems; a.master = r.in; a.out = r.out;
+    a.state = sp.state.now(); a.next = sp.state.next(); a.window = sp.tables.dev; a.twiddles = sp.tables.dev + sp.n_fft; a.rows = sp.rows.dev;
+    a.n_buses = call.n_buses; a.frames = call.frames; a.n_fft = sp.n_fft; a.hop = sp.hop; a.pos = sp.pos;
+    return s2r_launch_spectrum(a, c.stream);
+}
+
+hipError_t S2rPostChain::launch_resampler(const S2rPostCtx &c, const S2rPostCall &call) const {
+    const Resampler &rs = res; const auto &r = call.route.reader[S2R_MASTER_RESAMPLER - S2R_MASTER_WRITERS];
+    POST_HIP(rs.table_dev.send(rs.table, 0, c.stream));          // (not valid until the commit)
+    POST_HIP(rs.state.upload(c.stream));
+    S2rResampler a{};
+    a.stems = r.stems; a.master = r.in; a.out = r.out;
+    a.state = rs.state.now(); a.next = rs.state.next(); a.table = rs.table_dev.dev; a.res = rs.res.dev; a.res_dev = call.route.res_dev;
+    a.n_buses = call.n_buses; a.frames = call.frames; a.L = rs.L; a.M = rs.M; a.T = rs.T; a.ph = rs.ph; a.count = rs.call_count; a.out_cap = rs.cap();
+    return s2r_launch_resampler(a, c.stream);
+}
+
+hipError_t S2rPostChain::launch_pcm(const S2rPostCtx &c, const S2rPostCall &call) const {       // last of all
+    const Pcm &pm = pcm; const auto &r = call.route.reader[S2R_MASTER_PCM - S2R_MASTER_WRITERS];
+    POST_HIP(pm.state.upload(c.stream));
+    S2rPcm a{};
+    a.stems = r.stems; a.master = r.in; a.out = r.out;
+    a.state = pm.state.now(); a.next = pm.state.next(); a.pcm = pm.samples.dev; a.clips = pm.counts.dev;
+    std::memcpy(a.h, pm.h, sizeof a.h);
+    a.n_buses = call.n_buses; a.frames = call.frames; a.pstride = pm.cap(); a.bits = pm.bits; a.dither = pm.dither; a.n_taps = pm.n_taps;
+    a.seed = pm.seed; a.t = pm.t;
+    if (call.run[S2R_MASTER_RESAMPLER]) { a.n_buses = S2R_MAX_BUSES; a.frames = res.call_count; }        // the resampler's output: all eight buses, then the master, `count` frames each
+    return s2r_launch_pcm(a, c.stream);
 }
 
 hipError_t S2rPostChain::launch_eq(const S2rPostCtx &c, const S2rPostCall &call) const {
@@ -293,10 +287,10 @@ hipError_t S2rPostChain::launch_dyn(const S2rPostCtx &c, const S2rPostCall &call
         if (!runs(S2R_BUS_DYN, b, call.n_buses)) continue;
         const BusDyn &f = dyn[b];
         S2rDynBus &d = a.bus[b];
-        d.line = f.now(); d.next = f.next(); d.curve = dyn_curves + (size_t)b * S2R_DYN_CURVE_POINTS;
+        d.line = f.now(); d.next = f.next(); d.curve = dyn_curves.dev + (size_t)b * S2R_DYN_CURVE_POINTS;
         d.key = f.key; d.a_att = f.a_att; d.a_rel = f.a_rel;
     }
-    a.in = call.route.stage[S2R_BUS_DYN].in; a.out = call.route.stage[S2R_BUS_DYN].out; a.meter = dyn_meter_dev; a.n_buses = call.n_buses; a.frames = call.frames;
+    a.in = call.route.stage[S2R_BUS_DYN].in; a.out = call.route.stage[S2R_BUS_DYN].out; a.meter = dyn_meter.dev; a.n_buses = call.n_buses; a.frames = call.frames;
     return s2r_launch_bus_dyn(a, c.stream);
 }
 
@@ -306,7 +300,7 @@ hipError_t S2rPostChain::launch_drive(const S2rPostCtx &c, const S2rPostCall &ca
         const BusDrive &f = drive[b];
         if (!f.present()) continue;
         S2rDriveBus &d = a.bus[b];
-        d.curve = drive_curves + (size_t)b * S2R_DRIVE_CURVE_POINTS; d.line = f.now(); d.next = f.next();
+        d.curve = drive_curves.dev + (size_t)b * S2R_DRIVE_CURVE_POINTS; d.line = f.now(); d.next = f.next();
         d.pre = f.pre; d.dry = f.dry; d.wet = f.wet;
     }
     const S2rDriveTaps &taps = drive_taps();
@@ -391,15 +385,15 @@ void S2rPostChain::commit(const S2rPostCall &call) {
     for (uint32_t b = 0; b < call.n_buses; b++) {                // ... and what is no flip: the LFOs' phases, and the dynamics kernel's minima are the call's meters
         if (chorus[b].present()) chorus[b].phase += chorus[b].phase_inc * call.frames;
         if (flanger[b].present()) flanger[b].phase += flanger[b].phase_inc * call.frames;
-        if (runs(S2R_BUS_DYN, b, call.n_buses)) dyn[b].min_gain = dyn_meter[b];
+        if (runs(S2R_BUS_DYN, b, call.n_buses)) dyn[b].min_gain = dyn_meter.host[b];
     }
-    if (call.master) {                                           // the block partials in block order, and applied = target
+    if (call.run[S2R_MASTER_MIX]) {                                   // the block partials in block order, and applied = target
         Master &ms = master;
         const uint32_t n_ch = (call.n_buses + 1u) * 2u, n_blocks = (call.frames + S2R_METER_BLOCK - 1u) / S2R_METER_BLOCK;
         for (uint32_t ch = 0; ch < n_ch; ch++) {
             float peak = 0.0f, energy = 0.0f;
             for (uint32_t k = 0; k < n_blocks; k++) {
-                const float *row = ms.partials + (size_t)k * S2R_MASTER_ROW;
+                const float *row = ms.partials.host + (size_t)k * S2R_MASTER_ROW;
                 peak = row[ch] > peak ? row[ch] : peak;
                 energy = energy + row[S2R_MASTER_CH + ch];
             }
@@ -407,93 +401,83 @@ void S2rPostChain::commit(const S2rPostCall &call) {
         }
         ms.metered = true; ms.meter_buses = call.n_buses; snap_master();
     }
-    if (mb_on(call)) {                                           // the state has moved on, and the walkers' minima are the call's meters
+    if (call.run[S2R_MASTER_MULTIBAND]) {                             // the state has moved on, and the walkers' minima are the call's meters
         Multiband &f = mb;
-        f.state.committed(); f.curves_valid = true; f.metered = true;
-        for (uint32_t j = 0; j < f.n_bands; j++) f.min_gain[j] = f.meter[j];
+        f.state.committed(); f.curves_dev.committed(); f.metered = true;
+        for (uint32_t j = 0; j < f.n_bands; j++) f.min_gain[j] = f.meter.host[j];
     }
-    if (call.limited) {                                          // the state has moved on, and the workgroups' rows give the call's meters
+    if (call.run[S2R_MASTER_LIMITER]) {                               // the state has moved on, and the workgroups' rows give the call's meters
         Limiter &lm = limiter;
         lm.state.committed();
         const uint32_t n_blocks = (call.frames + S2R_LIMITER_BLOCK - 1u) / S2R_LIMITER_BLOCK;
-        float mn = lm.partials[0], pk = lm.partials[1];
+        float mn = lm.partials.host[0], pk = lm.partials.host[1];
         for (uint32_t k = 1; k < n_blocks; k++) {
-            const float *row = lm.partials + (size_t)k * 2u;
+            const float *row = lm.partials.host + (size_t)k * 2u;
             mn = row[0] < mn ? row[0] : mn;
             pk = row[1] > pk ? row[1] : pk;
         }
         lm.min_gain = mn; lm.out_peak = pk; lm.metered = true;
     }
-    if (spec_on(call)) {                                         // the state has moved on, and the call's rows join the rows kept
+    if (call.run[S2R_MASTER_SPECTRUM]) {                              // the state has moved on, and the call's rows join the rows kept
         Spectrum &sp = spec;
-        sp.state.committed(); sp.tables_valid = true;
-        sp.kept.take(sp.rows, sp.pos, call.frames, sp.hop);
+        sp.state.committed(); sp.tables.committed();
+        sp.kept.take(sp.rows.host, sp.pos, call.frames, sp.hop);
     }
-    if (pcm_runs(call)) {                                        // the state and t have moved on; the call's clips join the held ones
+    if (call.run[S2R_MASTER_PCM]) {                                   // the state and t have moved on; the call's clips join the held ones
         Pcm &pm = pcm;
-        const uint32_t made = res_on(call) ? res.call_count : call.frames;
+        const uint32_t made = call.run[S2R_MASTER_RESAMPLER] ? res.call_count : call.frames;
         pm.state.committed(); pm.t += made; pm.frames = made; pm.have = true;
         for (uint32_t q = 0; q < S2R_PCM_CHANNELS; q++) {
-            pm.clips_last[q] = pm.counts[q];
-            pm.clips_held[q] = pm.clips_held[q] + pm.counts[q] < pm.clips_held[q] ? UINT32_MAX : pm.clips_held[q] + pm.counts[q];
+            pm.clips_last[q] = pm.counts.host[q];
+            pm.clips_held[q] = pm.clips_held[q] + pm.counts.host[q] < pm.clips_held[q] ? UINT32_MAX : pm.clips_held[q] + pm.counts.host[q];
         }
-    } else if (pcm_on(call)) {                                   // the resampler made no frame: no kernel ran, state, t and the held clips stay
+    } else if (call.pcm_idle) {                                  // the resampler made no frame: no kernel ran, state, t and the held clips stay
         Pcm &pm = pcm;
         pm.frames = 0; pm.have = true;
         for (uint32_t q = 0; q < S2R_PCM_CHANNELS; q++) pm.clips_last[q] = 0u;
     }
-    if (res_on(call)) {                                          // the state and ph have moved on
+    if (call.run[S2R_MASTER_RESAMPLER]) {                             // the state and ph have moved on
         Resampler &rs = res;
-        rs.state.committed(); rs.table_valid = true;
+        rs.state.committed(); rs.table_dev.committed();
         rs.ph = (uint32_t)((uint64_t)rs.ph + (uint64_t)rs.call_count * rs.M - (uint64_t)call.frames * rs.L);
         rs.count = rs.call_count; rs.have = true;
     }
-    if (loud_on(call)) {                                         // the state has moved on; the call's hops join the rows, its peaks the held ones
+    if (call.run[S2R_MASTER_LOUDNESS]) {                              // the state has moved on; the call's hops join the rows, its peaks the held ones
         Loudness &ld = loud;
         ld.state.committed();
-        ld.kept.take(ld.rows, ld.pos, call.frames, ld.hop);
+        ld.kept.take(ld.rows.host, ld.pos, call.frames, ld.hop);
         const uint32_t n_blocks = (call.frames + S2R_LOUDNESS_BLOCK - 1u) / S2R_LOUDNESS_BLOCK;
         for (uint32_t ch = 0; ch < 2u; ch++) {
-            float pk = ld.peaks[ch];
-            for (uint32_t k = 1; k < n_blocks; k++) pk = ld.peaks[(size_t)k * 2u + ch] > pk ? ld.peaks[(size_t)k * 2u + ch] : pk;
+            float pk = ld.peaks.host[ch];
+            for (uint32_t k = 1; k < n_blocks; k++) pk = ld.peaks.host[(size_t)k * 2u + ch] > pk ? ld.peaks.host[(size_t)k * 2u + ch] : pk;
             ld.tp_last[ch] = pk;
             ld.tp_held[ch] = pk > ld.tp_held[ch] ? pk : ld.tp_held[ch];
         }
     }
 }
 
-// a stage that the fill could have run and did not reads 0; a panned fill leaves all ten values alone, a bus fill the master's two
+// a stage that the fill could have run and did not reads 0; a panned fill leaves all fifteen values alone, a bus fill the master stages' seven
 hipError_t S2rPostChain::read_timers(const S2rPostCall &call) {
     if (call.n_buses) for (int k = 0; k < S2R_BUS_STAGES; k++) { stage[k].timer.ms = 0.0f; if (call.on[k]) POST_HIP(stage[k].timer.read()); }
-    if (call.master) {
-        POST_HIP(master.timer.read());
-        mb.timer.ms = 0.0f;
-        if (mb_on(call)) POST_HIP(mb.timer.read());
-        limiter.timer.ms = 0.0f;
-        if (call.limited) POST_HIP(limiter.timer.read());
-        loud.timer.ms = 0.0f;
-        if (loud_on(call)) POST_HIP(loud.timer.read());
-        spec.timer.ms = 0.0f;
-        if (spec_on(call)) POST_HIP(spec.timer.read());
-        res.timer.ms = 0.0f;
-        if (res_on(call)) POST_HIP(res.timer.read());
-        pcm.timer.ms = 0.0f;
-        if (pcm_runs(call)) POST_HIP(pcm.timer.read());
-    }
+    if (call.master) for (int k = 0; k < S2R_MASTER_STAGES; k++) { master_timer[k].ms = 0.0f; if (call.run[k]) POST_HIP(master_timer[k].read()); }
     return hipSuccess;
 }
 
 void S2rPostChain::release() {
     for (uint32_t b = 0; b < S2R_MAX_BUSES; b++) { drop(eq[b]); drop(dyn[b]); drop(drive[b]); drop(flanger[b]); drop(chorus[b]); drop(delay[b]); drop(fx[b]); drop(room[b]); }
     for (Stem &st : stage) { if (st.buffer) (void)hipFree(st.buffer); st.timer.destroy(); }
-    // ... and what is neither a line nor a stage's buffer
-    for (S2rMirror *m : {&limiter.state, &loud.state, &spec.state, &pcm.state, &res.state, &mb.state}) m->free();
-    for (float *p : {dyn_curves, drive_curves, master.stage, limiter.in, loud.in, spec.tables, res.table_dev, res.res_dev, mb.in, mb.curves_dev}) if (p) (void)hipFree(p);
-    for (float *p : {dyn_meter, master.partials, limiter.partials, loud.rows, loud.peaks, spec.rows, res.res, mb.meter}) if (p) (void)hipHostFree(p);
-    if (pcm.samples) (void)hipHostFree(pcm.samples);
-    if (pcm.counts) (void)hipHostFree(pcm.counts);
-    for (S2rPostTimer *t : {&master.timer, &limiter.timer, &loud.timer, &spec.timer, &pcm.timer, &res.timer, &mb.timer}) t->destroy();
+    free_all(dyn_curves, dyn_meter, drive_curves);               // ... and what is neither a line nor a stage's buffer, stage by stage
+    free_all(master.stage, master.partials);
+    free_all(mb.state, mb.in, mb.curves_dev, mb.meter);
+    free_all(limiter.state, limiter.in, limiter.partials);
+    free_all(loud.state, loud.in, loud.rows, loud.peaks);
+    free_all(spec.state, spec.tables, spec.rows);
+    free_all(res.state, res.table_dev, res.res, res.res_dev);
+    free_all(pcm.state, pcm.samples, pcm.counts);
+    for (S2rPostTimer &t : master_timer) t.destroy();
 }
+
+
 
 hipError_t S2rPostChain::set_eq(const S2rPostCtx &c, uint32_t bus, uint32_t n_bands, const float *coeffs) {
     if (n_bands == 0) { drop(eq[bus]); return hipSuccess; }
@@ -507,21 +491,20 @@ hipError_t S2rPostChain::set_eq(const S2rPostCtx &c, uint32_t bus, uint32_t n_ba
 // everything that can fail for want of memory, so that a refused set leaves the earlier dynamics whole.
 hipError_t S2rPostChain::set_dyn(const S2rPostCtx &c, uint32_t bus, uint32_t key, const float *curve, float a_att, float a_rel, bool keep_state) {
     if (!curve) { drop(dyn[bus]); return hipSuccess; }
-    float *const row = dyn_curves ? dyn_curves + (size_t)bus * S2R_DYN_CURVE_POINTS : nullptr;
     if (keep_state) {
         BusDyn &d = dyn[bus];
-        POST_HIP(hipMemcpyAsync(row, curve, S2R_DYN_CURVE_POINTS * sizeof(float), hipMemcpyHostToDevice, c.stream));
+        POST_HIP(hipMemcpyAsync(dyn_curves.dev + (size_t)bus * S2R_DYN_CURVE_POINTS, curve, S2R_DYN_CURVE_POINTS * sizeof(float), hipMemcpyHostToDevice, c.stream));
         POST_HIP(hipStreamSynchronize(c.stream));
         d.key = key; d.a_att = a_att; d.a_rel = a_rel;
         d.curve.assign(curve, curve + S2R_DYN_CURVE_POINTS);
         return hipSuccess;
     }
-    if (!dyn_curves) POST_HIP(hipMalloc((void **)&dyn_curves, (size_t)S2R_MAX_BUSES * S2R_DYN_CURVE_POINTS * sizeof(float)));
-    POST_HIP(pinned_rows(dyn_meter, dyn_meter_dev, S2R_MAX_BUSES));
+    POST_HIP(dyn_curves.reserve((size_t)S2R_MAX_BUSES * S2R_DYN_CURVE_POINTS));
+    POST_HIP(dyn_meter.reserve(S2R_MAX_BUSES));
     BusDyn f;
     f.key = key; f.a_att = a_att; f.a_rel = a_rel; f.history = 1u;
     f.curve.assign(curve, curve + S2R_DYN_CURVE_POINTS);
-    float *const to = dyn_curves + (size_t)bus * S2R_DYN_CURVE_POINTS;
+    float *const to = dyn_curves.dev + (size_t)bus * S2R_DYN_CURVE_POINTS;
     return replace(c, stage[S2R_BUS_DYN].buffer, dyn[bus], f, 1u, [&](BusDyn &n) {          // y = curve[0], the gain at silence
         POST_HIP(hipMemcpyAsync(n.line[0], n.curve.data(), sizeof(float), hipMemcpyHostToDevice, c.stream));
         return hipMemcpyAsync(to, n.curve.data(), S2R_DYN_CURVE_POINTS * sizeof(float), hipMemcpyHostToDevice, c.stream);
@@ -536,18 +519,18 @@ hipError_t S2rPostChain::set_drive(const S2rPostCtx &c, uint32_t bus, const floa
     if (keep_state) {
         BusDrive &d = drive[bus];
         if (curve) {
-            POST_HIP(hipMemcpyAsync(drive_curves + bus * kRow, curve, kRow * sizeof(float), hipMemcpyHostToDevice, c.stream));
+            POST_HIP(hipMemcpyAsync(drive_curves.dev + bus * kRow, curve, kRow * sizeof(float), hipMemcpyHostToDevice, c.stream));
             POST_HIP(hipStreamSynchronize(c.stream));
             d.curve.assign(curve, curve + kRow);
         }
         d.pre = pre; d.dry = dry; d.wet = wet;
         return hipSuccess;
     }
-    if (!drive_curves) POST_HIP(hipMalloc((void **)&drive_curves, (size_t)S2R_MAX_BUSES * kRow * sizeof(float)));
+    POST_HIP(drive_curves.reserve((size_t)S2R_MAX_BUSES * kRow));
     BusDrive f;
     f.pre = pre; f.dry = dry; f.wet = wet; f.history = S2R_DRIVE_HISTORY;
     f.curve.assign(curve, curve + kRow);
-    float *const to = drive_curves + bus * kRow;
+    float *const to = drive_curves.dev + bus * kRow;
     return replace(c, stage[S2R_BUS_DRIVE].buffer, drive[bus], f, 2u * (size_t)S2R_DRIVE_HISTORY, [&](BusDrive &n) {
         return hipMemcpyAsync(to, n.curve.data(), kRow * sizeof(float), hipMemcpyHostToDevice, c.stream);
     });
@@ -667,7 +650,7 @@ void S2rPostChain::set_limiter_state(const float *xh, const float *gh) {
 void S2rPostChain::set_multiband(uint32_t n_bands, const float *lp, const float *hp, const float *ap, const float *curves, const float *a_att, const float *a_rel,
                                  bool keep_state) {
     Multiband &f = mb;
-    f.curves_valid = false;
+    f.curves_dev.valid = false;
     if (!n_bands) { f.n_bands = 0; f.curves.clear(); f.state.off(); f.metered = false; return; }
     f.n_bands = n_bands;
     if (n_bands >= 2u) { std::memcpy(f.lp, lp, (size_t)(n_bands - 1u) * 5u * sizeof(float)); std::memcpy(f.hp, hp, (size_t)(n_bands - 1u) * 5u * sizeof(float)); }
@@ -705,7 +688,7 @@ void S2rPostChain::reset_loudness() {
 
 void S2rPostChain::set_spectrum(uint32_t n_fft, uint32_t hop, const float *window, uint32_t max_rows) {
     Spectrum &sp = spec;
-    sp.tables_valid = false;
+    sp.tables.valid = false;
     if (!window) { sp.n_fft = sp.hop = 0; sp.window.clear(); sp.twiddles.clear(); }
     else {
         sp.n_fft = n_fft; sp.hop = hop;
@@ -751,7 +734,7 @@ void S2rPostChain::set_resampler(uint32_t L, uint32_t M, uint32_t T, const float
     rs.L = table ? L : 0u; rs.M = table ? M : 0u; rs.T = table ? T : 0u;
     if (table) rs.table.assign(table, table + (size_t)L * T);
     else rs.table.clear();
-    rs.table_valid = false;
+    rs.table_dev.valid = false;
     if (table) reset_resampler();
     else { rs.state.off(); rs.ph = 0; rs.have = false; rs.count = 0; }
 }

@@ -1,10 +1,13 @@
 // s2r_post.h — the chain behind the bus mixdown of s2r_fill_buses and s2r_fill_master: the eight bus stages in the order of
 // S2rBusStage (s2r_post_route.h) — the buses' equalisers, their dynamics (4.22), drives (4.24), flangers (4.25),
 // choruses (4.20), feedback delays (4.19), convolution reverbs (4.16) and rooms (4.23) —, then the master section (4.17), the master's multiband compressor (4.31) and the master
-// limiter (4.18), and behind it the loudness and true-peak meters (4.26), the spectrum meters (4.27), the sample-rate converter (4.29) and the PCM stage (4.28).  The bus stages keep their
-// histories in a S2rBusLine each; the stages behind the master fader keep their state in a S2rMirror each, and the two meters
-// their rows in a S2rRowStore each (s2r_post_keep.h).  The chain owns what these stages own and knows nothing of the handle: its
-// functions take a S2rPostCtx and return the HIP error.  Per call: prepare, launch, — the caller's synchronise — commit, read_timers.
+// limiter (4.18), and behind it the loudness and true-peak meters (4.26), the spectrum meters (4.27), the sample-rate converter (4.29) and the PCM stage (4.28) — the seven master
+// stages, in the order of S2rMasterStage.  The bus stages keep their histories in a S2rBusLine each; the stages behind the master
+// fader keep their state in a S2rMirror each, and the two meters their rows in a S2rRowStore each (s2r_post_keep.h); what else a
+// master stage holds on the device is a S2rDevBuf or a S2rDevTable, what it shares with the host a S2rPinned.  The chain owns what
+// these stages own and knows nothing of the handle: its functions take a S2rPostCtx and return the HIP error.  Per call: prepare —
+// which alone decides what runs (call.on, call.run) and, through s2r_post_route, who reads and writes what —, launch — a walk over
+// the two stage lists —, the caller's synchronise, commit, read_timers.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <vector>
@@ -60,6 +63,31 @@ struct S2rMirror : S2rMirrorHost {
     void free() { for (float *&p : dev) if (p) { (void)hipFree(p); p = nullptr; } floats = 0; }
 };
 
+// Device memory that a fill reserves: at least n floats, allocated by the first that asks and regrown — what it held is gone then —
+// by one that asks for more.
+struct S2rDevBuf {
+    float *dev = nullptr;
+    size_t floats = 0;
+    hipError_t reserve(size_t n);
+    void free() { if (dev) (void)hipFree(dev); dev = nullptr; floats = 0; }
+};
+// ... that holds a table of the host's, good while `valid`: never after a regrowth or a set, from the commit of a fill that sent it on
+struct S2rDevTable : S2rDevBuf {
+    bool valid = false;
+    hipError_t reserve(size_t n) { if (n > floats) valid = false; return S2rDevBuf::reserve(n); }
+    hipError_t send(const std::vector<float> &host, size_t at, hipStream_t stream) const;       // to dev + at; nothing while valid
+    void committed() { valid = true; }
+};
+// Pinned memory that the device sees at `dev` and the host reads behind a synchronise: at least n of T, grown as a S2rDevBuf is.
+// `host` survives a failed hipHostGetDevicePointer, and the next call goes on from there.
+template <class T> struct S2rPinned {
+    T *host = nullptr, *dev = nullptr;
+    size_t count = 0;
+    bool grows(size_t n) const { return n > count; }             // reserve(n) would drop what it holds
+    hipError_t reserve(size_t n);
+    void free() { if (host) (void)hipHostFree(host); host = dev = nullptr; count = 0; }
+};
+
 struct S2rPostChain {
     // what a bus stage keeps beside its buses' effects
     struct Stem {
@@ -80,15 +108,15 @@ struct S2rPostChain {
         float min_gain = 1.0f;                   // the meter of the last successful call that ran these dynamics
         std::vector<float> curve;                // the host's copy of the table: S2R_DYN_CURVE_POINTS entries
     } dyn[S2R_MAX_BUSES];
-    float *dyn_curves = nullptr;                 // [S2R_MAX_BUSES][S2R_DYN_CURVE_POINTS] in device memory, allocated when dynamics are first set
-    float *dyn_meter = nullptr, *dyn_meter_dev = nullptr;        // pinned and device-mapped: [S2R_MAX_BUSES]
+    S2rDevBuf dyn_curves;                        // [S2R_MAX_BUSES][S2R_DYN_CURVE_POINTS], allocated when dynamics are first set
+    S2rPinned<float> dyn_meter;                  // [S2R_MAX_BUSES]
     // The drives (s2r_set_bus_drive): lines of [S2R_DRIVE_HISTORY][2], the bus's last input frames, oldest first, L then R; beside them
     // the tables on the device
     struct BusDrive : S2rBusLine {
         float pre = 0.0f, dry = 0.0f, wet = 0.0f;
         std::vector<float> curve;                // the host's copy of the table: S2R_DRIVE_CURVE_POINTS entries
     } drive[S2R_MAX_BUSES];
-    float *drive_curves = nullptr;               // [S2R_MAX_BUSES][S2R_DRIVE_CURVE_POINTS] in device memory, allocated when a drive is first set
+    S2rDevBuf drive_curves;                      // [S2R_MAX_BUSES][S2R_DRIVE_CURVE_POINTS], allocated when a drive is first set
     // The flangers (s2r_set_bus_flanger): lines of [H][2], the last frames of the stage's line signal w, oldest first, L then R, H =
     // history = floor(fl(base + depth)) + 1
     struct BusFlanger : S2rBusLine {
@@ -134,16 +162,18 @@ struct S2rPostChain {
     // the bus's effect of stage k runs in a call of n_buses buses: the bus is among them (an effect on a bus past the call's is idle in
     // it), and for the dynamics their key bus too
     bool runs(int k, uint32_t b, uint32_t n_buses) const { return b < n_buses && bus(k, b).present() && (k != S2R_BUS_DYN || dyn[b].key < n_buses); }
+    // The master stages.  Each one's timer, by S2rMasterStage: around its kernel in the last master fill, 0 when that ran none
+    // (tools/master_time.py, limiter_time.py, loudness_time.py, spectrum_time.py, pcm_time.py, resampler_time.py, multiband_time.py)
+    S2rPostTimer master_timer[S2R_MASTER_STAGES];
     // The master section.  Nothing is allocated before the first master fill.
     struct Master {
         float ret[S2R_MAX_BUSES], ret_app[S2R_MAX_BUSES];        // what the caller last set — the target — and what the last master fill left — the applied
         float fader = 1.0f, fader_app = 1.0f;
-        float *stage = nullptr;                  // [S2R_MAX_BUSES][2 * max_frames] in device memory: where the last stem writer of a master fill writes
-        float *partials = nullptr, *partials_dev = nullptr;      // pinned and device-mapped: [ceil(max_frames / S2R_METER_BLOCK)][S2R_MASTER_ROW]
+        S2rDevBuf stage;                         // [S2R_MAX_BUSES][2 * max_frames]: where the last stem writer of a master fill writes
+        S2rPinned<float> partials;               // [ceil(max_frames / S2R_METER_BLOCK)][S2R_MASTER_ROW]
         bool metered = false;                    // a master fill has succeeded: the meters below are its
         uint32_t meter_buses = 0;
         float peak[S2R_MASTER_CH], energy[S2R_MASTER_CH];
-        S2rPostTimer timer;                         // around the master kernel of the last master fill (tools/master_time.py)
         Master() { for (uint32_t b = 0; b < S2R_MAX_BUSES; b++) ret[b] = ret_app[b] = 1.0f; }
     } master;
     // The master limiter.  Nothing is allocated before the first master fill that finds it set.
@@ -154,11 +184,10 @@ struct S2rPostChain {
         // xh [lookahead][2] ([lookahead + 16][2] with the true-peak detector), then gh [2 * lookahead + hold], on the host and on the
         // device alike: n_x() + n_g() floats, in copies sized for the largest lookahead and hold
         S2rMirror state;
-        float *in = nullptr;                     // [2 * max_frames] in device memory: where the master kernel writes when the limiter is on
-        float *partials = nullptr, *partials_dev = nullptr;      // pinned and device-mapped: [ceil(max_frames / S2R_LIMITER_BLOCK)][2]
+        S2rDevBuf in;                            // [2 * max_frames]: where the writer in front writes when the limiter is on
+        S2rPinned<float> partials;               // [ceil(max_frames / S2R_LIMITER_BLOCK)][2]
         bool metered = false;                    // a master fill has run the limiter: the meters below are its
         float min_gain = 1.0f, out_peak = 0.0f;
-        S2rPostTimer timer;                         // around the limiter kernel of the last master fill: 0 when it ran none (tools/limiter_time.py)
         size_t n_x() const { return 2u * ((size_t)lookahead + (detector == S2R_LIMITER_TRUE_PEAK ? S2R_LIMITER_TP_HISTORY : 0u)); }
         size_t n_g() const { return 2u * (size_t)lookahead + hold; }
     } limiter;
@@ -169,28 +198,23 @@ struct S2rPostChain {
         uint32_t hop = 0;                        // 0: off
         S2rMirror state;                         // S2R_LOUDNESS_STATE floats
         uint32_t pos = 0;                        // the frames of the hop under way: the host's alone, and a kernel argument
-        float *in = nullptr;                     // [2 * max_frames] in device memory: where the master's last writer writes when the meter is on
-        float *rows = nullptr, *rows_dev = nullptr;              // pinned and device-mapped: [max_frames / 16 + 1][S2R_LOUDNESS_CHANNELS]
-        float *peaks = nullptr, *peaks_dev = nullptr;            // pinned and device-mapped: [ceil(max_frames / S2R_LOUDNESS_BLOCK)][2]
+        S2rDevBuf in;                            // [2 * max_frames]: the tail's input, where the master's last writer writes when any of the four readers is on
+        S2rPinned<float> rows;                   // [max_frames / 16 + 1][S2R_LOUDNESS_CHANNELS]
+        S2rPinned<float> peaks;                  // [ceil(max_frames / S2R_LOUDNESS_BLOCK)][2]
         S2rRowStore kept;                        // the hop rows kept: S2R_LOUDNESS_CHANNELS floats each, at most max_hops of them
         float tp_last[2] = {0.0f, 0.0f}, tp_held[2] = {0.0f, 0.0f};
-        S2rPostTimer timer;                      // around the loudness kernel of the last master fill: 0 when it ran none (tools/loudness_time.py)
     } loud;
     // The spectrum meters (s2r_set_master_spectrum), behind the loudness meters.  As theirs: nothing is allocated before
     // the first master fill that finds the meter set — and what is allocated then is sized by n_fft and hop, and grown by a later fill
     // that finds them larger —, and a handle on which it never was set makes the launches it always did.
     struct Spectrum {
         uint32_t n_fft = 0, hop = 0;             // both 0: off
-        std::vector<float> window, twiddles;     // [n_fft] and [n_fft / 2][2], the host's; the device's copy is good while tables_valid
-        bool tables_valid = false;
+        std::vector<float> window, twiddles;     // [n_fft] and [n_fft / 2][2], the host's
         S2rMirror state;                         // S2R_SPECTRUM_STATE(n_fft) floats
         uint32_t pos = 0;                        // the frames of the hop under way: the host's alone, and a kernel argument
-        float *tables = nullptr;                 // device memory: window [n_fft], then twiddles [n_fft / 2][2]; tables_floats in all
-        size_t tables_floats = 0;
-        float *rows = nullptr, *rows_dev = nullptr;              // pinned and device-mapped: [max_frames / hop + 1][9][n_fft / 2 + 1], rows_floats
-        size_t rows_floats = 0;
+        S2rDevTable tables;                      // window [n_fft], then twiddles [n_fft / 2][2]
+        S2rPinned<float> rows;                   // [max_frames / hop + 1][9][n_fft / 2 + 1]
         S2rRowStore kept;                        // the rows kept: S2R_SPECTRUM_ROW(n_fft) floats each, at most max_rows of them
-        S2rPostTimer timer;                      // around the spectrum kernel of the last master fill: 0 when it ran none (tools/spectrum_time.py)
     } spec;
     // The PCM stage (s2r_set_master_pcm), behind the spectrum meters, the last of a master fill.  As theirs: nothing is
     // allocated before the first master fill that finds the stage set, and a handle on which it never was set makes the launches it
@@ -200,60 +224,46 @@ struct S2rPostChain {
         float h[S2R_PCM_MAX_TAPS] = {};          // +0.0 past n_taps
         S2rMirror state;                         // S2R_PCM_STATE floats
         uint32_t t = 0;                          // the frames converted since the set or reset, mod 2^32: the host's alone, and a kernel argument
-        int32_t *samples = nullptr, *samples_dev = nullptr;      // pinned and device-mapped: [9][cap][2]
-        uint32_t cap = 0;                        // max_frames, or the resampler's S2R_RESAMPLER_MAX_OUT when a fill found that set: grown, never shrunk
+        S2rPinned<int32_t> samples;              // [9][cap()][2]
+        // max_frames, or the resampler's S2R_RESAMPLER_MAX_OUT when a fill found that set: grown, never shrunk
+        uint32_t cap() const { return (uint32_t)(samples.count / (2u * S2R_PCM_PROGRAMMES)); }
         bool have = false;                       // a master fill has run the stage since the set or reset: `frames` (0 with the resampler in front) is its
-        uint32_t *counts = nullptr, *counts_dev = nullptr;       // pinned and device-mapped: [S2R_PCM_CHANNELS], the call's clips
+        S2rPinned<uint32_t> counts;              // [S2R_PCM_CHANNELS], the call's clips
         uint32_t frames = 0;                     // the frames of the last successful fill that ran the stage
         uint32_t clips_last[S2R_PCM_CHANNELS] = {}, clips_held[S2R_PCM_CHANNELS] = {};
-        S2rPostTimer timer;                      // around the PCM kernel of the last master fill: 0 when it ran none (tools/pcm_time.py)
     } pcm;
     // The sample-rate converter (s2r_set_master_resampler), behind the spectrum meters and in front of the PCM stage.  As
     // theirs: nothing is allocated before the first master fill that finds the stage set — and what is allocated then is sized by L, M
     // and T, and grown by a later fill that finds them larger —, and a handle on which it never was set makes the launches it always did.
     struct Resampler {
         uint32_t L = 0, M = 0, T = 0;            // L 0: off
-        std::vector<float> table;                // [L][T], the host's; the device's copy is good while table_valid
-        bool table_valid = false;
-        float *table_dev = nullptr;              // device memory, table_floats
-        size_t table_floats = 0;
+        std::vector<float> table;                // [L][T], the host's
+        S2rDevTable table_dev;
         S2rMirror state;                         // S2R_RESAMPLER_STATE(T) floats
         uint32_t ph = 0;                         // the next output's position in 1 / L input frames: the host's alone, and a kernel argument
-        float *res = nullptr, *res_map = nullptr;                // pinned and device-mapped: [9][cap][2], the call's outputs
-        float *res_dev = nullptr;                // device memory, [9][cap][2]: the PCM kernel's input, allocated when a fill finds both stages set
-        uint32_t cap = 0, dev_cap = 0;           // S2R_RESAMPLER_MAX_OUT(max_frames, L, M) when they were allocated
+        S2rPinned<float> res;                    // [9][cap()][2], the call's outputs
+        S2rDevBuf res_dev;                       // as much: the PCM kernel's input, allocated when a fill finds both stages set
+        uint32_t cap() const { return (uint32_t)(res.count / (2u * S2R_RESAMPLER_PROGRAMMES)); }        // S2R_RESAMPLER_MAX_OUT(max_frames, L, M) when it was allocated
         uint32_t call_count = 0;                 // the output frames of the call under way (prepare)
         bool have = false;                       // a master fill has run the stage since the set or reset: `count` is its
         uint32_t count = 0;
-        S2rPostTimer timer;                      // around the resampler kernel of the last master fill: 0 when it ran none (tools/resampler_time.py)
     } res;
     // The master's multiband compressor (s2r_set_master_multiband), behind the master kernel and in front of the limiter.
     // As the stages above: nothing is allocated before the first master fill that finds the stage set, and a handle on which it never was
-    // set makes the launches it always did.  In a call that runs it the master kernel writes `in` instead of route.master_out, and the
-    // stage's kernel writes there in its place: the route itself (s2r_post_route.h) knows nothing of the stage.
+    // set makes the launches it always did.  A writer of the route (s2r_post_route.h) as the limiter is: in a call that runs it the
+    // master kernel writes `in`, and the stage's kernel writes where that would have.
     struct Multiband {
         uint32_t n_bands = 0;                    // B; 0: off
         float lp[S2R_MULTIBAND_MAX_BANDS - 1u][5] = {}, hp[S2R_MULTIBAND_MAX_BANDS - 1u][5] = {}, ap[S2R_MULTIBAND_MAX_BANDS - 2u][5] = {};
         float a_att[S2R_MULTIBAND_MAX_BANDS] = {}, a_rel[S2R_MULTIBAND_MAX_BANDS] = {};
-        std::vector<float> curves;               // the host's copy of the tables: [B][S2R_DYN_CURVE_POINTS]; the device's is good while curves_valid
-        bool curves_valid = false;
-        float *curves_dev = nullptr;             // [S2R_MULTIBAND_MAX_BANDS][S2R_DYN_CURVE_POINTS] in device memory
+        std::vector<float> curves;               // the host's copy of the tables: [B][S2R_DYN_CURVE_POINTS]
+        S2rDevTable curves_dev;                  // [S2R_MULTIBAND_MAX_BANDS][S2R_DYN_CURVE_POINTS]
         S2rMirror state;                         // S2R_MULTIBAND_STATE(B) floats, in copies sized for four bands
-        float *in = nullptr;                     // [2 * max_frames] in device memory: where the master kernel writes when the stage is on
-        float *meter = nullptr, *meter_dev = nullptr;            // pinned and device-mapped: [S2R_MULTIBAND_MAX_BANDS], the call's minima
+        S2rDevBuf in;                            // [2 * max_frames]: where the master kernel writes when the stage is on
+        S2rPinned<float> meter;                  // [S2R_MULTIBAND_MAX_BANDS], the call's minima
         bool metered = false;                    // a master fill has run the stage since the set or reset: the minima below are its
         float min_gain[S2R_MULTIBAND_MAX_BANDS] = {1.0f, 1.0f, 1.0f, 1.0f};
-        S2rPostTimer timer;                      // around the stage's kernel of the last master fill: 0 when it ran none (tools/multiband_time.py)
     } mb;
-    bool mb_on(const S2rPostCall &call) const { return call.master && mb.n_bands != 0; }
-    bool loud_on(const S2rPostCall &call) const { return call.master && loud.hop != 0; }
-    bool spec_on(const S2rPostCall &call) const { return call.master && spec.n_fft != 0; }
-    bool res_on(const S2rPostCall &call) const { return call.master && res.L != 0; }
-    bool pcm_on(const S2rPostCall &call) const { return call.master && pcm.bits != 0; }
-    // the PCM kernel runs in the call: behind the resampler only when that makes a frame
-    bool pcm_runs(const S2rPostCall &call) const { return pcm_on(call) && (!res_on(call) || res.call_count != 0); }
-    // a stage behind the master: whoever writes the master last writes it to device memory (loud.in), and the first kernel behind it copies it out
-    bool metered(const S2rPostCall &call) const { return loud_on(call) || spec_on(call) || res_on(call) || pcm_on(call); }
     // one fill: what it runs, its once-only allocations and its route; the launches in order, each between its timer's marks; after
     // the synchronise that succeeded, and only then, histories, applied values and state move on and the meters fold
     hipError_t prepare(const S2rPostCtx &c, uint32_t n_buses, uint32_t frames, bool master_fill, bool stems, S2rPostCall &call);
@@ -267,6 +277,15 @@ struct S2rPostChain {
     hipError_t launch_delay(const S2rPostCtx &c, const S2rPostCall &call) const;
     hipError_t launch_reverb(const S2rPostCtx &c, const S2rPostCall &call) const;
     hipError_t launch_room(const S2rPostCtx &c, const S2rPostCall &call) const;
+    // a master stage's part: what is still to be sent to the device — tables, a state set on the host —, the kernel's arguments from
+    // route.writer or route.reader, and the launch
+    hipError_t launch_master(const S2rPostCtx &c, const S2rPostCall &call) const;
+    hipError_t launch_multiband(const S2rPostCtx &c, const S2rPostCall &call) const;
+    hipError_t launch_limiter(const S2rPostCtx &c, const S2rPostCall &call) const;
+    hipError_t launch_loudness(const S2rPostCtx &c, const S2rPostCall &call) const;
+    hipError_t launch_spectrum(const S2rPostCtx &c, const S2rPostCall &call) const;
+    hipError_t launch_resampler(const S2rPostCtx &c, const S2rPostCall &call) const;
+    hipError_t launch_pcm(const S2rPostCtx &c, const S2rPostCall &call) const;
     void commit(const S2rPostCall &call);
     hipError_t read_timers(const S2rPostCall &call);
     void release();

@@ -31,11 +31,15 @@ def test_rule_functions_under_asan_ubsan(tmp_path):
 @pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
 def test_post_route_under_asan_ubsan(tmp_path):
     """who reads and writes what behind the bus mixdown (s2r_post_route, csrc/s2r_post_route.h, a header without HIP): a panned call,
-    bus fills x the 256 subsets of running bus stages, master fills x 256 subsets x limiter on or off x stems wanted or not, each route
-    against the 24 routes written out by hand (the table of tests/native/post_route.cpp) where it names the call, against the rule
-    walked in launch order without it — every buffer is written before it is read, the combine writes first, the last writer hits
-    the call's destination, no kernel reads a pinned output — and against the route of the same call with one more stage on, which
-    differs by exactly the pointer that stage takes over"""
+    bus fills x the 256 subsets of running bus stages, master fills x 256 subsets x the 64 subsets of {multiband, limiter, loudness,
+    spectrum, resampler, PCM} set (and the PCM stage idle behind a resampler that makes no frame) x stems wanted or not, each route
+    against the 24 routes of the bus stages and the 12 of the master stages written out by hand (the tables of
+    tests/native/post_route.cpp) where they name the call, against the rule walked in launch order without them — every buffer is
+    written once before it is read, the combine writes first, the last writer hits the call's destination, no kernel reads a pinned
+    output, exactly one stage writes the pinned master in a master fill, every reader reads what the last writer wrote, a stage that
+    does not run has null pointers — and against the route of the same call with one more stage on: a bus stage or a master writer
+    takes over exactly one pointer, a master reader moves at most the copy-out pointer and, if it is the only one, the last writer's
+    destination"""
     exe = str(tmp_path / "post_route")
     subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
                            "-I", os.path.join(ROOT, "synth2_amd", "csrc"), os.path.join(ROOT, "tests", "native", "post_route.cpp"), "-o", exe])
